@@ -252,6 +252,62 @@ def alt_c5(Handle, device, steps=10, warmup=10):
     return out
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6     # --dump-outputs: at most this much in all
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, h, coupled, dim, n_global, part, dist, rank, world):
+    """--dump-outputs DIR: what the timed path computed in its last step, i.e. what a caller of glims_step (and, on the
+    coupled configs, glims_solve_mechanics) receives from glims_get_state: DIR/concentration.npy [N] and, coupled,
+    DIR/displacement.npy [N, dim], float64, in global node order whatever the rank count.  When the full arrays exceed the
+    budget, the same fixed sample of nodes (seed DUMP_SEED, ascending node ids) is taken from every array, and its node ids
+    go to DIR/sample_node_ids.npy (float64, exact integers): identical for every run with the same arguments."""
+    c, u = h.get_state(want_u=coupled)
+    cols = 1 + (dim if coupled else 0)
+    headers = 4096
+    ids = None
+    if n_global * cols * 8 + headers > DUMP_BUDGET_BYTES:
+        m = (DUMP_BUDGET_BYTES - headers) // (8 * (cols + 1))
+        ids = np.sort(np.random.default_rng(DUMP_SEED).choice(n_global, m, replace=False))
+    if part is None:
+        own = np.arange(n_global, dtype=np.int64)
+        n_own = n_global
+    else:
+        own = np.asarray(part.global_ids[:part.n_own], dtype=np.int64)
+        n_own = part.n_own
+    cv = c[:n_own]
+    uv = u[:n_own * dim].reshape(n_own, dim) if coupled else None
+    if ids is not None:
+        keep = np.isin(own, ids)
+        own, cv, uv = own[keep], cv[keep], (uv[keep] if coupled else None)
+    pieces = [(own, cv, uv)]
+    if world > 1:
+        pieces = [None] * world
+        dist.all_gather_object(pieces, (own, cv, uv))
+    if rank != 0:
+        return
+    n_out = n_global if ids is None else len(ids)
+    conc = np.full(n_out, np.nan)
+    disp = np.full((n_out, dim), np.nan) if coupled else None
+    for g, cp, up in pieces:
+        pos = g if ids is None else np.searchsorted(ids, g)
+        conc[pos] = cp
+        if coupled:
+            disp[pos] = up
+    assert not np.isnan(conc).any(), "dump: nodes without an owner"
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"concentration": conc}
+    if coupled:
+        arrays["displacement"] = disp
+    if ids is not None:
+        arrays["sample_node_ids"] = ids.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    log("[bench] outputs of the last timed step -> %s: %s (%s)" %
+        (out_dir, ", ".join("%s%s" % (k, list(v.shape)) for k, v in arrays.items()),
+         "all %d nodes" % n_global if ids is None else "fixed sample of %d of %d nodes, seed %d" % (len(ids), n_global, DUMP_SEED)))
+
+
 def cheb_bytes(nnz, n_rows):
     """Algorithmic bytes of one pass of the dot-free Krylov iteration (k_cheb): the CSR SpMV's 12 nnz + 4 rows + 8 rows of
     gathered iterate, plus the recurrence's vector work: right-hand side, Dinv, direction read + written, new iterate
@@ -457,6 +513,8 @@ def main():
     ap.add_argument("--full-newton", type=int, default=0,
                     help="1: GLIMS_FLAG_FULL_NEWTON, a sweep after every linear solve (A/B against the default, which takes "
                          "the residual after a solve from the quadratic structure)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state they computed as DIR/<name>.npy (float64, <= 64 MB in all)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -627,6 +685,8 @@ def main():
         elapsed = float(tt.item())
     st = h.stats()
     steps_done = int(st['steps'] - steps_before)      # < K only if the solver gave up (status != 0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, h, coupled, dim, n_global, part, dist, rank, world)
     # the other two hot kernels (assembly sweep, PCG vector update): event pairs around every launch of theirs cost
     # ~0.1 ms per step at 1 M rows, so they are timed in a short pass of their own right after the timed region
     st_k = None
