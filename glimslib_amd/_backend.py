@@ -84,6 +84,14 @@ class Stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+MISFIT_C_L2, MISFIT_C_THRESH, MISFIT_U_L2 = 0, 1, 2
+
+
+class Misfit(C.Structure):
+    _fields_ = [("step", C.c_int64), ("kind", C.c_int), ("level", C.c_double), ("smooth", C.c_double),
+                ("weight", C.c_double), ("target", C.POINTER(C.c_double))]
+
+
 _dp = C.POINTER(C.c_double)
 _i32p = C.POINTER(C.c_int32)
 _i64p = C.POINTER(C.c_int64)
@@ -118,6 +126,9 @@ SIGNATURES = {
     "glims_snapshot_mechanics": (C.c_int, [_h, C.c_int64, _dp]),
     "glims_snapshot_clear": (C.c_int, [_h]),
     "glims_project": (C.c_int, [_h, _dp, _dp, C.c_int, C.c_double]),
+    "glims_adjoint_record": (C.c_int, [_h, C.c_int]),
+    "glims_adjoint_gradient": (C.c_int, [_h, C.c_int, C.POINTER(Misfit), _dp, _dp, _dp, _dp, _dp]),
+    "glims_adjoint_stats": (C.c_int, [_h, _i64p, _dp]),
     "glims_comm_unique_id": (C.c_int, [C.c_char_p]),
     "glims_comm_init": (C.c_int, [_h, C.c_int, C.c_int, C.c_char_p]),
     "glims_comm_selftest": (C.c_int, [_h]),
@@ -327,6 +338,42 @@ class Handle:
         x = np.empty_like(r)
         self._check(self.lib.glims_project(self._h, _ptr(r, _dp), _ptr(x, _dp), int(k), float(rtol)))
         return x.reshape(rhs.shape)
+
+    # -- discrete adjoint (glims_adjoint_*) -----------------------------------------------------------
+    def adjoint_record(self, on=True):
+        """on: clear the trajectory, keep the current state as c_0 and a device copy of c_n after every converged step."""
+        self._check(self.lib.glims_adjoint_record(self._h, 1 if on else 0))
+
+    def adjoint_gradient(self, terms, n_labels, want_dc0=True):
+        """terms: iterable of dicts {step, kind ('c_l2' | 'c_thresh' | 'u_l2' or MISFIT_*), target, weight=1, level=0,
+        smooth=1}; targets in the caller's node order ([n_nodes] or [n_nodes, dim]).
+        Returns (J, dJ/dD [n_labels], dJ/drho, dJ/dgamma, dJ/dc0 [n_nodes] or None)."""
+        kinds = {"c_l2": MISFIT_C_L2, "c_thresh": MISFIT_C_THRESH, "u_l2": MISFIT_U_L2}
+        terms = list(terms)
+        arr = (Misfit * max(1, len(terms)))()
+        keep = []
+        for k, t in enumerate(terms):
+            kind = kinds.get(t["kind"], t["kind"])
+            n = self.n_nodes * (self.dim if kind == MISFIT_U_L2 else 1)
+            tg = _f64(np.asarray(t["target"]).reshape(-1), (n,))
+            keep.append(tg)
+            arr[k] = Misfit(int(t["step"]), int(kind), float(t.get("level", 0.0)), float(t.get("smooth", 1.0)),
+                            float(t.get("weight", 1.0)), _ptr(tg, _dp))
+        J = C.c_double(0.0)
+        out = [np.zeros(int(n_labels)) for _ in range(3)]
+        dc0 = np.zeros(self.n_nodes) if want_dc0 else None
+        self._check(self.lib.glims_adjoint_gradient(self._h, len(terms), arr, C.byref(J), *[_ptr(a, _dp) for a in out],
+                                                    _ptr(dc0, _dp)))
+        return (J.value, out[0], out[1], out[2], dc0)
+
+    def adjoint_stats(self):
+        a = np.zeros(6, dtype=np.int64)
+        ms = C.c_double(0.0)
+        self._check(self.lib.glims_adjoint_stats(self._h, _ptr(a, _i64p), C.byref(ms)))
+        keys = ("gradients", "backward_steps", "pcg_its", "mech_solves", "mech_its", "recorded_states")
+        d = {k: int(v) for k, v in zip(keys, a)}
+        d["ms_backward"] = ms.value
+        return d
 
     # -- multi-GPU -------------------------------------------------------------------------------
     @staticmethod

@@ -345,6 +345,8 @@ int glims_set_materials(glims_ctx* h, int n_labels, const double* D, const doubl
     }
     h->mat.upload(m, h->st);
     GL_HIP(hipStreamSynchronize(h->st));
+    h->n_labels = n_labels;
+    h->adj.invalidate("glims_set_materials after recording started");
     h->have_materials = true;
     h->is_setup = false;
     h->pending = false;
@@ -398,6 +400,8 @@ int glims_set_dirichlet_c(glims_ctx* h, int64_t n, const int64_t* node_ids, cons
     h->dirichlet_c_exchange = h->world > 1;
     if (n <= 0) {
       if (h->have_fixed_c) h->mg_rd.ready = false;   // the RD hierarchy eliminates the constrained nodes
+      if (h->adj.recording && h->adj.had_fixed)
+        h->adj.invalidate("the Dirichlet node set of the concentration changed while recording");
       h->have_fixed_c = false;
       h->fixed_c_host.clear();
       h->dirichlet_c_dirty = false;
@@ -413,6 +417,8 @@ int glims_set_dirichlet_c(glims_ctx* h, int64_t n, const int64_t* node_ids, cons
       val[h->old2new[node_ids[k]]] = values[k];
     }
     if (fx != h->fixed_c_host) h->mg_rd.ready = false;   // new VALUES every step are the normal case: no rebuild for those
+    if (h->adj.recording && (!h->adj.had_fixed || fx != h->adj.fixed0))
+      h->adj.invalidate("the Dirichlet node set of the concentration changed while recording");
     h->fixed_c_host = fx;
     h->fixed_c.upload(fx, h->st);
     h->fixed_c_val.upload(val, h->st);
@@ -488,6 +494,7 @@ int glims_setup(glims_ctx* h, int with_mechanics) {
     for (int& hint : h->cg_hint) hint = 0;
     h->mech_hint = 0;
     GL_REQUIRE(h->have_materials, "glims_setup before glims_set_materials");
+    h->adj.invalidate("glims_setup after recording started");
     if (with_mechanics) {
       const size_t nd = (size_t)h->n_nodes * h->dim;
       if (!h->U.p) {
@@ -561,6 +568,7 @@ int glims_set_state(glims_ctx* h, const double* c, const double* u) {
     GL_HIP(hipStreamSynchronize(h->st));
     h->have_state = true;
     h->stats.steps = 0;
+    if (h->adj.recording) gl_adjoint_start(h);   // a new run: a new trajectory from this c_0
     return GLIMS_OK;
   });
 }
@@ -773,6 +781,38 @@ int glims_snapshot_clear(glims_ctx* h) {
     h->snapshots.clear();
     return GLIMS_OK;
   });
+}
+
+int glims_adjoint_record(glims_ctx* h, int on) {
+  return guarded(h, [&]() {
+    GL_REQUIRE(h->world <= 1, "glims_adjoint_record: partitioned handles are not supported (the adjoint is single-GPU for now)");
+    if (on) {
+      gl_adjoint_start(h);
+      GL_HIP(hipStreamSynchronize(h->st));
+    } else {
+      h->adj.recording = false;
+      h->adj.invalidate("recording was switched off");
+    }
+    return GLIMS_OK;
+  });
+}
+
+int glims_adjoint_gradient(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J, double* dJ_dD,
+                           double* dJ_drho, double* dJ_dgamma, double* dJ_dc0) {
+  return guarded(h, [&]() { return gl_adjoint_gradient(h, n_terms, terms, J, dJ_dD, dJ_drho, dJ_dgamma, dJ_dc0); });
+}
+
+int glims_adjoint_stats(const glims_ctx* h, int64_t out[6], double* ms) {
+  if (!h || !out) return GLIMS_E_USAGE;
+  const AdjointState& a = h->adj;
+  out[0] = a.gradients;
+  out[1] = a.steps;
+  out[2] = a.pcg_its;
+  out[3] = a.mech_solves;
+  out[4] = a.mech_its;
+  out[5] = (int64_t)a.traj.size();
+  if (ms) *ms = a.ms_backward;
+  return GLIMS_OK;
 }
 
 int glims_project(glims_ctx* h, const double* rhs, double* x, int ncomp, double rtol) {

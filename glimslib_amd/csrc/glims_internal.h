@@ -431,8 +431,33 @@ inline int gl_xrec_doubles(int bs, bool x32) { return x32 ? (bs == 3 ? 2 : 1) : 
 enum { SC_ALPHA = 0, SC_BETA, SC_GAMMA, SC_IT, SC_COUNT = 8 };
 #define GL_CG_HIST 64   // PCG iterations whose recurrence coefficients are recorded (Ritz values: spectral interval of the dot-free solves)
 
+// Recorded trajectory of the discrete adjoint (adjoint.hip, glims_adjoint_record / glims_adjoint_gradient)
+struct AdjointState {
+  bool recording = false;                  // gl_step appends c_n after every converged step
+  bool valid = false;                      // traj[0..] is a trajectory of the current operators
+  std::string why;                         // why it is not (message of GLIMS_E_USAGE)
+  std::vector<dvec<double>*> traj;         // c_0, c_1, ... (internal numbering), owned
+  bool had_fixed = false;                  // the concentration's Dirichlet node set when recording started
+  std::vector<uint8_t> fixed0;
+  dvec<int32_t> cell_nodes;                // [n_cells][nv]: internal node of every cell vertex (built by the first gradient)
+  int64_t gradients = 0, steps = 0, pcg_its = 0, mech_solves = 0, mech_its = 0;   // glims_adjoint_stats
+  double ms_backward = 0.0;
+  void clear() {
+    for (auto* d : traj) delete d;
+    traj.clear();
+  }
+  void invalidate(const char* m) {
+    if (!recording && traj.empty()) return;
+    clear();
+    valid = false;
+    why = m;
+  }
+  ~AdjointState() { clear(); }
+};
+
 struct glims_ctx {
   int dim = 0, nv = 0, device = 0;
+  int n_labels = 0;                        // of the last glims_set_materials
   int64_t n_nodes = 0, n_own = 0, n_cells = 0;
   hipStream_t st = nullptr, st_comm = nullptr;
   hipEvent_t ev_a = nullptr, ev_b = nullptr, ev_pack = nullptr, ev_halo = nullptr;
@@ -620,6 +645,8 @@ struct glims_ctx {
   glims_allreduce_fn tr_allreduce = nullptr;
   void* tr_user = nullptr;
 
+  AdjointState adj;
+
   std::string err;
 };
 
@@ -665,6 +692,17 @@ void gl_allreduce_bulk(glims_ctx* h, double* dev, size_t n);   // in-place sum o
 void gl_pair_of(glims_ctx* h, const double* u, float* ad /*[n_nodes][2]*/);   // (a, delta) = (u, u)
 void gl_apply_dirichlet_c(glims_ctx* h);                                     // c[fixed] = stored values (+ halo)
 void gl_block_dinv(glims_ctx* h);                                            // m_dinv of the constrained K_el
+
+// PCG with caller-owned vectors (the time stepper's work vectors stay untouched): on entry r = residual of x.  vals = scalar
+// operator plane (bs = 1, Jacobi `dinv`) or nullptr (K_el blocks, bs = dim, block-Jacobi `dinv`); mg: V-cycle instead
+int gl_pcg(glims_ctx* h, double* x, double* r, double* u, double* w, double* p, double* s, const double* dinv,
+           const double* vals, const uint8_t* fixed, int bs, MgHierarchy* mg, int mg_degree, double tol_abs, int maxit,
+           int64_t* its, double* res);
+// adjoint.hip ---------------------------------------------------------------------------------------
+void gl_adjoint_after_step(glims_ctx* h, int status);   // gl_step: record c_n of a converged step / invalidate
+void gl_adjoint_start(glims_ctx* h);                    // clear, store c_0 (the current state)
+int gl_adjoint_gradient(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J, double* dD, double* drho,
+                        double* dgamma, double* dc0);
 
 // mg.hip --------------------------------------------------------------------------------------------
 void gl_mesh_metrics(glims_ctx* h, const HostPattern& hp, const double* xyz_old);

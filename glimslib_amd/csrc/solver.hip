@@ -1180,6 +1180,15 @@ static int cg_solve(glims_ctx* h, const CgVecs& v, double tol_abs, int maxit, in
   return GLIMS_NOT_CONVERGED;
 }
 
+int gl_pcg(glims_ctx* h, double* x, double* r, double* u, double* w, double* p, double* s, const double* dinv,
+           const double* vals, const uint8_t* fixed, int bs, MgHierarchy* mg, int mg_degree, double tol_abs, int maxit,
+           int64_t* its, double* res) {
+  CgVecs v{x, r, u, w, p, s, dinv, vals, fixed, bs};
+  v.mg = mg;
+  v.mg_degree = mg_degree;
+  return cg_solve(h, v, tol_abs, maxit, 0, its, res);
+}
+
 // ---- the dot-free solve -------------------------------------------------------------------------------------------------
 // Safety factors on the chosen interval.  A lower end set too low only costs iterations (prototype: 0.5 x -> +50 %); an upper
 // end set too low makes the iteration diverge on what lies above it, so that end gets more room.
@@ -2168,6 +2177,7 @@ int gl_step(glims_ctx* h, int n_steps) {
     h->stats.last_newton_res = nr;
     if (status == GLIMS_OK) h->stats.steps++;
     else h->stats.failed_steps++;
+    if (h->adj.recording) gl_adjoint_after_step(h, status);   // D2D copy of c_n on the stream: no solver decision sees it
     // `auto` corrects its prediction by what the step just showed: Jacobi-PCG iterations per Newton solve above the
     // break-even -> the following steps use the hierarchy (the counts are global numbers: every rank switches together)
     if (status == GLIMS_OK && o.rd_precond == GLIMS_RD_PRECOND_AUTO && h->rd_precond_active == GLIMS_RD_PRECOND_JACOBI) {

@@ -1,0 +1,108 @@
+"""
+Parameter fitting on the device adjoint -- the counterpart of the reference's optimisation loop
+(optimization_workflow/image_based_optimization.py:660-767): a misfit J of the simulated fields, wrapped in
+``fenics.ReducedFunctional`` with the tissue parameters as controls (:700-708), handed with dJ/dm to scipy's L-BFGS-B
+(:710-722).
+
+Here J and dJ/dm come from one forward run with ``record_adjoint=True`` and one backward sweep on the GPU
+(``sim.adjoint_gradient``); there is no CPU gradient.  The controls follow the reference's forward entry
+points: ``TumorGrowthBrain.run_for_adjoint*`` (simulation_tumor_growth_brain_quad.py:127-210) with 2 / 3 / 4 / 5 parameters,
+``TumorGrowth.run_for_adjoint2`` / ``run_for_adjoint`` (simulation_tumor_growth.py:142-170) with 2 / 3.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+__all__ = ["ReducedFunctional", "minimize", "parameter_map"]
+
+BRAIN_NAMES = ("D_WM", "D_GM", "rho_WM", "rho_GM", "coupling")
+TUMOR_NAMES = ("diffusion", "proliferation", "coupling")
+
+
+def parameter_map(n_params, brain=True):
+    """
+    (names, P): the model parameters ``names`` are ``P @ m`` for the control vector m (linear maps of the reference:
+    2 parameters (D_WM, rho) with D_GM = 0.2 D_WM, rho_GM = rho_WM; 3: + coupling; 4: (D_WM, D_GM, rho, coupling);
+    5: all five).  Parameters not in ``names`` keep their values.
+    """
+    if brain:
+        P = {2: [[1, 0], [0.2, 0], [0, 1], [0, 1], [0, 0]],
+             3: [[1, 0, 0], [0.2, 0, 0], [0, 1, 0], [0, 1, 0], [0, 0, 1]],
+             4: [[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 1, 0], [0, 0, 1, 0], [0, 0, 0, 1]],
+             5: np.eye(5)}.get(int(n_params))
+        if P is None:
+            raise ValueError("TumorGrowthBrain controls: 2, 3, 4 or 5 parameters")
+        P = np.asarray(P, dtype=np.float64)
+        if n_params == 2:
+            return BRAIN_NAMES[:4], P[:4]   # the 2-parameter variant leaves the coupling alone
+        return BRAIN_NAMES, P
+    if int(n_params) not in (2, 3):
+        raise ValueError("TumorGrowth controls: 2 (diffusion, proliferation) or 3 (+ coupling) parameters")
+    return TUMOR_NAMES[:n_params], np.eye(int(n_params))
+
+
+class ReducedFunctional:
+    """
+    J(m) and dJ/dm(m) for a simulation ``sim`` (TumorGrowth / TumorGrowthBrain) and the controls of ``parameter_map``.
+
+    ``terms_builder(sim, n_steps)`` returns the misfit terms (see ``Handle.adjoint_gradient``) once the forward run of m has
+    taken ``n_steps`` steps.  The last m is cached: scipy's ``fun`` / ``jac`` pair for one m costs one forward and one
+    backward run.
+    """
+
+    def __init__(self, sim, n_params, terms_builder, run_kwargs=None):
+        self.sim = sim
+        self.n_params = int(n_params)
+        self.brain = hasattr(sim.params, "D_WM")
+        self.names, self.P = parameter_map(self.n_params, self.brain)
+        self.terms_builder = terms_builder
+        self.run_kwargs = dict(keep_nth=10 ** 9, save_method=None, clear_all=False, plot=False)
+        self.run_kwargs.update(run_kwargs or {})
+        self._m = None
+        self._J = None
+        self._dJ = None
+        self.evaluations = 0
+        self.history = []   # (m, J, |dJ/dm|) per evaluation (the reference's eval_cb_post / derivative_cb_post)
+
+    def _set_params(self, m):
+        q = self.P @ m
+        for name, v in zip(self.names, q):
+            setattr(self.sim.params, name, float(v))
+
+    def _model_gradient(self, g):
+        """dJ/d(names) from sim.adjoint_gradient's dict: per-label arrays sum over the labels (one scalar per name)."""
+        return np.array([float(np.sum(g[name])) for name in self.names])
+
+    def _evaluate(self, m):
+        m = np.array(m, dtype=np.float64).reshape(-1)
+        if m.shape != (self.n_params,):
+            raise ValueError("expected %d controls, got %s" % (self.n_params, m.shape))
+        if self._m is not None and np.array_equal(m, self._m):
+            return
+        self._set_params(m)
+        self.sim.run(record_adjoint=True, **self.run_kwargs)
+        n_steps = int(self.sim._backend.stats()["steps"])
+        g = self.sim.adjoint_gradient(self.terms_builder(self.sim, n_steps))
+        self._m, self._J = m, float(g["J"])
+        self._dJ = self.P.T @ self._model_gradient(g)
+        self.evaluations += 1
+        self.history.append((m.copy(), self._J, float(np.linalg.norm(self._dJ))))
+
+    def __call__(self, m):
+        self._evaluate(m)
+        return self._J
+
+    def derivative(self, m):
+        self._evaluate(m)
+        return self._dJ.copy()
+
+
+def minimize(rf, m0, bounds=(0.005, 0.5), method="L-BFGS-B", tol=1e-6, options=None):
+    """scipy.optimize.minimize on ``rf`` with ``jac=rf.derivative`` and the reference's defaults (bounds 0.005 .. 0.5 on
+    every control, L-BFGS-B, tol 1e-6, gtol 1e-6; image_based_optimization.py:710-722)."""
+    from scipy.optimize import minimize as _minimize
+    m0 = np.asarray(m0, dtype=np.float64)
+    opts = {"disp": False, "gtol": 1e-6}
+    opts.update(options or {})
+    bnds = [tuple(bounds)] * len(m0) if np.ndim(bounds[0]) == 0 else list(zip(*bounds))
+    return _minimize(rf, m0, jac=rf.derivative, bounds=bnds, method=method, tol=tol, options=opts)

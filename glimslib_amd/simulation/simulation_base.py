@@ -120,7 +120,7 @@ class FenicsSimulation(ABC):
 
     # -- run -----------------------------------------------------------------------------------------------
     def run(self, keep_nth=1, save_method='xdmf', clear_all=False, plot=True,
-            output_dir=config.output_dir_simulation_tmp, results_on_device=None):
+            output_dir=config.output_dir_simulation_tmp, results_on_device=None, record_adjoint=False):
         """
         simulation_base.py:236-317.  ``save_method``: None, 'vtk' (<field>/<field>_<step>.pvd + .vtu, the reference's
         layout) or 'xdmf' (solution.xdmf + solution.bin instead of solution.h5).
@@ -129,7 +129,11 @@ class FenicsSimulation(ABC):
         ``results_on_device`` (extension): keep the recorded steps in HBM and materialise them lazily -- the
         concentration is downloaded, and the displacement of a recorded step is solved, only when that step is
         accessed.  None = automatic (on for meshes of >= 100 000 nodes when nothing is written to disk per step).
+
+        ``record_adjoint`` (extension): keep the device trajectory of this run for ``adjoint_gradient`` (8 B per node
+        and step of HBM; the forward run is bit for bit the same).
         """
+        self._record_adjoint = bool(record_adjoint)
         if self.geometric_dimension == 3:
             plot = False
         self.logger.info("-- Computing solutions: ")

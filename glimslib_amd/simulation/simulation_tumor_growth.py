@@ -282,12 +282,42 @@ class TumorGrowth(FenicsSimulation):
         # unknown of each step, not u_previous
         h.set_state(u_previous.components[1], u_previous.components[0].reshape(-1) if mechanics else None)
         h.reset_stats()
+        if getattr(self, '_record_adjoint', False):
+            if not hasattr(h, 'adjoint_record'):
+                raise NotImplementedError("record_adjoint: the discrete adjoint is single-GPU for now")
+            h.adjoint_record(True)
+        elif hasattr(h, 'adjoint_record'):
+            h.adjoint_record(False)
         if hasattr(h, 'snapshot_clear'):
             h.snapshot_clear()
         self.solution = self.functionspace.new_function(name='solution_function')
         self.solution.label = 'solution_function'
         self.solution.assign(u_previous)
         self.solver = HipTimeStepSolver(self, h, mechanics)
+
+    # -- discrete adjoint (the backward half of the reference's adjoint entry points) -----------------------------
+    def _adjoint_raw(self, terms, need_dD=True):
+        """(J, dD, drho, dgamma, dc0) per tissue label of the run recorded by ``run(record_adjoint=True)``."""
+        h = self._backend
+        if h is None or not hasattr(h, 'adjoint_gradient'):
+            raise RuntimeError("adjoint_gradient needs a single-GPU run(record_adjoint=True) first")
+        if need_dD and getattr(self.bcs, 'von_neumann_bcs', None):
+            labels = self._labels()
+            flux = self.bcs.implement_von_neumann_bc(np.ones(len(labels)), subspace_id=1)
+            if np.any(np.asarray(flux) != 0.0):
+                raise NotImplementedError("adjoint_gradient: von Neumann data on the concentration scale with D; "
+                                          "dJ/dD is not available for such a run")
+        n_labels = int(self._labels().max()) + 1
+        return h.adjoint_gradient(terms, n_labels)
+
+    def adjoint_gradient(self, terms):
+        """
+        J and dJ/dm of the recorded run for the misfit ``terms`` (see ``Handle.adjoint_gradient``; the counterpart of
+        fenics.ReducedFunctional(J, controls).derivative, image_based_optimization.py:700-708).  Returns
+        {'J', 'diffusion', 'proliferation', 'coupling' (per-label arrays: the tables of DiscontinuousScalar), 'c0'}.
+        """
+        J, dD, drho, dgamma, dc0 = self._adjoint_raw(terms)
+        return {'J': J, 'diffusion': dD, 'proliferation': drho, 'coupling': dgamma, 'c0': dc0}
 
     # -- parameter sweeps (the forward half of the reference's adjoint entry points) -------------------------------
     def run_for_adjoint(self, parameters, output_dir=config.output_dir_simulation_tmp):

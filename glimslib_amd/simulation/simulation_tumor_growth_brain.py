@@ -68,6 +68,21 @@ class TumorGrowthBrain(TumorGrowth):
                              "(expected names CSF/WM/GM/Ventricles[/outside] in domain_names)" % missing)
         return t
 
+    def _tissue_id(self, name):
+        sd = self.subdomains
+        if hasattr(sd, 'tissue_name_id_map'):
+            return sd.tissue_name_id_map.get(name)
+        return {v: k for k, v in getattr(sd, 'tissue_id_name_map', {}).items()}.get(name)
+
+    def adjoint_gradient(self, terms):
+        """J and dJ/d(D_WM, D_GM, rho_WM, rho_GM, coupling) of the recorded run (see TumorGrowth.adjoint_gradient)."""
+        J, dD, drho, dgamma, dc0 = self._adjoint_raw(terms)
+        wm, gm = self._tissue_id('WM'), self._tissue_id('GM')
+        pick = lambda a, t: float(a[t]) if t is not None and t < len(a) else 0.0
+        return {'J': J, 'D_WM': pick(dD, wm), 'D_GM': pick(dD, gm), 'rho_WM': pick(drho, wm), 'rho_GM': pick(drho, gm),
+                # one global coupling constant on every tissue (_material_tables)
+                'coupling': float(np.sum(dgamma)), 'c0': dc0}
+
     def run_for_adjoint(self, parameters, output_dir=config.output_dir_simulation_tmp):
         """:127-145 -- (D_WM, D_GM, rho_WM, rho_GM, coupling)"""
         self.params.D_WM, self.params.D_GM = parameters[0], parameters[1]

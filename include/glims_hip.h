@@ -408,6 +408,53 @@ int glims_snapshot_load(glims_ctx* h, int64_t id, double* c);
 int glims_snapshot_mechanics(glims_ctx* h, int64_t id, double* u);
 int glims_snapshot_clear(glims_ctx* h);
 
+/* ---- discrete adjoint (single GPU) ---------------------------------------------------------------------------------------
+ * The reference fits the tissue parameters by L-BFGS-B on a misfit J of the simulated fields, with dJ/dm from dolfin-adjoint's
+ * fenics.ReducedFunctional.derivative (optimization_workflow/image_based_optimization.py:660-767, controls and derivative at
+ * :700-708; the forward runs it differentiates: run_for_adjoint*, simulation_tumor_growth*.py:142-170).  Here the gradient is
+ * the exact discrete adjoint of the backward-Euler / Newton scheme glims_step runs, on the device:
+ * one linear solve with the step's own Jacobian A(c_n) (symmetric: the forward preconditioner and PCG carry it) and one
+ * parameter-sensitivity pass per recorded step, backwards.
+ *
+ * glims_adjoint_record(h, 1) clears the trajectory, stores the current concentration as c_0 and from then on keeps a device
+ * copy of c_n after every CONVERGED step (8 B per node and step; not one bit of the forward run changes).  glims_set_state while
+ * recording starts a new trajectory at the new state.  A failed step, glims_setup / glims_set_materials, or a new Dirichlet
+ * node SET of the concentration invalidate it (new Dirichlet values do not: they carry no parameter sensitivity).  on = 0
+ * stops recording and releases the trajectory.  Partitioned handles (world > 1): GLIMS_E_USAGE, single GPU for now. */
+int glims_adjoint_record(glims_ctx* h, int on);
+
+/* One term of J, observed after recorded step `step` (0 = c_0).  `target` has n_nodes values (n_nodes * dim for
+ * GLIMS_MISFIT_U_L2, node-major), in the caller's node order; level / smooth are read by GLIMS_MISFIT_C_THRESH only.
+ *   GLIMS_MISFIT_C_L2      1/2 w (c_k - t)^T M (c_k - t)
+ *   GLIMS_MISFIT_C_THRESH  1/2 w (h(c_k) - t)^T M (h(c_k) - t),  h(c) = 1/2 (tanh((c - level) / smooth) + 1) NODEWISE
+ *                          (the reference's thresh(), image_based_optimization.py:1404-1407, is L2-projected instead)
+ *   GLIMS_MISFIT_U_L2      1/2 w (u_k - t)^T M_vec (u_k - t),  u_k = K_el^-1 (G c_k + f) (needs glims_setup(with_mechanics=1)) */
+#define GLIMS_MISFIT_C_L2 0
+#define GLIMS_MISFIT_C_THRESH 1
+#define GLIMS_MISFIT_U_L2 2
+typedef struct glims_misfit {
+  int64_t step;
+  int kind;
+  double level, smooth, weight;
+  const double* target;
+} glims_misfit;
+
+/* J of the recorded trajectory and its gradient: dJ_dD / dJ_drho / dJ_dgamma [n_labels of glims_set_materials] with respect
+ * to the per-label tables, dJ_dc0 [n_nodes] (caller's node order; may be NULL) with respect to the initial concentration.
+ * Any output pointer except J may be NULL.  The load vector of glims_set_rd_load is taken as parameter-independent (a
+ * Neumann flux term in it scales with D: the caller must not ask for dJ_dD then).  RD adjoint solves: PCG with the
+ * preconditioner the forward solves use, to ||r|| <= 1e-12 ||rhs||; elastic solves to 1e-12 ||rhs||.  The forward state
+ * (iterate, displacement, warm-start / Chebyshev / solve histories, glims_stats) is left exactly as it was; the same
+ * trajectory gives the same bits on every call.  Stands in for fenics.ReducedFunctional.__call__ + .derivative
+ * (image_based_optimization.py:700-708). */
+int glims_adjoint_gradient(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J, double* dJ_dD,
+                           double* dJ_drho, double* dJ_dgamma, double* dJ_dc0);
+
+/* Counters of the adjoint (not in glims_stats, whose layout is fixed): out[0] gradient calls, [1] backward steps,
+ * [2] RD adjoint PCG iterations, [3] elastic solves, [4] their PCG iterations, [5] recorded states held now;
+ * ms[0] wall time of the backward sweeps (may be NULL). */
+int glims_adjoint_stats(const glims_ctx* h, int64_t out[6], double* ms);
+
 /* L2 projection onto the P1 space: solves M x = rhs for `ncomp` right-hand sides stored [n_nodes][ncomp]
  * (rhs_i = int f phi_i dx, integrated by the caller), Jacobi-PCG to ||r|| <= rtol*||rhs|| per component.
  * Stands in for fenics.project(expr, FunctionSpace(mesh, "Lagrange", 1)) as used by the PostProcess classes
