@@ -200,6 +200,7 @@ class Handle:
         self._h = h
         self.options = Options()
         lib.glims_options_default(C.byref(self.options))
+        self.n_labels = None   # label count of the last successful set_materials
 
     # -- plumbing --------------------------------------------------------------------------------
     def _check(self, st, allow=()):
@@ -224,6 +225,7 @@ class Handle:
         n = len(arrs[0])
         assert all(a.shape == (n,) for a in arrs)
         self._check(self.lib.glims_set_materials(self._h, n, *[_ptr(a, _dp) for a in arrs]))
+        self.n_labels = n
 
     def set_options(self, **kw):
         for k, v in kw.items():
@@ -344,10 +346,16 @@ class Handle:
         """on: clear the trajectory, keep the current state as c_0 and a device copy of c_n after every converged step."""
         self._check(self.lib.glims_adjoint_record(self._h, 1 if on else 0))
 
-    def adjoint_gradient(self, terms, n_labels, want_dc0=True):
+    def adjoint_gradient(self, terms, n_labels=None, want_dc0=True):
         """terms: iterable of dicts {step, kind ('c_l2' | 'c_thresh' | 'u_l2' or MISFIT_*), target, weight=1, level=0,
         smooth=1}; targets in the caller's node order ([n_nodes] or [n_nodes, dim]).
-        Returns (J, dJ/dD [n_labels], dJ/drho, dJ/dgamma, dJ/dc0 [n_nodes] or None)."""
+        Returns (J, dJ/dD [n_labels], dJ/drho, dJ/dgamma, dJ/dc0 [n_nodes] or None).  The library writes one entry per label
+        of the last set_materials: n_labels, when given, must be that count (ValueError otherwise, before any call)."""
+        if self.n_labels is None:
+            raise ValueError("adjoint_gradient before set_materials")
+        if n_labels is not None and int(n_labels) != self.n_labels:
+            raise ValueError("adjoint_gradient: n_labels = %d, but set_materials gave %d labels" % (n_labels, self.n_labels))
+        n_labels = self.n_labels
         kinds = {"c_l2": MISFIT_C_L2, "c_thresh": MISFIT_C_THRESH, "u_l2": MISFIT_U_L2}
         terms = list(terms)
         arr = (Misfit * max(1, len(terms)))()

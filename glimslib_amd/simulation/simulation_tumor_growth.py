@@ -307,8 +307,7 @@ class TumorGrowth(FenicsSimulation):
             if np.any(np.asarray(flux) != 0.0):
                 raise NotImplementedError("adjoint_gradient: von Neumann data on the concentration scale with D; "
                                           "dJ/dD is not available for such a run")
-        n_labels = int(self._labels().max()) + 1
-        return h.adjoint_gradient(terms, n_labels)
+        return h.adjoint_gradient(terms)   # one entry per label of the handle's set_materials
 
     def adjoint_gradient(self, terms):
         """
