@@ -1868,6 +1868,7 @@ int gl_step(glims_ctx* h, int n_steps) {
       int slot = std::min(it, 6);   // (slot 7: second solves that start from the guess -- their counts say nothing about the ones from zero)
       int cs = GLIMS_OK;
       bool deferred = false;
+      bool cheb_idle = false;   // a dot-free solve with nothing to do (see there)
       ChebRun crun;
       if (use_cheb) {
         // |r| on entry: known to the host unless the solve starts from the warm-start guess -- then the count is chosen on the
@@ -1906,16 +1907,22 @@ int gl_step(glims_ctx* h, int n_steps) {
           GL_HIP(hipGetLastError());
           if (h->world > 1) gl_halo_exchange(h, h->cg_u.p, 1);   // (corrections are kept by their row owners: ghosts)
         }
-        last_ylast = second ? h->cheb_delta2.p : h->cheb_delta.p;
-        if (second) {
-          d2_written = true;
-          r1_now = nr;
-          used_warm2 = warm2;
+        // A solve from zero whose tolerance is already met (tol_lin >= |R_k|: a cg_atol above the residual) runs no pass and
+        // writes no correction: nothing is enqueued, c and the kept corrections stay as they are, nothing can be taken back --
+        // PCG's zero iterations.  (A warm-started solve still runs: its count is chosen on the device from |b - A u|.)
+        cheb_idle = !(ws_fused || warm2) && tol_lin >= nr;
+        if (!cheb_idle) {
+          last_ylast = second ? h->cheb_delta2.p : h->cheb_delta.p;
+          if (second) {
+            d2_written = true;
+            r1_now = nr;
+            used_warm2 = warm2;
+          }
+          crun = cheb_solve(h, v, tol_lin, nr, nr, cheap_next, (ws_fused || warm2) ? h->cg_u.p : (const double*)nullptr,
+                            last_ylast, second ? 1 : 0);
         }
-        crun = cheb_solve(h, v, tol_lin, nr, nr, cheap_next, (ws_fused || warm2) ? h->cg_u.p : (const double*)nullptr,
-                          last_ylast, second ? 1 : 0);
         deferred = crun.planned;
-        if (!deferred) {
+        if (!deferred && !cheb_idle) {
           h->stats.cg_its += crun.passes;
           h->stats.cheb_its += crun.passes;
           h->stats.last_cg_res = tol_lin;
@@ -2033,7 +2040,7 @@ int gl_step(glims_ctx* h, int n_steps) {
         fprintf(stderr, "  cheb: step %lld it %d  %.3e -> %.3e  tol_lin %.3e target %.3e  %s passes %d (m_dev %g) %s\n",
                 (long long)h->stats.steps, it, nr_before, nr, tol_lin, target, crun.planned ? "planned" : "host", crun.passes,
                 crun.planned ? km.info[0] : -1.0, cheap ? "cheap" : (speculate ? "sweep+spec" : "sweep"));
-      if (use_cheb && !(std::isfinite(nr) && (nr <= 0.5 * nr_before || nr <= target))) {
+      if (use_cheb && !cheb_idle && !(std::isfinite(nr) && (nr <= 0.5 * nr_before || nr <= target))) {
         // The Newton residual did not contract: part of the right-hand side lies outside the interval (the Chebyshev polynomial
         // grows there).  Take the correction back (it is still in cheb_delta), drop the interval -- this step's remaining
         // solves and the next step's run PCG and measure it again -- and repeat the iteration from a fresh sweep.
@@ -2079,7 +2086,7 @@ int gl_step(glims_ctx* h, int n_steps) {
       // A dot-free solve that contracts, but far less than it was sized for (10 x its tolerance plus the quadratic remainder),
       // has an interval that no longer fits what the right-hand sides excite: not a take-back -- the Newton iteration copes --
       // but two of them in a row make the next step a learning step instead of waiting for the 32nd.
-      if (use_cheb && it >= 1 && std::isfinite(nr)) {
+      if (use_cheb && !cheb_idle && it >= 1 && std::isfinite(nr)) {
         const bool weak = nr > target && nr > 10.0 * (tol_lin + (adaptive_forcing ? floor_pred : 0.0));
         cb.weak = weak ? cb.weak + 1 : 0;
         if (cb.weak >= 2) {
