@@ -1,5 +1,7 @@
 // Discrete adjoint of the backward-Euler / Newton scheme of gl_step: trajectory recording, the misfit
-// terms, the parameter-sensitivity pass, the coupling adjoint G^T mu and the backward sweep.  Single GPU.
+// terms, the parameter-sensitivity pass, the coupling adjoint G^T mu and the backward sweep.  Single GPU or partitioned
+// (world > 1: every rank sweeps its sub-mesh, the adjoint vectors exchange their ghosts before every operator use, each
+// cell enters the per-label sums on one rank only, and those sums are added over the ranks in rank order).
 //
 // Step n solves R_n = S c_n + dt N(c_n) c_n - M c_{n-1} - f_n = 0 (c_n fixed on the Dirichlet nodes).  Backwards from the last
 // recorded step N:  mu_n = K_el^-1 dJ/du_n (observed displacement terms only),  g_n = dJ/dc_n + G^T mu_n,
@@ -51,10 +53,57 @@ __global__ void k_cell_nodes(int64_t n_own, const int64_t* __restrict__ cslice_p
   }
 }
 
+// The same map on a partitioned handle: the rank holds every cell that touches an owned node, and the vertices of such a cell
+// that are ghosts have no owned row of their own.  Every owned row writes ALL vertices of its cells from its own column list
+// (the slot of vertex m is a column of the row); rows that share a cell write the same values.  seen[e] = 1 for every cell that
+// some owned row lists.
+template <int NV>
+__global__ void k_cell_nodes_all(int64_t n_own, const int64_t* __restrict__ slice_ptr, const int32_t* __restrict__ cols,
+                                 const int64_t* __restrict__ cslice_ptr, const uint32_t* __restrict__ cslots,
+                                 const int32_t* __restrict__ celem, int32_t* __restrict__ cell_nodes,
+                                 uint8_t* __restrict__ seen) {
+  const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= n_own) return;
+  const int64_t s = row >> 6, lane = row & 63;
+  const int64_t base = slice_ptr[s];
+  const int64_t cbase = cslice_ptr[s];
+  const int clen = (int)((cslice_ptr[s + 1] - cbase) >> 6);
+  for (int q = 0; q < clen; ++q) {
+    const int64_t ci = cbase + (int64_t)q * GL_WAVE + lane;
+    const int32_t e = celem[ci];
+    if (e < 0) continue;
+    const uint32_t sl = cslots[ci];
+#pragma unroll
+    for (int m = 0; m < NV; ++m)
+      cell_nodes[(int64_t)e * NV + m] = cols[base + (int64_t)((sl >> (8 * m)) & 255u) * GL_WAVE + lane];
+    seen[e] = 1;
+  }
+}
+
+// Counting rule of the per-label sums on a partitioned handle: a cell is counted by the smallest rank that owns one of its
+// vertices (that rank holds the cell).  owner of a local node: `rank` for the owned ones, ghost_owner[i - n_own] for the ghosts.
+// In place: counted[e] holds `seen` on entry.
+template <int NV>
+__global__ void k_cell_counted(int64_t n_cells, int64_t n_own, int rank, const int32_t* __restrict__ ghost_owner,
+                               const int32_t* __restrict__ cell_nodes, uint8_t* __restrict__ counted) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n_cells) return;
+  if (!counted[e]) return;   // listed by no owned row: not this rank's cell
+  int lo = rank;
+#pragma unroll
+  for (int m = 0; m < NV; ++m) {
+    const int64_t v = cell_nodes[e * NV + m];
+    if (v >= n_own) lo = min(lo, ghost_owner[v - n_own]);
+  }
+  counted[e] = lo == rank ? 1 : 0;
+}
+
 // Parameter-sensitivity pass, one thread per cell (grid-stride over a FIXED grid), labels [l0, l0 + LT) per launch.
 //   MODE 0 (c, lambda):  q0 = int_T grad lambda . grad c,  q1 = int_T lambda (c^2 - c)            (exact for P1)
 //   MODE 1 (c, mu):      q2 = mu^T G_T c with gamma = 1 = (2 mu_T + d lam_T) |T| / (d+1) div mu_h (sum_a c_a);
 //                        qcell[e] = gamma_T (2 mu_T + d lam_T) |T| / (d+1) div mu_h  (the cell's share of G^T mu)
+// counted (partitioned handles, else nullptr): cells with counted[e] = 0 stay out of the per-label sums (MODE 1 still writes
+// their qcell: the owned rows of the cell need its share of G^T mu).
 // Per-block partials [block][LT][3] in a fixed order (waves, then the block's four wave sums), no atomics: the sums are
 // bitwise reproducible.  Bytes per cell: the geometry record (1 + NV D) x 8 (56 B in 2-D, 104 B in 3-D), NV x 4 B of vertex ids,
 // 1 B of label (+ 8 B of qcell in MODE 1); the gathered vectors (2 x 8 B per node, mu: 8 d B) mostly hit the caches.
@@ -62,8 +111,8 @@ template <int D, int MODE>
 __global__ __launch_bounds__(256) void k_sens(int64_t n_cells, int l0, const int32_t* __restrict__ cell_nodes,
                                               const double* __restrict__ egeo, const uint8_t* __restrict__ label,
                                               const double* __restrict__ mat, const double* __restrict__ c,
-                                              const double* __restrict__ v, double* __restrict__ qcell,
-                                              double* __restrict__ partials) {
+                                              const double* __restrict__ v, const uint8_t* __restrict__ counted,
+                                              double* __restrict__ qcell, double* __restrict__ partials) {
   constexpr int NV = D + 1, GE = 1 + NV * D;
   constexpr double f3 = D == 2 ? 1.0 / 60.0 : 1.0 / 120.0;   // d! / (d+3)!
   constexpr double f2 = D == 2 ? 1.0 / 12.0 : 1.0 / 20.0;    // d! / (d+2)!
@@ -74,7 +123,7 @@ __global__ __launch_bounds__(256) void k_sens(int64_t n_cells, int l0, const int
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n_cells; e += stride) {
     const int lab = label[e];
     const int j = lab - l0;
-    if (MODE == 0 && (j < 0 || j >= GL_ADJ_LT)) continue;
+    if (MODE == 0 && (j < 0 || j >= GL_ADJ_LT || (counted && !counted[e]))) continue;
     const double* g = egeo + e * GE;
     const double vol = g[0];
     int nd[NV];
@@ -119,6 +168,7 @@ __global__ __launch_bounds__(256) void k_sens(int64_t n_cells, int l0, const int
       const double mu = mat[3 * GL_MAX_LABELS + lab], lam = mat[4 * GL_MAX_LABELS + lab];
       const double w = (2.0 * mu + D * lam) * vol * (1.0 / (D + 1)) * div;
       if (l0 == 0) qcell[e] = mat[2 * GL_MAX_LABELS + lab] * w;
+      if (counted && !counted[e]) continue;
       a0 = w * Sc;
     }
 #pragma unroll
@@ -286,13 +336,14 @@ template <int D>
 void sens_pass(glims_ctx* h, int mode, const double* c, const double* v, AdjWork& wk) {
   const AdjointState& a = h->adj;
   const int nb = (int)std::min<int64_t>(GL_ADJ_BLOCKS, grid_of(h->n_cells));
+  const uint8_t* counted = h->world > 1 ? a.counted.p : nullptr;
   for (int l0 = 0; l0 < h->n_labels; l0 += GL_ADJ_LT) {
     if (mode == 0)
       hipLaunchKernelGGL((k_sens<D, 0>), dim3(nb), dim3(256), 0, h->st, h->n_cells, l0, a.cell_nodes.p, h->egeo.p,
-                         h->label.p, h->mat.p, c, v, wk.qcell.p, wk.part.p);
+                         h->label.p, h->mat.p, c, v, counted, wk.qcell.p, wk.part.p);
     else
       hipLaunchKernelGGL((k_sens<D, 1>), dim3(nb), dim3(256), 0, h->st, h->n_cells, l0, a.cell_nodes.p, h->egeo.p,
-                         h->label.p, h->mat.p, c, v, wk.qcell.p, wk.part.p);
+                         h->label.p, h->mat.p, c, v, counted, wk.qcell.p, wk.part.p);
     GL_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_sens_final, dim3(1), dim3(1024), 0, h->st, nb, l0, h->n_labels, mode == 0 ? 0 : 2, wk.part.p,
                        wk.sums.p);
@@ -312,6 +363,8 @@ int solve_elastic(glims_ctx* h, AdjWork& wk, const double* rhs, double* x, const
   // r = rhs - K xD on the free dofs, x = 0
   GL_HIP(hipMemsetAsync(x, 0, (size_t)h->n_nodes * bs * sizeof(double), h->st));
   if (fx && xD) {
+    // (K xD reads the clamp values at the ghost columns; the same exchange, under the same condition, as gl_solve_mechanics)
+    if (xD == h->m_uD.p) gl_halo_exchange(h, h->m_uD.p, bs);
     gl_launch_spmv_block(h, h->st, h->pat.n_slices, nullptr, xD, wk.mKx.p, fx, nullptr, nullptr, 0, nullptr);
     hipLaunchKernelGGL(k_residual, dim3(grid_of(nd)), dim3(256), 0, h->st, nd, rhs, wk.mKx.p, fx, wk.mr.p);
   } else {
@@ -370,9 +423,26 @@ int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_o
   }
   if (a.cell_nodes.n != (size_t)h->n_cells * (D + 1)) {
     a.cell_nodes.alloc_zero((size_t)h->n_cells * (D + 1), h->st);   // (every entry is written on one GPU; 0 keeps a gap in range)
-    hipLaunchKernelGGL(k_cell_nodes<D + 1>, dim3(grid_of(n)), dim3(256), 0, h->st, n, h->pat.cslice_ptr.p,
-                       h->pat.cslots.p, h->pat.celem.p, h->pat.diag_k.p, a.cell_nodes.p);
-    GL_CHECK_LAUNCH();
+    if (h->world <= 1) {
+      hipLaunchKernelGGL(k_cell_nodes<D + 1>, dim3(grid_of(n)), dim3(256), 0, h->st, n, h->pat.cslice_ptr.p,
+                         h->pat.cslots.p, h->pat.celem.p, h->pat.diag_k.p, a.cell_nodes.p);
+      GL_CHECK_LAUNCH();
+    } else {
+      // ghost owners from the halo plan (ghosts grouped by owner: group p = peer_rank[p])
+      std::vector<int32_t> gown((size_t)std::max<int64_t>(1, nn - n), 0);
+      for (int p = 0; p < h->n_peers; ++p)
+        for (int64_t i = h->recv_ptr[p]; i < h->recv_ptr[p + 1]; ++i) gown[(size_t)i] = h->peer_rank[p];
+      dvec<int32_t> d_gown;
+      d_gown.upload(gown, h->st);
+      a.counted.alloc_zero((size_t)std::max<int64_t>(1, h->n_cells), h->st);
+      hipLaunchKernelGGL(k_cell_nodes_all<D + 1>, dim3(grid_of(n)), dim3(256), 0, h->st, n, h->pat.slice_ptr.p, h->pat.cols.p,
+                         h->pat.cslice_ptr.p, h->pat.cslots.p, h->pat.celem.p, a.cell_nodes.p, a.counted.p);
+      GL_CHECK_LAUNCH();
+      hipLaunchKernelGGL(k_cell_counted<D + 1>, dim3(grid_of(h->n_cells)), dim3(256), 0, h->st, h->n_cells, n, h->rank,
+                         d_gown.p, a.cell_nodes.p, a.counted.p);
+      GL_CHECK_LAUNCH();
+      GL_HIP(hipStreamSynchronize(h->st));   // d_gown goes out of scope
+    }
   }
   ForwardGuard guard(h, wk);
   const uint8_t* fxc = h->have_fixed_c ? h->fixed_c.p : nullptr;
@@ -382,6 +452,8 @@ int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_o
   double J = 0.0;
   int status = GLIMS_OK;
   for (int step = N; step >= 0 && status == GLIMS_OK; --step) {
+    // (c_n as recorded: gl_step leaves the ghosts of c current, but the adjoint does not rely on it -- one exchange per step)
+    gl_halo_exchange(h, a.traj[step]->p, 1);
     const double* c = a.traj[step]->p;
     GL_HIP(hipMemsetAsync(wk.g.p, 0, (size_t)nn * sizeof(double), h->st));
     bool have_u = false;
@@ -393,6 +465,7 @@ int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_o
         hipLaunchKernelGGL(k_misfit_c, dim3(grid_of(n)), dim3(256), 0, h->st, n, tm.kind, tm.level, tm.smooth, c, t, wk.e.p,
                            wk.hp.p);
         GL_CHECK_LAUNCH();
+        gl_halo_exchange(h, wk.e.p, 1);   // the mass SpMV reads e at the ghost columns
         mass_apply(h, wk.e.p, wk.Me.p);
         J += 0.5 * tm.weight * gl_dot(h, wk.e.p, wk.Me.p, n);
         hipLaunchKernelGGL(k_add_scaled_prod, dim3(grid_of(n)), dim3(256), 0, h->st, n, tm.weight, wk.hp.p, wk.Me.p, wk.g.p);
@@ -410,6 +483,7 @@ int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_o
       for (int comp = 0; comp < D; ++comp) {   // dJ/du = w M_vec (u - t), component by component through the scalar M
         hipLaunchKernelGGL(k_component, dim3(grid_of(n)), dim3(256), 0, h->st, n, D, comp, wk.uk.p, t, wk.e.p);
         GL_CHECK_LAUNCH();
+        gl_halo_exchange(h, wk.e.p, 1);
         mass_apply(h, wk.e.p, wk.Me.p);
         J += 0.5 * tm.weight * gl_dot(h, wk.e.p, wk.Me.p, n);
         hipLaunchKernelGGL(k_add_component, dim3(grid_of(n)), dim3(256), 0, h->st, n, D, comp, tm.weight, wk.Me.p,
@@ -422,6 +496,7 @@ int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_o
       int64_t its = 0;
       status = solve_elastic(h, wk, wk.murhs.p, wk.mu.p, nullptr, 1e-12, &its);
       if (status != GLIMS_OK) break;
+      gl_halo_exchange(h, wk.mu.p, D);   // qcell of every local cell, also those whose other vertices are ghosts
       sens_pass<D>(h, 1, c, wk.mu.p, wk);
       hipLaunchKernelGGL(k_gt_rows, dim3(grid_of(n)), dim3(256), 0, h->st, n, h->pat.cslice_ptr.p, h->pat.celem.p,
                          wk.qcell.p, wk.g.p);
@@ -463,6 +538,7 @@ int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_o
                       rd_mg ? &h->mg_rd : nullptr, rd_deg, 1e-12 * nb, std::max(h->opt.cg_maxit, 20000), &its, &res);
       a.pcg_its += its;
       if (status != GLIMS_OK) break;
+      gl_halo_exchange(h, wk.lam.p, 1);   // PCG updates the owned rows: the sensitivity pass and M lambda read the ghosts
       sens_pass<D>(h, 0, c, wk.lam.p, wk);
     } else {
       GL_HIP(hipMemsetAsync(wk.lam.p, 0, (size_t)nn * sizeof(double), h->st));
@@ -471,8 +547,27 @@ int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_o
     a.steps++;
   }
   std::vector<double> sums((size_t)GL_MAX_LABELS * 3);
-  GL_HIP(hipMemcpyAsync(sums.data(), wk.sums.p, sums.size() * sizeof(double), hipMemcpyDeviceToHost, h->st));
-  GL_HIP(hipStreamSynchronize(h->st));
+  if (h->world <= 1) {
+    GL_HIP(hipMemcpyAsync(sums.data(), wk.sums.p, sums.size() * sizeof(double), hipMemcpyDeviceToHost, h->st));
+    GL_HIP(hipStreamSynchronize(h->st));
+  } else {
+    // Every rank's 3 x n_labels sums, gathered by an all-reduce of [world][3 L] with zeros outside the own row (x + 0 is
+    // exact: whatever order the transport adds in, every rank receives every row bit for bit), then added in rank order on
+    // the host: the same bits on every rank.  Reached by every rank, also after a failed solve (the statuses are global).
+    const size_t L3 = (size_t)h->n_labels * 3;
+    dvec<double> all;
+    all.alloc_zero(std::max<size_t>(1, L3 * h->world), h->st);
+    if (L3) GL_HIP(hipMemcpyAsync(all.p + L3 * h->rank, wk.sums.p, L3 * sizeof(double), hipMemcpyDeviceToDevice, h->st));
+    gl_allreduce_bulk(h, all.p, L3 * h->world);
+    std::vector<double> rows(L3 * h->world);
+    if (L3) GL_HIP(hipMemcpyAsync(rows.data(), all.p, rows.size() * sizeof(double), hipMemcpyDeviceToHost, h->st));
+    GL_HIP(hipStreamSynchronize(h->st));
+    for (size_t k = 0; k < L3; ++k) {
+      double t = 0.0;
+      for (int r = 0; r < h->world; ++r) t += rows[L3 * r + k];
+      sums[k] = t;
+    }
+  }
   const double dt = h->opt.dt;
   for (int l = 0; l < h->n_labels; ++l) {
     if (dD) dD[l] = -dt * sums[l * 3 + 0];
@@ -520,10 +615,10 @@ void gl_adjoint_after_step(glims_ctx* h, int status) {
   a.traj.push_back(d);
 }
 
-int gl_adjoint_gradient(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J, double* dD, double* drho,
-                        double* dgamma, double* dc0) {
+namespace {
+// The argument and state checks of one rank (GLIMS_E_USAGE with the reason)
+void check_gradient_call(glims_ctx* h, int n_terms, const glims_misfit* terms, const double* J) {
   const AdjointState& a = h->adj;
-  GL_REQUIRE(h->world <= 1, "glims_adjoint_gradient: partitioned handles are not supported (the adjoint is single-GPU for now)");
   GL_REQUIRE(J, "glims_adjoint_gradient: null J");
   GL_REQUIRE(n_terms >= 0 && (n_terms == 0 || terms), "glims_adjoint_gradient: bad term list");
   GL_REQUIRE(h->is_setup, "glims_adjoint_gradient before glims_setup");
@@ -542,6 +637,37 @@ int gl_adjoint_gradient(glims_ctx* h, int n_terms, const glims_misfit* terms, do
                "glims_adjoint_gradient: threshold term needs smooth > 0");
     GL_REQUIRE(t.kind != GLIMS_MISFIT_U_L2 || h->have_mech,
                "glims_adjoint_gradient: a displacement term needs glims_setup(with_mechanics=1)");
+  }
+}
+}  // namespace
+
+int gl_adjoint_gradient(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J, double* dD, double* drho,
+                        double* dgamma, double* dc0) {
+  if (h->world <= 1) {
+    check_gradient_call(h, n_terms, terms, J);
+  } else {
+    // Collective: a rank that refused alone would leave the others waiting in the first halo exchange of the sweep.  Every
+    // rank's verdict goes through one all-reduce ([world] flags, 1 = refused), and every rank returns the same status.
+    std::string why;
+    try {
+      check_gradient_call(h, n_terms, terms, J);
+    } catch (const glims_error& e) {
+      if (e.code != GLIMS_E_USAGE) throw;
+      why = e.what();
+    }
+    std::vector<double> flag((size_t)h->world, 0.0);
+    flag[(size_t)h->rank] = why.empty() ? 0.0 : 1.0;
+    dvec<double> d_flag;
+    d_flag.upload(flag, h->st);
+    gl_allreduce_bulk(h, d_flag.p, flag.size());
+    GL_HIP(hipMemcpyAsync(flag.data(), d_flag.p, flag.size() * sizeof(double), hipMemcpyDeviceToHost, h->st));
+    GL_HIP(hipStreamSynchronize(h->st));
+    std::string refused;
+    for (int r = 0; r < h->world; ++r)
+      if (flag[(size_t)r] != 0.0) refused += (refused.empty() ? "" : ", ") + std::to_string(r);
+    if (!why.empty()) throw glims_error(GLIMS_E_USAGE, why + " (ranks that refused: " + refused + ")");
+    if (!refused.empty())
+      throw glims_error(GLIMS_E_USAGE, "glims_adjoint_gradient: refused on rank(s) " + refused + " (see their messages)");
   }
   return h->dim == 2 ? gradient_t<2>(h, n_terms, terms, J, dD, drho, dgamma, dc0)
                      : gradient_t<3>(h, n_terms, terms, J, dD, drho, dgamma, dc0);

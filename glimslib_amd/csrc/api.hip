@@ -785,7 +785,6 @@ int glims_snapshot_clear(glims_ctx* h) {
 
 int glims_adjoint_record(glims_ctx* h, int on) {
   return guarded(h, [&]() {
-    GL_REQUIRE(h->world <= 1, "glims_adjoint_record: partitioned handles are not supported (the adjoint is single-GPU for now)");
     if (on) {
       gl_adjoint_start(h);
       GL_HIP(hipStreamSynchronize(h->st));

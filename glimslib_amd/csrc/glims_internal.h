@@ -440,6 +440,7 @@ struct AdjointState {
   bool had_fixed = false;                  // the concentration's Dirichlet node set when recording started
   std::vector<uint8_t> fixed0;
   dvec<int32_t> cell_nodes;                // [n_cells][nv]: internal node of every cell vertex (built by the first gradient)
+  dvec<uint8_t> counted;                   // partitioned handles: [n_cells] 1 = this rank adds the cell to the per-label sums
   int64_t gradients = 0, steps = 0, pcg_its = 0, mech_solves = 0, mech_its = 0;   // glims_adjoint_stats
   double ms_backward = 0.0;
   void clear() {

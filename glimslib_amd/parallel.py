@@ -342,6 +342,37 @@ class DistributedHandle:
             out[gid] = v
         return out
 
+    # -- discrete adjoint (collective: every rank calls adjoint_gradient with the same terms) ---------------------------
+    @property
+    def n_labels(self):
+        return self.h.n_labels
+
+    def adjoint_record(self, on=True):
+        self.h.adjoint_record(on)
+
+    def adjoint_gradient(self, terms, n_labels=None, want_dc0=True):
+        """Handle.adjoint_gradient on the partitioned run: targets in GLOBAL node order ([n_global] or [n_global, dim]),
+        localised here; J and the per-label arrays come back bitwise the same on every rank, dJ/dc0 all-gathered into the
+        global order (as get_state does)."""
+        loc = []
+        for t in terms:
+            t = dict(t)
+            bs = self.dim if t["kind"] in ("u_l2", _backend.MISFIT_U_L2) else 1
+            t["target"] = self._local(t["target"], bs).reshape(-1)
+            loc.append(t)
+        J, dD, drho, dgamma, dc0 = self.h.adjoint_gradient(loc, n_labels=n_labels, want_dc0=want_dc0)
+        if want_dc0:
+            n_own = self.part.n_own
+            parts = [None] * self.world
+            self.dist.all_gather_object(parts, (self.part.global_ids[:n_own], dc0[:n_own]))
+            dc0 = np.empty(self.n_global)
+            for gid, v in parts:
+                dc0[gid] = v
+        return J, dD, drho, dgamma, dc0
+
+    def adjoint_stats(self):
+        return self.h.adjoint_stats()
+
     # -- global <-> local -----------------------------------------------------------------------------------------
     def _local(self, v, bs=1):
         v = np.asarray(v, dtype=np.float64).reshape(self.n_global, bs) if bs > 1 else np.asarray(v, dtype=np.float64)

@@ -283,8 +283,6 @@ class TumorGrowth(FenicsSimulation):
         h.set_state(u_previous.components[1], u_previous.components[0].reshape(-1) if mechanics else None)
         h.reset_stats()
         if getattr(self, '_record_adjoint', False):
-            if not hasattr(h, 'adjoint_record'):
-                raise NotImplementedError("record_adjoint: the discrete adjoint is single-GPU for now")
             h.adjoint_record(True)
         elif hasattr(h, 'adjoint_record'):
             h.adjoint_record(False)
@@ -300,7 +298,7 @@ class TumorGrowth(FenicsSimulation):
         """(J, dD, drho, dgamma, dc0) per tissue label of the run recorded by ``run(record_adjoint=True)``."""
         h = self._backend
         if h is None or not hasattr(h, 'adjoint_gradient'):
-            raise RuntimeError("adjoint_gradient needs a single-GPU run(record_adjoint=True) first")
+            raise RuntimeError("adjoint_gradient needs a run(record_adjoint=True) first")
         if need_dD and getattr(self.bcs, 'von_neumann_bcs', None):
             labels = self._labels()
             flux = self.bcs.implement_von_neumann_bc(np.ones(len(labels)), subspace_id=1)

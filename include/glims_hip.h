@@ -408,7 +408,7 @@ int glims_snapshot_load(glims_ctx* h, int64_t id, double* c);
 int glims_snapshot_mechanics(glims_ctx* h, int64_t id, double* u);
 int glims_snapshot_clear(glims_ctx* h);
 
-/* ---- discrete adjoint (single GPU) ---------------------------------------------------------------------------------------
+/* ---- discrete adjoint ----------------------------------------------------------------------------------------------------
  * The reference fits the tissue parameters by L-BFGS-B on a misfit J of the simulated fields, with dJ/dm from dolfin-adjoint's
  * fenics.ReducedFunctional.derivative (optimization_workflow/image_based_optimization.py:660-767, controls and derivative at
  * :700-708; the forward runs it differentiates: run_for_adjoint*, simulation_tumor_growth*.py:142-170).  Here the gradient is
@@ -420,7 +420,14 @@ int glims_snapshot_clear(glims_ctx* h);
  * copy of c_n after every CONVERGED step (8 B per node and step; not one bit of the forward run changes).  glims_set_state while
  * recording starts a new trajectory at the new state.  A failed step, glims_setup / glims_set_materials, or a new Dirichlet
  * node SET of the concentration invalidate it (new Dirichlet values do not: they carry no parameter sensitivity).  on = 0
- * stops recording and releases the trajectory.  Partitioned handles (world > 1): GLIMS_E_USAGE, single GPU for now. */
+ * stops recording and releases the trajectory.
+ *
+ * Partitioned handles (world > 1): recording is per rank (the local n_nodes per step, not collective).  glims_adjoint_gradient
+ * is COLLECTIVE: every rank calls it, with the same term list (SPMD: same count, order, steps, kinds, weights, levels and
+ * smooths; each rank's targets in its own local numbering).  A rank whose arguments or trajectory are refused makes every rank
+ * return GLIMS_E_USAGE (one all-reduce of the verdicts comes before any other collective).  J and the three per-label arrays
+ * are global and bitwise the same on every rank; dJ_dc0 is in the local numbering, meaningful on the owned nodes (ghost
+ * entries 0).  glims_adjoint_stats is per rank. */
 int glims_adjoint_record(glims_ctx* h, int on);
 
 /* One term of J, observed after recorded step `step` (0 = c_0).  `target` has n_nodes values (n_nodes * dim for
