@@ -128,6 +128,7 @@ SIGNATURES = {
     "glims_project": (C.c_int, [_h, _dp, _dp, C.c_int, C.c_double]),
     "glims_adjoint_record": (C.c_int, [_h, C.c_int]),
     "glims_adjoint_gradient": (C.c_int, [_h, C.c_int, C.POINTER(Misfit), _dp, _dp, _dp, _dp, _dp]),
+    "glims_adjoint_gradient_full": (C.c_int, [_h, C.c_int, C.POINTER(Misfit), _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "glims_adjoint_stats": (C.c_int, [_h, _i64p, _dp]),
     "glims_comm_unique_id": (C.c_int, [C.c_char_p]),
     "glims_comm_init": (C.c_int, [_h, C.c_int, C.c_int, C.c_char_p]),
@@ -346,10 +347,11 @@ class Handle:
         """on: clear the trajectory, keep the current state as c_0 and a device copy of c_n after every converged step."""
         self._check(self.lib.glims_adjoint_record(self._h, 1 if on else 0))
 
-    def adjoint_gradient(self, terms, n_labels=None, want_dc0=True):
+    def adjoint_gradient(self, terms, n_labels=None, want_dc0=True, elastic=False):
         """terms: iterable of dicts {step, kind ('c_l2' | 'c_thresh' | 'u_l2' or MISFIT_*), target, weight=1, level=0,
         smooth=1}; targets in the caller's node order ([n_nodes] or [n_nodes, dim]).
-        Returns (J, dJ/dD [n_labels], dJ/drho, dJ/dgamma, dJ/dc0 [n_nodes] or None).  The library writes one entry per label
+        Returns (J, dJ/dD [n_labels], dJ/drho, dJ/dgamma, dJ/dc0 [n_nodes] or None); with elastic=True (glims_adjoint_gradient_full)
+        (J, dJ/dD, dJ/drho, dJ/dgamma, dJ/dc0, dJ/dE [n_labels], dJ/dnu [n_labels]).  The library writes one entry per label
         of the last set_materials: n_labels, when given, must be that count (ValueError otherwise, before any call)."""
         if self.n_labels is None:
             raise ValueError("adjoint_gradient before set_materials")
@@ -368,8 +370,13 @@ class Handle:
             arr[k] = Misfit(int(t["step"]), int(kind), float(t.get("level", 0.0)), float(t.get("smooth", 1.0)),
                             float(t.get("weight", 1.0)), _ptr(tg, _dp))
         J = C.c_double(0.0)
-        out = [np.zeros(int(n_labels)) for _ in range(3)]
+        out = [np.zeros(int(n_labels)) for _ in range(5 if elastic else 3)]
         dc0 = np.zeros(self.n_nodes) if want_dc0 else None
+        if elastic:
+            self._check(self.lib.glims_adjoint_gradient_full(self._h, len(terms), arr, C.byref(J),
+                                                             *[_ptr(a, _dp) for a in out[:3]], _ptr(dc0, _dp),
+                                                             _ptr(out[3], _dp), _ptr(out[4], _dp)))
+            return (J.value, out[0], out[1], out[2], dc0, out[3], out[4])
         self._check(self.lib.glims_adjoint_gradient(self._h, len(terms), arr, C.byref(J), *[_ptr(a, _dp) for a in out],
                                                     _ptr(dc0, _dp)))
         return (J.value, out[0], out[1], out[2], dc0)

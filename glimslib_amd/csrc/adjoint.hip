@@ -7,7 +7,10 @@
 // recorded step N:  mu_n = K_el^-1 dJ/du_n (observed displacement terms only),  g_n = dJ/dc_n + G^T mu_n,
 // A(c_n) lambda_n = g_n + M lambda_{n+1} (masked: lambda = 0 on the constrained nodes), and per label t
 //   dJ/dD_t = -dt sum_n int_t grad lambda_n . grad c_n,   dJ/drho_t = -dt sum_n int_t lambda_n (c_n^2 - c_n),
-//   dJ/dgamma_t = sum_k mu_k^T G_t c_k,                   dJ/dc_0 = M lambda_1 + dJ/dc_0 (explicit).
+//   dJ/dgamma_t = sum_k mu_k^T G_t c_k,                   dJ/dc_0 = M lambda_1 + dJ/dc_0 (explicit),
+//   dJ/dp_t = sum_k mu_k^T (dG/dp c_k - dK/dp u_k)  for p = E_t, nu_t  (u_k with its Dirichlet values).  K and G are linear
+//   in the cell's Lame pair: A_t = sum int_t eps(mu):eps(u), B_t = sum int_t div mu div u and
+//   C_t = dJ/dgamma_t / (2 mu_t + d lam_t) give dJ/dp_t = gamma_t (2 mu' + d lam') C_t - (2 mu' A_t + lam' B_t).
 // (carrying capacity 1, as in the forward kernels: the reaction weights of k_corner_weights are rho |T| d!/(d+3)!.)
 #include "glims_internal.h"
 
@@ -102,11 +105,13 @@ __global__ void k_cell_counted(int64_t n_cells, int64_t n_own, int rank, const i
 //   MODE 0 (c, lambda):  q0 = int_T grad lambda . grad c,  q1 = int_T lambda (c^2 - c)            (exact for P1)
 //   MODE 1 (c, mu):      q2 = mu^T G_T c with gamma = 1 = (2 mu_T + d lam_T) |T| / (d+1) div mu_h (sum_a c_a);
 //                        qcell[e] = gamma_T (2 mu_T + d lam_T) |T| / (d+1) div mu_h  (the cell's share of G^T mu)
+//   MODE 2 (u, mu):      q0 = int_T eps(mu_h):eps(u_h),  q1 = int_T div mu_h div u_h  (both block size d; c is u here)
 // counted (partitioned handles, else nullptr): cells with counted[e] = 0 stay out of the per-label sums (MODE 1 still writes
 // their qcell: the owned rows of the cell need its share of G^T mu).
 // Per-block partials [block][LT][3] in a fixed order (waves, then the block's four wave sums), no atomics: the sums are
 // bitwise reproducible.  Bytes per cell: the geometry record (1 + NV D) x 8 (56 B in 2-D, 104 B in 3-D), NV x 4 B of vertex ids,
-// 1 B of label (+ 8 B of qcell in MODE 1); the gathered vectors (2 x 8 B per node, mu: 8 d B) mostly hit the caches.
+// 1 B of label (+ 8 B of qcell in MODE 1); the gathered vectors (2 x 8 B per node, mu: 8 d B; MODE 2: u and mu, 2 x 8 d B)
+// mostly hit the caches.
 template <int D, int MODE>
 __global__ __launch_bounds__(256) void k_sens(int64_t n_cells, int l0, const int32_t* __restrict__ cell_nodes,
                                               const double* __restrict__ egeo, const uint8_t* __restrict__ label,
@@ -123,53 +128,80 @@ __global__ __launch_bounds__(256) void k_sens(int64_t n_cells, int l0, const int
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n_cells; e += stride) {
     const int lab = label[e];
     const int j = lab - l0;
-    if (MODE == 0 && (j < 0 || j >= GL_ADJ_LT || (counted && !counted[e]))) continue;
+    if (MODE != 1 && (j < 0 || j >= GL_ADJ_LT || (counted && !counted[e]))) continue;
     const double* g = egeo + e * GE;
     const double vol = g[0];
     int nd[NV];
 #pragma unroll
     for (int m = 0; m < NV; ++m) nd[m] = cell_nodes[e * NV + m];
-    double cv[NV];
-#pragma unroll
-    for (int m = 0; m < NV; ++m) cv[m] = c[nd[m]];
     double a0 = 0.0, a1 = 0.0;
-    if (MODE == 0) {
-      double lv[NV], gc[D] = {0.0}, gl[D] = {0.0};
+    if (MODE == 2) {
+      // grad w_h [a][b] = d_a w_b = sum_m w_{m,b} dphi_m/dx_a
+      double gm[D][D] = {}, gu[D][D] = {};
 #pragma unroll
-      for (int m = 0; m < NV; ++m) lv[m] = v[nd[m]];
-      double Sl = 0.0, Sc = 0.0, lc = 0.0, cc = 0.0, lcc = 0.0;
+      for (int m = 0; m < NV; ++m)
 #pragma unroll
-      for (int m = 0; m < NV; ++m) {
+        for (int b = 0; b < D; ++b) {
+          const double vm = v[(int64_t)nd[m] * D + b], um = c[(int64_t)nd[m] * D + b];
 #pragma unroll
-        for (int a = 0; a < D; ++a) {
-          gc[a] += cv[m] * g[1 + m * D + a];
-          gl[a] += lv[m] * g[1 + m * D + a];
+          for (int a = 0; a < D; ++a) {
+            gm[a][b] += vm * g[1 + m * D + a];
+            gu[a][b] += um * g[1 + m * D + a];
+          }
         }
-        Sl += lv[m];
-        Sc += cv[m];
-        lc += lv[m] * cv[m];
-        cc += cv[m] * cv[m];
-        lcc += lv[m] * cv[m] * cv[m];
-      }
-      double gg = 0.0;
+      double ee = 0.0, dm = 0.0, du = 0.0;
 #pragma unroll
-      for (int a = 0; a < D; ++a) gg += gl[a] * gc[a];
-      a0 = vol * gg;
-      // sum_{abc} l_a c_b c_c prod(alpha!) = Sl Sc^2 + 2 Sc (l.c) + Sl (c.c) + 2 sum l_a c_a^2;   sum_{ab} l_a c_b (1 + delta_ab)
-      a1 = vol * (f3 * (Sl * Sc * Sc + 2.0 * Sc * lc + Sl * cc + 2.0 * lcc) - f2 * (Sl * Sc + lc));
+      for (int a = 0; a < D; ++a) {
+        dm += gm[a][a];
+        du += gu[a][a];
+#pragma unroll
+        for (int b = 0; b < D; ++b) ee += 0.25 * (gm[a][b] + gm[b][a]) * (gu[a][b] + gu[b][a]);
+      }
+      a0 = vol * ee;
+      a1 = vol * dm * du;
     } else {
-      double div = 0.0, Sc = 0.0;
+      double cv[NV];
 #pragma unroll
-      for (int m = 0; m < NV; ++m) {
-        Sc += cv[m];
+      for (int m = 0; m < NV; ++m) cv[m] = c[nd[m]];
+      if (MODE == 0) {
+        double lv[NV], gc[D] = {0.0}, gl[D] = {0.0};
 #pragma unroll
-        for (int a = 0; a < D; ++a) div += v[(int64_t)nd[m] * D + a] * g[1 + m * D + a];
+        for (int m = 0; m < NV; ++m) lv[m] = v[nd[m]];
+        double Sl = 0.0, Sc = 0.0, lc = 0.0, cc = 0.0, lcc = 0.0;
+#pragma unroll
+        for (int m = 0; m < NV; ++m) {
+#pragma unroll
+          for (int a = 0; a < D; ++a) {
+            gc[a] += cv[m] * g[1 + m * D + a];
+            gl[a] += lv[m] * g[1 + m * D + a];
+          }
+          Sl += lv[m];
+          Sc += cv[m];
+          lc += lv[m] * cv[m];
+          cc += cv[m] * cv[m];
+          lcc += lv[m] * cv[m] * cv[m];
+        }
+        double gg = 0.0;
+#pragma unroll
+        for (int a = 0; a < D; ++a) gg += gl[a] * gc[a];
+        a0 = vol * gg;
+        // sum_{abc} l_a c_b c_c prod(alpha!) = Sl Sc^2 + 2 Sc (l.c) + Sl (c.c) + 2 sum l_a c_a^2;
+        // sum_{ab} l_a c_b (1 + delta_ab)
+        a1 = vol * (f3 * (Sl * Sc * Sc + 2.0 * Sc * lc + Sl * cc + 2.0 * lcc) - f2 * (Sl * Sc + lc));
+      } else {
+        double div = 0.0, Sc = 0.0;
+#pragma unroll
+        for (int m = 0; m < NV; ++m) {
+          Sc += cv[m];
+#pragma unroll
+          for (int a = 0; a < D; ++a) div += v[(int64_t)nd[m] * D + a] * g[1 + m * D + a];
+        }
+        const double mu = mat[3 * GL_MAX_LABELS + lab], lam = mat[4 * GL_MAX_LABELS + lab];
+        const double w = (2.0 * mu + D * lam) * vol * (1.0 / (D + 1)) * div;
+        if (l0 == 0) qcell[e] = mat[2 * GL_MAX_LABELS + lab] * w;
+        if (counted && !counted[e]) continue;
+        a0 = w * Sc;
       }
-      const double mu = mat[3 * GL_MAX_LABELS + lab], lam = mat[4 * GL_MAX_LABELS + lab];
-      const double w = (2.0 * mu + D * lam) * vol * (1.0 / (D + 1)) * div;
-      if (l0 == 0) qcell[e] = mat[2 * GL_MAX_LABELS + lab] * w;
-      if (counted && !counted[e]) continue;
-      a0 = w * Sc;
     }
 #pragma unroll
     for (int q = 0; q < GL_ADJ_LT; ++q)
@@ -194,9 +226,10 @@ __global__ __launch_bounds__(256) void k_sens(int64_t n_cells, int l0, const int
   }
 }
 
-// second stage, fixed order over the blocks: sums[(l0 + q) * 3 + k_off + k] += sum_b partials[b][q][k].  One wave per sum
-// (16 waves): lane l adds blocks l, l + 64, ... in order, then the wave's butterfly -- the same order on every call
-__global__ __launch_bounds__(1024) void k_sens_final(int n_blocks, int l0, int n_labels, int k_off,
+// second stage, fixed order over the blocks: sums[(l0 + q) * ls + k_off + k] += sum_b partials[b][q][k] (ls sums per label).
+// One wave per sum (16 waves): lane l adds blocks l, l + 64, ... in order, then the wave's butterfly -- the same order on every
+// call
+__global__ __launch_bounds__(1024) void k_sens_final(int n_blocks, int l0, int n_labels, int ls, int k_off,
                                                      const double* __restrict__ partials, double* __restrict__ sums) {
   const int t = threadIdx.x >> 6, lane = threadIdx.x & 63;
   if (t >= GL_ADJ_LT * 2) return;
@@ -204,7 +237,7 @@ __global__ __launch_bounds__(1024) void k_sens_final(int n_blocks, int l0, int n
   for (int b = lane; b < n_blocks; b += 64) s += partials[(size_t)b * GL_ADJ_LT * 2 + t];
   s = wsum(s);
   const int q = t / 2, k = t % 2;
-  if (lane == 0 && l0 + q < n_labels && k_off + k <= 2) sums[(l0 + q) * 3 + k_off + k] += s;
+  if (lane == 0 && l0 + q < n_labels && k_off + k < ls) sums[(l0 + q) * ls + k_off + k] += s;
 }
 
 // g[row] += sum over the row's incidences of qcell[cell]  (G^T mu, atomics-free through the row-owned lists)
@@ -277,7 +310,7 @@ __global__ void k_perm(int64_t n, int bs, const int32_t* __restrict__ old2new, c
 
 // device scratch of one gradient call (released on return)
 struct AdjWork {
-  dvec<double> lam, lam_next, rhs, g, r, u, w, p, s, e, hp, Me, tmp, qcell, part, sums, vA, dinv, stage;
+  dvec<double> lam, lam_next, rhs, g, r, u, w, p, s, e, hp, Me, tmp, qcell, part, sums, esums, vA, dinv, stage;
   dvec<double> uk, murhs, mu, mr, mu_, mw, mp, ms, mKx;
   std::vector<dvec<double>*> targets;
   ~AdjWork() {
@@ -332,6 +365,7 @@ void mass_apply(glims_ctx* h, const double* x, double* y) {
   gl_launch_spmv(h, h->st, h->pat.n_slices, nullptr, h->vM.p, x, y, nullptr, nullptr, nullptr, nullptr, 0, nullptr);
 }
 
+// mode 0: (c, lambda) -> sums[l][0..1];  mode 1: (c, mu) -> sums[l][2] and qcell;  mode 2: (u, mu) -> esums[l][0..1]
 template <int D>
 void sens_pass(glims_ctx* h, int mode, const double* c, const double* v, AdjWork& wk) {
   const AdjointState& a = h->adj;
@@ -341,12 +375,18 @@ void sens_pass(glims_ctx* h, int mode, const double* c, const double* v, AdjWork
     if (mode == 0)
       hipLaunchKernelGGL((k_sens<D, 0>), dim3(nb), dim3(256), 0, h->st, h->n_cells, l0, a.cell_nodes.p, h->egeo.p,
                          h->label.p, h->mat.p, c, v, counted, wk.qcell.p, wk.part.p);
-    else
+    else if (mode == 1)
       hipLaunchKernelGGL((k_sens<D, 1>), dim3(nb), dim3(256), 0, h->st, h->n_cells, l0, a.cell_nodes.p, h->egeo.p,
                          h->label.p, h->mat.p, c, v, counted, wk.qcell.p, wk.part.p);
+    else
+      hipLaunchKernelGGL((k_sens<D, 2>), dim3(nb), dim3(256), 0, h->st, h->n_cells, l0, a.cell_nodes.p, h->egeo.p,
+                         h->label.p, h->mat.p, c, v, counted, wk.qcell.p, wk.part.p);
     GL_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_sens_final, dim3(1), dim3(1024), 0, h->st, nb, l0, h->n_labels, mode == 0 ? 0 : 2, wk.part.p,
-                       wk.sums.p);
+    if (mode < 2)
+      hipLaunchKernelGGL(k_sens_final, dim3(1), dim3(1024), 0, h->st, nb, l0, h->n_labels, 3, mode == 0 ? 0 : 2, wk.part.p,
+                         wk.sums.p);
+    else
+      hipLaunchKernelGGL(k_sens_final, dim3(1), dim3(1024), 0, h->st, nb, l0, h->n_labels, 2, 0, wk.part.p, wk.esums.p);
     GL_CHECK_LAUNCH();
   }
 }
@@ -390,7 +430,7 @@ int solve_elastic(glims_ctx* h, AdjWork& wk, const double* rhs, double* x, const
 
 template <int D>
 int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_out, double* dD, double* drho,
-               double* dgamma, double* dc0) {
+               double* dgamma, double* dc0, double* dE, double* dnu) {
   AdjointState& a = h->adj;
   const int64_t n = h->n_own, nn = h->n_nodes, nd = nn * D;
   const int N = (int)a.traj.size() - 1;
@@ -404,6 +444,8 @@ int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_o
   wk.qcell.alloc_zero((size_t)h->n_cells, h->st);
   wk.part.alloc_zero((size_t)GL_ADJ_BLOCKS * GL_ADJ_LT * 2, h->st);
   wk.sums.alloc_zero((size_t)GL_MAX_LABELS * 3, h->st);
+  const bool elastic = dE || dnu;   // the E / nu pass runs only when asked for
+  if (elastic) wk.esums.alloc_zero((size_t)GL_MAX_LABELS * 2, h->st);
   wk.stage.alloc_zero((size_t)nd, h->st);
   bool any_u = false;
   for (int k = 0; k < n_terms; ++k) any_u = any_u || terms[k].kind == GLIMS_MISFIT_U_L2;
@@ -501,6 +543,10 @@ int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_o
       hipLaunchKernelGGL(k_gt_rows, dim3(grid_of(n)), dim3(256), 0, h->st, n, h->pat.cslice_ptr.p, h->pat.celem.p,
                          wk.qcell.p, wk.g.p);
       GL_CHECK_LAUNCH();
+      if (elastic) {   // A_t, B_t from u_k (its clamp values in place: solve_elastic wrote them) and mu_k
+        gl_halo_exchange(h, wk.uk.p, D);   // PCG updates the owned rows: the cells at the cut read u_k at their ghosts
+        sens_pass<D>(h, 2, wk.uk.p, wk.mu.p, wk);
+      }
     }
     if (step == 0) {   // dJ/dc_0 = M lambda_1 + g_0
       if (dc0) {
@@ -546,25 +592,29 @@ int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_o
     std::swap(wk.lam.p, wk.lam_next.p);
     a.steps++;
   }
-  std::vector<double> sums((size_t)GL_MAX_LABELS * 3);
+  // sums: [L][3] (D, rho, gamma), then [L][2] (A, B) when the E / nu pass ran
+  const size_t L3 = (size_t)h->n_labels * 3, L2 = elastic ? (size_t)h->n_labels * 2 : 0, W = L3 + L2;
+  std::vector<double> sums(W);
   if (h->world <= 1) {
-    GL_HIP(hipMemcpyAsync(sums.data(), wk.sums.p, sums.size() * sizeof(double), hipMemcpyDeviceToHost, h->st));
+    GL_HIP(hipMemcpyAsync(sums.data(), wk.sums.p, L3 * sizeof(double), hipMemcpyDeviceToHost, h->st));
+    if (L2) GL_HIP(hipMemcpyAsync(sums.data() + L3, wk.esums.p, L2 * sizeof(double), hipMemcpyDeviceToHost, h->st));
     GL_HIP(hipStreamSynchronize(h->st));
   } else {
-    // Every rank's 3 x n_labels sums, gathered by an all-reduce of [world][3 L] with zeros outside the own row (x + 0 is
-    // exact: whatever order the transport adds in, every rank receives every row bit for bit), then added in rank order on
-    // the host: the same bits on every rank.  Reached by every rank, also after a failed solve (the statuses are global).
-    const size_t L3 = (size_t)h->n_labels * 3;
+    // Every rank's W = 3 (or 5) x n_labels sums, gathered by an all-reduce of [world][W] with zeros outside the own row
+    // (x + 0 is exact: whatever order the transport adds in, every rank receives every row bit for bit), then added in rank
+    // order on the host: the same bits on every rank.  Reached by every rank, also after a failed solve (the statuses are
+    // global; `elastic` is the same on every rank: the caller's outputs are SPMD).
     dvec<double> all;
-    all.alloc_zero(std::max<size_t>(1, L3 * h->world), h->st);
-    if (L3) GL_HIP(hipMemcpyAsync(all.p + L3 * h->rank, wk.sums.p, L3 * sizeof(double), hipMemcpyDeviceToDevice, h->st));
-    gl_allreduce_bulk(h, all.p, L3 * h->world);
-    std::vector<double> rows(L3 * h->world);
-    if (L3) GL_HIP(hipMemcpyAsync(rows.data(), all.p, rows.size() * sizeof(double), hipMemcpyDeviceToHost, h->st));
+    all.alloc_zero(std::max<size_t>(1, W * h->world), h->st);
+    if (L3) GL_HIP(hipMemcpyAsync(all.p + W * h->rank, wk.sums.p, L3 * sizeof(double), hipMemcpyDeviceToDevice, h->st));
+    if (L2) GL_HIP(hipMemcpyAsync(all.p + W * h->rank + L3, wk.esums.p, L2 * sizeof(double), hipMemcpyDeviceToDevice, h->st));
+    gl_allreduce_bulk(h, all.p, W * h->world);
+    std::vector<double> rows(W * h->world);
+    if (W) GL_HIP(hipMemcpyAsync(rows.data(), all.p, rows.size() * sizeof(double), hipMemcpyDeviceToHost, h->st));
     GL_HIP(hipStreamSynchronize(h->st));
-    for (size_t k = 0; k < L3; ++k) {
+    for (size_t k = 0; k < W; ++k) {
       double t = 0.0;
-      for (int r = 0; r < h->world; ++r) t += rows[L3 * r + k];
+      for (int r = 0; r < h->world; ++r) t += rows[W * r + k];
       sums[k] = t;
     }
   }
@@ -573,6 +623,24 @@ int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_o
     if (dD) dD[l] = -dt * sums[l * 3 + 0];
     if (drho) drho[l] = -dt * sums[l * 3 + 1];
     if (dgamma) dgamma[l] = sums[l * 3 + 2];
+  }
+  for (int l = 0; elastic && l < h->n_labels; ++l) {
+    // C_t = sum_k int_t |T|/(d+1) div mu_k sum_a c_k,a = (dJ/dgamma sum) / (2 mu_t + d lam_t): mode 1's sum carries the factor
+    const double* mh = h->mat_host.data();
+    const double gam = mh[2 * GL_MAX_LABELS + l], mu = mh[3 * GL_MAX_LABELS + l], lam = mh[4 * GL_MAX_LABELS + l];
+    const double E = mh[5 * GL_MAX_LABELS + l], nu = mh[6 * GL_MAX_LABELS + l];
+    const double den = 2.0 * mu + D * lam;
+    const double Ct = den != 0.0 ? sums[l * 3 + 2] / den : 0.0;
+    const double At = sums[L3 + l * 2 + 0], Bt = sums[L3 + l * 2 + 1];
+    const double q = (1.0 + nu) * (1.0 - 2.0 * nu);
+    if (dE) {
+      const double mp = 1.0 / (2.0 * (1.0 + nu)), lp = nu / q;
+      dE[l] = gam * (2.0 * mp + D * lp) * Ct - (2.0 * mp * At + lp * Bt);
+    }
+    if (dnu) {
+      const double mp = -E / (2.0 * (1.0 + nu) * (1.0 + nu)), lp = E * (1.0 + 2.0 * nu * nu) / (q * q);
+      dnu[l] = gam * (2.0 * mp + D * lp) * Ct - (2.0 * mp * At + lp * Bt);
+    }
   }
   *J_out = J;
   a.gradients++;
@@ -642,12 +710,12 @@ void check_gradient_call(glims_ctx* h, int n_terms, const glims_misfit* terms, c
 }  // namespace
 
 int gl_adjoint_gradient(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J, double* dD, double* drho,
-                        double* dgamma, double* dc0) {
+                        double* dgamma, double* dc0, double* dE, double* dnu) {
   if (h->world <= 1) {
     check_gradient_call(h, n_terms, terms, J);
   } else {
     // Collective: a rank that refused alone would leave the others waiting in the first halo exchange of the sweep.  Every
-    // rank's verdict goes through one all-reduce ([world] flags, 1 = refused), and every rank returns the same status.
+    // rank's verdict goes through one all-reduce ([2][world] flags, 1 = refused), and every rank returns the same status.
     std::string why;
     try {
       check_gradient_call(h, n_terms, terms, J);
@@ -655,8 +723,10 @@ int gl_adjoint_gradient(glims_ctx* h, int n_terms, const glims_misfit* terms, do
       if (e.code != GLIMS_E_USAGE) throw;
       why = e.what();
     }
-    std::vector<double> flag((size_t)h->world, 0.0);
+    // (second row: whether the rank asks for dJ/dE or dJ/dnu -- the size of the final all-reduce follows it)
+    std::vector<double> flag((size_t)h->world * 2, 0.0);
     flag[(size_t)h->rank] = why.empty() ? 0.0 : 1.0;
+    flag[(size_t)(h->world + h->rank)] = (dE || dnu) ? 1.0 : 0.0;
     dvec<double> d_flag;
     d_flag.upload(flag, h->st);
     gl_allreduce_bulk(h, d_flag.p, flag.size());
@@ -668,7 +738,10 @@ int gl_adjoint_gradient(glims_ctx* h, int n_terms, const glims_misfit* terms, do
     if (!why.empty()) throw glims_error(GLIMS_E_USAGE, why + " (ranks that refused: " + refused + ")");
     if (!refused.empty())
       throw glims_error(GLIMS_E_USAGE, "glims_adjoint_gradient: refused on rank(s) " + refused + " (see their messages)");
+    for (int r = 1; r < h->world; ++r)
+      if (flag[(size_t)(h->world + r)] != flag[(size_t)h->world])
+        throw glims_error(GLIMS_E_USAGE, "glims_adjoint_gradient_full: the ranks disagree on asking for dJ_dE / dJ_dnu");
   }
-  return h->dim == 2 ? gradient_t<2>(h, n_terms, terms, J, dD, drho, dgamma, dc0)
-                     : gradient_t<3>(h, n_terms, terms, J, dD, drho, dgamma, dc0);
+  return h->dim == 2 ? gradient_t<2>(h, n_terms, terms, J, dD, drho, dgamma, dc0, dE, dnu)
+                     : gradient_t<3>(h, n_terms, terms, J, dD, drho, dgamma, dc0, dE, dnu);
 }

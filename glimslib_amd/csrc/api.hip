@@ -345,6 +345,10 @@ int glims_set_materials(glims_ctx* h, int n_labels, const double* D, const doubl
     }
     h->mat.upload(m, h->st);
     GL_HIP(hipStreamSynchronize(h->st));
+    m.resize(7 * GL_MAX_LABELS, 0.0);
+    std::copy(E, E + n_labels, m.begin() + 5 * GL_MAX_LABELS);
+    std::copy(nu, nu + n_labels, m.begin() + 6 * GL_MAX_LABELS);
+    h->mat_host = std::move(m);
     h->n_labels = n_labels;
     h->adj.invalidate("glims_set_materials after recording started");
     h->have_materials = true;
@@ -796,9 +800,16 @@ int glims_adjoint_record(glims_ctx* h, int on) {
   });
 }
 
+int glims_adjoint_gradient_full(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J, double* dJ_dD,
+                                double* dJ_drho, double* dJ_dgamma, double* dJ_dc0, double* dJ_dE, double* dJ_dnu) {
+  return guarded(h, [&]() {
+    return gl_adjoint_gradient(h, n_terms, terms, J, dJ_dD, dJ_drho, dJ_dgamma, dJ_dc0, dJ_dE, dJ_dnu);
+  });
+}
+
 int glims_adjoint_gradient(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J, double* dJ_dD,
                            double* dJ_drho, double* dJ_dgamma, double* dJ_dc0) {
-  return guarded(h, [&]() { return gl_adjoint_gradient(h, n_terms, terms, J, dJ_dD, dJ_drho, dJ_dgamma, dJ_dc0); });
+  return glims_adjoint_gradient_full(h, n_terms, terms, J, dJ_dD, dJ_drho, dJ_dgamma, dJ_dc0, nullptr, nullptr);
 }
 
 int glims_adjoint_stats(const glims_ctx* h, int64_t out[6], double* ms) {

@@ -474,6 +474,7 @@ struct glims_ctx {
   dvec<double> egeo;                       // per cell: |T|, grad(lambda_a) [nv][dim]
   dvec<double> evol;                       // per cell: |T| once more, compact (the per-incidence weights read 8 B, not a 104-B record)
   dvec<double> mat;                        // [5][GL_MAX_LABELS]: D, rho, gamma, mu, lambda
+  std::vector<double> mat_host;            // host copy of mat, then E [GL_MAX_LABELS] and nu [GL_MAX_LABELS] (adjoint E / nu)
   bool have_materials = false, is_setup = false, have_mech = false, have_state = false;
 
   glims_options opt;
@@ -703,7 +704,7 @@ int gl_pcg(glims_ctx* h, double* x, double* r, double* u, double* w, double* p, 
 void gl_adjoint_after_step(glims_ctx* h, int status);   // gl_step: record c_n of a converged step / invalidate
 void gl_adjoint_start(glims_ctx* h);                    // clear, store c_0 (the current state)
 int gl_adjoint_gradient(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J, double* dD, double* drho,
-                        double* dgamma, double* dc0);
+                        double* dgamma, double* dc0, double* dE, double* dnu);
 
 // mg.hip --------------------------------------------------------------------------------------------
 void gl_mesh_metrics(glims_ctx* h, const HostPattern& hp, const double* xyz_old);

@@ -17,6 +17,8 @@ __all__ = ["ReducedFunctional", "minimize", "parameter_map"]
 
 BRAIN_NAMES = ("D_WM", "D_GM", "rho_WM", "rho_GM", "coupling")
 TUMOR_NAMES = ("diffusion", "proliferation", "coupling")
+# every parameter of TumorGrowthBrain.adjoint_gradient, for ReducedFunctional(names=...)
+BRAIN_CONTROLS = BRAIN_NAMES + ("E_GM", "E_WM", "E_CSF", "E_VENT", "nu_GM", "nu_WM", "nu_CSF", "nu_VENT")
 
 
 def parameter_map(n_params, brain=True):
@@ -43,18 +45,30 @@ def parameter_map(n_params, brain=True):
 
 class ReducedFunctional:
     """
-    J(m) and dJ/dm(m) for a simulation ``sim`` (TumorGrowth / TumorGrowthBrain) and the controls of ``parameter_map``.
+    J(m) and dJ/dm(m) for a simulation ``sim`` (TumorGrowth / TumorGrowthBrain) and the controls of ``parameter_map``, or,
+    with ``names`` (a tuple of TumorGrowthBrain parameter names, BRAIN_CONTROLS), exactly those parameters (P = identity):
+    ``names=('E_WM', 'coupling')`` makes m = (E_WM, coupling).
 
     ``terms_builder(sim, n_steps)`` returns the misfit terms (see ``Handle.adjoint_gradient``) once the forward run of m has
     taken ``n_steps`` steps.  The last m is cached: scipy's ``fun`` / ``jac`` pair for one m costs one forward and one
     backward run.
     """
 
-    def __init__(self, sim, n_params, terms_builder, run_kwargs=None):
+    def __init__(self, sim, n_params, terms_builder, run_kwargs=None, names=None):
         self.sim = sim
         self.n_params = int(n_params)
         self.brain = hasattr(sim.params, "D_WM")
-        self.names, self.P = parameter_map(self.n_params, self.brain)
+        if names is None:
+            self.names, self.P = parameter_map(self.n_params, self.brain)
+        else:
+            names = tuple(names)
+            if not self.brain:
+                raise ValueError("ReducedFunctional(names=...) selects TumorGrowthBrain parameters")
+            bad = [n for n in names if n not in BRAIN_CONTROLS]
+            if bad or len(set(names)) != len(names) or len(names) != self.n_params:
+                raise ValueError("names: %d distinct parameters of %s expected, got %s" % (self.n_params, BRAIN_CONTROLS,
+                                                                                          names))
+            self.names, self.P = names, np.eye(len(names))
         self.terms_builder = terms_builder
         self.run_kwargs = dict(keep_nth=10 ** 9, save_method=None, clear_all=False, plot=False)
         self.run_kwargs.update(run_kwargs or {})

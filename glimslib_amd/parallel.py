@@ -350,17 +350,18 @@ class DistributedHandle:
     def adjoint_record(self, on=True):
         self.h.adjoint_record(on)
 
-    def adjoint_gradient(self, terms, n_labels=None, want_dc0=True):
+    def adjoint_gradient(self, terms, n_labels=None, want_dc0=True, elastic=False):
         """Handle.adjoint_gradient on the partitioned run: targets in GLOBAL node order ([n_global] or [n_global, dim]),
         localised here; J and the per-label arrays come back bitwise the same on every rank, dJ/dc0 all-gathered into the
-        global order (as get_state does)."""
+        global order (as get_state does).  elastic=True (on every rank alike) appends dJ/dE and dJ/dnu."""
         loc = []
         for t in terms:
             t = dict(t)
             bs = self.dim if t["kind"] in ("u_l2", _backend.MISFIT_U_L2) else 1
             t["target"] = self._local(t["target"], bs).reshape(-1)
             loc.append(t)
-        J, dD, drho, dgamma, dc0 = self.h.adjoint_gradient(loc, n_labels=n_labels, want_dc0=want_dc0)
+        res = self.h.adjoint_gradient(loc, n_labels=n_labels, want_dc0=want_dc0, elastic=elastic)
+        J, dD, drho, dgamma, dc0 = res[:5]
         if want_dc0:
             n_own = self.part.n_own
             parts = [None] * self.world
@@ -368,7 +369,7 @@ class DistributedHandle:
             dc0 = np.empty(self.n_global)
             for gid, v in parts:
                 dc0[gid] = v
-        return J, dD, drho, dgamma, dc0
+        return (J, dD, drho, dgamma, dc0) + tuple(res[5:])
 
     def adjoint_stats(self):
         return self.h.adjoint_stats()

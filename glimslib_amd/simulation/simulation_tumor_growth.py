@@ -294,8 +294,9 @@ class TumorGrowth(FenicsSimulation):
         self.solver = HipTimeStepSolver(self, h, mechanics)
 
     # -- discrete adjoint (the backward half of the reference's adjoint entry points) -----------------------------
-    def _adjoint_raw(self, terms, need_dD=True):
-        """(J, dD, drho, dgamma, dc0) per tissue label of the run recorded by ``run(record_adjoint=True)``."""
+    def _adjoint_raw(self, terms, need_dD=True, elastic=False):
+        """(J, dD, drho, dgamma, dc0) per tissue label of the run recorded by ``run(record_adjoint=True)``; with elastic=True
+        followed by (dE, dnu)."""
         h = self._backend
         if h is None or not hasattr(h, 'adjoint_gradient'):
             raise RuntimeError("adjoint_gradient needs a run(record_adjoint=True) first")
@@ -305,16 +306,17 @@ class TumorGrowth(FenicsSimulation):
             if np.any(np.asarray(flux) != 0.0):
                 raise NotImplementedError("adjoint_gradient: von Neumann data on the concentration scale with D; "
                                           "dJ/dD is not available for such a run")
-        return h.adjoint_gradient(terms)   # one entry per label of the handle's set_materials
+        return h.adjoint_gradient(terms, elastic=elastic)   # one entry per label of the handle's set_materials
 
     def adjoint_gradient(self, terms):
         """
         J and dJ/dm of the recorded run for the misfit ``terms`` (see ``Handle.adjoint_gradient``; the counterpart of
         fenics.ReducedFunctional(J, controls).derivative, image_based_optimization.py:700-708).  Returns
-        {'J', 'diffusion', 'proliferation', 'coupling' (per-label arrays: the tables of DiscontinuousScalar), 'c0'}.
+        {'J', 'diffusion', 'proliferation', 'coupling', 'E', 'poisson' (per-label arrays: the tables of DiscontinuousScalar),
+        'c0'}.  'E' and 'poisson' are 0 unless a term observes the displacement.
         """
-        J, dD, drho, dgamma, dc0 = self._adjoint_raw(terms)
-        return {'J': J, 'diffusion': dD, 'proliferation': drho, 'coupling': dgamma, 'c0': dc0}
+        J, dD, drho, dgamma, dc0, dE, dnu = self._adjoint_raw(terms, elastic=True)
+        return {'J': J, 'diffusion': dD, 'proliferation': drho, 'coupling': dgamma, 'E': dE, 'poisson': dnu, 'c0': dc0}
 
     # -- parameter sweeps (the forward half of the reference's adjoint entry points) -------------------------------
     def run_for_adjoint(self, parameters, output_dir=config.output_dir_simulation_tmp):

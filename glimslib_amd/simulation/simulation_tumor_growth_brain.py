@@ -75,13 +75,19 @@ class TumorGrowthBrain(TumorGrowth):
         return {v: k for k, v in getattr(sd, 'tissue_id_name_map', {}).items()}.get(name)
 
     def adjoint_gradient(self, terms):
-        """J and dJ/d(D_WM, D_GM, rho_WM, rho_GM, coupling) of the recorded run (see TumorGrowth.adjoint_gradient)."""
-        J, dD, drho, dgamma, dc0 = self._adjoint_raw(terms)
+        """J and dJ/d(D_WM, D_GM, rho_WM, rho_GM, coupling, E_GM, E_WM, E_CSF, E_VENT, nu_GM, nu_WM, nu_CSF, nu_VENT) of the
+        recorded run (see TumorGrowth.adjoint_gradient).  The fixed 'outside' material is no parameter and has no key."""
+        J, dD, drho, dgamma, dc0, dE, dnu = self._adjoint_raw(terms, elastic=True)
         wm, gm = self._tissue_id('WM'), self._tissue_id('GM')
         pick = lambda a, t: float(a[t]) if t is not None and t < len(a) else 0.0
-        return {'J': J, 'D_WM': pick(dD, wm), 'D_GM': pick(dD, gm), 'rho_WM': pick(drho, wm), 'rho_GM': pick(drho, gm),
-                # one global coupling constant on every tissue (_material_tables)
-                'coupling': float(np.sum(dgamma)), 'c0': dc0}
+        g = {'J': J, 'D_WM': pick(dD, wm), 'D_GM': pick(dD, gm), 'rho_WM': pick(drho, wm), 'rho_GM': pick(drho, gm),
+             # one global coupling constant on every tissue (_material_tables)
+             'coupling': float(np.sum(dgamma)), 'c0': dc0}
+        for suffix, tissue in (('GM', 'GM'), ('WM', 'WM'), ('CSF', 'CSF'), ('VENT', 'Ventricles')):
+            t = self._tissue_id(tissue)
+            g['E_' + suffix] = pick(dE, t)
+            g['nu_' + suffix] = pick(dnu, t)
+        return g
 
     def run_for_adjoint(self, parameters, output_dir=config.output_dir_simulation_tmp):
         """:127-145 -- (D_WM, D_GM, rho_WM, rho_GM, coupling)"""

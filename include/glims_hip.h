@@ -457,6 +457,22 @@ typedef struct glims_misfit {
 int glims_adjoint_gradient(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J, double* dJ_dD,
                            double* dJ_drho, double* dJ_dgamma, double* dJ_dc0);
 
+/* glims_adjoint_gradient plus dJ_dE / dJ_dnu [n_labels of glims_set_materials], the derivatives with respect to the per-label
+ * Young's modulus and Poisson ratio (glims_adjoint_gradient is this call with both NULL; any output except J may be NULL).
+ * K_el and G are linear in each cell's Lame pair (mu_t, lam_t), so with u_k = K_el^-1 (G c_k + f) (its Dirichlet values in
+ * place) and mu_k = K_el^-1 dJ/du_k (0 on the constrained dofs) at every step k that a GLIMS_MISFIT_U_L2 term observes:
+ *   dJ/dp_t = sum_k mu_k^T (dG/dp c_k - dK/dp u_k) = gamma_t (2 mu' + d lam') C_t - (2 mu' A_t + lam' B_t),
+ *   A_t = sum_k int_t eps(mu_k):eps(u_k),  B_t = sum_k int_t div mu_k div u_k,  C_t = sum_k int_t 1/(d+1) div mu_k sum_a c_k,a
+ * (C_t per cell |T|/(d+1) div mu_k times the sum of c_k over its vertices), with
+ *   p = E_t:   mu' = 1 / (2 (1 + nu)),        lam' = nu / ((1 + nu)(1 - 2 nu))
+ *   p = nu_t:  mu' = -E / (2 (1 + nu)^2),     lam' = E (1 + 2 nu^2) / ((1 + nu)^2 (1 - 2 nu)^2).
+ * A term list without GLIMS_MISFIT_U_L2 gives dJ_dE = dJ_dnu = 0 exactly.  The E / nu pass (one per-cell pass per observed
+ * displacement step) runs only when dJ_dE or dJ_dnu is non-NULL; it adds no elastic solve, and the other outputs keep their
+ * bits.  Collective on partitioned handles like glims_adjoint_gradient: every rank passes NULL or non-NULL dJ_dE / dJ_dnu
+ * alike (GLIMS_E_USAGE on every rank otherwise); dJ_dE and dJ_dnu are bitwise the same on every rank. */
+int glims_adjoint_gradient_full(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J, double* dJ_dD,
+                                double* dJ_drho, double* dJ_dgamma, double* dJ_dc0, double* dJ_dE, double* dJ_dnu);
+
 /* Counters of the adjoint (not in glims_stats, whose layout is fixed): out[0] gradient calls, [1] backward steps,
  * [2] RD adjoint PCG iterations, [3] elastic solves, [4] their PCG iterations, [5] recorded states held now;
  * ms[0] wall time of the backward sweeps (may be NULL). */
