@@ -1,14 +1,20 @@
 #!/usr/bin/env python3
 """
 bench.py -- DoF-updates/s of the implicit reaction-diffusion time step on a 3-D brain-extent mesh, plus the
-HBM roofline fraction of the diffusion SpMV and a CPU baseline, as ONE JSON line on rank 0.
+HBM roofline fraction of the diffusion SpMV, as ONE JSON line on rank 0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c3|c2] [--n CELLS_PER_EDGE]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c3|c2] [--n CELLS_PER_EDGE] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 A "step" is one backward-Euler step of the concentration equation (Newton + Jacobi-PCG) over the whole mesh.
 N > 1: the SAME mesh is partitioned over N GPUs (strong scaling), halo exchange + all-reduce over RCCL.
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: everything on it was
+measured by those steps (headline, solver counts, the in-step roofline figures, per-rank figures).  --full adds what
+takes runs of its own or comes from other runs: the kernel pass after the timed steps, the isolated SpMV launches, the
+streaming ceiling, the fp32-Jacobian pass, the alt.* configurations, the CPU baselines and the committed PMC and
+full-run figures.
 """
 from __future__ import annotations
 
@@ -487,7 +493,7 @@ def alt_unstructured(Handle, device, steps=20, warmup=5, n_points=1000000):
     return out
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -495,9 +501,12 @@ def main():
     ap.add_argument("--workload", default=os.environ.get("GLIMS_BENCH_WORKLOAD", "c4"))
     ap.add_argument("--size", "--n", dest="n", type=int, default=0,
                     help="cells per edge (overrides the workload's size); use --size under torchrun, which claims --n*")
-    ap.add_argument("--spmv-reps", type=int, default=50)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-alt", action="store_true", help="skip the informational fp32-Jacobian-storage pass")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what takes runs of its own (per-kernel pass, isolated SpMV, "
+                         "streaming ceiling, alt.* passes, CPU baselines) and quote the committed PMC / full-run figures")
+    ap.add_argument("--spmv-reps", type=int, default=50, help="isolated SpMV launches (--full only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-alt", action="store_true", help="--full without the informational alt.* passes")
     ap.add_argument("--extrapolate", type=int, default=0)
     ap.add_argument("--cg-rtol", type=float, default=None, help="override glims_options.cg_rtol (tuning runs only)")
     ap.add_argument("--check-every", type=int, default=None)
@@ -515,7 +524,11 @@ def main():
                          "the residual after a solve from the quadratic structure)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the state they computed as DIR/<name>.npy (float64, <= 64 MB in all)")
-    args = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main():
+    args = parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
@@ -688,9 +701,9 @@ def main():
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, h, coupled, dim, n_global, part, dist, rank, world)
     # the other two hot kernels (assembly sweep, PCG vector update): event pairs around every launch of theirs cost
-    # ~0.1 ms per step at 1 M rows, so they are timed in a short pass of their own right after the timed region
+    # ~0.1 ms per step at 1 M rows, so they are timed in a short pass of their own right after the timed region (--full)
     st_k = None
-    if world == 1 and status == GLIMS_OK and not coupled:
+    if args.full and world == 1 and status == GLIMS_OK and not coupled:
         k_steps = max(2, min(5, args.steps))
         h.set_options(time_kernels=2)
         h.reset_stats()
@@ -708,11 +721,13 @@ def main():
     # rd_linear = PCG).  Algorithmic bytes per launch = SURVEY 8(d)'s CSR figure 12 nnz + 20 rows for the SpMV, plus the
     # recurrence's 32 B per row of extra vector traffic for k_cheb (cheb_bytes);
     # duration (a) inside the timed region: HIP events attached to every such launch of the steps (glims_options.time_kernels),
-    # (b) after it: `spmv_reps` back-to-back launches of the plain SpMV (glims_apply).
-    x = np.random.default_rng(0).standard_normal(h.n_nodes)
-    h.apply(0, x, reps=5)
-    _, ms = h.apply(0, x, reps=args.spmv_reps)
-    t_isolated = ms * 1e-3 / args.spmv_reps
+    # (b) after it: `spmv_reps` back-to-back launches of the plain SpMV (glims_apply; --full only, a plain run has no (b)).
+    t_isolated = None
+    if args.full:
+        x = np.random.default_rng(0).standard_normal(h.n_nodes)
+        h.apply(0, x, reps=5)
+        _, ms = h.apply(0, x, reps=args.spmv_reps)
+        t_isolated = ms * 1e-3 / args.spmv_reps
     cheb_dominant = st.get('n_cheb_steps', 0) > 0 and st['ms_cheb_steps'] >= st['ms_spmv_steps']
     in_step = cheb_dominant or st.get('n_spmv_steps', 0) > 0
     if cheb_dominant:
@@ -724,15 +739,15 @@ def main():
         b_alg = workloads.b_spmv_bytes(st['nnz'], st['n_rows'])
         n_timed, med_us = int(st['n_spmv_steps']), st['us_spmv_median']
     else:
-        t_op = t_isolated
+        t_op = t_isolated                                  # None in a plain run: no operator launch was timed
         b_alg = workloads.b_spmv_bytes(st['nnz'], st['n_rows'])
-        n_timed, med_us = args.spmv_reps, None
-    achieved = b_alg / t_op / 1e9
+        n_timed, med_us = (args.spmv_reps if args.full else 0), None
+    achieved = None if t_op is None else b_alg / t_op / 1e9
     # HBM-side bytes per launch from the PMC passes (FETCH_SIZE x2 on gfx950 + WRITE_SIZE, separate rocprofv3 runs,
     # calibrated on kernels with exactly known byte counts).  A LOOKUP into the committed summary of those passes, not
-    # a measurement of this run: only reported when this run's operator is the one the passes measured, and
+    # a measurement of this run (--full only): only reported when this run's operator is the one the passes measured, and
     # `traffic_source` names the file.
-    pmc, pmc_file = load_pmc(st, ("r05_c_pmc_c4.json", "r05_a_pmc_c4.json")) if world == 1 else (None, None)
+    pmc, pmc_file = load_pmc(st, ("r05_c_pmc_c4.json", "r05_a_pmc_c4.json")) if world == 1 and args.full else (None, None)
     unr = 16 if args.workload.lower() in ("bl", "brain_like", "brain-like", "u", "unstructured") else 8
     traffic = pmc_lookup(pmc, "k_cheb" if cheb_dominant else "k_spmv<1" if in_step else "k_spmv<0")
     steps_n = max(1, steps_done)
@@ -741,7 +756,7 @@ def main():
     dom_name = ("k_cheb<%d, %d, 1, double>" % (unr, st['stream_nontemporal'])) if cheb_dominant else \
                ("k_spmv<%d, %d, %d, 1, double>" % (1 if in_step else 0, unr, st['stream_nontemporal']))
     roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                "frac": None if achieved is None else achieved / HBM_PEAK_GBS, "traffic": traffic,
                 "traffic_source": None if traffic is None else
                 "lookup, not measured in this run: %s (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of the same "
                 "operator, tools/pmc_summary.py)" % pmc_file,
@@ -752,42 +767,44 @@ def main():
                                       if cheb_dominant else
                                       " (SELL-64, fp64 values, columns streamed as 16-bit window codes; algorithmic bytes "
                                       "still count 4-byte CSR columns: 12 nnz + 20 rows)"),
-                "algorithmic_bytes_per_launch": b_alg, "avg_launch_us": t_op * 1e6,
+                "algorithmic_bytes_per_launch": b_alg, "avg_launch_us": None if t_op is None else t_op * 1e6,
                 "median_launch_us": med_us, "launches_timed": n_timed,
                 "timed": "HIP events attached to the launches inside the timed steps" if in_step
-                         else "back-to-back launches after the timed steps (k_spmv<0,..>)",
-                "isolated_spmv_launch_us": t_isolated * 1e6,
+                         else "back-to-back launches after the timed steps (k_spmv<0,..>)" if args.full
+                         else "no operator launch inside the timed steps (the isolated launches are --full only)",
+                "isolated_spmv_launch_us": None if t_isolated is None else t_isolated * 1e6,
                 "kernels": kernels}
 
     # practical HBM ceiling of THIS device next to the nominal peak: streaming scale kernel y = 2 x over
     # 1 GiB, read + write bytes over the HIP-event time of the fastest of 10 launches (torch is only the allocator / launcher here;
-    # its memcpy path goes through the copy engines and is much slower than a kernel)
-    try:
-        src = torch.empty(1 << 27, dtype=torch.float64, device="cuda")
-        dst = torch.empty_like(src)
-        src.fill_(1.0)
-        torch.mul(src, 2.0, out=dst)
-        best = None
-        for _ in range(10):                     # one event pair per launch, fastest launch counts
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record()
+    # its memcpy path goes through the copy engines and is much slower than a kernel); --full only
+    if args.full:
+        try:
+            src = torch.empty(1 << 27, dtype=torch.float64, device="cuda")
+            dst = torch.empty_like(src)
+            src.fill_(1.0)
             torch.mul(src, 2.0, out=dst)
-            e1.record()
-            torch.cuda.synchronize()
-            t = e0.elapsed_time(e1) * 1e-3
-            best = t if best is None else min(best, t)
-        roofline["stream_ceiling"] = 2.0 * src.numel() * 8 / best / 1e9
-        del src, dst
-    except Exception:   # noqa: BLE001 -- informational only
-        roofline["stream_ceiling"] = None
+            best = None
+            for _ in range(10):                     # one event pair per launch, fastest launch counts
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                torch.mul(src, 2.0, out=dst)
+                e1.record()
+                torch.cuda.synchronize()
+                t = e0.elapsed_time(e1) * 1e-3
+                best = t if best is None else min(best, t)
+            roofline["stream_ceiling"] = 2.0 * src.numel() * 8 / best / 1e9
+            del src, dst
+        except Exception:   # noqa: BLE001 -- informational only
+            roofline["stream_ceiling"] = None
 
     # ---- informational: the same K steps with GLIMS_FLAG_FP32_JACOBIAN (A(c) stored / streamed in single precision
     # inside the Krylov solves; Newton residual, sums and every vector stay fp64).  OFF by default and NOT the headline:
     # reported next to it, with the distance between the two concentration fields after the same number of steps, so
     # that the decision about the default can be taken from measured numbers.
     alt = None
-    if world == 1 and not coupled and status == GLIMS_OK and not args.fp32_jacobian and not args.no_alt:
+    if args.full and world == 1 and not coupled and status == GLIMS_OK and not args.fp32_jacobian and not args.no_alt:
         try:
             n_post = st_k['_steps'] if st_k is not None else 0
             c_ref = h.get_state(want_u=False)[0].copy()          # default build after W + K + n_post steps
@@ -819,7 +836,7 @@ def main():
 
     # ---- informational, after the headline region: BASELINE configs C2 (a stiff step -> multigrid-preconditioned RD
     # solves) and C5 (coupled, 1 M nodes) under the same clock, each a few seconds; the headline handle is released first
-    if world == 1 and not args.no_alt and args.workload.lower() == "c4" and not args.n:
+    if args.full and world == 1 and not args.no_alt and args.workload.lower() == "c4" and not args.n:
         h.close()
         head_ns = 1e9 * elapsed / max(1, steps_done) / n_global if status == GLIMS_OK else None
         for key, fn in (("rank_sized", lambda H, d: alt_rank_sized(H, d, head_ns)),
@@ -911,7 +928,7 @@ def main():
         }
         # The config's FULL length (test_case_comparison_3D_atlas.py:84: 500 steps) as measured on this path by tools/run_long.py:
         # scalar keys read from the committed summary, quoted only while the library's sources are the ones that run measured
-        if args.workload.lower() == "c4" and not args.n and not coupled:
+        if args.full and args.workload.lower() == "c4" and not args.n and not coupled:
             try:
                 fr = json.load(open(os.path.join(HERE, "profiles", "long_c4_run.json")))
                 if fr.get("kernels_sha16") == kernels_sha16():
@@ -930,7 +947,7 @@ def main():
             out["ranks"] = ranks_info
         if alt is not None:
             out["alt"] = alt
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(None if coupled else w)
             try:
                 out["cpu_baseline"]["reference_like"] = cpu_reference_like()
