@@ -129,6 +129,8 @@ SIGNATURES = {
     "glims_adjoint_record": (C.c_int, [_h, C.c_int]),
     "glims_adjoint_gradient": (C.c_int, [_h, C.c_int, C.POINTER(Misfit), _dp, _dp, _dp, _dp, _dp]),
     "glims_adjoint_gradient_full": (C.c_int, [_h, C.c_int, C.POINTER(Misfit), _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "glims_adjoint_hessian": (C.c_int, [_h, C.c_int, C.POINTER(Misfit), C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                                        _dp, _dp, _dp, _dp, _dp, _dp]),
     "glims_adjoint_stats": (C.c_int, [_h, _i64p, _dp]),
     "glims_comm_unique_id": (C.c_int, [C.c_char_p]),
     "glims_comm_init": (C.c_int, [_h, C.c_int, C.c_int, C.c_char_p]),
@@ -358,17 +360,8 @@ class Handle:
         if n_labels is not None and int(n_labels) != self.n_labels:
             raise ValueError("adjoint_gradient: n_labels = %d, but set_materials gave %d labels" % (n_labels, self.n_labels))
         n_labels = self.n_labels
-        kinds = {"c_l2": MISFIT_C_L2, "c_thresh": MISFIT_C_THRESH, "u_l2": MISFIT_U_L2}
         terms = list(terms)
-        arr = (Misfit * max(1, len(terms)))()
-        keep = []
-        for k, t in enumerate(terms):
-            kind = kinds.get(t["kind"], t["kind"])
-            n = self.n_nodes * (self.dim if kind == MISFIT_U_L2 else 1)
-            tg = _f64(np.asarray(t["target"]).reshape(-1), (n,))
-            keep.append(tg)
-            arr[k] = Misfit(int(t["step"]), int(kind), float(t.get("level", 0.0)), float(t.get("smooth", 1.0)),
-                            float(t.get("weight", 1.0)), _ptr(tg, _dp))
+        arr, keep = self._misfit_array(terms)   # (keep: the target arrays the structs point into)
         J = C.c_double(0.0)
         out = [np.zeros(int(n_labels)) for _ in range(5 if elastic else 3)]
         dc0 = np.zeros(self.n_nodes) if want_dc0 else None
@@ -380,6 +373,58 @@ class Handle:
         self._check(self.lib.glims_adjoint_gradient(self._h, len(terms), arr, C.byref(J), *[_ptr(a, _dp) for a in out],
                                                     _ptr(dc0, _dp)))
         return (J.value, out[0], out[1], out[2], dc0)
+
+    def _misfit_array(self, terms):
+        """ctypes array of glims_misfit for the term dicts, and the target arrays it points into (keep them alive)."""
+        kinds = {"c_l2": MISFIT_C_L2, "c_thresh": MISFIT_C_THRESH, "u_l2": MISFIT_U_L2}
+        arr = (Misfit * max(1, len(terms)))()
+        keep = []
+        for k, t in enumerate(terms):
+            kind = kinds.get(t["kind"], t["kind"])
+            n = self.n_nodes * (self.dim if kind == MISFIT_U_L2 else 1)
+            tg = _f64(np.asarray(t["target"]).reshape(-1), (n,))
+            keep.append(tg)
+            arr[k] = Misfit(int(t["step"]), int(kind), float(t.get("level", 0.0)), float(t.get("smooth", 1.0)),
+                            float(t.get("weight", 1.0)), _ptr(tg, _dp))
+        return arr, keep
+
+    def adjoint_hessian(self, terms, directions, n_labels=None):
+        """glims_adjoint_hessian: J, the gradient and the Hessian-vector products of the recorded run for the misfit ``terms``
+        (as in adjoint_gradient) along 1 .. 8 ``directions``, each a dict {'D', 'rho', 'gamma' ([n_labels] or a scalar for
+        every label), 'c0' ([n_nodes], caller's order)} whose missing keys are 0.  Returns a dict {'J', 'D', 'rho', 'gamma',
+        'c0' (the gradient, as adjoint_gradient), 'hv_D', 'hv_rho', 'hv_gamma' ([n_dir, n_labels]), 'hv_c0' ([n_dir, n_nodes]),
+        'stats' (tangent-linear / second-order PCG iterations, extra elastic solves, ms)}."""
+        if self.n_labels is None:
+            raise ValueError("adjoint_hessian before set_materials")
+        if n_labels is not None and int(n_labels) != self.n_labels:
+            raise ValueError("adjoint_hessian: n_labels = %d, but set_materials gave %d labels" % (n_labels, self.n_labels))
+        L, n = self.n_labels, self.n_nodes
+        directions = list(directions)
+        P = len(directions)
+        terms = list(terms)
+        arr, keep = self._misfit_array(terms)
+
+        def table(key, size):
+            if not any(key in d for d in directions):
+                return None
+            t = np.zeros((max(1, P), size))
+            for p, d in enumerate(directions):
+                if d.get(key) is not None:
+                    t[p] = np.broadcast_to(np.asarray(d[key], dtype=np.float64), (size,))
+            return _f64(t)
+
+        dirs = [table("D", L), table("rho", L), table("gamma", L), table("c0", n)]
+        J = C.c_double(0.0)
+        g = [np.zeros(L) for _ in range(3)] + [np.zeros(n)]
+        hv = [np.zeros((max(1, P), L)) for _ in range(3)] + [np.zeros((max(1, P), n))]
+        st = np.zeros(4)
+        self._check(self.lib.glims_adjoint_hessian(self._h, len(terms), arr, int(P), *[_ptr(d, _dp) for d in dirs],
+                                                   C.byref(J), *[_ptr(a, _dp) for a in g], *[_ptr(a, _dp) for a in hv],
+                                                   _ptr(st, _dp)))
+        del keep
+        return {"J": J.value, "D": g[0], "rho": g[1], "gamma": g[2], "c0": g[3], "hv_D": hv[0][:P], "hv_rho": hv[1][:P],
+                "hv_gamma": hv[2][:P], "hv_c0": hv[3][:P],
+                "stats": {"tlm_pcg_its": int(st[0]), "soa_pcg_its": int(st[1]), "mech_solves": int(st[2]), "ms": st[3]}}
 
     def adjoint_stats(self):
         a = np.zeros(6, dtype=np.int64)

@@ -428,14 +428,11 @@ int solve_elastic(glims_ctx* h, AdjWork& wk, const double* rhs, double* x, const
   return cs;
 }
 
+// the work vectors, targets (internal numbering) and cell-vertex map of one gradient / Hessian call
 template <int D>
-int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_out, double* dD, double* drho,
-               double* dgamma, double* dc0, double* dE, double* dnu) {
+void adjoint_setup(glims_ctx* h, int n_terms, const glims_misfit* terms, bool elastic, AdjWork& wk) {
   AdjointState& a = h->adj;
   const int64_t n = h->n_own, nn = h->n_nodes, nd = nn * D;
-  const int N = (int)a.traj.size() - 1;
-  const double t0 = omp_get_wtime();
-  AdjWork wk;
   const size_t ne = (size_t)h->pat.total_entries;
   wk.vA.alloc(ne);
   wk.dinv.alloc((size_t)nn);
@@ -444,7 +441,6 @@ int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_o
   wk.qcell.alloc_zero((size_t)h->n_cells, h->st);
   wk.part.alloc_zero((size_t)GL_ADJ_BLOCKS * GL_ADJ_LT * 2, h->st);
   wk.sums.alloc_zero((size_t)GL_MAX_LABELS * 3, h->st);
-  const bool elastic = dE || dnu;   // the E / nu pass runs only when asked for
   if (elastic) wk.esums.alloc_zero((size_t)GL_MAX_LABELS * 2, h->st);
   wk.stage.alloc_zero((size_t)nd, h->st);
   bool any_u = false;
@@ -486,6 +482,18 @@ int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_o
       GL_HIP(hipStreamSynchronize(h->st));   // d_gown goes out of scope
     }
   }
+}
+
+template <int D>
+int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_out, double* dD, double* drho,
+               double* dgamma, double* dc0, double* dE, double* dnu) {
+  AdjointState& a = h->adj;
+  const int64_t n = h->n_own, nn = h->n_nodes, nd = nn * D;
+  const int N = (int)a.traj.size() - 1;
+  const double t0 = omp_get_wtime();
+  AdjWork wk;
+  const bool elastic = dE || dnu;   // the E / nu pass runs only when asked for
+  adjoint_setup<D>(h, n_terms, terms, elastic, wk);
   ForwardGuard guard(h, wk);
   const uint8_t* fxc = h->have_fixed_c ? h->fixed_c.p : nullptr;
   const bool rd_mg = h->rd_precond_active == GLIMS_RD_PRECOND_MULTIGRID;
@@ -648,6 +656,881 @@ int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_o
   return status;
 }
 
+// ---- second order: Hessian-vector products ("Second order") ----------------------------------------
+// P <= GL_HESS_MAXDIR directions per call.  Per-label direction tables dir[p][3][GL_MAX_LABELS] = (dD, drho, dgamma); node
+// vectors of the directions are stored column after column, [p][n_nodes].  Every column runs through the same arithmetic
+// whatever P is: column p of a P-direction call has the bits of a one-direction call.
+constexpr int GL_HESS_MAXDIR = 8;
+
+// Row-owned right-hand-side terms of the tangent-linear (MODE 0) and the second-order adjoint (MODE 1) solves, P columns per
+// launch, atomics-free through the incidence lists (each row adds its cells' shares in list order).  Cell T of label t,
+// vertex i = the row, f3 / f2 as in k_sens:
+//   MODE 0:  y_p[i] += -dt (dD_p[t] int_T grad c . grad phi_i + drho_p[t] int_T (c^2 - c) phi_i)
+//   MODE 1:  y_p[i] += -dt (2 rho_t int_T dc_p lam phi_i + dD_p[t] int_T grad lam . grad phi_i
+//                           + drho_p[t] int_T (2c - 1) lam phi_i)
+// Bytes per row and incidence: the slot word, cell id, geometry record and label as in the assembly; the gathered c / lam /
+// dc_p values mostly hit the caches.
+template <int D, int MODE>
+__global__ __launch_bounds__(256) void k_hess_rows(int64_t n_own, int P, int64_t ld, const int64_t* __restrict__ cslice_ptr,
+                                                   const uint32_t* __restrict__ cslots, const int32_t* __restrict__ celem,
+                                                   const uint8_t* __restrict__ diag_k, const int32_t* __restrict__ cell_nodes,
+                                                   const double* __restrict__ egeo, const uint8_t* __restrict__ label,
+                                                   const double* __restrict__ mat, const double* __restrict__ dir, double dt,
+                                                   const double* __restrict__ c, const double* __restrict__ lam,
+                                                   const double* __restrict__ dc, double* __restrict__ y) {
+  constexpr int NV = D + 1, GE = 1 + NV * D;
+  constexpr double f3 = D == 2 ? 1.0 / 60.0 : 1.0 / 120.0;   // d! / (d+3)!
+  constexpr double f2 = D == 2 ? 1.0 / 12.0 : 1.0 / 20.0;    // d! / (d+2)!
+  const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= n_own) return;
+  const int64_t s = row >> 6, lane = row & 63;
+  const int64_t cbase = cslice_ptr[s];
+  const int clen = (int)((cslice_ptr[s + 1] - cbase) >> 6);
+  const uint32_t dk = diag_k[row];
+  double acc[GL_HESS_MAXDIR];
+#pragma unroll
+  for (int p = 0; p < GL_HESS_MAXDIR; ++p) acc[p] = 0.0;
+  for (int q = 0; q < clen; ++q) {
+    const int64_t ci = cbase + (int64_t)q * GL_WAVE + lane;
+    const int32_t e = celem[ci];
+    if (e < 0) continue;
+    const uint32_t sl = cslots[ci];
+    const double* g = egeo + (int64_t)e * GE;
+    const double vol = g[0];
+    const int lab = label[e];
+    double gi[D];   // grad phi_i (the row's vertex of the cell)
+#pragma unroll
+    for (int a = 0; a < D; ++a) gi[a] = 0.0;
+#pragma unroll
+    for (int m = 0; m < NV; ++m)
+      if (((sl >> (8 * m)) & 255u) == dk)
+#pragma unroll
+        for (int a = 0; a < D; ++a) gi[a] = g[1 + m * D + a];
+    int nd[NV];
+    double cv[NV], gg[NV];   // gg[m] = grad phi_m . grad phi_i
+    double Sc = 0.0, cc = 0.0;
+#pragma unroll
+    for (int m = 0; m < NV; ++m) {
+      nd[m] = cell_nodes[(int64_t)e * NV + m];
+      cv[m] = c[nd[m]];
+      Sc += cv[m];
+      cc += cv[m] * cv[m];
+      double t = 0.0;
+#pragma unroll
+      for (int a = 0; a < D; ++a) t += g[1 + m * D + a] * gi[a];
+      gg[m] = t;
+    }
+    const double c_i = c[row];
+    if (MODE == 0) {
+      double Kc = 0.0;
+#pragma unroll
+      for (int m = 0; m < NV; ++m) Kc += cv[m] * gg[m];
+      Kc *= vol;
+      // sum_{jk} c_j c_k prod(alpha!) with i fixed = Sc^2 + c.c + 2 c_i Sc + 2 c_i^2;  sum_j c_j (1 + delta_ij) = Sc + c_i
+      const double Nc = vol * (f3 * (Sc * Sc + cc + 2.0 * c_i * Sc + 2.0 * c_i * c_i) - f2 * (Sc + c_i));
+#pragma unroll
+      for (int p = 0; p < GL_HESS_MAXDIR; ++p)
+        if (p < P) {
+          const double* dp = dir + (size_t)p * 3 * GL_MAX_LABELS;
+          acc[p] += -dt * (dp[lab] * Kc + dp[GL_MAX_LABELS + lab] * Nc);
+        }
+    } else {
+      double lv[NV], Sl = 0.0, Kl = 0.0, cl = 0.0;
+#pragma unroll
+      for (int m = 0; m < NV; ++m) {
+        lv[m] = lam[nd[m]];
+        Sl += lv[m];
+        Kl += lv[m] * gg[m];
+        cl += cv[m] * lv[m];
+      }
+      Kl *= vol;
+      const double l_i = lam[row];
+      const double Q = vol * (2.0 * f3 * (Sc * Sl + cl + c_i * Sl + l_i * Sc + 2.0 * c_i * l_i) - f2 * (Sl + l_i));
+      const double rho = mat[GL_MAX_LABELS + lab];
+#pragma unroll
+      for (int p = 0; p < GL_HESS_MAXDIR; ++p)
+        if (p < P) {
+          const double* dcp = dc + (size_t)p * ld;
+          double Sd = 0.0, dl = 0.0;
+#pragma unroll
+          for (int m = 0; m < NV; ++m) {
+            const double dv = dcp[nd[m]];
+            Sd += dv;
+            dl += dv * lv[m];
+          }
+          const double d_i = dcp[row];
+          const double R = vol * f3 * (Sd * Sl + dl + d_i * Sl + l_i * Sd + 2.0 * d_i * l_i);
+          const double* dp = dir + (size_t)p * 3 * GL_MAX_LABELS;
+          acc[p] += -dt * (2.0 * rho * R + dp[lab] * Kl + dp[GL_MAX_LABELS + lab] * Q);
+        }
+    }
+  }
+#pragma unroll
+  for (int p = 0; p < GL_HESS_MAXDIR; ++p)
+    if (p < P) y[(size_t)p * ld + row] += acc[p];
+}
+
+// Per-label Hessian sums of one direction, the layout, grid and fixed-order reduction of k_sens (then k_sens_final):
+//   q0 = int_T grad nu . grad c + grad lam . grad dc,   q1 = int_T nu (c^2 - c) + lam (2c - 1) dc   (exact for P1)
+template <int D>
+__global__ __launch_bounds__(256) void k_hsens(int64_t n_cells, int l0, const int32_t* __restrict__ cell_nodes,
+                                               const double* __restrict__ egeo, const uint8_t* __restrict__ label,
+                                               const double* __restrict__ c, const double* __restrict__ lam,
+                                               const double* __restrict__ dc, const double* __restrict__ nu,
+                                               double* __restrict__ partials) {
+  constexpr int NV = D + 1, GE = 1 + NV * D;
+  constexpr double f3 = D == 2 ? 1.0 / 60.0 : 1.0 / 120.0;
+  constexpr double f2 = D == 2 ? 1.0 / 12.0 : 1.0 / 20.0;
+  double acc[GL_ADJ_LT][2];
+#pragma unroll
+  for (int j = 0; j < GL_ADJ_LT; ++j) acc[j][0] = acc[j][1] = 0.0;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n_cells; e += stride) {
+    const int j = label[e] - l0;
+    if (j < 0 || j >= GL_ADJ_LT) continue;
+    const double* g = egeo + e * GE;
+    const double vol = g[0];
+    double gc[D] = {0.0}, gl[D] = {0.0}, gd[D] = {0.0}, gv[D] = {0.0};
+    double Sc = 0.0, Sl = 0.0, Sd = 0.0, Sv = 0.0, cc = 0.0, vc = 0.0, vcc = 0.0, cd = 0.0, ld = 0.0, lc = 0.0, lcd = 0.0;
+#pragma unroll
+    for (int m = 0; m < NV; ++m) {
+      const int64_t k = cell_nodes[e * NV + m];
+      const double cm = c[k], lm = lam[k], dm = dc[k], vm = nu[k];
+#pragma unroll
+      for (int a = 0; a < D; ++a) {
+        const double gm = g[1 + m * D + a];
+        gc[a] += cm * gm;
+        gl[a] += lm * gm;
+        gd[a] += dm * gm;
+        gv[a] += vm * gm;
+      }
+      Sc += cm;
+      Sl += lm;
+      Sd += dm;
+      Sv += vm;
+      cc += cm * cm;
+      vc += vm * cm;
+      vcc += vm * cm * cm;
+      cd += cm * dm;
+      ld += lm * dm;
+      lc += lm * cm;
+      lcd += lm * cm * dm;
+    }
+    double gg = 0.0;
+#pragma unroll
+    for (int a = 0; a < D; ++a) gg += gv[a] * gc[a] + gl[a] * gd[a];
+    const double a0 = vol * gg;
+    // sum_{abc} x_a y_b z_c prod(alpha!) = Sx Sy Sz + Sx (y.z) + Sy (x.z) + Sz (x.y) + 2 sum x y z
+    const double a1 = vol * (f3 * (Sv * Sc * Sc + 2.0 * Sc * vc + Sv * cc + 2.0 * vcc) - f2 * (Sv * Sc + vc) +
+                             2.0 * f3 * (Sl * Sc * Sd + Sl * cd + Sc * ld + Sd * lc + 2.0 * lcd) - f2 * (Sl * Sd + ld));
+#pragma unroll
+    for (int q = 0; q < GL_ADJ_LT; ++q)
+      if (q == j) {
+        acc[q][0] += a0;
+        acc[q][1] += a1;
+      }
+  }
+  __shared__ double sm[4][GL_ADJ_LT * 2];
+  const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+  for (int q = 0; q < GL_ADJ_LT; ++q)
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const double t = wsum(acc[q][k]);
+      if (lane == 0) sm[wid][q * 2 + k] = t;
+    }
+  __syncthreads();
+  if (threadIdx.x < GL_ADJ_LT * 2) {
+    const int t = threadIdx.x;
+    partials[(size_t)blockIdx.x * GL_ADJ_LT * 2 + t] = (sm[0][t] + sm[1][t]) + (sm[2][t] + sm[3][t]);
+  }
+}
+
+// y[row][a] = (G dc + sum_t dgamma_t G_t c)[row][a] = sum over the row's cells of
+//   (2 mu_T + d lam_T) |T| / (d+1) (gamma_T sum_m dc_m + dgamma_T sum_m c_m) dphi_row / dx_a     (owned rows; row-owned)
+template <int D>
+__global__ void k_gdir_rows(int64_t n_own, const int64_t* __restrict__ cslice_ptr, const uint32_t* __restrict__ cslots,
+                            const int32_t* __restrict__ celem, const uint8_t* __restrict__ diag_k,
+                            const int32_t* __restrict__ cell_nodes, const double* __restrict__ egeo,
+                            const uint8_t* __restrict__ label, const double* __restrict__ mat,
+                            const double* __restrict__ dgam, const double* __restrict__ c, const double* __restrict__ dc,
+                            double* __restrict__ y) {
+  constexpr int NV = D + 1, GE = 1 + NV * D;
+  const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= n_own) return;
+  const int64_t s = row >> 6, lane = row & 63;
+  const int64_t cbase = cslice_ptr[s];
+  const int clen = (int)((cslice_ptr[s + 1] - cbase) >> 6);
+  const uint32_t dk = diag_k[row];
+  double acc[D];
+#pragma unroll
+  for (int a = 0; a < D; ++a) acc[a] = 0.0;
+  for (int q = 0; q < clen; ++q) {
+    const int64_t ci = cbase + (int64_t)q * GL_WAVE + lane;
+    const int32_t e = celem[ci];
+    if (e < 0) continue;
+    const uint32_t sl = cslots[ci];
+    const double* g = egeo + (int64_t)e * GE;
+    const int lab = label[e];
+    double Sc = 0.0, Sd = 0.0;
+#pragma unroll
+    for (int m = 0; m < NV; ++m) {
+      const int32_t k = cell_nodes[(int64_t)e * NV + m];
+      Sc += c[k];
+      Sd += dc[k];
+    }
+    const double mu = mat[3 * GL_MAX_LABELS + lab], lam = mat[4 * GL_MAX_LABELS + lab];
+    const double w = (2.0 * mu + D * lam) * g[0] * (1.0 / (D + 1)) * (mat[2 * GL_MAX_LABELS + lab] * Sd + dgam[lab] * Sc);
+#pragma unroll
+    for (int m = 0; m < NV; ++m)
+      if (((sl >> (8 * m)) & 255u) == dk)
+#pragma unroll
+        for (int a = 0; a < D; ++a) acc[a] += w * g[1 + m * D + a];
+  }
+#pragma unroll
+  for (int a = 0; a < D; ++a) y[row * D + a] = acc[a];
+}
+
+// h'(c) and h''(c) of a concentration term (1 and 0 for C_L2)
+__device__ __forceinline__ void misfit_derivs(int kind, double level, double smooth, double c, double* hp, double* h2) {
+  if (kind == GLIMS_MISFIT_C_THRESH) {
+    const double th = tanh((c - level) / smooth);
+    *hp = 0.5 * (1.0 - th * th) / smooth;
+    *h2 = -th * (1.0 - th * th) / (smooth * smooth);
+  } else {
+    *hp = 1.0;
+    *h2 = 0.0;
+  }
+}
+__global__ void k_misfit_dir(int64_t n, int kind, double level, double smooth, const double* __restrict__ c,
+                             const double* __restrict__ dc, double* __restrict__ out) {   // out = h'(c) dc
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double hp, h2;
+  misfit_derivs(kind, level, smooth, c[i], &hp, &h2);
+  out[i] = hp * dc[i];
+}
+// dg += w (h' M(h' dc) + h'' M(h - t) dc), nodewise (Mhd = M(h' dc), Me = M(h - t))
+__global__ void k_misfit_second(int64_t n, int kind, double level, double smooth, double w, const double* __restrict__ c,
+                                const double* __restrict__ dc, const double* __restrict__ Me,
+                                const double* __restrict__ Mhd, double* __restrict__ dg) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double hp, h2;
+  misfit_derivs(kind, level, smooth, c[i], &hp, &h2);
+  dg[i] += w * (hp * Mhd[i] + h2 * Me[i] * dc[i]);
+}
+
+// MODE 1 of k_sens with the material table `mat`: qcell (the cells' shares of G^T v) and, when sums is not null,
+// sums[l][2] += v^T G_l c (gamma = 1)
+template <int D>
+void gt_pass(glims_ctx* h, const double* mat, const double* c, const double* v, double* qcell, double* part, double* sums) {
+  const int nb = (int)std::min<int64_t>(GL_ADJ_BLOCKS, grid_of(h->n_cells));
+  for (int l0 = 0; l0 < h->n_labels; l0 += GL_ADJ_LT) {
+    hipLaunchKernelGGL((k_sens<D, 1>), dim3(nb), dim3(256), 0, h->st, h->n_cells, l0, h->adj.cell_nodes.p, h->egeo.p,
+                       h->label.p, mat, c, v, (const uint8_t*)nullptr, qcell, part);
+    GL_CHECK_LAUNCH();
+    if (!sums) break;   // (qcell comes from the l0 = 0 launch)
+    hipLaunchKernelGGL(k_sens_final, dim3(1), dim3(1024), 0, h->st, nb, l0, h->n_labels, 3, 2, part, sums);
+    GL_CHECK_LAUNCH();
+  }
+}
+
+// A(c_n) x = rhs (0 on the constrained nodes) by the PCG of the first-order adjoint's lambda solve; x holds the initial
+// guess on entry (its constrained entries are set to 0)
+int rd_solve(glims_ctx* h, AdjWork& wk, const uint8_t* fxc, bool rd_mg, int rd_deg, const double* rhs, double* x,
+             int64_t* its) {
+  const int64_t n = h->n_own;
+  if (fxc) hipLaunchKernelGGL(k_zero_fixed, dim3(grid_of(n)), dim3(256), 0, h->st, n, fxc, x, (const double*)nullptr);
+  gl_launch_spmv(h, h->st, h->pat.n_slices, nullptr, h->vA.p, x, wk.w.p, fxc, nullptr, nullptr, nullptr, 0, nullptr);
+  hipLaunchKernelGGL(k_residual, dim3(grid_of(n)), dim3(256), 0, h->st, n, rhs, wk.w.p, fxc, wk.r.p);
+  GL_CHECK_LAUNCH();
+  const double nb = std::sqrt(gl_dot(h, rhs, rhs, n));
+  *its = 0;
+  if (!std::isfinite(nb)) return GLIMS_NAN;
+  if (nb == 0.0) {
+    GL_HIP(hipMemsetAsync(x, 0, (size_t)h->n_nodes * sizeof(double), h->st));
+    return GLIMS_OK;
+  }
+  double res = 0.0;
+  const int st = gl_pcg(h, x, wk.r.p, wk.u.p, wk.w.p, wk.p.p, wk.s.p, h->dinv.p, h->vA.p, fxc, 1,
+                        rd_mg ? &h->mg_rd : nullptr, rd_deg, 1e-12 * nb, std::max(h->opt.cg_maxit, 20000), its, &res);
+  if (fxc) hipLaunchKernelGGL(k_zero_fixed, dim3(grid_of(n)), dim3(256), 0, h->st, n, fxc, x, (const double*)nullptr);
+  GL_CHECK_LAUNCH();
+  return st;
+}
+
+// ---- P-column Jacobi-PCG: P independent solves A x_j = b_j sharing one k_spmm per iteration ------------------------------
+// Vectors interleaved [node][P].  Each column has its own alpha, beta, stopping test (||r_j|| <= tol_j) and done flag; a done
+// column is frozen (no update of x, r or p).  The 2P dot products (r.z, r.r) of an iteration come from one fixed-order
+// reduction (block partials on a fixed grid, then one wave per sum), p.Ap from k_spmm's fused partials: no float atomics,
+// and the arithmetic of column j does not depend on P.  State sc[6][P]: rz, rr, alpha, beta, tol, pq.
+constexpr int GL_MP_BLOCKS = 1024;
+enum { MP_RZ = 0, MP_RR, MP_ALPHA, MP_BETA, MP_TOL, MP_PQ, MP_N };
+
+// column-major [P][ld] <-> interleaved [n][P]; fixed rows give 0 (pack)
+template <int P>
+__global__ void k_mp_pack(int64_t n, int64_t ld, const double* __restrict__ src, const uint8_t* __restrict__ fixed,
+                          double* __restrict__ dst, int to_interleaved) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+#pragma unroll
+  for (int q = 0; q < P; ++q) {
+    if (to_interleaved) dst[i * P + q] = (fixed && fixed[i]) ? 0.0 : src[(int64_t)q * ld + i];
+    else dst[(int64_t)q * ld + i] = src[i * P + q];
+  }
+}
+
+template <int P>
+__device__ __forceinline__ void mp_block_partials(double (&v)[2 * P], double* __restrict__ part) {
+  __shared__ double sm[4][2 * P];
+  const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+  for (int k = 0; k < 2 * P; ++k) {
+    const double t = wsum(v[k]);
+    if (lane == 0) sm[wid][k] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x < 2 * P) {
+    const int k = threadIdx.x;
+    part[(size_t)blockIdx.x * 2 * P + k] = (sm[0][k] + sm[1][k]) + (sm[2][k] + sm[3][k]);
+  }
+}
+
+// mode 0 (start): r = b - Ax (Ax in q), p = z = Dinv r;  mode 1 (iteration): x += alpha p, r -= alpha q, z = Dinv r.
+// Both leave the block partials of (r.z, r.r) per column.
+template <int P>
+__global__ __launch_bounds__(256) void k_mp_vec(int mode, int64_t n, const uint8_t* __restrict__ fixed,
+                                                const double* __restrict__ dinv, const double* __restrict__ b,
+                                                double* __restrict__ x, double* __restrict__ r, double* __restrict__ p,
+                                                const double* __restrict__ q, const double* __restrict__ sc,
+                                                const int* __restrict__ done, double* __restrict__ part) {
+  double v[2 * P], al[P];
+  bool dn[P];
+#pragma unroll
+  for (int j = 0; j < P; ++j) {   // the column scalars, once per thread
+    dn[j] = done[j] != 0;
+    al[j] = sc[MP_ALPHA * P + j];
+  }
+#pragma unroll
+  for (int k = 0; k < 2 * P; ++k) v[k] = 0.0;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const bool fx = fixed && fixed[i];
+    const double di = dinv[i];
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+      if (dn[j]) continue;
+      const int64_t o = i * P + j;
+      double rr;
+      if (mode == 0) {
+        rr = fx ? 0.0 : b[o] - q[o];
+      } else {
+        const double a = al[j];
+        x[o] += a * p[o];
+        rr = r[o] - a * q[o];
+      }
+      r[o] = rr;
+      const double z = fx ? 0.0 : di * rr;
+      if (mode == 0) p[o] = z;
+      v[2 * j] += rr * z;
+      v[2 * j + 1] += rr * rr;
+    }
+  }
+  mp_block_partials<P>(v, part);
+}
+
+// p = Dinv r + beta p (columns still running)
+template <int P>
+__global__ void k_mp_dir(int64_t n, const uint8_t* __restrict__ fixed, const double* __restrict__ dinv,
+                         const double* __restrict__ r, double* __restrict__ p, const double* __restrict__ sc,
+                         const int* __restrict__ done) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const bool fx = fixed && fixed[i];
+  const double di = fx ? 0.0 : dinv[i];
+#pragma unroll
+  for (int j = 0; j < P; ++j) {
+    const bool dn = done[j] != 0;
+    const double be = sc[MP_BETA * P + j];
+    if (dn) continue;
+    const int64_t o = i * P + j;
+    p[o] = di * r[o] + be * p[o];
+  }
+}
+
+// The scalar step, one wave per sum (fixed order: lane l adds blocks l, l + 64, ..., then the butterfly), thread 0 per column:
+//   stage 0 (after the start):      rz, rr; done when ||r|| <= tol
+//   stage 1 (after k_spmm):          pq = p.Ap, alpha = rz / pq (breakdown: flags[1])
+//   stage 2 (after the update):      done when ||r|| <= tol (its[j] = it), else beta = rz' / rz;  flags[0] = all done
+template <int P>
+__global__ __launch_bounds__(1024) void k_mp_scalar(int stage, int it, int nb, const double* __restrict__ part,
+                                                    double* __restrict__ sc, int* __restrict__ done, int* __restrict__ its,
+                                                    int* __restrict__ flags) {
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int ns = stage == 1 ? P : 2 * P;
+  __shared__ double s[2 * P];
+  if (w < ns) {
+    double t = 0.0;
+    for (int bk = lane; bk < nb; bk += 64) t += part[(size_t)bk * ns + w];
+    t = wsum(t);
+    if (lane == 0) s[w] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  int all = 1;
+  for (int j = 0; j < P; ++j) {
+    if (!done[j]) {
+      if (stage == 1) {
+        const double pq = s[j];
+        sc[MP_PQ * P + j] = pq;
+        if (!(pq > 0.0) || !isfinite(pq)) {
+          flags[1] = 1;
+          done[j] = 1;
+        } else {
+          sc[MP_ALPHA * P + j] = sc[MP_RZ * P + j] / pq;
+        }
+      } else {
+        const double rz = s[2 * j], rr = s[2 * j + 1];
+        if (!isfinite(rr)) {
+          flags[1] = 1;
+          done[j] = 1;
+        } else if (sqrt(rr) <= sc[MP_TOL * P + j]) {
+          done[j] = 1;
+          its[j] = it;
+        } else if (stage == 2) {
+          sc[MP_BETA * P + j] = rz / sc[MP_RZ * P + j];
+        }
+        sc[MP_RZ * P + j] = rz;
+        sc[MP_RR * P + j] = rr;
+      }
+    }
+    all = all && done[j];
+  }
+  flags[0] = all;
+}
+
+struct MultiPcg {
+  dvec<double> X, B, R, Pv, Q, part, part2, sc;
+  dvec<int> done, its, flags;
+};
+
+template <int P>
+int mp_solve_t(glims_ctx* h, MultiPcg& m, const uint8_t* fxc, const double* rhs, double* x, int64_t ld,
+               const std::vector<double>& nb, int64_t* its_out) {
+  const int64_t n = h->n_own;
+  const unsigned g = grid_of(n);
+  const int nbk = (int)std::min<int64_t>(GL_MP_BLOCKS, g);
+  std::vector<double> sc((size_t)MP_N * P, 0.0);
+  std::vector<int> done(P, 0), its(P, 0), flags(2, 0);
+  for (int j = 0; j < P; ++j) {
+    sc[MP_TOL * P + j] = 1e-12 * nb[j];
+    done[j] = nb[j] == 0.0;   // a zero right-hand side: x_j = 0 (below), no iteration
+  }
+  m.sc.upload(sc, h->st);
+  m.done.upload(done, h->st);
+  m.its.upload(its, h->st);
+  m.flags.upload(flags, h->st);
+  for (int j = 0; j < P; ++j)
+    if (done[j]) GL_HIP(hipMemsetAsync(x + (size_t)j * ld, 0, (size_t)h->n_nodes * sizeof(double), h->st));
+  hipLaunchKernelGGL(k_mp_pack<P>, dim3(g), dim3(256), 0, h->st, n, ld, rhs, fxc, m.B.p, 1);
+  hipLaunchKernelGGL(k_mp_pack<P>, dim3(g), dim3(256), 0, h->st, n, ld, (const double*)x, fxc, m.X.p, 1);
+  GL_CHECK_LAUNCH();
+  gl_launch_spmm(h, P, h->vA.p, m.X.p, m.Q.p, fxc, nullptr);
+  hipLaunchKernelGGL(k_mp_vec<P>, dim3(nbk), dim3(256), 0, h->st, 0, n, fxc, h->dinv.p, m.B.p, m.X.p, m.R.p, m.Pv.p, m.Q.p,
+                     m.sc.p, m.done.p, m.part2.p);
+  hipLaunchKernelGGL(k_mp_scalar<P>, dim3(1), dim3(1024), 0, h->st, 0, 0, nbk, m.part2.p, m.sc.p, m.done.p, m.its.p,
+                     m.flags.p);
+  GL_CHECK_LAUNCH();
+  const int maxit = std::max(h->opt.cg_maxit, 20000), nbs = gl_spmm_blocks(h);
+  int it = 0;
+  for (;;) {
+    GL_HIP(hipMemcpyAsync(flags.data(), m.flags.p, 2 * sizeof(int), hipMemcpyDeviceToHost, h->st));
+    GL_HIP(hipStreamSynchronize(h->st));
+    if (flags[0] || it >= maxit) break;
+    for (int k = 0; k < 4 && it < maxit; ++k) {   // (done columns stay frozen: checking every 4 iterations changes no bit)
+      ++it;
+      gl_launch_spmm(h, P, h->vA.p, m.Pv.p, m.Q.p, fxc, m.part.p);
+      hipLaunchKernelGGL(k_mp_scalar<P>, dim3(1), dim3(1024), 0, h->st, 1, it, nbs, m.part.p, m.sc.p, m.done.p, m.its.p,
+                         m.flags.p);
+      hipLaunchKernelGGL(k_mp_vec<P>, dim3(nbk), dim3(256), 0, h->st, 1, n, fxc, h->dinv.p, m.B.p, m.X.p, m.R.p, m.Pv.p,
+                         m.Q.p, m.sc.p, m.done.p, m.part2.p);
+      hipLaunchKernelGGL(k_mp_scalar<P>, dim3(1), dim3(1024), 0, h->st, 2, it, nbk, m.part2.p, m.sc.p, m.done.p, m.its.p,
+                         m.flags.p);
+      hipLaunchKernelGGL(k_mp_dir<P>, dim3(g), dim3(256), 0, h->st, n, fxc, h->dinv.p, m.R.p, m.Pv.p, m.sc.p, m.done.p);
+      GL_CHECK_LAUNCH();
+    }
+  }
+  hipLaunchKernelGGL(k_mp_pack<P>, dim3(g), dim3(256), 0, h->st, n, ld, (const double*)m.X.p, fxc, x, 0);
+  GL_CHECK_LAUNCH();
+  GL_HIP(hipMemcpyAsync(its.data(), m.its.p, P * sizeof(int), hipMemcpyDeviceToHost, h->st));
+  GL_HIP(hipStreamSynchronize(h->st));
+  for (int j = 0; j < P; ++j) *its_out += its[j];
+  if (flags[1]) return GLIMS_NAN;
+  return flags[0] ? GLIMS_OK : GLIMS_NOT_CONVERGED;
+}
+
+// A(c_n) x_j = rhs_j for P columns (column-major [P][ld], rhs 0 on the constrained nodes; x holds the initial guesses): one
+// P-column Jacobi-PCG with the Jacobi preconditioner; with the RD multigrid (stiff steps) the V-cycle PCG of rd_solve runs
+// column by column (no batched V-cycle).  Stops column j at ||r|| <= 1e-12 ||rhs_j||.
+int rd_solve_cols(glims_ctx* h, AdjWork& wk, MultiPcg& m, const uint8_t* fxc, bool rd_mg, int rd_deg, int P,
+                  const double* rhs, double* x, int64_t ld, int64_t* its) {
+  if (rd_mg) {
+    int st = GLIMS_OK;
+    for (int j = 0; j < P && st == GLIMS_OK; ++j) {
+      int64_t k = 0;
+      st = rd_solve(h, wk, fxc, rd_mg, rd_deg, rhs + (size_t)j * ld, x + (size_t)j * ld, &k);
+      *its += k;
+    }
+    return st;
+  }
+  std::vector<double> nb(P);
+  for (int j = 0; j < P; ++j) {
+    nb[j] = std::sqrt(gl_dot(h, rhs + (size_t)j * ld, rhs + (size_t)j * ld, h->n_own));
+    if (!std::isfinite(nb[j])) return GLIMS_NAN;
+  }
+  switch (P) {
+    case 1: return mp_solve_t<1>(h, m, fxc, rhs, x, ld, nb, its);
+    case 2: return mp_solve_t<2>(h, m, fxc, rhs, x, ld, nb, its);
+    case 3: return mp_solve_t<3>(h, m, fxc, rhs, x, ld, nb, its);
+    case 4: return mp_solve_t<4>(h, m, fxc, rhs, x, ld, nb, its);
+    case 5: return mp_solve_t<5>(h, m, fxc, rhs, x, ld, nb, its);
+    case 6: return mp_solve_t<6>(h, m, fxc, rhs, x, ld, nb, its);
+    case 7: return mp_solve_t<7>(h, m, fxc, rhs, x, ld, nb, its);
+    default: return mp_solve_t<8>(h, m, fxc, rhs, x, ld, nb, its);
+  }
+}
+
+// glims_adjoint_stats counts gradient calls only: what the shared solves of a Hessian call add goes back on return
+struct AdjCountGuard {
+  AdjointState& a;
+  int64_t gradients, steps, pcg_its, mech_solves, mech_its;
+  double ms;
+  explicit AdjCountGuard(AdjointState& a_)
+      : a(a_), gradients(a_.gradients), steps(a_.steps), pcg_its(a_.pcg_its), mech_solves(a_.mech_solves),
+        mech_its(a_.mech_its), ms(a_.ms_backward) {}
+  ~AdjCountGuard() {
+    a.gradients = gradients;
+    a.steps = steps;
+    a.pcg_its = pcg_its;
+    a.mech_solves = mech_solves;
+    a.mech_its = mech_its;
+    a.ms_backward = ms;
+  }
+};
+
+// The first-order sweep of gradient_t, preceded by the tangent-linear sweep and interleaved with the second-order adjoint
+// solves of every direction.  Its per-step misfit / lambda / sensitivity body is a copy of gradient_t's (same kernels, same
+// order, same buffers: J and the gradient keep its bits, which tests/test_gpu_adjoint_hessian.py checks); a change to one
+// belongs in the other.
+template <int D>
+int hessian_t(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, const double* dir_D, const double* dir_rho,
+              const double* dir_gamma, const double* dir_c0, double* J_out, double* dD, double* drho, double* dgamma,
+              double* dc0, double* hv_D, double* hv_rho, double* hv_gamma, double* hv_c0, double* stats) {
+  AdjointState& a = h->adj;
+  const int64_t n = h->n_own, nn = h->n_nodes, nd = nn * D;
+  const int N = (int)a.traj.size() - 1;
+  const int L = h->n_labels;
+  const double t0 = omp_get_wtime();
+  bool any_u = false;
+  for (int k = 0; k < n_terms; ++k) any_u = any_u || terms[k].kind == GLIMS_MISFIT_U_L2;
+  {   // the stored tangent-linear states dominate: 8 P B per node and recorded state (see glims_hip.h)
+    const size_t need = 8 * ((size_t)(N + 1) * P * nn + (size_t)(9 * P + 16) * nn + (any_u ? (size_t)14 * nd : 0) +
+                             (size_t)2 * h->n_cells + (size_t)h->pat.total_entries);
+    size_t fr = 0, tot = 0;
+    GL_HIP(hipMemGetInfo(&fr, &tot));
+    if (need > fr)
+      throw glims_error(GLIMS_E_HIP, "glims_adjoint_hessian: " + std::to_string(P) + " directions over " +
+                                         std::to_string(N + 1) + " recorded states need about " +
+                                         std::to_string(need >> 20) + " MiB of device memory, " +
+                                         std::to_string(fr >> 20) + " MiB are free");
+  }
+  AdjCountGuard counts(a);
+  AdjWork wk;
+  adjoint_setup<D>(h, n_terms, terms, false, wk);
+  // direction tables; material copies with the gamma row replaced by dgamma_p (the dgamma_t G_t^T mu pass)
+  const size_t LM = GL_MAX_LABELS;
+  std::vector<double> dir((size_t)P * 3 * LM, 0.0), dmat((size_t)P * 5 * LM, 0.0);
+  for (int p = 0; p < P; ++p) {
+    for (int l = 0; l < L; ++l) {
+      dir[(p * 3 + 0) * LM + l] = dir_D ? dir_D[(size_t)p * L + l] : 0.0;
+      dir[(p * 3 + 1) * LM + l] = dir_rho ? dir_rho[(size_t)p * L + l] : 0.0;
+      dir[(p * 3 + 2) * LM + l] = dir_gamma ? dir_gamma[(size_t)p * L + l] : 0.0;
+    }
+    std::copy(h->mat_host.begin(), h->mat_host.begin() + 5 * LM, dmat.begin() + (size_t)p * 5 * LM);
+    std::copy(dir.begin() + (p * 3 + 2) * LM, dir.begin() + (p * 3 + 3) * LM, dmat.begin() + ((size_t)p * 5 + 2) * LM);
+  }
+  dvec<double> d_dir, d_dmat, dcs, nu, nu_next, dg, hrhs, hd, Mhd, hsums, hpart, hqcell;
+  dvec<double> urhs, du, dmurhs, dmu, ue, uMe;
+  d_dir.upload(dir, h->st);
+  d_dmat.upload(dmat, h->st);
+  dcs.alloc_zero((size_t)(N + 1) * P * nn, h->st);   // dc_n of direction p at dcs[(n P + p) nn]
+  for (auto* v : {&nu, &nu_next, &dg, &hrhs}) v->alloc_zero((size_t)P * nn, h->st);
+  hd.alloc_zero((size_t)nn, h->st);
+  Mhd.alloc_zero((size_t)nn, h->st);
+  hsums.alloc_zero((size_t)P * LM * 3, h->st);
+  hpart.alloc_zero((size_t)GL_ADJ_BLOCKS * GL_ADJ_LT * 2, h->st);
+  hqcell.alloc_zero((size_t)h->n_cells, h->st);
+  if (any_u) {
+    for (auto* v : {&urhs, &du, &dmurhs, &dmu}) v->alloc_zero((size_t)nd, h->st);
+    ue.alloc_zero((size_t)nn, h->st);
+    uMe.alloc_zero((size_t)nn, h->st);
+  }
+  if (dir_c0)
+    for (int p = 0; p < P; ++p) {
+      GL_HIP(hipMemcpyAsync(wk.stage.p, dir_c0 + (size_t)p * nn, (size_t)nn * sizeof(double), hipMemcpyHostToDevice, h->st));
+      hipLaunchKernelGGL(k_perm, dim3(grid_of(nn)), dim3(256), 0, h->st, nn, 1, h->d_old2new.p, wk.stage.p,
+                         dcs.p + (size_t)p * nn, 1);
+      GL_CHECK_LAUNCH();
+      GL_HIP(hipStreamSynchronize(h->st));
+    }
+  auto dc_of = [&](int step, int p) { return dcs.p + ((size_t)step * P + p) * nn; };
+  MultiPcg mp;   // the P-column solver's interleaved vectors [n_nodes][P] and scalars
+  for (auto* v : {&mp.X, &mp.B, &mp.R, &mp.Pv, &mp.Q}) v->alloc_zero((size_t)P * nn, h->st);
+  mp.part.alloc_zero((size_t)gl_spmm_blocks(h) * P, h->st);
+  mp.part2.alloc_zero((size_t)GL_MP_BLOCKS * 2 * P, h->st);
+  ForwardGuard guard(h, wk);
+  const uint8_t* fxc = h->have_fixed_c ? h->fixed_c.p : nullptr;
+  const bool rd_mg = h->rd_precond_active == GLIMS_RD_PRECOND_MULTIGRID;
+  if (rd_mg && !h->mg_rd.ready) gl_mg_setup_rd(h);
+  const int rd_deg = h->opt.rd_mg_smooth > 0 ? h->opt.rd_mg_smooth : (h->mg_rd.lattice ? 1 : 3);
+  const DevPattern& pt = h->pat;
+  const double dt = h->opt.dt;
+  int64_t tlm_its = 0, soa_its = 0, extra_mech = 0;
+  int status = GLIMS_OK;
+  // 1. tangent-linear sweep: A(c_n) dc_n = M dc_{n-1} - dt sum_t dD_t K_t c_n - dt sum_t drho_t int_t (c_n^2 - c_n) phi
+  for (int step = 1; step <= N && status == GLIMS_OK; ++step) {
+    const double* c = a.traj[step]->p;
+    GL_HIP(hipMemsetAsync(wk.tmp.p, 0, (size_t)nn * sizeof(double), h->st));
+    gl_rd_assemble(h, c, wk.tmp.p, nullptr, wk.w.p, nullptr, h->partials.p);
+    for (int p = 0; p < P; ++p)
+      gl_launch_spmv(h, h->st, pt.n_slices, nullptr, h->vM.p, dc_of(step - 1, p), hrhs.p + (size_t)p * nn, fxc, nullptr,
+                     nullptr, nullptr, 0, nullptr);
+    hipLaunchKernelGGL((k_hess_rows<D, 0>), dim3(grid_of(n)), dim3(256), 0, h->st, n, P, nn, pt.cslice_ptr.p, pt.cslots.p,
+                       pt.celem.p, pt.diag_k.p, a.cell_nodes.p, h->egeo.p, h->label.p, h->mat.p, d_dir.p, dt, c,
+                       (const double*)nullptr, (const double*)nullptr, hrhs.p);
+    GL_CHECK_LAUNCH();
+    for (int p = 0; p < P; ++p)
+      if (fxc)
+        hipLaunchKernelGGL(k_zero_fixed, dim3(grid_of(n)), dim3(256), 0, h->st, n, fxc, hrhs.p + (size_t)p * nn,
+                           (const double*)nullptr);
+    GL_CHECK_LAUNCH();
+    // warm start from dc_{n-1} (its constrained entries -- dc_0 may have some -- start at 0)
+    GL_HIP(hipMemcpyAsync(dc_of(step, 0), dc_of(step - 1, 0), (size_t)P * nn * sizeof(double), hipMemcpyDeviceToDevice,
+                          h->st));
+    if (fxc)
+      for (int p = 0; p < P; ++p)
+        hipLaunchKernelGGL(k_zero_fixed, dim3(grid_of(n)), dim3(256), 0, h->st, n, fxc, dc_of(step, p),
+                           (const double*)nullptr);
+    status = rd_solve_cols(h, wk, mp, fxc, rd_mg, rd_deg, P, hrhs.p, dc_of(step, 0), nn, &tlm_its);
+  }
+  // 2. the first-order sweep with the second-order adjoint nu_n of every direction
+  double J = 0.0;
+  for (int step = N; step >= 0 && status == GLIMS_OK; --step) {
+    gl_halo_exchange(h, a.traj[step]->p, 1);
+    const double* c = a.traj[step]->p;
+    GL_HIP(hipMemsetAsync(wk.g.p, 0, (size_t)nn * sizeof(double), h->st));
+    GL_HIP(hipMemsetAsync(dg.p, 0, (size_t)P * nn * sizeof(double), h->st));
+    bool have_u = false;
+    for (int k = 0; k < n_terms; ++k) {
+      const glims_misfit& tm = terms[k];
+      if (tm.step != step) continue;
+      const double* t = wk.targets[k]->p;
+      if (tm.kind != GLIMS_MISFIT_U_L2) {
+        hipLaunchKernelGGL(k_misfit_c, dim3(grid_of(n)), dim3(256), 0, h->st, n, tm.kind, tm.level, tm.smooth, c, t, wk.e.p,
+                           wk.hp.p);
+        GL_CHECK_LAUNCH();
+        gl_halo_exchange(h, wk.e.p, 1);
+        mass_apply(h, wk.e.p, wk.Me.p);
+        J += 0.5 * tm.weight * gl_dot(h, wk.e.p, wk.Me.p, n);
+        hipLaunchKernelGGL(k_add_scaled_prod, dim3(grid_of(n)), dim3(256), 0, h->st, n, tm.weight, wk.hp.p, wk.Me.p, wk.g.p);
+        GL_CHECK_LAUNCH();
+        for (int p = 0; p < P; ++p) {   // dg_p += w (h' M(h' dc) + h'' M(h - t) dc)
+          hipLaunchKernelGGL(k_misfit_dir, dim3(grid_of(n)), dim3(256), 0, h->st, n, tm.kind, tm.level, tm.smooth, c,
+                             dc_of(step, p), hd.p);
+          GL_CHECK_LAUNCH();
+          mass_apply(h, hd.p, Mhd.p);
+          hipLaunchKernelGGL(k_misfit_second, dim3(grid_of(n)), dim3(256), 0, h->st, n, tm.kind, tm.level, tm.smooth,
+                             tm.weight, c, dc_of(step, p), wk.Me.p, Mhd.p, dg.p + (size_t)p * nn);
+          GL_CHECK_LAUNCH();
+        }
+        continue;
+      }
+      if (!have_u) {
+        gl_apply_G(h, c, wk.murhs.p);
+        int64_t its = 0;
+        status = solve_elastic(h, wk, wk.murhs.p, wk.uk.p, h->have_fixed_u ? h->m_uD.p : nullptr, 1e-12, &its);
+        if (status != GLIMS_OK) break;
+        GL_HIP(hipMemsetAsync(wk.murhs.p, 0, (size_t)nd * sizeof(double), h->st));
+        have_u = true;
+      }
+      for (int comp = 0; comp < D; ++comp) {
+        hipLaunchKernelGGL(k_component, dim3(grid_of(n)), dim3(256), 0, h->st, n, D, comp, wk.uk.p, t, wk.e.p);
+        GL_CHECK_LAUNCH();
+        gl_halo_exchange(h, wk.e.p, 1);
+        mass_apply(h, wk.e.p, wk.Me.p);
+        J += 0.5 * tm.weight * gl_dot(h, wk.e.p, wk.Me.p, n);
+        hipLaunchKernelGGL(k_add_component, dim3(grid_of(n)), dim3(256), 0, h->st, n, D, comp, tm.weight, wk.Me.p,
+                           wk.murhs.p);
+        GL_CHECK_LAUNCH();
+      }
+    }
+    if (status != GLIMS_OK) break;
+    if (have_u) {
+      int64_t its = 0;
+      status = solve_elastic(h, wk, wk.murhs.p, wk.mu.p, nullptr, 1e-12, &its);
+      if (status != GLIMS_OK) break;
+      gl_halo_exchange(h, wk.mu.p, D);
+      sens_pass<D>(h, 1, c, wk.mu.p, wk);
+      hipLaunchKernelGGL(k_gt_rows, dim3(grid_of(n)), dim3(256), 0, h->st, n, h->pat.cslice_ptr.p, h->pat.celem.p,
+                         wk.qcell.p, wk.g.p);
+      GL_CHECK_LAUNCH();
+      // per direction: du = K_el^-1 (G dc + sum_t dgamma_t G_t c), dmu = K_el^-1 sum w M_vec du (0 on the constrained dofs);
+      // dg += G^T dmu + sum_t dgamma_t G_t^T mu;  H_gamma_t += dmu^T G_t c + mu^T G_t dc
+      for (int p = 0; p < P && status == GLIMS_OK; ++p) {
+        double* dgp = dg.p + (size_t)p * nn;
+        double* hs = hsums.p + (size_t)p * LM * 3;
+        hipLaunchKernelGGL(k_gdir_rows<D>, dim3(grid_of(n)), dim3(256), 0, h->st, n, pt.cslice_ptr.p, pt.cslots.p,
+                           pt.celem.p, pt.diag_k.p, a.cell_nodes.p, h->egeo.p, h->label.p, h->mat.p,
+                           d_dir.p + (p * 3 + 2) * LM, c, dc_of(step, p), urhs.p);
+        GL_CHECK_LAUNCH();
+        status = solve_elastic(h, wk, urhs.p, du.p, nullptr, 1e-12, &its);
+        if (status != GLIMS_OK) break;
+        GL_HIP(hipMemsetAsync(dmurhs.p, 0, (size_t)nd * sizeof(double), h->st));
+        for (int k = 0; k < n_terms; ++k) {
+          const glims_misfit& tm = terms[k];
+          if (tm.step != step || tm.kind != GLIMS_MISFIT_U_L2) continue;
+          for (int comp = 0; comp < D; ++comp) {
+            hipLaunchKernelGGL(k_component, dim3(grid_of(n)), dim3(256), 0, h->st, n, D, comp, du.p,
+                               (const double*)nullptr, ue.p);
+            GL_CHECK_LAUNCH();
+            mass_apply(h, ue.p, uMe.p);
+            hipLaunchKernelGGL(k_add_component, dim3(grid_of(n)), dim3(256), 0, h->st, n, D, comp, tm.weight, uMe.p,
+                               dmurhs.p);
+            GL_CHECK_LAUNCH();
+          }
+        }
+        status = solve_elastic(h, wk, dmurhs.p, dmu.p, nullptr, 1e-12, &its);
+        if (status != GLIMS_OK) break;
+        extra_mech += 2;
+        gt_pass<D>(h, h->mat.p, c, dmu.p, hqcell.p, hpart.p, hs);
+        hipLaunchKernelGGL(k_gt_rows, dim3(grid_of(n)), dim3(256), 0, h->st, n, pt.cslice_ptr.p, pt.celem.p, hqcell.p, dgp);
+        GL_CHECK_LAUNCH();
+        gt_pass<D>(h, h->mat.p, dc_of(step, p), wk.mu.p, hqcell.p, hpart.p, hs);
+        gt_pass<D>(h, d_dmat.p + (size_t)p * 5 * LM, c, wk.mu.p, hqcell.p, hpart.p, nullptr);
+        hipLaunchKernelGGL(k_gt_rows, dim3(grid_of(n)), dim3(256), 0, h->st, n, pt.cslice_ptr.p, pt.celem.p, hqcell.p, dgp);
+        GL_CHECK_LAUNCH();
+      }
+      if (status != GLIMS_OK) break;
+    }
+    if (step == 0) {
+      if (dc0) {
+        if (N > 0) gl_launch_spmv(h, h->st, h->pat.n_slices, nullptr, h->vM.p, wk.lam_next.p, wk.rhs.p, nullptr, wk.g.p,
+                                  nullptr, nullptr, 0, nullptr);
+        else GL_HIP(hipMemcpyAsync(wk.rhs.p, wk.g.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, h->st));
+        hipLaunchKernelGGL(k_perm, dim3(grid_of(nn)), dim3(256), 0, h->st, nn, 1, h->d_old2new.p, wk.rhs.p, wk.stage.p, 0);
+        GL_CHECK_LAUNCH();
+        GL_HIP(hipMemcpyAsync(dc0, wk.stage.p, (size_t)nn * sizeof(double), hipMemcpyDeviceToHost, h->st));
+        GL_HIP(hipStreamSynchronize(h->st));
+      }
+      for (int p = 0; hv_c0 && p < P; ++p) {   // (H dm)_c0 = M nu_1 + dg_0
+        double* y = hrhs.p + (size_t)p * nn;
+        if (N > 0) gl_launch_spmv(h, h->st, pt.n_slices, nullptr, h->vM.p, nu_next.p + (size_t)p * nn, y, nullptr,
+                                  dg.p + (size_t)p * nn, nullptr, nullptr, 0, nullptr);
+        else GL_HIP(hipMemcpyAsync(y, dg.p + (size_t)p * nn, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, h->st));
+        hipLaunchKernelGGL(k_perm, dim3(grid_of(nn)), dim3(256), 0, h->st, nn, 1, h->d_old2new.p, y, wk.stage.p, 0);
+        GL_CHECK_LAUNCH();
+        GL_HIP(hipMemcpyAsync(hv_c0 + (size_t)p * nn, wk.stage.p, (size_t)nn * sizeof(double), hipMemcpyDeviceToHost,
+                              h->st));
+        GL_HIP(hipStreamSynchronize(h->st));
+      }
+      break;
+    }
+    gl_launch_spmv(h, h->st, h->pat.n_slices, nullptr, h->vM.p, wk.lam_next.p, wk.rhs.p, fxc, wk.g.p, nullptr, nullptr, 0,
+                   nullptr);
+    if (fxc) hipLaunchKernelGGL(k_zero_fixed, dim3(grid_of(n)), dim3(256), 0, h->st, n, fxc, wk.rhs.p, (const double*)nullptr);
+    GL_CHECK_LAUNCH();
+    GL_HIP(hipMemsetAsync(wk.tmp.p, 0, (size_t)nn * sizeof(double), h->st));
+    gl_rd_assemble(h, c, wk.tmp.p, nullptr, wk.w.p, nullptr, h->partials.p);
+    GL_HIP(hipMemcpyAsync(wk.lam.p, wk.lam_next.p, (size_t)nn * sizeof(double), hipMemcpyDeviceToDevice, h->st));
+    gl_launch_spmv(h, h->st, h->pat.n_slices, nullptr, h->vA.p, wk.lam.p, wk.w.p, fxc, nullptr, nullptr, nullptr, 0, nullptr);
+    hipLaunchKernelGGL(k_residual, dim3(grid_of(n)), dim3(256), 0, h->st, n, wk.rhs.p, wk.w.p, fxc, wk.r.p);
+    GL_CHECK_LAUNCH();
+    const double nb = std::sqrt(gl_dot(h, wk.rhs.p, wk.rhs.p, n));
+    if (!std::isfinite(nb)) {
+      status = GLIMS_NAN;
+      break;
+    }
+    if (nb > 0.0) {
+      int64_t its = 0;
+      double res = 0.0;
+      status = gl_pcg(h, wk.lam.p, wk.r.p, wk.u.p, wk.w.p, wk.p.p, wk.s.p, h->dinv.p, h->vA.p, fxc, 1,
+                      rd_mg ? &h->mg_rd : nullptr, rd_deg, 1e-12 * nb, std::max(h->opt.cg_maxit, 20000), &its, &res);
+      a.pcg_its += its;
+      if (status != GLIMS_OK) break;
+      gl_halo_exchange(h, wk.lam.p, 1);
+      sens_pass<D>(h, 0, c, wk.lam.p, wk);
+    } else {
+      GL_HIP(hipMemsetAsync(wk.lam.p, 0, (size_t)nn * sizeof(double), h->st));
+    }
+    // nu_n: A(c_n) nu_n = M nu_{n+1} + dg_n - 2 dt sum_t rho_t int_t dc_n lam_n phi - dt sum_t dD_t K_t lam_n
+    //                     - dt sum_t drho_t int_t (2 c_n - 1) lam_n phi,   PCG from nu_{n+1}
+    for (int p = 0; p < P; ++p)
+      gl_launch_spmv(h, h->st, pt.n_slices, nullptr, h->vM.p, nu_next.p + (size_t)p * nn, hrhs.p + (size_t)p * nn, fxc,
+                     dg.p + (size_t)p * nn, nullptr, nullptr, 0, nullptr);
+    hipLaunchKernelGGL((k_hess_rows<D, 1>), dim3(grid_of(n)), dim3(256), 0, h->st, n, P, nn, pt.cslice_ptr.p, pt.cslots.p,
+                       pt.celem.p, pt.diag_k.p, a.cell_nodes.p, h->egeo.p, h->label.p, h->mat.p, d_dir.p, dt, c,
+                       wk.lam.p, dc_of(step, 0), hrhs.p);
+    GL_CHECK_LAUNCH();
+    const int nbk = (int)std::min<int64_t>(GL_ADJ_BLOCKS, grid_of(h->n_cells));
+    for (int p = 0; p < P; ++p)
+      if (fxc)
+        hipLaunchKernelGGL(k_zero_fixed, dim3(grid_of(n)), dim3(256), 0, h->st, n, fxc, hrhs.p + (size_t)p * nn,
+                           (const double*)nullptr);
+    GL_HIP(hipMemcpyAsync(nu.p, nu_next.p, (size_t)P * nn * sizeof(double), hipMemcpyDeviceToDevice, h->st));
+    status = rd_solve_cols(h, wk, mp, fxc, rd_mg, rd_deg, P, hrhs.p, nu.p, nn, &soa_its);
+    for (int p = 0; p < P && status == GLIMS_OK; ++p) {
+      double* x = nu.p + (size_t)p * nn;
+      for (int l0 = 0; l0 < L; l0 += GL_ADJ_LT) {   // (H dm)_{D,rho} sums of step n
+        hipLaunchKernelGGL(k_hsens<D>, dim3(nbk), dim3(256), 0, h->st, h->n_cells, l0, a.cell_nodes.p, h->egeo.p, h->label.p,
+                           c, wk.lam.p, dc_of(step, p), x, hpart.p);
+        GL_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_sens_final, dim3(1), dim3(1024), 0, h->st, nbk, l0, L, 3, 0, hpart.p,
+                           hsums.p + (size_t)p * LM * 3);
+        GL_CHECK_LAUNCH();
+      }
+    }
+    std::swap(nu.p, nu_next.p);
+    std::swap(wk.lam.p, wk.lam_next.p);
+    a.steps++;
+  }
+  const size_t L3 = (size_t)L * 3;
+  std::vector<double> sums(L3), hs((size_t)P * LM * 3);
+  GL_HIP(hipMemcpyAsync(sums.data(), wk.sums.p, L3 * sizeof(double), hipMemcpyDeviceToHost, h->st));
+  GL_HIP(hipMemcpyAsync(hs.data(), hsums.p, hs.size() * sizeof(double), hipMemcpyDeviceToHost, h->st));
+  GL_HIP(hipStreamSynchronize(h->st));
+  for (int l = 0; l < L; ++l) {
+    if (dD) dD[l] = -dt * sums[l * 3 + 0];
+    if (drho) drho[l] = -dt * sums[l * 3 + 1];
+    if (dgamma) dgamma[l] = sums[l * 3 + 2];
+  }
+  for (int p = 0; p < P; ++p)
+    for (int l = 0; l < L; ++l) {
+      const double* q = hs.data() + ((size_t)p * LM + l) * 3;
+      if (hv_D) hv_D[(size_t)p * L + l] = -dt * q[0];
+      if (hv_rho) hv_rho[(size_t)p * L + l] = -dt * q[1];
+      if (hv_gamma) hv_gamma[(size_t)p * L + l] = q[2];
+    }
+  *J_out = J;
+  if (stats) {
+    stats[0] = (double)tlm_its;
+    stats[1] = (double)soa_its;
+    stats[2] = (double)extra_mech;
+    stats[3] = 1e3 * (omp_get_wtime() - t0);
+  }
+  return status;
+}
+
 }  // namespace
 
 void gl_adjoint_start(glims_ctx* h) {
@@ -685,26 +1568,27 @@ void gl_adjoint_after_step(glims_ctx* h, int status) {
 
 namespace {
 // The argument and state checks of one rank (GLIMS_E_USAGE with the reason)
-void check_gradient_call(glims_ctx* h, int n_terms, const glims_misfit* terms, const double* J) {
+void check_gradient_call(glims_ctx* h, int n_terms, const glims_misfit* terms, const double* J,
+                         const std::string& who = "glims_adjoint_gradient") {
   const AdjointState& a = h->adj;
-  GL_REQUIRE(J, "glims_adjoint_gradient: null J");
-  GL_REQUIRE(n_terms >= 0 && (n_terms == 0 || terms), "glims_adjoint_gradient: bad term list");
-  GL_REQUIRE(h->is_setup, "glims_adjoint_gradient before glims_setup");
-  GL_REQUIRE(a.valid && !a.traj.empty(), "glims_adjoint_gradient: no valid trajectory (" + a.why + ")");
+  GL_REQUIRE(J, who + ": null J");
+  GL_REQUIRE(n_terms >= 0 && (n_terms == 0 || terms), who + ": bad term list");
+  GL_REQUIRE(h->is_setup, who + " before glims_setup");
+  GL_REQUIRE(a.valid && !a.traj.empty(), who + ": no valid trajectory (" + a.why + ")");
   if (a.had_fixed != h->have_fixed_c || (a.had_fixed && a.fixed0 != h->fixed_c_host))
-    throw glims_error(GLIMS_E_USAGE, "glims_adjoint_gradient: the Dirichlet node set changed since recording started");
+    throw glims_error(GLIMS_E_USAGE, who + ": the Dirichlet node set changed since recording started");
   const int64_t N = (int64_t)a.traj.size() - 1;
   for (int k = 0; k < n_terms; ++k) {
     const glims_misfit& t = terms[k];
-    GL_REQUIRE(t.step >= 0 && t.step <= N, "glims_adjoint_gradient: term " + std::to_string(k) + " observes step " +
+    GL_REQUIRE(t.step >= 0 && t.step <= N, who + ": term " + std::to_string(k) + " observes step " +
                                                std::to_string(t.step) + ", the recording has steps 0.." + std::to_string(N));
-    GL_REQUIRE(t.kind >= GLIMS_MISFIT_C_L2 && t.kind <= GLIMS_MISFIT_U_L2, "glims_adjoint_gradient: unknown misfit kind");
-    GL_REQUIRE(t.target, "glims_adjoint_gradient: null target");
-    GL_REQUIRE(std::isfinite(t.weight), "glims_adjoint_gradient: non-finite weight");
+    GL_REQUIRE(t.kind >= GLIMS_MISFIT_C_L2 && t.kind <= GLIMS_MISFIT_U_L2, who + ": unknown misfit kind");
+    GL_REQUIRE(t.target, who + ": null target");
+    GL_REQUIRE(std::isfinite(t.weight), who + ": non-finite weight");
     GL_REQUIRE(t.kind != GLIMS_MISFIT_C_THRESH || (t.smooth > 0.0 && std::isfinite(t.level)),
-               "glims_adjoint_gradient: threshold term needs smooth > 0");
+               who + ": threshold term needs smooth > 0");
     GL_REQUIRE(t.kind != GLIMS_MISFIT_U_L2 || h->have_mech,
-               "glims_adjoint_gradient: a displacement term needs glims_setup(with_mechanics=1)");
+               who + ": a displacement term needs glims_setup(with_mechanics=1)");
   }
 }
 }  // namespace
@@ -744,4 +1628,19 @@ int gl_adjoint_gradient(glims_ctx* h, int n_terms, const glims_misfit* terms, do
   }
   return h->dim == 2 ? gradient_t<2>(h, n_terms, terms, J, dD, drho, dgamma, dc0, dE, dnu)
                      : gradient_t<3>(h, n_terms, terms, J, dD, drho, dgamma, dc0, dE, dnu);
+}
+
+int gl_adjoint_hessian(glims_ctx* h, int n_terms, const glims_misfit* terms, int n_dir, const double* dir_D,
+                       const double* dir_rho, const double* dir_gamma, const double* dir_c0, double* J, double* dD,
+                       double* drho, double* dgamma, double* dc0, double* hv_D, double* hv_rho, double* hv_gamma,
+                       double* hv_c0, double* stats) {
+  // (every rank of a partitioned handle refuses alike: no collective is entered)
+  GL_REQUIRE(h->world <= 1, "glims_adjoint_hessian: not available on partitioned handles (world > 1)");
+  check_gradient_call(h, n_terms, terms, J, "glims_adjoint_hessian");
+  GL_REQUIRE(n_dir >= 1 && n_dir <= GL_HESS_MAXDIR, "glims_adjoint_hessian: n_dir = " + std::to_string(n_dir) +
+                                                        ", 1.." + std::to_string(GL_HESS_MAXDIR) + " directions per call");
+  return h->dim == 2 ? hessian_t<2>(h, n_terms, terms, n_dir, dir_D, dir_rho, dir_gamma, dir_c0, J, dD, drho, dgamma, dc0,
+                                    hv_D, hv_rho, hv_gamma, hv_c0, stats)
+                     : hessian_t<3>(h, n_terms, terms, n_dir, dir_D, dir_rho, dir_gamma, dir_c0, J, dD, drho, dgamma, dc0,
+                                    hv_D, hv_rho, hv_gamma, hv_c0, stats);
 }

@@ -677,6 +677,10 @@ void gl_launch_cheb(glims_ctx* h, hipStream_t st, int n_launch, const int32_t* s
                     double* ylast, double* x, const uint8_t* fixed, double c1, double c2, int k, int m_host, const int* plan,
                     int want_res, const PackMap& pm, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, int shift = 0,
                     double* nrm = nullptr);
+// y = A x for 1..8 columns stored interleaved [node][P] (k_spmm, on h->st); partials (optional): [gl_spmm_blocks][P] of x.y
+void gl_launch_spmm(glims_ctx* h, int P, const double* vals, const double* x, double* y, const uint8_t* fixed,
+                    double* partials);
+int gl_spmm_blocks(glims_ctx* h);
 void gl_launch_spmv_block(glims_ctx* h, hipStream_t st, int n_launch, const int32_t* slice_list, const double* x,
                           double* y, const uint8_t* fixed, const double* r, double* partials, int partial_off,
                           const int* done, bool single_precision_operator = false);
@@ -705,6 +709,10 @@ void gl_adjoint_after_step(glims_ctx* h, int status);   // gl_step: record c_n o
 void gl_adjoint_start(glims_ctx* h);                    // clear, store c_0 (the current state)
 int gl_adjoint_gradient(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J, double* dD, double* drho,
                         double* dgamma, double* dc0, double* dE, double* dnu);
+int gl_adjoint_hessian(glims_ctx* h, int n_terms, const glims_misfit* terms, int n_dir, const double* dir_D,
+                       const double* dir_rho, const double* dir_gamma, const double* dir_c0, double* J, double* dD,
+                       double* drho, double* dgamma, double* dc0, double* hv_D, double* hv_rho, double* hv_gamma,
+                       double* hv_c0, double* stats);
 
 // mg.hip --------------------------------------------------------------------------------------------
 void gl_mesh_metrics(glims_ctx* h, const HostPattern& hp, const double* xyz_old);

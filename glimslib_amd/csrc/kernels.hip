@@ -1664,6 +1664,119 @@ void gl_launch_spmv(glims_ctx* h, hipStream_t st, int n_launch, const int32_t* s
   GL_HIP(hipGetLastError());
 }
 
+// Multi-right-hand-side SELL-64 product: y[row][j] = (A x)[row][j] for P columns stored interleaved (x[node * P + j]), with
+// the pattern, 16-bit column codes and XCD block mapping of k_spmv.  Each value and column code is read once for all P
+// columns, and each column index costs one 8P-byte gather.  Column j is summed in entry order, as the P = 1 instantiation
+// (and k_spmv) sums it, so column j of a P-column product has the bits of a one-column product.  Constrained rows give 0.
+// partials (optional): per logical block and column, sum over the block's rows of x[row][j] y[row][j], in a fixed order
+// (each wave's butterfly, then the four waves).  The grid depends on the slice count only, not on P.
+// Algorithmic bytes: 12 per stored entry (8 B value + 4 B column; 2 B where the slice has codes) + 16 P per row (x, y) +
+// the row length and the fixed mask (2 B per row).
+template <int P, int CIDX, int UNR>
+__global__ __launch_bounds__(256) void k_spmm(int n_launch, int chunk, int64_t n_own, const int64_t* __restrict__ slice_ptr,
+                                              const int32_t* __restrict__ cols, const uint16_t* __restrict__ cols16,
+                                              const int32_t* __restrict__ win_base, const uint8_t* __restrict__ win_ok,
+                                              const uint8_t* __restrict__ rlen, const double* __restrict__ vals,
+                                              const double* __restrict__ x, double* __restrict__ y,
+                                              const uint8_t* __restrict__ fixed, double* __restrict__ partials, int remap) {
+  const int b = remap > 1 ? xcd_chunk_remap(blockIdx.x, gridDim.x, remap) : blockIdx.x;
+  const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int s_end = min(n_launch, (b + 1) * chunk);
+  double pd[P];
+#pragma unroll
+  for (int q = 0; q < P; ++q) pd[q] = 0.0;
+  for (int s = b * chunk + wid; s < s_end; s += 4) {
+    const int64_t row = (int64_t)s * GL_WAVE + lane;
+    const int64_t base = slice_ptr[s];
+    const int len = (int)((slice_ptr[s + 1] - base) >> 6);
+    const int rl = (int)rlen[row];
+    const bool comp = CIDX && win_ok[s];   // wave-uniform
+    const int32_t wb = comp ? win_base[(int64_t)s * GL_N_WIN + (lane & (GL_N_WIN - 1))] : 0;
+    double acc[P];
+#pragma unroll
+    for (int q = 0; q < P; ++q) acc[q] = 0.0;
+    for (int k = 0; k < len; k += UNR) {   // wave-uniform trip count: the code decode is a cross-lane read
+      int32_t cu[UNR];
+      double vu[UNR];
+#pragma unroll
+      for (int j = 0; j < UNR; ++j) {
+        const int64_t o = base + (int64_t)(k + j) * GL_WAVE + lane;
+        const bool in = k + j < rl;
+        if (comp) cu[j] = in ? (int32_t)__builtin_nontemporal_load(cols16 + o) : 0;
+        else cu[j] = in ? __builtin_nontemporal_load(cols + o) : 0;
+        vu[j] = in ? __builtin_nontemporal_load(vals + o) : 0.0;
+      }
+      if (comp) {
+#pragma unroll
+        for (int j = 0; j < UNR; ++j) cu[j] = decode_col((uint32_t)cu[j], wb);
+      }
+      // (entries beyond the row's length gather a valid column with value 0, as in spmv_row: no divergent branch)
+#pragma unroll
+      for (int j = 0; j < UNR; ++j) {
+        const double* xc = x + (int64_t)cu[j] * P;
+#pragma unroll
+        for (int q = 0; q < P; ++q) acc[q] += vu[j] * xc[q];
+      }
+    }
+    if (row < n_own) {
+      const bool fx = fixed && fixed[row];
+#pragma unroll
+      for (int q = 0; q < P; ++q) {
+        const double a = fx ? 0.0 : acc[q];
+        y[row * P + q] = a;
+        if (partials) pd[q] += x[row * P + q] * a;
+      }
+    }
+  }
+  if (!partials) return;
+  __shared__ double sm[4][P];
+#pragma unroll
+  for (int q = 0; q < P; ++q) {
+    double t = pd[q];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) t += __shfl_down(t, o, 64);
+    if (lane == 0) sm[wid][q] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x < P) {
+    const int q = threadIdx.x;
+    partials[(size_t)b * P + q] = (sm[0][q] + sm[1][q]) + (sm[2][q] + sm[3][q]);
+  }
+}
+
+int gl_spmm_blocks(glims_ctx* h) { return gl_spmv_grid(h->pat.n_slices); }
+
+void gl_launch_spmm(glims_ctx* h, int P, const double* vals, const double* x, double* y, const uint8_t* fixed,
+                    double* partials) {
+  const DevPattern& p = h->pat;
+  const int n_launch = p.n_slices;
+  if (n_launch <= 0) return;
+  const int grid = gl_spmv_grid(n_launch);
+  const int chunk = (n_launch + grid - 1) / grid;
+#define GL_SPMM2(PP, CIDX)                                                                                            \
+  hipLaunchKernelGGL((k_spmm<PP, CIDX, 8>), dim3(grid), dim3(256), 0, h->st, n_launch, chunk, h->n_own, p.slice_ptr.p,  \
+                     p.cols.p, p.cols16.p, p.win_base.p, p.win_ok.p, p.rlen.p, vals, x, y, fixed, partials, GL_XCD_CHUNK)
+#define GL_SPMM1(PP)                     \
+  do {                                   \
+    if (h->use_idx16) GL_SPMM2(PP, 1);   \
+    else GL_SPMM2(PP, 0);                \
+  } while (0)
+  switch (P) {
+    case 1: GL_SPMM1(1); break;
+    case 2: GL_SPMM1(2); break;
+    case 3: GL_SPMM1(3); break;
+    case 4: GL_SPMM1(4); break;
+    case 5: GL_SPMM1(5); break;
+    case 6: GL_SPMM1(6); break;
+    case 7: GL_SPMM1(7); break;
+    case 8: GL_SPMM1(8); break;
+    default: throw glims_error(GLIMS_E_USAGE, "gl_launch_spmm: 1..8 columns");
+  }
+#undef GL_SPMM1
+#undef GL_SPMM2
+  GL_HIP(hipGetLastError());
+}
+
 // One launch of the dot-free Krylov iteration (k_cheb) over a slice subset; same launch shape, stream policy and column-code
 // choice as the SpMV it replaces.
 void gl_launch_cheb(glims_ctx* h, hipStream_t st, int n_launch, const int32_t* slice_list, const double* vals,

@@ -75,7 +75,10 @@ class ReducedFunctional:
         self._m = None
         self._J = None
         self._dJ = None
+        self._H = None
+        self._n_steps = None
         self.evaluations = 0
+        self.hessian_calls = 0
         self.history = []   # (m, J, |dJ/dm|) per evaluation (the reference's eval_cb_post / derivative_cb_post)
 
     def _set_params(self, m):
@@ -99,6 +102,7 @@ class ReducedFunctional:
         g = self.sim.adjoint_gradient(self.terms_builder(self.sim, n_steps))
         self._m, self._J = m, float(g["J"])
         self._dJ = self.P.T @ self._model_gradient(g)
+        self._H, self._n_steps = None, n_steps
         self.evaluations += 1
         self.history.append((m.copy(), self._J, float(np.linalg.norm(self._dJ))))
 
@@ -110,13 +114,42 @@ class ReducedFunctional:
         self._evaluate(m)
         return self._dJ.copy()
 
+    def _model_directions(self):
+        """The n_params directions P e_j in the simulation's adjoint_hessian keys."""
+        if any(n.startswith(("E_", "nu_")) for n in self.names):
+            raise ValueError("ReducedFunctional.hessian: E / nu controls %s are first order only (the Hessian covers D, rho "
+                             "and the coupling)" % [n for n in self.names if n.startswith(("E_", "nu_"))])
+        key = (lambda n: n) if self.brain else {"diffusion": "diffusion", "proliferation": "proliferation",
+                                                 "coupling": "coupling"}.get
+        return [{key(name): float(v) for name, v in zip(self.names, self.P[:, j]) if v != 0.0}
+                for j in range(self.n_params)]
+
+    def hessian_matrix(self, m):
+        """P^T H P at m: all n_params directions in one Hessian call (after the forward run of m, shared with ``__call__``
+        and ``derivative``); cached with m."""
+        dirs = self._model_directions()
+        self._evaluate(m)
+        if self._H is None:
+            _, hv = self.sim.adjoint_hessian(self.terms_builder(self.sim, self._n_steps), dirs)
+            H = np.array([[float(np.sum(h[name])) for name in self.names] for h in hv]).T   # column j = H P e_j
+            self._H = self.P.T @ H
+            self.hessian_calls += 1
+        return self._H.copy()
+
+    def hessian(self, m, dm):
+        """The Hessian action P^T H P dm at m (fenics.ReducedFunctional.hessian; scipy's ``hessp``)."""
+        return self.hessian_matrix(m) @ np.asarray(dm, dtype=np.float64).reshape(-1)
+
 
 def minimize(rf, m0, bounds=(0.005, 0.5), method="L-BFGS-B", tol=1e-6, options=None):
     """scipy.optimize.minimize on ``rf`` with ``jac=rf.derivative`` and the reference's defaults (bounds 0.005 .. 0.5 on
-    every control, L-BFGS-B, tol 1e-6, gtol 1e-6; image_based_optimization.py:710-722)."""
+    every control, L-BFGS-B, tol 1e-6, gtol 1e-6; image_based_optimization.py:710-722).  method='trust-constr' also gets
+    ``hessp=rf.hessian``, the second-order adjoint."""
     from scipy.optimize import minimize as _minimize
     m0 = np.asarray(m0, dtype=np.float64)
     opts = {"disp": False, "gtol": 1e-6}
     opts.update(options or {})
     bnds = [tuple(bounds)] * len(m0) if np.ndim(bounds[0]) == 0 else list(zip(*bounds))
+    if method.lower() == "trust-constr":
+        return _minimize(rf, m0, jac=rf.derivative, hessp=rf.hessian, bounds=bnds, method=method, tol=tol, options=opts)
     return _minimize(rf, m0, jac=rf.derivative, bounds=bnds, method=method, tol=tol, options=opts)

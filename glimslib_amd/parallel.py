@@ -350,6 +350,10 @@ class DistributedHandle:
     def adjoint_record(self, on=True):
         self.h.adjoint_record(on)
 
+    def adjoint_hessian(self, terms, directions, n_labels=None):
+        """Second-order adjoint: single-GPU handles only (glims_adjoint_hessian refuses partitioned handles)."""
+        raise NotImplementedError("adjoint_hessian: not available on partitioned runs; use a single-GPU handle")
+
     def adjoint_gradient(self, terms, n_labels=None, want_dc0=True, elastic=False):
         """Handle.adjoint_gradient on the partitioned run: targets in GLOBAL node order ([n_global] or [n_global, dim]),
         localised here; J and the per-label arrays come back bitwise the same on every rank, dJ/dc0 all-gathered into the

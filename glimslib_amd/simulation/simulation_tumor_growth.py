@@ -318,6 +318,36 @@ class TumorGrowth(FenicsSimulation):
         J, dD, drho, dgamma, dc0, dE, dnu = self._adjoint_raw(terms, elastic=True)
         return {'J': J, 'diffusion': dD, 'proliferation': drho, 'coupling': dgamma, 'E': dE, 'poisson': dnu, 'c0': dc0}
 
+    def _adjoint_hessian_raw(self, terms, directions):
+        """Handle.adjoint_hessian of the recorded run; directions keyed 'D' / 'rho' / 'gamma' / 'c0'."""
+        h = self._backend
+        if h is None or not hasattr(h, 'adjoint_hessian'):
+            raise RuntimeError("adjoint_hessian needs a run(record_adjoint=True) first")
+        if getattr(self.bcs, 'von_neumann_bcs', None):
+            flux = self.bcs.implement_von_neumann_bc(np.ones(len(self._labels())), subspace_id=1)
+            if np.any(np.asarray(flux) != 0.0):
+                raise NotImplementedError("adjoint_hessian: von Neumann data on the concentration scale with D; "
+                                          "second derivatives in D are not available for such a run")
+        return h.adjoint_hessian(terms, directions)
+
+    def adjoint_hessian(self, terms, directions):
+        """
+        Hessian-vector products of J for the recorded run (the counterpart of fenics.ReducedFunctional.hessian), with J and
+        the gradient that come with them.  ``directions``: 1 .. 8 dicts keyed like adjoint_gradient's output --
+        'diffusion', 'proliferation', 'coupling' (per-label arrays, or a scalar for every label) and 'c0' ([n_nodes]);
+        missing keys are 0.  E and poisson are first order only.  Returns (g, hv): g = {'J', 'diffusion', 'proliferation',
+        'coupling', 'c0'}, hv = one dict {'diffusion', 'proliferation', 'coupling', 'c0'} per direction.
+        """
+        key = {'diffusion': 'D', 'proliferation': 'rho', 'coupling': 'gamma', 'c0': 'c0'}
+        bad = [k for d in directions for k in d if k not in key]
+        if bad:
+            raise ValueError("adjoint_hessian: directions take %s, got %s" % (tuple(key), bad))
+        r = self._adjoint_hessian_raw(terms, [{key[k]: v for k, v in d.items()} for d in directions])
+        g = {'J': r['J'], 'diffusion': r['D'], 'proliferation': r['rho'], 'coupling': r['gamma'], 'c0': r['c0']}
+        hv = [{'diffusion': r['hv_D'][p], 'proliferation': r['hv_rho'][p], 'coupling': r['hv_gamma'][p],
+               'c0': r['hv_c0'][p]} for p in range(len(directions))]
+        return g, hv
+
     # -- parameter sweeps (the forward half of the reference's adjoint entry points) -------------------------------
     def run_for_adjoint(self, parameters, output_dir=config.output_dir_simulation_tmp):
         """:142-155 -- update (diffusion, proliferation, coupling) and re-run on the same mesh / space."""

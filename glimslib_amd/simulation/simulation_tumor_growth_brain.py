@@ -89,6 +89,35 @@ class TumorGrowthBrain(TumorGrowth):
             g['nu_' + suffix] = pick(dnu, t)
         return g
 
+    def adjoint_hessian(self, terms, directions):
+        """Hessian-vector products (see TumorGrowth.adjoint_hessian) with directions keyed by the scalar names D_WM, D_GM,
+        rho_WM, rho_GM, coupling (one constant on every tissue) and c0; missing keys are 0.  Returns (g, hv) with g =
+        {'J', 'D_WM', 'D_GM', 'rho_WM', 'rho_GM', 'coupling', 'c0'} and one dict of the same keys (no 'J') per direction."""
+        names = ('D_WM', 'D_GM', 'rho_WM', 'rho_GM', 'coupling', 'c0')
+        bad = [k for d in directions for k in d if k not in names]
+        if bad:
+            raise ValueError("adjoint_hessian: directions take %s (E / nu are first order only), got %s" % (names, bad))
+        L = self._backend.n_labels if self._backend is not None else 0
+        wm, gm = self._tissue_id('WM'), self._tissue_id('GM')
+        dirs = []
+        for d in directions:
+            dD, drho = np.zeros(L), np.zeros(L)
+            for t, sfx in ((wm, 'WM'), (gm, 'GM')):
+                if t is not None and t < L:
+                    dD[t] += float(d.get('D_' + sfx, 0.0))
+                    drho[t] += float(d.get('rho_' + sfx, 0.0))
+            dirs.append({'D': dD, 'rho': drho, 'gamma': np.full(L, float(d.get('coupling', 0.0))), 'c0': d.get('c0')})
+        r = self._adjoint_hessian_raw(terms, dirs)
+        pick = lambda a, t: float(a[t]) if t is not None and t < len(a) else 0.0
+
+        def named(D, rho, gamma, c0):
+            return {'D_WM': pick(D, wm), 'D_GM': pick(D, gm), 'rho_WM': pick(rho, wm), 'rho_GM': pick(rho, gm),
+                    'coupling': float(np.sum(gamma)), 'c0': c0}
+
+        g = dict(named(r['D'], r['rho'], r['gamma'], r['c0']), J=r['J'])
+        hv = [named(r['hv_D'][p], r['hv_rho'][p], r['hv_gamma'][p], r['hv_c0'][p]) for p in range(len(directions))]
+        return g, hv
+
     def run_for_adjoint(self, parameters, output_dir=config.output_dir_simulation_tmp):
         """:127-145 -- (D_WM, D_GM, rho_WM, rho_GM, coupling)"""
         self.params.D_WM, self.params.D_GM = parameters[0], parameters[1]

@@ -473,6 +473,36 @@ int glims_adjoint_gradient(glims_ctx* h, int n_terms, const glims_misfit* terms,
 int glims_adjoint_gradient_full(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J, double* dJ_dD,
                                 double* dJ_drho, double* dJ_dgamma, double* dJ_dc0, double* dJ_dE, double* dJ_dnu);
 
+/* Second order: J, the gradient of glims_adjoint_gradient (bitwise the same: the lambda sweep issues gradient's kernels and
+ * solves in the same order on the same set-up) and
+ * n_dir (1..8) Hessian-vector products H dm of the recorded trajectory, dm = (dD, drho, dgamma [n_labels], dc0 [n_nodes]).
+ * Directions and products are laid out [n_dir][n_labels] and [n_dir][n_nodes] (caller's node order); a NULL direction array
+ * is 0, any output except J may be NULL.  Per direction, with A(c) the step Jacobian (symmetric) and K_t, G_t the label-t
+ * parts of the stiffness and coupling operators ("Second order"):
+ *   tangent-linear sweep  A(c_n) dc_n = M dc_{n-1} - dt sum_t dD_t K_t c_n - dt sum_t drho_t int_t (c_n^2 - c_n) phi,
+ *                         dc_0 = dir_c0 (or 0), dc_n = 0 on the Dirichlet nodes;
+ *   second-order adjoint  A(c_n) nu_n = M nu_{n+1} + dg_n - 2 dt sum_t rho_t int_t dc_n lam_n phi - dt sum_t dD_t K_t lam_n
+ *                         - dt sum_t drho_t int_t (2 c_n - 1) lam_n phi,  nu_{N+1} = 0, nu_n = 0 on the Dirichlet nodes;
+ *   dg_n = d(dJ/dc_n + G^T mu_n): C_L2 w M dc;  C_THRESH w (h' M(h' dc) + h'' M(h - t) dc) nodewise;  U_L2 G^T dmu_k +
+ *          sum_t dgamma_t G_t^T mu_k with du_k = K_el^-1 (G dc_k + sum_t dgamma_t G_t c_k), dmu_k = K_el^-1 w M_vec du_k;
+ *   hv_D_t = -dt sum_n int_t (grad nu_n . grad c_n + grad lam_n . grad dc_n),
+ *   hv_rho_t = -dt sum_n int_t (nu_n (c_n^2 - c_n) + lam_n (2 c_n - 1) dc_n),
+ *   hv_gamma_t = sum_k (dmu_k^T G_t c_k + mu_k^T G_t dc_k),   hv_c0 = M nu_1 + dg_0.
+ * RD solves (tangent-linear and second-order, every direction at every step): one n_dir-column Jacobi-PCG that shares a
+ * multi-right-hand-side SpMV per iteration, each column stopped at ||r|| <= 1e-12 ||rhs||; when the handle uses the RD
+ * multigrid (stiff steps) the V-cycle PCG runs column by column instead.  Column j of an n_dir-direction call has the bits
+ * of a one-direction call in direction j.  Elastic
+ * solves to 1e-12 ||rhs||, 2 per direction at each step a U_L2 term observes.  E and nu are first order only (no direction,
+ * no product).  Device memory on top of the trajectory: 8 n_dir B per node and recorded state (the stored dc_n) plus
+ * O(n_dir) vectors; a call that does not fit returns GLIMS_E_HIP before it allocates.  The forward state and glims_stats are
+ * left as they were; glims_adjoint_stats does not count this call.  stats (may be NULL) [4]: tangent-linear PCG iterations,
+ * second-order PCG iterations, extra elastic solves, wall ms.  Partitioned handles: GLIMS_E_USAGE on every rank.  Stands in
+ * for fenics.ReducedFunctional.hessian (the H that minimize_custom hands its optimizer, image_based_optimization.py:646). */
+int glims_adjoint_hessian(glims_ctx* h, int n_terms, const glims_misfit* terms, int n_dir, const double* dir_D,
+                          const double* dir_rho, const double* dir_gamma, const double* dir_c0, double* J, double* dJ_dD,
+                          double* dJ_drho, double* dJ_dgamma, double* dJ_dc0, double* hv_D, double* hv_rho,
+                          double* hv_gamma, double* hv_c0, double* stats);
+
 /* Counters of the adjoint (not in glims_stats, whose layout is fixed): out[0] gradient calls, [1] backward steps,
  * [2] RD adjoint PCG iterations, [3] elastic solves, [4] their PCG iterations, [5] recorded states held now;
  * ms[0] wall time of the backward sweeps (may be NULL). */
