@@ -5,7 +5,7 @@ differences of the numpy adjoint gradient, by symmetry and by a Taylor test of J
 import numpy as np
 import pytest
 
-from adjoint_common import make_problem, misfit
+from adjoint_common import make_problem, many_tissues, misfit, u_terms
 from adjoint_hessian_common import flat, gradient_at, hessian
 
 N_STEPS = 4
@@ -46,6 +46,55 @@ def test_hessian_matches_central_differences_of_the_gradient(dim):
                      ("c0", slice(3 * L, None))):
         err = np.linalg.norm(ana[sl] - num[sl]) / np.linalg.norm(num[sl])
         assert err <= 1e-6, (what, err, ana[sl][:4], num[sl][:4])
+
+
+# ---- the regimes of tests/test_gpu_adjoint_hessian_coverage.py ------------------------------------------------------------
+def _everywhere(prob, seed):
+    """dD, drho, dgamma on every label (absolute sizes, so a passive tissue's entries are not 0) and a dc0."""
+    rng = np.random.default_rng(seed)
+    L, n = prob.n_labels, len(prob.points)
+    return dict(D=0.03 * rng.uniform(-1, 1, L), rho=0.4 * rng.uniform(-1, 1, L), gamma=0.15 * rng.uniform(-1, 1, L),
+                c0=0.2 * rng.uniform(-1, 1, n) * (prob.c0 + 0.1))
+
+
+def _regime(case):
+    """(problem, N, terms)"""
+    if case == "tissues_clamp_and_loads":
+        prob = many_tissues(2, 9, n=8, empty=(3,), zero=(5,), zero_gamma=(5,), u_clamp=0.02, mech_load=1.0, rd_load=0.3)
+        return prob, N_STEPS, prob.terms(N_STEPS)
+    prob = many_tissues(2, 3, n=8, u_clamp=0.02, mech_load=1.0, seed=2)
+    n = len(prob.points)
+    if case == "u_terms_at_0_1_N_N":
+        return prob, N_STEPS, u_terms(prob, [0, 1, N_STEPS, N_STEPS], seed=3) + [
+            dict(step=N_STEPS, kind="c_l2", weight=1.0, target=np.full(n, 0.2))]
+    rng = np.random.default_rng(4)   # no steps: every term observes c_0
+    return prob, 0, [dict(step=0, kind="c_thresh", level=0.3, smooth=0.1, weight=1.5, target=rng.uniform(0, 1, n)),
+                     dict(step=0, kind="c_l2", weight=0.5, target=rng.uniform(0, 0.5, n))] + u_terms(prob, [0], seed=5)
+
+
+@pytest.mark.parametrize("case", ["tissues_clamp_and_loads", "u_terms_at_0_1_N_N", "no_steps"])
+def test_hessian_matches_central_differences_in_the_device_test_regimes(case):
+    """9 tissues (id 3 carried by no cell, id 5 with D = rho = gamma = 0) with clamp values, a mechanical and an RD load;
+    displacement terms at steps 0, 1, N, N; a recording of no steps, where the D and rho rows are exactly 0."""
+    prob, N, terms = _regime(case)
+    d = _everywhere(prob, 1)
+    o = prob.oracle()
+    hv = hessian(prob, o, prob.trajectory(o, N), terms, [d])[5][0]
+    ana = flat(prob, hv)
+    eps = 1e-4
+    m = _base(prob)
+    num = (gradient_at(prob, _shift(m, d, eps), N, terms)[1] - gradient_at(prob, _shift(m, d, -eps), N, terms)[1]) / (2 * eps)
+    L = prob.n_labels
+    for what, sl in (("D", slice(0, L)), ("rho", slice(L, 2 * L)), ("gamma", slice(2 * L, 3 * L)),
+                     ("c0", slice(3 * L, None))):
+        if N == 0 and what in ("D", "rho"):
+            assert not ana[sl].any() and not num[sl].any(), (what, ana[sl], num[sl])
+            continue
+        err = np.linalg.norm(ana[sl] - num[sl]) / np.linalg.norm(num[sl])
+        assert err <= 1e-6, (what, err, ana[sl][:4], num[sl][:4])
+    if case == "tissues_clamp_and_loads":
+        assert hv["D"][3] == 0 and hv["rho"][3] == 0 and hv["gamma"][3] == 0
+        assert hv["D"][5] != 0 and hv["rho"][5] != 0 and hv["gamma"][5] != 0
 
 
 @pytest.mark.parametrize("dim", [2, 3])
