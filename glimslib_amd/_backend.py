@@ -31,6 +31,9 @@ PRECOND_BLOCK_JACOBI, PRECOND_MULTIGRID = 0, 1
 RD_PRECOND_AUTO, RD_PRECOND_JACOBI, RD_PRECOND_MULTIGRID = 0, 1, 2
 RD_LINEAR_AUTO, RD_LINEAR_PCG, RD_LINEAR_CHEBYSHEV = 0, 1, 2
 STREAM_AUTO, STREAM_NONTEMPORAL, STREAM_CACHED = 0, 1, 2
+FIELD_C, FIELD_U, FIELD_SNAPSHOT_C, FIELD_HOST = 0, 1, 2, 3
+SAMPLE_EPS = 1e-10      # GLIMS_SAMPLE_EPS: a cell accepts a point iff min lambda >= -SAMPLE_EPS
+SAMPLE_MAX_COMP = 8
 ABI_VERSION = 6
 
 
@@ -132,6 +135,13 @@ SIGNATURES = {
     "glims_adjoint_hessian": (C.c_int, [_h, C.c_int, C.POINTER(Misfit), C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
                                         _dp, _dp, _dp, _dp, _dp, _dp]),
     "glims_adjoint_stats": (C.c_int, [_h, _i64p, _dp]),
+    "glims_sampler_create_points": (C.c_int, [_h, C.c_int64, _dp, C.c_int, _i64p]),
+    "glims_sampler_create_grid": (C.c_int, [_h, _dp, _dp, _i64p, C.c_int, _i64p]),
+    "glims_sampler_info": (C.c_int, [_h, C.c_int64, _i64p, _i64p]),
+    "glims_sampler_get": (C.c_int, [_h, C.c_int64, _i32p, _dp]),
+    "glims_sampler_apply": (C.c_int, [_h, C.c_int64, C.c_int, C.c_int64, _dp, C.c_int, C.c_double, _dp]),
+    "glims_sampler_apply_t": (C.c_int, [_h, C.c_int64, _dp, C.c_int, _dp]),
+    "glims_sampler_destroy": (C.c_int, [_h, C.c_int64]),
     "glims_comm_unique_id": (C.c_int, [C.c_char_p]),
     "glims_comm_init": (C.c_int, [_h, C.c_int, C.c_int, C.c_char_p]),
     "glims_comm_selftest": (C.c_int, [_h]),
@@ -435,6 +445,24 @@ class Handle:
         d["ms_backward"] = ms.value
         return d
 
+    # -- samplers --------------------------------------------------------------------------------
+    def sampler_points(self, xyz):
+        """Locate the points xyz [n, dim] in the mesh once; returns a :class:`Sampler`."""
+        xyz = _f64(np.asarray(xyz, dtype=np.float64).reshape(-1, self.dim))
+        sid = C.c_int64(-1)
+        self._check(self.lib.glims_sampler_create_points(self._h, xyz.shape[0], _ptr(xyz, _dp), 0, C.byref(sid)))
+        return Sampler(self, int(sid.value), None)
+
+    def sampler_grid(self, origin, spacing, size):
+        """Locate the points origin + index * spacing of a grid with size[a] points along axis a (x fastest)."""
+        o, sp = _f64(origin, (self.dim,)), _f64(spacing, (self.dim,))
+        sz = np.ascontiguousarray(size, dtype=np.int64)
+        assert sz.shape == (self.dim,)
+        sid = C.c_int64(-1)
+        self._check(self.lib.glims_sampler_create_grid(self._h, _ptr(o, _dp), _ptr(sp, _dp), _ptr(sz, _i64p), 0,
+                                                       C.byref(sid)))
+        return Sampler(self, int(sid.value), tuple(int(v) for v in sz))
+
     # -- multi-GPU -------------------------------------------------------------------------------
     @staticmethod
     def comm_unique_id():
@@ -479,3 +507,72 @@ class Handle:
         assert len(sp) == len(pr) + 1 and len(rc) == len(pr)
         self._check(self.lib.glims_set_halo(self._h, len(pr), _ptr(pr, _i32p), _ptr(sp, _i64p), _ptr(si, _i32p),
                                             _ptr(rc, _i64p)))
+
+
+class Sampler:
+    """A set of query points located once in a handle's mesh (``glims_sampler_*``): ``cells`` (the caller's cell index, -1
+    outside the mesh) and barycentric ``weights`` stay on the device and serve any number of ``apply`` calls."""
+
+    def __init__(self, handle, sid, grid_size):
+        self.handle, self.id, self.grid_size = handle, sid, grid_size
+        n, nf = C.c_int64(0), C.c_int64(0)
+        handle._check(handle.lib.glims_sampler_info(handle._h, sid, C.byref(n), C.byref(nf)))
+        self.n_points, self.n_found = int(n.value), int(nf.value)
+
+    def _get(self, want_cells, want_weights):
+        h = self.handle
+        cells = np.empty(self.n_points, dtype=np.int32) if want_cells else None
+        w = np.empty((self.n_points, h.dim + 1)) if want_weights else None
+        h._check(h.lib.glims_sampler_get(h._h, self.id, _ptr(cells, _i32p), _ptr(w, _dp)))
+        return cells, w
+
+    @property
+    def cells(self):
+        return self._get(True, False)[0]
+
+    @property
+    def weights(self):
+        return self._get(False, True)[1]
+
+    def apply(self, field, snapshot=None, fill=np.nan):
+        """P f at every point: ``field`` = 'c' (current concentration, or the device snapshot ``snapshot``), 'u' (current
+        displacement) or a nodal array [n_nodes] / [n_nodes, k] in the caller's node order.  Returns [n_points] for a
+        one-dimensional field, [n_points, k] otherwise; points outside the mesh hold ``fill``."""
+        h = self.handle
+        nodal, flat = None, False
+        if isinstance(field, str):
+            if field == 'c':
+                kind, ncomp, flat = (FIELD_C if snapshot is None else FIELD_SNAPSHOT_C), 1, True
+            elif field == 'u':
+                if snapshot is not None:
+                    raise ValueError("snapshots hold the concentration only")
+                kind, ncomp = FIELD_U, h.dim
+            else:
+                raise ValueError("field must be 'c', 'u' or a nodal array")
+        else:
+            a = np.asarray(field, dtype=np.float64)
+            if a.shape[0] != h.n_nodes:
+                raise ValueError("nodal array has %d rows, the mesh %d nodes" % (a.shape[0], h.n_nodes))
+            flat = a.ndim == 1
+            nodal = _f64(a.reshape(h.n_nodes, 1) if flat else a.reshape(h.n_nodes, -1))
+            kind, ncomp = FIELD_HOST, nodal.shape[1]
+        out = np.empty((self.n_points, ncomp))
+        h._check(h.lib.glims_sampler_apply(h._h, self.id, kind, -1 if snapshot is None else int(snapshot),
+                                           _ptr(nodal, _dp), int(ncomp), float(fill), _ptr(out, _dp)))
+        return out[:, 0] if flat else out
+
+    def apply_t(self, r):
+        """P^T r: r [n_points] or [n_points, k] -> nodal [n_nodes] / [n_nodes, k] (caller's node order)."""
+        h = self.handle
+        a = np.asarray(r, dtype=np.float64)
+        flat = a.ndim == 1
+        a = _f64(a.reshape(self.n_points, 1) if flat else a.reshape(self.n_points, a.shape[-1]))
+        g = np.empty((h.n_nodes, a.shape[1]))
+        h._check(h.lib.glims_sampler_apply_t(h._h, self.id, _ptr(a, _dp), int(a.shape[1]), _ptr(g, _dp)))
+        return g[:, 0] if flat else g
+
+    def close(self):
+        h = self.handle
+        if self.id is not None and getattr(h, "_h", None):
+            h._check(h.lib.glims_sampler_destroy(h._h, self.id))
+        self.id = None

@@ -428,11 +428,41 @@ int solve_elastic(glims_ctx* h, AdjWork& wk, const double* rhs, double* x, const
   return cs;
 }
 
+// cell -> vertex map in the internal numbering (AdjointState::cell_nodes; on partitioned handles also the counting rule of
+// the per-label sums), built once per handle by whoever needs it first: a gradient, or a sampler (gl_ensure_cell_nodes)
+template <int D>
+void build_cell_nodes(glims_ctx* h) {
+  AdjointState& a = h->adj;
+  const int64_t n = h->n_own, nn = h->n_nodes;
+  if (a.cell_nodes.n != (size_t)h->n_cells * (D + 1)) {
+    a.cell_nodes.alloc_zero((size_t)h->n_cells * (D + 1), h->st);   // (every entry is written on one GPU; 0 keeps a gap in range)
+    if (h->world <= 1) {
+      hipLaunchKernelGGL(k_cell_nodes<D + 1>, dim3(grid_of(n)), dim3(256), 0, h->st, n, h->pat.cslice_ptr.p,
+                         h->pat.cslots.p, h->pat.celem.p, h->pat.diag_k.p, a.cell_nodes.p);
+      GL_CHECK_LAUNCH();
+    } else {
+      // ghost owners from the halo plan (ghosts grouped by owner: group p = peer_rank[p])
+      std::vector<int32_t> gown((size_t)std::max<int64_t>(1, nn - n), 0);
+      for (int p = 0; p < h->n_peers; ++p)
+        for (int64_t i = h->recv_ptr[p]; i < h->recv_ptr[p + 1]; ++i) gown[(size_t)i] = h->peer_rank[p];
+      dvec<int32_t> d_gown;
+      d_gown.upload(gown, h->st);
+      a.counted.alloc_zero((size_t)std::max<int64_t>(1, h->n_cells), h->st);
+      hipLaunchKernelGGL(k_cell_nodes_all<D + 1>, dim3(grid_of(n)), dim3(256), 0, h->st, n, h->pat.slice_ptr.p, h->pat.cols.p,
+                         h->pat.cslice_ptr.p, h->pat.cslots.p, h->pat.celem.p, a.cell_nodes.p, a.counted.p);
+      GL_CHECK_LAUNCH();
+      hipLaunchKernelGGL(k_cell_counted<D + 1>, dim3(grid_of(h->n_cells)), dim3(256), 0, h->st, h->n_cells, n, h->rank,
+                         d_gown.p, a.cell_nodes.p, a.counted.p);
+      GL_CHECK_LAUNCH();
+      GL_HIP(hipStreamSynchronize(h->st));   // d_gown goes out of scope
+    }
+  }
+}
+
 // the work vectors, targets (internal numbering) and cell-vertex map of one gradient / Hessian call
 template <int D>
 void adjoint_setup(glims_ctx* h, int n_terms, const glims_misfit* terms, bool elastic, AdjWork& wk) {
-  AdjointState& a = h->adj;
-  const int64_t n = h->n_own, nn = h->n_nodes, nd = nn * D;
+  const int64_t nn = h->n_nodes, nd = nn * D;
   const size_t ne = (size_t)h->pat.total_entries;
   wk.vA.alloc(ne);
   wk.dinv.alloc((size_t)nn);
@@ -459,29 +489,7 @@ void adjoint_setup(glims_ctx* h, int n_terms, const glims_misfit* terms, bool el
     GL_CHECK_LAUNCH();
     GL_HIP(hipStreamSynchronize(h->st));   // the staging buffer is reused by the next target
   }
-  if (a.cell_nodes.n != (size_t)h->n_cells * (D + 1)) {
-    a.cell_nodes.alloc_zero((size_t)h->n_cells * (D + 1), h->st);   // (every entry is written on one GPU; 0 keeps a gap in range)
-    if (h->world <= 1) {
-      hipLaunchKernelGGL(k_cell_nodes<D + 1>, dim3(grid_of(n)), dim3(256), 0, h->st, n, h->pat.cslice_ptr.p,
-                         h->pat.cslots.p, h->pat.celem.p, h->pat.diag_k.p, a.cell_nodes.p);
-      GL_CHECK_LAUNCH();
-    } else {
-      // ghost owners from the halo plan (ghosts grouped by owner: group p = peer_rank[p])
-      std::vector<int32_t> gown((size_t)std::max<int64_t>(1, nn - n), 0);
-      for (int p = 0; p < h->n_peers; ++p)
-        for (int64_t i = h->recv_ptr[p]; i < h->recv_ptr[p + 1]; ++i) gown[(size_t)i] = h->peer_rank[p];
-      dvec<int32_t> d_gown;
-      d_gown.upload(gown, h->st);
-      a.counted.alloc_zero((size_t)std::max<int64_t>(1, h->n_cells), h->st);
-      hipLaunchKernelGGL(k_cell_nodes_all<D + 1>, dim3(grid_of(n)), dim3(256), 0, h->st, n, h->pat.slice_ptr.p, h->pat.cols.p,
-                         h->pat.cslice_ptr.p, h->pat.cslots.p, h->pat.celem.p, a.cell_nodes.p, a.counted.p);
-      GL_CHECK_LAUNCH();
-      hipLaunchKernelGGL(k_cell_counted<D + 1>, dim3(grid_of(h->n_cells)), dim3(256), 0, h->st, h->n_cells, n, h->rank,
-                         d_gown.p, a.cell_nodes.p, a.counted.p);
-      GL_CHECK_LAUNCH();
-      GL_HIP(hipStreamSynchronize(h->st));   // d_gown goes out of scope
-    }
-  }
+  build_cell_nodes<D>(h);
 }
 
 template <int D>
@@ -1532,6 +1540,12 @@ int hessian_t(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, const
 }
 
 }  // namespace
+
+const int32_t* gl_ensure_cell_nodes(glims_ctx* h) {
+  if (h->dim == 2) build_cell_nodes<2>(h);
+  else build_cell_nodes<3>(h);
+  return h->adj.cell_nodes.p;
+}
 
 void gl_adjoint_start(glims_ctx* h) {
   AdjointState& a = h->adj;

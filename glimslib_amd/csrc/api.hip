@@ -303,6 +303,7 @@ int glims_destroy(glims_ctx* h) {
   if (h->st_comm) (void)hipStreamSynchronize(h->st_comm);
   for (auto* d : h->snapshots) delete d;
   h->snapshots.clear();
+  gl_sampler_destroy_all(h);
   gl_comm_destroy(h);
   if (getenv("GLIMS_VERBOSE")) fprintf(stderr, "glims: deferred linear solves that ran out of iterations: %lld\n", (long long)h->stats_defer_miss);
   mailbox_close(h);
@@ -833,6 +834,63 @@ int glims_adjoint_stats(const glims_ctx* h, int64_t out[6], double* ms) {
   out[5] = (int64_t)a.traj.size();
   if (ms) *ms = a.ms_backward;
   return GLIMS_OK;
+}
+
+int glims_sampler_create_points(glims_ctx* h, int64_t n, const double* xyz, int flags, int64_t* id) {
+  return guarded(h, [&]() {
+    GL_REQUIRE(id, "glims_sampler_create_points: null id");
+    GL_REQUIRE(flags == 0, "glims_sampler_create_points: flags is reserved and must be 0");
+    GL_REQUIRE(n >= 0 && (n == 0 || xyz), "glims_sampler_create_points: n < 0 or null coordinates");
+    static const double none = 0.0;
+    *id = gl_sampler_create(h, n, xyz ? xyz : &none, nullptr, nullptr, nullptr);
+    return GLIMS_OK;
+  });
+}
+
+int glims_sampler_create_grid(glims_ctx* h, const double* origin, const double* spacing, const int64_t* size, int flags,
+                              int64_t* id) {
+  return guarded(h, [&]() {
+    GL_REQUIRE(id && origin && spacing && size, "glims_sampler_create_grid: null argument");
+    GL_REQUIRE(flags == 0, "glims_sampler_create_grid: flags is reserved and must be 0");
+    *id = gl_sampler_create(h, 0, nullptr, origin, spacing, size);
+    return GLIMS_OK;
+  });
+}
+
+int glims_sampler_info(glims_ctx* h, int64_t id, int64_t* n_points, int64_t* n_found) {
+  return guarded(h, [&]() {
+    gl_sampler_info(h, id, n_points, n_found);
+    return GLIMS_OK;
+  });
+}
+
+int glims_sampler_get(glims_ctx* h, int64_t id, int32_t* cell, double* w) {
+  return guarded(h, [&]() {
+    gl_sampler_get(h, id, cell, w);
+    return GLIMS_OK;
+  });
+}
+
+int glims_sampler_apply(glims_ctx* h, int64_t id, int field, int64_t snapshot, const double* nodal, int ncomp, double fill,
+                        double* out) {
+  return guarded(h, [&]() {
+    gl_sampler_apply(h, id, field, snapshot, nodal, ncomp, fill, out);
+    return GLIMS_OK;
+  });
+}
+
+int glims_sampler_apply_t(glims_ctx* h, int64_t id, const double* r, int ncomp, double* g) {
+  return guarded(h, [&]() {
+    gl_sampler_apply_t(h, id, r, ncomp, g);
+    return GLIMS_OK;
+  });
+}
+
+int glims_sampler_destroy(glims_ctx* h, int64_t id) {
+  return guarded(h, [&]() {
+    gl_sampler_destroy(h, id);
+    return GLIMS_OK;
+  });
 }
 
 int glims_project(glims_ctx* h, const double* rhs, double* x, int ncomp, double rtol) {

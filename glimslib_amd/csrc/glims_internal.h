@@ -456,6 +456,8 @@ struct AdjointState {
   ~AdjointState() { clear(); }
 };
 
+struct GlSampler;   // sample.hip
+
 struct glims_ctx {
   int dim = 0, nv = 0, device = 0;
   int n_labels = 0;                        // of the last glims_set_materials
@@ -648,6 +650,7 @@ struct glims_ctx {
   void* tr_user = nullptr;
 
   AdjointState adj;
+  std::vector<GlSampler*> samplers;         // owned (sample.hip); a destroyed sampler leaves a nullptr so that ids stay valid
 
   std::string err;
 };
@@ -713,6 +716,20 @@ int gl_adjoint_hessian(glims_ctx* h, int n_terms, const glims_misfit* terms, int
                        const double* dir_rho, const double* dir_gamma, const double* dir_c0, double* J, double* dD,
                        double* drho, double* dgamma, double* dc0, double* hv_D, double* hv_rho, double* hv_gamma,
                        double* hv_c0, double* stats);
+// AdjointState::cell_nodes ([n_cells][nv], internal cell order, the caller's vertex order), built on first use: the gradients
+// and the samplers share ONE builder
+const int32_t* gl_ensure_cell_nodes(glims_ctx* h);
+
+// sample.hip ----------------------------------------------------------------------------------------
+int64_t gl_sampler_create(glims_ctx* h, int64_t n, const double* xyz, const double* origin, const double* spacing,
+                          const int64_t* size);   // xyz != nullptr: point set; else the grid
+void gl_sampler_info(glims_ctx* h, int64_t id, int64_t* n_points, int64_t* n_found);
+void gl_sampler_get(glims_ctx* h, int64_t id, int32_t* cell, double* w);
+void gl_sampler_apply(glims_ctx* h, int64_t id, int field, int64_t snapshot, const double* nodal, int ncomp, double fill,
+                      double* out);
+void gl_sampler_apply_t(glims_ctx* h, int64_t id, const double* r, int ncomp, double* g);
+void gl_sampler_destroy(glims_ctx* h, int64_t id);
+void gl_sampler_destroy_all(glims_ctx* h);
 
 // mg.hip --------------------------------------------------------------------------------------------
 void gl_mesh_metrics(glims_ctx* h, const HostPattern& hp, const double* xyz_old);

@@ -1,0 +1,923 @@
+// Samplers: a fixed set of query points -- a voxel grid or a point set -- located once in the handle's
+// simplex mesh, kept as (cell, nodes, barycentric weights) per point, and applied to nodal fields:  P f (gather) and P^T r.
+//
+// Location is CELL-parallel "claiming": every cell visits the query points inside its (slightly padded) bounding box and, when
+// it accepts a point (min lambda >= -GLIMS_SAMPLE_EPS), does an integer atomicMin of its CALLER index into cell[p].  Integer
+// min does not depend on the order of arrival, so the winner -- the smallest caller index among the accepting cells -- is
+// bitwise reproducible.  A grid's points under a box are an index range (no coordinates exist in memory); a point set is
+// binned once into a uniform grid over its own bounding box (radix sort by bin), and a cell walks the bin rows under its box,
+// each row one contiguous range of the sorted points.  Cells whose box holds more than GL_SAMPLE_BIG candidates (a coarse mesh
+// under a fine grid) are queued and get a block each.  One pass over the points then computes the winner's weights.
+//
+// P^T r without float atomics, store-then-sum: the found points are sorted by winning cell (stable: point order inside a
+// cell), cut into chunks of at most GL_SAMPLE_CHUNK points that never straddle two cells; pass 1 writes per chunk
+// q[chunk][a] = sum_p w[p][a] r[p] in list order, pass 2 is row-owned -- every node walks its incidence list and adds, cell by
+// cell and chunk by chunk, the entries of its own vertex slot.
+#include "glims_internal.h"
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <limits>
+
+#include <rocprim/device/device_scan.hpp>
+
+#define GL_SAMPLE_BIG 256      // candidates under one cell's box above which the cell gets a block of its own
+#define GL_SAMPLE_CHUNK 256    // points per chunk of a cell's list in the transpose
+
+struct GlSampler {
+  int64_t n = 0, n_found = 0;
+  bool is_grid = false;
+  dvec<int32_t> cell;          // [n] caller's cell index, -1 = outside the mesh
+  dvec<int32_t> node;          // [n][nv] internal node of the winner's vertices (caller's vertex order; 0 when outside)
+  dvec<double> w;              // [n][nv]
+  // transpose (single-rank handles)
+  bool have_t = false;
+  int64_t n_chunks = 0;
+  dvec<int32_t> order;         // [n] points sorted by winning internal cell, the n_found found ones first
+  dvec<int32_t> cptr;          // [n_cells + 1] a cell's points in `order`
+  dvec<int32_t> chunk_ptr;     // [n_cells + 1] a cell's chunks
+  dvec<int32_t> chunk_cell;    // [n_chunks]
+  // staging, grown on demand
+  dvec<double> f_ext, f_int, out, q, g_int;
+};
+
+namespace {
+
+inline unsigned grid_of(int64_t n, int bs = 256) { return (unsigned)std::max<int64_t>(1, (n + bs - 1) / bs); }
+#define GL_CHECK_LAUNCH() GL_HIP(hipGetLastError())
+
+struct GridSpec {
+  double o[3], s[3];
+  long long n[3];
+};
+struct BinSpec {
+  double lo[3], hi[3], inv_h[3];
+  int nb[3];
+};
+
+// One cell's vertices and the rows of its inverse edge matrix: lambda_a = r[a-1] . (x - x0), a = 1..D, lambda_0 = 1 - sum.
+template <int D>
+struct CellGeo {
+  double x0[D], r[D][D], lo[D], hi[D];
+  bool ok;
+};
+
+template <int D>
+__device__ __forceinline__ void load_cell(const double* __restrict__ xyz, const int32_t* __restrict__ nd, CellGeo<D>& g) {
+  double x[D + 1][D];
+#pragma unroll
+  for (int m = 0; m <= D; ++m)
+#pragma unroll
+    for (int a = 0; a < D; ++a) x[m][a] = xyz[(int64_t)nd[m] * D + a];
+#pragma unroll
+  for (int a = 0; a < D; ++a) {
+    g.x0[a] = x[0][a];
+    double lo = x[0][a], hi = x[0][a];
+#pragma unroll
+    for (int m = 1; m <= D; ++m) {
+      lo = fmin(lo, x[m][a]);
+      hi = fmax(hi, x[m][a]);
+    }
+    g.lo[a] = lo;
+    g.hi[a] = hi;
+  }
+  double e[D][D];   // e[k] = x_{k+1} - x_0
+#pragma unroll
+  for (int k = 0; k < D; ++k)
+#pragma unroll
+    for (int a = 0; a < D; ++a) e[k][a] = x[k + 1][a] - x[0][a];
+  double det;
+  if constexpr (D == 2) {
+    det = e[0][0] * e[1][1] - e[0][1] * e[1][0];
+    g.r[0][0] = e[1][1] / det;
+    g.r[0][1] = -e[1][0] / det;
+    g.r[1][0] = -e[0][1] / det;
+    g.r[1][1] = e[0][0] / det;
+  } else {
+    double c[3][3];   // c[k] = e[k+1] x e[k+2]
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const double* p = e[(k + 1) % 3];
+      const double* q = e[(k + 2) % 3];
+      c[k][0] = p[1] * q[2] - p[2] * q[1];
+      c[k][1] = p[2] * q[0] - p[0] * q[2];
+      c[k][2] = p[0] * q[1] - p[1] * q[0];
+    }
+    det = e[0][0] * c[0][0] + e[0][1] * c[0][1] + e[0][2] * c[0][2];
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+      for (int a = 0; a < 3; ++a) g.r[k][a] = c[k][a] / det;
+  }
+  g.ok = det != 0.0 && isfinite(det);   // a cell this rank does not hold has all-zero vertices: never accepts
+}
+
+template <int D>
+__device__ __forceinline__ void bary(const CellGeo<D>& g, const double* x, double* lam /*[D+1]*/) {
+  double d[D];
+#pragma unroll
+  for (int a = 0; a < D; ++a) d[a] = x[a] - g.x0[a];
+  double s = 0.0;
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    double t = 0.0;
+#pragma unroll
+    for (int a = 0; a < D; ++a) t += g.r[k][a] * d[a];
+    lam[k + 1] = t;
+    s += t;
+  }
+  lam[0] = 1.0 - s;
+}
+
+template <int D>
+__device__ __forceinline__ bool accepts(const CellGeo<D>& g, const double* x) {
+  double lam[D + 1];
+  bary<D>(g, x, lam);
+  double m = lam[0];
+#pragma unroll
+  for (int k = 1; k <= D; ++k) m = fmin(m, lam[k]);   // fmin drops a NaN, the comparison below must not: test each
+  bool fin = true;
+#pragma unroll
+  for (int k = 0; k <= D; ++k) fin = fin && (lam[k] == lam[k]);
+  return fin && m >= -GLIMS_SAMPLE_EPS;
+}
+
+// What the bounding-box prefilter may miss is only what the cell would not accept: a point accepted with lambda >= -eps lies
+// within eps x (cell extent) of the cell; the pad is ten times that plus the rounding of the index arithmetic.
+template <int D>
+__device__ __forceinline__ double box_pad(const CellGeo<D>& g, int a, double extra) {
+  double ext = 0.0;
+#pragma unroll
+  for (int b = 0; b < D; ++b) ext += g.hi[b] - g.lo[b];
+  return 1e-9 * ext + 1e-12 * (fabs(g.lo[a]) + fabs(g.hi[a]) + extra);
+}
+
+// the coordinate numpy computes as origin + index * spacing: two roundings, no contraction into one fused operation
+__device__ __forceinline__ double grid_coord(const GridSpec& g, int a, long long i) {
+  return __dadd_rn(g.o[a], __dmul_rn((double)i, g.s[a]));
+}
+
+// index range [i0, i1] of the grid points inside the padded box along axis a; false = none (also for non-finite input)
+template <int D>
+__device__ __forceinline__ bool grid_range(const CellGeo<D>& g, const GridSpec& gs, int a, long long& i0, long long& i1) {
+  const double pad = box_pad<D>(g, a, fabs(gs.o[a]));
+  const double t0 = (g.lo[a] - pad - gs.o[a]) / gs.s[a];
+  const double t1 = (g.hi[a] + pad - gs.o[a]) / gs.s[a];
+  const double nmax = (double)(gs.n[a] - 1);
+  if (!(t0 <= nmax) || !(t1 >= 0.0)) return false;
+  i0 = t0 > 0.0 ? (long long)ceil(t0) : 0;
+  i1 = t1 < nmax ? (long long)floor(t1) : gs.n[a] - 1;
+  return i0 <= i1;
+}
+
+__device__ __forceinline__ int bin_of(const BinSpec& b, int a, double x) {   // clamped; monotone in x
+  const double t = (x - b.lo[a]) * b.inv_h[a];
+  if (!(t > 0.0)) return 0;
+  return t >= (double)(b.nb[a] - 1) ? b.nb[a] - 1 : (int)t;
+}
+
+template <int D>
+__device__ __forceinline__ bool bin_range(const CellGeo<D>& g, const BinSpec& b, int a, int& b0, int& b1) {
+  const double pad = box_pad<D>(g, a, 0.0);
+  const double lo = g.lo[a] - pad, hi = g.hi[a] + pad;
+  if (!(lo <= b.hi[a]) || !(hi >= b.lo[a])) return false;   // the box misses the point set (or is not finite)
+  b0 = bin_of(b, a, lo);
+  b1 = bin_of(b, a, hi);
+  return b0 <= b1;
+}
+
+// ---- grid ----------------------------------------------------------------------------------------------------------------
+// One thread per cell; boxes with more than GL_SAMPLE_BIG grid points are queued for k_claim_grid_big.
+template <int D>
+__global__ __launch_bounds__(256) void k_claim_grid(int64_t n_cells, const int32_t* __restrict__ cell_nodes,
+                                                    const double* __restrict__ xyz, const int32_t* __restrict__ new2old,
+                                                    GridSpec gs, int* __restrict__ cell, int32_t* __restrict__ big,
+                                                    int* __restrict__ n_big) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n_cells) return;
+  CellGeo<D> g;
+  load_cell<D>(xyz, cell_nodes + e * (D + 1), g);
+  if (!g.ok) return;
+  long long i0[3] = {0, 0, 0}, i1[3] = {0, 0, 0};
+#pragma unroll
+  for (int a = 0; a < D; ++a)
+    if (!grid_range<D>(g, gs, a, i0[a], i1[a])) return;
+  const long long cnt = (i1[0] - i0[0] + 1) * (i1[1] - i0[1] + 1) * (i1[2] - i0[2] + 1);
+  if (cnt > GL_SAMPLE_BIG) {
+    big[atomicAdd(n_big, 1)] = (int32_t)e;
+    return;
+  }
+  const int id = new2old ? new2old[e] : (int)e;
+  double x[3];
+  for (long long k = i0[2]; k <= i1[2]; ++k) {
+    if (D == 3) x[2] = grid_coord(gs, 2, k);
+    for (long long j = i0[1]; j <= i1[1]; ++j) {
+      x[1] = grid_coord(gs, 1, j);
+      for (long long i = i0[0]; i <= i1[0]; ++i) {
+        x[0] = grid_coord(gs, 0, i);
+        if (accepts<D>(g, x)) atomicMin(cell + ((k * gs.n[1] + j) * gs.n[0] + i), id);
+      }
+    }
+  }
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void k_claim_grid_big(int n_big, const int32_t* __restrict__ big,
+                                                        const int32_t* __restrict__ cell_nodes,
+                                                        const double* __restrict__ xyz, const int32_t* __restrict__ new2old,
+                                                        GridSpec gs, int* __restrict__ cell) {
+  if ((int)blockIdx.x >= n_big) return;
+  const int64_t e = big[blockIdx.x];
+  CellGeo<D> g;
+  load_cell<D>(xyz, cell_nodes + e * (D + 1), g);
+  long long i0[3] = {0, 0, 0}, i1[3] = {0, 0, 0};
+#pragma unroll
+  for (int a = 0; a < D; ++a)
+    if (!grid_range<D>(g, gs, a, i0[a], i1[a])) return;
+  const long long nx = i1[0] - i0[0] + 1, ny = i1[1] - i0[1] + 1, nz = i1[2] - i0[2] + 1;
+  const int id = new2old ? new2old[e] : (int)e;
+  for (long long t = threadIdx.x; t < nx * ny * nz; t += blockDim.x) {
+    const long long i = i0[0] + t % nx, j = i0[1] + (t / nx) % ny, k = i0[2] + t / (nx * ny);
+    double x[3];
+    x[0] = grid_coord(gs, 0, i);
+    x[1] = grid_coord(gs, 1, j);
+    if (D == 3) x[2] = grid_coord(gs, 2, k);
+    if (accepts<D>(g, x)) atomicMin(cell + ((k * gs.n[1] + j) * gs.n[0] + i), id);
+  }
+}
+
+// ---- point sets ------------------------------------------------------------------------------------------------------------
+template <int D>
+__global__ void k_point_bins(int64_t n, const double* __restrict__ xyz, BinSpec b, uint32_t trash, uint32_t* __restrict__ key,
+                             int32_t* __restrict__ val) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n) return;
+  uint32_t k = 0;
+  bool ok = true;
+#pragma unroll
+  for (int a = D - 1; a >= 0; --a) {
+    const double x = xyz[p * D + a];
+    ok = ok && x >= b.lo[a] && x <= b.hi[a];   // false for NaN
+    k = k * (uint32_t)b.nb[a] + (uint32_t)bin_of(b, a, x);
+  }
+  key[p] = ok ? k : trash;
+  val[p] = (int32_t)p;
+}
+
+template <int D>
+__global__ void k_gather_points(int64_t n, const int32_t* __restrict__ idx, const double* __restrict__ xyz,
+                                double* __restrict__ out) {
+  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= n) return;
+  const int64_t p = idx[q];
+#pragma unroll
+  for (int a = 0; a < D; ++a) out[q * D + a] = xyz[p * D + a];
+}
+
+// sorted points of bin row (j, k), bins b0 .. b1 along x: one contiguous range
+__device__ __forceinline__ void row_range(const BinSpec& b, const int32_t* __restrict__ bin_ptr, int b0, int b1, int j, int k,
+                                          int& lo, int& hi) {
+  const int64_t row = ((int64_t)k * b.nb[1] + j) * b.nb[0];
+  lo = bin_ptr[row + b0];
+  hi = bin_ptr[row + b1 + 1];
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void k_claim_points(int64_t n_cells, const int32_t* __restrict__ cell_nodes,
+                                                      const double* __restrict__ xyz, const int32_t* __restrict__ new2old,
+                                                      BinSpec bs, const int32_t* __restrict__ bin_ptr,
+                                                      const double* __restrict__ pts /*sorted*/, const int32_t* __restrict__ pid,
+                                                      int* __restrict__ cell, int32_t* __restrict__ big, int* __restrict__ n_big) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n_cells) return;
+  CellGeo<D> g;
+  load_cell<D>(xyz, cell_nodes + e * (D + 1), g);
+  if (!g.ok) return;
+  int b0[3] = {0, 0, 0}, b1[3] = {0, 0, 0};
+#pragma unroll
+  for (int a = 0; a < D; ++a)
+    if (!bin_range<D>(g, bs, a, b0[a], b1[a])) return;
+  long long cnt = 0;
+  for (int k = b0[2]; k <= b1[2]; ++k)
+    for (int j = b0[1]; j <= b1[1]; ++j) {
+      int lo, hi;
+      row_range(bs, bin_ptr, b0[0], b1[0], j, k, lo, hi);
+      cnt += hi - lo;
+    }
+  if (cnt == 0) return;
+  if (cnt > GL_SAMPLE_BIG) {
+    big[atomicAdd(n_big, 1)] = (int32_t)e;
+    return;
+  }
+  const int id = new2old ? new2old[e] : (int)e;
+  for (int k = b0[2]; k <= b1[2]; ++k)
+    for (int j = b0[1]; j <= b1[1]; ++j) {
+      int lo, hi;
+      row_range(bs, bin_ptr, b0[0], b1[0], j, k, lo, hi);
+      for (int q = lo; q < hi; ++q) {
+        double x[D];
+#pragma unroll
+        for (int a = 0; a < D; ++a) x[a] = pts[(int64_t)q * D + a];
+        if (accepts<D>(g, x)) atomicMin(cell + pid[q], id);
+      }
+    }
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void k_claim_points_big(int n_big, const int32_t* __restrict__ big,
+                                                          const int32_t* __restrict__ cell_nodes,
+                                                          const double* __restrict__ xyz, const int32_t* __restrict__ new2old,
+                                                          BinSpec bs, const int32_t* __restrict__ bin_ptr,
+                                                          const double* __restrict__ pts, const int32_t* __restrict__ pid,
+                                                          int* __restrict__ cell) {
+  if ((int)blockIdx.x >= n_big) return;
+  const int64_t e = big[blockIdx.x];
+  CellGeo<D> g;
+  load_cell<D>(xyz, cell_nodes + e * (D + 1), g);
+  int b0[3] = {0, 0, 0}, b1[3] = {0, 0, 0};
+#pragma unroll
+  for (int a = 0; a < D; ++a)
+    if (!bin_range<D>(g, bs, a, b0[a], b1[a])) return;
+  const int id = new2old ? new2old[e] : (int)e;
+  for (int k = b0[2]; k <= b1[2]; ++k)
+    for (int j = b0[1]; j <= b1[1]; ++j) {
+      int lo, hi;
+      row_range(bs, bin_ptr, b0[0], b1[0], j, k, lo, hi);
+      for (int q = lo + (int)threadIdx.x; q < hi; q += blockDim.x) {
+        double x[D];
+#pragma unroll
+        for (int a = 0; a < D; ++a) x[a] = pts[(int64_t)q * D + a];
+        if (accepts<D>(g, x)) atomicMin(cell + pid[q], id);
+      }
+    }
+}
+
+// ---- the winner's weights ------------------------------------------------------------------------------------------------
+__global__ void k_fill_i32(int64_t n, int v, int* __restrict__ x) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) x[i] = v;
+}
+__global__ void k_invert_cells(int64_t n, const int32_t* __restrict__ fwd, int32_t* __restrict__ inv) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) inv[fwd[i]] = (int32_t)i;
+}
+
+// cell[p]: INT_MAX (nobody claimed) -> -1.  key / val (optional): the sort input of the transpose, key = internal cell of the
+// winner, n_cells for the points outside.
+template <int D>
+__global__ __launch_bounds__(256) void k_weights(int64_t n, int64_t n_cells, const double* __restrict__ pts /*or null: grid*/,
+                                                 GridSpec gs, const int32_t* __restrict__ cell_nodes,
+                                                 const double* __restrict__ xyz, const int32_t* __restrict__ old2new,
+                                                 int* __restrict__ cell, int32_t* __restrict__ node, double* __restrict__ w,
+                                                 uint32_t* __restrict__ key, int32_t* __restrict__ val,
+                                                 unsigned long long* __restrict__ n_found) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int c = p < n ? cell[p] : -1;
+  const bool found = c >= 0 && c < n_cells;
+  // one counter update per block: a per-thread atomicAdd on ONE address serialises 140 k wave-level adds at 9 M points
+  const int found_here = __syncthreads_count(found);
+  if (threadIdx.x == 0 && found_here) atomicAdd(n_found, (unsigned long long)found_here);
+  if (p >= n) return;
+  int64_t e = n_cells;
+  double lam[D + 1];
+  int32_t nd[D + 1];
+#pragma unroll
+  for (int m = 0; m <= D; ++m) {
+    lam[m] = 0.0;
+    nd[m] = 0;
+  }
+  if (found) {
+    e = old2new ? old2new[c] : c;
+    double x[3];
+    if (pts) {
+#pragma unroll
+      for (int a = 0; a < D; ++a) x[a] = pts[p * D + a];
+    } else {
+      const long long i = p % gs.n[0], j = (p / gs.n[0]) % gs.n[1], k = p / (gs.n[0] * gs.n[1]);
+      x[0] = grid_coord(gs, 0, i);
+      x[1] = grid_coord(gs, 1, j);
+      if (D == 3) x[2] = grid_coord(gs, 2, k);
+    }
+#pragma unroll
+    for (int m = 0; m <= D; ++m) nd[m] = cell_nodes[e * (D + 1) + m];
+    CellGeo<D> g;
+    load_cell<D>(xyz, nd, g);
+    bary<D>(g, x, lam);
+  } else {
+    cell[p] = -1;
+  }
+#pragma unroll
+  for (int m = 0; m <= D; ++m) {
+    node[p * (D + 1) + m] = nd[m];
+    w[p * (D + 1) + m] = lam[m];
+  }
+  if (key) {
+    key[p] = (uint32_t)e;
+    val[p] = (int32_t)p;
+  }
+}
+
+// ---- P f -------------------------------------------------------------------------------------------------------------------
+// One thread per point: NV x (4 B node + 8 B weight) + 8 BS B out, the nodal field gathered through the caches.  BS = 0: any
+// component count by looping.
+template <int NV, int BS>
+__global__ __launch_bounds__(256) void k_sample(int64_t n, int ncomp, const int32_t* __restrict__ cell,
+                                                const int32_t* __restrict__ node, const double* __restrict__ w,
+                                                const double* __restrict__ f, double fill, double* __restrict__ out) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n) return;
+  const int nc = BS ? BS : ncomp;
+  if (cell[p] < 0) {
+    for (int a = 0; a < nc; ++a) out[p * nc + a] = fill;
+    return;
+  }
+  int32_t nd[NV];
+  double wt[NV];
+#pragma unroll
+  for (int m = 0; m < NV; ++m) {
+    nd[m] = node[p * NV + m];
+    wt[m] = w[p * NV + m];
+  }
+  if constexpr (BS > 0) {
+    double acc[BS];
+#pragma unroll
+    for (int a = 0; a < BS; ++a) acc[a] = 0.0;
+#pragma unroll
+    for (int m = 0; m < NV; ++m)
+#pragma unroll
+      for (int a = 0; a < BS; ++a) acc[a] += wt[m] * f[(int64_t)nd[m] * BS + a];
+#pragma unroll
+    for (int a = 0; a < BS; ++a) out[p * BS + a] = acc[a];
+  } else {
+    for (int a = 0; a < nc; ++a) {
+      double acc = 0.0;
+#pragma unroll
+      for (int m = 0; m < NV; ++m) acc += wt[m] * f[(int64_t)nd[m] * nc + a];
+      out[p * nc + a] = acc;
+    }
+  }
+}
+
+// caller's node order <-> internal
+__global__ void k_nodal_in(int64_t n, int bs, const int32_t* __restrict__ old2new, const double* __restrict__ ext,
+                           double* __restrict__ in) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * bs) return;
+  const int64_t o = i / bs;
+  in[(int64_t)old2new[o] * bs + (i - o * bs)] = ext[i];
+}
+__global__ void k_nodal_out(int64_t n, int bs, const int32_t* __restrict__ old2new, const double* __restrict__ in,
+                            double* __restrict__ ext) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * bs) return;
+  const int64_t o = i / bs;
+  ext[i] = in[(int64_t)old2new[o] * bs + (i - o * bs)];
+}
+
+// ---- P^T r -----------------------------------------------------------------------------------------------------------------
+__global__ void k_chunk_count(int64_t n_cells, const int32_t* __restrict__ cptr, int32_t* __restrict__ cnt) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e > n_cells) return;
+  cnt[e] = e < n_cells ? (cptr[e + 1] - cptr[e] + GL_SAMPLE_CHUNK - 1) / GL_SAMPLE_CHUNK : 0;
+}
+__global__ void k_chunk_cells(int64_t n_cells, const int32_t* __restrict__ chunk_ptr, int32_t* __restrict__ chunk_cell) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n_cells) return;
+  for (int c = chunk_ptr[e]; c < chunk_ptr[e + 1]; ++c) chunk_cell[c] = (int32_t)e;
+}
+
+// pass 1, one thread per chunk: q[chunk][a][comp] = sum over the chunk's points, in list order, of w[p][a] r[p][comp]
+template <int NV>
+__global__ __launch_bounds__(256) void k_sample_t_cells(int64_t n_chunks, int ncomp, const int32_t* __restrict__ chunk_cell,
+                                                        const int32_t* __restrict__ chunk_ptr, const int32_t* __restrict__ cptr,
+                                                        const int32_t* __restrict__ order, const double* __restrict__ w,
+                                                        const double* __restrict__ r, double* __restrict__ q) {
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= n_chunks) return;
+  const int e = chunk_cell[c];
+  const int lo = cptr[e] + (int)(c - chunk_ptr[e]) * GL_SAMPLE_CHUNK;
+  const int hi = min(lo + GL_SAMPLE_CHUNK, cptr[e + 1]);
+  for (int a = 0; a < ncomp; ++a) {
+    double acc[NV];
+#pragma unroll
+    for (int m = 0; m < NV; ++m) acc[m] = 0.0;
+    for (int k = lo; k < hi; ++k) {
+      const int64_t p = order[k];
+      const double rv = r[p * ncomp + a];
+#pragma unroll
+      for (int m = 0; m < NV; ++m) acc[m] += w[p * NV + m] * rv;
+    }
+#pragma unroll
+    for (int m = 0; m < NV; ++m) q[(c * NV + m) * ncomp + a] = acc[m];
+  }
+}
+
+// pass 2, one thread per node (row-owned, like the assembly): the node's cells in the order of its incidence list, each
+// cell's chunks in chunk order, the entry of the node's own vertex slot
+template <int NV>
+__global__ __launch_bounds__(256) void k_sample_t(int64_t n_own, int ncomp, const int64_t* __restrict__ cslice_ptr,
+                                                  const uint32_t* __restrict__ cslots, const int32_t* __restrict__ celem,
+                                                  const uint8_t* __restrict__ diag_k, const int32_t* __restrict__ chunk_ptr,
+                                                  const double* __restrict__ q, double* __restrict__ g) {
+  const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= n_own) return;
+  const int64_t s = row >> 6, lane = row & 63;
+  const int64_t cbase = cslice_ptr[s];
+  const int clen = (int)((cslice_ptr[s + 1] - cbase) >> 6);
+  const uint32_t dk = diag_k[row];
+  double acc[GLIMS_SAMPLE_MAX_COMP];
+#pragma unroll
+  for (int a = 0; a < GLIMS_SAMPLE_MAX_COMP; ++a) acc[a] = 0.0;
+  for (int k = 0; k < clen; ++k) {
+    const int64_t ci = cbase + (int64_t)k * GL_WAVE + lane;
+    const int32_t e = celem[ci];
+    if (e < 0) continue;
+    const int c0 = chunk_ptr[e], c1 = chunk_ptr[e + 1];
+    if (c0 == c1) continue;
+    const uint32_t sl = cslots[ci];
+    int own = 0;
+#pragma unroll
+    for (int m = 0; m < NV; ++m)
+      if (((sl >> (8 * m)) & 255u) == dk) own = m;
+    for (int64_t c = c0; c < c1; ++c)
+#pragma unroll
+      for (int a = 0; a < GLIMS_SAMPLE_MAX_COMP; ++a)
+        if (a < ncomp) acc[a] += q[(c * NV + own) * ncomp + a];
+  }
+#pragma unroll
+  for (int a = 0; a < GLIMS_SAMPLE_MAX_COMP; ++a)
+    if (a < ncomp) g[row * ncomp + a] = acc[a];
+}
+
+GlSampler& sampler_of(glims_ctx* h, int64_t id, const char* who) {
+  if (id < 0 || id >= (int64_t)h->samplers.size() || !h->samplers[(size_t)id])
+    throw glims_error(GLIMS_E_USAGE, std::string(who) + ": unknown sampler id " + std::to_string(id));
+  return *h->samplers[(size_t)id];
+}
+
+void need_memory(const char* who, size_t need) {
+  size_t fr = 0, tot = 0;
+  GL_HIP(hipMemGetInfo(&fr, &tot));
+  if (need > fr)
+    throw glims_error(GLIMS_E_HIP, std::string(who) + ": needs about " + std::to_string(need >> 20) +
+                                       " MiB of device memory, " + std::to_string(fr >> 20) + " MiB are free");
+}
+
+template <int D>
+void create_t(glims_ctx* h, GlSampler& s, const double* xyz_host, const GridSpec& gs) {
+  constexpr int NV = D + 1;
+  const int64_t n = s.n, ne = h->n_cells;
+  hipStream_t st = h->st;
+  const bool want_t = h->world <= 1;
+  // the sampler itself: 4 + NV (4 + 8) B per point (+ 4 B of order and ~8 B per cell for the transpose); transient: the claim
+  // queue, the inverse cell permutation, the sort's keys / values twice, a point set's coordinates twice and its bins
+  const size_t keep = (size_t)n * (4 + NV * 12 + (want_t ? 4 : 0)) + (want_t ? (size_t)ne * 12 : 0);
+  const size_t temp = (size_t)ne * 8 + (size_t)n * (16 + (s.is_grid ? 0 : 16 * D + 8)) + (64u << 20);
+  need_memory("glims_sampler_create", keep + temp);
+
+  const int32_t* cell_nodes = gl_ensure_cell_nodes(h);
+  const int32_t* new2old = h->cell_new2old.p;   // nullptr = identity (host symbolic phase)
+  s.cell.alloc((size_t)std::max<int64_t>(1, n));
+  s.node.alloc((size_t)std::max<int64_t>(1, n) * NV);
+  s.w.alloc((size_t)std::max<int64_t>(1, n) * NV);
+  dvec<int32_t> big;
+  dvec<int> n_big;
+  dvec<unsigned long long> d_found;
+  big.alloc((size_t)std::max<int64_t>(1, ne));
+  n_big.alloc_zero(1, st);
+  d_found.alloc_zero(1, st);
+  dvec<double> d_pts;
+  if (n > 0 && ne > 0) {
+    hipLaunchKernelGGL(k_fill_i32, dim3(grid_of(n)), dim3(256), 0, st, n, INT_MAX, s.cell.p);
+    GL_CHECK_LAUNCH();
+    int nb_host = 0;
+    if (s.is_grid) {
+      hipLaunchKernelGGL(k_claim_grid<D>, dim3(grid_of(ne)), dim3(256), 0, st, ne, cell_nodes, h->xyz_new.p, new2old, gs,
+                         s.cell.p, big.p, n_big.p);
+      GL_CHECK_LAUNCH();
+      GL_HIP(hipMemcpyAsync(&nb_host, n_big.p, sizeof(int), hipMemcpyDeviceToHost, st));
+      GL_HIP(hipStreamSynchronize(st));
+      if (nb_host > 0) {
+        hipLaunchKernelGGL(k_claim_grid_big<D>, dim3(nb_host), dim3(256), 0, st, nb_host, big.p, cell_nodes, h->xyz_new.p,
+                           new2old, gs, s.cell.p);
+        GL_CHECK_LAUNCH();
+      }
+    } else {
+      // bins over the bounding box of the (finite) query points: about two points per bin, not more bins than cells
+      BinSpec bs;
+      for (int a = 0; a < 3; ++a) {
+        bs.lo[a] = std::numeric_limits<double>::infinity();
+        bs.hi[a] = -std::numeric_limits<double>::infinity();
+        bs.inv_h[a] = 0.0;
+        bs.nb[a] = 1;
+      }
+      for (int64_t p = 0; p < n; ++p) {
+        bool fin = true;
+        for (int a = 0; a < D; ++a) fin = fin && std::isfinite(xyz_host[p * D + a]);
+        if (!fin) continue;
+        for (int a = 0; a < D; ++a) {
+          bs.lo[a] = std::min(bs.lo[a], xyz_host[p * D + a]);
+          bs.hi[a] = std::max(bs.hi[a], xyz_host[p * D + a]);
+        }
+      }
+      if (bs.lo[0] <= bs.hi[0]) {   // at least one finite point
+        double vol = 1.0;
+        int live = 0;
+        for (int a = 0; a < D; ++a)
+          if (bs.hi[a] > bs.lo[a]) {
+            vol *= bs.hi[a] - bs.lo[a];
+            ++live;
+          }
+        const double want = (double)std::max<int64_t>(1, std::min<int64_t>({n / 2, ne, (int64_t)1 << 27}));
+        const double hb = live ? std::pow(vol / want, 1.0 / live) : 1.0;
+        int64_t total = 1;
+        for (int a = 0; a < D; ++a) {
+          const double ext = bs.hi[a] - bs.lo[a];
+          if (ext > 0.0 && hb > 0.0) {
+            bs.nb[a] = (int)std::min(1024.0, std::max(1.0, std::floor(ext / hb)));
+            bs.inv_h[a] = bs.nb[a] / ext;
+          }
+          total *= bs.nb[a];
+        }
+        d_pts.upload(xyz_host, (size_t)n * D, st);
+        dvec<uint32_t> k_in, k_out;
+        dvec<int32_t> v_in, pid, bin_ptr;
+        dvec<double> pts_sorted;
+        k_in.alloc((size_t)n);
+        k_out.alloc((size_t)n);
+        v_in.alloc((size_t)n);
+        pid.alloc((size_t)n);
+        pts_sorted.alloc((size_t)n * D);
+        bin_ptr.alloc((size_t)total + 2);
+        hipLaunchKernelGGL(k_point_bins<D>, dim3(grid_of(n)), dim3(256), 0, st, n, d_pts.p, bs, (uint32_t)total, k_in.p,
+                           v_in.p);
+        GL_CHECK_LAUNCH();
+        int bits = 1;
+        while (((int64_t)1 << bits) <= total) ++bits;
+        gl_sort_pairs_u32(h, k_in.p, k_out.p, v_in.p, pid.p, (size_t)n, bits);
+        gl_offsets_of_sorted_keys(h, k_out.p, n, total + 1, bin_ptr.p);   // bin_ptr[total]: where the points outside start
+        hipLaunchKernelGGL(k_gather_points<D>, dim3(grid_of(n)), dim3(256), 0, st, n, pid.p, d_pts.p, pts_sorted.p);
+        GL_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_claim_points<D>, dim3(grid_of(ne)), dim3(256), 0, st, ne, cell_nodes, h->xyz_new.p, new2old, bs,
+                           bin_ptr.p, pts_sorted.p, pid.p, s.cell.p, big.p, n_big.p);
+        GL_CHECK_LAUNCH();
+        GL_HIP(hipMemcpyAsync(&nb_host, n_big.p, sizeof(int), hipMemcpyDeviceToHost, st));
+        GL_HIP(hipStreamSynchronize(st));
+        if (nb_host > 0) {
+          hipLaunchKernelGGL(k_claim_points_big<D>, dim3(nb_host), dim3(256), 0, st, nb_host, big.p, cell_nodes,
+                             h->xyz_new.p, new2old, bs, bin_ptr.p, pts_sorted.p, pid.p, s.cell.p);
+          GL_CHECK_LAUNCH();
+        }
+        GL_HIP(hipStreamSynchronize(st));   // the sort buffers go out of scope
+      }
+    }
+  }
+  big.release();
+  if (n == 0) return;
+  if (ne == 0) {
+    hipLaunchKernelGGL(k_fill_i32, dim3(grid_of(n)), dim3(256), 0, st, n, INT_MAX, s.cell.p);
+    GL_CHECK_LAUNCH();
+  }
+  if (!s.is_grid && !d_pts.p) d_pts.upload(xyz_host, (size_t)n * D, st);
+
+  // the winner's weights (and the transpose's sort input)
+  dvec<int32_t> c_old2new;
+  if (new2old && ne > 0) {
+    c_old2new.alloc((size_t)ne);
+    hipLaunchKernelGGL(k_invert_cells, dim3(grid_of(ne)), dim3(256), 0, st, ne, new2old, c_old2new.p);
+    GL_CHECK_LAUNCH();
+  }
+  dvec<uint32_t> k_in, k_out;
+  dvec<int32_t> v_in;
+  if (want_t) {
+    k_in.alloc((size_t)n);
+    k_out.alloc((size_t)n);
+    v_in.alloc((size_t)n);
+    s.order.alloc((size_t)n);
+  }
+  hipLaunchKernelGGL(k_weights<D>, dim3(grid_of(n)), dim3(256), 0, st, n, ne, s.is_grid ? nullptr : d_pts.p, gs, cell_nodes,
+                     h->xyz_new.p, c_old2new.p, s.cell.p, s.node.p, s.w.p, k_in.p, v_in.p, d_found.p);
+  GL_CHECK_LAUNCH();
+  unsigned long long nf = 0;
+  GL_HIP(hipMemcpyAsync(&nf, d_found.p, sizeof(nf), hipMemcpyDeviceToHost, st));
+  GL_HIP(hipStreamSynchronize(st));
+  s.n_found = (int64_t)nf;
+  if (!want_t) return;
+
+  int bits = 1;
+  while (((int64_t)1 << bits) <= ne) ++bits;
+  gl_sort_pairs_u32(h, k_in.p, k_out.p, v_in.p, s.order.p, (size_t)n, bits);   // stable: point order inside a cell
+  s.cptr.alloc((size_t)ne + 1);
+  gl_offsets_of_sorted_keys(h, k_out.p, n, ne, s.cptr.p);
+  dvec<int32_t> cnt;
+  cnt.alloc((size_t)ne + 1);
+  s.chunk_ptr.alloc((size_t)ne + 1);
+  hipLaunchKernelGGL(k_chunk_count, dim3(grid_of(ne + 1)), dim3(256), 0, st, ne, s.cptr.p, cnt.p);
+  GL_CHECK_LAUNCH();
+  {
+    size_t bytes = 0;
+    GL_HIP(rocprim::exclusive_scan(nullptr, bytes, cnt.p, s.chunk_ptr.p, (int32_t)0, (size_t)ne + 1, rocprim::plus<int32_t>(), st));
+    dvec<unsigned char> tmp;
+    tmp.alloc(std::max<size_t>(bytes, 16));
+    GL_HIP(rocprim::exclusive_scan(tmp.p, bytes, cnt.p, s.chunk_ptr.p, (int32_t)0, (size_t)ne + 1, rocprim::plus<int32_t>(), st));
+    int32_t nch = 0;
+    GL_HIP(hipMemcpyAsync(&nch, s.chunk_ptr.p + ne, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    GL_HIP(hipStreamSynchronize(st));
+    s.n_chunks = nch;
+  }
+  s.chunk_cell.alloc((size_t)std::max<int64_t>(1, s.n_chunks));
+  if (ne > 0) {
+    hipLaunchKernelGGL(k_chunk_cells, dim3(grid_of(ne)), dim3(256), 0, st, ne, s.chunk_ptr.p, s.chunk_cell.p);
+    GL_CHECK_LAUNCH();
+  }
+  GL_HIP(hipStreamSynchronize(st));
+  s.have_t = true;
+}
+
+template <int NV>
+void launch_sample(glims_ctx* h, GlSampler& s, int ncomp, const double* f, double fill, double* out) {
+  const dim3 g(grid_of(s.n)), b(256);
+#define GL_SAMPLE_CASE(BS)                                                                                              \
+  hipLaunchKernelGGL((k_sample<NV, BS>), g, b, 0, h->st, s.n, ncomp, s.cell.p, s.node.p, s.w.p, f, fill, out)
+  switch (ncomp) {
+    case 1: GL_SAMPLE_CASE(1); break;
+    case 2: GL_SAMPLE_CASE(2); break;
+    case 3: GL_SAMPLE_CASE(3); break;
+    default: GL_SAMPLE_CASE(0); break;
+  }
+#undef GL_SAMPLE_CASE
+  GL_CHECK_LAUNCH();
+}
+
+}  // namespace
+
+int64_t gl_sampler_create(glims_ctx* h, int64_t n, const double* xyz, const double* origin, const double* spacing,
+                          const int64_t* size) {
+  const int D = h->dim;
+  GridSpec gs;
+  for (int a = 0; a < 3; ++a) {
+    gs.o[a] = 0.0;
+    gs.s[a] = 1.0;
+    gs.n[a] = 1;
+  }
+  if (!xyz) {
+    n = 1;
+    for (int a = 0; a < D; ++a) {
+      GL_REQUIRE(size[a] > 0, "glims_sampler_create_grid: size[" + std::to_string(a) + "] = " + std::to_string(size[a]) +
+                                  " is not positive");
+      GL_REQUIRE(spacing[a] > 0.0 && std::isfinite(spacing[a]),
+                 "glims_sampler_create_grid: spacing[" + std::to_string(a) + "] is not positive");
+      GL_REQUIRE(std::isfinite(origin[a]), "glims_sampler_create_grid: origin is not finite");
+      gs.o[a] = origin[a];
+      gs.s[a] = spacing[a];
+      gs.n[a] = size[a];
+      GL_REQUIRE(size[a] < INT_MAX / n, "glims_sampler_create_grid: more than 2^31 - 1 points");
+      n *= size[a];
+    }
+  }
+  GL_REQUIRE(n < INT_MAX, "glims_sampler_create: more than 2^31 - 2 points");
+  GL_REQUIRE(h->xyz_new.n == (size_t)h->n_nodes * D, "mesh coordinates missing");
+  GL_REQUIRE(h->world > 1 || h->n_own == h->n_nodes,
+             "glims_sampler_create: a handle with ghost nodes needs its halo plan and transport first");
+  auto* s = new GlSampler();
+  try {
+    s->n = n;
+    s->is_grid = !xyz;
+    if (D == 2) create_t<2>(h, *s, xyz, gs);
+    else create_t<3>(h, *s, xyz, gs);
+  } catch (...) {
+    (void)hipStreamSynchronize(h->st);
+    delete s;
+    throw;
+  }
+  h->samplers.push_back(s);
+  return (int64_t)h->samplers.size() - 1;
+}
+
+void gl_sampler_info(glims_ctx* h, int64_t id, int64_t* n_points, int64_t* n_found) {
+  GlSampler& s = sampler_of(h, id, "glims_sampler_info");
+  if (n_points) *n_points = s.n;
+  if (n_found) *n_found = s.n_found;
+}
+
+void gl_sampler_get(glims_ctx* h, int64_t id, int32_t* cell, double* w) {
+  GlSampler& s = sampler_of(h, id, "glims_sampler_get");
+  if (s.n == 0) return;
+  if (cell) GL_HIP(hipMemcpyAsync(cell, s.cell.p, (size_t)s.n * sizeof(int32_t), hipMemcpyDeviceToHost, h->st));
+  if (w) GL_HIP(hipMemcpyAsync(w, s.w.p, (size_t)s.n * h->nv * sizeof(double), hipMemcpyDeviceToHost, h->st));
+  GL_HIP(hipStreamSynchronize(h->st));
+}
+
+void gl_sampler_apply(glims_ctx* h, int64_t id, int field, int64_t snapshot, const double* nodal, int ncomp, double fill,
+                      double* out) {
+  GlSampler& s = sampler_of(h, id, "glims_sampler_apply");
+  GL_REQUIRE(ncomp >= 1 && ncomp <= GLIMS_SAMPLE_MAX_COMP,
+             "glims_sampler_apply: ncomp = " + std::to_string(ncomp) + " outside 1 .. 8");
+  GL_REQUIRE(out || s.n == 0, "glims_sampler_apply: null output");
+  const double* f = nullptr;
+  switch (field) {
+    case GLIMS_FIELD_C:
+      GL_REQUIRE(h->have_state, "glims_sampler_apply: GLIMS_FIELD_C before glims_set_state");
+      GL_REQUIRE(ncomp == 1, "glims_sampler_apply: GLIMS_FIELD_C has 1 component");
+      f = h->c.p;
+      break;
+    case GLIMS_FIELD_U:
+      GL_REQUIRE(h->have_mech && h->U.p, "glims_sampler_apply: GLIMS_FIELD_U needs glims_setup(with_mechanics=1)");
+      GL_REQUIRE(ncomp == h->dim, "glims_sampler_apply: GLIMS_FIELD_U has dim components");
+      f = h->U.p;
+      break;
+    case GLIMS_FIELD_SNAPSHOT_C:
+      GL_REQUIRE(snapshot >= 0 && snapshot < (int64_t)h->snapshots.size() && h->snapshots[(size_t)snapshot],
+                 "glims_sampler_apply: unknown snapshot id " + std::to_string(snapshot));
+      GL_REQUIRE(ncomp == 1, "glims_sampler_apply: GLIMS_FIELD_SNAPSHOT_C has 1 component");
+      f = h->snapshots[(size_t)snapshot]->p;
+      break;
+    case GLIMS_FIELD_HOST: {
+      GL_REQUIRE(nodal, "glims_sampler_apply: GLIMS_FIELD_HOST needs the nodal array");
+      const size_t nn = (size_t)h->n_nodes * ncomp;
+      if (s.f_ext.n < nn) {
+        need_memory("glims_sampler_apply", 2 * nn * sizeof(double));
+        s.f_ext.alloc(nn);
+        s.f_int.alloc(nn);
+      }
+      GL_HIP(hipMemcpyAsync(s.f_ext.p, nodal, nn * sizeof(double), hipMemcpyHostToDevice, h->st));
+      hipLaunchKernelGGL(k_nodal_in, dim3(grid_of((int64_t)nn)), dim3(256), 0, h->st, h->n_nodes, ncomp, h->d_old2new.p,
+                         s.f_ext.p, s.f_int.p);
+      GL_CHECK_LAUNCH();
+      f = s.f_int.p;
+      break;
+    }
+    default:
+      GL_REQUIRE(false, "glims_sampler_apply: unknown field " + std::to_string(field));
+  }
+  if (s.n == 0) return;
+  const size_t no = (size_t)s.n * ncomp;
+  if (s.out.n < no) {
+    need_memory("glims_sampler_apply", no * sizeof(double));
+    s.out.alloc(no);
+  }
+  if (h->nv == 3) launch_sample<3>(h, s, ncomp, f, fill, s.out.p);
+  else launch_sample<4>(h, s, ncomp, f, fill, s.out.p);
+  GL_HIP(hipMemcpyAsync(out, s.out.p, no * sizeof(double), hipMemcpyDeviceToHost, h->st));
+  GL_HIP(hipStreamSynchronize(h->st));
+}
+
+void gl_sampler_apply_t(glims_ctx* h, int64_t id, const double* r, int ncomp, double* g) {
+  GlSampler& s = sampler_of(h, id, "glims_sampler_apply_t");
+  GL_REQUIRE(h->world <= 1, "glims_sampler_apply_t: not available on a partitioned handle (the per-cell sums would need the "
+                            "globally winning cell on every rank that holds it)");
+  GL_REQUIRE(ncomp >= 1 && ncomp <= GLIMS_SAMPLE_MAX_COMP,
+             "glims_sampler_apply_t: ncomp = " + std::to_string(ncomp) + " outside 1 .. 8");
+  GL_REQUIRE(g && (r || s.n == 0), "glims_sampler_apply_t: null argument");
+  const int64_t nn = h->n_nodes;
+  const size_t ng = (size_t)nn * ncomp, nr = (size_t)std::max<int64_t>(1, s.n) * ncomp;
+  const size_t nq = (size_t)std::max<int64_t>(1, s.n_chunks) * h->nv * ncomp;
+  if (s.g_int.n < ng || s.f_ext.n < ng || s.out.n < nr || s.q.n < nq) {
+    need_memory("glims_sampler_apply_t", (2 * ng + nr + nq) * sizeof(double));
+    if (s.g_int.n < ng) s.g_int.alloc(ng);
+    if (s.f_ext.n < ng) {
+      s.f_ext.alloc(ng);
+      s.f_int.alloc(ng);
+    }
+    if (s.out.n < nr) s.out.alloc(nr);
+    if (s.q.n < nq) s.q.alloc(nq);
+  }
+  if (s.n > 0 && s.have_t && s.n_chunks > 0) {
+    GL_HIP(hipMemcpyAsync(s.out.p, r, (size_t)s.n * ncomp * sizeof(double), hipMemcpyHostToDevice, h->st));
+    if (h->nv == 3)
+      hipLaunchKernelGGL(k_sample_t_cells<3>, dim3(grid_of(s.n_chunks)), dim3(256), 0, h->st, s.n_chunks, ncomp,
+                         s.chunk_cell.p, s.chunk_ptr.p, s.cptr.p, s.order.p, s.w.p, s.out.p, s.q.p);
+    else
+      hipLaunchKernelGGL(k_sample_t_cells<4>, dim3(grid_of(s.n_chunks)), dim3(256), 0, h->st, s.n_chunks, ncomp,
+                         s.chunk_cell.p, s.chunk_ptr.p, s.cptr.p, s.order.p, s.w.p, s.out.p, s.q.p);
+    GL_CHECK_LAUNCH();
+    const DevPattern& pt = h->pat;
+    if (h->nv == 3)
+      hipLaunchKernelGGL(k_sample_t<3>, dim3(grid_of(h->n_own)), dim3(256), 0, h->st, h->n_own, ncomp, pt.cslice_ptr.p,
+                         pt.cslots.p, pt.celem.p, pt.diag_k.p, s.chunk_ptr.p, s.q.p, s.g_int.p);
+    else
+      hipLaunchKernelGGL(k_sample_t<4>, dim3(grid_of(h->n_own)), dim3(256), 0, h->st, h->n_own, ncomp, pt.cslice_ptr.p,
+                         pt.cslots.p, pt.celem.p, pt.diag_k.p, s.chunk_ptr.p, s.q.p, s.g_int.p);
+    GL_CHECK_LAUNCH();
+  } else {
+    GL_HIP(hipMemsetAsync(s.g_int.p, 0, ng * sizeof(double), h->st));
+  }
+  hipLaunchKernelGGL(k_nodal_out, dim3(grid_of((int64_t)ng)), dim3(256), 0, h->st, nn, ncomp, h->d_old2new.p, s.g_int.p,
+                     s.f_ext.p);
+  GL_CHECK_LAUNCH();
+  GL_HIP(hipMemcpyAsync(g, s.f_ext.p, ng * sizeof(double), hipMemcpyDeviceToHost, h->st));
+  GL_HIP(hipStreamSynchronize(h->st));
+}
+
+void gl_sampler_destroy(glims_ctx* h, int64_t id) {
+  (void)sampler_of(h, id, "glims_sampler_destroy");
+  GL_HIP(hipStreamSynchronize(h->st));
+  delete h->samplers[(size_t)id];
+  h->samplers[(size_t)id] = nullptr;
+}
+
+void gl_sampler_destroy_all(glims_ctx* h) {
+  for (auto* s : h->samplers) delete s;
+  h->samplers.clear();
+}

@@ -378,6 +378,13 @@ class DistributedHandle:
     def adjoint_stats(self):
         return self.h.adjoint_stats()
 
+    # -- samplers (collective: every rank passes the same points) --------------------------------------------------------
+    def sampler_points(self, xyz):
+        return DistributedSampler(self, self.h.sampler_points(xyz))
+
+    def sampler_grid(self, origin, spacing, size):
+        return DistributedSampler(self, self.h.sampler_grid(origin, spacing, size))
+
     # -- global <-> local -----------------------------------------------------------------------------------------
     def _local(self, v, bs=1):
         v = np.asarray(v, dtype=np.float64).reshape(self.n_global, bs) if bs > 1 else np.asarray(v, dtype=np.float64)
@@ -422,3 +429,52 @@ class DistributedHandle:
             if want_u:
                 ug[gid] = uu
         return cg, (ug.reshape(-1) if want_u else None)
+
+
+class DistributedSampler:
+    """
+    ``_backend.Sampler`` of a partitioned run.  Every rank locates the (same) points in its own cells and translates its
+    winners to global cell ids; per point the SMALLEST GLOBAL CELL ID over the ranks wins -- the cell a single-GPU sampler
+    picks, because every cell is local to some rank and each rank has already taken the minimum over its own -- and among the
+    ranks that hold that cell the smallest rank supplies the value.  Every rank returns the same bits.
+    """
+
+    def __init__(self, dh, local):
+        self.dh, self.local = dh, local
+        self.n_points, self.grid_size = local.n_points, local.grid_size
+        lc = local.cells
+        g = np.where(lc >= 0, dh.part.cell_ids[np.maximum(lc, 0)], -1).astype(np.int64)
+        parts = [None] * dh.world
+        dh.dist.all_gather_object(parts, g)
+        big = np.iinfo(np.int64).max
+        allg = np.stack([np.where(a >= 0, a, big) for a in parts])          # [world, n]
+        win = allg.min(axis=0)
+        self.cells = np.where(win < big, win, -1).astype(np.int64)           # global cell ids
+        self.n_found = int((self.cells >= 0).sum())
+        holds = (allg == win[None, :]) & (win < big)[None, :]
+        self.supplier = np.where(self.cells >= 0, holds.argmax(axis=0), -1)  # smallest rank that holds the winner
+        self._mine = np.flatnonzero(self.supplier == dh.rank)
+
+    def apply(self, field, snapshot=None, fill=np.nan):
+        """As ``Sampler.apply``; a nodal array is given in the GLOBAL node order.  The fields' ghost values must be current
+        (they are after step / solve_mechanics)."""
+        dh = self.dh
+        if snapshot is not None:
+            raise ValueError("partitioned runs keep no device snapshots")
+        if isinstance(field, str):
+            loc = self.local.apply(field, fill=fill)
+        else:
+            a = np.asarray(field, dtype=np.float64)
+            loc = self.local.apply(a[dh.part.global_ids], fill=fill)
+        parts = [None] * dh.world
+        dh.dist.all_gather_object(parts, (self._mine, loc[self._mine]))
+        out = np.full(loc.shape, fill, dtype=np.float64)
+        for idx, v in parts:
+            out[idx] = v
+        return out
+
+    def apply_t(self, r):
+        raise NotImplementedError("apply_t: not available on partitioned runs (glims_sampler_apply_t refuses them)")
+
+    def close(self):
+        self.local.close()

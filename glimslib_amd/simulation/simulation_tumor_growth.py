@@ -293,6 +293,43 @@ class TumorGrowth(FenicsSimulation):
         self.solution.assign(u_previous)
         self.solver = HipTimeStepSolver(self, h, mechanics)
 
+    # -- images of the results ------------------------------------------------------------------------------------
+    def sample_image(self, subspace_name, recording_step, like=None, origin=None, spacing=None, size=None, fill=np.nan):
+        """
+        The recorded field `subspace_name` ('concentration' | 'displacement') of `recording_step` evaluated on a voxel grid
+        -> utils.data_io.Image (array [z,] y, x [, component]; voxels outside the mesh hold `fill`).  The grid is that of
+        the Image `like`, or origin / spacing / size (points per axis).  What the reference does voxel by voxel with
+        create_image_from_fenics_function (data_io.py:176-225), here one gather on the device: the grid is located in the
+        mesh once per simulation and grid, and serves every recording step.  With run(results_on_device=True) the
+        concentration goes from its device snapshot to the image without a nodal copy on the host; the displacement through
+        the lazy elastic solve of the results.  Partitioned runs: collective, every rank returns the same image.
+        """
+        from ..utils.data_io import _grid_image
+        if like is not None:
+            origin, spacing, size = like.GetOrigin(), like.GetSpacing(), like.GetSize()
+        if origin is None or spacing is None or size is None:
+            raise ValueError("sample_image needs `like` or origin, spacing and size")
+        h = self._backend
+        if h is None:
+            raise RuntimeError("sample_image needs a run() first")
+        key = (tuple(float(v) for v in origin), tuple(float(v) for v in spacing), tuple(int(v) for v in size))
+        cache = getattr(self, '_image_samplers', None)
+        if cache is None or cache[0] is not h:
+            cache = self._image_samplers = (h, {})
+        if key not in cache[1]:
+            cache[1][key] = h.sampler_grid(*key)
+        sampler = cache[1][key]
+        sid = self.functionspace.get_subspace_id(subspace_name)
+        obs = self.results.get_result(recording_step)
+        if obs is None:
+            raise KeyError("no result for recording step %r" % (recording_step,))
+        field = obs.get_field()
+        if sid == 1 and isinstance(field, DeviceSnapshotFunction) and isinstance(h, _backend.Handle):
+            out = sampler.apply('c', snapshot=field.snapshot_id, fill=fill)
+        else:
+            out = sampler.apply(np.asarray(field.components[sid]), fill=fill)
+        return _grid_image(out, key[2], key[0], key[1])
+
     # -- discrete adjoint (the backward half of the reference's adjoint entry points) -----------------------------
     def _adjoint_raw(self, terms, need_dD=True, elastic=False):
         """(J, dD, drho, dgamma, dc0) per tissue label of the run recorded by ``run(record_adjoint=True)``; with elastic=True

@@ -326,9 +326,71 @@ def get_measures_from_image(image):
     return origin, size, spacing, extent, dim, image.GetNumberOfComponentsPerPixel()
 
 
-def create_image_from_fenics_function(function, size_new=None):
+def _throw_away_handle(mesh, device):
+    """A handle on a bare mesh (labels 0, no set-up): all a sampler needs."""
+    from .. import _backend
+    return _backend.Handle(mesh.points, mesh.cells, np.zeros(len(mesh.cells), dtype=np.int32), device=int(device))
+
+
+def _grid_image(sampled, size, origin, spacing):
+    """[n_points] / [n_points, k] in grid order (x fastest) -> Image with array [z,] y, x [, k]."""
+    vec = sampled.ndim == 2
+    shape = tuple(int(v) for v in reversed(size)) + ((sampled.shape[1],) if vec else ())
+    return Image(sampled.reshape(shape), origin, spacing, is_vector=vec)
+
+
+def sample_function_on_grid(function, origin, spacing, size, device=0, fill=np.nan):
+    """Evaluates a P1 function (any simplex mesh) at origin + index * spacing, `size` points per axis, on the device ->
+    Image; voxels outside the mesh hold `fill`.  The device counterpart of the reference's voxel loop
+    (create_image_from_fenics_function, data_io.py:176-225)."""
+    h = _throw_away_handle(function.mesh, device)
+    try:
+        s = h.sampler_grid(origin, spacing, size)
+        out = s.apply(function.values(), fill=fill)
+    finally:
+        h.close()
+    return _grid_image(out, size, origin, spacing)
+
+
+def interpolate_non_matching(source_function, target, device=0, fill=np.nan):
+    """The reference's helper of this name (image_based_optimization.py:1410-1412, fenics.LagrangeInterpolator): the P1
+    source function evaluated at the nodes of another mesh.  `target`: a Mesh, a function space (its mesh) or a point array.
+    Returns a Function on the target mesh, or the array of values for a point array; points outside the source mesh hold
+    `fill`."""
+    from ..fenics_local import Function
+    tmesh = None
+    if isinstance(target, Mesh):
+        tmesh = target
+    elif callable(getattr(target, 'mesh', None)):
+        tmesh = target.mesh()
+    elif isinstance(getattr(target, 'mesh', None), Mesh):
+        tmesh = target.mesh
+    pts = tmesh.points if tmesh is not None else np.asarray(target, dtype=np.float64)
+    h = _throw_away_handle(source_function.mesh, device)
+    try:
+        s = h.sampler_points(pts)
+        out = s.apply(source_function.values(), fill=fill)
+    finally:
+        h.close()
+    if tmesh is None:
+        return out
+    return Function(tmesh, {None: out}, name=source_function.name(), space=target if tmesh is not target else None)
+
+
+def create_image_from_fenics_function(function, size_new=None, device=None):
     """Samples a P1 function of a structured mesh on the regular grid of its vertices (or on `size_new` points per
-    axis) -> Image.  On the mesh's own grid the samples are the nodal values (one sort, no point location)."""
+    axis) -> Image.  On the mesh's own grid the samples are the nodal values (one sort, no point location).
+    device=None: evaluation on the host (small grids only).  With a device ordinal the sampler evaluates the function there,
+    on any simplex mesh (the grid spans the mesh's bounding box; default size: the structured mesh's own)."""
+    if device is not None:
+        pts = function.mesh.points
+        lo, hi = pts.min(axis=0), pts.max(axis=0)
+        if size_new is None:
+            size_new = get_measures_from_structured_mesh(function.mesh)[1]
+        size_new = np.asarray(size_new, dtype=int)
+        axes = [np.linspace(lo[i], hi[i], size_new[i]) for i in range(len(lo))]
+        spacing = [compute_spacing(a) if len(a) > 1 else 1.0 for a in axes]
+        return sample_function_on_grid(function, lo, spacing, size_new, device=device)
     origin, size, spacing, extent, dim, vdim = get_measures_from_function(function)
     vals = function.values()
     if size_new is None or tuple(size_new) == tuple(size):

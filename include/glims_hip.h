@@ -514,6 +514,53 @@ int glims_adjoint_stats(const glims_ctx* h, int64_t out[6], double* ms);
  * (helper_classes.py:1566-1618, 1736-1786).  Ghost entries of rhs are ignored, ghosts of x are filled. */
 int glims_project(glims_ctx* h, const double* rhs, double* x, int ncomp, double rtol);
 
+/* ---- samplers: a P1 field evaluated at arbitrary points --------------------------------------------------------------------
+ * The reference evaluates FE functions off their mesh point by point: create_image_from_fenics_function loops function(Point)
+ * over every voxel (glimslib/utils/data_io.py:176-225), and fenics.LagrangeInterpolator moves fields between non-matching
+ * meshes (optimization_workflow/image_based_optimization.py:1410-1412, used at :1092; image_based_optimization_atlas.py:57,
+ * 103-104).  Both are "evaluate a P1 field at points".  A sampler is a fixed set of query points located ONCE in the handle's
+ * mesh and kept on the device as cell[p] and barycentric weights w[p][dim+1]; it is then applied to as many fields as the
+ * caller likes.  A sampler needs only glims_create (with GLIMS_FIELD_HOST a handle made from a bare mesh is an interpolator
+ * for any nodal array); it owns its buffers and touches neither the solver state nor glims_stats.
+ *
+ * The operator P:
+ *   - barycentric coordinates lambda_a(x) of x in cell T from the cell's vertex coordinates, fp64, lambda_0 = 1 - sum lambda_a;
+ *   - T accepts x iff min_a lambda_a >= -GLIMS_SAMPLE_EPS;
+ *   - among the accepting cells the one with the SMALLEST CALLER CELL INDEX wins (independent of the internal renumbering);
+ *   - no accepting cell: cell = -1, weights 0, sampled value = fill; the transpose ignores such points.
+ * Location is an integer atomic min per (cell, point) pair, the transpose uses no float atomics: both are bitwise reproducible.
+ *
+ * Partitioned handles (world > 1): samplers are rank-local, NOT collective.  A rank locates in its local cells and reports its
+ * local cell index; merging over the ranks is the host program's (smallest GLOBAL cell id wins).  The fields' ghost values must
+ * be current (glims_step / glims_solve_mechanics leave them so).  glims_sampler_apply_t returns GLIMS_E_USAGE there. */
+#define GLIMS_SAMPLE_EPS 1e-10   /* far above the rounding kappa(T) 2^-52 of lambda on every mesh class this library runs
+                                    (kappa <= 7.6e4 measured on random-point Delaunay meshes), twelve orders below a voxel */
+#define GLIMS_FIELD_C 0            /* the current concentration */
+#define GLIMS_FIELD_U 1            /* the current displacement (ncomp = dim; needs glims_setup(with_mechanics=1)) */
+#define GLIMS_FIELD_SNAPSHOT_C 2   /* the device snapshot `snapshot` of glims_snapshot_save: no host round trip */
+#define GLIMS_FIELD_HOST 3         /* nodal[n_nodes][ncomp], caller's node order */
+#define GLIMS_SAMPLE_MAX_COMP 8
+
+/* Points xyz[n][dim] (n = 0 is valid) / the voxel centres origin + index * spacing of a grid of size[dim] points per axis, x
+ * fastest (point p = (k * size[1] + j) * size[0] + i: the order of an image array [z][y][x]); no coordinates are uploaded for a
+ * grid.  flags is reserved and must be 0.  The id (>= 0) is valid until glims_sampler_destroy / glims_destroy. */
+int glims_sampler_create_points(glims_ctx* h, int64_t n, const double* xyz, int flags, int64_t* id);
+int glims_sampler_create_grid(glims_ctx* h, const double* origin, const double* spacing, const int64_t* size, int flags,
+                              int64_t* id);
+int glims_sampler_info(glims_ctx* h, int64_t id, int64_t* n_points, int64_t* n_found);   /* outputs may be NULL */
+/* cell[n]: the caller's cell index or -1;  w[n][dim+1]: the weights in the vertex order of the caller's `cells` row.  Either
+ * may be NULL. */
+int glims_sampler_get(glims_ctx* h, int64_t id, int32_t* cell, double* w);
+/* out[n][ncomp] = P f (ncomp 1..8; GLIMS_FIELD_C / _SNAPSHOT_C: 1, GLIMS_FIELD_U: dim); points outside the mesh get `fill`
+ * (NaN is what the reference's images hold there).  nodal is read for GLIMS_FIELD_HOST only, snapshot for _SNAPSHOT_C only. */
+int glims_sampler_apply(glims_ctx* h, int64_t id, int field, int64_t snapshot, const double* nodal, int ncomp, double fill,
+                        double* out);
+/* g[n_nodes][ncomp] = P^T r, r[n][ncomp], caller's node order; values of r at points outside the mesh are not read into any
+ * sum.  Per cell, the products w r are summed in point order (long lists in fixed chunks, added in chunk order), per node
+ * the cells in the order of the row's incidence list: the same bits on every call and on every handle of the same mesh. */
+int glims_sampler_apply_t(glims_ctx* h, int64_t id, const double* r, int ncomp, double* g);
+int glims_sampler_destroy(glims_ctx* h, int64_t id);   /* glims_destroy releases what is left */
+
 /* ---- single-node multi-GPU (one process per GPU, RCCL over xGMI) ------------------------------------- */
 
 #define GLIMS_UNIQUE_ID_BYTES 256   /* two RCCL unique ids: halo communicator + reduction communicator */
