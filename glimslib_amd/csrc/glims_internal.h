@@ -569,7 +569,6 @@ struct glims_ctx {
   double d2_r1 = 0.0;                      // ... and the Newton residual its second solve started from
   int d2_off = 0, d2_backoff = 8, d2_good = 0;   // steps for which the guess stays unused after one that missed the target; the length
                                            // doubles with every miss (8 .. 256) and returns to 8 after 32 guesses that did not
-  dvec<double> cheb_dir;                   // the running solve's direction d [n_nodes]
   dvec<int> cheb_plan;                     // [1] iteration count computed on the device (a step's first, warm-started solve)
   dvec<float> vKel32;                      // single-precision copy of K_el (inner solves of the elasticity solver)
   // vectors (internal numbering; length n_nodes unless noted)
@@ -676,7 +675,7 @@ void gl_launch_spmv(glims_ctx* h, hipStream_t st, int n_launch, const int32_t* s
                     double* partials, int partial_off, const int* done, const float* vals32 = nullptr,
                     hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 void gl_launch_cheb(glims_ctx* h, hipStream_t st, int n_launch, const int32_t* slice_list, const double* vals,
-                    const float* vals32, const double* y_in, double* y_out, double* b, const double* dinv, double* dvec,
+                    const float* vals32, const double* y_in, double* y_out, double* b, const double* dinv, const double* y_prev,
                     double* ylast, double* x, const uint8_t* fixed, double c1, double c2, int k, int m_host, const int* plan,
                     int want_res, const PackMap& pm, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, int shift = 0,
                     double* nrm = nullptr);

@@ -11,6 +11,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 
 namespace {
 
@@ -837,7 +838,7 @@ __global__ __launch_bounds__(GL_WAVE) void k_rd_matfree(
 // NT: values and columns are streamed exactly once per SpMV -> non-temporal, so that they do not displace the
 // gathered x entries from L2 / Infinity Cache
 // DK >= 0 (fused dot product): also returns x at the row's own column through xdiag (slot dk of the row), so that
-// the dot y.x does not read x[row] a second time
+// the dot y.x does not read x[row] a second time; `adiag` receives the diagonal's stored value A_ii the same way
 // `rl` = the lane's own row length: slots [rl, len) are padding (value 0, column = the row itself) and are NOT read -- the
 // rows of a slice are sorted by length, so the active lanes of a slot form a prefix and the memory system fetches only the
 // lines they touch.  On an unstructured mesh the padding is +19.5 % of the entries (sigma = 256); its bytes used to be
@@ -845,7 +846,7 @@ __global__ __launch_bounds__(GL_WAVE) void k_rd_matfree(
 template <int COMP, int UNR, int NT, int WANT_DIAG, class VT>
 __device__ __forceinline__ double spmv_row(const int32_t* __restrict__ cc, const uint16_t* __restrict__ c16,
                                             int32_t wb, const VT* __restrict__ v, const double* __restrict__ x,
-                                            int len, int rl, int dk, double& xdiag) {
+                                            int len, int rl, int dk, double& xdiag, double& adiag) {
   constexpr bool NTC = NT == 1, NTV = NT != 0;   // NT = 2: only the 8-byte value stream is non-temporal
   // (the loops run to the SLICE's length on every lane -- the column decode reads window bases across lanes, which needs
   //  all of them active -- and the loads are predicated on the lane's own row length)
@@ -882,7 +883,10 @@ __device__ __forceinline__ double spmv_row(const int32_t* __restrict__ cc, const
     for (int j = 0; j < UNR; ++j) acc += vu[j] * xu[j];
     if (WANT_DIAG) {
 #pragma unroll
-      for (int j = 0; j < UNR; ++j) xdiag = (k + j == dk) ? xu[j] : xdiag;
+      for (int j = 0; j < UNR; ++j) {
+        xdiag = (k + j == dk) ? xu[j] : xdiag;
+        adiag = (k + j == dk) ? vu[j] : adiag;
+      }
     }
   }
   if (k < len) {
@@ -913,7 +917,10 @@ __device__ __forceinline__ double spmv_row(const int32_t* __restrict__ cc, const
     for (int j = 0; j < UNR; ++j) acc += vu[j] * xu[j];
     if (WANT_DIAG) {
 #pragma unroll
-      for (int j = 0; j < UNR; ++j) xdiag = (k + j == dk) ? xu[j] : xdiag;
+      for (int j = 0; j < UNR; ++j) {
+        xdiag = (k + j == dk) ? xu[j] : xdiag;
+        adiag = (k + j == dk) ? vu[j] : adiag;
+      }
     }
   }
   return acc;
@@ -945,14 +952,14 @@ __global__ __launch_bounds__(256) void k_spmv(int n_launch, int chunk, const int
     const int64_t base = slice_ptr[s];
     const int len = (int)((slice_ptr[s + 1] - base) >> 6);
     const VT* v = vals + base + lane;
-    double acc, xd = 0.0;
+    double acc, xd = 0.0, ad = 0.0;   // (ad: the diagonal's value, unused here)
     const int dk = DOTS ? (int)diag_k[row] : -1;   // diag_k covers the padded rows of the last slice as well
     const int rl = (int)rlen[row];                 // ... and so does rlen (0 there)
     if (CIDX && win_ok[s]) {   // wave-uniform
       const int32_t wb = win_base[(int64_t)s * GL_N_WIN + (lane & (GL_N_WIN - 1))];
-      acc = spmv_row<1, UNR, NT, DOTS, VT>(nullptr, cols16 + base + lane, wb, v, x, len, rl, dk, xd);
+      acc = spmv_row<1, UNR, NT, DOTS, VT>(nullptr, cols16 + base + lane, wb, v, x, len, rl, dk, xd, ad);
     } else {
-      acc = spmv_row<0, UNR, NT, DOTS, VT>(cols + base + lane, nullptr, 0, v, x, len, rl, dk, xd);
+      acc = spmv_row<0, UNR, NT, DOTS, VT>(cols + base + lane, nullptr, 0, v, x, len, rl, dk, xd, ad);
     }
     if (row < n_own) {
       if (fixed && fixed[row]) acc = 0.0;
@@ -966,13 +973,17 @@ __global__ __launch_bounds__(256) void k_spmv(int n_launch, int chunk, const int
 
 // Dot-free Krylov iteration (round 5): ONE launch per iteration.  Step k of the Chebyshev semi-iteration for A y = b on the
 // spectrum [lmin, lmax] of Dinv A, with the vector work in the operator pass's epilogue -- the row owner has (A y)_row in
-// registers, and y_in[row] arrives with the gather of the diagonal entry:
+// registers, and y_in[row] and A_ii arrive with the gather of the diagonal entry:
 //     t = b - A y_in;   d = c1 d + c2 Dinv t;   y_out = y_in + d                              (passes 1 .. last)
-// The residual is recomputed from the iterate in every pass (no recurrence drift), the direction d is read and written by its
-// row only, so the pass moves 40 B of vectors per row (b, Dinv, d twice, y_out) next to the operator.  No dot product, no
-// reduction kernel, no all-reduce: the iteration count m follows from the interval and the wanted reduction (solver.hip,
-// cheb_solve), either known to the host (m_host) or, for a step's first solve, computed on the device from the norm of the
-// warm-started residual (*plan).  The LAST pass adds the correction y to the Newton iterate x and keeps a copy (ylast), so that
+// The residual is recomputed from the iterate in every pass (no recurrence drift).  Neither Dinv nor the direction is a stream
+// of its own: Dinv_row = 1 / A_ii is the division the sweep made, repeated on the value the row has just read, and the previous
+// direction is the difference of the last two iterates, d = y_in - y_prev, where y_prev is what the buffer y_out still holds
+// from two passes ago (read by the row's lane before it overwrites the word; the two pointers alias on purpose).  Pass 2 has no
+// such buffer yet: y_prev is the guess the solve started from (which may be ylast), or null for a start from zero.  So the pass
+// moves 24 B of vectors per row (b, y_prev, y_out) next to the operator; fp32 storage of the Jacobian still reads Dinv (32 B).
+// No dot product, no reduction kernel, no all-reduce: the iteration count m follows from the interval and the wanted reduction
+// (solver.hip, cheb_solve), either known to the host (m_host) or, for a step's first solve, computed on the device from the
+// norm of the warm-started residual (*plan).  The LAST pass adds the correction y to the Newton iterate x and keeps a copy (ylast), so that
 // a solve whose interval turns out wrong can be taken back (x -= ylast).
 //   want_res = 1: one more pass (k = last) computes only t = b - A y and stores it in b -- the residual of the final iterate,
 //                 which the quadratic-structure evaluation of the Newton residual builds on;
@@ -988,9 +999,9 @@ __global__ __launch_bounds__(256) void k_cheb(int n_launch, int chunk, const int
                                                const int32_t* __restrict__ win_base, const uint8_t* __restrict__ win_ok,
                                                const uint8_t* __restrict__ diag_k, const uint8_t* __restrict__ rlen,
                                                const VT* __restrict__ vals, const double* __restrict__ y_in,
-                                               double* __restrict__ y_out, double* __restrict__ b,
-                                               const double* __restrict__ dinv, double* __restrict__ dvec,
-                                               double* __restrict__ ylast, double* __restrict__ x,
+                                               double* y_out, double* __restrict__ b,
+                                               const double* __restrict__ dinv, const double* y_prev,
+                                               double* ylast, double* __restrict__ x,
                                                const uint8_t* __restrict__ fixed, double c1, double c2, int k, int m_host,
                                                const int* __restrict__ plan, int want_res, const PackMap pm, int remap,
                                                int shift, double* __restrict__ nrm) {
@@ -1008,24 +1019,31 @@ __global__ __launch_bounds__(256) void k_cheb(int n_launch, int chunk, const int
     const int64_t base = slice_ptr[s];
     const int len = (int)((slice_ptr[s + 1] - base) >> 6);
     const VT* v = vals + base + lane;
-    double acc, yn = 0.0;
+    double acc, yn = 0.0, ad = 1.0;
     const int dk = (int)diag_k[row];
     const int rl = (int)rlen[row];
     if (CIDX && win_ok[s]) {   // wave-uniform
       const int32_t wb = win_base[(int64_t)s * GL_N_WIN + (lane & (GL_N_WIN - 1))];
-      acc = spmv_row<1, UNR, NT, 1, VT>(nullptr, cols16 + base + lane, wb, v, y_in, len, rl, dk, yn);
+      acc = spmv_row<1, UNR, NT, 1, VT>(nullptr, cols16 + base + lane, wb, v, y_in, len, rl, dk, yn, ad);
     } else {
-      acc = spmv_row<0, UNR, NT, 1, VT>(cols + base + lane, nullptr, 0, v, y_in, len, rl, dk, yn);
+      acc = spmv_row<0, UNR, NT, 1, VT>(cols + base + lane, nullptr, 0, v, y_in, len, rl, dk, yn, ad);
     }
     if (row >= n_own) continue;
-    if (fixed && fixed[row]) acc = 0.0;   // constrained rows: b = 0 there, so every direction and the iterate stay 0
+    const bool fx = fixed && fixed[row];
+    if (fx) acc = 0.0;   // constrained rows: b = 0 there, so every direction and the iterate stay 0
     const double t = b[row] - acc;
     pn += t * t;
     if (direction) {
-      const double dn = (c1 != 0.0 ? c1 * dvec[row] : 0.0) + c2 * dinv[row] * t;
+      // Dinv: the sweep's 1 / A_ii, from the diagonal entry the row has just streamed (the same operand, the same division: the
+      // same bits as the stored array); the single-precision copy holds a rounded diagonal, so that variant reads the array
+      double di;
+      if constexpr (std::is_same<VT, double>::value) di = fx ? 1.0 : 1.0 / ad;
+      else di = dinv[row];
+      // the previous direction d = y_in - y_prev (y_prev null: the iterate before y_in is zero); read before y_out[row], which
+      // may be the same word, is written
+      const double dn = (c1 != 0.0 ? c1 * (y_prev ? yn - y_prev[row] : yn) : 0.0) + c2 * di * t;
       yn += dn;
       if (!fin) {
-        dvec[row] = dn;
         y_out[row] = yn;
         if (pm.ref) pack_row<1>(pm, row, &yn);
       }
@@ -1780,7 +1798,7 @@ void gl_launch_spmm(glims_ctx* h, int P, const double* vals, const double* x, do
 // One launch of the dot-free Krylov iteration (k_cheb) over a slice subset; same launch shape, stream policy and column-code
 // choice as the SpMV it replaces.
 void gl_launch_cheb(glims_ctx* h, hipStream_t st, int n_launch, const int32_t* slice_list, const double* vals,
-                    const float* vals32, const double* y_in, double* y_out, double* b, const double* dinv, double* dvec,
+                    const float* vals32, const double* y_in, double* y_out, double* b, const double* dinv, const double* y_prev,
                     double* ylast, double* x, const uint8_t* fixed, double c1, double c2, int k, int m_host, const int* plan,
                     int want_res, const PackMap& pm, hipEvent_t ev0, hipEvent_t ev1, int shift, double* nrm) {
   if (n_launch <= 0) return;
@@ -1794,12 +1812,12 @@ void gl_launch_cheb(glims_ctx* h, hipStream_t st, int n_launch, const int32_t* s
     if (ev0 || ev1)                                                                                                  \
       hipExtLaunchKernelGGL((k_cheb<UNR, NT, CIDX, VT>), dim3(grid), dim3(256), 0, st, ev0, ev1, 0, n_launch, chunk,  \
                             slice_list, h->n_own, p.slice_ptr.p, p.cols.p, p.cols16.p, p.win_base.p, p.win_ok.p,     \
-                            p.diag_k.p, p.rlen.p, VPTR, y_in, y_out, b, dinv, dvec, ylast, x, fixed, c1, c2, k,      \
+                            p.diag_k.p, p.rlen.p, VPTR, y_in, y_out, b, dinv, y_prev, ylast, x, fixed, c1, c2, k,    \
                             m_host, plan, want_res, pm, remap, shift, nrm);                                          \
     else                                                                                                             \
       hipLaunchKernelGGL((k_cheb<UNR, NT, CIDX, VT>), dim3(grid), dim3(256), 0, st, n_launch, chunk, slice_list,      \
                          h->n_own, p.slice_ptr.p, p.cols.p, p.cols16.p, p.win_base.p, p.win_ok.p, p.diag_k.p,        \
-                         p.rlen.p, VPTR, y_in, y_out, b, dinv, dvec, ylast, x, fixed, c1, c2, k, m_host, plan,       \
+                         p.rlen.p, VPTR, y_in, y_out, b, dinv, y_prev, ylast, x, fixed, c1, c2, k, m_host, plan,     \
                          want_res, pm, remap, shift, nrm);                                                           \
   } while (0)
 #define GL_CH3(UNR, CIDX, VT, VPTR)                                                                                  \

@@ -982,13 +982,11 @@ void gl_apply_dirichlet_c(glims_ctx* h) {
 // ===================================================================================================
 // Start of a solve from a zero guess: the first iterate needs no operator pass -- y_1 = d_1 = Dinv b / theta (+ its halo payload).
 __global__ __launch_bounds__(256) void k_cheb_start(int64_t n_own, const double* __restrict__ b, const double* __restrict__ dinv,
-                                                     double inv_theta, double* __restrict__ y, double* __restrict__ d,
-                                                     const PackMap pm) {
+                                                     double inv_theta, double* __restrict__ y, const PackMap pm) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_own; i += stride) {
     const double d0 = inv_theta * dinv[i] * b[i];
     y[i] = d0;
-    d[i] = d0;
     if (pm.ref) pack_row<1>(pm, i, &d0);
   }
 }
@@ -1364,6 +1362,9 @@ static double cheb_cost_ratio(glims_ctx* h) {
     v[0] /= h->world;
     v[1] /= h->world;
   }
+  // (60 B per row for a Chebyshev pass: the SpMV's 20 and the 40 B of vectors the pass moved while Dinv and the direction were
+  //  streams of their own.  It moves 24 B now (k_cheb), which would make the ratio 0.69 / 0.62 instead of 0.74 / 0.66 at 10 M /
+  //  1.26 M rows; the constant stays until the solves that this sends from PCG to the dot-free iteration have been measured)
   const double B0 = 40e6;
   return (12.0 * v[1] + 60.0 * v[0] + B0) / (12.0 * v[1] + 136.0 * v[0] + 3.0 * B0);
 }
@@ -1381,7 +1382,8 @@ struct ChebRun {
 };
 
 // Solves A y = b (b = v.r, the Newton right-hand side at v.x) for the correction y of v.x: iterates in v.p / v.s (two buffers
-// that change roles every pass), direction in cheb_dir; the last pass adds y to v.x and keeps it in ylast (take-back; next step's guess).
+// that change roles every pass; the buffer a pass writes still holds the iterate before the one it reads, and their difference is
+// the direction); the last pass adds y to v.x and keeps it in ylast (take-back; next step's guess).
 // v.r is left untouched unless want_res, in which case the final pass turns it into the residual b - A y.
 // warm_u: the solve starts from this guess (the predicted increment, ghosts valid; may be ylast) instead of zero; the iteration count
 // is then chosen on the device from |b - A u| (r_bound bounds the launches; hint_slot: which solve of the step), otherwise from r_norm = |b| here.
@@ -1390,7 +1392,6 @@ static ChebRun cheb_solve(glims_ctx* h, const CgVecs& v, double tol_abs, double 
   const DevPattern& p = h->pat;
   const bool split = h->world > 1 && h->n_peers > 0;
   const int64_t n = h->n_own;
-  h->cheb_dir.alloc((size_t)h->n_nodes);
   h->cheb_plan.alloc(1);
   double ia, ib;
   cheb_interval(h, tol_abs / std::max(r_norm > 0.0 ? r_norm : r_bound, tol_abs), &ia, &ib);
@@ -1424,7 +1425,7 @@ static ChebRun cheb_solve(glims_ctx* h, const CgVecs& v, double tol_abs, double 
   if (warm_u) {
     hipEvent_t* ev = h->timing(glims_ctx::TK_CHEB) ? h->pair(glims_ctx::TK_CHEB) : nullptr;
     // (one launch over all slices: the ghosts of u are current, nothing to exchange; the payload of d_1 is packed for pass 2)
-    gl_launch_cheb(h, h->st, p.n_slices, nullptr, v.vals, v.vals32, warm_u, v.p, v.r, v.dinv, h->cheb_dir.p,
+    gl_launch_cheb(h, h->st, p.n_slices, nullptr, v.vals, v.vals32, warm_u, v.p, v.r, v.dinv, nullptr,
                    ylast, v.x, v.fixed, 0.0, 1.0 / rec.theta, 1, GL_CHEB_MAX + 8, nullptr, want_res ? 1 : 0, pm,
                    ev ? ev[0] : nullptr, ev ? ev[1] : nullptr, shift, h->partials.p);
     reduce_partials(h, gl_spmv_grid(p.n_slices), 1, nullptr);
@@ -1436,7 +1437,7 @@ static ChebRun cheb_solve(glims_ctx* h, const CgVecs& v, double tol_abs, double 
   } else {
     // (zero guess: the first iterate y_1 = d_1 = Dinv b / theta needs no operator pass)
     hipLaunchKernelGGL(k_cheb_start, dim3(g), dim3(256), 0, h->st, n, (const double*)v.r, v.dinv, 1.0 / rec.theta, v.p,
-                       h->cheb_dir.p, pm);
+                       pm);
     GL_HIP(hipGetLastError());
   }
   const int last = (want_res ? m : m - 1) + shift;
@@ -1445,20 +1446,22 @@ static ChebRun cheb_solve(glims_ctx* h, const CgVecs& v, double tol_abs, double 
     double c1 = 0.0, c2 = 0.0;
     if (!want_res || k < m + shift) rec.next(&c1, &c2);
     const int* plan = run.planned ? h->cheb_plan.p : nullptr;
+    // the iterate before d_in: what d_out still holds -- except in pass 2, where it is the guess (none: zero)
+    const double* y_prev = k > 1 + shift ? d_out : warm_u;
     hipEvent_t* ev = h->timing(glims_ctx::TK_CHEB) ? h->pair(glims_ctx::TK_CHEB) : nullptr;
     if (!split) {
-      gl_launch_cheb(h, h->st, p.n_slices, nullptr, v.vals, v.vals32, d_in, d_out, v.r, v.dinv, h->cheb_dir.p,
+      gl_launch_cheb(h, h->st, p.n_slices, nullptr, v.vals, v.vals32, d_in, d_out, v.r, v.dinv, y_prev,
                      ylast, v.x, v.fixed, c1, c2, k, m, plan, want_res ? 1 : 0, pm, ev ? ev[0] : nullptr,
                      ev ? ev[1] : nullptr, shift);
     } else {
       // the ghosts of d_in travel (payload packed by the kernel that produced it) while the slices without ghost columns run
       halo_start(h, d_in, 1, /*prepacked=*/true);
       gl_launch_cheb(h, h->st, p.n_interior, p.interior_slices.p, v.vals, v.vals32, d_in, d_out, v.r, v.dinv,
-                     h->cheb_dir.p, ylast, v.x, v.fixed, c1, c2, k, m, plan, want_res ? 1 : 0, pm,
+                     y_prev, ylast, v.x, v.fixed, c1, c2, k, m, plan, want_res ? 1 : 0, pm,
                      ev ? ev[0] : nullptr, ev ? ev[1] : nullptr, shift);
       halo_finish(h);
       gl_launch_cheb(h, h->st, p.n_boundary, p.boundary_slices.p, v.vals, v.vals32, d_in, d_out, v.r, v.dinv,
-                     h->cheb_dir.p, ylast, v.x, v.fixed, c1, c2, k, m, plan, want_res ? 1 : 0, pm, nullptr, nullptr,
+                     y_prev, ylast, v.x, v.fixed, c1, c2, k, m, plan, want_res ? 1 : 0, pm, nullptr, nullptr,
                      shift);
     }
     std::swap(d_in, d_out);
