@@ -95,6 +95,17 @@ class Misfit(C.Structure):
                 ("weight", C.c_double), ("target", C.POINTER(C.c_double))]
 
 
+MISFIT_IMG_L2, MISFIT_IMG_THRESH = 0, 1
+_IMAGE_KINDS = {"img_l2": MISFIT_IMG_L2, "img_thresh": MISFIT_IMG_THRESH}
+
+
+class ImageMisfit(C.Structure):
+    """glims_image_misfit: an image-space misfit term (target / pweight in the point order of the sampler)."""
+    _fields_ = [("step", C.c_int64), ("sampler", C.c_int64), ("kind", C.c_int), ("level", C.c_double),
+                ("smooth", C.c_double), ("weight", C.c_double), ("target", C.POINTER(C.c_double)),
+                ("pweight", C.POINTER(C.c_double))]
+
+
 _dp = C.POINTER(C.c_double)
 _i32p = C.POINTER(C.c_int32)
 _i64p = C.POINTER(C.c_int64)
@@ -142,6 +153,8 @@ SIGNATURES = {
     "glims_sampler_apply": (C.c_int, [_h, C.c_int64, C.c_int, C.c_int64, _dp, C.c_int, C.c_double, _dp]),
     "glims_sampler_apply_t": (C.c_int, [_h, C.c_int64, _dp, C.c_int, _dp]),
     "glims_sampler_destroy": (C.c_int, [_h, C.c_int64]),
+    "glims_adjoint_image_terms": (C.c_int, [_h, C.c_int, C.POINTER(ImageMisfit)]),
+    "glims_adjoint_image_info": (C.c_int, [_h, C.c_int, _i64p]),
     "glims_comm_unique_id": (C.c_int, [C.c_char_p]),
     "glims_comm_init": (C.c_int, [_h, C.c_int, C.c_int, C.c_char_p]),
     "glims_comm_selftest": (C.c_int, [_h]),
@@ -214,6 +227,7 @@ class Handle:
         self.options = Options()
         lib.glims_options_default(C.byref(self.options))
         self.n_labels = None   # label count of the last successful set_materials
+        self._image_terms = []   # what the library's stored image terms were made from (see _sync_image_terms)
 
     # -- plumbing --------------------------------------------------------------------------------
     def _check(self, st, allow=()):
@@ -361,7 +375,10 @@ class Handle:
 
     def adjoint_gradient(self, terms, n_labels=None, want_dc0=True, elastic=False):
         """terms: iterable of dicts {step, kind ('c_l2' | 'c_thresh' | 'u_l2' or MISFIT_*), target, weight=1, level=0,
-        smooth=1}; targets in the caller's node order ([n_nodes] or [n_nodes, dim]).
+        smooth=1}; targets in the caller's node order ([n_nodes] or [n_nodes, dim]).  Image-space terms go in the same list:
+        {step, kind ('img_l2' | 'img_thresh'), sampler (a :class:`Sampler` of this handle), target ([n_points], any shape;
+        NaN = not observed), pweight=None, weight=1, level=0, smooth=1}; they are stored on the device (set_image_terms) and
+        re-sent only when they differ from what the handle holds.
         Returns (J, dJ/dD [n_labels], dJ/drho, dJ/dgamma, dJ/dc0 [n_nodes] or None); with elastic=True (glims_adjoint_gradient_full)
         (J, dJ/dD, dJ/drho, dJ/dgamma, dJ/dc0, dJ/dE [n_labels], dJ/dnu [n_labels]).  The library writes one entry per label
         of the last set_materials: n_labels, when given, must be that count (ValueError otherwise, before any call)."""
@@ -370,7 +387,7 @@ class Handle:
         if n_labels is not None and int(n_labels) != self.n_labels:
             raise ValueError("adjoint_gradient: n_labels = %d, but set_materials gave %d labels" % (n_labels, self.n_labels))
         n_labels = self.n_labels
-        terms = list(terms)
+        terms = self._split_terms(terms)
         arr, keep = self._misfit_array(terms)   # (keep: the target arrays the structs point into)
         J = C.c_double(0.0)
         out = [np.zeros(int(n_labels)) for _ in range(5 if elastic else 3)]
@@ -383,6 +400,56 @@ class Handle:
         self._check(self.lib.glims_adjoint_gradient(self._h, len(terms), arr, C.byref(J), *[_ptr(a, _dp) for a in out],
                                                     _ptr(dc0, _dp)))
         return (J.value, out[0], out[1], out[2], dc0)
+
+    # -- image-space misfit terms (glims_adjoint_image_*) ---------------------------------------------
+    @staticmethod
+    def _image_key(t):
+        """What identifies a stored image term: its scalars and the IDENTITY of its target / pweight arrays."""
+        sm = t["sampler"]
+        return (int(t["step"]), _IMAGE_KINDS.get(t["kind"], t["kind"]), int(getattr(sm, "id", sm)),
+                float(t.get("level", 0.0)), float(t.get("smooth", 1.0)), float(t.get("weight", 1.0)),
+                id(t["target"]), id(t.get("pweight")))
+
+    def set_image_terms(self, terms, _from_list=False):
+        """glims_adjoint_image_terms: replace the handle's stored image terms (an empty list clears them).  The target and
+        pweight arrays are copied to the device once; every later adjoint_gradient / adjoint_hessian adds these terms
+        (until a term list that carries image terms of its own replaces them)."""
+        terms = list(terms)
+        arr = (ImageMisfit * max(1, len(terms)))()
+        keep = []
+        for k, t in enumerate(terms):
+            sm = t["sampler"]
+            if isinstance(sm, Sampler) and sm.handle is not self:
+                raise ValueError("image term %d: its sampler belongs to another handle" % k)
+            kind = _IMAGE_KINDS.get(t["kind"], t["kind"])
+            n = sm.n_points if isinstance(sm, Sampler) else None
+            tg = _f64(np.asarray(t["target"], dtype=np.float64).reshape(-1), None if n is None else (n,))
+            q = t.get("pweight")
+            if q is not None:
+                q = _f64(np.asarray(q, dtype=np.float64).reshape(-1), tg.shape)
+            keep.append((tg, q))
+            arr[k] = ImageMisfit(int(t["step"]), int(getattr(sm, "id", sm)), int(kind), float(t.get("level", 0.0)),
+                                 float(t.get("smooth", 1.0)), float(t.get("weight", 1.0)), _ptr(tg, _dp), _ptr(q, _dp))
+        self._check(self.lib.glims_adjoint_image_terms(self._h, len(terms), arr))
+        # (the caller's arrays are kept alive: their identity is what _split_terms compares)
+        self._image_terms = [(self._image_key(t), t["target"], t.get("pweight")) for t in terms]
+        self._image_from_list = bool(_from_list)
+
+    def image_term_info(self, k):
+        """(sampler id, number of points, number of observed points) of stored image term k."""
+        out = np.zeros(3, dtype=np.int64)
+        self._check(self.lib.glims_adjoint_image_info(self._h, int(k), _ptr(out, _i64p)))
+        return tuple(int(v) for v in out)
+
+    def _split_terms(self, terms):
+        """The nodal terms of a mixed list; its image terms become the handle's stored list (re-sent only on a change)."""
+        terms = list(terms)
+        image = [t for t in terms if _IMAGE_KINDS.get(t["kind"]) is not None]
+        if not image and not getattr(self, "_image_from_list", False):
+            return terms   # (terms stored by set_image_terms itself stay)
+        if [self._image_key(t) for t in image] != [k for k, _, _ in self._image_terms]:
+            self.set_image_terms(image, _from_list=True)
+        return [t for t in terms if _IMAGE_KINDS.get(t["kind"]) is None]
 
     def _misfit_array(self, terms):
         """ctypes array of glims_misfit for the term dicts, and the target arrays it points into (keep them alive)."""
@@ -411,7 +478,7 @@ class Handle:
         L, n = self.n_labels, self.n_nodes
         directions = list(directions)
         P = len(directions)
-        terms = list(terms)
+        terms = self._split_terms(terms)
         arr, keep = self._misfit_array(terms)
 
         def table(key, size):

@@ -365,6 +365,18 @@ void mass_apply(glims_ctx* h, const double* x, double* y) {
   gl_launch_spmv(h, h->st, h->pat.n_slices, nullptr, h->vM.p, x, y, nullptr, nullptr, nullptr, nullptr, 0, nullptr);
 }
 
+// The stored image terms (glims_adjoint_image_terms) that observe `step`, in their list order, after the step's nodal terms:
+// g += P^T r of each, J += 1/2 w sum_p q_p (h(v_p) - t_p)^2; with P > 0 also dg_j += P^T r2_j for the Hessian's directions
+// dc (column-major [P][ld]).  No stored term: no launch.
+void image_terms_of_step(glims_ctx* h, int step, const double* c, double* g, double* J, int P = 0,
+                         const double* dc = nullptr, int64_t ld = 0, double* dg = nullptr) {
+  for (const GlImageTerm* t : h->img_terms) {
+    if (t->step != step) continue;
+    *J += 0.5 * t->weight * gl_image_misfit_grad(h, *t, c, g);
+    if (P > 0) gl_image_misfit_second(h, *t, c, dc, P, ld, dg);
+  }
+}
+
 // mode 0: (c, lambda) -> sums[l][0..1];  mode 1: (c, mu) -> sums[l][2] and qcell;  mode 2: (u, mu) -> esums[l][0..1]
 template <int D>
 void sens_pass(glims_ctx* h, int mode, const double* c, const double* v, AdjWork& wk) {
@@ -550,6 +562,7 @@ int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_o
       }
     }
     if (status != GLIMS_OK) break;
+    image_terms_of_step(h, step, c, wk.g.p, &J);
     if (have_u) {   // mu = K_el^-1 dJ/du (0 on the constrained dofs); g += G^T mu; dJ/dgamma_t += mu^T G_t c
       int64_t its = 0;
       status = solve_elastic(h, wk, wk.murhs.p, wk.mu.p, nullptr, 1e-12, &its);
@@ -1384,6 +1397,7 @@ int hessian_t(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, const
       }
     }
     if (status != GLIMS_OK) break;
+    image_terms_of_step(h, step, c, wk.g.p, &J, P, dc_of(step, 0), nn, dg.p);
     if (have_u) {
       int64_t its = 0;
       status = solve_elastic(h, wk, wk.murhs.p, wk.mu.p, nullptr, 1e-12, &its);
@@ -1604,6 +1618,10 @@ void check_gradient_call(glims_ctx* h, int n_terms, const glims_misfit* terms, c
     GL_REQUIRE(t.kind != GLIMS_MISFIT_U_L2 || h->have_mech,
                who + ": a displacement term needs glims_setup(with_mechanics=1)");
   }
+  for (size_t k = 0; k < h->img_terms.size(); ++k)
+    GL_REQUIRE(h->img_terms[k]->step <= N, who + ": stored image term " + std::to_string(k) + " observes step " +
+                                               std::to_string(h->img_terms[k]->step) + ", the recording has steps 0.." +
+                                               std::to_string(N));
 }
 }  // namespace
 

@@ -893,6 +893,20 @@ int glims_sampler_destroy(glims_ctx* h, int64_t id) {
   });
 }
 
+int glims_adjoint_image_terms(glims_ctx* h, int n, const glims_image_misfit* terms) {
+  return guarded(h, [&]() {
+    gl_image_terms_set(h, n, terms);
+    return GLIMS_OK;
+  });
+}
+
+int glims_adjoint_image_info(glims_ctx* h, int k, int64_t out[3]) {
+  return guarded(h, [&]() {
+    gl_image_term_info(h, k, out);
+    return GLIMS_OK;
+  });
+}
+
 int glims_project(glims_ctx* h, const double* rhs, double* x, int ncomp, double rtol) {
   return guarded(h, [&]() {
     GL_REQUIRE(rhs && x && ncomp >= 1 && rtol > 0.0, "bad arguments");

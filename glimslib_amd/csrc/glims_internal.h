@@ -458,6 +458,15 @@ struct AdjointState {
 
 struct GlSampler;   // sample.hip
 
+// One stored image-space misfit term (glims_adjoint_image_terms; kernels in sample.hip).  target holds NaN at every point that
+// is not observed (outside the mesh, NaN in the caller's array, q_p = 0): the misfit kernels test that alone.
+struct GlImageTerm {
+  int64_t step = 0, sampler = -1, n = 0, n_obs = 0;
+  int kind = 0;
+  double level = 0.0, smooth = 1.0, weight = 1.0;
+  dvec<double> target, pweight;             // [n]; pweight empty = 1
+};
+
 struct glims_ctx {
   int dim = 0, nv = 0, device = 0;
   int n_labels = 0;                        // of the last glims_set_materials
@@ -650,6 +659,7 @@ struct glims_ctx {
 
   AdjointState adj;
   std::vector<GlSampler*> samplers;         // owned (sample.hip); a destroyed sampler leaves a nullptr so that ids stay valid
+  std::vector<GlImageTerm*> img_terms;      // owned (sample.hip): the stored image-space misfit terms of the adjoint calls
 
   std::string err;
 };
@@ -728,7 +738,17 @@ void gl_sampler_apply(glims_ctx* h, int64_t id, int field, int64_t snapshot, con
                       double* out);
 void gl_sampler_apply_t(glims_ctx* h, int64_t id, const double* r, int ncomp, double* g);
 void gl_sampler_destroy(glims_ctx* h, int64_t id);
-void gl_sampler_destroy_all(glims_ctx* h);
+void gl_sampler_destroy_all(glims_ctx* h);   // (and the stored image terms)
+// g[row * ld_row + a * ld_comp] (internal numbering, owned rows) = or += (P^T r)[row][a]; r [n_points][ncomp] on the device
+void gl_sampler_transpose_dev(glims_ctx* h, int64_t id, const double* r_dev, int ncomp, double* g_int_dev, int64_t ld_row,
+                              int64_t ld_comp, bool accumulate);
+void gl_image_terms_set(glims_ctx* h, int n, const glims_image_misfit* terms);
+void gl_image_term_info(glims_ctx* h, int k, int64_t out[3]);
+// g += P^T r of stored term t at the state c (internal numbering); returns sum_p q_p (h(v_p) - t_p)^2 (fixed order)
+double gl_image_misfit_grad(glims_ctx* h, const GlImageTerm& t, const double* c, double* g);
+// dg[j * ld + row] += (P^T r2_j)[row] for the P directions dc[j * ld + .]
+void gl_image_misfit_second(glims_ctx* h, const GlImageTerm& t, const double* c, const double* dc, int P, int64_t ld,
+                            double* dg);
 
 // mg.hip --------------------------------------------------------------------------------------------
 void gl_mesh_metrics(glims_ctx* h, const HostPattern& hp, const double* xyz_old);

@@ -40,6 +40,7 @@ struct GlSampler {
   dvec<int32_t> chunk_cell;    // [n_chunks]
   // staging, grown on demand
   dvec<double> f_ext, f_int, out, q, g_int;
+  dvec<double> part;           // image misfit: per-block partial sums, then the total
 };
 
 namespace {
@@ -514,12 +515,13 @@ __global__ __launch_bounds__(256) void k_sample_t_cells(int64_t n_chunks, int nc
 }
 
 // pass 2, one thread per node (row-owned, like the assembly): the node's cells in the order of its incidence list, each
-// cell's chunks in chunk order, the entry of the node's own vertex slot
+// cell's chunks in chunk order, the entry of the node's own vertex slot.  Component a of row goes to g[row ld_row + a ld_comp].
 template <int NV>
 __global__ __launch_bounds__(256) void k_sample_t(int64_t n_own, int ncomp, const int64_t* __restrict__ cslice_ptr,
                                                   const uint32_t* __restrict__ cslots, const int32_t* __restrict__ celem,
                                                   const uint8_t* __restrict__ diag_k, const int32_t* __restrict__ chunk_ptr,
-                                                  const double* __restrict__ q, double* __restrict__ g) {
+                                                  const double* __restrict__ q, double* __restrict__ g, int64_t ld_row,
+                                                  int64_t ld_comp, int accumulate) {
   const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (row >= n_own) return;
   const int64_t s = row >> 6, lane = row & 63;
@@ -545,9 +547,137 @@ __global__ __launch_bounds__(256) void k_sample_t(int64_t n_own, int ncomp, cons
       for (int a = 0; a < GLIMS_SAMPLE_MAX_COMP; ++a)
         if (a < ncomp) acc[a] += q[(c * NV + own) * ncomp + a];
   }
+  // (accumulate: the row's own thread adds to what g holds -- two misfit terms on one step must add)
 #pragma unroll
   for (int a = 0; a < GLIMS_SAMPLE_MAX_COMP; ++a)
-    if (a < ncomp) g[row * ncomp + a] = acc[a];
+    if (a < ncomp) {
+      const int64_t o = row * ld_row + a * ld_comp;
+      g[o] = accumulate ? g[o] + acc[a] : acc[a];
+    }
+}
+
+// ---- image-space misfit terms (glims_hip.h, "image-space misfit terms") --------------------------------
+// once per stored term: t[p] = NaN where the point is not observed (outside the mesh, q_p = 0); counts the observed ones
+__global__ __launch_bounds__(256) void k_img_prepare(int64_t n, const int32_t* __restrict__ cell, const double* __restrict__ q,
+                                                     double* __restrict__ t, unsigned long long* __restrict__ n_obs) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool obs = false;
+  if (p < n) {
+    const double tv = t[p];
+    obs = cell[p] >= 0 && tv == tv && (!q || q[p] != 0.0);
+    if (!obs) t[p] = __longlong_as_double(0x7ff8000000000000LL);
+  }
+  const int here = __syncthreads_count(obs);
+  if (threadIdx.x == 0 && here) atomicAdd(n_obs, (unsigned long long)here);   // (integer: order-independent)
+}
+
+// h(v) - t is formed by the callers; h, h', h'' of a term kind
+__device__ __forceinline__ void img_h(int kind, double level, double smooth, double v, double& hv, double& hp, double& h2) {
+  if (kind == GLIMS_MISFIT_IMG_THRESH) {
+    const double th = tanh((v - level) / smooth);
+    hv = 0.5 * (th + 1.0);
+    hp = 0.5 * (1.0 - th * th) / smooth;
+    h2 = -th * (1.0 - th * th) / (smooth * smooth);
+  } else {
+    hv = v;
+    hp = 1.0;
+    h2 = 0.0;
+  }
+}
+
+__device__ __forceinline__ double img_wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  return v;
+}
+
+// One thread per point: v = sum_a w c[node] gathered from the recorded state (internal numbering), r[p] = weight q h'(v)
+// (h(v) - t) for an observed point (t not NaN), else 0 -- a NaN target enters no arithmetic.  part[block] = the block's sum of
+// q (h(v) - t)^2: the wave's butterfly, then the four wave sums in a fixed order.
+// Bytes per point: NV (4 + 8) node ids and weights + 8 (t) + 8 (q, if present) + 8 (r); c is gathered through the caches.
+template <int NV>
+__global__ __launch_bounds__(256) void k_img_misfit(int64_t n, int kind, double level, double smooth, double weight,
+                                                    const int32_t* __restrict__ node, const double* __restrict__ w,
+                                                    const double* __restrict__ c, const double* __restrict__ t,
+                                                    const double* __restrict__ q, double* __restrict__ r,
+                                                    double* __restrict__ part) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  double sq = 0.0;
+  if (p < n) {
+    const double tv = t[p];
+    double rv = 0.0;
+    if (tv == tv) {
+      double v = 0.0;
+#pragma unroll
+      for (int m = 0; m < NV; ++m) v += w[p * NV + m] * c[node[p * NV + m]];
+      double hv, hp, h2;
+      img_h(kind, level, smooth, v, hv, hp, h2);
+      const double qv = q ? q[p] : 1.0;
+      const double e = hv - tv;
+      rv = weight * qv * hp * e;
+      sq = qv * e * e;
+    }
+    r[p] = rv;
+  }
+  __shared__ double sm[4];
+  const double ws = img_wave_sum(sq);
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = ws;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
+}
+
+// second stage, ONE block: thread i adds the partials i, i + 1024, ... in block order, then the wave's butterfly and the 16
+// wave sums in order -- the same order on every call.  out[0] = the total.
+__global__ __launch_bounds__(1024) void k_img_sum(int64_t n_blocks, const double* __restrict__ part, double* __restrict__ out) {
+  double s = 0.0;
+  for (int64_t b = threadIdx.x; b < n_blocks; b += 1024) s += part[b];
+  __shared__ double sm[16];
+  s = img_wave_sum(s);
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double tsum = 0.0;
+    for (int k = 0; k < 16; ++k) tsum += sm[k];
+    out[0] = tsum;
+  }
+}
+
+// Second order, one thread per point, all P columns of a call: r2[p][j] = weight q (h'(v)^2 + h''(v) (h(v) - t)) (P dc_j)_p
+// (0 for a point that is not observed).  Column j runs the same arithmetic whatever P is.
+// Bytes per point: NV (4 + 8) + 8 (t) + 8 (q, if present) + 8 P (r2); c and the P columns of dc are gathered through the caches.
+template <int NV>
+__global__ __launch_bounds__(256) void k_img_misfit_dir(int64_t n, int P, int64_t ld, int kind, double level, double smooth,
+                                                        double weight, const int32_t* __restrict__ node,
+                                                        const double* __restrict__ w, const double* __restrict__ c,
+                                                        const double* __restrict__ dc, const double* __restrict__ t,
+                                                        const double* __restrict__ q, double* __restrict__ r2) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n) return;
+  const double tv = t[p];
+  if (!(tv == tv)) {
+    for (int j = 0; j < P; ++j) r2[p * P + j] = 0.0;
+    return;
+  }
+  int32_t nd[NV];
+  double wt[NV];
+  double v = 0.0;
+#pragma unroll
+  for (int m = 0; m < NV; ++m) {
+    nd[m] = node[p * NV + m];
+    wt[m] = w[p * NV + m];
+    v += wt[m] * c[nd[m]];
+  }
+  double hv, hp, h2;
+  img_h(kind, level, smooth, v, hv, hp, h2);
+  const double qv = q ? q[p] : 1.0;
+  const double coef = weight * qv * (hp * hp + h2 * (hv - tv));
+  for (int j = 0; j < P; ++j) {
+    const double* d = dc + (size_t)j * ld;
+    double dv = 0.0;
+#pragma unroll
+    for (int m = 0; m < NV; ++m) dv += wt[m] * d[nd[m]];
+    r2[p * P + j] = coef * dv;
+  }
 }
 
 GlSampler& sampler_of(glims_ctx* h, int64_t id, const char* who) {
@@ -863,6 +993,43 @@ void gl_sampler_apply(glims_ctx* h, int64_t id, int field, int64_t snapshot, con
   GL_HIP(hipStreamSynchronize(h->st));
 }
 
+// The two launches of P^T on device pointers: pass 1 into the sampler's chunk buffer, pass 2 row-owned into g (internal
+// numbering; overwritten, or added to with `accumulate`).  Without `accumulate` g is [n_nodes][ncomp] contiguous.
+void gl_sampler_transpose_dev(glims_ctx* h, int64_t id, const double* r_dev, int ncomp, double* g_int_dev, int64_t ld_row,
+                              int64_t ld_comp, bool accumulate) {
+  GlSampler& s = sampler_of(h, id, "glims_sampler_apply_t");
+  GL_REQUIRE(h->world <= 1, "glims_sampler_apply_t: not available on a partitioned handle (the per-cell sums would need the "
+                            "globally winning cell on every rank that holds it)");
+  GL_REQUIRE(ncomp >= 1 && ncomp <= GLIMS_SAMPLE_MAX_COMP,
+             "glims_sampler_apply_t: ncomp = " + std::to_string(ncomp) + " outside 1 .. 8");
+  if (!(s.n > 0 && s.have_t && s.n_chunks > 0)) {
+    if (!accumulate) GL_HIP(hipMemsetAsync(g_int_dev, 0, (size_t)h->n_nodes * ncomp * sizeof(double), h->st));
+    return;
+  }
+  const size_t nq = (size_t)s.n_chunks * h->nv * ncomp;
+  if (s.q.n < nq) {
+    need_memory("glims_sampler_apply_t", nq * sizeof(double));
+    s.q.alloc(nq);
+  }
+  if (h->nv == 3)
+    hipLaunchKernelGGL(k_sample_t_cells<3>, dim3(grid_of(s.n_chunks)), dim3(256), 0, h->st, s.n_chunks, ncomp,
+                       s.chunk_cell.p, s.chunk_ptr.p, s.cptr.p, s.order.p, s.w.p, r_dev, s.q.p);
+  else
+    hipLaunchKernelGGL(k_sample_t_cells<4>, dim3(grid_of(s.n_chunks)), dim3(256), 0, h->st, s.n_chunks, ncomp,
+                       s.chunk_cell.p, s.chunk_ptr.p, s.cptr.p, s.order.p, s.w.p, r_dev, s.q.p);
+  GL_CHECK_LAUNCH();
+  const DevPattern& pt = h->pat;
+  if (h->nv == 3)
+    hipLaunchKernelGGL(k_sample_t<3>, dim3(grid_of(h->n_own)), dim3(256), 0, h->st, h->n_own, ncomp, pt.cslice_ptr.p,
+                       pt.cslots.p, pt.celem.p, pt.diag_k.p, s.chunk_ptr.p, s.q.p, g_int_dev, ld_row, ld_comp,
+                       accumulate ? 1 : 0);
+  else
+    hipLaunchKernelGGL(k_sample_t<4>, dim3(grid_of(h->n_own)), dim3(256), 0, h->st, h->n_own, ncomp, pt.cslice_ptr.p,
+                       pt.cslots.p, pt.celem.p, pt.diag_k.p, s.chunk_ptr.p, s.q.p, g_int_dev, ld_row, ld_comp,
+                       accumulate ? 1 : 0);
+  GL_CHECK_LAUNCH();
+}
+
 void gl_sampler_apply_t(glims_ctx* h, int64_t id, const double* r, int ncomp, double* g) {
   GlSampler& s = sampler_of(h, id, "glims_sampler_apply_t");
   GL_REQUIRE(h->world <= 1, "glims_sampler_apply_t: not available on a partitioned handle (the per-cell sums would need the "
@@ -883,26 +1050,9 @@ void gl_sampler_apply_t(glims_ctx* h, int64_t id, const double* r, int ncomp, do
     if (s.out.n < nr) s.out.alloc(nr);
     if (s.q.n < nq) s.q.alloc(nq);
   }
-  if (s.n > 0 && s.have_t && s.n_chunks > 0) {
+  if (s.n > 0 && s.have_t && s.n_chunks > 0)
     GL_HIP(hipMemcpyAsync(s.out.p, r, (size_t)s.n * ncomp * sizeof(double), hipMemcpyHostToDevice, h->st));
-    if (h->nv == 3)
-      hipLaunchKernelGGL(k_sample_t_cells<3>, dim3(grid_of(s.n_chunks)), dim3(256), 0, h->st, s.n_chunks, ncomp,
-                         s.chunk_cell.p, s.chunk_ptr.p, s.cptr.p, s.order.p, s.w.p, s.out.p, s.q.p);
-    else
-      hipLaunchKernelGGL(k_sample_t_cells<4>, dim3(grid_of(s.n_chunks)), dim3(256), 0, h->st, s.n_chunks, ncomp,
-                         s.chunk_cell.p, s.chunk_ptr.p, s.cptr.p, s.order.p, s.w.p, s.out.p, s.q.p);
-    GL_CHECK_LAUNCH();
-    const DevPattern& pt = h->pat;
-    if (h->nv == 3)
-      hipLaunchKernelGGL(k_sample_t<3>, dim3(grid_of(h->n_own)), dim3(256), 0, h->st, h->n_own, ncomp, pt.cslice_ptr.p,
-                         pt.cslots.p, pt.celem.p, pt.diag_k.p, s.chunk_ptr.p, s.q.p, s.g_int.p);
-    else
-      hipLaunchKernelGGL(k_sample_t<4>, dim3(grid_of(h->n_own)), dim3(256), 0, h->st, h->n_own, ncomp, pt.cslice_ptr.p,
-                         pt.cslots.p, pt.celem.p, pt.diag_k.p, s.chunk_ptr.p, s.q.p, s.g_int.p);
-    GL_CHECK_LAUNCH();
-  } else {
-    GL_HIP(hipMemsetAsync(s.g_int.p, 0, ng * sizeof(double), h->st));
-  }
+  gl_sampler_transpose_dev(h, id, s.out.p, ncomp, s.g_int.p, ncomp, 1, false);
   hipLaunchKernelGGL(k_nodal_out, dim3(grid_of((int64_t)ng)), dim3(256), 0, h->st, nn, ncomp, h->d_old2new.p, s.g_int.p,
                      s.f_ext.p);
   GL_CHECK_LAUNCH();
@@ -910,14 +1060,138 @@ void gl_sampler_apply_t(glims_ctx* h, int64_t id, const double* r, int ncomp, do
   GL_HIP(hipStreamSynchronize(h->st));
 }
 
+// ---- stored image terms ----------------------------------------------------------------------------------------------------
+void gl_image_terms_set(glims_ctx* h, int n, const glims_image_misfit* terms) {
+  const char* who = "glims_adjoint_image_terms";
+  GL_REQUIRE(n >= 0 && (n == 0 || terms), std::string(who) + ": bad term list");
+  GL_REQUIRE(n == 0 || h->world <= 1, std::string(who) + ": not available on a partitioned handle (glims_sampler_apply_t, "
+                                                         "the transpose the gradient needs, is refused there)");
+  // every check before anything is allocated or the old list is touched
+  size_t need = 0;
+  for (int k = 0; k < n; ++k) {
+    const glims_image_misfit& t = terms[k];
+    const std::string tk = std::string(who) + ": term " + std::to_string(k);
+    GlSampler& s = sampler_of(h, t.sampler, who);
+    GL_REQUIRE(t.kind == GLIMS_MISFIT_IMG_L2 || t.kind == GLIMS_MISFIT_IMG_THRESH, tk + ": unknown kind");
+    GL_REQUIRE(t.kind != GLIMS_MISFIT_IMG_THRESH || (t.smooth > 0.0 && std::isfinite(t.smooth) && std::isfinite(t.level)),
+               tk + ": a threshold term needs smooth > 0 and a finite level");
+    GL_REQUIRE(std::isfinite(t.weight), tk + ": non-finite weight");
+    GL_REQUIRE(t.target, tk + ": null target");
+    GL_REQUIRE(t.step >= 0, tk + ": negative step");
+    if (t.pweight)
+      for (int64_t p = 0; p < s.n; ++p)
+        GL_REQUIRE(t.pweight[p] >= 0.0 && std::isfinite(t.pweight[p]),
+                   tk + ": pweight[" + std::to_string(p) + "] is negative or not finite");
+    need += (size_t)s.n * (t.pweight ? 16 : 8);
+  }
+  if (n > 0) need_memory(who, need + (1u << 20));
+  std::vector<GlImageTerm*> fresh;
+  try {
+    dvec<unsigned long long> d_obs;
+    for (int k = 0; k < n; ++k) {
+      const glims_image_misfit& t = terms[k];
+      GlSampler& s = sampler_of(h, t.sampler, who);
+      auto* g = new GlImageTerm();
+      fresh.push_back(g);
+      g->step = t.step;
+      g->sampler = t.sampler;
+      g->kind = t.kind;
+      g->level = t.level;
+      g->smooth = t.smooth;
+      g->weight = t.weight;
+      g->n = s.n;
+      if (s.n == 0) continue;
+      g->target.upload(t.target, (size_t)s.n, h->st);
+      if (t.pweight) g->pweight.upload(t.pweight, (size_t)s.n, h->st);
+      d_obs.alloc_zero(1, h->st);
+      hipLaunchKernelGGL(k_img_prepare, dim3(grid_of(s.n)), dim3(256), 0, h->st, s.n, s.cell.p, g->pweight.p, g->target.p,
+                         d_obs.p);
+      GL_CHECK_LAUNCH();
+      unsigned long long no = 0;
+      GL_HIP(hipMemcpyAsync(&no, d_obs.p, sizeof(no), hipMemcpyDeviceToHost, h->st));
+      GL_HIP(hipStreamSynchronize(h->st));   // (the caller's arrays are free again)
+      g->n_obs = (int64_t)no;
+    }
+  } catch (...) {
+    (void)hipStreamSynchronize(h->st);
+    for (auto* g : fresh) delete g;
+    throw;
+  }
+  for (auto* g : h->img_terms) delete g;
+  h->img_terms.swap(fresh);
+}
+
+void gl_image_term_info(glims_ctx* h, int k, int64_t out[3]) {
+  GL_REQUIRE(out, "glims_adjoint_image_info: null output");
+  GL_REQUIRE(k >= 0 && k < (int)h->img_terms.size(), "glims_adjoint_image_info: no stored term " + std::to_string(k));
+  const GlImageTerm& t = *h->img_terms[(size_t)k];
+  out[0] = t.sampler;
+  out[1] = t.n;
+  out[2] = t.n_obs;
+}
+
+namespace {
+// r / r2 live in the sampler's point staging, the partials in its own buffer
+void image_staging(glims_ctx* h, GlSampler& s, int ncomp) {
+  const size_t nr = (size_t)s.n * ncomp, np = (size_t)grid_of(s.n) + 1;
+  if (s.out.n < nr || s.part.n < np) {
+    need_memory("glims_adjoint_gradient (image terms)", (nr + np) * sizeof(double));
+    if (s.out.n < nr) s.out.alloc(nr);
+    if (s.part.n < np) s.part.alloc(np);
+  }
+}
+}  // namespace
+
+double gl_image_misfit_grad(glims_ctx* h, const GlImageTerm& t, const double* c, double* g) {
+  GlSampler& s = sampler_of(h, t.sampler, "glims_adjoint_gradient");
+  if (s.n == 0) return 0.0;
+  image_staging(h, s, 1);
+  const unsigned nb = grid_of(s.n);
+  if (h->nv == 3)
+    hipLaunchKernelGGL(k_img_misfit<3>, dim3(nb), dim3(256), 0, h->st, s.n, t.kind, t.level, t.smooth, t.weight, s.node.p,
+                       s.w.p, c, t.target.p, t.pweight.p, s.out.p, s.part.p);
+  else
+    hipLaunchKernelGGL(k_img_misfit<4>, dim3(nb), dim3(256), 0, h->st, s.n, t.kind, t.level, t.smooth, t.weight, s.node.p,
+                       s.w.p, c, t.target.p, t.pweight.p, s.out.p, s.part.p);
+  GL_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_img_sum, dim3(1), dim3(1024), 0, h->st, (int64_t)nb, s.part.p, s.part.p + nb);
+  GL_CHECK_LAUNCH();
+  gl_sampler_transpose_dev(h, t.sampler, s.out.p, 1, g, 1, 0, true);
+  double sum = 0.0;
+  GL_HIP(hipMemcpyAsync(&sum, s.part.p + nb, sizeof(double), hipMemcpyDeviceToHost, h->st));
+  GL_HIP(hipStreamSynchronize(h->st));
+  return sum;
+}
+
+void gl_image_misfit_second(glims_ctx* h, const GlImageTerm& t, const double* c, const double* dc, int P, int64_t ld,
+                            double* dg) {
+  GlSampler& s = sampler_of(h, t.sampler, "glims_adjoint_hessian");
+  if (s.n == 0) return;
+  image_staging(h, s, P);
+  if (h->nv == 3)
+    hipLaunchKernelGGL(k_img_misfit_dir<3>, dim3(grid_of(s.n)), dim3(256), 0, h->st, s.n, P, ld, t.kind, t.level, t.smooth,
+                       t.weight, s.node.p, s.w.p, c, dc, t.target.p, t.pweight.p, s.out.p);
+  else
+    hipLaunchKernelGGL(k_img_misfit_dir<4>, dim3(grid_of(s.n)), dim3(256), 0, h->st, s.n, P, ld, t.kind, t.level, t.smooth,
+                       t.weight, s.node.p, s.w.p, c, dc, t.target.p, t.pweight.p, s.out.p);
+  GL_CHECK_LAUNCH();
+  gl_sampler_transpose_dev(h, t.sampler, s.out.p, P, dg, 1, ld, true);
+}
+
 void gl_sampler_destroy(glims_ctx* h, int64_t id) {
   (void)sampler_of(h, id, "glims_sampler_destroy");
+  for (size_t k = 0; k < h->img_terms.size(); ++k)
+    GL_REQUIRE(h->img_terms[k]->sampler != id, "glims_sampler_destroy: sampler " + std::to_string(id) +
+                                                   " is used by stored image term " + std::to_string(k) +
+                                                   " (glims_adjoint_image_terms)");
   GL_HIP(hipStreamSynchronize(h->st));
   delete h->samplers[(size_t)id];
   h->samplers[(size_t)id] = nullptr;
 }
 
 void gl_sampler_destroy_all(glims_ctx* h) {
+  for (auto* t : h->img_terms) delete t;
+  h->img_terms.clear();
   for (auto* s : h->samplers) delete s;
   h->samplers.clear();
 }

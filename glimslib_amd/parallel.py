@@ -359,6 +359,10 @@ class DistributedHandle:
         localised here; J and the per-label arrays come back bitwise the same on every rank, dJ/dc0 all-gathered into the
         global order (as get_state does).  elastic=True (on every rank alike) appends dJ/dE and dJ/dnu."""
         loc = []
+        terms = list(terms)
+        if any(t["kind"] in ("img_l2", "img_thresh") for t in terms):
+            # (glims_adjoint_image_terms refuses partitioned handles: the sampler's transpose is single rank)
+            raise NotImplementedError("image-space misfit terms: not available on partitioned runs; use a single-GPU handle")
         for t in terms:
             t = dict(t)
             bs = self.dim if t["kind"] in ("u_l2", _backend.MISFIT_U_L2) else 1

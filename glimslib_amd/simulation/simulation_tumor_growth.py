@@ -294,6 +294,51 @@ class TumorGrowth(FenicsSimulation):
         self.solver = HipTimeStepSolver(self, h, mechanics)
 
     # -- images of the results ------------------------------------------------------------------------------------
+    def _grid_sampler(self, origin, spacing, size):
+        """(key, sampler) of a voxel grid: located in the mesh once per simulation (handle) and grid."""
+        h = self._backend
+        key = (tuple(float(v) for v in origin), tuple(float(v) for v in spacing), tuple(int(v) for v in size))
+        cache = getattr(self, '_image_samplers', None)
+        if cache is None or cache[0] is not h:
+            cache = self._image_samplers = (h, {})
+        if key not in cache[1]:
+            cache[1][key] = h.sampler_grid(*key)
+        return key, cache[1][key]
+
+    def image_term(self, step, image, kind='img_thresh', level=0.0, smooth=1.0, weight=1.0, mask=None,
+                   volume_weighted=True):
+        """
+        A misfit term that compares the concentration of recorded step `step` with the voxel image `image`
+        (utils.data_io.Image) WHERE THE IMAGE WAS MEASURED:  1/2 w sum_voxels q (h(c(x_voxel)) - image)^2  with h the
+        identity (kind='img_l2') or the tanh threshold of level / smooth ('img_thresh': a T1- / T2-like segmentation,
+        image_based_optimization.py:660-708).  Pass it to adjoint_gradient / adjoint_hessian / ReducedFunctional in the same
+        list as the nodal terms.  The grid sampler is the cached one of sample_image; NaN voxels and voxels outside the mesh
+        are not observed; `mask` (array like the image, >= 0) weighs the voxels.  With volume_weighted the weight is
+        multiplied by the voxel volume, so that J approximates 1/2 w int (h(c) - image)^2 dx and is on the scale of the nodal
+        mass-matrix terms.  The same arguments give the same term object, whose arrays the backend uploads once.
+        """
+        if self._backend is None:
+            raise RuntimeError("image_term needs a run() first (the grid is located in the run's device mesh)")
+        if getattr(image, 'is_vector', False):
+            raise ValueError("image_term takes a scalar image")
+        key = (int(step), id(image), kind, float(level), float(smooth), float(weight), id(mask), bool(volume_weighted))
+        cache = getattr(self, '_image_terms', None)
+        if cache is None or cache[0] is not self._backend:
+            cache = self._image_terms = (self._backend, {})
+        if key not in cache[1]:
+            _, sampler = self._grid_sampler(image.GetOrigin(), image.GetSpacing(), image.GetSize())
+            target = np.ascontiguousarray(image.array, dtype=np.float64).reshape(-1)     # [z, y, x]: the sampler's order
+            q = None
+            if mask is not None:
+                q = np.ascontiguousarray(mask, dtype=np.float64).reshape(-1)
+                if q.shape != target.shape:
+                    raise ValueError("image_term: the mask has %d voxels, the image %d" % (q.size, target.size))
+            w = float(weight) * (float(np.prod(image.GetSpacing())) if volume_weighted else 1.0)
+            term = dict(step=int(step), kind=kind, level=float(level), smooth=float(smooth), weight=w, sampler=sampler,
+                        target=target, pweight=q)
+            cache[1][key] = (term, image, mask)   # (image and mask stay alive: their identity is the key)
+        return cache[1][key][0]
+
     def sample_image(self, subspace_name, recording_step, like=None, origin=None, spacing=None, size=None, fill=np.nan):
         """
         The recorded field `subspace_name` ('concentration' | 'displacement') of `recording_step` evaluated on a voxel grid
@@ -312,13 +357,7 @@ class TumorGrowth(FenicsSimulation):
         h = self._backend
         if h is None:
             raise RuntimeError("sample_image needs a run() first")
-        key = (tuple(float(v) for v in origin), tuple(float(v) for v in spacing), tuple(int(v) for v in size))
-        cache = getattr(self, '_image_samplers', None)
-        if cache is None or cache[0] is not h:
-            cache = self._image_samplers = (h, {})
-        if key not in cache[1]:
-            cache[1][key] = h.sampler_grid(*key)
-        sampler = cache[1][key]
+        key, sampler = self._grid_sampler(origin, spacing, size)
         sid = self.functionspace.get_subspace_id(subspace_name)
         obs = self.results.get_result(recording_step)
         if obs is None:

@@ -561,6 +561,43 @@ int glims_sampler_apply(glims_ctx* h, int64_t id, int field, int64_t snapshot, c
 int glims_sampler_apply_t(glims_ctx* h, int64_t id, const double* r, int ncomp, double* g);
 int glims_sampler_destroy(glims_ctx* h, int64_t id);   /* glims_destroy releases what is left */
 
+/* ---- image-space misfit terms: a voxel image or point set as an observation of the recorded trajectory --------------------
+ * The reference compares the simulated concentration with thresholded T1 / T2 segmentations
+ * (optimization_workflow/image_based_optimization.py:660-708, thresh() at :1404).  Here the data stay where they were
+ * measured: with P the sampler's operator (above) and p its points,
+ *   J_img = 1/2 w sum_p q_p (h((P c_k)_p) - t_p)^2,
+ *   dJ_img/dc_k = P^T r,            r_p = w q_p h'(v_p) (h(v_p) - t_p),   v = P c_k,
+ *   d(dJ_img/dc_k) . dc = P^T r2,   r2_p = w q_p (h'(v_p)^2 + h''(v_p) (h(v_p) - t_p)) (P dc)_p.
+ * A point is OBSERVED iff the sampler found it in the mesh, t_p is not NaN and q_p != 0; the others add nothing (a NaN target
+ * enters no arithmetic).  The terms are STORED on the handle: glims_adjoint_image_terms copies target and pweight to the device
+ * once, and every later glims_adjoint_gradient / _gradient_full / _hessian call adds the stored terms to the J of its nodal
+ * list (n_terms = 0 there is fine): per step the nodal terms in list order, then the step's image terms in their list order.
+ * They survive glims_setup, glims_set_materials, glims_set_state and a new recording (they depend on the sampler and the data
+ * only); a term's `step` is checked against the trajectory by the gradient / Hessian call (GLIMS_E_USAGE).  Nothing passes
+ * through the host between the trajectory and the adjoint's right-hand side; the sum over the points is taken in a fixed order
+ * (per block, then the blocks in order) and P^T is the atomics-free transpose of glims_sampler_apply_t: J and every output
+ * have the same bits on every call.  With no stored term every call issues exactly the work it issued before.
+ *
+ * glims_adjoint_image_terms REPLACES the handle's whole list (n = 0 clears it).  GLIMS_E_USAGE, with the old list left in
+ * place: unknown sampler id or kind, a threshold term with smooth <= 0, a non-finite weight, a negative or non-finite q_p, a
+ * null target.  GLIMS_E_HIP (with the figures) when hipMemGetInfo says the copies do not fit.  Partitioned handles
+ * (world > 1): n > 0 returns GLIMS_E_USAGE on every rank (P^T is refused there), n = 0 GLIMS_OK.  glims_sampler_destroy of a
+ * sampler that a stored term uses returns GLIMS_E_USAGE and destroys nothing; glims_destroy releases the stored terms.
+ * Neither call touches the forward state, glims_stats or glims_adjoint_stats. */
+#define GLIMS_MISFIT_IMG_L2     0   /* h = identity */
+#define GLIMS_MISFIT_IMG_THRESH 1   /* h(v) = 1/2 (tanh((v - level)/smooth) + 1), as GLIMS_MISFIT_C_THRESH */
+typedef struct glims_image_misfit {
+  int64_t step;            /* recorded step observed (0 = c_0) */
+  int64_t sampler;         /* id from glims_sampler_create_grid / _points on this handle */
+  int     kind;
+  double  level, smooth, weight;
+  const double* target;    /* [n_points], point order of the sampler; NaN = point not observed */
+  const double* pweight;   /* [n_points] q_p (mask, voxel volume, ...), or NULL = 1 */
+} glims_image_misfit;
+int glims_adjoint_image_terms(glims_ctx* h, int n, const glims_image_misfit* terms);
+/* out = (sampler id, number of points, number of observed points) of stored term k */
+int glims_adjoint_image_info(glims_ctx* h, int k, int64_t out[3]);
+
 /* ---- single-node multi-GPU (one process per GPU, RCCL over xGMI) ------------------------------------- */
 
 #define GLIMS_UNIQUE_ID_BYTES 256   /* two RCCL unique ids: halo communicator + reduction communicator */
