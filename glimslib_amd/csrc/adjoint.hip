@@ -17,12 +17,11 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <memory>
 
 #include <omp.h>
 
 namespace {
-
-inline unsigned grid_of(int64_t n, int bs = 256) { return (unsigned)std::max<int64_t>(1, (n + bs - 1) / bs); }
 
 // labels per sensitivity launch: per-thread accumulators live in registers (LT x 3 doubles)
 constexpr int GL_ADJ_LT = 8;
@@ -32,6 +31,24 @@ __device__ __forceinline__ double wsum(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
   return v;
+}
+
+// Fixed-order epilogue of a 256-thread block that holds N per-thread sums: every wave's butterfly, then the block's four wave
+// sums as (w0 + w1) + (w2 + w3), one store per sum into part[block][N].  No atomics: the partials are bitwise reproducible.
+template <int N>
+__device__ __forceinline__ void block_partials(double (&v)[N], double* __restrict__ part) {
+  __shared__ double sm[4][N];
+  const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    const double t = wsum(v[k]);
+    if (lane == 0) sm[wid][k] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x < N) {
+    const int k = threadIdx.x;
+    part[(size_t)blockIdx.x * N + k] = (sm[0][k] + sm[1][k]) + (sm[2][k] + sm[3][k]);
+  }
 }
 
 // internal node of every cell vertex, from the row-owned incidence lists: the row whose diagonal slot is vertex m of cell e
@@ -210,6 +227,8 @@ __global__ __launch_bounds__(256) void k_sens(int64_t n_cells, int l0, const int
         acc[q][1] += a1;
       }
   }
+  // block_partials, written out: through the call MODE 1 loses the folding of its eight zero sums (acc[q][1]) and takes
+  // 16 / 18 more VGPRs in 2-D / 3-D
   __shared__ double sm[4][GL_ADJ_LT * 2];
   const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #pragma unroll
@@ -312,10 +331,7 @@ __global__ void k_perm(int64_t n, int bs, const int32_t* __restrict__ old2new, c
 struct AdjWork {
   dvec<double> lam, lam_next, rhs, g, r, u, w, p, s, e, hp, Me, tmp, qcell, part, sums, esums, vA, dinv, stage;
   dvec<double> uk, murhs, mu, mr, mu_, mw, mp, ms, mKx;
-  std::vector<dvec<double>*> targets;
-  ~AdjWork() {
-    for (auto* t : targets) delete t;
-  }
+  std::vector<std::unique_ptr<dvec<double>>> targets;
 };
 
 // Leaves the forward state as it was, also when an exception leaves gl_adjoint_gradient: the time stepper's Jacobian and
@@ -377,30 +393,40 @@ void image_terms_of_step(glims_ctx* h, int step, const double* c, double* g, dou
   }
 }
 
-// mode 0: (c, lambda) -> sums[l][0..1];  mode 1: (c, mu) -> sums[l][2] and qcell;  mode 2: (u, mu) -> esums[l][0..1]
+inline int sens_blocks(const glims_ctx* h) { return (int)std::min<int64_t>(GL_ADJ_BLOCKS, grid_of(h->n_cells)); }
+
+// k_sens<D, mode> over the labels, GL_ADJ_LT per launch, each followed by k_sens_final into sums[l][k_off + 0..1] (ls sums per
+// label; the sums beyond ls are dropped).  sums == nullptr (mode 1, qcell alone): the l0 = 0 launch writes qcell, no other runs.
 template <int D>
-void sens_pass(glims_ctx* h, int mode, const double* c, const double* v, AdjWork& wk) {
-  const AdjointState& a = h->adj;
-  const int nb = (int)std::min<int64_t>(GL_ADJ_BLOCKS, grid_of(h->n_cells));
-  const uint8_t* counted = h->world > 1 ? a.counted.p : nullptr;
+void sens_pass(glims_ctx* h, int mode, const double* mat, const double* c, const double* v, const uint8_t* counted,
+               double* qcell, double* part, double* sums, int ls, int k_off) {
+  const int nb = sens_blocks(h);
+  const auto kern = mode == 0 ? k_sens<D, 0> : mode == 1 ? k_sens<D, 1> : k_sens<D, 2>;
   for (int l0 = 0; l0 < h->n_labels; l0 += GL_ADJ_LT) {
-    if (mode == 0)
-      hipLaunchKernelGGL((k_sens<D, 0>), dim3(nb), dim3(256), 0, h->st, h->n_cells, l0, a.cell_nodes.p, h->egeo.p,
-                         h->label.p, h->mat.p, c, v, counted, wk.qcell.p, wk.part.p);
-    else if (mode == 1)
-      hipLaunchKernelGGL((k_sens<D, 1>), dim3(nb), dim3(256), 0, h->st, h->n_cells, l0, a.cell_nodes.p, h->egeo.p,
-                         h->label.p, h->mat.p, c, v, counted, wk.qcell.p, wk.part.p);
-    else
-      hipLaunchKernelGGL((k_sens<D, 2>), dim3(nb), dim3(256), 0, h->st, h->n_cells, l0, a.cell_nodes.p, h->egeo.p,
-                         h->label.p, h->mat.p, c, v, counted, wk.qcell.p, wk.part.p);
+    hipLaunchKernelGGL(kern, dim3(nb), dim3(256), 0, h->st, h->n_cells, l0, h->adj.cell_nodes.p, h->egeo.p, h->label.p, mat, c,
+                       v, counted, qcell, part);
     GL_CHECK_LAUNCH();
-    if (mode < 2)
-      hipLaunchKernelGGL(k_sens_final, dim3(1), dim3(1024), 0, h->st, nb, l0, h->n_labels, 3, mode == 0 ? 0 : 2, wk.part.p,
-                         wk.sums.p);
-    else
-      hipLaunchKernelGGL(k_sens_final, dim3(1), dim3(1024), 0, h->st, nb, l0, h->n_labels, 2, 0, wk.part.p, wk.esums.p);
+    if (!sums) break;
+    hipLaunchKernelGGL(k_sens_final, dim3(1), dim3(1024), 0, h->st, nb, l0, h->n_labels, ls, k_off, part, sums);
     GL_CHECK_LAUNCH();
   }
+}
+
+// A host vector [n_nodes][bs] in the caller's numbering into dst in the internal numbering, and a scalar device vector back
+// out, both through the staging buffer and synchronised (the buffer is free again on return)
+void upload_permuted(glims_ctx* h, AdjWork& wk, const double* host, int bs, double* dst) {
+  const int64_t nn = h->n_nodes;
+  GL_HIP(hipMemcpyAsync(wk.stage.p, host, (size_t)nn * bs * sizeof(double), hipMemcpyHostToDevice, h->st));
+  hipLaunchKernelGGL(k_perm, dim3(grid_of(nn * bs)), dim3(256), 0, h->st, nn, bs, h->d_old2new.p, wk.stage.p, dst, 1);
+  GL_CHECK_LAUNCH();
+  GL_HIP(hipStreamSynchronize(h->st));
+}
+void download_permuted(glims_ctx* h, AdjWork& wk, const double* src, double* host) {
+  const int64_t nn = h->n_nodes;
+  hipLaunchKernelGGL(k_perm, dim3(grid_of(nn)), dim3(256), 0, h->st, nn, 1, h->d_old2new.p, src, wk.stage.p, 0);
+  GL_CHECK_LAUNCH();
+  GL_HIP(hipMemcpyAsync(host, wk.stage.p, (size_t)nn * sizeof(double), hipMemcpyDeviceToHost, h->st));
+  GL_HIP(hipStreamSynchronize(h->st));
 }
 
 // K_el x = rhs with the Dirichlet dofs eliminated (x = xD there, or 0), to ||r|| <= rtol ||rhs||; the forward solve's
@@ -493,39 +519,60 @@ void adjoint_setup(glims_ctx* h, int n_terms, const glims_misfit* terms, bool el
   // targets -> internal numbering
   for (int k = 0; k < n_terms; ++k) {
     const int bs = terms[k].kind == GLIMS_MISFIT_U_L2 ? D : 1;
-    auto* t = new dvec<double>();
-    wk.targets.push_back(t);
-    t->alloc_zero((size_t)nn * bs, h->st);
-    GL_HIP(hipMemcpyAsync(wk.stage.p, terms[k].target, (size_t)nn * bs * sizeof(double), hipMemcpyHostToDevice, h->st));
-    hipLaunchKernelGGL(k_perm, dim3(grid_of(nn * bs)), dim3(256), 0, h->st, nn, bs, h->d_old2new.p, wk.stage.p, t->p, 1);
-    GL_CHECK_LAUNCH();
-    GL_HIP(hipStreamSynchronize(h->st));   // the staging buffer is reused by the next target
+    wk.targets.push_back(std::make_unique<dvec<double>>());
+    wk.targets.back()->alloc_zero((size_t)nn * bs, h->st);
+    upload_permuted(h, wk, terms[k].target, bs, wk.targets.back()->p);
   }
   build_cell_nodes<D>(h);
 }
 
+// The first-order backward sweep, step by step: what glims_adjoint_gradient runs, and what glims_adjoint_hessian runs with
+// its second-order work in between (same kernels, same order, same buffers: J and the gradient have the same bits in both).
+// Construct it after the ForwardGuard (the lazy RD hierarchy is the guard's to drop).  A step is
+//   c = begin_step;  have_u = nodal_terms;  [image terms: the caller]  if (have_u) coupling_adjoint;
+//   step 0: c0_output, else lambda_solve -- each stops the sweep by setting `status`.
 template <int D>
-int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_out, double* dD, double* drho,
-               double* dgamma, double* dc0, double* dE, double* dnu) {
-  AdjointState& a = h->adj;
-  const int64_t n = h->n_own, nn = h->n_nodes, nd = nn * D;
-  const int N = (int)a.traj.size() - 1;
-  const double t0 = omp_get_wtime();
-  AdjWork wk;
-  const bool elastic = dE || dnu;   // the E / nu pass runs only when asked for
-  adjoint_setup<D>(h, n_terms, terms, elastic, wk);
-  ForwardGuard guard(h, wk);
-  const uint8_t* fxc = h->have_fixed_c ? h->fixed_c.p : nullptr;
-  const bool rd_mg = h->rd_precond_active == GLIMS_RD_PRECOND_MULTIGRID;
-  if (rd_mg && !h->mg_rd.ready) gl_mg_setup_rd(h);
-  const int rd_deg = h->opt.rd_mg_smooth > 0 ? h->opt.rd_mg_smooth : (h->mg_rd.lattice ? 1 : 3);
+struct BackwardSweep {
+  glims_ctx* h;
+  AdjWork& wk;
+  const int n_terms;
+  const glims_misfit* terms;
+  const bool elastic;   // the E / nu pass (mode 2) runs with the coupling adjoint
+  const uint8_t* fxc;
+  bool rd_mg;
+  int rd_deg;
   double J = 0.0;
   int status = GLIMS_OK;
-  for (int step = N; step >= 0 && status == GLIMS_OK; --step) {
+
+  BackwardSweep(glims_ctx* h_, AdjWork& w, int n_terms_, const glims_misfit* terms_, bool elastic_)
+      : h(h_), wk(w), n_terms(n_terms_), terms(terms_), elastic(elastic_) {
+    fxc = h->have_fixed_c ? h->fixed_c.p : nullptr;
+    rd_mg = h->rd_precond_active == GLIMS_RD_PRECOND_MULTIGRID;
+    if (rd_mg && !h->mg_rd.ready) gl_mg_setup_rd(h);
+    rd_deg = h->opt.rd_mg_smooth > 0 ? h->opt.rd_mg_smooth : (h->mg_rd.lattice ? 1 : 3);
+  }
+  int last_step() const { return (int)h->adj.traj.size() - 1; }
+
+  // mode 0: (c, lambda) -> sums[l][0..1];  mode 1: (c, mu) -> sums[l][2] and qcell;  mode 2: (u, mu) -> esums[l][0..1]
+  void sens(int mode, const double* c, const double* v) {
+    sens_pass<D>(h, mode, h->mat.p, c, v, h->world > 1 ? h->adj.counted.p : nullptr, wk.qcell.p, wk.part.p,
+                 mode < 2 ? wk.sums.p : wk.esums.p, mode < 2 ? 3 : 2, mode == 1 ? 2 : 0);
+  }
+
+  // c_n with current ghosts, g = 0
+  const double* begin_step(int step) {
     // (c_n as recorded: gl_step leaves the ghosts of c current, but the adjoint does not rely on it -- one exchange per step)
-    gl_halo_exchange(h, a.traj[step]->p, 1);
-    const double* c = a.traj[step]->p;
-    GL_HIP(hipMemsetAsync(wk.g.p, 0, (size_t)nn * sizeof(double), h->st));
+    gl_halo_exchange(h, h->adj.traj[step]->p, 1);
+    GL_HIP(hipMemsetAsync(wk.g.p, 0, (size_t)h->n_nodes * sizeof(double), h->st));
+    return h->adj.traj[step]->p;
+  }
+
+  // The nodal terms that observe `step`, in list order: J and g += dJ/dc_n of the concentration terms (after each,
+  // after_c_term(term) runs while wk.Me still holds M (h(c) - t)); the displacement terms solve u_k once and add dJ/du_n to
+  // murhs.  True when the step has a displacement term (the coupling adjoint follows).
+  template <class Hook>
+  bool nodal_terms(int step, const double* c, Hook&& after_c_term) {
+    const int64_t n = h->n_own;
     bool have_u = false;
     for (int k = 0; k < n_terms; ++k) {
       const glims_misfit& tm = terms[k];
@@ -540,14 +587,15 @@ int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_o
         J += 0.5 * tm.weight * gl_dot(h, wk.e.p, wk.Me.p, n);
         hipLaunchKernelGGL(k_add_scaled_prod, dim3(grid_of(n)), dim3(256), 0, h->st, n, tm.weight, wk.hp.p, wk.Me.p, wk.g.p);
         GL_CHECK_LAUNCH();
+        after_c_term(tm);
         continue;
       }
       if (!have_u) {   // u_k = K_el^-1 (G c_k + f), once per observed step
         gl_apply_G(h, c, wk.murhs.p);
         int64_t its = 0;
         status = solve_elastic(h, wk, wk.murhs.p, wk.uk.p, h->have_fixed_u ? h->m_uD.p : nullptr, 1e-12, &its);
-        if (status != GLIMS_OK) break;
-        GL_HIP(hipMemsetAsync(wk.murhs.p, 0, (size_t)nd * sizeof(double), h->st));
+        if (status != GLIMS_OK) return have_u;
+        GL_HIP(hipMemsetAsync(wk.murhs.p, 0, (size_t)h->n_nodes * D * sizeof(double), h->st));
         have_u = true;
       }
       for (int comp = 0; comp < D; ++comp) {   // dJ/du = w M_vec (u - t), component by component through the scalar M
@@ -561,33 +609,40 @@ int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_o
         GL_CHECK_LAUNCH();
       }
     }
-    if (status != GLIMS_OK) break;
-    image_terms_of_step(h, step, c, wk.g.p, &J);
-    if (have_u) {   // mu = K_el^-1 dJ/du (0 on the constrained dofs); g += G^T mu; dJ/dgamma_t += mu^T G_t c
-      int64_t its = 0;
-      status = solve_elastic(h, wk, wk.murhs.p, wk.mu.p, nullptr, 1e-12, &its);
-      if (status != GLIMS_OK) break;
-      gl_halo_exchange(h, wk.mu.p, D);   // qcell of every local cell, also those whose other vertices are ghosts
-      sens_pass<D>(h, 1, c, wk.mu.p, wk);
-      hipLaunchKernelGGL(k_gt_rows, dim3(grid_of(n)), dim3(256), 0, h->st, n, h->pat.cslice_ptr.p, h->pat.celem.p,
-                         wk.qcell.p, wk.g.p);
-      GL_CHECK_LAUNCH();
-      if (elastic) {   // A_t, B_t from u_k (its clamp values in place: solve_elastic wrote them) and mu_k
-        gl_halo_exchange(h, wk.uk.p, D);   // PCG updates the owned rows: the cells at the cut read u_k at their ghosts
-        sens_pass<D>(h, 2, wk.uk.p, wk.mu.p, wk);
-      }
+    return have_u;
+  }
+
+  // mu = K_el^-1 dJ/du (0 on the constrained dofs); g += G^T mu; dJ/dgamma_t += mu^T G_t c
+  bool coupling_adjoint(const double* c) {
+    const int64_t n = h->n_own;
+    int64_t its = 0;
+    status = solve_elastic(h, wk, wk.murhs.p, wk.mu.p, nullptr, 1e-12, &its);
+    if (status != GLIMS_OK) return false;
+    gl_halo_exchange(h, wk.mu.p, D);   // qcell of every local cell, also those whose other vertices are ghosts
+    sens(1, c, wk.mu.p);
+    hipLaunchKernelGGL(k_gt_rows, dim3(grid_of(n)), dim3(256), 0, h->st, n, h->pat.cslice_ptr.p, h->pat.celem.p, wk.qcell.p,
+                       wk.g.p);
+    GL_CHECK_LAUNCH();
+    if (elastic) {   // A_t, B_t from u_k (its clamp values in place: solve_elastic wrote them) and mu_k
+      gl_halo_exchange(h, wk.uk.p, D);   // PCG updates the owned rows: the cells at the cut read u_k at their ghosts
+      sens(2, wk.uk.p, wk.mu.p);
     }
-    if (step == 0) {   // dJ/dc_0 = M lambda_1 + g_0
-      if (dc0) {
-        if (N > 0) gl_launch_spmv(h, h->st, h->pat.n_slices, nullptr, h->vM.p, wk.lam_next.p, wk.rhs.p, nullptr, wk.g.p,
-                                  nullptr, nullptr, 0, nullptr);
-        else GL_HIP(hipMemcpyAsync(wk.rhs.p, wk.g.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, h->st));
-        hipLaunchKernelGGL(k_perm, dim3(grid_of(nn)), dim3(256), 0, h->st, nn, 1, h->d_old2new.p, wk.rhs.p, wk.stage.p, 0);
-        GL_CHECK_LAUNCH();
-        GL_HIP(hipMemcpyAsync(dc0, wk.stage.p, (size_t)nn * sizeof(double), hipMemcpyDeviceToHost, h->st));
-      }
-      break;
-    }
+    return true;
+  }
+
+  // dJ/dc_0 = M lambda_1 + g_0, in the caller's numbering
+  void c0_output(double* dc0) {
+    if (last_step() > 0) gl_launch_spmv(h, h->st, h->pat.n_slices, nullptr, h->vM.p, wk.lam_next.p, wk.rhs.p, nullptr, wk.g.p,
+                                        nullptr, nullptr, 0, nullptr);
+    else GL_HIP(hipMemcpyAsync(wk.rhs.p, wk.g.p, (size_t)h->n_own * sizeof(double), hipMemcpyDeviceToDevice, h->st));
+    download_permuted(h, wk, wk.rhs.p, dc0);
+  }
+
+  // lambda_n: A(c_n) lambda_n = g_n + M lambda_{n+1} (masked) by PCG from lambda_{n+1}, then its D / rho sums.  Leaves
+  // lambda_n in wk.lam and A(c_n) with its diagonal in the swapped-in buffers; the caller ends the step with end_step().
+  bool lambda_solve(const double* c) {
+    AdjointState& a = h->adj;
+    const int64_t n = h->n_own, nn = h->n_nodes;
     // rhs = g_n + M lambda_{n+1}, 0 on the constrained nodes
     gl_launch_spmv(h, h->st, h->pat.n_slices, nullptr, h->vM.p, wk.lam_next.p, wk.rhs.p, fxc, wk.g.p, nullptr, nullptr, 0,
                    nullptr);
@@ -596,7 +651,6 @@ int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_o
     // A(c_n) (and its diagonal) into the swapped-in buffers; the residual output is scratch (b = 0)
     GL_HIP(hipMemsetAsync(wk.tmp.p, 0, (size_t)nn * sizeof(double), h->st));
     gl_rd_assemble(h, c, wk.tmp.p, nullptr, wk.w.p, nullptr, h->partials.p);
-    // lambda_n: PCG from lambda_{n+1}
     GL_HIP(hipMemcpyAsync(wk.lam.p, wk.lam_next.p, (size_t)nn * sizeof(double), hipMemcpyDeviceToDevice, h->st));
     gl_launch_spmv(h, h->st, h->pat.n_slices, nullptr, h->vA.p, wk.lam.p, wk.w.p, fxc, nullptr, nullptr, nullptr, 0, nullptr);
     hipLaunchKernelGGL(k_residual, dim3(grid_of(n)), dim3(256), 0, h->st, n, wk.rhs.p, wk.w.p, fxc, wk.r.p);
@@ -604,7 +658,7 @@ int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_o
     const double nb = std::sqrt(gl_dot(h, wk.rhs.p, wk.rhs.p, n));
     if (!std::isfinite(nb)) {
       status = GLIMS_NAN;
-      break;
+      return false;
     }
     if (nb > 0.0) {
       int64_t its = 0;
@@ -612,15 +666,54 @@ int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_o
       status = gl_pcg(h, wk.lam.p, wk.r.p, wk.u.p, wk.w.p, wk.p.p, wk.s.p, h->dinv.p, h->vA.p, fxc, 1,
                       rd_mg ? &h->mg_rd : nullptr, rd_deg, 1e-12 * nb, std::max(h->opt.cg_maxit, 20000), &its, &res);
       a.pcg_its += its;
-      if (status != GLIMS_OK) break;
+      if (status != GLIMS_OK) return false;
       gl_halo_exchange(h, wk.lam.p, 1);   // PCG updates the owned rows: the sensitivity pass and M lambda read the ghosts
-      sens_pass<D>(h, 0, c, wk.lam.p, wk);
+      sens(0, c, wk.lam.p);
     } else {
       GL_HIP(hipMemsetAsync(wk.lam.p, 0, (size_t)nn * sizeof(double), h->st));
     }
-    std::swap(wk.lam.p, wk.lam_next.p);
-    a.steps++;
+    return true;
   }
+  void end_step() {   // lambda_n becomes lambda_{n+1}
+    std::swap(wk.lam.p, wk.lam_next.p);
+    h->adj.steps++;
+  }
+
+  // dJ/dD_t, dJ/drho_t, dJ/dgamma_t from the [L][3] sums
+  void write_labels(const double* sums, double* dD, double* drho, double* dgamma) const {
+    const double dt = h->opt.dt;
+    for (int l = 0; l < h->n_labels; ++l) {
+      if (dD) dD[l] = -dt * sums[l * 3 + 0];
+      if (drho) drho[l] = -dt * sums[l * 3 + 1];
+      if (dgamma) dgamma[l] = sums[l * 3 + 2];
+    }
+  }
+};
+
+template <int D>
+int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_out, double* dD, double* drho,
+               double* dgamma, double* dc0, double* dE, double* dnu) {
+  AdjointState& a = h->adj;
+  const double t0 = omp_get_wtime();
+  AdjWork wk;
+  const bool elastic = dE || dnu;   // the E / nu pass runs only when asked for
+  adjoint_setup<D>(h, n_terms, terms, elastic, wk);
+  ForwardGuard guard(h, wk);
+  BackwardSweep<D> sw(h, wk, n_terms, terms, elastic);
+  for (int step = sw.last_step(); step >= 0; --step) {
+    const double* c = sw.begin_step(step);
+    const bool have_u = sw.nodal_terms(step, c, [](const glims_misfit&) {});
+    if (sw.status != GLIMS_OK) break;
+    image_terms_of_step(h, step, c, wk.g.p, &sw.J);
+    if (have_u && !sw.coupling_adjoint(c)) break;
+    if (step == 0) {
+      if (dc0) sw.c0_output(dc0);
+      break;
+    }
+    if (!sw.lambda_solve(c)) break;
+    sw.end_step();
+  }
+  const int status = sw.status;
   // sums: [L][3] (D, rho, gamma), then [L][2] (A, B) when the E / nu pass ran
   const size_t L3 = (size_t)h->n_labels * 3, L2 = elastic ? (size_t)h->n_labels * 2 : 0, W = L3 + L2;
   std::vector<double> sums(W);
@@ -647,12 +740,7 @@ int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_o
       sums[k] = t;
     }
   }
-  const double dt = h->opt.dt;
-  for (int l = 0; l < h->n_labels; ++l) {
-    if (dD) dD[l] = -dt * sums[l * 3 + 0];
-    if (drho) drho[l] = -dt * sums[l * 3 + 1];
-    if (dgamma) dgamma[l] = sums[l * 3 + 2];
-  }
+  sw.write_labels(sums.data(), dD, drho, dgamma);
   for (int l = 0; elastic && l < h->n_labels; ++l) {
     // C_t = sum_k int_t |T|/(d+1) div mu_k sum_a c_k,a = (dJ/dgamma sum) / (2 mu_t + d lam_t): mode 1's sum carries the factor
     const double* mh = h->mat_host.data();
@@ -671,7 +759,7 @@ int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_o
       dnu[l] = gam * (2.0 * mp + D * lp) * Ct - (2.0 * mp * At + lp * Bt);
     }
   }
-  *J_out = J;
+  *J_out = sw.J;
   a.gradients++;
   a.ms_backward += 1e3 * (omp_get_wtime() - t0);
   return status;
@@ -851,20 +939,7 @@ __global__ __launch_bounds__(256) void k_hsens(int64_t n_cells, int l0, const in
         acc[q][1] += a1;
       }
   }
-  __shared__ double sm[4][GL_ADJ_LT * 2];
-  const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int q = 0; q < GL_ADJ_LT; ++q)
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const double t = wsum(acc[q][k]);
-      if (lane == 0) sm[wid][q * 2 + k] = t;
-    }
-  __syncthreads();
-  if (threadIdx.x < GL_ADJ_LT * 2) {
-    const int t = threadIdx.x;
-    partials[(size_t)blockIdx.x * GL_ADJ_LT * 2 + t] = (sm[0][t] + sm[1][t]) + (sm[2][t] + sm[3][t]);
-  }
+  block_partials(reinterpret_cast<double (&)[GL_ADJ_LT * 2]>(acc), partials);   // flat: [q][k] at q * 2 + k
 }
 
 // y[row][a] = (G dc + sum_t dgamma_t G_t c)[row][a] = sum over the row's cells of
@@ -942,21 +1017,6 @@ __global__ void k_misfit_second(int64_t n, int kind, double level, double smooth
   dg[i] += w * (hp * Mhd[i] + h2 * Me[i] * dc[i]);
 }
 
-// MODE 1 of k_sens with the material table `mat`: qcell (the cells' shares of G^T v) and, when sums is not null,
-// sums[l][2] += v^T G_l c (gamma = 1)
-template <int D>
-void gt_pass(glims_ctx* h, const double* mat, const double* c, const double* v, double* qcell, double* part, double* sums) {
-  const int nb = (int)std::min<int64_t>(GL_ADJ_BLOCKS, grid_of(h->n_cells));
-  for (int l0 = 0; l0 < h->n_labels; l0 += GL_ADJ_LT) {
-    hipLaunchKernelGGL((k_sens<D, 1>), dim3(nb), dim3(256), 0, h->st, h->n_cells, l0, h->adj.cell_nodes.p, h->egeo.p,
-                       h->label.p, mat, c, v, (const uint8_t*)nullptr, qcell, part);
-    GL_CHECK_LAUNCH();
-    if (!sums) break;   // (qcell comes from the l0 = 0 launch)
-    hipLaunchKernelGGL(k_sens_final, dim3(1), dim3(1024), 0, h->st, nb, l0, h->n_labels, 3, 2, part, sums);
-    GL_CHECK_LAUNCH();
-  }
-}
-
 // A(c_n) x = rhs (0 on the constrained nodes) by the PCG of the first-order adjoint's lambda solve; x holds the initial
 // guess on entry (its constrained entries are set to 0)
 int rd_solve(glims_ctx* h, AdjWork& wk, const uint8_t* fxc, bool rd_mg, int rd_deg, const double* rhs, double* x,
@@ -1002,22 +1062,6 @@ __global__ void k_mp_pack(int64_t n, int64_t ld, const double* __restrict__ src,
   }
 }
 
-template <int P>
-__device__ __forceinline__ void mp_block_partials(double (&v)[2 * P], double* __restrict__ part) {
-  __shared__ double sm[4][2 * P];
-  const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int k = 0; k < 2 * P; ++k) {
-    const double t = wsum(v[k]);
-    if (lane == 0) sm[wid][k] = t;
-  }
-  __syncthreads();
-  if (threadIdx.x < 2 * P) {
-    const int k = threadIdx.x;
-    part[(size_t)blockIdx.x * 2 * P + k] = (sm[0][k] + sm[1][k]) + (sm[2][k] + sm[3][k]);
-  }
-}
-
 // mode 0 (start): r = b - Ax (Ax in q), p = z = Dinv r;  mode 1 (iteration): x += alpha p, r -= alpha q, z = Dinv r.
 // Both leave the block partials of (r.z, r.r) per column.
 template <int P>
@@ -1058,7 +1102,7 @@ __global__ __launch_bounds__(256) void k_mp_vec(int mode, int64_t n, const uint8
       v[2 * j + 1] += rr * rr;
     }
   }
-  mp_block_partials<P>(v, part);
+  block_partials(v, part);
 }
 
 // p = Dinv r + beta p (columns still running)
@@ -1240,10 +1284,8 @@ struct AdjCountGuard {
   }
 };
 
-// The first-order sweep of gradient_t, preceded by the tangent-linear sweep and interleaved with the second-order adjoint
-// solves of every direction.  Its per-step misfit / lambda / sensitivity body is a copy of gradient_t's (same kernels, same
-// order, same buffers: J and the gradient keep its bits, which tests/test_gpu_adjoint_hessian.py checks); a change to one
-// belongs in the other.
+// The tangent-linear sweep, then gradient_t's backward sweep (BackwardSweep: J and the gradient keep its bits, which
+// tests/test_gpu_adjoint_hessian.py checks) with the second-order adjoint work of every direction between its parts.
 template <int D>
 int hessian_t(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, const double* dir_D, const double* dir_rho,
               const double* dir_gamma, const double* dir_c0, double* J_out, double* dD, double* drho, double* dgamma,
@@ -1297,28 +1339,19 @@ int hessian_t(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, const
     ue.alloc_zero((size_t)nn, h->st);
     uMe.alloc_zero((size_t)nn, h->st);
   }
-  if (dir_c0)
-    for (int p = 0; p < P; ++p) {
-      GL_HIP(hipMemcpyAsync(wk.stage.p, dir_c0 + (size_t)p * nn, (size_t)nn * sizeof(double), hipMemcpyHostToDevice, h->st));
-      hipLaunchKernelGGL(k_perm, dim3(grid_of(nn)), dim3(256), 0, h->st, nn, 1, h->d_old2new.p, wk.stage.p,
-                         dcs.p + (size_t)p * nn, 1);
-      GL_CHECK_LAUNCH();
-      GL_HIP(hipStreamSynchronize(h->st));
-    }
+  for (int p = 0; dir_c0 && p < P; ++p) upload_permuted(h, wk, dir_c0 + (size_t)p * nn, 1, dcs.p + (size_t)p * nn);
   auto dc_of = [&](int step, int p) { return dcs.p + ((size_t)step * P + p) * nn; };
   MultiPcg mp;   // the P-column solver's interleaved vectors [n_nodes][P] and scalars
   for (auto* v : {&mp.X, &mp.B, &mp.R, &mp.Pv, &mp.Q}) v->alloc_zero((size_t)P * nn, h->st);
   mp.part.alloc_zero((size_t)gl_spmm_blocks(h) * P, h->st);
   mp.part2.alloc_zero((size_t)GL_MP_BLOCKS * 2 * P, h->st);
   ForwardGuard guard(h, wk);
-  const uint8_t* fxc = h->have_fixed_c ? h->fixed_c.p : nullptr;
-  const bool rd_mg = h->rd_precond_active == GLIMS_RD_PRECOND_MULTIGRID;
-  if (rd_mg && !h->mg_rd.ready) gl_mg_setup_rd(h);
-  const int rd_deg = h->opt.rd_mg_smooth > 0 ? h->opt.rd_mg_smooth : (h->mg_rd.lattice ? 1 : 3);
+  BackwardSweep<D> sw(h, wk, n_terms, terms, false);
+  const uint8_t* fxc = sw.fxc;
   const DevPattern& pt = h->pat;
   const double dt = h->opt.dt;
   int64_t tlm_its = 0, soa_its = 0, extra_mech = 0;
-  int status = GLIMS_OK;
+  int& status = sw.status;
   // 1. tangent-linear sweep: A(c_n) dc_n = M dc_{n-1} - dt sum_t dD_t K_t c_n - dt sum_t drho_t int_t (c_n^2 - c_n) phi
   for (int step = 1; step <= N && status == GLIMS_OK; ++step) {
     const double* c = a.traj[step]->p;
@@ -1343,75 +1376,38 @@ int hessian_t(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, const
       for (int p = 0; p < P; ++p)
         hipLaunchKernelGGL(k_zero_fixed, dim3(grid_of(n)), dim3(256), 0, h->st, n, fxc, dc_of(step, p),
                            (const double*)nullptr);
-    status = rd_solve_cols(h, wk, mp, fxc, rd_mg, rd_deg, P, hrhs.p, dc_of(step, 0), nn, &tlm_its);
+    status = rd_solve_cols(h, wk, mp, fxc, sw.rd_mg, sw.rd_deg, P, hrhs.p, dc_of(step, 0), nn, &tlm_its);
   }
   // 2. the first-order sweep with the second-order adjoint nu_n of every direction
-  double J = 0.0;
   for (int step = N; step >= 0 && status == GLIMS_OK; --step) {
-    gl_halo_exchange(h, a.traj[step]->p, 1);
-    const double* c = a.traj[step]->p;
-    GL_HIP(hipMemsetAsync(wk.g.p, 0, (size_t)nn * sizeof(double), h->st));
+    const double* c = sw.begin_step(step);
     GL_HIP(hipMemsetAsync(dg.p, 0, (size_t)P * nn * sizeof(double), h->st));
-    bool have_u = false;
-    for (int k = 0; k < n_terms; ++k) {
-      const glims_misfit& tm = terms[k];
-      if (tm.step != step) continue;
-      const double* t = wk.targets[k]->p;
-      if (tm.kind != GLIMS_MISFIT_U_L2) {
-        hipLaunchKernelGGL(k_misfit_c, dim3(grid_of(n)), dim3(256), 0, h->st, n, tm.kind, tm.level, tm.smooth, c, t, wk.e.p,
-                           wk.hp.p);
+    // after each concentration term, while wk.Me holds M (h - t):  dg_p += w (h' M(h' dc_p) + h'' M(h - t) dc_p)
+    const bool have_u = sw.nodal_terms(step, c, [&](const glims_misfit& tm) {
+      for (int p = 0; p < P; ++p) {
+        hipLaunchKernelGGL(k_misfit_dir, dim3(grid_of(n)), dim3(256), 0, h->st, n, tm.kind, tm.level, tm.smooth, c,
+                           dc_of(step, p), hd.p);
         GL_CHECK_LAUNCH();
-        gl_halo_exchange(h, wk.e.p, 1);
-        mass_apply(h, wk.e.p, wk.Me.p);
-        J += 0.5 * tm.weight * gl_dot(h, wk.e.p, wk.Me.p, n);
-        hipLaunchKernelGGL(k_add_scaled_prod, dim3(grid_of(n)), dim3(256), 0, h->st, n, tm.weight, wk.hp.p, wk.Me.p, wk.g.p);
-        GL_CHECK_LAUNCH();
-        for (int p = 0; p < P; ++p) {   // dg_p += w (h' M(h' dc) + h'' M(h - t) dc)
-          hipLaunchKernelGGL(k_misfit_dir, dim3(grid_of(n)), dim3(256), 0, h->st, n, tm.kind, tm.level, tm.smooth, c,
-                             dc_of(step, p), hd.p);
-          GL_CHECK_LAUNCH();
-          mass_apply(h, hd.p, Mhd.p);
-          hipLaunchKernelGGL(k_misfit_second, dim3(grid_of(n)), dim3(256), 0, h->st, n, tm.kind, tm.level, tm.smooth,
-                             tm.weight, c, dc_of(step, p), wk.Me.p, Mhd.p, dg.p + (size_t)p * nn);
-          GL_CHECK_LAUNCH();
-        }
-        continue;
-      }
-      if (!have_u) {
-        gl_apply_G(h, c, wk.murhs.p);
-        int64_t its = 0;
-        status = solve_elastic(h, wk, wk.murhs.p, wk.uk.p, h->have_fixed_u ? h->m_uD.p : nullptr, 1e-12, &its);
-        if (status != GLIMS_OK) break;
-        GL_HIP(hipMemsetAsync(wk.murhs.p, 0, (size_t)nd * sizeof(double), h->st));
-        have_u = true;
-      }
-      for (int comp = 0; comp < D; ++comp) {
-        hipLaunchKernelGGL(k_component, dim3(grid_of(n)), dim3(256), 0, h->st, n, D, comp, wk.uk.p, t, wk.e.p);
-        GL_CHECK_LAUNCH();
-        gl_halo_exchange(h, wk.e.p, 1);
-        mass_apply(h, wk.e.p, wk.Me.p);
-        J += 0.5 * tm.weight * gl_dot(h, wk.e.p, wk.Me.p, n);
-        hipLaunchKernelGGL(k_add_component, dim3(grid_of(n)), dim3(256), 0, h->st, n, D, comp, tm.weight, wk.Me.p,
-                           wk.murhs.p);
+        mass_apply(h, hd.p, Mhd.p);
+        hipLaunchKernelGGL(k_misfit_second, dim3(grid_of(n)), dim3(256), 0, h->st, n, tm.kind, tm.level, tm.smooth,
+                           tm.weight, c, dc_of(step, p), wk.Me.p, Mhd.p, dg.p + (size_t)p * nn);
         GL_CHECK_LAUNCH();
       }
-    }
+    });
     if (status != GLIMS_OK) break;
-    image_terms_of_step(h, step, c, wk.g.p, &J, P, dc_of(step, 0), nn, dg.p);
+    image_terms_of_step(h, step, c, wk.g.p, &sw.J, P, dc_of(step, 0), nn, dg.p);
     if (have_u) {
-      int64_t its = 0;
-      status = solve_elastic(h, wk, wk.murhs.p, wk.mu.p, nullptr, 1e-12, &its);
-      if (status != GLIMS_OK) break;
-      gl_halo_exchange(h, wk.mu.p, D);
-      sens_pass<D>(h, 1, c, wk.mu.p, wk);
-      hipLaunchKernelGGL(k_gt_rows, dim3(grid_of(n)), dim3(256), 0, h->st, n, h->pat.cslice_ptr.p, h->pat.celem.p,
-                         wk.qcell.p, wk.g.p);
-      GL_CHECK_LAUNCH();
+      if (!sw.coupling_adjoint(c)) break;
       // per direction: du = K_el^-1 (G dc + sum_t dgamma_t G_t c), dmu = K_el^-1 sum w M_vec du (0 on the constrained dofs);
       // dg += G^T dmu + sum_t dgamma_t G_t^T mu;  H_gamma_t += dmu^T G_t c + mu^T G_t dc
+      // (mode 1 of the sensitivity pass into the direction's own qcell, partials and sums; every cell counted)
+      auto gt_pass = [&](const double* mat, const double* x, const double* v, double* sums) {
+        sens_pass<D>(h, 1, mat, x, v, nullptr, hqcell.p, hpart.p, sums, 3, 2);
+      };
       for (int p = 0; p < P && status == GLIMS_OK; ++p) {
         double* dgp = dg.p + (size_t)p * nn;
         double* hs = hsums.p + (size_t)p * LM * 3;
+        int64_t its = 0;
         hipLaunchKernelGGL(k_gdir_rows<D>, dim3(grid_of(n)), dim3(256), 0, h->st, n, pt.cslice_ptr.p, pt.cslots.p,
                            pt.celem.p, pt.diag_k.p, a.cell_nodes.p, h->egeo.p, h->label.p, h->mat.p,
                            d_dir.p + (p * 3 + 2) * LM, c, dc_of(step, p), urhs.p);
@@ -1435,66 +1431,28 @@ int hessian_t(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, const
         status = solve_elastic(h, wk, dmurhs.p, dmu.p, nullptr, 1e-12, &its);
         if (status != GLIMS_OK) break;
         extra_mech += 2;
-        gt_pass<D>(h, h->mat.p, c, dmu.p, hqcell.p, hpart.p, hs);
+        gt_pass(h->mat.p, c, dmu.p, hs);
         hipLaunchKernelGGL(k_gt_rows, dim3(grid_of(n)), dim3(256), 0, h->st, n, pt.cslice_ptr.p, pt.celem.p, hqcell.p, dgp);
         GL_CHECK_LAUNCH();
-        gt_pass<D>(h, h->mat.p, dc_of(step, p), wk.mu.p, hqcell.p, hpart.p, hs);
-        gt_pass<D>(h, d_dmat.p + (size_t)p * 5 * LM, c, wk.mu.p, hqcell.p, hpart.p, nullptr);
+        gt_pass(h->mat.p, dc_of(step, p), wk.mu.p, hs);
+        gt_pass(d_dmat.p + (size_t)p * 5 * LM, c, wk.mu.p, nullptr);
         hipLaunchKernelGGL(k_gt_rows, dim3(grid_of(n)), dim3(256), 0, h->st, n, pt.cslice_ptr.p, pt.celem.p, hqcell.p, dgp);
         GL_CHECK_LAUNCH();
       }
       if (status != GLIMS_OK) break;
     }
     if (step == 0) {
-      if (dc0) {
-        if (N > 0) gl_launch_spmv(h, h->st, h->pat.n_slices, nullptr, h->vM.p, wk.lam_next.p, wk.rhs.p, nullptr, wk.g.p,
-                                  nullptr, nullptr, 0, nullptr);
-        else GL_HIP(hipMemcpyAsync(wk.rhs.p, wk.g.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, h->st));
-        hipLaunchKernelGGL(k_perm, dim3(grid_of(nn)), dim3(256), 0, h->st, nn, 1, h->d_old2new.p, wk.rhs.p, wk.stage.p, 0);
-        GL_CHECK_LAUNCH();
-        GL_HIP(hipMemcpyAsync(dc0, wk.stage.p, (size_t)nn * sizeof(double), hipMemcpyDeviceToHost, h->st));
-        GL_HIP(hipStreamSynchronize(h->st));
-      }
+      if (dc0) sw.c0_output(dc0);
       for (int p = 0; hv_c0 && p < P; ++p) {   // (H dm)_c0 = M nu_1 + dg_0
         double* y = hrhs.p + (size_t)p * nn;
         if (N > 0) gl_launch_spmv(h, h->st, pt.n_slices, nullptr, h->vM.p, nu_next.p + (size_t)p * nn, y, nullptr,
                                   dg.p + (size_t)p * nn, nullptr, nullptr, 0, nullptr);
         else GL_HIP(hipMemcpyAsync(y, dg.p + (size_t)p * nn, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, h->st));
-        hipLaunchKernelGGL(k_perm, dim3(grid_of(nn)), dim3(256), 0, h->st, nn, 1, h->d_old2new.p, y, wk.stage.p, 0);
-        GL_CHECK_LAUNCH();
-        GL_HIP(hipMemcpyAsync(hv_c0 + (size_t)p * nn, wk.stage.p, (size_t)nn * sizeof(double), hipMemcpyDeviceToHost,
-                              h->st));
-        GL_HIP(hipStreamSynchronize(h->st));
+        download_permuted(h, wk, y, hv_c0 + (size_t)p * nn);
       }
       break;
     }
-    gl_launch_spmv(h, h->st, h->pat.n_slices, nullptr, h->vM.p, wk.lam_next.p, wk.rhs.p, fxc, wk.g.p, nullptr, nullptr, 0,
-                   nullptr);
-    if (fxc) hipLaunchKernelGGL(k_zero_fixed, dim3(grid_of(n)), dim3(256), 0, h->st, n, fxc, wk.rhs.p, (const double*)nullptr);
-    GL_CHECK_LAUNCH();
-    GL_HIP(hipMemsetAsync(wk.tmp.p, 0, (size_t)nn * sizeof(double), h->st));
-    gl_rd_assemble(h, c, wk.tmp.p, nullptr, wk.w.p, nullptr, h->partials.p);
-    GL_HIP(hipMemcpyAsync(wk.lam.p, wk.lam_next.p, (size_t)nn * sizeof(double), hipMemcpyDeviceToDevice, h->st));
-    gl_launch_spmv(h, h->st, h->pat.n_slices, nullptr, h->vA.p, wk.lam.p, wk.w.p, fxc, nullptr, nullptr, nullptr, 0, nullptr);
-    hipLaunchKernelGGL(k_residual, dim3(grid_of(n)), dim3(256), 0, h->st, n, wk.rhs.p, wk.w.p, fxc, wk.r.p);
-    GL_CHECK_LAUNCH();
-    const double nb = std::sqrt(gl_dot(h, wk.rhs.p, wk.rhs.p, n));
-    if (!std::isfinite(nb)) {
-      status = GLIMS_NAN;
-      break;
-    }
-    if (nb > 0.0) {
-      int64_t its = 0;
-      double res = 0.0;
-      status = gl_pcg(h, wk.lam.p, wk.r.p, wk.u.p, wk.w.p, wk.p.p, wk.s.p, h->dinv.p, h->vA.p, fxc, 1,
-                      rd_mg ? &h->mg_rd : nullptr, rd_deg, 1e-12 * nb, std::max(h->opt.cg_maxit, 20000), &its, &res);
-      a.pcg_its += its;
-      if (status != GLIMS_OK) break;
-      gl_halo_exchange(h, wk.lam.p, 1);
-      sens_pass<D>(h, 0, c, wk.lam.p, wk);
-    } else {
-      GL_HIP(hipMemsetAsync(wk.lam.p, 0, (size_t)nn * sizeof(double), h->st));
-    }
+    if (!sw.lambda_solve(c)) break;
     // nu_n: A(c_n) nu_n = M nu_{n+1} + dg_n - 2 dt sum_t rho_t int_t dc_n lam_n phi - dt sum_t dD_t K_t lam_n
     //                     - dt sum_t drho_t int_t (2 c_n - 1) lam_n phi,   PCG from nu_{n+1}
     for (int p = 0; p < P; ++p)
@@ -1504,38 +1462,32 @@ int hessian_t(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, const
                        pt.celem.p, pt.diag_k.p, a.cell_nodes.p, h->egeo.p, h->label.p, h->mat.p, d_dir.p, dt, c,
                        wk.lam.p, dc_of(step, 0), hrhs.p);
     GL_CHECK_LAUNCH();
-    const int nbk = (int)std::min<int64_t>(GL_ADJ_BLOCKS, grid_of(h->n_cells));
     for (int p = 0; p < P; ++p)
       if (fxc)
         hipLaunchKernelGGL(k_zero_fixed, dim3(grid_of(n)), dim3(256), 0, h->st, n, fxc, hrhs.p + (size_t)p * nn,
                            (const double*)nullptr);
     GL_HIP(hipMemcpyAsync(nu.p, nu_next.p, (size_t)P * nn * sizeof(double), hipMemcpyDeviceToDevice, h->st));
-    status = rd_solve_cols(h, wk, mp, fxc, rd_mg, rd_deg, P, hrhs.p, nu.p, nn, &soa_its);
+    status = rd_solve_cols(h, wk, mp, fxc, sw.rd_mg, sw.rd_deg, P, hrhs.p, nu.p, nn, &soa_its);
     for (int p = 0; p < P && status == GLIMS_OK; ++p) {
       double* x = nu.p + (size_t)p * nn;
       for (int l0 = 0; l0 < L; l0 += GL_ADJ_LT) {   // (H dm)_{D,rho} sums of step n
-        hipLaunchKernelGGL(k_hsens<D>, dim3(nbk), dim3(256), 0, h->st, h->n_cells, l0, a.cell_nodes.p, h->egeo.p, h->label.p,
-                           c, wk.lam.p, dc_of(step, p), x, hpart.p);
+        hipLaunchKernelGGL(k_hsens<D>, dim3(sens_blocks(h)), dim3(256), 0, h->st, h->n_cells, l0, a.cell_nodes.p, h->egeo.p,
+                           h->label.p, c, wk.lam.p, dc_of(step, p), x, hpart.p);
         GL_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_sens_final, dim3(1), dim3(1024), 0, h->st, nbk, l0, L, 3, 0, hpart.p,
+        hipLaunchKernelGGL(k_sens_final, dim3(1), dim3(1024), 0, h->st, sens_blocks(h), l0, L, 3, 0, hpart.p,
                            hsums.p + (size_t)p * LM * 3);
         GL_CHECK_LAUNCH();
       }
     }
     std::swap(nu.p, nu_next.p);
-    std::swap(wk.lam.p, wk.lam_next.p);
-    a.steps++;
+    sw.end_step();
   }
   const size_t L3 = (size_t)L * 3;
   std::vector<double> sums(L3), hs((size_t)P * LM * 3);
   GL_HIP(hipMemcpyAsync(sums.data(), wk.sums.p, L3 * sizeof(double), hipMemcpyDeviceToHost, h->st));
   GL_HIP(hipMemcpyAsync(hs.data(), hsums.p, hs.size() * sizeof(double), hipMemcpyDeviceToHost, h->st));
   GL_HIP(hipStreamSynchronize(h->st));
-  for (int l = 0; l < L; ++l) {
-    if (dD) dD[l] = -dt * sums[l * 3 + 0];
-    if (drho) drho[l] = -dt * sums[l * 3 + 1];
-    if (dgamma) dgamma[l] = sums[l * 3 + 2];
-  }
+  sw.write_labels(sums.data(), dD, drho, dgamma);
   for (int p = 0; p < P; ++p)
     for (int l = 0; l < L; ++l) {
       const double* q = hs.data() + ((size_t)p * LM + l) * 3;
@@ -1543,7 +1495,7 @@ int hessian_t(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, const
       if (hv_rho) hv_rho[(size_t)p * L + l] = -dt * q[1];
       if (hv_gamma) hv_gamma[(size_t)p * L + l] = q[2];
     }
-  *J_out = J;
+  *J_out = sw.J;
   if (stats) {
     stats[0] = (double)tlm_its;
     stats[1] = (double)soa_its;
@@ -1581,17 +1533,16 @@ void gl_adjoint_after_step(glims_ctx* h, int status) {
     return;
   }
   if (!a.valid) return;   // invalidated while recording: stays so until the next glims_adjoint_record / glims_set_state
-  auto* d = new dvec<double>();
+  auto d = std::make_unique<dvec<double>>();
   try {
     d->alloc((size_t)h->n_nodes);
   } catch (const glims_error& e) {
-    delete d;
     a.invalidate("device memory exhausted while recording the trajectory");
     throw glims_error(GLIMS_E_HIP, std::string("adjoint trajectory: step ") + std::to_string(a.traj.size()) +
                                        " does not fit in device memory (" + e.what() + "); the trajectory is dropped");
   }
   GL_HIP(hipMemcpyAsync(d->p, h->c.p, (size_t)h->n_nodes * sizeof(double), hipMemcpyDeviceToDevice, h->st));
-  a.traj.push_back(d);
+  a.traj.push_back(std::move(d));
 }
 
 namespace {

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 #include <stdint.h>
+#include <algorithm>
+#include <memory>
 #include <string>
 #include <vector>
 #include <stdexcept>
@@ -88,6 +90,9 @@ struct dvec {
   }
   void upload(const std::vector<T>& h, hipStream_t s) { upload(h.data(), h.size(), s); }
 };
+
+// blocks of bs threads that cover n items (at least one)
+inline unsigned grid_of(int64_t n, int bs = 256) { return (unsigned)std::max<int64_t>(1, (n + bs - 1) / bs); }
 
 // Host-side result of the symbolic phase (setup_host.cpp).
 struct HostPattern {
@@ -436,24 +441,20 @@ struct AdjointState {
   bool recording = false;                  // gl_step appends c_n after every converged step
   bool valid = false;                      // traj[0..] is a trajectory of the current operators
   std::string why;                         // why it is not (message of GLIMS_E_USAGE)
-  std::vector<dvec<double>*> traj;         // c_0, c_1, ... (internal numbering), owned
+  std::vector<std::unique_ptr<dvec<double>>> traj;   // c_0, c_1, ... (internal numbering)
   bool had_fixed = false;                  // the concentration's Dirichlet node set when recording started
   std::vector<uint8_t> fixed0;
   dvec<int32_t> cell_nodes;                // [n_cells][nv]: internal node of every cell vertex (built by the first gradient)
   dvec<uint8_t> counted;                   // partitioned handles: [n_cells] 1 = this rank adds the cell to the per-label sums
   int64_t gradients = 0, steps = 0, pcg_its = 0, mech_solves = 0, mech_its = 0;   // glims_adjoint_stats
   double ms_backward = 0.0;
-  void clear() {
-    for (auto* d : traj) delete d;
-    traj.clear();
-  }
+  void clear() { traj.clear(); }
   void invalidate(const char* m) {
     if (!recording && traj.empty()) return;
     clear();
     valid = false;
     why = m;
   }
-  ~AdjointState() { clear(); }
 };
 
 struct GlSampler;   // sample.hip

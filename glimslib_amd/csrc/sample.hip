@@ -45,7 +45,6 @@ struct GlSampler {
 
 namespace {
 
-inline unsigned grid_of(int64_t n, int bs = 256) { return (unsigned)std::max<int64_t>(1, (n + bs - 1) / bs); }
 #define GL_CHECK_LAUNCH() GL_HIP(hipGetLastError())
 
 struct GridSpec {
