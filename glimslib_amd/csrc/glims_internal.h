@@ -606,6 +606,17 @@ struct glims_ctx {
   bool have_c_old = false;                                    // c_old holds the state at the start of the previous step
   bool pending = false;                                      // cg_r / b / vA already hold the first assembly of the next step
   double pending_r0 = 0.0;
+  // Fused guess pass (gl_step): the first pass of a dot-free solve that the sweep before it has run (guess in cg_u, y_1 in cg_p)
+  struct FusedGuess {
+    bool valid = false;
+    int kind = 0;               // 1: from the guess, 2: from zero
+    double ia = 0.0, ib = 0.0;  // the interval whose theta the sweep used
+    int second_order = 0;       // how the guess was extrapolated
+  };
+  FusedGuess fg1;                                             // ... of the next step's first solve: valid only next to `pending`
+  double fg2_red = 0.0;                                       // reduction the last second dot-free solve was asked for (0: none yet)
+  dvec<double> fg_part, fg_part2, fg_red;                     // its sums of |b - A u|^2 per slice and their reduction
+  dvec<double> ws_c_old_next, ws_du_next;                     // what k_ws_delta would have committed (exchanged with c_old / ws_du)
   dvec<double> U, mload, m_rhs, m_p, m_s, m_u, m_w, m_r, m_dinv, m_uD;   // mechanics, [n_nodes*dim]
   dvec<uint8_t> fixed_c, fixed_u;
   bool have_fixed_c = false, have_fixed_u = false, have_load_rd = false, have_mload = false;
@@ -675,8 +686,17 @@ void gl_rd_quad(glims_ctx* h, const float* ad /*[n_nodes][2] = (a, delta)*/, dou
                 int part = 0 /*GL_PART_ALL*/);
 int gl_spmv_grid(int n_launch);
 enum { GL_PART_ALL = 0, GL_PART_INTERIOR = 1, GL_PART_BOUNDARY = 2 };   // slices without / with ghost columns
+// The first pass of the dot-free solve that follows a sweep, folded into the sweep (kernels.hip, k_rd_assemble_sg)
+struct GlFusedSweep {
+  int kind = 0;               // 1: from the guess u (y1 = u + c2 Dinv (res - A u), part = sums of |res - A u|^2 per slice); 2: from zero
+  const double* u = nullptr;
+  double* y1 = nullptr;
+  double* part = nullptr;     // [gl_rd_grid]
+  double c2 = 0.0;            // 1 / theta of the solve's interval
+};
+bool gl_rd_fusable(glims_ctx* h);   // every slice class has a straight-line sweep kernel, fp64 Jacobian
 void gl_rd_assemble(glims_ctx* h, const double* c, const double* b, const double* b2, double* r_out, double* r2_out,
-                    double* partials /*[gl_rd_grid][2]*/, int part = GL_PART_ALL);
+                    double* partials /*[gl_rd_grid][2]*/, int part = GL_PART_ALL, const GlFusedSweep* fused = nullptr);
 void gl_spmv_scalar(glims_ctx* h, const double* vals, const double* x, double* y, bool masked);
 void gl_apply_G(glims_ctx* h, const double* c, double* y);
 void gl_rd_matfree(glims_ctx* h, const double* c, const double* x, double* y);

@@ -607,15 +607,35 @@ __global__ __launch_bounds__(GL_WAVE) void k_rd_quad_s(
 // diagonal accumulator lives in a register, the off-diagonal ones are bumped with ds_add_f64 (one LDS instruction per
 // contribution, no read - add - write round trip): a record costs 3 LDS reads + 3 LDS adds (NV = 4) instead of 8 + 4.
 // Every term is added to its accumulator in the same order as in k_rd_assemble.
-template <int NV, int CAP, int RB, int CIDX, class AT>
-__global__ __launch_bounds__(GL_WAVE) void k_rd_assemble_s(
-    const SliceDesc* __restrict__ desc, int64_t n_own, const int32_t* __restrict__ cols,
+//
+// FG (fused guess pass, AT = double only): the sweep's lanes hold the row of A they have just formed, the new right-hand side and
+// the diagonal -- everything pass 1 of the dot-free solve that follows (k_cheb with shift = 1, k = 1) would stream again.  FG = 1
+// also gathers the solve's guess u through the row's columns and emits what that pass would: t = res - A u (its square summed
+// per slice into fg_part), y_1 = u + (c2 / A_ii) t.  FG = 2: the solve starts from zero, y_1 = (c2 / A_ii) res (k_cheb_start).
+// `res` is the right-hand side of the solve that follows: r2_out's value in a sweep with b2, r_out's otherwise.  Bit for bit
+// what those kernels write: one fused multiply-add per slot in slot order from 0 (spmv_row; slots beyond the row's own length
+// add 0 x 0 there), the product c2 Dinv t rounded before it is added to u.
+struct FgArgs {
+  const double* u;      // the guess (FG = 1), all local nodes
+  double* y1;           // the first iterate, owned rows
+  double* part;         // [slices] sums of t^2 (FG = 1)
+  const uint8_t* rlen;  // the rows' own lengths (FG = 1)
+  double c2;            // 1 / theta
+};
+__device__ __forceinline__ double fg_first_iterate(double u, double p, double t) {
+#pragma clang fp contract(off)
+  const double dn = p * t + 0.0;   // (k_cheb: the c1 term, zero in pass 1, plus the rounded product)
+  return u + dn;
+}
+template <int NV, int CAP, int RB, int CIDX, class AT, int FG>
+__device__ __forceinline__ void rd_assemble_s_slice(
+    double* lds, const SliceDesc* __restrict__ desc, int64_t n_own, const int32_t* __restrict__ cols,
     const uint16_t* __restrict__ cols16, const int32_t* __restrict__ win_base, const uint32_t* __restrict__ cs2,
     const double* __restrict__ cw, const uint8_t* __restrict__ diag_k, const double* __restrict__ vS,
     AT* __restrict__ vA, const double* __restrict__ c, const double* __restrict__ b, const double* __restrict__ b2,
     double* __restrict__ r_out, double* __restrict__ r2_out, double* __restrict__ dinv,
-    const uint8_t* __restrict__ fixed, double two_dt, double* __restrict__ partials, int ldscap, int remap) {
-  extern __shared__ double lds[];
+    const uint8_t* __restrict__ fixed, double two_dt, double* __restrict__ partials, int ldscap, int remap,
+    const FgArgs& fg) {
   double* acc = lds;                             // [ldscap][64], ldscap <= CAP = the longest slice of the launch
   double* cn = lds + (size_t)ldscap * GL_WAVE;   // [ldscap][64]
   const int lane = threadIdx.x;
@@ -666,6 +686,12 @@ __global__ __launch_bounds__(GL_WAVE) void k_rd_assemble_s(
         acc[k * GL_WAVE + lane] = 0.0;
       }
   }
+  if constexpr (FG == 1) {
+    // (the columns stay live for the gather of the guess in phase 3 -- as the 32-bit indices, not as the 64-bit offsets the
+    //  gather above has formed from them: 16 registers instead of 32 across the records)
+#pragma unroll
+    for (int k = 0; k < CAP; ++k) asm volatile("" : "+v"(cu[k]));
+  }
   // ---- the row's entries of S: requested now, needed after the records
   double S8[CAP];
 #pragma unroll
@@ -700,28 +726,55 @@ __global__ __launch_bounds__(GL_WAVE) void k_rd_assemble_s(
       if (qq + j < clen) corner(wb_[j], sb_[j]);   // (wave-uniform; a padding record of a shorter row has weight 0 and slots 0)
   }
   // phase 3: A = S + 2 dt N(c), residual 1/2 (A + S) c, diagonal
-  double r = 0.0, dg = 1.0;
+  // (FG = 1: the guess through the columns the row still holds -- the incidence records' registers are free by now)
+  constexpr int GB = 16;   // gathers in flight
+  double ug[FG == 1 ? GB : 1];
+  int rl = 0;
+  if constexpr (FG == 1) rl = (int)fg.rlen[row];
+  double r = 0.0, dg = 1.0, au = 0.0, un = 0.0;
 #pragma unroll
-  for (int k = 0; k < CAP; ++k)
+  for (int k = 0; k < CAP; ++k) {
+    if constexpr (FG == 1) {
+      if (k % GB == 0) {
+#pragma unroll
+        for (int j = 0; j < GB; ++j)
+          if (k + j < CAP) ug[j] = fg.u[cu[k + j]];
+      }
+    }
     if (k < len) {
       const double a_k = (k == dk) ? acc_d : acc[k * GL_WAVE + lane];
       const double Av = S8[k] + two_dt * a_k;
       GL_STREAM(vA, d.base, k) = (AT)Av;
       r += 0.5 * (Av + S8[k]) * cn[k * GL_WAVE + lane];
       if (k == dk) dg = Av;
+      if constexpr (FG == 1) {
+        au = __builtin_fma(k < rl ? Av : 0.0, k < rl ? ug[k % GB] : 0.0, au);
+        if (k == dk) un = ug[k % GB];
+      }
     }
-  double rr = 0.0, rr2 = 0.0;
+  }
+  double rr = 0.0, rr2 = 0.0, tt = 0.0;
   asm volatile("" : "+v"(fxv));
   if (own) {
     const bool fx = fxv != 0;
     const double res = fx ? 0.0 : b_row - r;
     r_out[row] = res;
-    dinv[row] = fx ? 1.0 : 1.0 / dg;
+    const double di = fx ? 1.0 : 1.0 / dg;
+    dinv[row] = di;
     rr = res * res;
+    double rs = res;
     if (b2) {
       const double res2 = fx ? 0.0 : b2_row - r;
       r2_out[row] = res2;
       rr2 = res2 * res2;
+      rs = res2;
+    }
+    if constexpr (FG == 1) {
+      const double t = rs - (fx ? 0.0 : au);
+      tt = t * t;
+      fg.y1[row] = fg_first_iterate(un, fg.c2 * di, t);
+    } else if constexpr (FG == 2) {
+      fg.y1[row] = fg.c2 * di * rs;
     }
   }
   rr = wave_sum(rr);
@@ -730,8 +783,38 @@ __global__ __launch_bounds__(GL_WAVE) void k_rd_assemble_s(
     partials[(size_t)s * 2 + 0] = rr;
     partials[(size_t)s * 2 + 1] = rr2;
   }
+  if constexpr (FG == 1) {
+    tt = wave_sum(tt);
+    if (lane == 0) fg.part[s] = tt;
+  }
 }
 #undef GL_STREAM
+template <int NV, int CAP, int RB, int CIDX, class AT>
+__global__ __launch_bounds__(GL_WAVE) void k_rd_assemble_s(
+    const SliceDesc* __restrict__ desc, int64_t n_own, const int32_t* __restrict__ cols,
+    const uint16_t* __restrict__ cols16, const int32_t* __restrict__ win_base, const uint32_t* __restrict__ cs2,
+    const double* __restrict__ cw, const uint8_t* __restrict__ diag_k, const double* __restrict__ vS,
+    AT* __restrict__ vA, const double* __restrict__ c, const double* __restrict__ b, const double* __restrict__ b2,
+    double* __restrict__ r_out, double* __restrict__ r2_out, double* __restrict__ dinv,
+    const uint8_t* __restrict__ fixed, double two_dt, double* __restrict__ partials, int ldscap, int remap) {
+  extern __shared__ double lds[];
+  rd_assemble_s_slice<NV, CAP, RB, CIDX, AT, 0>(lds, desc, n_own, cols, cols16, win_base, cs2, cw, diag_k, vS, vA, c, b, b2,
+                                                r_out, r2_out, dinv, fixed, two_dt, partials, ldscap, remap, FgArgs{});
+}
+// ... and with the first pass of the dot-free solve that follows folded in (FG = 1, 2: see above)
+template <int NV, int CAP, int RB, int CIDX, int FG>
+__global__ __launch_bounds__(GL_WAVE) void k_rd_assemble_sg(
+    const SliceDesc* __restrict__ desc, int64_t n_own, const int32_t* __restrict__ cols,
+    const uint16_t* __restrict__ cols16, const int32_t* __restrict__ win_base, const uint32_t* __restrict__ cs2,
+    const double* __restrict__ cw, const uint8_t* __restrict__ diag_k, const double* __restrict__ vS,
+    double* __restrict__ vA, const double* __restrict__ c, const double* __restrict__ b, const double* __restrict__ b2,
+    double* __restrict__ r_out, double* __restrict__ r2_out, double* __restrict__ dinv,
+    const uint8_t* __restrict__ fixed, double two_dt, double* __restrict__ partials, int ldscap, int remap,
+    const FgArgs fg) {
+  extern __shared__ double lds[];
+  rd_assemble_s_slice<NV, CAP, RB, CIDX, double, FG>(lds, desc, n_own, cols, cols16, win_base, cs2, cw, diag_k, vS, vA, c, b,
+                                                     b2, r_out, r2_out, dinv, fixed, two_dt, partials, ldscap, remap, fg);
+}
 
 __global__ void k_make_desc(int n, const int32_t* __restrict__ list, const int64_t* __restrict__ slice_ptr,
                             const int64_t* __restrict__ cslice_ptr, const uint8_t* __restrict__ win_ok,
@@ -1534,11 +1617,64 @@ static ClassLaunch class_launch(const SliceClass& sc, int part) {
 // (k_rd_assemble_s), longer ones the looped one with 24 incidence records in flight per lane; one slice per block dealt to
 // the XCDs in chunks; cached (not non-temporal) streams.  AT: the Newton Jacobian is written in fp64 or
 // (GLIMS_FLAG_FP32_JACOBIAN) fp32.
+// fused (kind 1 / 2): the sweep also emits the first pass of the dot-free solve that follows (k_rd_assemble_sg); only where
+// gl_rd_fusable says so.
+bool gl_rd_fusable(glims_ctx* h) {
+  ensure_classes(h);
+  if (h->jac32) return false;
+  for (const SliceClass* sc : h->pat.classes)
+    if (sc->cap > 32) return false;   // (a class of the looped kernel: today's launches throughout)
+  return true;
+}
 void gl_rd_assemble(glims_ctx* h, const double* c, const double* b, const double* b2, double* r_out, double* r2_out,
-                    double* partials, int part) {
+                    double* partials, int part, const GlFusedSweep* fused) {
   ensure_classes(h);
   const DevPattern& p = h->pat;
   const uint8_t* fx = h->have_fixed_c ? h->fixed_c.p : nullptr;
+  if (fused && fused->kind != 0) {
+    GL_REQUIRE(gl_rd_fusable(h) && part == GL_PART_ALL && (fused->kind == 1 || fused->kind == 2),
+               "fused guess pass requested where the sweep has no kernel for it");
+    FgArgs fg;
+    fg.u = fused->u;
+    fg.y1 = fused->y1;
+    fg.part = fused->part;
+    fg.rlen = p.rlen.p;
+    fg.c2 = fused->c2;
+#define GL_RDG4(NV, CAP, RB, CIDX, FG)                                                                              \
+  do {                                                                                                             \
+    set_lds(k_rd_assemble_sg<NV, CAP, RB, CIDX, FG>, lds);                                                         \
+    hipLaunchKernelGGL((k_rd_assemble_sg<NV, CAP, RB, CIDX, FG>), dim3(cl.grid), dim3(GL_WAVE), lds, h->st, cl.desc, \
+                       h->n_own, p.cols.p, p.cols16.p, p.win_base.p, p.cs2.p, p.cw.p, p.diag_k.p, h->vS.p, h->vA.p,  \
+                       c, b, b2, r_out, r2_out, h->dinv.p, fx, 2.0 * h->opt.dt, partials, cap, GL_XCD_CHUNK, fg);   \
+  } while (0)
+#define GL_RDG3(NV, CIDX, FG)                                                                                       \
+  do {                                                                                                             \
+    if (cap <= 16) GL_RDG4(NV, 16, 26, CIDX, FG);                                                                  \
+    else if (cap <= 20) GL_RDG4(NV, 20, 24, CIDX, FG);                                                             \
+    else if (cap <= 24) GL_RDG4(NV, 24, 24, CIDX, FG);                                                             \
+    else GL_RDG4(NV, 32, 24, CIDX, FG);                                                                            \
+  } while (0)
+#define GL_RDG2(NV, CIDX)                                                                                           \
+  do {                                                                                                             \
+    if (fused->kind == 1) GL_RDG3(NV, CIDX, 1); else GL_RDG3(NV, CIDX, 2);                                          \
+  } while (0)
+    for (const SliceClass* sc : p.classes) {
+      const ClassLaunch cl = class_launch(*sc, part);
+      if (cl.grid <= 0) continue;
+      const int cap = sc->cap;
+      const size_t lds = (size_t)2 * cap * GL_WAVE * sizeof(double);
+      if (h->nv == 3) {
+        if (h->use_idx16) GL_RDG2(3, 1); else GL_RDG2(3, 0);
+      } else {
+        if (h->use_idx16) GL_RDG2(4, 1); else GL_RDG2(4, 0);
+      }
+    }
+#undef GL_RDG2
+#undef GL_RDG3
+#undef GL_RDG4
+    GL_HIP(hipGetLastError());
+    return;
+  }
 #define GL_RD(NV, CIDX, AT, APTR)                                                                                   \
   do {                                                                                                             \
     set_lds(k_rd_assemble<NV, 0, 24, CIDX, AT>, lds);                                                              \

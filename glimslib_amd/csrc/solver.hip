@@ -506,6 +506,28 @@ __global__ void k_d2_guess(int64_t n, const double* __restrict__ d, double* __re
   u[i] = second_order ? 2.0 * a - d_prev[i] : a;
   d_prev[i] = a;
 }
+// The same two guesses for a sweep that folds the solve's first pass in (gl_step, fused guess pass): nothing of the extrapolation's
+// state is touched -- what k_ws_delta would commit goes to spare buffers that change places with c_old / du when the guess is
+// used; k_d2_guess's d_prev = d becomes a swap of the two buffers (the solve rewrites its correction anyway).  Same expressions.
+__global__ void k_ws_delta_spec(int64_t n, const double* __restrict__ c, const double* __restrict__ c_old, double* __restrict__ u,
+                                const double* __restrict__ du, double* __restrict__ c_old_next, double* __restrict__ du_next,
+                                int second_order) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double ci = c[i];
+  const double d1 = ci - c_old[i];
+  const double ui = second_order ? 2.0 * d1 - du[i] : d1;
+  u[i] = ui;
+  du_next[i] = d1;
+  c_old_next[i] = ci;
+}
+__global__ void k_d2_guess_spec(int64_t n, const double* __restrict__ d, const double* __restrict__ d_prev, double* __restrict__ u,
+                                int second_order) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double a = d[i];
+  u[i] = second_order ? 2.0 * a - d_prev[i] : a;
+}
 // Is a guess u better than none?  Partial sums of |r - A u|^2 and |r|^2 (w = A u), grid-stride, two per block.
 __global__ __launch_bounds__(256) void k_guess_norms(int64_t n, const double* __restrict__ r, const double* __restrict__ w,
                                                       double* __restrict__ pv) {
@@ -771,6 +793,20 @@ static void reduce_partials(glims_ctx* h, int n, int nq, const int* done) {
     hipLaunchKernelGGL(k_reduce, dim3(1), dim3(1024), 0, h->st, nb1, nq, h->partials2.p, h->red.p, done, h->nm);
   } else {
     hipLaunchKernelGGL(k_reduce, dim3(1), dim3(1024), 0, h->st, n, nq, h->partials.p, h->red.p, done, h->nm);
+  }
+  GL_HIP(hipGetLastError());
+}
+
+// |res - A u|^2 of a guess pass that a sweep carried (its per-slice sums live in a buffer of their own, so the reductions
+// enqueued between the sweep and the solve leave them alone): same two stages, into fg_red[0]
+static void reduce_fused(glims_ctx* h, int n) {
+  if (n > 16384) {
+    const int per_block = 1024, nb1 = (n + per_block - 1) / per_block;
+    hipLaunchKernelGGL(k_reduce_stage1, dim3(nb1), dim3(256), 0, h->st, n, 1, per_block, h->fg_part.p, h->fg_part2.p,
+                       (const int*)nullptr);
+    hipLaunchKernelGGL(k_reduce, dim3(1), dim3(1024), 0, h->st, nb1, 1, h->fg_part2.p, h->fg_red.p, (const int*)nullptr, h->nm);
+  } else {
+    hipLaunchKernelGGL(k_reduce, dim3(1), dim3(1024), 0, h->st, n, 1, h->fg_part.p, h->fg_red.p, (const int*)nullptr, h->nm);
   }
   GL_HIP(hipGetLastError());
 }
@@ -1372,6 +1408,12 @@ static double cheb_cost_ratio(glims_ctx* h) {
 #ifndef GL_D2_ORDER
 #define GL_D2_ORDER 2                  // guess of a step's second solve: 1 = the previous step's correction, 2 = extrapolated from the last two
 #endif
+#ifndef GL_FUSE_FIRST
+#define GL_FUSE_FIRST 1                // the sweep that confirms a step carries the guess pass of the next step's first solve ...
+#endif
+#ifndef GL_FUSE_SECOND
+#define GL_FUSE_SECOND 1               // ... and the sweep after the first solve that of the second (0: builds for the A/B of either half)
+#endif
 static const double GL_D2_KAPPA_MAX = 6.0;   // ... only where the solve's interval has lmax / lmin below this
 static const int GL_CHEB_MAX = 96;    // launches of one solve at most
 static const int GL_CHEB_LONG = 48;   // solves that would need more passes than this run PCG
@@ -1387,8 +1429,11 @@ struct ChebRun {
 // v.r is left untouched unless want_res, in which case the final pass turns it into the residual b - A y.
 // warm_u: the solve starts from this guess (the predicted increment, ghosts valid; may be ylast) instead of zero; the iteration count
 // is then chosen on the device from |b - A u| (r_bound bounds the launches; hint_slot: which solve of the step), otherwise from r_norm = |b| here.
+// folded: the sweep that assembled this system has run the solve's first pass already (k_rd_assemble_sg, with this interval's
+// theta: the caller has checked that) -- y_1 is in v.p, and for a warm-started solve the sums of |b - A u|^2 are in fg_part; the
+// solve starts at pass 2 and every count stays what it would have been.
 static ChebRun cheb_solve(glims_ctx* h, const CgVecs& v, double tol_abs, double r_norm, double r_bound, bool want_res,
-                          const double* warm_u, double* ylast, int hint_slot) {
+                          const double* warm_u, double* ylast, int hint_slot, bool folded = false) {
   const DevPattern& p = h->pat;
   const bool split = h->world > 1 && h->n_peers > 0;
   const int64_t n = h->n_own;
@@ -1423,18 +1468,24 @@ static ChebRun cheb_solve(glims_ctx* h, const CgVecs& v, double tol_abs, double 
   const int shift = warm_u ? 1 : 0;
   double *d_in = v.p, *d_out = v.s;
   if (warm_u) {
-    hipEvent_t* ev = h->timing(glims_ctx::TK_CHEB) ? h->pair(glims_ctx::TK_CHEB) : nullptr;
-    // (one launch over all slices: the ghosts of u are current, nothing to exchange; the payload of d_1 is packed for pass 2)
-    gl_launch_cheb(h, h->st, p.n_slices, nullptr, v.vals, v.vals32, warm_u, v.p, v.r, v.dinv, nullptr,
-                   ylast, v.x, v.fixed, 0.0, 1.0 / rec.theta, 1, GL_CHEB_MAX + 8, nullptr, want_res ? 1 : 0, pm,
-                   ev ? ev[0] : nullptr, ev ? ev[1] : nullptr, shift, h->partials.p);
-    reduce_partials(h, gl_spmv_grid(p.n_slices), 1, nullptr);
-    allreduce_sum(h, h->red.p, 1);
-    hipLaunchKernelGGL(k_cheb_plan, dim3(1), dim3(1), 0, h->st, (const double*)h->red.p, tol_abs * tol_abs,
+    const double* rr_dev = h->red.p;
+    if (folded) {
+      reduce_fused(h, gl_rd_grid(h));
+      rr_dev = h->fg_red.p;
+    } else {
+      hipEvent_t* ev = h->timing(glims_ctx::TK_CHEB) ? h->pair(glims_ctx::TK_CHEB) : nullptr;
+      // (one launch over all slices: the ghosts of u are current, nothing to exchange; the payload of d_1 is packed for pass 2)
+      gl_launch_cheb(h, h->st, p.n_slices, nullptr, v.vals, v.vals32, warm_u, v.p, v.r, v.dinv, nullptr,
+                     ylast, v.x, v.fixed, 0.0, 1.0 / rec.theta, 1, GL_CHEB_MAX + 8, nullptr, want_res ? 1 : 0, pm,
+                     ev ? ev[0] : nullptr, ev ? ev[1] : nullptr, shift, h->partials.p);
+      reduce_partials(h, gl_spmv_grid(p.n_slices), 1, nullptr);
+      allreduce_sum(h, h->red.p, 1);
+    }
+    hipLaunchKernelGGL(k_cheb_plan, dim3(1), dim3(1), 0, h->st, rr_dev, tol_abs * tol_abs,
                        rec.inv_acosh_sigma(), 2, std::max(2, m), 2, h->cheb_plan.p, info_dev);
     GL_HIP(hipGetLastError());
     m = std::max(2, m);
-  } else {
+  } else if (!folded) {
     // (zero guess: the first iterate y_1 = d_1 = Dinv b / theta needs no operator pass)
     hipLaunchKernelGGL(k_cheb_start, dim3(g), dim3(256), 0, h->st, n, (const double*)v.r, v.dinv, 1.0 / rec.theta, v.p,
                        pm);
@@ -1467,6 +1518,7 @@ static ChebRun cheb_solve(glims_ctx* h, const CgVecs& v, double tol_abs, double 
     std::swap(d_in, d_out);
   }
   h->stats.cheb_solves++;
+  if (folded) h->stats.cheb_fused_passes++;
   return run;
 }
 
@@ -1479,8 +1531,9 @@ static ChebRun cheb_solve(glims_ctx* h, const CgVecs& v, double tol_abs, double 
 // `krylov`: also receives {iterations, rr, done} of a deferred linear solve enqueued before the sweep.
 // `exchange_c`: the ghosts of c are stale (a linear solve has just updated the owned values): in a partitioned run
 // the interior slices -- mass SpMV for b2 and sweep -- run while the halo is in flight, the boundary slices after it.
+// `fused` (single rank): the sweep also runs the first pass of the dot-free solve that follows it (GlFusedSweep).
 static void rd_sweep(glims_ctx* h, const double* b2, double* norms /*[2]*/, Mail* krylov = nullptr,
-                     bool exchange_c = false, bool mass_for_b2 = false) {
+                     bool exchange_c = false, bool mass_for_b2 = false, const GlFusedSweep* fused = nullptr) {
   const DevPattern& p = h->pat;
   const double* load = h->have_load_rd ? h->load_rd.p : nullptr;
   const bool split = exchange_c && h->world > 1 && h->n_peers > 0;
@@ -1491,7 +1544,7 @@ static void rd_sweep(glims_ctx* h, const double* b2, double* norms /*[2]*/, Mail
                      nullptr);
     const bool timed = h->timing(glims_ctx::TK_SWEEP);
     if (timed) h->tick(glims_ctx::TK_SWEEP);
-    gl_rd_assemble(h, h->c.p, h->b.p, b2, h->cg_r.p, h->cg_r2.p, h->partials.p);
+    gl_rd_assemble(h, h->c.p, h->b.p, b2, h->cg_r.p, h->cg_r2.p, h->partials.p, GL_PART_ALL, fused);
     if (timed) h->tick(glims_ctx::TK_SWEEP);
   } else {
     halo_start(h, h->c.p, 1);
@@ -1668,6 +1721,17 @@ int gl_step(glims_ctx* h, int n_steps) {
       cb.m_hint[0] = cb.m_hint[1] = 0;
       h->cg_hist.alloc((size_t)2 * GL_CG_HIST);
     }
+    // Fused guess pass: a sweep that is followed by a dot-free solve also runs that solve's first pass (k_rd_assemble_sg) --
+    // the guess pass of the step's first solve comes with the sweep that confirmed the previous step (h->fg1, lives and dies
+    // with `pending`), the second solve's guess (or start) pass with the sweep after the first solve (fg2).  Both are
+    // speculative: the guess is formed without committing the extrapolation's state, the interval is the one the solve is
+    // expected to use, and the solve takes the pass only if what it would have done itself is exactly that.
+    const bool fuse_on = (o.flags & GLIMS_FLAG_NO_FUSED_GUESS) == 0 && h->world == 1 && cheb_allowed && !extrapolate &&
+                         !h->jac32 && gl_rd_fusable(h);
+    if (!h->pending) h->fg1.valid = false;
+    const glims_ctx::FusedGuess fg1 = h->fg1;   // (this step's; whatever happens, it is not kept)
+    h->fg1.valid = false;
+    glims_ctx::FusedGuess fg2;
     if (h->pending) {
       // the sweep that verified the previous step already assembled A(c^n) and -R(c^n; c^n) for this one
       nr = h->pending_r0;
@@ -1823,6 +1887,7 @@ int gl_step(glims_ctx* h, int n_steps) {
         }
       }
       bool warm = false, ws_fused = false;
+      bool take_folded = false;   // this solve's first pass came with the last sweep
       if (it == 0 && (o.flags & GLIMS_FLAG_WARM_START) && !extrapolate) {   // both options own the c_old buffer
         // initial guess of the first linear solve = the increment predicted from the previous steps' (k_ws_delta): same linear
         // system, same solution, the Krylov iteration just starts closer.  One SpMV with the already assembled A(c^n).
@@ -1830,8 +1895,20 @@ int gl_step(glims_ctx* h, int n_steps) {
         // (dot-free solve: the guess u becomes direction 0 of the solve -- the product A u is then the solve's first operator
         //  pass and the correction accumulates from u: cheb_solve, warm_u)
         ws_fused = use_cheb && h->have_c_old;
-        hipLaunchKernelGGL(k_ws_delta, dim3(grid_exact(h->n_nodes)), dim3(256), 0, h->st, h->n_nodes, h->c.p,
-                           h->c_old.p, h->cg_u.p, h->ws_du.p, (h->have_c_old && h->ws_depth >= 1) ? 1 : 0);
+        const int ws_order = (h->have_c_old && h->ws_depth >= 1) ? 1 : 0;
+        if (fuse_on && fg1.valid && fg1.kind == 1 && ws_fused && !midpoint && fg1.second_order == ws_order) {
+          // (the guess is in cg_u, y_1 in cg_p: taken if the solve's interval is the one the sweep assumed)
+          double ia, ib;
+          cheb_interval(h, tol_lin / std::max(nr, tol_lin), &ia, &ib);
+          take_folded = ia == fg1.ia && ib == fg1.ib;
+        }
+        if (take_folded) {   // what k_ws_delta commits, written by k_ws_delta_spec
+          std::swap(h->c_old.p, h->ws_c_old_next.p);
+          std::swap(h->ws_du.p, h->ws_du_next.p);
+        } else {
+          hipLaunchKernelGGL(k_ws_delta, dim3(grid_exact(h->n_nodes)), dim3(256), 0, h->st, h->n_nodes, h->c.p,
+                             h->c_old.p, h->cg_u.p, h->ws_du.p, ws_order);
+        }
         h->ws_depth = h->have_c_old ? 1 : 0;   // (ws_du holds a real increment from the second warm-started step on)
         if (h->have_c_old) {
           warm = true;
@@ -1859,6 +1936,16 @@ int gl_step(glims_ctx* h, int n_steps) {
         }
         h->have_c_old = true;
       }
+      if (it == 0 && fuse_on && fg1.valid && fg1.kind == 2 && use_cheb && !ws_fused && tol_lin < nr) {
+        // (a first solve from zero whose start came with the sweep)
+        double ia, ib;
+        cheb_interval(h, tol_lin / std::max(nr, tol_lin), &ia, &ib);
+        take_folded = ia == fg1.ia && ib == fg1.ib;
+      }
+      if (it == 0 && getenv("GLIMS_VERBOSE_CHEB"))
+        fprintf(stderr, "  fused guess: step %lld first solve: payload %d kind %d order %d -- use_cheb %d ws_fused %d midpoint %d "
+                "mode %d -> folded %d\n", (long long)h->stats.steps, (int)fg1.valid, fg1.kind, fg1.second_order, (int)use_cheb,
+                (int)ws_fused, (int)midpoint, nw_mode, (int)take_folded);
       CgVecs v{h->c.p, h->cg_r.p, h->cg_u.p, h->cg_w.p, h->cg_p.p, h->cg_s.p,
                h->dinv.p, h->vA.p, h->have_fixed_c ? h->fixed_c.p : nullptr, 1};
       if (h->jac32) v.vals32 = h->vA32.p;
@@ -1902,12 +1989,31 @@ int gl_step(glims_ctx* h, int n_steps) {
           narrow = ib <= GL_D2_KAPPA_MAX * ia;
         }
         const bool warm2 = GL_D2_ORDER >= 1 && second && h->have_d2 && narrow && (o.flags & GLIMS_FLAG_WARM_START) && !extrapolate;
+        const int d2_order = (h->d2_depth >= 2 && GL_D2_ORDER >= 2) ? 1 : 0;
+        if (second && fuse_on && fg2.valid && !(!warm2 && tol_lin >= nr) &&
+            (fg2.kind == 1 ? (warm2 && fg2.second_order == d2_order) : !warm2)) {
+          double ia, ib;
+          cheb_interval(h, tol_lin / std::max(nr, tol_lin), &ia, &ib);
+          take_folded = ia == fg2.ia && ib == fg2.ib;
+        }
+        if (second && getenv("GLIMS_VERBOSE_CHEB"))
+          fprintf(stderr, "  fused guess: step %lld second solve: payload %d kind %d order %d [%.17g, %.17g] -- warm2 %d have_d2 %d narrow %d order %d "
+                  "regime %d/%d r1 %.3e/%.3e idle %d -> folded %d\n", (long long)h->stats.steps, (int)fg2.valid, fg2.kind,
+                  fg2.second_order, fg2.ia, fg2.ib, (int)warm2, (int)h->have_d2, (int)narrow, d2_order, regime_now, h->d2_regime, nr,
+                  h->d2_r1, (int)(!warm2 && tol_lin >= nr), (int)take_folded);
+        fg2.valid = false;
+        if (second) h->fg2_red = tol_lin / std::max(nr, tol_lin);   // (what the next step's sweep sizes its guess pass by)
         if (warm2) {
           // (linearly extrapolated from the last two; the guess goes where the first solve's went: cg_u is free again)
           h->d2_prev.alloc((size_t)h->n_nodes);
-          hipLaunchKernelGGL(k_d2_guess, dim3(grid_exact(n)), dim3(256), 0, h->st, n, (const double*)h->cheb_delta2.p,
-                             h->d2_prev.p, h->cg_u.p, (h->d2_depth >= 2 && GL_D2_ORDER >= 2) ? 1 : 0);
-          GL_HIP(hipGetLastError());
+          if (take_folded) {
+            // (the guess is in cg_u already, k_d2_guess_spec; d_prev = d by exchanging the buffers: the solve rewrites cheb_delta2)
+            std::swap(h->cheb_delta2.p, h->d2_prev.p);
+          } else {
+            hipLaunchKernelGGL(k_d2_guess, dim3(grid_exact(n)), dim3(256), 0, h->st, n, (const double*)h->cheb_delta2.p,
+                               h->d2_prev.p, h->cg_u.p, d2_order);
+            GL_HIP(hipGetLastError());
+          }
           if (h->world > 1) gl_halo_exchange(h, h->cg_u.p, 1);   // (corrections are kept by their row owners: ghosts)
         }
         // A solve from zero whose tolerance is already met (tol_lin >= |R_k|: a cg_atol above the residual) runs no pass and
@@ -1922,7 +2028,7 @@ int gl_step(glims_ctx* h, int n_steps) {
             used_warm2 = warm2;
           }
           crun = cheb_solve(h, v, tol_lin, nr, nr, cheap_next, (ws_fused || warm2) ? h->cg_u.p : (const double*)nullptr,
-                            last_ylast, second ? 1 : 0);
+                            last_ylast, second ? 1 : 0, take_folded);
         }
         deferred = crun.planned;
         if (!deferred && !cheb_idle) {
@@ -2010,8 +2116,61 @@ int gl_step(glims_ctx* h, int n_steps) {
       if (cheap) {
         rd_quad_update(h, ck_is_c0 ? h->nq_c0.p : h->nq_ck.p, norms, deferred ? &km : nullptr);
       } else {
+        // What this sweep can carry: with b2 the guess pass of the next step's first solve (used if the sweep confirms this
+        // step), after the step's first solve the second solve's guess pass, or its start from zero.
+        GlFusedSweep fs;
+        glims_ctx::FusedGuess fgn;
+        const bool warm_on = (o.flags & GLIMS_FLAG_WARM_START) != 0;
+        if (fuse_on && use_cheb) {
+          const int ns = gl_rd_grid(h);
+          h->fg_part.alloc((size_t)ns);
+          h->fg_part2.alloc((size_t)(ns + 1023) / 1024);
+          h->fg_red.alloc(1);
+          if (speculate && GL_FUSE_FIRST) {
+            // (not into a learning step, nor where the midpoint correction changes the right-hand side after the sweep)
+            if (cb.age + 1 >= 32) {
+              // (the next step re-measures the interval with PCG solves)
+            } else if (!(warm_on && h->have_c_old)) {   // (the next step's first solve starts from zero)
+              cheb_interval(h, first_rtol, &fgn.ia, &fgn.ib);
+              fgn.kind = 2;
+            } else if (!midpoint) {
+              cheb_interval(h, first_rtol, &fgn.ia, &fgn.ib);
+              fgn.kind = 1;
+              fgn.second_order = h->ws_depth >= 1 ? 1 : 0;
+              h->ws_c_old_next.alloc((size_t)h->n_nodes);
+              h->ws_du_next.alloc((size_t)h->n_nodes);
+              hipLaunchKernelGGL(k_ws_delta_spec, dim3(grid_exact(h->n_nodes)), dim3(256), 0, h->st, h->n_nodes,
+                                 (const double*)h->c.p, (const double*)h->c_old.p, h->cg_u.p, (const double*)h->ws_du.p,
+                                 h->ws_c_old_next.p, h->ws_du_next.p, fgn.second_order);
+            }
+          } else if (!speculate && GL_FUSE_SECOND && it == 0 && h->fg2_red > 0.0) {
+            // (the reduction the previous step's second solve was asked for stands in for this step's: it decides between the
+            //  loose and the tight interval only)
+            cheb_interval(h, h->fg2_red, &fgn.ia, &fgn.ib);
+            if (GL_D2_ORDER >= 1 && warm_on && h->have_d2 && fgn.ib <= GL_D2_KAPPA_MAX * fgn.ia) {
+              fgn.kind = 1;
+              fgn.second_order = (h->d2_depth >= 2 && GL_D2_ORDER >= 2) ? 1 : 0;
+              h->d2_prev.alloc((size_t)h->n_nodes);
+              hipLaunchKernelGGL(k_d2_guess_spec, dim3(grid_exact(n)), dim3(256), 0, h->st, n, (const double*)h->cheb_delta2.p,
+                                 (const double*)h->d2_prev.p, h->cg_u.p, fgn.second_order);
+            } else {
+              fgn.kind = 2;
+            }
+          }
+          if (fgn.kind != 0) {
+            GL_HIP(hipGetLastError());
+            fs.kind = fgn.kind;
+            fs.u = h->cg_u.p;
+            fs.y1 = h->cg_p.p;
+            fs.part = h->fg_part.p;
+            fs.c2 = 1.0 / ChebRec(fgn.ia, fgn.ib).theta;
+            fgn.valid = true;
+          }
+        }
         rd_sweep(h, speculate ? h->b2.p : nullptr, norms, deferred ? &km : nullptr, /*exchange_c=*/true,
-                 /*mass_for_b2=*/speculate);
+                 /*mass_for_b2=*/speculate, fgn.valid ? &fs : nullptr);
+        if (fgn.valid && !speculate) fg2 = fgn;
+        if (fgn.valid && speculate) h->fg1 = fgn;   // (kept only if the sweep confirms the step, see below)
         base_is_current = true;   // a fresh Jacobian: A_0 = A(c) from here on
         rebase = false;
       }
@@ -2064,6 +2223,8 @@ int gl_step(glims_ctx* h, int n_steps) {
         cb.lmax0 = cb.lmin0 = 0.0;   // (the loose interval is re-learnt from scratch)
         h->stats.cheb_fallbacks++;
         h->pending = false;
+        h->fg1.valid = false;
+        fg2.valid = false;
         rd_sweep(h, nullptr, norms, nullptr, /*exchange_c=*/true);
         nr = norms[0];
         base_is_current = true;
@@ -2129,6 +2290,7 @@ int gl_step(glims_ctx* h, int n_steps) {
         h->pending_r0 = norms[1];
         break;
       }
+      h->fg1.valid = false;   // (not confirmed: the next solve belongs to this step)
     }
     ++h->nw_steps;
     h->have_d2 = d2_written && status == GLIMS_OK;

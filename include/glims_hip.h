@@ -203,6 +203,13 @@ typedef struct glims_options {
                                            step returns does not -- the Newton tolerance decides that
                                            (ignored when GLIMS_FLAG_EXTRAPOLATE_GUESS is set) */
 
+#define GLIMS_FLAG_NO_FUSED_GUESS 1024    /* OFF by default.  Default: an assembly sweep that is followed by a dot-free solve also runs
+                                           that solve's first pass -- the guess pass of a step's first and second solve, or the
+                                           start of a second solve from zero -- on the row it has just formed, instead of a
+                                           launch that streams the Jacobian again (single rank, fp64 Jacobian, rows of at most
+                                           32 entries; same bits in every result, glims_stats.cheb_fused_passes counts them).
+                                           Set: the separate launches (A/B in one build) */
+
 typedef struct glims_stats {
   int64_t steps;            /* implicit time steps taken */
   int64_t newton_its;       /* Newton linear solves (RD) */
@@ -290,6 +297,9 @@ typedef struct glims_stats {
   double  mg_box_fraction;  /* elasticity multigrid, partitioned runs: this rank's work box / the replicated first grid (1 = the
                                whole grid: not box-limited); with parts that are boxes (recursive coordinate bisection) ~ 1 / ranks
                                + the smoothers' margin */
+  /* ---- appended under ABI 6 (readers of the older layout are unaffected) */
+  int64_t cheb_fused_passes;/* first passes of dot-free solves (guess pass, or start from zero) that an assembly sweep ran and
+                               the solve took over; still counted in cheb_its and cg_its (see GLIMS_FLAG_NO_FUSED_GUESS) */
 } glims_stats;
 
 /* ---- lifetime -------------------------------------------------------------------------------------- */
