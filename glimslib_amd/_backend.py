@@ -28,6 +28,7 @@ FLAG_FULL_NEWTON = 128
 FLAG_FIXED_FORCING = 256
 FLAG_MG_NO_LUMPING = 512
 FLAG_NO_FUSED_GUESS = 1024
+FLAG_NO_FUSED_MASS = 2048
 PRECOND_BLOCK_JACOBI, PRECOND_MULTIGRID = 0, 1
 RD_PRECOND_AUTO, RD_PRECOND_JACOBI, RD_PRECOND_MULTIGRID = 0, 1, 2
 RD_LINEAR_AUTO, RD_LINEAR_PCG, RD_LINEAR_CHEBYSHEV = 0, 1, 2
@@ -82,7 +83,8 @@ class Stats(C.Structure):
                 ("cheb_fallbacks", C.c_int64), ("cheb_learn_solves", C.c_int64), ("cheb_lmin", C.c_double),
                 ("cheb_lmax", C.c_double), ("ms_cheb_steps", C.c_double), ("n_cheb_steps", C.c_int64),
                 ("us_cheb_median", C.c_double), ("stream_nontemporal", C.c_int64), ("krylov_working_set", C.c_int64),
-                ("mg_box_fraction", C.c_double), ("cheb_fused_passes", C.c_int64)]
+                ("mg_box_fraction", C.c_double), ("cheb_fused_passes", C.c_int64),
+                ("rd_mass_in_sweep", C.c_int64), ("rd_mass_fallback_rows", C.c_int64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -312,7 +314,8 @@ class Handle:
 
     # -- operator hooks --------------------------------------------------------------------------
     def apply(self, which, x, reps=1):
-        """which: 0 A(c), 1 S, 2 M, 3 K_el, 4 G.  Returns (y, ms_total)."""
+        """which: 0 A(c), 1 S, 2 M, 3 K_el, 4 G; 10 = M x + rd_load as the stepping path's sweep forms it (glims_hip.h).
+        Returns (y, ms_total)."""
         d = self.dim
         nin = self.n_nodes * (d if which == 3 else 1)
         nout = self.n_nodes * (d if which in (3, 4) else 1)

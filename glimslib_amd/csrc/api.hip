@@ -628,6 +628,7 @@ int glims_reset_stats(glims_ctx* h) {
   h->stats.cheb_lmax = keep.cheb_lmax;
   h->stats.stream_nontemporal = keep.stream_nontemporal;
   h->stats.krylov_working_set = keep.krylov_working_set;
+  h->stats.rd_mass_fallback_rows = keep.rd_mass_fallback_rows;
   h->tev_used = 0;
   h->stats.steps = keep.steps;   // step counter drives the extrapolated guess; keep it
   return GLIMS_OK;
@@ -637,7 +638,10 @@ int glims_apply(glims_ctx* h, int which, const double* x, double* y, int reps, d
   return guarded(h, [&]() {
     GL_REQUIRE(h->is_setup, "glims_apply before glims_setup");
     GL_REQUIRE(x && y && reps >= 1, "bad arguments");
-    GL_REQUIRE(which >= 0 && which <= 9 && which != 6, "unknown operator");
+    GL_REQUIRE(which >= 0 && which <= 10 && which != 6, "unknown operator");
+    if (which == 10)
+      GL_REQUIRE(gl_rd_mass_in_sweep(h), "the sweep does not form the mass product on this handle (GLIMS_FLAG_NO_FUSED_MASS, "
+                                         "several ranks, fp32 Jacobian, or rows of more than 32 entries)");
     if (which == 7) GL_REQUIRE(h->have_state, "the matrix-free product needs the state c (glims_set_state)");
     if (which >= 8) h->pending = false;   // the sweep rewrites A(c), dinv and the Krylov work vectors
     const int d = h->dim;
@@ -650,13 +654,24 @@ int glims_apply(glims_ctx* h, int which, const double* x, double* y, int reps, d
     const bool saved_mload = h->have_mload;
     h->have_mload = false;
     dvec<double> zero_b;
-    if (which == 8) zero_b.alloc_zero((size_t)h->n_nodes, h->st);
+    if (which == 8 || which == 10) zero_b.alloc_zero((size_t)h->n_nodes, h->st);
     GL_HIP(hipEventRecord(h->ev_a, h->st));
     for (int r = 0; r < reps; ++r) {
       if (which == 7)   // matrix-free A(c) x from the incidence lists (measurement only)
         gl_rd_matfree(h, h->c.p, xin.p, yout.p);
       else if (which == 8)   // the assembly sweep at c = x with b = 0: y = -1/2 (A(x) + S) x; A(x) and its diagonal are left in place
         gl_rd_assemble(h, xin.p, zero_b.p, nullptr, yout.p, h->cg_r2.p, h->partials.p);
+      else if (which == 10) {   // b = M x + load as a step's first sweep forms it: fallback slices by the SpMV, the rest by the sweep
+        const DevPattern& p = h->pat;
+        GlMassSweep ms;
+        ms.load = h->have_load_rd ? h->load_rd.p : nullptr;
+        ms.bw = h->b.p;
+        if (p.n_mass_fb > 0)
+          gl_launch_spmv(h, h->st, p.n_mass_fb, p.mass_fb_slices.p, h->vM.p, xin.p, h->b.p, nullptr, ms.load, nullptr, nullptr,
+                         0, nullptr);
+        gl_rd_assemble(h, xin.p, h->b.p, nullptr, h->cg_r.p, h->cg_r2.p, h->partials.p, GL_PART_ALL, nullptr, &ms);
+        GL_HIP(hipMemcpyAsync(yout.p, h->b.p, (size_t)h->n_own * sizeof(double), hipMemcpyDeviceToDevice, h->st));
+      }
       else if (which == 9) {   // the quadratic-term pass with a = delta = x: y -= dt N(x) x per repetition
         h->nq_ad.alloc((size_t)2 * h->n_nodes);
         gl_pair_of(h, xin.p, h->nq_ad.p);
@@ -682,7 +697,7 @@ int glims_apply(glims_ctx* h, int which, const double* x, double* y, int reps, d
     from_device_perm(h, yout.p, y, blk_out ? d : 1, h->n_own);
     // which = 8 has left A(x) and its diagonal where A(c) belongs: put A(c) back (one more sweep, outside the timed region), so
     // that every later glims_apply(0 | 5), glims_project or glims_step sees the operator of the STATE, as after any other `which`
-    if (which == 8 && h->have_state) gl_rd_assemble(h, h->c.p, zero_b.p, nullptr, xin.p, h->cg_r2.p, h->partials.p);
+    if ((which == 8 || which == 10) && h->have_state) gl_rd_assemble(h, h->c.p, zero_b.p, nullptr, xin.p, h->cg_r2.p, h->partials.p);
     return GLIMS_OK;
   });
 }

@@ -166,6 +166,11 @@ struct DevPattern {
   dvec<double> cw;                         // per-incidence reaction weight rho_T |T| d!/(d+3)!
   dvec<uint32_t> cs2;                      // slot word re-ordered for the hot kernels: byte 0 = the row's own (diagonal) slot, then the cell's other vertices
   dvec<uint32_t> cq;                       // [incidence][2] = (re-ordered slot word, weight as float bits): the quadratic-term pass's 8-byte records
+  // the mass product from the sweep's incidence loop (k_corner_weights, rd_assemble_s_slice with MB = 1)
+  dvec<double> mass_q;                     // per padded row: (d+3) / rho where every cell of the row has the same rho > 0, else 0
+  dvec<int32_t> mass_fb_slices;            // slices with an owned row of mass_q = 0: these keep the mass SpMV (fallback rows)
+  int32_t n_mass_fb = 0;                   // ... their number
+  int64_t mass_fb_rows = 0;                // owned rows with mass_q = 0
   dvec<int32_t> interior_slices, boundary_slices;
   int32_t n_interior = 0, n_boundary = 0;
   std::vector<int> bucket_cap;
@@ -694,9 +699,19 @@ struct GlFusedSweep {
   double* part = nullptr;     // [gl_rd_grid]
   double c2 = 0.0;            // 1 / theta of the solve's interval
 };
+// The mass product b = M c + load formed by the sweep itself (MB = 1): the sweep DEFINES the right-hand side it is about to
+// use -- b2 in a sweep with two right-hand sides, b otherwise -- from its incidence records, row by row where
+// DevPattern::mass_q is not 0, and writes it to `bw` (that buffer: it is the next step's b); the rows with mass_q = 0 read
+// what the mass SpMV over DevPattern::mass_fb_slices has left there.
+struct GlMassSweep {
+  const double* load = nullptr;   // added to the product (may be null)
+  double* bw = nullptr;           // the buffer behind b2 (or b)
+};
 bool gl_rd_fusable(glims_ctx* h);   // every slice class has a straight-line sweep kernel, fp64 Jacobian
+bool gl_rd_mass_in_sweep(glims_ctx* h);   // the stepping path forms M c in the sweep (single rank, gl_rd_fusable, flag not set)
 void gl_rd_assemble(glims_ctx* h, const double* c, const double* b, const double* b2, double* r_out, double* r2_out,
-                    double* partials /*[gl_rd_grid][2]*/, int part = GL_PART_ALL, const GlFusedSweep* fused = nullptr);
+                    double* partials /*[gl_rd_grid][2]*/, int part = GL_PART_ALL, const GlFusedSweep* fused = nullptr,
+                    const GlMassSweep* mass = nullptr);
 void gl_spmv_scalar(glims_ctx* h, const double* vals, const double* x, double* y, bool masked);
 void gl_apply_G(glims_ctx* h, const double* c, double* y);
 void gl_rd_matfree(glims_ctx* h, const double* c, const double* x, double* y);

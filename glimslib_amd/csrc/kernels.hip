@@ -103,6 +103,10 @@ __global__ void k_egeo(int64_t n_cells, const double* __restrict__ xyz, const in
 // cell order.  The sweep and the quadratic-term pass then need no "is this vertex the row's own" test: the own vertex's
 // contribution (the diagonal formula) goes to a register, the others (the off-diagonal formula) to their slots.  (`cslots`
 // keeps the cell's vertex order, which the static assembly needs to find the vertex's gradient.)  One wave per slice.
+// Per row: the mass factor q = (d+3) / rho of a row whose cells all carry the bitwise same finite rho > 0 -- the consistent
+// mass row is then (M c)_i = q sum_T w_T (s_T + c_i), which the sweep forms from the records it walks anyway (MB = 1) --
+// and 0 for every other row (mixed or zero rho, ghost and padding rows: these keep the mass SpMV); mass_fb[s] = the
+// slice's owned rows among the latter.
 template <int D>
 __global__ __launch_bounds__(GL_WAVE) void k_corner_weights(const int64_t* __restrict__ cslice_ptr,
                                                              const int32_t* __restrict__ celem,
@@ -110,7 +114,9 @@ __global__ __launch_bounds__(GL_WAVE) void k_corner_weights(const int64_t* __res
                                                              const double* __restrict__ evol, const double* __restrict__ mat,
                                                              const uint8_t* __restrict__ diag_k,
                                                              const uint32_t* __restrict__ cslots, double* __restrict__ cw,
-                                                             uint32_t* __restrict__ cs2, uint2* __restrict__ cq) {
+                                                             uint32_t* __restrict__ cs2, uint2* __restrict__ cq,
+                                                             int64_t n_own, double* __restrict__ mass_q,
+                                                             int32_t* __restrict__ mass_fb) {
   constexpr int NV = D + 1;
   constexpr double fact = D == 2 ? 1.0 / 60.0 : 1.0 / 120.0;
   // (neighbouring slices on ONE XCD: the four rows that share a cell then share an L2 -- with block b on XCD b % 8 each of them
@@ -119,12 +125,20 @@ __global__ __launch_bounds__(GL_WAVE) void k_corner_weights(const int64_t* __res
   const int64_t cbase = cslice_ptr[s];
   const int clen = (int)((cslice_ptr[s + 1] - cbase) >> 6);
   const uint32_t dk = diag_k[(int64_t)s * GL_WAVE + lane];
+  double rho0 = 0.0;
+  bool seen = false, uniform = true;
   for (int q = 0; q < clen; ++q) {
     const int64_t i = cbase + (int64_t)q * GL_WAVE + lane;
     const int32_t e = celem[i];
     // (|T| from the compact array: through the 104-byte geometry records this kernel fetched a whole line per incidence,
     //  41.8 GB at 10 M rows -- profiles/r04_a_pmc_c4.json)
-    const double w = e < 0 ? 0.0 : mat[1 * GL_MAX_LABELS + label[e]] * evol[e] * fact;
+    const double rho = e < 0 ? 0.0 : mat[1 * GL_MAX_LABELS + label[e]];
+    const double w = e < 0 ? 0.0 : rho * evol[e] * fact;
+    if (e >= 0) {
+      if (!seen) rho0 = rho;
+      else if (__double_as_longlong(rho) != __double_as_longlong(rho0)) uniform = false;
+      seen = true;
+    }
     const uint32_t sl = cslots[i];
     uint32_t out = dk, pos = 1;
     if (e < 0) {
@@ -145,6 +159,12 @@ __global__ __launch_bounds__(GL_WAVE) void k_corner_weights(const int64_t* __res
     // feeds is itself a 1e-3 correction)
     cq[i] = make_uint2(out, __float_as_uint((float)w));
   }
+  const int64_t row = (int64_t)s * GL_WAVE + lane;
+  const bool own = row < n_own;
+  const bool fused = own && seen && uniform && rho0 > 0.0 && isfinite(rho0) && isfinite((double)(D + 3) / rho0);
+  mass_q[row] = fused ? (double)(D + 3) / rho0 : 0.0;
+  const int n_fb = __popcll(__ballot(own && !fused));
+  if (lane == 0) mass_fb[s] = n_fb;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -622,12 +642,24 @@ struct FgArgs {
   const uint8_t* rlen;  // the rows' own lengths (FG = 1)
   double c2;            // 1 / theta
 };
+// MB = 1 (mass product from the incidence loop): the consistent P1 mass row is (M c)_i = sum_T m_T (s_T + c_i) with
+// m_T = |T| d!/(d+2)! = w_T (d+3) / rho_T, and the loop below already holds w_T, s_T and c_i for every (row, cell) incidence:
+// one more accumulator per row, macc += w_T (s_T + c_i) in record order, and (M c)_i = q_i macc for a row whose cells share one
+// rho > 0 (q = (d+3) / rho, k_corner_weights).  The sweep then DEFINES the right-hand side b = M c + load it is about to use
+// -- b2 in a sweep with two right-hand sides, b otherwise -- instead of reading what a mass SpMV wrote, and writes it to `bw`
+// (the same buffer: it is the next step's b).  Rows with q = 0 (fallback rows) read the buffer as before: the mass SpMV
+// over their slices has run (DevPattern::mass_fb_slices).  Explicit fused multiply-adds: every instance forms the same bits.
+struct MassArgs {
+  const double* q;      // per padded row
+  const double* load;   // may be null
+  double* bw;           // the buffer behind b2 (b2 != null) or b
+};
 __device__ __forceinline__ double fg_first_iterate(double u, double p, double t) {
 #pragma clang fp contract(off)
   const double dn = p * t + 0.0;   // (k_cheb: the c1 term, zero in pass 1, plus the rounded product)
   return u + dn;
 }
-template <int NV, int CAP, int RB, int CIDX, class AT, int FG>
+template <int NV, int CAP, int RB, int CIDX, class AT, int FG, int MB>
 __device__ __forceinline__ void rd_assemble_s_slice(
     double* lds, const SliceDesc* __restrict__ desc, int64_t n_own, const int32_t* __restrict__ cols,
     const uint16_t* __restrict__ cols16, const int32_t* __restrict__ win_base, const uint32_t* __restrict__ cs2,
@@ -635,7 +667,7 @@ __device__ __forceinline__ void rd_assemble_s_slice(
     AT* __restrict__ vA, const double* __restrict__ c, const double* __restrict__ b, const double* __restrict__ b2,
     double* __restrict__ r_out, double* __restrict__ r2_out, double* __restrict__ dinv,
     const uint8_t* __restrict__ fixed, double two_dt, double* __restrict__ partials, int ldscap, int remap,
-    const FgArgs& fg) {
+    const FgArgs& fg, const MassArgs& ma) {
   double* acc = lds;                             // [ldscap][64], ldscap <= CAP = the longest slice of the launch
   double* cn = lds + (size_t)ldscap * GL_WAVE;   // [ldscap][64]
   const int lane = threadIdx.x;
@@ -653,9 +685,10 @@ __device__ __forceinline__ void rd_assemble_s_slice(
   }
   const bool own = row < n_own;
   const int64_t rowc = own ? row : n_own - 1;
-  const double b_row = b[rowc];
-  double b2_row = 0.0;
-  if (b2) b2_row = b2[rowc];
+  // (MB: the right-hand side this sweep defines is not read here -- its fallback lanes fetch it after the records)
+  double b_row = 0.0, b2_row = 0.0;
+  if (!MB || b2) b_row = b[rowc];
+  if (!MB && b2) b2_row = b2[rowc];
   uint32_t fxv = 0;
   if (fixed) fxv = fixed[rowc];
   const int dk = diag_k[row];
@@ -698,7 +731,7 @@ __device__ __forceinline__ void rd_assemble_s_slice(
   for (int k = 0; k < CAP; ++k) S8[k] = GL_STREAM(vS, d.base, min(k, len - 1));
   const double ci = cn[dk * GL_WAVE + lane];
   const double ci4 = 4.0 * ci;
-  double acc_d = 0.0;
+  double acc_d = 0.0, macc = 0.0;
   auto corner = [&](double w, uint32_t slots) {
     int k[NV];
     double cv[NV], st = ci;
@@ -710,6 +743,7 @@ __device__ __forceinline__ void rd_assemble_s_slice(
 #pragma unroll
     for (int m = 1; m < NV; ++m) st += cv[m];
     acc_d += w * (ci4 + 2.0 * st);
+    if constexpr (MB) macc = __builtin_fma(w, st + ci, macc);
 #pragma unroll
     for (int m = 1; m < NV; ++m) lds_add(&acc[k[m] * GL_WAVE + lane], w * (ci + cv[m] + st));
   };
@@ -725,6 +759,10 @@ __device__ __forceinline__ void rd_assemble_s_slice(
     for (int j = 0; j < RB; ++j)
       if (qq + j < clen) corner(wb_[j], sb_[j]);   // (wave-uniform; a padding record of a shorter row has weight 0 and slots 0)
   }
+  // (MB: the row's mass factor and load are requested half-way through phase 3 and looked at after it -- held from the top of
+  //  the kernel they cost four instances their third wave per SIMD, from the start of phase 3 still one: FG = 1 has its
+  //  gathers, the row of S and the columns live there)
+  double mq = 0.0, mload = 0.0;
   // phase 3: A = S + 2 dt N(c), residual 1/2 (A + S) c, diagonal
   // (FG = 1: the guess through the columns the row still holds -- the incidence records' registers are free by now)
   constexpr int GB = 16;   // gathers in flight
@@ -739,6 +777,12 @@ __device__ __forceinline__ void rd_assemble_s_slice(
 #pragma unroll
         for (int j = 0; j < GB; ++j)
           if (k + j < CAP) ug[j] = fg.u[cu[k + j]];
+      }
+    }
+    if constexpr (MB) {
+      if (k == CAP / 2) {   // (compile-time: the loop is fully unrolled -- once per row, whatever its length)
+        mq = ma.q[row];
+        if (ma.load) mload = ma.load[rowc];
       }
     }
     if (k < len) {
@@ -756,6 +800,13 @@ __device__ __forceinline__ void rd_assemble_s_slice(
   double rr = 0.0, rr2 = 0.0, tt = 0.0;
   asm volatile("" : "+v"(fxv));
   if (own) {
+    if constexpr (MB) {
+      // the right-hand side this sweep defines: q macc + load, or on a fallback lane what the mass SpMV over its slice wrote
+      double mass = __builtin_fma(mq, macc, mload);
+      if (mq == 0.0) mass = ma.bw[row];
+      else ma.bw[row] = mass;
+      if (b2) b2_row = mass; else b_row = mass;
+    }
     const bool fx = fxv != 0;
     const double res = fx ? 0.0 : b_row - r;
     r_out[row] = res;
@@ -789,20 +840,21 @@ __device__ __forceinline__ void rd_assemble_s_slice(
   }
 }
 #undef GL_STREAM
-template <int NV, int CAP, int RB, int CIDX, class AT>
+template <int NV, int CAP, int RB, int CIDX, class AT, int MB = 0>
 __global__ __launch_bounds__(GL_WAVE) void k_rd_assemble_s(
     const SliceDesc* __restrict__ desc, int64_t n_own, const int32_t* __restrict__ cols,
     const uint16_t* __restrict__ cols16, const int32_t* __restrict__ win_base, const uint32_t* __restrict__ cs2,
     const double* __restrict__ cw, const uint8_t* __restrict__ diag_k, const double* __restrict__ vS,
     AT* __restrict__ vA, const double* __restrict__ c, const double* __restrict__ b, const double* __restrict__ b2,
     double* __restrict__ r_out, double* __restrict__ r2_out, double* __restrict__ dinv,
-    const uint8_t* __restrict__ fixed, double two_dt, double* __restrict__ partials, int ldscap, int remap) {
+    const uint8_t* __restrict__ fixed, double two_dt, double* __restrict__ partials, int ldscap, int remap,
+    const MassArgs ma) {
   extern __shared__ double lds[];
-  rd_assemble_s_slice<NV, CAP, RB, CIDX, AT, 0>(lds, desc, n_own, cols, cols16, win_base, cs2, cw, diag_k, vS, vA, c, b, b2,
-                                                r_out, r2_out, dinv, fixed, two_dt, partials, ldscap, remap, FgArgs{});
+  rd_assemble_s_slice<NV, CAP, RB, CIDX, AT, 0, MB>(lds, desc, n_own, cols, cols16, win_base, cs2, cw, diag_k, vS, vA, c, b, b2,
+                                                    r_out, r2_out, dinv, fixed, two_dt, partials, ldscap, remap, FgArgs{}, ma);
 }
 // ... and with the first pass of the dot-free solve that follows folded in (FG = 1, 2: see above)
-template <int NV, int CAP, int RB, int CIDX, int FG>
+template <int NV, int CAP, int RB, int CIDX, int FG, int MB = 0>
 __global__ __launch_bounds__(GL_WAVE) void k_rd_assemble_sg(
     const SliceDesc* __restrict__ desc, int64_t n_own, const int32_t* __restrict__ cols,
     const uint16_t* __restrict__ cols16, const int32_t* __restrict__ win_base, const uint32_t* __restrict__ cs2,
@@ -810,10 +862,11 @@ __global__ __launch_bounds__(GL_WAVE) void k_rd_assemble_sg(
     double* __restrict__ vA, const double* __restrict__ c, const double* __restrict__ b, const double* __restrict__ b2,
     double* __restrict__ r_out, double* __restrict__ r2_out, double* __restrict__ dinv,
     const uint8_t* __restrict__ fixed, double two_dt, double* __restrict__ partials, int ldscap, int remap,
-    const FgArgs fg) {
+    const FgArgs fg, const MassArgs ma) {
   extern __shared__ double lds[];
-  rd_assemble_s_slice<NV, CAP, RB, CIDX, double, FG>(lds, desc, n_own, cols, cols16, win_base, cs2, cw, diag_k, vS, vA, c, b,
-                                                     b2, r_out, r2_out, dinv, fixed, two_dt, partials, ldscap, remap, fg);
+  rd_assemble_s_slice<NV, CAP, RB, CIDX, double, FG, MB>(lds, desc, n_own, cols, cols16, win_base, cs2, cw, diag_k, vS, vA, c,
+                                                         b, b2, r_out, r2_out, dinv, fixed, two_dt, partials, ldscap, remap, fg,
+                                                         ma);
 }
 
 __global__ void k_make_desc(int n, const int32_t* __restrict__ list, const int64_t* __restrict__ slice_ptr,
@@ -1510,9 +1563,29 @@ static void assemble_static_t(glims_ctx* h, int with_mechanics) {
   p.cw.alloc((size_t)p.total_corners);
   p.cs2.alloc((size_t)p.total_corners);
   p.cq.alloc((size_t)2 * p.total_corners);
+  p.mass_q.alloc((size_t)p.n_slices * GL_WAVE);
+  dvec<int32_t> mass_fb;
+  mass_fb.alloc((size_t)p.n_slices);
   hipLaunchKernelGGL(k_corner_weights<D>, dim3(p.n_slices), dim3(GL_WAVE), 0, h->st, p.cslice_ptr.p, p.celem.p, h->label.p,
-                     h->evol.p, h->mat.p, p.diag_k.p, p.cslots.p, p.cw.p, p.cs2.p, (uint2*)p.cq.p);
+                     h->evol.p, h->mat.p, p.diag_k.p, p.cslots.p, p.cw.p, p.cs2.p, (uint2*)p.cq.p, h->n_own, p.mass_q.p,
+                     mass_fb.p);
   GL_HIP(hipGetLastError());
+  {
+    // the slices that keep the mass SpMV (rows at an interface of two rho, or touching a tissue with rho = 0)
+    std::vector<int32_t> fb((size_t)p.n_slices), list;
+    GL_HIP(hipMemcpyAsync(fb.data(), mass_fb.p, fb.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->st));
+    GL_HIP(hipStreamSynchronize(h->st));
+    p.mass_fb_rows = 0;
+    for (int32_t sl = 0; sl < p.n_slices; ++sl)
+      if (fb[(size_t)sl] > 0) {
+        list.push_back(sl);
+        p.mass_fb_rows += fb[(size_t)sl];
+      }
+    p.n_mass_fb = (int32_t)list.size();
+    p.mass_fb_slices.upload(list, h->st);
+    GL_HIP(hipStreamSynchronize(h->st));   // `list` is a stack object
+    h->stats.rd_mass_fallback_rows = p.mass_fb_rows;
+  }
   if (with_mechanics) {
     h->vKel.alloc(ne * D * D);
     h->vG.alloc(ne * D);
@@ -1626,11 +1699,22 @@ bool gl_rd_fusable(glims_ctx* h) {
     if (sc->cap > 32) return false;   // (a class of the looped kernel: today's launches throughout)
   return true;
 }
+bool gl_rd_mass_in_sweep(glims_ctx* h) {
+  return (h->opt.flags & GLIMS_FLAG_NO_FUSED_MASS) == 0 && h->world == 1 && gl_rd_fusable(h);
+}
 void gl_rd_assemble(glims_ctx* h, const double* c, const double* b, const double* b2, double* r_out, double* r2_out,
-                    double* partials, int part, const GlFusedSweep* fused) {
+                    double* partials, int part, const GlFusedSweep* fused, const GlMassSweep* mass) {
   ensure_classes(h);
   const DevPattern& p = h->pat;
   const uint8_t* fx = h->have_fixed_c ? h->fixed_c.p : nullptr;
+  MassArgs ma{nullptr, nullptr, nullptr};
+  if (mass) {
+    GL_REQUIRE(gl_rd_fusable(h) && part == GL_PART_ALL && mass->bw == (b2 ? b2 : b),
+               "mass product requested where the sweep has no kernel for it");
+    ma.q = p.mass_q.p;
+    ma.load = mass->load;
+    ma.bw = mass->bw;
+  }
   if (fused && fused->kind != 0) {
     GL_REQUIRE(gl_rd_fusable(h) && part == GL_PART_ALL && (fused->kind == 1 || fused->kind == 2),
                "fused guess pass requested where the sweep has no kernel for it");
@@ -1640,23 +1724,33 @@ void gl_rd_assemble(glims_ctx* h, const double* c, const double* b, const double
     fg.part = fused->part;
     fg.rlen = p.rlen.p;
     fg.c2 = fused->c2;
-#define GL_RDG4(NV, CAP, RB, CIDX, FG)                                                                              \
+    // (MB = 1 only with two right-hand sides: the sweeps that carry a guess pass and define a b are the speculative ones)
+    GL_REQUIRE(!mass || b2, "fused guess pass with the mass product: two right-hand sides only");
+#define GL_RDG4(NV, CAP, RB, CIDX, FG, MB)                                                                          \
   do {                                                                                                             \
-    set_lds(k_rd_assemble_sg<NV, CAP, RB, CIDX, FG>, lds);                                                         \
-    hipLaunchKernelGGL((k_rd_assemble_sg<NV, CAP, RB, CIDX, FG>), dim3(cl.grid), dim3(GL_WAVE), lds, h->st, cl.desc, \
-                       h->n_own, p.cols.p, p.cols16.p, p.win_base.p, p.cs2.p, p.cw.p, p.diag_k.p, h->vS.p, h->vA.p,  \
-                       c, b, b2, r_out, r2_out, h->dinv.p, fx, 2.0 * h->opt.dt, partials, cap, GL_XCD_CHUNK, fg);   \
+    set_lds(k_rd_assemble_sg<NV, CAP, RB, CIDX, FG, MB>, lds);                                                     \
+    hipLaunchKernelGGL((k_rd_assemble_sg<NV, CAP, RB, CIDX, FG, MB>), dim3(cl.grid), dim3(GL_WAVE), lds, h->st,     \
+                       cl.desc, h->n_own, p.cols.p, p.cols16.p, p.win_base.p, p.cs2.p, p.cw.p, p.diag_k.p, h->vS.p, \
+                       h->vA.p, c, b, b2, r_out, r2_out, h->dinv.p, fx, 2.0 * h->opt.dt, partials, cap,             \
+                       GL_XCD_CHUNK, fg, ma);                                                                      \
   } while (0)
-#define GL_RDG3(NV, CIDX, FG)                                                                                       \
+  // (records of the first round trip, rows of at most 16 entries: 26 = 2 x 16 - 6; one fewer where the guess's gather, 32-bit
+  //  columns and the mass accumulator meet -- 170 registers with 26, two waves per SIMD instead of three; a row of 16 entries
+  //  then fetches its last record in a second round trip, the same terms in the same order)
+#define GL_RDG_RB16(NV, CIDX, FG, MB) ((NV) == 4 && (CIDX) == 0 && (FG) == 1 && (MB) == 1 ? 25 : 26)
+#define GL_RDG3(NV, CIDX, FG, MB)                                                                                   \
   do {                                                                                                             \
-    if (cap <= 16) GL_RDG4(NV, 16, 26, CIDX, FG);                                                                  \
-    else if (cap <= 20) GL_RDG4(NV, 20, 24, CIDX, FG);                                                             \
-    else if (cap <= 24) GL_RDG4(NV, 24, 24, CIDX, FG);                                                             \
-    else GL_RDG4(NV, 32, 24, CIDX, FG);                                                                            \
+    if (cap <= 16) GL_RDG4(NV, 16, GL_RDG_RB16(NV, CIDX, FG, MB), CIDX, FG, MB);                                   \
+    else if (cap <= 20) GL_RDG4(NV, 20, 24, CIDX, FG, MB);                                                         \
+    else if (cap <= 24) GL_RDG4(NV, 24, 24, CIDX, FG, MB);                                                         \
+    else GL_RDG4(NV, 32, 24, CIDX, FG, MB);                                                                        \
   } while (0)
 #define GL_RDG2(NV, CIDX)                                                                                           \
   do {                                                                                                             \
-    if (fused->kind == 1) GL_RDG3(NV, CIDX, 1); else GL_RDG3(NV, CIDX, 2);                                          \
+    if (fused->kind == 1 && mass) GL_RDG3(NV, CIDX, 1, 1);                                                         \
+    else if (fused->kind == 1) GL_RDG3(NV, CIDX, 1, 0);                                                            \
+    else if (mass) GL_RDG3(NV, CIDX, 2, 1);                                                                        \
+    else GL_RDG3(NV, CIDX, 2, 0);                                                                                  \
   } while (0)
     for (const SliceClass* sc : p.classes) {
       const ClassLaunch cl = class_launch(*sc, part);
@@ -1670,6 +1764,7 @@ void gl_rd_assemble(glims_ctx* h, const double* c, const double* b, const double
       }
     }
 #undef GL_RDG2
+#undef GL_RDG_RB16
 #undef GL_RDG3
 #undef GL_RDG4
     GL_HIP(hipGetLastError());
@@ -1688,7 +1783,23 @@ void gl_rd_assemble(glims_ctx* h, const double* c, const double* b, const double
     set_lds(k_rd_assemble_s<NV, CAP, RB, CIDX, AT>, lds);                                                          \
     hipLaunchKernelGGL((k_rd_assemble_s<NV, CAP, RB, CIDX, AT>), dim3(cl.grid), dim3(GL_WAVE), lds, h->st, cl.desc,  \
                        h->n_own, p.cols.p, p.cols16.p, p.win_base.p, p.cs2.p, p.cw.p, p.diag_k.p, h->vS.p, APTR, c,  \
-                       b, b2, r_out, r2_out, h->dinv.p, fx, 2.0 * h->opt.dt, partials, cap, GL_XCD_CHUNK);          \
+                       b, b2, r_out, r2_out, h->dinv.p, fx, 2.0 * h->opt.dt, partials, cap, GL_XCD_CHUNK, ma);      \
+  } while (0)
+  // (MB = 1: fp64 Jacobian, straight-line classes only -- gl_rd_fusable, required above)
+#define GL_RDM3(NV, CAP, RB, CIDX)                                                                                  \
+  do {                                                                                                             \
+    set_lds(k_rd_assemble_s<NV, CAP, RB, CIDX, double, 1>, lds);                                                   \
+    hipLaunchKernelGGL((k_rd_assemble_s<NV, CAP, RB, CIDX, double, 1>), dim3(cl.grid), dim3(GL_WAVE), lds, h->st,   \
+                       cl.desc, h->n_own, p.cols.p, p.cols16.p, p.win_base.p, p.cs2.p, p.cw.p, p.diag_k.p, h->vS.p, \
+                       h->vA.p, c, b, b2, r_out, r2_out, h->dinv.p, fx, 2.0 * h->opt.dt, partials, cap,             \
+                       GL_XCD_CHUNK, ma);                                                                          \
+  } while (0)
+#define GL_RDM2(NV, CIDX)                                                                                           \
+  do {                                                                                                             \
+    if (cap <= 16) GL_RDM3(NV, 16, 26, CIDX);                                                                      \
+    else if (cap <= 20) GL_RDM3(NV, 20, 24, CIDX);                                                                 \
+    else if (cap <= 24) GL_RDM3(NV, 24, 24, CIDX);                                                                 \
+    else GL_RDM3(NV, 32, 24, CIDX);                                                                                \
   } while (0)
   // (incidence records of the first round trip: an interior row of a tetrahedral mesh with n entries has 2 n - 6 of them)
 #define GL_RDS2(NV, CIDX, AT, APTR)                                                                                 \
@@ -1711,8 +1822,16 @@ void gl_rd_assemble(glims_ctx* h, const double* c, const double* b, const double
     if (cl.grid <= 0) continue;
     const int cap = sc->cap;
     const size_t lds = (size_t)2 * cap * GL_WAVE * sizeof(double);
-    if (h->nv == 3) GL_RDV(3); else GL_RDV(4);
+    if (mass) {
+      if (h->nv == 3) {
+        if (h->use_idx16) GL_RDM2(3, 1); else GL_RDM2(3, 0);
+      } else {
+        if (h->use_idx16) GL_RDM2(4, 1); else GL_RDM2(4, 0);
+      }
+    } else if (h->nv == 3) GL_RDV(3); else GL_RDV(4);
   }
+#undef GL_RDM2
+#undef GL_RDM3
 #undef GL_RDV
 #undef GL_RDS2
 #undef GL_RDS3

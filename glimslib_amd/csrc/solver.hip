@@ -1532,19 +1532,35 @@ static ChebRun cheb_solve(glims_ctx* h, const CgVecs& v, double tol_abs, double 
 // `exchange_c`: the ghosts of c are stale (a linear solve has just updated the owned values): in a partitioned run
 // the interior slices -- mass SpMV for b2 and sweep -- run while the halo is in flight, the boundary slices after it.
 // `fused` (single rank): the sweep also runs the first pass of the dot-free solve that follows it (GlFusedSweep).
+// `mass_for_b2` / `mass_for_b`: the sweep's second / only right-hand side is M c + load of the c it runs at, formed here
+// first -- by the mass SpMV, or where gl_rd_mass_in_sweep says so by the sweep itself from its incidence records (the SpMV
+// then covers the slices with fallback rows only: none on a mesh whose tissues share one rho > 0).  Every b of the stepping
+// path comes from the same formula either way, so a step gives the same bits whether or not a speculative sweep prepared it.
 static void rd_sweep(glims_ctx* h, const double* b2, double* norms /*[2]*/, Mail* krylov = nullptr,
-                     bool exchange_c = false, bool mass_for_b2 = false, const GlFusedSweep* fused = nullptr) {
+                     bool exchange_c = false, bool mass_for_b2 = false, const GlFusedSweep* fused = nullptr,
+                     bool mass_for_b = false) {
   const DevPattern& p = h->pat;
   const double* load = h->have_load_rd ? h->load_rd.p : nullptr;
   const bool split = exchange_c && h->world > 1 && h->n_peers > 0;
   if (!split) {
     if (exchange_c) gl_halo_exchange(h, h->c.p, 1);
-    if (mass_for_b2)
-      gl_launch_spmv(h, h->st, p.n_slices, nullptr, h->vM.p, h->c.p, h->b2.p, nullptr, load, nullptr, nullptr, 0,
-                     nullptr);
+    double* bdst = mass_for_b2 ? h->b2.p : h->b.p;
+    const bool mass_here = (mass_for_b2 || mass_for_b) && gl_rd_mass_in_sweep(h);
+    GlMassSweep ms;
+    ms.load = load;
+    ms.bw = bdst;
+    if (mass_here) {
+      if (p.n_mass_fb > 0)
+        gl_launch_spmv(h, h->st, p.n_mass_fb, p.mass_fb_slices.p, h->vM.p, h->c.p, bdst, nullptr, load, nullptr, nullptr, 0,
+                       nullptr);
+      h->stats.rd_mass_in_sweep++;
+    } else if (mass_for_b2 || mass_for_b) {
+      gl_launch_spmv(h, h->st, p.n_slices, nullptr, h->vM.p, h->c.p, bdst, nullptr, load, nullptr, nullptr, 0, nullptr);
+    }
     const bool timed = h->timing(glims_ctx::TK_SWEEP);
     if (timed) h->tick(glims_ctx::TK_SWEEP);
-    gl_rd_assemble(h, h->c.p, h->b.p, b2, h->cg_r.p, h->cg_r2.p, h->partials.p, GL_PART_ALL, fused);
+    gl_rd_assemble(h, h->c.p, h->b.p, b2, h->cg_r.p, h->cg_r2.p, h->partials.p, GL_PART_ALL, fused,
+                   mass_here ? &ms : nullptr);
     if (timed) h->tick(glims_ctx::TK_SWEEP);
   } else {
     halo_start(h, h->c.p, 1);
@@ -1738,8 +1754,12 @@ int gl_step(glims_ctx* h, int n_steps) {
       h->pending = false;
     } else {
       // b = M c^n + load          ('u_previous1 * v1 * dx', simulation_tumor_growth.py:117)
-      gl_launch_spmv(h, h->st, p.n_slices, nullptr, h->vM.p, h->c.p, h->b.p, nullptr, load, nullptr, nullptr, 0,
-                     nullptr);
+      // Where the iterate changes between this product and the sweep (new Dirichlet data, the extrapolated guess) it is formed
+      // here, on the old state; otherwise with the sweep (rd_sweep, mass_for_b: the same formula as a speculative sweep's b2).
+      const bool c_changes = h->dirichlet_c_dirty || h->dirichlet_c_exchange || extrapolate;
+      if (c_changes)
+        gl_launch_spmv(h, h->st, p.n_slices, nullptr, h->vM.p, h->c.p, h->b.p, nullptr, load, nullptr, nullptr, 0,
+                       nullptr);
       // new Dirichlet data enter the ITERATE, after the old state went into b = M c^n: the reference's u_previous
       // keeps the previous step's boundary values while the DirichletBC constrains the unknown
       // (a rank lists its OWN constrained nodes; their ghost copies on the neighbours follow by a halo exchange that every
@@ -1759,7 +1779,7 @@ int gl_step(glims_ctx* h, int n_steps) {
                            h->have_fixed_c ? h->fixed_c.p : nullptr, h->stats.steps > 0 ? 1 : 0);
         gl_halo_exchange(h, h->c.p, 1);
       }
-      rd_sweep(h, nullptr, norms);
+      rd_sweep(h, nullptr, norms, nullptr, /*exchange_c=*/false, /*mass_for_b2=*/false, nullptr, /*mass_for_b=*/!c_changes);
       nr = norms[0];
     }
     const double r0 = nr;

@@ -209,6 +209,17 @@ typedef struct glims_options {
                                            launch that streams the Jacobian again (single rank, fp64 Jacobian, rows of at most
                                            32 entries; same bits in every result, glims_stats.cheb_fused_passes counts them).
                                            Set: the separate launches (A/B in one build) */
+#define GLIMS_FLAG_NO_FUSED_MASS 2048     /* OFF by default.  Default: a sweep of the stepping path that is about to use a new
+                                           right-hand side b = M c + load (the speculative sweeps' b2, a step's first b) forms
+                                           that product itself from the (row, cell) incidence records it walks anyway -- for
+                                           every row whose cells share one rho > 0: (M c)_i = (d+3)/rho sum_T w_T (s_T + c_i)
+                                           -- and the mass SpMV runs over the slices with other rows only (interfaces of two
+                                           rho, tissues with rho = 0; glims_stats.rd_mass_fallback_rows) or not at all.  Single
+                                           rank, fp64 Jacobian, rows of at most 32 entries; the right-hand side differs from
+                                           the SpMV's in the last bits (another summation order), results agree to ~1e-15;
+                                           glims_stats.rd_mass_in_sweep counts the sweeps.  A step whose first b is formed
+                                           before new Dirichlet values or the extrapolated guess enter the iterate keeps the
+                                           SpMV for that b.  Set: the mass SpMV everywhere (A/B in one build) */
 
 typedef struct glims_stats {
   int64_t steps;            /* implicit time steps taken */
@@ -300,6 +311,10 @@ typedef struct glims_stats {
   /* ---- appended under ABI 6 (readers of the older layout are unaffected) */
   int64_t cheb_fused_passes;/* first passes of dot-free solves (guess pass, or start from zero) that an assembly sweep ran and
                                the solve took over; still counted in cheb_its and cg_its (see GLIMS_FLAG_NO_FUSED_GUESS) */
+  int64_t rd_mass_in_sweep; /* assembly sweeps that formed the mass product M c + load of their new right-hand side themselves
+                               (see GLIMS_FLAG_NO_FUSED_MASS) */
+  int64_t rd_mass_fallback_rows; /* owned rows whose mass product stays with the SpMV: cells of different rho, or rho = 0
+                               (set by glims_setup / glims_set_materials; kept by glims_reset_stats) */
 } glims_stats;
 
 /* ---- lifetime -------------------------------------------------------------------------------------- */
@@ -382,7 +397,12 @@ int glims_reset_stats(glims_ctx* h);
  *        measured 4.2x slower than the assembled product at 10 M rows -- 1.38 ms and 5.15 GB against 0.33 ms and 1.77 GB --
  *        profiles/r02_matfree_ab.txt);  8 = the assembly sweep at c = x with a zero right-hand side, y = -1/2 (A(x) + S) x
  *        (timing hook, tools/ab_sweep.py; with a state set, A(c) and its diagonal are re-assembled before the call returns);
- *        9 = the quadratic-term pass with a = delta = x, y -= dt N(x) x per repetition (timing hook).
+ *        9 = the quadratic-term pass with a = delta = x, y -= dt N(x) x per repetition (timing hook);
+ *        10 = TEST HOOK: y = M x + rd_load as the stepping path forms a step's first right-hand side where the sweep carries
+ *        the mass product (GLIMS_FLAG_NO_FUSED_MASS not set): the mass SpMV over the slices with fallback rows, then the
+ *        single-right-hand-side sweep at c = x, and the b it wrote is returned.  GLIMS_E_USAGE where that mode is off for the
+ *        handle.  Like glims_rd_residual it drops the system a previous step prepared (the next step re-assembles); with a
+ *        state set, A(c) and its diagonal are re-assembled before the call returns, as for which = 8.
  *        Ghost rows of y are returned as 0. */
 int glims_apply(glims_ctx* h, int which, const double* x, double* y, int reps, double* ms_total);
 
