@@ -2,7 +2,15 @@
 T1 / T2 segmentations (optimization_workflow/image_based_optimization.py:660-708, thresh() at :1404) -- where the images
 were measured: the misfit is a sum over the voxels of a grid that does not align with the mesh, evaluated and differentiated on
 the device (sim.image_term -> glims_adjoint_image_terms).  The images are made by a run with D = rho = 0.1 plus image noise;
-the fit starts from (0.05, 0.2) and ends with the Laplace covariance of the fitted parameters."""
+the fit starts from (0.05, 0.2) and ends with the Laplace covariance of the fitted parameters.
+
+The same script runs partitioned under
+
+    python -m torch.distributed.run --nproc-per-node 2 examples/adjoint_fit_images_2D.py
+
+(one rank per GPU; GLIMS_TRANSPORT=gloo GLIMS_FORCE_DEVICE=0 rehearses it with all ranks on one GPU): every rank holds the
+images, the grid's sampler is resolved over the ranks and rank 0 prints the same fit.  The Hessian, and with it the Laplace
+covariance, is a single-GPU call and is skipped there."""
 import os
 import sys
 import tempfile
@@ -10,6 +18,16 @@ import tempfile
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+world = int(os.environ.get("WORLD_SIZE", "1"))
+if world > 1:
+    import torch
+    import torch.distributed as dist
+    forced = os.environ.get("GLIMS_FORCE_DEVICE")
+    torch.cuda.set_device(int(forced if forced is not None else os.environ["LOCAL_RANK"]))
+    dist.init_process_group(backend="gloo" if forced is not None else "cpu:gloo,cuda:nccl")
+rank = dist.get_rank() if world > 1 else 0
+say = print if rank == 0 else (lambda *a, **k: None)
+
 from glimslib_amd import fenics_local as fenics  # noqa: E402
 from glimslib_amd.optimization import ReducedFunctional, minimize  # noqa: E402
 from glimslib_amd.simulation import TumorGrowth  # noqa: E402
@@ -59,15 +77,18 @@ terms = lambda sim, n_steps: [sim.image_term(n_steps, im, kind='img_thresh', lev
 sim = make_sim(0.05, 0.2)
 rf = ReducedFunctional(sim, 2, terms, run_kwargs=dict(output_dir=out))
 res = minimize(rf, [0.05, 0.2], options={"maxiter": 30, "gtol": 1e-12, "ftol": 1e-16}, tol=1e-16)
-print("fitted D = %.6f, rho = %.6f after %d L-BFGS-B iterations, %d forward + backward runs (J = %.3e)"
+say("fitted D = %.6f, rho = %.6f after %d L-BFGS-B iterations, %d forward + backward runs (J = %.3e)"
       % (res.x[0], res.x[1], res.nit, rf.evaluations, res.fun))
-_, n_vox, n_obs = sim._backend.image_term_info(0)
-print("each image: %d voxels, %d observed (inside the mesh)" % (n_vox, n_obs))
-# Laplace covariance: J is 1/2 |voxel| sum (h - t)^2, so the noise variance per unit of J's weight is sigma^2 / |voxel|
-H = rf.hessian_matrix(res.x)
-cov = sigma ** 2 * float(np.prod(grid['spacing'])) * np.linalg.inv(H)
-sd = np.sqrt(np.diag(cov))
-print("Hessian at the optimum:\n%s" % H)
-print("Laplace covariance:\n%s" % cov)
-print("standard deviations: D %.3e, rho %.3e;  D-rho correlation %.4f" % (sd[0], sd[1], cov[0, 1] / (sd[0] * sd[1])))
+_, n_vox, n_obs = sim._backend.image_term_info(0)   # (partitioned: the observed count summed over the ranks)
+say("each image: %d voxels, %d observed (inside the mesh)" % (n_vox, n_obs))
+if world == 1:
+    # Laplace covariance: J is 1/2 |voxel| sum (h - t)^2, so the noise variance per unit of J's weight is sigma^2 / |voxel|
+    H = rf.hessian_matrix(res.x)
+    cov = sigma ** 2 * float(np.prod(grid['spacing'])) * np.linalg.inv(H)
+    sd = np.sqrt(np.diag(cov))
+    print("Hessian at the optimum:\n%s" % H)
+    print("Laplace covariance:\n%s" % cov)
+    print("standard deviations: D %.3e, rho %.3e;  D-rho correlation %.4f" % (sd[0], sd[1], cov[0, 1] / (sd[0] * sd[1])))
 sim.close()
+if world > 1:
+    dist.destroy_process_group()

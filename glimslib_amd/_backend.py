@@ -155,6 +155,8 @@ SIGNATURES = {
     "glims_sampler_get": (C.c_int, [_h, C.c_int64, _i32p, _dp]),
     "glims_sampler_apply": (C.c_int, [_h, C.c_int64, C.c_int, C.c_int64, _dp, C.c_int, C.c_double, _dp]),
     "glims_sampler_apply_t": (C.c_int, [_h, C.c_int64, _dp, C.c_int, _dp]),
+    "glims_sampler_resolve": (C.c_int, [_h, C.c_int64, _i64p]),
+    "glims_sampler_get_counted": (C.c_int, [_h, C.c_int64, C.POINTER(C.c_uint8)]),
     "glims_sampler_destroy": (C.c_int, [_h, C.c_int64]),
     "glims_adjoint_image_terms": (C.c_int, [_h, C.c_int, C.POINTER(ImageMisfit)]),
     "glims_adjoint_image_info": (C.c_int, [_h, C.c_int, _i64p]),
@@ -604,6 +606,29 @@ class Sampler:
     @property
     def weights(self):
         return self._get(False, True)[1]
+
+    def resolve(self, cell_gid):
+        """glims_sampler_resolve (collective on a partitioned handle, every rank with the same points): cell_gid [n_cells] =
+        the global id of each of this handle's cells, strictly increasing (``partition_mesh``'s ``cell_ids``).  Afterwards
+        the sampler keeps only the points whose local winner is the global winner, ``n_found`` counts those, and ``apply_t``
+        works (owned rows complete, ghost rows 0).  A no-op on a single-GPU handle."""
+        h = self.handle
+        gid = np.ascontiguousarray(cell_gid, dtype=np.int64).reshape(-1)
+        if gid.shape != (h.n_cells,):
+            raise ValueError("cell_gid has %d entries, the handle %d cells" % (gid.size, h.n_cells))
+        h._check(h.lib.glims_sampler_resolve(h._h, self.id, _ptr(gid, _i64p)))
+        nf = C.c_int64(0)
+        h._check(h.lib.glims_sampler_info(h._h, self.id, None, C.byref(nf)))
+        self.n_found = int(nf.value)
+
+    @property
+    def counted(self):
+        """bool [n_points]: the points this rank adds to J and to the observed count (resolved samplers; otherwise the found
+        points)."""
+        h = self.handle
+        out = np.zeros(self.n_points, dtype=np.uint8)
+        h._check(h.lib.glims_sampler_get_counted(h._h, self.id, _ptr(out, C.POINTER(C.c_uint8))))
+        return out.astype(bool)
 
     def apply(self, field, snapshot=None, fill=np.nan):
         """P f at every point: ``field`` = 'c' (current concentration, or the device snapshot ``snapshot``), 'u' (current

@@ -383,12 +383,31 @@ void mass_apply(glims_ctx* h, const double* x, double* y) {
 
 // The stored image terms (glims_adjoint_image_terms) that observe `step`, in their list order, after the step's nodal terms:
 // g += P^T r of each, J += 1/2 w sum_p q_p (h(v_p) - t_p)^2; with P > 0 also dg_j += P^T r2_j for the Hessian's directions
-// dc (column-major [P][ld]).  No stored term: no launch.
+// dc (column-major [P][ld]).  No stored term: no launch.  Partitioned handles: a rank sums the points it COUNTS
+// (glims_sampler_resolve), the ranks' sums are gathered and added in rank order -- one small all-reduce per term that observes
+// the step, made by every rank (the stored list is SPMD: gl_adjoint_gradient has checked it).
+double sum_over_ranks(glims_ctx* h, double mine) {
+  // [world] with zeros outside the own entry: x + 0 is exact, every rank receives every entry bit for bit
+  dvec<double> all;
+  all.alloc_zero((size_t)h->world, h->st);
+  GL_HIP(hipMemcpyAsync(all.p + h->rank, &mine, sizeof(double), hipMemcpyHostToDevice, h->st));
+  GL_HIP(hipStreamSynchronize(h->st));
+  gl_allreduce_bulk(h, all.p, (size_t)h->world);
+  std::vector<double> rows((size_t)h->world);
+  GL_HIP(hipMemcpyAsync(rows.data(), all.p, rows.size() * sizeof(double), hipMemcpyDeviceToHost, h->st));
+  GL_HIP(hipStreamSynchronize(h->st));
+  double t = 0.0;
+  for (int r = 0; r < h->world; ++r) t += rows[(size_t)r];
+  return t;
+}
+
 void image_terms_of_step(glims_ctx* h, int step, const double* c, double* g, double* J, int P = 0,
                          const double* dc = nullptr, int64_t ld = 0, double* dg = nullptr) {
   for (const GlImageTerm* t : h->img_terms) {
     if (t->step != step) continue;
-    *J += 0.5 * t->weight * gl_image_misfit_grad(h, *t, c, g);
+    double sum = gl_image_misfit_grad(h, *t, c, g);
+    if (h->world > 1) sum = sum_over_ranks(h, sum);
+    *J += 0.5 * t->weight * sum;
     if (P > 0) gl_image_misfit_second(h, *t, c, dc, P, ld, dg);
   }
 }
@@ -1590,10 +1609,15 @@ int gl_adjoint_gradient(glims_ctx* h, int n_terms, const glims_misfit* terms, do
       if (e.code != GLIMS_E_USAGE) throw;
       why = e.what();
     }
-    // (second row: whether the rank asks for dJ/dE or dJ/dnu -- the size of the final all-reduce follows it)
-    std::vector<double> flag((size_t)h->world * 2, 0.0);
+    // (second row: whether the rank asks for dJ/dE or dJ/dnu -- the size of the final all-reduce follows it; third and fourth:
+    // the stored image terms, their count and a checksum of their steps -- the all-reduces of the sweep follow them)
+    std::vector<double> flag((size_t)h->world * 4, 0.0);
     flag[(size_t)h->rank] = why.empty() ? 0.0 : 1.0;
     flag[(size_t)(h->world + h->rank)] = (dE || dnu) ? 1.0 : 0.0;
+    uint64_t sum_steps = 0;
+    for (const GlImageTerm* t : h->img_terms) sum_steps = (sum_steps * 1000003ull + (uint64_t)t->step + 1) & ((1ull << 52) - 1);
+    flag[(size_t)(2 * h->world + h->rank)] = (double)h->img_terms.size();
+    flag[(size_t)(3 * h->world + h->rank)] = (double)sum_steps;
     dvec<double> d_flag;
     d_flag.upload(flag, h->st);
     gl_allreduce_bulk(h, d_flag.p, flag.size());
@@ -1608,6 +1632,11 @@ int gl_adjoint_gradient(glims_ctx* h, int n_terms, const glims_misfit* terms, do
     for (int r = 1; r < h->world; ++r)
       if (flag[(size_t)(h->world + r)] != flag[(size_t)h->world])
         throw glims_error(GLIMS_E_USAGE, "glims_adjoint_gradient_full: the ranks disagree on asking for dJ_dE / dJ_dnu");
+    for (int r = 1; r < h->world; ++r)
+      if (flag[(size_t)(2 * h->world + r)] != flag[(size_t)(2 * h->world)] ||
+          flag[(size_t)(3 * h->world + r)] != flag[(size_t)(3 * h->world)])
+        throw glims_error(GLIMS_E_USAGE, "glims_adjoint_gradient: the ranks disagree on the stored image terms (their count "
+                                         "or the steps they observe)");
   }
   return h->dim == 2 ? gradient_t<2>(h, n_terms, terms, J, dD, drho, dgamma, dc0, dE, dnu)
                      : gradient_t<3>(h, n_terms, terms, J, dD, drho, dgamma, dc0, dE, dnu);

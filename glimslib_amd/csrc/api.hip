@@ -901,6 +901,20 @@ int glims_sampler_apply_t(glims_ctx* h, int64_t id, const double* r, int ncomp, 
   });
 }
 
+int glims_sampler_resolve(glims_ctx* h, int64_t id, const int64_t* cell_gid) {
+  return guarded(h, [&]() {
+    gl_sampler_resolve(h, id, cell_gid);
+    return GLIMS_OK;
+  });
+}
+
+int glims_sampler_get_counted(glims_ctx* h, int64_t id, uint8_t* counted) {
+  return guarded(h, [&]() {
+    gl_sampler_get_counted(h, id, counted);
+    return GLIMS_OK;
+  });
+}
+
 int glims_sampler_destroy(glims_ctx* h, int64_t id) {
   return guarded(h, [&]() {
     gl_sampler_destroy(h, id);

@@ -773,6 +773,8 @@ void gl_sampler_get(glims_ctx* h, int64_t id, int32_t* cell, double* w);
 void gl_sampler_apply(glims_ctx* h, int64_t id, int field, int64_t snapshot, const double* nodal, int ncomp, double fill,
                       double* out);
 void gl_sampler_apply_t(glims_ctx* h, int64_t id, const double* r, int ncomp, double* g);
+void gl_sampler_resolve(glims_ctx* h, int64_t id, const int64_t* cell_gid);   // collective on partitioned handles
+void gl_sampler_get_counted(glims_ctx* h, int64_t id, uint8_t* counted);
 void gl_sampler_destroy(glims_ctx* h, int64_t id);
 void gl_sampler_destroy_all(glims_ctx* h);   // (and the stored image terms)
 // g[row * ld_row + a * ld_comp] (internal numbering, owned rows) = or += (P^T r)[row][a]; r [n_points][ncomp] on the device

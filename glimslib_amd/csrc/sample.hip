@@ -13,6 +13,11 @@
 // cell), cut into chunks of at most GL_SAMPLE_CHUNK points that never straddle two cells; pass 1 writes per chunk
 // q[chunk][a] = sum_p w[p][a] r[p] in list order, pass 2 is row-owned -- every node walks its incidence list and adds, cell by
 // cell and chunk by chunk, the entries of its own vertex slot.
+//
+// Partitioned handles: glims_sampler_resolve (collective, once per sampler) keeps on every rank only the points whose local
+// winner is the GLOBAL winner -- the smallest global cell id over the ranks -- and marks each point COUNTED on the smallest
+// rank that keeps it.  The transpose's lists are then built from the kept points and P^T runs as on one GPU: an owned row has
+// all its cells local, so its incidence list sees every kept point of every one of its cells and no exchange is needed.
 #include "glims_internal.h"
 
 #include <algorithm>
@@ -24,6 +29,8 @@
 
 #define GL_SAMPLE_BIG 256      // candidates under one cell's box above which the cell gets a block of its own
 #define GL_SAMPLE_CHUNK 256    // points per chunk of a cell's list in the transpose
+#define GL_RESOLVE_BYTES ((size_t)64 << 20)   // bound of the [world][chunk] key buffer of glims_sampler_resolve
+#define GL_RESOLVE_NONE 9007199254740992.0    // 2^53: key of a point this rank did not find (global cell ids lie below)
 
 struct GlSampler {
   int64_t n = 0, n_found = 0;
@@ -31,10 +38,13 @@ struct GlSampler {
   dvec<int32_t> cell;          // [n] caller's cell index, -1 = outside the mesh
   dvec<int32_t> node;          // [n][nv] internal node of the winner's vertices (caller's vertex order; 0 when outside)
   dvec<double> w;              // [n][nv]
-  // transpose (single-rank handles)
+  // partitioned handles: after glims_sampler_resolve the arrays above hold the KEPT points only (the others cell -1, w 0)
+  bool resolved = false;
+  dvec<uint8_t> counted;       // [n] resolved samplers: 1 = this rank adds the point to J and to the observed count
+  // transpose (built at creation on single-rank handles, by glims_sampler_resolve on partitioned ones)
   bool have_t = false;
   int64_t n_chunks = 0;
-  dvec<int32_t> order;         // [n] points sorted by winning internal cell, the n_found found ones first
+  dvec<int32_t> order;         // [n] points sorted by winning internal cell, the n_found found (kept) ones first
   dvec<int32_t> cptr;          // [n_cells + 1] a cell's points in `order`
   dvec<int32_t> chunk_ptr;     // [n_cells + 1] a cell's chunks
   dvec<int32_t> chunk_cell;    // [n_chunks]
@@ -556,15 +566,19 @@ __global__ __launch_bounds__(256) void k_sample_t(int64_t n_own, int ncomp, cons
 }
 
 // ---- image-space misfit terms (glims_hip.h, "image-space misfit terms") --------------------------------
-// once per stored term: t[p] = NaN where the point is not observed (outside the mesh, q_p = 0); counts the observed ones
+// once per stored term: t[p] = NaN where the point is not observed (outside the mesh, q_p = 0); counts the observed ones.
+// counted (resolved samplers, else null): only the counted points enter n_obs -- a kept point that another rank counts keeps
+// its target, P^T r needs its r here.
 __global__ __launch_bounds__(256) void k_img_prepare(int64_t n, const int32_t* __restrict__ cell, const double* __restrict__ q,
-                                                     double* __restrict__ t, unsigned long long* __restrict__ n_obs) {
+                                                     const uint8_t* __restrict__ counted, double* __restrict__ t,
+                                                     unsigned long long* __restrict__ n_obs) {
   const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   bool obs = false;
   if (p < n) {
     const double tv = t[p];
     obs = cell[p] >= 0 && tv == tv && (!q || q[p] != 0.0);
     if (!obs) t[p] = __longlong_as_double(0x7ff8000000000000LL);
+    if (counted && !counted[p]) obs = false;
   }
   const int here = __syncthreads_count(obs);
   if (threadIdx.x == 0 && here) atomicAdd(n_obs, (unsigned long long)here);   // (integer: order-independent)
@@ -592,14 +606,16 @@ __device__ __forceinline__ double img_wave_sum(double v) {
 
 // One thread per point: v = sum_a w c[node] gathered from the recorded state (internal numbering), r[p] = weight q h'(v)
 // (h(v) - t) for an observed point (t not NaN), else 0 -- a NaN target enters no arithmetic.  part[block] = the block's sum of
-// q (h(v) - t)^2: the wave's butterfly, then the four wave sums in a fixed order.
-// Bytes per point: NV (4 + 8) node ids and weights + 8 (t) + 8 (q, if present) + 8 (r); c is gathered through the caches.
+// q (h(v) - t)^2: the wave's butterfly, then the four wave sums in a fixed order.  counted (resolved samplers, else null): r
+// is written for every kept observed point, the square enters the sum only where this rank counts the point.
+// Bytes per point: NV (4 + 8) node ids and weights + 8 (t) + 8 (q, if present) + 1 (counted, if present) + 8 (r); c is
+// gathered through the caches.
 template <int NV>
 __global__ __launch_bounds__(256) void k_img_misfit(int64_t n, int kind, double level, double smooth, double weight,
                                                     const int32_t* __restrict__ node, const double* __restrict__ w,
                                                     const double* __restrict__ c, const double* __restrict__ t,
-                                                    const double* __restrict__ q, double* __restrict__ r,
-                                                    double* __restrict__ part) {
+                                                    const double* __restrict__ q, const uint8_t* __restrict__ counted,
+                                                    double* __restrict__ r, double* __restrict__ part) {
   const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   double sq = 0.0;
   if (p < n) {
@@ -615,6 +631,7 @@ __global__ __launch_bounds__(256) void k_img_misfit(int64_t n, int kind, double 
       const double e = hv - tv;
       rv = weight * qv * hp * e;
       sq = qv * e * e;
+      if (counted && !counted[p]) sq = 0.0;
     }
     r[p] = rv;
   }
@@ -679,6 +696,59 @@ __global__ __launch_bounds__(256) void k_img_misfit_dir(int64_t n, int P, int64_
   }
 }
 
+// ---- glims_sampler_resolve ---------------------------------------------------------------------------------------------------
+// keys: row `rank` of buf[world][m] (zero elsewhere) = the global id of the local winner of point p0 + i, as a double, or
+// GL_RESOLVE_NONE.  8 B written per point (+ 4 B cell, 8 B cell_gid gathered).
+__global__ __launch_bounds__(256) void k_resolve_keys(int64_t m, int64_t p0, const int32_t* __restrict__ cell,
+                                                      const int64_t* __restrict__ cell_gid, double* __restrict__ row) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  const int c = cell[p0 + i];
+  row[i] = c >= 0 ? (double)cell_gid[c] : GL_RESOLVE_NONE;
+}
+
+// pick, after the gather: per point the minimum over the rows and the smallest rank that attains it.  This rank KEEPS the point
+// iff its own key is that minimum (and a cell), and COUNTS it iff it is that smallest rank; a dropped point loses its cell,
+// nodes and weights.  key / val: the transpose's sort input (internal cell of a kept point, n_cells for the others).
+// Bytes per point: 8 world (keys) + 4 (cell) + 1 (counted) + 8 (key, val); NV 12 more for a dropped point.
+template <int NV>
+__global__ __launch_bounds__(256) void k_resolve_pick(int64_t m, int64_t p0, int world, int rank, int64_t n_cells,
+                                                      const double* __restrict__ buf, const int32_t* __restrict__ old2new,
+                                                      int32_t* __restrict__ cell, int32_t* __restrict__ node,
+                                                      double* __restrict__ w, uint8_t* __restrict__ counted,
+                                                      uint32_t* __restrict__ key, int32_t* __restrict__ val,
+                                                      unsigned long long* __restrict__ n_kept) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool keep = false;
+  if (i < m) {
+    const int64_t p = p0 + i;
+    double best = GL_RESOLVE_NONE;
+    int first = -1;
+    for (int r = 0; r < world; ++r) {
+      const double k = buf[(int64_t)r * m + i];
+      if (k < best) {
+        best = k;
+        first = r;
+      }
+    }
+    const int c = cell[p];
+    keep = c >= 0 && buf[(int64_t)rank * m + i] == best;
+    counted[p] = keep && first == rank ? 1 : 0;
+    if (!keep) {
+      cell[p] = -1;
+#pragma unroll
+      for (int a = 0; a < NV; ++a) {
+        node[p * NV + a] = 0;
+        w[p * NV + a] = 0.0;
+      }
+    }
+    key[p] = keep ? (uint32_t)(old2new ? old2new[c] : c) : (uint32_t)n_cells;
+    val[p] = (int32_t)p;
+  }
+  const int here = __syncthreads_count(keep);
+  if (threadIdx.x == 0 && here) atomicAdd(n_kept, (unsigned long long)here);   // (integer: order-independent)
+}
+
 GlSampler& sampler_of(glims_ctx* h, int64_t id, const char* who) {
   if (id < 0 || id >= (int64_t)h->samplers.size() || !h->samplers[(size_t)id])
     throw glims_error(GLIMS_E_USAGE, std::string(who) + ": unknown sampler id " + std::to_string(id));
@@ -691,6 +761,44 @@ void need_memory(const char* who, size_t need) {
   if (need > fr)
     throw glims_error(GLIMS_E_HIP, std::string(who) + ": needs about " + std::to_string(need >> 20) +
                                        " MiB of device memory, " + std::to_string(fr >> 20) + " MiB are free");
+}
+
+// The transpose's lists from its sort input (key[p] = internal cell of the point's winner, n_cells for a point that enters no
+// sum; val[p] = p): the stable sort, a cell's points and chunks.  Creation (single-rank handles) and glims_sampler_resolve.
+void build_transpose(glims_ctx* h, GlSampler& s, dvec<uint32_t>& k_in, dvec<int32_t>& v_in) {
+  const int64_t n = s.n, ne = h->n_cells;
+  hipStream_t st = h->st;
+  dvec<uint32_t> k_out;
+  k_out.alloc((size_t)n);
+  s.order.alloc((size_t)n);
+  int bits = 1;
+  while (((int64_t)1 << bits) <= ne) ++bits;
+  gl_sort_pairs_u32(h, k_in.p, k_out.p, v_in.p, s.order.p, (size_t)n, bits);   // stable: point order inside a cell
+  s.cptr.alloc((size_t)ne + 1);
+  gl_offsets_of_sorted_keys(h, k_out.p, n, ne, s.cptr.p);
+  dvec<int32_t> cnt;
+  cnt.alloc((size_t)ne + 1);
+  s.chunk_ptr.alloc((size_t)ne + 1);
+  hipLaunchKernelGGL(k_chunk_count, dim3(grid_of(ne + 1)), dim3(256), 0, st, ne, s.cptr.p, cnt.p);
+  GL_CHECK_LAUNCH();
+  {
+    size_t bytes = 0;
+    GL_HIP(rocprim::exclusive_scan(nullptr, bytes, cnt.p, s.chunk_ptr.p, (int32_t)0, (size_t)ne + 1, rocprim::plus<int32_t>(), st));
+    dvec<unsigned char> tmp;
+    tmp.alloc(std::max<size_t>(bytes, 16));
+    GL_HIP(rocprim::exclusive_scan(tmp.p, bytes, cnt.p, s.chunk_ptr.p, (int32_t)0, (size_t)ne + 1, rocprim::plus<int32_t>(), st));
+    int32_t nch = 0;
+    GL_HIP(hipMemcpyAsync(&nch, s.chunk_ptr.p + ne, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    GL_HIP(hipStreamSynchronize(st));
+    s.n_chunks = nch;
+  }
+  s.chunk_cell.alloc((size_t)std::max<int64_t>(1, s.n_chunks));
+  if (ne > 0) {
+    hipLaunchKernelGGL(k_chunk_cells, dim3(grid_of(ne)), dim3(256), 0, st, ne, s.chunk_ptr.p, s.chunk_cell.p);
+    GL_CHECK_LAUNCH();
+  }
+  GL_HIP(hipStreamSynchronize(st));
+  s.have_t = true;
 }
 
 template <int D>
@@ -817,13 +925,11 @@ void create_t(glims_ctx* h, GlSampler& s, const double* xyz_host, const GridSpec
     hipLaunchKernelGGL(k_invert_cells, dim3(grid_of(ne)), dim3(256), 0, st, ne, new2old, c_old2new.p);
     GL_CHECK_LAUNCH();
   }
-  dvec<uint32_t> k_in, k_out;
+  dvec<uint32_t> k_in;
   dvec<int32_t> v_in;
   if (want_t) {
     k_in.alloc((size_t)n);
-    k_out.alloc((size_t)n);
     v_in.alloc((size_t)n);
-    s.order.alloc((size_t)n);
   }
   hipLaunchKernelGGL(k_weights<D>, dim3(grid_of(n)), dim3(256), 0, st, n, ne, s.is_grid ? nullptr : d_pts.p, gs, cell_nodes,
                      h->xyz_new.p, c_old2new.p, s.cell.p, s.node.p, s.w.p, k_in.p, v_in.p, d_found.p);
@@ -834,34 +940,7 @@ void create_t(glims_ctx* h, GlSampler& s, const double* xyz_host, const GridSpec
   s.n_found = (int64_t)nf;
   if (!want_t) return;
 
-  int bits = 1;
-  while (((int64_t)1 << bits) <= ne) ++bits;
-  gl_sort_pairs_u32(h, k_in.p, k_out.p, v_in.p, s.order.p, (size_t)n, bits);   // stable: point order inside a cell
-  s.cptr.alloc((size_t)ne + 1);
-  gl_offsets_of_sorted_keys(h, k_out.p, n, ne, s.cptr.p);
-  dvec<int32_t> cnt;
-  cnt.alloc((size_t)ne + 1);
-  s.chunk_ptr.alloc((size_t)ne + 1);
-  hipLaunchKernelGGL(k_chunk_count, dim3(grid_of(ne + 1)), dim3(256), 0, st, ne, s.cptr.p, cnt.p);
-  GL_CHECK_LAUNCH();
-  {
-    size_t bytes = 0;
-    GL_HIP(rocprim::exclusive_scan(nullptr, bytes, cnt.p, s.chunk_ptr.p, (int32_t)0, (size_t)ne + 1, rocprim::plus<int32_t>(), st));
-    dvec<unsigned char> tmp;
-    tmp.alloc(std::max<size_t>(bytes, 16));
-    GL_HIP(rocprim::exclusive_scan(tmp.p, bytes, cnt.p, s.chunk_ptr.p, (int32_t)0, (size_t)ne + 1, rocprim::plus<int32_t>(), st));
-    int32_t nch = 0;
-    GL_HIP(hipMemcpyAsync(&nch, s.chunk_ptr.p + ne, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    GL_HIP(hipStreamSynchronize(st));
-    s.n_chunks = nch;
-  }
-  s.chunk_cell.alloc((size_t)std::max<int64_t>(1, s.n_chunks));
-  if (ne > 0) {
-    hipLaunchKernelGGL(k_chunk_cells, dim3(grid_of(ne)), dim3(256), 0, st, ne, s.chunk_ptr.p, s.chunk_cell.p);
-    GL_CHECK_LAUNCH();
-  }
-  GL_HIP(hipStreamSynchronize(st));
-  s.have_t = true;
+  build_transpose(h, s, k_in, v_in);
 }
 
 template <int NV>
@@ -993,12 +1072,14 @@ void gl_sampler_apply(glims_ctx* h, int64_t id, int field, int64_t snapshot, con
 }
 
 // The two launches of P^T on device pointers: pass 1 into the sampler's chunk buffer, pass 2 row-owned into g (internal
-// numbering; overwritten, or added to with `accumulate`).  Without `accumulate` g is [n_nodes][ncomp] contiguous.
+// numbering; overwritten, or added to with `accumulate`).  Without `accumulate` g is [n_nodes][ncomp] contiguous and is zeroed
+// first on a partitioned handle: pass 2 writes the owned rows, the ghost rows hold 0.
 void gl_sampler_transpose_dev(glims_ctx* h, int64_t id, const double* r_dev, int ncomp, double* g_int_dev, int64_t ld_row,
                               int64_t ld_comp, bool accumulate) {
   GlSampler& s = sampler_of(h, id, "glims_sampler_apply_t");
-  GL_REQUIRE(h->world <= 1, "glims_sampler_apply_t: not available on a partitioned handle (the per-cell sums would need the "
-                            "globally winning cell on every rank that holds it)");
+  GL_REQUIRE(h->world <= 1 || s.resolved,
+             "glims_sampler_apply_t: not available on a partitioned handle before glims_sampler_resolve (the per-cell sums "
+             "need the globally winning cell on every rank that holds it)");
   GL_REQUIRE(ncomp >= 1 && ncomp <= GLIMS_SAMPLE_MAX_COMP,
              "glims_sampler_apply_t: ncomp = " + std::to_string(ncomp) + " outside 1 .. 8");
   if (!(s.n > 0 && s.have_t && s.n_chunks > 0)) {
@@ -1010,6 +1091,8 @@ void gl_sampler_transpose_dev(glims_ctx* h, int64_t id, const double* r_dev, int
     need_memory("glims_sampler_apply_t", nq * sizeof(double));
     s.q.alloc(nq);
   }
+  if (!accumulate && h->n_own < h->n_nodes)
+    GL_HIP(hipMemsetAsync(g_int_dev, 0, (size_t)h->n_nodes * ncomp * sizeof(double), h->st));
   if (h->nv == 3)
     hipLaunchKernelGGL(k_sample_t_cells<3>, dim3(grid_of(s.n_chunks)), dim3(256), 0, h->st, s.n_chunks, ncomp,
                        s.chunk_cell.p, s.chunk_ptr.p, s.cptr.p, s.order.p, s.w.p, r_dev, s.q.p);
@@ -1031,8 +1114,9 @@ void gl_sampler_transpose_dev(glims_ctx* h, int64_t id, const double* r_dev, int
 
 void gl_sampler_apply_t(glims_ctx* h, int64_t id, const double* r, int ncomp, double* g) {
   GlSampler& s = sampler_of(h, id, "glims_sampler_apply_t");
-  GL_REQUIRE(h->world <= 1, "glims_sampler_apply_t: not available on a partitioned handle (the per-cell sums would need the "
-                            "globally winning cell on every rank that holds it)");
+  GL_REQUIRE(h->world <= 1 || s.resolved,
+             "glims_sampler_apply_t: not available on a partitioned handle before glims_sampler_resolve (the per-cell sums "
+             "need the globally winning cell on every rank that holds it)");
   GL_REQUIRE(ncomp >= 1 && ncomp <= GLIMS_SAMPLE_MAX_COMP,
              "glims_sampler_apply_t: ncomp = " + std::to_string(ncomp) + " outside 1 .. 8");
   GL_REQUIRE(g && (r || s.n == 0), "glims_sampler_apply_t: null argument");
@@ -1059,18 +1143,148 @@ void gl_sampler_apply_t(glims_ctx* h, int64_t id, const double* r, int ncomp, do
   GL_HIP(hipStreamSynchronize(h->st));
 }
 
+// ---- glims_sampler_resolve: the globally winning cell on every rank that holds it ------------------------------------------------
+namespace {
+// One rank's verdict (GLIMS_E_USAGE with the reason); returns the sampler
+GlSampler& check_resolve(glims_ctx* h, int64_t id, const int64_t* cell_gid) {
+  const char* who = "glims_sampler_resolve";
+  GlSampler& s = sampler_of(h, id, who);
+  // (a stored term's sampler is resolved already: the call is refused, not taken for a repeated resolve)
+  for (size_t k = 0; k < h->img_terms.size(); ++k)
+    GL_REQUIRE(h->img_terms[k]->sampler != id, std::string(who) + ": sampler " + std::to_string(id) +
+                                                   " is used by stored image term " + std::to_string(k));
+  if (s.resolved) return s;
+  GL_REQUIRE(cell_gid || h->n_cells == 0, std::string(who) + ": null cell_gid");
+  for (int64_t e = 0; e < h->n_cells; ++e) {
+    GL_REQUIRE(cell_gid[e] >= 0 && (double)cell_gid[e] < GL_RESOLVE_NONE,
+               std::string(who) + ": cell_gid[" + std::to_string(e) + "] is negative or not below 2^53");
+    GL_REQUIRE(e == 0 || cell_gid[e] > cell_gid[e - 1],
+               std::string(who) + ": cell_gid is not strictly increasing at " + std::to_string(e));
+  }
+  return s;
+}
+
+template <int NV>
+void resolve_t(glims_ctx* h, GlSampler& s, const int64_t* cell_gid) {
+  const int64_t n = s.n, ne = h->n_cells;
+  const int world = h->world;
+  hipStream_t st = h->st;
+  // the key buffer [world][m] stays bounded: the points go through it in chunks of m
+  const int64_t m_max = std::max<int64_t>(1, (int64_t)(GL_RESOLVE_BYTES / (sizeof(double) * (size_t)world)));
+  const int64_t m_buf = std::min<int64_t>(n, m_max);
+  // kept: counted, order and the per-cell lists; transient: the key buffer, the cell ids, the inverse cell permutation and the
+  // sort's keys / values twice
+  need_memory("glims_sampler_resolve", (size_t)n * 5 + (size_t)ne * 12 + (size_t)m_buf * world * sizeof(double) +
+                                           (size_t)ne * 12 + (size_t)n * 16 + (16u << 20));
+  dvec<int64_t> d_gid;
+  d_gid.upload(cell_gid, (size_t)ne, st);
+  dvec<int32_t> c_old2new;
+  if (h->cell_new2old.p && ne > 0) {
+    c_old2new.alloc((size_t)ne);
+    hipLaunchKernelGGL(k_invert_cells, dim3(grid_of(ne)), dim3(256), 0, st, ne, h->cell_new2old.p, c_old2new.p);
+    GL_CHECK_LAUNCH();
+  }
+  dvec<double> buf;
+  dvec<uint32_t> k_in;
+  dvec<int32_t> v_in;
+  dvec<unsigned long long> d_kept;
+  buf.alloc((size_t)m_buf * world);
+  k_in.alloc((size_t)n);
+  v_in.alloc((size_t)n);
+  d_kept.alloc_zero(1, st);
+  s.counted.alloc((size_t)n);
+  for (int64_t p0 = 0; p0 < n; p0 += m_buf) {
+    const int64_t m = std::min<int64_t>(m_buf, n - p0);
+    GL_HIP(hipMemsetAsync(buf.p, 0, (size_t)m * world * sizeof(double), st));
+    hipLaunchKernelGGL(k_resolve_keys, dim3(grid_of(m)), dim3(256), 0, st, m, p0, s.cell.p, d_gid.p,
+                       buf.p + (size_t)h->rank * m);
+    GL_CHECK_LAUNCH();
+    gl_allreduce_bulk(h, buf.p, (size_t)m * world);   // x + 0 is exact: every rank receives every row bit for bit
+    hipLaunchKernelGGL(k_resolve_pick<NV>, dim3(grid_of(m)), dim3(256), 0, st, m, p0, world, h->rank, ne, buf.p, c_old2new.p,
+                       s.cell.p, s.node.p, s.w.p, s.counted.p, k_in.p, v_in.p, d_kept.p);
+    GL_CHECK_LAUNCH();
+  }
+  unsigned long long nk = 0;
+  GL_HIP(hipMemcpyAsync(&nk, d_kept.p, sizeof(nk), hipMemcpyDeviceToHost, st));
+  GL_HIP(hipStreamSynchronize(st));
+  s.n_found = (int64_t)nk;
+  build_transpose(h, s, k_in, v_in);
+}
+}  // namespace
+
+void gl_sampler_resolve(glims_ctx* h, int64_t id, const int64_t* cell_gid) {
+  if (h->world <= 1) {
+    (void)sampler_of(h, id, "glims_sampler_resolve");   // the sampler is global already
+    return;
+  }
+  // Collective: a rank that refused alone would leave the others waiting in the gather.  Every rank's verdict, point count and
+  // state go through one all-reduce ([3][world], zeros outside the own column) before any other collective.
+  GlSampler* s = nullptr;
+  std::string why;
+  try {
+    s = &check_resolve(h, id, cell_gid);
+  } catch (const glims_error& e) {
+    if (e.code != GLIMS_E_USAGE) throw;
+    why = e.what();
+  }
+  const size_t W = (size_t)h->world;
+  std::vector<double> flag(3 * W, 0.0);
+  flag[(size_t)h->rank] = why.empty() ? 0.0 : 1.0;
+  flag[W + (size_t)h->rank] = s ? (double)s->n : 0.0;
+  flag[2 * W + (size_t)h->rank] = s && s->resolved ? 1.0 : 0.0;
+  dvec<double> d_flag;
+  d_flag.upload(flag, h->st);
+  gl_allreduce_bulk(h, d_flag.p, flag.size());
+  GL_HIP(hipMemcpyAsync(flag.data(), d_flag.p, flag.size() * sizeof(double), hipMemcpyDeviceToHost, h->st));
+  GL_HIP(hipStreamSynchronize(h->st));
+  std::string refused;
+  for (size_t r = 0; r < W; ++r)
+    if (flag[r] != 0.0) refused += (refused.empty() ? "" : ", ") + std::to_string(r);
+  if (!why.empty()) throw glims_error(GLIMS_E_USAGE, why + " (ranks that refused: " + refused + ")");
+  if (!refused.empty())
+    throw glims_error(GLIMS_E_USAGE, "glims_sampler_resolve: refused on rank(s) " + refused + " (see their messages)");
+  for (size_t r = 1; r < W; ++r) {
+    GL_REQUIRE(flag[W + r] == flag[W], "glims_sampler_resolve: the ranks disagree on n_points (rank 0: " +
+                                           std::to_string((long long)flag[W]) + ", rank " + std::to_string(r) + ": " +
+                                           std::to_string((long long)flag[W + r]) + ")");
+    GL_REQUIRE(flag[2 * W + r] == flag[2 * W], "glims_sampler_resolve: the sampler is resolved on some ranks only");
+  }
+  if (s->resolved) return;
+  if (s->n > 0) {
+    if (h->nv == 3) resolve_t<3>(h, *s, cell_gid);
+    else resolve_t<4>(h, *s, cell_gid);
+  }
+  s->resolved = true;
+}
+
+void gl_sampler_get_counted(glims_ctx* h, int64_t id, uint8_t* counted) {
+  GlSampler& s = sampler_of(h, id, "glims_sampler_get_counted");
+  if (s.n == 0) return;
+  GL_REQUIRE(counted, "glims_sampler_get_counted: null output");
+  if (s.resolved) {
+    GL_HIP(hipMemcpyAsync(counted, s.counted.p, (size_t)s.n, hipMemcpyDeviceToHost, h->st));
+    GL_HIP(hipStreamSynchronize(h->st));
+    return;
+  }
+  std::vector<int32_t> cell((size_t)s.n);
+  GL_HIP(hipMemcpyAsync(cell.data(), s.cell.p, (size_t)s.n * sizeof(int32_t), hipMemcpyDeviceToHost, h->st));
+  GL_HIP(hipStreamSynchronize(h->st));
+  for (int64_t p = 0; p < s.n; ++p) counted[p] = cell[(size_t)p] >= 0 ? 1 : 0;
+}
+
 // ---- stored image terms ----------------------------------------------------------------------------------------------------
 void gl_image_terms_set(glims_ctx* h, int n, const glims_image_misfit* terms) {
   const char* who = "glims_adjoint_image_terms";
   GL_REQUIRE(n >= 0 && (n == 0 || terms), std::string(who) + ": bad term list");
-  GL_REQUIRE(n == 0 || h->world <= 1, std::string(who) + ": not available on a partitioned handle (glims_sampler_apply_t, "
-                                                         "the transpose the gradient needs, is refused there)");
   // every check before anything is allocated or the old list is touched
   size_t need = 0;
   for (int k = 0; k < n; ++k) {
     const glims_image_misfit& t = terms[k];
     const std::string tk = std::string(who) + ": term " + std::to_string(k);
     GlSampler& s = sampler_of(h, t.sampler, who);
+    GL_REQUIRE(h->world <= 1 || s.resolved, tk + ": not available on a partitioned handle before glims_sampler_resolve of its "
+                                                 "sampler (glims_sampler_apply_t, the transpose the gradient needs, is "
+                                                 "refused until then)");
     GL_REQUIRE(t.kind == GLIMS_MISFIT_IMG_L2 || t.kind == GLIMS_MISFIT_IMG_THRESH, tk + ": unknown kind");
     GL_REQUIRE(t.kind != GLIMS_MISFIT_IMG_THRESH || (t.smooth > 0.0 && std::isfinite(t.smooth) && std::isfinite(t.level)),
                tk + ": a threshold term needs smooth > 0 and a finite level");
@@ -1103,8 +1317,8 @@ void gl_image_terms_set(glims_ctx* h, int n, const glims_image_misfit* terms) {
       g->target.upload(t.target, (size_t)s.n, h->st);
       if (t.pweight) g->pweight.upload(t.pweight, (size_t)s.n, h->st);
       d_obs.alloc_zero(1, h->st);
-      hipLaunchKernelGGL(k_img_prepare, dim3(grid_of(s.n)), dim3(256), 0, h->st, s.n, s.cell.p, g->pweight.p, g->target.p,
-                         d_obs.p);
+      hipLaunchKernelGGL(k_img_prepare, dim3(grid_of(s.n)), dim3(256), 0, h->st, s.n, s.cell.p, g->pweight.p,
+                         s.resolved ? s.counted.p : nullptr, g->target.p, d_obs.p);
       GL_CHECK_LAUNCH();
       unsigned long long no = 0;
       GL_HIP(hipMemcpyAsync(&no, d_obs.p, sizeof(no), hipMemcpyDeviceToHost, h->st));
@@ -1146,12 +1360,13 @@ double gl_image_misfit_grad(glims_ctx* h, const GlImageTerm& t, const double* c,
   if (s.n == 0) return 0.0;
   image_staging(h, s, 1);
   const unsigned nb = grid_of(s.n);
+  const uint8_t* counted = s.resolved ? s.counted.p : nullptr;   // (partitioned handles: this rank's share of the sum)
   if (h->nv == 3)
     hipLaunchKernelGGL(k_img_misfit<3>, dim3(nb), dim3(256), 0, h->st, s.n, t.kind, t.level, t.smooth, t.weight, s.node.p,
-                       s.w.p, c, t.target.p, t.pweight.p, s.out.p, s.part.p);
+                       s.w.p, c, t.target.p, t.pweight.p, counted, s.out.p, s.part.p);
   else
     hipLaunchKernelGGL(k_img_misfit<4>, dim3(nb), dim3(256), 0, h->st, s.n, t.kind, t.level, t.smooth, t.weight, s.node.p,
-                       s.w.p, c, t.target.p, t.pweight.p, s.out.p, s.part.p);
+                       s.w.p, c, t.target.p, t.pweight.p, counted, s.out.p, s.part.p);
   GL_CHECK_LAUNCH();
   hipLaunchKernelGGL(k_img_sum, dim3(1), dim3(1024), 0, h->st, (int64_t)nb, s.part.p, s.part.p + nb);
   GL_CHECK_LAUNCH();

@@ -359,11 +359,10 @@ class DistributedHandle:
         localised here; J and the per-label arrays come back bitwise the same on every rank, dJ/dc0 all-gathered into the
         global order (as get_state does).  elastic=True (on every rank alike) appends dJ/dE and dJ/dnu."""
         loc = []
-        terms = list(terms)
-        if any(t["kind"] in ("img_l2", "img_thresh") for t in terms):
-            # (glims_adjoint_image_terms refuses partitioned handles: the sampler's transpose is single rank)
-            raise NotImplementedError("image-space misfit terms: not available on partitioned runs; use a single-GPU handle")
         for t in terms:
+            if t["kind"] in _backend._IMAGE_KINDS:
+                loc.append(self._image_term(t))
+                continue
             t = dict(t)
             bs = self.dim if t["kind"] in ("u_l2", _backend.MISFIT_U_L2) else 1
             t["target"] = self._local(t["target"], bs).reshape(-1)
@@ -381,6 +380,26 @@ class DistributedHandle:
 
     def adjoint_stats(self):
         return self.h.adjoint_stats()
+
+    # -- image-space misfit terms: the sampler is a DistributedSampler, target / pweight are in POINT order (the same on every
+    #    rank, not localised); the rank-local handle stores them against the resolved rank-local sampler
+    def _image_term(self, t):
+        sm = t["sampler"]
+        if not isinstance(sm, DistributedSampler) or sm.dh is not self:
+            raise ValueError("image term: its sampler is not a DistributedSampler of this handle")
+        # (the caller's target / pweight objects stay: their identity is what Handle._split_terms compares)
+        return dict(t, sampler=sm.local)
+
+    def set_image_terms(self, terms):
+        """Handle.set_image_terms on every rank (an empty list clears them)."""
+        self.h.set_image_terms([self._image_term(t) for t in terms])
+
+    def image_term_info(self, k):
+        """(rank-local sampler id, number of points, number of observed points summed over the ranks) of stored term k."""
+        sid, n, n_obs = self.h.image_term_info(k)
+        parts = [None] * self.world
+        self.dist.all_gather_object(parts, int(n_obs))
+        return sid, n, int(sum(parts))
 
     # -- samplers (collective: every rank passes the same points) --------------------------------------------------------
     def sampler_points(self, xyz):
@@ -441,6 +460,10 @@ class DistributedSampler:
     winners to global cell ids; per point the SMALLEST GLOBAL CELL ID over the ranks wins -- the cell a single-GPU sampler
     picks, because every cell is local to some rank and each rank has already taken the minimum over its own -- and among the
     ranks that hold that cell the smallest rank supplies the value.  Every rank returns the same bits.
+
+    The rank-local sampler is then RESOLVED (``glims_sampler_resolve``): it keeps only the points whose local winner is the
+    global winner and counts a point on the smallest rank that keeps it -- the supplier above.  That makes ``apply_t`` and the
+    image-space misfit terms available; ``apply`` returns the bits it returned before.
     """
 
     def __init__(self, dh, local):
@@ -458,6 +481,7 @@ class DistributedSampler:
         holds = (allg == win[None, :]) & (win < big)[None, :]
         self.supplier = np.where(self.cells >= 0, holds.argmax(axis=0), -1)  # smallest rank that holds the winner
         self._mine = np.flatnonzero(self.supplier == dh.rank)
+        local.resolve(dh.part.cell_ids)
 
     def apply(self, field, snapshot=None, fill=np.nan):
         """As ``Sampler.apply``; a nodal array is given in the GLOBAL node order.  The fields' ghost values must be current
@@ -478,7 +502,17 @@ class DistributedSampler:
         return out
 
     def apply_t(self, r):
-        raise NotImplementedError("apply_t: not available on partitioned runs (glims_sampler_apply_t refuses them)")
+        """P^T r: r [n_points] or [n_points, k] in point order, the same on every rank; the owned rows of every rank
+        all-gathered into the GLOBAL node order (as ``get_state`` does).  Every rank returns the same array."""
+        dh = self.dh
+        g = self.local.apply_t(r)
+        n_own = dh.part.n_own
+        parts = [None] * dh.world
+        dh.dist.all_gather_object(parts, (dh.part.global_ids[:n_own], g[:n_own]))
+        out = np.zeros((dh.n_global,) + g.shape[1:])
+        for gid, v in parts:
+            out[gid] = v
+        return out
 
     def close(self):
         self.local.close()

@@ -560,9 +560,11 @@ int glims_project(glims_ctx* h, const double* rhs, double* x, int ncomp, double 
  *   - no accepting cell: cell = -1, weights 0, sampled value = fill; the transpose ignores such points.
  * Location is an integer atomic min per (cell, point) pair, the transpose uses no float atomics: both are bitwise reproducible.
  *
- * Partitioned handles (world > 1): samplers are rank-local, NOT collective.  A rank locates in its local cells and reports its
- * local cell index; merging over the ranks is the host program's (smallest GLOBAL cell id wins).  The fields' ghost values must
- * be current (glims_step / glims_solve_mechanics leave them so).  glims_sampler_apply_t returns GLIMS_E_USAGE there. */
+ * Partitioned handles (world > 1): creation is rank-local, NOT collective.  A rank locates in its local cells and reports its
+ * local cell index; merging P f over the ranks is the host program's (smallest GLOBAL cell id wins).  The fields' ghost values
+ * must be current (glims_step / glims_solve_mechanics leave them so).  Cells on the cut exist on several ranks and a point on a
+ * face, edge or vertex is accepted by several cells, so the ranks' local winners differ: until glims_sampler_resolve (below)
+ * has been called, glims_sampler_apply_t returns GLIMS_E_USAGE there. */
 #define GLIMS_SAMPLE_EPS 1e-10   /* far above the rounding kappa(T) 2^-52 of lambda on every mesh class this library runs
                                     (kappa <= 7.6e4 measured on random-point Delaunay meshes), twelve orders below a voxel */
 #define GLIMS_FIELD_C 0            /* the current concentration */
@@ -589,6 +591,21 @@ int glims_sampler_apply(glims_ctx* h, int64_t id, int field, int64_t snapshot, c
  * sum.  Per cell, the products w r are summed in point order (long lists in fixed chunks, added in chunk order), per node
  * the cells in the order of the row's incidence list: the same bits on every call and on every handle of the same mesh. */
 int glims_sampler_apply_t(glims_ctx* h, int64_t id, const double* r, int ncomp, double* g);
+/* Collective.  Every rank passes its rank-local sampler `id` of the SAME points and cell_gid[n_cells]: the global id of each
+ * of the caller's cells, strictly increasing in the caller's cell order (partition_mesh's cell_ids).  Afterwards the sampler
+ * is RESOLVED: a point whose local winner is not the smallest global cell id over all ranks is dropped on this rank (cell -1,
+ * weights 0), the transpose's lists are built from the kept points, and a point is COUNTED on the smallest rank that keeps it.
+ * world <= 1: GLIMS_OK, nothing changes (the sampler is already global).
+ * On a resolved sampler glims_sampler_info's n_found is the number of KEPT points, glims_sampler_apply fills the dropped
+ * points with `fill`, and glims_sampler_apply_t works: r[n][ncomp] is the same on every rank, g comes back in the caller's
+ * (local) node order with the OWNED rows complete and the ghost rows 0 -- an owned node has all its cells local and every
+ * rank that holds a cell keeps the same points in it, so no exchange is needed; the bits are the same on every call.
+ * GLIMS_E_USAGE on EVERY rank, with the sampler left as it was, when any rank has an unknown id, a null or not strictly
+ * increasing cell_gid, a sampler that a stored image term uses, or another n_points (the verdicts are all-reduced before any
+ * other collective).  Resolving twice is a no-op.  The keys travel in chunks of points through a buffer of at most 64 MiB. */
+int glims_sampler_resolve(glims_ctx* h, int64_t id, const int64_t* cell_gid);
+/* counted[n_points] (0/1); world <= 1 or unresolved: 1 where found */
+int glims_sampler_get_counted(glims_ctx* h, int64_t id, uint8_t* counted);
 int glims_sampler_destroy(glims_ctx* h, int64_t id);   /* glims_destroy releases what is left */
 
 /* ---- image-space misfit terms: a voxel image or point set as an observation of the recorded trajectory --------------------
@@ -610,10 +627,17 @@ int glims_sampler_destroy(glims_ctx* h, int64_t id);   /* glims_destroy releases
  *
  * glims_adjoint_image_terms REPLACES the handle's whole list (n = 0 clears it).  GLIMS_E_USAGE, with the old list left in
  * place: unknown sampler id or kind, a threshold term with smooth <= 0, a non-finite weight, a negative or non-finite q_p, a
- * null target.  GLIMS_E_HIP (with the figures) when hipMemGetInfo says the copies do not fit.  Partitioned handles
- * (world > 1): n > 0 returns GLIMS_E_USAGE on every rank (P^T is refused there), n = 0 GLIMS_OK.  glims_sampler_destroy of a
+ * null target.  GLIMS_E_HIP (with the figures) when hipMemGetInfo says the copies do not fit.  glims_sampler_destroy of a
  * sampler that a stored term uses returns GLIMS_E_USAGE and destroys nothing; glims_destroy releases the stored terms.
- * Neither call touches the forward state, glims_stats or glims_adjoint_stats. */
+ * Neither call touches the forward state, glims_stats or glims_adjoint_stats.
+ *
+ * Partitioned handles (world > 1): n > 0 needs every term's sampler RESOLVED (glims_sampler_resolve), else GLIMS_E_USAGE;
+ * every rank passes the same list (target and pweight in point order, the same on every rank) and n = 0 is always fine.  A
+ * rank computes r at the points it KEEPS -- P^T r fills its owned rows of dJ/dc_k without an exchange -- and adds the squares
+ * of the points it COUNTS; the ranks' sums of a term are gathered by one small all-reduce and added in rank order, so J and
+ * every output have the same bits on every rank and on every call.  glims_adjoint_gradient checks, in its first all-reduce,
+ * that the ranks agree on the stored list (count and steps) and refuses on all of them otherwise.  glims_adjoint_hessian
+ * stays refused on partitioned handles. */
 #define GLIMS_MISFIT_IMG_L2     0   /* h = identity */
 #define GLIMS_MISFIT_IMG_THRESH 1   /* h(v) = 1/2 (tanh((v - level)/smooth) + 1), as GLIMS_MISFIT_C_THRESH */
 typedef struct glims_image_misfit {
@@ -625,7 +649,8 @@ typedef struct glims_image_misfit {
   const double* pweight;   /* [n_points] q_p (mask, voxel volume, ...), or NULL = 1 */
 } glims_image_misfit;
 int glims_adjoint_image_terms(glims_ctx* h, int n, const glims_image_misfit* terms);
-/* out = (sampler id, number of points, number of observed points) of stored term k */
+/* out = (sampler id, number of points, number of observed points) of stored term k; on a partitioned handle out[2] is the
+ * number of observed points THIS RANK counts (their sum over the ranks is the term's observed count) */
 int glims_adjoint_image_info(glims_ctx* h, int k, int64_t out[3]);
 
 /* ---- single-node multi-GPU (one process per GPU, RCCL over xGMI) ------------------------------------- */
