@@ -165,6 +165,7 @@ struct DevPattern {
   dvec<int32_t> celem;
   dvec<double> cw;                         // per-incidence reaction weight rho_T |T| d!/(d+3)!
   dvec<uint32_t> cs2;                      // slot word re-ordered for the hot kernels: byte 0 = the row's own (diagonal) slot, then the cell's other vertices
+  dvec<uint32_t> cs16;                     // the straight-line sweeps' 16-bit slot words (own slot dropped, 5 bits per other vertex), two records of a lane per element (k_corner_weights); empty = not valid, the sweeps read cs2
   dvec<uint32_t> cq;                       // [incidence][2] = (re-ordered slot word, weight as float bits): the quadratic-term pass's 8-byte records
   // the mass product from the sweep's incidence loop (k_corner_weights, rd_assemble_s_slice with MB = 1)
   dvec<double> mass_q;                     // per padded row: (d+3) / rho where every cell of the row has the same rho > 0, else 0
@@ -617,10 +618,11 @@ struct glims_ctx {
     int kind = 0;               // 1: from the guess, 2: from zero
     double ia = 0.0, ib = 0.0;  // the interval whose theta the sweep used
     int second_order = 0;       // how the guess was extrapolated
+    double rr = 0.0;            // kind 1: |res - A u|^2 of the guess, from the sweep's mail (the solve's count follows from it)
   };
   FusedGuess fg1;                                             // ... of the next step's first solve: valid only next to `pending`
   double fg2_red = 0.0;                                       // reduction the last second dot-free solve was asked for (0: none yet)
-  dvec<double> fg_part, fg_part2, fg_red;                     // its sums of |b - A u|^2 per slice and their reduction
+  dvec<double> fg_part;                                       // its sums of |b - A u|^2 per slice (reduced with the sweep's norms)
   dvec<double> ws_c_old_next, ws_du_next;                     // what k_ws_delta would have committed (exchanged with c_old / ws_du)
   dvec<double> U, mload, m_rhs, m_p, m_s, m_u, m_w, m_r, m_dinv, m_uD;   // mechanics, [n_nodes*dim]
   dvec<uint8_t> fixed_c, fixed_u;

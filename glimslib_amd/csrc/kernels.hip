@@ -107,6 +107,15 @@ __global__ void k_egeo(int64_t n_cells, const double* __restrict__ xyz, const in
 // mass row is then (M c)_i = q sum_T w_T (s_T + c_i), which the sweep forms from the records it walks anyway (MB = 1) --
 // and 0 for every other row (mixed or zero rho, ghost and padding rows: these keep the mass SpMV); mass_fb[s] = the
 // slice's owned rows among the latter.
+// cs16 (may be null): the slot word of the straight-line sweeps, 16 bits -- the own slot dropped (the sweep has it from diag_k),
+// the slot of the cell's m-th other vertex in bits [5 (m-1), 5 m), same order as cs2, padding records 0.  Stored in pairs: the
+// words of a lane's records 2 j and 2 j + 1 are the low and high half of ONE 32-bit element, at gl_cs16_base(cbase, s) + j 64 +
+// lane (a slice of clen records has (clen + 1) / 2 such elements per lane: each slice gets 32 elements of slack for an odd
+// clen) -- the sweep then has half as many slot loads and slot registers as with cs2, where a 16-bit load per record cost two
+// registers more than cs2 and the 32-entry instances their third wave per SIMD.  Slots of a slice of at most 32 entries fit 5
+// bits; should one not, *cs16_bad is set and the handle keeps the 32-bit words.  (Slices longer than that belong to the looped
+// kernel, which reads cs2: their cs16 words are saturated and never read.)
+__host__ __device__ __forceinline__ int64_t gl_cs16_base(int64_t cbase, int s) { return (cbase >> 1) + (int64_t)s * 32; }
 template <int D>
 __global__ __launch_bounds__(GL_WAVE) void k_corner_weights(const int64_t* __restrict__ cslice_ptr,
                                                              const int32_t* __restrict__ celem,
@@ -116,7 +125,9 @@ __global__ __launch_bounds__(GL_WAVE) void k_corner_weights(const int64_t* __res
                                                              const uint32_t* __restrict__ cslots, double* __restrict__ cw,
                                                              uint32_t* __restrict__ cs2, uint2* __restrict__ cq,
                                                              int64_t n_own, double* __restrict__ mass_q,
-                                                             int32_t* __restrict__ mass_fb) {
+                                                             int32_t* __restrict__ mass_fb,
+                                                             const int64_t* __restrict__ slice_ptr,
+                                                             uint32_t* __restrict__ cs16, int32_t* __restrict__ cs16_bad) {
   constexpr int NV = D + 1;
   constexpr double fact = D == 2 ? 1.0 / 60.0 : 1.0 / 120.0;
   // (neighbouring slices on ONE XCD: the four rows that share a cell then share an L2 -- with block b on XCD b % 8 each of them
@@ -125,6 +136,7 @@ __global__ __launch_bounds__(GL_WAVE) void k_corner_weights(const int64_t* __res
   const int64_t cbase = cslice_ptr[s];
   const int clen = (int)((cslice_ptr[s + 1] - cbase) >> 6);
   const uint32_t dk = diag_k[(int64_t)s * GL_WAVE + lane];
+  const bool straight = cs16 && ((slice_ptr[s + 1] - slice_ptr[s]) >> 6) <= 32;
   double rho0 = 0.0;
   bool seen = false, uniform = true;
   for (int q = 0; q < clen; ++q) {
@@ -140,7 +152,7 @@ __global__ __launch_bounds__(GL_WAVE) void k_corner_weights(const int64_t* __res
       seen = true;
     }
     const uint32_t sl = cslots[i];
-    uint32_t out = dk, pos = 1;
+    uint32_t out = dk, pos = 1, out16 = 0u;
     if (e < 0) {
       out = 0u;   // padding: weight 0, every slot 0
     } else {
@@ -149,12 +161,17 @@ __global__ __launch_bounds__(GL_WAVE) void k_corner_weights(const int64_t* __res
         const uint32_t k = (sl >> (8 * m)) & 255u;
         if (k != dk) {
           out |= k << (8 * pos);
+          out16 |= min(k, 31u) << (5 * (pos - 1));
+          if (straight && k > 31u) *cs16_bad = 1;
           ++pos;
         }
       }
     }
     cw[i] = w;
     cs2[i] = out;
+    if (cs16)
+      reinterpret_cast<uint16_t*>(cs16)[2 * (gl_cs16_base(cbase, s) + (int64_t)(q >> 1) * GL_WAVE + lane) + (q & 1)] =
+          (uint16_t)out16;
     // the same record for the quadratic-term pass: slot word + the weight in single precision, 8 B instead of 12 (the term it
     // feeds is itself a 1e-3 correction)
     cq[i] = make_uint2(out, __float_as_uint((float)w));
@@ -659,7 +676,15 @@ __device__ __forceinline__ double fg_first_iterate(double u, double p, double t)
   const double dn = p * t + 0.0;   // (k_cheb: the c1 term, zero in pass 1, plus the rounded product)
   return u + dn;
 }
-template <int NV, int CAP, int RB, int CIDX, class AT, int FG, int MB>
+// ST: the slot stream's word -- uint16_t (cs16: 5-bit fields of the cell's other vertices, two records of a lane per 32-bit
+// element, k_corner_weights) or uint32_t (cs2, GLIMS_FLAG_SLOT_WORDS32: bytes 1..NV-1).  The same slots either way: every
+// instance forms the same bits.  `slots`: the element that holds record j's word.
+template <class ST>
+__device__ __forceinline__ int slot_field(uint32_t slots, int j, int m) {
+  if constexpr (sizeof(ST) == 2) return (int)((slots >> (16 * (j & 1) + 5 * (m - 1))) & 31u);
+  else return (int)((slots >> (8 * m)) & 255u);
+}
+template <int NV, int CAP, int RB, int CIDX, class AT, int FG, int MB, class ST>
 __device__ __forceinline__ void rd_assemble_s_slice(
     double* lds, const SliceDesc* __restrict__ desc, int64_t n_own, const int32_t* __restrict__ cols,
     const uint16_t* __restrict__ cols16, const int32_t* __restrict__ win_base, const uint32_t* __restrict__ cs2,
@@ -676,12 +701,17 @@ __device__ __forceinline__ void rd_assemble_s_slice(
   const int s = d.s, len = d.len, clen = d.clen;
   const int64_t row = (int64_t)s * GL_WAVE + lane;
   // ---- round trip 2 (program order = issue order; the column codes last, the next round trip waits for them)
+  constexpr bool W16 = sizeof(ST) == 2;
+  static_assert(!W16 || RB % 2 == 0, "paired slot words: an even number of records per round trip");
+  constexpr int SPR = W16 ? 2 : 1, NSB = RB / SPR;   // records per slot element; slot elements per round trip
+  const int64_t sbase = W16 ? gl_cs16_base(d.cbase, s) : d.cbase;
+  const int slast = (clen - 1) / SPR;
   double wb_[RB];
-  uint32_t sb_[RB];
+  uint32_t sb_[NSB];
 #pragma unroll
   for (int j = 0; j < RB; ++j) {
     wb_[j] = GL_STREAM(cw, d.cbase, min(j, clen - 1));
-    sb_[j] = GL_STREAM(cs2, d.cbase, min(j, clen - 1));
+    if (j % SPR == 0) sb_[j / SPR] = GL_STREAM(cs2, sbase, min(j / SPR, slast));
   }
   const bool own = row < n_own;
   const int64_t rowc = own ? row : n_own - 1;
@@ -732,12 +762,12 @@ __device__ __forceinline__ void rd_assemble_s_slice(
   const double ci = cn[dk * GL_WAVE + lane];
   const double ci4 = 4.0 * ci;
   double acc_d = 0.0, macc = 0.0;
-  auto corner = [&](double w, uint32_t slots) {
+  auto corner = [&](double w, uint32_t slots, int j) {
     int k[NV];
     double cv[NV], st = ci;
 #pragma unroll
     for (int m = 1; m < NV; ++m) {
-      k[m] = (int)((slots >> (8 * m)) & 255u);
+      k[m] = slot_field<ST>(slots, j, m);
       cv[m] = cn[k[m] * GL_WAVE + lane];
     }
 #pragma unroll
@@ -752,12 +782,12 @@ __device__ __forceinline__ void rd_assemble_s_slice(
 #pragma unroll
       for (int j = 0; j < RB; ++j) {
         wb_[j] = GL_STREAM(cw, d.cbase, min(qq + j, clen - 1));
-        sb_[j] = GL_STREAM(cs2, d.cbase, min(qq + j, clen - 1));
+        if (j % SPR == 0) sb_[j / SPR] = GL_STREAM(cs2, sbase, min((qq + j) / SPR, slast));
       }
     }
 #pragma unroll
     for (int j = 0; j < RB; ++j)
-      if (qq + j < clen) corner(wb_[j], sb_[j]);   // (wave-uniform; a padding record of a shorter row has weight 0 and slots 0)
+      if (qq + j < clen) corner(wb_[j], sb_[j / SPR], j);   // (wave-uniform; a padding record of a shorter row has weight 0 and slots 0)
   }
   // (MB: the row's mass factor and load are requested half-way through phase 3 and looked at after it -- held from the top of
   //  the kernel they cost four instances their third wave per SIMD, from the start of phase 3 still one: FG = 1 has its
@@ -840,7 +870,7 @@ __device__ __forceinline__ void rd_assemble_s_slice(
   }
 }
 #undef GL_STREAM
-template <int NV, int CAP, int RB, int CIDX, class AT, int MB = 0>
+template <int NV, int CAP, int RB, int CIDX, class AT, int MB = 0, class ST = uint32_t>
 __global__ __launch_bounds__(GL_WAVE) void k_rd_assemble_s(
     const SliceDesc* __restrict__ desc, int64_t n_own, const int32_t* __restrict__ cols,
     const uint16_t* __restrict__ cols16, const int32_t* __restrict__ win_base, const uint32_t* __restrict__ cs2,
@@ -850,11 +880,11 @@ __global__ __launch_bounds__(GL_WAVE) void k_rd_assemble_s(
     const uint8_t* __restrict__ fixed, double two_dt, double* __restrict__ partials, int ldscap, int remap,
     const MassArgs ma) {
   extern __shared__ double lds[];
-  rd_assemble_s_slice<NV, CAP, RB, CIDX, AT, 0, MB>(lds, desc, n_own, cols, cols16, win_base, cs2, cw, diag_k, vS, vA, c, b, b2,
+  rd_assemble_s_slice<NV, CAP, RB, CIDX, AT, 0, MB, ST>(lds, desc, n_own, cols, cols16, win_base, cs2, cw, diag_k, vS, vA, c, b, b2,
                                                     r_out, r2_out, dinv, fixed, two_dt, partials, ldscap, remap, FgArgs{}, ma);
 }
 // ... and with the first pass of the dot-free solve that follows folded in (FG = 1, 2: see above)
-template <int NV, int CAP, int RB, int CIDX, int FG, int MB = 0>
+template <int NV, int CAP, int RB, int CIDX, int FG, int MB = 0, class ST = uint32_t>
 __global__ __launch_bounds__(GL_WAVE) void k_rd_assemble_sg(
     const SliceDesc* __restrict__ desc, int64_t n_own, const int32_t* __restrict__ cols,
     const uint16_t* __restrict__ cols16, const int32_t* __restrict__ win_base, const uint32_t* __restrict__ cs2,
@@ -864,7 +894,7 @@ __global__ __launch_bounds__(GL_WAVE) void k_rd_assemble_sg(
     const uint8_t* __restrict__ fixed, double two_dt, double* __restrict__ partials, int ldscap, int remap,
     const FgArgs fg, const MassArgs ma) {
   extern __shared__ double lds[];
-  rd_assemble_s_slice<NV, CAP, RB, CIDX, double, FG, MB>(lds, desc, n_own, cols, cols16, win_base, cs2, cw, diag_k, vS, vA, c,
+  rd_assemble_s_slice<NV, CAP, RB, CIDX, double, FG, MB, ST>(lds, desc, n_own, cols, cols16, win_base, cs2, cw, diag_k, vS, vA, c,
                                                          b, b2, r_out, r2_out, dinv, fixed, two_dt, partials, ldscap, remap, fg,
                                                          ma);
 }
@@ -1562,19 +1592,29 @@ static void assemble_static_t(glims_ctx* h, int with_mechanics) {
   }
   p.cw.alloc((size_t)p.total_corners);
   p.cs2.alloc((size_t)p.total_corners);
+  // (the 16-bit slot words: only where a class of the straight-line sweeps will read them)
+  bool straight = false;
+  for (size_t bk = 0; bk < p.bucket_cap.size(); ++bk) straight = straight || (p.bucket_count[bk] > 0 && p.bucket_cap[bk] <= 32);
+  if (straight) p.cs16.alloc_zero((size_t)(p.total_corners / 2) + (size_t)p.n_slices * 32, h->st);
+  else p.cs16.release();
+  dvec<int32_t> cs16_bad;
+  cs16_bad.alloc_zero(1, h->st);
   p.cq.alloc((size_t)2 * p.total_corners);
   p.mass_q.alloc((size_t)p.n_slices * GL_WAVE);
   dvec<int32_t> mass_fb;
   mass_fb.alloc((size_t)p.n_slices);
   hipLaunchKernelGGL(k_corner_weights<D>, dim3(p.n_slices), dim3(GL_WAVE), 0, h->st, p.cslice_ptr.p, p.celem.p, h->label.p,
                      h->evol.p, h->mat.p, p.diag_k.p, p.cslots.p, p.cw.p, p.cs2.p, (uint2*)p.cq.p, h->n_own, p.mass_q.p,
-                     mass_fb.p);
+                     mass_fb.p, p.slice_ptr.p, p.cs16.p, cs16_bad.p);
   GL_HIP(hipGetLastError());
   {
     // the slices that keep the mass SpMV (rows at an interface of two rho, or touching a tissue with rho = 0)
     std::vector<int32_t> fb((size_t)p.n_slices), list;
+    int32_t bad16 = 0;
     GL_HIP(hipMemcpyAsync(fb.data(), mass_fb.p, fb.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->st));
+    GL_HIP(hipMemcpyAsync(&bad16, cs16_bad.p, sizeof(int32_t), hipMemcpyDeviceToHost, h->st));
     GL_HIP(hipStreamSynchronize(h->st));
+    if (bad16) p.cs16.release();   // (a slot of a short slice beyond 5 bits: cannot happen; the sweeps then read cs2)
     p.mass_fb_rows = 0;
     for (int32_t sl = 0; sl < p.n_slices; ++sl)
       if (fb[(size_t)sl] > 0) {
@@ -1707,6 +1747,9 @@ void gl_rd_assemble(glims_ctx* h, const double* c, const double* b, const double
   ensure_classes(h);
   const DevPattern& p = h->pat;
   const uint8_t* fx = h->have_fixed_c ? h->fixed_c.p : nullptr;
+  // the straight-line sweeps' slot stream: 16-bit words unless the handle has none or GLIMS_FLAG_SLOT_WORDS32 asks for cs2
+  const bool w16 = p.cs16.p != nullptr && (h->opt.flags & GLIMS_FLAG_SLOT_WORDS32) == 0;
+  if (w16) h->stats.rd_slot16_sweeps++;   // (cs16 exists only where a straight-line class reads it)
   MassArgs ma{nullptr, nullptr, nullptr};
   if (mass) {
     GL_REQUIRE(gl_rd_fusable(h) && part == GL_PART_ALL && mass->bw == (b2 ? b2 : b),
@@ -1726,24 +1769,30 @@ void gl_rd_assemble(glims_ctx* h, const double* c, const double* b, const double
     fg.c2 = fused->c2;
     // (MB = 1 only with two right-hand sides: the sweeps that carry a guess pass and define a b are the speculative ones)
     GL_REQUIRE(!mass || b2, "fused guess pass with the mass product: two right-hand sides only");
-#define GL_RDG4(NV, CAP, RB, CIDX, FG, MB)                                                                          \
+#define GL_RDG5(NV, CAP, RB, CIDX, FG, MB, ST, SPTR)                                                                \
   do {                                                                                                             \
-    set_lds(k_rd_assemble_sg<NV, CAP, RB, CIDX, FG, MB>, lds);                                                     \
-    hipLaunchKernelGGL((k_rd_assemble_sg<NV, CAP, RB, CIDX, FG, MB>), dim3(cl.grid), dim3(GL_WAVE), lds, h->st,     \
-                       cl.desc, h->n_own, p.cols.p, p.cols16.p, p.win_base.p, p.cs2.p, p.cw.p, p.diag_k.p, h->vS.p, \
+    set_lds(k_rd_assemble_sg<NV, CAP, RB, CIDX, FG, MB, ST>, lds);                                                 \
+    hipLaunchKernelGGL((k_rd_assemble_sg<NV, CAP, RB, CIDX, FG, MB, ST>), dim3(cl.grid), dim3(GL_WAVE), lds, h->st, \
+                       cl.desc, h->n_own, p.cols.p, p.cols16.p, p.win_base.p, SPTR, p.cw.p, p.diag_k.p, h->vS.p,    \
                        h->vA.p, c, b, b2, r_out, r2_out, h->dinv.p, fx, 2.0 * h->opt.dt, partials, cap,             \
                        GL_XCD_CHUNK, fg, ma);                                                                      \
   } while (0)
+#define GL_RDG4(NV, CAP, RB32, RB16, CIDX, FG, MB)                                                                  \
+  do {                                                                                                             \
+    if (w16) GL_RDG5(NV, CAP, RB16, CIDX, FG, MB, uint16_t, p.cs16.p);                                             \
+    else GL_RDG5(NV, CAP, RB32, CIDX, FG, MB, uint32_t, p.cs2.p);                                                  \
+  } while (0)
   // (records of the first round trip, rows of at most 16 entries: 26 = 2 x 16 - 6; one fewer where the guess's gather, 32-bit
   //  columns and the mass accumulator meet -- 170 registers with 26, two waves per SIMD instead of three; a row of 16 entries
-  //  then fetches its last record in a second round trip, the same terms in the same order)
+  //  then fetches its last record in a second round trip, the same terms in the same order.  With the paired 16-bit slot
+  //  words a round trip holds half as many slot registers: 26 records there too)
 #define GL_RDG_RB16(NV, CIDX, FG, MB) ((NV) == 4 && (CIDX) == 0 && (FG) == 1 && (MB) == 1 ? 25 : 26)
 #define GL_RDG3(NV, CIDX, FG, MB)                                                                                   \
   do {                                                                                                             \
-    if (cap <= 16) GL_RDG4(NV, 16, GL_RDG_RB16(NV, CIDX, FG, MB), CIDX, FG, MB);                                   \
-    else if (cap <= 20) GL_RDG4(NV, 20, 24, CIDX, FG, MB);                                                         \
-    else if (cap <= 24) GL_RDG4(NV, 24, 24, CIDX, FG, MB);                                                         \
-    else GL_RDG4(NV, 32, 24, CIDX, FG, MB);                                                                        \
+    if (cap <= 16) GL_RDG4(NV, 16, GL_RDG_RB16(NV, CIDX, FG, MB), 26, CIDX, FG, MB);                               \
+    else if (cap <= 20) GL_RDG4(NV, 20, 24, 24, CIDX, FG, MB);                                                     \
+    else if (cap <= 24) GL_RDG4(NV, 24, 24, 24, CIDX, FG, MB);                                                     \
+    else GL_RDG4(NV, 32, 24, 24, CIDX, FG, MB);                                                                    \
   } while (0)
 #define GL_RDG2(NV, CIDX)                                                                                           \
   do {                                                                                                             \
@@ -1767,6 +1816,7 @@ void gl_rd_assemble(glims_ctx* h, const double* c, const double* b, const double
 #undef GL_RDG_RB16
 #undef GL_RDG3
 #undef GL_RDG4
+#undef GL_RDG5
     GL_HIP(hipGetLastError());
     return;
   }
@@ -1778,21 +1828,24 @@ void gl_rd_assemble(glims_ctx* h, const double* c, const double* b, const double
                        p.cs2.p, p.cw.p, p.diag_k.p, h->vS.p, APTR, c, b, b2, r_out, r2_out, h->dinv.p, fx,           \
                        2.0 * h->opt.dt, partials, cap, GL_XCD_CHUNK);                                              \
   } while (0)
+#define GL_RDS4(NV, CAP, RB, CIDX, AT, APTR, MB, ST, SPTR)                                                          \
+  do {                                                                                                             \
+    set_lds(k_rd_assemble_s<NV, CAP, RB, CIDX, AT, MB, ST>, lds);                                                  \
+    hipLaunchKernelGGL((k_rd_assemble_s<NV, CAP, RB, CIDX, AT, MB, ST>), dim3(cl.grid), dim3(GL_WAVE), lds, h->st,  \
+                       cl.desc, h->n_own, p.cols.p, p.cols16.p, p.win_base.p, SPTR, p.cw.p, p.diag_k.p, h->vS.p,    \
+                       APTR, c, b, b2, r_out, r2_out, h->dinv.p, fx, 2.0 * h->opt.dt, partials, cap, GL_XCD_CHUNK,  \
+                       ma);                                                                                        \
+  } while (0)
 #define GL_RDS3(NV, CAP, RB, CIDX, AT, APTR)                                                                        \
   do {                                                                                                             \
-    set_lds(k_rd_assemble_s<NV, CAP, RB, CIDX, AT>, lds);                                                          \
-    hipLaunchKernelGGL((k_rd_assemble_s<NV, CAP, RB, CIDX, AT>), dim3(cl.grid), dim3(GL_WAVE), lds, h->st, cl.desc,  \
-                       h->n_own, p.cols.p, p.cols16.p, p.win_base.p, p.cs2.p, p.cw.p, p.diag_k.p, h->vS.p, APTR, c,  \
-                       b, b2, r_out, r2_out, h->dinv.p, fx, 2.0 * h->opt.dt, partials, cap, GL_XCD_CHUNK, ma);      \
+    if (w16) GL_RDS4(NV, CAP, RB, CIDX, AT, APTR, 0, uint16_t, p.cs16.p);                                          \
+    else GL_RDS4(NV, CAP, RB, CIDX, AT, APTR, 0, uint32_t, p.cs2.p);                                               \
   } while (0)
   // (MB = 1: fp64 Jacobian, straight-line classes only -- gl_rd_fusable, required above)
 #define GL_RDM3(NV, CAP, RB, CIDX)                                                                                  \
   do {                                                                                                             \
-    set_lds(k_rd_assemble_s<NV, CAP, RB, CIDX, double, 1>, lds);                                                   \
-    hipLaunchKernelGGL((k_rd_assemble_s<NV, CAP, RB, CIDX, double, 1>), dim3(cl.grid), dim3(GL_WAVE), lds, h->st,   \
-                       cl.desc, h->n_own, p.cols.p, p.cols16.p, p.win_base.p, p.cs2.p, p.cw.p, p.diag_k.p, h->vS.p, \
-                       h->vA.p, c, b, b2, r_out, r2_out, h->dinv.p, fx, 2.0 * h->opt.dt, partials, cap,             \
-                       GL_XCD_CHUNK, ma);                                                                          \
+    if (w16) GL_RDS4(NV, CAP, RB, CIDX, double, h->vA.p, 1, uint16_t, p.cs16.p);                                   \
+    else GL_RDS4(NV, CAP, RB, CIDX, double, h->vA.p, 1, uint32_t, p.cs2.p);                                        \
   } while (0)
 #define GL_RDM2(NV, CIDX)                                                                                           \
   do {                                                                                                             \
@@ -1835,6 +1888,7 @@ void gl_rd_assemble(glims_ctx* h, const double* c, const double* b, const double
 #undef GL_RDV
 #undef GL_RDS2
 #undef GL_RDS3
+#undef GL_RDS4
 #undef GL_RD
   GL_HIP(hipGetLastError());
 }

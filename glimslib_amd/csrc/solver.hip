@@ -264,15 +264,23 @@ __global__ __launch_bounds__(256) void k_cg_update(int64_t n_own, const double* 
 
 // red[q] = sum_b partials[b*nq + q] in a fixed order -> bitwise reproducible.  Two stages: `nb1` blocks each sum a
 // contiguous range into tmp[blk*nq + q], then one block sums tmp (a single block over ~1e5 partials took 98 us).
+// T3 (nq = 3): the partials are [n][2] and the third sum's live in an array of their own, third[n] (the fused guess pass's
+// |res - A u|^2 per slice next to the sweep's two residual norms): one chain of launches for the three, every sum in the order
+// it has when reduced alone -- the order depends on the element index only, not on nq.
+template <bool T3 = false>
 __global__ __launch_bounds__(256) void k_reduce_stage1(int n, int nq, int per_block,
                                                         const double* __restrict__ partials,
-                                                        double* __restrict__ tmp, const int* __restrict__ done) {
+                                                        double* __restrict__ tmp, const int* __restrict__ done,
+                                                        const double* __restrict__ third = nullptr) {
   if (done && *done) return;
   __shared__ double sm[4];
   const int lo = blockIdx.x * per_block, hi = min(n, lo + per_block);
   for (int q = 0; q < nq; ++q) {
     double v = 0.0;
-    for (int i = lo + threadIdx.x; i < hi; i += 256) v += partials[(size_t)i * nq + q];
+    if (T3 && q == 2)
+      for (int i = lo + threadIdx.x; i < hi; i += 256) v += third[i];
+    else
+      for (int i = lo + threadIdx.x; i < hi; i += 256) v += partials[(size_t)i * (T3 ? 2 : nq) + q];
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
     if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
@@ -284,15 +292,34 @@ __global__ __launch_bounds__(256) void k_reduce_stage1(int n, int nq, int per_bl
 
 // final stage: ONE block of 1024 threads, every thread keeps nq (<= 3) independent accumulators so that its loads
 // are all in flight together; fixed summation order (thread-strided, then a fixed tree) -> reproducible.
+template <bool T3 = false>
 __global__ __launch_bounds__(1024) void k_reduce(int n, int nq, const double* __restrict__ partials,
                                                   double* __restrict__ red, const int* __restrict__ done,
-                                                  const NodeMail nm) {
+                                                  const NodeMail nm, const double* __restrict__ third = nullptr) {
   if (done && *done) return;
   __shared__ double sm[16][3];
   double v[3] = {0.0, 0.0, 0.0};
   const int total = n * nq;   // partials are [n][nq]: walk the flat array with a stride that is a multiple of nq
   const int stride = 1024 * nq;
-  {
+  if constexpr (T3) {
+    // (partials [n][2] and third[n], see k_reduce_stage1: the same four chains per thread over the element index)
+    double a[4][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+    int e = threadIdx.x;
+    for (; e + 3 * 1024 < n; e += 4 * 1024)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        a[c][0] += partials[(size_t)(e + c * 1024) * 2];
+        a[c][1] += partials[(size_t)(e + c * 1024) * 2 + 1];
+        a[c][2] += third[e + c * 1024];
+      }
+    for (; e < n; e += 1024) {
+      a[0][0] += partials[(size_t)e * 2];
+      a[0][1] += partials[(size_t)e * 2 + 1];
+      a[0][2] += third[e];
+    }
+#pragma unroll
+    for (int q = 0; q < 3; ++q) v[q] = (a[0][q] + a[1][q]) + (a[2][q] + a[3][q]);
+  } else {
     // four independent strided chains per thread (the loop is latency-bound: 12 us for 16 k pairs with one chain)
     double a[4][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
     int i = threadIdx.x * nq;
@@ -788,25 +815,28 @@ void gl_comm_destroy(glims_ctx* h) {
 static void reduce_partials(glims_ctx* h, int n, int nq, const int* done) {
   if (n > 16384) {
     const int per_block = 1024, nb1 = (n + per_block - 1) / per_block;
-    hipLaunchKernelGGL(k_reduce_stage1, dim3(nb1), dim3(256), 0, h->st, n, nq, per_block, h->partials.p,
-                       h->partials2.p, done);
-    hipLaunchKernelGGL(k_reduce, dim3(1), dim3(1024), 0, h->st, nb1, nq, h->partials2.p, h->red.p, done, h->nm);
+    hipLaunchKernelGGL(k_reduce_stage1<false>, dim3(nb1), dim3(256), 0, h->st, n, nq, per_block, h->partials.p,
+                       h->partials2.p, done, (const double*)nullptr);
+    hipLaunchKernelGGL(k_reduce<false>, dim3(1), dim3(1024), 0, h->st, nb1, nq, h->partials2.p, h->red.p, done, h->nm,
+                       (const double*)nullptr);
   } else {
-    hipLaunchKernelGGL(k_reduce, dim3(1), dim3(1024), 0, h->st, n, nq, h->partials.p, h->red.p, done, h->nm);
+    hipLaunchKernelGGL(k_reduce<false>, dim3(1), dim3(1024), 0, h->st, n, nq, h->partials.p, h->red.p, done, h->nm,
+                       (const double*)nullptr);
   }
   GL_HIP(hipGetLastError());
 }
-
-// |res - A u|^2 of a guess pass that a sweep carried (its per-slice sums live in a buffer of their own, so the reductions
-// enqueued between the sweep and the solve leave them alone): same two stages, into fg_red[0]
-static void reduce_fused(glims_ctx* h, int n) {
+// ... of a sweep that carried a guess pass: red[0..1] from the pairs in partials, red[2] = |res - A u|^2 from the per-slice sums
+// in `third` -- the same launches, and red[2] has the bits reduce_fused gives
+static void reduce_partials3(glims_ctx* h, int n, const double* third) {
   if (n > 16384) {
     const int per_block = 1024, nb1 = (n + per_block - 1) / per_block;
-    hipLaunchKernelGGL(k_reduce_stage1, dim3(nb1), dim3(256), 0, h->st, n, 1, per_block, h->fg_part.p, h->fg_part2.p,
-                       (const int*)nullptr);
-    hipLaunchKernelGGL(k_reduce, dim3(1), dim3(1024), 0, h->st, nb1, 1, h->fg_part2.p, h->fg_red.p, (const int*)nullptr, h->nm);
+    hipLaunchKernelGGL(k_reduce_stage1<true>, dim3(nb1), dim3(256), 0, h->st, n, 3, per_block, h->partials.p,
+                       h->partials2.p, (const int*)nullptr, third);
+    hipLaunchKernelGGL(k_reduce<false>, dim3(1), dim3(1024), 0, h->st, nb1, 3, h->partials2.p, h->red.p,
+                       (const int*)nullptr, h->nm, (const double*)nullptr);
   } else {
-    hipLaunchKernelGGL(k_reduce, dim3(1), dim3(1024), 0, h->st, n, 1, h->fg_part.p, h->fg_red.p, (const int*)nullptr, h->nm);
+    hipLaunchKernelGGL(k_reduce<true>, dim3(1), dim3(1024), 0, h->st, n, 3, h->partials.p, h->red.p, (const int*)nullptr,
+                       h->nm, third);
   }
   GL_HIP(hipGetLastError());
 }
@@ -867,8 +897,8 @@ double gl_dot(glims_ctx* h, const double* a, const double* b, int64_t n, bool gl
     reduce_partials(h, (int)gd, 1, nullptr);
     allreduce_sum(h, h->red.p, 1);
   } else {   // rank-local value: no node-mailbox / RCCL step in the final block
-    hipLaunchKernelGGL(k_reduce, dim3(1), dim3(1024), 0, h->st, (int)gd, 1, h->partials.p, h->red.p, (const int*)nullptr,
-                       NodeMail());
+    hipLaunchKernelGGL(k_reduce<false>, dim3(1), dim3(1024), 0, h->st, (int)gd, 1, h->partials.p, h->red.p,
+                       (const int*)nullptr, NodeMail(), (const double*)nullptr);
     GL_HIP(hipGetLastError());
   }
   return read_red0(h);
@@ -1030,21 +1060,29 @@ __global__ __launch_bounds__(256) void k_cheb_start(int64_t n_own, const double*
 // the smallest m with 1 / T_m(sigma) <= tol / |t|, i.e. m = ceil(acosh(|t| / tol) / acosh(sigma)), at least m_min, at most m_max;
 // m_done if the guess alone meets the tolerance.  Left in plan[0] for the launches and in the Krylov info slot for the host's
 // statistics (travels with the next decision mail).
-__global__ void k_cheb_plan(const double* __restrict__ red, double tol2, double inv_acosh_sigma, int m_min, int m_max,
-                            int m_done, int* __restrict__ plan, double* __restrict__ info) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  const double rr = red[0];
-  int m = m_max;
-  if (isfinite(rr)) {
+// The count itself, one source for the device (k_cheb_plan) and for the host -- which decides where the norm has reached it
+// with a sweep's mail (cheb_solve, folded): the same expression, so the same count wherever the host's log / sqrt and the
+// device's agree in the last place at an integer boundary of the count.
+__host__ __device__ inline int gl_cheb_count(double rr, double tol2, double inv_acosh_sigma, int m_min, int m_max, int m_done) {
+  int m = m_max;   // (a norm that is not finite: every launch the bound allows; the Newton residual decides)
+  if (__builtin_isfinite(rr)) {
     // (m_done: the count when the tolerance is met already -- 0, or 2 for a solve whose first pass has run: the pass that adds
     //  the correction to the iterate is still to come)
     if (rr <= tol2) m = m_done;
     else {
       const double q = sqrt(rr / tol2);
       m = (int)ceil(log(q + sqrt(q * q - 1.0)) * inv_acosh_sigma);
-      m = max(m_min, min(m_max, m));
+      m = m > m_max ? m_max : m;
+      m = m < m_min ? m_min : m;
     }
   }
+  return m;
+}
+__global__ void k_cheb_plan(const double* __restrict__ red, double tol2, double inv_acosh_sigma, int m_min, int m_max,
+                            int m_done, int* __restrict__ plan, double* __restrict__ info) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const double rr = red[0];
+  const int m = gl_cheb_count(rr, tol2, inv_acosh_sigma, m_min, m_max, m_done);
   plan[0] = m;
   info[0] = (double)m;
   info[1] = rr;
@@ -1421,6 +1459,8 @@ static const int GL_CHEB_LONG = 48;   // solves that would need more passes than
 struct ChebRun {
   int passes = 0;        // operator passes enqueued that can run (host-known count), or the upper bound when planned
   bool planned = false;  // the count is computed on the device; it arrives in the Krylov info of the next decision mail
+  bool host_count = false;   // a warm-started solve whose count the host chose (folded: the norm came with the sweep's mail) ...
+  int m = 0, bound = 0;      // ... that count, and the passes its bound would have allowed (what `passes` is when planned)
 };
 
 // Solves A y = b (b = v.r, the Newton right-hand side at v.x) for the correction y of v.x: iterates in v.p / v.s (two buffers
@@ -1430,10 +1470,12 @@ struct ChebRun {
 // warm_u: the solve starts from this guess (the predicted increment, ghosts valid; may be ylast) instead of zero; the iteration count
 // is then chosen on the device from |b - A u| (r_bound bounds the launches; hint_slot: which solve of the step), otherwise from r_norm = |b| here.
 // folded: the sweep that assembled this system has run the solve's first pass already (k_rd_assemble_sg, with this interval's
-// theta: the caller has checked that) -- y_1 is in v.p, and for a warm-started solve the sums of |b - A u|^2 are in fg_part; the
-// solve starts at pass 2 and every count stays what it would have been.
+// theta: the caller has checked that) -- y_1 is in v.p, and for a warm-started solve the sums of |b - A u|^2 came with the sweep's mail (folded_rr); the
+// solve starts at pass 2 and every count stays what it would have been.  folded_rr: a folded warm-started solve's |b - A u|^2,
+// which reached the host with the sweep's two norms -- the host then chooses the count (gl_cheb_count, the bound as ever) and
+// enqueues exactly the passes that run: no second reduction, no plan kernel, no launch that returns at once.
 static ChebRun cheb_solve(glims_ctx* h, const CgVecs& v, double tol_abs, double r_norm, double r_bound, bool want_res,
-                          const double* warm_u, double* ylast, int hint_slot, bool folded = false) {
+                          const double* warm_u, double* ylast, int hint_slot, bool folded = false, double folded_rr = 0.0) {
   const DevPattern& p = h->pat;
   const bool split = h->world > 1 && h->n_peers > 0;
   const int64_t n = h->n_own;
@@ -1449,10 +1491,11 @@ static ChebRun cheb_solve(glims_ctx* h, const CgVecs& v, double tol_abs, double 
     pm.sendbuf = h->sendbuf.p;
   }
   ChebRun run;
-  run.planned = warm_u != nullptr;   // (then |r| on entry of the Chebyshev recurrence is only known to the device)
+  run.host_count = warm_u != nullptr && folded;
+  run.planned = warm_u != nullptr && !folded;   // (then |r| on entry of the Chebyshev recurrence is only known to the device)
   const int m_min = want_res ? 1 : 2;
   int m = 0;
-  if (run.planned) {
+  if (warm_u) {
     // upper bound of the launches: from the residual before the warm start -- or, once known, what the device chose last time
     // + 2 (like the PCG solves' hints: the launches beyond the device's count return at once, but each still costs a dispatch
     // and, in a partitioned run, a halo exchange); a count clipped by the bound is a slightly weaker Newton step
@@ -1467,21 +1510,22 @@ static ChebRun cheb_solve(glims_ctx* h, const CgVecs& v, double tol_abs, double 
   // square, from which the device chooses the count; no separate SpMV, no start kernel.
   const int shift = warm_u ? 1 : 0;
   double *d_in = v.p, *d_out = v.s;
-  if (warm_u) {
-    const double* rr_dev = h->red.p;
-    if (folded) {
-      reduce_fused(h, gl_rd_grid(h));
-      rr_dev = h->fg_red.p;
-    } else {
-      hipEvent_t* ev = h->timing(glims_ctx::TK_CHEB) ? h->pair(glims_ctx::TK_CHEB) : nullptr;
-      // (one launch over all slices: the ghosts of u are current, nothing to exchange; the payload of d_1 is packed for pass 2)
-      gl_launch_cheb(h, h->st, p.n_slices, nullptr, v.vals, v.vals32, warm_u, v.p, v.r, v.dinv, nullptr,
-                     ylast, v.x, v.fixed, 0.0, 1.0 / rec.theta, 1, GL_CHEB_MAX + 8, nullptr, want_res ? 1 : 0, pm,
-                     ev ? ev[0] : nullptr, ev ? ev[1] : nullptr, shift, h->partials.p);
-      reduce_partials(h, gl_spmv_grid(p.n_slices), 1, nullptr);
-      allreduce_sum(h, h->red.p, 1);
-    }
-    hipLaunchKernelGGL(k_cheb_plan, dim3(1), dim3(1), 0, h->st, rr_dev, tol_abs * tol_abs,
+  if (run.host_count) {
+    GL_REQUIRE(!split, "a folded guess pass on a partitioned handle: its norm is a rank-local sum");
+    const int m_bound = std::max(2, m);
+    run.bound = (want_res ? m_bound : m_bound - 1) + shift;
+    m = gl_cheb_count(folded_rr, tol_abs * tol_abs, rec.inv_acosh_sigma(), 2, m_bound, 2);
+    run.m = m;
+    h->stats.cheb_host_counts++;
+  } else if (warm_u) {
+    hipEvent_t* ev = h->timing(glims_ctx::TK_CHEB) ? h->pair(glims_ctx::TK_CHEB) : nullptr;
+    // (one launch over all slices: the ghosts of u are current, nothing to exchange; the payload of d_1 is packed for pass 2)
+    gl_launch_cheb(h, h->st, p.n_slices, nullptr, v.vals, v.vals32, warm_u, v.p, v.r, v.dinv, nullptr,
+                   ylast, v.x, v.fixed, 0.0, 1.0 / rec.theta, 1, GL_CHEB_MAX + 8, nullptr, want_res ? 1 : 0, pm,
+                   ev ? ev[0] : nullptr, ev ? ev[1] : nullptr, shift, h->partials.p);
+    reduce_partials(h, gl_spmv_grid(p.n_slices), 1, nullptr);
+    allreduce_sum(h, h->red.p, 1);
+    hipLaunchKernelGGL(k_cheb_plan, dim3(1), dim3(1), 0, h->st, (const double*)h->red.p, tol_abs * tol_abs,
                        rec.inv_acosh_sigma(), 2, std::max(2, m), 2, h->cheb_plan.p, info_dev);
     GL_HIP(hipGetLastError());
     m = std::max(2, m);
@@ -1519,6 +1563,7 @@ static ChebRun cheb_solve(glims_ctx* h, const CgVecs& v, double tol_abs, double 
   }
   h->stats.cheb_solves++;
   if (folded) h->stats.cheb_fused_passes++;
+  if (folded && !warm_u) h->stats.cheb_fused_zero_starts++;
   return run;
 }
 
@@ -1538,7 +1583,7 @@ static ChebRun cheb_solve(glims_ctx* h, const CgVecs& v, double tol_abs, double 
 // path comes from the same formula either way, so a step gives the same bits whether or not a speculative sweep prepared it.
 static void rd_sweep(glims_ctx* h, const double* b2, double* norms /*[2]*/, Mail* krylov = nullptr,
                      bool exchange_c = false, bool mass_for_b2 = false, const GlFusedSweep* fused = nullptr,
-                     bool mass_for_b = false) {
+                     bool mass_for_b = false, double* fused_rr = nullptr) {
   const DevPattern& p = h->pat;
   const double* load = h->have_load_rd ? h->load_rd.p : nullptr;
   const bool split = exchange_c && h->world > 1 && h->n_peers > 0;
@@ -1574,11 +1619,15 @@ static void rd_sweep(glims_ctx* h, const double* b2, double* norms /*[2]*/, Mail
                      nullptr, 0, nullptr);
     gl_rd_assemble(h, h->c.p, h->b.p, b2, h->cg_r.p, h->cg_r2.p, h->partials.p, GL_PART_BOUNDARY);
   }
-  reduce_partials(h, gl_rd_grid(h), 2, nullptr);
-  allreduce_sum(h, h->red.p, 2);
-  const Mail m = fetch(h, 2, krylov != nullptr);
+  // (a guess pass from a guess: its |res - A u|^2 travels with the two norms -- one reduce chain, one mail)
+  const bool three = !split && fused && fused->kind == 1;
+  if (three) reduce_partials3(h, gl_rd_grid(h), fused->part);
+  else reduce_partials(h, gl_rd_grid(h), 2, nullptr);
+  allreduce_sum(h, h->red.p, three ? 3 : 2);
+  const Mail m = fetch(h, three ? 3 : 2, krylov != nullptr);
   norms[0] = std::sqrt(m.red[0]);
   norms[1] = std::sqrt(m.red[1]);
+  if (fused_rr) *fused_rr = three ? m.red[2] : 0.0;
   if (krylov) *krylov = m;
   h->stats.rd_assemblies++;
 }
@@ -2048,10 +2097,18 @@ int gl_step(glims_ctx* h, int n_steps) {
             used_warm2 = warm2;
           }
           crun = cheb_solve(h, v, tol_lin, nr, nr, cheap_next, (ws_fused || warm2) ? h->cg_u.p : (const double*)nullptr,
-                            last_ylast, second ? 1 : 0, take_folded);
+                            last_ylast, second ? 1 : 0, take_folded, second ? fg2.rr : fg1.rr);
         }
         deferred = crun.planned;
-        if (!deferred && !cheb_idle) {
+        if (crun.host_count) {
+          // (the bookkeeping of a device-side count, fed at once instead of from the next mail -- see `deferred && use_cheb` below)
+          cb.m_hint[second ? 1 : 0] = std::max(1, crun.m);
+          if (it == 0) regime_now = crun.m + 100 * nw_mode;
+          if (second && crun.m >= crun.bound) d2_written = false;
+          h->stats.cg_its += crun.passes;
+          h->stats.cheb_its += crun.passes;
+          h->stats.last_cg_res = tol_lin;
+        } else if (!deferred && !cheb_idle) {
           h->stats.cg_its += crun.passes;
           h->stats.cheb_its += crun.passes;
           h->stats.last_cg_res = tol_lin;
@@ -2144,8 +2201,6 @@ int gl_step(glims_ctx* h, int n_steps) {
         if (fuse_on && use_cheb) {
           const int ns = gl_rd_grid(h);
           h->fg_part.alloc((size_t)ns);
-          h->fg_part2.alloc((size_t)(ns + 1023) / 1024);
-          h->fg_red.alloc(1);
           if (speculate && GL_FUSE_FIRST) {
             // (not into a learning step, nor where the midpoint correction changes the right-hand side after the sweep)
             if (cb.age + 1 >= 32) {
@@ -2188,7 +2243,7 @@ int gl_step(glims_ctx* h, int n_steps) {
           }
         }
         rd_sweep(h, speculate ? h->b2.p : nullptr, norms, deferred ? &km : nullptr, /*exchange_c=*/true,
-                 /*mass_for_b2=*/speculate, fgn.valid ? &fs : nullptr);
+                 /*mass_for_b2=*/speculate, fgn.valid ? &fs : nullptr, /*mass_for_b=*/false, &fgn.rr);
         if (fgn.valid && !speculate) fg2 = fgn;
         if (fgn.valid && speculate) h->fg1 = fgn;   // (kept only if the sweep confirms the step, see below)
         base_is_current = true;   // a fresh Jacobian: A_0 = A(c) from here on
@@ -2218,10 +2273,13 @@ int gl_step(glims_ctx* h, int n_steps) {
         if (km.done == 3) h->cg_hint[slot] = 0;   // breakdown: next time take the polled path
       }
       nr = norms[0];
-      if (use_cheb && getenv("GLIMS_VERBOSE_CHEB"))
+      if (use_cheb && getenv("GLIMS_VERBOSE_CHEB")) {
+        const char* count_by = crun.planned ? "planned" : (crun.host_count ? "host-m" : "host");
+        const double m_shown = crun.planned ? km.info[0] : (crun.host_count ? (double)crun.m : -1.0);
         fprintf(stderr, "  cheb: step %lld it %d  %.3e -> %.3e  tol_lin %.3e target %.3e  %s passes %d (m_dev %g) %s\n",
-                (long long)h->stats.steps, it, nr_before, nr, tol_lin, target, crun.planned ? "planned" : "host", crun.passes,
-                crun.planned ? km.info[0] : -1.0, cheap ? "cheap" : (speculate ? "sweep+spec" : "sweep"));
+                (long long)h->stats.steps, it, nr_before, nr, tol_lin, target, count_by, crun.passes, m_shown,
+                cheap ? "cheap" : (speculate ? "sweep+spec" : "sweep"));
+      }
       if (use_cheb && !cheb_idle && !(std::isfinite(nr) && (nr <= 0.5 * nr_before || nr <= target))) {
         // The Newton residual did not contract: part of the right-hand side lies outside the interval (the Chebyshev polynomial
         // grows there).  Take the correction back (it is still in cheb_delta), drop the interval -- this step's remaining
@@ -2681,7 +2739,8 @@ int gl_mailbox_selftest(glims_ctx* h) {
   GL_HIP(hipMemcpyAsync(h->partials.p, v, sizeof(v), hipMemcpyHostToDevice, h->st));
   NodeMail nm = h->nm;
   nm.timeout_ticks = 5ll * 100000000ll;
-  hipLaunchKernelGGL(k_reduce, dim3(1), dim3(1024), 0, h->st, 1, 3, h->partials.p, h->red.p, (const int*)nullptr, nm);
+  hipLaunchKernelGGL(k_reduce<false>, dim3(1), dim3(1024), 0, h->st, 1, 3, h->partials.p, h->red.p, (const int*)nullptr, nm,
+                     (const double*)nullptr);
   GL_HIP(hipGetLastError());
   double out[3] = {0.0, 0.0, 0.0};
   int err = 0;

@@ -220,6 +220,11 @@ typedef struct glims_options {
                                            glims_stats.rd_mass_in_sweep counts the sweeps.  A step whose first b is formed
                                            before new Dirichlet values or the extrapolated guess enter the iterate keeps the
                                            SpMV for that b.  Set: the mass SpMV everywhere (A/B in one build) */
+#define GLIMS_FLAG_SLOT_WORDS32 4096       /* OFF by default.  Default: the straight-line assembly sweeps (rows of at most 32
+                                           entries) read the slots of an incidence record from a 16-bit word -- the row's own
+                                           slot dropped, 5 bits for each other vertex of the cell -- instead of the 32-bit word
+                                           with a byte per vertex: 2 bytes less per (row, cell) incidence and sweep, the same
+                                           slots and the same bits in every result.  Set: the 32-bit words (A/B in one build) */
 
 typedef struct glims_stats {
   int64_t steps;            /* implicit time steps taken */
@@ -315,6 +320,13 @@ typedef struct glims_stats {
                                (see GLIMS_FLAG_NO_FUSED_MASS) */
   int64_t rd_mass_fallback_rows; /* owned rows whose mass product stays with the SpMV: cells of different rho, or rho = 0
                                (set by glims_setup / glims_set_materials; kept by glims_reset_stats) */
+  int64_t cheb_host_counts; /* warm-started dot-free solves whose pass count the host chose: the solve's first pass came with
+                               an assembly sweep, and |b - A u|^2 with that sweep's norms (no second reduction, no plan
+                               kernel, no launch that returns at once); the other warm-started solves choose it on the device */
+  int64_t cheb_fused_zero_starts; /* the folded first passes (cheb_fused_passes) of solves that start from zero: a count the host
+                               always knew; cheb_fused_passes = cheb_host_counts + cheb_fused_zero_starts */
+  int64_t rd_slot16_sweeps; /* assembly sweeps (glims_apply hooks included) whose straight-line launches read the 16-bit slot
+                               words; 0 under GLIMS_FLAG_SLOT_WORDS32 and on a mesh without a straight-line class */
 } glims_stats;
 
 /* ---- lifetime -------------------------------------------------------------------------------------- */
