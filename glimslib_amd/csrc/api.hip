@@ -354,7 +354,7 @@ int glims_set_materials(glims_ctx* h, int n_labels, const double* D, const doubl
     h->adj.invalidate("glims_set_materials after recording started");
     h->have_materials = true;
     h->is_setup = false;
-    h->pending = false;
+    h->prepared.drop();
     return GLIMS_OK;
   });
 }
@@ -383,7 +383,7 @@ int glims_set_options(glims_ctx* h, const glims_options* opt) {
     if (h->world > 1 && opt->rd_mg_smooth != h->opt.rd_mg_smooth) h->mg_rd.ready = false;
     if (opt->rd_precond != h->opt.rd_precond) {
       h->rd_precond_active = 0;                   // decided again by the next glims_step
-      for (int& hint : h->cg_hint) hint = 0;      // iteration counts of the other preconditioner predict nothing
+      for (int& hint : h->run.cg_hint) hint = 0;      // iteration counts of the other preconditioner predict nothing
     }
     // the solve history is a ring of `mech_history` slots: a new depth starts an empty ring (a larger depth would
     // otherwise count never-allocated slots as stored solves)
@@ -394,14 +394,14 @@ int glims_set_options(glims_ctx* h, const glims_options* opt) {
     if ((opt->flags ^ h->opt.flags) & (GLIMS_FLAG_MG_FP32_SMOOTHER | GLIMS_FLAG_MG_FP64_VECTORS | GLIMS_FLAG_MG_WHOLE_GRID | GLIMS_FLAG_MG_NO_LUMPING))
       h->mg.ready = h->mg_rd.ready = false;
     h->opt = *opt;
-    h->pending = false;
+    h->prepared.drop();
     return GLIMS_OK;
   });
 }
 
 int glims_set_dirichlet_c(glims_ctx* h, int64_t n, const int64_t* node_ids, const double* values) {
   return guarded(h, [&]() {
-    h->pending = false;
+    h->prepared.drop();
     h->dirichlet_c_exchange = h->world > 1;
     if (n <= 0) {
       if (h->have_fixed_c) h->mg_rd.ready = false;   // the RD hierarchy eliminates the constrained nodes
@@ -429,7 +429,7 @@ int glims_set_dirichlet_c(glims_ctx* h, int64_t n, const int64_t* node_ids, cons
     h->fixed_c_val.upload(val, h->st);
     h->have_fixed_c = true;
     h->dirichlet_c_dirty = true;   // written into the iterate by the next step, after b = M c^n took the old values
-    h->pending = false;
+    h->prepared.drop();
     GL_HIP(hipStreamSynchronize(h->st));
     return GLIMS_OK;
   });
@@ -465,7 +465,7 @@ int glims_set_dirichlet_u(glims_ctx* h, int64_t n, const int64_t* dof_ids, const
 
 int glims_set_rd_load(glims_ctx* h, const double* f) {
   return guarded(h, [&]() {
-    h->pending = false;
+    h->prepared.drop();
     if (!f) {
       h->have_load_rd = false;
       return GLIMS_OK;
@@ -496,7 +496,7 @@ int glims_setup(glims_ctx* h, int with_mechanics) {
     h->mg.ready = h->mg_rd.ready = false;
     h->rd_precond_active = 0;       // decided by the first glims_step (a collective in partitioned runs)
     h->stats.rd_precond_used = 0;
-    for (int& hint : h->cg_hint) hint = 0;
+    for (int& hint : h->run.cg_hint) hint = 0;
     h->mech_hint = 0;
     GL_REQUIRE(h->have_materials, "glims_setup before glims_set_materials");
     h->adj.invalidate("glims_setup after recording started");
@@ -514,12 +514,12 @@ int glims_setup(glims_ctx* h, int with_mechanics) {
       }
       if (!h->m_uD.p) h->m_uD.alloc_zero(nd, h->st);
     }
-    h->pending = false;
+    h->prepared.drop();
     h->jac32 = (h->opt.flags & GLIMS_FLAG_FP32_JACOBIAN) != 0;
     h->use_idx16 = (h->opt.flags & GLIMS_FLAG_INT32_COLUMNS) == 0;
     h->stats.nnz_idx16 = h->use_idx16 ? h->nnz_idx16_avail : 0;
-    h->cheb = glims_ctx::ChebState();   // the interval belongs to one operator
-    h->have_d2 = false;
+    h->run.cheb = ChebState();   // the interval belongs to one operator
+    h->run.have_d2 = false;
     {
       // Cache policy of the operator streams in the Krylov pass.  What one Krylov iteration touches: the stored entries
       // (values + column codes) and the iteration's vector traffic.  While that fits the 256 MiB Infinity Cache with room to
@@ -544,20 +544,14 @@ int glims_setup(glims_ctx* h, int with_mechanics) {
 int glims_set_state(glims_ctx* h, const double* c, const double* u) {
   return guarded(h, [&]() {
     GL_REQUIRE(c, "null concentration");
-    h->pending = false;
-    h->have_c_old = false;
-    h->have_d2 = false;
-    h->d2_off = h->d2_good = 0;
-    h->d2_backoff = 8;
+    h->prepared.drop();
     // A new state starts a new run (FenicsSimulation.run() may be called again on the same object, simulation_base.py:166-168,
-    // run_for_adjoint does): what the Newton iteration has learnt from the previous run's steps is forgotten, so that the run
-    // takes the iteration path -- and produces the bits -- of a fresh handle.  (What stays: the operators, both multigrid
-    // hierarchies and the preconditioner `auto` has settled on; they depend on the mesh and the parameters, not on the run.)
-    h->nw_mode = h->nw_hold = h->nw_since = h->nw_steps = 0;
-    h->cheb = glims_ctx::ChebState();   // ... and the spectral interval of the dot-free solves (measured again by the first step)
-    h->nq_first_ratio = 1e-3;
-    h->nq_skip_steps = 0;
-    for (int& hint : h->cg_hint) hint = 0;
+    // run_for_adjoint does): what the Newton iteration has learnt from the previous run's steps is forgotten -- the forcing mode,
+    // the guesses and their back-off, the iteration counts, the spectral interval of the dot-free solves (measured again by the
+    // first step) --, so that the run takes the iteration path -- and produces the bits -- of a fresh handle.  (What stays: the
+    // operators, both multigrid hierarchies and the preconditioner `auto` has settled on; they depend on the mesh and the
+    // parameters, not on the run.)
+    h->run = RunMemory();
     h->mech_hint = 0;
     h->mh_count = h->mh_next = 0;   // ... and the elasticity solver's history of right-hand sides
     to_device_perm(h, c, h->c.p, 1);
@@ -643,7 +637,7 @@ int glims_apply(glims_ctx* h, int which, const double* x, double* y, int reps, d
       GL_REQUIRE(gl_rd_mass_in_sweep(h), "the sweep does not form the mass product on this handle (GLIMS_FLAG_NO_FUSED_MASS, "
                                          "several ranks, fp32 Jacobian, or rows of more than 32 entries)");
     if (which == 7) GL_REQUIRE(h->have_state, "the matrix-free product needs the state c (glims_set_state)");
-    if (which >= 8) h->pending = false;   // the sweep rewrites A(c), dinv and the Krylov work vectors
+    if (which >= 8) h->prepared.drop();   // the sweep rewrites A(c), dinv and the Krylov work vectors
     const int d = h->dim;
     const bool blk_in = which == 3, blk_out = which == 3 || which == 4;
     if (blk_out) GL_REQUIRE(h->have_mech, "mechanics operators not assembled");
@@ -713,7 +707,7 @@ int glims_rd_residual(glims_ctx* h, const double* c, const double* c_prev, doubl
     to_device_perm(h, c_prev, dcp.p, 1);
     gl_launch_spmv(h, h->st, h->pat.n_slices, nullptr, h->vM.p, dcp.p, h->b.p, nullptr,
                    h->have_load_rd ? h->load_rd.p : nullptr, nullptr, nullptr, 0, nullptr);
-    h->pending = false;
+    h->prepared.drop();
     gl_rd_assemble(h, dc.p, h->b.p, nullptr, h->cg_r.p, h->cg_r2.p, h->partials.p);
     GL_HIP(hipStreamSynchronize(h->st));
     if (R) {

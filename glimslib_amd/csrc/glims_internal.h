@@ -9,6 +9,7 @@
 #include <vector>
 #include <stdexcept>
 #include "../../include/glims_hip.h"
+#include "step_policy.h"
 
 #define GL_WAVE 64                 // wavefront width of CDNA4; SELL slice height
 #define GL_SIGMA 256               // sigma window (rows) of the SELL-C-sigma row sort (tools/sigma_sweep.py: on an
@@ -548,43 +549,12 @@ struct glims_ctx {
   int spmv_unroll = 8;                     // entries in flight per lane of the scalar SpMV: 8 on lattice meshes, 16 on general ones
   int stream_nt = 1;                       // value / column-code streams of the Krylov operator pass non-temporal (1) or with the
                                            // default cache policy (0): glims_options.stream_policy, resolved at glims_setup
-  // Dot-free RD linear solves (Chebyshev semi-iteration, solver.hip): interval of the spectrum of Dinv A(c) the right-hand sides
-  // of this run excite, from the Lanczos coefficients of recorded PCG solves
-  struct ChebState {
-    bool valid = false;                    // [lmin, lmax] usable
-    // Two intervals: [1] from all PCG solves of the last learning step, [0] from its LOOSE ones only (reduction >= GL_CHEB_LOOSE):
-    // what a tight solve has to resolve (components of relative size 1e-7 at the ends of the spectrum) a solve to 3e-4 may
-    // ignore -- brain-like mesh at 1 M nodes: [0.70, 1.96] against [0.033, 3.63]
-    double lmin = 0.0, lmax = 0.0;         // [1]
-    double lmin0 = 0.0, lmax0 = 0.0;       // [0]; lmax0 = 0: none (then [1] serves)
-    double acc_lmin = 0.0, acc_lmax = 0.0; // ... being accumulated by the current learning step
-    double acc_lmin0 = 0.0, acc_lmax0 = 0.0;
-    int learned = 0, learned0 = 0;         // PCG solves that contributed to acc_* / acc_*0
-    int age = 0;                           // steps since the interval was measured
-    int weak = 0;                          // consecutive dot-free solves that contracted far less than they were sized for
-    int m_hint[2] = {0, 0};                // passes the device chose for the last warm-started solve (bounds the next one's launches):
-                                           // [0] a step's first solve, [1] its second
-    // Which iteration a solve AFTER a step's first one uses (the first, loose one always takes the dot-free iteration): PCG
-    // needs fewer operator passes for a tight solve (superlinear convergence: 8 iterations where the Chebyshev bound asks for
-    // 13-15 at config C4), the dot-free iteration cheaper ones.  cost_ratio = cost of a Chebyshev pass / cost of a PCG
-    // iteration from a byte model of the two (solver.hip, cheb_cost_ratio: 0.74 at 10 M rows, 0.66 at 1.26 M -- measured 0.74 /
-    // 0.6), pcg_its_per_decade from the tightest PCG solve of the last learning step.  Deterministic (no timings): the
-    // iteration path of a run stays reproducible bit for bit.  0 = unknown (then: Chebyshev).
-    double cost_ratio = 0.0, pcg_its_per_decade = 0.0;
-    int pcg_best_its = 0;                  // iterations of the solve pcg_its_per_decade comes from
-  } cheb;
+  RunMemory run;                           // what the time stepper remembers within one run (step_policy.h)
   double cheb_test_hi = 1.0;               // TEST HOOK GLIMS_CHEB_TEST_SCALE_HI (read by glims_create): factor on the measured upper end
   dvec<double> cg_hist;                    // [2 * GL_CG_HIST] (alpha_k, beta_k) of the running PCG solve
   dvec<double> cheb_delta;                 // the correction the last Chebyshev solve added to the iterate [n_nodes] (take-back)
-  dvec<double> cheb_delta2;                // the same of a step's SECOND solve: kept across the step boundary, it is the next step's guess
-  bool have_d2 = false;                    // ... cheb_delta2 holds the previous step's second correction (same run, no jump in the state)
+  dvec<double> cheb_delta2;                // the same of a step's SECOND solve: kept across the step boundary, it is the next step's guess (run.have_d2)
   dvec<double> d2_prev;                    // the second correction of the step before that one (linear extrapolation of the guess)
-  int d2_depth = 0;                        // consecutive steps whose second correction was kept (2: d2_prev is a real one)
-  int d2_regime = -1;                      // the step cheb_delta2 comes from: passes of its FIRST solve and the forcing mode (what that solve
-                                           // left behind depends on them) ...
-  double d2_r1 = 0.0;                      // ... and the Newton residual its second solve started from
-  int d2_off = 0, d2_backoff = 8, d2_good = 0;   // steps for which the guess stays unused after one that missed the target; the length
-                                           // doubles with every miss (8 .. 256) and returns to 8 after 32 guesses that did not
   dvec<int> cheb_plan;                     // [1] iteration count computed on the device (a step's first, warm-started solve)
   dvec<float> vKel32;                      // single-precision copy of K_el (inner solves of the elasticity solver)
   // vectors (internal numbering; length n_nodes unless noted)
@@ -594,12 +564,6 @@ struct glims_ctx {
   // use), the iterate before the last solve, and the two staged vectors a = c_new + c_k - 2 c_0, delta = c_new - c_k
   dvec<double> nq_c0, nq_ck;
   dvec<float> nq_ad;                                          // (a, delta) pairs, single precision (see k_rd_quad)
-  double nq_first_ratio = 1e-3;                               // residual contraction of the last step's first Newton iteration
-  // default forcing: how a step's FIRST solve is run (gl_step).  0: tolerance 0.3 cg_rtol; 1: the same + midpoint correction;
-  // 2: cg_rtol, no correction (for nw_hold steps after a step that took three iterations even with the correction)
-  int nw_mode = 0, nw_hold = 0, nw_since = 0, nw_steps = 0;   // nw_steps: steps since glims_set_state
-  int nq_skip_steps = 0;                                      // steps left without cheap evaluations (after a poor contraction)
-  int cg_hint[8] = {0, 0, 0, 0, 0, 0, 0, 0};                  // PCG iterations of the k-th Newton solve of the previous step
   int mech_hint = 0;
   // history of solved elasticity problems (right-hand side, free-dof solution): the operator is linear and time
   // independent, so the least-squares fit of a new right-hand side by the stored ones gives the initial guess
@@ -607,22 +571,9 @@ struct glims_ctx {
   dvec<double> mh_rhs[MHIST], mh_x[MHIST], mh_w[MHIST];   // solve history: right-hand sides, solutions, K_el x (= rhs - final residual)
   int mh_count = 0, mh_next = 0;           // depth: glims_options.mech_history
   double mh_G[MHIST][MHIST] = {{0.0}};     // Gram matrix (rhs_k, rhs_l) of the stored right-hand sides (host copy)
-  dvec<double> ws_du;                                         // the increment of the step before the last (warm start, k_ws_delta)
-  int ws_depth = 0;                                           // ... 1 once it holds a real increment
-  bool have_c_old = false;                                    // c_old holds the state at the start of the previous step
-  bool pending = false;                                      // cg_r / b / vA already hold the first assembly of the next step
-  double pending_r0 = 0.0;
-  // Fused guess pass (gl_step): the first pass of a dot-free solve that the sweep before it has run (guess in cg_u, y_1 in cg_p)
-  struct FusedGuess {
-    bool valid = false;
-    int kind = 0;               // 1: from the guess, 2: from zero
-    double ia = 0.0, ib = 0.0;  // the interval whose theta the sweep used
-    int second_order = 0;       // how the guess was extrapolated
-    double rr = 0.0;            // kind 1: |res - A u|^2 of the guess, from the sweep's mail (the solve's count follows from it)
-  };
-  FusedGuess fg1;                                             // ... of the next step's first solve: valid only next to `pending`
-  double fg2_red = 0.0;                                       // reduction the last second dot-free solve was asked for (0: none yet)
-  dvec<double> fg_part;                                       // its sums of |b - A u|^2 per slice (reduced with the sweep's norms)
+  dvec<double> ws_du;                                         // the increment of the step before the last (warm start, k_ws_delta; run.ws_depth)
+  PreparedStep prepared;                                      // the next step, where the last sweep already assembled it
+  dvec<double> fg_part;                                       // a fused guess pass's sums of |b - A u|^2 per slice (reduced with the sweep's norms)
   dvec<double> ws_c_old_next, ws_du_next;                     // what k_ws_delta would have committed (exchanged with c_old / ws_du)
   dvec<double> U, mload, m_rhs, m_p, m_s, m_u, m_w, m_r, m_dinv, m_uD;   // mechanics, [n_nodes*dim]
   dvec<uint8_t> fixed_c, fixed_u;

@@ -1039,8 +1039,8 @@ void gl_apply_dirichlet_c(glims_ctx* h) {
   hipLaunchKernelGGL(k_mask_assign, dim3(grid_exact(h->n_nodes)), dim3(256), 0, h->st, h->n_nodes, h->c.p,
                      h->fixed_c.p, (const double*)h->fixed_c_val.p);
   GL_HIP(hipGetLastError());
-  h->have_c_old = false;
-  h->have_d2 = false;
+  h->run.have_c_old = false;
+  h->run.have_d2 = false;
 }
 
 // ===================================================================================================
@@ -1262,10 +1262,7 @@ int gl_pcg(glims_ctx* h, double* x, double* r, double* u, double* w, double* p, 
 }
 
 // ---- the dot-free solve -------------------------------------------------------------------------------------------------
-// Safety factors on the chosen interval.  A lower end set too low only costs iterations (prototype: 0.5 x -> +50 %); an upper
-// end set too low makes the iteration diverge on what lies above it, so that end gets more room.
-static const double GL_CHEB_LO = 0.9, GL_CHEB_HI = 1.06;
-static const double GL_CHEB_LOOSE = 3e-5;   // reductions down to this use the interval of the loose learning solves
+// (the interval's safety factors and the rule that picks it: step_policy.h, cheb_interval)
 #define GL_CHEB_HIST GL_CG_HIST
 // Chebyshev recurrence on [a, b]: d_0 = z_0 / theta;  d_k = rho_k rho_(k-1) d_(k-1) + (2 rho_k / delta) z_k,  z = Dinv r
 struct ChebRec {
@@ -1404,7 +1401,7 @@ static void cheb_learn(glims_ctx* h, int64_t its, double eps) {
   if (getenv("GLIMS_VERBOSE"))
     fprintf(stderr, "glims dot-free solves: PCG solve of %lld iterations (reduction %.1e): Ritz values in [%.4f, %.4f], interval chosen "
             "[%.4f, %.4f]\n", (long long)its, eps, flo, fhi, lo, hi);
-  glims_ctx::ChebState& cs = h->cheb;
+  ChebState& cs = h->run.cheb;
   cs.acc_lmin = cs.learned ? std::min(cs.acc_lmin, lo) : lo;
   cs.acc_lmax = cs.learned ? std::max(cs.acc_lmax, hi) : hi;
   cs.learned++;
@@ -1414,13 +1411,6 @@ static void cheb_learn(glims_ctx* h, int64_t its, double eps) {
     cs.learned0++;
   }
   h->stats.cheb_learn_solves++;
-}
-// the interval a solve that wants the reduction `red` uses
-static void cheb_interval(const glims_ctx* h, double red, double* a, double* b) {
-  const glims_ctx::ChebState& cs = h->cheb;
-  const bool loose = red >= GL_CHEB_LOOSE && cs.lmax0 > 0.0;
-  *a = GL_CHEB_LO * (loose ? cs.lmin0 : cs.lmin);
-  *b = GL_CHEB_HI * (loose ? cs.lmax0 : cs.lmax) * h->cheb_test_hi;
 }
 
 // Cost of one Chebyshev pass relative to one PCG iteration (operator pass + reduction + vector update): algorithmic bytes of
@@ -1454,7 +1444,6 @@ static double cheb_cost_ratio(glims_ctx* h) {
 #endif
 static const double GL_D2_KAPPA_MAX = 6.0;   // ... only where the solve's interval has lmax / lmin below this
 static const int GL_CHEB_MAX = 96;    // launches of one solve at most
-static const int GL_CHEB_LONG = 48;   // solves that would need more passes than this run PCG
 
 struct ChebRun {
   int passes = 0;        // operator passes enqueued that can run (host-known count), or the upper bound when planned
@@ -1481,7 +1470,7 @@ static ChebRun cheb_solve(glims_ctx* h, const CgVecs& v, double tol_abs, double 
   const int64_t n = h->n_own;
   h->cheb_plan.alloc(1);
   double ia, ib;
-  cheb_interval(h, tol_abs / std::max(r_norm > 0.0 ? r_norm : r_bound, tol_abs), &ia, &ib);
+  cheb_interval(h->run.cheb, h->cheb_test_hi, tol_abs / std::max(r_norm > 0.0 ? r_norm : r_bound, tol_abs), &ia, &ib);
   ChebRec rec(ia, ib);
   PackMap pm;
   if (split && h->n_send > 0) {
@@ -1500,7 +1489,7 @@ static ChebRun cheb_solve(glims_ctx* h, const CgVecs& v, double tol_abs, double 
     // + 2 (like the PCG solves' hints: the launches beyond the device's count return at once, but each still costs a dispatch
     // and, in a partitioned run, a halo exchange); a count clipped by the bound is a slightly weaker Newton step
     m = std::min(GL_CHEB_MAX, std::max(m_min, rec.iterations(tol_abs / std::max(r_bound, tol_abs)) + 3));
-    if (h->cheb.m_hint[hint_slot] > 0) m = std::max(m_min, std::min(m, h->cheb.m_hint[hint_slot] + 2 + hint_slot));
+    if (h->run.cheb.m_hint[hint_slot] > 0) m = std::max(m_min, std::min(m, h->run.cheb.m_hint[hint_slot] + 2 + hint_slot));
   }
   else if (r_norm > tol_abs) m = std::min(GL_CHEB_MAX, std::max(m_min, rec.iterations(tol_abs / r_norm)));
   const unsigned g = grid_for(n);
@@ -1754,267 +1743,476 @@ void glims_ctx::timing_collect() {
   tev_used = 0;
 }
 
+// ===================================================================================================
+// the RD time stepper: gl_step is a loop over the phases below.  What a run remembers between steps is h->run (RunMemory),
+// what a step knows about itself StepFacts, one Newton iteration NewtonIt; the scalar decisions are in step_policy.h.
+// ===================================================================================================
+struct NewtonIt {
+  int it = 0, slot = 0;                   // slot: the cg_hint a PCG solve uses
+  double nr = 0.0, ia = 0.0, ib = 0.0;    // nr: |R| before the solve; [ia, ib]: see use_cheb
+  Forcing f;                              // its tolerance and what it is expected to leave
+  // The evaluation after the solve, decided before it: a sweep that also assembles the next step (speculate) / the cheap
+  // residual (cheap) / neither: a plain sweep.  use_cheb: a dot-free solve, on the interval [ia, ib] for f.tol_lin.
+  bool speculate = false, cheap = false, use_cheb = false;
+  // warm: the first solve is warm-started; ws_fused: ... the guess being the dot-free solve's direction 0; take_folded: the
+  // solve's first pass came with the last sweep; cheb_idle: a dot-free solve with nothing to do (see solve_cheb); deferred:
+  // the solve's count arrives with the mail of the evaluation after it
+  bool warm = false, ws_fused = false, take_folded = false, cheb_idle = false, deferred = false;
+  ChebRun crun;
+};
+
+static int d2_order(const RunMemory& run) { return (run.d2_depth >= 2 && GL_D2_ORDER >= 2) ? 1 : 0; }
+
+// Start of a step: the learning schedule of the dot-free solves, the step's first system -- taken from the sweep that confirmed
+// the previous step, or assembled -- and the step's modes.  Returns |R(c^n; c^n)|.
+static double step_begin(glims_ctx* h, RunMemory& run, StepFacts& sf, double* norms) {
+  const glims_options& o = h->opt;
+  const double* load = h->have_load_rd ? h->load_rd.p : nullptr;
+  sf.newton0 = h->stats.newton_its;
+  sf.cg0 = h->stats.cg_its;
+  sf.fixed_forcing = (o.flags & GLIMS_FLAG_FIXED_FORCING) != 0;
+  sf.extrapolate = (o.flags & GLIMS_FLAG_EXTRAPOLATE_GUESS) != 0;
+  sf.warm_on = (o.flags & GLIMS_FLAG_WARM_START) != 0;
+  // Dot-free linear solves (glims_options.rd_linear): Jacobi-preconditioned RD solves run the Chebyshev iteration on the
+  // interval measured by the PCG solves of a LEARNING step -- the first step of a run, every 32nd one after it, and the
+  // step after a solve had to be taken back.
+  ChebState& cb = run.cheb;
+  sf.cheb_allowed = o.rd_linear != GLIMS_RD_LINEAR_PCG && !sf.rd_mg;
+  if (sf.cheb_allowed && cb.valid && ++cb.age >= GL_CHEB_RELEARN) cb.valid = false;
+  sf.cheb_learning = sf.cheb_allowed && !cb.valid;
+  if (sf.cheb_learning) {
+    cb.learned = cb.learned0 = cb.pcg_best_its = cb.m_hint[0] = cb.m_hint[1] = 0;
+    h->cg_hist.alloc((size_t)2 * GL_CG_HIST);
+  }
+  // Fused guess pass: a sweep that is followed by a dot-free solve also runs that solve's first pass (k_rd_assemble_sg) --
+  // the guess pass of the step's first solve comes with the sweep that confirmed the previous step (h->prepared.guess, lives
+  // and dies with the prepared step), the second solve's guess (or start) pass with the sweep after the first solve (sf.fg2).
+  // Both are speculative: the guess is formed without committing the extrapolation's state, the interval is the one the solve
+  // is expected to use, and the solve takes the pass only if what it would have done itself is exactly that.
+  sf.fuse_on = (o.flags & GLIMS_FLAG_NO_FUSED_GUESS) == 0 && h->world == 1 && sf.cheb_allowed && !sf.extrapolate &&
+               !h->jac32 && gl_rd_fusable(h);
+  const PreparedStep prepared = h->prepared;   // (this step's; whatever happens, it is not kept)
+  h->prepared.drop();
+  sf.fg1 = prepared.guess;
+  // (where the sweep that verified the previous step already assembled A(c^n) and -R(c^n; c^n) for this one: nothing to do)
+  double nr = prepared.r0;
+  if (!prepared.valid) {
+    // b = M c^n + load          ('u_previous1 * v1 * dx', simulation_tumor_growth.py:117)
+    // Where the iterate changes between this product and the sweep (new Dirichlet data, the extrapolated guess) it is formed
+    // here, on the old state; otherwise with the sweep (rd_sweep, mass_for_b: the same formula as a speculative sweep's b2).
+    const bool c_changes = h->dirichlet_c_dirty || h->dirichlet_c_exchange || sf.extrapolate;
+    if (c_changes)
+      gl_launch_spmv(h, h->st, h->pat.n_slices, nullptr, h->vM.p, h->c.p, h->b.p, nullptr, load, nullptr, nullptr, 0, nullptr);
+    // new Dirichlet data enter the ITERATE, after the old state went into b = M c^n: the reference's u_previous
+    // keeps the previous step's boundary values while the DirichletBC constrains the unknown
+    // (a rank lists its OWN constrained nodes; their ghost copies on the neighbours follow by a halo exchange that every
+    //  rank takes part in -- also the ranks that own no constrained node: dirichlet_c_exchange)
+    if (h->dirichlet_c_dirty) gl_apply_dirichlet_c(h);
+    if (h->dirichlet_c_exchange) {
+      gl_halo_exchange(h, h->c.p, 1);
+      h->dirichlet_c_exchange = false;
+      // new boundary values are a jump in the iterate: no warm start from the previous increments -- on EVERY rank (the
+      // rank that wrote the values has dropped its own in gl_apply_dirichlet_c; a rank that kept it would run a differently
+      // shaped first solve -- the warm-started dot-free solve reduces |r| first -- and the ranks' collectives would no longer pair up)
+      run.have_c_old = false;
+      run.have_d2 = false;
+    }
+    if (sf.extrapolate) {
+      hipLaunchKernelGGL(k_extrapolate, dim3(grid_exact(h->n_own)), dim3(256), 0, h->st, h->n_own, h->c.p, h->c_old.p,
+                         h->have_fixed_c ? h->fixed_c.p : nullptr, h->stats.steps > 0 ? 1 : 0);
+      gl_halo_exchange(h, h->c.p, 1);
+    }
+    rd_sweep(h, nullptr, norms, nullptr, /*exchange_c=*/false, /*mass_for_b2=*/false, nullptr, /*mass_for_b=*/!c_changes);
+    nr = norms[0];
+  }
+  sf.r0 = nr;
+  sf.target = std::max(o.newton_atol, o.newton_rtol * sf.r0);
+  // Residuals from the quadratic structure (default; GLIMS_FLAG_FULL_NEWTON: a sweep after every solve).  Between two
+  // sweeps the solves use A_0 = A(c_0), the Jacobian the last sweep assembled; after such a solve the residual is the
+  // Krylov residual plus dt N(a) delta (rd_quad_update: 48 % of a sweep's bytes, no Jacobian written).  A sweep runs
+  // after the step's first solve (see cheap_next), and
+  // (a) where convergence is expected -- it returns the TRUE residual and assembles the next step's system, as before;
+  // (b) when the cheap residual reports convergence without (a) having been predicted; (c) after an iteration whose
+  // residual is more than 5 x the linear solve's tolerance (strong nonlinearity: dt rho |c - c_0| is no longer small) --
+  // the sweep's Jacobian then becomes the new A_0.  Not combined with the extrapolated guess (no verifying sweep there).
+  // (nor with the single-precision Jacobian: the Krylov residual then belongs to the rounded operator)
+  // After a step in which (c) struck, the next eight steps run with sweeps only: where the nonlinearity is that strong a
+  // cheap evaluation buys an extra Newton iteration (dt rho = 0.6: 46 against 38 iterations in 8 steps without this).
+  if (run.nq_skip_steps > 0) --run.nq_skip_steps;
+  sf.quad = (o.flags & GLIMS_FLAG_FULL_NEWTON) == 0 && !sf.extrapolate && !h->jac32 && run.nq_skip_steps == 0;
+  // Default forcing (round 4): the FIRST solve of a step decides whether two Newton iterations can be enough.  With the
+  // second solve's Jacobian at c_1, two iterations leave q_2 (r_1 / r_0)^2 r_0, q_2 = what the quadratic term alone leaves of
+  // a whole step (5e-4 late in config C4's run) -- below the Newton target 1e-10 r_0 only if r_1 <= 4e-4 r_0, i.e. with the
+  // first solve at 0.3 cg_rtol instead of cg_rtol (+0-1 PCG iterations) AND a first residual not dominated by the quadratic
+  // term.  Early in a run (small increments) the tolerance alone does it (mode 0: C4 steps 5-25 2.4 -> 2.1 iterations per
+  // step, 9.50 -> 9.37 ms; brain-like mesh 2.74 -> 2.65; C3 1.50 -> 1.46); later the quadratic term has to go too, which is
+  // what the midpoint correction of the first right-hand side does with the extrapolated increment (mode 1, one cheap pass:
+  // C4 steps 120-160 three solves -> two, 8.89 -> 8.19 ms; steps 300-340 9.38 -> 8.71; C3 1.51 -> 1.29; brain-like mesh
+  // 3.00 -> 2.70; profiles/r04_ab_midpoint.txt).  Either one alone is a loss there (tolerance alone: a third sweep, 9.67 ms;
+  // correction alone: 9.39).  How the mode follows the outcome: forcing_mode_after_step (mode 2: strong nonlinearity, where
+  // the extra effort buys nothing).  GLIMS_FLAG_FIXED_FORCING: cg_rtol for every solve, no correction (mode 2 throughout).
+  sf.nw_mode = (sf.quad && !sf.fixed_forcing) ? run.nw_mode : 2;
+  sf.midpoint = sf.quad && sf.nw_mode == 1;
+  sf.first_rtol = (sf.quad && sf.nw_mode != 2) ? GL_FIRST_RTOL * o.cg_rtol : o.cg_rtol;
+  sf.ratio_est = run.nq_first_ratio;
+  if (sf.quad) {
+    for (dvec<double>* v : {&h->nq_c0, &h->nq_ck}) v->alloc((size_t)h->n_nodes);
+    h->nq_ad.alloc((size_t)2 * h->n_nodes);
+  }
+  if (run.d2_off > 0) {
+    --run.d2_off;
+    run.have_d2 = false;
+  }
+  return nr;
+}
+
+// Guess of a step's first solve (both warm-start options own the c_old buffer), and whether the solve's first pass came with
+// the sweep that prepared the step.
+static void first_solve_guess(glims_ctx* h, RunMemory& run, StepFacts& sf, NewtonIt& s) {
+  const FusedGuess& fg1 = sf.fg1;
+  const bool same_interval = s.ia == fg1.ia && s.ib == fg1.ib;   // (the solve's interval is the one the sweep assumed)
+  if (sf.warm_on && !sf.extrapolate) {
+    // initial guess of the first linear solve = the increment predicted from the previous steps' (k_ws_delta): same linear
+    // system, same solution, the Krylov iteration just starts closer.  One SpMV with the already assembled A(c^n).
+    h->ws_du.alloc((size_t)h->n_nodes);
+    // (dot-free solve: the guess u becomes direction 0 of the solve -- the product A u is then the solve's first operator
+    //  pass and the correction accumulates from u: cheb_solve, warm_u)
+    s.ws_fused = s.use_cheb && run.have_c_old;
+    const int ws_order = (run.have_c_old && run.ws_depth >= 1) ? 1 : 0;
+    // (the guess is in cg_u, y_1 in cg_p)
+    s.take_folded = sf.fuse_on && fg1.valid && fg1.kind == 1 && s.ws_fused && !sf.midpoint && fg1.second_order == ws_order &&
+                    same_interval;
+    if (s.take_folded) {   // what k_ws_delta commits, written by k_ws_delta_spec
+      std::swap(h->c_old.p, h->ws_c_old_next.p);
+      std::swap(h->ws_du.p, h->ws_du_next.p);
+    } else {
+      hipLaunchKernelGGL(k_ws_delta, dim3(grid_exact(h->n_nodes)), dim3(256), 0, h->st, h->n_nodes, h->c.p,
+                         h->c_old.p, h->cg_u.p, h->ws_du.p, ws_order);
+    }
+    run.ws_depth = run.have_c_old ? 1 : 0;   // (ws_du holds a real increment from the second warm-started step on)
+    if (run.have_c_old) {
+      s.warm = true;
+      if (!s.ws_fused) {
+        gl_launch_spmv(h, h->st, h->pat.n_slices, nullptr, h->vA.p, h->cg_u.p, h->cg_w.p,
+                       h->have_fixed_c ? h->fixed_c.p : nullptr, nullptr, nullptr, nullptr, 0, nullptr,
+                       h->jac32 ? h->vA32.p : nullptr);
+        hipLaunchKernelGGL(k_ws_apply, dim3(grid_exact(h->n_own)), dim3(256), 0, h->st, h->n_own, h->cg_r.p, h->cg_w.p,
+                           h->c.p, h->cg_u.p);
+      }
+      // Midpoint correction of the step's first right-hand side.  For the exactly quadratic residual the whole step
+      // delta* = c* - c_0 satisfies  A(c_0 + delta* / 2) delta* = -R(c_0)  -- the midpoint Jacobian solves the step in
+      // ONE linear solve -- i.e.  A(c_0) delta* = -R(c_0) - dt N(delta*) delta*.  With delta* predicted by the previous
+      // step's increment u (the warm-start vector) the right-hand side gets the term -dt N(u) u from one cheap pass:
+      // what is left of the quadratic term after the first solve is dt rho |delta* - u| |delta*| instead of
+      // dt rho |delta*|^2, so the first Newton iteration contracts as far as its linear tolerance lets it.
+      if (sf.midpoint) {
+        h->nq_ad.alloc((size_t)2 * h->n_nodes);
+        hipLaunchKernelGGL(k_pair_of, dim3(grid_exact(h->n_nodes)), dim3(256), 0, h->st, h->n_nodes, h->cg_u.p,
+                           (float2*)h->nq_ad.p);
+        gl_rd_quad(h, h->nq_ad.p, h->cg_r.p, h->partials.p);
+        h->stats.rd_quad_updates++;
+        h->stats.midpoint_steps++;
+      }
+    }
+    run.have_c_old = true;
+  }
+  // (a first solve from zero whose start came with the sweep)
+  if (sf.fuse_on && fg1.valid && fg1.kind == 2 && s.use_cheb && !s.ws_fused && s.f.tol_lin < s.nr) s.take_folded = same_interval;
+  if (sf.verbose_cheb)
+    fprintf(stderr, "  fused guess: step %lld first solve: payload %d kind %d order %d -- use_cheb %d ws_fused %d midpoint %d "
+            "mode %d -> folded %d\n", (long long)h->stats.steps, (int)fg1.valid, fg1.kind, fg1.second_order, (int)s.use_cheb,
+            (int)s.ws_fused, (int)sf.midpoint, sf.nw_mode, (int)s.take_folded);
+}
+
+// Guess of a step's second solve, for either iteration: the previous step's second correction, linearly extrapolated from the
+// last two, into cg_u (where the first solve's went: it is free again) -- unless a sweep has put it there already (`folded`,
+// k_d2_guess_spec; d_prev = d then by exchanging the buffers: the solve rewrites cheb_delta2).
+static void second_solve_guess(glims_ctx* h, const RunMemory& run, bool folded) {
+  h->d2_prev.alloc((size_t)h->n_nodes);
+  if (folded) {
+    std::swap(h->cheb_delta2.p, h->d2_prev.p);
+  } else {
+    hipLaunchKernelGGL(k_d2_guess, dim3(grid_exact(h->n_own)), dim3(256), 0, h->st, h->n_own, (const double*)h->cheb_delta2.p,
+                       h->d2_prev.p, h->cg_u.p, d2_order(run));
+    GL_HIP(hipGetLastError());
+  }
+  if (h->world > 1) gl_halo_exchange(h, h->cg_u.p, 1);   // (corrections are kept by their row owners: ghosts)
+}
+
+// The count m of a warm-started dot-free solve (chosen by the host, or by the device and read from the next mail), `bound`
+// the launches it was allowed, `passes` the operator passes that ran.
+static void book_cheb_count(glims_ctx* h, RunMemory& run, StepFacts& sf, const NewtonIt& s, int64_t m, int bound, int64_t passes) {
+  run.cheb.m_hint[s.it == 1 ? 1 : 0] = (int)std::max<int64_t>(1, m);
+  if (s.it == 0) sf.regime_now = (int)m + 100 * sf.nw_mode;
+  // (a count that used up its launches: the guess was further off than the last ones -- not a basis for the next step's)
+  if (s.it == 1 && m >= bound) sf.d2_written = false;
+  h->stats.cg_its += passes;
+  h->stats.cheb_its += passes;
+  h->stats.last_cg_res = s.f.tol_lin;
+}
+
+// A dot-free solve and the bookkeeping of its count.  *ylast: where it leaves its correction (take-back).
+static void solve_cheb(glims_ctx* h, RunMemory& run, StepFacts& sf, NewtonIt& s, const CgVecs& v, double** ylast) {
+  const double nr = s.nr, tol_lin = s.f.tol_lin;
+  // |r| on entry: known to the host unless the solve starts from the warm-start guess -- then the count is chosen on the
+  // device from the norm its first pass measures
+  // A step's SECOND solve starts from the previous step's second correction: what the first solve leaves behind -- the
+  // quadratic remainder and the residual of a fixed polynomial applied to the extrapolation error -- changes by about a
+  // per cent from one step to the next (|R_1| over steps 20-28 of config C4: 1.31, 1.32, 1.34, 1.36, 1.40e-5), so the
+  // correction that removes it does too (where it continues the last one: d2_continues).
+  const bool second = s.it == 1;
+  h->cheb_delta.alloc((size_t)h->n_nodes);
+  if (second) h->cheb_delta2.alloc((size_t)h->n_nodes);
+  if (second && run.have_d2 && !d2_continues(run, sf.regime_now, nr)) run.have_d2 = false;
+  if (!run.have_d2) run.d2_depth = 0;   // (dropped since the last step: a new state, new boundary values, a take-back)
+  // Only on a narrow interval: the components that come back with the guess are the ones the solves' polynomial amplifies --
+  // outside the interval, where it grows like exp(degree) -- and a wide interval means long solves (random-point mesh, 1 M
+  // nodes, [0.18, 3.3]: 27-34 passes instead of 41-44 for eight steps, then a residual three times the target and a third
+  // Newton iteration per step for the sixteen after: 2.9 -> 3.6 ms per step; not used there).
+  const bool narrow = second && run.have_d2 && s.ib <= GL_D2_KAPPA_MAX * s.ia;
+  const bool warm2 = GL_D2_ORDER >= 1 && second && run.have_d2 && narrow && sf.warm_on && !sf.extrapolate;
+  const bool idle = !warm2 && tol_lin >= nr;
+  FusedGuess& fg2 = sf.fg2;
+  if (second && sf.fuse_on && fg2.valid && !idle && (fg2.kind == 1 ? (warm2 && fg2.second_order == d2_order(run)) : !warm2))
+    s.take_folded = s.ia == fg2.ia && s.ib == fg2.ib;
+  if (second && sf.verbose_cheb)
+    fprintf(stderr, "  fused guess: step %lld second solve: payload %d kind %d order %d [%.17g, %.17g] -- warm2 %d have_d2 %d narrow %d order %d "
+            "regime %d/%d r1 %.3e/%.3e idle %d -> folded %d\n", (long long)h->stats.steps, (int)fg2.valid, fg2.kind,
+            fg2.second_order, fg2.ia, fg2.ib, (int)warm2, (int)run.have_d2, (int)narrow, d2_order(run), sf.regime_now, run.d2_regime, nr,
+            run.d2_r1, (int)idle, (int)s.take_folded);
+  fg2.valid = false;
+  if (second) run.fg2_red = tol_lin / std::max(nr, tol_lin);   // (what the next step's sweep sizes its guess pass by)
+  if (warm2) second_solve_guess(h, run, s.take_folded);
+  // A solve from zero whose tolerance is already met (tol_lin >= |R_k|: a cg_atol above the residual) runs no pass and
+  // writes no correction: nothing is enqueued, c and the kept corrections stay as they are, nothing can be taken back --
+  // PCG's zero iterations.  (A warm-started solve still runs: its count is chosen on the device from |b - A u|.)
+  s.cheb_idle = !(s.ws_fused || warm2) && tol_lin >= nr;
+  if (!s.cheb_idle) {
+    *ylast = second ? h->cheb_delta2.p : h->cheb_delta.p;
+    if (second) sf.second_solve_ran(nr, warm2, /*pcg=*/false);
+    s.crun = cheb_solve(h, v, tol_lin, nr, nr, s.cheap, (s.ws_fused || warm2) ? h->cg_u.p : (const double*)nullptr, *ylast,
+                        second ? 1 : 0, s.take_folded, second ? fg2.rr : sf.fg1.rr);
+  }
+  s.deferred = s.crun.planned;
+  if (s.deferred || s.cheb_idle) return;   // (a device-side count is booked when its mail arrives: gl_step)
+  if (s.crun.host_count) return book_cheb_count(h, run, sf, s, s.crun.m, s.crun.bound, s.crun.passes);
+  if (s.it == 0) sf.regime_now = 1000 + s.crun.passes + 100 * sf.nw_mode;   // (a cold first solve: not the same thing as a warm one of that count)
+  h->stats.cg_its += s.crun.passes;
+  h->stats.cheb_its += s.crun.passes;
+  h->stats.last_cg_res = tol_lin;
+}
+
+// A PCG solve: in a learning step the one whose Lanczos coefficients measure the interval.  Returns cg_solve's status.
+static int solve_pcg(glims_ctx* h, RunMemory& run, StepFacts& sf, NewtonIt& s, CgVecs& v) {
+  const int64_t n = h->n_own;
+  const double nr = s.nr, tol_lin = s.f.tol_lin;
+  if (sf.cheb_learning) v.hist = h->cg_hist.p;
+  // The second solve's guess with PCG (the brain-like mesh's tight solves, multigrid-preconditioned stiff steps,
+  // rd_linear = PCG): same guess, applied like the first solve's (r -= A u, c += u).  PCG accumulates into c, so the
+  // correction is recovered as c after - c before.  No feedback problem here (PCG damps whatever the guess carries); the
+  // learning steps' solves start from zero (their Lanczos coefficients are to describe the right-hand side itself).
+  const bool second_pcg = s.it == 1 && !sf.cheb_learning && sf.warm_on && !sf.extrapolate;
+  if (second_pcg) {
+    h->cheb_delta2.alloc((size_t)h->n_nodes);
+    if (run.have_d2 && !d2_continues(run, sf.regime_now + GL_D2_REGIME_PCG, nr)) run.have_d2 = false;
+    if (!run.have_d2) run.d2_depth = 0;
+    const bool warm2 = GL_D2_ORDER >= 1 && run.have_d2;
+    if (warm2) second_solve_guess(h, run, /*folded=*/false);
+    GL_HIP(hipMemcpyAsync(h->cheb_delta2.p, h->c.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, h->st));
+    if (warm2) {
+      gl_launch_spmv(h, h->st, h->pat.n_slices, nullptr, h->vA.p, h->cg_u.p, h->cg_w.p,
+                     h->have_fixed_c ? h->fixed_c.p : nullptr, nullptr, nullptr, nullptr, 0, nullptr,
+                     h->jac32 ? h->vA32.p : nullptr);
+      // (applied only if it lowers the residual -- decided on the device from two sums: on stiff steps, where the solution
+      //  does not evolve smoothly from step to step, the extrapolated correction can be worse than none; 5.3 -> 5.6
+      //  V-cycle-preconditioned iterations per solve at 1 M rows with the guess always applied)
+      const unsigned gg = grid_for(n, 256, 1024);
+      hipLaunchKernelGGL(k_guess_norms, dim3(gg), dim3(256), 0, h->st, n, (const double*)h->cg_r.p, (const double*)h->cg_w.p,
+                         h->partials.p);
+      reduce_partials(h, (int)gg, 2, nullptr);
+      allreduce_sum(h, h->red.p, 2);
+      hipLaunchKernelGGL(k_ws_apply_if, dim3(grid_exact(n)), dim3(256), 0, h->st, n, h->cg_r.p, (const double*)h->cg_w.p,
+                         h->c.p, (const double*)h->cg_u.p, (const double*)h->red.p);
+      GL_HIP(hipGetLastError());
+      s.slot = 7;
+      if (run.cg_hint[7] <= 0) run.cg_hint[7] = run.cg_hint[1];   // (a first count to bound the launches: the solve from zero's)
+    }
+    sf.second_solve_ran(nr, warm2, /*pcg=*/true);
+  }
+  int64_t its = 0;
+  double res = 0.0;
+  const int cs = cg_solve(h, v, tol_lin, h->opt.cg_maxit, run.cg_hint[s.slot], &its, &res, /*defer=*/!sf.cheb_learning);
+  if (second_pcg) {
+    hipLaunchKernelGGL(k_d2_from_state, dim3(grid_exact(n)), dim3(256), 0, h->st, n, (const double*)h->c.p,
+                       h->cheb_delta2.p);
+    GL_HIP(hipGetLastError());
+  }
+  s.deferred = its < 0;
+  if (s.deferred) return cs;
+  run.cg_hint[s.slot] = (int)its;
+  h->stats.cg_its += its;
+  h->stats.last_cg_res = res;
+  if (sf.cheb_learning && cs == GLIMS_OK) {
+    // (reduction the solve achieved; a warm-started solve's initial residual is not known to the host: what was asked for)
+    cheb_learn(h, its, (!s.warm && res > 0.0 && res < nr) ? res / nr : tol_lin / nr);
+    // PCG's iterations per decade in the tightest solve whose initial residual the host knows (not a warm-started one)
+    if (!s.warm && its > run.cheb.pcg_best_its && res > 0.0 && res < nr) {
+      run.cheb.pcg_best_its = (int)its;
+      run.cheb.pcg_its_per_decade = (double)its / std::log10(nr / res);
+    }
+  }
+  return cs;
+}
+
+// The sweep after a solve, with what it can carry: with b2 the guess pass of the next step's first solve (*next; used if the
+// sweep confirms this step), after the step's first solve the second solve's guess pass, or its start from zero (sf.fg2).
+static void sweep_after_solve(glims_ctx* h, const RunMemory& run, StepFacts& sf, const NewtonIt& s, double* norms, Mail* km,
+                              FusedGuess* next) {
+  GlFusedSweep fs;
+  FusedGuess fgn;
+  if (sf.fuse_on && s.use_cheb) {
+    h->fg_part.alloc((size_t)gl_rd_grid(h));
+    if (s.speculate && GL_FUSE_FIRST) {
+      // (not into a learning step -- it re-measures the interval with PCG solves --, nor where the midpoint correction
+      //  changes the right-hand side after the sweep)
+      const bool from_zero = !(sf.warm_on && run.have_c_old);   // (the next step's first solve)
+      if (run.cheb.age + 1 < GL_CHEB_RELEARN && (from_zero || !sf.midpoint)) {
+        cheb_interval(run.cheb, h->cheb_test_hi, sf.first_rtol, &fgn.ia, &fgn.ib);
+        fgn.kind = from_zero ? 2 : 1;
+      }
+      if (fgn.kind == 1) {
+        fgn.second_order = run.ws_depth >= 1 ? 1 : 0;
+        h->ws_c_old_next.alloc((size_t)h->n_nodes);
+        h->ws_du_next.alloc((size_t)h->n_nodes);
+        hipLaunchKernelGGL(k_ws_delta_spec, dim3(grid_exact(h->n_nodes)), dim3(256), 0, h->st, h->n_nodes,
+                           (const double*)h->c.p, (const double*)h->c_old.p, h->cg_u.p, (const double*)h->ws_du.p,
+                           h->ws_c_old_next.p, h->ws_du_next.p, fgn.second_order);
+      }
+    } else if (!s.speculate && GL_FUSE_SECOND && s.it == 0 && run.fg2_red > 0.0) {
+      // (the reduction the previous step's second solve was asked for stands in for this step's: it decides between the
+      //  loose and the tight interval only)
+      cheb_interval(run.cheb, h->cheb_test_hi, run.fg2_red, &fgn.ia, &fgn.ib);
+      fgn.kind = 2;
+      if (GL_D2_ORDER >= 1 && sf.warm_on && run.have_d2 && fgn.ib <= GL_D2_KAPPA_MAX * fgn.ia) {
+        fgn.kind = 1;
+        fgn.second_order = d2_order(run);
+        h->d2_prev.alloc((size_t)h->n_nodes);
+        hipLaunchKernelGGL(k_d2_guess_spec, dim3(grid_exact(h->n_own)), dim3(256), 0, h->st, h->n_own,
+                           (const double*)h->cheb_delta2.p, (const double*)h->d2_prev.p, h->cg_u.p, fgn.second_order);
+      }
+    }
+    if (fgn.kind != 0) {
+      GL_HIP(hipGetLastError());
+      fs = GlFusedSweep{fgn.kind, h->cg_u.p, h->cg_p.p, h->fg_part.p, 1.0 / ChebRec(fgn.ia, fgn.ib).theta};
+      fgn.valid = true;
+    }
+  }
+  rd_sweep(h, s.speculate ? h->b2.p : nullptr, norms, s.deferred ? km : nullptr, /*exchange_c=*/true,
+           /*mass_for_b2=*/s.speculate, fgn.valid ? &fs : nullptr, /*mass_for_b=*/false, &fgn.rr);
+  if (fgn.valid && !s.speculate) sf.fg2 = fgn;
+  if (fgn.valid && s.speculate) *next = fgn;   // (kept only if the sweep confirms the step: gl_step)
+  sf.base_is_current = true;   // a fresh Jacobian: A_0 = A(c) from here on
+  sf.rebase = false;
+}
+
+// End of a step: what the next step's second-solve guess rests on, the learnt interval, the forcing mode, the counters, and
+// `auto`'s choice of the preconditioner (*rd_mg).
+static void step_end(glims_ctx* h, RunMemory& run, const StepFacts& sf, int status, double nr, bool* rd_mg) {
+  ChebState& cb = run.cheb;
+  run.have_d2 = sf.d2_written && status == GLIMS_OK;
+  if (run.have_d2) {
+    run.d2_regime = sf.regime_now + (sf.d2_pcg ? GL_D2_REGIME_PCG : 0);
+    run.d2_r1 = sf.r1_now;
+  }
+  run.d2_depth = run.have_d2 ? std::min(2, run.d2_depth + 1) : 0;
+  if (sf.cheb_learning && status == GLIMS_OK && cb.learned > 0) {
+    if (cb.cost_ratio == 0.0) cb.cost_ratio = cheb_cost_ratio(h);
+    // (the interval forgets slowly: an upper end that one step's right-hand sides did not excite is not dropped at once)
+    auto commit = [](double& lmin, double& lmax, double& acc_lmin, double& acc_lmax) {
+      if (lmax > 0.0) {
+        acc_lmax = std::max(acc_lmax, 0.5 * (acc_lmax + lmax));
+        acc_lmin = std::min(acc_lmin, 0.5 * (acc_lmin + lmin));
+      }
+      lmin = acc_lmin;
+      lmax = acc_lmax;
+    };
+    commit(cb.lmin, cb.lmax, cb.acc_lmin, cb.acc_lmax);
+    if (cb.learned0 > 0) commit(cb.lmin0, cb.lmax0, cb.acc_lmin0, cb.acc_lmax0);
+    cb.valid = true;
+    cb.age = 0;
+    h->stats.cheb_lmin = cb.lmin;
+    h->stats.cheb_lmax = cb.lmax;
+  }
+  forcing_mode_after_step(run, sf.quad && status == GLIMS_OK && !sf.fixed_forcing, h->stats.newton_its - sf.newton0,
+                          sf.warm2_miss);
+  h->stats.last_newton_res = nr;
+  (status == GLIMS_OK ? h->stats.steps : h->stats.failed_steps)++;
+  if (h->adj.recording) gl_adjoint_after_step(h, status);   // D2D copy of c_n on the stream: no solver decision sees it
+  // `auto` corrects its prediction by what the step just showed: Jacobi-PCG iterations per Newton solve above the
+  // break-even -> the following steps use the hierarchy (the counts are global numbers: every rank switches together)
+  if (status == GLIMS_OK && h->opt.rd_precond == GLIMS_RD_PRECOND_AUTO && h->rd_precond_active == GLIMS_RD_PRECOND_JACOBI) {
+    const int64_t dn = h->stats.newton_its - sf.newton0, dc = h->stats.cg_its - sf.cg0;
+    if (dn > 0 && (double)dc / (double)dn > h->rd_break_even) {
+      if (sf.verbose)
+        fprintf(stderr, "glims RD preconditioner: %.1f Jacobi-PCG iterations per Newton solve observed (break-even %.0f): "
+                "multigrid V-cycle from the next step on\n", (double)dc / (double)dn, h->rd_break_even);
+      h->rd_precond_active = GLIMS_RD_PRECOND_MULTIGRID;
+      h->stats.rd_precond_used = GLIMS_RD_PRECOND_MULTIGRID;
+      *rd_mg = true;
+      if (!h->mg_rd.ready) gl_mg_setup_rd(h);
+      for (int& hint : run.cg_hint) hint = 0;   // the counts of the Jacobi solves say nothing about the new ones
+    }
+  }
+}
+
 int gl_step(glims_ctx* h, int n_steps) {
   GL_REQUIRE(h->is_setup, "glims_step before glims_setup");
   GL_REQUIRE(h->have_state, "glims_step before glims_set_state");
-  const DevPattern& p = h->pat;
-  const int64_t n = h->n_own;
   const glims_options& o = h->opt;
-  const bool extrapolate = (o.flags & GLIMS_FLAG_EXTRAPOLATE_GUESS) != 0;
-  const double* load = h->have_load_rd ? h->load_rd.p : nullptr;
+  RunMemory& run = h->run;
   int status = GLIMS_OK;
   h->timing_begin();
   if (h->rd_precond_active == 0) gl_rd_choose_precond(h);
   bool rd_mg = h->rd_precond_active == GLIMS_RD_PRECOND_MULTIGRID;
   if (rd_mg && !h->mg_rd.ready) gl_mg_setup_rd(h);
   const int64_t rd_cycles0 = h->mg_rd.cycles;
+  const bool verbose = getenv("GLIMS_VERBOSE") != nullptr, verbose_cheb = getenv("GLIMS_VERBOSE_CHEB") != nullptr;
   GL_HIP(hipEventRecord(h->ev_a, h->st));
   for (int step = 0; step < n_steps && status == GLIMS_OK; ++step) {
-    const int64_t newton0 = h->stats.newton_its, cg0 = h->stats.cg_its;
+    StepFacts sf{verbose, verbose_cheb, rd_mg};
     double norms[2] = {0.0, 0.0};
-    double nr;
-    // Dot-free linear solves (glims_options.rd_linear): Jacobi-preconditioned RD solves run the Chebyshev iteration on the
-    // interval measured by the PCG solves of a LEARNING step -- the first step of a run, every 32nd one after it, and the
-    // step after a solve had to be taken back.
-    glims_ctx::ChebState& cb = h->cheb;
-    const bool cheb_allowed = o.rd_linear != GLIMS_RD_LINEAR_PCG && !rd_mg;
-    if (cheb_allowed && cb.valid && ++cb.age >= 32) cb.valid = false;
-    const bool cheb_learning = cheb_allowed && !cb.valid;
-    if (cheb_learning) {
-      cb.learned = cb.learned0 = 0;
-      cb.pcg_best_its = 0;
-      cb.m_hint[0] = cb.m_hint[1] = 0;
-      h->cg_hist.alloc((size_t)2 * GL_CG_HIST);
-    }
-    // Fused guess pass: a sweep that is followed by a dot-free solve also runs that solve's first pass (k_rd_assemble_sg) --
-    // the guess pass of the step's first solve comes with the sweep that confirmed the previous step (h->fg1, lives and dies
-    // with `pending`), the second solve's guess (or start) pass with the sweep after the first solve (fg2).  Both are
-    // speculative: the guess is formed without committing the extrapolation's state, the interval is the one the solve is
-    // expected to use, and the solve takes the pass only if what it would have done itself is exactly that.
-    const bool fuse_on = (o.flags & GLIMS_FLAG_NO_FUSED_GUESS) == 0 && h->world == 1 && cheb_allowed && !extrapolate &&
-                         !h->jac32 && gl_rd_fusable(h);
-    if (!h->pending) h->fg1.valid = false;
-    const glims_ctx::FusedGuess fg1 = h->fg1;   // (this step's; whatever happens, it is not kept)
-    h->fg1.valid = false;
-    glims_ctx::FusedGuess fg2;
-    if (h->pending) {
-      // the sweep that verified the previous step already assembled A(c^n) and -R(c^n; c^n) for this one
-      nr = h->pending_r0;
-      h->pending = false;
-    } else {
-      // b = M c^n + load          ('u_previous1 * v1 * dx', simulation_tumor_growth.py:117)
-      // Where the iterate changes between this product and the sweep (new Dirichlet data, the extrapolated guess) it is formed
-      // here, on the old state; otherwise with the sweep (rd_sweep, mass_for_b: the same formula as a speculative sweep's b2).
-      const bool c_changes = h->dirichlet_c_dirty || h->dirichlet_c_exchange || extrapolate;
-      if (c_changes)
-        gl_launch_spmv(h, h->st, p.n_slices, nullptr, h->vM.p, h->c.p, h->b.p, nullptr, load, nullptr, nullptr, 0,
-                       nullptr);
-      // new Dirichlet data enter the ITERATE, after the old state went into b = M c^n: the reference's u_previous
-      // keeps the previous step's boundary values while the DirichletBC constrains the unknown
-      // (a rank lists its OWN constrained nodes; their ghost copies on the neighbours follow by a halo exchange that every
-      //  rank takes part in -- also the ranks that own no constrained node: dirichlet_c_exchange)
-      if (h->dirichlet_c_dirty) gl_apply_dirichlet_c(h);
-      if (h->dirichlet_c_exchange) {
-        gl_halo_exchange(h, h->c.p, 1);
-        h->dirichlet_c_exchange = false;
-        // new boundary values are a jump in the iterate: no warm start from the previous increments -- on EVERY rank (the
-        // rank that wrote the values has dropped its own in gl_apply_dirichlet_c; a rank that kept it would run a differently
-        // shaped first solve -- the warm-started dot-free solve reduces |r| first -- and the ranks' collectives would no longer pair up)
-        h->have_c_old = false;
-        h->have_d2 = false;
-      }
-      if (extrapolate) {
-        hipLaunchKernelGGL(k_extrapolate, dim3(grid_exact(n)), dim3(256), 0, h->st, n, h->c.p, h->c_old.p,
-                           h->have_fixed_c ? h->fixed_c.p : nullptr, h->stats.steps > 0 ? 1 : 0);
-        gl_halo_exchange(h, h->c.p, 1);
-      }
-      rd_sweep(h, nullptr, norms, nullptr, /*exchange_c=*/false, /*mass_for_b2=*/false, nullptr, /*mass_for_b=*/!c_changes);
-      nr = norms[0];
-    }
-    const double r0 = nr;
-    const double target = std::max(o.newton_atol, o.newton_rtol * r0);
-    // Residuals from the quadratic structure (default; GLIMS_FLAG_FULL_NEWTON: a sweep after every solve).  Between two
-    // sweeps the solves use A_0 = A(c_0), the Jacobian the last sweep assembled; after such a solve the residual is the
-    // Krylov residual plus dt N(a) delta (rd_quad_update: 48 % of a sweep's bytes, no Jacobian written).  A sweep runs
-    // after the step's first solve (see cheap_next), and
-    // (a) where convergence is expected -- it returns the TRUE residual and assembles the next step's system, as before;
-    // (b) when the cheap residual reports convergence without (a) having been predicted; (c) after an iteration whose
-    // residual is more than 5 x the linear solve's tolerance (strong nonlinearity: dt rho |c - c_0| is no longer small) --
-    // the sweep's Jacobian then becomes the new A_0.  Not combined with the extrapolated guess (no verifying sweep there).
-    // (nor with the single-precision Jacobian: the Krylov residual then belongs to the rounded operator)
-    // After a step in which (c) struck, the next eight steps run with sweeps only: where the nonlinearity is that strong a
-    // cheap evaluation buys an extra Newton iteration (dt rho = 0.6: 46 against 38 iterations in 8 steps without this).
-    if (h->nq_skip_steps > 0) --h->nq_skip_steps;
-    const bool quad = (o.flags & GLIMS_FLAG_FULL_NEWTON) == 0 && !extrapolate && !h->jac32 && h->nq_skip_steps == 0;
-    bool rebase = false;   // (c)
-    // Copies of iterates are made only where a cheap evaluation follows (known before the solve): after a sweep the base
-    // point c_0 IS the current iterate (`base_is_current`), so the first such copy serves as c_0 and as c_k (`ck_is_c0`);
-    // a second cheap evaluation in a row copies c_k into a buffer of its own.  One 8 B / node copy per cheap evaluation.
-    // Default forcing (round 4): the FIRST solve of a step decides whether two Newton iterations can be enough.  With the
-    // second solve's Jacobian at c_1, two iterations leave q_2 (r_1 / r_0)^2 r_0, q_2 = what the quadratic term alone leaves of
-    // a whole step (5e-4 late in config C4's run) -- below the Newton target 1e-10 r_0 only if r_1 <= 4e-4 r_0, i.e. with the
-    // first solve at 0.3 cg_rtol instead of cg_rtol (+0-1 PCG iterations) AND a first residual not dominated by the quadratic
-    // term.  Early in a run (small increments) the tolerance alone does it (mode 0: C4 steps 5-25 2.4 -> 2.1 iterations per
-    // step, 9.50 -> 9.37 ms; brain-like mesh 2.74 -> 2.65; C3 1.50 -> 1.46); later the quadratic term has to go too, which is
-    // what the midpoint correction of the first right-hand side does with the extrapolated increment (mode 1, one cheap pass:
-    // C4 steps 120-160 three solves -> two, 8.89 -> 8.19 ms; steps 300-340 9.38 -> 8.71; C3 1.51 -> 1.29; brain-like mesh
-    // 3.00 -> 2.70; profiles/r04_ab_midpoint.txt).  Either one alone is a loss there (tolerance alone: a third sweep, 9.67 ms;
-    // correction alone: 9.39).  The mode follows the outcome: 0 until two steps within a few take three iterations (one step in ten
-    // doing so is cheaper than a pass on every step), then 1; a step that
-    // takes three WITH the correction sends the next 16 back to cg_rtol without it (mode 2: strong nonlinearity, where the
-    // extra effort buys nothing); every 64th step in mode 1 tries mode 0 again; the first 8 steps of a run do not count (no
-    // increments to extrapolate from yet).  GLIMS_FLAG_FIXED_FORCING: cg_rtol for every solve, no correction (mode 2 throughout).
-    const bool fixed_forcing = (o.flags & GLIMS_FLAG_FIXED_FORCING) != 0;
-    const int nw_mode = (quad && !fixed_forcing) ? h->nw_mode : 2;
-    const bool midpoint = quad && nw_mode == 1;
-    const double first_rtol = (quad && nw_mode != 2) ? 0.3 * o.cg_rtol : o.cg_rtol;
-    bool base_is_current = true, ck_is_c0 = false;
-    // (margin 3: with 1 the cheap pass reported convergence unpredicted -- pass + confirming sweep -- in 14-28 % of the steps
-    //  of C4 / C3, with 3 in 2 %; with 10 the failed confirmations are back)
-    const double spec_margin = 3.0;
-    double ratio_est = h->nq_first_ratio;   // contraction of the previous Newton iteration (first one: of the last step's first)
-    if (quad) {
-      for (dvec<double>* v : {&h->nq_c0, &h->nq_ck}) v->alloc((size_t)h->n_nodes);
-      h->nq_ad.alloc((size_t)2 * h->n_nodes);
-    }
     double* last_ylast = nullptr;   // where the last dot-free solve left its correction
-    int regime_now = -1;            // passes of this step's first solve when it was a dot-free one, and the forcing mode
-    double r1_now = 0.0;            // the Newton residual this step's second solve started from
-    bool pcg_rest = false;          // a dot-free solve of this step under-delivered: its remaining solves run PCG
-    bool used_warm2 = false;        // this step's second solve started from the previous step's second correction
-    bool warm2_miss = false;        // ... and left the residual above the target (the third iteration is the guess's doing)
-    bool d2_pcg = false;            // ... the second solve was a PCG one
-    if (h->d2_off > 0) {
-      --h->d2_off;
-      h->have_d2 = false;
-    }
-    bool d2_written = false;        // this step's second solve was a dot-free one (its correction is in cheb_delta2)
+    double nr = step_begin(h, run, sf, norms);
     for (int it = 0;; ++it) {
-      if (!std::isfinite(nr)) {
-        status = GLIMS_NAN;
-        break;
-      }
-      if (nr <= target) break;
-      if (it >= o.newton_maxit) {
-        status = GLIMS_NOT_CONVERGED;
-        break;
-      }
+      if (!std::isfinite(nr)) status = GLIMS_NAN;
+      else if (nr > sf.target && it >= o.newton_maxit) status = GLIMS_NOT_CONVERGED;
+      if (status != GLIMS_OK || nr <= sf.target) break;
       // A(c_k) delta = -R(c_k);  the update is accumulated straight into c (x0 = 0  <=>  x = c_k)
-      // Forcing term.  The first solve of a step gets cg_rtol (1e-3): the quadratic term dt N(delta) delta that the step
-      // leaves behind is of that size anyway.  From the second solve on the Jacobian is the one of c_1 and Newton converges
-      // quadratically: the remainder after a solve from residual nr is ~ q nr^2 / r0, with q = the contraction the step's first
-      // iteration was observed to achieve (R_1 / r_0: what the quadratic term alone leaves).  Solving to cg_rtol x nr again
-      // would stop three decades short of that floor and spend a whole Newton iteration (evaluation, start-up of a solve) on
-      // them: the linear tolerance follows the floor instead (Eisenstat & Walker's "eta_k = O(|R_k|)").  Where Jacobi-PCG
-      // needs few iterations per decade (lattice configs: 3.1 Newton iterations per step either way) nothing changes; on the
-      // unstructured brain-like mesh a step takes 2.25 Newton iterations instead of 4 and 30 PCG iterations instead of 39
-      // (fewer restarts of the Krylov space): 3.86 -> 2.86 ms per step; C3 1.79 -> 1.65; C4 unchanged (10.7 vs 10.7-10.9).
-      // Safety factor on the predicted remainder: 0.3 (with 1.0 more steps need a third iteration: 2.95 / 1.68 ms).
-      // GLIMS_FLAG_FIXED_FORCING: cg_rtol always.
-      const bool adaptive_forcing = (o.flags & GLIMS_FLAG_FIXED_FORCING) == 0 && it >= 1;
-      const double floor_pred = std::min(0.5, std::max(1e-6, h->nq_first_ratio)) * nr * (nr / std::max(r0, 1e-300));
-      const double tol_lin = std::max(std::max(o.cg_atol, 0.5 * target),
-                                      adaptive_forcing ? std::min(o.cg_rtol * nr, 0.3 * floor_pred)
-                                                       : (it == 0 ? first_rtol : o.cg_rtol) * nr);
-      // what this iteration is expected to leave: the linear residual plus the quadratic remainder
-      const double pred_next = adaptive_forcing ? tol_lin + floor_pred : nr * std::min(0.5, std::max(1e-6, ratio_est));
-      // Newton converges quadratically here (the nonlinearity is exactly quadratic): once the residual before the
-      // solve was below ~sqrt(rtol) of the initial one, the next sweep will almost surely only confirm convergence,
-      // so let it also assemble the next step (costs one extra mass SpMV, saves a whole sweep per step).
-      // Otherwise the evaluation after this solve is the cheap one -- both known before the solve.
-      // With cheap evaluations a sweep that FAILS to confirm convergence is the expensive mistake (C4, steps 60-160 of the
-      // 500: four iterations per step, the third evaluation a sweep that did not converge), so the prediction there is
-      // "this iteration contracts like the previous one did": residual x last observed contraction <= target.
-      const bool speculate_next =
-          !extrapolate && (quad ? pred_next <= spec_margin * target
-                                : nr <= 1e-4 * std::sqrt(o.newton_rtol / 1e-10) * r0);
-      // (not after the step's FIRST solve, which takes the big step: its sweep moves A_0 to c_1, within ~1e-3 |delta_0| of
-      //  the step's solution -- with A(c^n) kept instead every later iteration contracts by dt rho |c - c^n| ~ 3e-3 only,
-      //  and the count per step rose from 3.35 to 3.65 at config C4)
-      const bool cheap_next = quad && !speculate_next && !rebase && it >= 1;
-      if (cheap_next) {   // c_k, the point the right-hand side belongs to (before a warm start moves c; ghosts are current)
-        ck_is_c0 = base_is_current;
-        base_is_current = false;
-        GL_HIP(hipMemcpyAsync(ck_is_c0 ? h->nq_c0.p : h->nq_ck.p, h->c.p, (size_t)h->n_nodes * sizeof(double),
+      // What is known before the solve: its tolerance, the evaluation that will follow it, and which iteration runs it.
+      // (slot 7: second solves that start from the guess -- their counts say nothing about the ones from zero)
+      NewtonIt s{it, /*slot=*/std::min(it, 6), nr};
+      s.f = forcing_term(o, it, nr, sf.r0, sf.target, sf.first_rtol, run.nq_first_ratio, sf.ratio_est);
+      s.speculate = speculate_next(o, sf.extrapolate, sf.quad, s.f.pred_next, sf.target, nr, sf.r0);
+      s.cheap = cheap_next(sf.quad, s.speculate, sf.rebase, it);
+      // Copies of iterates are made only where a cheap evaluation follows (known before the solve): after a sweep the base
+      // point c_0 IS the current iterate (`base_is_current`), so the first such copy serves as c_0 and as c_k (`ck_is_c0`);
+      // a second cheap evaluation in a row copies c_k into a buffer of its own.  One 8 B / node copy per cheap evaluation.
+      if (s.cheap) {   // c_k, the point the right-hand side belongs to (before a warm start moves c; ghosts are current)
+        sf.ck_is_c0 = sf.base_is_current;
+        sf.base_is_current = false;
+        GL_HIP(hipMemcpyAsync(sf.ck_is_c0 ? h->nq_c0.p : h->nq_ck.p, h->c.p, (size_t)h->n_nodes * sizeof(double),
                               hipMemcpyDeviceToDevice, h->st));
       }
-      bool use_cheb = cheb_allowed && cb.valid && !pcg_rest;
-      if (use_cheb && tol_lin < nr) {
-        double ia, ib;
-        cheb_interval(h, tol_lin / nr, &ia, &ib);
-        ChebRec rec(ia, ib);
-        const int passes = rec.iterations(tol_lin / nr) - (cheap_next ? 0 : 1);
-        if (passes > GL_CHEB_LONG) {
-          // an ill-conditioned system (stiff step with the Jacobi preconditioner forced): the Chebyshev bound grows like
-          // sqrt(kappa) per decade, PCG converges superlinearly there -- and a count cut off at GL_CHEB_MAX would be a weak solve
-          use_cheb = false;
-        } else if (it >= 1 && o.rd_linear == GLIMS_RD_LINEAR_AUTO && cb.cost_ratio > 0.0 && cb.pcg_its_per_decade > 0.0) {
-          // a tight solve: PCG's iterations (from its rate in the last learning step) against the passes the Chebyshev bound
-          // asks for, weighted by what each costs
-          const double its_pcg = std::ceil(cb.pcg_its_per_decade * std::log10(nr / tol_lin)) + 1.0;
-          if (its_pcg < 0.95 * cb.cost_ratio * passes) use_cheb = false;
-        }
+      s.use_cheb = sf.cheb_allowed && run.cheb.valid && !sf.pcg_rest;
+      if (s.use_cheb) {
+        // (the interval of this solve, computed once; where the tolerance is met already the reduction asked for is 1, which
+        //  picks the loose interval like any reduction above GL_CHEB_LOOSE)
+        const double tol = s.f.tol_lin;
+        cheb_interval(run.cheb, h->cheb_test_hi, tol / std::max(nr, tol), &s.ia, &s.ib);
+        const int passes = ChebRec(s.ia, s.ib).iterations(tol / nr) - (s.cheap ? 0 : 1);
+        if (tol < nr && prefer_pcg(run.cheb, o.rd_linear == GLIMS_RD_LINEAR_AUTO, it, passes, nr, tol)) s.use_cheb = false;
       }
-      bool warm = false, ws_fused = false;
-      bool take_folded = false;   // this solve's first pass came with the last sweep
-      if (it == 0 && (o.flags & GLIMS_FLAG_WARM_START) && !extrapolate) {   // both options own the c_old buffer
-        // initial guess of the first linear solve = the increment predicted from the previous steps' (k_ws_delta): same linear
-        // system, same solution, the Krylov iteration just starts closer.  One SpMV with the already assembled A(c^n).
-        h->ws_du.alloc((size_t)h->n_nodes);
-        // (dot-free solve: the guess u becomes direction 0 of the solve -- the product A u is then the solve's first operator
-        //  pass and the correction accumulates from u: cheb_solve, warm_u)
-        ws_fused = use_cheb && h->have_c_old;
-        const int ws_order = (h->have_c_old && h->ws_depth >= 1) ? 1 : 0;
-        if (fuse_on && fg1.valid && fg1.kind == 1 && ws_fused && !midpoint && fg1.second_order == ws_order) {
-          // (the guess is in cg_u, y_1 in cg_p: taken if the solve's interval is the one the sweep assumed)
-          double ia, ib;
-          cheb_interval(h, tol_lin / std::max(nr, tol_lin), &ia, &ib);
-          take_folded = ia == fg1.ia && ib == fg1.ib;
-        }
-        if (take_folded) {   // what k_ws_delta commits, written by k_ws_delta_spec
-          std::swap(h->c_old.p, h->ws_c_old_next.p);
-          std::swap(h->ws_du.p, h->ws_du_next.p);
-        } else {
-          hipLaunchKernelGGL(k_ws_delta, dim3(grid_exact(h->n_nodes)), dim3(256), 0, h->st, h->n_nodes, h->c.p,
-                             h->c_old.p, h->cg_u.p, h->ws_du.p, ws_order);
-        }
-        h->ws_depth = h->have_c_old ? 1 : 0;   // (ws_du holds a real increment from the second warm-started step on)
-        if (h->have_c_old) {
-          warm = true;
-          if (!ws_fused) {
-            gl_launch_spmv(h, h->st, p.n_slices, nullptr, h->vA.p, h->cg_u.p, h->cg_w.p,
-                           h->have_fixed_c ? h->fixed_c.p : nullptr, nullptr, nullptr, nullptr, 0, nullptr,
-                           h->jac32 ? h->vA32.p : nullptr);
-            hipLaunchKernelGGL(k_ws_apply, dim3(grid_exact(n)), dim3(256), 0, h->st, n, h->cg_r.p, h->cg_w.p, h->c.p,
-                               h->cg_u.p);
-          }
-          // Midpoint correction of the step's first right-hand side.  For the exactly quadratic residual the whole step
-          // delta* = c* - c_0 satisfies  A(c_0 + delta* / 2) delta* = -R(c_0)  -- the midpoint Jacobian solves the step in
-          // ONE linear solve -- i.e.  A(c_0) delta* = -R(c_0) - dt N(delta*) delta*.  With delta* predicted by the previous
-          // step's increment u (the warm-start vector) the right-hand side gets the term -dt N(u) u from one cheap pass:
-          // what is left of the quadratic term after the first solve is dt rho |delta* - u| |delta*| instead of
-          // dt rho |delta*|^2, so the first Newton iteration contracts as far as its linear tolerance lets it.
-          if (midpoint) {
-            h->nq_ad.alloc((size_t)2 * h->n_nodes);
-            hipLaunchKernelGGL(k_pair_of, dim3(grid_exact(h->n_nodes)), dim3(256), 0, h->st, h->n_nodes, h->cg_u.p,
-                               (float2*)h->nq_ad.p);
-            gl_rd_quad(h, h->nq_ad.p, h->cg_r.p, h->partials.p);
-            h->stats.rd_quad_updates++;
-            h->stats.midpoint_steps++;
-          }
-        }
-        h->have_c_old = true;
-      }
-      if (it == 0 && fuse_on && fg1.valid && fg1.kind == 2 && use_cheb && !ws_fused && tol_lin < nr) {
-        // (a first solve from zero whose start came with the sweep)
-        double ia, ib;
-        cheb_interval(h, tol_lin / std::max(nr, tol_lin), &ia, &ib);
-        take_folded = ia == fg1.ia && ib == fg1.ib;
-      }
-      if (it == 0 && getenv("GLIMS_VERBOSE_CHEB"))
-        fprintf(stderr, "  fused guess: step %lld first solve: payload %d kind %d order %d -- use_cheb %d ws_fused %d midpoint %d "
-                "mode %d -> folded %d\n", (long long)h->stats.steps, (int)fg1.valid, fg1.kind, fg1.second_order, (int)use_cheb,
-                (int)ws_fused, (int)midpoint, nw_mode, (int)take_folded);
+      if (it == 0) first_solve_guess(h, run, sf, s);
       CgVecs v{h->c.p, h->cg_r.p, h->cg_u.p, h->cg_w.p, h->cg_p.p, h->cg_s.p,
                h->dinv.p, h->vA.p, h->have_fixed_c ? h->fixed_c.p : nullptr, 1};
       if (h->jac32) v.vals32 = h->vA32.p;
@@ -2022,247 +2220,27 @@ int gl_step(glims_ctx* h, int n_steps) {
         v.mg = &h->mg_rd;
         v.mg_degree = o.rd_mg_smooth > 0 ? o.rd_mg_smooth : (h->mg_rd.lattice ? 1 : 3);
       }
-      int64_t its = 0;
-      double res = 0.0;
-      int slot = std::min(it, 6);   // (slot 7: second solves that start from the guess -- their counts say nothing about the ones from zero)
       int cs = GLIMS_OK;
-      bool deferred = false;
-      bool cheb_idle = false;   // a dot-free solve with nothing to do (see there)
-      ChebRun crun;
-      if (use_cheb) {
-        // |r| on entry: known to the host unless the solve starts from the warm-start guess -- then the count is chosen on the
-        // device from the norm its first pass measures
-        // A step's SECOND solve starts from the previous step's second correction: what the first solve leaves behind -- the
-        // quadratic remainder and the residual of a fixed polynomial applied to the extrapolation error -- changes by about a
-        // per cent from one step to the next (|R_1| over steps 20-28 of config C4: 1.31, 1.32, 1.34, 1.36, 1.40e-5), so the
-        // correction that removes it does too.
-        const bool second = it == 1;
-        h->cheb_delta.alloc((size_t)h->n_nodes);
-        if (second) h->cheb_delta2.alloc((size_t)h->n_nodes);
-        // (what the first solve leaves behind is a fixed polynomial of the operator applied to the extrapolation error: a first solve
-        //  of another degree leaves something else -- config C4 / 8, step 24: 3 -> 2 passes, |R_1| 1.8e-5 -> 2.8e-5 -- and the
-        //  second corrections before and after such a change do not continue each other)
-        // The same for the forcing mode (a midpoint-corrected first right-hand side leaves a residual twenty times smaller), and
-        // the check that needs no model: the correction is proportional to the residual it removes, so |R_1| has to continue too.
-        if (second && h->have_d2 && (regime_now != h->d2_regime || !(nr > 0.7 * h->d2_r1 && nr < 1.43 * h->d2_r1)))
-          h->have_d2 = false;
-        if (!h->have_d2) h->d2_depth = 0;   // (dropped since the last step: a new state, new boundary values, a take-back)
-        // Only on a narrow interval: the components that come back with the guess are the ones the solves' polynomial amplifies --
-        // outside the interval, where it grows like exp(degree) -- and a wide interval means long solves (random-point mesh, 1 M
-        // nodes, [0.18, 3.3]: 27-34 passes instead of 41-44 for eight steps, then a residual three times the target and a third
-        // Newton iteration per step for the sixteen after: 2.9 -> 3.6 ms per step; not used there).
-        bool narrow = false;
-        if (second && h->have_d2) {
-          double ia, ib;
-          cheb_interval(h, tol_lin / nr, &ia, &ib);
-          narrow = ib <= GL_D2_KAPPA_MAX * ia;
-        }
-        const bool warm2 = GL_D2_ORDER >= 1 && second && h->have_d2 && narrow && (o.flags & GLIMS_FLAG_WARM_START) && !extrapolate;
-        const int d2_order = (h->d2_depth >= 2 && GL_D2_ORDER >= 2) ? 1 : 0;
-        if (second && fuse_on && fg2.valid && !(!warm2 && tol_lin >= nr) &&
-            (fg2.kind == 1 ? (warm2 && fg2.second_order == d2_order) : !warm2)) {
-          double ia, ib;
-          cheb_interval(h, tol_lin / std::max(nr, tol_lin), &ia, &ib);
-          take_folded = ia == fg2.ia && ib == fg2.ib;
-        }
-        if (second && getenv("GLIMS_VERBOSE_CHEB"))
-          fprintf(stderr, "  fused guess: step %lld second solve: payload %d kind %d order %d [%.17g, %.17g] -- warm2 %d have_d2 %d narrow %d order %d "
-                  "regime %d/%d r1 %.3e/%.3e idle %d -> folded %d\n", (long long)h->stats.steps, (int)fg2.valid, fg2.kind,
-                  fg2.second_order, fg2.ia, fg2.ib, (int)warm2, (int)h->have_d2, (int)narrow, d2_order, regime_now, h->d2_regime, nr,
-                  h->d2_r1, (int)(!warm2 && tol_lin >= nr), (int)take_folded);
-        fg2.valid = false;
-        if (second) h->fg2_red = tol_lin / std::max(nr, tol_lin);   // (what the next step's sweep sizes its guess pass by)
-        if (warm2) {
-          // (linearly extrapolated from the last two; the guess goes where the first solve's went: cg_u is free again)
-          h->d2_prev.alloc((size_t)h->n_nodes);
-          if (take_folded) {
-            // (the guess is in cg_u already, k_d2_guess_spec; d_prev = d by exchanging the buffers: the solve rewrites cheb_delta2)
-            std::swap(h->cheb_delta2.p, h->d2_prev.p);
-          } else {
-            hipLaunchKernelGGL(k_d2_guess, dim3(grid_exact(n)), dim3(256), 0, h->st, n, (const double*)h->cheb_delta2.p,
-                               h->d2_prev.p, h->cg_u.p, d2_order);
-            GL_HIP(hipGetLastError());
-          }
-          if (h->world > 1) gl_halo_exchange(h, h->cg_u.p, 1);   // (corrections are kept by their row owners: ghosts)
-        }
-        // A solve from zero whose tolerance is already met (tol_lin >= |R_k|: a cg_atol above the residual) runs no pass and
-        // writes no correction: nothing is enqueued, c and the kept corrections stay as they are, nothing can be taken back --
-        // PCG's zero iterations.  (A warm-started solve still runs: its count is chosen on the device from |b - A u|.)
-        cheb_idle = !(ws_fused || warm2) && tol_lin >= nr;
-        if (!cheb_idle) {
-          last_ylast = second ? h->cheb_delta2.p : h->cheb_delta.p;
-          if (second) {
-            d2_written = true;
-            r1_now = nr;
-            used_warm2 = warm2;
-          }
-          crun = cheb_solve(h, v, tol_lin, nr, nr, cheap_next, (ws_fused || warm2) ? h->cg_u.p : (const double*)nullptr,
-                            last_ylast, second ? 1 : 0, take_folded, second ? fg2.rr : fg1.rr);
-        }
-        deferred = crun.planned;
-        if (crun.host_count) {
-          // (the bookkeeping of a device-side count, fed at once instead of from the next mail -- see `deferred && use_cheb` below)
-          cb.m_hint[second ? 1 : 0] = std::max(1, crun.m);
-          if (it == 0) regime_now = crun.m + 100 * nw_mode;
-          if (second && crun.m >= crun.bound) d2_written = false;
-          h->stats.cg_its += crun.passes;
-          h->stats.cheb_its += crun.passes;
-          h->stats.last_cg_res = tol_lin;
-        } else if (!deferred && !cheb_idle) {
-          h->stats.cg_its += crun.passes;
-          h->stats.cheb_its += crun.passes;
-          h->stats.last_cg_res = tol_lin;
-          if (it == 0) regime_now = 1000 + crun.passes + 100 * nw_mode;   // (a cold first solve: not the same thing as a warm one of that count)
-        }
-      } else {
-        if (cheb_learning) v.hist = h->cg_hist.p;
-        // The second solve's guess with PCG (the brain-like mesh's tight solves, multigrid-preconditioned stiff steps,
-        // rd_linear = PCG): same guess, applied like the first solve's (r -= A u, c += u).  PCG accumulates into c, so the
-        // correction is recovered as c after - c before.  No feedback problem here (PCG damps whatever the guess carries); the
-        // learning steps' solves start from zero (their Lanczos coefficients are to describe the right-hand side itself).
-        const bool second_pcg = it == 1 && !cheb_learning && (o.flags & GLIMS_FLAG_WARM_START) && !extrapolate;
-        if (second_pcg) {
-          h->cheb_delta2.alloc((size_t)h->n_nodes);
-          const int regime_pcg = regime_now + 500;
-          if (h->have_d2 && (regime_pcg != h->d2_regime || !(nr > 0.7 * h->d2_r1 && nr < 1.43 * h->d2_r1))) h->have_d2 = false;
-          if (!h->have_d2) h->d2_depth = 0;
-          const bool warm2 = GL_D2_ORDER >= 1 && h->have_d2;
-          if (warm2) {
-            h->d2_prev.alloc((size_t)h->n_nodes);
-            hipLaunchKernelGGL(k_d2_guess, dim3(grid_exact(n)), dim3(256), 0, h->st, n, (const double*)h->cheb_delta2.p,
-                               h->d2_prev.p, h->cg_u.p, (h->d2_depth >= 2 && GL_D2_ORDER >= 2) ? 1 : 0);
-            if (h->world > 1) gl_halo_exchange(h, h->cg_u.p, 1);
-          }
-          GL_HIP(hipMemcpyAsync(h->cheb_delta2.p, h->c.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, h->st));
-          if (warm2) {
-            gl_launch_spmv(h, h->st, p.n_slices, nullptr, h->vA.p, h->cg_u.p, h->cg_w.p,
-                           h->have_fixed_c ? h->fixed_c.p : nullptr, nullptr, nullptr, nullptr, 0, nullptr,
-                           h->jac32 ? h->vA32.p : nullptr);
-            // (applied only if it lowers the residual -- decided on the device from two sums: on stiff steps, where the solution
-            //  does not evolve smoothly from step to step, the extrapolated correction can be worse than none; 5.3 -> 5.6
-            //  V-cycle-preconditioned iterations per solve at 1 M rows with the guess always applied)
-            const unsigned gg = grid_for(n, 256, 1024);
-            hipLaunchKernelGGL(k_guess_norms, dim3(gg), dim3(256), 0, h->st, n, (const double*)h->cg_r.p, (const double*)h->cg_w.p,
-                               h->partials.p);
-            reduce_partials(h, (int)gg, 2, nullptr);
-            allreduce_sum(h, h->red.p, 2);
-            hipLaunchKernelGGL(k_ws_apply_if, dim3(grid_exact(n)), dim3(256), 0, h->st, n, h->cg_r.p, (const double*)h->cg_w.p,
-                               h->c.p, (const double*)h->cg_u.p, (const double*)h->red.p);
-            GL_HIP(hipGetLastError());
-          }
-          d2_written = true;
-          d2_pcg = true;
-          r1_now = nr;
-          used_warm2 = warm2;
-          if (warm2) {
-            slot = 7;
-            if (h->cg_hint[7] <= 0) h->cg_hint[7] = h->cg_hint[1];   // (a first count to bound the launches: the solve from zero's)
-          }
-        }
-        cs = cg_solve(h, v, tol_lin, o.cg_maxit, h->cg_hint[slot], &its, &res, /*defer=*/!cheb_learning);
-        if (second_pcg) {
-          hipLaunchKernelGGL(k_d2_from_state, dim3(grid_exact(n)), dim3(256), 0, h->st, n, (const double*)h->c.p,
-                             h->cheb_delta2.p);
-          GL_HIP(hipGetLastError());
-        }
-        deferred = its < 0;
-        if (!deferred) {
-          h->cg_hint[slot] = (int)its;
-          h->stats.cg_its += its;
-          h->stats.last_cg_res = res;
-          if (cheb_learning && cs == GLIMS_OK) {
-            // (reduction the solve achieved; a warm-started solve's initial residual is not known to the host: what was asked for)
-            cheb_learn(h, its, (!warm && res > 0.0 && res < nr) ? res / nr : tol_lin / nr);
-            // PCG's iterations per decade in the tightest solve whose initial residual the host knows (not a warm-started one)
-            if (!warm && its > cb.pcg_best_its && res > 0.0 && res < nr) {
-              cb.pcg_best_its = (int)its;
-              cb.pcg_its_per_decade = (double)its / std::log10(nr / res);
-            }
-          }
-        }
-      }
+      if (s.use_cheb) solve_cheb(h, run, sf, s, v, &last_ylast);
+      else cs = solve_pcg(h, run, sf, s, v);
       h->stats.newton_its++;
       if (cs != GLIMS_OK) {
         gl_halo_exchange(h, h->c.p, 1);   // ghosts of c current again
         status = cs;
         break;
       }
-      const bool speculate = speculate_next, cheap = cheap_next;   // (decided before the solve, see there)
       Mail km;
-      const double nr_before = nr;
-      if (cheap) {
-        rd_quad_update(h, ck_is_c0 ? h->nq_c0.p : h->nq_ck.p, norms, deferred ? &km : nullptr);
-      } else {
-        // What this sweep can carry: with b2 the guess pass of the next step's first solve (used if the sweep confirms this
-        // step), after the step's first solve the second solve's guess pass, or its start from zero.
-        GlFusedSweep fs;
-        glims_ctx::FusedGuess fgn;
-        const bool warm_on = (o.flags & GLIMS_FLAG_WARM_START) != 0;
-        if (fuse_on && use_cheb) {
-          const int ns = gl_rd_grid(h);
-          h->fg_part.alloc((size_t)ns);
-          if (speculate && GL_FUSE_FIRST) {
-            // (not into a learning step, nor where the midpoint correction changes the right-hand side after the sweep)
-            if (cb.age + 1 >= 32) {
-              // (the next step re-measures the interval with PCG solves)
-            } else if (!(warm_on && h->have_c_old)) {   // (the next step's first solve starts from zero)
-              cheb_interval(h, first_rtol, &fgn.ia, &fgn.ib);
-              fgn.kind = 2;
-            } else if (!midpoint) {
-              cheb_interval(h, first_rtol, &fgn.ia, &fgn.ib);
-              fgn.kind = 1;
-              fgn.second_order = h->ws_depth >= 1 ? 1 : 0;
-              h->ws_c_old_next.alloc((size_t)h->n_nodes);
-              h->ws_du_next.alloc((size_t)h->n_nodes);
-              hipLaunchKernelGGL(k_ws_delta_spec, dim3(grid_exact(h->n_nodes)), dim3(256), 0, h->st, h->n_nodes,
-                                 (const double*)h->c.p, (const double*)h->c_old.p, h->cg_u.p, (const double*)h->ws_du.p,
-                                 h->ws_c_old_next.p, h->ws_du_next.p, fgn.second_order);
-            }
-          } else if (!speculate && GL_FUSE_SECOND && it == 0 && h->fg2_red > 0.0) {
-            // (the reduction the previous step's second solve was asked for stands in for this step's: it decides between the
-            //  loose and the tight interval only)
-            cheb_interval(h, h->fg2_red, &fgn.ia, &fgn.ib);
-            if (GL_D2_ORDER >= 1 && warm_on && h->have_d2 && fgn.ib <= GL_D2_KAPPA_MAX * fgn.ia) {
-              fgn.kind = 1;
-              fgn.second_order = (h->d2_depth >= 2 && GL_D2_ORDER >= 2) ? 1 : 0;
-              h->d2_prev.alloc((size_t)h->n_nodes);
-              hipLaunchKernelGGL(k_d2_guess_spec, dim3(grid_exact(n)), dim3(256), 0, h->st, n, (const double*)h->cheb_delta2.p,
-                                 (const double*)h->d2_prev.p, h->cg_u.p, fgn.second_order);
-            } else {
-              fgn.kind = 2;
-            }
-          }
-          if (fgn.kind != 0) {
-            GL_HIP(hipGetLastError());
-            fs.kind = fgn.kind;
-            fs.u = h->cg_u.p;
-            fs.y1 = h->cg_p.p;
-            fs.part = h->fg_part.p;
-            fs.c2 = 1.0 / ChebRec(fgn.ia, fgn.ib).theta;
-            fgn.valid = true;
-          }
-        }
-        rd_sweep(h, speculate ? h->b2.p : nullptr, norms, deferred ? &km : nullptr, /*exchange_c=*/true,
-                 /*mass_for_b2=*/speculate, fgn.valid ? &fs : nullptr, /*mass_for_b=*/false, &fgn.rr);
-        if (fgn.valid && !speculate) fg2 = fgn;
-        if (fgn.valid && speculate) h->fg1 = fgn;   // (kept only if the sweep confirms the step, see below)
-        base_is_current = true;   // a fresh Jacobian: A_0 = A(c) from here on
-        rebase = false;
-      }
-      if (deferred && use_cheb) {   // the count the device chose for the warm-started solve
+      FusedGuess next_guess;
+      if (s.cheap) rd_quad_update(h, sf.ck_is_c0 ? h->nq_c0.p : h->nq_ck.p, norms, s.deferred ? &km : nullptr);
+      else sweep_after_solve(h, run, sf, s, norms, &km, &next_guess);
+      if (s.deferred && s.use_cheb) {   // the count the device chose for the warm-started solve came with the mail
         const int64_t m_dev = (int64_t)km.info[0];
-        cb.m_hint[it == 1 ? 1 : 0] = (int)std::max<int64_t>(1, m_dev);
-        if (it == 0) regime_now = (int)m_dev + 100 * nw_mode;
-        // (a count that used up its launches: the guess was further off than the last ones -- not a basis for the next step's)
-        if (it == 1 && m_dev >= crun.passes) d2_written = false;
-        const int64_t passes = std::max<int64_t>(0, std::min<int64_t>(crun.passes, (cheap ? m_dev : m_dev - 1) + 1));
-        h->stats.cg_its += passes;
-        h->stats.cheb_its += passes;
-        h->stats.last_cg_res = tol_lin;
-      } else if (deferred) {
+        const int64_t passes = std::max<int64_t>(0, std::min<int64_t>(s.crun.passes, (s.cheap ? m_dev : m_dev - 1) + 1));
+        book_cheb_count(h, run, sf, s, m_dev, s.crun.passes, passes);
+      } else if (s.deferred) {
         // the linear solve's outcome arrives with the sweep: a solve that used up its hint + 2 iterations simply
         // was a slightly weaker Newton step (the residual below decides); give it more room next time
-        h->cg_hint[slot] = km.done == 1 ? (int)km.info[0] : (int)km.info[0] + 2;
+        run.cg_hint[s.slot] = km.done == 1 ? (int)km.info[0] : (int)km.info[0] + 2;
         if (km.done != 1) h->stats_defer_miss++;
         h->stats.cg_its += (int64_t)km.info[0];
         h->stats.last_cg_res = std::sqrt(km.info[1]);
@@ -2270,179 +2248,76 @@ int gl_step(glims_ctx* h, int n_steps) {
           status = GLIMS_NAN;
           break;
         }
-        if (km.done == 3) h->cg_hint[slot] = 0;   // breakdown: next time take the polled path
+        if (km.done == 3) run.cg_hint[s.slot] = 0;   // breakdown: next time take the polled path
       }
       nr = norms[0];
-      if (use_cheb && getenv("GLIMS_VERBOSE_CHEB")) {
-        const char* count_by = crun.planned ? "planned" : (crun.host_count ? "host-m" : "host");
-        const double m_shown = crun.planned ? km.info[0] : (crun.host_count ? (double)crun.m : -1.0);
+      if (s.use_cheb && verbose_cheb) {
+        const char* count_by = s.crun.planned ? "planned" : (s.crun.host_count ? "host-m" : "host");
+        const double m_shown = s.crun.planned ? km.info[0] : (s.crun.host_count ? (double)s.crun.m : -1.0);
         fprintf(stderr, "  cheb: step %lld it %d  %.3e -> %.3e  tol_lin %.3e target %.3e  %s passes %d (m_dev %g) %s\n",
-                (long long)h->stats.steps, it, nr_before, nr, tol_lin, target, count_by, crun.passes, m_shown,
-                cheap ? "cheap" : (speculate ? "sweep+spec" : "sweep"));
+                (long long)h->stats.steps, it, s.nr, nr, s.f.tol_lin, sf.target, count_by, s.crun.passes, m_shown,
+                s.cheap ? "cheap" : (s.speculate ? "sweep+spec" : "sweep"));
       }
-      if (use_cheb && !cheb_idle && !(std::isfinite(nr) && (nr <= 0.5 * nr_before || nr <= target))) {
-        // The Newton residual did not contract: part of the right-hand side lies outside the interval (the Chebyshev polynomial
-        // grows there).  Take the correction back (it is still in cheb_delta), drop the interval -- this step's remaining
-        // solves and the next step's run PCG and measure it again -- and repeat the iteration from a fresh sweep.
-        if (getenv("GLIMS_VERBOSE"))
+      const bool ran_cheb = s.use_cheb && !s.cheb_idle;
+      if (ran_cheb && !(std::isfinite(nr) && (nr <= 0.5 * s.nr || nr <= sf.target))) {
+        // Take-back.  The Newton residual did not contract: part of the right-hand side lies outside the interval (the
+        // Chebyshev polynomial grows there).  Take the correction back (it is still in last_ylast), drop the interval -- this
+        // step's remaining solves and the next step's run PCG and measure it again -- and repeat the iteration from a fresh sweep.
+        if (verbose)
           fprintf(stderr, "glims dot-free solves: step %lld, Newton iteration %d: residual %.3e -> %.3e (target %.3e, linear tolerance "
-                  "%.3e, %s count, %d passes enqueued) -- taken back, PCG from here\n", (long long)h->stats.steps, it, nr_before, nr,
-                  target, tol_lin, crun.planned ? "device-side" : "host-side", crun.passes);
-        hipLaunchKernelGGL(k_sub_inplace, dim3(grid_exact(n)), dim3(256), 0, h->st, n, h->c.p, (const double*)last_ylast);
-        d2_written = false;
-        h->have_d2 = false;
-        if (it == 1 && used_warm2) {
-          h->d2_off = h->d2_backoff;
-          h->d2_backoff = std::min(256, 2 * h->d2_backoff);
-          h->d2_good = 0;
-        }
+                  "%.3e, %s count, %d passes enqueued) -- taken back, PCG from here\n", (long long)h->stats.steps, it, s.nr, nr,
+                  sf.target, s.f.tol_lin, s.crun.planned ? "device-side" : "host-side", s.crun.passes);
+        hipLaunchKernelGGL(k_sub_inplace, dim3(grid_exact(h->n_own)), dim3(256), 0, h->st, h->n_own, h->c.p, (const double*)last_ylast);
+        sf.d2_written = false;
+        run.have_d2 = false;
+        if (it == 1 && sf.used_warm2) d2_missed(run);
         GL_HIP(hipGetLastError());
-        cb.valid = false;
-        cb.lmax0 = cb.lmin0 = 0.0;   // (the loose interval is re-learnt from scratch)
+        run.cheb.valid = false;
+        run.cheb.lmax0 = run.cheb.lmin0 = 0.0;   // (the loose interval is re-learnt from scratch)
         h->stats.cheb_fallbacks++;
-        h->pending = false;
-        h->fg1.valid = false;
-        fg2.valid = false;
+        h->prepared.drop();
+        sf.fg2.valid = false;
         rd_sweep(h, nullptr, norms, nullptr, /*exchange_c=*/true);
+        sf.base_is_current = true;
+        sf.rebase = false;
         nr = norms[0];
-        base_is_current = true;
-        rebase = false;
         continue;
       }
-      // A second solve that started from the guess and left the residual above the target (by any margin): what it left is more
-      // likely the guess's doing (components that the previous steps' solves amplified instead of damping come back with it) than
-      // the quadratic remainder -- the third solve runs PCG, and the guess stays unused for a while (the solves from zero in
-      // between start clean): 8 steps, doubling with every miss.
-      if (it == 1 && used_warm2 && std::isfinite(nr)) {
-        if (nr > target) {
-          pcg_rest = true;
-          d2_written = false;
-          warm2_miss = true;
-          h->d2_off = h->d2_backoff;
-          h->d2_backoff = std::min(256, 2 * h->d2_backoff);
-          h->d2_good = 0;
-        } else if (++h->d2_good >= 32) {
-          h->d2_backoff = 8;
-        }
+      // A second solve that started from the guess and left the residual above the target: the third solve runs PCG, and the
+      // guess stays unused for a while (d2_missed)
+      const bool guess_judged = it == 1 && sf.used_warm2 && std::isfinite(nr);
+      if (guess_judged && nr <= sf.target) d2_hit(run);
+      if (guess_judged && nr > sf.target) {
+        sf.pcg_rest = sf.warm2_miss = true;
+        sf.d2_written = false;
+        d2_missed(run);
       }
-      // A dot-free solve that contracts, but far less than it was sized for (10 x its tolerance plus the quadratic remainder),
-      // has an interval that no longer fits what the right-hand sides excite: not a take-back -- the Newton iteration copes --
-      // but two of them in a row make the next step a learning step instead of waiting for the 32nd.
-      if (use_cheb && !cheb_idle && it >= 1 && std::isfinite(nr)) {
-        const bool weak = nr > target && nr > 10.0 * (tol_lin + (adaptive_forcing ? floor_pred : 0.0));
-        cb.weak = weak ? cb.weak + 1 : 0;
-        if (cb.weak >= 2) {
-          cb.age = 1 << 20;
-          cb.weak = 0;
-        }
+      if (ran_cheb && it >= 1 && std::isfinite(nr)) count_weak_solve(run.cheb, nr, sf.target, s.f.tol_lin + (s.f.adaptive ? s.f.floor_pred : 0.0));
+      if (std::isfinite(nr) && s.nr > 0.0) {
+        sf.ratio_est = nr / s.nr;
+        if (it == 0) run.nq_first_ratio = sf.ratio_est;
       }
-      if (std::isfinite(nr) && nr_before > 0.0) {
-        ratio_est = nr / nr_before;
-        if (it == 0) h->nq_first_ratio = ratio_est;
+      bool confirming = s.speculate;   // the last sweep also assembled the next step
+      if (s.cheap && std::isfinite(nr) && nr <= sf.target) {
+        // (b) converged by the cheap residual, unpredicted: the true residual and the next step's system from a sweep
+        rd_sweep(h, h->b2.p, norms, nullptr, /*exchange_c=*/false, /*mass_for_b2=*/true);
+        sf.base_is_current = true;
+        nr = norms[0];
+        confirming = true;
+      } else if (s.cheap && std::isfinite(nr) && needs_rebase(o, s.f, nr, s.nr)) {
+        sf.rebase = true;   // (c)
+        run.nq_skip_steps = GL_REBASE_SKIP;
+        h->stats.rebase_events++;
       }
-      if (cheap && std::isfinite(nr)) {
-        if (nr <= target) {
-          // (b) converged by the cheap residual, unpredicted: the true residual and the next step's system from a sweep
-          rd_sweep(h, h->b2.p, norms, nullptr, /*exchange_c=*/false, /*mass_for_b2=*/true);
-          base_is_current = true;
-          nr = norms[0];
-          if (std::isfinite(nr) && nr <= target) {
-            std::swap(h->b.p, h->b2.p);
-            std::swap(h->cg_r.p, h->cg_r2.p);
-            h->pending = true;
-            h->pending_r0 = norms[1];
-            break;
-          }
-        } else if (nr > 5.0 * (adaptive_forcing ? std::max(tol_lin, floor_pred) : o.cg_rtol * nr_before)) {
-          // (c): the solve was asked for cg_rtol (cheap evaluations only happen where that bound, not the Newton target,
-          // set its tolerance); a residual five times larger is the Jacobian's age showing
-          rebase = true;
-          h->nq_skip_steps = 9;
-          h->stats.rebase_events++;
-        }
-      }
-      if (speculate && std::isfinite(nr) && nr <= target) {
+      if (confirming && std::isfinite(nr) && nr <= sf.target) {
+        // Accept the prepared step: the sweep confirmed this one, its second system is the next step's first.
         std::swap(h->b.p, h->b2.p);
         std::swap(h->cg_r.p, h->cg_r2.p);
-        h->pending = true;
-        h->pending_r0 = norms[1];
+        h->prepared = PreparedStep{true, norms[1], next_guess};
         break;
       }
-      h->fg1.valid = false;   // (not confirmed: the next solve belongs to this step)
     }
-    ++h->nw_steps;
-    h->have_d2 = d2_written && status == GLIMS_OK;
-    if (h->have_d2) {
-      h->d2_regime = regime_now + (d2_pcg ? 500 : 0);
-      h->d2_r1 = r1_now;
-    }
-    h->d2_depth = h->have_d2 ? std::min(2, h->d2_depth + 1) : 0;
-    if (cheb_learning && status == GLIMS_OK && cb.learned > 0) {
-      if (cb.cost_ratio == 0.0) cb.cost_ratio = cheb_cost_ratio(h);
-      // (the interval forgets slowly: an upper end that one step's right-hand sides did not excite is not dropped at once)
-      if (cb.lmax > 0.0) {
-        cb.acc_lmax = std::max(cb.acc_lmax, 0.5 * (cb.acc_lmax + cb.lmax));
-        cb.acc_lmin = std::min(cb.acc_lmin, 0.5 * (cb.acc_lmin + cb.lmin));
-      }
-      cb.lmin = cb.acc_lmin;
-      cb.lmax = cb.acc_lmax;
-      if (cb.learned0 > 0) {
-        if (cb.lmax0 > 0.0) {
-          cb.acc_lmax0 = std::max(cb.acc_lmax0, 0.5 * (cb.acc_lmax0 + cb.lmax0));
-          cb.acc_lmin0 = std::min(cb.acc_lmin0, 0.5 * (cb.acc_lmin0 + cb.lmin0));
-        }
-        cb.lmin0 = cb.acc_lmin0;
-        cb.lmax0 = cb.acc_lmax0;
-      }
-      cb.valid = true;
-      cb.age = 0;
-      h->stats.cheb_lmin = cb.lmin;
-      h->stats.cheb_lmax = cb.lmax;
-    }
-    // (the first steps of a run have no increments to extrapolate from and take three iterations whatever the mode: they do
-    //  not speak for it)
-    if (quad && status == GLIMS_OK && !fixed_forcing && h->nw_steps > 8) {
-      // (a third iteration that the second solve's guess caused says nothing about the forcing mode)
-      const int64_t count = h->stats.newton_its - newton0 - (warm2_miss ? 1 : 0);
-      if (h->nw_mode == 0) {
-        // (one step in ten taking a third iteration is cheaper than the correction's pass on every step: two within a few)
-        h->nw_hold = count >= 3 ? h->nw_hold + 4 : std::max(0, h->nw_hold - 1);
-        if (h->nw_hold >= 6) {
-          h->nw_mode = 1;
-          h->nw_since = h->nw_hold = 0;
-        }
-      } else if (h->nw_mode == 1) {
-        if (count >= 3) {
-          h->nw_mode = 2;
-          h->nw_hold = 16;
-        } else if (++h->nw_since % 64 == 0) {
-          h->nw_mode = 0;
-          h->nw_hold = 0;
-        }
-      } else if (--h->nw_hold <= 0) {
-        h->nw_mode = 1;
-        h->nw_since = 0;
-      }
-    }
-    h->stats.last_newton_res = nr;
-    if (status == GLIMS_OK) h->stats.steps++;
-    else h->stats.failed_steps++;
-    if (h->adj.recording) gl_adjoint_after_step(h, status);   // D2D copy of c_n on the stream: no solver decision sees it
-    // `auto` corrects its prediction by what the step just showed: Jacobi-PCG iterations per Newton solve above the
-    // break-even -> the following steps use the hierarchy (the counts are global numbers: every rank switches together)
-    if (status == GLIMS_OK && o.rd_precond == GLIMS_RD_PRECOND_AUTO && h->rd_precond_active == GLIMS_RD_PRECOND_JACOBI) {
-      const int64_t dn = h->stats.newton_its - newton0, dc = h->stats.cg_its - cg0;
-      if (dn > 0 && (double)dc / (double)dn > h->rd_break_even) {
-        if (getenv("GLIMS_VERBOSE"))
-          fprintf(stderr, "glims RD preconditioner: %.1f Jacobi-PCG iterations per Newton solve observed (break-even %.0f): "
-                  "multigrid V-cycle from the next step on\n", (double)dc / (double)dn, h->rd_break_even);
-        h->rd_precond_active = GLIMS_RD_PRECOND_MULTIGRID;
-        h->stats.rd_precond_used = GLIMS_RD_PRECOND_MULTIGRID;
-        rd_mg = true;
-        if (!h->mg_rd.ready) gl_mg_setup_rd(h);
-        for (int& hint : h->cg_hint) hint = 0;   // the counts of the Jacobi solves say nothing about the new ones
-      }
-    }
+    step_end(h, run, sf, status, nr, &rd_mg);
   }
   GL_HIP(hipEventRecord(h->ev_b, h->st));
   GL_HIP(hipEventSynchronize(h->ev_b));
@@ -2467,7 +2342,7 @@ __global__ void k_mass_dinv(int64_t n_own, const int64_t* __restrict__ slice_ptr
 int gl_project(glims_ctx* h, double* rhs, double* x, double rtol) {
   GL_REQUIRE(h->is_setup, "glims_project before glims_setup");
   const int64_t n = h->n_own;
-  h->pending = false;   // dinv and the PCG work vectors are shared with the time stepper
+  h->prepared.drop();   // dinv and the PCG work vectors are shared with the time stepper
   hipLaunchKernelGGL(k_mass_dinv, dim3(grid_exact(n)), dim3(256), 0, h->st, n, h->pat.slice_ptr.p, h->pat.diag_k.p,
                      h->vM.p, h->dinv.p);
   const unsigned gd = grid_for(n, 256, 1024);
