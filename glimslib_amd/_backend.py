@@ -139,6 +139,7 @@ SIGNATURES = {
     "glims_reset_stats": (C.c_int, [_h]),
     "glims_apply": (C.c_int, [_h, C.c_int, _dp, _dp, C.c_int, _dp]),
     "glims_rd_residual": (C.c_int, [_h, _dp, _dp, _dp]),
+    "glims_peek_partials": (C.c_int, [_h, _dp]),
     "glims_get_numbering": (C.c_int, [_h, _i32p]),
     "glims_pattern_checksum": (C.c_int, [_h, C.POINTER(C.c_uint64)]),
     "glims_snapshot_save": (C.c_int, [_h, _i64p]),
@@ -319,7 +320,10 @@ class Handle:
 
     # -- operator hooks --------------------------------------------------------------------------
     def apply(self, which, x, reps=1):
-        """which: 0 A(c), 1 S, 2 M, 3 K_el, 4 G; 10 = M x + rd_load as the stepping path's sweep forms it (glims_hip.h).
+        """which: 0 A(c), 1 S, 2 M, 3 K_el, 4 G; 7 the matrix-free A(c) x; 8 the assembly sweep at c = x with b = 0,
+        y = -1/2 (A(x) + S) x; 9 the quadratic-term pass with a = delta = x, y = -reps dt N(x) x; 10 = M x + rd_load as the
+        stepping path's sweep forms it; 11 the quadratic-term pass prepared as the stepper prepares it from x and the state c,
+        y = -reps dt N(x + c) (x - c) (needs a state).  Hooks 9 and 11 return Dirichlet rows as 0 (glims_hip.h).
         Returns (y, ms_total)."""
         d = self.dim
         nin = self.n_nodes * (d if which == 3 else 1)
@@ -336,6 +340,13 @@ class Handle:
         R = np.empty(self.n_nodes)
         self._check(self.lib.glims_rd_residual(self._h, _ptr(c, _dp), _ptr(cp, _dp), _ptr(R, _dp)))
         return R
+
+    def peek_partials(self):
+        """(sum of |row|^2, sum of the second right-hand side's) over the slice sums the last sweep or quadratic-term pass left
+        (glims_peek_partials)."""
+        a = np.zeros(2)
+        self._check(self.lib.glims_peek_partials(self._h, _ptr(a, _dp)))
+        return a
 
     def numbering(self):
         """old2new: internal index of every node of the caller's numbering."""

@@ -632,11 +632,12 @@ int glims_apply(glims_ctx* h, int which, const double* x, double* y, int reps, d
   return guarded(h, [&]() {
     GL_REQUIRE(h->is_setup, "glims_apply before glims_setup");
     GL_REQUIRE(x && y && reps >= 1, "bad arguments");
-    GL_REQUIRE(which >= 0 && which <= 10 && which != 6, "unknown operator");
+    GL_REQUIRE(which >= 0 && which <= 11 && which != 6, "unknown operator");
     if (which == 10)
       GL_REQUIRE(gl_rd_mass_in_sweep(h), "the sweep does not form the mass product on this handle (GLIMS_FLAG_NO_FUSED_MASS, "
                                          "several ranks, fp32 Jacobian, or rows of more than 32 entries)");
     if (which == 7) GL_REQUIRE(h->have_state, "the matrix-free product needs the state c (glims_set_state)");
+    if (which == 11) GL_REQUIRE(h->have_state, "the quadratic-term pass with a != delta needs the state c (glims_set_state)");
     if (which >= 8) h->prepared.drop();   // the sweep rewrites A(c), dinv and the Krylov work vectors
     const int d = h->dim;
     const bool blk_in = which == 3, blk_out = which == 3 || which == 4;
@@ -648,7 +649,7 @@ int glims_apply(glims_ctx* h, int which, const double* x, double* y, int reps, d
     const bool saved_mload = h->have_mload;
     h->have_mload = false;
     dvec<double> zero_b;
-    if (which == 8 || which == 10) zero_b.alloc_zero((size_t)h->n_nodes, h->st);
+    if (which == 8 || which == 10 || which == 11) zero_b.alloc_zero((size_t)h->n_nodes, h->st);
     GL_HIP(hipEventRecord(h->ev_a, h->st));
     for (int r = 0; r < reps; ++r) {
       if (which == 7)   // matrix-free A(c) x from the incidence lists (measurement only)
@@ -669,6 +670,11 @@ int glims_apply(glims_ctx* h, int which, const double* x, double* y, int reps, d
       else if (which == 9) {   // the quadratic-term pass with a = delta = x: y -= dt N(x) x per repetition
         h->nq_ad.alloc((size_t)2 * h->n_nodes);
         gl_pair_of(h, xin.p, h->nq_ad.p);
+        gl_rd_quad(h, h->nq_ad.p, yout.p, h->partials.p);
+      }
+      else if (which == 11) {   // the same pass prepared as the stepper prepares it (c_new = x, c_k = c, c_0 = 0):
+        h->nq_ad.alloc((size_t)2 * h->n_nodes);   // y -= dt N(x + c) (x - c) per repetition
+        gl_quad_prep(h, xin.p, h->c.p, zero_b.p, h->nq_ad.p);
         gl_rd_quad(h, h->nq_ad.p, yout.p, h->partials.p);
       }
       else if (which == 5)   // A x with the fused dot product of the Krylov iteration (timing studies)
@@ -692,6 +698,23 @@ int glims_apply(glims_ctx* h, int which, const double* x, double* y, int reps, d
     // which = 8 has left A(x) and its diagonal where A(c) belongs: put A(c) back (one more sweep, outside the timed region), so
     // that every later glims_apply(0 | 5), glims_project or glims_step sees the operator of the STATE, as after any other `which`
     if ((which == 8 || which == 10) && h->have_state) gl_rd_assemble(h, h->c.p, zero_b.p, nullptr, xin.p, h->cg_r2.p, h->partials.p);
+    return GLIMS_OK;
+  });
+}
+
+int glims_peek_partials(glims_ctx* h, double out[2]) {
+  return guarded(h, [&]() {
+    GL_REQUIRE(h->is_setup, "glims_peek_partials before glims_setup");
+    GL_REQUIRE(out, "null output");
+    const size_t n = (size_t)gl_rd_grid(h);
+    std::vector<double> part(2 * n);
+    GL_HIP(hipStreamSynchronize(h->st));
+    if (n) GL_HIP(hipMemcpy(part.data(), h->partials.p, 2 * n * sizeof(double), hipMemcpyDeviceToHost));
+    out[0] = out[1] = 0.0;
+    for (size_t s = 0; s < n; ++s) {   // slice order
+      out[0] += part[2 * s];
+      out[1] += part[2 * s + 1];
+    }
     return GLIMS_OK;
   });
 }

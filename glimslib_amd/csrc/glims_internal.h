@@ -697,6 +697,8 @@ int gl_project(glims_ctx* h, double* rhs_dev /*[n_nodes], overwritten*/, double*
 double gl_dot(glims_ctx* h, const double* a, const double* b, int64_t n, bool global = true);   // deterministic; host value
 void gl_allreduce_bulk(glims_ctx* h, double* dev, size_t n);   // in-place sum over ranks of a device vector (RCCL / transport)
 void gl_pair_of(glims_ctx* h, const double* u, float* ad /*[n_nodes][2]*/);   // (a, delta) = (u, u)
+// (a, delta) = (c_new + c_k - 2 c_0, c_new - c_k) over all local nodes, as the stepper prepares the pass (k_quad_prep)
+void gl_quad_prep(glims_ctx* h, const double* c_new, const double* c_k, const double* c_0, float* ad /*[n_nodes][2]*/);
 void gl_apply_dirichlet_c(glims_ctx* h);                                     // c[fixed] = stored values (+ halo)
 void gl_block_dinv(glims_ctx* h);                                            // m_dinv of the constrained K_el
 

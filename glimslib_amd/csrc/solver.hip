@@ -1638,6 +1638,11 @@ __global__ void k_quad_prep(int64_t i0, int64_t n, const double* __restrict__ cn
   const double x = cn[i], y = ck[i], z = c0[i];
   ad[i] = make_float2((float)((x - z) + (y - z)), (float)(x - y));   // differences in double, then rounded
 }
+void gl_quad_prep(glims_ctx* h, const double* cn, const double* ck, const double* c0, float* ad) {
+  hipLaunchKernelGGL(k_quad_prep, dim3(grid_of(h->n_nodes)), dim3(256), 0, h->st, (int64_t)0, h->n_nodes, cn, ck, c0,
+                     (float2*)ad);
+  GL_HIP(hipGetLastError());
+}
 
 // The Newton residual after a solve with the step's first Jacobian, from the quadratic structure (k_rd_quad): the Krylov
 // solver's final residual vector (in cg_r) becomes the next right-hand side, norms[0] its norm.  `krylov`: see rd_sweep.

@@ -409,18 +409,37 @@ int glims_reset_stats(glims_ctx* h);
  *        measured 4.2x slower than the assembled product at 10 M rows -- 1.38 ms and 5.15 GB against 0.33 ms and 1.77 GB --
  *        profiles/r02_matfree_ab.txt);  8 = the assembly sweep at c = x with a zero right-hand side, y = -1/2 (A(x) + S) x
  *        (timing hook, tools/ab_sweep.py; with a state set, A(c) and its diagonal are re-assembled before the call returns);
- *        9 = the quadratic-term pass with a = delta = x, y -= dt N(x) x per repetition (timing hook);
+ *        9 = the quadratic-term pass (k_rd_quad / k_rd_quad_s) with a = delta = x rounded to single precision: y starts at 0
+ *        and every repetition runs the pass on it, y <- y - dt N(x) x, so `reps` repetitions return -reps dt N(x) x up to the
+ *        pass's single-precision rounding (timing hook and TEST HOOK).  N(a)_ij = sum_T rho_T int_T a_h phi_i phi_j.  Rows with
+ *        a Dirichlet value of the concentration (glims_set_dirichlet_c) are returned as exactly 0, ghost rows as 0.  No state is
+ *        needed and neither the state nor A(c) is touched; the slice sums the last repetition left (|y|^2 per slice) can be read
+ *        with glims_peek_partials;
  *        10 = TEST HOOK: y = M x + rd_load as the stepping path forms a step's first right-hand side where the sweep carries
  *        the mass product (GLIMS_FLAG_NO_FUSED_MASS not set): the mass SpMV over the slices with fallback rows, then the
  *        single-right-hand-side sweep at c = x, and the b it wrote is returned.  GLIMS_E_USAGE where that mode is off for the
  *        handle.  Like glims_rd_residual it drops the system a previous step prepared (the next step re-assembles); with a
  *        state set, A(c) and its diagonal are re-assembled before the call returns, as for which = 8.
+ *        11 = TEST HOOK: the quadratic-term pass with a != delta, prepared as the stepper prepares it after a solve.  Needs a
+ *        state (GLIMS_E_USAGE without one).  Every repetition runs the stepper's preparation kernel with c_new = x, c_k = the
+ *        state c as glims_get_state returns it (Dirichlet values set since the last step are not yet in it) and c_0 = 0, i.e.
+ *        a = x + c and delta = x - c, both formed in double and then rounded to single precision, and then the pass on y, which
+ *        starts at 0: y <- y - dt N(x + c) (x - c), so `reps` repetitions return -reps dt N(x + c) (x - c).  Rows returned as
+ *        0 and the slice sums: as for which = 9.  Like which = 8 .. 10 it drops the system a previous step prepared; the state
+ *        and A(c) are not touched.
  *        Ghost rows of y are returned as 0. */
 int glims_apply(glims_ctx* h, int which, const double* x, double* y, int reps, double* ms_total);
 
 /* Assembles A(c) and the Newton residual R(c; c_prev) for host vectors (ghost rows 0):
  *   R = 1/2 (A(c) + S) c - M c_prev - rd_load.  R may be NULL. */
 int glims_rd_residual(glims_ctx* h, const double* c, const double* c_prev, double* R);
+
+/* TEST HOOK: what the last incidence-list kernel -- the assembly sweep (glims_apply 8 | 10, glims_rd_residual, a step) or the
+ * quadratic-term pass (glims_apply 9 | 11) -- left in its per-slice partial sums [slices][2]: out[k] = the sum of column k over
+ * the slices in slice order, in double.  Column 0 is the squared norm of the rows the kernel wrote (padding rows of the last
+ * slice, ghost rows and Dirichlet rows add 0), column 1 the second right-hand side's (0 where the kernel has none).  Reads
+ * only: no run memory, mailbox or reduce chain is touched.  GLIMS_E_USAGE before glims_setup. */
+int glims_peek_partials(glims_ctx* h, double out[2]);
 
 /* Diagnostics of the symbolic phase (node renumbering, SELL-64 sparsity, incidence lists, column codes -- built on the
  * device by glims_create; DOLFIN's counterpart is the dofmap + AIJ preallocation behind fenics.FunctionSpace,
