@@ -623,6 +623,8 @@ int glims_reset_stats(glims_ctx* h) {
   h->stats.stream_nontemporal = keep.stream_nontemporal;
   h->stats.krylov_working_set = keep.krylov_working_set;
   h->stats.rd_mass_fallback_rows = keep.rd_mass_fallback_rows;
+  h->stats.rd_rec_compact_slices = keep.rd_rec_compact_slices;
+  h->stats.rd_rec_full_slices = keep.rd_rec_full_slices;
   h->tev_used = 0;
   h->stats.steps = keep.steps;   // step counter drives the extrapolated guess; keep it
   return GLIMS_OK;

@@ -132,7 +132,7 @@ int gl_host_threads();   // OpenMP team the host phases may use (affinity mask, 
 void build_host_pattern(HostPattern& hp, int dim, int64_t n_nodes, int64_t n_own, int64_t n_cells,
                         const double* xyz, const int32_t* cells);
 
-// Everything a wave of the incidence-list kernels needs to know about its slice, in ONE 32-byte scalar load (the chain
+// Everything a wave of the incidence-list kernels needs to know about its slice, in ONE 40-byte scalar load (the chain
 // slice list -> slice offsets -> incidence offsets -> window flag was four dependent memory round trips before a wave could
 // issue its first useful load)
 struct SliceDesc {
@@ -140,6 +140,7 @@ struct SliceDesc {
   int32_t s;               // slice
   int32_t len, clen;       // entries / incidence records per lane
   int32_t ok;              // the slice has 16-bit column codes
+  int64_t wbase;           // compact record words (record_words.h): the bit pattern the slice's weight offsets count from
 };
 
 // Slices of similar length that the incidence-list kernels launch together (kernels.hip, ensure_classes)
@@ -148,6 +149,11 @@ struct SliceClass {
   int n = 0, n_interior = 0;   // slices; the interior ones (no ghost column) come first
   dvec<SliceDesc> desc;        // ... as descriptors (straight-line kernels)
   dvec<int32_t> list;          // ... as plain slice ids (looped kernels, classes of more than 32 entries per row)
+  std::vector<int32_t> host_list;   // ... the same on the host
+  // the same slices split by record stream (straight-line classes; rebuilt when the weights change, kernels.hip): compact
+  // interior, compact boundary, full interior, full boundary -- each in the order of `desc`
+  dvec<SliceDesc> rdesc;
+  int n_compact[2] = {0, 0}, n_full[2] = {0, 0};   // [interior, boundary]
 };
 
 // Device-resident SELL-64 sparsity + incidence lists.
@@ -167,6 +173,11 @@ struct DevPattern {
   dvec<double> cw;                         // per-incidence reaction weight rho_T |T| d!/(d+3)!
   dvec<uint32_t> cs2;                      // slot word re-ordered for the hot kernels: byte 0 = the row's own (diagonal) slot, then the cell's other vertices
   dvec<uint32_t> cs16;                     // the straight-line sweeps' 16-bit slot words (own slot dropped, 5 bits per other vertex), two records of a lane per element (k_corner_weights); empty = not valid, the sweeps read cs2
+  dvec<uint32_t> cr32;                     // the straight-line sweeps' compact records (record_words.h): slot fields of cs16 + the weight's offset from the slice base, 4 B instead of cw + cs16's 10; empty = none (no cs16), the sweeps read cw + cs16 / cs2
+  dvec<int64_t> rec_base;                  // ... per slice: the base (bit pattern of its first real record's weight)
+  dvec<uint8_t> rec_ok;                    // ... per slice: 1 = compact (straight-line slice whose every offset fits), 0 = full
+  std::vector<uint8_t> rec_ok_host;        // ... the same on the host (k_corner_weights ran: the classes' record lists are stale)
+  bool rec_lists_stale = true;
   dvec<uint32_t> cq;                       // [incidence][2] = (re-ordered slot word, weight as float bits): the quadratic-term pass's 8-byte records
   // the mass product from the sweep's incidence loop (k_corner_weights, rd_assemble_s_slice with MB = 1)
   dvec<double> mass_q;                     // per padded row: (d+3) / rho where every cell of the row has the same rho > 0, else 0

@@ -7,6 +7,7 @@
 // private LDS column acc[slot*64 + lane] (bank = lane -> conflict-free for any slot), so the segmented scatter-add
 // of FEM assembly needs neither atomics nor colouring and is bitwise reproducible.
 #include "glims_internal.h"
+#include "record_words.h"
 #include <hip/hip_ext.h>
 
 #include <algorithm>
@@ -115,6 +116,9 @@ __global__ void k_egeo(int64_t n_cells, const double* __restrict__ xyz, const in
 // registers more than cs2 and the 32-entry instances their third wave per SIMD.  Slots of a slice of at most 32 entries fit 5
 // bits; should one not, *cs16_bad is set and the handle keeps the 32-bit words.  (Slices longer than that belong to the looped
 // kernel, which reads cs2: their cs16 words are saturated and never read.)
+// cr32 (null where cs16 is): the compact record word of record_words.h -- cs16's fields and the weight's offset from the slice
+// base rec_base[s], in the layout of cw; rec_ok[s] = 1 for a straight-line slice whose every real record fits (a compact
+// slice: its sweep reads cr32 alone), else 0 (a full slice: cw + cs16, its cr32 words are never read).
 __host__ __device__ __forceinline__ int64_t gl_cs16_base(int64_t cbase, int s) { return (cbase >> 1) + (int64_t)s * 32; }
 template <int D>
 __global__ __launch_bounds__(GL_WAVE) void k_corner_weights(const int64_t* __restrict__ cslice_ptr,
@@ -127,7 +131,9 @@ __global__ __launch_bounds__(GL_WAVE) void k_corner_weights(const int64_t* __res
                                                              int64_t n_own, double* __restrict__ mass_q,
                                                              int32_t* __restrict__ mass_fb,
                                                              const int64_t* __restrict__ slice_ptr,
-                                                             uint32_t* __restrict__ cs16, int32_t* __restrict__ cs16_bad) {
+                                                             uint32_t* __restrict__ cs16, int32_t* __restrict__ cs16_bad,
+                                                             uint32_t* __restrict__ cr32, int64_t* __restrict__ rec_base,
+                                                             uint8_t* __restrict__ rec_ok) {
   constexpr int NV = D + 1;
   constexpr double fact = D == 2 ? 1.0 / 60.0 : 1.0 / 120.0;
   // (neighbouring slices on ONE XCD: the four rows that share a cell then share an L2 -- with block b on XCD b % 8 each of them
@@ -139,6 +145,8 @@ __global__ __launch_bounds__(GL_WAVE) void k_corner_weights(const int64_t* __res
   const bool straight = cs16 && ((slice_ptr[s + 1] - slice_ptr[s]) >> 6) <= 32;
   double rho0 = 0.0;
   bool seen = false, uniform = true;
+  int64_t wbase = 0;                    // (wave-uniform)
+  bool have_base = false, fits = true;
   for (int q = 0; q < clen; ++q) {
     const int64_t i = cbase + (int64_t)q * GL_WAVE + lane;
     const int32_t e = celem[i];
@@ -163,6 +171,7 @@ __global__ __launch_bounds__(GL_WAVE) void k_corner_weights(const int64_t* __res
           out |= k << (8 * pos);
           out16 |= min(k, 31u) << (5 * (pos - 1));
           if (straight && k > 31u) *cs16_bad = 1;
+          if (k > 31u) fits = false;
           ++pos;
         }
       }
@@ -172,6 +181,22 @@ __global__ __launch_bounds__(GL_WAVE) void k_corner_weights(const int64_t* __res
     if (cs16)
       reinterpret_cast<uint16_t*>(cs16)[2 * (gl_cs16_base(cbase, s) + (int64_t)(q >> 1) * GL_WAVE + lane) + (q & 1)] =
           (uint16_t)out16;
+    if (cr32) {
+      if (!have_base) {   // the slice's first real record: lowest q, then lowest lane
+        const unsigned long long real = __ballot(e >= 0);
+        if (real) {
+          wbase = __shfl((long long)gl_rw_bits(w), __ffsll(real) - 1);
+          have_base = true;
+        }
+      }
+      uint32_t word = gl_rw_pack_zero();
+      if (e >= 0) {
+        const int64_t dl = gl_rw_delta(wbase, w);
+        if (gl_rw_fits(dl)) word = gl_rw_pack(out16, dl);
+        else fits = false;
+      }
+      cr32[i] = word;
+    }
     // the same record for the quadratic-term pass: slot word + the weight in single precision, 8 B instead of 12 (the term it
     // feeds is itself a 1e-3 correction)
     cq[i] = make_uint2(out, __float_as_uint((float)w));
@@ -182,6 +207,11 @@ __global__ __launch_bounds__(GL_WAVE) void k_corner_weights(const int64_t* __res
   mass_q[row] = fused ? (double)(D + 3) / rho0 : 0.0;
   const int n_fb = __popcll(__ballot(own && !fused));
   if (lane == 0) mass_fb[s] = n_fb;
+  const bool compact = cr32 && straight && __ballot(!fits) == 0ull;
+  if (lane == 0) {
+    rec_base[s] = wbase;
+    rec_ok[s] = compact ? 1 : 0;
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -679,9 +709,17 @@ __device__ __forceinline__ double fg_first_iterate(double u, double p, double t)
 // ST: the slot stream's word -- uint16_t (cs16: 5-bit fields of the cell's other vertices, two records of a lane per 32-bit
 // element, k_corner_weights) or uint32_t (cs2, GLIMS_FLAG_SLOT_WORDS32: bytes 1..NV-1).  The same slots either way: every
 // instance forms the same bits.  `slots`: the element that holds record j's word.
+// rec32_t: the compact record word (cr32, record_words.h) -- cs16's fields in bits [14:0] and, in the same word, the weight
+// as an offset from the slice's base (SliceDesc::wbase, in scalar registers with the descriptor): ONE load and one register
+// per record in flight instead of 2.5, no cw stream.  Decoded to the 64 bits cw holds: the same bits in every result.  Only
+// the descriptor lists of compact slices are launched with it.
+struct rec32_t {
+  uint32_t w;
+};
 template <class ST>
 __device__ __forceinline__ int slot_field(uint32_t slots, int j, int m) {
-  if constexpr (sizeof(ST) == 2) return (int)((slots >> (16 * (j & 1) + 5 * (m - 1))) & 31u);
+  if constexpr (std::is_same<ST, rec32_t>::value) return gl_rw_slot_field(slots, m);
+  else if constexpr (sizeof(ST) == 2) return (int)((slots >> (16 * (j & 1) + 5 * (m - 1))) & 31u);
   else return (int)((slots >> (8 * m)) & 255u);
 }
 template <int NV, int CAP, int RB, int CIDX, class AT, int FG, int MB, class ST>
@@ -701,16 +739,16 @@ __device__ __forceinline__ void rd_assemble_s_slice(
   const int s = d.s, len = d.len, clen = d.clen;
   const int64_t row = (int64_t)s * GL_WAVE + lane;
   // ---- round trip 2 (program order = issue order; the column codes last, the next round trip waits for them)
-  constexpr bool W16 = sizeof(ST) == 2;
+  constexpr bool W16 = sizeof(ST) == 2, R32 = std::is_same<ST, rec32_t>::value;
   static_assert(!W16 || RB % 2 == 0, "paired slot words: an even number of records per round trip");
   constexpr int SPR = W16 ? 2 : 1, NSB = RB / SPR;   // records per slot element; slot elements per round trip
   const int64_t sbase = W16 ? gl_cs16_base(d.cbase, s) : d.cbase;
   const int slast = (clen - 1) / SPR;
-  double wb_[RB];
+  double wb_[R32 ? 1 : RB];   // (R32: the weight travels in the slot element)
   uint32_t sb_[NSB];
 #pragma unroll
   for (int j = 0; j < RB; ++j) {
-    wb_[j] = GL_STREAM(cw, d.cbase, min(j, clen - 1));
+    if constexpr (!R32) wb_[j] = GL_STREAM(cw, d.cbase, min(j, clen - 1));
     if (j % SPR == 0) sb_[j / SPR] = GL_STREAM(cs2, sbase, min(j / SPR, slast));
   }
   const bool own = row < n_own;
@@ -781,13 +819,16 @@ __device__ __forceinline__ void rd_assemble_s_slice(
     if (qq > 0) {   // rows with more than RB incidences
 #pragma unroll
       for (int j = 0; j < RB; ++j) {
-        wb_[j] = GL_STREAM(cw, d.cbase, min(qq + j, clen - 1));
+        if constexpr (!R32) wb_[j] = GL_STREAM(cw, d.cbase, min(qq + j, clen - 1));
         if (j % SPR == 0) sb_[j / SPR] = GL_STREAM(cs2, sbase, min((qq + j) / SPR, slast));
       }
     }
 #pragma unroll
     for (int j = 0; j < RB; ++j)
-      if (qq + j < clen) corner(wb_[j], sb_[j / SPR], j);   // (wave-uniform; a padding record of a shorter row has weight 0 and slots 0)
+      if (qq + j < clen) {   // (wave-uniform; a padding record of a shorter row has weight 0 and slots 0)
+        if constexpr (R32) corner(gl_rw_weight(sb_[j], d.wbase), sb_[j], j);
+        else corner(wb_[j], sb_[j / SPR], j);
+      }
   }
   // (MB: the row's mass factor and load are requested half-way through phase 3 and looked at after it -- held from the top of
   //  the kernel they cost four instances their third wave per SIMD, from the start of phase 3 still one: FG = 1 has its
@@ -901,7 +942,7 @@ __global__ __launch_bounds__(GL_WAVE) void k_rd_assemble_sg(
 
 __global__ void k_make_desc(int n, const int32_t* __restrict__ list, const int64_t* __restrict__ slice_ptr,
                             const int64_t* __restrict__ cslice_ptr, const uint8_t* __restrict__ win_ok,
-                            SliceDesc* __restrict__ desc) {
+                            const int64_t* __restrict__ rec_base, SliceDesc* __restrict__ desc) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int s = list[i];
@@ -912,6 +953,7 @@ __global__ void k_make_desc(int n, const int32_t* __restrict__ list, const int64
   d.len = (int)((slice_ptr[s + 1] - d.base) >> 6);
   d.clen = (int)((cslice_ptr[s + 1] - d.cbase) >> 6);
   d.ok = win_ok[s];
+  d.wbase = rec_base ? rec_base[s] : 0;
   desc[i] = d;
 }
 
@@ -1599,13 +1641,18 @@ static void assemble_static_t(glims_ctx* h, int with_mechanics) {
   else p.cs16.release();
   dvec<int32_t> cs16_bad;
   cs16_bad.alloc_zero(1, h->st);
+  // (the compact record words: where cs16 is; which slices are compact depends on the materials, so this runs with them)
+  if (straight) p.cr32.alloc((size_t)p.total_corners);
+  else p.cr32.release();
+  p.rec_base.alloc_zero((size_t)p.n_slices, h->st);
+  p.rec_ok.alloc_zero((size_t)p.n_slices, h->st);
   p.cq.alloc((size_t)2 * p.total_corners);
   p.mass_q.alloc((size_t)p.n_slices * GL_WAVE);
   dvec<int32_t> mass_fb;
   mass_fb.alloc((size_t)p.n_slices);
   hipLaunchKernelGGL(k_corner_weights<D>, dim3(p.n_slices), dim3(GL_WAVE), 0, h->st, p.cslice_ptr.p, p.celem.p, h->label.p,
                      h->evol.p, h->mat.p, p.diag_k.p, p.cslots.p, p.cw.p, p.cs2.p, (uint2*)p.cq.p, h->n_own, p.mass_q.p,
-                     mass_fb.p, p.slice_ptr.p, p.cs16.p, cs16_bad.p);
+                     mass_fb.p, p.slice_ptr.p, p.cs16.p, cs16_bad.p, p.cr32.p, p.rec_base.p, p.rec_ok.p);
   GL_HIP(hipGetLastError());
   {
     // the slices that keep the mass SpMV (rows at an interface of two rho, or touching a tissue with rho = 0)
@@ -1613,8 +1660,21 @@ static void assemble_static_t(glims_ctx* h, int with_mechanics) {
     int32_t bad16 = 0;
     GL_HIP(hipMemcpyAsync(fb.data(), mass_fb.p, fb.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->st));
     GL_HIP(hipMemcpyAsync(&bad16, cs16_bad.p, sizeof(int32_t), hipMemcpyDeviceToHost, h->st));
+    p.rec_ok_host.assign((size_t)p.n_slices, 0);
+    GL_HIP(hipMemcpyAsync(p.rec_ok_host.data(), p.rec_ok.p, p.rec_ok_host.size(), hipMemcpyDeviceToHost, h->st));
     GL_HIP(hipStreamSynchronize(h->st));
-    if (bad16) p.cs16.release();   // (a slot of a short slice beyond 5 bits: cannot happen; the sweeps then read cs2)
+    if (bad16) {   // (a slot of a short slice beyond 5 bits: cannot happen; the sweeps then read cs2)
+      p.cs16.release();
+      p.cr32.release();
+    }
+    if (!p.cr32.p) p.rec_ok_host.assign((size_t)p.n_slices, 0);
+    p.rec_lists_stale = true;   // (the classes' compact / full descriptor lists: rebuilt by the next sweep)
+    int64_t n_straight = 0, n_compact = 0;
+    for (size_t bk = 0; bk < p.bucket_cap.size(); ++bk)
+      if (p.bucket_cap[bk] <= 32) n_straight += p.bucket_count[bk];
+    for (uint8_t ok : p.rec_ok_host) n_compact += ok;
+    h->stats.rd_rec_compact_slices = n_compact;
+    h->stats.rd_rec_full_slices = n_straight - n_compact;
     p.mass_fb_rows = 0;
     for (int32_t sl = 0; sl < p.n_slices; ++sl)
       if (fb[(size_t)sl] > 0) {
@@ -1703,9 +1763,10 @@ static void ensure_classes(glims_ctx* h) {
     sc->list.upload(all, h->st);
     sc->desc.alloc((size_t)sc->n);
     hipLaunchKernelGGL(k_make_desc, dim3((unsigned)((sc->n + 255) / 256)), dim3(256), 0, h->st, sc->n, sc->list.p,
-                       p.slice_ptr.p, p.cslice_ptr.p, p.win_ok.p, sc->desc.p);
+                       p.slice_ptr.p, p.cslice_ptr.p, p.win_ok.p, (const int64_t*)nullptr, sc->desc.p);
     GL_HIP(hipGetLastError());
     GL_HIP(hipStreamSynchronize(h->st));   // `all` is a stack object
+    sc->host_list = std::move(all);
     p.classes.push_back(sc);
     if (getenv("GLIMS_VERBOSE"))
       fprintf(stderr, "glims slice class: %d slices (%d interior) of at most %d entries: %s kernels, %d waves per CU in the sweep\n",
@@ -1723,6 +1784,60 @@ static ClassLaunch class_launch(const SliceClass& sc, int part) {
   const int n_int = sc.n_interior;
   const int off = part == GL_PART_BOUNDARY ? n_int : 0;
   return {part == GL_PART_ALL ? sc.n : part == GL_PART_INTERIOR ? n_int : sc.n - n_int, sc.desc.p + off, sc.list.p + off};
+}
+
+// The straight-line classes' descriptor lists split by record stream (record_words.h): SliceClass::rdesc = compact interior,
+// compact boundary, full interior, full boundary, each in the order of SliceClass::desc, with the slices' bases.  Which slices
+// are compact depends on the weights: rebuilt after every k_corner_weights.  A class without a compact slice gets no list (its
+// sweeps launch `desc` as before).
+static void ensure_record_lists(glims_ctx* h) {
+  DevPattern& p = h->pat;
+  if (!p.rec_lists_stale) return;
+  p.rec_lists_stale = false;
+  for (SliceClass* sc : p.classes) {
+    sc->rdesc.release();
+    sc->n_compact[0] = sc->n_compact[1] = sc->n_full[0] = sc->n_full[1] = 0;
+    if (sc->cap > 32 || !p.cr32.p) continue;
+    std::vector<int32_t> part[4];
+    for (int i = 0; i < sc->n; ++i) {
+      const int32_t s = sc->host_list[(size_t)i];
+      part[(p.rec_ok_host[(size_t)s] ? 0 : 2) + (i >= sc->n_interior ? 1 : 0)].push_back(s);
+    }
+    if (part[0].empty() && part[1].empty()) continue;
+    std::vector<int32_t> all;
+    for (const auto& v : part) all.insert(all.end(), v.begin(), v.end());
+    dvec<int32_t> list;
+    list.upload(all, h->st);
+    sc->rdesc.alloc((size_t)sc->n);
+    hipLaunchKernelGGL(k_make_desc, dim3((unsigned)((sc->n + 255) / 256)), dim3(256), 0, h->st, sc->n, list.p, p.slice_ptr.p,
+                       p.cslice_ptr.p, p.win_ok.p, p.rec_base.p, sc->rdesc.p);
+    GL_HIP(hipGetLastError());
+    GL_HIP(hipStreamSynchronize(h->st));   // `all` and `list` are stack objects
+    for (int b = 0; b < 2; ++b) {
+      sc->n_compact[b] = (int)part[b].size();
+      sc->n_full[b] = (int)part[2 + b].size();
+    }
+  }
+}
+// ... what a sweep of class `sc` launches: [0] the compact list (the rec32_t instance), [1] the full list.  Without a compact
+// list: [1] is class_launch.
+static void record_launches(const SliceClass& sc, int part, bool rec, ClassLaunch out[2]) {
+  out[0] = ClassLaunch{0, nullptr, nullptr};
+  out[1] = class_launch(sc, part);
+  if (!rec || !sc.rdesc.p) return;
+  const int nc = sc.n_compact[0] + sc.n_compact[1];
+  const int lo = part == GL_PART_BOUNDARY ? 1 : 0, hi = part == GL_PART_INTERIOR ? 1 : 2;
+  int coff = 0, foff = nc, cn = 0, fn = 0;
+  if (lo == 1) {
+    coff += sc.n_compact[0];
+    foff += sc.n_full[0];
+  }
+  for (int b = lo; b < hi; ++b) {
+    cn += sc.n_compact[b];
+    fn += sc.n_full[b];
+  }
+  out[0] = ClassLaunch{cn, sc.rdesc.p + coff, nullptr};
+  out[1] = ClassLaunch{fn, sc.rdesc.p + foff, nullptr};
 }
 
 // Assembles A(c) and the Newton right-hand side(s).  partials: [gl_rd_grid][2] = (|b - ..|^2, |b2 - ..|^2).
@@ -1750,6 +1865,19 @@ void gl_rd_assemble(glims_ctx* h, const double* c, const double* b, const double
   // the straight-line sweeps' slot stream: 16-bit words unless the handle has none or GLIMS_FLAG_SLOT_WORDS32 asks for cs2
   const bool w16 = p.cs16.p != nullptr && (h->opt.flags & GLIMS_FLAG_SLOT_WORDS32) == 0;
   if (w16) h->stats.rd_slot16_sweeps++;   // (cs16 exists only where a straight-line class reads it)
+  // ... and the compact slices' records from cr32 alone (the 16-bit fields and the weight in one word): fp64 Jacobian with
+  // 16-bit column codes -- the int32-column and fp32-Jacobian handles keep cw + cs16 -- unless GLIMS_FLAG_RECORD_WORDS_FULL
+  const bool rec = w16 && p.cr32.p != nullptr && (h->opt.flags & GLIMS_FLAG_RECORD_WORDS_FULL) == 0 && !h->jac32 && h->use_idx16;
+  ensure_record_lists(h);
+  {
+    bool any = false;
+    for (const SliceClass* sc : p.classes) {
+      ClassLaunch rl[2];
+      record_launches(*sc, part, rec, rl);
+      any = any || rl[0].grid > 0;
+    }
+    if (any) h->stats.rd_rec32_sweeps++;
+  }
   MassArgs ma{nullptr, nullptr, nullptr};
   if (mass) {
     GL_REQUIRE(gl_rd_fusable(h) && part == GL_PART_ALL && mass->bw == (b2 ? b2 : b),
@@ -1801,17 +1929,40 @@ void gl_rd_assemble(glims_ctx* h, const double* c, const double* b, const double
     else if (mass) GL_RDG3(NV, CIDX, 2, 1);                                                                        \
     else GL_RDG3(NV, CIDX, 2, 0);                                                                                  \
   } while (0)
+  // (the compact lists: 16-bit column codes only; records per round trip as the cs16 siblings)
+#define GL_RDG3R(NV, FG, MB)                                                                                        \
+  do {                                                                                                             \
+    if (cap <= 16) GL_RDG5(NV, 16, 26, 1, FG, MB, rec32_t, p.cr32.p);                                              \
+    else if (cap <= 20) GL_RDG5(NV, 20, 24, 1, FG, MB, rec32_t, p.cr32.p);                                         \
+    else if (cap <= 24) GL_RDG5(NV, 24, 24, 1, FG, MB, rec32_t, p.cr32.p);                                         \
+    else GL_RDG5(NV, 32, 24, 1, FG, MB, rec32_t, p.cr32.p);                                                        \
+  } while (0)
+#define GL_RDG2R(NV)                                                                                                \
+  do {                                                                                                             \
+    if (fused->kind == 1 && mass) GL_RDG3R(NV, 1, 1);                                                              \
+    else if (fused->kind == 1) GL_RDG3R(NV, 1, 0);                                                                 \
+    else if (mass) GL_RDG3R(NV, 2, 1);                                                                             \
+    else GL_RDG3R(NV, 2, 0);                                                                                       \
+  } while (0)
     for (const SliceClass* sc : p.classes) {
-      const ClassLaunch cl = class_launch(*sc, part);
-      if (cl.grid <= 0) continue;
+      ClassLaunch rl[2];
+      record_launches(*sc, part, rec, rl);
       const int cap = sc->cap;
       const size_t lds = (size_t)2 * cap * GL_WAVE * sizeof(double);
+      if (rl[0].grid > 0) {
+        const ClassLaunch cl = rl[0];
+        if (h->nv == 3) GL_RDG2R(3); else GL_RDG2R(4);
+      }
+      const ClassLaunch cl = rl[1];
+      if (cl.grid <= 0) continue;
       if (h->nv == 3) {
         if (h->use_idx16) GL_RDG2(3, 1); else GL_RDG2(3, 0);
       } else {
         if (h->use_idx16) GL_RDG2(4, 1); else GL_RDG2(4, 0);
       }
     }
+#undef GL_RDG2R
+#undef GL_RDG3R
 #undef GL_RDG2
 #undef GL_RDG_RB16
 #undef GL_RDG3
@@ -1870,11 +2021,30 @@ void gl_rd_assemble(glims_ctx* h, const double* c, const double* b, const double
     else if (h->use_idx16) GL_RDS2(NV, 1, double, h->vA.p);                                                        \
     else GL_RDS2(NV, 0, double, h->vA.p);                                                                          \
   } while (0)
+  // (the compact lists: fp64 Jacobian, 16-bit column codes, with or without the mass product)
+#define GL_RDR3(NV, CAP, RB)                                                                                        \
+  do {                                                                                                             \
+    if (mass) GL_RDS4(NV, CAP, RB, 1, double, h->vA.p, 1, rec32_t, p.cr32.p);                                      \
+    else GL_RDS4(NV, CAP, RB, 1, double, h->vA.p, 0, rec32_t, p.cr32.p);                                           \
+  } while (0)
+#define GL_RDR2(NV)                                                                                                 \
+  do {                                                                                                             \
+    if (cap <= 16) GL_RDR3(NV, 16, 26);                                                                            \
+    else if (cap <= 20) GL_RDR3(NV, 20, 24);                                                                       \
+    else if (cap <= 24) GL_RDR3(NV, 24, 24);                                                                       \
+    else GL_RDR3(NV, 32, 24);                                                                                      \
+  } while (0)
   for (const SliceClass* sc : p.classes) {
-    const ClassLaunch cl = class_launch(*sc, part);
-    if (cl.grid <= 0) continue;
+    ClassLaunch rl[2];
+    record_launches(*sc, part, rec, rl);
     const int cap = sc->cap;
     const size_t lds = (size_t)2 * cap * GL_WAVE * sizeof(double);
+    if (rl[0].grid > 0) {
+      const ClassLaunch cl = rl[0];
+      if (h->nv == 3) GL_RDR2(3); else GL_RDR2(4);
+    }
+    const ClassLaunch cl = rl[1];
+    if (cl.grid <= 0) continue;
     if (mass) {
       if (h->nv == 3) {
         if (h->use_idx16) GL_RDM2(3, 1); else GL_RDM2(3, 0);
@@ -1883,6 +2053,8 @@ void gl_rd_assemble(glims_ctx* h, const double* c, const double* b, const double
       }
     } else if (h->nv == 3) GL_RDV(3); else GL_RDV(4);
   }
+#undef GL_RDR2
+#undef GL_RDR3
 #undef GL_RDM2
 #undef GL_RDM3
 #undef GL_RDV

@@ -224,7 +224,17 @@ typedef struct glims_options {
                                            entries) read the slots of an incidence record from a 16-bit word -- the row's own
                                            slot dropped, 5 bits for each other vertex of the cell -- instead of the 32-bit word
                                            with a byte per vertex: 2 bytes less per (row, cell) incidence and sweep, the same
-                                           slots and the same bits in every result.  Set: the 32-bit words (A/B in one build) */
+                                           slots and the same bits in every result.  Set: the 32-bit words (A/B in one build;
+                                           the compact records below embed the 16-bit fields and are switched off as well) */
+#define GLIMS_FLAG_RECORD_WORDS_FULL 8192  /* OFF by default.  Default: a straight-line sweep reads the records of a COMPACT slice
+                                           from one 32-bit word each -- the 16-bit slot fields and, in the upper 17 bits, the
+                                           offset of the fp64 reaction weight's bit pattern from a per-slice base -- instead
+                                           of the weight (8 B) and the slot word (2 B): 6 bytes less per (row, cell) incidence
+                                           and sweep, decoded to the same 64 bits, so the same bits in every result.  A slice
+                                           is compact where its weights differ by rounding noise only (congruent cells of one
+                                           rho: lattices, voxel meshes; glims_stats.rd_rec_compact_slices); the other (full)
+                                           slices keep today's streams.  fp64 Jacobian with 16-bit column codes only.
+                                           Set: weight + slot word for every slice (A/B in one build) */
 
 typedef struct glims_stats {
   int64_t steps;            /* implicit time steps taken */
@@ -326,7 +336,13 @@ typedef struct glims_stats {
   int64_t cheb_fused_zero_starts; /* the folded first passes (cheb_fused_passes) of solves that start from zero: a count the host
                                always knew; cheb_fused_passes = cheb_host_counts + cheb_fused_zero_starts */
   int64_t rd_slot16_sweeps; /* assembly sweeps (glims_apply hooks included) whose straight-line launches read the 16-bit slot
-                               words; 0 under GLIMS_FLAG_SLOT_WORDS32 and on a mesh without a straight-line class */
+                               words (in cs16 or inside the compact records); 0 under GLIMS_FLAG_SLOT_WORDS32 and on a mesh
+                               without a straight-line class */
+  int64_t rd_rec_compact_slices; /* slices of straight-line classes whose records fit the compact 32-bit word ... */
+  int64_t rd_rec_full_slices;    /* ... and those that do not (both set by glims_setup; kept by glims_reset_stats) */
+  int64_t rd_rec32_sweeps;  /* assembly sweeps (glims_apply hooks included) that read compact records for at least one slice; 0
+                               under GLIMS_FLAG_RECORD_WORDS_FULL, GLIMS_FLAG_SLOT_WORDS32, GLIMS_FLAG_INT32_COLUMNS and
+                               GLIMS_FLAG_FP32_JACOBIAN */
 } glims_stats;
 
 /* ---- lifetime -------------------------------------------------------------------------------------- */
