@@ -154,6 +154,8 @@ SIGNATURES = {
     "glims_adjoint_gradient_full": (C.c_int, [_h, C.c_int, C.POINTER(Misfit), _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "glims_adjoint_hessian": (C.c_int, [_h, C.c_int, C.POINTER(Misfit), C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
                                         _dp, _dp, _dp, _dp, _dp, _dp]),
+    "glims_adjoint_hessian_spmd": (C.c_int, [_h, C.c_int, C.POINTER(Misfit), C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                                             _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "glims_adjoint_stats": (C.c_int, [_h, _i64p, _dp]),
     "glims_sampler_create_points": (C.c_int, [_h, C.c_int64, _dp, C.c_int, _i64p]),
     "glims_sampler_create_grid": (C.c_int, [_h, _dp, _dp, _i64p, C.c_int, _i64p]),
@@ -487,12 +489,15 @@ class Handle:
                             float(t.get("weight", 1.0)), _ptr(tg, _dp))
         return arr, keep
 
-    def adjoint_hessian(self, terms, directions, n_labels=None):
+    def adjoint_hessian(self, terms, directions, n_labels=None, collective=False):
         """glims_adjoint_hessian: J, the gradient and the Hessian-vector products of the recorded run for the misfit ``terms``
         (as in adjoint_gradient) along 1 .. 8 ``directions``, each a dict {'D', 'rho', 'gamma' ([n_labels] or a scalar for
         every label), 'c0' ([n_nodes], caller's order)} whose missing keys are 0.  Returns a dict {'J', 'D', 'rho', 'gamma',
         'c0' (the gradient, as adjoint_gradient), 'hv_D', 'hv_rho', 'hv_gamma' ([n_dir, n_labels]), 'hv_c0' ([n_dir, n_nodes]),
-        'stats' (tangent-linear / second-order PCG iterations, extra elastic solves, ms)}."""
+        'stats' (tangent-linear / second-order PCG iterations, extra elastic solves, ms)}.
+        collective=True calls glims_adjoint_hessian_spmd: the same call on one GPU, and on a partitioned handle the
+        collective one (every rank with the same terms and directions; 'c0' entries in the local numbering, ghosts of
+        'hv_c0' are 0).  The default keeps refusing partitioned handles."""
         if self.n_labels is None:
             raise ValueError("adjoint_hessian before set_materials")
         if n_labels is not None and int(n_labels) != self.n_labels:
@@ -517,9 +522,9 @@ class Handle:
         g = [np.zeros(L) for _ in range(3)] + [np.zeros(n)]
         hv = [np.zeros((max(1, P), L)) for _ in range(3)] + [np.zeros((max(1, P), n))]
         st = np.zeros(4)
-        self._check(self.lib.glims_adjoint_hessian(self._h, len(terms), arr, int(P), *[_ptr(d, _dp) for d in dirs],
-                                                   C.byref(J), *[_ptr(a, _dp) for a in g], *[_ptr(a, _dp) for a in hv],
-                                                   _ptr(st, _dp)))
+        call = self.lib.glims_adjoint_hessian_spmd if collective else self.lib.glims_adjoint_hessian
+        self._check(call(self._h, len(terms), arr, int(P), *[_ptr(d, _dp) for d in dirs], C.byref(J),
+                         *[_ptr(a, _dp) for a in g], *[_ptr(a, _dp) for a in hv], _ptr(st, _dp)))
         del keep
         return {"J": J.value, "D": g[0], "rho": g[1], "gamma": g[2], "c0": g[3], "hv_D": hv[0][:P], "hv_rho": hv[1][:P],
                 "hv_gamma": hv[2][:P], "hv_c0": hv[3][:P],

@@ -900,12 +900,13 @@ __global__ __launch_bounds__(256) void k_hess_rows(int64_t n_own, int P, int64_t
 
 // Per-label Hessian sums of one direction, the layout, grid and fixed-order reduction of k_sens (then k_sens_final):
 //   q0 = int_T grad nu . grad c + grad lam . grad dc,   q1 = int_T nu (c^2 - c) + lam (2c - 1) dc   (exact for P1)
+// counted: as in k_sens (partitioned handles, else nullptr)
 template <int D>
 __global__ __launch_bounds__(256) void k_hsens(int64_t n_cells, int l0, const int32_t* __restrict__ cell_nodes,
                                                const double* __restrict__ egeo, const uint8_t* __restrict__ label,
                                                const double* __restrict__ c, const double* __restrict__ lam,
                                                const double* __restrict__ dc, const double* __restrict__ nu,
-                                               double* __restrict__ partials) {
+                                               const uint8_t* __restrict__ counted, double* __restrict__ partials) {
   constexpr int NV = D + 1, GE = 1 + NV * D;
   constexpr double f3 = D == 2 ? 1.0 / 60.0 : 1.0 / 120.0;
   constexpr double f2 = D == 2 ? 1.0 / 12.0 : 1.0 / 20.0;
@@ -915,7 +916,7 @@ __global__ __launch_bounds__(256) void k_hsens(int64_t n_cells, int l0, const in
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n_cells; e += stride) {
     const int j = label[e] - l0;
-    if (j < 0 || j >= GL_ADJ_LT) continue;
+    if (j < 0 || j >= GL_ADJ_LT || (counted && !counted[e])) continue;
     const double* g = egeo + e * GE;
     const double vol = g[0];
     double gc[D] = {0.0}, gl[D] = {0.0}, gd[D] = {0.0}, gv[D] = {0.0};
@@ -1042,6 +1043,7 @@ int rd_solve(glims_ctx* h, AdjWork& wk, const uint8_t* fxc, bool rd_mg, int rd_d
              int64_t* its) {
   const int64_t n = h->n_own;
   if (fxc) hipLaunchKernelGGL(k_zero_fixed, dim3(grid_of(n)), dim3(256), 0, h->st, n, fxc, x, (const double*)nullptr);
+  gl_halo_exchange(h, x, 1);   // (partitioned handles: the guess at the ghost columns, with its zeros on the constrained nodes)
   gl_launch_spmv(h, h->st, h->pat.n_slices, nullptr, h->vA.p, x, wk.w.p, fxc, nullptr, nullptr, nullptr, 0, nullptr);
   hipLaunchKernelGGL(k_residual, dim3(grid_of(n)), dim3(256), 0, h->st, n, rhs, wk.w.p, fxc, wk.r.p);
   GL_CHECK_LAUNCH();
@@ -1148,20 +1150,8 @@ __global__ void k_mp_dir(int64_t n, const uint8_t* __restrict__ fixed, const dou
 //   stage 1 (after k_spmm):          pq = p.Ap, alpha = rz / pq (breakdown: flags[1])
 //   stage 2 (after the update):      done when ||r|| <= tol (its[j] = it), else beta = rz' / rz;  flags[0] = all done
 template <int P>
-__global__ __launch_bounds__(1024) void k_mp_scalar(int stage, int it, int nb, const double* __restrict__ part,
-                                                    double* __restrict__ sc, int* __restrict__ done, int* __restrict__ its,
-                                                    int* __restrict__ flags) {
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int ns = stage == 1 ? P : 2 * P;
-  __shared__ double s[2 * P];
-  if (w < ns) {
-    double t = 0.0;
-    for (int bk = lane; bk < nb; bk += 64) t += part[(size_t)bk * ns + w];
-    t = wsum(t);
-    if (lane == 0) s[w] = t;
-  }
-  __syncthreads();
-  if (threadIdx.x != 0) return;
+__device__ __forceinline__ void mp_scalar_step(int stage, int it, const double* s, double* __restrict__ sc,
+                                               int* __restrict__ done, int* __restrict__ its, int* __restrict__ flags) {
   int all = 1;
   for (int j = 0; j < P; ++j) {
     if (!done[j]) {
@@ -1193,11 +1183,87 @@ __global__ __launch_bounds__(1024) void k_mp_scalar(int stage, int it, int nb, c
   }
   flags[0] = all;
 }
+template <int P>
+__global__ __launch_bounds__(1024) void k_mp_scalar(int stage, int it, int nb, const double* __restrict__ part,
+                                                    double* __restrict__ sc, int* __restrict__ done, int* __restrict__ its,
+                                                    int* __restrict__ flags) {
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int ns = stage == 1 ? P : 2 * P;
+  __shared__ double s[2 * P];
+  if (w < ns) {
+    double t = 0.0;
+    for (int bk = lane; bk < nb; bk += 64) t += part[(size_t)bk * ns + w];
+    t = wsum(t);
+    if (lane == 0) s[w] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  mp_scalar_step<P>(stage, it, s, sc, done, its, flags);
+}
+
+// Partitioned handles: the sums of an iteration are over all ranks and the same bits on all of them.  k_mp_rank_sums reduces
+// this rank's block partials in k_mp_scalar's order into row `rank` of rows[world][ns] and zeroes the other rows; the
+// all-reduce of rows then is a gather (x + 0 is exact in every transport); k_mp_scalar_ranks adds the rows in rank order and
+// takes the scalar step.  Every rank holds the same sc, done, its and flags afterwards.
+__global__ __launch_bounds__(1024) void k_mp_rank_sums(int ns, int nb, int rank, int world, const double* __restrict__ part,
+                                                       double* __restrict__ rows) {
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  __shared__ double s[2 * 8];
+  if (w < ns) {
+    double t = 0.0;
+    for (int bk = lane; bk < nb; bk += 64) t += part[(size_t)bk * ns + w];
+    t = wsum(t);
+    if (lane == 0) s[w] = t;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < world * ns; i += blockDim.x) rows[i] = i / ns == rank ? s[i - rank * ns] : 0.0;
+}
+template <int P>
+__global__ void k_mp_scalar_ranks(int stage, int it, int world, const double* __restrict__ rows, double* __restrict__ sc,
+                                  int* __restrict__ done, int* __restrict__ its, int* __restrict__ flags) {
+  const int ns = stage == 1 ? P : 2 * P;
+  __shared__ double s[2 * P];
+  if (threadIdx.x < ns) {
+    double t = 0.0;
+    for (int r = 0; r < world; ++r) t += rows[r * ns + threadIdx.x];
+    s[threadIdx.x] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  mp_scalar_step<P>(stage, it, s, sc, done, its, flags);
+}
 
 struct MultiPcg {
   dvec<double> X, B, R, Pv, Q, part, part2, sc;
   dvec<int> done, its, flags;
+  // partitioned handles: the send buffer of the [n_nodes][P] ghost exchanges (n_send x P: the handle's own holds n_send x dim)
+  // and the [world][2 P] rows of the cross-rank sums
+  dvec<double> sendbuf, rows;
 };
+
+// the scalar step after a reduction of `nb` block partials (stage as in k_mp_scalar); on a partitioned handle through the
+// gather of every rank's sums
+template <int P>
+void mp_scalar(glims_ctx* h, MultiPcg& m, int stage, int it, int nb, const double* part) {
+  if (h->world <= 1) {
+    hipLaunchKernelGGL(k_mp_scalar<P>, dim3(1), dim3(1024), 0, h->st, stage, it, nb, part, m.sc.p, m.done.p, m.its.p,
+                       m.flags.p);
+    GL_CHECK_LAUNCH();
+    return;
+  }
+  const int ns = stage == 1 ? P : 2 * P;
+  hipLaunchKernelGGL(k_mp_rank_sums, dim3(1), dim3(1024), 0, h->st, ns, nb, h->rank, h->world, part, m.rows.p);
+  GL_CHECK_LAUNCH();
+  gl_allreduce_bulk(h, m.rows.p, (size_t)h->world * ns);
+  hipLaunchKernelGGL(k_mp_scalar_ranks<P>, dim3(1), dim3(64), 0, h->st, stage, it, h->world, (const double*)m.rows.p, m.sc.p,
+                     m.done.p, m.its.p, m.flags.p);
+  GL_CHECK_LAUNCH();
+}
+// ghosts of an interleaved [n_nodes][P] operand of k_spmm
+void mp_exchange(glims_ctx* h, MultiPcg& m, double* v, int P) {
+  if (h->world <= 1) return;
+  gl_halo_exchange_buf(h, v, P, m.sendbuf.p);
+}
 
 template <int P>
 int mp_solve_t(glims_ctx* h, MultiPcg& m, const uint8_t* fxc, const double* rhs, double* x, int64_t ld,
@@ -1220,12 +1286,12 @@ int mp_solve_t(glims_ctx* h, MultiPcg& m, const uint8_t* fxc, const double* rhs,
   hipLaunchKernelGGL(k_mp_pack<P>, dim3(g), dim3(256), 0, h->st, n, ld, rhs, fxc, m.B.p, 1);
   hipLaunchKernelGGL(k_mp_pack<P>, dim3(g), dim3(256), 0, h->st, n, ld, (const double*)x, fxc, m.X.p, 1);
   GL_CHECK_LAUNCH();
+  mp_exchange(h, m, m.X.p, P);
   gl_launch_spmm(h, P, h->vA.p, m.X.p, m.Q.p, fxc, nullptr);
   hipLaunchKernelGGL(k_mp_vec<P>, dim3(nbk), dim3(256), 0, h->st, 0, n, fxc, h->dinv.p, m.B.p, m.X.p, m.R.p, m.Pv.p, m.Q.p,
                      m.sc.p, m.done.p, m.part2.p);
-  hipLaunchKernelGGL(k_mp_scalar<P>, dim3(1), dim3(1024), 0, h->st, 0, 0, nbk, m.part2.p, m.sc.p, m.done.p, m.its.p,
-                     m.flags.p);
   GL_CHECK_LAUNCH();
+  mp_scalar<P>(h, m, 0, 0, nbk, m.part2.p);
   const int maxit = std::max(h->opt.cg_maxit, 20000), nbs = gl_spmm_blocks(h);
   int it = 0;
   for (;;) {
@@ -1234,13 +1300,13 @@ int mp_solve_t(glims_ctx* h, MultiPcg& m, const uint8_t* fxc, const double* rhs,
     if (flags[0] || it >= maxit) break;
     for (int k = 0; k < 4 && it < maxit; ++k) {   // (done columns stay frozen: checking every 4 iterations changes no bit)
       ++it;
+      mp_exchange(h, m, m.Pv.p, P);
       gl_launch_spmm(h, P, h->vA.p, m.Pv.p, m.Q.p, fxc, m.part.p);
-      hipLaunchKernelGGL(k_mp_scalar<P>, dim3(1), dim3(1024), 0, h->st, 1, it, nbs, m.part.p, m.sc.p, m.done.p, m.its.p,
-                         m.flags.p);
+      mp_scalar<P>(h, m, 1, it, nbs, m.part.p);
       hipLaunchKernelGGL(k_mp_vec<P>, dim3(nbk), dim3(256), 0, h->st, 1, n, fxc, h->dinv.p, m.B.p, m.X.p, m.R.p, m.Pv.p,
                          m.Q.p, m.sc.p, m.done.p, m.part2.p);
-      hipLaunchKernelGGL(k_mp_scalar<P>, dim3(1), dim3(1024), 0, h->st, 2, it, nbk, m.part2.p, m.sc.p, m.done.p, m.its.p,
-                         m.flags.p);
+      GL_CHECK_LAUNCH();
+      mp_scalar<P>(h, m, 2, it, nbk, m.part2.p);
       hipLaunchKernelGGL(k_mp_dir<P>, dim3(g), dim3(256), 0, h->st, n, fxc, h->dinv.p, m.R.p, m.Pv.p, m.sc.p, m.done.p);
       GL_CHECK_LAUNCH();
     }
@@ -1303,12 +1369,34 @@ struct AdjCountGuard {
   }
 };
 
+// Device memory of a Hessian call on top of the trajectory, and what is free now: the stored tangent-linear states dominate,
+// 8 P B per node and recorded state (see glims_hip.h)
+bool hessian_fits(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, std::string* why) {
+  const int64_t nn = h->n_nodes, nd = nn * h->dim;
+  const int N = (int)h->adj.traj.size() - 1;
+  bool any_u = false;
+  for (int k = 0; k < n_terms; ++k) any_u = any_u || terms[k].kind == GLIMS_MISFIT_U_L2;
+  const size_t need = 8 * ((size_t)(N + 1) * P * nn + (size_t)(9 * P + 16) * nn + (any_u ? (size_t)14 * nd : 0) +
+                           (size_t)2 * h->n_cells + (size_t)h->pat.total_entries);
+  size_t fr = 0, tot = 0;
+  GL_HIP(hipMemGetInfo(&fr, &tot));
+  if (need <= fr) return true;
+  *why = "glims_adjoint_hessian: " + std::to_string(P) + " directions over " + std::to_string(N + 1) +
+         " recorded states need about " + std::to_string(need >> 20) + " MiB of device memory, " + std::to_string(fr >> 20) +
+         " MiB are free";
+  return false;
+}
+
 // The tangent-linear sweep, then gradient_t's backward sweep (BackwardSweep: J and the gradient keep its bits, which
 // tests/test_gpu_adjoint_hessian.py checks) with the second-order adjoint work of every direction between its parts.
+// Partitioned handles (glims_adjoint_hessian_spmd, which has taken the memory verdict of all ranks: mem_checked): dc_n, nu_n,
+// du and dmu exchange their ghosts after their solves, hd and ue before the mass product, the per-label sums count a cell on
+// one rank (AdjointState::counted) and are gathered with the gradient's.
 template <int D>
 int hessian_t(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, const double* dir_D, const double* dir_rho,
               const double* dir_gamma, const double* dir_c0, double* J_out, double* dD, double* drho, double* dgamma,
-              double* dc0, double* hv_D, double* hv_rho, double* hv_gamma, double* hv_c0, double* stats) {
+              double* dc0, double* hv_D, double* hv_rho, double* hv_gamma, double* hv_c0, double* stats,
+              bool mem_checked) {
   AdjointState& a = h->adj;
   const int64_t n = h->n_own, nn = h->n_nodes, nd = nn * D;
   const int N = (int)a.traj.size() - 1;
@@ -1316,16 +1404,9 @@ int hessian_t(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, const
   const double t0 = omp_get_wtime();
   bool any_u = false;
   for (int k = 0; k < n_terms; ++k) any_u = any_u || terms[k].kind == GLIMS_MISFIT_U_L2;
-  {   // the stored tangent-linear states dominate: 8 P B per node and recorded state (see glims_hip.h)
-    const size_t need = 8 * ((size_t)(N + 1) * P * nn + (size_t)(9 * P + 16) * nn + (any_u ? (size_t)14 * nd : 0) +
-                             (size_t)2 * h->n_cells + (size_t)h->pat.total_entries);
-    size_t fr = 0, tot = 0;
-    GL_HIP(hipMemGetInfo(&fr, &tot));
-    if (need > fr)
-      throw glims_error(GLIMS_E_HIP, "glims_adjoint_hessian: " + std::to_string(P) + " directions over " +
-                                         std::to_string(N + 1) + " recorded states need about " +
-                                         std::to_string(need >> 20) + " MiB of device memory, " +
-                                         std::to_string(fr >> 20) + " MiB are free");
+  if (!mem_checked) {
+    std::string why;
+    if (!hessian_fits(h, n_terms, terms, P, &why)) throw glims_error(GLIMS_E_HIP, why);
   }
   AdjCountGuard counts(a);
   AdjWork wk;
@@ -1358,14 +1439,25 @@ int hessian_t(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, const
     ue.alloc_zero((size_t)nn, h->st);
     uMe.alloc_zero((size_t)nn, h->st);
   }
+  const bool part = h->world > 1;
+  const uint8_t* counted = part ? a.counted.p : nullptr;
+  // ghosts of P vectors stored column after column (no-ops on one GPU)
+  auto exchange_cols = [&](double* v) {
+    for (int p = 0; part && p < P; ++p) gl_halo_exchange(h, v + (size_t)p * nn, 1);
+  };
   for (int p = 0; dir_c0 && p < P; ++p) upload_permuted(h, wk, dir_c0 + (size_t)p * nn, 1, dcs.p + (size_t)p * nn);
   auto dc_of = [&](int step, int p) { return dcs.p + ((size_t)step * P + p) * nn; };
   MultiPcg mp;   // the P-column solver's interleaved vectors [n_nodes][P] and scalars
   for (auto* v : {&mp.X, &mp.B, &mp.R, &mp.Pv, &mp.Q}) v->alloc_zero((size_t)P * nn, h->st);
   mp.part.alloc_zero((size_t)gl_spmm_blocks(h) * P, h->st);
   mp.part2.alloc_zero((size_t)GL_MP_BLOCKS * 2 * P, h->st);
+  if (part) {
+    mp.sendbuf.alloc_zero((size_t)std::max<int64_t>(h->n_send, 1) * P, h->st);
+    mp.rows.alloc_zero((size_t)h->world * 2 * P, h->st);
+  }
   ForwardGuard guard(h, wk);
   BackwardSweep<D> sw(h, wk, n_terms, terms, false);
+  if (dir_c0) exchange_cols(dcs.p);   // (the caller's ghost entries are not trusted; under the guard: glims_stats stay)
   const uint8_t* fxc = sw.fxc;
   const DevPattern& pt = h->pat;
   const double dt = h->opt.dt;
@@ -1373,6 +1465,7 @@ int hessian_t(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, const
   int& status = sw.status;
   // 1. tangent-linear sweep: A(c_n) dc_n = M dc_{n-1} - dt sum_t dD_t K_t c_n - dt sum_t drho_t int_t (c_n^2 - c_n) phi
   for (int step = 1; step <= N && status == GLIMS_OK; ++step) {
+    gl_halo_exchange(h, a.traj[step]->p, 1);   // (as BackwardSweep::begin_step)
     const double* c = a.traj[step]->p;
     GL_HIP(hipMemsetAsync(wk.tmp.p, 0, (size_t)nn * sizeof(double), h->st));
     gl_rd_assemble(h, c, wk.tmp.p, nullptr, wk.w.p, nullptr, h->partials.p);
@@ -1396,6 +1489,8 @@ int hessian_t(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, const
         hipLaunchKernelGGL(k_zero_fixed, dim3(grid_of(n)), dim3(256), 0, h->st, n, fxc, dc_of(step, p),
                            (const double*)nullptr);
     status = rd_solve_cols(h, wk, mp, fxc, sw.rd_mg, sw.rd_deg, P, hrhs.p, dc_of(step, 0), nn, &tlm_its);
+    // the solve updates the owned rows: the next step's M dc, the row and cell passes of the second sweep read the ghosts
+    if (status == GLIMS_OK) exchange_cols(dc_of(step, 0));
   }
   // 2. the first-order sweep with the second-order adjoint nu_n of every direction
   for (int step = N; step >= 0 && status == GLIMS_OK; --step) {
@@ -1407,6 +1502,7 @@ int hessian_t(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, const
         hipLaunchKernelGGL(k_misfit_dir, dim3(grid_of(n)), dim3(256), 0, h->st, n, tm.kind, tm.level, tm.smooth, c,
                            dc_of(step, p), hd.p);
         GL_CHECK_LAUNCH();
+        gl_halo_exchange(h, hd.p, 1);
         mass_apply(h, hd.p, Mhd.p);
         hipLaunchKernelGGL(k_misfit_second, dim3(grid_of(n)), dim3(256), 0, h->st, n, tm.kind, tm.level, tm.smooth,
                            tm.weight, c, dc_of(step, p), wk.Me.p, Mhd.p, dg.p + (size_t)p * nn);
@@ -1419,9 +1515,10 @@ int hessian_t(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, const
       if (!sw.coupling_adjoint(c)) break;
       // per direction: du = K_el^-1 (G dc + sum_t dgamma_t G_t c), dmu = K_el^-1 sum w M_vec du (0 on the constrained dofs);
       // dg += G^T dmu + sum_t dgamma_t G_t^T mu;  H_gamma_t += dmu^T G_t c + mu^T G_t dc
-      // (mode 1 of the sensitivity pass into the direction's own qcell, partials and sums; every cell counted)
+      // (mode 1 of the sensitivity pass into the direction's own qcell, partials and sums; qcell of every cell, the sums of
+      // the cells this rank counts)
       auto gt_pass = [&](const double* mat, const double* x, const double* v, double* sums) {
-        sens_pass<D>(h, 1, mat, x, v, nullptr, hqcell.p, hpart.p, sums, 3, 2);
+        sens_pass<D>(h, 1, mat, x, v, counted, hqcell.p, hpart.p, sums, 3, 2);
       };
       for (int p = 0; p < P && status == GLIMS_OK; ++p) {
         double* dgp = dg.p + (size_t)p * nn;
@@ -1433,6 +1530,7 @@ int hessian_t(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, const
         GL_CHECK_LAUNCH();
         status = solve_elastic(h, wk, urhs.p, du.p, nullptr, 1e-12, &its);
         if (status != GLIMS_OK) break;
+        gl_halo_exchange(h, du.p, D);
         GL_HIP(hipMemsetAsync(dmurhs.p, 0, (size_t)nd * sizeof(double), h->st));
         for (int k = 0; k < n_terms; ++k) {
           const glims_misfit& tm = terms[k];
@@ -1441,6 +1539,7 @@ int hessian_t(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, const
             hipLaunchKernelGGL(k_component, dim3(grid_of(n)), dim3(256), 0, h->st, n, D, comp, du.p,
                                (const double*)nullptr, ue.p);
             GL_CHECK_LAUNCH();
+            gl_halo_exchange(h, ue.p, 1);
             mass_apply(h, ue.p, uMe.p);
             hipLaunchKernelGGL(k_add_component, dim3(grid_of(n)), dim3(256), 0, h->st, n, D, comp, tm.weight, uMe.p,
                                dmurhs.p);
@@ -1450,6 +1549,7 @@ int hessian_t(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, const
         status = solve_elastic(h, wk, dmurhs.p, dmu.p, nullptr, 1e-12, &its);
         if (status != GLIMS_OK) break;
         extra_mech += 2;
+        gl_halo_exchange(h, dmu.p, D);   // qcell of the cells at the cut
         gt_pass(h->mat.p, c, dmu.p, hs);
         hipLaunchKernelGGL(k_gt_rows, dim3(grid_of(n)), dim3(256), 0, h->st, n, pt.cslice_ptr.p, pt.celem.p, hqcell.p, dgp);
         GL_CHECK_LAUNCH();
@@ -1487,11 +1587,12 @@ int hessian_t(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, const
                            (const double*)nullptr);
     GL_HIP(hipMemcpyAsync(nu.p, nu_next.p, (size_t)P * nn * sizeof(double), hipMemcpyDeviceToDevice, h->st));
     status = rd_solve_cols(h, wk, mp, fxc, sw.rd_mg, sw.rd_deg, P, hrhs.p, nu.p, nn, &soa_its);
+    if (status == GLIMS_OK) exchange_cols(nu.p);   // k_hsens and M nu_{n+1} read the ghosts
     for (int p = 0; p < P && status == GLIMS_OK; ++p) {
       double* x = nu.p + (size_t)p * nn;
       for (int l0 = 0; l0 < L; l0 += GL_ADJ_LT) {   // (H dm)_{D,rho} sums of step n
         hipLaunchKernelGGL(k_hsens<D>, dim3(sens_blocks(h)), dim3(256), 0, h->st, h->n_cells, l0, a.cell_nodes.p, h->egeo.p,
-                           h->label.p, c, wk.lam.p, dc_of(step, p), x, hpart.p);
+                           h->label.p, c, wk.lam.p, dc_of(step, p), x, counted, hpart.p);
         GL_CHECK_LAUNCH();
         hipLaunchKernelGGL(k_sens_final, dim3(1), dim3(1024), 0, h->st, sens_blocks(h), l0, L, 3, 0, hpart.p,
                            hsums.p + (size_t)p * LM * 3);
@@ -1503,9 +1604,33 @@ int hessian_t(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, const
   }
   const size_t L3 = (size_t)L * 3;
   std::vector<double> sums(L3), hs((size_t)P * LM * 3);
-  GL_HIP(hipMemcpyAsync(sums.data(), wk.sums.p, L3 * sizeof(double), hipMemcpyDeviceToHost, h->st));
-  GL_HIP(hipMemcpyAsync(hs.data(), hsums.p, hs.size() * sizeof(double), hipMemcpyDeviceToHost, h->st));
-  GL_HIP(hipStreamSynchronize(h->st));
+  if (!part) {
+    GL_HIP(hipMemcpyAsync(sums.data(), wk.sums.p, L3 * sizeof(double), hipMemcpyDeviceToHost, h->st));
+    GL_HIP(hipMemcpyAsync(hs.data(), hsums.p, hs.size() * sizeof(double), hipMemcpyDeviceToHost, h->st));
+    GL_HIP(hipStreamSynchronize(h->st));
+  } else {
+    // as gradient_t: every rank's W sums (the gradient's [L][3], then [P][L][3] of the directions) gathered through
+    // [world][W] with zeros outside the own row and added in rank order on the host -- reached by every rank, also after a
+    // failed solve (the statuses are global)
+    const size_t W = L3 + (size_t)P * L3;
+    dvec<double> all;
+    all.alloc_zero(W * h->world, h->st);
+    double* row = all.p + W * h->rank;
+    GL_HIP(hipMemcpyAsync(row, wk.sums.p, L3 * sizeof(double), hipMemcpyDeviceToDevice, h->st));
+    for (int p = 0; p < P; ++p)
+      GL_HIP(hipMemcpyAsync(row + L3 * (1 + p), hsums.p + (size_t)p * LM * 3, L3 * sizeof(double), hipMemcpyDeviceToDevice,
+                            h->st));
+    gl_allreduce_bulk(h, all.p, W * h->world);
+    std::vector<double> rows(W * h->world);
+    GL_HIP(hipMemcpyAsync(rows.data(), all.p, rows.size() * sizeof(double), hipMemcpyDeviceToHost, h->st));
+    GL_HIP(hipStreamSynchronize(h->st));
+    for (size_t k = 0; k < W; ++k) {
+      double t = 0.0;
+      for (int r = 0; r < h->world; ++r) t += rows[W * r + k];
+      if (k < L3) sums[k] = t;
+      else hs[((k - L3) / L3) * LM * 3 + (k - L3) % L3] = t;
+    }
+  }
   sw.write_labels(sums.data(), dD, drho, dgamma);
   for (int p = 0; p < P; ++p)
     for (int l = 0; l < L; ++l) {
@@ -1642,6 +1767,22 @@ int gl_adjoint_gradient(glims_ctx* h, int n_terms, const glims_misfit* terms, do
                      : gradient_t<3>(h, n_terms, terms, J, dD, drho, dgamma, dc0, dE, dnu);
 }
 
+namespace {
+int hessian_dispatch(glims_ctx* h, int n_terms, const glims_misfit* terms, int n_dir, const double* dir_D,
+                     const double* dir_rho, const double* dir_gamma, const double* dir_c0, double* J, double* dD, double* drho,
+                     double* dgamma, double* dc0, double* hv_D, double* hv_rho, double* hv_gamma, double* hv_c0, double* stats,
+                     bool mem_checked) {
+  return h->dim == 2 ? hessian_t<2>(h, n_terms, terms, n_dir, dir_D, dir_rho, dir_gamma, dir_c0, J, dD, drho, dgamma, dc0,
+                                    hv_D, hv_rho, hv_gamma, hv_c0, stats, mem_checked)
+                     : hessian_t<3>(h, n_terms, terms, n_dir, dir_D, dir_rho, dir_gamma, dir_c0, J, dD, drho, dgamma, dc0,
+                                    hv_D, hv_rho, hv_gamma, hv_c0, stats, mem_checked);
+}
+void check_n_dir(int n_dir) {
+  GL_REQUIRE(n_dir >= 1 && n_dir <= GL_HESS_MAXDIR, "glims_adjoint_hessian: n_dir = " + std::to_string(n_dir) +
+                                                        ", 1.." + std::to_string(GL_HESS_MAXDIR) + " directions per call");
+}
+}  // namespace
+
 int gl_adjoint_hessian(glims_ctx* h, int n_terms, const glims_misfit* terms, int n_dir, const double* dir_D,
                        const double* dir_rho, const double* dir_gamma, const double* dir_c0, double* J, double* dD,
                        double* drho, double* dgamma, double* dc0, double* hv_D, double* hv_rho, double* hv_gamma,
@@ -1649,10 +1790,69 @@ int gl_adjoint_hessian(glims_ctx* h, int n_terms, const glims_misfit* terms, int
   // (every rank of a partitioned handle refuses alike: no collective is entered)
   GL_REQUIRE(h->world <= 1, "glims_adjoint_hessian: not available on partitioned handles (world > 1)");
   check_gradient_call(h, n_terms, terms, J, "glims_adjoint_hessian");
-  GL_REQUIRE(n_dir >= 1 && n_dir <= GL_HESS_MAXDIR, "glims_adjoint_hessian: n_dir = " + std::to_string(n_dir) +
-                                                        ", 1.." + std::to_string(GL_HESS_MAXDIR) + " directions per call");
-  return h->dim == 2 ? hessian_t<2>(h, n_terms, terms, n_dir, dir_D, dir_rho, dir_gamma, dir_c0, J, dD, drho, dgamma, dc0,
-                                    hv_D, hv_rho, hv_gamma, hv_c0, stats)
-                     : hessian_t<3>(h, n_terms, terms, n_dir, dir_D, dir_rho, dir_gamma, dir_c0, J, dD, drho, dgamma, dc0,
-                                    hv_D, hv_rho, hv_gamma, hv_c0, stats);
+  check_n_dir(n_dir);
+  return hessian_dispatch(h, n_terms, terms, n_dir, dir_D, dir_rho, dir_gamma, dir_c0, J, dD, drho, dgamma, dc0, hv_D, hv_rho,
+                          hv_gamma, hv_c0, stats, false);
+}
+
+int gl_adjoint_hessian_spmd(glims_ctx* h, int n_terms, const glims_misfit* terms, int n_dir, const double* dir_D,
+                            const double* dir_rho, const double* dir_gamma, const double* dir_c0, double* J, double* dD,
+                            double* drho, double* dgamma, double* dc0, double* hv_D, double* hv_rho, double* hv_gamma,
+                            double* hv_c0, double* stats) {
+  if (h->world <= 1)
+    return gl_adjoint_hessian(h, n_terms, terms, n_dir, dir_D, dir_rho, dir_gamma, dir_c0, J, dD, drho, dgamma, dc0, hv_D,
+                              hv_rho, hv_gamma, hv_c0, stats);
+  // Collective, as the partitioned gl_adjoint_gradient: every rank's verdict on its arguments and trajectory, its n_dir, the
+  // NULL pattern of its direction arrays, its stored image terms and its memory verdict go through ONE all-reduce
+  // ([6][world], zeros outside the own column) before any other collective; every rank returns the same status.
+  const std::string who = "glims_adjoint_hessian_spmd";
+  std::string why, why_mem;
+  try {
+    check_gradient_call(h, n_terms, terms, J, who);
+    check_n_dir(n_dir);
+  } catch (const glims_error& e) {
+    if (e.code != GLIMS_E_USAGE) throw;
+    why = e.what();
+  }
+  const bool fits = !why.empty() || hessian_fits(h, n_terms, terms, n_dir, &why_mem);
+  const size_t w = (size_t)h->world, r0 = (size_t)h->rank;
+  std::vector<double> flag(w * 6, 0.0);
+  uint64_t sum_steps = 0;
+  for (const GlImageTerm* t : h->img_terms) sum_steps = (sum_steps * 1000003ull + (uint64_t)t->step + 1) & ((1ull << 52) - 1);
+  flag[r0] = why.empty() ? 0.0 : 1.0;
+  flag[w + r0] = (double)n_dir;
+  flag[2 * w + r0] = (dir_D ? 1.0 : 0.0) + (dir_rho ? 2.0 : 0.0) + (dir_gamma ? 4.0 : 0.0) + (dir_c0 ? 8.0 : 0.0);
+  flag[3 * w + r0] = (double)h->img_terms.size();
+  flag[4 * w + r0] = (double)sum_steps;
+  flag[5 * w + r0] = fits ? 0.0 : 1.0;
+  dvec<double> d_flag;
+  d_flag.upload(flag, h->st);
+  gl_allreduce_bulk(h, d_flag.p, flag.size());
+  GL_HIP(hipMemcpyAsync(flag.data(), d_flag.p, flag.size() * sizeof(double), hipMemcpyDeviceToHost, h->st));
+  GL_HIP(hipStreamSynchronize(h->st));
+  auto ranks_with = [&](size_t row) {
+    std::string s;
+    for (size_t r = 0; r < w; ++r)
+      if (flag[row * w + r] != 0.0) s += (s.empty() ? "" : ", ") + std::to_string(r);
+    return s;
+  };
+  auto differs = [&](size_t row) {
+    for (size_t r = 1; r < w; ++r)
+      if (flag[row * w + r] != flag[row * w]) return true;
+    return false;
+  };
+  const std::string refused = ranks_with(0);
+  if (!why.empty()) throw glims_error(GLIMS_E_USAGE, why + " (ranks that refused: " + refused + ")");
+  if (!refused.empty()) throw glims_error(GLIMS_E_USAGE, who + ": refused on rank(s) " + refused + " (see their messages)");
+  if (differs(1)) throw glims_error(GLIMS_E_USAGE, who + ": the ranks disagree on n_dir");
+  if (differs(2))
+    throw glims_error(GLIMS_E_USAGE, who + ": the ranks disagree on which of dir_D / dir_rho / dir_gamma / dir_c0 are NULL");
+  if (differs(3) || differs(4))
+    throw glims_error(GLIMS_E_USAGE, who + ": the ranks disagree on the stored image terms (their count or the steps they "
+                                         "observe)");
+  const std::string short_mem = ranks_with(5);
+  if (!fits) throw glims_error(GLIMS_E_HIP, why_mem + " (ranks short of memory: " + short_mem + ")");
+  if (!short_mem.empty()) throw glims_error(GLIMS_E_HIP, who + ": rank(s) " + short_mem + " are short of device memory");
+  return hessian_dispatch(h, n_terms, terms, n_dir, dir_D, dir_rho, dir_gamma, dir_c0, J, dD, drho, dgamma, dc0, hv_D, hv_rho,
+                          hv_gamma, hv_c0, stats, true);
 }

@@ -857,6 +857,16 @@ int glims_adjoint_hessian(glims_ctx* h, int n_terms, const glims_misfit* terms, 
   });
 }
 
+int glims_adjoint_hessian_spmd(glims_ctx* h, int n_terms, const glims_misfit* terms, int n_dir, const double* dir_D,
+                               const double* dir_rho, const double* dir_gamma, const double* dir_c0, double* J,
+                               double* dJ_dD, double* dJ_drho, double* dJ_dgamma, double* dJ_dc0, double* hv_D,
+                               double* hv_rho, double* hv_gamma, double* hv_c0, double* stats) {
+  return guarded(h, [&]() {
+    return gl_adjoint_hessian_spmd(h, n_terms, terms, n_dir, dir_D, dir_rho, dir_gamma, dir_c0, J, dJ_dD, dJ_drho,
+                                   dJ_dgamma, dJ_dc0, hv_D, hv_rho, hv_gamma, hv_c0, stats);
+  });
+}
+
 int glims_adjoint_stats(const glims_ctx* h, int64_t out[6], double* ms) {
   if (!h || !out) return GLIMS_E_USAGE;
   const AdjointState& a = h->adj;

@@ -701,6 +701,8 @@ void gl_launch_spmv_block(glims_ctx* h, hipStream_t st, int n_launch, const int3
 int gl_step(glims_ctx* h, int n_steps);
 int gl_solve_mechanics(glims_ctx* h, const double* c_dev = nullptr);   // c_dev: concentration to use (default: state)
 void gl_halo_exchange(glims_ctx* h, double* vec, int bs);   // blocking w.r.t. h->st (no overlap)
+// the same through the caller's send buffer of n_send x bs doubles (the handle's own holds n_send x dim: bs <= dim only)
+void gl_halo_exchange_buf(glims_ctx* h, double* vec, int bs, double* sendbuf);
 void gl_comm_destroy(glims_ctx* h);
 int gl_comm_selftest(glims_ctx* h);
 int gl_mailbox_selftest(glims_ctx* h);
@@ -727,6 +729,11 @@ int gl_adjoint_hessian(glims_ctx* h, int n_terms, const glims_misfit* terms, int
                        const double* dir_rho, const double* dir_gamma, const double* dir_c0, double* J, double* dD,
                        double* drho, double* dgamma, double* dc0, double* hv_D, double* hv_rho, double* hv_gamma,
                        double* hv_c0, double* stats);
+// glims_adjoint_hessian_spmd: the same call on world <= 1, collective on partitioned handles
+int gl_adjoint_hessian_spmd(glims_ctx* h, int n_terms, const glims_misfit* terms, int n_dir, const double* dir_D,
+                            const double* dir_rho, const double* dir_gamma, const double* dir_c0, double* J, double* dD,
+                            double* drho, double* dgamma, double* dc0, double* hv_D, double* hv_rho, double* hv_gamma,
+                            double* hv_c0, double* stats);
 // AdjointState::cell_nodes ([n_cells][nv], internal cell order, the caller's vertex order), built on first use: the gradients
 // and the samplers share ONE builder
 const int32_t* gl_ensure_cell_nodes(glims_ctx* h);

@@ -701,18 +701,20 @@ inline unsigned grid_exact(int64_t n, int bs = 256) { return (unsigned)((n + bs 
 // ===================================================================================================
 // halo exchange (RCCL grouped send/recv on the communication stream)
 // ===================================================================================================
-// `prepacked`: the kernel that produced `vec` has written the send buffer already (PackMap)
-static void halo_start(glims_ctx* h, double* vec, int bs, bool prepacked = false) {
+// `prepacked`: the kernel that produced `vec` has written the send buffer already (PackMap).  `sbuf`: the caller's send
+// buffer of n_send x bs doubles (bs > dim does not fit the handle's own), else h->sendbuf.
+static void halo_start(glims_ctx* h, double* vec, int bs, bool prepacked = false, double* sbuf = nullptr) {
   if (h->world <= 1 || h->n_peers == 0) return;
+  if (!sbuf) sbuf = h->sendbuf.p;
   h->stats.halo_exchanges++;
   h->stats.halo_bytes += h->n_send * bs * (int64_t)sizeof(double);
   if (h->n_send > 0 && !prepacked) {
     hipLaunchKernelGGL(k_pack, dim3(grid_exact(h->n_send * bs)), dim3(256), 0, h->st, h->n_send, bs,
-                       h->send_idx.p, vec, h->sendbuf.p);
+                       h->send_idx.p, vec, sbuf);
     GL_HIP(hipGetLastError());
   }
   if (h->tr_halo) {
-    const int rc = h->tr_halo(h->tr_user, h->sendbuf.p, h->send_ptr.data(), vec + h->n_own * bs, h->recv_ptr.data(),
+    const int rc = h->tr_halo(h->tr_user, sbuf, h->send_ptr.data(), vec + h->n_own * bs, h->recv_ptr.data(),
                               h->n_peers, h->peer_rank.data(), bs, (void*)h->st);
     if (rc != 0) throw glims_error(GLIMS_E_RCCL, "transport halo callback failed (" + std::to_string(rc) + ")");
     return;
@@ -726,7 +728,7 @@ static void halo_start(glims_ctx* h, double* vec, int bs, bool prepacked = false
   for (int p = 0; p < h->n_peers; ++p) {
     const int64_t ns = h->send_ptr[p + 1] - h->send_ptr[p], nr = h->recv_ptr[p + 1] - h->recv_ptr[p];
     if (ns > 0)
-      GL_NCCL(ncclSend(h->sendbuf.p + h->send_ptr[p] * bs, (size_t)ns * bs, ncclDouble, h->peer_rank[p],
+      GL_NCCL(ncclSend(sbuf + h->send_ptr[p] * bs, (size_t)ns * bs, ncclDouble, h->peer_rank[p],
                        h->comm_halo, h->st_comm));
     if (nr > 0)
       GL_NCCL(ncclRecv(vec + (h->n_own + h->recv_ptr[p]) * bs, (size_t)nr * bs, ncclDouble, h->peer_rank[p],
@@ -747,6 +749,10 @@ static void halo_finish(glims_ctx* h) {
 }
 void gl_halo_exchange(glims_ctx* h, double* vec, int bs) {
   halo_start(h, vec, bs);
+  halo_finish(h);
+}
+void gl_halo_exchange_buf(glims_ctx* h, double* vec, int bs, double* sendbuf) {
+  halo_start(h, vec, bs, false, sendbuf);
   halo_finish(h);
 }
 void gl_exchange(glims_ctx* h, const std::vector<int32_t>& peers, const std::vector<int64_t>& send_ptr,

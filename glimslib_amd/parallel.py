@@ -350,14 +350,9 @@ class DistributedHandle:
     def adjoint_record(self, on=True):
         self.h.adjoint_record(on)
 
-    def adjoint_hessian(self, terms, directions, n_labels=None):
-        """Second-order adjoint: single-GPU handles only (glims_adjoint_hessian refuses partitioned handles)."""
-        raise NotImplementedError("adjoint_hessian: not available on partitioned runs; use a single-GPU handle")
-
-    def adjoint_gradient(self, terms, n_labels=None, want_dc0=True, elastic=False):
-        """Handle.adjoint_gradient on the partitioned run: targets in GLOBAL node order ([n_global] or [n_global, dim]),
-        localised here; J and the per-label arrays come back bitwise the same on every rank, dJ/dc0 all-gathered into the
-        global order (as get_state does).  elastic=True (on every rank alike) appends dJ/dE and dJ/dnu."""
+    def _local_terms(self, terms):
+        """The term dicts with their nodal targets localised (GLOBAL node order in) and their image terms on the rank-local
+        sampler."""
         loc = []
         for t in terms:
             if t["kind"] in _backend._IMAGE_KINDS:
@@ -367,7 +362,38 @@ class DistributedHandle:
             bs = self.dim if t["kind"] in ("u_l2", _backend.MISFIT_U_L2) else 1
             t["target"] = self._local(t["target"], bs).reshape(-1)
             loc.append(t)
-        res = self.h.adjoint_gradient(loc, n_labels=n_labels, want_dc0=want_dc0, elastic=elastic)
+        return loc
+
+    def _gather_owned(self, v):
+        """Rank-local node vectors [..., n_local] -> the GLOBAL order, from every rank's owned entries (as get_state)."""
+        n_own = self.part.n_own
+        parts = [None] * self.world
+        self.dist.all_gather_object(parts, (self.part.global_ids[:n_own], np.ascontiguousarray(v[..., :n_own])))
+        out = np.empty(v.shape[:-1] + (self.n_global,))
+        for gid, a in parts:
+            out[..., gid] = a
+        return out
+
+    def adjoint_hessian(self, terms, directions, n_labels=None):
+        """Handle.adjoint_hessian on the partitioned run (glims_adjoint_hessian_spmd, collective: every rank calls it with
+        the same terms and directions).  Targets and 'c0' directions in GLOBAL node order, localised here; J and every
+        per-label array come back bitwise the same on every rank; 'c0' and 'hv_c0' are all-gathered into the global order."""
+        dirs = []
+        for d in directions:
+            d = dict(d)
+            if d.get("c0") is not None:
+                d["c0"] = self._local(np.broadcast_to(np.asarray(d["c0"], dtype=np.float64), (self.n_global,)))
+            dirs.append(d)
+        r = self.h.adjoint_hessian(self._local_terms(terms), dirs, n_labels=n_labels, collective=True)
+        r["c0"] = self._gather_owned(r["c0"])
+        r["hv_c0"] = self._gather_owned(r["hv_c0"])
+        return r
+
+    def adjoint_gradient(self, terms, n_labels=None, want_dc0=True, elastic=False):
+        """Handle.adjoint_gradient on the partitioned run: targets in GLOBAL node order ([n_global] or [n_global, dim]),
+        localised here; J and the per-label arrays come back bitwise the same on every rank, dJ/dc0 all-gathered into the
+        global order (as get_state does).  elastic=True (on every rank alike) appends dJ/dE and dJ/dnu."""
+        res = self.h.adjoint_gradient(self._local_terms(terms), n_labels=n_labels, want_dc0=want_dc0, elastic=elastic)
         J, dD, drho, dgamma, dc0 = res[:5]
         if want_dc0:
             n_own = self.part.n_own

@@ -573,12 +573,32 @@ int glims_adjoint_gradient_full(glims_ctx* h, int n_terms, const glims_misfit* t
  * no product).  Device memory on top of the trajectory: 8 n_dir B per node and recorded state (the stored dc_n) plus
  * O(n_dir) vectors; a call that does not fit returns GLIMS_E_HIP before it allocates.  The forward state and glims_stats are
  * left as they were; glims_adjoint_stats does not count this call.  stats (may be NULL) [4]: tangent-linear PCG iterations,
- * second-order PCG iterations, extra elastic solves, wall ms.  Partitioned handles: GLIMS_E_USAGE on every rank.  Stands in
+ * second-order PCG iterations, extra elastic solves, wall ms.  Partitioned handles: GLIMS_E_USAGE on every rank (no
+ * collective is entered; glims_adjoint_hessian_spmd below is the collective call).  Stands in
  * for fenics.ReducedFunctional.hessian (the H that minimize_custom hands its optimizer, image_based_optimization.py:646). */
 int glims_adjoint_hessian(glims_ctx* h, int n_terms, const glims_misfit* terms, int n_dir, const double* dir_D,
                           const double* dir_rho, const double* dir_gamma, const double* dir_c0, double* J, double* dJ_dD,
                           double* dJ_drho, double* dJ_dgamma, double* dJ_dc0, double* hv_D, double* hv_rho,
                           double* hv_gamma, double* hv_c0, double* stats);
+
+/* glims_adjoint_hessian, collective on partitioned handles.  world <= 1: the same function, the same bits in every output.
+ * world > 1, with the contract of the partitioned glims_adjoint_gradient: every rank calls it with the same term list
+ * (targets in its local numbering), the same n_dir, the same dir_D / dir_rho / dir_gamma tables and the same NULL pattern of
+ * the four direction arrays.  dir_c0 and hv_c0 are [n_dir][n_nodes] in the local numbering: the owned entries of dir_c0 are
+ * read (its ghost entries are not trusted: dc_0 exchanges its ghosts after the upload), the owned entries of hv_c0 are
+ * written and its ghost entries are 0.  J, the gradient arrays, hv_D, hv_rho and hv_gamma are bitwise the same on every rank
+ * and on every call; J and the gradient are bitwise those of glims_adjoint_gradient on the same handle.  Each cell enters
+ * the per-label sums on the smallest rank that owns one of its vertices; the ranks' sums are added in rank order.  The
+ * n_dir-column PCG exchanges the ghosts of its operand before every multi-right-hand-side SpMV and takes its scalar step
+ * from sums over all ranks (two all-reduces per iteration), so every rank runs the same iterations; column j still has the
+ * bits of a one-direction call.  Before any other collective the ranks' verdicts -- arguments and trajectory, n_dir, the
+ * NULL pattern, the stored image terms (count and steps), device memory -- go through one all-reduce: if any rank refuses,
+ * every rank returns the same status (GLIMS_E_USAGE, or GLIMS_E_HIP for memory) and the handle is left as it was.  stats is
+ * per rank (the iteration counts are the same on all ranks).  Single node; E and nu stay first order. */
+int glims_adjoint_hessian_spmd(glims_ctx* h, int n_terms, const glims_misfit* terms, int n_dir, const double* dir_D,
+                               const double* dir_rho, const double* dir_gamma, const double* dir_c0, double* J,
+                               double* dJ_dD, double* dJ_drho, double* dJ_dgamma, double* dJ_dc0, double* hv_D,
+                               double* hv_rho, double* hv_gamma, double* hv_c0, double* stats);
 
 /* Counters of the adjoint (not in glims_stats, whose layout is fixed): out[0] gradient calls, [1] backward steps,
  * [2] RD adjoint PCG iterations, [3] elastic solves, [4] their PCG iterations, [5] recorded states held now;
