@@ -8,6 +8,7 @@
 // of FEM assembly needs neither atomics nor colouring and is bitwise reproducible.
 #include "glims_internal.h"
 #include "record_words.h"
+#include "sweep_instances.h"
 #include <hip/hip_ext.h>
 
 #include <algorithm>
@@ -1561,6 +1562,39 @@ static void set_lds(K kern, size_t bytes) {
     GL_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
 }
 
+// Run-time values as template arguments: gl_switch(f, v1, gl_vals<a, b, ..>(), v2, gl_vals<..>(), ..) calls
+// f(gl_c<V1>(), gl_c<V2>(), ..) for the listed values that equal v1, v2, .. and returns what f returns; false where a value is
+// not in its list.  f is a generic lambda that returns bool and guards with `if constexpr` the combinations that have no
+// kernel: every combination it does not discard is instantiated.  A chain of integer compares: nothing is allocated.
+template <int V>
+using gl_c = std::integral_constant<int, V>;
+template <int... Vs>
+struct gl_vals {};
+template <class F>
+static bool gl_switch(F&& f) {
+  return f();
+}
+template <class F, int... Vs, class... Rest>
+static bool gl_switch(F&& f, int v, gl_vals<Vs...>, Rest... rest) {
+  return ((v == Vs && gl_switch([&](auto... cs) { return f(gl_c<Vs>(), cs...); }, rest...)) || ...);
+}
+using gl_bool = gl_vals<0, 1>;
+// b where the constant says so, else a (operands of two types, such as an operator's fp64 and fp32 copies)
+template <int WHICH, class A, class B>
+static auto gl_either(A a, B b) {
+  if constexpr (WHICH != 0) return b;
+  else return a;
+}
+
+// One launch.  ev0 / ev1 (glims_options.time_kernels): start / stop events attached to THIS dispatch (hipExtLaunchKernelGGL) --
+// the kernel's own timestamps, no extra packets in the queue.  hipEventRecord before and after the launch put a 5-6 us idle
+// gap on either side of every SpMV (profiles/r02_c3_timeline.txt), 14 % of the step at 1 M rows.
+template <class K, class... A>
+static void gl_launch(K kern, int grid, int block, size_t lds, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1, A... args) {
+  if (ev0 || ev1) hipExtLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, st, ev0, ev1, 0, args...);
+  else hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, st, args...);
+}
+
 void gl_compute_egeo(glims_ctx* h, const double* d_xyz, const int32_t* d_cells) {
   const int GE = 1 + h->nv * h->dim;
   h->egeo.alloc((size_t)h->n_cells * GE);
@@ -1716,7 +1750,7 @@ int gl_rd_grid(const glims_ctx* h) { return h->pat.n_slices; }
 // ---- slice classes ------------------------------------------------------------------------------------------------------
 // The incidence-list kernels are launched per class of slice length: their LDS footprint (16 B x length per row for the
 // sweep) decides how many waves a CU holds, so the (few) long rows of an unstructured mesh must not size it for everybody;
-// and the straight-line kernels unroll to a compile-time bound (16 / 20 / 24 / 32 entries; classes of longer slices take the
+// and the straight-line kernels unroll to a compile-time bound (sweep_instances.h; classes of longer slices take the
 // looped kernels).  Built once per handle from the symbolic phase's length classes: a class of fewer than 1024 slices (less
 // than half a round of waves: it costs a launch tail of one wave lifetime, ~14 us, for nothing) joins the next shorter one
 // unless that would cost the shorter class a resident wave per CU.
@@ -1841,9 +1875,8 @@ static void record_launches(const SliceClass& sc, int part, bool rec, ClassLaunc
 }
 
 // Assembles A(c) and the Newton right-hand side(s).  partials: [gl_rd_grid][2] = (|b - ..|^2, |b2 - ..|^2).
-// Kernel configuration (measured): classes of at most 32 entries per row take the straight-line kernel
-// (k_rd_assemble_s), longer ones the looped one with 24 incidence records in flight per lane; one slice per block dealt to
-// the XCDs in chunks; cached (not non-temporal) streams.  AT: the Newton Jacobian is written in fp64 or
+// Kernel configuration (measured): which instance a class takes is sweep_instances.h's to say; one slice
+// per block dealt to the XCDs in chunks; cached (not non-temporal) streams.  AT: the Newton Jacobian is written in fp64 or
 // (GLIMS_FLAG_FP32_JACOBIAN) fp32.
 // fused (kind 1 / 2): the sweep also emits the first pass of the dot-free solve that follows (k_rd_assemble_sg); only where
 // gl_rd_fusable says so.
@@ -1857,11 +1890,61 @@ bool gl_rd_fusable(glims_ctx* h) {
 bool gl_rd_mass_in_sweep(glims_ctx* h) {
   return (h->opt.flags & GLIMS_FLAG_NO_FUSED_MASS) == 0 && h->world == 1 && gl_rd_fusable(h);
 }
+// (the message of a launch without an instance: built on that path only)
+static std::string key_text(const char* what, const GlSweepKey& k) {
+  return std::string(what) + " has no instance for nv " + std::to_string(k.nv) + ", cap " + std::to_string(k.cap) + ", rb " +
+         std::to_string(k.rb) + ", cidx " + std::to_string(k.cidx) + ", at " + std::to_string(k.at) + ", fg " +
+         std::to_string(k.fg) + ", mb " + std::to_string(k.mb) + ", st " + std::to_string(k.st);
+}
+// what every launch of one sweep shares
+struct SweepArgs {
+  const double *c, *b, *b2;
+  double *r_out, *r2_out, *partials;
+  const uint8_t* fixed;
+  MassArgs ma;
+  FgArgs fg;   // (key.fg != 0)
+};
+// one launch of the instance `k` names over cl; class_cap: the longest row of the class.  false: no such instance.
+static bool launch_sweep(glims_ctx* h, const GlSweepKey& k, const ClassLaunch& cl, int class_cap, const SweepArgs& a) {
+  const DevPattern& p = h->pat;
+  const size_t lds = gl_sweep_lds(class_cap);
+  return gl_switch(
+      [&](auto NV, auto CAP, auto CIDX, auto AT, auto FG, auto MB, auto ST) {
+        if constexpr (gl_sweep_instance(NV, CAP, CIDX, AT, FG, MB, ST)) {
+          constexpr int RB = gl_sweep_records(NV, CAP, CIDX, FG, MB, ST);
+          using at_t = std::conditional_t<AT == GL_AT_F32, float, double>;
+          using st_t = std::conditional_t<ST == GL_ST_U16, uint16_t, std::conditional_t<ST == GL_ST_REC32, rec32_t, uint32_t>>;
+          at_t* vA = gl_either<AT == GL_AT_F32>(h->vA.p, h->vA32.p);
+          if constexpr (CAP == 0) {
+            set_lds(k_rd_assemble<NV, 0, RB, CIDX, at_t>, lds);
+            hipLaunchKernelGGL((k_rd_assemble<NV, 0, RB, CIDX, at_t>), dim3(cl.grid), dim3(GL_WAVE), lds, h->st, cl.list,
+                               h->n_own, p.slice_ptr.p, p.cols.p, p.cols16.p, p.win_base.p, p.win_ok.p, p.cslice_ptr.p,
+                               p.cs2.p, p.cw.p, p.diag_k.p, h->vS.p, vA, a.c, a.b, a.b2, a.r_out, a.r2_out, h->dinv.p,
+                               a.fixed, 2.0 * h->opt.dt, a.partials, class_cap, GL_XCD_CHUNK);
+          } else {
+            const uint32_t* slots = ST == GL_ST_U16 ? p.cs16.p : ST == GL_ST_REC32 ? p.cr32.p : p.cs2.p;
+            auto straight = [&](auto kern, auto... tail) {   // (the two families differ in their last arguments)
+              set_lds(kern, lds);
+              hipLaunchKernelGGL(kern, dim3(cl.grid), dim3(GL_WAVE), lds, h->st, cl.desc, h->n_own, p.cols.p, p.cols16.p,
+                                 p.win_base.p, slots, p.cw.p, p.diag_k.p, h->vS.p, vA, a.c, a.b, a.b2, a.r_out, a.r2_out,
+                                 h->dinv.p, a.fixed, 2.0 * h->opt.dt, a.partials, class_cap, GL_XCD_CHUNK, tail...);
+            };
+            if constexpr (FG != 0) straight(k_rd_assemble_sg<NV, CAP, RB, CIDX, FG, MB, st_t>, a.fg, a.ma);
+            else straight(k_rd_assemble_s<NV, CAP, RB, CIDX, at_t, MB, st_t>, a.ma);
+          }
+          return true;
+        } else {
+          return false;
+        }
+      },
+      k.nv, gl_vals<3, 4>(), k.cap, gl_vals<0, 16, 20, 24, 32>(), k.cidx, gl_bool(), k.at, gl_vals<GL_AT_F64, GL_AT_F32>(), k.fg,
+      gl_vals<0, 1, 2>(), k.mb, gl_bool(), k.st, gl_vals<GL_ST_U32, GL_ST_U16, GL_ST_REC32>());
+}
+
 void gl_rd_assemble(glims_ctx* h, const double* c, const double* b, const double* b2, double* r_out, double* r2_out,
                     double* partials, int part, const GlFusedSweep* fused, const GlMassSweep* mass) {
   ensure_classes(h);
   const DevPattern& p = h->pat;
-  const uint8_t* fx = h->have_fixed_c ? h->fixed_c.p : nullptr;
   // the straight-line sweeps' slot stream: 16-bit words unless the handle has none or GLIMS_FLAG_SLOT_WORDS32 asks for cs2
   const bool w16 = p.cs16.p != nullptr && (h->opt.flags & GLIMS_FLAG_SLOT_WORDS32) == 0;
   if (w16) h->stats.rd_slot16_sweeps++;   // (cs16 exists only where a straight-line class reads it)
@@ -1869,199 +1952,33 @@ void gl_rd_assemble(glims_ctx* h, const double* c, const double* b, const double
   // 16-bit column codes -- the int32-column and fp32-Jacobian handles keep cw + cs16 -- unless GLIMS_FLAG_RECORD_WORDS_FULL
   const bool rec = w16 && p.cr32.p != nullptr && (h->opt.flags & GLIMS_FLAG_RECORD_WORDS_FULL) == 0 && !h->jac32 && h->use_idx16;
   ensure_record_lists(h);
-  {
-    bool any = false;
-    for (const SliceClass* sc : p.classes) {
-      ClassLaunch rl[2];
-      record_launches(*sc, part, rec, rl);
-      any = any || rl[0].grid > 0;
-    }
-    if (any) h->stats.rd_rec32_sweeps++;
-  }
-  MassArgs ma{nullptr, nullptr, nullptr};
+  SweepArgs a{c, b, b2, r_out, r2_out, partials, h->have_fixed_c ? h->fixed_c.p : nullptr, MassArgs{nullptr, nullptr, nullptr}, FgArgs{}};
   if (mass) {
     GL_REQUIRE(gl_rd_fusable(h) && part == GL_PART_ALL && mass->bw == (b2 ? b2 : b),
                "mass product requested where the sweep has no kernel for it");
-    ma.q = p.mass_q.p;
-    ma.load = mass->load;
-    ma.bw = mass->bw;
+    a.ma = MassArgs{p.mass_q.p, mass->load, mass->bw};
   }
-  if (fused && fused->kind != 0) {
-    GL_REQUIRE(gl_rd_fusable(h) && part == GL_PART_ALL && (fused->kind == 1 || fused->kind == 2),
+  const int fg_kind = fused ? fused->kind : 0;
+  if (fg_kind != 0) {
+    GL_REQUIRE(gl_rd_fusable(h) && part == GL_PART_ALL && (fg_kind == 1 || fg_kind == 2),
                "fused guess pass requested where the sweep has no kernel for it");
-    FgArgs fg;
-    fg.u = fused->u;
-    fg.y1 = fused->y1;
-    fg.part = fused->part;
-    fg.rlen = p.rlen.p;
-    fg.c2 = fused->c2;
     // (MB = 1 only with two right-hand sides: the sweeps that carry a guess pass and define a b are the speculative ones)
     GL_REQUIRE(!mass || b2, "fused guess pass with the mass product: two right-hand sides only");
-#define GL_RDG5(NV, CAP, RB, CIDX, FG, MB, ST, SPTR)                                                                \
-  do {                                                                                                             \
-    set_lds(k_rd_assemble_sg<NV, CAP, RB, CIDX, FG, MB, ST>, lds);                                                 \
-    hipLaunchKernelGGL((k_rd_assemble_sg<NV, CAP, RB, CIDX, FG, MB, ST>), dim3(cl.grid), dim3(GL_WAVE), lds, h->st, \
-                       cl.desc, h->n_own, p.cols.p, p.cols16.p, p.win_base.p, SPTR, p.cw.p, p.diag_k.p, h->vS.p,    \
-                       h->vA.p, c, b, b2, r_out, r2_out, h->dinv.p, fx, 2.0 * h->opt.dt, partials, cap,             \
-                       GL_XCD_CHUNK, fg, ma);                                                                      \
-  } while (0)
-#define GL_RDG4(NV, CAP, RB32, RB16, CIDX, FG, MB)                                                                  \
-  do {                                                                                                             \
-    if (w16) GL_RDG5(NV, CAP, RB16, CIDX, FG, MB, uint16_t, p.cs16.p);                                             \
-    else GL_RDG5(NV, CAP, RB32, CIDX, FG, MB, uint32_t, p.cs2.p);                                                  \
-  } while (0)
-  // (records of the first round trip, rows of at most 16 entries: 26 = 2 x 16 - 6; one fewer where the guess's gather, 32-bit
-  //  columns and the mass accumulator meet -- 170 registers with 26, two waves per SIMD instead of three; a row of 16 entries
-  //  then fetches its last record in a second round trip, the same terms in the same order.  With the paired 16-bit slot
-  //  words a round trip holds half as many slot registers: 26 records there too)
-#define GL_RDG_RB16(NV, CIDX, FG, MB) ((NV) == 4 && (CIDX) == 0 && (FG) == 1 && (MB) == 1 ? 25 : 26)
-#define GL_RDG3(NV, CIDX, FG, MB)                                                                                   \
-  do {                                                                                                             \
-    if (cap <= 16) GL_RDG4(NV, 16, GL_RDG_RB16(NV, CIDX, FG, MB), 26, CIDX, FG, MB);                               \
-    else if (cap <= 20) GL_RDG4(NV, 20, 24, 24, CIDX, FG, MB);                                                     \
-    else if (cap <= 24) GL_RDG4(NV, 24, 24, 24, CIDX, FG, MB);                                                     \
-    else GL_RDG4(NV, 32, 24, 24, CIDX, FG, MB);                                                                    \
-  } while (0)
-#define GL_RDG2(NV, CIDX)                                                                                           \
-  do {                                                                                                             \
-    if (fused->kind == 1 && mass) GL_RDG3(NV, CIDX, 1, 1);                                                         \
-    else if (fused->kind == 1) GL_RDG3(NV, CIDX, 1, 0);                                                            \
-    else if (mass) GL_RDG3(NV, CIDX, 2, 1);                                                                        \
-    else GL_RDG3(NV, CIDX, 2, 0);                                                                                  \
-  } while (0)
-  // (the compact lists: 16-bit column codes only; records per round trip as the cs16 siblings)
-#define GL_RDG3R(NV, FG, MB)                                                                                        \
-  do {                                                                                                             \
-    if (cap <= 16) GL_RDG5(NV, 16, 26, 1, FG, MB, rec32_t, p.cr32.p);                                              \
-    else if (cap <= 20) GL_RDG5(NV, 20, 24, 1, FG, MB, rec32_t, p.cr32.p);                                         \
-    else if (cap <= 24) GL_RDG5(NV, 24, 24, 1, FG, MB, rec32_t, p.cr32.p);                                         \
-    else GL_RDG5(NV, 32, 24, 1, FG, MB, rec32_t, p.cr32.p);                                                        \
-  } while (0)
-#define GL_RDG2R(NV)                                                                                                \
-  do {                                                                                                             \
-    if (fused->kind == 1 && mass) GL_RDG3R(NV, 1, 1);                                                              \
-    else if (fused->kind == 1) GL_RDG3R(NV, 1, 0);                                                                 \
-    else if (mass) GL_RDG3R(NV, 2, 1);                                                                             \
-    else GL_RDG3R(NV, 2, 0);                                                                                       \
-  } while (0)
-    for (const SliceClass* sc : p.classes) {
-      ClassLaunch rl[2];
-      record_launches(*sc, part, rec, rl);
-      const int cap = sc->cap;
-      const size_t lds = (size_t)2 * cap * GL_WAVE * sizeof(double);
-      if (rl[0].grid > 0) {
-        const ClassLaunch cl = rl[0];
-        if (h->nv == 3) GL_RDG2R(3); else GL_RDG2R(4);
-      }
-      const ClassLaunch cl = rl[1];
-      if (cl.grid <= 0) continue;
-      if (h->nv == 3) {
-        if (h->use_idx16) GL_RDG2(3, 1); else GL_RDG2(3, 0);
-      } else {
-        if (h->use_idx16) GL_RDG2(4, 1); else GL_RDG2(4, 0);
-      }
-    }
-#undef GL_RDG2R
-#undef GL_RDG3R
-#undef GL_RDG2
-#undef GL_RDG_RB16
-#undef GL_RDG3
-#undef GL_RDG4
-#undef GL_RDG5
-    GL_HIP(hipGetLastError());
-    return;
+    a.fg = FgArgs{fused->u, fused->y1, fused->part, p.rlen.p, fused->c2};
   }
-#define GL_RD(NV, CIDX, AT, APTR)                                                                                   \
-  do {                                                                                                             \
-    set_lds(k_rd_assemble<NV, 0, 24, CIDX, AT>, lds);                                                              \
-    hipLaunchKernelGGL((k_rd_assemble<NV, 0, 24, CIDX, AT>), dim3(cl.grid), dim3(GL_WAVE), lds, h->st, cl.list,     \
-                       h->n_own, p.slice_ptr.p, p.cols.p, p.cols16.p, p.win_base.p, p.win_ok.p, p.cslice_ptr.p,     \
-                       p.cs2.p, p.cw.p, p.diag_k.p, h->vS.p, APTR, c, b, b2, r_out, r2_out, h->dinv.p, fx,           \
-                       2.0 * h->opt.dt, partials, cap, GL_XCD_CHUNK);                                              \
-  } while (0)
-#define GL_RDS4(NV, CAP, RB, CIDX, AT, APTR, MB, ST, SPTR)                                                          \
-  do {                                                                                                             \
-    set_lds(k_rd_assemble_s<NV, CAP, RB, CIDX, AT, MB, ST>, lds);                                                  \
-    hipLaunchKernelGGL((k_rd_assemble_s<NV, CAP, RB, CIDX, AT, MB, ST>), dim3(cl.grid), dim3(GL_WAVE), lds, h->st,  \
-                       cl.desc, h->n_own, p.cols.p, p.cols16.p, p.win_base.p, SPTR, p.cw.p, p.diag_k.p, h->vS.p,    \
-                       APTR, c, b, b2, r_out, r2_out, h->dinv.p, fx, 2.0 * h->opt.dt, partials, cap, GL_XCD_CHUNK,  \
-                       ma);                                                                                        \
-  } while (0)
-#define GL_RDS3(NV, CAP, RB, CIDX, AT, APTR)                                                                        \
-  do {                                                                                                             \
-    if (w16) GL_RDS4(NV, CAP, RB, CIDX, AT, APTR, 0, uint16_t, p.cs16.p);                                          \
-    else GL_RDS4(NV, CAP, RB, CIDX, AT, APTR, 0, uint32_t, p.cs2.p);                                               \
-  } while (0)
-  // (MB = 1: fp64 Jacobian, straight-line classes only -- gl_rd_fusable, required above)
-#define GL_RDM3(NV, CAP, RB, CIDX)                                                                                  \
-  do {                                                                                                             \
-    if (w16) GL_RDS4(NV, CAP, RB, CIDX, double, h->vA.p, 1, uint16_t, p.cs16.p);                                   \
-    else GL_RDS4(NV, CAP, RB, CIDX, double, h->vA.p, 1, uint32_t, p.cs2.p);                                        \
-  } while (0)
-#define GL_RDM2(NV, CIDX)                                                                                           \
-  do {                                                                                                             \
-    if (cap <= 16) GL_RDM3(NV, 16, 26, CIDX);                                                                      \
-    else if (cap <= 20) GL_RDM3(NV, 20, 24, CIDX);                                                                 \
-    else if (cap <= 24) GL_RDM3(NV, 24, 24, CIDX);                                                                 \
-    else GL_RDM3(NV, 32, 24, CIDX);                                                                                \
-  } while (0)
-  // (incidence records of the first round trip: an interior row of a tetrahedral mesh with n entries has 2 n - 6 of them)
-#define GL_RDS2(NV, CIDX, AT, APTR)                                                                                 \
-  do {                                                                                                             \
-    if (cap <= 16) GL_RDS3(NV, 16, 26, CIDX, AT, APTR);                                                            \
-    else if (cap <= 20) GL_RDS3(NV, 20, 24, CIDX, AT, APTR);                                                       \
-    else if (cap <= 24) GL_RDS3(NV, 24, 24, CIDX, AT, APTR);                                                       \
-    else if (cap <= 32) GL_RDS3(NV, 32, 24, CIDX, AT, APTR);                                                       \
-    else GL_RD(NV, CIDX, AT, APTR);                                                                                \
-  } while (0)
-#define GL_RDV(NV)                                                                                                  \
-  do {                                                                                                             \
-    if (h->jac32 && h->use_idx16) GL_RDS2(NV, 1, float, h->vA32.p);                                                \
-    else if (h->jac32) GL_RDS2(NV, 0, float, h->vA32.p);                                                           \
-    else if (h->use_idx16) GL_RDS2(NV, 1, double, h->vA.p);                                                        \
-    else GL_RDS2(NV, 0, double, h->vA.p);                                                                          \
-  } while (0)
-  // (the compact lists: fp64 Jacobian, 16-bit column codes, with or without the mass product)
-#define GL_RDR3(NV, CAP, RB)                                                                                        \
-  do {                                                                                                             \
-    if (mass) GL_RDS4(NV, CAP, RB, 1, double, h->vA.p, 1, rec32_t, p.cr32.p);                                      \
-    else GL_RDS4(NV, CAP, RB, 1, double, h->vA.p, 0, rec32_t, p.cr32.p);                                           \
-  } while (0)
-#define GL_RDR2(NV)                                                                                                 \
-  do {                                                                                                             \
-    if (cap <= 16) GL_RDR3(NV, 16, 26);                                                                            \
-    else if (cap <= 20) GL_RDR3(NV, 20, 24);                                                                       \
-    else if (cap <= 24) GL_RDR3(NV, 24, 24);                                                                       \
-    else GL_RDR3(NV, 32, 24);                                                                                      \
-  } while (0)
+  bool any_rec32 = false;
   for (const SliceClass* sc : p.classes) {
-    ClassLaunch rl[2];
+    ClassLaunch rl[2];   // [0] the class's compact slices, [1] its other ones
     record_launches(*sc, part, rec, rl);
-    const int cap = sc->cap;
-    const size_t lds = (size_t)2 * cap * GL_WAVE * sizeof(double);
-    if (rl[0].grid > 0) {
-      const ClassLaunch cl = rl[0];
-      if (h->nv == 3) GL_RDR2(3); else GL_RDR2(4);
+    for (int e = 0; e < 2; ++e) {
+      if (rl[e].grid <= 0) continue;
+      const GlSweepKey k = gl_sweep_key(h->nv, sc->cap, h->use_idx16, h->jac32, fg_kind, mass != nullptr,
+                                        e == 0 ? GL_ST_REC32 : w16 ? GL_ST_U16 : GL_ST_U32);
+      GL_REQUIRE(k.ok && launch_sweep(h, k, rl[e], sc->cap, a), key_text("the assembly sweep", k));
+      any_rec32 = any_rec32 || e == 0;
     }
-    const ClassLaunch cl = rl[1];
-    if (cl.grid <= 0) continue;
-    if (mass) {
-      if (h->nv == 3) {
-        if (h->use_idx16) GL_RDM2(3, 1); else GL_RDM2(3, 0);
-      } else {
-        if (h->use_idx16) GL_RDM2(4, 1); else GL_RDM2(4, 0);
-      }
-    } else if (h->nv == 3) GL_RDV(3); else GL_RDV(4);
   }
-#undef GL_RDR2
-#undef GL_RDR3
-#undef GL_RDM2
-#undef GL_RDM3
-#undef GL_RDV
-#undef GL_RDS2
-#undef GL_RDS3
-#undef GL_RDS4
-#undef GL_RD
+  if (any_rec32) h->stats.rd_rec32_sweeps++;
   GL_HIP(hipGetLastError());
 }
 
@@ -2070,37 +1987,35 @@ void gl_rd_quad(glims_ctx* h, const float* ad, double* r, double* partials, int 
   ensure_classes(h);
   const DevPattern& p = h->pat;
   const uint8_t* fx = h->have_fixed_c ? h->fixed_c.p : nullptr;
-#define GL_RQS(NV, CAP, RB, CIDX)                                                                                    \
-  hipLaunchKernelGGL((k_rd_quad_s<NV, CAP, RB, CIDX>), dim3(cl.grid), dim3(GL_WAVE), lds, h->st, cl.desc, h->n_own,   \
-                     p.cols.p, p.cols16.p, p.win_base.p, (const uint2*)p.cq.p, p.diag_k.p, (const float2*)ad, r, fx,  \
-                     h->opt.dt, partials, cap, GL_XCD_CHUNK)
-#define GL_RQ(NV, CIDX)                                                                                             \
-  do {                                                                                                             \
-    if (cap <= 16) GL_RQS(NV, 16, 28, CIDX);                                                                       \
-    else if (cap <= 20) GL_RQS(NV, 20, 32, CIDX);                                                                  \
-    else if (cap <= 24) GL_RQS(NV, 24, 32, CIDX);                                                                  \
-    else if (cap <= 32) GL_RQS(NV, 32, 32, CIDX);                                                                  \
-    else {                                                                                                         \
-      set_lds(k_rd_quad<NV, 24, CIDX>, lds);                                                                       \
-      hipLaunchKernelGGL((k_rd_quad<NV, 24, CIDX>), dim3(cl.grid), dim3(GL_WAVE), lds, h->st, cl.list, h->n_own,     \
-                         p.slice_ptr.p, p.cols.p, p.cols16.p, p.win_base.p, p.win_ok.p, p.cslice_ptr.p,            \
-                         (const uint2*)p.cq.p, p.diag_k.p, (const float2*)ad, r, fx, h->opt.dt, partials, cap,      \
-                         GL_XCD_CHUNK);                                                                            \
-    }                                                                                                              \
-  } while (0)
   for (const SliceClass* sc : p.classes) {
     const ClassLaunch cl = class_launch(*sc, part);
     if (cl.grid <= 0) continue;
     const int cap = sc->cap;
-    const size_t lds = (size_t)cap * GL_WAVE * sizeof(float2);
-    if (h->nv == 3) {
-      if (h->use_idx16) GL_RQ(3, 1); else GL_RQ(3, 0);
-    } else {
-      if (h->use_idx16) GL_RQ(4, 1); else GL_RQ(4, 0);
-    }
+    const size_t lds = gl_quad_lds(cap);
+    const GlSweepKey k = gl_quad_key(h->nv, cap, h->use_idx16);
+    const bool launched = k.ok && gl_switch(
+        [&](auto NV, auto CAP, auto CIDX) {
+          if constexpr (gl_quad_instance(NV, CAP, CIDX)) {
+            constexpr int RB = gl_quad_records(CAP);
+            if constexpr (CAP == 0) {
+              set_lds(k_rd_quad<NV, RB, CIDX>, lds);
+              hipLaunchKernelGGL((k_rd_quad<NV, RB, CIDX>), dim3(cl.grid), dim3(GL_WAVE), lds, h->st, cl.list, h->n_own,
+                                 p.slice_ptr.p, p.cols.p, p.cols16.p, p.win_base.p, p.win_ok.p, p.cslice_ptr.p,
+                                 (const uint2*)p.cq.p, p.diag_k.p, (const float2*)ad, r, fx, h->opt.dt, partials, cap,
+                                 GL_XCD_CHUNK);
+            } else {
+              hipLaunchKernelGGL((k_rd_quad_s<NV, CAP, RB, CIDX>), dim3(cl.grid), dim3(GL_WAVE), lds, h->st, cl.desc, h->n_own,
+                                 p.cols.p, p.cols16.p, p.win_base.p, (const uint2*)p.cq.p, p.diag_k.p, (const float2*)ad, r,
+                                 fx, h->opt.dt, partials, cap, GL_XCD_CHUNK);
+            }
+            return true;
+          } else {
+            return false;
+          }
+        },
+        k.nv, gl_vals<3, 4>(), k.cap, gl_vals<0, 16, 20, 24, 32>(), k.cidx, gl_bool());
+    GL_REQUIRE(launched, key_text("the quadratic-term pass", k));
   }
-#undef GL_RQ
-#undef GL_RQS
   GL_HIP(hipGetLastError());
 }
 
@@ -2122,44 +2037,25 @@ void gl_launch_spmv(glims_ctx* h, hipStream_t st, int n_launch, const int32_t* s
   const int grid = gl_spmv_grid(n_launch);
   const int chunk = (n_launch + grid - 1) / grid;
   const int remap = slice_list ? 0 : GL_XCD_CHUNK;
-  // ev0 / ev1 (glims_options.time_kernels): start / stop events attached to THIS dispatch (hipExtLaunchKernelGGL) --
-  // the kernel's own timestamps, no extra packets in the queue.  hipEventRecord before and after the launch put a
-  // 5-6 us idle gap on either side of every SpMV (profiles/r02_c3_timeline.txt), 14 % of the step at 1 M rows.
   // Entries in flight per lane (h->spmv_unroll): 8 on lattice meshes, 16 -- a whole typical row -- on general ones, where
   // the x gather misses the caches far more often (1 M-point Delaunay mesh: 58.5 / 52.5 / 48.7 us with 4 / 8 / 16; the
-  // brain-extent box at 10 M rows: 332 / 323 / 323 us isolated, 366 / 356 / 379 inside the time steps).
-  const int unr = h->spmv_unroll;
-#define GL_SPMV5(DOTS, UNR, NT, CIDX, VT, VPTR)                                                                      \
-  do {                                                                                                               \
-    if (ev0 || ev1)                                                                                                  \
-      hipExtLaunchKernelGGL((k_spmv<DOTS, UNR, NT, CIDX, VT>), dim3(grid), dim3(256), 0, st, ev0, ev1, 0, n_launch,   \
-                            chunk, slice_list, h->n_own, p.slice_ptr.p, p.cols.p, p.cols16.p, p.win_base.p,          \
-                            p.win_ok.p, p.diag_k.p, p.rlen.p, VPTR, x, y, fixed, addv, r, partials, partial_off,     \
-                            done, remap);                                                                            \
-    else                                                                                                             \
-      hipLaunchKernelGGL((k_spmv<DOTS, UNR, NT, CIDX, VT>), dim3(grid), dim3(256), 0, st, n_launch, chunk, slice_list, \
-                         h->n_own, p.slice_ptr.p, p.cols.p, p.cols16.p, p.win_base.p, p.win_ok.p, p.diag_k.p,        \
-                         p.rlen.p, VPTR, x, y, fixed, addv, r, partials, partial_off, done, remap);                  \
-  } while (0)
-#define GL_SPMV4(DOTS, UNR, CIDX, VT, VPTR)                                                                          \
-  do {                                                                                                               \
-    if (h->stream_nt) GL_SPMV5(DOTS, UNR, 1, CIDX, VT, VPTR);                                                        \
-    else GL_SPMV5(DOTS, UNR, 0, CIDX, VT, VPTR);                                                                     \
-  } while (0)
-#define GL_SPMV3(DOTS, CIDX)                                                                                         \
-  do {                                                                                                               \
-    if (vals32) GL_SPMV4(DOTS, 8, CIDX, float, vals32);                                                              \
-    else if (unr >= 16) GL_SPMV4(DOTS, 16, CIDX, double, vals);                                                      \
-    else GL_SPMV4(DOTS, 8, CIDX, double, vals);                                                                      \
-  } while (0)
-  if (r) {
-    if (h->use_idx16) GL_SPMV3(1, 1); else GL_SPMV3(1, 0);
-  } else {
-    if (h->use_idx16) GL_SPMV3(0, 1); else GL_SPMV3(0, 0);
-  }
-#undef GL_SPMV3
-#undef GL_SPMV4
-#undef GL_SPMV5
+  // brain-extent box at 10 M rows: 332 / 323 / 323 us isolated, 366 / 356 / 379 inside the time steps).  fp32 values: 8.
+  const int unr = !vals32 && h->spmv_unroll >= 16 ? 16 : 8;
+  gl_switch(
+      [&](auto DOTS, auto UNR, auto NT, auto CIDX, auto F32) {
+        if constexpr (F32 && UNR != 8) {
+          return false;
+        } else {
+          using vt = std::conditional_t<F32 != 0, float, double>;
+          const vt* v = gl_either<F32>(vals, vals32);
+          gl_launch(k_spmv<DOTS, UNR, NT, CIDX, vt>, grid, 256, 0, st, ev0, ev1, n_launch, chunk, slice_list, h->n_own,
+                    p.slice_ptr.p, p.cols.p, p.cols16.p, p.win_base.p, p.win_ok.p, p.diag_k.p, p.rlen.p, v, x, y, fixed, addv,
+                    r, partials, partial_off, done, remap);
+          return true;
+        }
+      },
+      r ? 1 : 0, gl_bool(), unr, gl_vals<8, 16>(), h->stream_nt ? 1 : 0, gl_bool(), h->use_idx16 ? 1 : 0, gl_bool(),
+      vals32 ? 1 : 0, gl_bool());
   GL_HIP(hipGetLastError());
 }
 
@@ -2252,27 +2148,14 @@ void gl_launch_spmm(glims_ctx* h, int P, const double* vals, const double* x, do
   if (n_launch <= 0) return;
   const int grid = gl_spmv_grid(n_launch);
   const int chunk = (n_launch + grid - 1) / grid;
-#define GL_SPMM2(PP, CIDX)                                                                                            \
-  hipLaunchKernelGGL((k_spmm<PP, CIDX, 8>), dim3(grid), dim3(256), 0, h->st, n_launch, chunk, h->n_own, p.slice_ptr.p,  \
-                     p.cols.p, p.cols16.p, p.win_base.p, p.win_ok.p, p.rlen.p, vals, x, y, fixed, partials, GL_XCD_CHUNK)
-#define GL_SPMM1(PP)                     \
-  do {                                   \
-    if (h->use_idx16) GL_SPMM2(PP, 1);   \
-    else GL_SPMM2(PP, 0);                \
-  } while (0)
-  switch (P) {
-    case 1: GL_SPMM1(1); break;
-    case 2: GL_SPMM1(2); break;
-    case 3: GL_SPMM1(3); break;
-    case 4: GL_SPMM1(4); break;
-    case 5: GL_SPMM1(5); break;
-    case 6: GL_SPMM1(6); break;
-    case 7: GL_SPMM1(7); break;
-    case 8: GL_SPMM1(8); break;
-    default: throw glims_error(GLIMS_E_USAGE, "gl_launch_spmm: 1..8 columns");
-  }
-#undef GL_SPMM1
-#undef GL_SPMM2
+  const bool launched = gl_switch(
+      [&](auto PP, auto CIDX) {
+        hipLaunchKernelGGL((k_spmm<PP, CIDX, 8>), dim3(grid), dim3(256), 0, h->st, n_launch, chunk, h->n_own, p.slice_ptr.p,
+                           p.cols.p, p.cols16.p, p.win_base.p, p.win_ok.p, p.rlen.p, vals, x, y, fixed, partials, GL_XCD_CHUNK);
+        return true;
+      },
+      P, gl_vals<1, 2, 3, 4, 5, 6, 7, 8>(), h->use_idx16 ? 1 : 0, gl_bool());
+  if (!launched) throw glims_error(GLIMS_E_USAGE, "gl_launch_spmm: 1..8 columns");
   GL_HIP(hipGetLastError());
 }
 
@@ -2287,35 +2170,21 @@ void gl_launch_cheb(glims_ctx* h, hipStream_t st, int n_launch, const int32_t* s
   const int grid = gl_spmv_grid(n_launch);
   const int chunk = (n_launch + grid - 1) / grid;
   const int remap = slice_list ? 0 : GL_XCD_CHUNK;
-  const int unr = h->spmv_unroll;
-#define GL_CH4(UNR, NT, CIDX, VT, VPTR)                                                                              \
-  do {                                                                                                               \
-    if (ev0 || ev1)                                                                                                  \
-      hipExtLaunchKernelGGL((k_cheb<UNR, NT, CIDX, VT>), dim3(grid), dim3(256), 0, st, ev0, ev1, 0, n_launch, chunk,  \
-                            slice_list, h->n_own, p.slice_ptr.p, p.cols.p, p.cols16.p, p.win_base.p, p.win_ok.p,     \
-                            p.diag_k.p, p.rlen.p, VPTR, y_in, y_out, b, dinv, y_prev, ylast, x, fixed, c1, c2, k,    \
-                            m_host, plan, want_res, pm, remap, shift, nrm);                                          \
-    else                                                                                                             \
-      hipLaunchKernelGGL((k_cheb<UNR, NT, CIDX, VT>), dim3(grid), dim3(256), 0, st, n_launch, chunk, slice_list,      \
-                         h->n_own, p.slice_ptr.p, p.cols.p, p.cols16.p, p.win_base.p, p.win_ok.p, p.diag_k.p,        \
-                         p.rlen.p, VPTR, y_in, y_out, b, dinv, y_prev, ylast, x, fixed, c1, c2, k, m_host, plan,     \
-                         want_res, pm, remap, shift, nrm);                                                           \
-  } while (0)
-#define GL_CH3(UNR, CIDX, VT, VPTR)                                                                                  \
-  do {                                                                                                               \
-    if (h->stream_nt) GL_CH4(UNR, 1, CIDX, VT, VPTR);                                                                \
-    else GL_CH4(UNR, 0, CIDX, VT, VPTR);                                                                             \
-  } while (0)
-#define GL_CH2(CIDX)                                                                                                 \
-  do {                                                                                                               \
-    if (vals32) GL_CH3(8, CIDX, float, vals32);                                                                      \
-    else if (unr >= 16) GL_CH3(16, CIDX, double, vals);                                                              \
-    else GL_CH3(8, CIDX, double, vals);                                                                              \
-  } while (0)
-  if (h->use_idx16) GL_CH2(1); else GL_CH2(0);
-#undef GL_CH2
-#undef GL_CH3
-#undef GL_CH4
+  const int unr = !vals32 && h->spmv_unroll >= 16 ? 16 : 8;
+  gl_switch(
+      [&](auto UNR, auto NT, auto CIDX, auto F32) {
+        if constexpr (F32 && UNR != 8) {
+          return false;
+        } else {
+          using vt = std::conditional_t<F32 != 0, float, double>;
+          const vt* v = gl_either<F32>(vals, vals32);
+          gl_launch(k_cheb<UNR, NT, CIDX, vt>, grid, 256, 0, st, ev0, ev1, n_launch, chunk, slice_list, h->n_own, p.slice_ptr.p,
+                    p.cols.p, p.cols16.p, p.win_base.p, p.win_ok.p, p.diag_k.p, p.rlen.p, v, y_in, y_out, b, dinv, y_prev, ylast,
+                    x, fixed, c1, c2, k, m_host, plan, want_res, pm, remap, shift, nrm);
+          return true;
+        }
+      },
+      unr, gl_vals<8, 16>(), h->stream_nt ? 1 : 0, gl_bool(), h->use_idx16 ? 1 : 0, gl_bool(), vals32 ? 1 : 0, gl_bool());
   GL_HIP(hipGetLastError());
 }
 
@@ -2327,23 +2196,15 @@ void gl_launch_spmv_block(glims_ctx* h, hipStream_t st, int n_launch, const int3
   const int grid = gl_spmv_grid(n_launch);
   const int chunk = (n_launch + grid - 1) / grid;
   const int remap = slice_list ? 0 : GL_XCD_CHUNK;
-#define GL_BLK(BS, DOTS)                                                                                         \
-  do {                                                                                                           \
-    if (single_precision_operator)                                                                               \
-      hipLaunchKernelGGL((k_spmv_block2<BS, DOTS, 2, float>), dim3(grid), dim3(256), 0, st, n_launch, chunk,      \
-                         slice_list, h->n_own, p.slice_ptr.p, p.cols.p, h->vKel32.p, x, y, fixed, r, partials,    \
-                         partial_off, done, remap);                                                          \
-    else                                                                                                         \
-      hipLaunchKernelGGL((k_spmv_block2<BS, DOTS, 2, double>), dim3(grid), dim3(256), 0, st, n_launch, chunk,     \
-                         slice_list, h->n_own, p.slice_ptr.p, p.cols.p, h->vKel.p, x, y, fixed, r, partials,      \
-                         partial_off, done, remap);                                                          \
-  } while (0)
-  if (h->dim == 2) {
-    if (r) GL_BLK(2, 1); else GL_BLK(2, 0);
-  } else {
-    if (r) GL_BLK(3, 1); else GL_BLK(3, 0);
-  }
-#undef GL_BLK
+  gl_switch(
+      [&](auto BS, auto DOTS, auto F32) {
+        using vt = std::conditional_t<F32 != 0, float, double>;
+        hipLaunchKernelGGL((k_spmv_block2<BS, DOTS, 2, vt>), dim3(grid), dim3(256), 0, st, n_launch, chunk, slice_list, h->n_own,
+                           p.slice_ptr.p, p.cols.p, gl_either<F32>(h->vKel.p, h->vKel32.p), x, y, fixed, r, partials, partial_off,
+                           done, remap);
+        return true;
+      },
+      h->dim == 2 ? 2 : 3, gl_vals<2, 3>(), r ? 1 : 0, gl_bool(), single_precision_operator ? 1 : 0, gl_bool());
   GL_HIP(hipGetLastError());
 }
 
@@ -2404,40 +2265,23 @@ void gl_launch_mg_fine(glims_ctx* h, MgHierarchy& mg, int mode, const double* xi
   const bool half = mg.half_smoother;
   const bool c16 = h->use_idx16 && h->stats.nnz_idx16 == h->stats.nnz_padded;   // every slice has 16-bit codes
   const bool x32 = mg.x32 && mode != 2;   // the power iteration of the set-up (mode 2) works on double vectors
-  // entries in flight per lane: 2 blocks of 3 x 3 (2 x 2), or 8 scalars (an interior row of a tetrahedral mesh has 15)
-#define GL_MGF4(BS, KB, MODE, VT, VPTR, CIDX, XT)                                                                    \
-  hipLaunchKernelGGL((k_mg_fine<BS, MODE, KB, VT, CIDX, XT>), dim3(grid), dim3(256), 0, h->st, n_launch, slist, pv0,  \
-                     chunk, h->n_own, p.slice_ptr.p, p.cols.p, p.cols16.p, p.win_base.p, VPTR, mg.dinv0.p, mg.sc.p,         \
-                     fx, (const XT*)xin, (const XT*)r, (XT*)d, (XT*)xout, uout, c1, c2, GL_XCD_CHUNK, done, r_full, pv)
-#define GL_MGF3(BS, KB, MODE, VT, VPTR, CIDX)                                                                        \
-  do {                                                                                                               \
-    if (MODE != 2 && x32) GL_MGF4(BS, KB, MODE, VT, VPTR, CIDX, float);                                              \
-    else GL_MGF4(BS, KB, MODE, VT, VPTR, CIDX, double);                                                              \
-  } while (0)
-#define GL_MGF2(BS, KB, MODE, CIDX)                                                                                  \
-  do {                                                                                                               \
-    if (half) GL_MGF3(BS, KB, MODE, _Float16, (const _Float16*)mg.v16.p, CIDX);                                      \
-    else GL_MGF3(BS, KB, MODE, float, mg.vK32s.p, CIDX);                                                             \
-  } while (0)
-#define GL_MGF(BS, KB, MODE)                                                                                         \
-  do {                                                                                                               \
-    if (c16) GL_MGF2(BS, KB, MODE, 1); else GL_MGF2(BS, KB, MODE, 0);                                                \
-  } while (0)
-#define GL_MGFM(BS, KB)                                                                                              \
-  do {                                                                                                               \
-    if (mode == 0) GL_MGF(BS, KB, 0); else if (mode == 1) GL_MGF(BS, KB, 1); else GL_MGF(BS, KB, 2);                 \
-  } while (0)
   const bool timed = &mg == &h->mg && mode != 2 && part == 0 && h->timing(glims_ctx::TK_MGFINE);
   if (timed) h->tick(glims_ctx::TK_MGFINE);
-  if (mg.bs == 1) GL_MGFM(1, 8);
-  else if (mg.bs == 2) GL_MGFM(2, 2);
-  else GL_MGFM(3, 2);
+  const bool launched = gl_switch(
+      [&](auto BS, auto MODE, auto HALF, auto CIDX, auto X32) {
+        // entries in flight per lane: 2 blocks of 3 x 3 (2 x 2), or 8 scalars (an interior row of a tetrahedral mesh has 15)
+        constexpr int KB = BS == 1 ? 8 : 2;
+        using vt = std::conditional_t<HALF != 0, _Float16, float>;
+        using xt = std::conditional_t<X32 != 0, float, double>;
+        hipLaunchKernelGGL((k_mg_fine<BS, MODE, KB, vt, CIDX, xt>), dim3(grid), dim3(256), 0, h->st, n_launch, slist, pv0, chunk,
+                           h->n_own, p.slice_ptr.p, p.cols.p, p.cols16.p, p.win_base.p,
+                           gl_either<HALF>(mg.vK32s.p, (const _Float16*)mg.v16.p), mg.dinv0.p, mg.sc.p, fx, (const xt*)xin,
+                           (const xt*)r, (xt*)d, (xt*)xout, uout, c1, c2, GL_XCD_CHUNK, done, r_full, pv);
+        return true;
+      },
+      mg.bs, gl_vals<1, 2, 3>(), mode, gl_vals<0, 1, 2>(), half ? 1 : 0, gl_bool(), c16 ? 1 : 0, gl_bool(), x32 ? 1 : 0, gl_bool());
+  GL_REQUIRE(launched, "gl_launch_mg_fine: block size 1..3, mode 0..2");
   if (timed) h->tick(glims_ctx::TK_MGFINE);
-#undef GL_MGFM
-#undef GL_MGF
-#undef GL_MGF2
-#undef GL_MGF3
-#undef GL_MGF4
   GL_HIP(hipGetLastError());
 }
 
@@ -2453,28 +2297,32 @@ void gl_make_smoother_copy(glims_ctx* h, MgHierarchy& mg, bool half, bool exchan
   mg.dinv0.alloc((size_t)h->n_own * bs * bs);
   const uint8_t* fx = mg.op_fixed;
   const unsigned g = (unsigned)((n_pad + 255) / 256);
-#define GL_SCALING(BS)                                                                                               \
-  hipLaunchKernelGGL(k_mg_scaling<BS>, dim3(g), dim3(256), 0, h->st, h->n_own, n_pad, p.slice_ptr.p, p.diag_k.p,       \
-                     mg.op_vals, fx, mg.op_dinv, mg.sc.p, mg.dinv0.p)
-  if (bs == 1) GL_SCALING(1); else if (bs == 2) GL_SCALING(2); else GL_SCALING(3);
-#undef GL_SCALING
+  const bool scaled = gl_switch(
+      [&](auto BS) {
+        hipLaunchKernelGGL(k_mg_scaling<BS>, dim3(g), dim3(256), 0, h->st, h->n_own, n_pad, p.slice_ptr.p, p.diag_k.p, mg.op_vals,
+                           fx, mg.op_dinv, mg.sc.p, mg.dinv0.p);
+        return true;
+      },
+      bs, gl_vals<1, 2, 3>());
+  GL_REQUIRE(scaled, "gl_make_smoother_copy: block size 1..3");
   GL_HIP(hipGetLastError());
   if (exchange_scale) gl_halo_exchange(h, mg.sc.p, bs);
   const size_t nk = (size_t)p.total_entries * bs * bs;
-#define GL_COPY(BS, OT, OUT)                                                                                         \
-  hipLaunchKernelGGL((k_scaled_copy<BS, OT>), dim3(p.n_slices), dim3(GL_WAVE), 0, h->st, p.n_slices, p.slice_ptr.p,   \
-                     p.cols.p, mg.op_vals, mg.sc.p, OUT)
   if (half) {
     mg.v16.alloc(nk);
     mg.vK32s.release();
-    _Float16* out = (_Float16*)mg.v16.p;
-    if (bs == 1) GL_COPY(1, _Float16, out); else if (bs == 2) GL_COPY(2, _Float16, out); else GL_COPY(3, _Float16, out);
   } else {
     mg.vK32s.alloc(nk);
     mg.v16.release();
-    if (bs == 1) GL_COPY(1, float, mg.vK32s.p); else if (bs == 2) GL_COPY(2, float, mg.vK32s.p); else GL_COPY(3, float, mg.vK32s.p);
   }
-#undef GL_COPY
+  gl_switch(
+      [&](auto BS, auto HALF) {
+        using ot = std::conditional_t<HALF != 0, _Float16, float>;
+        hipLaunchKernelGGL((k_scaled_copy<BS, ot>), dim3(p.n_slices), dim3(GL_WAVE), 0, h->st, p.n_slices, p.slice_ptr.p, p.cols.p,
+                           mg.op_vals, mg.sc.p, gl_either<HALF>(mg.vK32s.p, (_Float16*)mg.v16.p));
+        return true;
+      },
+      bs, gl_vals<1, 2, 3>(), half ? 1 : 0, gl_bool());
   GL_HIP(hipGetLastError());
 }
 
@@ -2486,15 +2334,14 @@ void gl_rd_matfree(glims_ctx* h, const double* c, const double* x, double* y) {
     if (sc->n <= 0) continue;
     const int cap = sc->cap;
     const size_t lds = (size_t)3 * cap * GL_WAVE * sizeof(double);
-    if (h->nv == 3) {
-      set_lds(k_rd_matfree<3>, lds);
-      hipLaunchKernelGGL(k_rd_matfree<3>, dim3(sc->n), dim3(GL_WAVE), lds, h->st, sc->list.p, h->n_own, p.slice_ptr.p,
-                         p.cols.p, p.cslice_ptr.p, p.cs2.p, p.cw.p, p.diag_k.p, h->vS.p, c, x, y, 2.0 * h->opt.dt, cap);
-    } else {
-      set_lds(k_rd_matfree<4>, lds);
-      hipLaunchKernelGGL(k_rd_matfree<4>, dim3(sc->n), dim3(GL_WAVE), lds, h->st, sc->list.p, h->n_own, p.slice_ptr.p,
-                         p.cols.p, p.cslice_ptr.p, p.cs2.p, p.cw.p, p.diag_k.p, h->vS.p, c, x, y, 2.0 * h->opt.dt, cap);
-    }
+    gl_switch(
+        [&](auto NV) {
+          set_lds(k_rd_matfree<NV>, lds);
+          hipLaunchKernelGGL(k_rd_matfree<NV>, dim3(sc->n), dim3(GL_WAVE), lds, h->st, sc->list.p, h->n_own, p.slice_ptr.p,
+                             p.cols.p, p.cslice_ptr.p, p.cs2.p, p.cw.p, p.diag_k.p, h->vS.p, c, x, y, 2.0 * h->opt.dt, cap);
+          return true;
+        },
+        h->nv == 3 ? 3 : 4, gl_vals<3, 4>());
   }
   GL_HIP(hipGetLastError());
 }
