@@ -36,6 +36,12 @@ RD_PRECOND_AUTO, RD_PRECOND_JACOBI, RD_PRECOND_MULTIGRID = 0, 1, 2
 RD_LINEAR_AUTO, RD_LINEAR_PCG, RD_LINEAR_CHEBYSHEV = 0, 1, 2
 STREAM_AUTO, STREAM_NONTEMPORAL, STREAM_CACHED = 0, 1, 2
 FIELD_C, FIELD_U, FIELD_SNAPSHOT_C, FIELD_HOST = 0, 1, 2, 3
+FIELD_DERIVED = 4       # the result of the last glims_derive, sampled from its device buffer
+DERIVE_CURRENT, DERIVE_HOST = -1, -2
+# glims_derive kinds by name (GLIMS_DERIVE_*); the first two are tensors
+DERIVE_KINDS = {"strain_tensor": 0, "stress_tensor": 1, "pressure": 2, "van_mises_stress": 3, "displacement_norm": 4,
+                "log_growth": 5, "mech_expansion": 6, "total_jacobian": 7, "growth_induced_jacobian": 8,
+                "concentration_deformed_config": 9}
 SAMPLE_EPS = 1e-10      # GLIMS_SAMPLE_EPS: a cell accepts a point iff min lambda >= -SAMPLE_EPS
 SAMPLE_MAX_COMP = 8
 ABI_VERSION = 6
@@ -149,6 +155,8 @@ SIGNATURES = {
     "glims_snapshot_mechanics": (C.c_int, [_h, C.c_int64, _dp]),
     "glims_snapshot_clear": (C.c_int, [_h]),
     "glims_project": (C.c_int, [_h, _dp, _dp, C.c_int, C.c_double]),
+    "glims_derive": (C.c_int, [_h, C.c_int, C.c_int64, _dp, _dp, C.c_double, _dp]),
+    "glims_derive_info": (C.c_int, [_h, _i64p]),
     "glims_adjoint_record": (C.c_int, [_h, C.c_int]),
     "glims_adjoint_gradient": (C.c_int, [_h, C.c_int, C.POINTER(Misfit), _dp, _dp, _dp, _dp, _dp]),
     "glims_adjoint_gradient_full": (C.c_int, [_h, C.c_int, C.POINTER(Misfit), _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
@@ -294,6 +302,7 @@ class Handle:
 
     def setup(self, with_mechanics=True):
         self._check(self.lib.glims_setup(self._h, 1 if with_mechanics else 0))
+        self.with_mechanics = bool(with_mechanics)   # (derive: the kinds that need u are refused without it)
 
     # -- state -----------------------------------------------------------------------------------
     def set_state(self, c, u=None):
@@ -391,6 +400,43 @@ class Handle:
         x = np.empty_like(r)
         self._check(self.lib.glims_project(self._h, _ptr(r, _dp), _ptr(x, _dp), int(k), float(rtol)))
         return x.reshape(rhs.shape)
+
+    # -- derived fields (glims_derive) -----------------------------------------------------------------
+    def derive(self, kind, snapshot=None, c=None, u=None, rtol=1e-12, fetch=True):
+        """One derived field of a step, computed on the device (glims_derive).  ``kind``: a name of DERIVE_KINDS or its
+        number.  Source: ``snapshot`` (an id of snapshot_save; the displacement is solved on the device where the kind needs
+        it), host arrays ``c`` [n_nodes] / ``u`` [n_nodes, dim] in the caller's node order (either may be None where the kind
+        needs none), or neither: the handle's current c and U as they stand.  Returns the nodal field ([n_nodes], tensors
+        [n_nodes, dim, dim]); with fetch=False nothing is copied back and None is returned -- the result stays on the device
+        for ``Sampler.apply('derived')``.  ``last_derive_status`` holds the call's status: GLIMS_NOT_CONVERGED (a solve stopped
+        at its iteration cap: the field comes from what it reached, as solve_mechanics / snapshot_mechanics hand back their
+        displacement) does not raise, GLIMS_NAN and the refusals do."""
+        k = DERIVE_KINDS[kind] if isinstance(kind, str) else int(kind)
+        if snapshot is not None and (c is not None or u is not None):
+            raise ValueError("derive: give a snapshot or host arrays, not both")
+        if snapshot is not None:
+            src = int(snapshot)
+        elif c is not None or u is not None:
+            src = DERIVE_HOST
+            c = None if c is None else _f64(c, (self.n_nodes,))
+            u = None if u is None else _f64(np.asarray(u, dtype=np.float64).reshape(-1), (self.n_nodes * self.dim,))
+        else:
+            src = DERIVE_CURRENT
+        out = None
+        if fetch:
+            out = np.empty((self.n_nodes, self.dim, self.dim) if k in (0, 1) else (self.n_nodes,))
+        st = self.lib.glims_derive(self._h, k, src, _ptr(c, _dp), _ptr(u, _dp), float(rtol), _ptr(out, _dp))
+        if st >= 0:   # (a refused call changes nothing: the earlier result stays where it was)
+            self._derived_ncomp = self.dim * (self.dim + 1) // 2 if k in (0, 1) else 1
+        self.last_derive_status = st
+        self._check(st, allow=(GLIMS_NOT_CONVERGED,))
+        return out
+
+    def derive_info(self):
+        """Cumulative counters of derive(): cell passes, mass solves, elastic solves, hits of the projected-stress cache."""
+        a = np.zeros(4, dtype=np.int64)
+        self._check(self.lib.glims_derive_info(self._h, _ptr(a, _i64p)))
+        return dict(zip(("cell_passes", "mass_solves", "elastic_solves", "cache_hits"), (int(v) for v in a)))
 
     # -- discrete adjoint (glims_adjoint_*) -----------------------------------------------------------
     def adjoint_record(self, on=True):
@@ -653,8 +699,10 @@ class Sampler:
 
     def apply(self, field, snapshot=None, fill=np.nan):
         """P f at every point: ``field`` = 'c' (current concentration, or the device snapshot ``snapshot``), 'u' (current
-        displacement) or a nodal array [n_nodes] / [n_nodes, k] in the caller's node order.  Returns [n_points] for a
-        one-dimensional field, [n_points, k] otherwise; points outside the mesh hold ``fill``."""
+        displacement), 'derived' (the result of the handle's last ``derive``, from its device buffer: [n_points] for a scalar,
+        [n_points, d(d+1)/2] symmetric components xx, yy, (zz,) xy, (xz, yz) for a tensor) or a nodal array [n_nodes] /
+        [n_nodes, k] in the caller's node order.  Returns [n_points] for a one-dimensional field, [n_points, k] otherwise;
+        points outside the mesh hold ``fill``."""
         h = self.handle
         nodal, flat = None, False
         if isinstance(field, str):
@@ -664,8 +712,13 @@ class Sampler:
                 if snapshot is not None:
                     raise ValueError("snapshots hold the concentration only")
                 kind, ncomp = FIELD_U, h.dim
+            elif field == 'derived':
+                if snapshot is not None:
+                    raise ValueError("'derived' is the last derive()'s result; it takes no snapshot")
+                ncomp = getattr(h, "_derived_ncomp", 1)
+                kind, flat = FIELD_DERIVED, ncomp == 1
             else:
-                raise ValueError("field must be 'c', 'u' or a nodal array")
+                raise ValueError("field must be 'c', 'u', 'derived' or a nodal array")
         else:
             a = np.asarray(field, dtype=np.float64)
             if a.shape[0] != h.n_nodes:

@@ -86,6 +86,8 @@ int guarded(glims_ctx* h, F&& f) {
 
 }  // namespace
 
+void gl_to_device_perm(glims_ctx* h, const double* host, double* dst, int bs) { to_device_perm(h, host, dst, bs); }
+
 extern "C" {
 
 int glims_abi_version(void) { return GLIMS_ABI_VERSION; }
@@ -327,6 +329,7 @@ int glims_set_materials(glims_ctx* h, int n_labels, const double* D, const doubl
     h->mh_count = h->mh_next = 0;   // the elasticity solve history belongs to one operator
     h->mg.ready = h->mg_rd.ready = false;
     h->rd_precond_active = 0;
+    h->derive.forget_u();           // ... and so does the displacement a derive solved (and the projected stress)
     GL_REQUIRE(n_labels > 0 && n_labels <= GL_MAX_LABELS, "n_labels out of range");
     GL_REQUIRE(D && rho && gamma && E && nu, "null material table");
     std::vector<double> m(5 * GL_MAX_LABELS, 0.0);
@@ -439,6 +442,7 @@ int glims_set_dirichlet_u(glims_ctx* h, int64_t n, const int64_t* dof_ids, const
   return guarded(h, [&]() {
     h->mh_count = h->mh_next = 0;   // the elasticity solve history belongs to one operator
     h->mg.ready = false;            // ... and so does the multigrid hierarchy (constrained dofs are eliminated in it)
+    h->derive.forget_u();
     if (n <= 0) {
       h->have_fixed_u = false;
       return GLIMS_OK;
@@ -479,6 +483,7 @@ int glims_set_rd_load(glims_ctx* h, const double* f) {
 
 int glims_set_mech_load(glims_ctx* h, const double* f) {
   return guarded(h, [&]() {
+    h->derive.forget_u();
     if (!f) {
       h->have_mload = false;
       return GLIMS_OK;
@@ -495,6 +500,7 @@ int glims_setup(glims_ctx* h, int with_mechanics) {
     h->mh_count = h->mh_next = 0;   // the elasticity solve history belongs to one operator
     h->mg.ready = h->mg_rd.ready = false;
     h->rd_precond_active = 0;       // decided by the first glims_step (a collective in partitioned runs)
+    h->derive.forget_u();
     h->stats.rd_precond_used = 0;
     for (int& hint : h->run.cg_hint) hint = 0;
     h->mech_hint = 0;
@@ -545,6 +551,7 @@ int glims_set_state(glims_ctx* h, const double* c, const double* u) {
   return guarded(h, [&]() {
     GL_REQUIRE(c, "null concentration");
     h->prepared.drop();
+    h->derive.forget_u();
     // A new state starts a new run (FenicsSimulation.run() may be called again on the same object, simulation_base.py:166-168,
     // run_for_adjoint does): what the Newton iteration has learnt from the previous run's steps is forgotten -- the forcing mode,
     // the guesses and their back-off, the iteration counts, the spectral interval of the dot-free solves (measured again by the
@@ -585,11 +592,17 @@ int glims_get_state(glims_ctx* h, double* c, double* u) {
 }
 
 int glims_step(glims_ctx* h, int n_steps) {
-  return guarded(h, [&]() { return gl_step(h, n_steps); });
+  return guarded(h, [&]() {
+    h->derive.forget_u();
+    return gl_step(h, n_steps);
+  });
 }
 
 int glims_solve_mechanics(glims_ctx* h) {
-  return guarded(h, [&]() { return gl_solve_mechanics(h); });
+  return guarded(h, [&]() {
+    h->derive.forget_u();
+    return gl_solve_mechanics(h);
+  });
 }
 
 int glims_get_stats(const glims_ctx* h, glims_stats* st) {
@@ -808,7 +821,9 @@ int glims_snapshot_load(glims_ctx* h, int64_t id, double* c) {
 int glims_snapshot_mechanics(glims_ctx* h, int64_t id, double* u) {
   return guarded(h, [&]() {
     GL_REQUIRE(u && id >= 0 && id < (int64_t)h->snapshots.size() && h->snapshots[id], "unknown snapshot id");
+    h->derive.forget_u();
     const int st = gl_solve_mechanics(h, h->snapshots[id]->p);
+    if (st == GLIMS_OK) h->derive.u_snapshot = id;   // glims_derive of this snapshot does not solve again
     from_device_perm(h, h->U.p, u, h->dim, h->n_nodes);
     return st;
   });
@@ -818,6 +833,7 @@ int glims_snapshot_clear(glims_ctx* h) {
   return guarded(h, [&]() {
     for (auto* d : h->snapshots) delete d;
     h->snapshots.clear();
+    h->derive.forget_u();   // ids start again at 0
     return GLIMS_OK;
   });
 }
@@ -984,6 +1000,21 @@ int glims_project(glims_ctx* h, const double* rhs, double* x, int ncomp, double 
     }
     return status;
   });
+}
+
+int glims_derive(glims_ctx* h, int kind, int64_t snapshot, const double* c_host, const double* u_host, double rtol,
+                 double* out) {
+  return guarded(h, [&]() { return gl_derive(h, kind, snapshot, c_host, u_host, rtol, out); });
+}
+
+int glims_derive_info(const glims_ctx* h, int64_t out[4]) {
+  if (!h || !out) return GLIMS_E_USAGE;
+  const DeriveState& d = h->derive;
+  out[0] = d.n_cell_passes;
+  out[1] = d.n_mass_solves;
+  out[2] = d.n_elastic_solves;
+  out[3] = d.n_cache_hits;
+  return GLIMS_OK;
 }
 
 int glims_comm_unique_id(char id[GLIMS_UNIQUE_ID_BYTES]) {

@@ -486,6 +486,33 @@ struct GlImageTerm {
   dvec<double> target, pweight;             // [n]; pweight empty = 1
 };
 
+// Derived fields of a recorded step (derive.hip, glims_derive): the last result, the scratch of the two passes, the one-entry
+// cache of the projected stress, and which snapshot's displacement the handle's U holds
+struct DeriveState {
+  dvec<double> res;                        // last result, planes [ncomp][n_nodes], internal numbering (tensors: symmetric components)
+  dvec<double> res_il;                     // ... interleaved [n_nodes][ncomp] for the samplers (ncomp > 1; filled on first use)
+  bool res_il_valid = false;
+  int ncomp = 0;                           // ncomp = 0: nothing derived yet
+  dvec<double> cellv;                      // cell pass output, planes [ncomp | nv][n_cells]
+  dvec<double> rhs;                        // gathered right-hand sides, planes [ncomp][n_nodes]
+  dvec<double> sc, su;                     // GLIMS_DERIVE_HOST: c [n_nodes] and u [n_nodes][dim], internal numbering
+  dvec<double> p1;                         // first-stage P1 field of the growth-induced Jacobian [n_nodes]
+  dvec<double> out_stage;                  // the caller's [n_nodes][ncomp | d*d] before the copy to the host
+  dvec<double> stress;                     // cached projected stress, planes [d(d+1)/2][n_nodes]
+  bool stress_valid = false;
+  int64_t stress_src = 0;                  // ... of this source (snapshot id or GLIMS_DERIVE_CURRENT)
+  uint64_t stress_gen = 0;                 // ... and this displacement generation
+  double stress_rtol = 0.0;                // ... solved to this tolerance (reused by calls that ask for no tighter one)
+  uint64_t u_gen = 1;                      // advances whenever U, the materials or the elastic operator may have changed
+  int64_t u_snapshot = -1;                 // snapshot whose displacement U holds, -1 = none
+  std::vector<uint8_t> label_used;         // [GL_MAX_LABELS] 1 = some cell carries the label (empty: not yet read)
+  int64_t n_cell_passes = 0, n_mass_solves = 0, n_elastic_solves = 0, n_cache_hits = 0;   // glims_derive_info
+  void forget_u() {
+    u_snapshot = -1;
+    ++u_gen;
+  }
+};
+
 struct glims_ctx {
   int dim = 0, nv = 0, device = 0;
   int n_labels = 0;                        // of the last glims_set_materials
@@ -641,6 +668,7 @@ struct glims_ctx {
   AdjointState adj;
   std::vector<GlSampler*> samplers;         // owned (sample.hip); a destroyed sampler leaves a nullptr so that ids stay valid
   std::vector<GlImageTerm*> img_terms;      // owned (sample.hip): the stored image-space misfit terms of the adjoint calls
+  DeriveState derive;
 
   std::string err;
 };
@@ -760,6 +788,13 @@ double gl_image_misfit_grad(glims_ctx* h, const GlImageTerm& t, const double* c,
 // dg[j * ld + row] += (P^T r2_j)[row] for the P directions dc[j * ld + .]
 void gl_image_misfit_second(glims_ctx* h, const GlImageTerm& t, const double* c, const double* dc, int P, int64_t ld,
                             double* dg);
+
+// api.hip: caller's node order -> internal, through h->stage (synchronises h->st)
+void gl_to_device_perm(glims_ctx* h, const double* host, double* dst, int bs);
+// derive.hip ----------------------------------------------------------------------------------------
+int gl_derive(glims_ctx* h, int kind, int64_t snapshot, const double* c_host, const double* u_host, double rtol, double* out);
+// the last result as the samplers read a nodal field ([n_nodes][ncomp], internal numbering); refuses when there is none
+const double* gl_derive_sampled(glims_ctx* h, int ncomp);
 
 // mg.hip --------------------------------------------------------------------------------------------
 void gl_mesh_metrics(glims_ctx* h, const HostPattern& hp, const double* xyz_old);

@@ -1056,6 +1056,9 @@ void gl_sampler_apply(glims_ctx* h, int64_t id, int field, int64_t snapshot, con
       f = s.f_int.p;
       break;
     }
+    case GLIMS_FIELD_DERIVED:
+      f = gl_derive_sampled(h, ncomp);
+      break;
     default:
       GL_REQUIRE(false, "glims_sampler_apply: unknown field " + std::to_string(field));
   }

@@ -339,9 +339,15 @@ class TumorGrowth(FenicsSimulation):
             cache[1][key] = (term, image, mask)   # (image and mask stay alive: their identity is the key)
         return cache[1][key][0]
 
+    DERIVED_IMAGES = ('pressure', 'van_mises_stress', 'total_jacobian', 'growth_induced_jacobian',
+                      'concentration_deformed_config', 'log_growth', 'displacement_norm', 'strain_tensor', 'stress_tensor')
+
     def sample_image(self, subspace_name, recording_step, like=None, origin=None, spacing=None, size=None, fill=np.nan):
         """
-        The recorded field `subspace_name` ('concentration' | 'displacement') of `recording_step` evaluated on a voxel grid
+        The recorded field `subspace_name` ('concentration' | 'displacement') of `recording_step`, or one of its derived
+        fields (DERIVED_IMAGES: the PostProcess fields; tensors as their symmetric components xx, yy, (zz,) xy, (xz, yz) in
+        the last axis; a step recorded on the device is derived and sampled there, nothing nodal crosses to the host),
+        evaluated on a voxel grid
         -> utils.data_io.Image (array [z,] y, x [, component]; voxels outside the mesh hold `fill`).  The grid is that of
         the Image `like`, or origin / spacing / size (points per axis).  What the reference does voxel by voxel with
         create_image_from_fenics_function (data_io.py:176-225), here one gather on the device: the grid is located in the
@@ -358,6 +364,13 @@ class TumorGrowth(FenicsSimulation):
         if h is None:
             raise RuntimeError("sample_image needs a run() first")
         key, sampler = self._grid_sampler(origin, spacing, size)
+        if subspace_name in self.DERIVED_IMAGES:
+            if self.results.get_result(recording_step) is None:
+                raise KeyError("no result for recording step %r" % (recording_step,))
+            pp = getattr(self, '_image_postprocess', None)
+            if pp is None or pp._backend is not h or pp._results is not self.results:
+                pp = self._image_postprocess = self._make_postprocess(None, None)
+            return _grid_image(pp.sample(subspace_name, recording_step, sampler, fill), key[2], key[0], key[1])
         sid = self.functionspace.get_subspace_id(subspace_name)
         obs = self.results.get_result(recording_step)
         if obs is None:
@@ -437,15 +450,20 @@ class TumorGrowth(FenicsSimulation):
         self.run(keep_nth=1, save_method=None, clear_all=False, plot=False, output_dir=output_dir)
         return self.solution
 
-    def init_postprocess(self, output_dir=config.output_dir_simulation_tmp):
-        """:172-173 -- derived fields (stress, pressure, Jacobians ...) of the recorded solutions"""
+    def _make_postprocess(self, output_dir, device):
         from ..simulation_helpers.postprocess import PostProcessTumorGrowth
         if self._backend is None:
             raise RuntimeError("init_postprocess needs a finished run() (the L2 projections run on its device backend)")
         labels = self._labels()
         t = self._material_tables(int(labels.max()) + 1)
-        self.postprocess = PostProcessTumorGrowth(self.results, self.params, output_dir=output_dir,
-                                                  backend=self._backend, tables=t, labels=labels)
+        return PostProcessTumorGrowth(self.results, self.params, output_dir=output_dir, backend=self._backend, tables=t,
+                                      labels=labels, device=device)
+
+    def init_postprocess(self, output_dir=config.output_dir_simulation_tmp, device=None):
+        """:172-173 -- derived fields (stress, pressure, Jacobians ...) of the recorded solutions.  ``device`` (extension):
+        None computes the steps that were recorded on the device (run(results_on_device=True), one GPU) there and the others
+        in numpy; True sends host-resident results to the device as well; False keeps numpy throughout."""
+        self.postprocess = self._make_postprocess(output_dir, device)
         return self.postprocess
 
     def solver_statistics(self):

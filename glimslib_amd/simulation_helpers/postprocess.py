@@ -7,6 +7,11 @@ Every field of the reference is ``fenics.project(<UFL expression>, P1 space)``, 
 ``M p = int expr * phi_i dx``.  Here the right-hand side is integrated with numpy (cell-wise constants exactly,
 polynomial / nonlinear integrands with a degree-7 conical-product Gauss rule) and the mass solve runs on the device
 (``glims_project``).  Tensor fields are returned as Functions with values of shape [N, d, d].
+
+Where the recorded step lives on the device (``run(results_on_device=True)`` on one GPU) every field is computed there instead
+(``Handle.derive``, csrc/derive.hip: the same integrands, rule and two-stage structure): nothing but the
+result crosses to the host.  ``device=True`` sends host-resident results the same way, ``device=False`` keeps numpy; the numpy
+methods below remain the statement of what the device computes.
 """
 from __future__ import annotations
 
@@ -52,8 +57,10 @@ def simplex_quadrature(d, n=4):
 class PostProcess:
     """helper_classes.py:1521-1732 (numeric part)."""
 
-    def __init__(self, results, params, output_dir=None, plot_params=None, backend=None, tables=None, labels=None):
+    def __init__(self, results, params, output_dir=None, plot_params=None, backend=None, tables=None, labels=None,
+                 device=None):
         self.logger = logging.getLogger(__name__)
+        self._device = device                                     # None: device snapshots only; True: always; False: never
         self._results = results
         self._params = params
         self._functionspace = results._functionspace
@@ -103,6 +110,71 @@ class PostProcess:
         u = self.get_solution_displacement(recording_step).values()            # [N, d]
         return np.einsum('mad,mab->mbd', self._grad, u[self._mesh.cells])      # [M, b, d] = d u_b / d x_d
 
+    # -- device path ------------------------------------------------------------------------------------------------
+    _NEEDS_U = ('strain_tensor', 'stress_tensor', 'pressure', 'van_mises_stress', 'displacement_norm', 'total_jacobian',
+                'concentration_deformed_config')
+    _NEEDS_C = ('log_growth', 'mech_expansion', 'growth_induced_jacobian', 'concentration_deformed_config')
+
+    def _derive(self, kind, recording_step=None, fetch=True):
+        """(True, nodal array or None) when the field was computed by ``Handle.derive``, (False, None) when numpy is to do it:
+        always for ``device=False`` and on partitioned backends, for host-resident results unless ``device=True``, and for the
+        kinds that read u on a run without mechanics (on_device)."""
+        from .. import _backend
+        h = self._backend
+        if not self.on_device(recording_step, kind):
+            return False, None
+        if recording_step is None:
+            recording_step = self._results.get_recording_steps()[-1]
+        field = self._results.get_result(recording_step).get_field()
+        sid = getattr(field, 'snapshot_id', None)
+        if sid is not None:                                       # a device snapshot: immutable, nothing on the host to lose
+            solves = h.derive_info()['elastic_solves']
+            try:
+                out = h.derive(kind, snapshot=sid, fetch=fetch)
+            finally:
+                if h.derive_info()['elastic_solves'] != solves:   # the device's displacement buffer now belongs to this step
+                    field.components._solver._mech_current = False
+        else:
+            c = np.asarray(field.components[1]) if kind in self._NEEDS_C else None
+            u = np.asarray(field.components[0]) if kind in self._NEEDS_U else None
+            out = h.derive(kind, c=c, u=u, fetch=fetch)
+        if h.last_derive_status != _backend.GLIMS_OK:             # as the lazy displacement of the numpy path: warn and go on
+            self.logger.warning("    - %s: a solve did not converge (status %d)" % (kind, h.last_derive_status))
+        return True, out
+
+    def on_device(self, recording_step=None, kind=None):
+        """Does ``recording_step`` (its field ``kind``, when given) take the device path?  A run without mechanics has no
+        displacement on the device: the kinds that read u stay with numpy there, which takes u = 0 from the results."""
+        from .. import _backend
+        h = self._backend
+        if self._device is False or not isinstance(h, _backend.Handle):
+            return False
+        if kind in self._NEEDS_U and not getattr(h, 'with_mechanics', True):
+            return False
+        if recording_step is None:
+            recording_step = self._results.get_recording_steps()[-1]
+        field = self._results.get_result(recording_step).get_field()
+        return bool(self._device) or getattr(field, 'snapshot_id', None) is not None
+
+    _GETTERS = {'strain_tensor': 'get_strain_tensor', 'stress_tensor': 'get_stress_tensor', 'pressure': 'get_pressure',
+                'van_mises_stress': 'get_van_mises_stress', 'displacement_norm': 'get_displacement_norm',
+                'log_growth': 'get_logistic_growth', 'mech_expansion': 'get_mech_expansion',
+                'total_jacobian': 'get_total_jacobian', 'growth_induced_jacobian': 'get_growth_induced_jacobian',
+                'concentration_deformed_config': 'get_concentration_deformed_configuration'}
+
+    def sample(self, kind, recording_step, sampler, fill=np.nan):
+        """The derived field ``kind`` (a key of _GETTERS) at a sampler's points: on the device path straight from the result's
+        device buffer, else the numpy field through ``sampler.apply``.  Tensors as their symmetric components xx, yy, (zz,)
+        xy, (xz, yz)."""
+        if self._derive(kind, recording_step, fetch=False)[0]:
+            return sampler.apply('derived', fill=fill)
+        v = getattr(self, self._GETTERS[kind])(recording_step).values()
+        if v.ndim == 3:
+            d = v.shape[-1]
+            pairs = [(a, a) for a in range(d)] + [(a, b) for a in range(d) for b in range(a + 1, d)]
+            v = np.stack([v[:, a, b] for a, b in pairs], axis=1)
+        return sampler.apply(v, fill=fill)
+
     # -- projections ------------------------------------------------------------------------------------------------
     def _solve_mass(self, rhs):
         if self._backend is None:
@@ -143,38 +215,59 @@ class PostProcess:
     # -- fields ---------------------------------------------------------------------------------------------------
     def get_strain_tensor(self, recording_step=None):
         """:1566-1573"""
+        done, out = self._derive('strain_tensor', recording_step)
+        if done:
+            return Function(self._mesh, {None: out}, name="strain_tensor")
         return self.project_cell_field(mle.compute_strain(self._cell_grad_u(recording_step)), "strain_tensor")
 
     def get_stress_tensor(self, recording_step=None):
         """:1736-1744 -- 2 mu eps + lambda tr(eps) I with cell-wise mu, lambda"""
+        done, out = self._derive('stress_tensor', recording_step)
+        if done:
+            return Function(self._mesh, {None: out}, name="stress_tensor")
         E, nu = self._cell_values('E'), self._cell_values('nu')
         sig = mle.compute_stress(self._cell_grad_u(recording_step), mle.compute_mu(E, nu), mle.compute_lambda(E, nu))
         return self.project_cell_field(sig, "stress_tensor")
 
     def get_pressure(self, recording_step=None):
         """:1587-1593 -- 1/3 tr(stress) of the projected (P1) stress; projecting a P1 field again is the identity"""
+        done, out = self._derive('pressure', recording_step)
+        if done:
+            return Function(self._mesh, {None: out}, name="pressure")
         s = self.get_stress_tensor(recording_step).values()
         return Function(self._mesh, {None: mle.compute_pressure_from_stress_tensor(s)}, name="pressure")
 
     def get_van_mises_stress(self, recording_step=None):
         """:1595-1601"""
+        done, out = self._derive('van_mises_stress', recording_step)
+        if done:
+            return Function(self._mesh, {None: out}, name="van_mises_stress")
         s = self.get_stress_tensor(recording_step).values()
         d = self._mesh.dim
         return self.project_pointwise(lambda sq: mle.compute_van_mises_stress(sq, d), [s], name="van_mises_stress")
 
     def get_displacement_norm(self, recording_step=None):
         """:1612-1618"""
+        done, out = self._derive('displacement_norm', recording_step)
+        if done:
+            return Function(self._mesh, {None: out}, name="displacement_norm")
         u = self.get_solution_displacement(recording_step).values()
         return self.project_pointwise(lambda uq: np.sqrt((uq * uq).sum(axis=-1)), [u], name="displacement_norm")
 
     def get_logistic_growth(self, recording_step=None):
         """:1746-1752"""
+        done, out = self._derive('log_growth', recording_step)
+        if done:
+            return Function(self._mesh, {None: out}, name="log_growth")
         c = self.get_solution_concentration(recording_step).values()
         rho = self._cell_values('rho')
         return self.project_pointwise(lambda cq, r: mrd.compute_growth_logistic(cq, r, 1.0), [c], [rho], "log_growth")
 
     def get_mech_expansion(self, recording_step=None):
         """:1754-1761 -- c * coupling * I"""
+        done, out = self._derive('mech_expansion', recording_step)
+        if done:
+            return Function(self._mesh, {None: out[:, None, None] * np.eye(self._mesh.dim)}, name="mech_expansion")
         c = self.get_solution_concentration(recording_step).values()
         d = self._mesh.dim
         gam = self._cell_values('gamma')
@@ -185,10 +278,16 @@ class PostProcess:
 
     def get_total_jacobian(self, recording_step=None):
         """:1763-1769 -- det(I + grad u), constant per cell"""
+        done, out = self._derive('total_jacobian', recording_step)
+        if done:
+            return Function(self._mesh, {None: out}, name="total_jacobian")
         return self.project_cell_field(mle.compute_total_jacobian(self._cell_grad_u(recording_step)), "total_jacobian")
 
     def get_growth_induced_jacobian(self, recording_step=None):
         """:1771-1777 -- det(I + P1 growth strain)"""
+        done, out = self._derive('growth_induced_jacobian', recording_step)
+        if done:
+            return Function(self._mesh, {None: out}, name="growth_induced_jacobian")
         sg = self.get_mech_expansion(recording_step).values()
         d = self._mesh.dim
         return self.project_pointwise(lambda s: mle.compute_growth_induced_jacobian(s, d), [sg],
@@ -196,6 +295,9 @@ class PostProcess:
 
     def get_concentration_deformed_configuration(self, recording_step=None):
         """:1779-1786 -- c * J_growth / J_total (math_linear_elasticity.py:66-70)"""
+        done, out = self._derive('concentration_deformed_config', recording_step)
+        if done:
+            return Function(self._mesh, {None: out}, name="concentration_deformed_config")
         c = self.get_solution_concentration(recording_step).values()
         d = self._mesh.dim
         gam = self._cell_values('gamma')
@@ -225,7 +327,9 @@ class PostProcess:
         return list(np.einsum('fab,fb->a', smean, nrm))
 
     def save_all(self, save_method='vtk', clear_all=False, selection=slice(None), output_dir=None):
-        """:1922-1943 -- writes the derived fields of the selected recording steps as .vtu files"""
+        """:1922-1943 -- writes the derived fields of the selected recording steps as .vtu files.  On the device path every
+        field is fetched once; the displacement of a step is solved once (by the recorded displacement's own lazy solve, which
+        the derived fields then find in place) and its stress is projected once (pressure and von Mises share it)."""
         from ..utils.vtu_io import write_vtu
         out = output_dir or self.output_dir
         os.makedirs(out, exist_ok=True)

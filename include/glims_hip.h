@@ -24,6 +24,8 @@
  *   GLIMS_VERBOSE        any value: timing lines of the set-up phases and the solver's one-off decisions (preconditioner,
  *                        spectral interval of the dot-free solves, solves taken back) on stderr
  *   GLIMS_VERBOSE_CHEB   any value: one line per dot-free RD solve (residual before / after, tolerance, passes)
+ *   GLIMS_DERIVE_TIMING  any value: glims_derive puts a HIP event pair around its cell pass and around its gather and prints one
+ *                        line per projection with both times on stderr (tools/derive_cost.py; a synchronisation per pass)
  *   GLIMS_HOST_THREADS   OpenMP team of the host-side symbolic phase (default: the CPUs this process may use,
  *                        divided by the ranks on the host)
  *   GLIMS_HOST_SYMBOLIC  TEST HOOK: glims_create runs the host (OpenMP) implementation of the symbolic phase instead of
@@ -651,7 +653,9 @@ int glims_sampler_info(glims_ctx* h, int64_t id, int64_t* n_points, int64_t* n_f
  * may be NULL. */
 int glims_sampler_get(glims_ctx* h, int64_t id, int32_t* cell, double* w);
 /* out[n][ncomp] = P f (ncomp 1..8; GLIMS_FIELD_C / _SNAPSHOT_C: 1, GLIMS_FIELD_U: dim); points outside the mesh get `fill`
- * (NaN is what the reference's images hold there).  nodal is read for GLIMS_FIELD_HOST only, snapshot for _SNAPSHOT_C only. */
+ * (NaN is what the reference's images hold there).  nodal is read for GLIMS_FIELD_HOST only, snapshot for _SNAPSHOT_C only.
+ * GLIMS_FIELD_DERIVED (defined with glims_derive below): the result of the last glims_derive, ncomp = its component count (1, or
+ * d(d+1)/2 for a tensor); GLIMS_E_USAGE with nothing derived or another ncomp. */
 int glims_sampler_apply(glims_ctx* h, int64_t id, int field, int64_t snapshot, const double* nodal, int ncomp, double fill,
                         double* out);
 /* g[n_nodes][ncomp] = P^T r, r[n][ncomp], caller's node order; values of r at points outside the mesh are not read into any
@@ -719,6 +723,69 @@ int glims_adjoint_image_terms(glims_ctx* h, int n, const glims_image_misfit* ter
 /* out = (sampler id, number of points, number of observed points) of stored term k; on a partitioned handle out[2] is the
  * number of observed points THIS RANK counts (their sum over the ranks is the term's observed count) */
 int glims_adjoint_image_info(glims_ctx* h, int k, int64_t out[3]);
+
+/* ---- derived fields of a recorded step, on the device -----------------------------------------------------------------------
+ * The reference's PostProcess classes project UFL expressions of a recorded step onto the P1 space (helper_classes.py:1521-1972:
+ * get_strain_tensor :1566, get_pressure :1587, get_van_mises_stress :1595, get_displacement_norm :1612, get_stress_tensor :1736,
+ * get_logistic_growth :1746, get_mech_expansion :1754, get_total_jacobian :1763, get_growth_induced_jacobian :1771,
+ * get_concentration_deformed_configuration :1779; save_all :1922 writes them).  glims_derive computes one such field from data
+ * that are already on the device: a per-cell pass evaluates the integrand -- cell-wise constants
+ * exactly, the others with the 16 / 64-point conical-product Gauss-Jacobi rule of csrc/derive_quadrature.h (degree 7) --, an
+ * atomics-free gather along each row's incidence list sums the right-hand sides, and glims_project's Jacobi-PCG solves the mass
+ * systems component by component to ||r|| <= rtol ||rhs||.  The same arguments give the same bits on every call.
+ *
+ * Source of c and u:
+ *   snapshot >= 0          an id of glims_snapshot_save; where the kind needs the displacement it is solved on the device as
+ *                          glims_snapshot_mechanics solves it (same status codes), unless the handle's U already belongs to that
+ *                          snapshot.  glims_snapshot_mechanics sets that memory; glims_step, glims_set_state,
+ *                          glims_solve_mechanics, glims_set_materials, glims_setup, a new elastic Dirichlet set or load and
+ *                          glims_snapshot_clear forget it.
+ *   GLIMS_DERIVE_CURRENT   the handle's current c and U as they stand (the caller has solved the mechanics)
+ *   GLIMS_DERIVE_HOST      c_host[n_nodes], u_host[n_nodes*dim] in the caller's node order (NULL where the kind needs none);
+ *                          uploaded into scratch, neither c nor U is touched
+ * Kinds (ncomp components; tensors are kept and sampled as their d(d+1)/2 symmetric components xx, yy, (zz,) xy, (xz, yz)):
+ *   _STRAIN           projection of eps(u_h)                              cell-wise constant   tensor
+ *   _STRESS           projection of 2 mu_T eps + lambda_T tr(eps) I       cell-wise constant   tensor
+ *   _PRESSURE         1/3 tr of the P1 stress of _STRESS, nodewise (no further solve)          scalar
+ *   _VON_MISES        projection of sqrt(3/2 dev:dev) of the P1 stress (dev = sigma - 1/3 tr I) scalar, second stage
+ *   _DISP_NORM        projection of |u_h|                                                      scalar
+ *   _LOG_GROWTH       projection of rho_T c_h (1 - c_h)                                        scalar
+ *   _MECH_EXPANSION   gamma c nodewise when gamma is one value over all cells (the labels the cells carry), else the projection of
+ *                     gamma_T c_h; the scalar s of the growth strain s I                       scalar
+ *   _TOTAL_JACOBIAN   projection of det(I + grad u_h)                     cell-wise constant   scalar
+ *   _GROWTH_JACOBIAN  projection of (1 + s_h)^d, s_h the P1 field of _MECH_EXPANSION           scalar, second stage
+ *   _CONC_DEFORMED    projection of c_h (1 + gamma_T c_h)^d / det(I + grad u_h)                scalar
+ * The projected P1 stress of (snapshot or CURRENT, displacement generation) is kept in a one-entry device cache: _PRESSURE and
+ * _VON_MISES of one step project it once between them; a cached stress is reused only by calls whose rtol is not tighter than
+ * the one it was solved to.  glims_derive_info makes that countable.
+ *
+ * The result stays on the device (planes [ncomp][n_nodes], internal numbering) until the next glims_derive or glims_destroy;
+ * glims_sampler_apply(field = GLIMS_FIELD_DERIVED, ncomp = its component count) evaluates it at a sampler's points.  out (may be
+ * NULL) receives [n_nodes] for a scalar and the full [n_nodes][d][d] for a tensor, caller's node order.
+ *
+ * Like glims_project the call shares the Jacobi diagonal and the PCG work vectors with the time stepper and drops the step the
+ * last sweep prepared; the steps that follow have the bits of a run that never called it.
+ * Returns the worst status of its solves (GLIMS_OK / GLIMS_NOT_CONVERGED / GLIMS_NAN).  GLIMS_E_USAGE, with a reason in
+ * glims_last_error and nothing changed: unknown kind or snapshot, a call before glims_setup, a kind that needs u on a handle set
+ * up without mechanics, GLIMS_DERIVE_CURRENT before glims_set_state, a required host pointer that is NULL, rtol <= 0, a
+ * partitioned handle (world > 1: the host path of the Python layer stays there). */
+#define GLIMS_DERIVE_STRAIN 0
+#define GLIMS_DERIVE_STRESS 1
+#define GLIMS_DERIVE_PRESSURE 2
+#define GLIMS_DERIVE_VON_MISES 3
+#define GLIMS_DERIVE_DISP_NORM 4
+#define GLIMS_DERIVE_LOG_GROWTH 5
+#define GLIMS_DERIVE_MECH_EXPANSION 6
+#define GLIMS_DERIVE_TOTAL_JACOBIAN 7
+#define GLIMS_DERIVE_GROWTH_JACOBIAN 8
+#define GLIMS_DERIVE_CONC_DEFORMED 9
+#define GLIMS_DERIVE_CURRENT (-1)
+#define GLIMS_DERIVE_HOST (-2)
+#define GLIMS_FIELD_DERIVED 4      /* glims_sampler_apply: the result of the last glims_derive, from its device buffer */
+int glims_derive(glims_ctx* h, int kind, int64_t snapshot, const double* c_host, const double* u_host, double rtol,
+                 double* out);
+/* cumulative since glims_create: out[0] cell passes, [1] mass solves, [2] elastic solves, [3] hits of the stress cache */
+int glims_derive_info(const glims_ctx* h, int64_t out[4]);
 
 /* ---- single-node multi-GPU (one process per GPU, RCCL over xGMI) ------------------------------------- */
 
