@@ -7,6 +7,7 @@ Signatures mirror ``include/glims_hip.h`` one to one.
 from __future__ import annotations
 
 import ctypes as C
+import logging
 import os
 
 import numpy as np
@@ -37,6 +38,7 @@ RD_LINEAR_AUTO, RD_LINEAR_PCG, RD_LINEAR_CHEBYSHEV = 0, 1, 2
 STREAM_AUTO, STREAM_NONTEMPORAL, STREAM_CACHED = 0, 1, 2
 FIELD_C, FIELD_U, FIELD_SNAPSHOT_C, FIELD_HOST = 0, 1, 2, 3
 FIELD_DERIVED = 4       # the result of the last glims_derive, sampled from its device buffer
+FIELD_XYZ = 5           # the mesh's reference coordinates: on a deformed sampler the back map X(x_p)
 DERIVE_CURRENT, DERIVE_HOST = -1, -2
 # glims_derive kinds by name (GLIMS_DERIVE_*); the first two are tensors
 DERIVE_KINDS = {"strain_tensor": 0, "stress_tensor": 1, "pressure": 2, "van_mises_stress": 3, "displacement_norm": 4,
@@ -167,6 +169,10 @@ SIGNATURES = {
     "glims_adjoint_stats": (C.c_int, [_h, _i64p, _dp]),
     "glims_sampler_create_points": (C.c_int, [_h, C.c_int64, _dp, C.c_int, _i64p]),
     "glims_sampler_create_grid": (C.c_int, [_h, _dp, _dp, _i64p, C.c_int, _i64p]),
+    "glims_sampler_create_grid_deformed": (C.c_int, [_h, _dp, _dp, _i64p, C.c_int64, _dp, C.c_double, C.c_int, _i64p]),
+    "glims_sampler_create_points_deformed": (C.c_int, [_h, C.c_int64, _dp, C.c_int64, _dp, C.c_double, C.c_int, _i64p]),
+    "glims_sampler_deformation_info": (C.c_int, [_h, C.c_int64, _i64p, _dp]),
+    "glims_sampler_warp": (C.c_int, [_h, C.c_int64, _dp, _dp, _dp, _i64p, C.c_int, C.c_int, C.c_double, _dp]),
     "glims_sampler_info": (C.c_int, [_h, C.c_int64, _i64p, _i64p]),
     "glims_sampler_get": (C.c_int, [_h, C.c_int64, _i32p, _dp]),
     "glims_sampler_apply": (C.c_int, [_h, C.c_int64, C.c_int, C.c_int64, _dp, C.c_int, C.c_double, _dp]),
@@ -586,21 +592,59 @@ class Handle:
         return d
 
     # -- samplers --------------------------------------------------------------------------------
-    def sampler_points(self, xyz):
-        """Locate the points xyz [n, dim] in the mesh once; returns a :class:`Sampler`."""
+    def _deformation_source(self, deformed_by):
+        """(u_source, u_host) of the deformed creators: a snapshot id, 'current', or a nodal array [n_nodes, dim]."""
+        if isinstance(deformed_by, str):
+            if deformed_by != 'current':
+                raise ValueError("deformed_by must be a snapshot id, 'current' or a nodal array [n_nodes, dim]")
+            return DERIVE_CURRENT, None
+        if isinstance(deformed_by, (int, np.integer)):
+            if deformed_by < 0:
+                raise ValueError("deformed_by: snapshot ids are not negative")
+            return int(deformed_by), None
+        u = np.asarray(deformed_by, dtype=np.float64)
+        if u.size != self.n_nodes * self.dim:
+            raise ValueError("deformed_by has %d entries, the mesh %d nodes x %d" % (u.size, self.n_nodes, self.dim))
+        return DERIVE_HOST, _f64(u.reshape(-1), (self.n_nodes * self.dim,))
+
+    def _deformed_status(self, st):
+        self.last_sampler_status = st
+        self._check(st, allow=(GLIMS_NOT_CONVERGED,))
+        if st == GLIMS_NOT_CONVERGED:
+            logging.getLogger(__name__).warning(
+                "deformed sampler: the displacement solve stopped at its iteration cap; the points are located in the mesh "
+                "displaced by what it reached")
+
+    def sampler_points(self, xyz, deformed_by=None, scale=1.0):
+        """Locate the points xyz [n, dim] in the mesh once; returns a :class:`Sampler`.  With ``deformed_by`` (a snapshot id,
+        'current', or a nodal displacement [n_nodes, dim] in the caller's node order) the points are located in the mesh
+        displaced by ``scale`` times that displacement (glims_sampler_create_points_deformed): the sampler then evaluates
+        fields at the material points that sit at xyz, and stays as it is whatever the handle does later.
+        ``last_sampler_status`` holds the status of the displacement solve (GLIMS_NOT_CONVERGED is a logged warning)."""
         xyz = _f64(np.asarray(xyz, dtype=np.float64).reshape(-1, self.dim))
         sid = C.c_int64(-1)
-        self._check(self.lib.glims_sampler_create_points(self._h, xyz.shape[0], _ptr(xyz, _dp), 0, C.byref(sid)))
+        if deformed_by is None:
+            self._check(self.lib.glims_sampler_create_points(self._h, xyz.shape[0], _ptr(xyz, _dp), 0, C.byref(sid)))
+        else:
+            src, u = self._deformation_source(deformed_by)
+            self._deformed_status(self.lib.glims_sampler_create_points_deformed(
+                self._h, xyz.shape[0], _ptr(xyz, _dp), src, _ptr(u, _dp), float(scale), 0, C.byref(sid)))
         return Sampler(self, int(sid.value), None)
 
-    def sampler_grid(self, origin, spacing, size):
-        """Locate the points origin + index * spacing of a grid with size[a] points along axis a (x fastest)."""
+    def sampler_grid(self, origin, spacing, size, deformed_by=None, scale=1.0):
+        """Locate the points origin + index * spacing of a grid with size[a] points along axis a (x fastest).  ``deformed_by``
+        / ``scale``: as for sampler_points (glims_sampler_create_grid_deformed)."""
         o, sp = _f64(origin, (self.dim,)), _f64(spacing, (self.dim,))
         sz = np.ascontiguousarray(size, dtype=np.int64)
         assert sz.shape == (self.dim,)
         sid = C.c_int64(-1)
-        self._check(self.lib.glims_sampler_create_grid(self._h, _ptr(o, _dp), _ptr(sp, _dp), _ptr(sz, _i64p), 0,
-                                                       C.byref(sid)))
+        if deformed_by is None:
+            self._check(self.lib.glims_sampler_create_grid(self._h, _ptr(o, _dp), _ptr(sp, _dp), _ptr(sz, _i64p), 0,
+                                                           C.byref(sid)))
+        else:
+            src, u = self._deformation_source(deformed_by)
+            self._deformed_status(self.lib.glims_sampler_create_grid_deformed(
+                self._h, _ptr(o, _dp), _ptr(sp, _dp), _ptr(sz, _i64p), src, _ptr(u, _dp), float(scale), 0, C.byref(sid)))
         return Sampler(self, int(sid.value), tuple(int(v) for v in sz))
 
     # -- multi-GPU -------------------------------------------------------------------------------
@@ -658,6 +702,12 @@ class Sampler:
         n, nf = C.c_int64(0), C.c_int64(0)
         handle._check(handle.lib.glims_sampler_info(handle._h, sid, C.byref(n), C.byref(nf)))
         self.n_points, self.n_found = int(n.value), int(nf.value)
+        # deformed samplers (glims_sampler_deformation_info): cells whose det(E_deformed) / det(E_reference) is not > 0, and
+        # the smallest such ratio = min_T det(I + scale grad u_h); 0 and 1 on an undeformed sampler
+        info = np.zeros(2, dtype=np.int64)
+        mr = C.c_double(1.0)
+        handle._check(handle.lib.glims_sampler_deformation_info(handle._h, sid, _ptr(info, _i64p), C.byref(mr)))
+        self.deformed, self.n_inverted, self.min_jacobian = bool(info[0]), int(info[1]), float(mr.value)
 
     def _get(self, want_cells, want_weights):
         h = self.handle
@@ -699,7 +749,7 @@ class Sampler:
 
     def apply(self, field, snapshot=None, fill=np.nan):
         """P f at every point: ``field`` = 'c' (current concentration, or the device snapshot ``snapshot``), 'u' (current
-        displacement), 'derived' (the result of the handle's last ``derive``, from its device buffer: [n_points] for a scalar,
+        displacement), 'x' (the mesh's reference coordinates: on a deformed sampler the back map X(x_p)), 'derived' (the result of the handle's last ``derive``, from its device buffer: [n_points] for a scalar,
         [n_points, d(d+1)/2] symmetric components xx, yy, (zz,) xy, (xz, yz) for a tensor) or a nodal array [n_nodes] /
         [n_nodes, k] in the caller's node order.  Returns [n_points] for a one-dimensional field, [n_points, k] otherwise;
         points outside the mesh hold ``fill``."""
@@ -712,13 +762,17 @@ class Sampler:
                 if snapshot is not None:
                     raise ValueError("snapshots hold the concentration only")
                 kind, ncomp = FIELD_U, h.dim
+            elif field == 'x':
+                if snapshot is not None:
+                    raise ValueError("'x' takes no snapshot")
+                kind, ncomp = FIELD_XYZ, h.dim
             elif field == 'derived':
                 if snapshot is not None:
                     raise ValueError("'derived' is the last derive()'s result; it takes no snapshot")
                 ncomp = getattr(h, "_derived_ncomp", 1)
                 kind, flat = FIELD_DERIVED, ncomp == 1
             else:
-                raise ValueError("field must be 'c', 'u', 'derived' or a nodal array")
+                raise ValueError("field must be 'c', 'u', 'x', 'derived' or a nodal array")
         else:
             a = np.asarray(field, dtype=np.float64)
             if a.shape[0] != h.n_nodes:
@@ -740,6 +794,31 @@ class Sampler:
         g = np.empty((h.n_nodes, a.shape[1]))
         h._check(h.lib.glims_sampler_apply_t(h._h, self.id, _ptr(a, _dp), int(a.shape[1]), _ptr(g, _dp)))
         return g[:, 0] if flat else g
+
+    def back_map(self, fill=np.nan):
+        """X(x_p) [n_points, dim]: the reference position of the material point that sits at x_p (``apply('x')``)."""
+        return self.apply('x', fill=fill)
+
+    def warp(self, array, origin, spacing, order='linear', fill=np.nan):
+        """image(X(x_p)) at every point (glims_sampler_warp): ``array`` [z,] y, x [, component] with voxel centres origin +
+        index * spacing, ``order`` 'linear' (d-linear) or 'nearest'.  Returns [n_points] or [n_points, k]; points outside
+        the mesh and points whose X lies outside the source image hold ``fill``."""
+        h = self.handle
+        if order not in ('linear', 'nearest', 0, 1):
+            raise ValueError("order must be 'linear' or 'nearest'")
+        o = 1 if order in ('linear', 1) else 0
+        a = np.asarray(array, dtype=np.float64)
+        if a.ndim not in (h.dim, h.dim + 1):
+            raise ValueError("the source image has %d axes, the mesh %d dimensions" % (a.ndim, h.dim))
+        flat = a.ndim == h.dim
+        size = np.ascontiguousarray(a.shape[:h.dim][::-1], dtype=np.int64)
+        ncomp = 1 if flat else a.shape[-1]
+        a = _f64(a.reshape(-1))
+        og, sp = _f64(origin, (h.dim,)), _f64(spacing, (h.dim,))
+        out = np.empty((self.n_points, max(1, ncomp)))
+        h._check(h.lib.glims_sampler_warp(h._h, self.id, _ptr(a, _dp), _ptr(og, _dp), _ptr(sp, _dp), _ptr(size, _i64p),
+                                          int(ncomp), o, float(fill), _ptr(out, _dp)))
+        return out[:, 0] if flat else out
 
     def close(self):
         h = self.handle

@@ -917,6 +917,41 @@ int glims_sampler_create_grid(glims_ctx* h, const double* origin, const double* 
   });
 }
 
+int glims_sampler_create_grid_deformed(glims_ctx* h, const double* origin, const double* spacing, const int64_t* size,
+                                       int64_t u_source, const double* u_host, double scale, int flags, int64_t* id) {
+  return guarded(h, [&]() {
+    GL_REQUIRE(id && origin && spacing && size, "glims_sampler_create_grid_deformed: null argument");
+    GL_REQUIRE(flags == 0, "glims_sampler_create_grid_deformed: flags is reserved and must be 0");
+    return gl_sampler_create_deformed(h, 0, nullptr, origin, spacing, size, u_source, u_host, scale, id);
+  });
+}
+
+int glims_sampler_create_points_deformed(glims_ctx* h, int64_t n, const double* xyz, int64_t u_source, const double* u_host,
+                                         double scale, int flags, int64_t* id) {
+  return guarded(h, [&]() {
+    GL_REQUIRE(id, "glims_sampler_create_points_deformed: null id");
+    GL_REQUIRE(flags == 0, "glims_sampler_create_points_deformed: flags is reserved and must be 0");
+    GL_REQUIRE(n >= 0 && (n == 0 || xyz), "glims_sampler_create_points_deformed: n < 0 or null coordinates");
+    static const double none = 0.0;
+    return gl_sampler_create_deformed(h, n, xyz ? xyz : &none, nullptr, nullptr, nullptr, u_source, u_host, scale, id);
+  });
+}
+
+int glims_sampler_deformation_info(glims_ctx* h, int64_t id, int64_t out[2], double* min_ratio) {
+  return guarded(h, [&]() {
+    gl_sampler_deformation_info(h, id, out, min_ratio);
+    return GLIMS_OK;
+  });
+}
+
+int glims_sampler_warp(glims_ctx* h, int64_t id, const double* image, const double* origin, const double* spacing,
+                       const int64_t* size, int ncomp, int order, double fill, double* out) {
+  return guarded(h, [&]() {
+    gl_sampler_warp(h, id, image, origin, spacing, size, ncomp, order, fill, out);
+    return GLIMS_OK;
+  });
+}
+
 int glims_sampler_info(glims_ctx* h, int64_t id, int64_t* n_points, int64_t* n_found) {
   return guarded(h, [&]() {
     gl_sampler_info(h, id, n_points, n_found);

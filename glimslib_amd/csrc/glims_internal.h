@@ -769,6 +769,13 @@ const int32_t* gl_ensure_cell_nodes(glims_ctx* h);
 // sample.hip ----------------------------------------------------------------------------------------
 int64_t gl_sampler_create(glims_ctx* h, int64_t n, const double* xyz, const double* origin, const double* spacing,
                           const int64_t* size);   // xyz != nullptr: point set; else the grid
+// the same points located in the mesh displaced by scale u (u_source: snapshot id, GLIMS_DERIVE_CURRENT or _HOST); returns the
+// elastic solve's status
+int gl_sampler_create_deformed(glims_ctx* h, int64_t n, const double* xyz, const double* origin, const double* spacing,
+                               const int64_t* size, int64_t u_source, const double* u_host, double scale, int64_t* id);
+void gl_sampler_deformation_info(glims_ctx* h, int64_t id, int64_t out[2], double* min_ratio);
+void gl_sampler_warp(glims_ctx* h, int64_t id, const double* image, const double* origin, const double* spacing,
+                     const int64_t* size, int ncomp, int order, double fill, double* out);
 void gl_sampler_info(glims_ctx* h, int64_t id, int64_t* n_points, int64_t* n_found);
 void gl_sampler_get(glims_ctx* h, int64_t id, int32_t* cell, double* w);
 void gl_sampler_apply(glims_ctx* h, int64_t id, int field, int64_t snapshot, const double* nodal, int ncomp, double fill,

@@ -18,6 +18,11 @@
 // winner is the GLOBAL winner -- the smallest global cell id over the ranks -- and marks each point COUNTED on the smallest
 // rank that keeps it.  The transpose's lists are then built from the kept points and P^T runs as on one GPU: an owned row has
 // all its cells local, so its incidence list sees every kept point of every one of its cells and no exchange is needed.
+//
+// Deformed samplers (single-rank handles): the same claim and weight kernels run on a transient coordinate array
+// y = fl(X + fl(scale u)) instead of the mesh's own, so a point x_p is located in the DISPLACED mesh; with its cell, nodes and
+// weights P f is f at the material point X(x_p) that sits at x_p, and P applied to the reference coordinates is the back map
+// X(x_p) itself.  glims_sampler_warp evaluates a voxel image at X(x_p) without materialising X.
 #include "glims_internal.h"
 
 #include <algorithm>
@@ -51,6 +56,11 @@ struct GlSampler {
   // staging, grown on demand
   dvec<double> f_ext, f_int, out, q, g_int;
   dvec<double> part;           // image misfit: per-block partial sums, then the total
+  // deformed samplers (glims_sampler_create_*_deformed): located in the mesh at X + scale u, frozen from then on
+  bool deformed = false;
+  int64_t n_inverted = 0;      // cells whose det(E_deformed) / det(E_reference) is not > 0
+  double min_ratio = 1.0;      // the smallest such ratio
+  dvec<double> img;            // glims_sampler_warp: the source image of the call
 };
 
 namespace {
@@ -749,6 +759,165 @@ __global__ __launch_bounds__(256) void k_resolve_pick(int64_t m, int64_t p0, int
   if (threadIdx.x == 0 && here) atomicAdd(n_kept, (unsigned long long)here);   // (integer: order-independent)
 }
 
+// ---- deformed samplers -------------------------------------------------------------------------------------------------------
+// One thread per node: y = fl(X + fl(scale u)), two roundings, never contracted (numpy's points + scale * u).
+// Bytes per node: 16 D in (X, u), 8 D out.
+template <int D>
+__global__ __launch_bounds__(256) void k_deform_xyz(int64_t n, const double* __restrict__ X, const double* __restrict__ u,
+                                                    double scale, double* __restrict__ y) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+#pragma unroll
+  for (int a = 0; a < D; ++a) y[i * D + a] = __dadd_rn(X[i * D + a], __dmul_rn(scale, u[i * D + a]));
+}
+
+template <int D>
+__device__ __forceinline__ double edge_det(const double* __restrict__ xyz, const int32_t* nd) {
+  double e[D][D];
+#pragma unroll
+  for (int k = 0; k < D; ++k)
+#pragma unroll
+    for (int a = 0; a < D; ++a) e[k][a] = xyz[(int64_t)nd[k + 1] * D + a] - xyz[(int64_t)nd[0] * D + a];
+  if constexpr (D == 2) {
+    return e[0][0] * e[1][1] - e[0][1] * e[1][0];
+  } else {
+    return e[0][0] * (e[1][1] * e[2][2] - e[1][2] * e[2][1]) - e[0][1] * (e[1][0] * e[2][2] - e[1][2] * e[2][0]) +
+           e[0][2] * (e[1][0] * e[2][1] - e[1][1] * e[2][0]);
+  }
+}
+
+__device__ __forceinline__ double wave_min(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_down(v, o, 64));
+  return v;
+}
+
+// One thread per cell: ratio = det(E_deformed) / det(E_reference) = det(I + scale grad u_h) on the cell.  n_bad counts the
+// cells whose ratio is not > 0 (folded, flat or non-finite; an integer atomic per block), part[block] = the block's smallest
+// ratio (fmin drops a NaN; min does not depend on the order, so the result is the same on every call).
+// Bytes per cell: 4 (D + 1) node ids + 8 per block; 2 D (D + 1) coordinates gathered through the caches.
+template <int D>
+__global__ __launch_bounds__(256) void k_deform_cells(int64_t n_cells, const int32_t* __restrict__ cell_nodes,
+                                                      const double* __restrict__ X, const double* __restrict__ y,
+                                                      double* __restrict__ part, unsigned long long* __restrict__ n_bad) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  double ratio = __longlong_as_double(0x7ff0000000000000LL);   // +inf: neutral for min
+  bool bad = false;
+  if (e < n_cells) {
+    int32_t nd[D + 1];
+#pragma unroll
+    for (int m = 0; m <= D; ++m) nd[m] = cell_nodes[e * (D + 1) + m];
+    ratio = edge_det<D>(y, nd) / edge_det<D>(X, nd);
+    bad = !(ratio > 0.0) || !isfinite(ratio);
+  }
+  const int bad_here = __syncthreads_count(bad);
+  if (threadIdx.x == 0 && bad_here) atomicAdd(n_bad, (unsigned long long)bad_here);
+  __shared__ double sm[4];
+  const double wm = wave_min(ratio);
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = wm;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = fmin(fmin(sm[0], sm[1]), fmin(sm[2], sm[3]));
+}
+
+// second stage, ONE block over the per-block minima
+__global__ __launch_bounds__(1024) void k_deform_min(int64_t n_blocks, const double* __restrict__ part, double* __restrict__ out) {
+  double m = __longlong_as_double(0x7ff0000000000000LL);
+  for (int64_t b = threadIdx.x; b < n_blocks; b += 1024) m = fmin(m, part[b]);
+  __shared__ double sm[16];
+  m = wave_min(m);
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = sm[0];
+    for (int k = 1; k < 16; ++k) t = fmin(t, sm[k]);
+    out[0] = t;
+  }
+}
+
+// glims_sampler_warp, one thread per point: out[p][.] = image(X(x_p)), X = sum_m w[p][m] X_node(m) the back-mapped position
+// (formed in registers, never stored).  Per axis t = (X - o) / s.
+//   ORDER 1 (d-linear): inside iff 0 <= t <= n - 1; i0 = min(floor(t), n - 2) (n = 1: i0 = 0, f = 0), f = t - i0; the value is
+//           the sum over the 2^D corners (z outermost, x innermost) of (product of f or 1 - f) * voxel -- plain IEEE arithmetic,
+//           a NaN voxel of the stencil propagates even where its weight is 0.
+//   ORDER 0 (nearest): inside iff -0.5 <= t < n - 0.5; index floor(t + 0.5) (kept <= n - 1 where t + 0.5 rounds up to n).
+// A point outside the mesh or outside the source image gets `fill`.
+// Bytes per found point: NV (4 + 8) node ids and weights + 4 (cell) read, 8 ncomp written; the NV D reference coordinates and the
+// 2^D (or 1) x ncomp voxels are gathered through the caches.
+template <int NV, int D, int ORDER>
+__global__ __launch_bounds__(256) void k_warp(int64_t n, int ncomp, const int32_t* __restrict__ cell,
+                                              const int32_t* __restrict__ node, const double* __restrict__ w,
+                                              const double* __restrict__ xyz, GridSpec gs, const double* __restrict__ img,
+                                              double fill, double* __restrict__ out) {
+  static_assert(NV == D + 1, "simplices");
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n) return;
+  bool inside = cell[p] >= 0;
+  int64_t base = 0;          // voxel (i0, j0, k0)
+  double f[D];
+  if (inside) {
+    double X[D];
+#pragma unroll
+    for (int a = 0; a < D; ++a) X[a] = 0.0;
+#pragma unroll
+    for (int m = 0; m < NV; ++m) {
+      const int64_t nd = node[p * NV + m];
+      const double wt = w[p * NV + m];
+#pragma unroll
+      for (int a = 0; a < D; ++a) X[a] += wt * xyz[nd * D + a];
+    }
+    int64_t stride = 1;
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+      const double t = (X[a] - gs.o[a]) / gs.s[a];
+      const long long na = gs.n[a];
+      long long i0;
+      if constexpr (ORDER == 1) {
+        inside = inside && t >= 0.0 && t <= (double)(na - 1);   // (false for a NaN)
+        const double fl = floor(t);
+        i0 = na > 1 ? (fl < (double)(na - 2) ? (long long)fl : na - 2) : 0;
+        f[a] = na > 1 ? t - (double)i0 : 0.0;
+      } else {
+        inside = inside && t >= -0.5 && t < (double)na - 0.5;
+        const double fl = floor(t + 0.5);
+        i0 = fl < (double)(na - 1) ? (long long)fl : na - 1;
+        f[a] = 0.0;
+      }
+      if (!inside) i0 = 0;   // (never an index from a value that failed the test)
+      base += (int64_t)i0 * stride;
+      stride *= na;
+    }
+  }
+  if (!inside) {
+    for (int c = 0; c < ncomp; ++c) out[p * ncomp + c] = fill;
+    return;
+  }
+  if constexpr (ORDER == 0) {
+    for (int c = 0; c < ncomp; ++c) out[p * ncomp + c] = img[base * ncomp + c];
+  } else {
+    constexpr int NC = 1 << D;
+    double cw[NC];
+    int64_t off[NC];
+    // an axis of one voxel has no second corner: its stencil offset is 0 and f = 0, the corner enters twice with weights 1, 0
+    const int64_t sx = gs.n[0] > 1 ? 1 : 0;
+    const int64_t sy = gs.n[1] > 1 ? gs.n[0] : 0;
+    const int64_t sz = D == 3 && gs.n[2] > 1 ? gs.n[0] * gs.n[1] : 0;
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+      const int bx = k & 1, by = (k >> 1) & 1, bz = (k >> 2) & 1;
+      double wt = by ? f[1] : 1.0 - f[1];
+      if constexpr (D == 3) wt = (bz ? f[2] : 1.0 - f[2]) * wt;
+      cw[k] = wt * (bx ? f[0] : 1.0 - f[0]);
+      off[k] = base + bx * sx + by * sy + bz * sz;
+    }
+    for (int c = 0; c < ncomp; ++c) {
+      double acc = 0.0;
+#pragma unroll
+      for (int k = 0; k < NC; ++k) acc += cw[k] * img[off[k] * ncomp + c];
+      out[p * ncomp + c] = acc;
+    }
+  }
+}
+
 GlSampler& sampler_of(glims_ctx* h, int64_t id, const char* who) {
   if (id < 0 || id >= (int64_t)h->samplers.size() || !h->samplers[(size_t)id])
     throw glims_error(GLIMS_E_USAGE, std::string(who) + ": unknown sampler id " + std::to_string(id));
@@ -802,7 +971,9 @@ void build_transpose(glims_ctx* h, GlSampler& s, dvec<uint32_t>& k_in, dvec<int3
 }
 
 template <int D>
-void create_t(glims_ctx* h, GlSampler& s, const double* xyz_host, const GridSpec& gs) {
+// coords: the [n_nodes][D] node coordinates (internal numbering) the points are located in -- the mesh's own, or a deformed
+// sampler's transient x = X + scale u
+void create_t(glims_ctx* h, GlSampler& s, const double* xyz_host, const GridSpec& gs, const double* coords) {
   constexpr int NV = D + 1;
   const int64_t n = s.n, ne = h->n_cells;
   hipStream_t st = h->st;
@@ -830,13 +1001,13 @@ void create_t(glims_ctx* h, GlSampler& s, const double* xyz_host, const GridSpec
     GL_CHECK_LAUNCH();
     int nb_host = 0;
     if (s.is_grid) {
-      hipLaunchKernelGGL(k_claim_grid<D>, dim3(grid_of(ne)), dim3(256), 0, st, ne, cell_nodes, h->xyz_new.p, new2old, gs,
+      hipLaunchKernelGGL(k_claim_grid<D>, dim3(grid_of(ne)), dim3(256), 0, st, ne, cell_nodes, coords, new2old, gs,
                          s.cell.p, big.p, n_big.p);
       GL_CHECK_LAUNCH();
       GL_HIP(hipMemcpyAsync(&nb_host, n_big.p, sizeof(int), hipMemcpyDeviceToHost, st));
       GL_HIP(hipStreamSynchronize(st));
       if (nb_host > 0) {
-        hipLaunchKernelGGL(k_claim_grid_big<D>, dim3(nb_host), dim3(256), 0, st, nb_host, big.p, cell_nodes, h->xyz_new.p,
+        hipLaunchKernelGGL(k_claim_grid_big<D>, dim3(nb_host), dim3(256), 0, st, nb_host, big.p, cell_nodes, coords,
                            new2old, gs, s.cell.p);
         GL_CHECK_LAUNCH();
       }
@@ -896,14 +1067,14 @@ void create_t(glims_ctx* h, GlSampler& s, const double* xyz_host, const GridSpec
         gl_offsets_of_sorted_keys(h, k_out.p, n, total + 1, bin_ptr.p);   // bin_ptr[total]: where the points outside start
         hipLaunchKernelGGL(k_gather_points<D>, dim3(grid_of(n)), dim3(256), 0, st, n, pid.p, d_pts.p, pts_sorted.p);
         GL_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_claim_points<D>, dim3(grid_of(ne)), dim3(256), 0, st, ne, cell_nodes, h->xyz_new.p, new2old, bs,
+        hipLaunchKernelGGL(k_claim_points<D>, dim3(grid_of(ne)), dim3(256), 0, st, ne, cell_nodes, coords, new2old, bs,
                            bin_ptr.p, pts_sorted.p, pid.p, s.cell.p, big.p, n_big.p);
         GL_CHECK_LAUNCH();
         GL_HIP(hipMemcpyAsync(&nb_host, n_big.p, sizeof(int), hipMemcpyDeviceToHost, st));
         GL_HIP(hipStreamSynchronize(st));
         if (nb_host > 0) {
           hipLaunchKernelGGL(k_claim_points_big<D>, dim3(nb_host), dim3(256), 0, st, nb_host, big.p, cell_nodes,
-                             h->xyz_new.p, new2old, bs, bin_ptr.p, pts_sorted.p, pid.p, s.cell.p);
+                             coords, new2old, bs, bin_ptr.p, pts_sorted.p, pid.p, s.cell.p);
           GL_CHECK_LAUNCH();
         }
         GL_HIP(hipStreamSynchronize(st));   // the sort buffers go out of scope
@@ -932,7 +1103,7 @@ void create_t(glims_ctx* h, GlSampler& s, const double* xyz_host, const GridSpec
     v_in.alloc((size_t)n);
   }
   hipLaunchKernelGGL(k_weights<D>, dim3(grid_of(n)), dim3(256), 0, st, n, ne, s.is_grid ? nullptr : d_pts.p, gs, cell_nodes,
-                     h->xyz_new.p, c_old2new.p, s.cell.p, s.node.p, s.w.p, k_in.p, v_in.p, d_found.p);
+                     coords, c_old2new.p, s.cell.p, s.node.p, s.w.p, k_in.p, v_in.p, d_found.p);
   GL_CHECK_LAUNCH();
   unsigned long long nf = 0;
   GL_HIP(hipMemcpyAsync(&nf, d_found.p, sizeof(nf), hipMemcpyDeviceToHost, st));
@@ -960,10 +1131,11 @@ void launch_sample(glims_ctx* h, GlSampler& s, int ncomp, const double* f, doubl
 
 }  // namespace
 
-int64_t gl_sampler_create(glims_ctx* h, int64_t n, const double* xyz, const double* origin, const double* spacing,
-                          const int64_t* size) {
+namespace {
+// The creators' checks of their points (every creator refuses the same things, before anything is allocated); returns n.
+int64_t check_points(glims_ctx* h, int64_t n, const double* xyz, const double* origin, const double* spacing,
+                     const int64_t* size, GridSpec& gs) {
   const int D = h->dim;
-  GridSpec gs;
   for (int a = 0; a < 3; ++a) {
     gs.o[a] = 0.0;
     gs.s[a] = 1.0;
@@ -988,19 +1160,185 @@ int64_t gl_sampler_create(glims_ctx* h, int64_t n, const double* xyz, const doub
   GL_REQUIRE(h->xyz_new.n == (size_t)h->n_nodes * D, "mesh coordinates missing");
   GL_REQUIRE(h->world > 1 || h->n_own == h->n_nodes,
              "glims_sampler_create: a handle with ghost nodes needs its halo plan and transport first");
+  return n;
+}
+
+// locates the points in the mesh whose nodes sit at `coords`; the caller owns the sampler until it enters h->samplers
+GlSampler* create_on(glims_ctx* h, int64_t n, const double* xyz, const GridSpec& gs, const double* coords) {
   auto* s = new GlSampler();
   try {
     s->n = n;
     s->is_grid = !xyz;
-    if (D == 2) create_t<2>(h, *s, xyz, gs);
-    else create_t<3>(h, *s, xyz, gs);
+    if (h->dim == 2) create_t<2>(h, *s, xyz, gs, coords);
+    else create_t<3>(h, *s, xyz, gs, coords);
   } catch (...) {
     (void)hipStreamSynchronize(h->st);
     delete s;
     throw;
   }
-  h->samplers.push_back(s);
+  return s;
+}
+
+// n_inverted and min_ratio of a deformed sampler: one pass over the cells, then one block over the per-block minima
+template <int D>
+void deformation_stats(glims_ctx* h, GlSampler& s, const double* y) {
+  const int64_t ne = h->n_cells;
+  if (ne == 0) return;
+  const unsigned nb = grid_of(ne);
+  dvec<double> part;
+  dvec<unsigned long long> d_bad;
+  part.alloc((size_t)nb + 1);
+  d_bad.alloc_zero(1, h->st);
+  hipLaunchKernelGGL(k_deform_cells<D>, dim3(nb), dim3(256), 0, h->st, ne, gl_ensure_cell_nodes(h), h->xyz_new.p, y, part.p,
+                     d_bad.p);
+  GL_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_deform_min, dim3(1), dim3(1024), 0, h->st, (int64_t)nb, part.p, part.p + nb);
+  GL_CHECK_LAUNCH();
+  unsigned long long bad = 0;
+  double mn = 1.0;
+  GL_HIP(hipMemcpyAsync(&bad, d_bad.p, sizeof(bad), hipMemcpyDeviceToHost, h->st));
+  GL_HIP(hipMemcpyAsync(&mn, part.p + nb, sizeof(mn), hipMemcpyDeviceToHost, h->st));
+  GL_HIP(hipStreamSynchronize(h->st));
+  s.n_inverted = (int64_t)bad;
+  s.min_ratio = mn;
+}
+}  // namespace
+
+int64_t gl_sampler_create(glims_ctx* h, int64_t n, const double* xyz, const double* origin, const double* spacing,
+                          const int64_t* size) {
+  GridSpec gs;
+  n = check_points(h, n, xyz, origin, spacing, size, gs);
+  h->samplers.push_back(create_on(h, n, xyz, gs, h->xyz_new.p));
   return (int64_t)h->samplers.size() - 1;
+}
+
+int gl_sampler_create_deformed(glims_ctx* h, int64_t n, const double* xyz, const double* origin, const double* spacing,
+                               const int64_t* size, int64_t u_source, const double* u_host, double scale, int64_t* id) {
+  const char* who = "glims_sampler_create_deformed";
+  // ---- refusals: nothing is allocated or changed before the last of them ----
+  GL_REQUIRE(h->world <= 1, std::string(who) + ": not available on a partitioned handle (world > 1)");
+  GL_REQUIRE(std::isfinite(scale), std::string(who) + ": scale is not finite");
+  if (u_source == GLIMS_DERIVE_HOST) {
+    GL_REQUIRE(u_host, std::string(who) + ": GLIMS_DERIVE_HOST needs u_host (null pointer)");
+  } else {
+    GL_REQUIRE(h->is_setup && h->have_mech && h->U.p,
+               std::string(who) + ": a snapshot or GLIMS_DERIVE_CURRENT source needs the displacement: "
+                                  "glims_setup(with_mechanics=1) first");
+    if (u_source == GLIMS_DERIVE_CURRENT) {
+      GL_REQUIRE(h->have_state, std::string(who) + ": GLIMS_DERIVE_CURRENT before glims_set_state");
+    } else {
+      GL_REQUIRE(u_source >= 0 && u_source < (int64_t)h->snapshots.size() && h->snapshots[(size_t)u_source],
+                 std::string(who) + ": unknown snapshot id " + std::to_string(u_source));
+      GL_REQUIRE(h->have_state, std::string(who) + ": a snapshot source before glims_set_state");
+    }
+  }
+  GridSpec gs;
+  n = check_points(h, n, xyz, origin, spacing, size, gs);
+  const int D = h->dim;
+  const int64_t nn = h->n_nodes;
+  need_memory(who, (size_t)nn * D * sizeof(double) * (u_source == GLIMS_DERIVE_HOST ? 2 : 1) + (1u << 20));
+  // ---- the displacement ----
+  int status = GLIMS_OK;
+  dvec<double> u_up;
+  const double* u = h->U.p;
+  if (u_source == GLIMS_DERIVE_HOST) {
+    u_up.alloc((size_t)std::max<int64_t>(1, nn * D));
+    gl_to_device_perm(h, u_host, u_up.p, D);   // the permuting upload: neither c nor U is touched
+    u = u_up.p;
+  } else if (u_source != GLIMS_DERIVE_CURRENT && h->derive.u_snapshot != u_source) {
+    // as glims_snapshot_mechanics solves it; glims_derive of the same snapshot finds U in place and the other way round
+    h->derive.forget_u();
+    status = gl_solve_mechanics(h, h->snapshots[(size_t)u_source]->p);
+    h->derive.n_elastic_solves++;
+    if (status == GLIMS_OK) h->derive.u_snapshot = u_source;
+    if (status == GLIMS_NAN) return status;
+  }
+  // ---- y = X + scale u, its cells' determinants, the location ----
+  dvec<double> y;
+  y.alloc((size_t)std::max<int64_t>(1, nn * D));
+  if (nn > 0) {
+    if (D == 2) hipLaunchKernelGGL(k_deform_xyz<2>, dim3(grid_of(nn)), dim3(256), 0, h->st, nn, h->xyz_new.p, u, scale, y.p);
+    else hipLaunchKernelGGL(k_deform_xyz<3>, dim3(grid_of(nn)), dim3(256), 0, h->st, nn, h->xyz_new.p, u, scale, y.p);
+    GL_CHECK_LAUNCH();
+  }
+  GlSampler* s = create_on(h, n, xyz, gs, y.p);
+  try {
+    s->deformed = true;
+    if (D == 2) deformation_stats<2>(h, *s, y.p);
+    else deformation_stats<3>(h, *s, y.p);
+  } catch (...) {
+    (void)hipStreamSynchronize(h->st);
+    delete s;
+    throw;
+  }
+  GL_HIP(hipStreamSynchronize(h->st));   // y and the uploaded u go out of scope
+  h->samplers.push_back(s);
+  *id = (int64_t)h->samplers.size() - 1;
+  return status;
+}
+
+void gl_sampler_deformation_info(glims_ctx* h, int64_t id, int64_t out[2], double* min_ratio) {
+  GlSampler& s = sampler_of(h, id, "glims_sampler_deformation_info");
+  if (out) {
+    out[0] = s.deformed ? 1 : 0;
+    out[1] = s.deformed ? s.n_inverted : 0;
+  }
+  if (min_ratio) *min_ratio = s.deformed ? s.min_ratio : 1.0;
+}
+
+void gl_sampler_warp(glims_ctx* h, int64_t id, const double* image, const double* origin, const double* spacing,
+                     const int64_t* size, int ncomp, int order, double fill, double* out) {
+  const char* who = "glims_sampler_warp";
+  GlSampler& s = sampler_of(h, id, who);
+  GL_REQUIRE(h->world <= 1, std::string(who) + ": not available on a partitioned handle (world > 1)");
+  GL_REQUIRE(order == 0 || order == 1, std::string(who) + ": order = " + std::to_string(order) + " is neither 0 (nearest) nor 1 (linear)");
+  GL_REQUIRE(ncomp >= 1 && ncomp <= GLIMS_SAMPLE_MAX_COMP, std::string(who) + ": ncomp = " + std::to_string(ncomp) + " outside 1 .. 8");
+  GL_REQUIRE(image, std::string(who) + ": null image");
+  GL_REQUIRE(origin && spacing && size, std::string(who) + ": null origin, spacing or size");
+  GL_REQUIRE(out || s.n == 0, std::string(who) + ": null output");
+  const int D = h->dim;
+  GridSpec gs;
+  for (int a = 0; a < 3; ++a) {
+    gs.o[a] = 0.0;
+    gs.s[a] = 1.0;
+    gs.n[a] = 1;
+  }
+  double nvox_d = 1.0;
+  size_t nvox = 1;
+  for (int a = 0; a < D; ++a) {
+    GL_REQUIRE(size[a] > 0, std::string(who) + ": size[" + std::to_string(a) + "] = " + std::to_string(size[a]) + " is not positive");
+    GL_REQUIRE(spacing[a] > 0.0 && std::isfinite(spacing[a]), std::string(who) + ": spacing[" + std::to_string(a) + "] is not positive");
+    GL_REQUIRE(std::isfinite(origin[a]), std::string(who) + ": origin is not finite");
+    gs.o[a] = origin[a];
+    gs.s[a] = spacing[a];
+    gs.n[a] = size[a];
+    nvox_d *= (double)size[a];
+    GL_REQUIRE(nvox_d < 1099511627776.0, std::string(who) + ": more than 2^40 voxels");
+    nvox *= (size_t)size[a];
+  }
+  if (s.n == 0) return;
+  const size_t ni = nvox * (size_t)ncomp, no = (size_t)s.n * ncomp;
+  if (s.img.n < ni || s.out.n < no) {
+    need_memory(who, ((s.img.n < ni ? ni : 0) + (s.out.n < no ? no : 0)) * sizeof(double));
+    if (s.img.n < ni) s.img.alloc(ni);
+    if (s.out.n < no) s.out.alloc(no);
+  }
+  GL_HIP(hipMemcpyAsync(s.img.p, image, ni * sizeof(double), hipMemcpyHostToDevice, h->st));
+  const dim3 g(grid_of(s.n)), b(256);
+#define GL_WARP_CASE(NV, DD, ORD)                                                                                       \
+  hipLaunchKernelGGL((k_warp<NV, DD, ORD>), g, b, 0, h->st, s.n, ncomp, s.cell.p, s.node.p, s.w.p, h->xyz_new.p, gs, \
+                     s.img.p, fill, s.out.p)
+  if (D == 2) {
+    if (order == 1) GL_WARP_CASE(3, 2, 1);
+    else GL_WARP_CASE(3, 2, 0);
+  } else {
+    if (order == 1) GL_WARP_CASE(4, 3, 1);
+    else GL_WARP_CASE(4, 3, 0);
+  }
+#undef GL_WARP_CASE
+  GL_CHECK_LAUNCH();
+  GL_HIP(hipMemcpyAsync(out, s.out.p, no * sizeof(double), hipMemcpyDeviceToHost, h->st));
+  GL_HIP(hipStreamSynchronize(h->st));
 }
 
 void gl_sampler_info(glims_ctx* h, int64_t id, int64_t* n_points, int64_t* n_found) {
@@ -1058,6 +1396,10 @@ void gl_sampler_apply(glims_ctx* h, int64_t id, int field, int64_t snapshot, con
     }
     case GLIMS_FIELD_DERIVED:
       f = gl_derive_sampled(h, ncomp);
+      break;
+    case GLIMS_FIELD_XYZ:   // the REFERENCE coordinates: on a deformed sampler the back map X(x_p)
+      GL_REQUIRE(ncomp == h->dim, "glims_sampler_apply: GLIMS_FIELD_XYZ has dim components");
+      f = h->xyz_new.p;
       break;
     default:
       GL_REQUIRE(false, "glims_sampler_apply: unknown field " + std::to_string(field));
@@ -1288,6 +1630,8 @@ void gl_image_terms_set(glims_ctx* h, int n, const glims_image_misfit* terms) {
     GL_REQUIRE(h->world <= 1 || s.resolved, tk + ": not available on a partitioned handle before glims_sampler_resolve of its "
                                                  "sampler (glims_sampler_apply_t, the transpose the gradient needs, is "
                                                  "refused until then)");
+    GL_REQUIRE(!s.deformed, tk + ": its sampler is a deformed one: its points move with the state through u, the derivative of "
+                               "the location is not built and a frozen-location gradient would be inexact");
     GL_REQUIRE(t.kind == GLIMS_MISFIT_IMG_L2 || t.kind == GLIMS_MISFIT_IMG_THRESH, tk + ": unknown kind");
     GL_REQUIRE(t.kind != GLIMS_MISFIT_IMG_THRESH || (t.smooth > 0.0 && std::isfinite(t.smooth) && std::isfinite(t.level)),
                tk + ": a threshold term needs smooth > 0 and a finite level");

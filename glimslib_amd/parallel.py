@@ -428,11 +428,19 @@ class DistributedHandle:
         return sid, n, int(sum(parts))
 
     # -- samplers (collective: every rank passes the same points) --------------------------------------------------------
-    def sampler_points(self, xyz):
+    def sampler_points(self, xyz, deformed_by=None, scale=1.0):
+        self._no_deformed(deformed_by)
         return DistributedSampler(self, self.h.sampler_points(xyz))
 
-    def sampler_grid(self, origin, spacing, size):
+    def sampler_grid(self, origin, spacing, size, deformed_by=None, scale=1.0):
+        self._no_deformed(deformed_by)
         return DistributedSampler(self, self.h.sampler_grid(origin, spacing, size))
+
+    @staticmethod
+    def _no_deformed(deformed_by):
+        if deformed_by is not None:
+            raise NotImplementedError("deformed-configuration samplers are not available on partitioned runs (the points "
+                                      "would have to be located in every rank's displaced cells); run on one GPU")
 
     # -- global <-> local -----------------------------------------------------------------------------------------
     def _local(self, v, bs=1):

@@ -305,6 +305,46 @@ class TumorGrowth(FenicsSimulation):
             cache[1][key] = h.sampler_grid(*key)
         return key, cache[1][key]
 
+    def _deformed_grid_sampler(self, recording_step, origin, spacing, size):
+        """(key, sampler) of a voxel grid located in the mesh DISPLACED by the displacement of `recording_step`.  One deformed
+        sampler is kept per grid: asking for another step closes it (a 128^3 sampler is about 110 MB of device memory).  A step
+        recorded on the device is the snapshot source (one elastic solve, shared with the derived fields of that step); host-
+        resident results hand over the step's displacement array."""
+        h = self._backend
+        if h is None:
+            raise RuntimeError("a deformed image needs a run() first (the grid is located in the run's displaced device mesh)")
+        if not isinstance(h, _backend.Handle):
+            raise NotImplementedError("deformed-configuration images are not available on partitioned runs (the grid would "
+                                      "have to be located in every rank's displaced cells); run on one GPU")
+        obs = self.results.get_result(recording_step)
+        if obs is None:
+            raise KeyError("no result for recording step %r" % (recording_step,))
+        key = (tuple(float(v) for v in origin), tuple(float(v) for v in spacing), tuple(int(v) for v in size))
+        cache = getattr(self, '_deformed_samplers', None)
+        if cache is None or cache[0] is not h or cache[1] is not self.results:
+            if cache is not None and cache[0] is h:
+                for _, old in cache[2].values():
+                    old.close()
+            cache = self._deformed_samplers = (h, self.results, {})
+        ent = cache[2].get(key)
+        if ent is not None and ent[0] == recording_step:
+            return key, ent[1]
+        if ent is not None:
+            ent[1].close()
+            del cache[2][key]
+        field = obs.get_field()
+        if isinstance(field, DeviceSnapshotFunction) and self.solver.mechanics:
+            sampler = h.sampler_grid(*key, deformed_by=int(field.snapshot_id))
+            self.solver._mech_current = False           # the device's displacement buffer now belongs to this step
+        else:
+            sampler = h.sampler_grid(*key, deformed_by=np.asarray(field.components[0], dtype=np.float64))
+        if sampler.n_inverted > 0:
+            self.logger.warning("    - recording step %r: the displaced mesh has %d inverted cell(s) (smallest det(I + grad u) = "
+                                "%.3e); where it overlaps itself the smallest cell index wins"
+                                % (recording_step, sampler.n_inverted, sampler.min_jacobian))
+        cache[2][key] = (recording_step, sampler)
+        return key, sampler
+
     def image_term(self, step, image, kind='img_thresh', level=0.0, smooth=1.0, weight=1.0, mask=None,
                    volume_weighted=True):
         """
@@ -342,7 +382,8 @@ class TumorGrowth(FenicsSimulation):
     DERIVED_IMAGES = ('pressure', 'van_mises_stress', 'total_jacobian', 'growth_induced_jacobian',
                       'concentration_deformed_config', 'log_growth', 'displacement_norm', 'strain_tensor', 'stress_tensor')
 
-    def sample_image(self, subspace_name, recording_step, like=None, origin=None, spacing=None, size=None, fill=np.nan):
+    def sample_image(self, subspace_name, recording_step, like=None, origin=None, spacing=None, size=None, fill=np.nan,
+                     deformed=False):
         """
         The recorded field `subspace_name` ('concentration' | 'displacement') of `recording_step`, or one of its derived
         fields (DERIVED_IMAGES: the PostProcess fields; tensors as their symmetric components xx, yy, (zz,) xy, (xz, yz) in
@@ -354,6 +395,11 @@ class TumorGrowth(FenicsSimulation):
         mesh once per simulation and grid, and serves every recording step.  With run(results_on_device=True) the
         concentration goes from its device snapshot to the image without a nodal copy on the host; the displacement through
         the lazy elastic solve of the results.  Partitioned runs: collective, every rank returns the same image.
+
+        deformed=True: the image in the DEFORMED configuration x = X + u(X), what an MR image of the grown tumour shows -- the
+        grid is located in the mesh displaced by that step's displacement, so a voxel at x holds the field at the material
+        point X(x) that sits there.  One deformed sampler is cached per grid and replaced when another step is asked for;
+        a warning is logged when the displaced mesh has inverted cells.  Not available on partitioned runs.
         """
         from ..utils.data_io import _grid_image
         if like is not None:
@@ -363,7 +409,10 @@ class TumorGrowth(FenicsSimulation):
         h = self._backend
         if h is None:
             raise RuntimeError("sample_image needs a run() first")
-        key, sampler = self._grid_sampler(origin, spacing, size)
+        if deformed:
+            key, sampler = self._deformed_grid_sampler(recording_step, origin, spacing, size)
+        else:
+            key, sampler = self._grid_sampler(origin, spacing, size)
         if subspace_name in self.DERIVED_IMAGES:
             if self.results.get_result(recording_step) is None:
                 raise KeyError("no result for recording step %r" % (recording_step,))
@@ -381,6 +430,85 @@ class TumorGrowth(FenicsSimulation):
         else:
             out = sampler.apply(np.asarray(field.components[sid]), fill=fill)
         return _grid_image(out, key[2], key[0], key[1])
+
+    @staticmethod
+    def _grid_of(like, origin, spacing, size, who):
+        if like is not None:
+            origin, spacing, size = like.GetOrigin(), like.GetSpacing(), like.GetSize()
+        if origin is None or spacing is None or size is None:
+            raise ValueError("%s needs `like` or origin, spacing and size" % who)
+        return origin, spacing, size
+
+    def label_image(self, recording_step=None, like=None, origin=None, spacing=None, size=None, deformed=False, fill=0):
+        """
+        The cell labels (tissue ids) at the voxels of a grid -> Image: the reference's `label_map` image
+        (vtk_utils.resample_to_image of the result mesh, image_based_optimization.py:895-911).  A voxel holds the label of
+        the cell the sampler found it in, `fill` outside the mesh.  With deformed=True and a recording step the grid is
+        located in the mesh displaced by that step's displacement (the deformed label map); without a step it is the
+        undeformed one.  The array is int32 for an integer `fill`, float64 otherwise.
+        """
+        from ..utils.data_io import _grid_image
+        origin, spacing, size = self._grid_of(like, origin, spacing, size, "label_image")
+        if self._backend is None:
+            raise RuntimeError("label_image needs a run() first")
+        if deformed and recording_step is not None:
+            key, sampler = self._deformed_grid_sampler(recording_step, origin, spacing, size)
+        else:
+            key, sampler = self._grid_sampler(origin, spacing, size)
+        cells = np.asarray(sampler.cells)
+        labels = np.asarray(self._labels())
+        integral = float(fill) == int(fill) if np.isfinite(fill) else False
+        out = np.full(len(cells), fill, dtype=np.int32 if integral else np.float64)
+        found = cells >= 0
+        out[found] = labels[cells[found]]
+        return _grid_image(out, key[2], key[0], key[1])
+
+    def warp_image(self, image, recording_step, like=None, order='linear', fill=np.nan):
+        """
+        `image` (utils.data_io.Image, scalar or vector) as the deformed anatomy of `recording_step` would show it, on the grid
+        of `like` (default: the image's own):  out(x) = image(X(x)),  X(x) the reference position of the material point that
+        the step's displacement carries to x -- the exact inverse of the P1 map X -> X + u_h(X), evaluated on the device
+        without building a displacement image.  What the reference does with ANTs and the negated displacement image
+        (image_based_optimization.py:927-929).  order: 'linear' | 'nearest'; voxels outside the displaced mesh, and voxels
+        whose X falls outside `image`, hold `fill`.
+        """
+        from ..utils.data_io import _grid_image
+        grid = like if like is not None else image
+        key, sampler = self._deformed_grid_sampler(recording_step, grid.GetOrigin(), grid.GetSpacing(), grid.GetSize())
+        out = sampler.warp(np.asarray(image.array, dtype=np.float64), image.GetOrigin(), image.GetSpacing(), order=order,
+                           fill=fill)
+        return _grid_image(out, key[2], key[0], key[1])
+
+    def create_deformed_images(self, recording_step, ref_image, output_dir=None):
+        """
+        The images of the reference's `_create_deformed_image` (image_based_optimization.py:876-941) on the grid of
+        `ref_image`, as a dict of Images; written as <name>.mha into `output_dir` when one is given:
+          label_img_orig        the cell labels on the undeformed mesh
+          labels_warped         the cell labels on the mesh displaced by the step's displacement
+          displacement_img      u(X) on the reference frame (NaN outside the mesh)
+          displacement_img_inv  X(x) - x on the deformed frame (NaN outside the displaced mesh): the exact inverse of the P1
+                                map.  (Deviation: the reference writes -u(X) on the REFERENCE frame, the first-order
+                                approximation of this field that ANTs then applies.)
+          image_warped          ref_image(X(x)), d-linear: the reference image as the deformed anatomy would show it
+        """
+        from ..utils.data_io import Image
+        o, sp, sz = ref_image.GetOrigin(), ref_image.GetSpacing(), ref_image.GetSize()
+        self._deformed_grid_sampler(recording_step, o, sp, sz)      # (the refusals first: no run yet, a partitioned run)
+        out = {'label_img_orig': self.label_image(like=ref_image),
+               'labels_warped': self.label_image(recording_step, like=ref_image, deformed=True),
+               'displacement_img': self.sample_image('displacement', recording_step, like=ref_image)}
+        key, sampler = self._deformed_grid_sampler(recording_step, o, sp, sz)
+        d = len(sz)
+        ax = [float(o[a]) + np.arange(int(sz[a]), dtype=np.float64) * float(sp[a]) for a in range(d)]
+        grid = np.stack(np.meshgrid(*ax[::-1], indexing='ij')[::-1], axis=-1)          # [z,] y, x, component
+        X = sampler.back_map().reshape(grid.shape)
+        out['displacement_img_inv'] = Image(X - grid, o, sp, is_vector=True)
+        out['image_warped'] = self.warp_image(ref_image, recording_step)
+        if output_dir is not None:
+            os.makedirs(output_dir, exist_ok=True)
+            for name, img in out.items():
+                img.write(os.path.join(output_dir, name + '.mha'))
+        return out
 
     # -- discrete adjoint (the backward half of the reference's adjoint entry points) -----------------------------
     def _adjoint_raw(self, terms, need_dD=True, elastic=False):

@@ -655,7 +655,8 @@ int glims_sampler_get(glims_ctx* h, int64_t id, int32_t* cell, double* w);
 /* out[n][ncomp] = P f (ncomp 1..8; GLIMS_FIELD_C / _SNAPSHOT_C: 1, GLIMS_FIELD_U: dim); points outside the mesh get `fill`
  * (NaN is what the reference's images hold there).  nodal is read for GLIMS_FIELD_HOST only, snapshot for _SNAPSHOT_C only.
  * GLIMS_FIELD_DERIVED (defined with glims_derive below): the result of the last glims_derive, ncomp = its component count (1, or
- * d(d+1)/2 for a tensor); GLIMS_E_USAGE with nothing derived or another ncomp. */
+ * d(d+1)/2 for a tensor); GLIMS_E_USAGE with nothing derived or another ncomp.  GLIMS_FIELD_XYZ (defined with the deformed
+ * samplers below): the mesh's reference coordinates, ncomp = dim. */
 int glims_sampler_apply(glims_ctx* h, int64_t id, int field, int64_t snapshot, const double* nodal, int ncomp, double fill,
                         double* out);
 /* g[n_nodes][ncomp] = P^T r, r[n][ncomp], caller's node order; values of r at points outside the mesh are not read into any
@@ -678,6 +679,54 @@ int glims_sampler_resolve(glims_ctx* h, int64_t id, const int64_t* cell_gid);
 /* counted[n_points] (0/1); world <= 1 or unresolved: 1 where found */
 int glims_sampler_get_counted(glims_ctx* h, int64_t id, uint8_t* counted);
 int glims_sampler_destroy(glims_ctx* h, int64_t id);   /* glims_destroy releases what is left */
+
+/* ---- deformed-configuration samplers and image warping ----------------------------------------------------------------------
+ * The samplers above live in the REFERENCE configuration X.  An MR image shows the DEFORMED configuration x = X + u(X); the
+ * reference's optimisation workflow builds its targets there by warping the result mesh with vtk and pushing images through ANTs
+ * (image_based_optimization.py:876-941 _create_deformed_image, :264-292).  A deformed sampler locates its points in the mesh
+ * whose node a sits at
+ *     y_a = fl(X_a + fl(scale * u_a))            (two roundings, never contracted: numpy's  X + scale * u),
+ * with the rules of the samplers above applied to those coordinates: acceptance with GLIMS_SAMPLE_EPS, the smallest caller
+ * cell index wins (also where a FOLDED mesh overlaps itself), the winner's barycentric weights.  With scale = 0 it equals the
+ * undeformed sampler bit for bit.  Since it keeps only (cell, nodes, weights), glims_sampler_apply / _apply_t / _get / _info /
+ * _destroy and GLIMS_FIELD_DERIVED work on it unchanged: P f is f at the material point that sits at x_p.
+ * GLIMS_FIELD_XYZ (every sampler) applies P to the mesh's reference coordinates: on a deformed sampler the back map X(x_p), the
+ * exact inverse of the P1 map X -> X + scale u_h(X) where that map is one-to-one; on the others x_p itself.
+ *
+ * u_source (the constants are defined with glims_derive below): an id of glims_snapshot_save -- its displacement is solved as
+ * glims_snapshot_mechanics solves it (U is written, the solve enters the elastic solve history), unless U already belongs to that
+ * snapshot: the same memory glims_derive uses, so a derive and a deformed sampler of one step solve once between them, in either
+ * order (glims_derive_info's elastic solves count both) --; GLIMS_DERIVE_CURRENT: U as it stands; GLIMS_DERIVE_HOST:
+ * u_host[n_nodes*dim], caller's node order (neither c nor U is touched).  CURRENT and HOST change nothing on the handle; in
+ * every case the concentration steps that follow keep the bits of a handle that never made the call.
+ * The sampler is FROZEN: later steps, solves or glims_snapshot_clear do not move it.
+ * Returns the worst status of the elastic solve (GLIMS_OK / GLIMS_NOT_CONVERGED / GLIMS_NAN; the sampler exists for the first
+ * two).  GLIMS_E_USAGE with a reason, before anything is allocated or changed: a partitioned handle (world > 1), a snapshot or
+ * CURRENT source on a handle set up without mechanics, an unknown snapshot, CURRENT before glims_set_state, HOST with a NULL
+ * u_host, a non-finite scale, flags != 0, and everything the undeformed creators refuse.
+ * glims_adjoint_image_terms refuses a deformed sampler: its points depend on the state through u, the derivative of the location
+ * is not built, and a frozen-location gradient would be silently inexact. */
+#define GLIMS_FIELD_XYZ 5   /* glims_sampler_apply: the mesh's REFERENCE coordinates (ncomp = dim) -> the back map X(x_p) */
+int glims_sampler_create_grid_deformed(glims_ctx* h, const double* origin, const double* spacing, const int64_t* size,
+                                       int64_t u_source, const double* u_host, double scale, int flags, int64_t* id);
+int glims_sampler_create_points_deformed(glims_ctx* h, int64_t n, const double* xyz, int64_t u_source, const double* u_host,
+                                         double scale, int flags, int64_t* id);
+/* out[0] = 1 for a deformed sampler (0: the others, out[1] = 0, *min_ratio = 1); out[1] = number of cells whose ratio
+ * det(E_deformed) / det(E_reference) is not > 0 (folded, flat or non-finite); *min_ratio = the smallest ratio
+ * (= min_T det(I + scale grad u_h)).  Either output may be NULL. */
+int glims_sampler_deformation_info(glims_ctx* h, int64_t id, int64_t out[2], double* min_ratio);
+/* out[n][ncomp] = image(X(x_p)): the source image (array [z][y][x][ncomp], voxel centres origin + index * spacing, size points
+ * per axis) evaluated at the back-mapped position X = sum_a w_a X_a of every found point.  Per axis t = (X - o) / s.
+ *   order 1 (d-linear): the point is inside the source iff 0 <= t <= n - 1 on every axis; i0 = min(floor(t), n - 2) (n = 1:
+ *           i0 = 0 and f = 0), f = t - i0; the value is the sum over the 2^d corners of the product of f or 1 - f, times the
+ *           voxel -- plain IEEE arithmetic, so a NaN voxel of the stencil propagates.
+ *   order 0 (nearest voxel): inside iff -0.5 <= t < n - 0.5, the index is floor(t + 0.5).
+ * Points outside the mesh, and points whose X lies outside the source image, get `fill`.  ncomp is 1..8.  Works on every
+ * sampler of a single-rank handle (on an undeformed one X(x_p) = x_p: plain resampling inside the mesh).  The image is
+ * uploaded per call into the sampler's staging; the same arguments give the same bits.  GLIMS_E_USAGE: order outside {0, 1},
+ * ncomp outside 1..8, a NULL image, a non-positive size or spacing, a partitioned handle. */
+int glims_sampler_warp(glims_ctx* h, int64_t id, const double* image, const double* origin, const double* spacing,
+                       const int64_t* size, int ncomp, int order, double fill, double* out);
 
 /* ---- image-space misfit terms: a voxel image or point set as an observation of the recorded trajectory --------------------
  * The reference compares the simulated concentration with thresholded T1 / T2 segmentations
