@@ -330,6 +330,7 @@ __global__ void k_perm(int64_t n, int bs, const int32_t* __restrict__ old2new, c
 // device scratch of one gradient call (released on return)
 struct AdjWork {
   dvec<double> lam, lam_next, rhs, g, r, u, w, p, s, e, hp, Me, tmp, qcell, part, sums, esums, vA, dinv, stage;
+  dvec<uint8_t> lin;   // stays empty: the sweeps of the adjoint (which write wk.vA, ForwardGuard) keep no exact-linearity flags
   dvec<double> uk, murhs, mu, mr, mu_, mw, mp, ms, mKx;
   std::vector<std::unique_ptr<dvec<double>>> targets;
 };
@@ -356,6 +357,9 @@ struct ForwardGuard {
     h->opt.time_kernels = 0;
     std::swap(h->vA.p, wk.vA.p);
     std::swap(h->vA.n, wk.vA.n);
+    // (the exact-linearity flags describe the values of ONE buffer: the sweeps in here write wk.vA and so wk.lin)
+    std::swap(h->lin.p, wk.lin.p);
+    std::swap(h->lin.n, wk.lin.n);
     std::swap(h->dinv.p, wk.dinv.p);
     std::swap(h->dinv.n, wk.dinv.n);
   }
@@ -363,6 +367,8 @@ struct ForwardGuard {
     (void)hipStreamSynchronize(h->st);
     std::swap(h->vA.p, wk.vA.p);
     std::swap(h->vA.n, wk.vA.n);
+    std::swap(h->lin.p, wk.lin.p);
+    std::swap(h->lin.n, wk.lin.n);
     std::swap(h->dinv.p, wk.dinv.p);
     std::swap(h->dinv.n, wk.dinv.n);
     h->jac32 = jac32;

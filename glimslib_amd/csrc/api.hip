@@ -608,11 +608,18 @@ int glims_solve_mechanics(glims_ctx* h) {
 int glims_get_stats(const glims_ctx* h, glims_stats* st) {
   if (!h || !st) return GLIMS_E_USAGE;
   *st = h->stats;
+  int64_t ring = 0;   // (the flags as they are now: a snapshot, not a counter; and the coded passes still in the ring)
+  gl_value_code_counts(h, &st->rd_lin_slices, &ring);
+  st->cheb_coded_passes += ring;
   return GLIMS_OK;
 }
 
 int glims_reset_stats(glims_ctx* h) {
   if (!h) return GLIMS_E_USAGE;
+  try {
+    gl_harvest_coded_passes(h);   // (empties the ring: passes before the reset are not counted after it)
+  } catch (const std::exception&) {
+  }
   glims_stats keep = h->stats;
   std::memset(&h->stats, 0, sizeof(h->stats));
   h->stats.n_rows = keep.n_rows;
@@ -638,6 +645,8 @@ int glims_reset_stats(glims_ctx* h) {
   h->stats.rd_mass_fallback_rows = keep.rd_mass_fallback_rows;
   h->stats.rd_rec_compact_slices = keep.rd_rec_compact_slices;
   h->stats.rd_rec_full_slices = keep.rd_rec_full_slices;
+  h->stats.rd_scode_slices = keep.rd_scode_slices;
+  h->stats.rd_scode_uncoded_slices = keep.rd_scode_uncoded_slices;
   h->tev_used = 0;
   h->stats.steps = keep.steps;   // step counter drives the extrapolated guess; keep it
   return GLIMS_OK;

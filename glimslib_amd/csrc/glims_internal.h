@@ -178,6 +178,10 @@ struct DevPattern {
   dvec<uint8_t> rec_ok;                    // ... per slice: 1 = compact (straight-line slice whose every offset fits), 0 = full
   std::vector<uint8_t> rec_ok_host;        // ... the same on the host (k_corner_weights ran: the classes' record lists are stale)
   bool rec_lists_stale = true;
+  // the coded entries of S for the dot-free pass (value_codes.h; built after every k_assemble_static, kernels.hip): empty = none
+  dvec<uint32_t> scode;                    // per padded entry, SELL layout of vS: column code + value code (dictionary index, delta)
+  dvec<int64_t> sdict;                     // ... per slice: its 32 dictionary bases (bit patterns)
+  dvec<uint8_t> scoded;                    // ... per slice: 1 = every real entry has a code (at most 32 bases), 0 = uncoded
   dvec<uint32_t> cq;                       // [incidence][2] = (re-ordered slot word, weight as float bits): the quadratic-term pass's 8-byte records
   // the mass product from the sweep's incidence loop (k_corner_weights, rd_assemble_s_slice with MB = 1)
   dvec<double> mass_q;                     // per padded row: (d+3) / rho where every cell of the row has the same rho > 0, else 0
@@ -582,6 +586,12 @@ struct glims_ctx {
 
   // scalar operator planes (SELL-64 layout) and block planes
   dvec<double> vM, vS, vA, vKel, vG;
+  // per slice: 1 = the slice of vA holds the bits of vS (A = S + 2 dt N(c) with fl(..) = S there), written by EVERY kernel that
+  // writes the slice of vA (the straight-line sweeps test, every other writer stores 0): the flag cannot outlive the values it
+  // describes.  Empty = the handle streams no value codes (gl_value_codes_wanted) and no kernel writes or reads it.
+  dvec<uint8_t> lin;                       // [n_slices] flags, then [GL_VC_HIT_RING] one byte per launch of the dot-free pass
+                                           // that was given the coded stream: set by the launch if a wave read a coded slice
+  int vc_launches = 0;                     // ... bytes of the ring handed out since it was last emptied
   dvec<float> vA32;                        // Newton Jacobian in single precision (GLIMS_FLAG_FP32_JACOBIAN only)
   bool jac32 = false;
   int spmv_unroll = 8;                     // entries in flight per lane of the scalar SpMV: 8 on lattice meshes, 16 on general ones
@@ -699,6 +709,10 @@ struct GlMassSweep {
   const double* load = nullptr;   // added to the product (may be null)
   double* bw = nullptr;           // the buffer behind b2 (or b)
 };
+bool gl_value_codes_wanted(const glims_ctx* h);   // the dot-free passes of this handle may stream coded slices (value_codes.h)
+constexpr int GL_VC_HIT_RING = 1024;
+void gl_value_code_counts(const glims_ctx* h, int64_t* lin_slices, int64_t* ring_passes);   // (synchronises the stream)
+void gl_harvest_coded_passes(glims_ctx* h);
 bool gl_rd_fusable(glims_ctx* h);   // every slice class has a straight-line sweep kernel, fp64 Jacobian
 bool gl_rd_mass_in_sweep(glims_ctx* h);   // the stepping path forms M c in the sweep (single rank, gl_rd_fusable, flag not set)
 void gl_rd_assemble(glims_ctx* h, const double* c, const double* b, const double* b2, double* r_out, double* r2_out,

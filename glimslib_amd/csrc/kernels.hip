@@ -8,11 +8,14 @@
 // of FEM assembly needs neither atomics nor colouring and is bitwise reproducible.
 #include "glims_internal.h"
 #include "record_words.h"
+#include "value_codes.h"
 #include "sweep_instances.h"
 #include <hip/hip_ext.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
+#include <cstdint>
 #include <type_traits>
 
 namespace {
@@ -338,7 +341,8 @@ __global__ __launch_bounds__(GL_WAVE) void k_rd_assemble(
     const uint8_t* __restrict__ diag_k, const double* __restrict__ vS, AT* __restrict__ vA,
     const double* __restrict__ c, const double* __restrict__ b, const double* __restrict__ b2,
     double* __restrict__ r_out, double* __restrict__ r2_out, double* __restrict__ dinv,
-    const uint8_t* __restrict__ fixed, double two_dt, double* __restrict__ partials, int max_len, int remap) {
+    const uint8_t* __restrict__ fixed, double two_dt, double* __restrict__ partials, int max_len, int remap,
+    uint8_t* __restrict__ lin) {
   // one block (= one wave) per slice of this launch's length class; LDS = 2 * max_len columns of 64 doubles
   extern __shared__ double lds[];
   double* acc = lds;
@@ -482,6 +486,7 @@ __global__ __launch_bounds__(GL_WAVE) void k_rd_assemble(
   if (lane == 0) {
     partials[(size_t)s * 2 + 0] = rr;
     partials[(size_t)s * 2 + 1] = rr2;
+    if (lin) lin[s] = 0;   // (this kernel writes the slice of vA and does not test it: see rd_assemble_s_slice)
   }
 }
 
@@ -731,7 +736,7 @@ __device__ __forceinline__ void rd_assemble_s_slice(
     AT* __restrict__ vA, const double* __restrict__ c, const double* __restrict__ b, const double* __restrict__ b2,
     double* __restrict__ r_out, double* __restrict__ r2_out, double* __restrict__ dinv,
     const uint8_t* __restrict__ fixed, double two_dt, double* __restrict__ partials, int ldscap, int remap,
-    const FgArgs& fg, const MassArgs& ma) {
+    const FgArgs& fg, const MassArgs& ma, uint8_t* __restrict__ lin) {
   double* acc = lds;                             // [ldscap][64], ldscap <= CAP = the longest slice of the launch
   double* cn = lds + (size_t)ldscap * GL_WAVE;   // [ldscap][64]
   const int lane = threadIdx.x;
@@ -842,6 +847,10 @@ __device__ __forceinline__ void rd_assemble_s_slice(
   int rl = 0;
   if constexpr (FG == 1) rl = (int)fg.rlen[row];
   double r = 0.0, dg = 1.0, au = 0.0, un = 0.0;
+  // `lin` (per slice, may be null): 1 = every entry this wave writes to vA has the bits of its entry of S -- the reaction term
+  // vanished in rounding, fl(S + 2 dt N(c)) = S -- so that a pass over the slice may read the coded S instead (value_codes.h).
+  // Invariant: whoever writes a slice of vA writes its flag (the fp32 instances do not write vA at all: they store 0).
+  bool same = std::is_same<AT, double>::value;
 #pragma unroll
   for (int k = 0; k < CAP; ++k) {
     if constexpr (FG == 1) {
@@ -861,6 +870,7 @@ __device__ __forceinline__ void rd_assemble_s_slice(
       const double a_k = (k == dk) ? acc_d : acc[k * GL_WAVE + lane];
       const double Av = S8[k] + two_dt * a_k;
       GL_STREAM(vA, d.base, k) = (AT)Av;
+      same = same && gl_vc_bits(Av) == gl_vc_bits(S8[k]);
       r += 0.5 * (Av + S8[k]) * cn[k * GL_WAVE + lane];
       if (k == dk) dg = Av;
       if constexpr (FG == 1) {
@@ -906,6 +916,10 @@ __device__ __forceinline__ void rd_assemble_s_slice(
     partials[(size_t)s * 2 + 0] = rr;
     partials[(size_t)s * 2 + 1] = rr2;
   }
+  if (lin) {   // (wave-uniform)
+    const bool all_same = __all(same ? 1 : 0) != 0;
+    if (lane == 0) lin[s] = all_same ? 1 : 0;
+  }
   if constexpr (FG == 1) {
     tt = wave_sum(tt);
     if (lane == 0) fg.part[s] = tt;
@@ -920,10 +934,11 @@ __global__ __launch_bounds__(GL_WAVE) void k_rd_assemble_s(
     AT* __restrict__ vA, const double* __restrict__ c, const double* __restrict__ b, const double* __restrict__ b2,
     double* __restrict__ r_out, double* __restrict__ r2_out, double* __restrict__ dinv,
     const uint8_t* __restrict__ fixed, double two_dt, double* __restrict__ partials, int ldscap, int remap,
-    const MassArgs ma) {
+    const MassArgs ma, uint8_t* __restrict__ lin) {
   extern __shared__ double lds[];
   rd_assemble_s_slice<NV, CAP, RB, CIDX, AT, 0, MB, ST>(lds, desc, n_own, cols, cols16, win_base, cs2, cw, diag_k, vS, vA, c, b, b2,
-                                                    r_out, r2_out, dinv, fixed, two_dt, partials, ldscap, remap, FgArgs{}, ma);
+                                                    r_out, r2_out, dinv, fixed, two_dt, partials, ldscap, remap, FgArgs{}, ma,
+                                                    lin);
 }
 // ... and with the first pass of the dot-free solve that follows folded in (FG = 1, 2: see above)
 template <int NV, int CAP, int RB, int CIDX, int FG, int MB = 0, class ST = uint32_t>
@@ -934,11 +949,11 @@ __global__ __launch_bounds__(GL_WAVE) void k_rd_assemble_sg(
     double* __restrict__ vA, const double* __restrict__ c, const double* __restrict__ b, const double* __restrict__ b2,
     double* __restrict__ r_out, double* __restrict__ r2_out, double* __restrict__ dinv,
     const uint8_t* __restrict__ fixed, double two_dt, double* __restrict__ partials, int ldscap, int remap,
-    const FgArgs fg, const MassArgs ma) {
+    const FgArgs fg, const MassArgs ma, uint8_t* __restrict__ lin) {
   extern __shared__ double lds[];
   rd_assemble_s_slice<NV, CAP, RB, CIDX, double, FG, MB, ST>(lds, desc, n_own, cols, cols16, win_base, cs2, cw, diag_k, vS, vA, c,
                                                          b, b2, r_out, r2_out, dinv, fixed, two_dt, partials, ldscap, remap, fg,
-                                                         ma);
+                                                         ma, lin);
 }
 
 __global__ void k_make_desc(int n, const int32_t* __restrict__ list, const int64_t* __restrict__ slice_ptr,
@@ -1052,6 +1067,9 @@ __global__ __launch_bounds__(GL_WAVE) void k_rd_matfree(
 // rows of a slice are sorted by length, so the active lanes of a slot form a prefix and the memory system fetches only the
 // lines they touch.  On an unstructured mesh the padding is +19.5 % of the entries (sigma = 256); its bytes used to be
 // streamed like all others.
+// (acc += v * x below is ONE fused multiply-add per slot: the build contracts it (hipcc's default, -ffp-contract=fast), and
+//  spmv_row_coded, which must form the same bits, writes the fused operation out; a build with contraction off would make
+//  the two differ in the last place)
 template <int COMP, int UNR, int NT, int WANT_DIAG, class VT>
 __device__ __forceinline__ double spmv_row(const int32_t* __restrict__ cc, const uint16_t* __restrict__ c16,
                                             int32_t wb, const VT* __restrict__ v, const double* __restrict__ x,
@@ -1135,6 +1153,69 @@ __device__ __forceinline__ double spmv_row(const int32_t* __restrict__ cc, const
   return acc;
 }
 
+// The same row from the CODED stream of an exactly-linear slice (value_codes.h): one 32-bit word per entry -- the column code
+// and, as (dictionary index, delta), the value -- instead of 2 + 8 bytes.  `dict`: this wave's copy of the slice's 32 bases in
+// LDS (256 B: one bank row, a ds_read_b64 of any mix of indices has no bank conflict).  The decode is an integer add on the
+// base: the very 64 bits vA holds for the slice, so every product below has the operands of spmv_row.  The additions are
+// spmv_row's as well, one fused multiply-add per slot in slot order from 0 up to the slice's length rounded up to UNR
+// (`len_u`: spmv_row's batches -- its ragged tail adds 0 x 0 for the slots beyond a row's length), so the sum has the same bits.
+// Halving the bytes per load halves what a batch keeps in flight, so a batch here is 16 entries: a row of a tetrahedral mesh
+// (15) is ONE round trip.
+// DENSE (DevPattern::scoded = 2): every row of the slice has the slice's length, which is what a lattice's interior slices
+// look like -- no lane is masked, no load is predicated, and a slot beyond the length adds +0.0 on every lane.  Otherwise the
+// loads are predicated on the lane's own length as in spmv_row (slots beyond it contribute 0 x 0).
+// The diagonal's value and x[row] are not picked out of the batch (four selects per slot): the caller reads them again,
+// one word and one double per row that the pass has just touched.
+// `ws`: the slice's first word, `len` / `len_u`: in scalar registers (the caller has made them so: the words' addresses are
+// then a scalar base plus the lane, like the gathers' -- `x` plus a 32-bit byte offset, which is why a handle of 2^29 nodes or
+// more streams no codes, gl_launch_cheb).
+template <int NT, bool DENSE>
+__device__ __forceinline__ double spmv_row_coded(const uint32_t* __restrict__ ws, int lane, int32_t wb, const int64_t* dict,
+                                                  const double* __restrict__ x, int len, int len_u, int rl) {
+  constexpr int B = 16;
+  double acc = 0.0;
+  for (int k = 0; k < len_u; k += B) {
+    uint32_t wu[B], vp[B / 2];
+    double xu[B];
+#pragma unroll
+    for (int j = 0; j < B; ++j) {
+      const uint32_t* w = ws + (int64_t)(DENSE ? min(k + j, len - 1) : k + j) * GL_WAVE;   // (DENSE: clamped, no predicate)
+      wu[j] = DENSE || k + j < rl ? (NT == 1 ? __builtin_nontemporal_load(w + lane) : w[lane]) : 0u;
+    }
+    // (the column decode reads window bases across lanes: every lane takes part, as in spmv_row)
+    // Before the gathers are issued a lane reduces the words to what it still needs: the 32-bit columns and the value codes,
+    // two to a register -- 24 registers next to the 32 of the gathered operands (with the words and the 64-bit addresses of
+    // all sixteen gathers live at once the compiler reports 107 vector registers for the kernel, 4 waves per SIMD).
+    int32_t cu[B];
+#pragma unroll
+    for (int j = 0; j < B; ++j) cu[j] = decode_col(gl_vc_col(wu[j]), wb);
+#pragma unroll
+    for (int j = 0; j < B / 2; ++j) vp[j] = gl_vc_pair(wu[2 * j], wu[2 * j + 1]);
+#pragma unroll
+    for (int j = 0; j < B; ++j) asm volatile("" : "+v"(cu[j]));
+#pragma unroll
+    for (int j = 0; j < B / 2; ++j) asm volatile("" : "+v"(vp[j]));
+#pragma unroll
+    for (int j = 0; j < B; ++j)
+      xu[j] = DENSE || k + j < rl ? *(const double*)((const char*)x + ((uint32_t)cu[j] << 3)) : 0.0;
+#pragma unroll
+    for (int j = 0; j < B; ++j) {
+      if (k + j < len_u) {   // (wave-uniform)
+        const uint32_t cj = gl_vc_pair_word(vp[j / 2], j & 1);
+        const double vj = gl_vc_value_at(dict[gl_vc_index(cj)], gl_vc_delta_of(cj));
+        // (explicit fused multiply-adds: what the compiler makes of spmv_row's acc += v * x; written as that expression, the
+        //  two arms below were merged into a product, a select and an addition -- one rounding more)
+        if (DENSE) {
+          if (k + j < len) acc = __builtin_fma(vj, xu[j], acc);   // (wave-uniform)
+          else acc = __builtin_fma(0.0, 0.0, acc);                // (spmv_row's 0 x 0: a sum of -0.0 becomes +0.0 as there)
+        } else {
+          acc = __builtin_fma(k + j < rl ? vj : 0.0, xu[j], acc);
+        }
+      }
+    }
+  }
+  return acc;
+}
 
 // VT = double; float only for the optional single-precision copy of the Newton Jacobian (GLIMS_FLAG_FP32_JACOBIAN).
 template <int DOTS, int UNR, int NT, int CIDX, class VT = double>
@@ -1201,8 +1282,17 @@ __global__ __launch_bounds__(256) void k_spmv(int n_launch, int chunk, const int
 // warm start needs anyway IS this pass, no separate SpMV and no start kernel; every count moves by one.  nrm (pass 1 of such a
 // solve): the partial sums of |t|^2 per block, from which the device chooses the iteration count.
 // y_in is gathered (ghosts included), y_out written by the row owner: two buffers that change roles every launch.
+// Waves per SIMD of the instances with a coded path (fp64 values, 16-bit column codes): what they had before it, 6 with UNR = 8
+// and 4 with 16, stated so that the register allocation of the three paths together is held to it -- left to itself the
+// compiler settles at 85 / 133 vector registers, 5 / 3 waves.  With the bound: 79 / 124 vector registers (76 / 127 before the
+// coded path), no scratch and no vector register spilled, but the scalar registers run out (106 of 106): 30 (UNR = 8) and 61
+// (UNR = 16) scalar values are parked in lanes of a vector register (v_writelane / v_readlane, no memory traffic; 0 and 8
+// before).  What that costs the uncoded path is measured, not argued: profiles/ab_value_codes.txt, the rounds under
+// GLIMS_FLAG_NO_VALUE_CODES against the parent build.  The other instances (fp32 values, int32 columns) carry neither the
+// bound nor the scalar wave number below and compile to what they were.
 template <int UNR, int NT, int CIDX, class VT>
-__global__ __launch_bounds__(256) void k_cheb(int n_launch, int chunk, const int32_t* __restrict__ slice_list,
+__global__ __launch_bounds__(256)
+__attribute__((amdgpu_waves_per_eu((CIDX != 0 && std::is_same<VT, double>::value) ? (UNR == 8 ? 6 : 4) : 1))) void k_cheb(int n_launch, int chunk, const int32_t* __restrict__ slice_list,
                                                int64_t n_own, const int64_t* __restrict__ slice_ptr,
                                                const int32_t* __restrict__ cols, const uint16_t* __restrict__ cols16,
                                                const int32_t* __restrict__ win_base, const uint8_t* __restrict__ win_ok,
@@ -1213,14 +1303,23 @@ __global__ __launch_bounds__(256) void k_cheb(int n_launch, int chunk, const int
                                                double* ylast, double* __restrict__ x,
                                                const uint8_t* __restrict__ fixed, double c1, double c2, int k, int m_host,
                                                const int* __restrict__ plan, int want_res, const PackMap pm, int remap,
-                                               int shift, double* __restrict__ nrm) {
+                                               int shift, double* __restrict__ nrm, const uint8_t* __restrict__ lin,
+                                               const uint8_t* __restrict__ scoded, const uint32_t* __restrict__ scode,
+                                               const int64_t* __restrict__ sdict, uint8_t* __restrict__ hit) {
+  // (coded slices, fp64 values with 16-bit column codes only: each wave's copy of its slice's dictionary)
+  constexpr bool CODES = CIDX != 0 && std::is_same<VT, double>::value;
+  __shared__ int64_t dict_lds[CODES ? 4 : 1][GL_VC_BASES];
   const int m = plan ? *plan : m_host;
   const int last = (want_res ? m : m - 1) + shift;
   if (k > last) return;
   const bool direction = !want_res || k < m + shift, fin = k == last;
   double pn = 0.0;
+  bool any_coded = false;   // this wave has read a slice from the coded stream: the launch counts as a coded pass (*hit)
   const int blk = remap > 1 ? xcd_chunk_remap(blockIdx.x, gridDim.x, remap) : blockIdx.x;
-  const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  // (CODES: the wave's number into a scalar register -- the slice, its offsets and its length are then scalars too, and the
+  //  three paths below are scalar branches; as vector values they keep the kernel at 82 vector registers and 5 waves per SIMD
+  //  even with the coded batch cut to 4 entries)
+  const int wid = CODES ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int s_end = min(n_launch, (blk + 1) * chunk);
   for (int si = blk * chunk + wid; si < s_end; si += 4) {
     const int s = slice_list ? slice_list[si] : si;
@@ -1231,7 +1330,36 @@ __global__ __launch_bounds__(256) void k_cheb(int n_launch, int chunk, const int
     double acc, yn = 0.0, ad = 1.0;
     const int dk = (int)diag_k[row];
     const int rl = (int)rlen[row];
-    if (CIDX && win_ok[s]) {   // wave-uniform
+    // `lin` null: the launch streams no codes.  Otherwise a slice whose values are S's bit for bit (the flag of the sweep that
+    // wrote them) and whose entries of S all have a code is read from the 4-byte words: the same operands, the same sums.
+    int coded = 0;
+    // (scoded implies win_ok; 2 = every row has `len` entries.  Into a scalar register: a branch the compiler takes for
+    //  divergent keeps the coded path's results live through the other paths, which costs them a wave per SIMD)
+    if constexpr (CODES) coded = __builtin_amdgcn_readfirstlane(lin && lin[s] ? (int)scoded[s] : 0);
+    if (coded) {   // wave-uniform
+      if constexpr (CODES) {
+        any_coded = true;
+        const int32_t wb = win_base[(int64_t)s * GL_N_WIN + (lane & (GL_N_WIN - 1))];
+        // (the slice's place and length into scalar registers: they are wave-uniform, which the compiler cannot see)
+        const int len_s = __builtin_amdgcn_readfirstlane(len);
+        const uint32_t* ws = scode + (((int64_t)__builtin_amdgcn_readfirstlane((int)(base >> 32)) << 32) |
+                                      (uint32_t)__builtin_amdgcn_readfirstlane((int)base));
+        int64_t* dict = dict_lds[wid];
+        __builtin_amdgcn_wave_barrier();   // (the previous slice's look-ups come first; a wave's LDS accesses execute in order)
+        if (lane < GL_VC_BASES) dict[lane] = sdict[(int64_t)s * GL_VC_BASES + lane];
+        __builtin_amdgcn_wave_barrier();
+        const int len_u = (len_s + UNR - 1) / UNR * UNR;
+        acc = coded == 2 ? spmv_row_coded<NT, true>(ws, lane, wb, dict, y_in, len_s, len_u, rl)
+                         : spmv_row_coded<NT, false>(ws, lane, wb, dict, y_in, len_s, len_u, rl);
+        // x[row] and A_ii again (spmv_row hands them over from its batches; the diagonal's column is the row itself): asked for
+        // after the row -- both lines are in the cache by now, and three registers less are live across the batch
+        if (rl > 0) {
+          const uint32_t wd = ws[dk * GL_WAVE + lane];
+          yn = y_in[row];
+          ad = gl_vc_value(wd, dict[gl_vc_index(wd)]);
+        }
+      }
+    } else if (CIDX && win_ok[s]) {   // wave-uniform
       const int32_t wb = win_base[(int64_t)s * GL_N_WIN + (lane & (GL_N_WIN - 1))];
       acc = spmv_row<1, UNR, NT, 1, VT>(nullptr, cols16 + base + lane, wb, v, y_in, len, rl, dk, yn, ad);
     } else {
@@ -1264,6 +1392,7 @@ __global__ __launch_bounds__(256) void k_cheb(int n_launch, int chunk, const int
       x[row] += yn;
     }
   }
+  if (any_coded && lane == 0) *hit = 1;   // (the same byte from every such wave of the launch; the host counts the bytes)
   if (nrm) spmv_dot_partial(pn, blk, nrm, 0);
 }
 
@@ -1738,11 +1867,158 @@ static void assemble_static_t(glims_ctx* h, int with_mechanics) {
   }
 }
 
+// ---- the coded entries of S (value_codes.h) --------------------------------------------------------------------------------
+// One wave per slice with 16-bit column codes: the dictionary by the greedy rule -- the smallest bit pattern (as a signed 64-bit
+// integer) among the slice's real entries that no base covers yet becomes base - 1023, a wave-wide minimum per base; lane i
+// keeps base i --, then every entry's word: its column code and, for a real entry, the base that covers it and the offset from
+// it.  A slice that needs more than 32 bases, or has no column codes, is uncoded (scoded = 0; its words are not read).
+__global__ __launch_bounds__(GL_WAVE) void k_build_value_codes(const int64_t* __restrict__ slice_ptr,
+                                                                const uint16_t* __restrict__ cols16,
+                                                                const uint8_t* __restrict__ win_ok,
+                                                                const uint8_t* __restrict__ rlen, const double* __restrict__ vS,
+                                                                uint32_t* __restrict__ scode, int64_t* __restrict__ sdict,
+                                                                uint8_t* __restrict__ scoded) {   // scoded: 0 = uncoded, 1 = coded, 2 = coded and every row has the slice's length
+  const int s = blockIdx.x, lane = threadIdx.x;
+  const int64_t base = slice_ptr[s];
+  const int len = (int)((slice_ptr[s + 1] - base) >> 6);
+  const int rl = (int)rlen[(int64_t)s * GL_WAVE + lane];
+  const double* sv = vS + base + lane;
+  bool ok = win_ok[s] != 0;   // (wave-uniform, like every branch on it below)
+  long long my_base = 0;
+  int nb = 0;
+  if (ok) {
+    bool first = true;
+    long long covered = 0;   // every pattern <= covered has a base
+    for (;;) {
+      long long mn = 0;
+      int has = 0;
+      for (int k = 0; k < rl; ++k) {
+        const long long b = gl_vc_bits(sv[(int64_t)k * GL_WAVE]);
+        if ((first || b > covered) && (!has || b < mn)) {
+          mn = b;
+          has = 1;
+        }
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const long long om = __shfl_xor(mn, o, 64);
+        const int oh = __shfl_xor(has, o, 64);
+        if (oh && (!has || om < mn)) mn = om;
+        has |= oh;
+      }
+      if (!has) break;
+      if (nb == GL_VC_BASES || mn > INT64_MAX - GL_VC_SPAN) {   // (the second: patterns of NaNs at the top of the range)
+        ok = false;
+        break;
+      }
+      if (lane == nb) my_base = gl_vc_base_for(mn);
+      covered = mn + GL_VC_SPAN;
+      first = false;
+      ++nb;
+    }
+  }
+  bool fit = true;
+  if (ok) {
+    for (int k = 0; k < len; ++k) {
+      const int64_t e = base + (int64_t)k * GL_WAVE + lane;
+      const uint32_t col = cols16[e];
+      const double v = sv[(int64_t)k * GL_WAVE];
+      int idx = -1;
+      int64_t dl = 0;
+      for (int i = 0; i < nb; ++i) {   // (every lane takes part in the cross-lane reads; the clusters are disjoint)
+        const int64_t bi = __shfl(my_base, i, 64);
+        const int64_t d = gl_vc_delta(bi, v);
+        if (idx < 0 && gl_vc_fits(d)) {
+          idx = i;
+          dl = d;
+        }
+      }
+      uint32_t word = gl_vc_pack_padding(col);
+      if (k < rl) {
+        if (idx < 0) fit = false;
+        else word = gl_vc_pack(col, idx, dl);
+      }
+      scode[e] = word;
+    }
+  }
+  const bool coded = ok && __all(fit ? 1 : 0) != 0;
+  const bool dense = __all(rl == len ? 1 : 0) != 0;   // every row as long as the slice: the pass masks no lane
+  if (lane < GL_VC_BASES) sdict[(int64_t)s * GL_VC_BASES + lane] = coded ? my_base : 0;
+  if (lane == 0) scoded[s] = coded ? (dense ? 2 : 1) : 0;
+}
+
+// Which handles stream coded slices in their dot-free passes: fp64 Jacobian with 16-bit column codes on one rank, unless
+// GLIMS_FLAG_NO_VALUE_CODES.  (Partitioned handles keep the 10-byte stream: nothing about them has been measured.)
+bool gl_value_codes_wanted(const glims_ctx* h) {
+  return (h->opt.flags & GLIMS_FLAG_NO_VALUE_CODES) == 0 && !h->jac32 && h->use_idx16 && h->world == 1;
+}
+
+// after k_assemble_static: S is new, and vA holds a copy of it that no sweep has flagged
+static void build_value_codes(glims_ctx* h) {
+  DevPattern& p = h->pat;
+  gl_harvest_coded_passes(h);   // (the ring goes or is cleared below: what it holds is added to the statistics first)
+  h->stats.rd_scode_slices = h->stats.rd_scode_uncoded_slices = h->stats.rd_lin_slices = 0;
+  if (!gl_value_codes_wanted(h) || p.n_slices <= 0) {
+    p.scode.release();
+    p.sdict.release();
+    p.scoded.release();
+    h->lin.release();
+    return;
+  }
+  const auto t0 = std::chrono::steady_clock::now();
+  p.scode.alloc((size_t)p.total_entries);
+  p.sdict.alloc((size_t)p.n_slices * GL_VC_BASES);
+  p.scoded.alloc((size_t)p.n_slices);
+  h->lin.alloc_zero((size_t)p.n_slices + GL_VC_HIT_RING, h->st);   // (the flags, then the coded passes' ring: gl_coded_pass_slot)
+  h->vc_launches = 0;
+  hipLaunchKernelGGL(k_build_value_codes, dim3(p.n_slices), dim3(GL_WAVE), 0, h->st, p.slice_ptr.p, p.cols16.p, p.win_ok.p,
+                     p.rlen.p, h->vS.p, p.scode.p, p.sdict.p, p.scoded.p);
+  GL_HIP(hipGetLastError());
+  std::vector<uint8_t> coded((size_t)p.n_slices);
+  GL_HIP(hipMemcpyAsync(coded.data(), p.scoded.p, coded.size(), hipMemcpyDeviceToHost, h->st));
+  GL_HIP(hipStreamSynchronize(h->st));
+  int64_t nc = 0;
+  for (uint8_t c : coded) nc += c != 0;
+  h->stats.rd_scode_slices = nc;
+  h->stats.rd_scode_uncoded_slices = (int64_t)p.n_slices - nc;
+  if (getenv("GLIMS_VERBOSE")) {
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    fprintf(stderr, "glims value codes: %lld of %d slices coded, %.1f MB of words and dictionaries, %.2f ms\n", (long long)nc,
+            p.n_slices, ((double)p.total_entries * 4 + (double)p.n_slices * (GL_VC_BASES * 8 + 2)) / 1e6, ms);
+  }
+}
+
+// The flags and the ring as they are now: (slices flagged exactly linear, coded passes not yet added to the statistics).
+void gl_value_code_counts(const glims_ctx* h, int64_t* lin_slices, int64_t* ring_passes) {
+  *lin_slices = *ring_passes = 0;
+  if (!h->lin.p || h->lin.n <= GL_VC_HIT_RING) return;
+  std::vector<uint8_t> f(h->lin.n);
+  if (hipStreamSynchronize(h->st) != hipSuccess) return;
+  if (hipMemcpy(f.data(), h->lin.p, f.size(), hipMemcpyDeviceToHost) != hipSuccess) return;
+  const size_t ns = f.size() - GL_VC_HIT_RING;
+  for (size_t i = 0; i < f.size(); ++i) (i < ns ? *lin_slices : *ring_passes) += f[i] != 0;
+}
+// ... the ring's passes into glims_stats.cheb_coded_passes, and an empty ring
+void gl_harvest_coded_passes(glims_ctx* h) {
+  int64_t lin = 0, ring = 0;
+  gl_value_code_counts(h, &lin, &ring);
+  h->stats.cheb_coded_passes += ring;
+  h->vc_launches = 0;
+  if (h->lin.p && h->lin.n > GL_VC_HIT_RING)
+    GL_HIP(hipMemsetAsync(h->lin.p + (h->lin.n - GL_VC_HIT_RING), 0, GL_VC_HIT_RING, h->st));
+}
+// the byte of the next launch that is given the coded stream
+static uint8_t* gl_coded_pass_slot(glims_ctx* h) {
+  if (h->vc_launches == GL_VC_HIT_RING) gl_harvest_coded_passes(h);   // (once in 1024 passes: a synchronisation and 1 KB)
+  return h->lin.p + (h->lin.n - GL_VC_HIT_RING) + h->vc_launches++;
+}
+
 void gl_assemble_static(glims_ctx* h, int with_mechanics) {
   if (h->dim == 2)
     assemble_static_t<2>(h, with_mechanics);
   else
     assemble_static_t<3>(h, with_mechanics);
+  build_value_codes(h);
 }
 
 int gl_rd_grid(const glims_ctx* h) { return h->pat.n_slices; }
@@ -1915,12 +2191,13 @@ static bool launch_sweep(glims_ctx* h, const GlSweepKey& k, const ClassLaunch& c
           using at_t = std::conditional_t<AT == GL_AT_F32, float, double>;
           using st_t = std::conditional_t<ST == GL_ST_U16, uint16_t, std::conditional_t<ST == GL_ST_REC32, rec32_t, uint32_t>>;
           at_t* vA = gl_either<AT == GL_AT_F32>(h->vA.p, h->vA32.p);
+          uint8_t* lin = h->world == 1 ? h->lin.p : nullptr;   // (null: the handle keeps no flags)
           if constexpr (CAP == 0) {
             set_lds(k_rd_assemble<NV, 0, RB, CIDX, at_t>, lds);
             hipLaunchKernelGGL((k_rd_assemble<NV, 0, RB, CIDX, at_t>), dim3(cl.grid), dim3(GL_WAVE), lds, h->st, cl.list,
                                h->n_own, p.slice_ptr.p, p.cols.p, p.cols16.p, p.win_base.p, p.win_ok.p, p.cslice_ptr.p,
                                p.cs2.p, p.cw.p, p.diag_k.p, h->vS.p, vA, a.c, a.b, a.b2, a.r_out, a.r2_out, h->dinv.p,
-                               a.fixed, 2.0 * h->opt.dt, a.partials, class_cap, GL_XCD_CHUNK);
+                               a.fixed, 2.0 * h->opt.dt, a.partials, class_cap, GL_XCD_CHUNK, lin);
           } else {
             const uint32_t* slots = ST == GL_ST_U16 ? p.cs16.p : ST == GL_ST_REC32 ? p.cr32.p : p.cs2.p;
             auto straight = [&](auto kern, auto... tail) {   // (the two families differ in their last arguments)
@@ -1929,8 +2206,8 @@ static bool launch_sweep(glims_ctx* h, const GlSweepKey& k, const ClassLaunch& c
                                  p.win_base.p, slots, p.cw.p, p.diag_k.p, h->vS.p, vA, a.c, a.b, a.b2, a.r_out, a.r2_out,
                                  h->dinv.p, a.fixed, 2.0 * h->opt.dt, a.partials, class_cap, GL_XCD_CHUNK, tail...);
             };
-            if constexpr (FG != 0) straight(k_rd_assemble_sg<NV, CAP, RB, CIDX, FG, MB, st_t>, a.fg, a.ma);
-            else straight(k_rd_assemble_s<NV, CAP, RB, CIDX, at_t, MB, st_t>, a.ma);
+            if constexpr (FG != 0) straight(k_rd_assemble_sg<NV, CAP, RB, CIDX, FG, MB, st_t>, a.fg, a.ma, lin);
+            else straight(k_rd_assemble_s<NV, CAP, RB, CIDX, at_t, MB, st_t>, a.ma, lin);
           }
           return true;
         } else {
@@ -2171,6 +2448,13 @@ void gl_launch_cheb(glims_ctx* h, hipStream_t st, int n_launch, const int32_t* s
   const int chunk = (n_launch + grid - 1) / grid;
   const int remap = slice_list ? 0 : GL_XCD_CHUNK;
   const int unr = !vals32 && h->spmv_unroll >= 16 ? 16 : 8;
+  // the coded slices' stream (value_codes.h): only for the handle's own Jacobian -- `lin` describes h->vA and nothing else --
+  // in fp64 with 16-bit column codes; a handle without codes (gl_value_codes_wanted) has no flags either
+  const bool codes = gl_value_codes_wanted(h) && h->n_nodes < ((int64_t)1 << 29) && h->lin.p != nullptr &&
+                     p.scode.p != nullptr && vals == h->vA.p && !vals32;
+  // cheb_coded_passes counts the launches in which a wave took the coded path: each such launch sets a byte of its own in
+  // the ring behind the flags, and the host adds the bytes up when the ring is full and when the statistics are asked for
+  uint8_t* hit = codes ? gl_coded_pass_slot(h) : nullptr;
   gl_switch(
       [&](auto UNR, auto NT, auto CIDX, auto F32) {
         if constexpr (F32 && UNR != 8) {
@@ -2180,7 +2464,8 @@ void gl_launch_cheb(glims_ctx* h, hipStream_t st, int n_launch, const int32_t* s
           const vt* v = gl_either<F32>(vals, vals32);
           gl_launch(k_cheb<UNR, NT, CIDX, vt>, grid, 256, 0, st, ev0, ev1, n_launch, chunk, slice_list, h->n_own, p.slice_ptr.p,
                     p.cols.p, p.cols16.p, p.win_base.p, p.win_ok.p, p.diag_k.p, p.rlen.p, v, y_in, y_out, b, dinv, y_prev, ylast,
-                    x, fixed, c1, c2, k, m_host, plan, want_res, pm, remap, shift, nrm);
+                    x, fixed, c1, c2, k, m_host, plan, want_res, pm, remap, shift, nrm, codes ? h->lin.p : nullptr, p.scoded.p,
+                    p.scode.p, p.sdict.p, hit);
           return true;
         }
       },

@@ -237,6 +237,18 @@ typedef struct glims_options {
                                            rho: lattices, voxel meshes; glims_stats.rd_rec_compact_slices); the other (full)
                                            slices keep today's streams.  fp64 Jacobian with 16-bit column codes only.
                                            Set: weight + slot word for every slice (A/B in one build) */
+#define GLIMS_FLAG_NO_VALUE_CODES 16384    /* OFF by default.  Default: a pass of the dot-free Krylov solve reads a slice of the
+                                           Jacobian whose stored values ARE those of the static operator S, bit for bit (away
+                                           from the tumour fl(S + 2 dt N(c)) = S; the assembly sweep flags such slices, per
+                                           slice and per sweep), from one 32-bit word per entry -- the 16-bit column code, a
+                                           5-bit index into the slice's dictionary of 32 bit patterns and an 11-bit offset --
+                                           instead of the value (8 B) and the column code (2 B), decoded to the same 64 bits,
+                                           so the same bits in every result.  The words are built by glims_setup (4 bytes per
+                                           padded entry of extra device memory); a slice of S that needs more than 32
+                                           dictionary entries keeps the 10-byte stream (glims_stats.rd_scode_slices).  fp64
+                                           Jacobian with 16-bit column codes on one rank only; partitioned handles, the PCG,
+                                           the multigrid and the adjoint read the stored values as before.
+                                           Set: no words are built and every pass reads the values (A/B in one build) */
 
 typedef struct glims_stats {
   int64_t steps;            /* implicit time steps taken */
@@ -345,6 +357,14 @@ typedef struct glims_stats {
   int64_t rd_rec32_sweeps;  /* assembly sweeps (glims_apply hooks included) that read compact records for at least one slice; 0
                                under GLIMS_FLAG_RECORD_WORDS_FULL, GLIMS_FLAG_SLOT_WORDS32, GLIMS_FLAG_INT32_COLUMNS and
                                GLIMS_FLAG_FP32_JACOBIAN */
+  int64_t rd_scode_slices;  /* slices of S whose entries all have a 32-bit value code (at most 32 dictionary entries) ... */
+  int64_t rd_scode_uncoded_slices; /* ... and those that have none (both set by glims_setup, kept by glims_reset_stats; both 0
+                               where no codes are built: GLIMS_FLAG_NO_VALUE_CODES, GLIMS_FLAG_FP32_JACOBIAN,
+                               GLIMS_FLAG_INT32_COLUMNS, partitioned handles) */
+  int64_t rd_lin_slices;    /* slices the latest assembly sweep found exactly linear (their values of A are S's, bit for bit),
+                               read from the device by glims_get_stats; not a running count */
+  int64_t cheb_coded_passes; /* launches of the dot-free pass in which at least one slice -- exactly linear and coded -- was read
+                               from the 4-byte words (counted on the device, collected by glims_get_stats) */
 } glims_stats;
 
 /* ---- lifetime -------------------------------------------------------------------------------------- */
@@ -414,6 +434,11 @@ int glims_step(glims_ctx* h, int n_steps);
  * from it should it miss the tolerance; glims_stats.last_mech_res is that true residual. */
 int glims_solve_mechanics(glims_ctx* h);
 
+/* A copy of the counters.  On a handle that streams value codes (GLIMS_FLAG_NO_VALUE_CODES not set, fp64 Jacobian, 16-bit column
+ * codes, one rank) the call also waits for the handle's stream and reads one byte per slice plus 1 KB from the device (about
+ * 160 KB at 10 M rows): rd_lin_slices is the device's flags as they are now, and cheb_coded_passes includes the launches the
+ * device has counted since they were last collected.  Every other handle gets the plain copy, without synchronisation.  (The
+ * solver itself collects those launches once in 1024 coded passes, with one synchronisation of its stream.) */
 int glims_get_stats(const glims_ctx* h, glims_stats* st);
 int glims_reset_stats(glims_ctx* h);
 

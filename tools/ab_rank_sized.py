@@ -52,7 +52,7 @@ def main():
         best = {}
         for rnd in range(rounds):
             for label, opts, flags in variants:
-                h.set_options(dt=w.dt, flags=B.FLAG_WARM_START | flags, time_kernels=int(os.environ.get('TIME_KERNELS', '1')), **opts)
+                h.set_options(dt=w.dt, flags=B.FLAG_WARM_START | flags | int(os.environ.get('EXTRA_FLAGS', '0')), time_kernels=int(os.environ.get('TIME_KERNELS', '1')), **opts)
                 h.setup(False)
                 h.set_state(w.c0)
                 st = h.step(W)

@@ -25,21 +25,24 @@ h.set_state(w.c0)
 done = 0
 prev = h.stats()
 windows = []
+lin_windows = []   # (first step of the window, ms per step, exactly-linear slices after it: glims_stats.rd_lin_slices)
 final_status = 0
 while done < total:
     st = h.step(min(chunk, total - done))
     s = h.stats()
     n = s['steps'] - prev['steps']
     c = h.get_state(want_u=False)[0] if (st != 0 or (done // chunk) % 10 == 9) else None
-    print("steps %4d..%4d status %d  newton/step %.2f (sweeps %.2f, cheap passes %.2f)  cg/step %.2f  |R| %.3e  cg res %.3e  ms/step %.2f%s" %
+    print("steps %4d..%4d status %d  newton/step %.2f (sweeps %.2f, cheap passes %.2f)  cg/step %.2f  |R| %.3e  cg res %.3e  ms/step %.2f  linear slices %d of %d coded, coded passes/step %.2f%s" %
           (done, done + n, st, (s['newton_its'] - prev['newton_its']) / max(n, 1),
            (s['rd_assemblies'] - prev['rd_assemblies']) / max(n, 1),
            (s['rd_quad_updates'] - prev['rd_quad_updates']) / max(n, 1),
            (s['cg_its'] - prev['cg_its']) / max(n, 1), s['last_newton_res'], s['last_cg_res'],
-           (s['ms_steps'] - prev['ms_steps']) / max(n, 1),
+           (s['ms_steps'] - prev['ms_steps']) / max(n, 1), s['rd_lin_slices'], s['rd_scode_slices'],
+           (s['cheb_coded_passes'] - prev['cheb_coded_passes']) / max(n, 1),
            "" if c is None else "  c in [%.3e, %.6f], mass %.6e" % (c.min(), c.max(), c.sum())), flush=True)
     if n > 0:
         windows.append((n, (s['ms_steps'] - prev['ms_steps']) / n))
+        lin_windows.append((done, round((s['ms_steps'] - prev['ms_steps']) / n, 3), int(s['rd_lin_slices'])))
     final_status = st
     prev = s
     done += max(n, 1) if st == 0 else chunk
@@ -57,5 +60,7 @@ if len(sys.argv) > 4:
                "chunk": chunk, "ms_per_step_mean": sum(k * m for k, m in windows) / max(1, tot),
                "ms_per_step_min_window": min(full) if full else None, "ms_per_step_max_window": max(full) if full else None,
                "newton_its_per_step": s['newton_its'] / max(1, tot), "krylov_passes_per_step": s['cg_its'] / max(1, tot),
-               "chebyshev_fallbacks": int(s['cheb_fallbacks']), "kernels_sha16": kernels_sha16()},
+               "chebyshev_fallbacks": int(s['cheb_fallbacks']), "value_code_slices": int(s['rd_scode_slices']),
+               "slices": int((s['n_rows'] + 63) // 64), "windows_step_ms_linear_slices": lin_windows,
+               "kernels_sha16": kernels_sha16()},
               open(sys.argv[4], "w"), indent=1)
