@@ -45,6 +45,9 @@ DERIVE_CURRENT, DERIVE_HOST = -1, -2
 DERIVE_KINDS = {"strain_tensor": 0, "stress_tensor": 1, "pressure": 2, "van_mises_stress": 3, "displacement_norm": 4,
                 "log_growth": 5, "mech_expansion": 6, "total_jacobian": 7, "growth_induced_jacobian": 8,
                 "concentration_deformed_config": 9}
+# glims_observe kinds by name (GLIMS_OBSERVE_*)
+OBSERVE_KINDS = {"mass": 0, "sharp": 1, "smooth": 2}
+OBSERVE_MAX_QUERIES = 8
 SAMPLE_EPS = 1e-10      # GLIMS_SAMPLE_EPS: a cell accepts a point iff min lambda >= -SAMPLE_EPS
 SAMPLE_MAX_COMP = 8
 ABI_VERSION = 6
@@ -125,6 +128,11 @@ class ImageMisfit(C.Structure):
                 ("pweight", C.POINTER(C.c_double))]
 
 
+class Observable(C.Structure):
+    """glims_observable: one query of glims_observe (kind: OBSERVE_KINDS; smooth: 'smooth' only)."""
+    _fields_ = [("kind", C.c_int), ("level", C.c_double), ("smooth", C.c_double)]
+
+
 _dp = C.POINTER(C.c_double)
 _i32p = C.POINTER(C.c_int32)
 _i64p = C.POINTER(C.c_int64)
@@ -162,6 +170,8 @@ SIGNATURES = {
     "glims_project": (C.c_int, [_h, _dp, _dp, C.c_int, C.c_double]),
     "glims_derive": (C.c_int, [_h, C.c_int, C.c_int64, _dp, _dp, C.c_double, _dp]),
     "glims_derive_info": (C.c_int, [_h, _i64p]),
+    "glims_observe": (C.c_int, [_h, C.c_int, _i64p, _dp, _dp, C.c_int, C.c_double, C.c_int, C.POINTER(Observable), _dp]),
+    "glims_observe_info": (C.c_int, [_h, _i64p]),
     "glims_adjoint_record": (C.c_int, [_h, C.c_int]),
     "glims_adjoint_gradient": (C.c_int, [_h, C.c_int, C.POINTER(Misfit), _dp, _dp, _dp, _dp, _dp]),
     "glims_adjoint_gradient_full": (C.c_int, [_h, C.c_int, C.POINTER(Misfit), _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
@@ -446,6 +456,56 @@ class Handle:
         a = np.zeros(4, dtype=np.int64)
         self._check(self.lib.glims_derive_info(self._h, _ptr(a, _i64p)))
         return dict(zip(("cell_passes", "mass_solves", "elastic_solves", "cache_hits"), (int(v) for v in a)))
+
+    # -- volumes and centres of mass per label (glims_observe) ---------------------------------------------
+    def observe(self, queries, snapshots=None, c=None, u=None, deformed=False, scale=1.0):
+        """Measure and first moments of the queries per label, computed on the device (glims_observe).  ``queries``: a list of
+        (kind, level, smooth) -- kind a name of OBSERVE_KINDS or its number; level and smooth may be left out where the kind
+        reads none.  Source: ``snapshots`` (ids of snapshot_save, one cell pass each), host arrays ``c`` [n_nodes] (and ``u``
+        [n_nodes, dim] when ``deformed``) in the caller's node order, or neither: the handle's current c and U as they stand.
+        ``deformed``: the configuration x = X + scale u (a snapshot's displacement is solved on the device).  Returns
+        [n_src, n_q, n_labels, 1 + dim] = (V, M_0 ..); more than OBSERVE_MAX_QUERIES queries go in several calls.
+        ``last_observe_status`` holds the worst status of the calls: GLIMS_NOT_CONVERGED does not raise, GLIMS_NAN and the
+        refusals do."""
+        qs = []
+        for q in queries:
+            q = tuple(q) if isinstance(q, (tuple, list)) else (q,)
+            kind = OBSERVE_KINDS[q[0]] if isinstance(q[0], str) else int(q[0])
+            qs.append((kind, float(q[1]) if len(q) > 1 else 0.0, float(q[2]) if len(q) > 2 else 1.0))
+        if snapshots is not None and (c is not None or u is not None):
+            raise ValueError("observe: give snapshots or host arrays, not both")
+        if snapshots is not None:
+            src = np.ascontiguousarray(np.atleast_1d(snapshots), dtype=np.int64)
+        elif c is not None or u is not None:
+            src = np.array([DERIVE_HOST], dtype=np.int64)
+            c = None if c is None else _f64(c, (self.n_nodes,))
+            u = None if u is None else _f64(np.asarray(u, dtype=np.float64).reshape(-1), (self.n_nodes * self.dim,))
+        else:
+            src = np.array([DERIVE_CURRENT], dtype=np.int64)
+        if self.n_labels is None:
+            raise BackendError(GLIMS_E_USAGE, "observe before set_materials")
+        out = np.zeros((len(src), len(qs), self.n_labels, 1 + self.dim))
+        worst = GLIMS_OK
+        for q0 in range(0, max(len(qs), 1), OBSERVE_MAX_QUERIES):
+            part = qs[q0:q0 + OBSERVE_MAX_QUERIES]
+            arr = (Observable * max(len(part), 1))()
+            for k, (kind, level, smooth) in enumerate(part):
+                arr[k].kind, arr[k].level, arr[k].smooth = kind, level, smooth
+            res = np.zeros((len(src), len(part), self.n_labels, 1 + self.dim))
+            st = self.lib.glims_observe(self._h, len(src), _ptr(src, _i64p), _ptr(c, _dp), _ptr(u, _dp),
+                                        1 if deformed else 0, float(scale), len(part), arr, _ptr(res, _dp))
+            self.last_observe_status = st
+            self._check(st, allow=(GLIMS_NOT_CONVERGED,))
+            worst = max(worst, st)
+            out[:, q0:q0 + len(part)] = res
+        self.last_observe_status = worst
+        return out
+
+    def observe_info(self):
+        """Cumulative counters of observe(): cell passes, elastic solves, sources observed."""
+        a = np.zeros(4, dtype=np.int64)
+        self._check(self.lib.glims_observe_info(self._h, _ptr(a, _i64p)))
+        return dict(zip(("cell_passes", "elastic_solves", "sources"), (int(v) for v in a[:3])))
 
     # -- discrete adjoint (glims_adjoint_*) -----------------------------------------------------------
     def adjoint_record(self, on=True):

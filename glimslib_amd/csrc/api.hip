@@ -1061,6 +1061,21 @@ int glims_derive_info(const glims_ctx* h, int64_t out[4]) {
   return GLIMS_OK;
 }
 
+int glims_observe(glims_ctx* h, int n_src, const int64_t* src, const double* c_host, const double* u_host, int deformed,
+                  double scale, int n_q, const glims_observable* q, double* out) {
+  return guarded(h, [&]() { return gl_observe(h, n_src, src, c_host, u_host, deformed, scale, n_q, q, out); });
+}
+
+int glims_observe_info(const glims_ctx* h, int64_t out[4]) {
+  if (!h || !out) return GLIMS_E_USAGE;
+  const ObserveState& o = h->observe;
+  out[0] = o.n_cell_passes;
+  out[1] = o.n_elastic_solves;
+  out[2] = o.n_sources;
+  out[3] = 0;
+  return GLIMS_OK;
+}
+
 int glims_comm_unique_id(char id[GLIMS_UNIQUE_ID_BYTES]) {
   static_assert(GLIMS_UNIQUE_ID_BYTES >= 2 * sizeof(ncclUniqueId), "unique id buffer too small");
   if (!id) return GLIMS_E_USAGE;

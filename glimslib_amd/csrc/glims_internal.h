@@ -517,6 +517,18 @@ struct DeriveState {
   }
 };
 
+// Observables of recorded steps (observe.hip, glims_observe): which labels the cells carry, the per-wave tables of the cell pass
+// and the call's result before it goes to the host
+struct ObserveState {
+  std::vector<int32_t> slot_label;         // compact slot -> label, ascending (empty: the labels were not read yet)
+  dvec<int32_t> label_slot;                // [GL_MAX_LABELS] label -> compact slot, -1 = no cell carries it
+  dvec<int32_t> d_slot_label;              // slot_label on the device
+  dvec<double> part;                       // per-wave tables [waves][slots][n_q][1 + dim]
+  dvec<double> res;                        // [n_src][n_q][n_labels][1 + dim]
+  dvec<double> sc, su;                     // GLIMS_DERIVE_HOST: c [n_nodes] and u [n_nodes][dim], internal numbering
+  int64_t n_cell_passes = 0, n_elastic_solves = 0, n_sources = 0;   // glims_observe_info
+};
+
 struct glims_ctx {
   int dim = 0, nv = 0, device = 0;
   int n_labels = 0;                        // of the last glims_set_materials
@@ -679,6 +691,7 @@ struct glims_ctx {
   std::vector<GlSampler*> samplers;         // owned (sample.hip); a destroyed sampler leaves a nullptr so that ids stay valid
   std::vector<GlImageTerm*> img_terms;      // owned (sample.hip): the stored image-space misfit terms of the adjoint calls
   DeriveState derive;
+  ObserveState observe;
 
   std::string err;
 };
@@ -816,6 +829,9 @@ void gl_to_device_perm(glims_ctx* h, const double* host, double* dst, int bs);
 int gl_derive(glims_ctx* h, int kind, int64_t snapshot, const double* c_host, const double* u_host, double rtol, double* out);
 // the last result as the samplers read a nodal field ([n_nodes][ncomp], internal numbering); refuses when there is none
 const double* gl_derive_sampled(glims_ctx* h, int ncomp);
+// observe.hip ---------------------------------------------------------------------------------------
+int gl_observe(glims_ctx* h, int n_src, const int64_t* src, const double* c_host, const double* u_host, int deformed,
+               double scale, int n_q, const glims_observable* q, double* out);
 
 // mg.hip --------------------------------------------------------------------------------------------
 void gl_mesh_metrics(glims_ctx* h, const HostPattern& hp, const double* xyz_old);

@@ -594,5 +594,83 @@ class TumorGrowth(FenicsSimulation):
         self.postprocess = self._make_postprocess(output_dir, device)
         return self.postprocess
 
+    # -- volumes and centres of mass per tissue ------------------------------------------------------------------------------
+    def observe(self, queries, steps=None, deformed=False, device=None):
+        """
+        Measure and first moments of `queries` per tissue label for the recording steps `steps` (default: all) ->
+        (array [n_steps, n_q, n_labels, 1 + dim] = (V, M_0 ..), list of steps).  `queries`: (kind[, level[, smooth]]) tuples
+        with kind 'mass' (q = c), 'sharp' (q = 1 where c >= level, exact) or 'smooth' (the reference's thresh(): q =
+        1/2 (tanh((c - level) / smooth) + 1), degree-7 quadrature); simulation_helpers/observables.py states them in numpy.
+        deformed=True integrates over the configuration x = X + u of each step: the volume an image shows.
+        Steps recorded on the device (run(results_on_device=True), one GPU) are observed there in ONE backend call -- one cell
+        pass per step, the displacement solved lazily on the device where `deformed` asks for it; host-resident steps go
+        through numpy unless device=True; device=False and partitioned runs keep numpy throughout.
+        """
+        from ..simulation_helpers import observables
+        h = self._backend
+        if h is None:
+            raise RuntimeError("observe needs a finished run()")
+        qs = observables.normalise_queries(queries)
+        steps = list(self.results.get_recording_steps()) if steps is None else [int(s) for s in steps]
+        labels = self._labels()
+        n_labels = int(labels.max()) + 1
+        dim = self.geometric_dimension
+        deformed = bool(deformed) and bool(self.solver.mechanics)          # (no mechanics: u = 0)
+        on_dev = device is not False and isinstance(h, _backend.Handle)
+        out = np.zeros((len(steps), len(qs), n_labels, 1 + dim))
+        fields = []
+        for s in steps:
+            obs = self.results.get_result(s)
+            if obs is None:
+                raise KeyError("no result for recording step %r" % (s,))
+            fields.append(obs.get_field())
+        snap = [k for k, f in enumerate(fields) if on_dev and getattr(f, 'snapshot_id', None) is not None]
+        if snap:
+            res = h.observe(qs, snapshots=[int(fields[k].snapshot_id) for k in snap], deformed=deformed)
+            if deformed:
+                self.solver._mech_current = False          # the device's displacement buffer now belongs to a recorded step
+            if h.last_observe_status != _backend.GLIMS_OK:
+                self.logger.warning("    - observe: a displacement solve did not converge (status %d)" % h.last_observe_status)
+            out[snap] = res[:, :, :n_labels]
+        for k, f in enumerate(fields):
+            if k in snap:
+                continue
+            c = np.asarray(f.components[1], dtype=np.float64)
+            u = np.asarray(f.components[0], dtype=np.float64) if deformed else None
+            if on_dev and device:
+                out[k] = h.observe(qs, c=c, u=u, deformed=deformed)[0][:, :n_labels]
+            else:
+                out[k] = observables.observe(self.mesh.points, self.mesh.cells, labels, c, qs, n_labels, u=u)
+        return out, steps
+
+    def compute_from_conc_for_each_time_step(self, threshold=0.12, computation='volume', kind='sharp', smooth=0.01,
+                                             deformed=False, device=None):
+        """
+        ImageBasedOptimizationBase.compute_from_conc_for_each_time_step (image_based_optimization.py:1333-1397) for this
+        simulation: per recording step the tumour volume above `threshold` ('volume') or its centre of mass ('com'), over the
+        whole domain and per tissue -> pandas DataFrame with the reference's columns: 'sim_time_step', then 'all' and one
+        column per tissue name of subdomains.tissue_id_name_map (lower-cased) for 'volume', 'all_0..', '<name>_0..' for
+        'com'.  The centre of mass is NaN where the volume is not > 0 (compute_com).  kind='sharp' integrates
+        conditional(c >= threshold, 1, 0) exactly, 'smooth' the thresh() field of width `smooth`, 'mass' gives int c dx
+        (`threshold` unused).  `deformed`, `device`: see observe().  The reference's L2 projection of q before the
+        per-tissue integrals is left out.
+        """
+        import pandas as pd
+        from ..simulation_helpers import observables
+        if computation not in ('volume', 'com'):
+            raise ValueError("computation must be 'volume' or 'com'")
+        table, steps = self.observe([(kind, threshold, smooth)], deformed=deformed, device=device)
+        V, com = observables.totals_and_com(table[:, 0])                   # [n_steps, 1 + n_labels], [.., dim]
+        names = [('all', 0)] + [(str(name).lower(), 1 + int(tid)) for tid, name in
+                                getattr(self.subdomains, 'tissue_id_name_map', {}).items() if int(tid) + 1 < V.shape[1]]
+        cols = {'sim_time_step': steps}
+        for name, k in names:
+            if computation == 'volume':
+                cols[name] = V[:, k]
+            else:
+                for a in range(com.shape[-1]):
+                    cols["%s_%d" % (name, a)] = com[:, k, a]
+        return pd.DataFrame(cols)
+
     def solver_statistics(self):
         return self._backend.stats() if self._backend is not None else {}

@@ -26,6 +26,8 @@
  *   GLIMS_VERBOSE_CHEB   any value: one line per dot-free RD solve (residual before / after, tolerance, passes)
  *   GLIMS_DERIVE_TIMING  any value: glims_derive puts a HIP event pair around its cell pass and around its gather and prints one
  *                        line per projection with both times on stderr (tools/derive_cost.py; a synchronisation per pass)
+ *   GLIMS_OBSERVE_TIMING any value: glims_observe puts a HIP event pair around each source's pass and prints one line per source
+ *                        with the time on stderr (a synchronisation per source)
  *   GLIMS_HOST_THREADS   OpenMP team of the host-side symbolic phase (default: the CPUs this process may use,
  *                        divided by the ranks on the host)
  *   GLIMS_HOST_SYMBOLIC  TEST HOOK: glims_create runs the host (OpenMP) implementation of the symbolic phase instead of
@@ -860,6 +862,51 @@ int glims_derive(glims_ctx* h, int kind, int64_t snapshot, const double* c_host,
                  double* out);
 /* cumulative since glims_create: out[0] cell passes, [1] mass solves, [2] elastic solves, [3] hits of the stress cache */
 int glims_derive_info(const glims_ctx* h, int64_t out[4]);
+
+/* ---- tumour volumes and centres of mass per tissue, on the device ---------------------------------------------------------------
+ * The first numbers the reference's workflow computes from a run: ImageBasedOptimizationBase.compute_from_conc_for_each_time_step
+ * (optimization_workflow/image_based_optimization.py:1333-1397) takes q = conditional(c >= threshold, 1, 0) of every recording
+ * step and integrates compute_volume / compute_com over dx and over dx(subdomain_id) of every tissue; compute_volume_thresholded /
+ * compute_com_all (:1262-1301, :1416-1430, :1470-1472) do the same for the smooth thresh() fields, post_process (:1305) runs all
+ * of it for T2 = 0.12 and T1 = 0.80.  glims_observe computes, for every source, query and label, the measure and the first
+ * moments of q over the cells of that label (the per-cell mathematics is csrc/observe_clip.h):
+ *   GLIMS_OBSERVE_MASS    q = c_h                                      exact
+ *   GLIMS_OBSERVE_SHARP   q = 1 where c_h >= level (a tie is in)       exact: the simplex is clipped at the level set
+ *   GLIMS_OBSERVE_SMOOTH  q = 1/2 (tanh((c_h - level) / smooth) + 1)   the degree-7 rule of csrc/derive_quadrature.h (the discrete
+ *                                                                      statement of that rule, not a converged integral where
+ *                                                                      smooth is far below the range of c over a cell)
+ * src[i]: an id of glims_snapshot_save; with n_src == 1 also GLIMS_DERIVE_CURRENT (the handle's c, and U as it stands) or
+ * GLIMS_DERIVE_HOST (c_host[n_nodes], u_host[n_nodes*dim] in the caller's node order, uploaded into scratch), as in glims_derive.
+ * out[n_src][n_q][n_labels][1 + dim] = (V, M_0 .. M_{dim-1}) with n_labels that of glims_set_materials; a label that no cell
+ * carries gets exact zeros; the whole-domain figures are the sums over the labels and the centre of mass is M / V (the caller's).
+ *
+ * deformed = 0: the reference configuration, V = int q dX.  deformed = 1: the configuration x = X + scale u, V = int q det(I +
+ * scale grad u) dX and the moments of x; a folded cell counts negatively (as GLIMS_DERIVE_TOTAL_JACOBIAN).  It needs
+ * glims_setup(with_mechanics=1); a snapshot's displacement is solved as glims_snapshot_mechanics solves it (same status codes; U
+ * is written and the solve enters the elastic solve history) unless U already belongs to that snapshot -- the memory glims_derive
+ * and the deformed samplers use; glims_observe_info and glims_derive_info count the solve.  Nothing else the time stepper owns
+ * is touched: the steps that follow have the bits of a run that never called it.
+ *
+ * One pass over the cells per source serves all n_q queries (glims_observe_info counts the passes); there are no floating-point
+ * atomics and the same handle and arguments give the same bits on every call.  With GLIMS_OBSERVE_TIMING set (any value) an
+ * event pair around each source's pass prints one line per source on stderr.
+ * Returns the worst status of its elastic solves (GLIMS_OK / GLIMS_NOT_CONVERGED / GLIMS_NAN).  GLIMS_E_USAGE, with a reason in
+ * glims_last_error and nothing written: a call before glims_setup, an unknown kind or snapshot, n_q outside 1..8, n_src < 1,
+ * CURRENT / HOST with n_src != 1, CURRENT before glims_set_state, a required pointer that is NULL, smooth <= 0 of a SMOOTH query,
+ * deformed on a handle set up without mechanics, a scale or level that is not finite, a cell label >= n_labels, a partitioned
+ * handle (world > 1: the numpy statement of the Python layer serves there). */
+#define GLIMS_OBSERVE_MASS 0
+#define GLIMS_OBSERVE_SHARP 1
+#define GLIMS_OBSERVE_SMOOTH 2
+#define GLIMS_OBSERVE_MAX_QUERIES 8
+typedef struct glims_observable {
+  int kind;               /* GLIMS_OBSERVE_* */
+  double level, smooth;   /* smooth: SMOOTH only */
+} glims_observable;
+int glims_observe(glims_ctx* h, int n_src, const int64_t* src, const double* c_host, const double* u_host, int deformed,
+                  double scale, int n_q, const glims_observable* q, double* out);
+/* cumulative since glims_create: out[0] cell passes, [1] elastic solves, [2] sources observed, [3] 0 */
+int glims_observe_info(const glims_ctx* h, int64_t out[4]);
 
 /* ---- single-node multi-GPU (one process per GPU, RCCL over xGMI) ------------------------------------- */
 
