@@ -355,7 +355,9 @@ class Handle:
         """which: 0 A(c), 1 S, 2 M, 3 K_el, 4 G; 7 the matrix-free A(c) x; 8 the assembly sweep at c = x with b = 0,
         y = -1/2 (A(x) + S) x; 9 the quadratic-term pass with a = delta = x, y = -reps dt N(x) x; 10 = M x + rd_load as the
         stepping path's sweep forms it; 11 the quadratic-term pass prepared as the stepper prepares it from x and the state c,
-        y = -reps dt N(x + c) (x - c) (needs a state).  Hooks 9 and 11 return Dirichlet rows as 0 (glims_hip.h).
+        y = -reps dt N(x + c) (x - c) (needs a state); 12 (test hook) y_i = dinv_i x_i with the inverse diagonal the most
+        recent assembly sweep left (1 on Dirichlet rows; GLIMS_E_USAGE before any sweep).  Hooks 9 and 11 return Dirichlet
+        rows as 0 (glims_hip.h).
         Returns (y, ms_total)."""
         d = self.dim
         nin = self.n_nodes * (d if which == 3 else 1)

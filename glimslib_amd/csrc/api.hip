@@ -39,6 +39,12 @@ __global__ void k_perm_out(int64_t n, int64_t n_valid_new, int bs, const int32_t
   ext[i] = nw < n_valid_new ? in[nw * bs + a] : 0.0;
 }
 
+// y_i = d_i x_i over the owned rows (glims_apply 12)
+__global__ void k_scale_rows(int64_t n, const double* __restrict__ d, const double* __restrict__ x, double* __restrict__ y) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) y[i] = d[i] * x[i];
+}
+
 inline unsigned grid_exact(int64_t n, int bs = 256) { return (unsigned)((n + bs - 1) / bs); }
 
 void to_device_perm(glims_ctx* h, const double* host, double* dst, int bs) {
@@ -254,6 +260,7 @@ int glims_create(glims_ctx** out, int dim, int64_t n_nodes, int64_t n_own, int64
     h->c_old.alloc_zero(nn, h->st);
     h->b.alloc_zero(nn, h->st);
     h->dinv.alloc_zero(nn, h->st);
+    h->swept = false;
     h->cg_p.alloc_zero(nn, h->st);
     h->cg_s.alloc_zero(nn, h->st);
     h->cg_u.alloc_zero(nn, h->st);
@@ -656,13 +663,14 @@ int glims_apply(glims_ctx* h, int which, const double* x, double* y, int reps, d
   return guarded(h, [&]() {
     GL_REQUIRE(h->is_setup, "glims_apply before glims_setup");
     GL_REQUIRE(x && y && reps >= 1, "bad arguments");
-    GL_REQUIRE(which >= 0 && which <= 11 && which != 6, "unknown operator");
+    GL_REQUIRE(which >= 0 && which <= 12 && which != 6, "unknown operator");
+    if (which == 12) GL_REQUIRE(h->swept, "no assembly sweep has run on this handle: its diagonal is not formed yet");
     if (which == 10)
       GL_REQUIRE(gl_rd_mass_in_sweep(h), "the sweep does not form the mass product on this handle (GLIMS_FLAG_NO_FUSED_MASS, "
                                          "several ranks, fp32 Jacobian, or rows of more than 32 entries)");
     if (which == 7) GL_REQUIRE(h->have_state, "the matrix-free product needs the state c (glims_set_state)");
     if (which == 11) GL_REQUIRE(h->have_state, "the quadratic-term pass with a != delta needs the state c (glims_set_state)");
-    if (which >= 8) h->prepared.drop();   // the sweep rewrites A(c), dinv and the Krylov work vectors
+    if (which >= 8 && which != 12) h->prepared.drop();   // the sweep rewrites A(c), dinv and the Krylov work vectors
     const int d = h->dim;
     const bool blk_in = which == 3, blk_out = which == 3 || which == 4;
     if (blk_out) GL_REQUIRE(h->have_mech, "mechanics operators not assembled");
@@ -700,6 +708,10 @@ int glims_apply(glims_ctx* h, int which, const double* x, double* y, int reps, d
         h->nq_ad.alloc((size_t)2 * h->n_nodes);   // y -= dt N(x + c) (x - c) per repetition
         gl_quad_prep(h, xin.p, h->c.p, zero_b.p, h->nq_ad.p);
         gl_rd_quad(h, h->nq_ad.p, yout.p, h->partials.p);
+      }
+      else if (which == 12) {   // y = dinv x with the diagonal the most recent sweep left (nothing else is launched or touched)
+        if (h->n_own > 0)
+          hipLaunchKernelGGL(k_scale_rows, dim3(grid_exact(h->n_own)), dim3(256), 0, h->st, h->n_own, h->dinv.p, xin.p, yout.p);
       }
       else if (which == 5)   // A x with the fused dot product of the Krylov iteration (timing studies)
         gl_launch_spmv(h, h->st, h->pat.n_slices, nullptr, h->vA.p, xin.p, yout.p, nullptr, nullptr, xin.p,

@@ -619,6 +619,7 @@ struct glims_ctx {
   dvec<float> vKel32;                      // single-precision copy of K_el (inner solves of the elasticity solver)
   // vectors (internal numbering; length n_nodes unless noted)
   dvec<double> c, c_old, b, load_rd, dinv;
+  bool swept = false;                      // an assembly sweep has written dinv since the vectors were allocated (glims_apply 12)
   dvec<double> cg_p, cg_s, cg_u, cg_w, cg_r, cg_r2, b2;     // scalar CG work vectors; r2/b2: speculative next step
   // Newton residuals from the quadratic structure (k_rd_quad): the step's first iterate c_0 (whose Jacobian the solves
   // use), the iterate before the last solve, and the two staged vectors a = c_new + c_k - 2 c_0, delta = c_new - c_k

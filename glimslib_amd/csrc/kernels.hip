@@ -2257,6 +2257,7 @@ void gl_rd_assemble(glims_ctx* h, const double* c, const double* b, const double
   }
   if (any_rec32) h->stats.rd_rec32_sweeps++;
   GL_HIP(hipGetLastError());
+  h->swept = true;   // (a sweep in two parts launches both before anything reads dinv)
 }
 
 // r <- r - dt N(a) delta and the partial sums of |r|^2; same launch shape as the sweep

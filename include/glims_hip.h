@@ -472,6 +472,11 @@ int glims_reset_stats(glims_ctx* h);
  *        starts at 0: y <- y - dt N(x + c) (x - c), so `reps` repetitions return -reps dt N(x + c) (x - c).  Rows returned as
  *        0 and the slice sums: as for which = 9.  Like which = 8 .. 10 it drops the system a previous step prepared; the state
  *        and A(c) are not touched.
+ *        12 = TEST HOOK: y_i = dinv_i x_i with the inverse diagonal as the most recent assembly sweep left it (glims_apply
+ *        8 | 10, glims_rd_residual, a step): 1 / A_ii of that sweep's iterate, and exactly 1 on rows with a Dirichlet value of
+ *        the concentration.  It feeds Jacobi-PCG and the folded first iterate and is visible nowhere else.  Nothing but the
+ *        product is launched; the state, A(c) and a prepared system are not touched.  GLIMS_E_USAGE before any sweep has run
+ *        on the handle.
  *        Ghost rows of y are returned as 0. */
 int glims_apply(glims_ctx* h, int which, const double* x, double* y, int reps, double* ms_total);
 

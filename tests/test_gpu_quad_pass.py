@@ -207,7 +207,7 @@ def test_misuse(backend):
         h.apply(11, x)
     assert ei.value.code == backend.GLIMS_E_USAGE and "needs the state" in str(ei.value)
     with pytest.raises(backend.BackendError) as ei:
-        h.apply(12, x)
+        h.apply(13, x)
     assert ei.value.code == backend.GLIMS_E_USAGE and "unknown operator" in str(ei.value)
     h.apply(9, x)                          # no state needed
     h.set_state(w.c0)
