@@ -460,9 +460,7 @@ int solve_elastic(glims_ctx* h, AdjWork& wk, const double* rhs, double* x, const
   const int bs = h->dim;
   const int64_t nd = h->n_own * bs;
   const uint8_t* fx = h->have_fixed_u ? h->fixed_u.p : nullptr;
-  const bool use_mg = h->opt.mech_precond == GLIMS_PRECOND_MULTIGRID;
-  if (use_mg && !h->mg.ready) gl_mg_setup_mech(h);
-  else if (!use_mg) gl_block_dinv(h);
+  const bool use_mg = gl_mech_precondition(h);
   // r = rhs - K xD on the free dofs, x = 0
   GL_HIP(hipMemsetAsync(x, 0, (size_t)h->n_nodes * bs * sizeof(double), h->st));
   if (fx && xD) {

@@ -333,10 +333,10 @@ int glims_destroy(glims_ctx* h) {
 int glims_set_materials(glims_ctx* h, int n_labels, const double* D, const double* rho, const double* gamma,
                         const double* E, const double* nu) {
   return guarded(h, [&]() {
-    h->mh_count = h->mh_next = 0;   // the elasticity solve history belongs to one operator
+    h->mech.forget_operator();
     h->mg.ready = h->mg_rd.ready = false;
     h->rd_precond_active = 0;
-    h->derive.forget_u();           // ... and so does the displacement a derive solved (and the projected stress)
+    h->derive.forget_u();           // the displacement a derive solved (and the projected stress) belongs to one operator too
     GL_REQUIRE(n_labels > 0 && n_labels <= GL_MAX_LABELS, "n_labels out of range");
     GL_REQUIRE(D && rho && gamma && E && nu, "null material table");
     std::vector<double> m(5 * GL_MAX_LABELS, 0.0);
@@ -397,7 +397,7 @@ int glims_set_options(glims_ctx* h, const glims_options* opt) {
     }
     // the solve history is a ring of `mech_history` slots: a new depth starts an empty ring (a larger depth would
     // otherwise count never-allocated slots as stored solves)
-    if (opt->mech_history != h->opt.mech_history) h->mh_count = h->mh_next = 0;
+    if (opt->mech_history != h->opt.mech_history) h->mech.forget_operator();
     if (opt->dt != h->opt.dt) h->is_setup = false;
     if ((opt->flags ^ h->opt.flags) & (GLIMS_FLAG_FP32_JACOBIAN | GLIMS_FLAG_INT32_COLUMNS)) h->is_setup = false;
     if (opt->stream_policy != h->opt.stream_policy) h->is_setup = false;
@@ -447,8 +447,8 @@ int glims_set_dirichlet_c(glims_ctx* h, int64_t n, const int64_t* node_ids, cons
 
 int glims_set_dirichlet_u(glims_ctx* h, int64_t n, const int64_t* dof_ids, const double* values) {
   return guarded(h, [&]() {
-    h->mh_count = h->mh_next = 0;   // the elasticity solve history belongs to one operator
-    h->mg.ready = false;            // ... and so does the multigrid hierarchy (constrained dofs are eliminated in it)
+    h->mech.forget_operator();
+    h->mg.ready = false;            // the multigrid hierarchy belongs to one operator too (constrained dofs are eliminated in it)
     h->derive.forget_u();
     if (n <= 0) {
       h->have_fixed_u = false;
@@ -504,13 +504,12 @@ int glims_set_mech_load(glims_ctx* h, const double* f) {
 
 int glims_setup(glims_ctx* h, int with_mechanics) {
   return guarded(h, [&]() {
-    h->mh_count = h->mh_next = 0;   // the elasticity solve history belongs to one operator
+    h->mech.forget_run();
     h->mg.ready = h->mg_rd.ready = false;
     h->rd_precond_active = 0;       // decided by the first glims_step (a collective in partitioned runs)
     h->derive.forget_u();
     h->stats.rd_precond_used = 0;
     for (int& hint : h->run.cg_hint) hint = 0;
-    h->mech_hint = 0;
     GL_REQUIRE(h->have_materials, "glims_setup before glims_set_materials");
     h->adj.invalidate("glims_setup after recording started");
     if (with_mechanics) {
@@ -566,8 +565,7 @@ int glims_set_state(glims_ctx* h, const double* c, const double* u) {
     // operators, both multigrid hierarchies and the preconditioner `auto` has settled on; they depend on the mesh and the
     // parameters, not on the run.)
     h->run = RunMemory();
-    h->mech_hint = 0;
-    h->mh_count = h->mh_next = 0;   // ... and the elasticity solver's history of right-hand sides
+    h->mech.forget_run();   // ... and the elasticity solver's history of right-hand sides and its iteration hint
     to_device_perm(h, c, h->c.p, 1);
     h->have_state = true;
     h->dirichlet_c_dirty = h->have_fixed_c;

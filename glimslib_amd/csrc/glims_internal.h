@@ -10,6 +10,7 @@
 #include <stdexcept>
 #include "../../include/glims_hip.h"
 #include "step_policy.h"
+#include "mech_policy.h"
 
 #define GL_WAVE 64                 // wavefront width of CDNA4; SELL slice height
 #define GL_SIGMA 256               // sigma window (rows) of the SELL-C-sigma row sort (tools/sigma_sweep.py: on an
@@ -529,6 +530,24 @@ struct ObserveState {
   int64_t n_cell_passes = 0, n_elastic_solves = 0, n_sources = 0;   // glims_observe_info
 };
 
+// What gl_solve_mechanics remembers from one solve to the next.  The history of solved elasticity problems (right-hand side,
+// free-dof solution): the operator is linear and time independent, so the least-squares fit of a new right-hand side by the
+// stored ones gives the initial guess (mech_policy.h).  The history belongs to ONE elastic operator -- whatever changes K_el or
+// the set of constrained dofs calls forget_operator() --, and with the iteration hint to one run: glims_setup and
+// glims_set_state call forget_run(), so that a restarted run takes the iteration path of a fresh handle.  (The hint only sizes the
+// first batch of cg_solve's launches, so forget_operator() leaves it alone.)  The device arrays stay allocated either way.
+struct MechMemory {
+  MechRing ring;
+  dvec<double> rhs[GL_MHIST], x[GL_MHIST], w[GL_MHIST];   // right-hand sides, solutions, K_el x (= rhs - final residual)
+  double G[GL_MHIST][GL_MHIST] = {{0.0}};  // Gram matrix (rhs_k, rhs_l) of the stored right-hand sides (host copy)
+  int hint = 0;                            // PCG iterations of the last fp64 solve
+  void forget_operator() { ring.restart(); }
+  void forget_run() {
+    ring.restart();
+    hint = 0;
+  }
+};
+
 struct glims_ctx {
   int dim = 0, nv = 0, device = 0;
   int n_labels = 0;                        // of the last glims_set_materials
@@ -625,13 +644,7 @@ struct glims_ctx {
   // use), the iterate before the last solve, and the two staged vectors a = c_new + c_k - 2 c_0, delta = c_new - c_k
   dvec<double> nq_c0, nq_ck;
   dvec<float> nq_ad;                                          // (a, delta) pairs, single precision (see k_rd_quad)
-  int mech_hint = 0;
-  // history of solved elasticity problems (right-hand side, free-dof solution): the operator is linear and time
-  // independent, so the least-squares fit of a new right-hand side by the stored ones gives the initial guess
-  static constexpr int MHIST = 16;  // upper bound of glims_options.mech_history
-  dvec<double> mh_rhs[MHIST], mh_x[MHIST], mh_w[MHIST];   // solve history: right-hand sides, solutions, K_el x (= rhs - final residual)
-  int mh_count = 0, mh_next = 0;           // depth: glims_options.mech_history
-  double mh_G[MHIST][MHIST] = {{0.0}};     // Gram matrix (rhs_k, rhs_l) of the stored right-hand sides (host copy)
+  MechMemory mech;                         // what the elasticity solve remembers from one solve to the next
   dvec<double> ws_du;                                         // the increment of the step before the last (warm start, k_ws_delta; run.ws_depth)
   PreparedStep prepared;                                      // the next step, where the last sweep already assembled it
   dvec<double> fg_part;                                       // a fused guess pass's sums of |b - A u|^2 per slice (reduced with the sweep's norms)
@@ -770,6 +783,7 @@ void gl_pair_of(glims_ctx* h, const double* u, float* ad /*[n_nodes][2]*/);   //
 void gl_quad_prep(glims_ctx* h, const double* c_new, const double* c_k, const double* c_0, float* ad /*[n_nodes][2]*/);
 void gl_apply_dirichlet_c(glims_ctx* h);                                     // c[fixed] = stored values (+ halo)
 void gl_block_dinv(glims_ctx* h);                                            // m_dinv of the constrained K_el
+bool gl_mech_precondition(glims_ctx* h);   // the elasticity solves' preconditioner, ready to use; returns: it is the multigrid
 
 // PCG with caller-owned vectors (the time stepper's work vectors stay untouched): on entry r = residual of x.  vals = scalar
 // operator plane (bs = 1, Jacobi `dinv`) or nullptr (K_el blocks, bs = dim, block-Jacobi `dinv`); mg: V-cycle instead

@@ -491,6 +491,12 @@ __global__ void k_sub(int64_t n, double* __restrict__ y, const double* __restric
   if (i < n) y[i] = (fixed && fixed[i]) ? 0.0 : a[i] - b[i];
 }
 
+__global__ void k_sub_from(int64_t n, double* __restrict__ y, const double* __restrict__ b,
+                           const uint8_t* __restrict__ fixed) {   // y -= b, 0 on fixed dofs
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) y[i] = (fixed && fixed[i]) ? 0.0 : y[i] - b[i];
+}
+
 __global__ void k_mask_assign(int64_t n, double* __restrict__ y, const uint8_t* __restrict__ fixed,
                               const double* __restrict__ vals) {   // y[fixed] = vals ? vals[i] : 0
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2375,243 +2381,222 @@ int gl_project(glims_ctx* h, double* rhs, double* x, double rtol) {
 // ===================================================================================================
 // mechanics:  K_el u = G c + f,  Dirichlet dofs eliminated symmetrically (projected operator P K P)
 // ===================================================================================================
-int gl_solve_mechanics(glims_ctx* h, const double* c_dev) {
-  GL_REQUIRE(h->is_setup && h->have_mech, "glims_solve_mechanics needs glims_setup(with_mechanics=1)");
-  GL_REQUIRE(h->have_state, "glims_solve_mechanics before glims_set_state");
-  const DevPattern& p = h->pat;
-  const int bs = h->dim;
-  const int64_t nd = h->n_own * bs;
-  const uint8_t* fx = h->have_fixed_u ? h->fixed_u.p : nullptr;
-  const int mh_depth = std::max(0, std::min((int)glims_ctx::MHIST, h->opt.mech_history));
-  if (h->mh_next >= std::max(1, mh_depth)) h->mh_count = h->mh_next = 0;   // the depth option shrank
-  const double t_wall0 = omp_get_wtime();
-  if (h->opt.time_kernels) h->timing_begin();   // (kernel pairs: time_kernels = 3 only; exchange pairs of a partitioned run: any)
-  // preconditioner of the constrained operator: one multigrid V-cycle (built on first use, K_el does not change in
-  // time) or block-Jacobi
+// gl_solve_mechanics is a sequence of the phases below.  What the handle remembers between solves is h->mech (MechMemory),
+// what one solve knows about itself MechSolve; the fit and the scalar rules are in mech_policy.h.
+struct MechSolve {
+  int bs = 0;
+  int64_t nd = 0;               // owned dofs
+  const uint8_t* fx = nullptr;  // constrained dofs (nullptr: none)
+  unsigned gd = 0;              // grid of the reductions
+  bool use_mg = false, verbose = false;   // (verbose: GLIMS_VERBOSE, read once per call)
+  int depth = 0, m_hist = 0;    // slots of the ring; stored solves the guess is fitted to
+  double g[GL_MHIST] = {0.0};   // (rhs_k, rhs) against the stored right-hand sides
+  double nb2 = 0.0, nb = 0.0, tol = 0.0;   // ||rhs||^2, ||rhs||, absolute tolerance of the solve
+};
+
+// preconditioner of the constrained operator: one multigrid V-cycle (built on first use, K_el does not change in
+// time) or block-Jacobi
+bool gl_mech_precondition(glims_ctx* h) {
   const bool use_mg = h->opt.mech_precond == GLIMS_PRECOND_MULTIGRID;
   if (use_mg && !h->mg.ready) gl_mg_setup_mech(h);
   else if (!use_mg) gl_block_dinv(h);
-  // rhs = G c + f - K u_D, zero on constrained dofs
+  return use_mg;
+}
+
+// rhs = G c + f - K u_D, zero on constrained dofs
+static void mech_rhs(glims_ctx* h, const MechSolve& s, const double* c_dev) {
   gl_apply_G(h, c_dev ? c_dev : h->c.p, h->m_rhs.p);
-  if (fx) {
-    gl_halo_exchange(h, h->m_uD.p, bs);
+  if (s.fx) {
+    gl_halo_exchange(h, h->m_uD.p, s.bs);
     gl_spmv_block(h, h->m_uD.p, h->m_w.p, false);
-    hipLaunchKernelGGL(k_sub, dim3(grid_exact(nd)), dim3(256), 0, h->st, nd, h->m_rhs.p, h->m_rhs.p, h->m_w.p, fx);
+    hipLaunchKernelGGL(k_sub_from, dim3(grid_exact(s.nd)), dim3(256), 0, h->st, s.nd, h->m_rhs.p, h->m_w.p, s.fx);
   }
-  // ||rhs||^2 for the relative tolerance and g_k = (rhs_k, rhs) against the stored right-hand sides of the solve
-  // history: three products per pass over rhs and one host read per pass (one product per launch and read cost 27
-  // round trips = 0.8 ms per solve at depth 6); the Gram matrix of the stored right-hand sides is kept on the host
-  // and grows by the row g when this solve's right-hand side is stored
-  const unsigned gd = grid_for(nd, 256, 1024);
-  const int m_hist = (h->mh_count > 0 && mh_depth > 0) ? h->mh_count : 0;
-  double g[glims_ctx::MHIST] = {0.0};
-  double nb2 = 0.0;
-  for (int q0 = -1; q0 < m_hist; q0 += 3) {   // value -1 = (rhs, rhs), values 0.. = (rhs_k, rhs)
+}
+
+// ||rhs||^2 for the relative tolerance and g_k = (rhs_k, rhs) against the stored right-hand sides of the solve
+// history: three products per pass over rhs and one host read per pass (one product per launch and read cost 27
+// round trips = 0.8 ms per solve at depth 6); the Gram matrix of the stored right-hand sides is kept on the host
+// and grows by the row g when this solve's right-hand side is stored
+static void mech_history_products(glims_ctx* h, MechSolve& s) {
+  for (int q0 = -1; q0 < s.m_hist; q0 += 3) {   // value -1 = (rhs, rhs), values 0.. = (rhs_k, rhs)
     Dot3 dv;
-    const int nq = std::min(3, m_hist - q0);
+    const int nq = std::min(3, s.m_hist - q0);
     for (int q = 0; q < 3; ++q) {
       const int k = q0 + q;
-      dv.a[q] = (q < nq) ? (k < 0 ? h->m_rhs.p : h->mh_rhs[k].p) : h->m_rhs.p;
+      dv.a[q] = (q < nq) ? (k < 0 ? h->m_rhs.p : h->mech.rhs[k].p) : h->m_rhs.p;
     }
-    hipLaunchKernelGGL(k_dot3, dim3(gd), dim3(256), 0, h->st, nd, nq, dv, h->m_rhs.p, h->partials.p);
+    hipLaunchKernelGGL(k_dot3, dim3(s.gd), dim3(256), 0, h->st, s.nd, nq, dv, h->m_rhs.p, h->partials.p);
     GL_HIP(hipGetLastError());
-    reduce_partials(h, (int)gd, nq, nullptr);
+    reduce_partials(h, (int)s.gd, nq, nullptr);
     allreduce_sum(h, h->red.p, nq);   // partitioned run: every rank gets the same sums, hence the same coefficients
     double out[3];
     read_red(h, nq, out);
     for (int q = 0; q < nq; ++q) {
       const int k = q0 + q;
-      if (k < 0) nb2 = out[q];
-      else g[k] = out[q];
+      if (k < 0) s.nb2 = out[q];
+      else s.g[k] = out[q];
     }
   }
-  const double nb = std::sqrt(nb2);
-  if (!std::isfinite(nb)) return GLIMS_NAN;
-  const double tol = std::max(h->opt.mech_atol, h->opt.mech_rtol * nb);
-  // Initial guess.  K_el is linear and does not change in time, so if rhs ~ sum_k a_k rhs_k for previously solved
-  // right-hand sides then x ~ sum_k a_k x_k with residual rhs - sum_k a_k rhs_k: least-squares fit over the stored
-  // solves; the concentration evolves smoothly, the fit removes several decades of the initial residual.
-  // Falls back to the previous displacement (the fit with a = e_last) when that is better or the history is empty.
-  if (m_hist > 0) {
-    const int m = m_hist;
-    double (*G)[glims_ctx::MHIST] = h->mh_G;
-    // normal equations with a small ridge (the right-hand sides of consecutive steps are nearly parallel)
-    double a[glims_ctx::MHIST] = {0.0};
-    {
-      double A[glims_ctx::MHIST][glims_ctx::MHIST + 1];
-      double tr = 0.0;
-      for (int k = 0; k < m; ++k) tr += G[k][k];
-      for (int k = 0; k < m; ++k) {
-        for (int l = 0; l < m; ++l) A[k][l] = G[k][l] + (k == l ? 1e-13 * tr : 0.0);
-        A[k][m] = g[k];
-      }
-      bool ok = true;
-      for (int c = 0; c < m && ok; ++c) {   // Gaussian elimination with partial pivoting on the m x m system
-        int piv = c;
-        for (int r = c + 1; r < m; ++r)
-          if (std::fabs(A[r][c]) > std::fabs(A[piv][c])) piv = r;
-        if (!(std::fabs(A[piv][c]) > 0.0)) {
-          ok = false;
-          break;
-        }
-        for (int q = 0; q <= m; ++q) std::swap(A[c][q], A[piv][q]);
-        for (int r = c + 1; r < m; ++r) {
-          const double f = A[r][c] / A[c][c];
-          for (int q = c; q <= m; ++q) A[r][q] -= f * A[c][q];
-        }
-      }
-      if (ok)
-        for (int c = m - 1; c >= 0; --c) {
-          double v = A[c][m];
-          for (int q = c + 1; q < m; ++q) v -= A[c][q] * a[q];
-          a[c] = v / A[c][c];
-        }
-      // predicted squared residual of the fit against the plain warm start (most recent solution alone)
-      auto res2 = [&](const double* coef) {
-        double v = nb * nb;
-        for (int k = 0; k < m; ++k) {
-          v -= 2.0 * coef[k] * g[k];
-          for (int l = 0; l < m; ++l) v += coef[k] * coef[l] * G[k][l];
-        }
-        return v;
-      };
-      double e_last[glims_ctx::MHIST] = {0.0};
-      const int last = (h->mh_next + mh_depth - 1) % mh_depth;
-      e_last[last] = 1.0;
-      bool finite = ok;
-      for (int k = 0; k < m; ++k) finite = finite && std::isfinite(a[k]);
-      if (!finite || !(res2(a) <= res2(e_last)))
-        for (int k = 0; k < m; ++k) a[k] = e_last[k];
-    }
+  s.nb = std::sqrt(s.nb2);
+}
+
+// m_r = rhs - m_w on the free dofs, with m_w = K U (U's ghosts are current) unless the caller has that product already
+static void mech_residual(glims_ctx* h, const MechSolve& s, bool have_product) {
+  if (!have_product)
+    gl_launch_spmv_block(h, h->st, h->pat.n_slices, nullptr, h->U.p, h->m_w.p, s.fx, nullptr, nullptr, 0, nullptr);
+  hipLaunchKernelGGL(k_sub, dim3(grid_exact(s.nd)), dim3(256), 0, h->st, s.nd, h->m_r.p, h->m_rhs.p, h->m_w.p, s.fx);
+  GL_HIP(hipGetLastError());
+}
+
+static double mech_norm_of_r(glims_ctx* h, const MechSolve& s) {
+  hipLaunchKernelGGL(k_dot_partials, dim3(s.gd), dim3(256), 0, h->st, s.nd, h->m_r.p, h->m_r.p, h->partials.p);
+  reduce_partials(h, (int)s.gd, 1, nullptr);
+  allreduce_sum(h, h->red.p, 1);
+  return std::sqrt(read_red0(h));
+}
+
+// the true residual of U with the fp64 operator: m_w = K U, m_r = rhs - K U; returns ||m_r||
+static double mech_true_residual(glims_ctx* h, const MechSolve& s) {
+  gl_halo_exchange(h, h->U.p, s.bs);
+  mech_residual(h, s, false);
+  return mech_norm_of_r(h, s);
+}
+
+// Initial guess from the solve history (mech_policy.h, mech_history_fit) or the previous displacement, and its residual
+static void mech_guess(glims_ctx* h, const MechSolve& s) {
+  const MechMemory& mem = h->mech;
+  if (s.m_hist > 0) {
+    const int m = s.m_hist;
+    double a[GL_MHIST];
+    mech_history_fit(m, mem.G, s.g, s.nb, mem.ring.last(s.depth), a);
     LinComb lc;
     for (int k = 0; k < 16; ++k) {
-      lc.x[k] = h->mh_x[k < m ? k : 0].p;
+      lc.x[k] = mem.x[k < m ? k : 0].p;
       lc.a[k] = k < m ? a[k] : 0.0;
     }
-    hipLaunchKernelGGL(k_lincomb, dim3(grid_exact(nd)), dim3(256), 0, h->st, nd, m, lc, h->U.p);
+    hipLaunchKernelGGL(k_lincomb, dim3(grid_exact(s.nd)), dim3(256), 0, h->st, s.nd, m, lc, h->U.p);
     // K_el of that combination without an operator pass: K x_k = rhs_k - (final residual of solve k) was stored with x_k
-    for (int k = 0; k < 16; ++k) lc.x[k] = h->mh_w[k < m ? k : 0].p;
-    hipLaunchKernelGGL(k_lincomb, dim3(grid_exact(nd)), dim3(256), 0, h->st, nd, m, lc, h->m_w.p);
+    for (int k = 0; k < 16; ++k) lc.x[k] = mem.w[k < m ? k : 0].p;
+    hipLaunchKernelGGL(k_lincomb, dim3(grid_exact(s.nd)), dim3(256), 0, h->st, s.nd, m, lc, h->m_w.p);
     GL_HIP(hipGetLastError());
   }
   // x = guess on the free dofs (previous displacement if there is no history), 0 on constrained ones
-  if (fx) hipLaunchKernelGGL(k_mask_assign, dim3(grid_exact(nd)), dim3(256), 0, h->st, nd, h->U.p, fx,
-                             (const double*)nullptr);
-  gl_halo_exchange(h, h->U.p, bs);
-  if (m_hist == 0) gl_launch_spmv_block(h, h->st, p.n_slices, nullptr, h->U.p, h->m_w.p, fx, nullptr, nullptr, 0, nullptr);
-  hipLaunchKernelGGL(k_sub, dim3(grid_exact(nd)), dim3(256), 0, h->st, nd, h->m_r.p, h->m_rhs.p, h->m_w.p, fx);
-  GL_HIP(hipGetLastError());
-  CgVecs v{h->U.p, h->m_r.p, h->m_u.p, h->m_w.p, h->m_p.p, h->m_s.p, h->m_dinv.p, nullptr, fx, bs};
-  v.mg = use_mg ? &h->mg : nullptr;
+  if (s.fx) hipLaunchKernelGGL(k_mask_assign, dim3(grid_exact(s.nd)), dim3(256), 0, h->st, s.nd, h->U.p, s.fx,
+                               (const double*)nullptr);
+  gl_halo_exchange(h, h->U.p, s.bs);
+  mech_residual(h, s, s.m_hist > 0);
+}
+
+// fp64 solve.  Verification pass with the fp64 operator: m_w = K U, m_r = rhs - K U.  The recurrence residual the Krylov
+// iteration stops on drifts away from the true one by rounding, and the solve history keeps K x_k for the next solves'
+// initial residuals -- it must be the product itself, not "rhs minus what the recurrence believes", or the gap of one
+// solve enters every later one through the (sign-alternating) least-squares coefficients and is never seen again.
+// One operator pass per solve (0.23 ms of ~10 at config C5).  If the true residual misses the tolerance by more than
+// the drift one expects, the iteration continues from it.
+static int mech_solve_fp64(glims_ctx* h, const MechSolve& s, const CgVecs& v, int64_t* its, double* res) {
+  int cs = cg_solve(h, v, s.tol, h->opt.mech_maxit, h->mech.hint, its, res);
+  h->mech.hint = (int)*its;
+  for (int round = 0; cs == GLIMS_OK; ++round) {
+    *res = mech_true_residual(h, s);
+    if (!std::isfinite(*res)) return GLIMS_NAN;
+    if (s.verbose)
+      fprintf(stderr, "glims elasticity solve: %lld iterations, recurrence residual <= %.3e, true residual %.3e (%.2f x the tolerance)\n",
+              (long long)*its, s.tol, *res, *res / s.tol);
+    if (mech_verify_done(*res, s.tol, round)) break;
+    int64_t more = 0;
+    double r2 = 0.0;
+    cs = cg_solve(h, v, s.tol, h->opt.mech_maxit, 0, &more, &r2);
+    *its += more;
+  }
+  return cs;
+}
+
+// Mixed precision: the inner PCG streams a single-precision copy of K_el (40 instead of 76 bytes per block entry;
+// products and sums in fp64) and reduces the residual by mech_inner_tol; the outer loop recomputes the true residual with
+// the fp64 operator and repeats.  The answer converges to the fp64 tolerance like the plain solver's (iterative
+// refinement); if a cycle gains less than a factor 2 the remaining ones use the fp64 operator.
+static int mech_solve_mixed(glims_ctx* h, const MechSolve& s, CgVecs& v, int64_t* its, double* res) {
+  gl_make_kel32(h);
+  double nr = mech_norm_of_r(h, s);
+  v.k32 = true;
+  for (int outer = 0; outer < GL_MECH_OUTER; ++outer) {
+    *res = nr;
+    if (!std::isfinite(nr)) return GLIMS_NAN;
+    if (nr <= s.tol) break;
+    if (*its >= h->opt.mech_maxit || outer == GL_MECH_OUTER - 1) return GLIMS_NOT_CONVERGED;
+    int64_t in_its = 0;
+    double in_res = 0.0;
+    const int ics = cg_solve(h, v, mech_inner_tol(s.tol, nr), (int)std::max<int64_t>(1, h->opt.mech_maxit - *its), 0,
+                             &in_its, &in_res);
+    *its += in_its;
+    if (ics == GLIMS_NAN) return ics;
+    const double nr_new = mech_true_residual(h, s);
+    if (mech_fp32_exhausted(nr_new, nr)) v.k32 = false;   // single precision has given what it can
+    nr = nr_new;
+  }
+  return GLIMS_OK;
+}
+
+// remember (rhs, free-dof solution) for the next initial guess
+static void mech_remember(glims_ctx* h, const MechSolve& s) {
+  MechMemory& mem = h->mech;
+  const int slot = mem.ring.next;
+  const size_t len = (size_t)h->n_nodes * s.bs, bytes = (size_t)s.nd * sizeof(double);
+  mem.rhs[slot].alloc(len);
+  mem.x[slot].alloc(len);
+  GL_HIP(hipMemcpyAsync(mem.rhs[slot].p, h->m_rhs.p, bytes, hipMemcpyDeviceToDevice, h->st));
+  GL_HIP(hipMemcpyAsync(mem.x[slot].p, h->U.p, bytes, hipMemcpyDeviceToDevice, h->st));
+  // m_w = K U on the free dofs: the product of the verification pass itself (mech_solve_fp64), never "rhs - recurrence residual"
+  mem.w[slot].alloc(len);
+  GL_HIP(hipMemcpyAsync(mem.w[slot].p, h->m_w.p, bytes, hipMemcpyDeviceToDevice, h->st));
+  for (int l = 0; l < s.m_hist; ++l) mem.G[slot][l] = mem.G[l][slot] = s.g[l];   // g against the slots that stay
+  mem.G[slot][slot] = s.nb2;
+  mem.ring.advance(s.depth);
+}
+
+// the clamp values go back into U; every rank's ghosts are current when the call returns
+static void mech_finish(glims_ctx* h, const MechSolve& s) {
+  if (s.fx) hipLaunchKernelGGL(k_mask_assign, dim3(grid_exact(s.nd)), dim3(256), 0, h->st, s.nd, h->U.p, s.fx,
+                               (const double*)h->m_uD.p);
+  gl_halo_exchange(h, h->U.p, s.bs);
+  GL_HIP(hipStreamSynchronize(h->st));
+}
+
+int gl_solve_mechanics(glims_ctx* h, const double* c_dev) {
+  GL_REQUIRE(h->is_setup && h->have_mech, "glims_solve_mechanics needs glims_setup(with_mechanics=1)");
+  GL_REQUIRE(h->have_state, "glims_solve_mechanics before glims_set_state");
+  MechSolve s;
+  s.bs = h->dim;
+  s.nd = h->n_own * s.bs;
+  s.fx = h->have_fixed_u ? h->fixed_u.p : nullptr;
+  s.gd = grid_for(s.nd, 256, 1024);
+  s.verbose = getenv("GLIMS_VERBOSE") != nullptr;
+  s.depth = MechRing::depth_of(h->opt.mech_history);
+  h->mech.ring.fit_depth(s.depth);
+  s.m_hist = h->mech.ring.stored(s.depth);
+  const double t_wall0 = omp_get_wtime();
+  if (h->opt.time_kernels) h->timing_begin();   // (kernel pairs: time_kernels = 3 only; exchange pairs of a partitioned run: any)
+  s.use_mg = gl_mech_precondition(h);
+  mech_rhs(h, s, c_dev);
+  mech_history_products(h, s);
+  if (!std::isfinite(s.nb)) return GLIMS_NAN;
+  s.tol = std::max(h->opt.mech_atol, h->opt.mech_rtol * s.nb);
+  mech_guess(h, s);
+  CgVecs v{h->U.p, h->m_r.p, h->m_u.p, h->m_w.p, h->m_p.p, h->m_s.p, h->m_dinv.p, nullptr, s.fx, s.bs};
+  v.mg = s.use_mg ? &h->mg : nullptr;
   v.mg_degree = h->opt.mg_smooth;
   const int64_t cycles0 = h->mg.cycles;
   int64_t its = 0;
   double res = 0.0;
-  int cs = GLIMS_OK;
-  // Mixed precision (mech_mixed: 0 off, 1 auto, 2 always).  Auto = with the block-Jacobi preconditioner, where an
-  // iteration IS one operator pass, and only where the operator is streamed from HBM (below ~256 MB, the Infinity Cache,
-  // an iteration is latency bound and the restarts of the refinement loop only add iterations).  Never with the multigrid
-  // preconditioner: the operator pass is 7 % of an iteration there, and the restarts cost more than that -- C5 at 10 M
-  // nodes 102 vs 107 ms per solve, Delaunay 1 M points 99 vs 117 ms, and with a stiff inclusion (stiffness jump 1e4) the
-  // restarted iteration loses the superlinear phase of CG altogether: 11 iterations against 29-55.
-  const bool big = (size_t)p.total_entries * bs * bs * sizeof(double) > ((size_t)256 << 20);
-  const bool mixed = h->opt.mech_mixed == 2 || (h->opt.mech_mixed == 1 && big && !use_mg);
-  if (mixed) gl_make_kel32(h);
-  auto norm_of_m_r = [&]() {
-    hipLaunchKernelGGL(k_dot_partials, dim3(gd), dim3(256), 0, h->st, nd, h->m_r.p, h->m_r.p, h->partials.p);
-    reduce_partials(h, (int)gd, 1, nullptr);
-    allreduce_sum(h, h->red.p, 1);
-    return std::sqrt(read_red0(h));
-  };
-  if (!mixed) {
-    cs = cg_solve(h, v, tol, h->opt.mech_maxit, h->mech_hint, &its, &res);
-    h->mech_hint = (int)its;
-    // Verification pass with the fp64 operator: m_w = K U, m_r = rhs - K U.  The recurrence residual the Krylov iteration
-    // stops on drifts away from the true one by rounding, and the solve history below keeps K x_k for the next solves'
-    // initial residuals -- it must be the product itself, not "rhs minus what the recurrence believes", or the gap of one
-    // solve enters every later one through the (sign-alternating) least-squares coefficients and is never seen again.
-    // One operator pass per solve (0.23 ms of ~10 at config C5).  If the true residual misses the tolerance by more than
-    // the drift one expects, the iteration continues from it.
-    for (int round = 0; cs == GLIMS_OK; ++round) {
-      gl_halo_exchange(h, h->U.p, bs);
-      gl_launch_spmv_block(h, h->st, p.n_slices, nullptr, h->U.p, h->m_w.p, fx, nullptr, nullptr, 0, nullptr);
-      hipLaunchKernelGGL(k_sub, dim3(grid_exact(nd)), dim3(256), 0, h->st, nd, h->m_r.p, h->m_rhs.p, h->m_w.p, fx);
-      GL_HIP(hipGetLastError());
-      res = norm_of_m_r();
-      if (!std::isfinite(res)) {
-        cs = GLIMS_NAN;
-        break;
-      }
-      if (getenv("GLIMS_VERBOSE"))
-        fprintf(stderr, "glims elasticity solve: %lld iterations, recurrence residual <= %.3e, true residual %.3e (%.2f x the tolerance)\n",
-                (long long)its, tol, res, res / tol);
-      if (res <= 4.0 * tol || round >= 2) break;
-      int64_t more = 0;
-      double r2 = 0.0;
-      cs = cg_solve(h, v, tol, h->opt.mech_maxit, 0, &more, &r2);
-      its += more;
-    }
-  } else {
-    // Mixed precision: the inner PCG streams a single-precision copy of K_el (40 instead of 76 bytes per block entry;
-    // products and sums in fp64) and reduces the residual by 1e-3; the outer loop recomputes the true residual with
-    // the fp64 operator and repeats.  The answer converges to the fp64 tolerance like the plain solver's (iterative
-    // refinement); if a cycle gains less than a factor 2 the remaining ones use the fp64 operator.
-    double nr = norm_of_m_r();
-    v.k32 = true;
-    for (int outer = 0; outer < 12; ++outer) {
-      res = nr;
-      if (!std::isfinite(nr)) {
-        cs = GLIMS_NAN;
-        break;
-      }
-      if (nr <= tol) break;
-      if (its >= h->opt.mech_maxit || outer == 11) {
-        cs = GLIMS_NOT_CONVERGED;
-        break;
-      }
-      int64_t in_its = 0;
-      double in_res = 0.0;
-      // inner reduction 1e-6 (round 1: 1e-3): the single-precision operator is good for that, and with the
-      // solve-history guess (initial residual ~1e-6 |rhs|) ONE inner solve then reaches the target -- the loop costs
-      // two fp64 operator passes (initial residual, verification) instead of four to five
-      const int ics = cg_solve(h, v, std::max(tol, 1e-6 * nr), (int)std::max<int64_t>(1, h->opt.mech_maxit - its), 0,
-                               &in_its, &in_res);
-      its += in_its;
-      if (ics == GLIMS_NAN) {
-        cs = ics;
-        break;
-      }
-      gl_halo_exchange(h, h->U.p, bs);
-      gl_launch_spmv_block(h, h->st, p.n_slices, nullptr, h->U.p, h->m_w.p, fx, nullptr, nullptr, 0, nullptr);
-      hipLaunchKernelGGL(k_sub, dim3(grid_exact(nd)), dim3(256), 0, h->st, nd, h->m_r.p, h->m_rhs.p, h->m_w.p, fx);
-      GL_HIP(hipGetLastError());
-      const double nr_new = norm_of_m_r();
-      if (!(nr_new < 0.5 * nr)) v.k32 = false;   // single precision has given what it can
-      nr = nr_new;
-    }
-  }
+  const size_t operator_bytes = (size_t)h->pat.total_entries * s.bs * s.bs * sizeof(double);
+  const int cs = mech_mixed_wanted(h->opt.mech_mixed, operator_bytes, s.use_mg) ? mech_solve_mixed(h, s, v, &its, &res)
+                                                                                : mech_solve_fp64(h, s, v, &its, &res);
   h->stats.mech_cg_its += its;
   h->stats.mg_cycles += h->mg.cycles - cycles0;
   h->stats.mech_solves++;
   h->stats.last_mech_res = res;
-  if (cs == GLIMS_OK && mh_depth > 0) {   // remember (rhs, free-dof solution) for the next initial guess
-    const int slot = h->mh_next;
-    h->mh_rhs[slot].alloc((size_t)h->n_nodes * bs);
-    h->mh_x[slot].alloc((size_t)h->n_nodes * bs);
-    GL_HIP(hipMemcpyAsync(h->mh_rhs[slot].p, h->m_rhs.p, (size_t)nd * sizeof(double), hipMemcpyDeviceToDevice, h->st));
-    GL_HIP(hipMemcpyAsync(h->mh_x[slot].p, h->U.p, (size_t)nd * sizeof(double), hipMemcpyDeviceToDevice, h->st));
-    // m_w = K U on the free dofs: the product of the verification pass itself (see above), never "rhs - recurrence residual"
-    h->mh_w[slot].alloc((size_t)h->n_nodes * bs);
-    GL_HIP(hipMemcpyAsync(h->mh_w[slot].p, h->m_w.p, (size_t)nd * sizeof(double), hipMemcpyDeviceToDevice, h->st));
-    for (int l = 0; l < m_hist; ++l) h->mh_G[slot][l] = h->mh_G[l][slot] = g[l];   // g against the slots that stay
-    h->mh_G[slot][slot] = nb2;
-    h->mh_next = (slot + 1) % mh_depth;
-    h->mh_count = std::min(h->mh_count + 1, mh_depth);
-  }
-  if (fx) hipLaunchKernelGGL(k_mask_assign, dim3(grid_exact(nd)), dim3(256), 0, h->st, nd, h->U.p, fx,
-                             (const double*)h->m_uD.p);
-  gl_halo_exchange(h, h->U.p, bs);
-  GL_HIP(hipStreamSynchronize(h->st));
+  if (cs == GLIMS_OK && s.depth > 0) mech_remember(h, s);
+  mech_finish(h, s);
   h->stats.ms_mech += 1e3 * (omp_get_wtime() - t_wall0);
   if (h->opt.time_kernels) h->timing_collect();
   return cs;

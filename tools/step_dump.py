@@ -34,7 +34,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 FLOATS = ("last_newton_res", "last_cg_res", "cheb_lmin", "cheb_lmax")
 
 
-def compare(pa, pb):
+def compare(pa, pb, restarted="restarted", fresh="fresh_from_step8"):
     a, b = np.load(pa), np.load(pb)
     bad = sorted(set(a.files) ^ set(b.files))
     for k in bad:
@@ -49,12 +49,15 @@ def compare(pa, pb):
                 for j in np.flatnonzero((a[k] != b[k]).any(axis=0)):
                     print("    %-28s %s | %s" % (names[j], a[k][-1, j], b[k][-1, j]))
     print("%d arrays, %d differ" % (len(set(a.files) | set(b.files)), len(bad)))
-    # within each file: the run restarted with set_state against the fresh handle started from the same state
+    # within each file: the run restarted with set_state against the fresh handle started from the same state (printed, not
+    # part of the verdict; files without such a pair have nothing to print)
     for path, f in ((pa, a), (pb, b)):
-        for k in ("c", "counters", "residuals"):
-            x, y = f["restarted/" + k], f["fresh_from_step8/" + k]
-            print("%-24s restarted/%-10s vs fresh_from_step8/%-10s %s" %
-                  (os.path.basename(path), k, k, "equal" if x.shape == y.shape and np.array_equal(x, y) else "DIFFERENT"))
+        for k in sorted(k[len(restarted) + 1:] for k in f.files if k.startswith(restarted + "/") and not k.endswith("_names")):
+            if fresh + "/" + k not in f.files:
+                continue
+            x, y = f[restarted + "/" + k], f[fresh + "/" + k]
+            print("%-24s %s/%-10s vs %s/%-10s %s" % (os.path.basename(path), restarted, k, fresh, k,
+                                                     "equal" if x.shape == y.shape and np.array_equal(x, y) else "DIFFERENT"))
     return 1 if bad else 0
 
 
