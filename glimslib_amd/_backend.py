@@ -128,6 +128,15 @@ class ImageMisfit(C.Structure):
                 ("pweight", C.POINTER(C.c_double))]
 
 
+class DeformedImageMisfit(C.Structure):
+    """glims_deformed_image_misfit: an image term of the deformed configuration; it carries its own point set (xyz, or the
+    grid origin / spacing / size when xyz is NULL)."""
+    _fields_ = [("step", C.c_int64), ("kind", C.c_int), ("level", C.c_double), ("smooth", C.c_double),
+                ("weight", C.c_double), ("scale", C.c_double), ("n_points", C.c_int64), ("xyz", C.POINTER(C.c_double)),
+                ("origin", C.c_double * 3), ("spacing", C.c_double * 3), ("size", C.c_int64 * 3),
+                ("target", C.POINTER(C.c_double)), ("pweight", C.POINTER(C.c_double))]
+
+
 class Observable(C.Structure):
     """glims_observable: one query of glims_observe (kind: OBSERVE_KINDS; smooth: 'smooth' only)."""
     _fields_ = [("kind", C.c_int), ("level", C.c_double), ("smooth", C.c_double)]
@@ -195,6 +204,8 @@ SIGNATURES = {
     "glims_sampler_destroy": (C.c_int, [_h, C.c_int64]),
     "glims_adjoint_image_terms": (C.c_int, [_h, C.c_int, C.POINTER(ImageMisfit)]),
     "glims_adjoint_image_info": (C.c_int, [_h, C.c_int, _i64p]),
+    "glims_adjoint_deformed_image_terms": (C.c_int, [_h, C.c_int, C.POINTER(DeformedImageMisfit)]),
+    "glims_adjoint_deformed_image_info": (C.c_int, [_h, C.c_int, _i64p, _dp]),
     "glims_comm_unique_id": (C.c_int, [C.c_char_p]),
     "glims_comm_init": (C.c_int, [_h, C.c_int, C.c_int, C.c_char_p]),
     "glims_comm_selftest": (C.c_int, [_h]),
@@ -268,6 +279,8 @@ class Handle:
         lib.glims_options_default(C.byref(self.options))
         self.n_labels = None   # label count of the last successful set_materials
         self._image_terms = []   # what the library's stored image terms were made from (see _sync_image_terms)
+        self._deformed_terms = []   # ... and the stored deformed image terms (see _split_terms)
+        self._warned_folded = False
 
     # -- plumbing --------------------------------------------------------------------------------
     def _check(self, st, allow=()):
@@ -519,7 +532,9 @@ class Handle:
         smooth=1}; targets in the caller's node order ([n_nodes] or [n_nodes, dim]).  Image-space terms go in the same list:
         {step, kind ('img_l2' | 'img_thresh'), sampler (a :class:`Sampler` of this handle), target ([n_points], any shape;
         NaN = not observed), pweight=None, weight=1, level=0, smooth=1}; they are stored on the device (set_image_terms) and
-        re-sent only when they differ from what the handle holds.
+        re-sent only when they differ from what the handle holds.  An image term with ``deformed=True`` observes the DEFORMED
+        configuration x = X + scale u_k and carries its own points instead of a sampler: {..., deformed=True, scale=1.0,
+        grid=(origin, spacing, size) or points=[n_points, dim]} (set_deformed_image_terms; the gradient through the location).
         Returns (J, dJ/dD [n_labels], dJ/drho, dJ/dgamma, dJ/dc0 [n_nodes] or None); with elastic=True (glims_adjoint_gradient_full)
         (J, dJ/dD, dJ/drho, dJ/dgamma, dJ/dc0, dJ/dE [n_labels], dJ/dnu [n_labels]).  The library writes one entry per label
         of the last set_materials: n_labels, when given, must be that count (ValueError otherwise, before any call)."""
@@ -537,9 +552,11 @@ class Handle:
             self._check(self.lib.glims_adjoint_gradient_full(self._h, len(terms), arr, C.byref(J),
                                                              *[_ptr(a, _dp) for a in out[:3]], _ptr(dc0, _dp),
                                                              _ptr(out[3], _dp), _ptr(out[4], _dp)))
+            self._warn_folded()
             return (J.value, out[0], out[1], out[2], dc0, out[3], out[4])
         self._check(self.lib.glims_adjoint_gradient(self._h, len(terms), arr, C.byref(J), *[_ptr(a, _dp) for a in out],
                                                     _ptr(dc0, _dp)))
+        self._warn_folded()
         return (J.value, out[0], out[1], out[2], dc0)
 
     # -- image-space misfit terms (glims_adjoint_image_*) ---------------------------------------------
@@ -582,9 +599,100 @@ class Handle:
         self._check(self.lib.glims_adjoint_image_info(self._h, int(k), _ptr(out, _i64p)))
         return tuple(int(v) for v in out)
 
-    def _split_terms(self, terms):
-        """The nodal terms of a mixed list; its image terms become the handle's stored list (re-sent only on a change)."""
+    # -- image terms of the deformed configuration (glims_adjoint_deformed_image_*) -------------------
+    @staticmethod
+    def _deformed_key(t):
+        pts = t.get("points")
+        grid = t.get("grid")
+        gk = None if grid is None else tuple(tuple(float(v) for v in np.ravel(a)) for a in grid)
+        return (int(t["step"]), _IMAGE_KINDS.get(t["kind"], t["kind"]), float(t.get("level", 0.0)),
+                float(t.get("smooth", 1.0)), float(t.get("weight", 1.0)), float(t.get("scale", 1.0)), gk, id(pts),
+                id(t["target"]), id(t.get("pweight")))
+
+    def set_deformed_image_terms(self, terms, _from_list=False):
+        """glims_adjoint_deformed_image_terms: replace the handle's stored DEFORMED image terms (an empty list clears them).
+        Each term: {step, kind ('img_l2' | 'img_thresh'), target, pweight=None, weight=1, level=0, smooth=1, scale=1.0} and
+        either grid=(origin, spacing, size) (target in the order of an image array [z,] y, x) or points=[n_points, dim].
+        Points, target and pweight are copied to the device once; every later adjoint_gradient locates the points in the mesh
+        at X + scale u_k and adds the term with its gradient through the location."""
         terms = list(terms)
+        arr = (DeformedImageMisfit * max(1, len(terms)))()
+        keep = []
+        for k, t in enumerate(terms):
+            kind = _IMAGE_KINDS.get(t["kind"], t["kind"])
+            m = DeformedImageMisfit()
+            m.step, m.kind = int(t["step"]), int(kind)
+            m.level, m.smooth = float(t.get("level", 0.0)), float(t.get("smooth", 1.0))
+            m.weight, m.scale = float(t.get("weight", 1.0)), float(t.get("scale", 1.0))
+            if t.get("points") is not None:
+                xyz = _f64(np.asarray(t["points"], dtype=np.float64).reshape(-1, self.dim))
+                n = xyz.shape[0]
+                m.n_points, m.xyz = n, _ptr(xyz, _dp)
+                keep.append(xyz)
+            elif t.get("grid") is not None:
+                origin, spacing, size = t["grid"]
+                size = [int(v) for v in np.ravel(size)]
+                if not (len(size) == len(np.ravel(origin)) == len(np.ravel(spacing)) == self.dim):
+                    raise ValueError("deformed image term %d: the grid has not %d axes" % (k, self.dim))
+                for a in range(self.dim):
+                    m.origin[a], m.spacing[a], m.size[a] = float(np.ravel(origin)[a]), float(np.ravel(spacing)[a]), size[a]
+                n = int(np.prod(size)) if min(size) > 0 else None
+                m.n_points, m.xyz = 0, None
+            else:
+                raise ValueError("deformed image term %d: needs grid=(origin, spacing, size) or points" % k)
+            tg = t["target"]
+            if tg is not None:
+                tg = _f64(np.asarray(tg, dtype=np.float64).reshape(-1))
+                if n is not None and tg.shape != (n,):
+                    raise ValueError("deformed image term %d: target has %d values, the term %d points" % (k, tg.size, n))
+            q = t.get("pweight")
+            if q is not None:
+                q = _f64(np.asarray(q, dtype=np.float64).reshape(-1))
+                if n is not None and q.shape != (n,):
+                    raise ValueError("deformed image term %d: pweight has %d values, the term %d points" % (k, q.size, n))
+            keep.append((tg, q))
+            m.target, m.pweight = _ptr(tg, _dp), _ptr(q, _dp)
+            arr[k] = m
+        self._check(self.lib.glims_adjoint_deformed_image_terms(self._h, len(terms), arr))
+        del keep
+        self._deformed_terms = [(self._deformed_key(t), t) for t in terms]   # (the dicts keep the compared arrays alive)
+        self._deformed_from_list = bool(_from_list)
+        self._warned_folded = False
+
+    def deformed_image_term_info(self, k):
+        """Stored deformed image term k at its LAST evaluation: a dict n_points, found, observed, folded (cells of the mesh
+        at X + scale u_k whose determinant ratio is not > 0), min_ratio; found / observed / folded are -1 before the first."""
+        out = np.zeros(4, dtype=np.int64)
+        mr = C.c_double(1.0)
+        self._check(self.lib.glims_adjoint_deformed_image_info(self._h, int(k), _ptr(out, _i64p), C.byref(mr)))
+        return dict(n_points=int(out[0]), found=int(out[1]), observed=int(out[2]), folded=int(out[3]), min_ratio=mr.value)
+
+    def has_deformed_image_terms(self):
+        return bool(self._deformed_terms)
+
+    def _warn_folded(self):
+        """Once per stored list: the last gradient call located points in a mesh with folded cells."""
+        if self._warned_folded or not self._deformed_terms:
+            return
+        for k in range(len(self._deformed_terms)):
+            info = self.deformed_image_term_info(k)
+            if info["folded"] > 0:
+                import warnings
+                warnings.warn("deformed image term %d: %d cells of the displaced mesh are folded (smallest determinant ratio "
+                              "min_ratio = %.3g); points in such cells carry no gradient through their location"
+                              % (k, info["folded"], info["min_ratio"]), RuntimeWarning, stacklevel=3)
+                self._warned_folded = True
+                return
+
+    def _split_terms(self, terms):
+        """The nodal terms of a mixed list; its image terms become the handle's stored lists -- the fixed ones and those with
+        deformed=True, each re-sent only on a change."""
+        terms = list(terms)
+        moving = [t for t in terms if _IMAGE_KINDS.get(t["kind"]) is not None and t.get("deformed")]
+        if moving or getattr(self, "_deformed_from_list", False):
+            if [self._deformed_key(t) for t in moving] != [k for k, _ in self._deformed_terms]:
+                self.set_deformed_image_terms(moving, _from_list=True)
+            terms = [t for t in terms if not (_IMAGE_KINDS.get(t["kind"]) is not None and t.get("deformed"))]
         image = [t for t in terms if _IMAGE_KINDS.get(t["kind"]) is not None]
         if not image and not getattr(self, "_image_from_list", False):
             return terms   # (terms stored by set_image_terms itself stay)
@@ -622,6 +730,10 @@ class Handle:
         L, n = self.n_labels, self.n_nodes
         directions = list(directions)
         P = len(directions)
+        terms = list(terms)
+        if any(_IMAGE_KINDS.get(t["kind"]) is not None and t.get("deformed") for t in terms):
+            raise NotImplementedError("adjoint_hessian: second order through the location of a deformed image term is not "
+                                      "built (glims_adjoint_hessian refuses while such a term is stored)")
         terms = self._split_terms(terms)
         arr, keep = self._misfit_array(terms)
 

@@ -534,7 +534,7 @@ void adjoint_setup(glims_ctx* h, int n_terms, const glims_misfit* terms, bool el
   wk.sums.alloc_zero((size_t)GL_MAX_LABELS * 3, h->st);
   if (elastic) wk.esums.alloc_zero((size_t)GL_MAX_LABELS * 2, h->st);
   wk.stage.alloc_zero((size_t)nd, h->st);
-  bool any_u = false;
+  bool any_u = !h->dimg_terms.empty();   // (a deformed image term observes u_k as a displacement term does)
   for (int k = 0; k < n_terms; ++k) any_u = any_u || terms[k].kind == GLIMS_MISFIT_U_L2;
   if (any_u)
     for (auto* v : {&wk.uk, &wk.murhs, &wk.mu, &wk.mr, &wk.mu_, &wk.mw, &wk.mp, &wk.ms, &wk.mKx})
@@ -552,7 +552,8 @@ void adjoint_setup(glims_ctx* h, int n_terms, const glims_misfit* terms, bool el
 // The first-order backward sweep, step by step: what glims_adjoint_gradient runs, and what glims_adjoint_hessian runs with
 // its second-order work in between (same kernels, same order, same buffers: J and the gradient have the same bits in both).
 // Construct it after the ForwardGuard (the lazy RD hierarchy is the guard's to drop).  A step is
-//   c = begin_step;  have_u = nodal_terms;  [image terms: the caller]  if (have_u) coupling_adjoint;
+//   c = begin_step;  have_u = nodal_terms;  [image terms: the caller]  have_u = deformed_image_terms;
+//   if (have_u) coupling_adjoint;
 //   step 0: c0_output, else lambda_solve -- each stops the sweep by setting `status`.
 template <int D>
 struct BackwardSweep {
@@ -590,6 +591,33 @@ struct BackwardSweep {
     return h->adj.traj[step]->p;
   }
 
+  // u_k = K_el^-1 (G c_k + f) into wk.uk, murhs = 0: once per observed step, for its first displacement term or, when it has
+  // none, its first deformed image term
+  bool solve_uk(const double* c) {
+    gl_apply_G(h, c, wk.murhs.p);
+    int64_t its = 0;
+    status = solve_elastic(h, wk, wk.murhs.p, wk.uk.p, h->have_fixed_u ? h->m_uD.p : nullptr, 1e-12, &its);
+    if (status != GLIMS_OK) return false;
+    GL_HIP(hipMemsetAsync(wk.murhs.p, 0, (size_t)h->n_nodes * D * sizeof(double), h->st));
+    return true;
+  }
+
+  // The stored deformed image terms (glims_adjoint_deformed_image_terms) that observe `step`, in their list order, after the
+  // step's nodal and fixed image terms: the points are located in the mesh at X + scale u_k, J += 1/2 w sum_p q_p (h(v_p) -
+  // t_p)^2, g += P^T r and murhs += P^T S (the load through the location).  have_u: u_k is solved already; returns whether
+  // it is now (the coupling adjoint follows then).  No stored term: no launch.
+  bool deformed_image_terms(int step, const double* c, bool have_u) {
+    for (GlDeformedImageTerm* t : h->dimg_terms) {
+      if (t->step != step) continue;
+      if (!have_u) {
+        if (!solve_uk(c)) return have_u;
+        have_u = true;
+      }
+      J += 0.5 * t->weight * gl_deformed_image_misfit_grad(h, *t, c, wk.uk.p, wk.g.p, wk.murhs.p);
+    }
+    return have_u;
+  }
+
   // The nodal terms that observe `step`, in list order: J and g += dJ/dc_n of the concentration terms (after each,
   // after_c_term(term) runs while wk.Me still holds M (h(c) - t)); the displacement terms solve u_k once and add dJ/du_n to
   // murhs.  True when the step has a displacement term (the coupling adjoint follows).
@@ -613,12 +641,8 @@ struct BackwardSweep {
         after_c_term(tm);
         continue;
       }
-      if (!have_u) {   // u_k = K_el^-1 (G c_k + f), once per observed step
-        gl_apply_G(h, c, wk.murhs.p);
-        int64_t its = 0;
-        status = solve_elastic(h, wk, wk.murhs.p, wk.uk.p, h->have_fixed_u ? h->m_uD.p : nullptr, 1e-12, &its);
-        if (status != GLIMS_OK) return have_u;
-        GL_HIP(hipMemsetAsync(wk.murhs.p, 0, (size_t)h->n_nodes * D * sizeof(double), h->st));
+      if (!have_u) {
+        if (!solve_uk(c)) return have_u;
         have_u = true;
       }
       for (int comp = 0; comp < D; ++comp) {   // dJ/du = w M_vec (u - t), component by component through the scalar M
@@ -725,9 +749,13 @@ int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_o
   BackwardSweep<D> sw(h, wk, n_terms, terms, elastic);
   for (int step = sw.last_step(); step >= 0; --step) {
     const double* c = sw.begin_step(step);
-    const bool have_u = sw.nodal_terms(step, c, [](const glims_misfit&) {});
+    bool have_u = sw.nodal_terms(step, c, [](const glims_misfit&) {});
     if (sw.status != GLIMS_OK) break;
     image_terms_of_step(h, step, c, wk.g.p, &sw.J);
+    if (!h->dimg_terms.empty()) {
+      have_u = sw.deformed_image_terms(step, c, have_u);
+      if (sw.status != GLIMS_OK) break;
+    }
     if (have_u && !sw.coupling_adjoint(c)) break;
     if (step == 0) {
       if (dc0) sw.c0_output(dc0);
@@ -1721,6 +1749,10 @@ void check_gradient_call(glims_ctx* h, int n_terms, const glims_misfit* terms, c
     GL_REQUIRE(h->img_terms[k]->step <= N, who + ": stored image term " + std::to_string(k) + " observes step " +
                                                std::to_string(h->img_terms[k]->step) + ", the recording has steps 0.." +
                                                std::to_string(N));
+  for (size_t k = 0; k < h->dimg_terms.size(); ++k)
+    GL_REQUIRE(h->dimg_terms[k]->step <= N, who + ": stored deformed image term " + std::to_string(k) + " observes step " +
+                                                std::to_string(h->dimg_terms[k]->step) + ", the recording has steps 0.." +
+                                                std::to_string(N));
 }
 }  // namespace
 
@@ -1793,6 +1825,9 @@ int gl_adjoint_hessian(glims_ctx* h, int n_terms, const glims_misfit* terms, int
                        double* hv_c0, double* stats) {
   // (every rank of a partitioned handle refuses alike: no collective is entered)
   GL_REQUIRE(h->world <= 1, "glims_adjoint_hessian: not available on partitioned handles (world > 1)");
+  GL_REQUIRE(h->dimg_terms.empty(), "glims_adjoint_hessian: second order through the location of the stored deformed image "
+                                    "terms is not built (a Hessian without them would be wrong): clear them with "
+                                    "glims_adjoint_deformed_image_terms(h, 0, NULL) first");
   check_gradient_call(h, n_terms, terms, J, "glims_adjoint_hessian");
   check_n_dir(n_dir);
   return hessian_dispatch(h, n_terms, terms, n_dir, dir_D, dir_rho, dir_gamma, dir_c0, J, dD, drho, dgamma, dc0, hv_D, hv_rho,

@@ -1035,6 +1035,20 @@ int glims_adjoint_image_info(glims_ctx* h, int k, int64_t out[3]) {
   });
 }
 
+int glims_adjoint_deformed_image_terms(glims_ctx* h, int n, const glims_deformed_image_misfit* terms) {
+  return guarded(h, [&]() {
+    gl_deformed_image_terms_set(h, n, terms);
+    return GLIMS_OK;
+  });
+}
+
+int glims_adjoint_deformed_image_info(glims_ctx* h, int k, int64_t out[4], double* min_ratio) {
+  return guarded(h, [&]() {
+    gl_deformed_image_term_info(h, k, out, min_ratio);
+    return GLIMS_OK;
+  });
+}
+
 int glims_project(glims_ctx* h, const double* rhs, double* x, int ncomp, double rtol) {
   return guarded(h, [&]() {
     GL_REQUIRE(rhs && x && ncomp >= 1 && rtol > 0.0, "bad arguments");

@@ -491,6 +491,25 @@ struct GlImageTerm {
   dvec<double> target, pweight;             // [n]; pweight empty = 1
 };
 
+// One stored image term of the DEFORMED configuration (glims_adjoint_deformed_image_terms; kernels in sample.hip).  Its points
+// are located anew, in the mesh at X + scale u_k, at every evaluation: the term owns its point set and a scratch sampler.
+// target holds NaN where the caller's array does or where q_p = 0; whether a point is found is decided per evaluation.
+struct GlDeformedImageTerm {
+  int64_t step = 0, n = 0;
+  int kind = 0;
+  double level = 0.0, smooth = 1.0, weight = 1.0, scale = 1.0;
+  bool is_grid = true;
+  double origin[3] = {0.0, 0.0, 0.0}, spacing[3] = {1.0, 1.0, 1.0};
+  int64_t size[3] = {1, 1, 1};
+  std::vector<double> xyz;                  // point set [n][dim] (the binning of the location reads it on the host)
+  dvec<double> target, pweight;             // [n]; pweight empty = 1
+  GlSampler* scratch = nullptr;             // owned (sample.hip): the location of the last evaluation
+  dvec<double> y, S;                        // deformed coordinates [n_nodes][dim]; S [n][dim]
+  dvec<unsigned long long> cnt;             // [1] observed points of the evaluation
+  int64_t n_found = -1, n_obs = -1, n_folded = -1;   // of the LAST evaluation (-1 before the first)
+  double min_ratio = 1.0;
+};
+
 // Derived fields of a recorded step (derive.hip, glims_derive): the last result, the scratch of the two passes, the one-entry
 // cache of the projected stress, and which snapshot's displacement the handle's U holds
 struct DeriveState {
@@ -704,6 +723,7 @@ struct glims_ctx {
   AdjointState adj;
   std::vector<GlSampler*> samplers;         // owned (sample.hip); a destroyed sampler leaves a nullptr so that ids stay valid
   std::vector<GlImageTerm*> img_terms;      // owned (sample.hip): the stored image-space misfit terms of the adjoint calls
+  std::vector<GlDeformedImageTerm*> dimg_terms;   // owned (sample.hip): the stored deformed-configuration image terms
   DeriveState derive;
   ObserveState observe;
 
@@ -826,7 +846,7 @@ void gl_sampler_apply_t(glims_ctx* h, int64_t id, const double* r, int ncomp, do
 void gl_sampler_resolve(glims_ctx* h, int64_t id, const int64_t* cell_gid);   // collective on partitioned handles
 void gl_sampler_get_counted(glims_ctx* h, int64_t id, uint8_t* counted);
 void gl_sampler_destroy(glims_ctx* h, int64_t id);
-void gl_sampler_destroy_all(glims_ctx* h);   // (and the stored image terms)
+void gl_sampler_destroy_all(glims_ctx* h);   // (and the stored image terms of both lists)
 // g[row * ld_row + a * ld_comp] (internal numbering, owned rows) = or += (P^T r)[row][a]; r [n_points][ncomp] on the device
 void gl_sampler_transpose_dev(glims_ctx* h, int64_t id, const double* r_dev, int ncomp, double* g_int_dev, int64_t ld_row,
                               int64_t ld_comp, bool accumulate);
@@ -837,6 +857,12 @@ double gl_image_misfit_grad(glims_ctx* h, const GlImageTerm& t, const double* c,
 // dg[j * ld + row] += (P^T r2_j)[row] for the P directions dc[j * ld + .]
 void gl_image_misfit_second(glims_ctx* h, const GlImageTerm& t, const double* c, const double* dc, int P, int64_t ld,
                             double* dg);
+void gl_deformed_image_terms_set(glims_ctx* h, int n, const glims_deformed_image_misfit* terms);
+void gl_deformed_image_term_info(glims_ctx* h, int k, int64_t out[4], double* min_ratio);
+// Stored deformed term t at the state c and displacement u (both internal numbering): locates its points in the mesh at
+// X + scale u, g += P^T r, murhs[row * dim + a] += (P^T S)[row][a]; returns sum_p q_p (h(v_p) - t_p)^2 (fixed order)
+double gl_deformed_image_misfit_grad(glims_ctx* h, GlDeformedImageTerm& t, const double* c, const double* u, double* g,
+                                     double* murhs);
 
 // api.hip: caller's node order -> internal, through h->stage (synchronises h->st)
 void gl_to_device_perm(glims_ctx* h, const double* host, double* dst, int bs);

@@ -834,6 +834,81 @@ __global__ __launch_bounds__(1024) void k_deform_min(int64_t n_blocks, const dou
   }
 }
 
+// Image term of the deformed configuration (glims_hip.h, "image terms in the deformed configuration"),
+// one thread per point of a sampler located in the mesh at y = X + scale u_k.  v, h, r[p] and the block's partial sum of
+// q (h(v) - t)^2 are formed exactly as in k_img_misfit (same expressions, same order: with scale = 0 the two agree bit for
+// bit); on top of them the location's load  S[p][.] = -scale r_p grad_y c_k|T(p),  grad_y c = sum_k (c_{k+1} - c_0) R_k with
+// R the rows of the winner's inverse edge matrix in the DEFORMED coordinates (load_cell).  A winner whose ratio
+// det(E_deformed) / det(E_reference) is not > 0 or not finite gets S = 0.  A point is observed iff it was found (cell >= 0)
+// and its target is not NaN (q_p = 0 was turned into a NaN target when the term was stored); n_obs counts them (integer).
+// The gradient is formed per POINT, not once per cell: a per-cell pass would write 8 D B per cell and save the points the
+// 16 D NV B of gathered coordinates, which the caches serve -- the choice is by bytes and unmeasured.
+// Bytes per point: 4 (cell) + NV (4 + 8) node ids and weights + 8 (t) + 8 (q, if present) + 8 (r) + 8 D (S); c and the
+// 2 D NV coordinates (y and X) are gathered through the caches.
+template <int NV>
+__global__ __launch_bounds__(256) void k_img_misfit_deformed(int64_t n, int kind, double level, double smooth, double weight,
+                                                             double scale, const int32_t* __restrict__ cell,
+                                                             const int32_t* __restrict__ node, const double* __restrict__ w,
+                                                             const double* __restrict__ c, const double* __restrict__ X,
+                                                             const double* __restrict__ y, const double* __restrict__ t,
+                                                             const double* __restrict__ q, double* __restrict__ r,
+                                                             double* __restrict__ S, double* __restrict__ part,
+                                                             unsigned long long* __restrict__ n_obs) {
+  constexpr int D = NV - 1;
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  double sq = 0.0;
+  bool obs = false;
+  if (p < n) {
+    const double tv = t[p];
+    double rv = 0.0;
+    double sv[D];
+#pragma unroll
+    for (int a = 0; a < D; ++a) sv[a] = 0.0;
+    if (tv == tv && cell[p] >= 0) {
+      obs = true;
+      double v = 0.0;
+#pragma unroll
+      for (int m = 0; m < NV; ++m) v += w[p * NV + m] * c[node[p * NV + m]];
+      double hv, hp, h2;
+      img_h(kind, level, smooth, v, hv, hp, h2);
+      const double qv = q ? q[p] : 1.0;
+      const double e = hv - tv;
+      rv = weight * qv * hp * e;
+      sq = qv * e * e;
+      int32_t nd[NV];
+#pragma unroll
+      for (int m = 0; m < NV; ++m) nd[m] = node[p * NV + m];
+      CellGeo<D> g;
+      load_cell<D>(y, nd, g);
+      const double ratio = edge_det<D>(y, nd) / edge_det<D>(X, nd);
+      if (g.ok && ratio > 0.0 && isfinite(ratio)) {
+        const double c0 = c[nd[0]];
+        double grad[D];
+#pragma unroll
+        for (int a = 0; a < D; ++a) grad[a] = 0.0;
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+          const double dk = c[nd[k + 1]] - c0;
+#pragma unroll
+          for (int a = 0; a < D; ++a) grad[a] += dk * g.r[k][a];
+        }
+#pragma unroll
+        for (int a = 0; a < D; ++a) sv[a] = -scale * rv * grad[a];
+      }
+    }
+    r[p] = rv;
+#pragma unroll
+    for (int a = 0; a < D; ++a) S[p * D + a] = sv[a];
+  }
+  const int here = __syncthreads_count(obs);
+  if (threadIdx.x == 0 && here) atomicAdd(n_obs, (unsigned long long)here);   // (integer: order-independent)
+  __shared__ double sm[4];
+  const double ws = img_wave_sum(sq);
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = ws;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
+}
+
 // glims_sampler_warp, one thread per point: out[p][.] = image(X(x_p)), X = sum_m w[p][m] X_node(m) the back-mapped position
 // (formed in registers, never stored).  Per axis t = (X - o) / s.
 //   ORDER 1 (d-linear): inside iff 0 <= t <= n - 1; i0 = min(floor(t), n - 2) (n = 1: i0 = 0, f = 0), f = t - i0; the value is
@@ -1419,9 +1494,9 @@ void gl_sampler_apply(glims_ctx* h, int64_t id, int field, int64_t snapshot, con
 // The two launches of P^T on device pointers: pass 1 into the sampler's chunk buffer, pass 2 row-owned into g (internal
 // numbering; overwritten, or added to with `accumulate`).  Without `accumulate` g is [n_nodes][ncomp] contiguous and is zeroed
 // first on a partitioned handle: pass 2 writes the owned rows, the ghost rows hold 0.
-void gl_sampler_transpose_dev(glims_ctx* h, int64_t id, const double* r_dev, int ncomp, double* g_int_dev, int64_t ld_row,
-                              int64_t ld_comp, bool accumulate) {
-  GlSampler& s = sampler_of(h, id, "glims_sampler_apply_t");
+namespace {
+void transpose_on(glims_ctx* h, GlSampler& s, const double* r_dev, int ncomp, double* g_int_dev, int64_t ld_row,
+                  int64_t ld_comp, bool accumulate) {
   GL_REQUIRE(h->world <= 1 || s.resolved,
              "glims_sampler_apply_t: not available on a partitioned handle before glims_sampler_resolve (the per-cell sums "
              "need the globally winning cell on every rank that holds it)");
@@ -1455,6 +1530,12 @@ void gl_sampler_transpose_dev(glims_ctx* h, int64_t id, const double* r_dev, int
                        pt.cslots.p, pt.celem.p, pt.diag_k.p, s.chunk_ptr.p, s.q.p, g_int_dev, ld_row, ld_comp,
                        accumulate ? 1 : 0);
   GL_CHECK_LAUNCH();
+}
+}  // namespace
+
+void gl_sampler_transpose_dev(glims_ctx* h, int64_t id, const double* r_dev, int ncomp, double* g_int_dev, int64_t ld_row,
+                              int64_t ld_comp, bool accumulate) {
+  transpose_on(h, sampler_of(h, id, "glims_sampler_apply_t"), r_dev, ncomp, g_int_dev, ld_row, ld_comp, accumulate);
 }
 
 void gl_sampler_apply_t(glims_ctx* h, int64_t id, const double* r, int ncomp, double* g) {
@@ -1739,6 +1820,183 @@ void gl_image_misfit_second(glims_ctx* h, const GlImageTerm& t, const double* c,
   gl_sampler_transpose_dev(h, t.sampler, s.out.p, P, dg, 1, ld, true);
 }
 
+// ---- stored image terms of the deformed configuration ------------------------------------------------------------------------
+namespace {
+void delete_deformed_term(GlDeformedImageTerm* t) {
+  if (!t) return;
+  delete t->scratch;
+  delete t;
+}
+}  // namespace
+
+void gl_deformed_image_terms_set(glims_ctx* h, int n, const glims_deformed_image_misfit* terms) {
+  const char* who = "glims_adjoint_deformed_image_terms";
+  GL_REQUIRE(n >= 0 && (n == 0 || terms), std::string(who) + ": bad term list");
+  // every check before anything is allocated or the old list is touched
+  if (n > 0) {
+    GL_REQUIRE(h->world <= 1, std::string(who) + ": not available on a partitioned handle (world > 1)");
+    GL_REQUIRE(h->is_setup && h->have_mech,
+               std::string(who) + ": the terms move with the displacement: glims_setup(with_mechanics=1) first");
+  }
+  const int D = h->dim;
+  size_t need = 0;
+  std::vector<int64_t> np((size_t)std::max(1, n), 0);
+  for (int k = 0; k < n; ++k) {
+    const glims_deformed_image_misfit& t = terms[k];
+    const std::string tk = std::string(who) + ": term " + std::to_string(k);
+    GL_REQUIRE(t.kind == GLIMS_MISFIT_IMG_L2 || t.kind == GLIMS_MISFIT_IMG_THRESH, tk + ": unknown kind");
+    GL_REQUIRE(t.kind != GLIMS_MISFIT_IMG_THRESH || (t.smooth > 0.0 && std::isfinite(t.smooth) && std::isfinite(t.level)),
+               tk + ": a threshold term needs smooth > 0 and a finite level");
+    GL_REQUIRE(std::isfinite(t.weight), tk + ": non-finite weight");
+    GL_REQUIRE(std::isfinite(t.scale), tk + ": non-finite scale");
+    GL_REQUIRE(t.target, tk + ": null target");
+    GL_REQUIRE(t.step >= 0, tk + ": negative step");
+    GL_REQUIRE(!t.xyz || t.n_points >= 0, tk + ": negative n_points");
+    GridSpec gs;
+    const int64_t np_k = check_points(h, t.n_points, t.xyz, t.origin, t.spacing, t.size, gs);
+    np[(size_t)k] = np_k;
+    if (t.pweight)
+      for (int64_t p = 0; p < np_k; ++p)
+        GL_REQUIRE(t.pweight[p] >= 0.0 && std::isfinite(t.pweight[p]),
+                   tk + ": pweight[" + std::to_string(p) + "] is negative or not finite");
+    // the copies (target, pweight), S and r, the scratch sampler with its transpose, the deformed coordinates; the location's
+    // transient buffers are checked again by every evaluation
+    need += (size_t)np_k * ((t.pweight ? 16 : 8) + 8 * (D + 1) + 4 + (D + 1) * 12 + 4) + (size_t)h->n_cells * 12 +
+            (size_t)h->n_nodes * D * 8;
+  }
+  if (n > 0) need_memory(who, need + (1u << 20));
+  std::vector<GlDeformedImageTerm*> fresh;
+  try {
+    for (int k = 0; k < n; ++k) {
+      const glims_deformed_image_misfit& t = terms[k];
+      const int64_t np_k = np[(size_t)k];
+      auto* g = new GlDeformedImageTerm();
+      fresh.push_back(g);
+      g->step = t.step;
+      g->kind = t.kind;
+      g->level = t.level;
+      g->smooth = t.smooth;
+      g->weight = t.weight;
+      g->scale = t.scale;
+      g->n = np_k;
+      g->is_grid = !t.xyz;
+      if (t.xyz) {
+        g->xyz.assign(t.xyz, t.xyz + (size_t)np_k * D);
+      } else {
+        for (int a = 0; a < D; ++a) {
+          g->origin[a] = t.origin[a];
+          g->spacing[a] = t.spacing[a];
+          g->size[a] = t.size[a];
+        }
+      }
+      if (np_k == 0) continue;
+      // q_p = 0 is "not observed" whatever the location says: a NaN target, as the fixed terms keep it
+      std::vector<double> tg(t.target, t.target + (size_t)np_k);
+      if (t.pweight)
+        for (int64_t p = 0; p < np_k; ++p)
+          if (t.pweight[p] == 0.0) tg[(size_t)p] = std::numeric_limits<double>::quiet_NaN();
+      g->target.upload(tg, h->st);
+      if (t.pweight) g->pweight.upload(t.pweight, (size_t)np_k, h->st);
+      GL_HIP(hipStreamSynchronize(h->st));   // (tg and the caller's arrays are free again)
+    }
+  } catch (...) {
+    (void)hipStreamSynchronize(h->st);
+    for (auto* g : fresh) delete_deformed_term(g);
+    throw;
+  }
+  GL_HIP(hipStreamSynchronize(h->st));
+  for (auto* g : h->dimg_terms) delete_deformed_term(g);
+  h->dimg_terms.swap(fresh);
+}
+
+void gl_deformed_image_term_info(glims_ctx* h, int k, int64_t out[4], double* min_ratio) {
+  const char* who = "glims_adjoint_deformed_image_info";
+  GL_REQUIRE(out, std::string(who) + ": null output");
+  GL_REQUIRE(k >= 0 && k < (int)h->dimg_terms.size(), std::string(who) + ": no stored term " + std::to_string(k));
+  const GlDeformedImageTerm& t = *h->dimg_terms[(size_t)k];
+  out[0] = t.n;
+  out[1] = t.n_found;
+  out[2] = t.n_obs;
+  out[3] = t.n_folded;
+  if (min_ratio) *min_ratio = t.min_ratio;
+}
+
+double gl_deformed_image_misfit_grad(glims_ctx* h, GlDeformedImageTerm& t, const double* c, const double* u, double* g,
+                                     double* murhs) {
+  const char* who = "glims_adjoint_gradient (deformed image terms)";
+  const int D = h->dim;
+  const int64_t nn = h->n_nodes;
+  if (t.n == 0) {
+    t.n_found = t.n_obs = t.n_folded = 0;
+    t.min_ratio = 1.0;
+    return 0.0;
+  }
+  const size_t ny = (size_t)std::max<int64_t>(1, nn * D), ns = (size_t)t.n * D;
+  if (t.y.n != ny || t.S.n != ns) {
+    need_memory(who, (ny + ns) * sizeof(double));
+    t.y.alloc(ny);
+    t.S.alloc(ns);
+  }
+  t.cnt.alloc_zero(1, h->st);
+  // y = X + scale u_k, the location in it (cell, nodes, weights and the transpose's lists), the cells' determinant ratios
+  if (nn > 0) {
+    if (D == 2) hipLaunchKernelGGL(k_deform_xyz<2>, dim3(grid_of(nn)), dim3(256), 0, h->st, nn, h->xyz_new.p, u, t.scale, t.y.p);
+    else hipLaunchKernelGGL(k_deform_xyz<3>, dim3(grid_of(nn)), dim3(256), 0, h->st, nn, h->xyz_new.p, u, t.scale, t.y.p);
+    GL_CHECK_LAUNCH();
+  }
+  GridSpec gs;
+  for (int a = 0; a < 3; ++a) {
+    gs.o[a] = t.origin[a];
+    gs.s[a] = t.spacing[a];
+    gs.n[a] = t.size[a];
+  }
+  if (!t.scratch) t.scratch = new GlSampler();
+  GlSampler& s = *t.scratch;
+  s.n = t.n;
+  s.is_grid = t.is_grid;
+  s.deformed = true;
+  s.have_t = false;
+  s.n_chunks = 0;
+  const double* xyz_host = t.is_grid ? nullptr : t.xyz.data();
+  if (D == 2) {
+    create_t<2>(h, s, xyz_host, gs, t.y.p);
+    deformation_stats<2>(h, s, t.y.p);
+  } else {
+    create_t<3>(h, s, xyz_host, gs, t.y.p);
+    deformation_stats<3>(h, s, t.y.p);
+  }
+  image_staging(h, s, 1);
+  const size_t nq = (size_t)std::max<int64_t>(1, s.n_chunks) * h->nv * D;   // (both transposes below fit)
+  if (s.q.n < nq) {
+    need_memory(who, nq * sizeof(double));
+    s.q.alloc(nq);
+  }
+  const unsigned nb = grid_of(s.n);
+  if (h->nv == 3)
+    hipLaunchKernelGGL(k_img_misfit_deformed<3>, dim3(nb), dim3(256), 0, h->st, s.n, t.kind, t.level, t.smooth, t.weight,
+                       t.scale, s.cell.p, s.node.p, s.w.p, c, h->xyz_new.p, t.y.p, t.target.p, t.pweight.p, s.out.p, t.S.p,
+                       s.part.p, t.cnt.p);
+  else
+    hipLaunchKernelGGL(k_img_misfit_deformed<4>, dim3(nb), dim3(256), 0, h->st, s.n, t.kind, t.level, t.smooth, t.weight,
+                       t.scale, s.cell.p, s.node.p, s.w.p, c, h->xyz_new.p, t.y.p, t.target.p, t.pweight.p, s.out.p, t.S.p,
+                       s.part.p, t.cnt.p);
+  GL_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_img_sum, dim3(1), dim3(1024), 0, h->st, (int64_t)nb, s.part.p, s.part.p + nb);
+  GL_CHECK_LAUNCH();
+  transpose_on(h, s, s.out.p, 1, g, 1, 0, true);       // dJ/dc_k += P^T r
+  transpose_on(h, s, t.S.p, D, murhs, D, 1, true);     // dJ/du_k += P^T S
+  double sum = 0.0;
+  unsigned long long no = 0;
+  GL_HIP(hipMemcpyAsync(&sum, s.part.p + nb, sizeof(double), hipMemcpyDeviceToHost, h->st));
+  GL_HIP(hipMemcpyAsync(&no, t.cnt.p, sizeof(no), hipMemcpyDeviceToHost, h->st));
+  GL_HIP(hipStreamSynchronize(h->st));
+  t.n_found = s.n_found;
+  t.n_obs = (int64_t)no;
+  t.n_folded = s.n_inverted;
+  t.min_ratio = s.min_ratio;
+  return sum;
+}
+
 void gl_sampler_destroy(glims_ctx* h, int64_t id) {
   (void)sampler_of(h, id, "glims_sampler_destroy");
   for (size_t k = 0; k < h->img_terms.size(); ++k)
@@ -1753,6 +2011,8 @@ void gl_sampler_destroy(glims_ctx* h, int64_t id) {
 void gl_sampler_destroy_all(glims_ctx* h) {
   for (auto* t : h->img_terms) delete t;
   h->img_terms.clear();
+  for (auto* t : h->dimg_terms) delete_deformed_term(t);
+  h->dimg_terms.clear();
   for (auto* s : h->samplers) delete s;
   h->samplers.clear();
 }

@@ -47,7 +47,11 @@ class ReducedFunctional:
     """
     J(m) and dJ/dm(m) for a simulation ``sim`` (TumorGrowth / TumorGrowthBrain) and the controls of ``parameter_map``, or,
     with ``names`` (a tuple of TumorGrowthBrain parameter names, BRAIN_CONTROLS), exactly those parameters (P = identity):
-    ``names=('E_WM', 'coupling')`` makes m = (E_WM, coupling).
+    ``names=('E_WM', 'coupling')`` makes m = (E_WM, coupling).  On a TumorGrowth simulation ``names`` picks among
+    ('diffusion', 'proliferation', 'coupling'), e.g. ``names=('coupling', 'diffusion')`` for a fit to a deformed image.
+
+    A term list with a deformed image term (``sim.image_term(..., deformed=True)``) is first order only: ``hessian`` and
+    ``hessian_matrix`` raise NotImplementedError.
 
     ``terms_builder(sim, n_steps)`` returns the misfit terms (see ``Handle.adjoint_gradient``) once the forward run of m has
     taken ``n_steps`` steps.  The last m is cached: scipy's ``fun`` / ``jac`` pair for one m costs one forward and one
@@ -62,12 +66,10 @@ class ReducedFunctional:
             self.names, self.P = parameter_map(self.n_params, self.brain)
         else:
             names = tuple(names)
-            if not self.brain:
-                raise ValueError("ReducedFunctional(names=...) selects TumorGrowthBrain parameters")
-            bad = [n for n in names if n not in BRAIN_CONTROLS]
+            allowed = BRAIN_CONTROLS if self.brain else TUMOR_NAMES   # (TumorGrowth: e.g. names=('coupling', 'diffusion'))
+            bad = [n for n in names if n not in allowed]
             if bad or len(set(names)) != len(names) or len(names) != self.n_params:
-                raise ValueError("names: %d distinct parameters of %s expected, got %s" % (self.n_params, BRAIN_CONTROLS,
-                                                                                          names))
+                raise ValueError("names: %d distinct parameters of %s expected, got %s" % (self.n_params, allowed, names))
             self.names, self.P = names, np.eye(len(names))
         self.terms_builder = terms_builder
         self.run_kwargs = dict(keep_nth=10 ** 9, save_method=None, clear_all=False, plot=False)
@@ -130,7 +132,11 @@ class ReducedFunctional:
         dirs = self._model_directions()
         self._evaluate(m)
         if self._H is None:
-            _, hv = self.sim.adjoint_hessian(self.terms_builder(self.sim, self._n_steps), dirs)
+            terms = self.terms_builder(self.sim, self._n_steps)
+            if any(t.get("deformed") for t in terms):
+                raise NotImplementedError("ReducedFunctional.hessian: second order through the location of a deformed image "
+                                          "term is not built; use a first-order method (L-BFGS-B)")
+            _, hv = self.sim.adjoint_hessian(terms, dirs)
             H = np.array([[float(np.sum(h[name])) for name in self.names] for h in hv]).T   # column j = H P e_j
             self._H = self.P.T @ H
             self.hessian_calls += 1

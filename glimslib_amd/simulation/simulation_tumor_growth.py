@@ -346,7 +346,7 @@ class TumorGrowth(FenicsSimulation):
         return key, sampler
 
     def image_term(self, step, image, kind='img_thresh', level=0.0, smooth=1.0, weight=1.0, mask=None,
-                   volume_weighted=True):
+                   volume_weighted=True, deformed=False, scale=1.0):
         """
         A misfit term that compares the concentration of recorded step `step` with the voxel image `image`
         (utils.data_io.Image) WHERE THE IMAGE WAS MEASURED:  1/2 w sum_voxels q (h(c(x_voxel)) - image)^2  with h the
@@ -356,17 +356,30 @@ class TumorGrowth(FenicsSimulation):
         are not observed; `mask` (array like the image, >= 0) weighs the voxels.  With volume_weighted the weight is
         multiplied by the voxel volume, so that J approximates 1/2 w int (h(c) - image)^2 dx and is on the scale of the nodal
         mass-matrix terms.  The same arguments give the same term object, whose arrays the backend uploads once.
+
+        deformed=True: the image shows the DEFORMED configuration x = X + scale u(X) (what sample_image(..., deformed=True)
+        produces: a segmentation of a tumour with mass effect).  The term then carries the grid of `image` and no sampler;
+        every gradient call locates the voxels in the mesh displaced by the step's own displacement and differentiates
+        through that location, so the coupling, E and the Poisson ratio get a gradient from image data alone.  J has a kink
+        where a voxel centre crosses a cell face; second order (adjoint_hessian) is not available with such a term, and
+        neither are partitioned runs.
         """
         if self._backend is None:
             raise RuntimeError("image_term needs a run() first (the grid is located in the run's device mesh)")
         if getattr(image, 'is_vector', False):
             raise ValueError("image_term takes a scalar image")
-        key = (int(step), id(image), kind, float(level), float(smooth), float(weight), id(mask), bool(volume_weighted))
+        if deformed and not isinstance(self._backend, _backend.Handle):
+            raise NotImplementedError("image_term(deformed=True) is not available on partitioned runs (the voxels would have "
+                                      "to be located in every rank's displaced cells); run on one GPU")
+        if deformed and not self.solver.mechanics:
+            raise ValueError("image_term(deformed=True) needs a run with mechanics (the voxels move with the displacement)")
+        key = (int(step), id(image), kind, float(level), float(smooth), float(weight), id(mask), bool(volume_weighted),
+               bool(deformed), float(scale))
         cache = getattr(self, '_image_terms', None)
         if cache is None or cache[0] is not self._backend:
             cache = self._image_terms = (self._backend, {})
         if key not in cache[1]:
-            _, sampler = self._grid_sampler(image.GetOrigin(), image.GetSpacing(), image.GetSize())
+            sampler = None if deformed else self._grid_sampler(image.GetOrigin(), image.GetSpacing(), image.GetSize())[1]
             target = np.ascontiguousarray(image.array, dtype=np.float64).reshape(-1)     # [z, y, x]: the sampler's order
             q = None
             if mask is not None:
@@ -374,8 +387,14 @@ class TumorGrowth(FenicsSimulation):
                 if q.shape != target.shape:
                     raise ValueError("image_term: the mask has %d voxels, the image %d" % (q.size, target.size))
             w = float(weight) * (float(np.prod(image.GetSpacing())) if volume_weighted else 1.0)
-            term = dict(step=int(step), kind=kind, level=float(level), smooth=float(smooth), weight=w, sampler=sampler,
-                        target=target, pweight=q)
+            term = dict(step=int(step), kind=kind, level=float(level), smooth=float(smooth), weight=w, target=target,
+                        pweight=q)
+            if deformed:
+                term.update(deformed=True, scale=float(scale),
+                            grid=(tuple(float(v) for v in image.GetOrigin()), tuple(float(v) for v in image.GetSpacing()),
+                                  tuple(int(v) for v in image.GetSize())))
+            else:
+                term['sampler'] = sampler
             cache[1][key] = (term, image, mask)   # (image and mask stay alive: their identity is the key)
         return cache[1][key][0]
 
@@ -545,6 +564,9 @@ class TumorGrowth(FenicsSimulation):
             if np.any(np.asarray(flux) != 0.0):
                 raise NotImplementedError("adjoint_hessian: von Neumann data on the concentration scale with D; "
                                           "second derivatives in D are not available for such a run")
+        if any(t.get('deformed') for t in terms):
+            raise NotImplementedError("adjoint_hessian: second order through the location of a deformed image term "
+                                      "(image_term(deformed=True)) is not built; use a first-order method")
         return h.adjoint_hessian(terms, directions)
 
     def adjoint_hessian(self, terms, directions):

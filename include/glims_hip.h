@@ -736,8 +736,8 @@ int glims_sampler_destroy(glims_ctx* h, int64_t id);   /* glims_destroy releases
  * two).  GLIMS_E_USAGE with a reason, before anything is allocated or changed: a partitioned handle (world > 1), a snapshot or
  * CURRENT source on a handle set up without mechanics, an unknown snapshot, CURRENT before glims_set_state, HOST with a NULL
  * u_host, a non-finite scale, flags != 0, and everything the undeformed creators refuse.
- * glims_adjoint_image_terms refuses a deformed sampler: its points depend on the state through u, the derivative of the location
- * is not built, and a frozen-location gradient would be silently inexact. */
+ * glims_adjoint_image_terms refuses a deformed sampler: its points depend on the state through u, and a frozen-location
+ * gradient would be silently inexact.  glims_adjoint_deformed_image_terms (below) is the term that moves with the state. */
 #define GLIMS_FIELD_XYZ 5   /* glims_sampler_apply: the mesh's REFERENCE coordinates (ncomp = dim) -> the back map X(x_p) */
 int glims_sampler_create_grid_deformed(glims_ctx* h, const double* origin, const double* spacing, const int64_t* size,
                                        int64_t u_source, const double* u_host, double scale, int flags, int64_t* id);
@@ -804,6 +804,55 @@ int glims_adjoint_image_terms(glims_ctx* h, int n, const glims_image_misfit* ter
 /* out = (sampler id, number of points, number of observed points) of stored term k; on a partitioned handle out[2] is the
  * number of observed points THIS RANK counts (their sum over the ranks is the term's observed count) */
 int glims_adjoint_image_info(glims_ctx* h, int k, int64_t out[3]);
+
+/* ---- image terms in the deformed configuration: the gradient through the location ---------------------------------------------
+ * The terms above observe the REFERENCE configuration X.  A scan shows x = X + u(X): a segmentation of a tumour with mass effect
+ * is a target in the deformed configuration, and it is the only image data that carry information on the coupling, E and nu
+ * (the reference gets a displacement target from an ANTs registration instead, image_based_optimization.py:264-292).  A deformed
+ * term observing recorded step k locates its points x_p, at EVERY evaluation, in the mesh whose node a sits at
+ *     y_a = fl(X_a + fl(scale * u_k,a)),   u_k = K_el^-1 (G c_k + f)   (the adjoint's own solve, to 1e-12 ||rhs||),
+ * with the rules of the samplers (GLIMS_SAMPLE_EPS, the smallest caller cell index wins), and with the winner's weights w_p,a
+ *     v_p = sum_a w_p,a c_k,a,    J_img = 1/2 w sum_p q_p (h(v_p) - t_p)^2,    r_p = w q_p h'(v_p) (h(v_p) - t_p),
+ *     dJ_img/dc_k = P^T r                                   (the formula above with the deformed weights),
+ *     dJ_img/du_k = P^T S,   S_p = -scale r_p grad_y c_k|T(p)   [n_points][dim],
+ * since differentiating sum_a w_a y_a = x_p gives dv_p/dy_b = -w_p,b grad_y c_k|T(p), the constant gradient of c_k on the
+ * deformed cell.  dJ/du_k is added to the right-hand side of the elastic adjoint, the vector a GLIMS_MISFIT_U_L2 term of the
+ * same step writes to: u_k is solved ONCE per observed step and mu_k = K_el^-1 dJ/du_k once, whatever the number of terms;
+ * G^T mu_k and the gamma, E and nu sums follow as for a displacement term (Dirichlet dofs as that solve handles them).
+ * J is continuous and piecewise smooth in the parameters: it has a KINK where a point crosses a cell face and a JUMP where a
+ * point enters or leaves the displaced mesh (possible only where the boundary is not clamped).  The gradient is that of the
+ * smooth piece the evaluation sits on.  A winning cell whose det(E_deformed) / det(E_reference) is not > 0 (folded, flat or
+ * non-finite) gets S_p = 0.
+ *
+ * A point is OBSERVED iff it is found in the displaced mesh AT THIS EVALUATION, t_p is not NaN and q_p != 0.  The sampler keeps
+ * no coordinates, so a moving term carries its own point set: xyz[n_points][dim], or (xyz == NULL) the grid origin + index *
+ * spacing of size[dim] points, x fastest; it is copied to the device once, with target and pweight.  The terms are a SECOND
+ * stored list: glims_adjoint_deformed_image_terms replaces this list only (n = 0 clears it), and glims_adjoint_gradient /
+ * _gradient_full evaluate, per step, the nodal terms in list order, then the fixed image terms, then the deformed terms in
+ * list order.  With an empty deformed list every call issues exactly the work it issued before.  The forward state,
+ * glims_stats, the forward path's elastic solve history and the derive cache of U are left as they were; no float atomics,
+ * block sums in a fixed order: the same call gives the same bits every time.  With scale = 0, J and the c-derivatives have
+ * the bits of the fixed term on the same points and dJ/du_k is 0.
+ *
+ * GLIMS_E_USAGE with a reason, the old list left in place: a partitioned handle (world > 1), a handle set up without
+ * mechanics, an unknown kind, smooth <= 0 for a threshold term, a non-finite weight or scale, a negative or non-finite q_p, a
+ * null target, and everything the sampler creators refuse of their points.  A step beyond the trajectory is refused by the
+ * gradient call.  GLIMS_E_HIP (with the figures) when hipMemGetInfo says the copies or the scratch sampler do not fit.
+ * Second order through the location is not built: glims_adjoint_hessian / _hessian_spmd return GLIMS_E_USAGE while the list
+ * is non-empty. */
+typedef struct glims_deformed_image_misfit {
+  int64_t step; int kind;                 /* GLIMS_MISFIT_IMG_L2 / _IMG_THRESH */
+  double level, smooth, weight, scale;
+  int64_t n_points; const double* xyz;    /* point set [n_points][dim], or xyz == NULL: the grid below */
+  double origin[3], spacing[3]; int64_t size[3];
+  const double* target;                   /* [n_points] or grid order [z][y][x]; NaN = not observed */
+  const double* pweight;                  /* q_p or NULL */
+} glims_deformed_image_misfit;
+int glims_adjoint_deformed_image_terms(glims_ctx* h, int n, const glims_deformed_image_misfit* terms);
+/* out = n_points, found, observed, folded cells of the LAST evaluation of term k (-1 before the first); min_ratio likewise
+ * (1 before the first).  folded cells / min_ratio: the figures of glims_sampler_deformation_info for the mesh at X + scale u_k
+ * (cells of the mesh whose ratio is not > 0; the smallest ratio). */
+int glims_adjoint_deformed_image_info(glims_ctx* h, int k, int64_t out[4], double* min_ratio);
 
 /* ---- derived fields of a recorded step, on the device -----------------------------------------------------------------------
  * The reference's PostProcess classes project UFL expressions of a recorded step onto the P1 space (helper_classes.py:1521-1972:
