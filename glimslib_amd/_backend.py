@@ -188,6 +188,7 @@ SIGNATURES = {
                                         _dp, _dp, _dp, _dp, _dp, _dp]),
     "glims_adjoint_hessian_spmd": (C.c_int, [_h, C.c_int, C.POINTER(Misfit), C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
                                              _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "glims_adjoint_hessian_full": (C.c_int, [_h, C.c_int, C.POINTER(Misfit), C.c_int] + [_dp] * 20),
     "glims_adjoint_stats": (C.c_int, [_h, _i64p, _dp]),
     "glims_sampler_create_points": (C.c_int, [_h, C.c_int64, _dp, C.c_int, _i64p]),
     "glims_sampler_create_grid": (C.c_int, [_h, _dp, _dp, _i64p, C.c_int, _i64p]),
@@ -722,7 +723,20 @@ class Handle:
         'stats' (tangent-linear / second-order PCG iterations, extra elastic solves, ms)}.
         collective=True calls glims_adjoint_hessian_spmd: the same call on one GPU, and on a partitioned handle the
         collective one (every rank with the same terms and directions; 'c0' entries in the local numbering, ghosts of
-        'hv_c0' are 0).  The default keeps refusing partitioned handles."""
+        'hv_c0' are 0).  The default keeps refusing partitioned handles.  E and nu are first order here: a direction keyed
+        'E' or 'nu' is a ValueError (adjoint_hessian_full takes them)."""
+        return self._adjoint_hessian(terms, directions, n_labels, collective, False)
+
+    def adjoint_hessian_full(self, terms, directions, n_labels=None):
+        """glims_adjoint_hessian_full (one GPU): adjoint_hessian whose directions take 'E' and 'nu' ([n_labels] or a scalar
+        for every label) as well -- the exact second-order elastic adjoint -- and whose result gains 'E', 'nu' (dJ/dE, dJ/dnu
+        as adjoint_gradient(elastic=True)) and 'hv_E', 'hv_nu' ([n_dir, n_labels]).  No elastic solve is added
+        ('stats'['mech_solves'] as adjoint_hessian).  A partitioned handle is refused by the library (BackendError,
+        GLIMS_E_USAGE), and so is a direction in 'E' / 'nu' on a handle set up without mechanics; without such a direction
+        that handle gets the call with NULL hv_E / hv_nu (no displacement term can exist there: the products are 0)."""
+        return self._adjoint_hessian(terms, directions, n_labels, False, True)
+
+    def _adjoint_hessian(self, terms, directions, n_labels, collective, elastic):
         if self.n_labels is None:
             raise ValueError("adjoint_hessian before set_materials")
         if n_labels is not None and int(n_labels) != self.n_labels:
@@ -731,6 +745,8 @@ class Handle:
         directions = list(directions)
         P = len(directions)
         terms = list(terms)
+        if not elastic and any(k in d for d in directions for k in ("E", "nu")):
+            raise ValueError("adjoint_hessian: E / nu are first order here; directions in 'E' / 'nu' go to adjoint_hessian_full")
         if any(_IMAGE_KINDS.get(t["kind"]) is not None and t.get("deformed") for t in terms):
             raise NotImplementedError("adjoint_hessian: second order through the location of a deformed image term is not "
                                       "built (glims_adjoint_hessian refuses while such a term is stored)")
@@ -751,6 +767,21 @@ class Handle:
         g = [np.zeros(L) for _ in range(3)] + [np.zeros(n)]
         hv = [np.zeros((max(1, P), L)) for _ in range(3)] + [np.zeros((max(1, P), n))]
         st = np.zeros(4)
+        if elastic:
+            edirs = [table("E", L), table("nu", L)]
+            eg = [np.zeros(L) for _ in range(2)]
+            ehv = [np.zeros((max(1, P), L)) for _ in range(2)]
+            # (the library refuses non-NULL hv_E / hv_nu on a handle without mechanics: asked for only where they can be non-zero)
+            want = getattr(self, "with_mechanics", True) or any(d is not None for d in edirs)
+            self._check(self.lib.glims_adjoint_hessian_full(
+                self._h, len(terms), arr, int(P), *[_ptr(d, _dp) for d in dirs + edirs], C.byref(J),
+                *[_ptr(a, _dp) for a in g + eg], *[_ptr(a, _dp) for a in hv], *[_ptr(a if want else None, _dp) for a in ehv],
+                _ptr(st, _dp)))
+            del keep
+            return {"J": J.value, "D": g[0], "rho": g[1], "gamma": g[2], "c0": g[3], "E": eg[0], "nu": eg[1],
+                    "hv_D": hv[0][:P], "hv_rho": hv[1][:P], "hv_gamma": hv[2][:P], "hv_c0": hv[3][:P], "hv_E": ehv[0][:P],
+                    "hv_nu": ehv[1][:P],
+                    "stats": {"tlm_pcg_its": int(st[0]), "soa_pcg_its": int(st[1]), "mech_solves": int(st[2]), "ms": st[3]}}
         call = self.lib.glims_adjoint_hessian_spmd if collective else self.lib.glims_adjoint_hessian
         self._check(call(self._h, len(terms), arr, int(P), *[_ptr(d, _dp) for d in dirs], C.byref(J),
                          *[_ptr(a, _dp) for a in g], *[_ptr(a, _dp) for a in hv], _ptr(st, _dp)))

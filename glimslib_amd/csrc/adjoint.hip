@@ -13,6 +13,7 @@
 //   C_t = dJ/dgamma_t / (2 mu_t + d lam_t) give dJ/dp_t = gamma_t (2 mu' + d lam') C_t - (2 mu' A_t + lam' B_t).
 // (carrying capacity 1, as in the forward kernels: the reaction weights of k_corner_weights are rho |T| d!/(d+3)!.)
 #include "glims_internal.h"
+#include "lame_derivs.h"
 
 #include <algorithm>
 #include <cmath>
@@ -737,6 +738,26 @@ struct BackwardSweep {
   }
 };
 
+// The totals (A_t, B_t, C_t) of label l from the gradient's sums: sums3 [L][3] (D, rho, gamma), esums [L][2] (A, B).
+// C_t = sum_k int_t |T|/(d+1) div mu_k sum_a c_k,a = (dJ/dgamma sum) / (2 mu_t + d lam_t): mode 1's sum carries the factor
+ElasticSums elastic_totals(const glims_ctx* h, int dim, int l, const double* sums3, const double* esums) {
+  const double* mh = h->mat_host.data();
+  const double den = 2.0 * mh[3 * GL_MAX_LABELS + l] + dim * mh[4 * GL_MAX_LABELS + l];
+  return {esums[l * 2 + 0], esums[l * 2 + 1], den != 0.0 ? sums3[l * 3 + 2] / den : 0.0};
+}
+
+// dJ/dE_t, dJ/dnu_t in label order (lame_derivs.h)
+void write_elastic_labels(const glims_ctx* h, int dim, const double* sums3, const double* esums, double* dE, double* dnu) {
+  const double* mh = h->mat_host.data();
+  for (int l = 0; l < h->n_labels; ++l) {
+    const double gam = mh[2 * GL_MAX_LABELS + l];
+    const LameDerivs d = lame_derivs(mh[5 * GL_MAX_LABELS + l], mh[6 * GL_MAX_LABELS + l]);
+    const ElasticSums tot = elastic_totals(h, dim, l, sums3, esums);
+    if (dE) dE[l] = elastic_gradient_row(dim, gam, d.m_E, d.l_E, tot);
+    if (dnu) dnu[l] = elastic_gradient_row(dim, gam, d.m_nu, d.l_nu, tot);
+  }
+}
+
 template <int D>
 int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_out, double* dD, double* drho,
                double* dgamma, double* dc0, double* dE, double* dnu) {
@@ -792,24 +813,7 @@ int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_o
     }
   }
   sw.write_labels(sums.data(), dD, drho, dgamma);
-  for (int l = 0; elastic && l < h->n_labels; ++l) {
-    // C_t = sum_k int_t |T|/(d+1) div mu_k sum_a c_k,a = (dJ/dgamma sum) / (2 mu_t + d lam_t): mode 1's sum carries the factor
-    const double* mh = h->mat_host.data();
-    const double gam = mh[2 * GL_MAX_LABELS + l], mu = mh[3 * GL_MAX_LABELS + l], lam = mh[4 * GL_MAX_LABELS + l];
-    const double E = mh[5 * GL_MAX_LABELS + l], nu = mh[6 * GL_MAX_LABELS + l];
-    const double den = 2.0 * mu + D * lam;
-    const double Ct = den != 0.0 ? sums[l * 3 + 2] / den : 0.0;
-    const double At = sums[L3 + l * 2 + 0], Bt = sums[L3 + l * 2 + 1];
-    const double q = (1.0 + nu) * (1.0 - 2.0 * nu);
-    if (dE) {
-      const double mp = 1.0 / (2.0 * (1.0 + nu)), lp = nu / q;
-      dE[l] = gam * (2.0 * mp + D * lp) * Ct - (2.0 * mp * At + lp * Bt);
-    }
-    if (dnu) {
-      const double mp = -E / (2.0 * (1.0 + nu) * (1.0 + nu)), lp = E * (1.0 + 2.0 * nu * nu) / (q * q);
-      dnu[l] = gam * (2.0 * mp + D * lp) * Ct - (2.0 * mp * At + lp * Bt);
-    }
-  }
+  if (elastic) write_elastic_labels(h, D, sums.data(), sums.data() + L3, dE, dnu);
   *J_out = sw.J;
   a.gradients++;
   a.ms_backward += 1e3 * (omp_get_wtime() - t0);
@@ -996,12 +1000,17 @@ __global__ __launch_bounds__(256) void k_hsens(int64_t n_cells, int l0, const in
 
 // y[row][a] = (G dc + sum_t dgamma_t G_t c)[row][a] = sum over the row's cells of
 //   (2 mu_T + d lam_T) |T| / (d+1) (gamma_T sum_m dc_m + dgamma_T sum_m c_m) dphi_row / dx_a     (owned rows; row-owned)
-template <int D>
+// EL (a direction in E / nu): plus dkap_T |T| / (d+1) sum_m c_m dphi_row / dx_a with the per-label table
+// dkap_t = gamma_t (2 dm_t + d dl_t), the E / nu part of dG c, and the row's entries of `sub` (dK u_k, from k_dkel_rows) are
+// subtracted on the way out: y = G dc + dG c - dK u_k from one pass.  The terms of EL = false keep their arithmetic and its
+// order.
+template <int D, bool EL>
 __global__ void k_gdir_rows(int64_t n_own, const int64_t* __restrict__ cslice_ptr, const uint32_t* __restrict__ cslots,
                             const int32_t* __restrict__ celem, const uint8_t* __restrict__ diag_k,
                             const int32_t* __restrict__ cell_nodes, const double* __restrict__ egeo,
                             const uint8_t* __restrict__ label, const double* __restrict__ mat,
-                            const double* __restrict__ dgam, const double* __restrict__ c, const double* __restrict__ dc,
+                            const double* __restrict__ dgam, const double* __restrict__ dkap,
+                            const double* __restrict__ sub, const double* __restrict__ c, const double* __restrict__ dc,
                             double* __restrict__ y) {
   constexpr int NV = D + 1, GE = 1 + NV * D;
   const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1028,7 +1037,8 @@ __global__ void k_gdir_rows(int64_t n_own, const int64_t* __restrict__ cslice_pt
       Sd += dc[k];
     }
     const double mu = mat[3 * GL_MAX_LABELS + lab], lam = mat[4 * GL_MAX_LABELS + lab];
-    const double w = (2.0 * mu + D * lam) * g[0] * (1.0 / (D + 1)) * (mat[2 * GL_MAX_LABELS + lab] * Sd + dgam[lab] * Sc);
+    double w = (2.0 * mu + D * lam) * g[0] * (1.0 / (D + 1)) * (mat[2 * GL_MAX_LABELS + lab] * Sd + dgam[lab] * Sc);
+    if (EL) w += dkap[lab] * g[0] * (1.0 / (D + 1)) * Sc;
 #pragma unroll
     for (int m = 0; m < NV; ++m)
       if (((sl >> (8 * m)) & 255u) == dk)
@@ -1036,7 +1046,151 @@ __global__ void k_gdir_rows(int64_t n_own, const int64_t* __restrict__ cslice_pt
         for (int a = 0; a < D; ++a) acc[a] += w * g[1 + m * D + a];
   }
 #pragma unroll
-  for (int a = 0; a < D; ++a) y[row * D + a] = acc[a];
+  for (int a = 0; a < D; ++a) y[row * D + a] = EL ? acc[a] - sub[row * D + a] : acc[a];
+}
+
+// y_p[row][b] = (dK_p v)[row][b] = sum over the row's cells T of |T| (2 dm_p,T eps(v)|_T + dl_p,T div v|_T I) grad phi_row, the
+// stiffness operator along the E / nu part of direction p applied to a displacement-like vector v (u_k with its Dirichlet
+// values, or mu_k).  Row-owned through the incidence lists, no atomics, P <= GL_HESS_MAXDIR columns per launch: the cell's
+// strain is formed once, each column adds two products per component.  dlame[p][2][GL_MAX_LABELS] = (dm, dl) per label;
+// columns stored one after the other, ld apart.  Bytes per row and incidence: the slot word, cell id, geometry record and
+// label as in k_hess_rows; the gathered v (8 d B per vertex) mostly hits the caches; 8 d P B written per row.
+template <int D>
+__global__ __launch_bounds__(256) void k_dkel_rows(int64_t n_own, int P, int64_t ld, const int64_t* __restrict__ cslice_ptr,
+                                                   const uint32_t* __restrict__ cslots, const int32_t* __restrict__ celem,
+                                                   const uint8_t* __restrict__ diag_k, const int32_t* __restrict__ cell_nodes,
+                                                   const double* __restrict__ egeo, const uint8_t* __restrict__ label,
+                                                   const double* __restrict__ dlame, const double* __restrict__ v,
+                                                   double* __restrict__ y) {
+  constexpr int NV = D + 1, GE = 1 + NV * D;
+  const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= n_own) return;
+  const int64_t s = row >> 6, lane = row & 63;
+  const int64_t cbase = cslice_ptr[s];
+  const int clen = (int)((cslice_ptr[s + 1] - cbase) >> 6);
+  const uint32_t dk = diag_k[row];
+  double acc[GL_HESS_MAXDIR][D];
+#pragma unroll
+  for (int p = 0; p < GL_HESS_MAXDIR; ++p)
+#pragma unroll
+    for (int b = 0; b < D; ++b) acc[p][b] = 0.0;
+  for (int q = 0; q < clen; ++q) {
+    const int64_t ci = cbase + (int64_t)q * GL_WAVE + lane;
+    const int32_t e = celem[ci];
+    if (e < 0) continue;
+    const uint32_t sl = cslots[ci];
+    const double* g = egeo + (int64_t)e * GE;
+    const double vol = g[0];
+    const int lab = label[e];
+    double gi[D];   // grad phi_i (the row's vertex of the cell)
+#pragma unroll
+    for (int a = 0; a < D; ++a) gi[a] = 0.0;
+#pragma unroll
+    for (int m = 0; m < NV; ++m)
+      if (((sl >> (8 * m)) & 255u) == dk)
+#pragma unroll
+        for (int a = 0; a < D; ++a) gi[a] = g[1 + m * D + a];
+    // grad v_h [a][b] = d_a v_b = sum_m v_{m,b} dphi_m/dx_a
+    double gv[D][D] = {};
+#pragma unroll
+    for (int m = 0; m < NV; ++m) {
+      const int64_t k = cell_nodes[(int64_t)e * NV + m];
+#pragma unroll
+      for (int b = 0; b < D; ++b) {
+        const double vm = v[k * D + b];
+#pragma unroll
+        for (int a = 0; a < D; ++a) gv[a][b] += vm * g[1 + m * D + a];
+      }
+    }
+    double tr = 0.0, se[D];   // se = 2 eps(v) grad phi_i
+#pragma unroll
+    for (int a = 0; a < D; ++a) tr += gv[a][a];
+#pragma unroll
+    for (int b = 0; b < D; ++b) {
+      double t = 0.0;
+#pragma unroll
+      for (int a = 0; a < D; ++a) t += (gv[a][b] + gv[b][a]) * gi[a];
+      se[b] = t;
+    }
+#pragma unroll
+    for (int p = 0; p < GL_HESS_MAXDIR; ++p)
+      if (p < P) {
+        const double* dp = dlame + (size_t)p * 2 * GL_MAX_LABELS;
+        const double dm = dp[lab], dl = dp[GL_MAX_LABELS + lab];
+#pragma unroll
+        for (int b = 0; b < D; ++b) acc[p][b] += vol * (dm * se[b] + dl * tr * gi[b]);
+      }
+  }
+#pragma unroll
+  for (int p = 0; p < GL_HESS_MAXDIR; ++p)
+    if (p < P)
+#pragma unroll
+      for (int b = 0; b < D; ++b) y[(size_t)p * ld + row * D + b] = acc[p][b];
+}
+
+// Per-label second-order sums of the E / nu rows, one direction: the layout, grid and fixed-order reduction of k_sens (then
+// k_sens_final), with a partials buffer of its own.  Geometry and vertex ids are read once for both pairs:
+//   q0 = int_T eps(dmu):eps(u) + eps(mu):eps(du),   q1 = int_T div dmu div u + div mu div du
+// counted: as in k_sens (partitioned handles, else nullptr)
+template <int D>
+__global__ __launch_bounds__(256) void k_hesens(int64_t n_cells, int l0, const int32_t* __restrict__ cell_nodes,
+                                                const double* __restrict__ egeo, const uint8_t* __restrict__ label,
+                                                const double* __restrict__ u, const double* __restrict__ mu,
+                                                const double* __restrict__ du, const double* __restrict__ dmu,
+                                                const uint8_t* __restrict__ counted, double* __restrict__ partials) {
+  constexpr int NV = D + 1, GE = 1 + NV * D;
+  double acc[GL_ADJ_LT][2];
+#pragma unroll
+  for (int j = 0; j < GL_ADJ_LT; ++j) acc[j][0] = acc[j][1] = 0.0;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n_cells; e += stride) {
+    const int j = label[e] - l0;
+    if (j < 0 || j >= GL_ADJ_LT || (counted && !counted[e])) continue;
+    const double* g = egeo + e * GE;
+    const double vol = g[0];
+    // grad w_h [a][b] = d_a w_b = sum_m w_{m,b} dphi_m/dx_a
+    double gu[D][D] = {}, gm[D][D] = {}, gdu[D][D] = {}, gdm[D][D] = {};
+#pragma unroll
+    for (int m = 0; m < NV; ++m) {
+      const int64_t k = cell_nodes[e * NV + m];
+#pragma unroll
+      for (int b = 0; b < D; ++b) {
+        const double um = u[k * D + b], mm = mu[k * D + b], dum = du[k * D + b], dmm = dmu[k * D + b];
+#pragma unroll
+        for (int a = 0; a < D; ++a) {
+          const double ga = g[1 + m * D + a];
+          gu[a][b] += um * ga;
+          gm[a][b] += mm * ga;
+          gdu[a][b] += dum * ga;
+          gdm[a][b] += dmm * ga;
+        }
+      }
+    }
+    double ee = 0.0, tu = 0.0, tm = 0.0, tdu = 0.0, tdm = 0.0;
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+      tu += gu[a][a];
+      tm += gm[a][a];
+      tdu += gdu[a][a];
+      tdm += gdm[a][a];
+#pragma unroll
+      for (int b = 0; b < D; ++b)
+        ee += 0.25 * ((gdm[a][b] + gdm[b][a]) * (gu[a][b] + gu[b][a]) + (gm[a][b] + gm[b][a]) * (gdu[a][b] + gdu[b][a]));
+    }
+    const double a0 = vol * ee, a1 = vol * (tdm * tu + tm * tdu);
+#pragma unroll
+    for (int q = 0; q < GL_ADJ_LT; ++q)
+      if (q == j) {
+        acc[q][0] += a0;
+        acc[q][1] += a1;
+      }
+  }
+  block_partials(reinterpret_cast<double (&)[GL_ADJ_LT * 2]>(acc), partials);   // flat: [q][k] at q * 2 + k
+}
+
+__global__ void k_sub(int64_t n, const double* __restrict__ x, double* __restrict__ y) {   // y -= x
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) y[i] -= x[i];
 }
 
 // h'(c) and h''(c) of a concentration term (1 and 0 for C_L2)
@@ -1403,13 +1557,15 @@ struct AdjCountGuard {
 
 // Device memory of a Hessian call on top of the trajectory, and what is free now: the stored tangent-linear states dominate,
 // 8 P B per node and recorded state (see glims_hip.h)
-bool hessian_fits(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, std::string* why) {
+// el_dirs (glims_adjoint_hessian_full with a direction in E / nu): 2 P more vectors of dim x n_nodes (dK_p u_k, dK_p mu_k)
+bool hessian_fits(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, std::string* why, bool el_dirs = false) {
   const int64_t nn = h->n_nodes, nd = nn * h->dim;
   const int N = (int)h->adj.traj.size() - 1;
   bool any_u = false;
   for (int k = 0; k < n_terms; ++k) any_u = any_u || terms[k].kind == GLIMS_MISFIT_U_L2;
   const size_t need = 8 * ((size_t)(N + 1) * P * nn + (size_t)(9 * P + 16) * nn + (any_u ? (size_t)14 * nd : 0) +
-                           (size_t)2 * h->n_cells + (size_t)h->pat.total_entries);
+                           (any_u && el_dirs ? (size_t)2 * P * nd : 0) + (size_t)2 * h->n_cells +
+                           (size_t)h->pat.total_entries);
   size_t fr = 0, tot = 0;
   GL_HIP(hipMemGetInfo(&fr, &tot));
   if (need <= fr) return true;
@@ -1424,11 +1580,19 @@ bool hessian_fits(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, s
 // Partitioned handles (glims_adjoint_hessian_spmd, which has taken the memory verdict of all ranks: mem_checked): dc_n, nu_n,
 // du and dmu exchange their ghosts after their solves, hd and ue before the mass product, the per-label sums count a cell on
 // one rank (AdjointState::counted) and are gathered with the gradient's.
+// el (glims_adjoint_hessian_full, one GPU; nullptr otherwise): the E / nu directions, gradient rows and products.  The sweep
+// then runs the gradient's E / nu pass (mode 2) as glims_adjoint_gradient_full does; with a direction in E / nu (el_dirs) du
+// and dmu take -dK u_k and -dK mu_k on their right-hand sides, dG carries its E / nu part, and k_hesens sums the E / nu rows.
+// Without one, every launch of the other outputs is the one glims_adjoint_hessian issues: the same bits.
+struct ElasticSecond {
+  const double *dir_E, *dir_nu;
+  double *dE, *dnu, *hv_E, *hv_nu;
+};
 template <int D>
 int hessian_t(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, const double* dir_D, const double* dir_rho,
               const double* dir_gamma, const double* dir_c0, double* J_out, double* dD, double* drho, double* dgamma,
               double* dc0, double* hv_D, double* hv_rho, double* hv_gamma, double* hv_c0, double* stats,
-              bool mem_checked) {
+              bool mem_checked, const ElasticSecond* el = nullptr) {
   AdjointState& a = h->adj;
   const int64_t n = h->n_own, nn = h->n_nodes, nd = nn * D;
   const int N = (int)a.traj.size() - 1;
@@ -1438,11 +1602,13 @@ int hessian_t(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, const
   for (int k = 0; k < n_terms; ++k) any_u = any_u || terms[k].kind == GLIMS_MISFIT_U_L2;
   if (!mem_checked) {
     std::string why;
-    if (!hessian_fits(h, n_terms, terms, P, &why)) throw glims_error(GLIMS_E_HIP, why);
+    if (!hessian_fits(h, n_terms, terms, P, &why, el && (el->dir_E || el->dir_nu))) throw glims_error(GLIMS_E_HIP, why);
   }
+  const bool el_dirs = el && any_u && (el->dir_E || el->dir_nu);
+  const bool el_sums = el && any_u && (el->hv_E || el->hv_nu);   // also without el_dirs: the mixed rows H[E, D] ... are not 0
   AdjCountGuard counts(a);
   AdjWork wk;
-  adjoint_setup<D>(h, n_terms, terms, false, wk);
+  adjoint_setup<D>(h, n_terms, terms, el != nullptr, wk);
   // direction tables; material copies with the gamma row replaced by dgamma_p (the dgamma_t G_t^T mu pass)
   const size_t LM = GL_MAX_LABELS;
   std::vector<double> dir((size_t)P * 3 * LM, 0.0), dmat((size_t)P * 5 * LM, 0.0);
@@ -1459,6 +1625,39 @@ int hessian_t(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, const
   dvec<double> urhs, du, dmurhs, dmu, ue, uMe;
   d_dir.upload(dir, h->st);
   d_dmat.upload(dmat, h->st);
+  // E / nu directions: (dm, dl)_p per label [P][2][LM]; dkap_p = gamma (2 dm_p + d dl_p) [P][LM] (the E / nu part of dG c);
+  // material copies with the Lame rows replaced by (dm_p, dl_p) (the E / nu part of dG^T mu through mode 1 and k_gt_rows)
+  std::vector<double> dlame, dkap, dmat2;
+  dvec<double> d_dlame, d_dkap, d_dmat2, dKu, dKmu, hesums, hepart;
+  if (el_dirs) {
+    dlame.assign((size_t)P * 2 * LM, 0.0);
+    dkap.assign((size_t)P * LM, 0.0);
+    dmat2.assign((size_t)P * 5 * LM, 0.0);
+    const double* mh = h->mat_host.data();
+    for (int p = 0; p < P; ++p) {
+      std::copy(h->mat_host.begin(), h->mat_host.begin() + 5 * LM, dmat2.begin() + (size_t)p * 5 * LM);
+      for (int l = 0; l < L; ++l) {
+        const LameDerivs d = lame_derivs(mh[5 * LM + l], mh[6 * LM + l]);
+        double dm, dl;
+        lame_direction(d, el->dir_E ? el->dir_E[(size_t)p * L + l] : 0.0, el->dir_nu ? el->dir_nu[(size_t)p * L + l] : 0.0,
+                       &dm, &dl);
+        dlame[((size_t)p * 2 + 0) * LM + l] = dm;
+        dlame[((size_t)p * 2 + 1) * LM + l] = dl;
+        dkap[(size_t)p * LM + l] = mh[2 * LM + l] * (2.0 * dm + D * dl);
+      }
+      std::copy(dlame.begin() + (size_t)p * 2 * LM, dlame.begin() + ((size_t)p * 2 + 2) * LM,
+                dmat2.begin() + ((size_t)p * 5 + 3) * LM);
+    }
+    d_dlame.upload(dlame, h->st);
+    d_dkap.upload(dkap, h->st);
+    d_dmat2.upload(dmat2, h->st);
+    dKu.alloc_zero((size_t)P * nd, h->st);
+    dKmu.alloc_zero((size_t)P * nd, h->st);
+  }
+  if (el_sums) {
+    hesums.alloc_zero((size_t)P * LM * 2, h->st);
+    hepart.alloc_zero((size_t)GL_ADJ_BLOCKS * GL_ADJ_LT * 2, h->st);
+  }
   dcs.alloc_zero((size_t)(N + 1) * P * nn, h->st);   // dc_n of direction p at dcs[(n P + p) nn]
   for (auto* v : {&nu, &nu_next, &dg, &hrhs}) v->alloc_zero((size_t)P * nn, h->st);
   hd.alloc_zero((size_t)nn, h->st);
@@ -1488,7 +1687,7 @@ int hessian_t(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, const
     mp.rows.alloc_zero((size_t)h->world * 2 * P, h->st);
   }
   ForwardGuard guard(h, wk);
-  BackwardSweep<D> sw(h, wk, n_terms, terms, false);
+  BackwardSweep<D> sw(h, wk, n_terms, terms, el != nullptr);
   if (dir_c0) exchange_cols(dcs.p);   // (the caller's ghost entries are not trusted; under the guard: glims_stats stay)
   const uint8_t* fxc = sw.fxc;
   const DevPattern& pt = h->pat;
@@ -1552,13 +1751,28 @@ int hessian_t(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, const
       auto gt_pass = [&](const double* mat, const double* x, const double* v, double* sums) {
         sens_pass<D>(h, 1, mat, x, v, counted, hqcell.p, hpart.p, sums, 3, 2);
       };
+      if (el_dirs) {   // dK_p u_k (u_k with its Dirichlet values: the lifting term is differentiated too) and dK_p mu_k
+        for (const auto& vy : {std::make_pair((const double*)wk.uk.p, dKu.p), std::make_pair((const double*)wk.mu.p, dKmu.p)}) {
+          hipLaunchKernelGGL(k_dkel_rows<D>, dim3(grid_of(n)), dim3(256), 0, h->st, n, P, nd, pt.cslice_ptr.p, pt.cslots.p,
+                             pt.celem.p, pt.diag_k.p, a.cell_nodes.p, h->egeo.p, h->label.p, d_dlame.p, vy.first, vy.second);
+          GL_CHECK_LAUNCH();
+        }
+      }
       for (int p = 0; p < P && status == GLIMS_OK; ++p) {
         double* dgp = dg.p + (size_t)p * nn;
         double* hs = hsums.p + (size_t)p * LM * 3;
         int64_t its = 0;
-        hipLaunchKernelGGL(k_gdir_rows<D>, dim3(grid_of(n)), dim3(256), 0, h->st, n, pt.cslice_ptr.p, pt.cslots.p,
-                           pt.celem.p, pt.diag_k.p, a.cell_nodes.p, h->egeo.p, h->label.p, h->mat.p,
-                           d_dir.p + (p * 3 + 2) * LM, c, dc_of(step, p), urhs.p);
+        if (el_dirs) {   // G dc + dG c - dK u_k
+          hipLaunchKernelGGL((k_gdir_rows<D, true>), dim3(grid_of(n)), dim3(256), 0, h->st, n, pt.cslice_ptr.p, pt.cslots.p,
+                             pt.celem.p, pt.diag_k.p, a.cell_nodes.p, h->egeo.p, h->label.p, h->mat.p,
+                             d_dir.p + (p * 3 + 2) * LM, d_dkap.p + (size_t)p * LM, dKu.p + (size_t)p * nd, c, dc_of(step, p),
+                             urhs.p);
+        } else {
+          hipLaunchKernelGGL((k_gdir_rows<D, false>), dim3(grid_of(n)), dim3(256), 0, h->st, n, pt.cslice_ptr.p, pt.cslots.p,
+                             pt.celem.p, pt.diag_k.p, a.cell_nodes.p, h->egeo.p, h->label.p, h->mat.p,
+                             d_dir.p + (p * 3 + 2) * LM, (const double*)nullptr, (const double*)nullptr, c, dc_of(step, p),
+                             urhs.p);
+        }
         GL_CHECK_LAUNCH();
         status = solve_elastic(h, wk, urhs.p, du.p, nullptr, 1e-12, &its);
         if (status != GLIMS_OK) break;
@@ -1578,6 +1792,10 @@ int hessian_t(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, const
             GL_CHECK_LAUNCH();
           }
         }
+        if (el_dirs) {   // - dK mu_k
+          hipLaunchKernelGGL(k_sub, dim3(grid_of(n * D)), dim3(256), 0, h->st, n * D, dKmu.p + (size_t)p * nd, dmurhs.p);
+          GL_CHECK_LAUNCH();
+        }
         status = solve_elastic(h, wk, dmurhs.p, dmu.p, nullptr, 1e-12, &its);
         if (status != GLIMS_OK) break;
         extra_mech += 2;
@@ -1589,6 +1807,23 @@ int hessian_t(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, const
         gt_pass(d_dmat.p + (size_t)p * 5 * LM, c, wk.mu.p, nullptr);
         hipLaunchKernelGGL(k_gt_rows, dim3(grid_of(n)), dim3(256), 0, h->st, n, pt.cslice_ptr.p, pt.celem.p, hqcell.p, dgp);
         GL_CHECK_LAUNCH();
+        if (el_dirs) {
+          // the E / nu part of dG^T mu: gamma_t (2 dm_t + d dl_t) |T|/(d+1) div mu per cell, then the rows
+          gt_pass(d_dmat2.p + (size_t)p * 5 * LM, c, wk.mu.p, nullptr);
+          hipLaunchKernelGGL(k_gt_rows, dim3(grid_of(n)), dim3(256), 0, h->st, n, pt.cslice_ptr.p, pt.celem.p, hqcell.p, dgp);
+          GL_CHECK_LAUNCH();
+        }
+        if (el_sums) {
+          // A_t(dmu, u) + A_t(mu, du), B_t(dmu, u) + B_t(mu, du) of step k (u_k's ghosts: coupling_adjoint exchanged them)
+          for (int l0 = 0; l0 < L; l0 += GL_ADJ_LT) {
+            hipLaunchKernelGGL(k_hesens<D>, dim3(sens_blocks(h)), dim3(256), 0, h->st, h->n_cells, l0, a.cell_nodes.p,
+                               h->egeo.p, h->label.p, wk.uk.p, wk.mu.p, du.p, dmu.p, counted, hepart.p);
+            GL_CHECK_LAUNCH();
+            hipLaunchKernelGGL(k_sens_final, dim3(1), dim3(1024), 0, h->st, sens_blocks(h), l0, L, 2, 0, hepart.p,
+                               hesums.p + (size_t)p * LM * 2);
+            GL_CHECK_LAUNCH();
+          }
+        }
       }
       if (status != GLIMS_OK) break;
     }
@@ -1636,9 +1871,12 @@ int hessian_t(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, const
   }
   const size_t L3 = (size_t)L * 3;
   std::vector<double> sums(L3), hs((size_t)P * LM * 3);
+  std::vector<double> esums((size_t)L * 2, 0.0), hes((size_t)P * LM * 2, 0.0);   // (el: one GPU)
   if (!part) {
     GL_HIP(hipMemcpyAsync(sums.data(), wk.sums.p, L3 * sizeof(double), hipMemcpyDeviceToHost, h->st));
     GL_HIP(hipMemcpyAsync(hs.data(), hsums.p, hs.size() * sizeof(double), hipMemcpyDeviceToHost, h->st));
+    if (el) GL_HIP(hipMemcpyAsync(esums.data(), wk.esums.p, esums.size() * sizeof(double), hipMemcpyDeviceToHost, h->st));
+    if (el_sums) GL_HIP(hipMemcpyAsync(hes.data(), hesums.p, hes.size() * sizeof(double), hipMemcpyDeviceToHost, h->st));
     GL_HIP(hipStreamSynchronize(h->st));
   } else {
     // as gradient_t: every rank's W sums (the gradient's [L][3], then [P][L][3] of the directions) gathered through
@@ -1671,6 +1909,30 @@ int hessian_t(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, const
       if (hv_rho) hv_rho[(size_t)p * L + l] = -dt * q[1];
       if (hv_gamma) hv_gamma[(size_t)p * L + l] = q[2];
     }
+  if (el) {
+    // the E / nu rows next to the first-order combination, in label order (lame_derivs.h): the gradient's totals (A_t, B_t, C_t),
+    // the direction's sums (mode 1's sums carry kappa_t, as C_t does), and the extra term of the gamma row
+    write_elastic_labels(h, D, sums.data(), esums.data(), el->dE, el->dnu);
+    const double* mh = h->mat_host.data();
+    for (int p = 0; p < P; ++p)
+      for (int l = 0; l < L; ++l) {
+        const size_t o = (size_t)p * L + l;
+        const double dEl = el->dir_E ? el->dir_E[o] : 0.0, dnul = el->dir_nu ? el->dir_nu[o] : 0.0;
+        const LameDerivs d = lame_derivs(mh[5 * LM + l], mh[6 * LM + l]);
+        const ElasticSums tot = elastic_totals(h, D, l, sums.data(), esums.data());
+        const double den = 2.0 * mh[3 * LM + l] + D * mh[4 * LM + l];
+        const ElasticSums sd = {hes[((size_t)p * LM + l) * 2 + 0], hes[((size_t)p * LM + l) * 2 + 1],
+                                den != 0.0 ? hs[((size_t)p * LM + l) * 3 + 2] / den : 0.0};
+        const double gam = mh[2 * LM + l], dgam = dir_gamma ? dir_gamma[o] : 0.0;
+        if (el->hv_E) el->hv_E[o] = elastic_hessian_row(D, 0, d, gam, dgam, dEl, dnul, tot, sd);
+        if (el->hv_nu) el->hv_nu[o] = elastic_hessian_row(D, 1, d, gam, dgam, dEl, dnul, tot, sd);
+        if (el_dirs && hv_gamma) {
+          double dm, dl;
+          lame_direction(d, dEl, dnul, &dm, &dl);
+          hv_gamma[o] += (2.0 * dm + D * dl) * tot.C;
+        }
+      }
+  }
   *J_out = sw.J;
   if (stats) {
     stats[0] = (double)tlm_its;
@@ -1807,15 +2069,15 @@ namespace {
 int hessian_dispatch(glims_ctx* h, int n_terms, const glims_misfit* terms, int n_dir, const double* dir_D,
                      const double* dir_rho, const double* dir_gamma, const double* dir_c0, double* J, double* dD, double* drho,
                      double* dgamma, double* dc0, double* hv_D, double* hv_rho, double* hv_gamma, double* hv_c0, double* stats,
-                     bool mem_checked) {
+                     bool mem_checked, const ElasticSecond* el = nullptr) {
   return h->dim == 2 ? hessian_t<2>(h, n_terms, terms, n_dir, dir_D, dir_rho, dir_gamma, dir_c0, J, dD, drho, dgamma, dc0,
-                                    hv_D, hv_rho, hv_gamma, hv_c0, stats, mem_checked)
+                                    hv_D, hv_rho, hv_gamma, hv_c0, stats, mem_checked, el)
                      : hessian_t<3>(h, n_terms, terms, n_dir, dir_D, dir_rho, dir_gamma, dir_c0, J, dD, drho, dgamma, dc0,
-                                    hv_D, hv_rho, hv_gamma, hv_c0, stats, mem_checked);
+                                    hv_D, hv_rho, hv_gamma, hv_c0, stats, mem_checked, el);
 }
-void check_n_dir(int n_dir) {
-  GL_REQUIRE(n_dir >= 1 && n_dir <= GL_HESS_MAXDIR, "glims_adjoint_hessian: n_dir = " + std::to_string(n_dir) +
-                                                        ", 1.." + std::to_string(GL_HESS_MAXDIR) + " directions per call");
+void check_n_dir(int n_dir, const std::string& who = "glims_adjoint_hessian") {
+  GL_REQUIRE(n_dir >= 1 && n_dir <= GL_HESS_MAXDIR, who + ": n_dir = " + std::to_string(n_dir) + ", 1.." +
+                                                        std::to_string(GL_HESS_MAXDIR) + " directions per call");
 }
 }  // namespace
 
@@ -1832,6 +2094,26 @@ int gl_adjoint_hessian(glims_ctx* h, int n_terms, const glims_misfit* terms, int
   check_n_dir(n_dir);
   return hessian_dispatch(h, n_terms, terms, n_dir, dir_D, dir_rho, dir_gamma, dir_c0, J, dD, drho, dgamma, dc0, hv_D, hv_rho,
                           hv_gamma, hv_c0, stats, false);
+}
+
+int gl_adjoint_hessian_full(glims_ctx* h, int n_terms, const glims_misfit* terms, int n_dir, const double* dir_D,
+                            const double* dir_rho, const double* dir_gamma, const double* dir_c0, const double* dir_E,
+                            const double* dir_nu, double* J, double* dD, double* drho, double* dgamma, double* dc0, double* dE,
+                            double* dnu, double* hv_D, double* hv_rho, double* hv_gamma, double* hv_c0, double* hv_E,
+                            double* hv_nu, double* stats) {
+  const std::string who = "glims_adjoint_hessian_full";
+  // (every rank of a partitioned handle refuses alike, before any collective)
+  GL_REQUIRE(h->world <= 1, who + ": not available on partitioned handles (world > 1): E / nu are first order there");
+  GL_REQUIRE(h->dimg_terms.empty(), who + ": second order through the location of the stored deformed image terms is not "
+                                          "built (a Hessian without them would be wrong): clear them with "
+                                          "glims_adjoint_deformed_image_terms(h, 0, NULL) first");
+  check_gradient_call(h, n_terms, terms, J, who);
+  check_n_dir(n_dir, who);
+  GL_REQUIRE(h->have_mech || !(dir_E || dir_nu || hv_E || hv_nu),
+             who + ": dir_E / dir_nu / hv_E / hv_nu need glims_setup(with_mechanics=1)");
+  const ElasticSecond el = {dir_E, dir_nu, dE, dnu, hv_E, hv_nu};
+  return hessian_dispatch(h, n_terms, terms, n_dir, dir_D, dir_rho, dir_gamma, dir_c0, J, dD, drho, dgamma, dc0, hv_D, hv_rho,
+                          hv_gamma, hv_c0, stats, false, &el);
 }
 
 int gl_adjoint_hessian_spmd(glims_ctx* h, int n_terms, const glims_misfit* terms, int n_dir, const double* dir_D,

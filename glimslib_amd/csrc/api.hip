@@ -902,6 +902,18 @@ int glims_adjoint_hessian_spmd(glims_ctx* h, int n_terms, const glims_misfit* te
   });
 }
 
+int glims_adjoint_hessian_full(glims_ctx* h, int n_terms, const glims_misfit* terms, int n_dir, const double* dir_D,
+                               const double* dir_rho, const double* dir_gamma, const double* dir_c0, const double* dir_E,
+                               const double* dir_nu, double* J, double* dJ_dD, double* dJ_drho, double* dJ_dgamma,
+                               double* dJ_dc0, double* dJ_dE, double* dJ_dnu, double* hv_D, double* hv_rho, double* hv_gamma,
+                               double* hv_c0, double* hv_E, double* hv_nu, double* stats) {
+  return guarded(h, [&]() {
+    return gl_adjoint_hessian_full(h, n_terms, terms, n_dir, dir_D, dir_rho, dir_gamma, dir_c0, dir_E, dir_nu, J, dJ_dD,
+                                   dJ_drho, dJ_dgamma, dJ_dc0, dJ_dE, dJ_dnu, hv_D, hv_rho, hv_gamma, hv_c0, hv_E, hv_nu,
+                                   stats);
+  });
+}
+
 int glims_adjoint_stats(const glims_ctx* h, int64_t out[6], double* ms) {
   if (!h || !out) return GLIMS_E_USAGE;
   const AdjointState& a = h->adj;

@@ -824,6 +824,12 @@ int gl_adjoint_hessian_spmd(glims_ctx* h, int n_terms, const glims_misfit* terms
                             const double* dir_rho, const double* dir_gamma, const double* dir_c0, double* J, double* dD,
                             double* drho, double* dgamma, double* dc0, double* hv_D, double* hv_rho, double* hv_gamma,
                             double* hv_c0, double* stats);
+// glims_adjoint_hessian_full: directions and products in E / nu too (one GPU)
+int gl_adjoint_hessian_full(glims_ctx* h, int n_terms, const glims_misfit* terms, int n_dir, const double* dir_D,
+                            const double* dir_rho, const double* dir_gamma, const double* dir_c0, const double* dir_E,
+                            const double* dir_nu, double* J, double* dD, double* drho, double* dgamma, double* dc0, double* dE,
+                            double* dnu, double* hv_D, double* hv_rho, double* hv_gamma, double* hv_c0, double* hv_E,
+                            double* hv_nu, double* stats);
 // AdjointState::cell_nodes ([n_cells][nv], internal cell order, the caller's vertex order), built on first use: the gradients
 // and the samplers share ONE builder
 const int32_t* gl_ensure_cell_nodes(glims_ctx* h);

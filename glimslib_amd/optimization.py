@@ -50,6 +50,10 @@ class ReducedFunctional:
     ``names=('E_WM', 'coupling')`` makes m = (E_WM, coupling).  On a TumorGrowth simulation ``names`` picks among
     ('diffusion', 'proliferation', 'coupling'), e.g. ``names=('coupling', 'diffusion')`` for a fit to a deformed image.
 
+    ``elastic_hessian=True`` (one GPU) lets ``hessian`` / ``hessian_matrix`` -- and so ``minimize(method='trust-constr')`` --
+    cover E_* / nu_* controls through ``sim.adjoint_hessian(..., elastic=True)``, the exact second-order elastic adjoint; by
+    default such controls are first order only and the Hessian raises.
+
     A term list with a deformed image term (``sim.image_term(..., deformed=True)``) is first order only: ``hessian`` and
     ``hessian_matrix`` raise NotImplementedError.
 
@@ -58,8 +62,9 @@ class ReducedFunctional:
     backward run.
     """
 
-    def __init__(self, sim, n_params, terms_builder, run_kwargs=None, names=None):
+    def __init__(self, sim, n_params, terms_builder, run_kwargs=None, names=None, elastic_hessian=False):
         self.sim = sim
+        self.elastic_hessian = bool(elastic_hessian)
         self.n_params = int(n_params)
         self.brain = hasattr(sim.params, "D_WM")
         if names is None:
@@ -118,7 +123,7 @@ class ReducedFunctional:
 
     def _model_directions(self):
         """The n_params directions P e_j in the simulation's adjoint_hessian keys."""
-        if any(n.startswith(("E_", "nu_")) for n in self.names):
+        if not self.elastic_hessian and any(n.startswith(("E_", "nu_")) for n in self.names):
             raise ValueError("ReducedFunctional.hessian: E / nu controls %s are first order only (the Hessian covers D, rho "
                              "and the coupling)" % [n for n in self.names if n.startswith(("E_", "nu_"))])
         key = (lambda n: n) if self.brain else {"diffusion": "diffusion", "proliferation": "proliferation",
@@ -136,7 +141,10 @@ class ReducedFunctional:
             if any(t.get("deformed") for t in terms):
                 raise NotImplementedError("ReducedFunctional.hessian: second order through the location of a deformed image "
                                           "term is not built; use a first-order method (L-BFGS-B)")
-            _, hv = self.sim.adjoint_hessian(terms, dirs)
+            if self.elastic_hessian:
+                _, hv = self.sim.adjoint_hessian(terms, dirs, elastic=True)
+            else:
+                _, hv = self.sim.adjoint_hessian(terms, dirs)
             H = np.array([[float(np.sum(h[name])) for name in self.names] for h in hv]).T   # column j = H P e_j
             self._H = self.P.T @ H
             self.hessian_calls += 1

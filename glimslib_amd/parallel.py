@@ -374,6 +374,12 @@ class DistributedHandle:
             out[..., gid] = a
         return out
 
+    def adjoint_hessian_full(self, terms, directions, n_labels=None):
+        """Second order in E / nu (Handle.adjoint_hessian_full, glims_adjoint_hessian_full) runs on one GPU only: raised
+        here, before any collective."""
+        raise NotImplementedError("adjoint_hessian_full (second order in E / nu, elastic=True) is not available on "
+                                  "partitioned runs")
+
     def adjoint_hessian(self, terms, directions, n_labels=None):
         """Handle.adjoint_hessian on the partitioned run (glims_adjoint_hessian_spmd, collective: every rank calls it with
         the same terms and directions).  Targets and 'c0' directions in GLOBAL node order, localised here; J and every

@@ -554,8 +554,9 @@ class TumorGrowth(FenicsSimulation):
         J, dD, drho, dgamma, dc0, dE, dnu = self._adjoint_raw(terms, elastic=True)
         return {'J': J, 'diffusion': dD, 'proliferation': drho, 'coupling': dgamma, 'E': dE, 'poisson': dnu, 'c0': dc0}
 
-    def _adjoint_hessian_raw(self, terms, directions):
-        """Handle.adjoint_hessian of the recorded run; directions keyed 'D' / 'rho' / 'gamma' / 'c0'."""
+    def _adjoint_hessian_raw(self, terms, directions, elastic=False):
+        """Handle.adjoint_hessian of the recorded run; directions keyed 'D' / 'rho' / 'gamma' / 'c0' (elastic=True: also
+        'E' / 'nu')."""
         h = self._backend
         if h is None or not hasattr(h, 'adjoint_hessian'):
             raise RuntimeError("adjoint_hessian needs a run(record_adjoint=True) first")
@@ -567,24 +568,34 @@ class TumorGrowth(FenicsSimulation):
         if any(t.get('deformed') for t in terms):
             raise NotImplementedError("adjoint_hessian: second order through the location of a deformed image term "
                                       "(image_term(deformed=True)) is not built; use a first-order method")
+        if elastic:   # (a partitioned run's DistributedHandle raises NotImplementedError)
+            return h.adjoint_hessian_full(terms, directions)
         return h.adjoint_hessian(terms, directions)
 
-    def adjoint_hessian(self, terms, directions):
+    def adjoint_hessian(self, terms, directions, elastic=False):
         """
         Hessian-vector products of J for the recorded run (the counterpart of fenics.ReducedFunctional.hessian), with J and
         the gradient that come with them.  ``directions``: 1 .. 8 dicts keyed like adjoint_gradient's output --
         'diffusion', 'proliferation', 'coupling' (per-label arrays, or a scalar for every label) and 'c0' ([n_nodes]);
         missing keys are 0.  E and poisson are first order only.  Returns (g, hv): g = {'J', 'diffusion', 'proliferation',
         'coupling', 'c0'}, hv = one dict {'diffusion', 'proliferation', 'coupling', 'c0'} per direction.
+        elastic=True (one GPU): directions take 'E' and 'poisson' as well (the exact second-order elastic adjoint), and g
+        and every hv gain those two keys.
         """
         key = {'diffusion': 'D', 'proliferation': 'rho', 'coupling': 'gamma', 'c0': 'c0'}
+        if elastic:
+            key.update(E='E', poisson='nu')
         bad = [k for d in directions for k in d if k not in key]
         if bad:
             raise ValueError("adjoint_hessian: directions take %s, got %s" % (tuple(key), bad))
-        r = self._adjoint_hessian_raw(terms, [{key[k]: v for k, v in d.items()} for d in directions])
+        r = self._adjoint_hessian_raw(terms, [{key[k]: v for k, v in d.items()} for d in directions], elastic=elastic)
         g = {'J': r['J'], 'diffusion': r['D'], 'proliferation': r['rho'], 'coupling': r['gamma'], 'c0': r['c0']}
         hv = [{'diffusion': r['hv_D'][p], 'proliferation': r['hv_rho'][p], 'coupling': r['hv_gamma'][p],
                'c0': r['hv_c0'][p]} for p in range(len(directions))]
+        if elastic:
+            g.update(E=r['E'], poisson=r['nu'])
+            for p, h in enumerate(hv):
+                h.update(E=r['hv_E'][p], poisson=r['hv_nu'][p])
         return g, hv
 
     # -- parameter sweeps (the forward half of the reference's adjoint entry points) -------------------------------

@@ -89,12 +89,19 @@ class TumorGrowthBrain(TumorGrowth):
             g['nu_' + suffix] = pick(dnu, t)
         return g
 
-    def adjoint_hessian(self, terms, directions):
+    _ELASTIC_TISSUES = (('GM', 'GM'), ('WM', 'WM'), ('CSF', 'CSF'), ('VENT', 'Ventricles'))
+
+    def adjoint_hessian(self, terms, directions, elastic=False):
         """Hessian-vector products (see TumorGrowth.adjoint_hessian) with directions keyed by the scalar names D_WM, D_GM,
         rho_WM, rho_GM, coupling (one constant on every tissue) and c0; missing keys are 0.  Returns (g, hv) with g =
-        {'J', 'D_WM', 'D_GM', 'rho_WM', 'rho_GM', 'coupling', 'c0'} and one dict of the same keys (no 'J') per direction."""
+        {'J', 'D_WM', 'D_GM', 'rho_WM', 'rho_GM', 'coupling', 'c0'} and one dict of the same keys (no 'J') per direction.
+        elastic=True (one GPU): directions also take E_GM, E_WM, E_CSF, E_VENT, nu_GM, nu_WM, nu_CSF, nu_VENT, and g and
+        every hv gain those keys; without it such a key is a ValueError (E / nu are first order only by default)."""
         names = ('D_WM', 'D_GM', 'rho_WM', 'rho_GM', 'coupling', 'c0')
-        bad = [k for d in directions for k in d if k not in names]
+        enames = tuple(p + s for p in ('E_', 'nu_') for s, _ in self._ELASTIC_TISSUES) if elastic else ()
+        bad = [k for d in directions for k in d if k not in names + enames]
+        if bad and elastic:
+            raise ValueError("adjoint_hessian: directions take %s, got %s" % (names + enames, bad))
         if bad:
             raise ValueError("adjoint_hessian: directions take %s (E / nu are first order only), got %s" % (names, bad))
         L = self._backend.n_labels if self._backend is not None else 0
@@ -107,15 +114,31 @@ class TumorGrowthBrain(TumorGrowth):
                     dD[t] += float(d.get('D_' + sfx, 0.0))
                     drho[t] += float(d.get('rho_' + sfx, 0.0))
             dirs.append({'D': dD, 'rho': drho, 'gamma': np.full(L, float(d.get('coupling', 0.0))), 'c0': d.get('c0')})
-        r = self._adjoint_hessian_raw(terms, dirs)
+            if elastic:
+                dE, dnu = np.zeros(L), np.zeros(L)
+                for sfx, tissue in self._ELASTIC_TISSUES:
+                    t = self._tissue_id(tissue)
+                    if t is not None and t < L:
+                        dE[t] += float(d.get('E_' + sfx, 0.0))
+                        dnu[t] += float(d.get('nu_' + sfx, 0.0))
+                dirs[-1].update(E=dE, nu=dnu)
+        r = self._adjoint_hessian_raw(terms, dirs, elastic=elastic)
         pick = lambda a, t: float(a[t]) if t is not None and t < len(a) else 0.0
 
-        def named(D, rho, gamma, c0):
-            return {'D_WM': pick(D, wm), 'D_GM': pick(D, gm), 'rho_WM': pick(rho, wm), 'rho_GM': pick(rho, gm),
-                    'coupling': float(np.sum(gamma)), 'c0': c0}
+        def named(D, rho, gamma, c0, E=None, nu=None):
+            out = {'D_WM': pick(D, wm), 'D_GM': pick(D, gm), 'rho_WM': pick(rho, wm), 'rho_GM': pick(rho, gm),
+                   'coupling': float(np.sum(gamma)), 'c0': c0}
+            if elastic:
+                for sfx, tissue in self._ELASTIC_TISSUES:
+                    t = self._tissue_id(tissue)
+                    out['E_' + sfx] = pick(E, t)
+                    out['nu_' + sfx] = pick(nu, t)
+            return out
 
-        g = dict(named(r['D'], r['rho'], r['gamma'], r['c0']), J=r['J'])
-        hv = [named(r['hv_D'][p], r['hv_rho'][p], r['hv_gamma'][p], r['hv_c0'][p]) for p in range(len(directions))]
+        eg = (r['E'], r['nu']) if elastic else ()
+        g = dict(named(r['D'], r['rho'], r['gamma'], r['c0'], *eg), J=r['J'])
+        hv = [named(r['hv_D'][p], r['hv_rho'][p], r['hv_gamma'][p], r['hv_c0'][p],
+                    *((r['hv_E'][p], r['hv_nu'][p]) if elastic else ())) for p in range(len(directions))]
         return g, hv
 
     def run_for_adjoint(self, parameters, output_dir=config.output_dir_simulation_tmp):

@@ -604,7 +604,7 @@ int glims_adjoint_gradient_full(glims_ctx* h, int n_terms, const glims_misfit* t
  * multigrid (stiff steps) the V-cycle PCG runs column by column instead.  Column j of an n_dir-direction call has the bits
  * of a one-direction call in direction j.  Elastic
  * solves to 1e-12 ||rhs||, 2 per direction at each step a U_L2 term observes.  E and nu are first order only (no direction,
- * no product).  Device memory on top of the trajectory: 8 n_dir B per node and recorded state (the stored dc_n) plus
+ * no product; glims_adjoint_hessian_full below has both).  Device memory on top of the trajectory: 8 n_dir B per node and recorded state (the stored dc_n) plus
  * O(n_dir) vectors; a call that does not fit returns GLIMS_E_HIP before it allocates.  The forward state and glims_stats are
  * left as they were; glims_adjoint_stats does not count this call.  stats (may be NULL) [4]: tangent-linear PCG iterations,
  * second-order PCG iterations, extra elastic solves, wall ms.  Partitioned handles: GLIMS_E_USAGE on every rank (no
@@ -628,11 +628,41 @@ int glims_adjoint_hessian(glims_ctx* h, int n_terms, const glims_misfit* terms, 
  * bits of a one-direction call.  Before any other collective the ranks' verdicts -- arguments and trajectory, n_dir, the
  * NULL pattern, the stored image terms (count and steps), device memory -- go through one all-reduce: if any rank refuses,
  * every rank returns the same status (GLIMS_E_USAGE, or GLIMS_E_HIP for memory) and the handle is left as it was.  stats is
- * per rank (the iteration counts are the same on all ranks).  Single node; E and nu stay first order. */
+ * per rank (the iteration counts are the same on all ranks).  Single node; E and nu stay first order (second order in them:
+ * glims_adjoint_hessian_full, one GPU). */
 int glims_adjoint_hessian_spmd(glims_ctx* h, int n_terms, const glims_misfit* terms, int n_dir, const double* dir_D,
                                const double* dir_rho, const double* dir_gamma, const double* dir_c0, double* J,
                                double* dJ_dD, double* dJ_drho, double* dJ_dgamma, double* dJ_dc0, double* hv_D,
                                double* hv_rho, double* hv_gamma, double* hv_c0, double* stats);
+
+/* glims_adjoint_hessian with directions and products in the per-label Young's modulus and Poisson ratio too (appended under
+ * ABI 6): dm = (dD, drho, dgamma, dE, dnu [n_labels], dc0 [n_nodes]).  Layouts and NULL rules of glims_adjoint_hessian: dir_E /
+ * dir_nu / hv_E / hv_nu are [n_dir][n_labels], a NULL direction array is 0, any output except J may be NULL; J and the six
+ * gradient arrays are bitwise those of glims_adjoint_gradient_full, and with dir_E = dir_nu = NULL hv_D / hv_rho / hv_gamma /
+ * hv_c0 are bitwise those of glims_adjoint_hessian.  The concentration does not depend on E or nu; K_el and G are linear in
+ * each cell's Lame pair (m, l), so with (dm_t, dl_t) = dE_t d_E(m, l)_t + dnu_t d_nu(m, l)_t, kappa(m, l) = 2 m + d l,
+ * dK = sum_t the stiffness with the pair (dm_t, dl_t), dG = sum_t (dgamma_t kappa_t + gamma_t kappa(dm_t, dl_t)) G_t per unit
+ * coefficient, at every step k that a U_L2 term observes (u_k with its Dirichlet values, du_k = dmu_k = 0 on the constrained
+ * dofs):
+ *   K du_k = G dc_k + dG c_k - dK u_k,     K dmu_k = w M_vec du_k - dK mu_k,     dg_k += G^T dmu_k + dG^T mu_k,
+ *   hv_p_t = gamma_t kappa(m_p, l_p) [C_t(dmu, c) + C_t(mu, dc)] - 2 m_p [A_t(dmu, u) + A_t(mu, du)]
+ *            - l_p [B_t(dmu, u) + B_t(mu, du)] + [dgamma_t kappa(m_p, l_p) + gamma_t kappa(dm_p, dl_p)] C_t(mu, c)
+ *            - 2 dm_p A_t(mu, u) - dl_p B_t(mu, u)          summed over k, for p = E, nu,
+ *   (m_p, l_p) = d_p(m, l)_t, (dm_p, dl_p) = dE_t d_pE(m, l)_t + dnu_t d_pnu(m, l)_t  (A_t, B_t, C_t as in
+ *   glims_adjoint_gradient_full; the derivatives: csrc/lame_derivs.h),
+ *   hv_gamma_t gains kappa(dm_t, dl_t) sum_k C_t(mu_k, c_k); hv_D, hv_rho and hv_c0 change through dmu_k and dG^T mu_k alone.
+ * No elastic solve is added (stats[2] as glims_adjoint_hessian): a direction in E / nu costs two row-owned passes of dK per
+ * observed step (all columns at once), one more cell and row pass of dG^T mu and the E / nu sum pass per direction.  A term
+ * list without GLIMS_MISFIT_U_L2 gives hv_E = hv_nu = 0 exactly.  Column j of an n_dir-direction call has the bits of a
+ * one-direction call; the same trajectory gives the same bits on every call.  Device memory: 2 n_dir more vectors of
+ * dim x n_nodes when dir_E or dir_nu is given, inside the check that glims_adjoint_hessian makes before it allocates.
+ * GLIMS_E_USAGE, the handle left as it was: a partitioned handle (on every rank, before any collective), stored deformed image
+ * terms, n_dir outside 1..8, a non-NULL dir_E / dir_nu / hv_E / hv_nu on a handle set up without mechanics. */
+int glims_adjoint_hessian_full(glims_ctx* h, int n_terms, const glims_misfit* terms, int n_dir, const double* dir_D,
+                               const double* dir_rho, const double* dir_gamma, const double* dir_c0, const double* dir_E,
+                               const double* dir_nu, double* J, double* dJ_dD, double* dJ_drho, double* dJ_dgamma,
+                               double* dJ_dc0, double* dJ_dE, double* dJ_dnu, double* hv_D, double* hv_rho, double* hv_gamma,
+                               double* hv_c0, double* hv_E, double* hv_nu, double* stats);
 
 /* Counters of the adjoint (not in glims_stats, whose layout is fixed): out[0] gradient calls, [1] backward steps,
  * [2] RD adjoint PCG iterations, [3] elastic solves, [4] their PCG iterations, [5] recorded states held now;
