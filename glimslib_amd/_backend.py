@@ -33,6 +33,7 @@ FLAG_NO_FUSED_MASS = 2048
 FLAG_SLOT_WORDS32 = 4096
 FLAG_RECORD_WORDS_FULL = 8192
 FLAG_NO_VALUE_CODES = 16384
+FLAG_STORE_LINEAR_SLICES = 32768
 PRECOND_BLOCK_JACOBI, PRECOND_MULTIGRID = 0, 1
 RD_PRECOND_AUTO, RD_PRECOND_JACOBI, RD_PRECOND_MULTIGRID = 0, 1, 2
 RD_LINEAR_AUTO, RD_LINEAR_PCG, RD_LINEAR_CHEBYSHEV = 0, 1, 2
@@ -103,7 +104,8 @@ class Stats(C.Structure):
                 ("rd_slot16_sweeps", C.c_int64), ("rd_rec_compact_slices", C.c_int64),
                 ("rd_rec_full_slices", C.c_int64), ("rd_rec32_sweeps", C.c_int64),
                 ("rd_scode_slices", C.c_int64), ("rd_scode_uncoded_slices", C.c_int64),
-                ("rd_lin_slices", C.c_int64), ("cheb_coded_passes", C.c_int64)]
+                ("rd_lin_slices", C.c_int64), ("cheb_coded_passes", C.c_int64),
+                ("rd_lin_kept_slices", C.c_int64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}

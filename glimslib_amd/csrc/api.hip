@@ -614,7 +614,7 @@ int glims_get_stats(const glims_ctx* h, glims_stats* st) {
   if (!h || !st) return GLIMS_E_USAGE;
   *st = h->stats;
   int64_t ring = 0;   // (the flags as they are now: a snapshot, not a counter; and the coded passes still in the ring)
-  gl_value_code_counts(h, &st->rd_lin_slices, &ring);
+  gl_value_code_counts(h, &st->rd_lin_slices, &st->rd_lin_kept_slices, &ring);
   st->cheb_coded_passes += ring;
   return GLIMS_OK;
 }

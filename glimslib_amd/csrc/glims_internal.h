@@ -35,6 +35,8 @@
 #define GL_STREAM_CACHED_LIMIT (1024ll << 20)
 // (chunks of 128-512 blocks change the in-step kernel times by <= 2 %: profiles/r04_ab_xcd_chunk.txt)
 #define GL_XCD_CHUNK 64
+// ... and a bit above it in the straight-line sweeps' `remap` argument: store every slice of vA (GLIMS_FLAG_STORE_LINEAR_SLICES)
+#define GL_SWEEP_STORE_ALL (1 << 16)
 
 struct glims_error : std::runtime_error {
   int code;
@@ -636,9 +638,11 @@ struct glims_ctx {
 
   // scalar operator planes (SELL-64 layout) and block planes
   dvec<double> vM, vS, vA, vKel, vG;
-  // per slice: 1 = the slice of vA holds the bits of vS (A = S + 2 dt N(c) with fl(..) = S there), written by EVERY kernel that
-  // writes the slice of vA (the straight-line sweeps test, every other writer stores 0): the flag cannot outlive the values it
-  // describes.  Empty = the handle streams no value codes (gl_value_codes_wanted) and no kernel writes or reads it.
+  // per slice: non-zero = the MEMORY of vA's slice holds the bits of vS (A = S + 2 dt N(c) with fl(..) = S there): 1 = stored by
+  // the latest sweep, 2 = found linear again by it and not stored (rd_assemble_s_slice).  Written by EVERY kernel that writes
+  // the slice of vA (the straight-line sweeps test, every other writer stores 0; a copy of vS into vA is followed by cleared
+  // flags, build_value_codes): the flag cannot outlive the values it describes.  Empty = the handle streams no value codes
+  // (gl_value_codes_wanted), no kernel writes or reads it and every sweep stores every slice.
   dvec<uint8_t> lin;                       // [n_slices] flags, then [GL_VC_HIT_RING] one byte per launch of the dot-free pass
                                            // that was given the coded stream: set by the launch if a wave read a coded slice
   int vc_launches = 0;                     // ... bytes of the ring handed out since it was last emptied
@@ -758,7 +762,7 @@ struct GlMassSweep {
 };
 bool gl_value_codes_wanted(const glims_ctx* h);   // the dot-free passes of this handle may stream coded slices (value_codes.h)
 constexpr int GL_VC_HIT_RING = 1024;
-void gl_value_code_counts(const glims_ctx* h, int64_t* lin_slices, int64_t* ring_passes);   // (synchronises the stream)
+void gl_value_code_counts(const glims_ctx* h, int64_t* lin_slices, int64_t* kept_slices, int64_t* ring_passes);   // (synchronises the stream)
 void gl_harvest_coded_passes(glims_ctx* h);
 bool gl_rd_fusable(glims_ctx* h);   // every slice class has a straight-line sweep kernel, fp64 Jacobian
 bool gl_rd_mass_in_sweep(glims_ctx* h);   // the stepping path forms M c in the sweep (single rank, gl_rd_fusable, flag not set)

@@ -741,7 +741,9 @@ __device__ __forceinline__ void rd_assemble_s_slice(
   double* cn = lds + (size_t)ldscap * GL_WAVE;   // [ldscap][64]
   const int lane = threadIdx.x;
   const uint32_t lane_u = threadIdx.x;
-  const SliceDesc d = desc[remap > 1 ? xcd_chunk_remap(blockIdx.x, gridDim.x, 4 * remap) : blockIdx.x];
+  // (`remap`: the XCD chunk in its low bits; GL_SWEEP_STORE_ALL: every slice of vA is stored, GLIMS_FLAG_STORE_LINEAR_SLICES)
+  const int chunk = remap & (GL_SWEEP_STORE_ALL - 1);
+  const SliceDesc d = desc[chunk > 1 ? xcd_chunk_remap(blockIdx.x, gridDim.x, 4 * chunk) : blockIdx.x];
   const int s = d.s, len = d.len, clen = d.clen;
   const int64_t row = (int64_t)s * GL_WAVE + lane;
   // ---- round trip 2 (program order = issue order; the column codes last, the next round trip waits for them)
@@ -847,9 +849,19 @@ __device__ __forceinline__ void rd_assemble_s_slice(
   int rl = 0;
   if constexpr (FG == 1) rl = (int)fg.rlen[row];
   double r = 0.0, dg = 1.0, au = 0.0, un = 0.0;
-  // `lin` (per slice, may be null): 1 = every entry this wave writes to vA has the bits of its entry of S -- the reaction term
-  // vanished in rounding, fl(S + 2 dt N(c)) = S -- so that a pass over the slice may read the coded S instead (value_codes.h).
-  // Invariant: whoever writes a slice of vA writes its flag (the fp32 instances do not write vA at all: they store 0).
+  // `lin` (per slice, may be null): non-zero = the MEMORY of vA's slice holds the bits of S's -- the reaction term vanished in
+  // rounding, fl(S + 2 dt N(c)) = S, in the sweep that last stored the slice and in every sweep since -- so that a pass over
+  // the slice may read the coded S instead (value_codes.h), and a sweep that finds the slice linear again need not store it.
+  // 1: linear, stored by this sweep; 2: linear, store left out; 0: anything else.  Invariant: whoever writes a slice of vA
+  // writes its flag (the fp32 instances do not write vA at all: they store 0), and nobody sets a non-zero flag over values
+  // other than S's.
+  // Where a store can be left out (fp64, flags kept, no GLIMS_FLAG_STORE_LINEAR_SLICES) the row's values of A stay in S8's
+  // registers through the loop and are stored after it -- unless the slice's flag was non-zero and every entry has S's bits
+  // once more: those len stores would change nothing in memory.  Every other launch stores inside the loop, entry by entry,
+  // as before (the stores drain under the loop's LDS reads: after it they cost 0.03 ms per step at C4).
+  const bool can_keep = std::is_same<AT, double>::value && lin != nullptr && (remap & GL_SWEEP_STORE_ALL) == 0;   // wave-uniform
+  int len_now = can_keep ? 0 : len;   // entries stored inside the loop
+  asm volatile("" : "+s"(len_now));
   bool same = std::is_same<AT, double>::value;
 #pragma unroll
   for (int k = 0; k < CAP; ++k) {
@@ -868,10 +880,12 @@ __device__ __forceinline__ void rd_assemble_s_slice(
     }
     if (k < len) {
       const double a_k = (k == dk) ? acc_d : acc[k * GL_WAVE + lane];
-      const double Av = S8[k] + two_dt * a_k;
-      GL_STREAM(vA, d.base, k) = (AT)Av;
-      same = same && gl_vc_bits(Av) == gl_vc_bits(S8[k]);
-      r += 0.5 * (Av + S8[k]) * cn[k * GL_WAVE + lane];
+      const double Sv = S8[k];
+      const double Av = Sv + two_dt * a_k;
+      same = same && gl_vc_bits(Av) == gl_vc_bits(Sv);
+      r += 0.5 * (Av + Sv) * cn[k * GL_WAVE + lane];
+      if (k < len_now) GL_STREAM(vA, d.base, k) = (AT)Av;
+      S8[k] = Av;   // (or stored after the loop, or not at all)
       if (k == dk) dg = Av;
       if constexpr (FG == 1) {
         au = __builtin_fma(k < rl ? Av : 0.0, k < rl ? ug[k % GB] : 0.0, au);
@@ -879,6 +893,24 @@ __device__ __forceinline__ void rd_assemble_s_slice(
       }
     }
   }
+  // The slice's present flag: requested only where it matters (a slice found linear), after the loop, and looked at after the
+  // row's results and the wave's sums below, which cover its latency.  (Held from round trip 2 it is one more register across
+  // the records and costs five instances a wave per SIMD; requested half-way through phase 3 it still costs two.)
+  const bool all_same = __all(same ? 1 : 0) != 0;
+  const bool may_keep = can_keep && all_same;   // wave-uniform
+  uint32_t old_flag = 0;
+  if (may_keep) old_flag = lin[s];
+  auto store_row = [&]() {
+    // (the length as a fresh scalar, compared again here: with `len` itself the compiler keeps the loop's CAP conditions alive
+    //  as lane masks for these stores -- 2 x CAP scalar registers, which spill into a vector register and cost the CAP = 32
+    //  instances with 32-bit slot words a wave per SIMD)
+    int slen = len;
+    asm volatile("" : "+s"(slen));
+#pragma unroll
+    for (int k = 0; k < CAP; ++k)
+      if (k < slen) GL_STREAM(vA, d.base, k) = (AT)S8[k];
+  };
+  if (can_keep && !may_keep) store_row();   // (not linear, nothing to wait for: at once)
   double rr = 0.0, rr2 = 0.0, tt = 0.0;
   asm volatile("" : "+v"(fxv));
   if (own) {
@@ -916,9 +948,11 @@ __device__ __forceinline__ void rd_assemble_s_slice(
     partials[(size_t)s * 2 + 0] = rr;
     partials[(size_t)s * 2 + 1] = rr2;
   }
+  asm volatile("" : "+v"(old_flag));   // (looked at HERE, as fxv is: not where it was requested)
+  const bool keep = may_keep && __builtin_amdgcn_readfirstlane(old_flag) != 0;   // wave-uniform
+  if (may_keep && !keep) store_row();   // (a slice that is linear for the first time)
   if (lin) {   // (wave-uniform)
-    const bool all_same = __all(same ? 1 : 0) != 0;
-    if (lane == 0) lin[s] = all_same ? 1 : 0;
+    if (lane == 0) lin[s] = all_same ? (keep ? 2 : 1) : 0;
   }
   if constexpr (FG == 1) {
     tt = wave_sum(tt);
@@ -1957,7 +1991,7 @@ bool gl_value_codes_wanted(const glims_ctx* h) {
 static void build_value_codes(glims_ctx* h) {
   DevPattern& p = h->pat;
   gl_harvest_coded_passes(h);   // (the ring goes or is cleared below: what it holds is added to the statistics first)
-  h->stats.rd_scode_slices = h->stats.rd_scode_uncoded_slices = h->stats.rd_lin_slices = 0;
+  h->stats.rd_scode_slices = h->stats.rd_scode_uncoded_slices = h->stats.rd_lin_slices = h->stats.rd_lin_kept_slices = 0;
   if (!gl_value_codes_wanted(h) || p.n_slices <= 0) {
     p.scode.release();
     p.sdict.release();
@@ -1988,20 +2022,22 @@ static void build_value_codes(glims_ctx* h) {
   }
 }
 
-// The flags and the ring as they are now: (slices flagged exactly linear, coded passes not yet added to the statistics).
-void gl_value_code_counts(const glims_ctx* h, int64_t* lin_slices, int64_t* ring_passes) {
-  *lin_slices = *ring_passes = 0;
+// The flags and the ring as they are now: (slices flagged exactly linear, those of them whose store the latest sweep left out,
+// coded passes not yet added to the statistics).
+void gl_value_code_counts(const glims_ctx* h, int64_t* lin_slices, int64_t* kept_slices, int64_t* ring_passes) {
+  *lin_slices = *kept_slices = *ring_passes = 0;
   if (!h->lin.p || h->lin.n <= GL_VC_HIT_RING) return;
   std::vector<uint8_t> f(h->lin.n);
   if (hipStreamSynchronize(h->st) != hipSuccess) return;
   if (hipMemcpy(f.data(), h->lin.p, f.size(), hipMemcpyDeviceToHost) != hipSuccess) return;
   const size_t ns = f.size() - GL_VC_HIT_RING;
   for (size_t i = 0; i < f.size(); ++i) (i < ns ? *lin_slices : *ring_passes) += f[i] != 0;
+  for (size_t i = 0; i < ns; ++i) *kept_slices += f[i] == 2;
 }
 // ... the ring's passes into glims_stats.cheb_coded_passes, and an empty ring
 void gl_harvest_coded_passes(glims_ctx* h) {
-  int64_t lin = 0, ring = 0;
-  gl_value_code_counts(h, &lin, &ring);
+  int64_t lin = 0, kept = 0, ring = 0;
+  gl_value_code_counts(h, &lin, &kept, &ring);
   h->stats.cheb_coded_passes += ring;
   h->vc_launches = 0;
   if (h->lin.p && h->lin.n > GL_VC_HIT_RING)
@@ -2200,11 +2236,13 @@ static bool launch_sweep(glims_ctx* h, const GlSweepKey& k, const ClassLaunch& c
                                a.fixed, 2.0 * h->opt.dt, a.partials, class_cap, GL_XCD_CHUNK, lin);
           } else {
             const uint32_t* slots = ST == GL_ST_U16 ? p.cs16.p : ST == GL_ST_REC32 ? p.cr32.p : p.cs2.p;
+            // (GLIMS_FLAG_STORE_LINEAR_SLICES travels as a bit of `remap`: data, not an instance)
+            const int remap = GL_XCD_CHUNK | ((h->opt.flags & GLIMS_FLAG_STORE_LINEAR_SLICES) ? GL_SWEEP_STORE_ALL : 0);
             auto straight = [&](auto kern, auto... tail) {   // (the two families differ in their last arguments)
               set_lds(kern, lds);
               hipLaunchKernelGGL(kern, dim3(cl.grid), dim3(GL_WAVE), lds, h->st, cl.desc, h->n_own, p.cols.p, p.cols16.p,
                                  p.win_base.p, slots, p.cw.p, p.diag_k.p, h->vS.p, vA, a.c, a.b, a.b2, a.r_out, a.r2_out,
-                                 h->dinv.p, a.fixed, 2.0 * h->opt.dt, a.partials, class_cap, GL_XCD_CHUNK, tail...);
+                                 h->dinv.p, a.fixed, 2.0 * h->opt.dt, a.partials, class_cap, remap, tail...);
             };
             if constexpr (FG != 0) straight(k_rd_assemble_sg<NV, CAP, RB, CIDX, FG, MB, st_t>, a.fg, a.ma, lin);
             else straight(k_rd_assemble_s<NV, CAP, RB, CIDX, at_t, MB, st_t>, a.ma, lin);

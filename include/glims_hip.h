@@ -251,6 +251,16 @@ typedef struct glims_options {
                                            Jacobian with 16-bit column codes on one rank only; partitioned handles, the PCG,
                                            the multigrid and the adjoint read the stored values as before.
                                            Set: no words are built and every pass reads the values (A/B in one build) */
+#define GLIMS_FLAG_STORE_LINEAR_SLICES 32768 /* OFF by default.  Default: a straight-line assembly sweep that finds a slice of 64
+                                           rows exactly linear (every value of A = S + 2 dt N(c) it has formed has the bits of
+                                           its entry of S) where the previous sweep found and left it so does not store the
+                                           slice's values: the memory holds those very bits already (8 B per entry and sweep
+                                           less; glims_stats.rd_lin_kept_slices).  Every incidence is still streamed, every row
+                                           assembled and tested, and every residual, diagonal and flag written; the stored
+                                           Jacobian keeps its bits for every reader.  On the handles that keep the per-slice
+                                           flags only (those of GLIMS_FLAG_NO_VALUE_CODES's default); every other handle
+                                           stores every slice as before.
+                                           Set: every sweep stores every slice (A/B in one build) */
 
 typedef struct glims_stats {
   int64_t steps;            /* implicit time steps taken */
@@ -367,6 +377,9 @@ typedef struct glims_stats {
                                read from the device by glims_get_stats; not a running count */
   int64_t cheb_coded_passes; /* launches of the dot-free pass in which at least one slice -- exactly linear and coded -- was read
                                from the 4-byte words (counted on the device, collected by glims_get_stats) */
+  int64_t rd_lin_kept_slices; /* those of rd_lin_slices whose values the latest assembly sweep did not store, because the memory
+                               held S's bits already (read from the device like rd_lin_slices; not a running count; 0 under
+                               GLIMS_FLAG_STORE_LINEAR_SLICES) */
 } glims_stats;
 
 /* ---- lifetime -------------------------------------------------------------------------------------- */
@@ -438,7 +451,7 @@ int glims_solve_mechanics(glims_ctx* h);
 
 /* A copy of the counters.  On a handle that streams value codes (GLIMS_FLAG_NO_VALUE_CODES not set, fp64 Jacobian, 16-bit column
  * codes, one rank) the call also waits for the handle's stream and reads one byte per slice plus 1 KB from the device (about
- * 160 KB at 10 M rows): rd_lin_slices is the device's flags as they are now, and cheb_coded_passes includes the launches the
+ * 160 KB at 10 M rows): rd_lin_slices and rd_lin_kept_slices are the device's flags as they are now, and cheb_coded_passes includes the launches the
  * device has counted since they were last collected.  Every other handle gets the plain copy, without synchronisation.  (The
  * solver itself collects those launches once in 1024 coded passes, with one synchronisation of its stream.) */
 int glims_get_stats(const glims_ctx* h, glims_stats* st);
