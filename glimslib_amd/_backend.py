@@ -144,6 +144,13 @@ class Observable(C.Structure):
     _fields_ = [("kind", C.c_int), ("level", C.c_double), ("smooth", C.c_double)]
 
 
+class ObservableMisfit(C.Structure):
+    """glims_observable_misfit: a volume misfit term J = 1/2 weight (V - target)^2 of a glims_observe measure (labels: a uint8
+    mask [n_labels] of the counted labels, or NULL for the whole domain)."""
+    _fields_ = [("step", C.c_int64), ("kind", C.c_int), ("level", C.c_double), ("smooth", C.c_double),
+                ("weight", C.c_double), ("target", C.c_double), ("labels", C.POINTER(C.c_uint8))]
+
+
 _dp = C.POINTER(C.c_double)
 _i32p = C.POINTER(C.c_int32)
 _i64p = C.POINTER(C.c_int64)
@@ -209,6 +216,8 @@ SIGNATURES = {
     "glims_adjoint_image_info": (C.c_int, [_h, C.c_int, _i64p]),
     "glims_adjoint_deformed_image_terms": (C.c_int, [_h, C.c_int, C.POINTER(DeformedImageMisfit)]),
     "glims_adjoint_deformed_image_info": (C.c_int, [_h, C.c_int, _i64p, _dp]),
+    "glims_adjoint_observable_terms": (C.c_int, [_h, C.c_int, C.POINTER(ObservableMisfit)]),
+    "glims_adjoint_observable_info": (C.c_int, [_h, C.c_int, _i64p, _dp]),
     "glims_comm_unique_id": (C.c_int, [C.c_char_p]),
     "glims_comm_init": (C.c_int, [_h, C.c_int, C.c_int, C.c_char_p]),
     "glims_comm_selftest": (C.c_int, [_h]),
@@ -283,6 +292,8 @@ class Handle:
         self.n_labels = None   # label count of the last successful set_materials
         self._image_terms = []   # what the library's stored image terms were made from (see _sync_image_terms)
         self._deformed_terms = []   # ... and the stored deformed image terms (see _split_terms)
+        self._observable_terms = []   # ... and the keys of the stored volume terms
+        self._observable_from_list = False
         self._warned_folded = False
 
     # -- plumbing --------------------------------------------------------------------------------
@@ -687,10 +698,62 @@ class Handle:
                 self._warned_folded = True
                 return
 
+    # -- volume misfit terms (glims_adjoint_observable_*) ----------------------------------------------
+    @staticmethod
+    def _observable_key(t):
+        """What identifies a stored volume term: its scalars and the counted labels."""
+        lab = t.get("labels")
+        kind = t.get("observable", "smooth")
+        return (int(t["step"]), OBSERVE_KINDS.get(kind, kind), float(t.get("level", 0.0)), float(t.get("smooth", 1.0)),
+                float(t.get("weight", 1.0)), float(t["target"]),
+                None if lab is None else tuple(bool(v) for v in np.ravel(lab)))
+
+    def set_observable_terms(self, terms, _from_list=False):
+        """glims_adjoint_observable_terms: replace the handle's stored volume terms (an empty list clears them).  Each term:
+        {step, observable ('mass' | 'sharp' | 'smooth' or GLIMS_OBSERVE_*), target, weight=1, level=0, smooth=1, labels=None}
+        with J = 1/2 weight (V - target)^2, V the measure observe() returns for (observable, level, smooth) on recorded step
+        ``step`` in the reference configuration, summed over the labels whose entry of ``labels`` ([n_labels], truthy =
+        counted) is set, or over the whole domain.  Every later adjoint_gradient / adjoint_hessian adds these terms."""
+        terms = list(terms)
+        arr = (ObservableMisfit * max(1, len(terms)))()
+        keep = []
+        for k, t in enumerate(terms):
+            kind = t.get("observable", "smooth")
+            kind = OBSERVE_KINDS[kind] if isinstance(kind, str) else int(kind)
+            lab = t.get("labels")
+            if lab is not None:
+                if self.n_labels is None:
+                    raise BackendError(GLIMS_E_USAGE, "set_observable_terms before set_materials")
+                lab = np.ascontiguousarray(np.asarray(lab).reshape(-1) != 0, dtype=np.uint8)
+                if lab.shape != (self.n_labels,):
+                    raise ValueError("volume term %d: labels has %d entries, set_materials gave %d labels"
+                                     % (k, lab.size, self.n_labels))
+                keep.append(lab)
+            arr[k] = ObservableMisfit(int(t["step"]), kind, float(t.get("level", 0.0)), float(t.get("smooth", 1.0)),
+                                      float(t.get("weight", 1.0)), float(t["target"]),
+                                      None if lab is None else lab.ctypes.data_as(C.POINTER(C.c_uint8)))
+        self._check(self.lib.glims_adjoint_observable_terms(self._h, len(terms), arr))
+        del keep
+        self._observable_terms = [self._observable_key(t) for t in terms]
+        self._observable_from_list = bool(_from_list)
+
+    def observable_term_info(self, k):
+        """Stored volume term k: a dict counted (cells of the counted labels), cut (cells the level set cut at the LAST
+        evaluation; -1 before the first and for 'mass' / 'smooth'), V (the last measure; NaN before the first)."""
+        out = np.zeros(2, dtype=np.int64)
+        V = C.c_double(0.0)
+        self._check(self.lib.glims_adjoint_observable_info(self._h, int(k), _ptr(out, _i64p), C.byref(V)))
+        return dict(counted=int(out[0]), cut=int(out[1]), V=V.value)
+
     def _split_terms(self, terms):
         """The nodal terms of a mixed list; its image terms become the handle's stored lists -- the fixed ones and those with
-        deformed=True, each re-sent only on a change."""
+        deformed=True -- and its volume terms (kind 'obs_volume') the third, each re-sent only on a change."""
         terms = list(terms)
+        volume = [t for t in terms if t["kind"] == "obs_volume"]
+        if volume or getattr(self, "_observable_from_list", False):
+            if [self._observable_key(t) for t in volume] != getattr(self, "_observable_terms", []):
+                self.set_observable_terms(volume, _from_list=True)
+            terms = [t for t in terms if t["kind"] != "obs_volume"]
         moving = [t for t in terms if _IMAGE_KINDS.get(t["kind"]) is not None and t.get("deformed")]
         if moving or getattr(self, "_deformed_from_list", False):
             if [self._deformed_key(t) for t in moving] != [k for k, _ in self._deformed_terms]:
@@ -752,6 +815,11 @@ class Handle:
         if any(_IMAGE_KINDS.get(t["kind"]) is not None and t.get("deformed") for t in terms):
             raise NotImplementedError("adjoint_hessian: second order through the location of a deformed image term is not "
                                       "built (glims_adjoint_hessian refuses while such a term is stored)")
+        if any(t["kind"] == "obs_volume" and OBSERVE_KINDS.get(t.get("observable", "smooth"), t.get("observable")) == 1
+               for t in terms):
+            raise NotImplementedError("adjoint_hessian: a sharp volume term is piecewise smooth, with jumps in its second "
+                                      "derivative; second order is built for 'mass' and 'smooth' (glims_adjoint_hessian "
+                                      "refuses while such a term is stored)")
         terms = self._split_terms(terms)
         arr, keep = self._misfit_array(terms)
 

@@ -777,6 +777,7 @@ int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_o
       have_u = sw.deformed_image_terms(step, c, have_u);
       if (sw.status != GLIMS_OK) break;
     }
+    gl_observable_terms_of_step(h, step, c, wk.g.p, &sw.J, 0, nullptr, 0, nullptr);
     if (have_u && !sw.coupling_adjoint(c)) break;
     if (step == 0) {
       if (dc0) sw.c0_output(dc0);
@@ -1742,6 +1743,7 @@ int hessian_t(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, const
     });
     if (status != GLIMS_OK) break;
     image_terms_of_step(h, step, c, wk.g.p, &sw.J, P, dc_of(step, 0), nn, dg.p);
+    gl_observable_terms_of_step(h, step, c, wk.g.p, &sw.J, P, dc_of(step, 0), nn, dg.p);
     if (have_u) {
       if (!sw.coupling_adjoint(c)) break;
       // per direction: du = K_el^-1 (G dc + sum_t dgamma_t G_t c), dmu = K_el^-1 sum w M_vec du (0 on the constrained dofs);
@@ -1986,7 +1988,7 @@ void gl_adjoint_after_step(glims_ctx* h, int status) {
 namespace {
 // The argument and state checks of one rank (GLIMS_E_USAGE with the reason)
 void check_gradient_call(glims_ctx* h, int n_terms, const glims_misfit* terms, const double* J,
-                         const std::string& who = "glims_adjoint_gradient") {
+                         const std::string& who = "glims_adjoint_gradient", bool second_order = false) {
   const AdjointState& a = h->adj;
   GL_REQUIRE(J, who + ": null J");
   GL_REQUIRE(n_terms >= 0 && (n_terms == 0 || terms), who + ": bad term list");
@@ -2015,6 +2017,7 @@ void check_gradient_call(glims_ctx* h, int n_terms, const glims_misfit* terms, c
     GL_REQUIRE(h->dimg_terms[k]->step <= N, who + ": stored deformed image term " + std::to_string(k) + " observes step " +
                                                 std::to_string(h->dimg_terms[k]->step) + ", the recording has steps 0.." +
                                                 std::to_string(N));
+  gl_observable_terms_check(h, N, who, second_order);
 }
 }  // namespace
 
@@ -2090,7 +2093,7 @@ int gl_adjoint_hessian(glims_ctx* h, int n_terms, const glims_misfit* terms, int
   GL_REQUIRE(h->dimg_terms.empty(), "glims_adjoint_hessian: second order through the location of the stored deformed image "
                                     "terms is not built (a Hessian without them would be wrong): clear them with "
                                     "glims_adjoint_deformed_image_terms(h, 0, NULL) first");
-  check_gradient_call(h, n_terms, terms, J, "glims_adjoint_hessian");
+  check_gradient_call(h, n_terms, terms, J, "glims_adjoint_hessian", true);
   check_n_dir(n_dir);
   return hessian_dispatch(h, n_terms, terms, n_dir, dir_D, dir_rho, dir_gamma, dir_c0, J, dD, drho, dgamma, dc0, hv_D, hv_rho,
                           hv_gamma, hv_c0, stats, false);
@@ -2107,7 +2110,7 @@ int gl_adjoint_hessian_full(glims_ctx* h, int n_terms, const glims_misfit* terms
   GL_REQUIRE(h->dimg_terms.empty(), who + ": second order through the location of the stored deformed image terms is not "
                                           "built (a Hessian without them would be wrong): clear them with "
                                           "glims_adjoint_deformed_image_terms(h, 0, NULL) first");
-  check_gradient_call(h, n_terms, terms, J, who);
+  check_gradient_call(h, n_terms, terms, J, who, true);
   check_n_dir(n_dir, who);
   GL_REQUIRE(h->have_mech || !(dir_E || dir_nu || hv_E || hv_nu),
              who + ": dir_E / dir_nu / hv_E / hv_nu need glims_setup(with_mechanics=1)");

@@ -1061,6 +1061,20 @@ int glims_adjoint_deformed_image_info(glims_ctx* h, int k, int64_t out[4], doubl
   });
 }
 
+int glims_adjoint_observable_terms(glims_ctx* h, int n, const glims_observable_misfit* terms) {
+  return guarded(h, [&]() {
+    gl_observable_terms_set(h, n, terms);
+    return GLIMS_OK;
+  });
+}
+
+int glims_adjoint_observable_info(glims_ctx* h, int k, int64_t out[2], double* V) {
+  return guarded(h, [&]() {
+    gl_observable_term_info(h, k, out, V);
+    return GLIMS_OK;
+  });
+}
+
 int glims_project(glims_ctx* h, const double* rhs, double* x, int ncomp, double rtol) {
   return guarded(h, [&]() {
     GL_REQUIRE(rhs && x && ncomp >= 1 && rtol > 0.0, "bad arguments");

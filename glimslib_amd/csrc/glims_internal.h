@@ -4,6 +4,7 @@
 #include <rccl/rccl.h>
 #include <stdint.h>
 #include <algorithm>
+#include <cmath>
 #include <memory>
 #include <string>
 #include <vector>
@@ -551,6 +552,32 @@ struct ObserveState {
   int64_t n_cell_passes = 0, n_elastic_solves = 0, n_sources = 0;   // glims_observe_info
 };
 
+// One stored volume misfit term (glims_adjoint_observable_terms; kernels in observe.hip): J = 1/2 weight (V - target)^2 with V the
+// measure of the query over the cells of the counted labels, in the reference configuration
+struct GlObservableTerm {
+  int64_t step = 0;
+  int kind = 0;
+  double level = 0.0, smooth = 1.0, weight = 1.0, target = 0.0;
+  std::vector<uint8_t> mask;               // [n_labels of the call that stored it]: non-zero = counted; empty = every label
+  int64_t n_counted = 0;                   // cells of the counted labels
+  int64_t n_cut = -1;                      // SHARP: cells the level set cut at the LAST evaluation (-1 before the first)
+  double V = NAN;                          // the measure of the LAST evaluation (NaN before the first)
+};
+
+// The stored volume terms and the scratch of their passes (observe.hip): per batch of up to GLIMS_OBSERVE_MAX_QUERIES terms that
+// observe one step, the vertex partials as planes [term][vertex][cell], the per-wave sums and the reduced values
+struct ObsTermState {
+  std::vector<GlObservableTerm> terms;
+  std::vector<int64_t> label_cells;        // [GL_MAX_LABELS] cells per label (empty: the labels were not read yet)
+  dvec<double> planes;                     // d V_T / d c_a            [terms of the batch][dim + 1][n_cells]
+  dvec<double> planes2;                    // (H_T dc_j)_a, one direction at a time (second order), same layout
+  dvec<double> part;                       // per-wave sums [waves][terms of the batch]
+  dvec<unsigned int> cut_part;             // per-wave counts of cut cells, same layout
+  dvec<double> vals;                       // [3][MAX_QUERIES]: V, coef = weight (V - target), weight g^T dc_j
+  dvec<long long> cuts;                    // [MAX_QUERIES]
+  int64_t n_cell_passes = 0, n_gathers = 0;   // cumulative (tools/observable_term_cost.py reads the timing lines instead)
+};
+
 // What gl_solve_mechanics remembers from one solve to the next.  The history of solved elasticity problems (right-hand side,
 // free-dof solution): the operator is linear and time independent, so the least-squares fit of a new right-hand side by the
 // stored ones gives the initial guess (mech_policy.h).  The history belongs to ONE elastic operator -- whatever changes K_el or
@@ -730,6 +757,7 @@ struct glims_ctx {
   std::vector<GlDeformedImageTerm*> dimg_terms;   // owned (sample.hip): the stored deformed-configuration image terms
   DeriveState derive;
   ObserveState observe;
+  ObsTermState obs_terms;                   // the stored volume misfit terms of the adjoint calls (observe.hip)
 
   std::string err;
 };
@@ -883,6 +911,15 @@ const double* gl_derive_sampled(glims_ctx* h, int ncomp);
 // observe.hip ---------------------------------------------------------------------------------------
 int gl_observe(glims_ctx* h, int n_src, const int64_t* src, const double* c_host, const double* u_host, int deformed,
                double scale, int n_q, const glims_observable* q, double* out);
+void gl_observable_terms_set(glims_ctx* h, int n, const glims_observable_misfit* terms);
+void gl_observable_term_info(glims_ctx* h, int k, int64_t out[2], double* V);
+// the checks a gradient / Hessian call makes of the stored volume terms (GLIMS_E_USAGE): steps within 0..N, mask lengths = n_labels,
+// and with second_order no SHARP term
+void gl_observable_terms_check(glims_ctx* h, int64_t N, const std::string& who, bool second_order);
+// The stored volume terms that observe `step`, in list order (c, g, dc, dg in the internal numbering): J += 1/2 w (V - t)^2,
+// g += w (V - t) grad V; with P > 0 also dg[j * ld + .] += w (grad V (grad V^T dc_j) + (V - t) H dc_j).  No such term: no launch.
+void gl_observable_terms_of_step(glims_ctx* h, int step, const double* c, double* g, double* J, int P, const double* dc,
+                                 int64_t ld, double* dg);
 
 // mg.hip --------------------------------------------------------------------------------------------
 void gl_mesh_metrics(glims_ctx* h, const HostPattern& hp, const double* xyz_old);

@@ -10,6 +10,7 @@
 // No float atomics; the same handle and arguments give the same bits on every call.
 #include "glims_internal.h"
 #include "observe_clip.h"
+#include "observe_grad.h"
 
 #include <cmath>
 #include <cstdio>
@@ -168,6 +169,244 @@ __global__ __launch_bounds__(256) void k_observe_sum(int64_t n_waves, int n_q, i
     const int k = i % no, q = (i / no) % n_q, s = i / (no * n_q);
     out[((size_t)q * n_labels + slot_label[s]) * no + k] = sm[0];
   }
+}
+
+// ---- volume misfit terms (glims_adjoint_observable_terms; the per-cell mathematics is observe_grad.h) ---------------------------
+//   k_observe_grad_cells  one lane per cell over the grid of k_observe_cells, ONE pass for up to GLIMS_OBSERVE_MAX_QUERIES stored
+//                         terms of a step: per term the d+1 vertex partials |T| d b0 / d c_a as planes [term][a][cell] (exact
+//                         zeros where the term's mask excludes the cell) and the wave's sum of V_T into its own row of `part`
+//   k_observe_second_cells  the same pass for one Hessian direction: grad V_T . dc|_T summed per wave, (H_T dc)_a as planes
+//   k_observe_grad_sum    one block per term: the per-wave rows summed in a fixed order; V, weight (V - target), the cut cells
+//   k_observe_grad_rows   lane = row along cslice_ptr / celem (as k_derive_rows<NV, 1, 1>): g[row] += sum_t coef_t sum_incidences
+//                         partial -- the row owns its sum, no atomics
+struct ObsGradTerms {
+  int n;
+  int kind[GLIMS_OBSERVE_MAX_QUERIES];
+  double level[GLIMS_OBSERVE_MAX_QUERIES], smooth[GLIMS_OBSERVE_MAX_QUERIES];
+  double weight[GLIMS_OBSERVE_MAX_QUERIES], target[GLIMS_OBSERVE_MAX_QUERIES];
+  unsigned long long mask[GLIMS_OBSERVE_MAX_QUERIES][GL_MAX_LABELS / 64];   // bit l: the cells of label l are counted
+};
+static_assert(GL_MAX_LABELS == 256, "ObsGradTerms::mask is four 64-bit words per term");
+
+__device__ __forceinline__ bool obs_counted(const ObsGradTerms& ts, int q, int lab) {
+  const int w = lab >> 6;
+  const unsigned long long m = w == 0 ? ts.mask[q][0] : w == 1 ? ts.mask[q][1] : w == 2 ? ts.mask[q][2] : ts.mask[q][3];
+  return (m >> (lab & 63)) & 1ull;
+}
+
+// part / cut_part: rows [waves][MAX_QUERIES], every entry written here: a wave keeps its sums in its own row of LDS (lane 0 alone
+// touches it) and stores the row once after the loop
+template <int D>
+__global__ __launch_bounds__(256) void k_observe_grad_cells(int64_t n_cells, const int32_t* __restrict__ cell_nodes,
+                                                            const uint8_t* __restrict__ label, const double* __restrict__ evol,
+                                                            const double* __restrict__ c, ObsGradTerms ts,
+                                                            double* __restrict__ planes, double* __restrict__ part,
+                                                            unsigned int* __restrict__ cut_part) {
+  constexpr int NV = D + 1;
+  const int lane = threadIdx.x & (GL_WAVE - 1), wave = threadIdx.x / GL_WAVE;
+  const int64_t gwave = (int64_t)blockIdx.x * GL_OBS_WAVES + wave;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  __shared__ double acc[GL_OBS_WAVES][GLIMS_OBSERVE_MAX_QUERIES];
+  __shared__ unsigned int acc_cut[GL_OBS_WAVES][GLIMS_OBSERVE_MAX_QUERIES];
+  if (lane == 0)
+    for (int q = 0; q < GLIMS_OBSERVE_MAX_QUERIES; ++q) {
+      acc[wave][q] = 0.0;
+      acc_cut[wave][q] = 0u;
+    }
+  // (wave-uniform trip count: the 64 cells of an iteration are consecutive)
+  for (int64_t base = (int64_t)blockIdx.x * blockDim.x + wave * GL_WAVE; base < n_cells; base += stride) {
+    const int64_t e = base + lane;
+    const bool valid = e < n_cells;
+    int lab = 0;
+    double cv[NV], T = 0.0;
+#pragma unroll
+    for (int m = 0; m < NV; ++m) cv[m] = 0.0;
+    if (valid) {
+      lab = label[e];
+      T = evol[e];
+#pragma unroll
+      for (int m = 0; m < NV; ++m) cv[m] = c[cell_nodes[e * NV + m]];
+    }
+    for (int q = 0; q < ts.n; ++q) {
+      double g[NV], v = 0.0;
+#pragma unroll
+      for (int m = 0; m < NV; ++m) g[m] = 0.0;
+      bool cut = false;
+      if (valid && obs_counted(ts, q, lab)) {
+        const int kind = ts.kind[q];
+        double b0;
+        if (kind == GLIMS_OBSERVE_MASS) {
+          b0 = glims_og_mass<D>(cv, g);
+        } else if (kind == GLIMS_OBSERVE_SHARP) {
+          int n_in = 0;
+          b0 = glims_og_sharp<D>(ts.level[q], cv, g, &n_in);
+          cut = n_in > 0 && n_in < NV;
+        } else {
+          if constexpr (D == 2)
+            b0 = glims_og_smooth<2, GLIMS_DQ2_N>(ts.level[q], ts.smooth[q], cv, c_oq2_lam, c_oq2_w, g, nullptr, nullptr);
+          else
+            b0 = glims_og_smooth<3, GLIMS_DQ3_N>(ts.level[q], ts.smooth[q], cv, c_oq3_lam, c_oq3_w, g, nullptr, nullptr);
+        }
+        v = T * b0;
+#pragma unroll
+        for (int m = 0; m < NV; ++m) g[m] *= T;
+      }
+      if (valid) {
+#pragma unroll
+        for (int m = 0; m < NV; ++m) planes[((int64_t)q * NV + m) * n_cells + e] = g[m];
+      }
+      const double r = wave_sum(v);
+      const unsigned int n_cut = (unsigned int)__popcll(__ballot(cut));
+      if (lane == 0) {
+        acc[wave][q] += r;
+        acc_cut[wave][q] += n_cut;
+      }
+    }
+  }
+  if (lane == 0)
+    for (int q = 0; q < GLIMS_OBSERVE_MAX_QUERIES; ++q) {
+      part[gwave * GLIMS_OBSERVE_MAX_QUERIES + q] = acc[wave][q];
+      cut_part[gwave * GLIMS_OBSERVE_MAX_QUERIES + q] = acc_cut[wave][q];
+    }
+}
+
+// One Hessian direction dc: per term the wave's sum of grad V_T . dc|_T (from the planes of k_observe_grad_cells) into `part`,
+// and planes2 [term][a][cell] = |T| (H_T dc)_a -- SMOOTH alone has one; zeros for the other kinds and the cells not counted
+template <int D>
+__global__ __launch_bounds__(256) void k_observe_second_cells(int64_t n_cells, const int32_t* __restrict__ cell_nodes,
+                                                              const uint8_t* __restrict__ label, const double* __restrict__ evol,
+                                                              const double* __restrict__ c, const double* __restrict__ dc,
+                                                              ObsGradTerms ts, const double* __restrict__ planes,
+                                                              double* __restrict__ planes2, double* __restrict__ part) {
+  constexpr int NV = D + 1;
+  const int lane = threadIdx.x & (GL_WAVE - 1), wave = threadIdx.x / GL_WAVE;
+  const int64_t gwave = (int64_t)blockIdx.x * GL_OBS_WAVES + wave;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  __shared__ double acc[GL_OBS_WAVES][GLIMS_OBSERVE_MAX_QUERIES];   // (as k_observe_grad_cells)
+  if (lane == 0)
+    for (int q = 0; q < GLIMS_OBSERVE_MAX_QUERIES; ++q) acc[wave][q] = 0.0;
+  for (int64_t base = (int64_t)blockIdx.x * blockDim.x + wave * GL_WAVE; base < n_cells; base += stride) {
+    const int64_t e = base + lane;
+    const bool valid = e < n_cells;
+    int lab = 0;
+    double cv[NV], dv[NV], T = 0.0;
+#pragma unroll
+    for (int m = 0; m < NV; ++m) cv[m] = dv[m] = 0.0;
+    if (valid) {
+      lab = label[e];
+      T = evol[e];
+#pragma unroll
+      for (int m = 0; m < NV; ++m) {
+        const int32_t nd = cell_nodes[e * NV + m];
+        cv[m] = c[nd];
+        dv[m] = dc[nd];
+      }
+    }
+    for (int q = 0; q < ts.n; ++q) {
+      double Hd[NV], s = 0.0;
+#pragma unroll
+      for (int m = 0; m < NV; ++m) Hd[m] = 0.0;
+      if (valid) {
+#pragma unroll
+        for (int m = 0; m < NV; ++m) s += planes[((int64_t)q * NV + m) * n_cells + e] * dv[m];
+        if (ts.kind[q] == GLIMS_OBSERVE_SMOOTH && obs_counted(ts, q, lab)) {
+          double g[NV];
+          if constexpr (D == 2)
+            (void)glims_og_smooth<2, GLIMS_DQ2_N>(ts.level[q], ts.smooth[q], cv, c_oq2_lam, c_oq2_w, g, dv, Hd);
+          else
+            (void)glims_og_smooth<3, GLIMS_DQ3_N>(ts.level[q], ts.smooth[q], cv, c_oq3_lam, c_oq3_w, g, dv, Hd);
+#pragma unroll
+          for (int m = 0; m < NV; ++m) Hd[m] *= T;
+        }
+#pragma unroll
+        for (int m = 0; m < NV; ++m) planes2[((int64_t)q * NV + m) * n_cells + e] = Hd[m];
+      }
+      const double r = wave_sum(s);
+      if (lane == 0) acc[wave][q] += r;
+    }
+  }
+  if (lane == 0)
+    for (int q = 0; q < GLIMS_OBSERVE_MAX_QUERIES; ++q) part[gwave * GLIMS_OBSERVE_MAX_QUERIES + q] = acc[wave][q];
+}
+
+// One block per term q: S = the per-wave rows summed in a fixed order.  mode 0: vals[q] = V = S, vals[MAXQ + q] = weight (V -
+// target), cuts[q] = the cut cells;  mode 1: vals[2 MAXQ + q] = weight S  (weight g^T dc_j of a Hessian direction)
+__global__ __launch_bounds__(256) void k_observe_grad_sum(int64_t n_waves, const double* __restrict__ part,
+                                                          const unsigned int* __restrict__ cut_part, ObsGradTerms ts, int mode,
+                                                          double* __restrict__ vals, long long* __restrict__ cuts) {
+  __shared__ double sm[256];
+  __shared__ long long sc[256];
+  const int q = blockIdx.x;
+  double acc = 0.0;
+  long long cnt = 0;
+  for (int64_t w = threadIdx.x; w < n_waves; w += 256) {
+    acc += part[w * GLIMS_OBSERVE_MAX_QUERIES + q];
+    if (mode == 0) cnt += cut_part[w * GLIMS_OBSERVE_MAX_QUERIES + q];
+  }
+  sm[threadIdx.x] = acc;
+  sc[threadIdx.x] = cnt;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) {
+      sm[threadIdx.x] += sm[threadIdx.x + o];
+      sc[threadIdx.x] += sc[threadIdx.x + o];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    if (mode == 0) {
+      vals[q] = sm[0];
+      vals[GLIMS_OBSERVE_MAX_QUERIES + q] = ts.weight[q] * (sm[0] - ts.target[q]);
+      cuts[q] = sc[0];
+    } else {
+      vals[2 * GLIMS_OBSERVE_MAX_QUERIES + q] = ts.weight[q] * sm[0];
+    }
+  }
+}
+
+// g[row] += sum_t (coef_a[t] A_t + coef_b[t] B_t), A_t / B_t = the row's sums, along its incidence list in list order, of the
+// planes pa / pb [t][a][cell] at the vertex a the row is in that cell (pb == nullptr: the first part alone).  The terms' sum
+// starts from 0 and is added to g once: a list sent in two parts gives the bits of the whole.
+template <int NV>
+__global__ __launch_bounds__(256) void k_observe_grad_rows(int64_t n_own, int64_t n_cells,
+                                                           const int64_t* __restrict__ cslice_ptr,
+                                                           const int32_t* __restrict__ celem,
+                                                           const int32_t* __restrict__ cell_nodes, int n_t,
+                                                           const double* __restrict__ pa, const double* __restrict__ coef_a,
+                                                           const double* __restrict__ pb, const double* __restrict__ coef_b,
+                                                           double* __restrict__ g) {
+  const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= n_own) return;
+  const int64_t s = row >> 6, lane = row & 63;
+  const int64_t cbase = cslice_ptr[s];
+  const int clen = (int)((cslice_ptr[s + 1] - cbase) >> 6);
+  double A[GLIMS_OBSERVE_MAX_QUERIES], B[GLIMS_OBSERVE_MAX_QUERIES];
+#pragma unroll
+  for (int t = 0; t < GLIMS_OBSERVE_MAX_QUERIES; ++t) A[t] = B[t] = 0.0;
+  for (int k = 0; k < clen; ++k) {
+    const int32_t e = celem[cbase + (int64_t)k * GL_WAVE + lane];
+    if (e < 0) continue;
+    int a = -1;
+#pragma unroll
+    for (int m = 0; m < NV; ++m)
+      if (cell_nodes[(int64_t)e * NV + m] == (int32_t)row) a = m;
+    if (a < 0) continue;
+#pragma unroll
+    for (int t = 0; t < GLIMS_OBSERVE_MAX_QUERIES; ++t)
+      if (t < n_t) {
+        const int64_t at = ((int64_t)t * NV + a) * n_cells + e;
+        A[t] += pa[at];
+        if (pb) B[t] += pb[at];
+      }
+  }
+  double sum = 0.0;
+#pragma unroll
+  for (int t = 0; t < GLIMS_OBSERVE_MAX_QUERIES; ++t)
+    if (t < n_t) {
+      sum += coef_a[t] * A[t];
+      if (pb) sum += coef_b[t] * B[t];
+    }
+  g[row] += sum;
 }
 
 inline int worse(int a, int b) { return a == GLIMS_NAN || b == GLIMS_OK ? a : b; }
@@ -337,4 +576,244 @@ int gl_observe(glims_ctx* h, int n_src, const int64_t* src, const double* c_host
   }
   std::copy(host.begin(), host.end(), out);
   return status;
+}
+
+// ---- volume misfit terms: the stored list and its passes -------------------------------------------------------------------------
+namespace {
+
+// cells per label, read from the device once per handle
+void ensure_label_cells(glims_ctx* h) {
+  ObsTermState& os = h->obs_terms;
+  if (!os.label_cells.empty()) return;
+  std::vector<uint8_t> lab((size_t)h->n_cells);
+  if (h->n_cells > 0) {
+    GL_HIP(hipMemcpyAsync(lab.data(), h->label.p, lab.size(), hipMemcpyDeviceToHost, h->st));
+    GL_HIP(hipStreamSynchronize(h->st));
+  }
+  os.label_cells.assign(GL_MAX_LABELS, 0);
+  for (uint8_t l : lab) os.label_cells[l]++;
+}
+
+// The scratch of the passes, sized from the mesh for nt terms per pass (the largest batch of the stored list; second: with the
+// planes of a Hessian direction).  Grow-only: a buffer that is large enough stays, one that is too small is released before the
+// free memory is asked for, so that its bytes count; GLIMS_E_HIP with the figures when the new size does not fit.
+// gl_observable_terms_set releases the planes whenever the list is replaced or cleared.
+void ensure_term_scratch(glims_ctx* h, int nt, bool second, int64_t n_waves) {
+  ObsTermState& os = h->obs_terms;
+  const size_t plane = (size_t)nt * (h->dim + 1) * (size_t)h->n_cells;
+  const size_t rows = (size_t)n_waves * GLIMS_OBSERVE_MAX_QUERIES;
+  size_t need = 0;
+  if (os.planes.n < plane) {
+    os.planes.release();
+    need += plane * sizeof(double);
+  }
+  if (second && os.planes2.n < plane) {
+    os.planes2.release();
+    need += plane * sizeof(double);
+  }
+  if (os.part.n < rows) need += rows * (sizeof(double) + sizeof(unsigned int));
+  if (need) {
+    size_t fr = 0, tot = 0;
+    GL_HIP(hipMemGetInfo(&fr, &tot));
+    if (need > fr)
+      throw glims_error(GLIMS_E_HIP, "glims_adjoint_observable_terms: the vertex partials of " + std::to_string(nt) +
+                                         " volume terms over " + std::to_string(h->n_cells) + " cells need about " +
+                                         std::to_string(need >> 20) + " MiB of device memory, " + std::to_string(fr >> 20) +
+                                         " MiB are free");
+  }
+  if (os.planes.n < plane) os.planes.alloc(plane);
+  if (second && os.planes2.n < plane) os.planes2.alloc(plane);
+  if (os.part.n < rows) {
+    os.part.alloc(rows);
+    os.cut_part.alloc(rows);
+  }
+  os.vals.alloc((size_t)3 * GLIMS_OBSERVE_MAX_QUERIES);
+  os.cuts.alloc((size_t)GLIMS_OBSERVE_MAX_QUERIES);
+}
+
+template <int D>
+void observable_batch(glims_ctx* h, const std::vector<int>& batch, int nt_alloc, const double* c, double* g, double* J, int P,
+                      const double* dc, int64_t ld, double* dg, int step) {
+  ObsTermState& os = h->obs_terms;
+  constexpr int NV = D + 1, MQ = GLIMS_OBSERVE_MAX_QUERIES;
+  const int nt = (int)batch.size();
+  ObsGradTerms ts;
+  ts.n = nt;
+  for (int q = 0; q < MQ; ++q) {
+    ts.kind[q] = GLIMS_OBSERVE_MASS;
+    ts.level[q] = ts.weight[q] = ts.target[q] = 0.0;
+    ts.smooth[q] = 1.0;
+    for (int w = 0; w < GL_MAX_LABELS / 64; ++w) ts.mask[q][w] = 0ull;
+  }
+  for (int q = 0; q < nt; ++q) {
+    const GlObservableTerm& t = os.terms[(size_t)batch[(size_t)q]];
+    ts.kind[q] = t.kind;
+    ts.level[q] = t.level;
+    ts.smooth[q] = t.kind == GLIMS_OBSERVE_SMOOTH ? t.smooth : 1.0;
+    ts.weight[q] = t.weight;
+    ts.target[q] = t.target;
+    for (int l = 0; l < GL_MAX_LABELS; ++l)
+      if (t.mask.empty() || (l < (int)t.mask.size() && t.mask[(size_t)l])) ts.mask[q][l >> 6] |= 1ull << (l & 63);
+  }
+  double vals[2 * MQ] = {0.0};
+  long long cuts[MQ] = {0};
+  if (h->n_cells > 0) {
+    const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(GL_OBS_BLOCKS, grid_of(h->n_cells)));
+    const int64_t n_waves = (int64_t)nb * GL_OBS_WAVES;
+    ensure_term_scratch(h, nt_alloc, P > 0, n_waves);
+    const int32_t* cn = gl_ensure_cell_nodes(h);
+    // GLIMS_OBSERVABLE_TIMING: an event pair around the cell pass (with its sum) and one around the gather, one line per batch
+    const bool timed = getenv("GLIMS_OBSERVABLE_TIMING") != nullptr;
+    float ms_cells = 0.f, ms_rows = 0.f;
+    auto tick = [&]() {
+      if (timed) GL_HIP(hipEventRecord(h->ev_a, h->st));
+    };
+    auto tock = [&](float* ms) {
+      if (!timed) return;
+      GL_HIP(hipEventRecord(h->ev_b, h->st));
+      GL_HIP(hipEventSynchronize(h->ev_b));
+      GL_HIP(hipEventElapsedTime(ms, h->ev_a, h->ev_b));
+    };
+    tick();
+    hipLaunchKernelGGL(k_observe_grad_cells<D>, dim3(nb), dim3(256), 0, h->st, h->n_cells, cn, h->label.p, h->evol.p, c, ts,
+                       os.planes.p, os.part.p, os.cut_part.p);
+    GL_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_observe_grad_sum, dim3(nt), dim3(256), 0, h->st, n_waves, os.part.p, os.cut_part.p, ts, 0, os.vals.p,
+                       os.cuts.p);
+    GL_CHECK_LAUNCH();
+    tock(&ms_cells);
+    tick();
+    hipLaunchKernelGGL(k_observe_grad_rows<NV>, dim3(grid_of(h->n_own)), dim3(256), 0, h->st, h->n_own, h->n_cells,
+                       h->pat.cslice_ptr.p, h->pat.celem.p, cn, nt, os.planes.p, os.vals.p + MQ, (const double*)nullptr,
+                       (const double*)nullptr, g);
+    GL_CHECK_LAUNCH();
+    tock(&ms_rows);
+    os.n_cell_passes++;
+    os.n_gathers++;
+    if (timed)
+      fprintf(stderr, "glims observable terms: step %d  terms %d  cells %.4f ms  gather %.4f ms\n", step, nt, ms_cells, ms_rows);
+    for (int p = 0; p < P; ++p) {
+      // dg_p += sum_t (weight_t (g_t^T dc_p) G_t + weight_t (V_t - target_t) H_t dc_p)
+      hipLaunchKernelGGL(k_observe_second_cells<D>, dim3(nb), dim3(256), 0, h->st, h->n_cells, cn, h->label.p, h->evol.p, c,
+                         dc + (size_t)p * ld, ts, os.planes.p, os.planes2.p, os.part.p);
+      GL_CHECK_LAUNCH();
+      hipLaunchKernelGGL(k_observe_grad_sum, dim3(nt), dim3(256), 0, h->st, n_waves, os.part.p, os.cut_part.p, ts, 1, os.vals.p,
+                         os.cuts.p);
+      GL_CHECK_LAUNCH();
+      hipLaunchKernelGGL(k_observe_grad_rows<NV>, dim3(grid_of(h->n_own)), dim3(256), 0, h->st, h->n_own, h->n_cells,
+                         h->pat.cslice_ptr.p, h->pat.celem.p, cn, nt, os.planes.p, os.vals.p + 2 * MQ, os.planes2.p,
+                         os.vals.p + MQ, dg + (size_t)p * ld);
+      GL_CHECK_LAUNCH();
+      os.n_cell_passes++;
+      os.n_gathers++;
+    }
+    GL_HIP(hipMemcpyAsync(vals, os.vals.p, sizeof(vals), hipMemcpyDeviceToHost, h->st));
+    GL_HIP(hipMemcpyAsync(cuts, os.cuts.p, sizeof(cuts), hipMemcpyDeviceToHost, h->st));
+    GL_HIP(hipStreamSynchronize(h->st));
+  }
+  for (int q = 0; q < nt; ++q) {
+    GlObservableTerm& t = os.terms[(size_t)batch[(size_t)q]];
+    t.V = vals[q];
+    t.n_cut = t.kind == GLIMS_OBSERVE_SHARP ? (int64_t)cuts[q] : -1;
+    const double r = t.V - t.target;
+    *J += 0.5 * t.weight * (r * r);
+  }
+}
+
+}  // namespace
+
+void gl_observable_terms_set(glims_ctx* h, int n, const glims_observable_misfit* terms) {
+  const std::string who = "glims_adjoint_observable_terms";
+  ObsTermState& os = h->obs_terms;
+  GL_REQUIRE(n >= 0 && (n == 0 || terms), who + ": bad term list");
+  if (n == 0) {   // clearing is always possible; the planes go with the list
+    os.terms.clear();
+    os.planes.release();
+    os.planes2.release();
+    return;
+  }
+  GL_REQUIRE(h->world <= 1, who + ": not available on a partitioned handle (world > 1)");
+  GL_REQUIRE(h->is_setup, who + " before glims_setup");
+  GL_REQUIRE(h->n_labels > 0, who + " before glims_set_materials");
+  for (int k = 0; k < n; ++k) {
+    const glims_observable_misfit& t = terms[k];
+    const std::string tk = " of term " + std::to_string(k);
+    GL_REQUIRE(t.step >= 0, who + ": negative step" + tk);
+    GL_REQUIRE(t.kind >= GLIMS_OBSERVE_MASS && t.kind <= GLIMS_OBSERVE_SMOOTH,
+               who + ": unknown kind " + std::to_string(t.kind) + tk);
+    GL_REQUIRE(std::isfinite(t.level), who + ": level" + tk + " is not finite");
+    GL_REQUIRE(t.kind != GLIMS_OBSERVE_SMOOTH || t.smooth > 0.0, who + ": smooth" + tk + " must be positive");
+    GL_REQUIRE(std::isfinite(t.weight), who + ": weight" + tk + " is not finite");
+    GL_REQUIRE(std::isfinite(t.target), who + ": target" + tk + " is not finite");
+  }
+  ensure_label_cells(h);
+  std::vector<GlObservableTerm> fresh((size_t)n);
+  for (int k = 0; k < n; ++k) {
+    const glims_observable_misfit& t = terms[k];
+    GlObservableTerm& f = fresh[(size_t)k];
+    f.step = t.step;
+    f.kind = t.kind;
+    f.level = t.level;
+    f.smooth = t.kind == GLIMS_OBSERVE_SMOOTH ? t.smooth : 1.0;
+    f.weight = t.weight;
+    f.target = t.target;
+    if (t.labels) {
+      f.mask.assign(t.labels, t.labels + h->n_labels);
+      for (int l = 0; l < h->n_labels; ++l)
+        if (f.mask[(size_t)l]) f.n_counted += os.label_cells[(size_t)l];
+    } else {
+      f.n_counted = h->n_cells;
+    }
+  }
+  os.terms.swap(fresh);
+  // (the next call sizes the planes for the largest batch of THIS list)
+  os.planes.release();
+  os.planes2.release();
+}
+
+void gl_observable_term_info(glims_ctx* h, int k, int64_t out[2], double* V) {
+  const ObsTermState& os = h->obs_terms;
+  GL_REQUIRE(out && V, "glims_adjoint_observable_info: null output");
+  GL_REQUIRE(k >= 0 && k < (int)os.terms.size(), "glims_adjoint_observable_info: no stored term " + std::to_string(k));
+  const GlObservableTerm& t = os.terms[(size_t)k];
+  out[0] = t.n_counted;
+  out[1] = t.n_cut;
+  *V = t.V;
+}
+
+void gl_observable_terms_check(glims_ctx* h, int64_t N, const std::string& who, bool second_order) {
+  const ObsTermState& os = h->obs_terms;
+  for (size_t k = 0; k < os.terms.size(); ++k) {
+    const GlObservableTerm& t = os.terms[k];
+    GL_REQUIRE(t.step <= N, who + ": stored volume term " + std::to_string(k) + " observes step " + std::to_string(t.step) +
+                                ", the recording has steps 0.." + std::to_string(N));
+    GL_REQUIRE(t.mask.empty() || (int)t.mask.size() == h->n_labels,
+               who + ": the label mask of stored volume term " + std::to_string(k) + " has " + std::to_string(t.mask.size()) +
+                   " entries, glims_set_materials now has " + std::to_string(h->n_labels) + " labels");
+    GL_REQUIRE(!second_order || t.kind != GLIMS_OBSERVE_SHARP,
+               who + ": stored volume term " + std::to_string(k) + " is SHARP: its measure is piecewise smooth, with jumps in "
+                     "the second derivative where the level set crosses a vertex; second order is built for MASS and SMOOTH");
+  }
+}
+
+void gl_observable_terms_of_step(glims_ctx* h, int step, const double* c, double* g, double* J, int P, const double* dc,
+                                 int64_t ld, double* dg) {
+  ObsTermState& os = h->obs_terms;
+  std::vector<int> here;
+  for (size_t k = 0; k < os.terms.size(); ++k)
+    if (os.terms[k].step == step) here.push_back((int)k);
+  if (here.empty()) return;
+  // the planes serve the largest batch of the whole list: no step of this or a later call reallocates them
+  std::vector<int> per_step;
+  for (const GlObservableTerm& t : os.terms) {
+    if ((size_t)t.step >= per_step.size()) per_step.resize((size_t)t.step + 1, 0);
+    per_step[(size_t)t.step]++;
+  }
+  const int nt_alloc = std::min(GLIMS_OBSERVE_MAX_QUERIES, *std::max_element(per_step.begin(), per_step.end()));
+  for (size_t b = 0; b < here.size(); b += GLIMS_OBSERVE_MAX_QUERIES) {
+    const std::vector<int> batch(here.begin() + (long)b,
+                                 here.begin() + (long)std::min(here.size(), b + GLIMS_OBSERVE_MAX_QUERIES));
+    if (h->dim == 2) observable_batch<2>(h, batch, nt_alloc, c, g, J, P, dc, ld, dg, step);
+    else observable_batch<3>(h, batch, nt_alloc, c, g, J, P, dc, ld, dg, step);
+  }
 }

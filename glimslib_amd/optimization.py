@@ -55,7 +55,8 @@ class ReducedFunctional:
     default such controls are first order only and the Hessian raises.
 
     A term list with a deformed image term (``sim.image_term(..., deformed=True)``) is first order only: ``hessian`` and
-    ``hessian_matrix`` raise NotImplementedError.
+    ``hessian_matrix`` raise NotImplementedError.  So is a list with a sharp volume term (``sim.volume_term(kind='sharp')``);
+    smooth and mass volume terms have their second order.
 
     ``terms_builder(sim, n_steps)`` returns the misfit terms (see ``Handle.adjoint_gradient``) once the forward run of m has
     taken ``n_steps`` steps.  The last m is cached: scipy's ``fun`` / ``jac`` pair for one m costs one forward and one
@@ -141,6 +142,9 @@ class ReducedFunctional:
             if any(t.get("deformed") for t in terms):
                 raise NotImplementedError("ReducedFunctional.hessian: second order through the location of a deformed image "
                                           "term is not built; use a first-order method (L-BFGS-B)")
+            if any(t.get("kind") == "obs_volume" and t.get("observable") == "sharp" for t in terms):
+                raise NotImplementedError("ReducedFunctional.hessian: a sharp volume term is piecewise smooth, with jumps in "
+                                          "its second derivative; use volume_term(kind='smooth') or a first-order method")
             if self.elastic_hessian:
                 _, hv = self.sim.adjoint_hessian(terms, dirs, elastic=True)
             else:

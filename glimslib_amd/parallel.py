@@ -355,6 +355,8 @@ class DistributedHandle:
         sampler."""
         loc = []
         for t in terms:
+            if t["kind"] == "obs_volume":
+                self._no_volume_terms()
             if t["kind"] in _backend._IMAGE_KINDS:
                 loc.append(self._image_term(t))
                 continue
@@ -432,6 +434,18 @@ class DistributedHandle:
         parts = [None] * self.world
         self.dist.all_gather_object(parts, int(n_obs))
         return sid, n, int(sum(parts))
+
+    # -- volume misfit terms: single-rank handles only (the library refuses them on a partitioned handle, as glims_observe) --
+    @staticmethod
+    def _no_volume_terms():
+        raise NotImplementedError("volume misfit terms (set_observable_terms, kind 'obs_volume') are not available on "
+                                  "partitioned runs")
+
+    def set_observable_terms(self, terms):
+        self._no_volume_terms()
+
+    def observable_term_info(self, k):
+        self._no_volume_terms()
 
     # -- samplers (collective: every rank passes the same points) --------------------------------------------------------
     def sampler_points(self, xyz, deformed_by=None, scale=1.0):

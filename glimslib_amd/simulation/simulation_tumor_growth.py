@@ -398,6 +398,36 @@ class TumorGrowth(FenicsSimulation):
             cache[1][key] = (term, image, mask)   # (image and mask stay alive: their identity is the key)
         return cache[1][key][0]
 
+    def volume_term(self, step, target, threshold=0.12, kind='smooth', smooth=0.01, tissues=None, weight=1.0):
+        """
+        A misfit term that compares a tumour VOLUME of recorded step `step` with the number `target`:
+        1/2 weight (V - target)^2, V the volume compute_from_conc_for_each_time_step(threshold, 'volume', kind, smooth) reports
+        (reference configuration) -- kind 'sharp' (c >= threshold, exact clipping), 'smooth' (the thresh() field of width
+        `smooth`) or 'mass' (int c dx, `threshold` unused).  `tissues`: names of that table's columns (the tissue names of
+        subdomains.tissue_id_name_map, any case) whose cells are counted; None = the whole domain ('all').  Pass it to
+        adjoint_gradient / ReducedFunctional in the same list as nodal and image terms: the backend stores it on the device and
+        adds weight (V - target) dV/dc to the backward sweep.  'sharp' is first order only (V is piecewise smooth: its
+        second derivative jumps where the level set crosses a mesh node); 'smooth' and 'mass' also serve adjoint_hessian.
+        Partitioned runs raise NotImplementedError when the term is used.
+        """
+        if kind not in _backend.OBSERVE_KINDS:
+            raise ValueError("volume_term: kind must be one of %s" % (tuple(_backend.OBSERVE_KINDS),))
+        mask = None
+        if tissues is not None:
+            if isinstance(tissues, str):
+                tissues = [tissues]
+            n_labels = int(self._labels().max()) + 1
+            ids = {str(name).lower(): int(tid) for tid, name in getattr(self.subdomains, 'tissue_id_name_map', {}).items()}
+            mask = np.zeros(n_labels, dtype=np.uint8)
+            for name in tissues:
+                tid = ids.get(str(name).lower())
+                if tid is None:
+                    raise ValueError("volume_term: unknown tissue %r (known: %s)" % (name, sorted(ids)))
+                if tid < n_labels:          # (a tissue that no cell carries counts nothing)
+                    mask[tid] = 1
+        return dict(step=int(step), kind='obs_volume', observable=kind, level=float(threshold), smooth=float(smooth),
+                    target=float(target), weight=float(weight), labels=mask)
+
     DERIVED_IMAGES = ('pressure', 'van_mises_stress', 'total_jacobian', 'growth_induced_jacobian',
                       'concentration_deformed_config', 'log_growth', 'displacement_norm', 'strain_tensor', 'stress_tensor')
 
@@ -568,6 +598,9 @@ class TumorGrowth(FenicsSimulation):
         if any(t.get('deformed') for t in terms):
             raise NotImplementedError("adjoint_hessian: second order through the location of a deformed image term "
                                       "(image_term(deformed=True)) is not built; use a first-order method")
+        if any(t.get('kind') == 'obs_volume' and t.get('observable') == 'sharp' for t in terms):
+            raise NotImplementedError("adjoint_hessian: a sharp volume term (volume_term(kind='sharp')) is piecewise smooth, "
+                                      "with jumps in its second derivative; use kind='smooth' or a first-order method")
         if elastic:   # (a partitioned run's DistributedHandle raises NotImplementedError)
             return h.adjoint_hessian_full(terms, directions)
         return h.adjoint_hessian(terms, directions)

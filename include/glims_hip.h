@@ -28,6 +28,8 @@
  *                        line per projection with both times on stderr (tools/derive_cost.py; a synchronisation per pass)
  *   GLIMS_OBSERVE_TIMING any value: glims_observe puts a HIP event pair around each source's pass and prints one line per source
  *                        with the time on stderr (a synchronisation per source)
+ *   GLIMS_OBSERVABLE_TIMING any value: the stored volume misfit terms put a HIP event pair around their cell pass and around their
+ *                        gather and print one line per pass with both times on stderr (tools/observable_term_cost.py)
  *   GLIMS_HOST_THREADS   OpenMP team of the host-side symbolic phase (default: the CPUs this process may use,
  *                        divided by the ranks on the host)
  *   GLIMS_HOST_SYMBOLIC  TEST HOOK: glims_create runs the host (OpenMP) implementation of the symbolic phase instead of
@@ -1004,6 +1006,51 @@ int glims_observe(glims_ctx* h, int n_src, const int64_t* src, const double* c_h
                   double scale, int n_q, const glims_observable* q, double* out);
 /* cumulative since glims_create: out[0] cell passes, [1] elastic solves, [2] sources observed, [3] 0 */
 int glims_observe_info(const glims_ctx* h, int64_t out[4]);
+
+/* ---- volume misfit terms: fits to tumour-volume series --------------------------------------------------------------------------
+ * The clinical datum is often a volume series, not an image: the T2- / T1-like tumour volume (c above 0.12 / 0.80) at a few scan
+ * dates, per tissue or over the whole domain -- the numbers glims_observe computes.  A stored volume term makes such a number a
+ * misfit term of the adjoint calls (the per-cell mathematics is csrc/observe_grad.h).  For the term that
+ * observes recorded step k,
+ *     V = sum over the cells T of the counted labels of V_T(c_k),    J_obs = 1/2 weight (V - target)^2,
+ * V the measure glims_observe returns for the query (kind, level, smooth) in the REFERENCE configuration (deformed = 0), summed
+ * over the counted labels, and
+ *     dJ_obs/dc_k = weight (V - target) g,    g_i = sum over the counted cells T that hold node i of dV_T/dc_i:
+ *   MASS    dV_T/dc_i = |T| / (d+1)
+ *   SMOOTH  dV_T/dc_i = |T| sum_q w_q h'(v_q) lam_qi      (the degree-7 rule of glims_observe, differentiated as it stands)
+ *   SHARP   the derivative of the clipped fraction through the edge parameters t = (c_a - level) / (c_a - c_b) of the cut edges;
+ *           a cell with 0 or d+1 vertices in contributes 0.  V is continuous and piecewise smooth in c: the gradient is that of
+ *           the smooth piece the evaluation sits on (a tie c_i == level counts as in).
+ * The terms are a THIRD stored list: glims_adjoint_observable_terms replaces this list only (n = 0 clears it), and every gradient /
+ * Hessian call evaluates, per step, the nodal terms in list order, then the fixed image terms, the deformed image terms and the
+ * volume terms, each in list order.  With an empty list every call issues exactly the work it issued before.  One pass over the
+ * cells serves up to GLIMS_OBSERVE_MAX_QUERIES terms of a step (more terms: more passes, in list order); it writes the vertex
+ * partials per cell, block sums in a fixed order give V, and a row-owned gather along the incidence lists adds them to the
+ * sweep's right-hand side: no float atomics, the same call gives the same bits every time.  The scratch (8 (dim+1) n_cells bytes per
+ * term of a pass, twice that in a Hessian call) is sized from the mesh; GLIMS_E_HIP with the figures when hipMemGetInfo says it
+ * does not fit.  The terms survive glims_setup, glims_set_materials (same label count), glims_set_state and a new recording;
+ * they touch neither the forward state nor glims_stats nor the bits of later steps.
+ *
+ * Second order (glims_adjoint_hessian, _hessian_spmd with world = 1, _hessian_full), MASS and SMOOTH: per direction j
+ *     dg_j += weight (g (g^T dc_j) + (V - target) H dc_j),    H = sum_T |T| sum_q w_q h''(v_q) lam_q lam_q^T  (MASS: 0),
+ * g^T dc_j summed cell by cell in the same fixed order.  SHARP is piecewise smooth with jumps in its second derivative where
+ * the level set crosses a vertex: while a SHARP term is stored the Hessian entry points return GLIMS_E_USAGE.
+ *
+ * GLIMS_E_USAGE with a reason, the old list left in place: a partitioned handle (world > 1), a call before glims_setup, an unknown
+ * kind, smooth <= 0 of a SMOOTH term, a level, weight or target that is not finite, a negative step.  A gradient or Hessian call
+ * refuses a term whose step is beyond the trajectory and a stored mask whose length is no longer n_labels.
+ * Not built: centre-of-mass and moment terms, volumes of the deformed configuration, partitioned handles, second order for SHARP. */
+typedef struct glims_observable_misfit {
+  int64_t step;              /* recorded step observed (0 = c_0) */
+  int     kind;              /* GLIMS_OBSERVE_MASS / _SHARP / _SMOOTH */
+  double  level, smooth;     /* as glims_observable */
+  double  weight, target;    /* J_obs = 1/2 weight (V - target)^2 */
+  const uint8_t* labels;     /* [n_labels of glims_set_materials]: non-zero = that label's cells are counted; NULL = all */
+} glims_observable_misfit;
+int glims_adjoint_observable_terms(glims_ctx* h, int n, const glims_observable_misfit* terms);   /* replaces the list; n = 0 clears */
+/* stored term k: out[0] the number of counted cells, out[1] the cells the level set cut at the LAST evaluation (-1 before the
+ * first, and for MASS / SMOOTH), *V the last V (NaN before the first) */
+int glims_adjoint_observable_info(glims_ctx* h, int k, int64_t out[2], double* V);
 
 /* ---- single-node multi-GPU (one process per GPU, RCCL over xGMI) ------------------------------------- */
 

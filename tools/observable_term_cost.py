@@ -1,0 +1,131 @@
+#!/usr/bin/env python
+"""
+What stored volume misfit terms (glims_adjoint_observable_terms) add to a gradient call, on the brain-like unstructured mesh:
+  * the wall time of adjoint_gradient of a recorded run with one nodal term and NO stored volume term -- the behaviour before the
+    terms existed, the baseline -- median of `--reps` calls after one warm-up,
+  * the same call with 1, 8 and 16 SMOOTH terms and with 8 SHARP terms on the last step (16 terms: two cell passes), and
+  * per pass the time of the cell pass (k_observe_grad_cells + its block sums) and of the row-owned gather
+    (k_observe_grad_rows), from the library's own HIP event pairs (GLIMS_OBSERVABLE_TIMING; measured in a separate run of calls:
+    the event pairs synchronise the stream),
+next to the algorithmic bytes of a pass: per cell its vertex ids, label and volume, per node c once, and the planes of vertex
+partials written by the cell pass and read back by the gather (8 (d+1) bytes per cell and term, each way).
+
+    python tools/observable_term_cost.py [--nodes 1000000] [--steps 10] [--reps 5]
+
+Writes one JSON line per configuration to profiles/observable_term_cost.jsonl (or --out).
+"""
+import argparse
+import json
+import os
+import re
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+CONFIGS = [("none", None, 0), ("smooth_1", "smooth", 1), ("smooth_8", "smooth", 8), ("smooth_16", "smooth", 16),
+           ("sharp_8", "sharp", 8)]
+
+
+def pass_times(h, nodal, n_labels, reps):
+    """[(terms, cells ms, gather ms)] of every pass of `reps` gradient calls after one warm-up"""
+    os.environ["GLIMS_OBSERVABLE_TIMING"] = "1"
+    with tempfile.TemporaryFile(mode="w+b") as tmp:
+        sys.stderr.flush()
+        saved = os.dup(2)
+        os.dup2(tmp.fileno(), 2)
+        try:
+            for rep in range(reps + 1):
+                h.adjoint_gradient(nodal, n_labels, want_dc0=False)
+                os.write(2, b"glims observable terms: end of call\n")
+        finally:
+            os.dup2(saved, 2)
+            os.close(saved)
+            del os.environ["GLIMS_OBSERVABLE_TIMING"]
+        tmp.seek(0)
+        calls, cur = [], []
+        for line in tmp.read().decode().splitlines():
+            if "end of call" in line:
+                calls.append(cur)
+                cur = []
+                continue
+            m = re.match(r"glims observable terms: step (\d+)\s+terms (\d+)\s+cells ([0-9.]+) ms\s+gather ([0-9.]+) ms", line)
+            if m:
+                cur.append((int(m.group(2)), float(m.group(3)), float(m.group(4))))
+    return calls[1:]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--nodes", type=int, default=1000000)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "observable_term_cost.jsonl"))
+    args = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        print("observable_term_cost.py: no GPU visible", file=sys.stderr)
+        return 3
+    from glimslib_amd import _backend, workloads
+    w = workloads.config_brain_like(args.nodes, mechanics=False, isolate=True)   # (the mesh builder forks: not from this process)
+    mesh, d = w.mesh, w.mesh.points.shape[1]
+    labels = np.asarray(w.cell_label)
+    n_labels = len(w.tables["D"])
+    n_cells, n_nodes = int(mesh.num_cells()), int(mesh.num_vertices())
+    h = _backend.Handle(mesh.points, mesh.cells, labels)
+    h.set_materials(*[w.tables[k] for k in ("D", "rho", "gamma", "E", "nu")])
+    h.set_options(dt=w.dt)
+    h.setup(False)
+    h.set_state(w.c0)
+    h.adjoint_record(True)
+    assert h.step(args.steps) == _backend.GLIMS_OK
+    c_last = h.get_state(want_u=False)[0]
+    nodal = [dict(step=args.steps, kind="c_l2", target=0.9 * c_last)]
+    lines = []
+    for name, kind, n in CONFIGS:
+        # levels spread over the reference's T2 .. T1 thresholds, as fractions of the run's largest c where the short run stays
+        # below 1 (a level above every nodal value would cut no cell); target 0, so that every term pulls
+        levels = np.linspace(0.12, 0.80, max(n, 1)) * min(1.0, float(c_last.max()))
+        h.set_observable_terms([dict(step=args.steps, kind="obs_volume", observable=kind, level=float(lv), smooth=0.05,
+                                     target=0.0, weight=1.0) for lv in levels[:n]])
+        walls = []
+        for rep in range(args.reps + 1):
+            t0 = time.perf_counter()
+            J = h.adjoint_gradient(nodal, n_labels, want_dc0=False)[0]
+            walls.append(time.perf_counter() - t0)
+        rec = dict(config=name, workload=w.name, n_nodes=n_nodes, n_cells=n_cells, steps=args.steps, kind=kind, n_terms=n,
+                   J=float(J), gradient_wall_s=round(float(np.median(walls[1:])), 5),
+                   gradient_wall_s_by_call=[round(float(v), 5) for v in walls[1:]])
+        if n:
+            calls = pass_times(h, nodal, n_labels, args.reps)
+            per_pass = [p for c in calls for p in c]
+            rec.update(passes_per_call=len(calls[0]), terms_per_pass=[p[0] for p in calls[0]],
+                       cells_ms_per_pass=round(float(np.median([p[1] for p in per_pass])), 4),
+                       gather_ms_per_pass=round(float(np.median([p[2] for p in per_pass])), 4),
+                       cells_ms_by_pass=[round(float(np.median([c[k][1] for c in calls])), 4) for k in range(len(calls[0]))],
+                       gather_ms_by_pass=[round(float(np.median([c[k][2] for c in calls])), 4) for k in range(len(calls[0]))])
+            nt = calls[0][0][0]
+            plane = 8 * (d + 1) * n_cells * nt
+            rec.update(model_bytes_cells=int(n_cells * (4 * (d + 1) + 1 + 8) + n_nodes * 8 + plane),
+                       model_bytes_gather=int(n_cells * (d + 1) * (4 + 4 * (d + 1)) + plane + 16 * n_nodes),
+                       V_first=h.observable_term_info(0)["V"], cut_first=h.observable_term_info(0)["cut"])
+        lines.append(rec)
+        print(json.dumps(rec), flush=True)
+    base = lines[0]["gradient_wall_s"]
+    for rec in lines[1:]:
+        rec["added_wall_s"] = round(rec["gradient_wall_s"] - base, 5)
+    h.set_observable_terms([])
+    h.close()
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        for ln in lines:
+            f.write(json.dumps(ln) + "\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
