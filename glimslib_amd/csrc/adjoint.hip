@@ -13,6 +13,7 @@
 //   C_t = dJ/dgamma_t / (2 mu_t + d lam_t) give dJ/dp_t = gamma_t (2 mu' + d lam') C_t - (2 mu' A_t + lam' B_t).
 // (carrying capacity 1, as in the forward kernels: the reaction weights of k_corner_weights are rho |T| d!/(d+3)!.)
 #include "glims_internal.h"
+#include "hessian_plan.h"
 #include "lame_derivs.h"
 
 #include <algorithm>
@@ -23,10 +24,6 @@
 #include <omp.h>
 
 namespace {
-
-// labels per sensitivity launch: per-thread accumulators live in registers (LT x 3 doubles)
-constexpr int GL_ADJ_LT = 8;
-constexpr int GL_ADJ_BLOCKS = 2048;   // fixed grid of the sensitivity pass: the reduction order does not depend on the mesh
 
 __device__ __forceinline__ double wsum(double v) {
 #pragma unroll
@@ -388,23 +385,56 @@ void mass_apply(glims_ctx* h, const double* x, double* y) {
   gl_launch_spmv(h, h->st, h->pat.n_slices, nullptr, h->vM.p, x, y, nullptr, nullptr, nullptr, nullptr, 0, nullptr);
 }
 
+// Sums that every rank holds a share of (hessian_plan.h: RowPart), from src (device, or one host scalar) into dst at the same
+// stride.  One GPU: the plain download.  Partitioned handles: every rank's W sums are gathered by an all-reduce of
+// [world][W] (`count` doubles, from the call's buffer table) with zeros outside the own row -- x + 0 is exact: whatever order
+// the transport adds in, every rank receives every row bit for bit -- and added in rank order on the host: the same bits on
+// every rank.  Reached by every rank, also after a failed solve (the statuses are global; the parts are the same on every
+// rank: the caller's outputs are SPMD).
+struct SumPart {
+  RowPart lay;
+  const double* src;
+  double* dst;
+  bool host_src = false;
+};
+void gather_label_sums(glims_ctx* h, const std::vector<SumPart>& parts, size_t count) {
+  if (h->world <= 1) {
+    for (const SumPart& p : parts)
+      if (p.lay.len)   // (the whole array, with the gaps between its runs)
+        GL_HIP(hipMemcpyAsync(p.dst, p.src, p.lay.chunks * p.lay.stride * sizeof(double), hipMemcpyDeviceToHost, h->st));
+    GL_HIP(hipStreamSynchronize(h->st));
+    return;
+  }
+  std::vector<RowPart> lay;
+  for (const SumPart& p : parts) lay.push_back(p.lay);
+  const size_t W = row_width(lay);
+  if (count < W * h->world) throw std::logic_error("adjoint: the gather of the per-label sums is larger than the call's table says");
+  dvec<double> all;
+  all.alloc_zero(count, h->st);
+  double* row = all.p + W * h->rank;
+  for (const SumPart& p : parts)
+    for (size_t c = 0; c < p.lay.chunks && p.lay.len; ++c, row += p.lay.len)
+      GL_HIP(hipMemcpyAsync(row, p.src + c * p.lay.stride, p.lay.len * sizeof(double),
+                            p.host_src ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, h->st));
+  if (!parts.empty() && parts[0].host_src) GL_HIP(hipStreamSynchronize(h->st));
+  gl_allreduce_bulk(h, all.p, W * h->world);
+  std::vector<double> rows(W * h->world), sum(W);
+  if (W) GL_HIP(hipMemcpyAsync(rows.data(), all.p, rows.size() * sizeof(double), hipMemcpyDeviceToHost, h->st));
+  GL_HIP(hipStreamSynchronize(h->st));
+  add_rows_in_rank_order(h->world, W, rows.data(), sum.data());
+  std::vector<double*> dst;
+  for (const SumPart& p : parts) dst.push_back(p.dst);
+  scatter_row(lay, sum.data(), dst.data());
+}
+
 // The stored image terms (glims_adjoint_image_terms) that observe `step`, in their list order, after the step's nodal terms:
 // g += P^T r of each, J += 1/2 w sum_p q_p (h(v_p) - t_p)^2; with P > 0 also dg_j += P^T r2_j for the Hessian's directions
 // dc (column-major [P][ld]).  No stored term: no launch.  Partitioned handles: a rank sums the points it COUNTS
 // (glims_sampler_resolve), the ranks' sums are gathered and added in rank order -- one small all-reduce per term that observes
 // the step, made by every rank (the stored list is SPMD: gl_adjoint_gradient has checked it).
 double sum_over_ranks(glims_ctx* h, double mine) {
-  // [world] with zeros outside the own entry: x + 0 is exact, every rank receives every entry bit for bit
-  dvec<double> all;
-  all.alloc_zero((size_t)h->world, h->st);
-  GL_HIP(hipMemcpyAsync(all.p + h->rank, &mine, sizeof(double), hipMemcpyHostToDevice, h->st));
-  GL_HIP(hipStreamSynchronize(h->st));
-  gl_allreduce_bulk(h, all.p, (size_t)h->world);
-  std::vector<double> rows((size_t)h->world);
-  GL_HIP(hipMemcpyAsync(rows.data(), all.p, rows.size() * sizeof(double), hipMemcpyDeviceToHost, h->st));
-  GL_HIP(hipStreamSynchronize(h->st));
   double t = 0.0;
-  for (int r = 0; r < h->world; ++r) t += rows[(size_t)r];
+  gather_label_sums(h, {{{1, 1, 1}, &mine, &t, true}}, (size_t)h->world);
   return t;
 }
 
@@ -521,31 +551,52 @@ void build_cell_nodes(glims_ctx* h) {
   }
 }
 
+// What sizes a call (hessian_plan.h) but for the flags of the E / nu part, which the caller derives from its arguments
+HessShape adjoint_shape(glims_ctx* h, int n_terms, const glims_misfit* terms, int P) {
+  HessShape s;
+  s.N = (int)h->adj.traj.size() - 1;
+  s.P = P;
+  s.dim = h->dim;
+  s.n_labels = h->n_labels;
+  s.world = h->world;
+  s.n_nodes = h->n_nodes;
+  s.n_cells = h->n_cells;
+  s.total_entries = h->pat.total_entries;
+  s.n_send = h->n_send;
+  s.spmm_blocks = P > 0 ? gl_spmm_blocks(h) : 0;
+  for (int k = 0; k < n_terms; ++k) s.term_is_u.push_back(terms[k].kind == GLIMS_MISFIT_U_L2);
+  s.any_u = hess_any_u(s.term_is_u, !h->dimg_terms.empty());
+  return s;
+}
+
+// v = the call's buffer `name` (the k-th of that name), zeroed unless told otherwise; a buffer the call does not have
+// (count 0) stays empty
+template <class T>
+void take(glims_ctx* h, const std::vector<HessBuffer>& table, const char* name, dvec<T>& v, bool zero = true, int k = 0) {
+  const HessBuffer& b = hess_buffer(table, name, k);
+  if (b.elem != sizeof(T)) throw std::logic_error(std::string("adjoint: element size of buffer '") + name + "'");
+  if (zero) v.alloc_zero(b.count, h->st);
+  else v.alloc(b.count);
+}
+
 // the work vectors, targets (internal numbering) and cell-vertex map of one gradient / Hessian call
 template <int D>
-void adjoint_setup(glims_ctx* h, int n_terms, const glims_misfit* terms, bool elastic, AdjWork& wk) {
-  const int64_t nn = h->n_nodes, nd = nn * D;
-  const size_t ne = (size_t)h->pat.total_entries;
-  wk.vA.alloc(ne);
-  wk.dinv.alloc((size_t)nn);
-  for (auto* v : {&wk.lam, &wk.lam_next, &wk.rhs, &wk.g, &wk.r, &wk.u, &wk.w, &wk.p, &wk.s, &wk.e, &wk.hp, &wk.Me, &wk.tmp})
-    v->alloc_zero((size_t)nn, h->st);
-  wk.qcell.alloc_zero((size_t)h->n_cells, h->st);
-  wk.part.alloc_zero((size_t)GL_ADJ_BLOCKS * GL_ADJ_LT * 2, h->st);
-  wk.sums.alloc_zero((size_t)GL_MAX_LABELS * 3, h->st);
-  if (elastic) wk.esums.alloc_zero((size_t)GL_MAX_LABELS * 2, h->st);
-  wk.stage.alloc_zero((size_t)nd, h->st);
-  bool any_u = !h->dimg_terms.empty();   // (a deformed image term observes u_k as a displacement term does)
-  for (int k = 0; k < n_terms; ++k) any_u = any_u || terms[k].kind == GLIMS_MISFIT_U_L2;
-  if (any_u)
-    for (auto* v : {&wk.uk, &wk.murhs, &wk.mu, &wk.mr, &wk.mu_, &wk.mw, &wk.mp, &wk.ms, &wk.mKx})
-      v->alloc_zero((size_t)nd, h->st);
+void adjoint_setup(glims_ctx* h, const std::vector<HessBuffer>& table, int n_terms, const glims_misfit* terms, AdjWork& wk) {
+  take(h, table, "vA", wk.vA, false);
+  take(h, table, "dinv", wk.dinv, false);
+  const std::pair<const char*, dvec<double>*> vecs[] = {
+      {"lam", &wk.lam}, {"lam_next", &wk.lam_next}, {"rhs", &wk.rhs}, {"g", &wk.g}, {"r", &wk.r}, {"u", &wk.u}, {"w", &wk.w},
+      {"p", &wk.p}, {"s", &wk.s}, {"e", &wk.e}, {"hp", &wk.hp}, {"Me", &wk.Me}, {"tmp", &wk.tmp}, {"qcell", &wk.qcell},
+      {"part", &wk.part}, {"sums", &wk.sums}, {"esums", &wk.esums}, {"stage", &wk.stage},
+      // with an observed displacement (a deformed image term observes u_k as a displacement term does)
+      {"uk", &wk.uk}, {"murhs", &wk.murhs}, {"mu", &wk.mu}, {"mr", &wk.mr}, {"mu_", &wk.mu_}, {"mw", &wk.mw}, {"mp", &wk.mp},
+      {"ms", &wk.ms}, {"mKx", &wk.mKx}};
+  for (const auto& v : vecs) take(h, table, v.first, *v.second);
   // targets -> internal numbering
   for (int k = 0; k < n_terms; ++k) {
-    const int bs = terms[k].kind == GLIMS_MISFIT_U_L2 ? D : 1;
     wk.targets.push_back(std::make_unique<dvec<double>>());
-    wk.targets.back()->alloc_zero((size_t)nn * bs, h->st);
-    upload_permuted(h, wk, terms[k].target, bs, wk.targets.back()->p);
+    take(h, table, "target", *wk.targets.back(), true, k);
+    upload_permuted(h, wk, terms[k].target, terms[k].kind == GLIMS_MISFIT_U_L2 ? D : 1, wk.targets.back()->p);
   }
   build_cell_nodes<D>(h);
 }
@@ -738,26 +789,6 @@ struct BackwardSweep {
   }
 };
 
-// The totals (A_t, B_t, C_t) of label l from the gradient's sums: sums3 [L][3] (D, rho, gamma), esums [L][2] (A, B).
-// C_t = sum_k int_t |T|/(d+1) div mu_k sum_a c_k,a = (dJ/dgamma sum) / (2 mu_t + d lam_t): mode 1's sum carries the factor
-ElasticSums elastic_totals(const glims_ctx* h, int dim, int l, const double* sums3, const double* esums) {
-  const double* mh = h->mat_host.data();
-  const double den = 2.0 * mh[3 * GL_MAX_LABELS + l] + dim * mh[4 * GL_MAX_LABELS + l];
-  return {esums[l * 2 + 0], esums[l * 2 + 1], den != 0.0 ? sums3[l * 3 + 2] / den : 0.0};
-}
-
-// dJ/dE_t, dJ/dnu_t in label order (lame_derivs.h)
-void write_elastic_labels(const glims_ctx* h, int dim, const double* sums3, const double* esums, double* dE, double* dnu) {
-  const double* mh = h->mat_host.data();
-  for (int l = 0; l < h->n_labels; ++l) {
-    const double gam = mh[2 * GL_MAX_LABELS + l];
-    const LameDerivs d = lame_derivs(mh[5 * GL_MAX_LABELS + l], mh[6 * GL_MAX_LABELS + l]);
-    const ElasticSums tot = elastic_totals(h, dim, l, sums3, esums);
-    if (dE) dE[l] = elastic_gradient_row(dim, gam, d.m_E, d.l_E, tot);
-    if (dnu) dnu[l] = elastic_gradient_row(dim, gam, d.m_nu, d.l_nu, tot);
-  }
-}
-
 template <int D>
 int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_out, double* dD, double* drho,
                double* dgamma, double* dc0, double* dE, double* dnu) {
@@ -765,7 +796,10 @@ int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_o
   const double t0 = omp_get_wtime();
   AdjWork wk;
   const bool elastic = dE || dnu;   // the E / nu pass runs only when asked for
-  adjoint_setup<D>(h, n_terms, terms, elastic, wk);
+  HessShape shape = adjoint_shape(h, n_terms, terms, 0);
+  shape.el = elastic;
+  const std::vector<HessBuffer> table = hessian_buffers(shape);
+  adjoint_setup<D>(h, table, n_terms, terms, wk);
   ForwardGuard guard(h, wk);
   BackwardSweep<D> sw(h, wk, n_terms, terms, elastic);
   for (int step = sw.last_step(); step >= 0; --step) {
@@ -788,33 +822,12 @@ int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_o
   }
   const int status = sw.status;
   // sums: [L][3] (D, rho, gamma), then [L][2] (A, B) when the E / nu pass ran
-  const size_t L3 = (size_t)h->n_labels * 3, L2 = elastic ? (size_t)h->n_labels * 2 : 0, W = L3 + L2;
-  std::vector<double> sums(W);
-  if (h->world <= 1) {
-    GL_HIP(hipMemcpyAsync(sums.data(), wk.sums.p, L3 * sizeof(double), hipMemcpyDeviceToHost, h->st));
-    if (L2) GL_HIP(hipMemcpyAsync(sums.data() + L3, wk.esums.p, L2 * sizeof(double), hipMemcpyDeviceToHost, h->st));
-    GL_HIP(hipStreamSynchronize(h->st));
-  } else {
-    // Every rank's W = 3 (or 5) x n_labels sums, gathered by an all-reduce of [world][W] with zeros outside the own row
-    // (x + 0 is exact: whatever order the transport adds in, every rank receives every row bit for bit), then added in rank
-    // order on the host: the same bits on every rank.  Reached by every rank, also after a failed solve (the statuses are
-    // global; `elastic` is the same on every rank: the caller's outputs are SPMD).
-    dvec<double> all;
-    all.alloc_zero(std::max<size_t>(1, W * h->world), h->st);
-    if (L3) GL_HIP(hipMemcpyAsync(all.p + W * h->rank, wk.sums.p, L3 * sizeof(double), hipMemcpyDeviceToDevice, h->st));
-    if (L2) GL_HIP(hipMemcpyAsync(all.p + W * h->rank + L3, wk.esums.p, L2 * sizeof(double), hipMemcpyDeviceToDevice, h->st));
-    gl_allreduce_bulk(h, all.p, W * h->world);
-    std::vector<double> rows(W * h->world);
-    if (W) GL_HIP(hipMemcpyAsync(rows.data(), all.p, rows.size() * sizeof(double), hipMemcpyDeviceToHost, h->st));
-    GL_HIP(hipStreamSynchronize(h->st));
-    for (size_t k = 0; k < W; ++k) {
-      double t = 0.0;
-      for (int r = 0; r < h->world; ++r) t += rows[W * r + k];
-      sums[k] = t;
-    }
-  }
+  const std::vector<RowPart> lay = label_row_parts(h->n_labels, elastic, 0);
+  std::vector<double> sums(lay[0].len), esums(lay[1].len);
+  gather_label_sums(h, {{lay[0], wk.sums.p, sums.data()}, {lay[1], wk.esums.p, esums.data()}},
+                    hess_buffer(table, "gather").count);
   sw.write_labels(sums.data(), dD, drho, dgamma);
-  if (elastic) write_elastic_labels(h, D, sums.data(), sums.data() + L3, dE, dnu);
+  if (elastic) write_elastic_labels(h->mat_host.data(), h->n_labels, D, sums.data(), esums.data(), dE, dnu);
   *J_out = sw.J;
   a.gradients++;
   a.ms_backward += 1e3 * (omp_get_wtime() - t0);
@@ -825,7 +838,6 @@ int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_o
 // P <= GL_HESS_MAXDIR directions per call.  Per-label direction tables dir[p][3][GL_MAX_LABELS] = (dD, drho, dgamma); node
 // vectors of the directions are stored column after column, [p][n_nodes].  Every column runs through the same arithmetic
 // whatever P is: column p of a P-direction call has the bits of a one-direction call.
-constexpr int GL_HESS_MAXDIR = 8;
 
 // Row-owned right-hand-side terms of the tangent-linear (MODE 0) and the second-order adjoint (MODE 1) solves, P columns per
 // launch, atomics-free through the incidence lists (each row adds its cells' shares in list order).  Cell T of label t,
@@ -1254,8 +1266,8 @@ int rd_solve(glims_ctx* h, AdjWork& wk, const uint8_t* fxc, bool rd_mg, int rd_d
 // column is frozen (no update of x, r or p).  The 2P dot products (r.z, r.r) of an iteration come from one fixed-order
 // reduction (block partials on a fixed grid, then one wave per sum), p.Ap from k_spmm's fused partials: no float atomics,
 // and the arithmetic of column j does not depend on P.  State sc[6][P]: rz, rr, alpha, beta, tol, pq.
-constexpr int GL_MP_BLOCKS = 1024;
 enum { MP_RZ = 0, MP_RR, MP_ALPHA, MP_BETA, MP_TOL, MP_PQ, MP_N };
+static_assert(MP_N == GL_MP_SCALARS, "hessian_plan.h sizes the scalar buffer");
 
 // column-major [P][ld] <-> interleaved [n][P]; fixed rows give 0 (pack)
 template <int P>
@@ -1556,393 +1568,368 @@ struct AdjCountGuard {
   }
 };
 
-// Device memory of a Hessian call on top of the trajectory, and what is free now: the stored tangent-linear states dominate,
-// 8 P B per node and recorded state (see glims_hip.h)
-// el_dirs (glims_adjoint_hessian_full with a direction in E / nu): 2 P more vectors of dim x n_nodes (dK_p u_k, dK_p mu_k)
-bool hessian_fits(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, std::string* why, bool el_dirs = false) {
-  const int64_t nn = h->n_nodes, nd = nn * h->dim;
-  const int N = (int)h->adj.traj.size() - 1;
-  bool any_u = false;
-  for (int k = 0; k < n_terms; ++k) any_u = any_u || terms[k].kind == GLIMS_MISFIT_U_L2;
-  const size_t need = 8 * ((size_t)(N + 1) * P * nn + (size_t)(9 * P + 16) * nn + (any_u ? (size_t)14 * nd : 0) +
-                           (any_u && el_dirs ? (size_t)2 * P * nd : 0) + (size_t)2 * h->n_cells +
-                           (size_t)h->pat.total_entries);
+// The arguments of a Hessian call.  el (glims_adjoint_hessian_full, one GPU; nullptr otherwise): the E / nu directions,
+// gradient rows and products.
+struct ElasticSecond {
+  const double *dir_E, *dir_nu;
+  double *dE, *dnu, *hv_E, *hv_nu;
+};
+struct HessCall {
+  int n_terms;
+  const glims_misfit* terms;
+  int P;
+  const double *dir_D, *dir_rho, *dir_gamma, *dir_c0;
+  double *J, *dD, *drho, *dgamma, *dc0, *hv_D, *hv_rho, *hv_gamma, *hv_c0, *stats;
+  bool mem_checked = false;   // glims_adjoint_hessian_spmd has taken the memory verdict of all ranks
+  const ElasticSecond* el = nullptr;
+};
+
+HessShape hessian_shape(glims_ctx* h, const HessCall& c) {
+  HessShape s = adjoint_shape(h, c.n_terms, c.terms, c.P);
+  s.el = c.el != nullptr;
+  s.el_dirs = hess_el_dirs(s.el, s.any_u, c.el && (c.el->dir_E || c.el->dir_nu));
+  s.el_sums = hess_el_sums(s.el, s.any_u, c.el && (c.el->hv_E || c.el->hv_nu));
+  return s;
+}
+
+// Device memory of a Hessian call on top of the trajectory -- the sum of its buffer table (hessian_plan.h) -- and what is
+// free now: the stored tangent-linear states dominate, 8 P B per node and recorded state (see glims_hip.h)
+bool hessian_fits(const HessShape& s, std::string* why) {
+  const size_t need = hessian_bytes(s);
   size_t fr = 0, tot = 0;
   GL_HIP(hipMemGetInfo(&fr, &tot));
   if (need <= fr) return true;
-  *why = "glims_adjoint_hessian: " + std::to_string(P) + " directions over " + std::to_string(N + 1) +
+  *why = "glims_adjoint_hessian: " + std::to_string(s.P) + " directions over " + std::to_string(s.N + 1) +
          " recorded states need about " + std::to_string(need >> 20) + " MiB of device memory, " + std::to_string(fr >> 20) +
          " MiB are free";
   return false;
 }
 
-// The tangent-linear sweep, then gradient_t's backward sweep (BackwardSweep: J and the gradient keep its bits, which
-// tests/test_gpu_adjoint_hessian.py checks) with the second-order adjoint work of every direction between its parts.
-// Partitioned handles (glims_adjoint_hessian_spmd, which has taken the memory verdict of all ranks: mem_checked): dc_n, nu_n,
-// du and dmu exchange their ghosts after their solves, hd and ue before the mass product, the per-label sums count a cell on
-// one rank (AdjointState::counted) and are gathered with the gradient's.
-// el (glims_adjoint_hessian_full, one GPU; nullptr otherwise): the E / nu directions, gradient rows and products.  The sweep
-// then runs the gradient's E / nu pass (mode 2) as glims_adjoint_gradient_full does; with a direction in E / nu (el_dirs) du
-// and dmu take -dK u_k and -dK mu_k on their right-hand sides, dG carries its E / nu part, and k_hesens sums the E / nu rows.
-// Without one, every launch of the other outputs is the one glims_adjoint_hessian issues: the same bits.
-struct ElasticSecond {
-  const double *dir_E, *dir_nu;
-  double *dE, *dnu, *hv_E, *hv_nu;
-};
-template <int D>
-int hessian_t(glims_ctx* h, int n_terms, const glims_misfit* terms, int P, const double* dir_D, const double* dir_rho,
-              const double* dir_gamma, const double* dir_c0, double* J_out, double* dD, double* drho, double* dgamma,
-              double* dc0, double* hv_D, double* hv_rho, double* hv_gamma, double* hv_c0, double* stats,
-              bool mem_checked, const ElasticSecond* el = nullptr) {
-  AdjointState& a = h->adj;
-  const int64_t n = h->n_own, nn = h->n_nodes, nd = nn * D;
-  const int N = (int)a.traj.size() - 1;
-  const int L = h->n_labels;
-  const double t0 = omp_get_wtime();
-  bool any_u = false;
-  for (int k = 0; k < n_terms; ++k) any_u = any_u || terms[k].kind == GLIMS_MISFIT_U_L2;
-  if (!mem_checked) {
-    std::string why;
-    if (!hessian_fits(h, n_terms, terms, P, &why, el && (el->dir_E || el->dir_nu))) throw glims_error(GLIMS_E_HIP, why);
-  }
-  const bool el_dirs = el && any_u && (el->dir_E || el->dir_nu);
-  const bool el_sums = el && any_u && (el->hv_E || el->hv_nu);   // also without el_dirs: the mixed rows H[E, D] ... are not 0
-  AdjCountGuard counts(a);
+// Every device buffer of a Hessian call, allocated from the call's table: the first-order work vectors (filled by
+// adjoint_setup), the P-column solver's, the direction tables and the second-order vectors.  Node vectors of the directions
+// are stored column after column, [p][n_nodes].
+struct HessMemory {
+  const int P;
+  const int64_t nn, nd;
+  const std::vector<HessBuffer> table;
   AdjWork wk;
-  adjoint_setup<D>(h, n_terms, terms, el != nullptr, wk);
-  // direction tables; material copies with the gamma row replaced by dgamma_p (the dgamma_t G_t^T mu pass)
-  const size_t LM = GL_MAX_LABELS;
-  std::vector<double> dir((size_t)P * 3 * LM, 0.0), dmat((size_t)P * 5 * LM, 0.0);
-  for (int p = 0; p < P; ++p) {
-    for (int l = 0; l < L; ++l) {
-      dir[(p * 3 + 0) * LM + l] = dir_D ? dir_D[(size_t)p * L + l] : 0.0;
-      dir[(p * 3 + 1) * LM + l] = dir_rho ? dir_rho[(size_t)p * L + l] : 0.0;
-      dir[(p * 3 + 2) * LM + l] = dir_gamma ? dir_gamma[(size_t)p * L + l] : 0.0;
+  MultiPcg mp;
+  dvec<double> d_dir, d_dmat, d_dlame, d_dkap, d_dmat2, dKu, dKmu, hesums, hepart;
+  dvec<double> dcs, nu, nu_next, dg, hrhs, hd, Mhd, hsums, hpart, hqcell, urhs, du, dmurhs, dmu, ue, uMe;
+
+  HessMemory(glims_ctx* h, const HessShape& s)
+      : P(s.P), nn(s.n_nodes), nd(s.n_nodes * s.dim), table(hessian_buffers(s)) {
+    const std::pair<const char*, dvec<double>*> vecs[] = {
+        {"dKu", &dKu}, {"dKmu", &dKmu}, {"hesums", &hesums}, {"hepart", &hepart}, {"dcs", &dcs}, {"nu", &nu},
+        {"nu_next", &nu_next}, {"dg", &dg}, {"hrhs", &hrhs}, {"hd", &hd}, {"Mhd", &Mhd}, {"hsums", &hsums}, {"hpart", &hpart},
+        {"hqcell", &hqcell}, {"urhs", &urhs}, {"du", &du}, {"dmurhs", &dmurhs}, {"dmu", &dmu}, {"ue", &ue}, {"uMe", &uMe},
+        {"mp.X", &mp.X}, {"mp.B", &mp.B}, {"mp.R", &mp.R}, {"mp.Pv", &mp.Pv}, {"mp.Q", &mp.Q}, {"mp.part", &mp.part},
+        {"mp.part2", &mp.part2}, {"mp.sendbuf", &mp.sendbuf}, {"mp.rows", &mp.rows}};
+    for (const auto& v : vecs) take(h, table, v.first, *v.second);
+    // written before they are read: the direction tables (upload_directions) and the solver's scalars (mp_solve_t)
+    const std::pair<const char*, dvec<double>*> filled[] = {{"d_dir", &d_dir}, {"d_dmat", &d_dmat}, {"d_dlame", &d_dlame},
+                                                            {"d_dkap", &d_dkap}, {"d_dmat2", &d_dmat2}, {"mp.sc", &mp.sc}};
+    for (const auto& v : filled) take(h, table, v.first, *v.second, false);
+    take(h, table, "mp.done", mp.done, false);
+    take(h, table, "mp.its", mp.its, false);
+    take(h, table, "mp.flags", mp.flags, false);
+  }
+  void upload_directions(glims_ctx* h, const HessDirections& d) {
+    const std::pair<dvec<double>*, const std::vector<double>*> tabs[] = {
+        {&d_dir, &d.dir}, {&d_dmat, &d.dmat}, {&d_dlame, &d.dlame}, {&d_dkap, &d.dkap}, {&d_dmat2, &d.dmat2}};
+    for (const auto& t : tabs) {
+      if (t.first->n != t.second->size()) throw std::logic_error("adjoint: a direction table and its buffer differ in size");
+      t.first->upload(*t.second, h->st);
     }
-    std::copy(h->mat_host.begin(), h->mat_host.begin() + 5 * LM, dmat.begin() + (size_t)p * 5 * LM);
-    std::copy(dir.begin() + (p * 3 + 2) * LM, dir.begin() + (p * 3 + 3) * LM, dmat.begin() + ((size_t)p * 5 + 2) * LM);
   }
-  dvec<double> d_dir, d_dmat, dcs, nu, nu_next, dg, hrhs, hd, Mhd, hsums, hpart, hqcell;
-  dvec<double> urhs, du, dmurhs, dmu, ue, uMe;
-  d_dir.upload(dir, h->st);
-  d_dmat.upload(dmat, h->st);
-  // E / nu directions: (dm, dl)_p per label [P][2][LM]; dkap_p = gamma (2 dm_p + d dl_p) [P][LM] (the E / nu part of dG c);
-  // material copies with the Lame rows replaced by (dm_p, dl_p) (the E / nu part of dG^T mu through mode 1 and k_gt_rows)
-  std::vector<double> dlame, dkap, dmat2;
-  dvec<double> d_dlame, d_dkap, d_dmat2, dKu, dKmu, hesums, hepart;
-  if (el_dirs) {
-    dlame.assign((size_t)P * 2 * LM, 0.0);
-    dkap.assign((size_t)P * LM, 0.0);
-    dmat2.assign((size_t)P * 5 * LM, 0.0);
-    const double* mh = h->mat_host.data();
-    for (int p = 0; p < P; ++p) {
-      std::copy(h->mat_host.begin(), h->mat_host.begin() + 5 * LM, dmat2.begin() + (size_t)p * 5 * LM);
-      for (int l = 0; l < L; ++l) {
-        const LameDerivs d = lame_derivs(mh[5 * LM + l], mh[6 * LM + l]);
-        double dm, dl;
-        lame_direction(d, el->dir_E ? el->dir_E[(size_t)p * L + l] : 0.0, el->dir_nu ? el->dir_nu[(size_t)p * L + l] : 0.0,
-                       &dm, &dl);
-        dlame[((size_t)p * 2 + 0) * LM + l] = dm;
-        dlame[((size_t)p * 2 + 1) * LM + l] = dl;
-        dkap[(size_t)p * LM + l] = mh[2 * LM + l] * (2.0 * dm + D * dl);
-      }
-      std::copy(dlame.begin() + (size_t)p * 2 * LM, dlame.begin() + ((size_t)p * 2 + 2) * LM,
-                dmat2.begin() + ((size_t)p * 5 + 3) * LM);
-    }
-    d_dlame.upload(dlame, h->st);
-    d_dkap.upload(dkap, h->st);
-    d_dmat2.upload(dmat2, h->st);
-    dKu.alloc_zero((size_t)P * nd, h->st);
-    dKmu.alloc_zero((size_t)P * nd, h->st);
-  }
-  if (el_sums) {
-    hesums.alloc_zero((size_t)P * LM * 2, h->st);
-    hepart.alloc_zero((size_t)GL_ADJ_BLOCKS * GL_ADJ_LT * 2, h->st);
-  }
-  dcs.alloc_zero((size_t)(N + 1) * P * nn, h->st);   // dc_n of direction p at dcs[(n P + p) nn]
-  for (auto* v : {&nu, &nu_next, &dg, &hrhs}) v->alloc_zero((size_t)P * nn, h->st);
-  hd.alloc_zero((size_t)nn, h->st);
-  Mhd.alloc_zero((size_t)nn, h->st);
-  hsums.alloc_zero((size_t)P * LM * 3, h->st);
-  hpart.alloc_zero((size_t)GL_ADJ_BLOCKS * GL_ADJ_LT * 2, h->st);
-  hqcell.alloc_zero((size_t)h->n_cells, h->st);
-  if (any_u) {
-    for (auto* v : {&urhs, &du, &dmurhs, &dmu}) v->alloc_zero((size_t)nd, h->st);
-    ue.alloc_zero((size_t)nn, h->st);
-    uMe.alloc_zero((size_t)nn, h->st);
-  }
-  const bool part = h->world > 1;
-  const uint8_t* counted = part ? a.counted.p : nullptr;
-  // ghosts of P vectors stored column after column (no-ops on one GPU)
-  auto exchange_cols = [&](double* v) {
-    for (int p = 0; part && p < P; ++p) gl_halo_exchange(h, v + (size_t)p * nn, 1);
-  };
-  for (int p = 0; dir_c0 && p < P; ++p) upload_permuted(h, wk, dir_c0 + (size_t)p * nn, 1, dcs.p + (size_t)p * nn);
-  auto dc_of = [&](int step, int p) { return dcs.p + ((size_t)step * P + p) * nn; };
-  MultiPcg mp;   // the P-column solver's interleaved vectors [n_nodes][P] and scalars
-  for (auto* v : {&mp.X, &mp.B, &mp.R, &mp.Pv, &mp.Q}) v->alloc_zero((size_t)P * nn, h->st);
-  mp.part.alloc_zero((size_t)gl_spmm_blocks(h) * P, h->st);
-  mp.part2.alloc_zero((size_t)GL_MP_BLOCKS * 2 * P, h->st);
-  if (part) {
-    mp.sendbuf.alloc_zero((size_t)std::max<int64_t>(h->n_send, 1) * P, h->st);
-    mp.rows.alloc_zero((size_t)h->world * 2 * P, h->st);
-  }
-  ForwardGuard guard(h, wk);
-  BackwardSweep<D> sw(h, wk, n_terms, terms, el != nullptr);
-  if (dir_c0) exchange_cols(dcs.p);   // (the caller's ghost entries are not trusted; under the guard: glims_stats stay)
-  const uint8_t* fxc = sw.fxc;
-  const DevPattern& pt = h->pat;
-  const double dt = h->opt.dt;
+  double* col(dvec<double>& v, int p) const { return v.p + (size_t)p * nn; }                 // column p of nu, dg, hrhs ...
+  double* dc_of(int step, int p) const { return dcs.p + ((size_t)step * P + p) * nn; }       // dc_step of direction p
+  double* hsums_of(int p) const { return hsums.p + (size_t)p * GL_MAX_LABELS * 3; }
+  double* hesums_of(int p) const { return hesums.p + (size_t)p * GL_MAX_LABELS * 2; }
+  const double* dgamma_of(int p) const { return d_dir.p + ((size_t)p * 3 + 2) * GL_MAX_LABELS; }
+  const double* dmat_of(const dvec<double>& t, int p) const { return t.p + (size_t)p * 5 * GL_MAX_LABELS; }
+};
+
+// The second-order work of a Hessian call, phase by phase, between the parts of gradient_t's backward sweep (BackwardSweep:
+// J and the gradient keep its bits, which tests/test_gpu_adjoint_hessian.py checks).  Every phase stops the call by setting
+// sw.status.
+// Partitioned handles: dc_n, nu_n, du and dmu exchange their ghosts after their solves, hd and ue before the mass product,
+// the per-label sums count a cell on one rank (AdjointState::counted) and are gathered with the gradient's.
+// el: the sweep runs the gradient's E / nu pass (mode 2) as glims_adjoint_gradient_full does; with a direction in E / nu
+// (el_dirs) du and dmu take -dK u_k and -dK mu_k on their right-hand sides, dG carries its E / nu part, and k_hesens sums the
+// E / nu rows.  Without one, every launch of the other outputs is the one glims_adjoint_hessian issues: the same bits.
+template <int D>
+struct HessianSweep {
+  glims_ctx* h;
+  const HessCall& call;
+  const HessShape& s;
+  HessMemory& m;
+  BackwardSweep<D>& sw;
+  AdjWork& wk;
+  const DevPattern& pt;
+  const int P, L, N;
+  const int64_t n, nn, nd;
+  const double dt;
+  const uint8_t *fxc, *counted;
   int64_t tlm_its = 0, soa_its = 0, extra_mech = 0;
-  int& status = sw.status;
-  // 1. tangent-linear sweep: A(c_n) dc_n = M dc_{n-1} - dt sum_t dD_t K_t c_n - dt sum_t drho_t int_t (c_n^2 - c_n) phi
-  for (int step = 1; step <= N && status == GLIMS_OK; ++step) {
-    gl_halo_exchange(h, a.traj[step]->p, 1);   // (as BackwardSweep::begin_step)
-    const double* c = a.traj[step]->p;
+
+  HessianSweep(glims_ctx* h_, const HessCall& c, const HessShape& s_, HessMemory& m_, BackwardSweep<D>& sw_)
+      : h(h_), call(c), s(s_), m(m_), sw(sw_), wk(m_.wk), pt(h_->pat), P(s_.P), L(s_.n_labels), N(s_.N), n(h_->n_own),
+        nn(m_.nn), nd(m_.nd), dt(h_->opt.dt), fxc(sw_.fxc), counted(s_.world > 1 ? h_->adj.counted.p : nullptr) {}
+
+  // ghosts of P vectors stored column after column (no-ops on one GPU)
+  void exchange_cols(double* v) {
+    for (int p = 0; s.world > 1 && p < P; ++p) gl_halo_exchange(h, v + (size_t)p * nn, 1);
+  }
+  // y = M x (+ add); fixed: the rows of the constrained nodes are left out
+  void mass_col(const double* x, const double* add, double* y, const uint8_t* fixed) {
+    gl_launch_spmv(h, h->st, pt.n_slices, nullptr, h->vM.p, x, y, fixed, add, nullptr, nullptr, 0, nullptr);
+  }
+  // 0 on the constrained nodes of every column of v
+  void zero_fixed_cols(double* v) {
+    for (int p = 0; fxc && p < P; ++p) {
+      hipLaunchKernelGGL(k_zero_fixed, dim3(grid_of(n)), dim3(256), 0, h->st, n, fxc, v + (size_t)p * nn, (const double*)nullptr);
+      GL_CHECK_LAUNCH();
+    }
+  }
+  template <int MODE>
+  void hess_rows(const double* c, const double* lam, const double* dc) {
+    hipLaunchKernelGGL((k_hess_rows<D, MODE>), dim3(grid_of(n)), dim3(256), 0, h->st, n, P, nn, pt.cslice_ptr.p, pt.cslots.p,
+                       pt.celem.p, pt.diag_k.p, h->adj.cell_nodes.p, h->egeo.p, h->label.p, h->mat.p, m.d_dir.p, dt, c, lam, dc,
+                       m.hrhs.p);
+    GL_CHECK_LAUNCH();
+  }
+  // mode 1 of the sensitivity pass into the directions' own qcell and partials: qcell of every cell, into `sums` (if any) the
+  // cells this rank counts
+  void gt_pass(const double* mat, const double* x, const double* v, double* sums) {
+    sens_pass<D>(h, 1, mat, x, v, counted, m.hqcell.p, m.hpart.p, sums, 3, 2);
+  }
+  void gt_rows(double* dgp) {   // dg_p += the rows' sums of hqcell
+    hipLaunchKernelGGL(k_gt_rows, dim3(grid_of(n)), dim3(256), 0, h->st, n, pt.cslice_ptr.p, pt.celem.p, m.hqcell.p, dgp);
+    GL_CHECK_LAUNCH();
+  }
+
+  // A(c_n) dc_n = M dc_{n-1} - dt sum_t dD_t K_t c_n - dt sum_t drho_t int_t (c_n^2 - c_n) phi, all directions.
+  // Reads traj[step], dcs[step - 1], d_dir; writes the swapped-in A(c_n), hrhs, dcs[step].
+  void tangent_linear_step(int step) {
+    gl_halo_exchange(h, h->adj.traj[step]->p, 1);   // (as BackwardSweep::begin_step)
+    const double* c = h->adj.traj[step]->p;
     GL_HIP(hipMemsetAsync(wk.tmp.p, 0, (size_t)nn * sizeof(double), h->st));
     gl_rd_assemble(h, c, wk.tmp.p, nullptr, wk.w.p, nullptr, h->partials.p);
-    for (int p = 0; p < P; ++p)
-      gl_launch_spmv(h, h->st, pt.n_slices, nullptr, h->vM.p, dc_of(step - 1, p), hrhs.p + (size_t)p * nn, fxc, nullptr,
-                     nullptr, nullptr, 0, nullptr);
-    hipLaunchKernelGGL((k_hess_rows<D, 0>), dim3(grid_of(n)), dim3(256), 0, h->st, n, P, nn, pt.cslice_ptr.p, pt.cslots.p,
-                       pt.celem.p, pt.diag_k.p, a.cell_nodes.p, h->egeo.p, h->label.p, h->mat.p, d_dir.p, dt, c,
-                       (const double*)nullptr, (const double*)nullptr, hrhs.p);
-    GL_CHECK_LAUNCH();
-    for (int p = 0; p < P; ++p)
-      if (fxc)
-        hipLaunchKernelGGL(k_zero_fixed, dim3(grid_of(n)), dim3(256), 0, h->st, n, fxc, hrhs.p + (size_t)p * nn,
-                           (const double*)nullptr);
-    GL_CHECK_LAUNCH();
+    for (int p = 0; p < P; ++p) mass_col(m.dc_of(step - 1, p), nullptr, m.col(m.hrhs, p), fxc);
+    hess_rows<0>(c, nullptr, nullptr);
+    zero_fixed_cols(m.hrhs.p);
     // warm start from dc_{n-1} (its constrained entries -- dc_0 may have some -- start at 0)
-    GL_HIP(hipMemcpyAsync(dc_of(step, 0), dc_of(step - 1, 0), (size_t)P * nn * sizeof(double), hipMemcpyDeviceToDevice,
+    GL_HIP(hipMemcpyAsync(m.dc_of(step, 0), m.dc_of(step - 1, 0), (size_t)P * nn * sizeof(double), hipMemcpyDeviceToDevice,
                           h->st));
-    if (fxc)
-      for (int p = 0; p < P; ++p)
-        hipLaunchKernelGGL(k_zero_fixed, dim3(grid_of(n)), dim3(256), 0, h->st, n, fxc, dc_of(step, p),
-                           (const double*)nullptr);
-    status = rd_solve_cols(h, wk, mp, fxc, sw.rd_mg, sw.rd_deg, P, hrhs.p, dc_of(step, 0), nn, &tlm_its);
+    zero_fixed_cols(m.dc_of(step, 0));
+    sw.status = rd_solve_cols(h, wk, m.mp, fxc, sw.rd_mg, sw.rd_deg, P, m.hrhs.p, m.dc_of(step, 0), nn, &tlm_its);
     // the solve updates the owned rows: the next step's M dc, the row and cell passes of the second sweep read the ghosts
-    if (status == GLIMS_OK) exchange_cols(dc_of(step, 0));
+    if (sw.status == GLIMS_OK) exchange_cols(m.dc_of(step, 0));
   }
-  // 2. the first-order sweep with the second-order adjoint nu_n of every direction
-  for (int step = N; step >= 0 && status == GLIMS_OK; --step) {
-    const double* c = sw.begin_step(step);
-    GL_HIP(hipMemsetAsync(dg.p, 0, (size_t)P * nn * sizeof(double), h->st));
-    // after each concentration term, while wk.Me holds M (h - t):  dg_p += w (h' M(h' dc_p) + h'' M(h - t) dc_p)
-    const bool have_u = sw.nodal_terms(step, c, [&](const glims_misfit& tm) {
-      for (int p = 0; p < P; ++p) {
-        hipLaunchKernelGGL(k_misfit_dir, dim3(grid_of(n)), dim3(256), 0, h->st, n, tm.kind, tm.level, tm.smooth, c,
-                           dc_of(step, p), hd.p);
-        GL_CHECK_LAUNCH();
-        gl_halo_exchange(h, hd.p, 1);
-        mass_apply(h, hd.p, Mhd.p);
-        hipLaunchKernelGGL(k_misfit_second, dim3(grid_of(n)), dim3(256), 0, h->st, n, tm.kind, tm.level, tm.smooth,
-                           tm.weight, c, dc_of(step, p), wk.Me.p, Mhd.p, dg.p + (size_t)p * nn);
-        GL_CHECK_LAUNCH();
-      }
-    });
-    if (status != GLIMS_OK) break;
-    image_terms_of_step(h, step, c, wk.g.p, &sw.J, P, dc_of(step, 0), nn, dg.p);
-    gl_observable_terms_of_step(h, step, c, wk.g.p, &sw.J, P, dc_of(step, 0), nn, dg.p);
-    if (have_u) {
-      if (!sw.coupling_adjoint(c)) break;
-      // per direction: du = K_el^-1 (G dc + sum_t dgamma_t G_t c), dmu = K_el^-1 sum w M_vec du (0 on the constrained dofs);
-      // dg += G^T dmu + sum_t dgamma_t G_t^T mu;  H_gamma_t += dmu^T G_t c + mu^T G_t dc
-      // (mode 1 of the sensitivity pass into the direction's own qcell, partials and sums; qcell of every cell, the sums of
-      // the cells this rank counts)
-      auto gt_pass = [&](const double* mat, const double* x, const double* v, double* sums) {
-        sens_pass<D>(h, 1, mat, x, v, counted, hqcell.p, hpart.p, sums, 3, 2);
-      };
-      if (el_dirs) {   // dK_p u_k (u_k with its Dirichlet values: the lifting term is differentiated too) and dK_p mu_k
-        for (const auto& vy : {std::make_pair((const double*)wk.uk.p, dKu.p), std::make_pair((const double*)wk.mu.p, dKmu.p)}) {
-          hipLaunchKernelGGL(k_dkel_rows<D>, dim3(grid_of(n)), dim3(256), 0, h->st, n, P, nd, pt.cslice_ptr.p, pt.cslots.p,
-                             pt.celem.p, pt.diag_k.p, a.cell_nodes.p, h->egeo.p, h->label.p, d_dlame.p, vy.first, vy.second);
-          GL_CHECK_LAUNCH();
-        }
-      }
-      for (int p = 0; p < P && status == GLIMS_OK; ++p) {
-        double* dgp = dg.p + (size_t)p * nn;
-        double* hs = hsums.p + (size_t)p * LM * 3;
-        int64_t its = 0;
-        if (el_dirs) {   // G dc + dG c - dK u_k
-          hipLaunchKernelGGL((k_gdir_rows<D, true>), dim3(grid_of(n)), dim3(256), 0, h->st, n, pt.cslice_ptr.p, pt.cslots.p,
-                             pt.celem.p, pt.diag_k.p, a.cell_nodes.p, h->egeo.p, h->label.p, h->mat.p,
-                             d_dir.p + (p * 3 + 2) * LM, d_dkap.p + (size_t)p * LM, dKu.p + (size_t)p * nd, c, dc_of(step, p),
-                             urhs.p);
-        } else {
-          hipLaunchKernelGGL((k_gdir_rows<D, false>), dim3(grid_of(n)), dim3(256), 0, h->st, n, pt.cslice_ptr.p, pt.cslots.p,
-                             pt.celem.p, pt.diag_k.p, a.cell_nodes.p, h->egeo.p, h->label.p, h->mat.p,
-                             d_dir.p + (p * 3 + 2) * LM, (const double*)nullptr, (const double*)nullptr, c, dc_of(step, p),
-                             urhs.p);
-        }
-        GL_CHECK_LAUNCH();
-        status = solve_elastic(h, wk, urhs.p, du.p, nullptr, 1e-12, &its);
-        if (status != GLIMS_OK) break;
-        gl_halo_exchange(h, du.p, D);
-        GL_HIP(hipMemsetAsync(dmurhs.p, 0, (size_t)nd * sizeof(double), h->st));
-        for (int k = 0; k < n_terms; ++k) {
-          const glims_misfit& tm = terms[k];
-          if (tm.step != step || tm.kind != GLIMS_MISFIT_U_L2) continue;
-          for (int comp = 0; comp < D; ++comp) {
-            hipLaunchKernelGGL(k_component, dim3(grid_of(n)), dim3(256), 0, h->st, n, D, comp, du.p,
-                               (const double*)nullptr, ue.p);
-            GL_CHECK_LAUNCH();
-            gl_halo_exchange(h, ue.p, 1);
-            mass_apply(h, ue.p, uMe.p);
-            hipLaunchKernelGGL(k_add_component, dim3(grid_of(n)), dim3(256), 0, h->st, n, D, comp, tm.weight, uMe.p,
-                               dmurhs.p);
-            GL_CHECK_LAUNCH();
-          }
-        }
-        if (el_dirs) {   // - dK mu_k
-          hipLaunchKernelGGL(k_sub, dim3(grid_of(n * D)), dim3(256), 0, h->st, n * D, dKmu.p + (size_t)p * nd, dmurhs.p);
-          GL_CHECK_LAUNCH();
-        }
-        status = solve_elastic(h, wk, dmurhs.p, dmu.p, nullptr, 1e-12, &its);
-        if (status != GLIMS_OK) break;
-        extra_mech += 2;
-        gl_halo_exchange(h, dmu.p, D);   // qcell of the cells at the cut
-        gt_pass(h->mat.p, c, dmu.p, hs);
-        hipLaunchKernelGGL(k_gt_rows, dim3(grid_of(n)), dim3(256), 0, h->st, n, pt.cslice_ptr.p, pt.celem.p, hqcell.p, dgp);
-        GL_CHECK_LAUNCH();
-        gt_pass(h->mat.p, dc_of(step, p), wk.mu.p, hs);
-        gt_pass(d_dmat.p + (size_t)p * 5 * LM, c, wk.mu.p, nullptr);
-        hipLaunchKernelGGL(k_gt_rows, dim3(grid_of(n)), dim3(256), 0, h->st, n, pt.cslice_ptr.p, pt.celem.p, hqcell.p, dgp);
-        GL_CHECK_LAUNCH();
-        if (el_dirs) {
-          // the E / nu part of dG^T mu: gamma_t (2 dm_t + d dl_t) |T|/(d+1) div mu per cell, then the rows
-          gt_pass(d_dmat2.p + (size_t)p * 5 * LM, c, wk.mu.p, nullptr);
-          hipLaunchKernelGGL(k_gt_rows, dim3(grid_of(n)), dim3(256), 0, h->st, n, pt.cslice_ptr.p, pt.celem.p, hqcell.p, dgp);
-          GL_CHECK_LAUNCH();
-        }
-        if (el_sums) {
-          // A_t(dmu, u) + A_t(mu, du), B_t(dmu, u) + B_t(mu, du) of step k (u_k's ghosts: coupling_adjoint exchanged them)
-          for (int l0 = 0; l0 < L; l0 += GL_ADJ_LT) {
-            hipLaunchKernelGGL(k_hesens<D>, dim3(sens_blocks(h)), dim3(256), 0, h->st, h->n_cells, l0, a.cell_nodes.p,
-                               h->egeo.p, h->label.p, wk.uk.p, wk.mu.p, du.p, dmu.p, counted, hepart.p);
-            GL_CHECK_LAUNCH();
-            hipLaunchKernelGGL(k_sens_final, dim3(1), dim3(1024), 0, h->st, sens_blocks(h), l0, L, 2, 0, hepart.p,
-                               hesums.p + (size_t)p * LM * 2);
-            GL_CHECK_LAUNCH();
-          }
-        }
-      }
-      if (status != GLIMS_OK) break;
+
+  // After a concentration term, while wk.Me holds M (h - t):  dg_p += w (h' M(h' dc_p) + h'' M(h - t) dc_p).
+  // Reads dcs[step], wk.Me; writes hd, Mhd, dg.
+  void concentration_second(int step, const double* c, const glims_misfit& tm) {
+    for (int p = 0; p < P; ++p) {
+      hipLaunchKernelGGL(k_misfit_dir, dim3(grid_of(n)), dim3(256), 0, h->st, n, tm.kind, tm.level, tm.smooth, c,
+                         m.dc_of(step, p), m.hd.p);
+      GL_CHECK_LAUNCH();
+      gl_halo_exchange(h, m.hd.p, 1);
+      mass_apply(h, m.hd.p, m.Mhd.p);
+      hipLaunchKernelGGL(k_misfit_second, dim3(grid_of(n)), dim3(256), 0, h->st, n, tm.kind, tm.level, tm.smooth, tm.weight,
+                         c, m.dc_of(step, p), wk.Me.p, m.Mhd.p, m.col(m.dg, p));
+      GL_CHECK_LAUNCH();
     }
-    if (step == 0) {
-      if (dc0) sw.c0_output(dc0);
-      for (int p = 0; hv_c0 && p < P; ++p) {   // (H dm)_c0 = M nu_1 + dg_0
-        double* y = hrhs.p + (size_t)p * nn;
-        if (N > 0) gl_launch_spmv(h, h->st, pt.n_slices, nullptr, h->vM.p, nu_next.p + (size_t)p * nn, y, nullptr,
-                                  dg.p + (size_t)p * nn, nullptr, nullptr, 0, nullptr);
-        else GL_HIP(hipMemcpyAsync(y, dg.p + (size_t)p * nn, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, h->st));
-        download_permuted(h, wk, y, hv_c0 + (size_t)p * nn);
+  }
+
+  // dK_p u_k (u_k with its Dirichlet values: the lifting term is differentiated too) and dK_p mu_k into dKu, dKmu
+  void dkel_products() {
+    for (const auto& vy : {std::make_pair((const double*)wk.uk.p, m.dKu.p), std::make_pair((const double*)wk.mu.p, m.dKmu.p)}) {
+      hipLaunchKernelGGL(k_dkel_rows<D>, dim3(grid_of(n)), dim3(256), 0, h->st, n, P, nd, pt.cslice_ptr.p, pt.cslots.p,
+                         pt.celem.p, pt.diag_k.p, h->adj.cell_nodes.p, h->egeo.p, h->label.p, m.d_dlame.p, vy.first, vy.second);
+      GL_CHECK_LAUNCH();
+    }
+  }
+  // du = K_el^-1 (G dc + sum_t dgamma_t G_t c), with el_dirs G dc + dG c - dK u_k: urhs, then du with current ghosts
+  bool du_solve(int step, const double* c, int p) {
+    const auto kern = s.el_dirs ? k_gdir_rows<D, true> : k_gdir_rows<D, false>;
+    hipLaunchKernelGGL(kern, dim3(grid_of(n)), dim3(256), 0, h->st, n, pt.cslice_ptr.p, pt.cslots.p, pt.celem.p, pt.diag_k.p,
+                       h->adj.cell_nodes.p, h->egeo.p, h->label.p, h->mat.p, m.dgamma_of(p),
+                       s.el_dirs ? m.d_dkap.p + (size_t)p * GL_MAX_LABELS : (const double*)nullptr,
+                       s.el_dirs ? m.dKu.p + (size_t)p * nd : (const double*)nullptr, c, m.dc_of(step, p), m.urhs.p);
+    GL_CHECK_LAUNCH();
+    int64_t its = 0;
+    sw.status = solve_elastic(h, wk, m.urhs.p, m.du.p, nullptr, 1e-12, &its);
+    if (sw.status != GLIMS_OK) return false;
+    gl_halo_exchange(h, m.du.p, D);
+    return true;
+  }
+  // dmu = K_el^-1 sum w M_vec du (0 on the constrained dofs), with el_dirs - dK mu_k: dmurhs through ue, uMe, then dmu with
+  // current ghosts
+  bool dmu_solve(int step, int p) {
+    GL_HIP(hipMemsetAsync(m.dmurhs.p, 0, (size_t)nd * sizeof(double), h->st));
+    for (int k = 0; k < call.n_terms; ++k) {
+      const glims_misfit& tm = call.terms[k];
+      if (tm.step != step || tm.kind != GLIMS_MISFIT_U_L2) continue;
+      for (int comp = 0; comp < D; ++comp) {
+        hipLaunchKernelGGL(k_component, dim3(grid_of(n)), dim3(256), 0, h->st, n, D, comp, m.du.p, (const double*)nullptr,
+                           m.ue.p);
+        GL_CHECK_LAUNCH();
+        gl_halo_exchange(h, m.ue.p, 1);
+        mass_apply(h, m.ue.p, m.uMe.p);
+        hipLaunchKernelGGL(k_add_component, dim3(grid_of(n)), dim3(256), 0, h->st, n, D, comp, tm.weight, m.uMe.p, m.dmurhs.p);
+        GL_CHECK_LAUNCH();
       }
+    }
+    if (s.el_dirs) {   // - dK mu_k
+      hipLaunchKernelGGL(k_sub, dim3(grid_of(n * D)), dim3(256), 0, h->st, n * D, m.dKmu.p + (size_t)p * nd, m.dmurhs.p);
+      GL_CHECK_LAUNCH();
+    }
+    int64_t its = 0;
+    sw.status = solve_elastic(h, wk, m.dmurhs.p, m.dmu.p, nullptr, 1e-12, &its);
+    if (sw.status != GLIMS_OK) return false;
+    gl_halo_exchange(h, m.dmu.p, D);   // qcell of the cells at the cut
+    return true;
+  }
+  // dg_p += G^T dmu + sum_t dgamma_t G_t^T mu (+ the E / nu part of dG^T mu);  H_gamma_t += dmu^T G_t c + mu^T G_t dc
+  void gt_contributions(int step, const double* c, int p) {
+    gt_pass(h->mat.p, c, m.dmu.p, m.hsums_of(p));
+    gt_rows(m.col(m.dg, p));
+    gt_pass(h->mat.p, m.dc_of(step, p), wk.mu.p, m.hsums_of(p));
+    gt_pass(m.dmat_of(m.d_dmat, p), c, wk.mu.p, nullptr);
+    gt_rows(m.col(m.dg, p));
+    if (s.el_dirs) {   // gamma_t (2 dm_t + d dl_t) |T|/(d+1) div mu per cell, then the rows
+      gt_pass(m.dmat_of(m.d_dmat2, p), c, wk.mu.p, nullptr);
+      gt_rows(m.col(m.dg, p));
+    }
+  }
+  // A_t(dmu, u) + A_t(mu, du), B_t(dmu, u) + B_t(mu, du) of step k (u_k's ghosts: coupling_adjoint exchanged them)
+  void elastic_sums(int p) {
+    for (int l0 = 0; l0 < L; l0 += GL_ADJ_LT) {
+      hipLaunchKernelGGL(k_hesens<D>, dim3(sens_blocks(h)), dim3(256), 0, h->st, h->n_cells, l0, h->adj.cell_nodes.p, h->egeo.p,
+                         h->label.p, wk.uk.p, wk.mu.p, m.du.p, m.dmu.p, counted, m.hepart.p);
+      GL_CHECK_LAUNCH();
+      hipLaunchKernelGGL(k_sens_final, dim3(1), dim3(1024), 0, h->st, sens_blocks(h), l0, L, 2, 0, m.hepart.p, m.hesums_of(p));
+      GL_CHECK_LAUNCH();
+    }
+  }
+  // The displacement part of a step that has one, after the coupling adjoint (wk.uk, wk.mu): per direction two elastic solves,
+  // their share of dg and of the gamma (and E / nu) sums.  Reads dcs[step]; writes dg, hsums, hesums.
+  bool coupling_second(int step, const double* c) {
+    if (s.el_dirs) dkel_products();
+    for (int p = 0; p < P; ++p) {
+      if (!du_solve(step, c, p) || !dmu_solve(step, p)) return false;
+      extra_mech += 2;
+      gt_contributions(step, c, p);
+      if (s.el_sums) elastic_sums(p);
+    }
+    return true;
+  }
+
+  // Step 0: dJ/dc_0, and (H dm)_c0 = M nu_1 + dg_0 of every direction through hrhs
+  void c0_rows() {
+    if (call.dc0) sw.c0_output(call.dc0);
+    for (int p = 0; call.hv_c0 && p < P; ++p) {
+      double* y = m.col(m.hrhs, p);
+      if (N > 0) mass_col(m.col(m.nu_next, p), m.col(m.dg, p), y, nullptr);
+      else GL_HIP(hipMemcpyAsync(y, m.col(m.dg, p), (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, h->st));
+      download_permuted(h, wk, y, call.hv_c0 + (size_t)p * nn);
+    }
+  }
+
+  // nu_n: A(c_n) nu_n = M nu_{n+1} + dg_n - 2 dt sum_t rho_t int_t dc_n lam_n phi - dt sum_t dD_t K_t lam_n
+  //                     - dt sum_t drho_t int_t (2 c_n - 1) lam_n phi,   PCG from nu_{n+1}; then the (H dm)_{D,rho} sums of step n.
+  // After lambda_solve (wk.lam, A(c_n) in the swapped-in buffers).  Reads dg, dcs[step], nu_next; writes hrhs, nu (which
+  // becomes nu_next), hsums.
+  void second_adjoint_step(int step, const double* c) {
+    for (int p = 0; p < P; ++p) mass_col(m.col(m.nu_next, p), m.col(m.dg, p), m.col(m.hrhs, p), fxc);
+    hess_rows<1>(c, wk.lam.p, m.dc_of(step, 0));
+    zero_fixed_cols(m.hrhs.p);
+    GL_HIP(hipMemcpyAsync(m.nu.p, m.nu_next.p, (size_t)P * nn * sizeof(double), hipMemcpyDeviceToDevice, h->st));
+    sw.status = rd_solve_cols(h, wk, m.mp, fxc, sw.rd_mg, sw.rd_deg, P, m.hrhs.p, m.nu.p, nn, &soa_its);
+    if (sw.status == GLIMS_OK) exchange_cols(m.nu.p);   // k_hsens and M nu_{n+1} read the ghosts
+    for (int p = 0; p < P && sw.status == GLIMS_OK; ++p)
+      for (int l0 = 0; l0 < L; l0 += GL_ADJ_LT) {
+        hipLaunchKernelGGL(k_hsens<D>, dim3(sens_blocks(h)), dim3(256), 0, h->st, h->n_cells, l0, h->adj.cell_nodes.p, h->egeo.p,
+                           h->label.p, c, wk.lam.p, m.dc_of(step, p), m.col(m.nu, p), counted, m.hpart.p);
+        GL_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_sens_final, dim3(1), dim3(1024), 0, h->st, sens_blocks(h), l0, L, 3, 0, m.hpart.p, m.hsums_of(p));
+        GL_CHECK_LAUNCH();
+      }
+    std::swap(m.nu.p, m.nu_next.p);
+  }
+
+  // The gather of the per-label sums (every rank reaches it, also after a failed solve) and the rows of every output
+  void label_outputs(const HessDirections& dirs) {
+    const size_t LM = GL_MAX_LABELS;
+    const std::vector<RowPart> lay = label_row_parts(L, s.el, P, s.el_sums);
+    std::vector<double> sums((size_t)L * 3), hs((size_t)P * LM * 3), esums((size_t)L * 2, 0.0), hes((size_t)P * LM * 2, 0.0);
+    gather_label_sums(h, {{lay[0], wk.sums.p, sums.data()}, {lay[1], wk.esums.p, esums.data()},
+                          {lay[2], m.hsums.p, hs.data()}, {lay[3], m.hesums.p, hes.data()}},
+                      hess_buffer(m.table, "gather").count);
+    const ElasticSecond none = {}, &el = call.el ? *call.el : none;
+    sw.write_labels(sums.data(), call.dD, call.drho, call.dgamma);
+    if (call.el) write_elastic_labels(h->mat_host.data(), L, D, sums.data(), esums.data(), el.dE, el.dnu);
+    hessian_label_rows(dirs, call.el != nullptr, dt, h->mat_host.data(), sums.data(), hs.data(), esums.data(), hes.data(),
+                       call.hv_D, call.hv_rho, call.hv_gamma, el.hv_E, el.hv_nu);
+  }
+};
+
+// The tangent-linear sweep, then gradient_t's backward sweep with the second-order adjoint work of every direction between
+// its parts (HessianSweep).  The guards' order matters: the counters, then the forward state, then the sweep (the lazy RD
+// hierarchy is the ForwardGuard's to drop).
+template <int D>
+int hessian_t(glims_ctx* h, const HessCall& call) {
+  const double t0 = omp_get_wtime();
+  const HessShape shape = hessian_shape(h, call);
+  if (!call.mem_checked) {
+    std::string why;
+    if (!hessian_fits(shape, &why)) throw glims_error(GLIMS_E_HIP, why);
+  }
+  const int P = shape.P, N = shape.N;
+  const int64_t nn = shape.n_nodes;
+  const ElasticSecond none = {}, &el = call.el ? *call.el : none;
+  AdjCountGuard counts(h->adj);
+  HessMemory mem(h, shape);
+  AdjWork& wk = mem.wk;
+  adjoint_setup<D>(h, mem.table, call.n_terms, call.terms, wk);
+  const HessDirections dirs(P, shape.n_labels, D, h->mat_host.data(), call.dir_D, call.dir_rho, call.dir_gamma, el.dir_E,
+                            el.dir_nu, shape.el_dirs);
+  mem.upload_directions(h, dirs);
+  for (int p = 0; call.dir_c0 && p < P; ++p) upload_permuted(h, wk, call.dir_c0 + (size_t)p * nn, 1, mem.dc_of(0, p));
+  ForwardGuard guard(h, wk);
+  BackwardSweep<D> sw(h, wk, call.n_terms, call.terms, shape.el);
+  HessianSweep<D> hs(h, call, shape, mem, sw);
+  if (call.dir_c0) hs.exchange_cols(mem.dcs.p);   // (the caller's ghost entries are not trusted; under the guard: glims_stats stay)
+  // 1. the tangent-linear sweep
+  for (int step = 1; step <= N && sw.status == GLIMS_OK; ++step) hs.tangent_linear_step(step);
+  // 2. the first-order sweep with the second-order adjoint nu_n of every direction
+  for (int step = N; step >= 0 && sw.status == GLIMS_OK; --step) {
+    const double* c = sw.begin_step(step);
+    GL_HIP(hipMemsetAsync(mem.dg.p, 0, (size_t)P * nn * sizeof(double), h->st));
+    const bool have_u = sw.nodal_terms(step, c, [&](const glims_misfit& tm) { hs.concentration_second(step, c, tm); });
+    if (sw.status != GLIMS_OK) break;
+    image_terms_of_step(h, step, c, wk.g.p, &sw.J, P, mem.dc_of(step, 0), nn, mem.dg.p);
+    gl_observable_terms_of_step(h, step, c, wk.g.p, &sw.J, P, mem.dc_of(step, 0), nn, mem.dg.p);
+    if (have_u && !(sw.coupling_adjoint(c) && hs.coupling_second(step, c))) break;
+    if (step == 0) {
+      hs.c0_rows();
       break;
     }
     if (!sw.lambda_solve(c)) break;
-    // nu_n: A(c_n) nu_n = M nu_{n+1} + dg_n - 2 dt sum_t rho_t int_t dc_n lam_n phi - dt sum_t dD_t K_t lam_n
-    //                     - dt sum_t drho_t int_t (2 c_n - 1) lam_n phi,   PCG from nu_{n+1}
-    for (int p = 0; p < P; ++p)
-      gl_launch_spmv(h, h->st, pt.n_slices, nullptr, h->vM.p, nu_next.p + (size_t)p * nn, hrhs.p + (size_t)p * nn, fxc,
-                     dg.p + (size_t)p * nn, nullptr, nullptr, 0, nullptr);
-    hipLaunchKernelGGL((k_hess_rows<D, 1>), dim3(grid_of(n)), dim3(256), 0, h->st, n, P, nn, pt.cslice_ptr.p, pt.cslots.p,
-                       pt.celem.p, pt.diag_k.p, a.cell_nodes.p, h->egeo.p, h->label.p, h->mat.p, d_dir.p, dt, c,
-                       wk.lam.p, dc_of(step, 0), hrhs.p);
-    GL_CHECK_LAUNCH();
-    for (int p = 0; p < P; ++p)
-      if (fxc)
-        hipLaunchKernelGGL(k_zero_fixed, dim3(grid_of(n)), dim3(256), 0, h->st, n, fxc, hrhs.p + (size_t)p * nn,
-                           (const double*)nullptr);
-    GL_HIP(hipMemcpyAsync(nu.p, nu_next.p, (size_t)P * nn * sizeof(double), hipMemcpyDeviceToDevice, h->st));
-    status = rd_solve_cols(h, wk, mp, fxc, sw.rd_mg, sw.rd_deg, P, hrhs.p, nu.p, nn, &soa_its);
-    if (status == GLIMS_OK) exchange_cols(nu.p);   // k_hsens and M nu_{n+1} read the ghosts
-    for (int p = 0; p < P && status == GLIMS_OK; ++p) {
-      double* x = nu.p + (size_t)p * nn;
-      for (int l0 = 0; l0 < L; l0 += GL_ADJ_LT) {   // (H dm)_{D,rho} sums of step n
-        hipLaunchKernelGGL(k_hsens<D>, dim3(sens_blocks(h)), dim3(256), 0, h->st, h->n_cells, l0, a.cell_nodes.p, h->egeo.p,
-                           h->label.p, c, wk.lam.p, dc_of(step, p), x, counted, hpart.p);
-        GL_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_sens_final, dim3(1), dim3(1024), 0, h->st, sens_blocks(h), l0, L, 3, 0, hpart.p,
-                           hsums.p + (size_t)p * LM * 3);
-        GL_CHECK_LAUNCH();
-      }
-    }
-    std::swap(nu.p, nu_next.p);
+    hs.second_adjoint_step(step, c);
     sw.end_step();
   }
-  const size_t L3 = (size_t)L * 3;
-  std::vector<double> sums(L3), hs((size_t)P * LM * 3);
-  std::vector<double> esums((size_t)L * 2, 0.0), hes((size_t)P * LM * 2, 0.0);   // (el: one GPU)
-  if (!part) {
-    GL_HIP(hipMemcpyAsync(sums.data(), wk.sums.p, L3 * sizeof(double), hipMemcpyDeviceToHost, h->st));
-    GL_HIP(hipMemcpyAsync(hs.data(), hsums.p, hs.size() * sizeof(double), hipMemcpyDeviceToHost, h->st));
-    if (el) GL_HIP(hipMemcpyAsync(esums.data(), wk.esums.p, esums.size() * sizeof(double), hipMemcpyDeviceToHost, h->st));
-    if (el_sums) GL_HIP(hipMemcpyAsync(hes.data(), hesums.p, hes.size() * sizeof(double), hipMemcpyDeviceToHost, h->st));
-    GL_HIP(hipStreamSynchronize(h->st));
-  } else {
-    // as gradient_t: every rank's W sums (the gradient's [L][3], then [P][L][3] of the directions) gathered through
-    // [world][W] with zeros outside the own row and added in rank order on the host -- reached by every rank, also after a
-    // failed solve (the statuses are global)
-    const size_t W = L3 + (size_t)P * L3;
-    dvec<double> all;
-    all.alloc_zero(W * h->world, h->st);
-    double* row = all.p + W * h->rank;
-    GL_HIP(hipMemcpyAsync(row, wk.sums.p, L3 * sizeof(double), hipMemcpyDeviceToDevice, h->st));
-    for (int p = 0; p < P; ++p)
-      GL_HIP(hipMemcpyAsync(row + L3 * (1 + p), hsums.p + (size_t)p * LM * 3, L3 * sizeof(double), hipMemcpyDeviceToDevice,
-                            h->st));
-    gl_allreduce_bulk(h, all.p, W * h->world);
-    std::vector<double> rows(W * h->world);
-    GL_HIP(hipMemcpyAsync(rows.data(), all.p, rows.size() * sizeof(double), hipMemcpyDeviceToHost, h->st));
-    GL_HIP(hipStreamSynchronize(h->st));
-    for (size_t k = 0; k < W; ++k) {
-      double t = 0.0;
-      for (int r = 0; r < h->world; ++r) t += rows[W * r + k];
-      if (k < L3) sums[k] = t;
-      else hs[((k - L3) / L3) * LM * 3 + (k - L3) % L3] = t;
-    }
+  hs.label_outputs(dirs);
+  *call.J = sw.J;
+  if (call.stats) {
+    call.stats[0] = (double)hs.tlm_its;
+    call.stats[1] = (double)hs.soa_its;
+    call.stats[2] = (double)hs.extra_mech;
+    call.stats[3] = 1e3 * (omp_get_wtime() - t0);
   }
-  sw.write_labels(sums.data(), dD, drho, dgamma);
-  for (int p = 0; p < P; ++p)
-    for (int l = 0; l < L; ++l) {
-      const double* q = hs.data() + ((size_t)p * LM + l) * 3;
-      if (hv_D) hv_D[(size_t)p * L + l] = -dt * q[0];
-      if (hv_rho) hv_rho[(size_t)p * L + l] = -dt * q[1];
-      if (hv_gamma) hv_gamma[(size_t)p * L + l] = q[2];
-    }
-  if (el) {
-    // the E / nu rows next to the first-order combination, in label order (lame_derivs.h): the gradient's totals (A_t, B_t, C_t),
-    // the direction's sums (mode 1's sums carry kappa_t, as C_t does), and the extra term of the gamma row
-    write_elastic_labels(h, D, sums.data(), esums.data(), el->dE, el->dnu);
-    const double* mh = h->mat_host.data();
-    for (int p = 0; p < P; ++p)
-      for (int l = 0; l < L; ++l) {
-        const size_t o = (size_t)p * L + l;
-        const double dEl = el->dir_E ? el->dir_E[o] : 0.0, dnul = el->dir_nu ? el->dir_nu[o] : 0.0;
-        const LameDerivs d = lame_derivs(mh[5 * LM + l], mh[6 * LM + l]);
-        const ElasticSums tot = elastic_totals(h, D, l, sums.data(), esums.data());
-        const double den = 2.0 * mh[3 * LM + l] + D * mh[4 * LM + l];
-        const ElasticSums sd = {hes[((size_t)p * LM + l) * 2 + 0], hes[((size_t)p * LM + l) * 2 + 1],
-                                den != 0.0 ? hs[((size_t)p * LM + l) * 3 + 2] / den : 0.0};
-        const double gam = mh[2 * LM + l], dgam = dir_gamma ? dir_gamma[o] : 0.0;
-        if (el->hv_E) el->hv_E[o] = elastic_hessian_row(D, 0, d, gam, dgam, dEl, dnul, tot, sd);
-        if (el->hv_nu) el->hv_nu[o] = elastic_hessian_row(D, 1, d, gam, dgam, dEl, dnul, tot, sd);
-        if (el_dirs && hv_gamma) {
-          double dm, dl;
-          lame_direction(d, dEl, dnul, &dm, &dl);
-          hv_gamma[o] += (2.0 * dm + D * dl) * tot.C;
-        }
-      }
-  }
-  *J_out = sw.J;
-  if (stats) {
-    stats[0] = (double)tlm_its;
-    stats[1] = (double)soa_its;
-    stats[2] = (double)extra_mech;
-    stats[3] = 1e3 * (omp_get_wtime() - t0);
-  }
-  return status;
+  return sw.status;
 }
 
 }  // namespace
@@ -2069,14 +2056,8 @@ int gl_adjoint_gradient(glims_ctx* h, int n_terms, const glims_misfit* terms, do
 }
 
 namespace {
-int hessian_dispatch(glims_ctx* h, int n_terms, const glims_misfit* terms, int n_dir, const double* dir_D,
-                     const double* dir_rho, const double* dir_gamma, const double* dir_c0, double* J, double* dD, double* drho,
-                     double* dgamma, double* dc0, double* hv_D, double* hv_rho, double* hv_gamma, double* hv_c0, double* stats,
-                     bool mem_checked, const ElasticSecond* el = nullptr) {
-  return h->dim == 2 ? hessian_t<2>(h, n_terms, terms, n_dir, dir_D, dir_rho, dir_gamma, dir_c0, J, dD, drho, dgamma, dc0,
-                                    hv_D, hv_rho, hv_gamma, hv_c0, stats, mem_checked, el)
-                     : hessian_t<3>(h, n_terms, terms, n_dir, dir_D, dir_rho, dir_gamma, dir_c0, J, dD, drho, dgamma, dc0,
-                                    hv_D, hv_rho, hv_gamma, hv_c0, stats, mem_checked, el);
+int hessian_dispatch(glims_ctx* h, const HessCall& call) {
+  return h->dim == 2 ? hessian_t<2>(h, call) : hessian_t<3>(h, call);
 }
 void check_n_dir(int n_dir, const std::string& who = "glims_adjoint_hessian") {
   GL_REQUIRE(n_dir >= 1 && n_dir <= GL_HESS_MAXDIR, who + ": n_dir = " + std::to_string(n_dir) + ", 1.." +
@@ -2095,8 +2076,8 @@ int gl_adjoint_hessian(glims_ctx* h, int n_terms, const glims_misfit* terms, int
                                     "glims_adjoint_deformed_image_terms(h, 0, NULL) first");
   check_gradient_call(h, n_terms, terms, J, "glims_adjoint_hessian", true);
   check_n_dir(n_dir);
-  return hessian_dispatch(h, n_terms, terms, n_dir, dir_D, dir_rho, dir_gamma, dir_c0, J, dD, drho, dgamma, dc0, hv_D, hv_rho,
-                          hv_gamma, hv_c0, stats, false);
+  return hessian_dispatch(h, {n_terms, terms, n_dir, dir_D, dir_rho, dir_gamma, dir_c0, J, dD, drho, dgamma, dc0, hv_D, hv_rho,
+                              hv_gamma, hv_c0, stats});
 }
 
 int gl_adjoint_hessian_full(glims_ctx* h, int n_terms, const glims_misfit* terms, int n_dir, const double* dir_D,
@@ -2115,8 +2096,8 @@ int gl_adjoint_hessian_full(glims_ctx* h, int n_terms, const glims_misfit* terms
   GL_REQUIRE(h->have_mech || !(dir_E || dir_nu || hv_E || hv_nu),
              who + ": dir_E / dir_nu / hv_E / hv_nu need glims_setup(with_mechanics=1)");
   const ElasticSecond el = {dir_E, dir_nu, dE, dnu, hv_E, hv_nu};
-  return hessian_dispatch(h, n_terms, terms, n_dir, dir_D, dir_rho, dir_gamma, dir_c0, J, dD, drho, dgamma, dc0, hv_D, hv_rho,
-                          hv_gamma, hv_c0, stats, false, &el);
+  return hessian_dispatch(h, {n_terms, terms, n_dir, dir_D, dir_rho, dir_gamma, dir_c0, J, dD, drho, dgamma, dc0, hv_D, hv_rho,
+                              hv_gamma, hv_c0, stats, false, &el});
 }
 
 int gl_adjoint_hessian_spmd(glims_ctx* h, int n_terms, const glims_misfit* terms, int n_dir, const double* dir_D,
@@ -2138,7 +2119,9 @@ int gl_adjoint_hessian_spmd(glims_ctx* h, int n_terms, const glims_misfit* terms
     if (e.code != GLIMS_E_USAGE) throw;
     why = e.what();
   }
-  const bool fits = !why.empty() || hessian_fits(h, n_terms, terms, n_dir, &why_mem);
+  const HessCall call = {n_terms, terms, n_dir, dir_D, dir_rho, dir_gamma, dir_c0, J, dD, drho, dgamma, dc0, hv_D, hv_rho,
+                         hv_gamma, hv_c0, stats, true};
+  const bool fits = !why.empty() || hessian_fits(hessian_shape(h, call), &why_mem);
   const size_t w = (size_t)h->world, r0 = (size_t)h->rank;
   std::vector<double> flag(w * 6, 0.0);
   uint64_t sum_steps = 0;
@@ -2177,6 +2160,5 @@ int gl_adjoint_hessian_spmd(glims_ctx* h, int n_terms, const glims_misfit* terms
   const std::string short_mem = ranks_with(5);
   if (!fits) throw glims_error(GLIMS_E_HIP, why_mem + " (ranks short of memory: " + short_mem + ")");
   if (!short_mem.empty()) throw glims_error(GLIMS_E_HIP, who + ": rank(s) " + short_mem + " are short of device memory");
-  return hessian_dispatch(h, n_terms, terms, n_dir, dir_D, dir_rho, dir_gamma, dir_c0, J, dD, drho, dgamma, dc0, hv_D, hv_rho,
-                          hv_gamma, hv_c0, stats, true);
+  return hessian_dispatch(h, call);
 }

@@ -7,6 +7,7 @@ median, min and max of --reps calls after one warm-up, with the tangent-linear a
 direction, for config C3 (1 M-node lattice) and the 1.04 M-node brain-like mesh.  One JSON line per workload on stdout.
 
     python tools/adjoint_hessian_cost.py [--steps 20] [--which c3,brain_like] [--dirs 1,2,5] [--reps 5]
+                                         [--lib path/to/libglimship.so --build NAME]   # another build of the library, named
 
 --elastic measures what directions in E / nu add ("Second order in E and nu"): the handle is set up with
 mechanics (u = 0 on the workload's Dirichlet nodes), one u_l2 term observes the last step, and glims_adjoint_hessian_full with
@@ -135,7 +136,12 @@ def main():
                     "glims_adjoint_hessian, one u_l2 term (see above)")
     ap.add_argument("--pure-columns", action="store_true", help="with --elastic: the full call's columns are dE / dnu alone "
                     "instead of dE / dnu added to the D / rho columns")
+    ap.add_argument("--lib", help="measure this build of libglimship.so instead of the tree's (A/B of two builds in one session)")
+    ap.add_argument("--build", help="a name for the build, added to every JSON line as 'build'")
     a = ap.parse_args()
+    if a.lib:
+        _backend.LIB_PATH = os.path.abspath(a.lib)
+    tag = (lambda d: dict(d, build=a.build)) if a.build else (lambda d: d)
     dirs = [int(x) for x in a.dirs.split(",")]
     for name in a.which.split(","):
         if name == "c3":
@@ -145,9 +151,9 @@ def main():
         else:
             raise SystemExit("unknown workload " + name)
         if a.elastic:
-            print(json.dumps(measure_elastic(w, a.steps, dirs, a.reps, a.pure_columns)), flush=True)
+            print(json.dumps(tag(measure_elastic(w, a.steps, dirs, a.reps, a.pure_columns))), flush=True)
         else:
-            print(json.dumps(measure(w, a.steps, dirs, a.reps)), flush=True)
+            print(json.dumps(tag(measure(w, a.steps, dirs, a.reps))), flush=True)
 
 
 if __name__ == "__main__":
