@@ -151,6 +151,12 @@ class ObservableMisfit(C.Structure):
                 ("weight", C.c_double), ("target", C.c_double), ("labels", C.POINTER(C.c_uint8))]
 
 
+class ObservableMisfit2(C.Structure):
+    """glims_observable_misfit2: ObservableMisfit, then the configuration the cells are measured in (deformed: at X + scale u_k,
+    with the gradient through u_k)."""
+    _fields_ = ObservableMisfit._fields_ + [("deformed", C.c_int), ("scale", C.c_double)]
+
+
 _dp = C.POINTER(C.c_double)
 _i32p = C.POINTER(C.c_int32)
 _i64p = C.POINTER(C.c_int64)
@@ -218,6 +224,8 @@ SIGNATURES = {
     "glims_adjoint_deformed_image_info": (C.c_int, [_h, C.c_int, _i64p, _dp]),
     "glims_adjoint_observable_terms": (C.c_int, [_h, C.c_int, C.POINTER(ObservableMisfit)]),
     "glims_adjoint_observable_info": (C.c_int, [_h, C.c_int, _i64p, _dp]),
+    "glims_adjoint_observable_terms2": (C.c_int, [_h, C.c_int, C.POINTER(ObservableMisfit2)]),
+    "glims_adjoint_observable_info2": (C.c_int, [_h, C.c_int, _i64p, _dp, _dp]),
     "glims_comm_unique_id": (C.c_int, [C.c_char_p]),
     "glims_comm_init": (C.c_int, [_h, C.c_int, C.c_int, C.c_char_p]),
     "glims_comm_selftest": (C.c_int, [_h]),
@@ -686,6 +694,7 @@ class Handle:
 
     def _warn_folded(self):
         """Once per stored list: the last gradient call located points in a mesh with folded cells."""
+        self._warn_folded_volumes()
         if self._warned_folded or not self._deformed_terms:
             return
         for k in range(len(self._deformed_terms)):
@@ -698,24 +707,45 @@ class Handle:
                 self._warned_folded = True
                 return
 
+    def _warn_folded_volumes(self):
+        """Once per stored list: the last gradient call measured a deformed volume term on a mesh with folded cells."""
+        if getattr(self, "_warned_folded_volumes", True):
+            return
+        for k, key in enumerate(self._observable_terms):
+            if not key[-2]:
+                continue
+            info = self.observable_term_info2(k)
+            if info["folded"] > 0:
+                import warnings
+                warnings.warn("deformed volume term %d: %d counted cells of the displaced mesh are folded (smallest volume "
+                              "ratio min_ratio = %.3g); they count negatively" % (k, info["folded"], info["min_ratio"]),
+                              RuntimeWarning, stacklevel=4)
+                self._warned_folded_volumes = True
+                return
+
     # -- volume misfit terms (glims_adjoint_observable_*) ----------------------------------------------
     @staticmethod
     def _observable_key(t):
         """What identifies a stored volume term: its scalars and the counted labels."""
         lab = t.get("labels")
         kind = t.get("observable", "smooth")
+        deformed = bool(t.get("deformed", False))
         return (int(t["step"]), OBSERVE_KINDS.get(kind, kind), float(t.get("level", 0.0)), float(t.get("smooth", 1.0)),
                 float(t.get("weight", 1.0)), float(t["target"]),
-                None if lab is None else tuple(bool(v) for v in np.ravel(lab)))
+                None if lab is None else tuple(bool(v) for v in np.ravel(lab)),
+                deformed, float(t.get("scale", 1.0)) if deformed else 1.0)
 
     def set_observable_terms(self, terms, _from_list=False):
         """glims_adjoint_observable_terms: replace the handle's stored volume terms (an empty list clears them).  Each term:
-        {step, observable ('mass' | 'sharp' | 'smooth' or GLIMS_OBSERVE_*), target, weight=1, level=0, smooth=1, labels=None}
-        with J = 1/2 weight (V - target)^2, V the measure observe() returns for (observable, level, smooth) on recorded step
-        ``step`` in the reference configuration, summed over the labels whose entry of ``labels`` ([n_labels], truthy =
-        counted) is set, or over the whole domain.  Every later adjoint_gradient / adjoint_hessian adds these terms."""
+        {step, observable ('mass' | 'sharp' | 'smooth' or GLIMS_OBSERVE_*), target, weight=1, level=0, smooth=1, labels=None,
+        deformed=False, scale=1.0} with J = 1/2 weight (V - target)^2, V the measure observe() returns for (observable, level,
+        smooth) on recorded step ``step``, summed over the labels whose entry of ``labels`` ([n_labels], truthy = counted) is
+        set, or over the whole domain -- in the reference configuration, or with ``deformed=True`` of the cells at
+        X + scale u_k (observe(..., deformed=True, scale)); the gradient of such a term goes through u_k as well, so it reaches
+        the coupling, E and nu (a handle with mechanics; first order only).  Every later adjoint_gradient / adjoint_hessian
+        adds these terms."""
         terms = list(terms)
-        arr = (ObservableMisfit * max(1, len(terms)))()
+        arr = (ObservableMisfit2 * max(1, len(terms)))()
         keep = []
         for k, t in enumerate(terms):
             kind = t.get("observable", "smooth")
@@ -729,13 +759,28 @@ class Handle:
                     raise ValueError("volume term %d: labels has %d entries, set_materials gave %d labels"
                                      % (k, lab.size, self.n_labels))
                 keep.append(lab)
-            arr[k] = ObservableMisfit(int(t["step"]), kind, float(t.get("level", 0.0)), float(t.get("smooth", 1.0)),
-                                      float(t.get("weight", 1.0)), float(t["target"]),
-                                      None if lab is None else lab.ctypes.data_as(C.POINTER(C.c_uint8)))
-        self._check(self.lib.glims_adjoint_observable_terms(self._h, len(terms), arr))
+            deformed = bool(t.get("deformed", False))
+            arr[k] = ObservableMisfit2(int(t["step"]), kind, float(t.get("level", 0.0)), float(t.get("smooth", 1.0)),
+                                       float(t.get("weight", 1.0)), float(t["target"]),
+                                       None if lab is None else lab.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                       1 if deformed else 0, float(t.get("scale", 1.0)) if deformed else 1.0)
+        self._check(self.lib.glims_adjoint_observable_terms2(self._h, len(terms), arr))
         del keep
         self._observable_terms = [self._observable_key(t) for t in terms]
         self._observable_from_list = bool(_from_list)
+        self._warned_folded_volumes = not any(key[-2] for key in self._observable_terms)
+
+    def has_deformed_volume_terms(self):
+        return any(key[-2] for key in getattr(self, "_observable_terms", []))
+
+    def observable_term_info2(self, k):
+        """glims_adjoint_observable_info2: observable_term_info(k) with folded (the counted cells of the displaced mesh whose
+        volume ratio vol(y) / vol(X) is not > 0 at the LAST evaluation; -1 before the first and for a reference term) and
+        min_ratio (the smallest ratio over the counted cells; NaN before the first evaluation and for a reference term)."""
+        out = np.zeros(4, dtype=np.int64)
+        V, mr = C.c_double(0.0), C.c_double(0.0)
+        self._check(self.lib.glims_adjoint_observable_info2(self._h, int(k), _ptr(out, _i64p), C.byref(V), C.byref(mr)))
+        return dict(counted=int(out[0]), cut=int(out[1]), folded=int(out[2]), V=V.value, min_ratio=mr.value)
 
     def observable_term_info(self, k):
         """Stored volume term k: a dict counted (cells of the counted labels), cut (cells the level set cut at the LAST
@@ -815,6 +860,9 @@ class Handle:
         if any(_IMAGE_KINDS.get(t["kind"]) is not None and t.get("deformed") for t in terms):
             raise NotImplementedError("adjoint_hessian: second order through the location of a deformed image term is not "
                                       "built (glims_adjoint_hessian refuses while such a term is stored)")
+        if any(t["kind"] == "obs_volume" and t.get("deformed") for t in terms):
+            raise NotImplementedError("adjoint_hessian: second order through the displacement of a deformed volume term is "
+                                      "not built (glims_adjoint_hessian refuses while such a term is stored)")
         if any(t["kind"] == "obs_volume" and OBSERVE_KINDS.get(t.get("observable", "smooth"), t.get("observable")) == 1
                for t in terms):
             raise NotImplementedError("adjoint_hessian: a sharp volume term is piecewise smooth, with jumps in its second "

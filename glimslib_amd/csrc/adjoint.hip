@@ -565,7 +565,8 @@ HessShape adjoint_shape(glims_ctx* h, int n_terms, const glims_misfit* terms, in
   s.n_send = h->n_send;
   s.spmm_blocks = P > 0 ? gl_spmm_blocks(h) : 0;
   for (int k = 0; k < n_terms; ++k) s.term_is_u.push_back(terms[k].kind == GLIMS_MISFIT_U_L2);
-  s.any_u = hess_any_u(s.term_is_u, !h->dimg_terms.empty());
+  // (a deformed image or volume term observes u_k as a displacement term does)
+  s.any_u = hess_any_u(s.term_is_u, !h->dimg_terms.empty() || gl_observable_terms_any_deformed(h));
   return s;
 }
 
@@ -811,7 +812,12 @@ int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_o
       have_u = sw.deformed_image_terms(step, c, have_u);
       if (sw.status != GLIMS_OK) break;
     }
-    gl_observable_terms_of_step(h, step, c, wk.g.p, &sw.J, 0, nullptr, 0, nullptr);
+    // a deformed volume term of a step that has no u_k yet: one solve, before the step's volume terms
+    if (!have_u && gl_observable_terms_need_u(h, step)) {
+      if (!sw.solve_uk(c)) break;
+      have_u = true;
+    }
+    gl_observable_terms_of_step(h, step, c, wk.g.p, &sw.J, 0, nullptr, 0, nullptr, wk.uk.p, wk.murhs.p);
     if (have_u && !sw.coupling_adjoint(c)) break;
     if (step == 0) {
       if (dc0) sw.c0_output(dc0);

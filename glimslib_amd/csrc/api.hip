@@ -1075,6 +1075,21 @@ int glims_adjoint_observable_info(glims_ctx* h, int k, int64_t out[2], double* V
   });
 }
 
+int glims_adjoint_observable_terms2(glims_ctx* h, int n, const glims_observable_misfit2* terms) {
+  return guarded(h, [&]() {
+    GL_REQUIRE(n >= 0 && (n == 0 || terms), "glims_adjoint_observable_terms2: bad term list");
+    gl_observable_terms_set(h, n, nullptr, terms);
+    return GLIMS_OK;
+  });
+}
+
+int glims_adjoint_observable_info2(glims_ctx* h, int k, int64_t out[4], double* V, double* min_ratio) {
+  return guarded(h, [&]() {
+    gl_observable_term_info2(h, k, out, V, min_ratio);
+    return GLIMS_OK;
+  });
+}
+
 int glims_project(glims_ctx* h, const double* rhs, double* x, int ncomp, double rtol) {
   return guarded(h, [&]() {
     GL_REQUIRE(rhs && x && ncomp >= 1 && rtol > 0.0, "bad arguments");

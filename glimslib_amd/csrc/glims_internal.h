@@ -553,7 +553,7 @@ struct ObserveState {
 };
 
 // One stored volume misfit term (glims_adjoint_observable_terms; kernels in observe.hip): J = 1/2 weight (V - target)^2 with V the
-// measure of the query over the cells of the counted labels, in the reference configuration
+// measure of the query over the cells of the counted labels, in the reference configuration or (deformed) at X + scale u_k
 struct GlObservableTerm {
   int64_t step = 0;
   int kind = 0;
@@ -562,6 +562,10 @@ struct GlObservableTerm {
   int64_t n_counted = 0;                   // cells of the counted labels
   int64_t n_cut = -1;                      // SHARP: cells the level set cut at the LAST evaluation (-1 before the first)
   double V = NAN;                          // the measure of the LAST evaluation (NaN before the first)
+  int deformed = 0;                        // the cells are measured at y = X + scale u_k; the gradient goes through u_k too
+  double scale = 1.0;
+  int64_t n_folded = -1;                   // deformed: counted cells with vol(y) / vol(X) not > 0 at the LAST evaluation
+  double min_ratio = NAN;                  // deformed: the smallest vol(y) / vol(X) over the counted cells, LAST evaluation
 };
 
 // The stored volume terms and the scratch of their passes (observe.hip): per batch of up to GLIMS_OBSERVE_MAX_QUERIES terms that
@@ -575,6 +579,15 @@ struct ObsTermState {
   dvec<unsigned int> cut_part;             // per-wave counts of cut cells, same layout
   dvec<double> vals;                       // [3][MAX_QUERIES]: V, coef = weight (V - target), weight g^T dc_j
   dvec<long long> cuts;                    // [MAX_QUERIES]
+  // a list with a deformed term (k_observe_grad_cells<D, 1>, k_observe_def_load_cells): b0 per term and cell, the combined
+  // u-load per vertex, component and cell, the per-wave folded counts and smallest ratios, and their reduced values
+  dvec<double> b0_planes;                  // [terms of the batch][n_cells]
+  dvec<double> load_planes;                // [dim + 1][dim][n_cells]
+  dvec<unsigned int> fold_part;            // [waves][MAX_QUERIES]
+  dvec<double> ratio_part;                 // [waves][MAX_QUERIES]
+  dvec<long long> folds;                   // [MAX_QUERIES]
+  dvec<double> ratios;                     // [MAX_QUERIES]
+  int64_t n_def_passes = 0;                // cumulative cell passes with DEF = 1
   int64_t n_cell_passes = 0, n_gathers = 0;   // cumulative (tools/observable_term_cost.py reads the timing lines instead)
 };
 
@@ -911,15 +924,22 @@ const double* gl_derive_sampled(glims_ctx* h, int ncomp);
 // observe.hip ---------------------------------------------------------------------------------------
 int gl_observe(glims_ctx* h, int n_src, const int64_t* src, const double* c_host, const double* u_host, int deformed,
                double scale, int n_q, const glims_observable* q, double* out);
-void gl_observable_terms_set(glims_ctx* h, int n, const glims_observable_misfit* terms);
+// (terms2 == nullptr: the old entry point's structs, stored with deformed = 0)
+void gl_observable_terms_set(glims_ctx* h, int n, const glims_observable_misfit* terms,
+                             const glims_observable_misfit2* terms2 = nullptr);
 void gl_observable_term_info(glims_ctx* h, int k, int64_t out[2], double* V);
+void gl_observable_term_info2(glims_ctx* h, int k, int64_t out[4], double* V, double* min_ratio);
+// whether a stored volume term is deformed / whether one observes `step` (the sweep solves u_k for that step then)
+bool gl_observable_terms_any_deformed(const glims_ctx* h);
+bool gl_observable_terms_need_u(const glims_ctx* h, int step);
 // the checks a gradient / Hessian call makes of the stored volume terms (GLIMS_E_USAGE): steps within 0..N, mask lengths = n_labels,
-// and with second_order no SHARP term
+// a deformed term only on a handle with mechanics, and with second_order no SHARP and no deformed term
 void gl_observable_terms_check(glims_ctx* h, int64_t N, const std::string& who, bool second_order);
 // The stored volume terms that observe `step`, in list order (c, g, dc, dg in the internal numbering): J += 1/2 w (V - t)^2,
 // g += w (V - t) grad V; with P > 0 also dg[j * ld + .] += w (grad V (grad V^T dc_j) + (V - t) H dc_j).  No such term: no launch.
+// A deformed term of the step reads uk (u_k [n_nodes][dim], solved by the caller) and adds dJ/du_k to murhs [n_nodes][dim].
 void gl_observable_terms_of_step(glims_ctx* h, int step, const double* c, double* g, double* J, int P, const double* dc,
-                                 int64_t ld, double* dg);
+                                 int64_t ld, double* dg, const double* uk = nullptr, double* murhs = nullptr);
 
 // mg.hip --------------------------------------------------------------------------------------------
 void gl_mesh_metrics(glims_ctx* h, const HostPattern& hp, const double* xyz_old);

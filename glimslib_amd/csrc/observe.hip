@@ -179,11 +179,17 @@ __global__ __launch_bounds__(256) void k_observe_sum(int64_t n_waves, int n_q, i
 //   k_observe_grad_sum    one block per term: the per-wave rows summed in a fixed order; V, weight (V - target), the cut cells
 //   k_observe_grad_rows   lane = row along cslice_ptr / celem (as k_derive_rows<NV, 1, 1>): g[row] += sum_t coef_t sum_incidences
 //                         partial -- the row owns its sum, no atomics
+// A batch with a term of the DEFORMED configuration (glims_adjoint_observable_terms2) runs k_observe_grad_cells<D, 1>, then
+//   k_observe_def_load_cells  one lane per cell: the combined planes of dJ/du_k (coefficients times the cofactors of the cell)
+//   k_observe_grad_rows<NV, D>  their row-owned gather into the load of the step's elastic adjoint
+//   k_observe_def_sum     one block per term: the folded cells and the smallest volume ratio
 struct ObsGradTerms {
   int n;
   int kind[GLIMS_OBSERVE_MAX_QUERIES];
   double level[GLIMS_OBSERVE_MAX_QUERIES], smooth[GLIMS_OBSERVE_MAX_QUERIES];
   double weight[GLIMS_OBSERVE_MAX_QUERIES], target[GLIMS_OBSERVE_MAX_QUERIES];
+  int deformed[GLIMS_OBSERVE_MAX_QUERIES];   // the term measures the cells at X + scale u (k_observe_grad_cells<D, 1>)
+  double scale[GLIMS_OBSERVE_MAX_QUERIES];
   unsigned long long mask[GLIMS_OBSERVE_MAX_QUERIES][GL_MAX_LABELS / 64];   // bit l: the cells of label l are counted
 };
 static_assert(GL_MAX_LABELS == 256, "ObsGradTerms::mask is four 64-bit words per term");
@@ -195,23 +201,38 @@ __device__ __forceinline__ bool obs_counted(const ObsGradTerms& ts, int q, int l
 }
 
 // part / cut_part: rows [waves][MAX_QUERIES], every entry written here: a wave keeps its sums in its own row of LDS (lane 0 alone
-// touches it) and stores the row once after the loop
-template <int D>
+// touches it) and stores the row once after the loop.
+// DEF = 0: every term measures the reference cells (|T| = evol); xyz, u, b0p, fold_part and ratio_part are not touched.
+// DEF = 1 (a batch with a deformed term): X and u_k at the cell's vertices are read once; a deformed term forms y = X + scale u
+// with its OWN scale and takes T = sigma vol(y), sigma = the reference orientation (as k_observe_cells<D, 1>: a folded cell
+// counts negatively); it also writes b0 as the plane b0p [term][cell] (what k_observe_def_load_cells multiplies the cofactors
+// with; 0 where the cell is not counted) and the wave's count of counted cells with vol(y) / vol(X) not > 0 and its smallest
+// such ratio into fold_part / ratio_part (rows as part).  A reference term of the same batch takes evol[e] as in DEF = 0.
+template <int D, int DEF>
 __global__ __launch_bounds__(256) void k_observe_grad_cells(int64_t n_cells, const int32_t* __restrict__ cell_nodes,
                                                             const uint8_t* __restrict__ label, const double* __restrict__ evol,
                                                             const double* __restrict__ c, ObsGradTerms ts,
                                                             double* __restrict__ planes, double* __restrict__ part,
-                                                            unsigned int* __restrict__ cut_part) {
+                                                            unsigned int* __restrict__ cut_part,
+                                                            const double* __restrict__ xyz, const double* __restrict__ u,
+                                                            double* __restrict__ b0p, unsigned int* __restrict__ fold_part,
+                                                            double* __restrict__ ratio_part) {
   constexpr int NV = D + 1;
   const int lane = threadIdx.x & (GL_WAVE - 1), wave = threadIdx.x / GL_WAVE;
   const int64_t gwave = (int64_t)blockIdx.x * GL_OBS_WAVES + wave;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   __shared__ double acc[GL_OBS_WAVES][GLIMS_OBSERVE_MAX_QUERIES];
   __shared__ unsigned int acc_cut[GL_OBS_WAVES][GLIMS_OBSERVE_MAX_QUERIES];
+  __shared__ unsigned int acc_fold[DEF ? GL_OBS_WAVES : 1][GLIMS_OBSERVE_MAX_QUERIES];
+  __shared__ double acc_ratio[DEF ? GL_OBS_WAVES : 1][GLIMS_OBSERVE_MAX_QUERIES];
   if (lane == 0)
     for (int q = 0; q < GLIMS_OBSERVE_MAX_QUERIES; ++q) {
       acc[wave][q] = 0.0;
       acc_cut[wave][q] = 0u;
+      if constexpr (DEF) {
+        acc_fold[wave][q] = 0u;
+        acc_ratio[wave][q] = INFINITY;
+      }
     }
   // (wave-uniform trip count: the 64 cells of an iteration are consecutive)
   for (int64_t base = (int64_t)blockIdx.x * blockDim.x + wave * GL_WAVE; base < n_cells; base += stride) {
@@ -221,19 +242,49 @@ __global__ __launch_bounds__(256) void k_observe_grad_cells(int64_t n_cells, con
     double cv[NV], T = 0.0;
 #pragma unroll
     for (int m = 0; m < NV; ++m) cv[m] = 0.0;
+    [[maybe_unused]] double X[NV][D], U[NV][D], volX = 1.0;
     if (valid) {
       lab = label[e];
       T = evol[e];
 #pragma unroll
-      for (int m = 0; m < NV; ++m) cv[m] = c[cell_nodes[e * NV + m]];
+      for (int m = 0; m < NV; ++m) {
+        const int32_t nd = cell_nodes[e * NV + m];
+        cv[m] = c[nd];
+        if constexpr (DEF) {
+#pragma unroll
+          for (int a = 0; a < D; ++a) {
+            X[m][a] = xyz[(int64_t)nd * D + a];
+            U[m][a] = u[(int64_t)nd * D + a];
+          }
+        }
+      }
+      if constexpr (DEF) volX = glims_oc_volume<D>(X);
     }
     for (int q = 0; q < ts.n; ++q) {
       double g[NV], v = 0.0;
 #pragma unroll
       for (int m = 0; m < NV; ++m) g[m] = 0.0;
       bool cut = false;
+      [[maybe_unused]] bool folded = false;
+      [[maybe_unused]] double ratio = INFINITY, b0_out = 0.0;
       if (valid && obs_counted(ts, q, lab)) {
         const int kind = ts.kind[q];
+        if constexpr (DEF) {
+          if (ts.deformed[q]) {
+            double y[NV][D];
+            const double sc = ts.scale[q];
+#pragma unroll
+            for (int m = 0; m < NV; ++m)
+#pragma unroll
+              for (int a = 0; a < D; ++a) y[m][a] = X[m][a] + sc * U[m][a];
+            const double vy = glims_oc_volume<D>(y);
+            T = volX < 0.0 ? -vy : vy;
+            ratio = vy / volX;
+            folded = !(ratio > 0.0);
+          } else {
+            T = evol[e];
+          }
+        }
         double b0;
         if (kind == GLIMS_OBSERVE_MASS) {
           b0 = glims_og_mass<D>(cv, g);
@@ -250,10 +301,14 @@ __global__ __launch_bounds__(256) void k_observe_grad_cells(int64_t n_cells, con
         v = T * b0;
 #pragma unroll
         for (int m = 0; m < NV; ++m) g[m] *= T;
+        if constexpr (DEF) b0_out = b0;
       }
       if (valid) {
 #pragma unroll
         for (int m = 0; m < NV; ++m) planes[((int64_t)q * NV + m) * n_cells + e] = g[m];
+        if constexpr (DEF) {
+          if (ts.deformed[q]) b0p[(int64_t)q * n_cells + e] = b0_out;
+        }
       }
       const double r = wave_sum(v);
       const unsigned int n_cut = (unsigned int)__popcll(__ballot(cut));
@@ -261,13 +316,106 @@ __global__ __launch_bounds__(256) void k_observe_grad_cells(int64_t n_cells, con
         acc[wave][q] += r;
         acc_cut[wave][q] += n_cut;
       }
+      if constexpr (DEF) {
+        if (ts.deformed[q]) {   // (wave-uniform)
+          const unsigned int n_fold = (unsigned int)__popcll(__ballot(folded));
+          // a NaN ratio (a degenerate reference cell) counts as folded and is left out of the minimum
+          double mr = ratio == ratio ? ratio : INFINITY;
+#pragma unroll
+          for (int o = GL_WAVE / 2; o > 0; o >>= 1) mr = fmin(mr, __shfl_xor(mr, o, GL_WAVE));
+          if (lane == 0) {
+            acc_fold[wave][q] += n_fold;
+            acc_ratio[wave][q] = fmin(acc_ratio[wave][q], mr);
+          }
+        }
+      }
     }
   }
   if (lane == 0)
     for (int q = 0; q < GLIMS_OBSERVE_MAX_QUERIES; ++q) {
       part[gwave * GLIMS_OBSERVE_MAX_QUERIES + q] = acc[wave][q];
       cut_part[gwave * GLIMS_OBSERVE_MAX_QUERIES + q] = acc_cut[wave][q];
+      if constexpr (DEF) {
+        fold_part[gwave * GLIMS_OBSERVE_MAX_QUERIES + q] = acc_fold[wave][q];
+        ratio_part[gwave * GLIMS_OBSERVE_MAX_QUERIES + q] = acc_ratio[wave][q];
+      }
     }
+}
+
+// The u-load of a batch's deformed terms, one lane per cell (launched after k_observe_grad_sum, which leaves coef_t = weight_t
+// (V_t - target_t) on the device): lp [a][k][cell] = sum over the deformed terms t of coef_t s_t sigma b0_t d vol(y(s_t)) / d y_a,k
+// with the cofactors of glims_og_volume_grad at the term's own y = X + s_t u -- 8 (d+1) d n_cells bytes whatever the number of
+// terms.  Every entry is written (zeros where no term counts the cell); k_observe_grad_rows<NV, D> gathers the planes into murhs.
+template <int D>
+__global__ __launch_bounds__(256) void k_observe_def_load_cells(int64_t n_cells, const int32_t* __restrict__ cell_nodes,
+                                                                const double* __restrict__ xyz, const double* __restrict__ u,
+                                                                ObsGradTerms ts, const double* __restrict__ b0p,
+                                                                const double* __restrict__ coef, double* __restrict__ lp) {
+  constexpr int NV = D + 1;
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n_cells) return;
+  double X[NV][D], U[NV][D], acc[NV][D];
+#pragma unroll
+  for (int m = 0; m < NV; ++m) {
+    const int32_t nd = cell_nodes[e * NV + m];
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+      X[m][a] = xyz[(int64_t)nd * D + a];
+      U[m][a] = u[(int64_t)nd * D + a];
+      acc[m][a] = 0.0;
+    }
+  }
+  const double sigma = glims_oc_volume<D>(X) < 0.0 ? -1.0 : 1.0;
+  for (int q = 0; q < ts.n; ++q) {
+    if (!ts.deformed[q]) continue;
+    const double sc = ts.scale[q];
+    const double f = coef[q] * sc * sigma * b0p[(int64_t)q * n_cells + e];
+    if (f == 0.0) continue;   // (a cell the term does not count, b0 = 0 or scale = 0: exact zeros are added nowhere)
+    double y[NV][D], dv[NV][D];
+#pragma unroll
+    for (int m = 0; m < NV; ++m)
+#pragma unroll
+      for (int a = 0; a < D; ++a) y[m][a] = X[m][a] + sc * U[m][a];
+    glims_og_volume_grad<D>(y, dv);
+#pragma unroll
+    for (int m = 0; m < NV; ++m)
+#pragma unroll
+      for (int a = 0; a < D; ++a) acc[m][a] += f * dv[m][a];
+  }
+#pragma unroll
+  for (int m = 0; m < NV; ++m)
+#pragma unroll
+    for (int a = 0; a < D; ++a) lp[((int64_t)m * D + a) * n_cells + e] = acc[m][a];
+}
+
+// One block per term q of a batch with deformed terms: folds[q] = the folded counted cells, ratios[q] = the smallest ratio
+// (+inf where no cell is counted), from the per-wave rows; integer sums and minima: the order does not matter
+__global__ __launch_bounds__(256) void k_observe_def_sum(int64_t n_waves, const unsigned int* __restrict__ fold_part,
+                                                         const double* __restrict__ ratio_part, long long* __restrict__ folds,
+                                                         double* __restrict__ ratios) {
+  __shared__ double sm[256];
+  __shared__ long long sc[256];
+  const int q = blockIdx.x;
+  double mr = INFINITY;
+  long long cnt = 0;
+  for (int64_t w = threadIdx.x; w < n_waves; w += 256) {
+    mr = fmin(mr, ratio_part[w * GLIMS_OBSERVE_MAX_QUERIES + q]);
+    cnt += fold_part[w * GLIMS_OBSERVE_MAX_QUERIES + q];
+  }
+  sm[threadIdx.x] = mr;
+  sc[threadIdx.x] = cnt;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) {
+      sm[threadIdx.x] = fmin(sm[threadIdx.x], sm[threadIdx.x + o]);
+      sc[threadIdx.x] += sc[threadIdx.x + o];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    folds[q] = sc[0];
+    ratios[q] = sm[0];
+  }
 }
 
 // One Hessian direction dc: per term the wave's sum of grad V_T . dc|_T (from the planes of k_observe_grad_cells) into `part`,
@@ -367,7 +515,9 @@ __global__ __launch_bounds__(256) void k_observe_grad_sum(int64_t n_waves, const
 // g[row] += sum_t (coef_a[t] A_t + coef_b[t] B_t), A_t / B_t = the row's sums, along its incidence list in list order, of the
 // planes pa / pb [t][a][cell] at the vertex a the row is in that cell (pb == nullptr: the first part alone).  The terms' sum
 // starts from 0 and is added to g once: a list sent in two parts gives the bits of the whole.
-template <int NV>
+// NC = 1 is the gather of the c-partials.  NC = D gathers ONE combined term with NC components per vertex, planes pa
+// [a][comp][cell], into g[row * NC + comp] (the u-load of k_observe_def_load_cells into murhs): n_t = 1, pb = nullptr.
+template <int NV, int NC>
 __global__ __launch_bounds__(256) void k_observe_grad_rows(int64_t n_own, int64_t n_cells,
                                                            const int64_t* __restrict__ cslice_ptr,
                                                            const int32_t* __restrict__ celem,
@@ -380,6 +530,25 @@ __global__ __launch_bounds__(256) void k_observe_grad_rows(int64_t n_own, int64_
   const int64_t s = row >> 6, lane = row & 63;
   const int64_t cbase = cslice_ptr[s];
   const int clen = (int)((cslice_ptr[s + 1] - cbase) >> 6);
+  if constexpr (NC > 1) {
+    double A[NC];
+#pragma unroll
+    for (int q = 0; q < NC; ++q) A[q] = 0.0;
+    for (int k = 0; k < clen; ++k) {
+      const int32_t e = celem[cbase + (int64_t)k * GL_WAVE + lane];
+      if (e < 0) continue;
+      int a = -1;
+#pragma unroll
+      for (int m = 0; m < NV; ++m)
+        if (cell_nodes[(int64_t)e * NV + m] == (int32_t)row) a = m;
+      if (a < 0) continue;
+#pragma unroll
+      for (int q = 0; q < NC; ++q) A[q] += pa[((int64_t)a * NC + q) * n_cells + e];
+    }
+#pragma unroll
+    for (int q = 0; q < NC; ++q) g[row * NC + q] += A[q];
+    return;
+  }
   double A[GLIMS_OBSERVE_MAX_QUERIES], B[GLIMS_OBSERVE_MAX_QUERIES];
 #pragma unroll
   for (int t = 0; t < GLIMS_OBSERVE_MAX_QUERIES; ++t) A[t] = B[t] = 0.0;
@@ -631,9 +800,46 @@ void ensure_term_scratch(glims_ctx* h, int nt, bool second, int64_t n_waves) {
   os.cuts.alloc((size_t)GLIMS_OBSERVE_MAX_QUERIES);
 }
 
+// The further scratch of a list with a deformed term, with the same refusal: b0 per term of a pass and cell (8 n_cells bytes per
+// term) and the combined u-load (8 (dim+1) dim n_cells bytes per pass), the per-wave folded counts and ratios.  A list without
+// such a term never comes here.
+void ensure_def_scratch(glims_ctx* h, int nt, int64_t n_waves) {
+  ObsTermState& os = h->obs_terms;
+  const size_t b0n = (size_t)nt * (size_t)h->n_cells;
+  const size_t ldn = (size_t)(h->dim + 1) * h->dim * (size_t)h->n_cells;
+  const size_t rows = (size_t)n_waves * GLIMS_OBSERVE_MAX_QUERIES;
+  size_t need = 0;
+  if (os.b0_planes.n < b0n) {
+    os.b0_planes.release();
+    need += b0n * sizeof(double);
+  }
+  if (os.load_planes.n < ldn) {
+    os.load_planes.release();
+    need += ldn * sizeof(double);
+  }
+  if (os.fold_part.n < rows) need += rows * (sizeof(double) + sizeof(unsigned int));
+  if (need) {
+    size_t fr = 0, tot = 0;
+    GL_HIP(hipMemGetInfo(&fr, &tot));
+    if (need > fr)
+      throw glims_error(GLIMS_E_HIP, "glims_adjoint_observable_terms2: the b0 planes of " + std::to_string(nt) +
+                                         " deformed volume terms and the displacement load over " + std::to_string(h->n_cells) +
+                                         " cells need about " + std::to_string(need >> 20) + " MiB of device memory, " +
+                                         std::to_string(fr >> 20) + " MiB are free");
+  }
+  if (os.b0_planes.n < b0n) os.b0_planes.alloc(b0n);
+  if (os.load_planes.n < ldn) os.load_planes.alloc(ldn);
+  if (os.fold_part.n < rows) {
+    os.fold_part.alloc(rows);
+    os.ratio_part.alloc(rows);
+  }
+  os.folds.alloc((size_t)GLIMS_OBSERVE_MAX_QUERIES);
+  os.ratios.alloc((size_t)GLIMS_OBSERVE_MAX_QUERIES);
+}
+
 template <int D>
 void observable_batch(glims_ctx* h, const std::vector<int>& batch, int nt_alloc, const double* c, double* g, double* J, int P,
-                      const double* dc, int64_t ld, double* dg, int step) {
+                      const double* dc, int64_t ld, double* dg, int step, const double* uk, double* murhs) {
   ObsTermState& os = h->obs_terms;
   constexpr int NV = D + 1, MQ = GLIMS_OBSERVE_MAX_QUERIES;
   const int nt = (int)batch.size();
@@ -643,10 +849,16 @@ void observable_batch(glims_ctx* h, const std::vector<int>& batch, int nt_alloc,
     ts.kind[q] = GLIMS_OBSERVE_MASS;
     ts.level[q] = ts.weight[q] = ts.target[q] = 0.0;
     ts.smooth[q] = 1.0;
+    ts.deformed[q] = 0;
+    ts.scale[q] = 0.0;
     for (int w = 0; w < GL_MAX_LABELS / 64; ++w) ts.mask[q][w] = 0ull;
   }
+  bool any_def = false;
   for (int q = 0; q < nt; ++q) {
     const GlObservableTerm& t = os.terms[(size_t)batch[(size_t)q]];
+    ts.deformed[q] = t.deformed;
+    ts.scale[q] = t.deformed ? t.scale : 0.0;
+    any_def = any_def || t.deformed;
     ts.kind[q] = t.kind;
     ts.level[q] = t.level;
     ts.smooth[q] = t.kind == GLIMS_OBSERVE_SMOOTH ? t.smooth : 1.0;
@@ -655,16 +867,19 @@ void observable_batch(glims_ctx* h, const std::vector<int>& batch, int nt_alloc,
     for (int l = 0; l < GL_MAX_LABELS; ++l)
       if (t.mask.empty() || (l < (int)t.mask.size() && t.mask[(size_t)l])) ts.mask[q][l >> 6] |= 1ull << (l & 63);
   }
-  double vals[2 * MQ] = {0.0};
-  long long cuts[MQ] = {0};
+  if (any_def && !(uk && murhs)) throw std::logic_error("observable_batch: a deformed volume term without u_k");
+  double vals[2 * MQ] = {0.0}, ratios[MQ];
+  long long cuts[MQ] = {0}, folds[MQ] = {0};
+  for (int q = 0; q < MQ; ++q) ratios[q] = INFINITY;
   if (h->n_cells > 0) {
     const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(GL_OBS_BLOCKS, grid_of(h->n_cells)));
     const int64_t n_waves = (int64_t)nb * GL_OBS_WAVES;
     ensure_term_scratch(h, nt_alloc, P > 0, n_waves);
+    if (gl_observable_terms_any_deformed(h)) ensure_def_scratch(h, nt_alloc, n_waves);   // (from the list: no step reallocates)
     const int32_t* cn = gl_ensure_cell_nodes(h);
     // GLIMS_OBSERVABLE_TIMING: an event pair around the cell pass (with its sum) and one around the gather, one line per batch
     const bool timed = getenv("GLIMS_OBSERVABLE_TIMING") != nullptr;
-    float ms_cells = 0.f, ms_rows = 0.f;
+    float ms_cells = 0.f, ms_rows = 0.f, ms_load = 0.f, ms_urows = 0.f;
     auto tick = [&]() {
       if (timed) GL_HIP(hipEventRecord(h->ev_a, h->st));
     };
@@ -675,15 +890,23 @@ void observable_batch(glims_ctx* h, const std::vector<int>& batch, int nt_alloc,
       GL_HIP(hipEventElapsedTime(ms, h->ev_a, h->ev_b));
     };
     tick();
-    hipLaunchKernelGGL(k_observe_grad_cells<D>, dim3(nb), dim3(256), 0, h->st, h->n_cells, cn, h->label.p, h->evol.p, c, ts,
-                       os.planes.p, os.part.p, os.cut_part.p);
+    if (any_def) {
+      hipLaunchKernelGGL((k_observe_grad_cells<D, 1>), dim3(nb), dim3(256), 0, h->st, h->n_cells, cn, h->label.p, h->evol.p, c,
+                         ts, os.planes.p, os.part.p, os.cut_part.p, h->xyz_new.p, uk, os.b0_planes.p, os.fold_part.p,
+                         os.ratio_part.p);
+      os.n_def_passes++;
+    } else {
+      hipLaunchKernelGGL((k_observe_grad_cells<D, 0>), dim3(nb), dim3(256), 0, h->st, h->n_cells, cn, h->label.p, h->evol.p, c,
+                         ts, os.planes.p, os.part.p, os.cut_part.p, (const double*)nullptr, (const double*)nullptr,
+                         (double*)nullptr, (unsigned int*)nullptr, (double*)nullptr);
+    }
     GL_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_observe_grad_sum, dim3(nt), dim3(256), 0, h->st, n_waves, os.part.p, os.cut_part.p, ts, 0, os.vals.p,
                        os.cuts.p);
     GL_CHECK_LAUNCH();
     tock(&ms_cells);
     tick();
-    hipLaunchKernelGGL(k_observe_grad_rows<NV>, dim3(grid_of(h->n_own)), dim3(256), 0, h->st, h->n_own, h->n_cells,
+    hipLaunchKernelGGL((k_observe_grad_rows<NV, 1>), dim3(grid_of(h->n_own)), dim3(256), 0, h->st, h->n_own, h->n_cells,
                        h->pat.cslice_ptr.p, h->pat.celem.p, cn, nt, os.planes.p, os.vals.p + MQ, (const double*)nullptr,
                        (const double*)nullptr, g);
     GL_CHECK_LAUNCH();
@@ -692,6 +915,29 @@ void observable_batch(glims_ctx* h, const std::vector<int>& batch, int nt_alloc,
     os.n_gathers++;
     if (timed)
       fprintf(stderr, "glims observable terms: step %d  terms %d  cells %.4f ms  gather %.4f ms\n", step, nt, ms_cells, ms_rows);
+    if (any_def) {
+      // dJ/du_k of the batch's deformed terms: the combined cofactor planes (the coefficients are on the device), then their
+      // row-owned gather into murhs; the folded counts and smallest ratios of the cell pass
+      tick();
+      hipLaunchKernelGGL(k_observe_def_load_cells<D>, dim3(grid_of(h->n_cells)), dim3(256), 0, h->st, h->n_cells, cn,
+                         h->xyz_new.p, uk, ts, os.b0_planes.p, os.vals.p + MQ, os.load_planes.p);
+      GL_CHECK_LAUNCH();
+      tock(&ms_load);
+      tick();
+      hipLaunchKernelGGL((k_observe_grad_rows<NV, D>), dim3(grid_of(h->n_own)), dim3(256), 0, h->st, h->n_own, h->n_cells,
+                         h->pat.cslice_ptr.p, h->pat.celem.p, cn, 1, os.load_planes.p, (const double*)nullptr,
+                         (const double*)nullptr, (const double*)nullptr, murhs);
+      GL_CHECK_LAUNCH();
+      tock(&ms_urows);
+      hipLaunchKernelGGL(k_observe_def_sum, dim3(nt), dim3(256), 0, h->st, n_waves, os.fold_part.p, os.ratio_part.p,
+                         os.folds.p, os.ratios.p);
+      GL_CHECK_LAUNCH();
+      GL_HIP(hipMemcpyAsync(folds, os.folds.p, sizeof(folds), hipMemcpyDeviceToHost, h->st));
+      GL_HIP(hipMemcpyAsync(ratios, os.ratios.p, sizeof(ratios), hipMemcpyDeviceToHost, h->st));
+      if (timed)
+        fprintf(stderr, "glims observable terms: step %d  deformed pass  load %.4f ms  u-gather %.4f ms\n", step, ms_load,
+                ms_urows);
+    }
     for (int p = 0; p < P; ++p) {
       // dg_p += sum_t (weight_t (g_t^T dc_p) G_t + weight_t (V_t - target_t) H_t dc_p)
       hipLaunchKernelGGL(k_observe_second_cells<D>, dim3(nb), dim3(256), 0, h->st, h->n_cells, cn, h->label.p, h->evol.p, c,
@@ -700,7 +946,7 @@ void observable_batch(glims_ctx* h, const std::vector<int>& batch, int nt_alloc,
       hipLaunchKernelGGL(k_observe_grad_sum, dim3(nt), dim3(256), 0, h->st, n_waves, os.part.p, os.cut_part.p, ts, 1, os.vals.p,
                          os.cuts.p);
       GL_CHECK_LAUNCH();
-      hipLaunchKernelGGL(k_observe_grad_rows<NV>, dim3(grid_of(h->n_own)), dim3(256), 0, h->st, h->n_own, h->n_cells,
+      hipLaunchKernelGGL((k_observe_grad_rows<NV, 1>), dim3(grid_of(h->n_own)), dim3(256), 0, h->st, h->n_own, h->n_cells,
                          h->pat.cslice_ptr.p, h->pat.celem.p, cn, nt, os.planes.p, os.vals.p + 2 * MQ, os.planes2.p,
                          os.vals.p + MQ, dg + (size_t)p * ld);
       GL_CHECK_LAUNCH();
@@ -715,6 +961,10 @@ void observable_batch(glims_ctx* h, const std::vector<int>& batch, int nt_alloc,
     GlObservableTerm& t = os.terms[(size_t)batch[(size_t)q]];
     t.V = vals[q];
     t.n_cut = t.kind == GLIMS_OBSERVE_SHARP ? (int64_t)cuts[q] : -1;
+    if (t.deformed) {
+      t.n_folded = (int64_t)folds[q];
+      t.min_ratio = std::isfinite(ratios[q]) ? ratios[q] : NAN;   // (no counted cell: nothing to take the minimum of)
+    }
     const double r = t.V - t.target;
     *J += 0.5 * t.weight * (r * r);
   }
@@ -722,21 +972,37 @@ void observable_batch(glims_ctx* h, const std::vector<int>& batch, int nt_alloc,
 
 }  // namespace
 
-void gl_observable_terms_set(glims_ctx* h, int n, const glims_observable_misfit* terms) {
-  const std::string who = "glims_adjoint_observable_terms";
+void gl_observable_terms_set(glims_ctx* h, int n, const glims_observable_misfit* terms1,
+                             const glims_observable_misfit2* terms2) {
+  const std::string who = terms2 ? "glims_adjoint_observable_terms2" : "glims_adjoint_observable_terms";
   ObsTermState& os = h->obs_terms;
-  GL_REQUIRE(n >= 0 && (n == 0 || terms), who + ": bad term list");
-  if (n == 0) {   // clearing is always possible; the planes go with the list
-    os.terms.clear();
+  GL_REQUIRE(n >= 0 && (n == 0 || terms1 || terms2), who + ": bad term list");
+  auto drop_planes = [&os]() {
     os.planes.release();
     os.planes2.release();
+    os.b0_planes.release();
+    os.load_planes.release();
+  };
+  if (n == 0) {   // clearing is always possible; the planes go with the list
+    os.terms.clear();
+    drop_planes();
     return;
+  }
+  // one internal form for both entry points: the old struct is a term of the reference configuration
+  std::vector<glims_observable_misfit2> terms((size_t)n);
+  for (int k = 0; k < n; ++k) {
+    if (terms2) {
+      terms[(size_t)k] = terms2[k];
+    } else {
+      const glims_observable_misfit& t = terms1[k];
+      terms[(size_t)k] = {t.step, t.kind, t.level, t.smooth, t.weight, t.target, t.labels, 0, 1.0};
+    }
   }
   GL_REQUIRE(h->world <= 1, who + ": not available on a partitioned handle (world > 1)");
   GL_REQUIRE(h->is_setup, who + " before glims_setup");
   GL_REQUIRE(h->n_labels > 0, who + " before glims_set_materials");
   for (int k = 0; k < n; ++k) {
-    const glims_observable_misfit& t = terms[k];
+    const glims_observable_misfit2& t = terms[(size_t)k];
     const std::string tk = " of term " + std::to_string(k);
     GL_REQUIRE(t.step >= 0, who + ": negative step" + tk);
     GL_REQUIRE(t.kind >= GLIMS_OBSERVE_MASS && t.kind <= GLIMS_OBSERVE_SMOOTH,
@@ -745,12 +1011,18 @@ void gl_observable_terms_set(glims_ctx* h, int n, const glims_observable_misfit*
     GL_REQUIRE(t.kind != GLIMS_OBSERVE_SMOOTH || t.smooth > 0.0, who + ": smooth" + tk + " must be positive");
     GL_REQUIRE(std::isfinite(t.weight), who + ": weight" + tk + " is not finite");
     GL_REQUIRE(std::isfinite(t.target), who + ": target" + tk + " is not finite");
+    GL_REQUIRE(!t.deformed || (h->have_mech && h->U.p),
+               who + ": term " + std::to_string(k) + " is deformed: the deformed configuration needs the displacement, "
+                     "glims_setup(with_mechanics=1) first");
+    GL_REQUIRE(!t.deformed || std::isfinite(t.scale), who + ": scale" + tk + " is not finite");
   }
   ensure_label_cells(h);
   std::vector<GlObservableTerm> fresh((size_t)n);
   for (int k = 0; k < n; ++k) {
-    const glims_observable_misfit& t = terms[k];
+    const glims_observable_misfit2& t = terms[(size_t)k];
     GlObservableTerm& f = fresh[(size_t)k];
+    f.deformed = t.deformed ? 1 : 0;
+    f.scale = t.deformed ? t.scale : 1.0;
     f.step = t.step;
     f.kind = t.kind;
     f.level = t.level;
@@ -767,8 +1039,32 @@ void gl_observable_terms_set(glims_ctx* h, int n, const glims_observable_misfit*
   }
   os.terms.swap(fresh);
   // (the next call sizes the planes for the largest batch of THIS list)
-  os.planes.release();
-  os.planes2.release();
+  drop_planes();
+}
+
+void gl_observable_term_info2(glims_ctx* h, int k, int64_t out[4], double* V, double* min_ratio) {
+  const ObsTermState& os = h->obs_terms;
+  GL_REQUIRE(out && V && min_ratio, "glims_adjoint_observable_info2: null output");
+  GL_REQUIRE(k >= 0 && k < (int)os.terms.size(), "glims_adjoint_observable_info2: no stored term " + std::to_string(k));
+  const GlObservableTerm& t = os.terms[(size_t)k];
+  out[0] = t.n_counted;
+  out[1] = t.n_cut;
+  out[2] = t.deformed ? t.n_folded : -1;
+  out[3] = 0;
+  *V = t.V;
+  *min_ratio = t.deformed ? t.min_ratio : NAN;
+}
+
+bool gl_observable_terms_any_deformed(const glims_ctx* h) {
+  for (const GlObservableTerm& t : h->obs_terms.terms)
+    if (t.deformed) return true;
+  return false;
+}
+
+bool gl_observable_terms_need_u(const glims_ctx* h, int step) {
+  for (const GlObservableTerm& t : h->obs_terms.terms)
+    if (t.deformed && t.step == step) return true;
+  return false;
 }
 
 void gl_observable_term_info(glims_ctx* h, int k, int64_t out[2], double* V) {
@@ -793,11 +1089,17 @@ void gl_observable_terms_check(glims_ctx* h, int64_t N, const std::string& who, 
     GL_REQUIRE(!second_order || t.kind != GLIMS_OBSERVE_SHARP,
                who + ": stored volume term " + std::to_string(k) + " is SHARP: its measure is piecewise smooth, with jumps in "
                      "the second derivative where the level set crosses a vertex; second order is built for MASS and SMOOTH");
+    GL_REQUIRE(!t.deformed || h->have_mech,
+               who + ": stored volume term " + std::to_string(k) + " is deformed: it needs glims_setup(with_mechanics=1)");
+    GL_REQUIRE(!second_order || !t.deformed,
+               who + ": stored volume term " + std::to_string(k) + " is deformed: second order through the displacement is "
+                     "not built (a Hessian without it would be wrong); clear the list with "
+                     "glims_adjoint_observable_terms2(h, 0, NULL) or store reference-configuration terms first");
   }
 }
 
 void gl_observable_terms_of_step(glims_ctx* h, int step, const double* c, double* g, double* J, int P, const double* dc,
-                                 int64_t ld, double* dg) {
+                                 int64_t ld, double* dg, const double* uk, double* murhs) {
   ObsTermState& os = h->obs_terms;
   std::vector<int> here;
   for (size_t k = 0; k < os.terms.size(); ++k)
@@ -813,7 +1115,7 @@ void gl_observable_terms_of_step(glims_ctx* h, int step, const double* c, double
   for (size_t b = 0; b < here.size(); b += GLIMS_OBSERVE_MAX_QUERIES) {
     const std::vector<int> batch(here.begin() + (long)b,
                                  here.begin() + (long)std::min(here.size(), b + GLIMS_OBSERVE_MAX_QUERIES));
-    if (h->dim == 2) observable_batch<2>(h, batch, nt_alloc, c, g, J, P, dc, ld, dg, step);
-    else observable_batch<3>(h, batch, nt_alloc, c, g, J, P, dc, ld, dg, step);
+    if (h->dim == 2) observable_batch<2>(h, batch, nt_alloc, c, g, J, P, dc, ld, dg, step, uk, murhs);
+    else observable_batch<3>(h, batch, nt_alloc, c, g, J, P, dc, ld, dg, step, uk, murhs);
   }
 }

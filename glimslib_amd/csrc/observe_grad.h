@@ -2,7 +2,9 @@
 // simplex with P1 vertex values c_0 .. c_d and the query (MASS / SHARP / SMOOTH) of observe_clip.h, the fraction b0 = V_T / |T| and
 //   g[i]  = d b0 / d c_i                          (the measure's gradient is |T| g)
 //   Hd[i] = sum_j d2 b0 / (d c_i d c_j) dc_j      (MASS: 0; SMOOTH: the rule's own second derivative; SHARP: not defined here)
-// Everything is in barycentric terms: no positions enter, |T| multiplies at the caller's.
+// Everything is in barycentric terms: no positions enter, |T| multiplies at the caller's.  For the terms of the deformed
+// configuration, whose |T| depends on the displacement, glims_og_volume_grad gives the derivative of the cell volume by the
+// vertex positions (tests/observe_def_grad_check.cpp runs it on the host).
 //
 //   MASS    b0 = mean(c):  g[i] = 1 / (d+1).
 //   SMOOTH  b0 = sum_q w_q h(v_q), v_q = sum_a lam_qa c_a, h(v) = 1/2 (tanh((v - level) / smooth) + 1):
@@ -151,6 +153,35 @@ GLIMS_OC_HD double glims_og_smooth(double level, double smooth, const double (&c
     }
   }
   return b0;
+}
+
+// The signed volume of observe_clip.h by the vertex positions: dvol[a][k] = d glims_oc_volume(p) / d p[a][k], the cofactor vector
+// of vertex a.  2-D: half the opposite edge rotated by a quarter turn; 3-D: one sixth of the cross product of two edges of the
+// opposite face, with the sign of the vertex.  Every vertex gets its own expression (none is minus the sum of the others) and
+// nothing is divided: a degenerate simplex has finite cofactors, and sum_a dvol[a] = 0 holds to rounding.  The volume is
+// multilinear in the vertex positions, so a central difference in one component reproduces dvol up to rounding.
+template <int D>
+GLIMS_OC_HD void glims_og_volume_grad(const double (&p)[D + 1][D], double (&dvol)[D + 1][D]) {
+  if constexpr (D == 2) {
+    dvol[0][0] = 0.5 * (p[1][1] - p[2][1]);
+    dvol[0][1] = 0.5 * (p[2][0] - p[1][0]);
+    dvol[1][0] = 0.5 * (p[2][1] - p[0][1]);
+    dvol[1][1] = 0.5 * (p[0][0] - p[2][0]);
+    dvol[2][0] = 0.5 * (p[0][1] - p[1][1]);
+    dvol[2][1] = 0.5 * (p[1][0] - p[0][0]);
+  } else {
+    // vertex a: sign_a / 6 (p_j - p_i) x (p_k - p_i) with (i, j, k) the other three in ascending order, sign = -, +, -, +
+    constexpr int oth[4][3] = {{1, 2, 3}, {0, 2, 3}, {0, 1, 3}, {0, 1, 2}};
+    for (int a = 0; a < 4; ++a) {
+      const int i = oth[a][0], j = oth[a][1], k = oth[a][2];
+      const double e0 = p[j][0] - p[i][0], e1 = p[j][1] - p[i][1], e2 = p[j][2] - p[i][2];
+      const double f0 = p[k][0] - p[i][0], f1 = p[k][1] - p[i][1], f2 = p[k][2] - p[i][2];
+      const double s = (a & 1) ? (1.0 / 6.0) : (-1.0 / 6.0);
+      dvol[a][0] = s * (e1 * f2 - e2 * f1);
+      dvol[a][1] = s * (e2 * f0 - e0 * f2);
+      dvol[a][2] = s * (e0 * f1 - e1 * f0);
+    }
+  }
 }
 
 // one query of one simplex, host side (the rule from derive_quadrature.h's static tables): b0, g and (dc != nullptr, MASS / SMOOTH)

@@ -139,6 +139,9 @@ class ReducedFunctional:
         self._evaluate(m)
         if self._H is None:
             terms = self.terms_builder(self.sim, self._n_steps)
+            if any(t.get("deformed") and t.get("kind") == "obs_volume" for t in terms):
+                raise NotImplementedError("ReducedFunctional.hessian: second order through the displacement of a deformed "
+                                          "volume term is not built; use a first-order method (L-BFGS-B)")
             if any(t.get("deformed") for t in terms):
                 raise NotImplementedError("ReducedFunctional.hessian: second order through the location of a deformed image "
                                           "term is not built; use a first-order method (L-BFGS-B)")

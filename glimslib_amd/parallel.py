@@ -447,6 +447,9 @@ class DistributedHandle:
     def observable_term_info(self, k):
         self._no_volume_terms()
 
+    def observable_term_info2(self, k):
+        self._no_volume_terms()
+
     # -- samplers (collective: every rank passes the same points) --------------------------------------------------------
     def sampler_points(self, xyz, deformed_by=None, scale=1.0):
         self._no_deformed(deformed_by)

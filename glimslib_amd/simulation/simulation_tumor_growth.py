@@ -398,7 +398,8 @@ class TumorGrowth(FenicsSimulation):
             cache[1][key] = (term, image, mask)   # (image and mask stay alive: their identity is the key)
         return cache[1][key][0]
 
-    def volume_term(self, step, target, threshold=0.12, kind='smooth', smooth=0.01, tissues=None, weight=1.0):
+    def volume_term(self, step, target, threshold=0.12, kind='smooth', smooth=0.01, tissues=None, weight=1.0, deformed=False,
+                    scale=1.0):
         """
         A misfit term that compares a tumour VOLUME of recorded step `step` with the number `target`:
         1/2 weight (V - target)^2, V the volume compute_from_conc_for_each_time_step(threshold, 'volume', kind, smooth) reports
@@ -409,9 +410,22 @@ class TumorGrowth(FenicsSimulation):
         adds weight (V - target) dV/dc to the backward sweep.  'sharp' is first order only (V is piecewise smooth: its
         second derivative jumps where the level set crosses a mesh node); 'smooth' and 'mass' also serve adjoint_hessian.
         Partitioned runs raise NotImplementedError when the term is used.
+
+        deformed=True: V is the volume of the DEFORMED configuration x = X + scale u(X) of that step, the number
+        compute_from_conc_for_each_time_step(deformed=True) reports and the one a scan shows.  Its gradient goes through the
+        displacement as well, so such terms carry the coupling, E and nu (parameters a reference-configuration volume gives an
+        exactly zero gradient).  A 'sharp' term whose threshold lies below every concentration (threshold=-1) has the
+        indicator 1 everywhere: it is the deformed volume of the counted `tissues` themselves -- the volume of a compressed
+        neighbouring tissue, such as the ventricles under mass effect.  Needs a run with mechanics (ValueError otherwise) and
+        one GPU (NotImplementedError on a partitioned run); first order only (adjoint_hessian raises NotImplementedError).
+        With deformed=False the returned dict is the one described above, without further keys.
         """
         if kind not in _backend.OBSERVE_KINDS:
             raise ValueError("volume_term: kind must be one of %s" % (tuple(_backend.OBSERVE_KINDS),))
+        if deformed and self._backend is not None and not isinstance(self._backend, _backend.Handle):
+            raise NotImplementedError("volume_term(deformed=True) is not available on partitioned runs")
+        if deformed and not self.solver.mechanics:
+            raise ValueError("volume_term(deformed=True) needs a run with mechanics (the cells move with the displacement)")
         mask = None
         if tissues is not None:
             if isinstance(tissues, str):
@@ -425,8 +439,11 @@ class TumorGrowth(FenicsSimulation):
                     raise ValueError("volume_term: unknown tissue %r (known: %s)" % (name, sorted(ids)))
                 if tid < n_labels:          # (a tissue that no cell carries counts nothing)
                     mask[tid] = 1
-        return dict(step=int(step), kind='obs_volume', observable=kind, level=float(threshold), smooth=float(smooth),
+        term = dict(step=int(step), kind='obs_volume', observable=kind, level=float(threshold), smooth=float(smooth),
                     target=float(target), weight=float(weight), labels=mask)
+        if deformed:
+            term.update(deformed=True, scale=float(scale))
+        return term
 
     DERIVED_IMAGES = ('pressure', 'van_mises_stress', 'total_jacobian', 'growth_induced_jacobian',
                       'concentration_deformed_config', 'log_growth', 'displacement_norm', 'strain_tensor', 'stress_tensor')
@@ -595,6 +612,9 @@ class TumorGrowth(FenicsSimulation):
             if np.any(np.asarray(flux) != 0.0):
                 raise NotImplementedError("adjoint_hessian: von Neumann data on the concentration scale with D; "
                                           "second derivatives in D are not available for such a run")
+        if any(t.get('deformed') and t.get('kind') == 'obs_volume' for t in terms):
+            raise NotImplementedError("adjoint_hessian: second order through the displacement of a deformed volume term "
+                                      "(volume_term(deformed=True)) is not built; use a first-order method")
         if any(t.get('deformed') for t in terms):
             raise NotImplementedError("adjoint_hessian: second order through the location of a deformed image term "
                                       "(image_term(deformed=True)) is not built; use a first-order method")

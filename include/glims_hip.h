@@ -29,7 +29,8 @@
  *   GLIMS_OBSERVE_TIMING any value: glims_observe puts a HIP event pair around each source's pass and prints one line per source
  *                        with the time on stderr (a synchronisation per source)
  *   GLIMS_OBSERVABLE_TIMING any value: the stored volume misfit terms put a HIP event pair around their cell pass and around their
- *                        gather and print one line per pass with both times on stderr (tools/observable_term_cost.py)
+ *                        gather and print one line per pass with both times on stderr (tools/observable_term_cost.py); a pass
+ *                        with a deformed term adds a line with the times of its load kernel and of the load's gather
  *   GLIMS_HOST_THREADS   OpenMP team of the host-side symbolic phase (default: the CPUs this process may use,
  *                        divided by the ranks on the host)
  *   GLIMS_HOST_SYMBOLIC  TEST HOOK: glims_create runs the host (OpenMP) implementation of the symbolic phase instead of
@@ -1039,7 +1040,25 @@ int glims_observe_info(const glims_ctx* h, int64_t out[4]);
  * GLIMS_E_USAGE with a reason, the old list left in place: a partitioned handle (world > 1), a call before glims_setup, an unknown
  * kind, smooth <= 0 of a SMOOTH term, a level, weight or target that is not finite, a negative step.  A gradient or Hessian call
  * refuses a term whose step is beyond the trajectory and a stored mask whose length is no longer n_labels.
- * Not built: centre-of-mass and moment terms, volumes of the deformed configuration, partitioned handles, second order for SHARP. */
+ *
+ * Volumes of the DEFORMED configuration (glims_adjoint_observable_terms2, deformed = 1): a volume measured on a scan is a volume
+ * of x = X + u(X).  Such a term measures every counted cell at y = X + scale u_k, u_k = K_el^-1 (G c_k + f) solved inside the
+ * sweep (1e-12), as glims_observe(..., deformed = 1, scale) does:
+ *     V = sum_T sigma_T vol(y_T) b0_T(c_k),    sigma_T = +-1 the reference orientation of the cell (a folded cell counts negatively),
+ *     dJ/dc_k,i = weight (V - target) sum_{T holds i} sigma_T vol(y_T) d b0_T / d c_i,
+ *     dJ/du_k,a = weight (V - target) scale sum_{T holds a} sigma_T b0_T d vol(y_T) / d y_a,
+ * d vol / d y_a the cofactor vector of vertex a (csrc/observe_grad.h, glims_og_volume_grad; nothing is divided, a degenerate
+ * displaced cell has finite cofactors).  V is a polynomial in u: no kink, no point location.  dJ/du_k joins the load of the
+ * elastic adjoint of step k (one u_k solve and one adjoint solve per observed step, shared with the step's displacement and
+ * deformed image terms), so volume data now carry the coupling, E and nu.  A SHARP term whose level lies below every
+ * concentration (-1, say) has b0 = 1 and no c-partials: it is the deformed volume of the counted tissues -- the ventricles
+ * under mass effect.  The terms stay ONE stored list: a batch of up to GLIMS_OBSERVE_MAX_QUERIES terms of a step may mix both
+ * kinds, list order is kept, and a batch without a deformed term runs the kernels and gives the bits it gave before.  Extra
+ * scratch of a list with a deformed term: 8 n_cells bytes per term of a pass (b0) and 8 (dim+1) dim n_cells bytes (the combined
+ * load), through the same hipMemGetInfo refusal.  Second order through u is not built: while a deformed volume term is stored,
+ * glims_adjoint_hessian, _hessian_spmd and _hessian_full return GLIMS_E_USAGE.  Further refusals of _terms2 (GLIMS_E_USAGE,
+ * the old list left in place): a deformed term on a handle set up without mechanics, a scale that is not finite.
+ * Not built: centre-of-mass and moment terms, partitioned handles, second order for SHARP and for deformed terms. */
 typedef struct glims_observable_misfit {
   int64_t step;              /* recorded step observed (0 = c_0) */
   int     kind;              /* GLIMS_OBSERVE_MASS / _SHARP / _SMOOTH */
@@ -1051,6 +1070,23 @@ int glims_adjoint_observable_terms(glims_ctx* h, int n, const glims_observable_m
 /* stored term k: out[0] the number of counted cells, out[1] the cells the level set cut at the LAST evaluation (-1 before the
  * first, and for MASS / SMOOTH), *V the last V (NaN before the first) */
 int glims_adjoint_observable_info(glims_ctx* h, int k, int64_t out[2], double* V);
+/* the fields of glims_observable_misfit, then the configuration the cells are measured in */
+typedef struct glims_observable_misfit2 {
+  int64_t step;
+  int     kind;
+  double  level, smooth;
+  double  weight, target;
+  const uint8_t* labels;
+  int     deformed;          /* 0: the reference configuration (as glims_observable_misfit); 1: the cells at X + scale u_k */
+  double  scale;             /* deformed = 1: multiplies u_k (finite); ignored otherwise */
+} glims_observable_misfit2;
+/* replaces the SAME stored list as glims_adjoint_observable_terms (which stores its terms with deformed = 0); n = 0 clears */
+int glims_adjoint_observable_terms2(glims_ctx* h, int n, const glims_observable_misfit2* terms);
+/* stored term k: out[0] counted cells, out[1] cut cells (as _info), out[2] the counted cells folded (vol(y) / vol(X) not > 0)
+ * at the LAST evaluation, out[3] = 0; *V the last V, *min_ratio the smallest vol(y) / vol(X) over the counted cells (NaN when
+ * no cell is counted).  Before the first evaluation out[2] = -1, *V = NaN, *min_ratio = NaN; a reference term keeps
+ * out[2] = -1 and *min_ratio = NaN. */
+int glims_adjoint_observable_info2(glims_ctx* h, int k, int64_t out[4], double* V, double* min_ratio);
 
 /* ---- single-node multi-GPU (one process per GPU, RCCL over xGMI) ------------------------------------- */
 
