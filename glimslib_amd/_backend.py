@@ -157,6 +157,12 @@ class ObservableMisfit2(C.Structure):
     _fields_ = ObservableMisfit._fields_ + [("deformed", C.c_int), ("scale", C.c_double)]
 
 
+class ObservableMisfit3(C.Structure):
+    """glims_observable_misfit3: ObservableMisfit2, then what the term compares (moment 0: the volume with target; 1: the
+    centre of mass M / V with target_x [dim])."""
+    _fields_ = ObservableMisfit2._fields_ + [("moment", C.c_int), ("target_x", C.c_double * 3)]
+
+
 _dp = C.POINTER(C.c_double)
 _i32p = C.POINTER(C.c_int32)
 _i64p = C.POINTER(C.c_int64)
@@ -226,6 +232,8 @@ SIGNATURES = {
     "glims_adjoint_observable_info": (C.c_int, [_h, C.c_int, _i64p, _dp]),
     "glims_adjoint_observable_terms2": (C.c_int, [_h, C.c_int, C.POINTER(ObservableMisfit2)]),
     "glims_adjoint_observable_info2": (C.c_int, [_h, C.c_int, _i64p, _dp, _dp]),
+    "glims_adjoint_observable_terms3": (C.c_int, [_h, C.c_int, C.POINTER(ObservableMisfit3)]),
+    "glims_adjoint_observable_info3": (C.c_int, [_h, C.c_int, _i64p, _dp, _dp, _dp]),
     "glims_comm_unique_id": (C.c_int, [C.c_char_p]),
     "glims_comm_init": (C.c_int, [_h, C.c_int, C.c_int, C.c_char_p]),
     "glims_comm_selftest": (C.c_int, [_h]),
@@ -692,8 +700,21 @@ class Handle:
     def has_deformed_image_terms(self):
         return bool(self._deformed_terms)
 
+    def _warn_empty_com(self):
+        """Once per stored list: the last gradient call found the measure of a centre-of-mass term empty."""
+        if getattr(self, "_warned_empty_com", True):
+            return
+        for k, key in enumerate(self._observable_terms):
+            if isinstance(key[5], tuple) and self.observable_term_info(k)["empty"]:
+                import warnings
+                warnings.warn("centre-of-mass term %d: its measure was empty (V not > 0) at the last evaluation; the term "
+                              "contributed J = 0 and no gradient there" % k, RuntimeWarning, stacklevel=4)
+                self._warned_empty_com = True
+                return
+
     def _warn_folded(self):
         """Once per stored list: the last gradient call located points in a mesh with folded cells."""
+        self._warn_empty_com()
         self._warn_folded_volumes()
         if self._warned_folded or not self._deformed_terms:
             return
@@ -730,8 +751,10 @@ class Handle:
         lab = t.get("labels")
         kind = t.get("observable", "smooth")
         deformed = bool(t.get("deformed", False))
+        com = t.get("kind") == "obs_com"
         return (int(t["step"]), OBSERVE_KINDS.get(kind, kind), float(t.get("level", 0.0)), float(t.get("smooth", 1.0)),
-                float(t.get("weight", 1.0)), float(t["target"]),
+                float(t.get("weight", 1.0)),
+                ("com",) + tuple(float(v) for v in np.ravel(t["target"])) if com else float(t["target"]),
                 None if lab is None else tuple(bool(v) for v in np.ravel(lab)),
                 deformed, float(t.get("scale", 1.0)) if deformed else 1.0)
 
@@ -743,9 +766,15 @@ class Handle:
         set, or over the whole domain -- in the reference configuration, or with ``deformed=True`` of the cells at
         X + scale u_k (observe(..., deformed=True, scale)); the gradient of such a term goes through u_k as well, so it reaches
         the coupling, E and nu (a handle with mechanics; first order only).  Every later adjoint_gradient / adjoint_hessian
-        adds these terms."""
+        adds these terms.
+
+        A dict with kind='obs_com' is a CENTRE-OF-MASS term (glims_adjoint_observable_terms3): J = 1/2 weight |M / V - target|^2
+        with target = [x, y(, z)] and V, M the measure and first moments observe() returns for the same query, labels and
+        configuration.  Where V is not > 0 at an evaluation the term contributes nothing there (observable_term_info(k)
+        ['empty']); first order only.  A list without such a term goes through glims_adjoint_observable_terms2 as before."""
         terms = list(terms)
-        arr = (ObservableMisfit2 * max(1, len(terms)))()
+        any_com = any(t.get("kind") == "obs_com" for t in terms)
+        arr = ((ObservableMisfit3 if any_com else ObservableMisfit2) * max(1, len(terms)))()
         keep = []
         for k, t in enumerate(terms):
             kind = t.get("observable", "smooth")
@@ -760,15 +789,46 @@ class Handle:
                                      % (k, lab.size, self.n_labels))
                 keep.append(lab)
             deformed = bool(t.get("deformed", False))
-            arr[k] = ObservableMisfit2(int(t["step"]), kind, float(t.get("level", 0.0)), float(t.get("smooth", 1.0)),
-                                       float(t.get("weight", 1.0)), float(t["target"]),
-                                       None if lab is None else lab.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                       1 if deformed else 0, float(t.get("scale", 1.0)) if deformed else 1.0)
-        self._check(self.lib.glims_adjoint_observable_terms2(self._h, len(terms), arr))
+            com = t.get("kind") == "obs_com"
+            fields = (int(t["step"]), kind, float(t.get("level", 0.0)), float(t.get("smooth", 1.0)),
+                      float(t.get("weight", 1.0)), 0.0 if com else float(t["target"]),
+                      None if lab is None else lab.ctypes.data_as(C.POINTER(C.c_uint8)),
+                      1 if deformed else 0, float(t.get("scale", 1.0)) if deformed else 1.0)
+            if any_com:
+                tx = np.zeros(3)
+                if com:
+                    x = np.asarray(t["target"], dtype=np.float64).reshape(-1)
+                    if x.shape != (self.dim,):
+                        raise ValueError("centre-of-mass term %d: target has %d entries, the mesh has dimension %d"
+                                         % (k, x.size, self.dim))
+                    tx[:self.dim] = x
+                arr[k] = ObservableMisfit3(*fields, int(t.get("moment", 1)) if com else 0, (C.c_double * 3)(*tx))
+            else:
+                arr[k] = ObservableMisfit2(*fields)
+        if any_com:
+            self._check(self.lib.glims_adjoint_observable_terms3(self._h, len(terms), arr))
+        else:
+            self._check(self.lib.glims_adjoint_observable_terms2(self._h, len(terms), arr))
         del keep
         self._observable_terms = [self._observable_key(t) for t in terms]
         self._observable_from_list = bool(_from_list)
         self._warned_folded_volumes = not any(key[-2] for key in self._observable_terms)
+        self._warned_empty_com = not any_com
+
+    def has_com_terms(self):
+        return any(isinstance(key[5], tuple) for key in getattr(self, "_observable_terms", []))
+
+    def observable_term_info3(self, k):
+        """glims_adjoint_observable_info3: observable_term_info2(k) with empty (the LAST evaluation found the measure of this
+        centre-of-mass term not > 0) and com ([dim]: the last M / V; NaN before the first evaluation, when empty and for a
+        volume term)."""
+        out = np.zeros(4, dtype=np.int64)
+        V, mr = C.c_double(0.0), C.c_double(0.0)
+        com = np.full(3, np.nan)
+        self._check(self.lib.glims_adjoint_observable_info3(self._h, int(k), _ptr(out, _i64p), C.byref(V), C.byref(mr),
+                                                            _ptr(com, _dp)))
+        return dict(counted=int(out[0]), cut=int(out[1]), folded=int(out[2]), V=V.value, min_ratio=mr.value,
+                    empty=bool(out[3]), com=com[:self.dim].copy())
 
     def has_deformed_volume_terms(self):
         return any(key[-2] for key in getattr(self, "_observable_terms", []))
@@ -784,7 +844,12 @@ class Handle:
 
     def observable_term_info(self, k):
         """Stored volume term k: a dict counted (cells of the counted labels), cut (cells the level set cut at the LAST
-        evaluation; -1 before the first and for 'mass' / 'smooth'), V (the last measure; NaN before the first)."""
+        evaluation; -1 before the first and for 'mass' / 'smooth'), V (the last measure; NaN before the first).  A
+        centre-of-mass term gains com and empty (observable_term_info3)."""
+        keys = getattr(self, "_observable_terms", [])
+        if 0 <= int(k) < len(keys) and isinstance(keys[int(k)][5], tuple):
+            info = self.observable_term_info3(k)
+            return dict(counted=info["counted"], cut=info["cut"], V=info["V"], com=info["com"], empty=info["empty"])
         out = np.zeros(2, dtype=np.int64)
         V = C.c_double(0.0)
         self._check(self.lib.glims_adjoint_observable_info(self._h, int(k), _ptr(out, _i64p), C.byref(V)))
@@ -794,11 +859,11 @@ class Handle:
         """The nodal terms of a mixed list; its image terms become the handle's stored lists -- the fixed ones and those with
         deformed=True -- and its volume terms (kind 'obs_volume') the third, each re-sent only on a change."""
         terms = list(terms)
-        volume = [t for t in terms if t["kind"] == "obs_volume"]
+        volume = [t for t in terms if t["kind"] in ("obs_volume", "obs_com")]
         if volume or getattr(self, "_observable_from_list", False):
             if [self._observable_key(t) for t in volume] != getattr(self, "_observable_terms", []):
                 self.set_observable_terms(volume, _from_list=True)
-            terms = [t for t in terms if t["kind"] != "obs_volume"]
+            terms = [t for t in terms if t["kind"] not in ("obs_volume", "obs_com")]
         moving = [t for t in terms if _IMAGE_KINDS.get(t["kind"]) is not None and t.get("deformed")]
         if moving or getattr(self, "_deformed_from_list", False):
             if [self._deformed_key(t) for t in moving] != [k for k, _ in self._deformed_terms]:
@@ -859,6 +924,9 @@ class Handle:
             raise ValueError("adjoint_hessian: E / nu are first order here; directions in 'E' / 'nu' go to adjoint_hessian_full")
         if any(_IMAGE_KINDS.get(t["kind"]) is not None and t.get("deformed") for t in terms):
             raise NotImplementedError("adjoint_hessian: second order through the location of a deformed image term is not "
+                                      "built (glims_adjoint_hessian refuses while such a term is stored)")
+        if any(t["kind"] == "obs_com" for t in terms):
+            raise NotImplementedError("adjoint_hessian: second order of a centre-of-mass term (the quotient M / V) is not "
                                       "built (glims_adjoint_hessian refuses while such a term is stored)")
         if any(t["kind"] == "obs_volume" and t.get("deformed") for t in terms):
             raise NotImplementedError("adjoint_hessian: second order through the displacement of a deformed volume term is "

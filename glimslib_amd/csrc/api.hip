@@ -1090,6 +1090,21 @@ int glims_adjoint_observable_info2(glims_ctx* h, int k, int64_t out[4], double* 
   });
 }
 
+int glims_adjoint_observable_terms3(glims_ctx* h, int n, const glims_observable_misfit3* terms) {
+  return guarded(h, [&]() {
+    GL_REQUIRE(n >= 0 && (n == 0 || terms), "glims_adjoint_observable_terms3: bad term list");
+    gl_observable_terms_set(h, n, nullptr, nullptr, terms);
+    return GLIMS_OK;
+  });
+}
+
+int glims_adjoint_observable_info3(glims_ctx* h, int k, int64_t out[4], double* V, double* min_ratio, double com[3]) {
+  return guarded(h, [&]() {
+    gl_observable_term_info3(h, k, out, V, min_ratio, com);
+    return GLIMS_OK;
+  });
+}
+
 int glims_project(glims_ctx* h, const double* rhs, double* x, int ncomp, double rtol) {
   return guarded(h, [&]() {
     GL_REQUIRE(rhs && x && ncomp >= 1 && rtol > 0.0, "bad arguments");

@@ -566,6 +566,11 @@ struct GlObservableTerm {
   double scale = 1.0;
   int64_t n_folded = -1;                   // deformed: counted cells with vol(y) / vol(X) not > 0 at the LAST evaluation
   double min_ratio = NAN;                  // deformed: the smallest vol(y) / vol(X) over the counted cells, LAST evaluation
+  // a centre-of-mass term (glims_adjoint_observable_terms3, moment = 1): J = 1/2 weight |M / V - target_x|^2; `target` is unused
+  int moment = 0;
+  double target_x[3] = {0.0, 0.0, 0.0};
+  double com[3] = {NAN, NAN, NAN};         // M / V of the LAST evaluation (NaN before the first and when the measure was empty)
+  int empty = 0;                           // the LAST evaluation found V not > 0: the term contributed nothing
 };
 
 // The stored volume terms and the scratch of their passes (observe.hip): per batch of up to GLIMS_OBSERVE_MAX_QUERIES terms that
@@ -587,6 +592,13 @@ struct ObsTermState {
   dvec<double> ratio_part;                 // [waves][MAX_QUERIES]
   dvec<long long> folds;                   // [MAX_QUERIES]
   dvec<double> ratios;                     // [MAX_QUERIES]
+  // a list with a centre-of-mass term (k_observe_mom_cells, k_observe_mom_sum): the per-wave sums of V and M and, per term of
+  // the batch, GL_OBS_MOM doubles (V, M, X, alpha, J, empty) that stay on the device between the passes; with a DEFORMED
+  // centre-of-mass term also sigma vol(y) b[1 + m] per term, vertex and cell (the second part of its u-load)
+  dvec<double> mom_part;                   // [waves][MAX_QUERIES][4]
+  dvec<double> mom_vals;                   // [MAX_QUERIES][GL_OBS_MOM]
+  dvec<double> b1_planes;                  // [terms of the batch][dim + 1][n_cells]
+  int64_t n_mom_passes = 0;                // cumulative moments passes
   int64_t n_def_passes = 0;                // cumulative cell passes with DEF = 1
   int64_t n_cell_passes = 0, n_gathers = 0;   // cumulative (tools/observable_term_cost.py reads the timing lines instead)
 };
@@ -926,9 +938,10 @@ int gl_observe(glims_ctx* h, int n_src, const int64_t* src, const double* c_host
                double scale, int n_q, const glims_observable* q, double* out);
 // (terms2 == nullptr: the old entry point's structs, stored with deformed = 0)
 void gl_observable_terms_set(glims_ctx* h, int n, const glims_observable_misfit* terms,
-                             const glims_observable_misfit2* terms2 = nullptr);
+                             const glims_observable_misfit2* terms2 = nullptr, const glims_observable_misfit3* terms3 = nullptr);
 void gl_observable_term_info(glims_ctx* h, int k, int64_t out[2], double* V);
 void gl_observable_term_info2(glims_ctx* h, int k, int64_t out[4], double* V, double* min_ratio);
+void gl_observable_term_info3(glims_ctx* h, int k, int64_t out[4], double* V, double* min_ratio, double com[3]);
 // whether a stored volume term is deformed / whether one observes `step` (the sweep solves u_k for that step then)
 bool gl_observable_terms_any_deformed(const glims_ctx* h);
 bool gl_observable_terms_need_u(const glims_ctx* h, int step);

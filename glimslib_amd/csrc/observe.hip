@@ -183,6 +183,11 @@ __global__ __launch_bounds__(256) void k_observe_sum(int64_t n_waves, int n_q, i
 //   k_observe_def_load_cells  one lane per cell: the combined planes of dJ/du_k (coefficients times the cofactors of the cell)
 //   k_observe_grad_rows<NV, D>  their row-owned gather into the load of the step's elastic adjoint
 //   k_observe_def_sum     one block per term: the folded cells and the smallest volume ratio
+// A batch with a CENTRE-OF-MASS term (glims_adjoint_observable_terms3) first runs
+//   k_observe_mom_cells   one lane per cell: per such term the wave's sums of V_T and M_T (the arithmetic of k_observe_cells)
+//   k_observe_mom_sum     one block per term: V, M in a fixed order, then X = M / V, alpha, J and the empty flag, left on the device
+// and then the COM = 1 instances of k_observe_grad_cells / k_observe_def_load_cells, which weight the first-moment partials
+// with psi = alpha . (p - X) and write them into the same planes; gather and u-gather are unchanged
 struct ObsGradTerms {
   int n;
   int kind[GLIMS_OBSERVE_MAX_QUERIES];
@@ -191,7 +196,12 @@ struct ObsGradTerms {
   int deformed[GLIMS_OBSERVE_MAX_QUERIES];   // the term measures the cells at X + scale u (k_observe_grad_cells<D, 1>)
   double scale[GLIMS_OBSERVE_MAX_QUERIES];
   unsigned long long mask[GLIMS_OBSERVE_MAX_QUERIES][GL_MAX_LABELS / 64];   // bit l: the cells of label l are counted
+  int moment[GLIMS_OBSERVE_MAX_QUERIES];     // a centre-of-mass term (target_x in place of target)
+  double target_x[GLIMS_OBSERVE_MAX_QUERIES][3];
 };
+// what k_observe_mom_sum leaves on the device per centre-of-mass term of a batch
+constexpr int GL_OBS_MOM = 12;       // V, M[3], X[3], alpha[3], J, empty
+constexpr int GL_OBS_MOM_X = 4, GL_OBS_MOM_ALPHA = 7, GL_OBS_MOM_J = 10, GL_OBS_MOM_EMPTY = 11;
 static_assert(GL_MAX_LABELS == 256, "ObsGradTerms::mask is four 64-bit words per term");
 
 __device__ __forceinline__ bool obs_counted(const ObsGradTerms& ts, int q, int lab) {
@@ -208,7 +218,12 @@ __device__ __forceinline__ bool obs_counted(const ObsGradTerms& ts, int q, int l
 // counts negatively); it also writes b0 as the plane b0p [term][cell] (what k_observe_def_load_cells multiplies the cofactors
 // with; 0 where the cell is not counted) and the wave's count of counted cells with vol(y) / vol(X) not > 0 and its smallest
 // such ratio into fold_part / ratio_part (rows as part).  A reference term of the same batch takes evol[e] as in DEF = 0.
-template <int D, int DEF>
+// COM = 1 (a batch with a centre-of-mass term, after k_observe_mom_sum has left X and alpha in `mom`): X is read whatever DEF is;
+// such a term forms psi_m = alpha . (p_m - X) at its own positions p (X, or y when deformed) and writes T sum_m psi_m
+// d b[1 + m] / d c_a into the planes (glims_og_moment_*); its entry of `part` is V again.  A deformed one writes B = sum_m
+// b[1 + m] psi_m in place of b0 and T b[1 + m] as the planes b1p [term][a][cell].  The volume terms of the batch are computed
+// as with COM = 0.
+template <int D, int DEF, int COM>
 __global__ __launch_bounds__(256) void k_observe_grad_cells(int64_t n_cells, const int32_t* __restrict__ cell_nodes,
                                                             const uint8_t* __restrict__ label, const double* __restrict__ evol,
                                                             const double* __restrict__ c, ObsGradTerms ts,
@@ -216,7 +231,8 @@ __global__ __launch_bounds__(256) void k_observe_grad_cells(int64_t n_cells, con
                                                             unsigned int* __restrict__ cut_part,
                                                             const double* __restrict__ xyz, const double* __restrict__ u,
                                                             double* __restrict__ b0p, unsigned int* __restrict__ fold_part,
-                                                            double* __restrict__ ratio_part) {
+                                                            double* __restrict__ ratio_part, const double* __restrict__ mom,
+                                                            double* __restrict__ b1p) {
   constexpr int NV = D + 1;
   const int lane = threadIdx.x & (GL_WAVE - 1), wave = threadIdx.x / GL_WAVE;
   const int64_t gwave = (int64_t)blockIdx.x * GL_OBS_WAVES + wave;
@@ -250,11 +266,11 @@ __global__ __launch_bounds__(256) void k_observe_grad_cells(int64_t n_cells, con
       for (int m = 0; m < NV; ++m) {
         const int32_t nd = cell_nodes[e * NV + m];
         cv[m] = c[nd];
-        if constexpr (DEF) {
+        if constexpr (DEF || COM) {
 #pragma unroll
           for (int a = 0; a < D; ++a) {
             X[m][a] = xyz[(int64_t)nd * D + a];
-            U[m][a] = u[(int64_t)nd * D + a];
+            if constexpr (DEF) U[m][a] = u[(int64_t)nd * D + a];
           }
         }
       }
@@ -262,8 +278,14 @@ __global__ __launch_bounds__(256) void k_observe_grad_cells(int64_t n_cells, con
     }
     for (int q = 0; q < ts.n; ++q) {
       double g[NV], v = 0.0;
+      [[maybe_unused]] double b1_out[NV];
+      [[maybe_unused]] bool is_mom = false;
+      if constexpr (COM) is_mom = ts.moment[q] != 0;   // (wave-uniform)
 #pragma unroll
-      for (int m = 0; m < NV; ++m) g[m] = 0.0;
+      for (int m = 0; m < NV; ++m) {
+        g[m] = 0.0;
+        if constexpr (COM) b1_out[m] = 0.0;
+      }
       bool cut = false;
       [[maybe_unused]] bool folded = false;
       [[maybe_unused]] double ratio = INFINITY, b0_out = 0.0;
@@ -285,29 +307,79 @@ __global__ __launch_bounds__(256) void k_observe_grad_cells(int64_t n_cells, con
             T = evol[e];
           }
         }
-        double b0;
-        if (kind == GLIMS_OBSERVE_MASS) {
-          b0 = glims_og_mass<D>(cv, g);
-        } else if (kind == GLIMS_OBSERVE_SHARP) {
-          int n_in = 0;
-          b0 = glims_og_sharp<D>(ts.level[q], cv, g, &n_in);
-          cut = n_in > 0 && n_in < NV;
-        } else {
-          if constexpr (D == 2)
-            b0 = glims_og_smooth<2, GLIMS_DQ2_N>(ts.level[q], ts.smooth[q], cv, c_oq2_lam, c_oq2_w, g, nullptr, nullptr);
-          else
-            b0 = glims_og_smooth<3, GLIMS_DQ3_N>(ts.level[q], ts.smooth[q], cv, c_oq3_lam, c_oq3_w, g, nullptr, nullptr);
+        double b0 = 0.0;
+        bool done = false;
+        if constexpr (COM) {
+          if (is_mom) {
+            const double* mv = mom + q * GL_OBS_MOM;
+            double psi[NV], b[D + 2];
+#pragma unroll
+            for (int m = 0; m < NV; ++m) {
+              double s = 0.0;
+#pragma unroll
+              for (int a = 0; a < D; ++a) {
+                double pa = X[m][a];
+                if constexpr (DEF) {
+                  if (ts.deformed[q]) pa = X[m][a] + ts.scale[q] * U[m][a];
+                }
+                s += mv[GL_OBS_MOM_ALPHA + a] * (pa - mv[GL_OBS_MOM_X + a]);
+              }
+              psi[m] = s;
+            }
+            if (kind == GLIMS_OBSERVE_MASS) {
+              glims_og_moment_mass<D>(cv, psi, b, g);
+            } else if (kind == GLIMS_OBSERVE_SHARP) {
+              const int n_in = glims_og_moment_sharp<D>(ts.level[q], cv, psi, b, g);
+              cut = n_in > 0 && n_in < NV;
+            } else {
+              if constexpr (D == 2)
+                glims_og_moment_smooth<2, GLIMS_DQ2_N>(ts.level[q], ts.smooth[q], cv, c_oq2_lam, c_oq2_w, psi, b, g);
+              else
+                glims_og_moment_smooth<3, GLIMS_DQ3_N>(ts.level[q], ts.smooth[q], cv, c_oq3_lam, c_oq3_w, psi, b, g);
+            }
+            b0 = b[0];
+            double B = 0.0;
+#pragma unroll
+            for (int m = 0; m < NV; ++m) {
+              B += b[1 + m] * psi[m];
+              b1_out[m] = T * b[1 + m];
+            }
+            if constexpr (DEF) b0_out = B;
+            done = true;
+          }
+        }
+        if (!done) {
+          if (kind == GLIMS_OBSERVE_MASS) {
+            b0 = glims_og_mass<D>(cv, g);
+          } else if (kind == GLIMS_OBSERVE_SHARP) {
+            int n_in = 0;
+            b0 = glims_og_sharp<D>(ts.level[q], cv, g, &n_in);
+            cut = n_in > 0 && n_in < NV;
+          } else {
+            if constexpr (D == 2)
+              b0 = glims_og_smooth<2, GLIMS_DQ2_N>(ts.level[q], ts.smooth[q], cv, c_oq2_lam, c_oq2_w, g, nullptr, nullptr);
+            else
+              b0 = glims_og_smooth<3, GLIMS_DQ3_N>(ts.level[q], ts.smooth[q], cv, c_oq3_lam, c_oq3_w, g, nullptr, nullptr);
+          }
+          if constexpr (DEF) b0_out = b0;
         }
         v = T * b0;
 #pragma unroll
         for (int m = 0; m < NV; ++m) g[m] *= T;
-        if constexpr (DEF) b0_out = b0;
       }
       if (valid) {
 #pragma unroll
         for (int m = 0; m < NV; ++m) planes[((int64_t)q * NV + m) * n_cells + e] = g[m];
         if constexpr (DEF) {
-          if (ts.deformed[q]) b0p[(int64_t)q * n_cells + e] = b0_out;
+          if (ts.deformed[q]) {
+            b0p[(int64_t)q * n_cells + e] = b0_out;
+            if constexpr (COM) {
+              if (is_mom) {
+#pragma unroll
+                for (int m = 0; m < NV; ++m) b1p[((int64_t)q * NV + m) * n_cells + e] = b1_out[m];
+              }
+            }
+          }
         }
       }
       const double r = wave_sum(v);
@@ -346,11 +418,14 @@ __global__ __launch_bounds__(256) void k_observe_grad_cells(int64_t n_cells, con
 // (V_t - target_t) on the device): lp [a][k][cell] = sum over the deformed terms t of coef_t s_t sigma b0_t d vol(y(s_t)) / d y_a,k
 // with the cofactors of glims_og_volume_grad at the term's own y = X + s_t u -- 8 (d+1) d n_cells bytes whatever the number of
 // terms.  Every entry is written (zeros where no term counts the cell); k_observe_grad_rows<NV, D> gathers the planes into murhs.
-template <int D>
+// COM = 1: a deformed centre-of-mass term has coef = 1 (0 when empty) and B in place of b0, and adds coef s T b[1 + m] alpha_k
+// from the planes b1p and the alpha k_observe_mom_sum left in `mom`.
+template <int D, int COM>
 __global__ __launch_bounds__(256) void k_observe_def_load_cells(int64_t n_cells, const int32_t* __restrict__ cell_nodes,
                                                                 const double* __restrict__ xyz, const double* __restrict__ u,
                                                                 ObsGradTerms ts, const double* __restrict__ b0p,
-                                                                const double* __restrict__ coef, double* __restrict__ lp) {
+                                                                const double* __restrict__ coef, double* __restrict__ lp,
+                                                                const double* __restrict__ b1p, const double* __restrict__ mom) {
   constexpr int NV = D + 1;
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n_cells) return;
@@ -370,6 +445,17 @@ __global__ __launch_bounds__(256) void k_observe_def_load_cells(int64_t n_cells,
     if (!ts.deformed[q]) continue;
     const double sc = ts.scale[q];
     const double f = coef[q] * sc * sigma * b0p[(int64_t)q * n_cells + e];
+    if constexpr (COM) {
+      if (ts.moment[q]) {
+        const double fs = coef[q] * sc;
+#pragma unroll
+        for (int m = 0; m < NV; ++m) {
+          const double w = fs * b1p[((int64_t)q * NV + m) * n_cells + e];
+#pragma unroll
+          for (int a = 0; a < D; ++a) acc[m][a] += w * mom[q * GL_OBS_MOM + GL_OBS_MOM_ALPHA + a];
+        }
+      }
+    }
     if (f == 0.0) continue;   // (a cell the term does not count, b0 = 0 or scale = 0: exact zeros are added nowhere)
     double y[NV][D], dv[NV][D];
 #pragma unroll
@@ -415,6 +501,150 @@ __global__ __launch_bounds__(256) void k_observe_def_sum(int64_t n_waves, const 
   if (threadIdx.x == 0) {
     folds[q] = sc[0];
     ratios[q] = sm[0];
+  }
+}
+
+// The moments pass of a batch with a centre-of-mass term: the arithmetic of k_observe_cells restricted to the batch's masks.  One
+// lane per cell over the grid of k_observe_grad_cells; per centre-of-mass term the wave's sums of V_T = T b[0] and
+// M_T,a = T sum_m b[1 + m] p_m,a (glims_oc_*, glims_oc_map) into its own row of mom_part [waves][MAX_QUERIES][4], every entry
+// written.  T and p as in k_observe_grad_cells: evol and X, or sigma vol(y) and y = X + scale u for a deformed term (DEF = 1).
+template <int D, int DEF>
+__global__ __launch_bounds__(256) void k_observe_mom_cells(int64_t n_cells, const int32_t* __restrict__ cell_nodes,
+                                                           const uint8_t* __restrict__ label, const double* __restrict__ evol,
+                                                           const double* __restrict__ c, ObsGradTerms ts,
+                                                           const double* __restrict__ xyz, const double* __restrict__ u,
+                                                           double* __restrict__ mom_part) {
+  constexpr int NV = D + 1;
+  const int lane = threadIdx.x & (GL_WAVE - 1), wave = threadIdx.x / GL_WAVE;
+  const int64_t gwave = (int64_t)blockIdx.x * GL_OBS_WAVES + wave;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  __shared__ double acc[GL_OBS_WAVES][GLIMS_OBSERVE_MAX_QUERIES][4];
+  if (lane == 0)
+    for (int q = 0; q < GLIMS_OBSERVE_MAX_QUERIES; ++q)
+      for (int k = 0; k < 4; ++k) acc[wave][q][k] = 0.0;
+  // (wave-uniform trip count: the 64 cells of an iteration are consecutive)
+  for (int64_t base = (int64_t)blockIdx.x * blockDim.x + wave * GL_WAVE; base < n_cells; base += stride) {
+    const int64_t e = base + lane;
+    const bool valid = e < n_cells;
+    int lab = 0;
+    double cv[NV], X[NV][D], Tref = 0.0;
+    [[maybe_unused]] double U[NV][D], volX = 1.0;
+#pragma unroll
+    for (int m = 0; m < NV; ++m) {
+      cv[m] = 0.0;
+#pragma unroll
+      for (int a = 0; a < D; ++a) {
+        X[m][a] = 0.0;
+        if constexpr (DEF) U[m][a] = 0.0;
+      }
+    }
+    if (valid) {
+      lab = label[e];
+      Tref = evol[e];
+#pragma unroll
+      for (int m = 0; m < NV; ++m) {
+        const int32_t nd = cell_nodes[e * NV + m];
+        cv[m] = c[nd];
+#pragma unroll
+        for (int a = 0; a < D; ++a) {
+          X[m][a] = xyz[(int64_t)nd * D + a];
+          if constexpr (DEF) U[m][a] = u[(int64_t)nd * D + a];
+        }
+      }
+      if constexpr (DEF) volX = glims_oc_volume<D>(X);
+    }
+    for (int q = 0; q < ts.n; ++q) {
+      if (!ts.moment[q]) continue;   // (wave-uniform)
+      double o[NV];
+#pragma unroll
+      for (int k = 0; k < NV; ++k) o[k] = 0.0;
+      if (valid && obs_counted(ts, q, lab)) {
+        double p[NV][D], T = Tref;
+#pragma unroll
+        for (int m = 0; m < NV; ++m)
+#pragma unroll
+          for (int a = 0; a < D; ++a) p[m][a] = X[m][a];
+        if constexpr (DEF) {
+          if (ts.deformed[q]) {
+            const double sc = ts.scale[q];
+#pragma unroll
+            for (int m = 0; m < NV; ++m)
+#pragma unroll
+              for (int a = 0; a < D; ++a) p[m][a] = X[m][a] + sc * U[m][a];
+            const double vy = glims_oc_volume<D>(p);
+            T = volX < 0.0 ? -vy : vy;
+          }
+        }
+        double b[D + 2];
+        const int kind = ts.kind[q];
+        if (kind == GLIMS_OBSERVE_MASS) {
+          glims_oc_mass<D>(cv, b);
+        } else if (kind == GLIMS_OBSERVE_SHARP) {
+          glims_oc_sharp<D>(ts.level[q], cv, b);
+        } else {
+          if constexpr (D == 2) glims_oc_smooth<2, GLIMS_DQ2_N>(ts.level[q], ts.smooth[q], cv, c_oq2_lam, c_oq2_w, b);
+          else glims_oc_smooth<3, GLIMS_DQ3_N>(ts.level[q], ts.smooth[q], cv, c_oq3_lam, c_oq3_w, b);
+        }
+        glims_oc_map<D>(T, p, b, o);
+      }
+#pragma unroll
+      for (int k = 0; k < NV; ++k) {
+        const double r = wave_sum(o[k]);
+        if (lane == 0) acc[wave][q][k] += r;
+      }
+    }
+  }
+  if (lane == 0)
+    for (int q = 0; q < GLIMS_OBSERVE_MAX_QUERIES; ++q)
+      for (int k = 0; k < 4; ++k) mom_part[(gwave * GLIMS_OBSERVE_MAX_QUERIES + q) * 4 + k] = acc[wave][q][k];
+}
+
+// One block per term q of a batch with a centre-of-mass term: V and M = the per-wave rows summed in a fixed order, then, by one
+// thread, X = M / V, alpha = weight (X - target_x) / V and J = 1/2 weight |X - target_x|^2 into mom [q][GL_OBS_MOM].  A measure
+// that is not > 0 is EMPTY: X = alpha = J = 0 and the flag set, so that every partial of the term comes out as an exact zero.
+// The rows of the batch's volume terms are zeroed.
+__global__ __launch_bounds__(256) void k_observe_mom_sum(int64_t n_waves, int dim, const double* __restrict__ mom_part,
+                                                         ObsGradTerms ts, double* __restrict__ mom) {
+  __shared__ double sm[256];
+  __shared__ double tot[4];
+  const int q = blockIdx.x;
+  if (!ts.moment[q]) {
+    if (threadIdx.x < GL_OBS_MOM) mom[q * GL_OBS_MOM + threadIdx.x] = 0.0;
+    return;
+  }
+  for (int k = 0; k <= dim; ++k) {
+    double acc = 0.0;
+    for (int64_t w = threadIdx.x; w < n_waves; w += 256) acc += mom_part[(w * GLIMS_OBSERVE_MAX_QUERIES + q) * 4 + k];
+    sm[threadIdx.x] = acc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+      if ((int)threadIdx.x < o) sm[threadIdx.x] += sm[threadIdx.x + o];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) tot[k] = sm[0];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    double* mv = mom + q * GL_OBS_MOM;
+    const double V = tot[0];
+    const bool empty = !(V > 0.0);
+    double J = 0.0;
+    mv[0] = V;
+    for (int a = 0; a < 3; ++a) {
+      const double M = a < dim ? tot[1 + a] : 0.0;
+      double X = 0.0, al = 0.0;
+      if (!empty && a < dim) {
+        X = M / V;
+        const double r = X - ts.target_x[q][a];
+        al = ts.weight[q] * r / V;
+        J += r * r;
+      }
+      mv[1 + a] = M;
+      mv[GL_OBS_MOM_X + a] = X;
+      mv[GL_OBS_MOM_ALPHA + a] = al;
+    }
+    mv[GL_OBS_MOM_J] = 0.5 * ts.weight[q] * J;
+    mv[GL_OBS_MOM_EMPTY] = empty ? 1.0 : 0.0;
   }
 }
 
@@ -479,9 +709,11 @@ __global__ __launch_bounds__(256) void k_observe_second_cells(int64_t n_cells, c
 
 // One block per term q: S = the per-wave rows summed in a fixed order.  mode 0: vals[q] = V = S, vals[MAXQ + q] = weight (V -
 // target), cuts[q] = the cut cells;  mode 1: vals[2 MAXQ + q] = weight S  (weight g^T dc_j of a Hessian direction)
+// mom != nullptr (a batch with a centre-of-mass term, mode 0): such a term's coefficient is 1, or 0 when its measure was empty
 __global__ __launch_bounds__(256) void k_observe_grad_sum(int64_t n_waves, const double* __restrict__ part,
                                                           const unsigned int* __restrict__ cut_part, ObsGradTerms ts, int mode,
-                                                          double* __restrict__ vals, long long* __restrict__ cuts) {
+                                                          double* __restrict__ vals, long long* __restrict__ cuts,
+                                                          const double* __restrict__ mom) {
   __shared__ double sm[256];
   __shared__ long long sc[256];
   const int q = blockIdx.x;
@@ -505,6 +737,7 @@ __global__ __launch_bounds__(256) void k_observe_grad_sum(int64_t n_waves, const
     if (mode == 0) {
       vals[q] = sm[0];
       vals[GLIMS_OBSERVE_MAX_QUERIES + q] = ts.weight[q] * (sm[0] - ts.target[q]);
+      if (mom && ts.moment[q]) vals[GLIMS_OBSERVE_MAX_QUERIES + q] = mom[q * GL_OBS_MOM + GL_OBS_MOM_EMPTY] != 0.0 ? 0.0 : 1.0;
       cuts[q] = sc[0];
     } else {
       vals[2 * GLIMS_OBSERVE_MAX_QUERIES + q] = ts.weight[q] * sm[0];
@@ -837,6 +1070,32 @@ void ensure_def_scratch(glims_ctx* h, int nt, int64_t n_waves) {
   os.ratios.alloc((size_t)GLIMS_OBSERVE_MAX_QUERIES);
 }
 
+// The scratch of a list with a centre-of-mass term, with the same refusal: the per-wave moment rows, and with a DEFORMED such term
+// the planes sigma vol(y) b[1 + m] (8 (dim+1) n_cells bytes per term of a pass).  A list without such a term never comes here.
+void ensure_mom_scratch(glims_ctx* h, int nt, int64_t n_waves, bool deformed) {
+  ObsTermState& os = h->obs_terms;
+  const size_t b1n = deformed ? (size_t)nt * (h->dim + 1) * (size_t)h->n_cells : 0;
+  const size_t rows = (size_t)n_waves * GLIMS_OBSERVE_MAX_QUERIES * 4;
+  size_t need = 0;
+  if (os.b1_planes.n < b1n) {
+    os.b1_planes.release();
+    need += b1n * sizeof(double);
+  }
+  if (os.mom_part.n < rows) need += rows * sizeof(double);
+  if (need) {
+    size_t fr = 0, tot = 0;
+    GL_HIP(hipMemGetInfo(&fr, &tot));
+    if (need > fr)
+      throw glims_error(GLIMS_E_HIP, "glims_adjoint_observable_terms3: the moment rows and the first-moment planes of " +
+                                         std::to_string(nt) + " centre-of-mass terms over " + std::to_string(h->n_cells) +
+                                         " cells need about " + std::to_string(need >> 20) + " MiB of device memory, " +
+                                         std::to_string(fr >> 20) + " MiB are free");
+  }
+  if (os.b1_planes.n < b1n) os.b1_planes.alloc(b1n);
+  if (os.mom_part.n < rows) os.mom_part.alloc(rows);
+  os.mom_vals.alloc((size_t)GLIMS_OBSERVE_MAX_QUERIES * GL_OBS_MOM);
+}
+
 template <int D>
 void observable_batch(glims_ctx* h, const std::vector<int>& batch, int nt_alloc, const double* c, double* g, double* J, int P,
                       const double* dc, int64_t ld, double* dg, int step, const double* uk, double* murhs) {
@@ -852,8 +1111,10 @@ void observable_batch(glims_ctx* h, const std::vector<int>& batch, int nt_alloc,
     ts.deformed[q] = 0;
     ts.scale[q] = 0.0;
     for (int w = 0; w < GL_MAX_LABELS / 64; ++w) ts.mask[q][w] = 0ull;
+    ts.moment[q] = 0;
+    for (int a = 0; a < 3; ++a) ts.target_x[q][a] = 0.0;
   }
-  bool any_def = false;
+  bool any_def = false, any_com = false;
   for (int q = 0; q < nt; ++q) {
     const GlObservableTerm& t = os.terms[(size_t)batch[(size_t)q]];
     ts.deformed[q] = t.deformed;
@@ -864,22 +1125,35 @@ void observable_batch(glims_ctx* h, const std::vector<int>& batch, int nt_alloc,
     ts.smooth[q] = t.kind == GLIMS_OBSERVE_SMOOTH ? t.smooth : 1.0;
     ts.weight[q] = t.weight;
     ts.target[q] = t.target;
+    ts.moment[q] = t.moment;
+    any_com = any_com || t.moment;
+    for (int a = 0; a < 3; ++a) ts.target_x[q][a] = t.target_x[a];
     for (int l = 0; l < GL_MAX_LABELS; ++l)
       if (t.mask.empty() || (l < (int)t.mask.size() && t.mask[(size_t)l])) ts.mask[q][l >> 6] |= 1ull << (l & 63);
   }
   if (any_def && !(uk && murhs)) throw std::logic_error("observable_batch: a deformed volume term without u_k");
-  double vals[2 * MQ] = {0.0}, ratios[MQ];
+  if (any_com && P > 0) throw std::logic_error("observable_batch: second order with a centre-of-mass term");
+  double vals[2 * MQ] = {0.0}, ratios[MQ], moms[MQ * GL_OBS_MOM] = {0.0};
   long long cuts[MQ] = {0}, folds[MQ] = {0};
-  for (int q = 0; q < MQ; ++q) ratios[q] = INFINITY;
+  for (int q = 0; q < MQ; ++q) {
+    ratios[q] = INFINITY;
+    moms[q * GL_OBS_MOM + GL_OBS_MOM_EMPTY] = 1.0;   // (a mesh without cells: every measure is empty)
+  }
   if (h->n_cells > 0) {
     const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(GL_OBS_BLOCKS, grid_of(h->n_cells)));
     const int64_t n_waves = (int64_t)nb * GL_OBS_WAVES;
     ensure_term_scratch(h, nt_alloc, P > 0, n_waves);
     if (gl_observable_terms_any_deformed(h)) ensure_def_scratch(h, nt_alloc, n_waves);   // (from the list: no step reallocates)
+    bool list_com = false, list_def_com = false;
+    for (const GlObservableTerm& t : os.terms) {
+      list_com = list_com || t.moment;
+      list_def_com = list_def_com || (t.moment && t.deformed);
+    }
+    if (list_com) ensure_mom_scratch(h, nt_alloc, n_waves, list_def_com);
     const int32_t* cn = gl_ensure_cell_nodes(h);
     // GLIMS_OBSERVABLE_TIMING: an event pair around the cell pass (with its sum) and one around the gather, one line per batch
     const bool timed = getenv("GLIMS_OBSERVABLE_TIMING") != nullptr;
-    float ms_cells = 0.f, ms_rows = 0.f, ms_load = 0.f, ms_urows = 0.f;
+    float ms_cells = 0.f, ms_rows = 0.f, ms_load = 0.f, ms_urows = 0.f, ms_mom = 0.f;
     auto tick = [&]() {
       if (timed) GL_HIP(hipEventRecord(h->ev_a, h->st));
     };
@@ -889,20 +1163,45 @@ void observable_batch(glims_ctx* h, const std::vector<int>& batch, int nt_alloc,
       GL_HIP(hipEventSynchronize(h->ev_b));
       GL_HIP(hipEventElapsedTime(ms, h->ev_a, h->ev_b));
     };
+    const double* mom = any_com ? os.mom_vals.p : nullptr;
+    if (any_com) {
+      // the quotient needs V and M before any partial can be weighted: the moments pass and its sum leave them on the device
+      tick();
+      if (any_def)
+        hipLaunchKernelGGL((k_observe_mom_cells<D, 1>), dim3(nb), dim3(256), 0, h->st, h->n_cells, cn, h->label.p, h->evol.p, c,
+                           ts, h->xyz_new.p, uk, os.mom_part.p);
+      else
+        hipLaunchKernelGGL((k_observe_mom_cells<D, 0>), dim3(nb), dim3(256), 0, h->st, h->n_cells, cn, h->label.p, h->evol.p, c,
+                           ts, h->xyz_new.p, (const double*)nullptr, os.mom_part.p);
+      GL_CHECK_LAUNCH();
+      hipLaunchKernelGGL(k_observe_mom_sum, dim3(nt), dim3(256), 0, h->st, n_waves, D, os.mom_part.p, ts, os.mom_vals.p);
+      GL_CHECK_LAUNCH();
+      tock(&ms_mom);
+      os.n_mom_passes++;
+    }
     tick();
     if (any_def) {
-      hipLaunchKernelGGL((k_observe_grad_cells<D, 1>), dim3(nb), dim3(256), 0, h->st, h->n_cells, cn, h->label.p, h->evol.p, c,
-                         ts, os.planes.p, os.part.p, os.cut_part.p, h->xyz_new.p, uk, os.b0_planes.p, os.fold_part.p,
-                         os.ratio_part.p);
+      if (any_com)
+        hipLaunchKernelGGL((k_observe_grad_cells<D, 1, 1>), dim3(nb), dim3(256), 0, h->st, h->n_cells, cn, h->label.p, h->evol.p,
+                           c, ts, os.planes.p, os.part.p, os.cut_part.p, h->xyz_new.p, uk, os.b0_planes.p, os.fold_part.p,
+                           os.ratio_part.p, mom, os.b1_planes.p);
+      else
+        hipLaunchKernelGGL((k_observe_grad_cells<D, 1, 0>), dim3(nb), dim3(256), 0, h->st, h->n_cells, cn, h->label.p, h->evol.p,
+                           c, ts, os.planes.p, os.part.p, os.cut_part.p, h->xyz_new.p, uk, os.b0_planes.p, os.fold_part.p,
+                           os.ratio_part.p, (const double*)nullptr, (double*)nullptr);
       os.n_def_passes++;
+    } else if (any_com) {
+      hipLaunchKernelGGL((k_observe_grad_cells<D, 0, 1>), dim3(nb), dim3(256), 0, h->st, h->n_cells, cn, h->label.p, h->evol.p, c,
+                         ts, os.planes.p, os.part.p, os.cut_part.p, h->xyz_new.p, (const double*)nullptr, (double*)nullptr,
+                         (unsigned int*)nullptr, (double*)nullptr, mom, (double*)nullptr);
     } else {
-      hipLaunchKernelGGL((k_observe_grad_cells<D, 0>), dim3(nb), dim3(256), 0, h->st, h->n_cells, cn, h->label.p, h->evol.p, c,
+      hipLaunchKernelGGL((k_observe_grad_cells<D, 0, 0>), dim3(nb), dim3(256), 0, h->st, h->n_cells, cn, h->label.p, h->evol.p, c,
                          ts, os.planes.p, os.part.p, os.cut_part.p, (const double*)nullptr, (const double*)nullptr,
-                         (double*)nullptr, (unsigned int*)nullptr, (double*)nullptr);
+                         (double*)nullptr, (unsigned int*)nullptr, (double*)nullptr, (const double*)nullptr, (double*)nullptr);
     }
     GL_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_observe_grad_sum, dim3(nt), dim3(256), 0, h->st, n_waves, os.part.p, os.cut_part.p, ts, 0, os.vals.p,
-                       os.cuts.p);
+                       os.cuts.p, mom);
     GL_CHECK_LAUNCH();
     tock(&ms_cells);
     tick();
@@ -915,12 +1214,18 @@ void observable_batch(glims_ctx* h, const std::vector<int>& batch, int nt_alloc,
     os.n_gathers++;
     if (timed)
       fprintf(stderr, "glims observable terms: step %d  terms %d  cells %.4f ms  gather %.4f ms\n", step, nt, ms_cells, ms_rows);
+    if (timed && any_com) fprintf(stderr, "glims observable terms: step %d  moments pass %.4f ms\n", step, ms_mom);
     if (any_def) {
       // dJ/du_k of the batch's deformed terms: the combined cofactor planes (the coefficients are on the device), then their
       // row-owned gather into murhs; the folded counts and smallest ratios of the cell pass
       tick();
-      hipLaunchKernelGGL(k_observe_def_load_cells<D>, dim3(grid_of(h->n_cells)), dim3(256), 0, h->st, h->n_cells, cn,
-                         h->xyz_new.p, uk, ts, os.b0_planes.p, os.vals.p + MQ, os.load_planes.p);
+      if (any_com)
+        hipLaunchKernelGGL((k_observe_def_load_cells<D, 1>), dim3(grid_of(h->n_cells)), dim3(256), 0, h->st, h->n_cells, cn,
+                           h->xyz_new.p, uk, ts, os.b0_planes.p, os.vals.p + MQ, os.load_planes.p, os.b1_planes.p, mom);
+      else
+        hipLaunchKernelGGL((k_observe_def_load_cells<D, 0>), dim3(grid_of(h->n_cells)), dim3(256), 0, h->st, h->n_cells, cn,
+                           h->xyz_new.p, uk, ts, os.b0_planes.p, os.vals.p + MQ, os.load_planes.p, (const double*)nullptr,
+                           (const double*)nullptr);
       GL_CHECK_LAUNCH();
       tock(&ms_load);
       tick();
@@ -944,7 +1249,7 @@ void observable_batch(glims_ctx* h, const std::vector<int>& batch, int nt_alloc,
                          dc + (size_t)p * ld, ts, os.planes.p, os.planes2.p, os.part.p);
       GL_CHECK_LAUNCH();
       hipLaunchKernelGGL(k_observe_grad_sum, dim3(nt), dim3(256), 0, h->st, n_waves, os.part.p, os.cut_part.p, ts, 1, os.vals.p,
-                         os.cuts.p);
+                         os.cuts.p, (const double*)nullptr);
       GL_CHECK_LAUNCH();
       hipLaunchKernelGGL((k_observe_grad_rows<NV, 1>), dim3(grid_of(h->n_own)), dim3(256), 0, h->st, h->n_own, h->n_cells,
                          h->pat.cslice_ptr.p, h->pat.celem.p, cn, nt, os.planes.p, os.vals.p + 2 * MQ, os.planes2.p,
@@ -955,6 +1260,7 @@ void observable_batch(glims_ctx* h, const std::vector<int>& batch, int nt_alloc,
     }
     GL_HIP(hipMemcpyAsync(vals, os.vals.p, sizeof(vals), hipMemcpyDeviceToHost, h->st));
     GL_HIP(hipMemcpyAsync(cuts, os.cuts.p, sizeof(cuts), hipMemcpyDeviceToHost, h->st));
+    if (any_com) GL_HIP(hipMemcpyAsync(moms, os.mom_vals.p, sizeof(moms), hipMemcpyDeviceToHost, h->st));
     GL_HIP(hipStreamSynchronize(h->st));
   }
   for (int q = 0; q < nt; ++q) {
@@ -965,6 +1271,14 @@ void observable_batch(glims_ctx* h, const std::vector<int>& batch, int nt_alloc,
       t.n_folded = (int64_t)folds[q];
       t.min_ratio = std::isfinite(ratios[q]) ? ratios[q] : NAN;   // (no counted cell: nothing to take the minimum of)
     }
+    if (t.moment) {
+      const double* mv = moms + q * GL_OBS_MOM;
+      t.V = mv[0];
+      t.empty = mv[GL_OBS_MOM_EMPTY] != 0.0 ? 1 : 0;
+      for (int a = 0; a < 3; ++a) t.com[a] = !t.empty && a < D ? mv[GL_OBS_MOM_X + a] : NAN;
+      *J += mv[GL_OBS_MOM_J];
+      continue;
+    }
     const double r = t.V - t.target;
     *J += 0.5 * t.weight * (r * r);
   }
@@ -973,36 +1287,44 @@ void observable_batch(glims_ctx* h, const std::vector<int>& batch, int nt_alloc,
 }  // namespace
 
 void gl_observable_terms_set(glims_ctx* h, int n, const glims_observable_misfit* terms1,
-                             const glims_observable_misfit2* terms2) {
-  const std::string who = terms2 ? "glims_adjoint_observable_terms2" : "glims_adjoint_observable_terms";
+                             const glims_observable_misfit2* terms2, const glims_observable_misfit3* terms3) {
+  const std::string who = terms3   ? "glims_adjoint_observable_terms3"
+                          : terms2 ? "glims_adjoint_observable_terms2"
+                                   : "glims_adjoint_observable_terms";
   ObsTermState& os = h->obs_terms;
-  GL_REQUIRE(n >= 0 && (n == 0 || terms1 || terms2), who + ": bad term list");
+  GL_REQUIRE(n >= 0 && (n == 0 || terms1 || terms2 || terms3), who + ": bad term list");
   auto drop_planes = [&os]() {
     os.planes.release();
     os.planes2.release();
     os.b0_planes.release();
     os.load_planes.release();
+    os.b1_planes.release();
   };
   if (n == 0) {   // clearing is always possible; the planes go with the list
     os.terms.clear();
     drop_planes();
     return;
   }
-  // one internal form for both entry points: the old struct is a term of the reference configuration
-  std::vector<glims_observable_misfit2> terms((size_t)n);
+  // one internal form for the entry points: the first struct is a term of the reference configuration, the first two are
+  // volume terms
+  std::vector<glims_observable_misfit3> terms((size_t)n);
   for (int k = 0; k < n; ++k) {
-    if (terms2) {
-      terms[(size_t)k] = terms2[k];
+    if (terms3) {
+      terms[(size_t)k] = terms3[k];
+    } else if (terms2) {
+      const glims_observable_misfit2& t = terms2[k];
+      terms[(size_t)k] = {t.step, t.kind, t.level, t.smooth, t.weight, t.target, t.labels, t.deformed, t.scale, 0,
+                          {0.0, 0.0, 0.0}};
     } else {
       const glims_observable_misfit& t = terms1[k];
-      terms[(size_t)k] = {t.step, t.kind, t.level, t.smooth, t.weight, t.target, t.labels, 0, 1.0};
+      terms[(size_t)k] = {t.step, t.kind, t.level, t.smooth, t.weight, t.target, t.labels, 0, 1.0, 0, {0.0, 0.0, 0.0}};
     }
   }
   GL_REQUIRE(h->world <= 1, who + ": not available on a partitioned handle (world > 1)");
   GL_REQUIRE(h->is_setup, who + " before glims_setup");
   GL_REQUIRE(h->n_labels > 0, who + " before glims_set_materials");
   for (int k = 0; k < n; ++k) {
-    const glims_observable_misfit2& t = terms[(size_t)k];
+    const glims_observable_misfit3& t = terms[(size_t)k];
     const std::string tk = " of term " + std::to_string(k);
     GL_REQUIRE(t.step >= 0, who + ": negative step" + tk);
     GL_REQUIRE(t.kind >= GLIMS_OBSERVE_MASS && t.kind <= GLIMS_OBSERVE_SMOOTH,
@@ -1010,7 +1332,13 @@ void gl_observable_terms_set(glims_ctx* h, int n, const glims_observable_misfit*
     GL_REQUIRE(std::isfinite(t.level), who + ": level" + tk + " is not finite");
     GL_REQUIRE(t.kind != GLIMS_OBSERVE_SMOOTH || t.smooth > 0.0, who + ": smooth" + tk + " must be positive");
     GL_REQUIRE(std::isfinite(t.weight), who + ": weight" + tk + " is not finite");
-    GL_REQUIRE(std::isfinite(t.target), who + ": target" + tk + " is not finite");
+    GL_REQUIRE(t.moment >= 0 && t.moment <= 1, who + ": moment " + std::to_string(t.moment) + tk + " outside 0..1");
+    if (t.moment) {
+      for (int a = 0; a < h->dim; ++a)
+        GL_REQUIRE(std::isfinite(t.target_x[a]), who + ": target_x[" + std::to_string(a) + "]" + tk + " is not finite");
+    } else {
+      GL_REQUIRE(std::isfinite(t.target), who + ": target" + tk + " is not finite");
+    }
     GL_REQUIRE(!t.deformed || (h->have_mech && h->U.p),
                who + ": term " + std::to_string(k) + " is deformed: the deformed configuration needs the displacement, "
                      "glims_setup(with_mechanics=1) first");
@@ -1019,8 +1347,10 @@ void gl_observable_terms_set(glims_ctx* h, int n, const glims_observable_misfit*
   ensure_label_cells(h);
   std::vector<GlObservableTerm> fresh((size_t)n);
   for (int k = 0; k < n; ++k) {
-    const glims_observable_misfit2& t = terms[(size_t)k];
+    const glims_observable_misfit3& t = terms[(size_t)k];
     GlObservableTerm& f = fresh[(size_t)k];
+    f.moment = t.moment;
+    for (int a = 0; a < h->dim; ++a) f.target_x[a] = t.moment ? t.target_x[a] : 0.0;
     f.deformed = t.deformed ? 1 : 0;
     f.scale = t.deformed ? t.scale : 1.0;
     f.step = t.step;
@@ -1028,7 +1358,7 @@ void gl_observable_terms_set(glims_ctx* h, int n, const glims_observable_misfit*
     f.level = t.level;
     f.smooth = t.kind == GLIMS_OBSERVE_SMOOTH ? t.smooth : 1.0;
     f.weight = t.weight;
-    f.target = t.target;
+    f.target = t.moment ? 0.0 : t.target;
     if (t.labels) {
       f.mask.assign(t.labels, t.labels + h->n_labels);
       for (int l = 0; l < h->n_labels; ++l)
@@ -1053,6 +1383,16 @@ void gl_observable_term_info2(glims_ctx* h, int k, int64_t out[4], double* V, do
   out[3] = 0;
   *V = t.V;
   *min_ratio = t.deformed ? t.min_ratio : NAN;
+}
+
+void gl_observable_term_info3(glims_ctx* h, int k, int64_t out[4], double* V, double* min_ratio, double com[3]) {
+  const ObsTermState& os = h->obs_terms;
+  GL_REQUIRE(out && V && min_ratio && com, "glims_adjoint_observable_info3: null output");
+  GL_REQUIRE(k >= 0 && k < (int)os.terms.size(), "glims_adjoint_observable_info3: no stored term " + std::to_string(k));
+  gl_observable_term_info2(h, k, out, V, min_ratio);
+  const GlObservableTerm& t = os.terms[(size_t)k];
+  out[3] = t.moment && t.empty ? 1 : 0;
+  for (int a = 0; a < 3; ++a) com[a] = t.moment && a < h->dim ? t.com[a] : NAN;
 }
 
 bool gl_observable_terms_any_deformed(const glims_ctx* h) {
@@ -1091,6 +1431,9 @@ void gl_observable_terms_check(glims_ctx* h, int64_t N, const std::string& who, 
                      "the second derivative where the level set crosses a vertex; second order is built for MASS and SMOOTH");
     GL_REQUIRE(!t.deformed || h->have_mech,
                who + ": stored volume term " + std::to_string(k) + " is deformed: it needs glims_setup(with_mechanics=1)");
+    GL_REQUIRE(!second_order || !t.moment,
+               who + ": stored term " + std::to_string(k) + " is a centre-of-mass term: second order of the quotient M / V is "
+                     "not built; clear the list with glims_adjoint_observable_terms3(h, 0, NULL) or store volume terms first");
     GL_REQUIRE(!second_order || !t.deformed,
                who + ": stored volume term " + std::to_string(k) + " is deformed: second order through the displacement is "
                      "not built (a Hessian without it would be wrong); clear the list with "

@@ -184,6 +184,243 @@ GLIMS_OC_HD void glims_og_volume_grad(const double (&p)[D + 1][D], double (&dvol
   }
 }
 
+// ---- first moments (centre-of-mass terms) ------------------------------------------------------------------------------------------
+// With D1[m][i] = d b[1 + m] / d c_i and weights psi_m handed in, the glims_og_moment_* give the values b[0 .. d+1] of
+// observe_clip.h (the same formulas, to rounding) and the contraction g[i] = sum_m psi_m D1[m][i] -- the gradient of the scalar
+// S(c) = sum_m psi_m b[1 + m](c).  psi knows the positions; nothing here does.
+//   MASS    D1[m][i] = (1 + delta_mi) / ((d+1)(d+2)):  g[i] = (sum_m psi_m + psi_i) / ((d+1)(d+2))
+//   SMOOTH  D1[m][i] = sum_q w_q h'(v_q) lam_qi lam_qm:  g[i] = sum_q w_q h'(v_q) lam_qi (sum_m lam_qm psi_m)
+//   SHARP   glims_oc_sharp's formulas differentiated through the edge parameters t (dt/dc as in glims_og_sharp):
+//             corner simplex at v, s_j its extent along v -> j:  F = frac Q,  frac = prod_j s_j,
+//               Q = (psi_v (1 + sum_j (1 - s_j)) + sum_j psi_j s_j) / (d+1),   dF/ds_j = (prod_{k != j} s_k) Q + frac (psi_j - psi_v) / (d+1),
+//               S = F (1 in) or sum_m psi_m / (d+1) - F (1 out); the products that leave one factor out are formed explicitly
+//             3-D prism: the three tetrahedra of glims_oc_add_tet in forward mode over the four t (glims_og_d4: a value and its
+//               four partials), in the local vertex order (a, b, e, f) so that every index is a constant.  The three
+//               determinants are sigma times products of factors in [0, 1] with ONE sign sigma, that of the vertex order
+//               (a, e, f, b) -- +1 in the local order: |det| = sigma det is differentiated as such, so that a factor that is 0
+//               (a tie: a tetrahedron of zero volume) still has the derivative of the piece the evaluation sits on
+//           0 or d+1 vertices in: g = 0.  A tie counts as in.  The only divisions are those by c_a - c_o > 0.
+
+// MASS
+template <int D>
+GLIMS_OC_HD void glims_og_moment_mass(const double (&c)[D + 1], const double (&psi)[D + 1], double (&b)[D + 2],
+                                      double (&g)[D + 1]) {
+  constexpr int NV = D + 1;
+  glims_oc_mass<D>(c, b);
+  double sp = 0.0;
+  for (int m = 0; m < NV; ++m) sp += psi[m];
+  for (int i = 0; i < NV; ++i) g[i] = (sp + psi[i]) * (1.0 / (NV * (NV + 1)));
+}
+
+// SMOOTH with the rule handed in (as glims_og_smooth)
+template <int D, int NQ>
+GLIMS_OC_HD void glims_og_moment_smooth(double level, double smooth, const double (&c)[D + 1], const double (*lam)[D + 1],
+                                        const double* w, const double (&psi)[D + 1], double (&b)[D + 2], double (&g)[D + 1]) {
+  constexpr int NV = D + 1;
+  for (int k = 0; k < NV + 1; ++k) b[k] = 0.0;
+  for (int i = 0; i < NV; ++i) g[i] = 0.0;
+  const double inv = 1.0 / smooth;
+  for (int q = 0; q < NQ; ++q) {
+    double cq = 0.0, pq = 0.0;
+    for (int a = 0; a < NV; ++a) {
+      cq += lam[q][a] * c[a];
+      pq += lam[q][a] * psi[a];
+    }
+    const double th = tanh((cq - level) / smooth);
+    const double f = w[q] * (0.5 * (th + 1.0));
+    b[0] += f;
+    for (int k = 0; k < NV; ++k) b[1 + k] += f * lam[q][k];
+    const double h1 = w[q] * (0.5 * (1.0 - th * th) * inv) * pq;
+    for (int i = 0; i < NV; ++i) g[i] += h1 * lam[q][i];
+  }
+}
+
+// a value and its partials by the four edge parameters of the prism
+struct glims_og_d4 {
+  double v, d[4];
+};
+GLIMS_OC_HD glims_og_d4 glims_og_d4_const(double v) { return {v, {0.0, 0.0, 0.0, 0.0}}; }
+GLIMS_OC_HD glims_og_d4 glims_og_d4_add(const glims_og_d4& x, const glims_og_d4& y) {
+  glims_og_d4 r;
+  r.v = x.v + y.v;
+  for (int k = 0; k < 4; ++k) r.d[k] = x.d[k] + y.d[k];
+  return r;
+}
+GLIMS_OC_HD glims_og_d4 glims_og_d4_sub(const glims_og_d4& x, const glims_og_d4& y) {
+  glims_og_d4 r;
+  r.v = x.v - y.v;
+  for (int k = 0; k < 4; ++k) r.d[k] = x.d[k] - y.d[k];
+  return r;
+}
+GLIMS_OC_HD glims_og_d4 glims_og_d4_mul(const glims_og_d4& x, const glims_og_d4& y) {
+  glims_og_d4 r;
+  r.v = x.v * y.v;
+  for (int k = 0; k < 4; ++k) r.d[k] = x.d[k] * y.v + x.v * y.d[k];
+  return r;
+}
+
+// glims_oc_add_tet in forward mode: adds the tetrahedron's b and, to S, sum_k psi_k (its fraction times the mean of its vertices)_k;
+// sigma = the sign its determinant has wherever it is not 0
+GLIMS_OC_HD void glims_og_add_tet(const glims_og_d4* q0, const glims_og_d4* q1, const glims_og_d4* q2, const glims_og_d4* q3,
+                                  double sigma, const double (&psi)[4], double (&b)[5], glims_og_d4& S) {
+  const glims_og_d4 a0 = glims_og_d4_sub(q1[1], q0[1]), a1 = glims_og_d4_sub(q1[2], q0[2]), a2 = glims_og_d4_sub(q1[3], q0[3]);
+  const glims_og_d4 b0 = glims_og_d4_sub(q2[1], q0[1]), b1 = glims_og_d4_sub(q2[2], q0[2]), b2 = glims_og_d4_sub(q2[3], q0[3]);
+  const glims_og_d4 c0 = glims_og_d4_sub(q3[1], q0[1]), c1 = glims_og_d4_sub(q3[2], q0[2]), c2 = glims_og_d4_sub(q3[3], q0[3]);
+  const glims_og_d4 m0 = glims_og_d4_sub(glims_og_d4_mul(b1, c2), glims_og_d4_mul(b2, c1));
+  const glims_og_d4 m1 = glims_og_d4_sub(glims_og_d4_mul(b0, c2), glims_og_d4_mul(b2, c0));
+  const glims_og_d4 m2 = glims_og_d4_sub(glims_og_d4_mul(b0, c1), glims_og_d4_mul(b1, c0));
+  glims_og_d4 f = glims_og_d4_add(glims_og_d4_sub(glims_og_d4_mul(a0, m0), glims_og_d4_mul(a1, m1)), glims_og_d4_mul(a2, m2));
+  f.v *= sigma;
+  for (int k = 0; k < 4; ++k) f.d[k] *= sigma;
+  b[0] += f.v;
+  for (int k = 0; k < 4; ++k) {
+    glims_og_d4 mean = glims_og_d4_add(glims_og_d4_add(q0[k], q1[k]), glims_og_d4_add(q2[k], q3[k]));
+    mean.v *= 0.25;
+    for (int j = 0; j < 4; ++j) mean.d[j] *= 0.25;
+    const glims_og_d4 fm = glims_og_d4_mul(f, mean);
+    b[1 + k] += fm.v;
+    S.v += psi[k] * fm.v;
+    for (int j = 0; j < 4; ++j) S.d[j] += psi[k] * fm.d[j];
+  }
+}
+
+// SHARP: returns the in-count (the cell is cut iff 0 < n_in < d+1)
+template <int D>
+GLIMS_OC_HD int glims_og_moment_sharp(double level, const double (&c)[D + 1], const double (&psi)[D + 1], double (&b)[D + 2],
+                                      double (&g)[D + 1]) {
+  constexpr int NV = D + 1;
+  int n_in = 0;
+  for (int i = 0; i < NV; ++i) {
+    n_in += c[i] >= level ? 1 : 0;
+    g[i] = 0.0;
+  }
+  for (int k = 0; k < NV + 1; ++k) b[k] = 0.0;
+  if (n_in == 0) return n_in;
+  if (n_in == NV) {
+    b[0] = 1.0;
+    for (int k = 0; k < NV; ++k) b[1 + k] = 1.0 / NV;
+    return n_in;
+  }
+  if (n_in == 1 || n_in == NV - 1) {
+    const bool corner_in = n_in == 1;
+    int v = 0;
+    for (int i = 0; i < NV; ++i)
+      if ((c[i] >= level) == corner_in) v = i;
+    double s[NV], ds_j[NV], ds_v[NV];   // s_j and its partials by c_j and by c_v (as glims_og_sharp)
+    double frac = 1.0, sum_rest = 0.0;
+    for (int j = 0; j < NV; ++j) {
+      s[j] = 0.0;
+      ds_j[j] = ds_v[j] = 0.0;
+      if (j == v) continue;
+      const int a = corner_in ? v : j, o = corner_in ? j : v;
+      const double den = c[a] - c[o];
+      const double t = (c[a] - level) / den;
+      if (corner_in) {
+        s[j] = t;
+        ds_j[j] = t / den;
+        ds_v[j] = (1.0 - t) / den;
+      } else {
+        s[j] = 1.0 - t;
+        ds_j[j] = -(1.0 - t) / den;
+        ds_v[j] = -t / den;
+      }
+      frac *= s[j];
+      sum_rest += 1.0 - s[j];
+    }
+    double m[NV], Q = 0.0;
+    for (int j = 0; j < NV; ++j) {
+      m[j] = (j == v ? 1.0 + sum_rest : s[j]) * (1.0 / NV);
+      Q += psi[j] * m[j];
+    }
+    if (corner_in) {
+      b[0] = frac;
+      for (int k = 0; k < NV; ++k) b[1 + k] = frac * m[k];
+    } else {
+      b[0] = 1.0 - frac;
+      for (int k = 0; k < NV; ++k) b[1 + k] = 1.0 / NV - frac * m[k];
+    }
+    const double sign = corner_in ? 1.0 : -1.0;   // S = F or sum psi / (d+1) - F
+    double gv = 0.0;
+    for (int j = 0; j < NV; ++j) {
+      if (j == v) continue;
+      double rest = 1.0;
+      for (int k = 0; k < NV; ++k)
+        if (k != v && k != j) rest *= s[k];
+      const double dF = rest * Q + frac * ((psi[j] - psi[v]) * (1.0 / NV));
+      g[j] = sign * dF * ds_j[j];
+      gv += dF * ds_v[j];
+    }
+    g[v] = sign * gv;
+    return n_in;
+  }
+  if constexpr (D == 3) {
+    int in[2], out[2], ni = 0, no = 0;
+    for (int i = 0; i < 4; ++i) {
+      if (c[i] >= level) in[ni++] = i;
+      else out[no++] = i;
+    }
+    // The prism of glims_oc_sharp in the LOCAL vertex order (a, b, e, f) = (in[0], in[1], out[0], out[1]): every index below is
+    // a constant, so the forward-mode values stay in registers; only c, psi, b and g are addressed through in / out.  The
+    // parameter t[x][k] (in-vertex x, out-vertex k) is direction 2 x + k.
+    const double cl[4] = {c[in[0]], c[in[1]], c[out[0]], c[out[1]]};
+    const double pl[4] = {psi[in[0]], psi[in[1]], psi[out[0]], psi[out[1]]};
+    glims_og_d4 A[3][4], B[3][4];
+    for (int r = 0; r < 3; ++r)
+      for (int k = 0; k < 4; ++k) A[r][k] = B[r][k] = glims_og_d4_const(0.0);
+    A[0][0].v = 1.0;
+    B[0][1].v = 1.0;
+    double dt_in[2][2], dt_out[2][2];
+    for (int k = 0; k < 2; ++k) {
+      const double dena = cl[0] - cl[2 + k], denb = cl[1] - cl[2 + k];
+      const double ta = (cl[0] - level) / dena;
+      const double tb = (cl[1] - level) / denb;
+      dt_in[0][k] = (1.0 - ta) / dena;
+      dt_out[0][k] = ta / dena;
+      dt_in[1][k] = (1.0 - tb) / denb;
+      dt_out[1][k] = tb / denb;
+      A[1 + k][0].v = 1.0 - ta;
+      A[1 + k][0].d[k] = -1.0;
+      A[1 + k][2 + k].v = ta;
+      A[1 + k][2 + k].d[k] = 1.0;
+      B[1 + k][1].v = 1.0 - tb;
+      B[1 + k][1].d[2 + k] = -1.0;
+      B[1 + k][2 + k].v = tb;
+      B[1 + k][2 + k].d[2 + k] = 1.0;
+    }
+    // sigma: the determinant of (e_a, e_e, e_f, e_b) in the local coordinates 1 .. 3 -- rows (e_2 - e_0, e_3 - e_0, e_1 - e_0)
+    // = ((0, 1, 0), (0, 0, 1), (1, 0, 0)), an even permutation
+    const double sigma = 1.0;
+    double bl[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    glims_og_d4 S = glims_og_d4_const(0.0);
+    glims_og_add_tet(A[0], A[1], A[2], B[0], sigma, pl, bl, S);
+    glims_og_add_tet(A[1], A[2], B[0], B[1], sigma, pl, bl, S);
+    glims_og_add_tet(A[2], B[0], B[1], B[2], sigma, pl, bl, S);
+    b[0] = bl[0];
+    b[1 + in[0]] = bl[1];
+    b[1 + in[1]] = bl[2];
+    b[1 + out[0]] = bl[3];
+    b[1 + out[1]] = bl[4];
+    for (int x = 0; x < 2; ++x)
+      for (int k = 0; k < 2; ++k) {
+        g[in[x]] += S.d[2 * x + k] * dt_in[x][k];
+        g[out[k]] += S.d[2 * x + k] * dt_out[x][k];
+      }
+  }
+  return n_in;
+}
+
+// one query of one simplex, host side: b[0 .. d+1] and g = the psi-contraction of D1; returns the in-count of a SHARP query,
+// -1 for the other kinds
+template <int D>
+inline int glims_og_moment_cell(int kind, double level, double smooth, const double (&c)[D + 1], const double (&psi)[D + 1],
+                                double (&b)[D + 2], double (&g)[D + 1]) {
+  if (kind == GLIMS_OC_MASS) glims_og_moment_mass<D>(c, psi, b, g);
+  else if (kind == GLIMS_OC_SHARP) return glims_og_moment_sharp<D>(level, c, psi, b, g);
+  else if constexpr (D == 2) glims_og_moment_smooth<2, GLIMS_DQ2_N>(level, smooth, c, glims_dq2_lam, glims_dq2_w, psi, b, g);
+  else glims_og_moment_smooth<3, GLIMS_DQ3_N>(level, smooth, c, glims_dq3_lam, glims_dq3_w, psi, b, g);
+  return -1;
+}
+
 // one query of one simplex, host side (the rule from derive_quadrature.h's static tables): b0, g and (dc != nullptr, MASS / SMOOTH)
 // Hd; returns the in-count of a SHARP query, -1 for the other kinds
 template <int D>

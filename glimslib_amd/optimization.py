@@ -58,13 +58,31 @@ class ReducedFunctional:
     ``hessian_matrix`` raise NotImplementedError.  So is a list with a sharp volume term (``sim.volume_term(kind='sharp')``);
     smooth and mass volume terms have their second order.
 
+    ``iv_controls=('x0', 'y0')`` appends SEED controls: user parameters of the concentration's initial-value ``Expression``
+    (attributes, see ``fenics_local.Expression``), e.g. the seed position of ``exp(-a |x - x_seed|^2)``.  The control vector
+    is the model parameters followed by the initial-value parameters; dJ/dp = dJ/dc0 . dc0/dp with dJ/dc0 from the adjoint and
+    dc0/dp the central difference of the NODAL INTERPOLANT alone (two evaluations of the Expression on the host, never of the
+    simulation; step 1e-6 max(1, |p|)).  Seed controls are first order only (``hessian`` / ``hessian_matrix`` raise
+    NotImplementedError) and need bounds of their own in ``minimize`` (``bounds=(lo_list, hi_list)``: a position is not a
+    rate).  A seed is only identifiable with a centre-of-mass term (``sim.com_term``) or an image as data.  A list with a
+    centre-of-mass term is first order only as well.
+
     ``terms_builder(sim, n_steps)`` returns the misfit terms (see ``Handle.adjoint_gradient``) once the forward run of m has
     taken ``n_steps`` steps.  The last m is cached: scipy's ``fun`` / ``jac`` pair for one m costs one forward and one
     backward run.
     """
 
-    def __init__(self, sim, n_params, terms_builder, run_kwargs=None, names=None, elastic_hessian=False):
+    def __init__(self, sim, n_params, terms_builder, run_kwargs=None, names=None, elastic_hessian=False, iv_controls=()):
         self.sim = sim
+        self.iv_controls = tuple(iv_controls)
+        if len(set(self.iv_controls)) != len(self.iv_controls):
+            raise ValueError("iv_controls: distinct parameter names expected, got %s" % (self.iv_controls,))
+        if self.iv_controls:
+            iv = self._iv_expression()
+            bad = [n for n in self.iv_controls if n not in iv._param_names]
+            if bad:
+                raise ValueError("iv_controls: %s are no user parameters of the concentration's initial-value Expression "
+                                 "(it has %s)" % (bad, tuple(iv._param_names)))
         self.elastic_hessian = bool(elastic_hessian)
         self.n_params = int(n_params)
         self.brain = hasattr(sim.params, "D_WM")
@@ -89,7 +107,37 @@ class ReducedFunctional:
         self.hessian_calls = 0
         self.history = []   # (m, J, |dJ/dm|) per evaluation (the reference's eval_cb_post / derivative_cb_post)
 
+    def _iv_expression(self):
+        """The initial-value Expression of the concentration (subspace 1 of the coupled space)."""
+        params = self.sim.params
+        iv = params.get_iv(1) if params._functionspace.has_subspaces else params.get_iv(None)
+        if iv is None or not hasattr(iv, "_param_names"):
+            raise ValueError("iv_controls need an initial-value Expression with user parameters for the concentration")
+        return iv
+
+    def iv_derivative(self, name):
+        """dc0/dp [n_nodes] for the initial-value parameter `name` at its present value: the central difference of the nodal
+        interpolant with step h = 1e-6 max(1, |p|) (truncation h^2 / 6 times the third derivative of c0 by p and rounding
+        eps / h, both about 1e-10 for a Gaussian of unit width).  The parameter is left as it was."""
+        iv = self._iv_expression()
+        X = np.asarray(self.sim.mesh.points, dtype=np.float64)
+        p = float(getattr(iv, name))
+        h = 1e-6 * max(1.0, abs(p))
+        try:
+            setattr(iv, name, p + h)
+            up = np.asarray(iv(X), dtype=np.float64).reshape(-1)
+            setattr(iv, name, p - h)
+            dn = np.asarray(iv(X), dtype=np.float64).reshape(-1)
+        finally:
+            setattr(iv, name, p)
+        return (up - dn) / (2.0 * h)
+
     def _set_params(self, m):
+        m, seed = m[:self.n_params], m[self.n_params:]
+        if self.iv_controls:
+            iv = self._iv_expression()
+            for name, v in zip(self.iv_controls, seed):
+                setattr(iv, name, float(v))
         q = self.P @ m
         for name, v in zip(self.names, q):
             setattr(self.sim.params, name, float(v))
@@ -100,8 +148,8 @@ class ReducedFunctional:
 
     def _evaluate(self, m):
         m = np.array(m, dtype=np.float64).reshape(-1)
-        if m.shape != (self.n_params,):
-            raise ValueError("expected %d controls, got %s" % (self.n_params, m.shape))
+        if m.shape != (self.n_params + len(self.iv_controls),):
+            raise ValueError("expected %d controls, got %s" % (self.n_params + len(self.iv_controls), m.shape))
         if self._m is not None and np.array_equal(m, self._m):
             return
         self._set_params(m)
@@ -110,6 +158,9 @@ class ReducedFunctional:
         g = self.sim.adjoint_gradient(self.terms_builder(self.sim, n_steps))
         self._m, self._J = m, float(g["J"])
         self._dJ = self.P.T @ self._model_gradient(g)
+        if self.iv_controls:
+            dc0 = np.asarray(g["c0"], dtype=np.float64).reshape(-1)
+            self._dJ = np.concatenate([self._dJ, [float(dc0 @ self.iv_derivative(name)) for name in self.iv_controls]])
         self._H, self._n_steps = None, n_steps
         self.evaluations += 1
         self.history.append((m.copy(), self._J, float(np.linalg.norm(self._dJ))))
@@ -135,10 +186,16 @@ class ReducedFunctional:
     def hessian_matrix(self, m):
         """P^T H P at m: all n_params directions in one Hessian call (after the forward run of m, shared with ``__call__``
         and ``derivative``); cached with m."""
+        if self.iv_controls:
+            raise NotImplementedError("ReducedFunctional.hessian: initial-value controls %s are first order only; use a "
+                                      "first-order method (L-BFGS-B)" % (self.iv_controls,))
         dirs = self._model_directions()
         self._evaluate(m)
         if self._H is None:
             terms = self.terms_builder(self.sim, self._n_steps)
+            if any(t.get("kind") == "obs_com" for t in terms):
+                raise NotImplementedError("ReducedFunctional.hessian: second order of a centre-of-mass term is not built; "
+                                          "use a first-order method (L-BFGS-B)")
             if any(t.get("deformed") and t.get("kind") == "obs_volume" for t in terms):
                 raise NotImplementedError("ReducedFunctional.hessian: second order through the displacement of a deformed "
                                           "volume term is not built; use a first-order method (L-BFGS-B)")
@@ -165,7 +222,9 @@ class ReducedFunctional:
 def minimize(rf, m0, bounds=(0.005, 0.5), method="L-BFGS-B", tol=1e-6, options=None):
     """scipy.optimize.minimize on ``rf`` with ``jac=rf.derivative`` and the reference's defaults (bounds 0.005 .. 0.5 on
     every control, L-BFGS-B, tol 1e-6, gtol 1e-6; image_based_optimization.py:710-722).  method='trust-constr' also gets
-    ``hessp=rf.hessian``, the second-order adjoint."""
+    ``hessp=rf.hessian``, the second-order adjoint.  ``bounds`` is one (lo, hi) pair for every control or per-control
+    ``(lo_list, hi_list)``; with ``iv_controls`` give the latter: the seed controls need bounds of their own (the box the
+    seed may lie in) -- the default rate bounds would pin a position to 0.005 .. 0.5."""
     from scipy.optimize import minimize as _minimize
     m0 = np.asarray(m0, dtype=np.float64)
     opts = {"disp": False, "gtol": 1e-6}

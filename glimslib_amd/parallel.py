@@ -355,7 +355,7 @@ class DistributedHandle:
         sampler."""
         loc = []
         for t in terms:
-            if t["kind"] == "obs_volume":
+            if t["kind"] in ("obs_volume", "obs_com"):
                 self._no_volume_terms()
             if t["kind"] in _backend._IMAGE_KINDS:
                 loc.append(self._image_term(t))
@@ -438,8 +438,8 @@ class DistributedHandle:
     # -- volume misfit terms: single-rank handles only (the library refuses them on a partitioned handle, as glims_observe) --
     @staticmethod
     def _no_volume_terms():
-        raise NotImplementedError("volume misfit terms (set_observable_terms, kind 'obs_volume') are not available on "
-                                  "partitioned runs")
+        raise NotImplementedError("volume and centre-of-mass misfit terms (set_observable_terms, kinds 'obs_volume' and "
+                                  "'obs_com') are not available on partitioned runs")
 
     def set_observable_terms(self, terms):
         self._no_volume_terms()
@@ -448,6 +448,9 @@ class DistributedHandle:
         self._no_volume_terms()
 
     def observable_term_info2(self, k):
+        self._no_volume_terms()
+
+    def observable_term_info3(self, k):
         self._no_volume_terms()
 
     # -- samplers (collective: every rank passes the same points) --------------------------------------------------------

@@ -420,12 +420,36 @@ class TumorGrowth(FenicsSimulation):
         one GPU (NotImplementedError on a partitioned run); first order only (adjoint_hessian raises NotImplementedError).
         With deformed=False the returned dict is the one described above, without further keys.
         """
+        return self._measure_term('volume_term', step, float(target), threshold, kind, smooth, tissues, weight, deformed, scale)
+
+    def com_term(self, step, target, threshold=0.12, kind='smooth', smooth=0.01, tissues=None, weight=1.0, deformed=False,
+                 scale=1.0):
+        """
+        A misfit term that compares the CENTRE OF MASS of recorded step `step` with the point `target` = [x, y(, z)]:
+        1/2 weight |X - target|^2, X = M / V the centre of mass compute_from_conc_for_each_time_step(threshold, 'com', kind,
+        smooth) and compute_com_all report, of the same measure as volume_term (same kind, threshold, smooth, `tissues`,
+        deformed and scale, with the same errors).  A volume series fixes how fast a tumour grows, a centre-of-mass series
+        where it started and which way it drifts; with deformed=True the centre of mass of x = X + scale u(X) also carries
+        the coupling, E and nu.  Pass it to adjoint_gradient / ReducedFunctional in the same list as the other terms.  Where
+        the measure is empty at an evaluation (V not > 0: nothing above the threshold yet) the term contributes J = 0 and no
+        gradient there, with one RuntimeWarning per term list.  First order only (adjoint_hessian raises
+        NotImplementedError); partitioned runs raise NotImplementedError when the term is used.
+        """
+        x = np.asarray(target, dtype=np.float64).reshape(-1)
+        if x.shape != (int(self.mesh.points.shape[1]),):
+            raise ValueError("com_term: target has %d entries, the mesh has dimension %d" % (x.size, self.mesh.points.shape[1]))
+        term = self._measure_term('com_term', step, 0.0, threshold, kind, smooth, tissues, weight, deformed, scale)
+        term.update(kind='obs_com', target=x.copy())
+        return term
+
+    def _measure_term(self, who, step, target, threshold, kind, smooth, tissues, weight, deformed, scale):
+        """The dict of volume_term / com_term: the query, the counted labels and the configuration."""
         if kind not in _backend.OBSERVE_KINDS:
-            raise ValueError("volume_term: kind must be one of %s" % (tuple(_backend.OBSERVE_KINDS),))
+            raise ValueError("%s: kind must be one of %s" % (who, tuple(_backend.OBSERVE_KINDS)))
         if deformed and self._backend is not None and not isinstance(self._backend, _backend.Handle):
-            raise NotImplementedError("volume_term(deformed=True) is not available on partitioned runs")
+            raise NotImplementedError("%s(deformed=True) is not available on partitioned runs" % who)
         if deformed and not self.solver.mechanics:
-            raise ValueError("volume_term(deformed=True) needs a run with mechanics (the cells move with the displacement)")
+            raise ValueError("%s(deformed=True) needs a run with mechanics (the cells move with the displacement)" % who)
         mask = None
         if tissues is not None:
             if isinstance(tissues, str):
@@ -436,7 +460,7 @@ class TumorGrowth(FenicsSimulation):
             for name in tissues:
                 tid = ids.get(str(name).lower())
                 if tid is None:
-                    raise ValueError("volume_term: unknown tissue %r (known: %s)" % (name, sorted(ids)))
+                    raise ValueError("%s: unknown tissue %r (known: %s)" % (who, name, sorted(ids)))
                 if tid < n_labels:          # (a tissue that no cell carries counts nothing)
                     mask[tid] = 1
         term = dict(step=int(step), kind='obs_volume', observable=kind, level=float(threshold), smooth=float(smooth),
@@ -612,6 +636,9 @@ class TumorGrowth(FenicsSimulation):
             if np.any(np.asarray(flux) != 0.0):
                 raise NotImplementedError("adjoint_hessian: von Neumann data on the concentration scale with D; "
                                           "second derivatives in D are not available for such a run")
+        if any(t.get('kind') == 'obs_com' for t in terms):
+            raise NotImplementedError("adjoint_hessian: second order of a centre-of-mass term (com_term) is not built; use "
+                                      "a first-order method")
         if any(t.get('deformed') and t.get('kind') == 'obs_volume' for t in terms):
             raise NotImplementedError("adjoint_hessian: second order through the displacement of a deformed volume term "
                                       "(volume_term(deformed=True)) is not built; use a first-order method")

@@ -1058,7 +1058,26 @@ int glims_observe_info(const glims_ctx* h, int64_t out[4]);
  * load), through the same hipMemGetInfo refusal.  Second order through u is not built: while a deformed volume term is stored,
  * glims_adjoint_hessian, _hessian_spmd and _hessian_full return GLIMS_E_USAGE.  Further refusals of _terms2 (GLIMS_E_USAGE,
  * the old list left in place): a deformed term on a handle set up without mechanics, a scale that is not finite.
- * Not built: centre-of-mass and moment terms, partitioned handles, second order for SHARP and for deformed terms. */
+ *
+ * CENTRE-OF-MASS terms (glims_adjoint_observable_terms3, moment = 1): the other number the workflow reports per scan and tissue.
+ * With p = X, or p = y = X + scale u_k for a deformed term, T_T the signed measure factor of the volume terms (|T|, or
+ * sigma_T vol(y_T)) and b_T[0 .. d+1] the barycentric values of the query (csrc/observe_clip.h),
+ *     V = sum_T T_T b_T[0],   M_a = sum_T T_T sum_m b_T[1 + m] p_m,a,   X = M / V,   J_com = 1/2 weight |X - target_x|^2  (a < dim),
+ * V and M the numbers glims_observe returns, summed over the counted labels.  With alpha = weight (X - target_x) / V and
+ * psi_m,T = alpha . (p_m,T - X), both held fixed,
+ *     dJ/dc_k,i = sum_{T holds i} T_T sum_m psi_m,T d b_T[1 + m] / d c_i,
+ *     dJ/du_k,n = scale sum_{T holds n as vertex m} sigma_T (B_T cof_m(y_T) + vol(y_T) b_T[1 + m] alpha),   B_T = sum_m b_T[1 + m] psi_m,T.
+ * A quotient needs V and M before any partial can be weighted: a batch with such a term first runs a moments pass over the
+ * cells and a fixed-order sum that leave V, M, X, alpha and J on the device (no host round trip), then the gradient pass of
+ * the volume terms, which writes the psi-weighted partials into the same planes (coefficient 1).  A batch may mix volume and
+ * centre-of-mass terms of both configurations; one without a centre-of-mass term launches the kernels and gives the bits it
+ * gave before.  EMPTY measure: if V is not > 0 at an evaluation the term adds J = 0 and zero gradients there (out[3] = 1 of
+ * _info3); it is no error -- an optimiser may step there.  Extra scratch: 8 (dim+1) n_cells bytes per deformed centre-of-mass
+ * term of a pass, through the same hipMemGetInfo refusal.  Second order is not built: while a centre-of-mass term is stored,
+ * glims_adjoint_hessian, _hessian_spmd and _hessian_full return GLIMS_E_USAGE.  Further refusals of _terms3 (GLIMS_E_USAGE,
+ * the old list left in place): moment outside 0 .. 1, a target_x entry (of the first dim) that is not finite; and everything
+ * _terms2 refuses.
+ * Not built: higher moments, partitioned handles, second order for SHARP, for deformed and for centre-of-mass terms. */
 typedef struct glims_observable_misfit {
   int64_t step;              /* recorded step observed (0 = c_0) */
   int     kind;              /* GLIMS_OBSERVE_MASS / _SHARP / _SMOOTH */
@@ -1087,6 +1106,23 @@ int glims_adjoint_observable_terms2(glims_ctx* h, int n, const glims_observable_
  * no cell is counted).  Before the first evaluation out[2] = -1, *V = NaN, *min_ratio = NaN; a reference term keeps
  * out[2] = -1 and *min_ratio = NaN. */
 int glims_adjoint_observable_info2(glims_ctx* h, int k, int64_t out[4], double* V, double* min_ratio);
+/* the fields of glims_observable_misfit2, then what the term compares */
+typedef struct glims_observable_misfit3 {
+  int64_t step;
+  int     kind;
+  double  level, smooth;
+  double  weight, target;
+  const uint8_t* labels;
+  int     deformed;
+  double  scale;
+  int     moment;            /* 0: the volume term (target used), 1: centre of mass (target_x used) */
+  double  target_x[3];       /* [dim] */
+} glims_observable_misfit3;
+/* replaces the SAME stored list as glims_adjoint_observable_terms / _terms2 (which store their terms with moment = 0); n = 0 clears */
+int glims_adjoint_observable_terms3(glims_ctx* h, int n, const glims_observable_misfit3* terms);
+/* as _info2, plus out[3] = 1 when the LAST evaluation found the measure of a centre-of-mass term empty (V not > 0), and
+ * com[0 .. dim-1] = the last X = M / V: NaN before the first evaluation, when empty, for a volume term and in com[dim ..] */
+int glims_adjoint_observable_info3(glims_ctx* h, int k, int64_t out[4], double* V, double* min_ratio, double com[3]);
 
 /* ---- single-node multi-GPU (one process per GPU, RCCL over xGMI) ------------------------------------- */
 

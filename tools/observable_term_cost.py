@@ -22,6 +22,15 @@ configuration plus a u_l2 term on the same step -- so that both sides pay the st
 with the volume terms deformed; medians of `--reps` after a warm-up.  Per pass, from the library's event pairs: the DEF = 1 cell
 pass with its sum, the gather of the c-partials, the load kernel (k_observe_def_load_cells) and the D-component gather into the
 elastic adjoint's load, with the algorithmic bytes of each.  APPENDS its lines (config "deformed_*") to the same file.
+
+    python tools/observable_term_cost.py --com [--nodes 1000000] [--steps 10] [--reps 5]
+
+What CENTRE-OF-MASS terms cost (glims_adjoint_observable_terms3), on the same mesh with mechanics on: eight SMOOTH and eight SHARP
+terms on the last step, in the reference and in the deformed configuration, once as volume terms and once as centre-of-mass
+terms, in ONE process.  Per pass, from the library's event pairs: the moments pass (k_observe_mom_cells + its sum; centre of
+mass only), the gradient cell pass with its sum, the gather, and for deformed terms the load kernel and the u-gather.  The
+figure of merit is (moments + cells) of the centre-of-mass batch over cells of the volume batch.  APPENDS its lines (config
+"com_*" / "vol_*") to profiles/com_term_cost.jsonl (or --out).
 """
 import argparse
 import json
@@ -98,6 +107,104 @@ def deformed_pass_times(h, terms, n_labels, reps):
             if m and cur:
                 cur[-1][3:] = [float(m.group(2)), float(m.group(3))]
     return calls[1:]
+
+
+def com_pass_times(h, terms, n_labels, reps):
+    """[[terms, cells ms, gather ms, load ms, u-gather ms, moments ms]] of every pass of `reps` gradient calls after a warm-up"""
+    os.environ["GLIMS_OBSERVABLE_TIMING"] = "1"
+    with tempfile.TemporaryFile(mode="w+b") as tmp:
+        sys.stderr.flush()
+        saved = os.dup(2)
+        os.dup2(tmp.fileno(), 2)
+        try:
+            for rep in range(reps + 1):
+                h.adjoint_gradient(terms, n_labels, want_dc0=False)
+                os.write(2, b"glims observable terms: end of call\n")
+        finally:
+            os.dup2(saved, 2)
+            os.close(saved)
+            del os.environ["GLIMS_OBSERVABLE_TIMING"]
+        tmp.seek(0)
+        calls, cur = [], []
+        for line in tmp.read().decode().splitlines():
+            if "end of call" in line:
+                calls.append(cur)
+                cur = []
+                continue
+            m = re.match(r"glims observable terms: step (\d+)\s+terms (\d+)\s+cells ([0-9.]+) ms\s+gather ([0-9.]+) ms", line)
+            if m:
+                cur.append([int(m.group(2)), float(m.group(3)), float(m.group(4)), 0.0, 0.0, 0.0])
+            m = re.match(r"glims observable terms: step (\d+)\s+deformed pass\s+load ([0-9.]+) ms\s+u-gather ([0-9.]+) ms", line)
+            if m and cur:
+                cur[-1][3:5] = [float(m.group(2)), float(m.group(3))]
+            m = re.match(r"glims observable terms: step (\d+)\s+moments pass ([0-9.]+) ms", line)
+            if m and cur:
+                cur[-1][5] = float(m.group(2))
+    return calls[1:]
+
+
+def main_com(args):
+    from glimslib_amd import _backend, workloads
+    from oracle.glims_oracle import boundary_facets
+    w = workloads.config_brain_like(args.nodes, isolate=True)   # (the mesh builder forks: not from this process)
+    mesh, d = w.mesh, w.mesh.points.shape[1]
+    pts = np.asarray(mesh.points, dtype=np.float64)
+    n_labels = len(w.tables["D"])
+    n_cells, n_nodes = int(mesh.num_cells()), int(mesh.num_vertices())
+    h = _backend.Handle(pts, mesh.cells, np.asarray(w.cell_label, dtype=np.int32))
+    h.set_materials(*[w.tables[k] for k in ("D", "rho", "gamma", "E", "nu")])
+    h.set_options(dt=w.dt)
+    xb = np.unique(boundary_facets(mesh.cells)[0])
+    h.set_dirichlet_u((xb[:, None] * d + np.arange(d)[None]).ravel(), np.zeros(len(xb) * d))
+    h.setup(with_mechanics=True)
+    h.set_state(w.c0)
+    h.adjoint_record(True)
+    assert h.step(args.steps) == _backend.GLIMS_OK
+    c_last = h.get_state(want_u=False)[0]
+    centre = pts.mean(axis=0)
+    n = 8
+    levels = np.linspace(0.12, 0.80, n) * min(1.0, float(c_last.max()))
+    lines = []
+    for kind in ("smooth", "sharp"):
+        for deformed in (False, True):
+            vol_ms = None
+            for what in ("vol", "com"):
+                terms = [dict(step=args.steps, kind="obs_volume" if what == "vol" else "obs_com", observable=kind,
+                              level=float(lv), smooth=0.05, target=0.0 if what == "vol" else centre, weight=1.0,
+                              deformed=deformed, scale=1.0) for lv in levels]
+                h.set_observable_terms(terms)
+                walls = []
+                for rep in range(args.reps + 1):
+                    t0 = time.perf_counter()
+                    J = h.adjoint_gradient([], n_labels, want_dc0=False)[0]
+                    walls.append(time.perf_counter() - t0)
+                calls = com_pass_times(h, [], n_labels, args.reps)
+                per_pass = [p for c in calls for p in c]
+                med = lambda k: round(float(np.median([p[k] for p in per_pass])), 4)
+                info = h.observable_term_info(0)
+                rec = dict(config="%s_%s%s_%d" % (what, "deformed_" if deformed else "", kind, n), workload=w.name,
+                           n_nodes=n_nodes, n_cells=n_cells, steps=args.steps, kind=kind, n_terms=n, deformed=deformed,
+                           J=float(J), gradient_wall_s=round(float(np.median(walls[1:])), 5), passes_per_call=len(calls[0]),
+                           moments_ms_per_pass=med(5), cells_ms_per_pass=med(1), gather_ms_per_pass=med(2),
+                           load_ms_per_pass=med(3), u_gather_ms_per_pass=med(4), V_first=info["V"], cut_first=info["cut"])
+                if what == "vol":
+                    vol_ms = rec
+                else:
+                    rec["com_first"] = [float(v) for v in info["com"]]
+                    rec["cell_passes_over_volume_batch"] = round((rec["moments_ms_per_pass"] + rec["cells_ms_per_pass"]) /
+                                                                 vol_ms["cells_ms_per_pass"], 3)
+                    rec["gather_over_volume_batch"] = round(rec["gather_ms_per_pass"] / vol_ms["gather_ms_per_pass"], 3)
+                    # the moments pass: vertex ids, label and volume per cell, c and X (and u_k) once per node
+                    rec["model_bytes_moments"] = int(n_cells * (4 * (d + 1) + 1 + 8) + n_nodes * 8 * (1 + d * (2 if deformed else 1)))
+                lines.append(rec)
+                print(json.dumps(rec), flush=True)
+    h.set_observable_terms([])
+    h.close()
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "a") as f:
+        for ln in lines:
+            f.write(json.dumps(ln) + "\n")
+    return 0
 
 
 def main_deformed(args):
@@ -184,15 +291,20 @@ def main_deformed(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--deformed", action="store_true", help="the deformed-configuration comparison (appends to --out)")
+    ap.add_argument("--com", action="store_true", help="centre-of-mass terms against volume terms (appends to --out)")
     ap.add_argument("--nodes", type=int, default=1000000)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "observable_term_cost.jsonl"))
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "com_term_cost.jsonl" if args.com else "observable_term_cost.jsonl")
     import torch
     if not torch.cuda.is_available():
         print("observable_term_cost.py: no GPU visible", file=sys.stderr)
         return 3
+    if args.com:
+        return main_com(args)
     if args.deformed:
         return main_deformed(args)
     from glimslib_amd import _backend, workloads
