@@ -130,6 +130,13 @@ class ImageMisfit(C.Structure):
                 ("pweight", C.POINTER(C.c_double))]
 
 
+class DisplacementImageMisfit(C.Structure):
+    """glims_displacement_image_misfit: a displacement-image misfit term (target [n_points][dim] / pweight [n_points] in the
+    point order of the sampler, cweight the per-component weights)."""
+    _fields_ = [("step", C.c_int64), ("sampler", C.c_int64), ("weight", C.c_double), ("scale", C.c_double),
+                ("cweight", C.c_double * 3), ("target", C.POINTER(C.c_double)), ("pweight", C.POINTER(C.c_double))]
+
+
 class DeformedImageMisfit(C.Structure):
     """glims_deformed_image_misfit: an image term of the deformed configuration; it carries its own point set (xyz, or the
     grid origin / spacing / size when xyz is NULL)."""
@@ -226,6 +233,8 @@ SIGNATURES = {
     "glims_sampler_destroy": (C.c_int, [_h, C.c_int64]),
     "glims_adjoint_image_terms": (C.c_int, [_h, C.c_int, C.POINTER(ImageMisfit)]),
     "glims_adjoint_image_info": (C.c_int, [_h, C.c_int, _i64p]),
+    "glims_adjoint_displacement_image_terms": (C.c_int, [_h, C.c_int, C.POINTER(DisplacementImageMisfit)]),
+    "glims_adjoint_displacement_image_info": (C.c_int, [_h, C.c_int, _i64p]),
     "glims_adjoint_deformed_image_terms": (C.c_int, [_h, C.c_int, C.POINTER(DeformedImageMisfit)]),
     "glims_adjoint_deformed_image_info": (C.c_int, [_h, C.c_int, _i64p, _dp]),
     "glims_adjoint_observable_terms": (C.c_int, [_h, C.c_int, C.POINTER(ObservableMisfit)]),
@@ -308,6 +317,7 @@ class Handle:
         self.n_labels = None   # label count of the last successful set_materials
         self._image_terms = []   # what the library's stored image terms were made from (see _sync_image_terms)
         self._deformed_terms = []   # ... and the stored deformed image terms (see _split_terms)
+        self._displacement_terms = []   # ... and the stored displacement image terms
         self._observable_terms = []   # ... and the keys of the stored volume terms
         self._observable_from_list = False
         self._warned_folded = False
@@ -562,7 +572,9 @@ class Handle:
         smooth=1}; targets in the caller's node order ([n_nodes] or [n_nodes, dim]).  Image-space terms go in the same list:
         {step, kind ('img_l2' | 'img_thresh'), sampler (a :class:`Sampler` of this handle), target ([n_points], any shape;
         NaN = not observed), pweight=None, weight=1, level=0, smooth=1}; they are stored on the device (set_image_terms) and
-        re-sent only when they differ from what the handle holds.  An image term with ``deformed=True`` observes the DEFORMED
+        re-sent only when they differ from what the handle holds.  A displacement image term {step, kind: 'img_u_l2',
+        sampler, target [n_points, dim], pweight=None, weight=1, scale=1, cweight=None} compares the sampled displacement
+        with a warp field or landmark displacements (set_displacement_image_terms).  An image term with ``deformed=True`` observes the DEFORMED
         configuration x = X + scale u_k and carries its own points instead of a sampler: {..., deformed=True, scale=1.0,
         grid=(origin, spacing, size) or points=[n_points, dim]} (set_deformed_image_terms; the gradient through the location).
         Returns (J, dJ/dD [n_labels], dJ/drho, dJ/dgamma, dJ/dc0 [n_nodes] or None); with elastic=True (glims_adjoint_gradient_full)
@@ -627,6 +639,59 @@ class Handle:
         """(sampler id, number of points, number of observed points) of stored image term k."""
         out = np.zeros(3, dtype=np.int64)
         self._check(self.lib.glims_adjoint_image_info(self._h, int(k), _ptr(out, _i64p)))
+        return tuple(int(v) for v in out)
+
+    # -- displacement-image misfit terms (glims_adjoint_displacement_image_*) --------------------------
+    def _displacement_key(self, t):
+        """What identifies a stored displacement image term: its scalars and the IDENTITY of its target / pweight arrays."""
+        sm = t["sampler"]
+        cw = t.get("cweight")
+        cw = None if cw is None else tuple(float(v) for v in np.ravel(cw))
+        return (int(t["step"]), int(getattr(sm, "id", sm)), float(t.get("weight", 1.0)), float(t.get("scale", 1.0)), cw,
+                id(t["target"]), id(t.get("pweight")))
+
+    def set_displacement_image_terms(self, terms, _from_list=False):
+        """glims_adjoint_displacement_image_terms: replace the handle's stored displacement image terms (an empty list
+        clears them).  Each term: {step, kind: 'img_u_l2', sampler (a fixed :class:`Sampler` of this handle), target
+        [n_points, dim] (NaN = not observed), pweight=None, weight=1, scale=1, cweight=None ([dim] component weights, default
+        1)}.  J = 1/2 weight sum_p q_p sum_a cweight_a (scale (P u_k)_pa - target_pa)^2.  Target and pweight are copied to the
+        device once; every later adjoint_gradient / adjoint_hessian adds these terms."""
+        terms = list(terms)
+        arr = (DisplacementImageMisfit * max(1, len(terms)))()
+        keep = []
+        for k, t in enumerate(terms):
+            sm = t["sampler"]
+            if isinstance(sm, Sampler) and sm.handle is not self:
+                raise ValueError("displacement image term %d: its sampler belongs to another handle" % k)
+            tg = np.asarray(t["target"], dtype=np.float64)
+            if tg.size % self.dim or (isinstance(sm, Sampler) and tg.size != sm.n_points * self.dim):
+                raise ValueError("displacement image term %d: target has %d values, not n_points x %d" % (k, tg.size, self.dim))
+            tg = _f64(tg.reshape(-1, self.dim))
+            q = t.get("pweight")
+            if q is not None:
+                q = _f64(np.asarray(q, dtype=np.float64).reshape(-1), (tg.shape[0],))
+            cw = t.get("cweight")
+            cw = np.ones(self.dim) if cw is None else np.asarray(cw, dtype=np.float64).reshape(-1)
+            if cw.size != self.dim:
+                raise ValueError("displacement image term %d: cweight has %d entries, the mesh %d dimensions"
+                                 % (k, cw.size, self.dim))
+            keep.append((tg, q))
+            m = DisplacementImageMisfit()
+            m.step, m.sampler = int(t["step"]), int(getattr(sm, "id", sm))
+            m.weight, m.scale = float(t.get("weight", 1.0)), float(t.get("scale", 1.0))
+            for a in range(3):
+                m.cweight[a] = float(cw[a]) if a < self.dim else 0.0
+            m.target, m.pweight = _ptr(tg, _dp), _ptr(q, _dp)
+            arr[k] = m
+        self._check(self.lib.glims_adjoint_displacement_image_terms(self._h, len(terms), arr))
+        # (the caller's arrays are kept alive: their identity is what _split_terms compares)
+        self._displacement_terms = [(self._displacement_key(t), t["target"], t.get("pweight")) for t in terms]
+        self._displacement_from_list = bool(_from_list)
+
+    def displacement_image_term_info(self, k):
+        """(sampler id, number of points, number of observed points) of stored displacement image term k."""
+        out = np.zeros(3, dtype=np.int64)
+        self._check(self.lib.glims_adjoint_displacement_image_info(self._h, int(k), _ptr(out, _i64p)))
         return tuple(int(v) for v in out)
 
     # -- image terms of the deformed configuration (glims_adjoint_deformed_image_*) -------------------
@@ -864,6 +929,11 @@ class Handle:
             if [self._observable_key(t) for t in volume] != getattr(self, "_observable_terms", []):
                 self.set_observable_terms(volume, _from_list=True)
             terms = [t for t in terms if t["kind"] not in ("obs_volume", "obs_com")]
+        warp = [t for t in terms if t["kind"] == "img_u_l2"]
+        if warp or getattr(self, "_displacement_from_list", False):
+            if [self._displacement_key(t) for t in warp] != [k for k, _, _ in self._displacement_terms]:
+                self.set_displacement_image_terms(warp, _from_list=True)
+            terms = [t for t in terms if t["kind"] != "img_u_l2"]
         moving = [t for t in terms if _IMAGE_KINDS.get(t["kind"]) is not None and t.get("deformed")]
         if moving or getattr(self, "_deformed_from_list", False):
             if [self._deformed_key(t) for t in moving] != [k for k, _ in self._deformed_terms]:

@@ -565,8 +565,8 @@ HessShape adjoint_shape(glims_ctx* h, int n_terms, const glims_misfit* terms, in
   s.n_send = h->n_send;
   s.spmm_blocks = P > 0 ? gl_spmm_blocks(h) : 0;
   for (int k = 0; k < n_terms; ++k) s.term_is_u.push_back(terms[k].kind == GLIMS_MISFIT_U_L2);
-  // (a deformed image or volume term observes u_k as a displacement term does)
-  s.any_u = hess_any_u(s.term_is_u, !h->dimg_terms.empty() || gl_observable_terms_any_deformed(h));
+  // (a displacement image term, a deformed image or volume term observes u_k as a displacement term does)
+  s.any_u = hess_any_u(s.term_is_u, !h->uimg_terms.empty() || !h->dimg_terms.empty() || gl_observable_terms_any_deformed(h));
   return s;
 }
 
@@ -649,14 +649,37 @@ struct BackwardSweep {
   bool solve_uk(const double* c) {
     gl_apply_G(h, c, wk.murhs.p);
     int64_t its = 0;
+    const bool timed = getenv("GLIMS_UIMG_TIMING") != nullptr;   // (next to the figures of the displacement image terms)
+    const double t0 = timed ? omp_get_wtime() : 0.0;
     status = solve_elastic(h, wk, wk.murhs.p, wk.uk.p, h->have_fixed_u ? h->m_uD.p : nullptr, 1e-12, &its);
+    if (timed) {
+      GL_HIP(hipStreamSynchronize(h->st));
+      fprintf(stderr, "glims displacement image terms: u_k solve %.4f ms  %lld iterations\n", 1e3 * (omp_get_wtime() - t0),
+              (long long)its);
+    }
     if (status != GLIMS_OK) return false;
     GL_HIP(hipMemsetAsync(wk.murhs.p, 0, (size_t)h->n_nodes * D * sizeof(double), h->st));
     return true;
   }
 
+  // The stored displacement image terms (glims_adjoint_displacement_image_terms) that observe `step`, in their list order,
+  // after the step's nodal and fixed image terms: J += 1/2 w sum_p q_p sum_a kappa_a (s (P u_k)_p,a - d_p,a)^2 and
+  // murhs += P^T R.  have_u: u_k is solved already; returns whether it is now (the coupling adjoint follows then).  No stored
+  // term: no launch.
+  bool displacement_image_terms(int step, const double* c, bool have_u) {
+    for (const GlDisplacementImageTerm* t : h->uimg_terms) {
+      if (t->step != step) continue;
+      if (!have_u) {
+        if (!solve_uk(c)) return have_u;
+        have_u = true;
+      }
+      J += 0.5 * t->weight * gl_displacement_image_misfit_grad(h, *t, wk.uk.p, wk.murhs.p);
+    }
+    return have_u;
+  }
+
   // The stored deformed image terms (glims_adjoint_deformed_image_terms) that observe `step`, in their list order, after the
-  // step's nodal and fixed image terms: the points are located in the mesh at X + scale u_k, J += 1/2 w sum_p q_p (h(v_p) -
+  // step's nodal, fixed image and displacement image terms: the points are located in the mesh at X + scale u_k, J += 1/2 w sum_p q_p (h(v_p) -
   // t_p)^2, g += P^T r and murhs += P^T S (the load through the location).  have_u: u_k is solved already; returns whether
   // it is now (the coupling adjoint follows then).  No stored term: no launch.
   bool deformed_image_terms(int step, const double* c, bool have_u) {
@@ -808,6 +831,10 @@ int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_o
     bool have_u = sw.nodal_terms(step, c, [](const glims_misfit&) {});
     if (sw.status != GLIMS_OK) break;
     image_terms_of_step(h, step, c, wk.g.p, &sw.J);
+    if (!h->uimg_terms.empty()) {
+      have_u = sw.displacement_image_terms(step, c, have_u);
+      if (sw.status != GLIMS_OK) break;
+    }
     if (!h->dimg_terms.empty()) {
       have_u = sw.deformed_image_terms(step, c, have_u);
       if (sw.status != GLIMS_OK) break;
@@ -1771,8 +1798,8 @@ struct HessianSweep {
     gl_halo_exchange(h, m.du.p, D);
     return true;
   }
-  // dmu = K_el^-1 sum w M_vec du (0 on the constrained dofs), with el_dirs - dK mu_k: dmurhs through ue, uMe, then dmu with
-  // current ghosts
+  // dmu = K_el^-1 (sum w M_vec du + sum P^T R2(du)) (0 on the constrained dofs), with el_dirs - dK mu_k: dmurhs through ue,
+  // uMe and the samplers' staging, then dmu with current ghosts
   bool dmu_solve(int step, int p) {
     GL_HIP(hipMemsetAsync(m.dmurhs.p, 0, (size_t)nd * sizeof(double), h->st));
     for (int k = 0; k < call.n_terms; ++k) {
@@ -1788,6 +1815,10 @@ struct HessianSweep {
         GL_CHECK_LAUNCH();
       }
     }
+    // the stored displacement image terms of the step, in list order: dmurhs += P^T R2 of this direction's du.  The call holds
+    // one tangent du at a time, so the P-column kernel runs with one column per direction.
+    for (const GlDisplacementImageTerm* t : h->uimg_terms)
+      if (t->step == step) gl_displacement_image_misfit_second(h, *t, m.du.p, 1, nd, m.dmurhs.p);
     if (s.el_dirs) {   // - dK mu_k
       hipLaunchKernelGGL(k_sub, dim3(grid_of(n * D)), dim3(256), 0, h->st, n * D, m.dKmu.p + (size_t)p * nd, m.dmurhs.p);
       GL_CHECK_LAUNCH();
@@ -1914,9 +1945,13 @@ int hessian_t(glims_ctx* h, const HessCall& call) {
   for (int step = N; step >= 0 && sw.status == GLIMS_OK; --step) {
     const double* c = sw.begin_step(step);
     GL_HIP(hipMemsetAsync(mem.dg.p, 0, (size_t)P * nn * sizeof(double), h->st));
-    const bool have_u = sw.nodal_terms(step, c, [&](const glims_misfit& tm) { hs.concentration_second(step, c, tm); });
+    bool have_u = sw.nodal_terms(step, c, [&](const glims_misfit& tm) { hs.concentration_second(step, c, tm); });
     if (sw.status != GLIMS_OK) break;
     image_terms_of_step(h, step, c, wk.g.p, &sw.J, P, mem.dc_of(step, 0), nn, mem.dg.p);
+    if (!h->uimg_terms.empty()) {   // (their second order: dmu_solve, from each direction's du)
+      have_u = sw.displacement_image_terms(step, c, have_u);
+      if (sw.status != GLIMS_OK) break;
+    }
     gl_observable_terms_of_step(h, step, c, wk.g.p, &sw.J, P, mem.dc_of(step, 0), nn, mem.dg.p);
     if (have_u && !(sw.coupling_adjoint(c) && hs.coupling_second(step, c))) break;
     if (step == 0) {
@@ -2006,6 +2041,12 @@ void check_gradient_call(glims_ctx* h, int n_terms, const glims_misfit* terms, c
     GL_REQUIRE(h->img_terms[k]->step <= N, who + ": stored image term " + std::to_string(k) + " observes step " +
                                                std::to_string(h->img_terms[k]->step) + ", the recording has steps 0.." +
                                                std::to_string(N));
+  for (size_t k = 0; k < h->uimg_terms.size(); ++k) {
+    GL_REQUIRE(h->uimg_terms[k]->step <= N, who + ": stored displacement image term " + std::to_string(k) + " observes step " +
+                                                std::to_string(h->uimg_terms[k]->step) + ", the recording has steps 0.." +
+                                                std::to_string(N));
+    GL_REQUIRE(h->have_mech, who + ": a stored displacement image term needs glims_setup(with_mechanics=1)");
+  }
   for (size_t k = 0; k < h->dimg_terms.size(); ++k)
     GL_REQUIRE(h->dimg_terms[k]->step <= N, who + ": stored deformed image term " + std::to_string(k) + " observes step " +
                                                 std::to_string(h->dimg_terms[k]->step) + ", the recording has steps 0.." +

@@ -1061,6 +1061,20 @@ int glims_adjoint_deformed_image_info(glims_ctx* h, int k, int64_t out[4], doubl
   });
 }
 
+int glims_adjoint_displacement_image_terms(glims_ctx* h, int n, const glims_displacement_image_misfit* terms) {
+  return guarded(h, [&]() {
+    gl_displacement_image_terms_set(h, n, terms);
+    return GLIMS_OK;
+  });
+}
+
+int glims_adjoint_displacement_image_info(glims_ctx* h, int k, int64_t out[3]) {
+  return guarded(h, [&]() {
+    gl_displacement_image_term_info(h, k, out);
+    return GLIMS_OK;
+  });
+}
+
 int glims_adjoint_observable_terms(glims_ctx* h, int n, const glims_observable_misfit* terms) {
   return guarded(h, [&]() {
     gl_observable_terms_set(h, n, terms);

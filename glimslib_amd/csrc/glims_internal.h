@@ -494,6 +494,17 @@ struct GlImageTerm {
   dvec<double> target, pweight;             // [n]; pweight empty = 1
 };
 
+// One stored displacement-image misfit term (glims_adjoint_displacement_image_terms; kernels in sample.hip).  target is kept
+// as component planes [dim][n] so that the point-parallel kernels read it coalesced; plane 0 holds NaN at every point that is
+// not observed (outside the mesh, q_p = 0, NaN in a component with kappa_a != 0) -- the misfit kernels test that alone -- and
+// the planes of the components with kappa_a = 0 hold 0 at the observed points (they enter no arithmetic).
+struct GlDisplacementImageTerm {
+  int64_t step = 0, sampler = -1, n = 0, n_obs = 0;
+  double weight = 1.0, scale = 1.0;
+  double cweight[3] = {1.0, 1.0, 1.0};
+  dvec<double> target, pweight;             // [dim][n]; [n], empty = 1
+};
+
 // One stored image term of the DEFORMED configuration (glims_adjoint_deformed_image_terms; kernels in sample.hip).  Its points
 // are located anew, in the mesh at X + scale u_k, at every evaluation: the term owns its point set and a scratch sampler.
 // target holds NaN where the caller's array does or where q_p = 0; whether a point is found is decided per evaluation.
@@ -780,6 +791,7 @@ struct glims_ctx {
   std::vector<GlSampler*> samplers;         // owned (sample.hip); a destroyed sampler leaves a nullptr so that ids stay valid
   std::vector<GlImageTerm*> img_terms;      // owned (sample.hip): the stored image-space misfit terms of the adjoint calls
   std::vector<GlDeformedImageTerm*> dimg_terms;   // owned (sample.hip): the stored deformed-configuration image terms
+  std::vector<GlDisplacementImageTerm*> uimg_terms;   // owned (sample.hip): the stored displacement-image terms
   DeriveState derive;
   ObserveState observe;
   ObsTermState obs_terms;                   // the stored volume misfit terms of the adjoint calls (observe.hip)
@@ -920,6 +932,14 @@ double gl_image_misfit_grad(glims_ctx* h, const GlImageTerm& t, const double* c,
 // dg[j * ld + row] += (P^T r2_j)[row] for the P directions dc[j * ld + .]
 void gl_image_misfit_second(glims_ctx* h, const GlImageTerm& t, const double* c, const double* dc, int P, int64_t ld,
                             double* dg);
+void gl_displacement_image_terms_set(glims_ctx* h, int n, const glims_displacement_image_misfit* terms);
+void gl_displacement_image_term_info(glims_ctx* h, int k, int64_t out[3]);
+// murhs[row * dim + a] += (P^T R)[row][a] of stored term t at the displacement u ([n_nodes][dim], internal numbering); returns
+// sum_p q_p sum_a kappa_a (s (P u)_p,a - d_p,a)^2 (fixed order)
+double gl_displacement_image_misfit_grad(glims_ctx* h, const GlDisplacementImageTerm& t, const double* u, double* murhs);
+// dmurhs[j * ld + row * dim + a] += (P^T R2_j)[row][a] for the P tangents du[j * ld + .] ([n_nodes][dim] each)
+void gl_displacement_image_misfit_second(glims_ctx* h, const GlDisplacementImageTerm& t, const double* du, int P, int64_t ld,
+                                         double* dmurhs);
 void gl_deformed_image_terms_set(glims_ctx* h, int n, const glims_deformed_image_misfit* terms);
 void gl_deformed_image_term_info(glims_ctx* h, int k, int64_t out[4], double* min_ratio);
 // Stored deformed term t at the state c and displacement u (both internal numbering): locates its points in the mesh at

@@ -37,8 +37,9 @@ struct HessShape {
   bool el_sums = false;                // the E / nu rows of the Hessian are summed (k_hesens)
 };
 
-// A step is observed through the displacement when a nodal term is a displacement term or a stored deformed image term
-// observes u_k (gradient calls only: the Hessian calls refuse those)
+// A step is observed through the displacement when a nodal term is a displacement term, or a stored term observes u_k: a
+// displacement image term (gradient and Hessian calls) or a deformed image / volume term (gradient calls only: the Hessian
+// calls refuse those)
 inline bool hess_any_u(const std::vector<uint8_t>& term_is_u, bool deformed_terms = false) {
   bool any = deformed_terms;
   for (uint8_t u : term_is_u) any = any || u != 0;

@@ -706,6 +706,160 @@ __global__ __launch_bounds__(256) void k_img_misfit_dir(int64_t n, int P, int64_
   }
 }
 
+// ---- displacement-image misfit terms (glims_hip.h, "displacement-image misfit terms") ------------------
+// The target d is kept as component planes d[a * n + p]: a wave reads 64 consecutive doubles of a plane (512 B), where the
+// caller's [n][D] rows would put the D loads of a lane 8 D bytes apart.  R / R2 must be [n][D] rows for P^T (k_sample_t_cells
+// reads r[p * ncomp + a]); the block's 256 D values go through LDS and leave as consecutive doubles.
+struct UimgKappa {
+  double k[3];
+};
+
+// once per stored term: d[0 * n + p] = NaN where the point is not observed (outside the mesh, q_p = 0, NaN in a component with
+// kappa_a != 0), and at an observed point the components with kappa_a = 0 become 0; counts the observed points.
+template <int D>
+__global__ __launch_bounds__(256) void k_uimg_prepare(int64_t n, const int32_t* __restrict__ cell, const double* __restrict__ q,
+                                                      UimgKappa kap, double* __restrict__ d,
+                                                      unsigned long long* __restrict__ n_obs) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool obs = false;
+  if (p < n) {
+    obs = cell[p] >= 0 && (!q || q[p] != 0.0);
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+      const double dv = d[(int64_t)a * n + p];
+      if (kap.k[a] != 0.0 && !(dv == dv)) obs = false;
+    }
+    if (!obs) {
+      d[p] = __longlong_as_double(0x7ff8000000000000LL);
+    } else {
+#pragma unroll
+      for (int a = 0; a < D; ++a)
+        if (kap.k[a] == 0.0) d[(int64_t)a * n + p] = 0.0;
+    }
+  }
+  const int here = __syncthreads_count(obs);
+  if (threadIdx.x == 0 && here) atomicAdd(n_obs, (unsigned long long)here);   // (integer: order-independent)
+}
+
+// the block's rows sr[256][D] to out[(first point of the block) * D ...], consecutive doubles; after a __syncthreads of its own
+template <int D>
+__device__ __forceinline__ void uimg_store_rows(int64_t n, const double* sr, double* __restrict__ out) {
+  __syncthreads();
+  const int64_t base = (int64_t)blockIdx.x * 256 * D, end = n * D;
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    const int64_t i = base + k * 256 + threadIdx.x;
+    if (i < end) out[i] = sr[k * 256 + threadIdx.x];
+  }
+}
+
+// One thread per point: (P u)_p,a = sum_m w u[node_m][a] gathered from u_k ([node][D], internal numbering),
+// e_a = s (P u)_p,a - d_p,a, R[p][a] = weight q kappa_a s e_a for an observed point (plane 0 of d not NaN) and a component
+// with kappa_a != 0, else 0 -- the others enter no arithmetic.  part[block] = the block's sum of q sum_a kappa_a e_a^2: the
+// wave's butterfly, then the four wave sums in a fixed order.
+// Bytes per point: (D + 1) (4 + 8) node ids and weights + 8 D (d) + 8 (q, if present) + 8 D (R); u is gathered through the
+// caches (D consecutive doubles per node).  2-D: 76 B, 3-D: 104 B with q.
+template <int D>
+__global__ __launch_bounds__(256) void k_uimg_misfit(int64_t n, double weight, double scale, UimgKappa kap,
+                                                     const int32_t* __restrict__ node, const double* __restrict__ w,
+                                                     const double* __restrict__ u, const double* __restrict__ d,
+                                                     const double* __restrict__ q, double* __restrict__ R,
+                                                     double* __restrict__ part) {
+  constexpr int NV = D + 1;
+  __shared__ double sr[256 * D];
+  __shared__ double sm[4];
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  double sq = 0.0, rv[D];
+#pragma unroll
+  for (int a = 0; a < D; ++a) rv[a] = 0.0;
+  if (p < n) {
+    const double d0 = d[p];
+    if (d0 == d0) {
+      int32_t nd[NV];
+      double wt[NV];
+#pragma unroll
+      for (int m = 0; m < NV; ++m) {
+        nd[m] = node[p * NV + m];
+        wt[m] = w[p * NV + m];
+      }
+      const double qv = q ? q[p] : 1.0;
+#pragma unroll
+      for (int a = 0; a < D; ++a) {
+        if (kap.k[a] == 0.0) continue;
+        double v = 0.0;
+#pragma unroll
+        for (int m = 0; m < NV; ++m) v += wt[m] * u[(int64_t)nd[m] * D + a];
+        const double e = scale * v - (a == 0 ? d0 : d[(int64_t)a * n + p]);
+        rv[a] = weight * qv * kap.k[a] * scale * e;
+        sq += kap.k[a] * e * e;
+      }
+      sq *= qv;
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < D; ++a) sr[threadIdx.x * D + a] = rv[a];
+  const double ws = img_wave_sum(sq);
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = ws;
+  uimg_store_rows<D>(n, sr, R);
+  if (threadIdx.x == 0) part[blockIdx.x] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
+}
+
+// Second order, one thread per point, all P columns of a call: R2[j][p][a] = weight q kappa_a s^2 (P du_j)_p,a (0 for a point
+// that is not observed or a component with kappa_a = 0); column j is a contiguous [n][D] block, what P^T reads, and runs the
+// same arithmetic whatever P is.
+// Bytes per point: (D + 1) (4 + 8) + 8 (plane 0 of d) + 8 (q, if present) + 8 D P (R2); the P tangents are gathered through
+// the caches.
+template <int D>
+__global__ __launch_bounds__(256) void k_uimg_misfit_dir(int64_t n, int P, int64_t ld, double weight, double scale,
+                                                         UimgKappa kap, const int32_t* __restrict__ node,
+                                                         const double* __restrict__ w, const double* __restrict__ du,
+                                                         const double* __restrict__ d, const double* __restrict__ q,
+                                                         double* __restrict__ R2) {
+  constexpr int NV = D + 1;
+  __shared__ double sr[256 * D];
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int32_t nd[NV];
+  double wt[NV], coef[D];
+#pragma unroll
+  for (int m = 0; m < NV; ++m) {
+    nd[m] = 0;
+    wt[m] = 0.0;
+  }
+#pragma unroll
+  for (int a = 0; a < D; ++a) coef[a] = 0.0;
+  bool obs = false;
+  if (p < n) {
+    const double d0 = d[p];
+    obs = d0 == d0;
+  }
+  if (obs) {
+#pragma unroll
+    for (int m = 0; m < NV; ++m) {
+      nd[m] = node[p * NV + m];
+      wt[m] = w[p * NV + m];
+    }
+    const double qv = q ? q[p] : 1.0;
+#pragma unroll
+    for (int a = 0; a < D; ++a) coef[a] = weight * qv * kap.k[a] * scale * scale;
+  }
+  for (int j = 0; j < P; ++j) {
+    const double* dj = du + (size_t)j * ld;
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+      double r = 0.0;
+      if (obs && kap.k[a] != 0.0) {
+        double v = 0.0;
+#pragma unroll
+        for (int m = 0; m < NV; ++m) v += wt[m] * dj[(int64_t)nd[m] * D + a];
+        r = coef[a] * v;
+      }
+      sr[threadIdx.x * D + a] = r;
+    }
+    uimg_store_rows<D>(n, sr, R2 + (size_t)j * n * D);
+    __syncthreads();   // sr is rewritten by the next column
+  }
+}
+
 // ---- glims_sampler_resolve ---------------------------------------------------------------------------------------------------
 // keys: row `rank` of buf[world][m] (zero elsewhere) = the global id of the local winner of point p0 + i, as a double, or
 // GL_RESOLVE_NONE.  8 B written per point (+ 4 B cell, 8 B cell_gid gathered).
@@ -1820,6 +1974,154 @@ void gl_image_misfit_second(glims_ctx* h, const GlImageTerm& t, const double* c,
   gl_sampler_transpose_dev(h, t.sampler, s.out.p, P, dg, 1, ld, true);
 }
 
+// ---- stored displacement-image terms -------------------------------------------------------------------------------------------
+void gl_displacement_image_terms_set(glims_ctx* h, int n, const glims_displacement_image_misfit* terms) {
+  const char* who = "glims_adjoint_displacement_image_terms";
+  GL_REQUIRE(n >= 0 && (n == 0 || terms), std::string(who) + ": bad term list");
+  const int D = h->dim;
+  // every check before anything is allocated or the old list is touched
+  if (n > 0) {
+    GL_REQUIRE(h->world <= 1, std::string(who) + ": not available on partitioned handles (world > 1)");
+    GL_REQUIRE(h->is_setup && h->have_mech, std::string(who) + ": a displacement image term needs glims_setup(with_mechanics=1)");
+  }
+  size_t need = 0;
+  for (int k = 0; k < n; ++k) {
+    const glims_displacement_image_misfit& t = terms[k];
+    const std::string tk = std::string(who) + ": term " + std::to_string(k);
+    GlSampler& s = sampler_of(h, t.sampler, who);
+    GL_REQUIRE(!s.deformed, tk + ": its sampler is a deformed one: the term compares u at reference points (a warp field on "
+                               "the deformed grid is not built)");
+    GL_REQUIRE(std::isfinite(t.weight), tk + ": non-finite weight");
+    GL_REQUIRE(std::isfinite(t.scale), tk + ": non-finite scale");
+    bool any = false;
+    for (int a = 0; a < D; ++a) {
+      GL_REQUIRE(t.cweight[a] >= 0.0 && std::isfinite(t.cweight[a]),
+                 tk + ": cweight[" + std::to_string(a) + "] is negative or not finite");
+      any = any || t.cweight[a] != 0.0;
+    }
+    GL_REQUIRE(any, tk + ": every cweight is 0: the term observes nothing");
+    GL_REQUIRE(t.target, tk + ": null target");
+    GL_REQUIRE(t.step >= 0, tk + ": negative step");
+    if (t.pweight)
+      for (int64_t p = 0; p < s.n; ++p)
+        GL_REQUIRE(t.pweight[p] >= 0.0 && std::isfinite(t.pweight[p]),
+                   tk + ": pweight[" + std::to_string(p) + "] is negative or not finite");
+    need += (size_t)s.n * 8 * (D + (t.pweight ? 1 : 0));
+  }
+  if (n > 0) need_memory(who, need + (1u << 20));
+  std::vector<GlDisplacementImageTerm*> fresh;
+  try {
+    dvec<unsigned long long> d_obs;
+    std::vector<double> planes;
+    for (int k = 0; k < n; ++k) {
+      const glims_displacement_image_misfit& t = terms[k];
+      GlSampler& s = sampler_of(h, t.sampler, who);
+      auto* g = new GlDisplacementImageTerm();
+      fresh.push_back(g);
+      g->step = t.step;
+      g->sampler = t.sampler;
+      g->weight = t.weight;
+      g->scale = t.scale;
+      UimgKappa kap = {{0.0, 0.0, 0.0}};
+      for (int a = 0; a < D; ++a) kap.k[a] = g->cweight[a] = t.cweight[a];
+      for (int a = D; a < 3; ++a) g->cweight[a] = 0.0;
+      g->n = s.n;
+      if (s.n == 0) continue;
+      planes.resize((size_t)s.n * D);   // the caller's rows [n][D] -> planes [D][n]
+      for (int64_t p = 0; p < s.n; ++p)
+        for (int a = 0; a < D; ++a) planes[(size_t)a * s.n + p] = t.target[(size_t)p * D + a];
+      g->target.upload(planes.data(), planes.size(), h->st);
+      if (t.pweight) g->pweight.upload(t.pweight, (size_t)s.n, h->st);
+      d_obs.alloc_zero(1, h->st);
+      if (D == 2)
+        hipLaunchKernelGGL(k_uimg_prepare<2>, dim3(grid_of(s.n)), dim3(256), 0, h->st, s.n, s.cell.p, g->pweight.p, kap,
+                           g->target.p, d_obs.p);
+      else
+        hipLaunchKernelGGL(k_uimg_prepare<3>, dim3(grid_of(s.n)), dim3(256), 0, h->st, s.n, s.cell.p, g->pweight.p, kap,
+                           g->target.p, d_obs.p);
+      GL_CHECK_LAUNCH();
+      unsigned long long no = 0;
+      GL_HIP(hipMemcpyAsync(&no, d_obs.p, sizeof(no), hipMemcpyDeviceToHost, h->st));
+      GL_HIP(hipStreamSynchronize(h->st));   // (the caller's arrays and `planes` are free again)
+      g->n_obs = (int64_t)no;
+    }
+  } catch (...) {
+    (void)hipStreamSynchronize(h->st);
+    for (auto* g : fresh) delete g;
+    throw;
+  }
+  for (auto* g : h->uimg_terms) delete g;
+  h->uimg_terms.swap(fresh);
+}
+
+void gl_displacement_image_term_info(glims_ctx* h, int k, int64_t out[3]) {
+  const char* who = "glims_adjoint_displacement_image_info";
+  GL_REQUIRE(out, std::string(who) + ": null output");
+  GL_REQUIRE(k >= 0 && k < (int)h->uimg_terms.size(), std::string(who) + ": no stored term " + std::to_string(k));
+  const GlDisplacementImageTerm& t = *h->uimg_terms[(size_t)k];
+  out[0] = t.sampler;
+  out[1] = t.n;
+  out[2] = t.n_obs;
+}
+
+double gl_displacement_image_misfit_grad(glims_ctx* h, const GlDisplacementImageTerm& t, const double* u, double* murhs) {
+  GlSampler& s = sampler_of(h, t.sampler, "glims_adjoint_gradient");
+  if (s.n == 0) return 0.0;
+  const int D = h->dim;
+  image_staging(h, s, D);
+  const unsigned nb = grid_of(s.n);
+  const UimgKappa kap = {{t.cweight[0], t.cweight[1], t.cweight[2]}};
+  // GLIMS_UIMG_TIMING: an event pair around the misfit kernel with its sum and one around the transpose, one line per term
+  const bool timed = getenv("GLIMS_UIMG_TIMING") != nullptr;
+  float ms_misfit = 0.f, ms_t = 0.f;
+  if (timed) GL_HIP(hipEventRecord(h->ev_a, h->st));
+  if (D == 2)
+    hipLaunchKernelGGL(k_uimg_misfit<2>, dim3(nb), dim3(256), 0, h->st, s.n, t.weight, t.scale, kap, s.node.p, s.w.p, u,
+                       t.target.p, t.pweight.p, s.out.p, s.part.p);
+  else
+    hipLaunchKernelGGL(k_uimg_misfit<3>, dim3(nb), dim3(256), 0, h->st, s.n, t.weight, t.scale, kap, s.node.p, s.w.p, u,
+                       t.target.p, t.pweight.p, s.out.p, s.part.p);
+  GL_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_img_sum, dim3(1), dim3(1024), 0, h->st, (int64_t)nb, s.part.p, s.part.p + nb);
+  GL_CHECK_LAUNCH();
+  if (timed) {
+    GL_HIP(hipEventRecord(h->ev_b, h->st));
+    GL_HIP(hipEventSynchronize(h->ev_b));
+    GL_HIP(hipEventElapsedTime(&ms_misfit, h->ev_a, h->ev_b));
+    GL_HIP(hipEventRecord(h->ev_a, h->st));
+  }
+  transpose_on(h, s, s.out.p, D, murhs, D, 1, true);
+  if (timed) {
+    GL_HIP(hipEventRecord(h->ev_b, h->st));
+    GL_HIP(hipEventSynchronize(h->ev_b));
+    GL_HIP(hipEventElapsedTime(&ms_t, h->ev_a, h->ev_b));
+    fprintf(stderr, "glims displacement image terms: step %lld  points %lld  misfit %.4f ms  transpose %.4f ms\n",
+            (long long)t.step, (long long)s.n, ms_misfit, ms_t);
+  }
+  double sum = 0.0;
+  GL_HIP(hipMemcpyAsync(&sum, s.part.p + nb, sizeof(double), hipMemcpyDeviceToHost, h->st));
+  GL_HIP(hipStreamSynchronize(h->st));
+  return sum;
+}
+
+void gl_displacement_image_misfit_second(glims_ctx* h, const GlDisplacementImageTerm& t, const double* du, int P, int64_t ld,
+                                         double* dmurhs) {
+  GlSampler& s = sampler_of(h, t.sampler, "glims_adjoint_hessian");
+  if (s.n == 0) return;
+  const int D = h->dim;
+  image_staging(h, s, D * P);
+  const UimgKappa kap = {{t.cweight[0], t.cweight[1], t.cweight[2]}};
+  if (D == 2)
+    hipLaunchKernelGGL(k_uimg_misfit_dir<2>, dim3(grid_of(s.n)), dim3(256), 0, h->st, s.n, P, ld, t.weight, t.scale, kap,
+                       s.node.p, s.w.p, du, t.target.p, t.pweight.p, s.out.p);
+  else
+    hipLaunchKernelGGL(k_uimg_misfit_dir<3>, dim3(grid_of(s.n)), dim3(256), 0, h->st, s.n, P, ld, t.weight, t.scale, kap,
+                       s.node.p, s.w.p, du, t.target.p, t.pweight.p, s.out.p);
+  GL_CHECK_LAUNCH();
+  for (int j = 0; j < P; ++j)
+    transpose_on(h, s, s.out.p + (size_t)j * s.n * D, D, dmurhs + (size_t)j * ld, D, 1, true);
+}
+
 // ---- stored image terms of the deformed configuration ------------------------------------------------------------------------
 namespace {
 void delete_deformed_term(GlDeformedImageTerm* t) {
@@ -2003,6 +2305,10 @@ void gl_sampler_destroy(glims_ctx* h, int64_t id) {
     GL_REQUIRE(h->img_terms[k]->sampler != id, "glims_sampler_destroy: sampler " + std::to_string(id) +
                                                    " is used by stored image term " + std::to_string(k) +
                                                    " (glims_adjoint_image_terms)");
+  for (size_t k = 0; k < h->uimg_terms.size(); ++k)
+    GL_REQUIRE(h->uimg_terms[k]->sampler != id, "glims_sampler_destroy: sampler " + std::to_string(id) +
+                                                    " is used by stored displacement image term " + std::to_string(k) +
+                                                    " (glims_adjoint_displacement_image_terms)");
   GL_HIP(hipStreamSynchronize(h->st));
   delete h->samplers[(size_t)id];
   h->samplers[(size_t)id] = nullptr;
@@ -2013,6 +2319,8 @@ void gl_sampler_destroy_all(glims_ctx* h) {
   h->img_terms.clear();
   for (auto* t : h->dimg_terms) delete_deformed_term(t);
   h->dimg_terms.clear();
+  for (auto* t : h->uimg_terms) delete t;
+  h->uimg_terms.clear();
   for (auto* s : h->samplers) delete s;
   h->samplers.clear();
 }

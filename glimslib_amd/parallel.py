@@ -357,6 +357,8 @@ class DistributedHandle:
         for t in terms:
             if t["kind"] in ("obs_volume", "obs_com"):
                 self._no_volume_terms()
+            if t["kind"] == "img_u_l2":
+                self._no_displacement_image_terms()
             if t["kind"] in _backend._IMAGE_KINDS:
                 loc.append(self._image_term(t))
                 continue
@@ -434,6 +436,18 @@ class DistributedHandle:
         parts = [None] * self.world
         self.dist.all_gather_object(parts, int(n_obs))
         return sid, n, int(sum(parts))
+
+    # -- displacement-image misfit terms: single-rank handles only (the library refuses them on a partitioned handle) --------
+    @staticmethod
+    def _no_displacement_image_terms():
+        raise NotImplementedError("displacement image misfit terms (set_displacement_image_terms, kind 'img_u_l2') are not "
+                                  "available on partitioned runs")
+
+    def set_displacement_image_terms(self, terms):
+        self._no_displacement_image_terms()
+
+    def displacement_image_term_info(self, k):
+        self._no_displacement_image_terms()
 
     # -- volume misfit terms: single-rank handles only (the library refuses them on a partitioned handle, as glims_observe) --
     @staticmethod

@@ -398,6 +398,103 @@ class TumorGrowth(FenicsSimulation):
             cache[1][key] = (term, image, mask)   # (image and mask stay alive: their identity is the key)
         return cache[1][key][0]
 
+    def _displacement_term_checks(self, who):
+        if self._backend is None:
+            raise RuntimeError("%s needs a run() first (the points are located in the run's device mesh)" % who)
+        if not self.solver.mechanics:
+            raise ValueError("%s needs a run with mechanics (it observes the displacement)" % who)
+        if not isinstance(self._backend, _backend.Handle):
+            raise NotImplementedError("%s is not available on partitioned runs; run on one GPU" % who)
+
+    @staticmethod
+    def _component_weights(components, dim, who):
+        if components is None:
+            return None
+        cw = tuple(float(v) for v in np.ravel(components))
+        if len(cw) != dim:
+            raise ValueError("%s: components has %d entries, the mesh %d dimensions" % (who, len(cw), dim))
+        return cw
+
+    def displacement_image_term(self, step, image, weight=1.0, mask=None, volume_weighted=True, scale=1.0, components=None):
+        """
+        A misfit term that compares the displacement of recorded step `step` with a WARP-FIELD image (utils.data_io.Image
+        with `dim` channels, e.g. the deformation field of an image registration, image_based_optimization.py:943-978) where
+        the image was measured:  1/2 w sum_voxels q sum_a kappa_a (scale u_a(X_voxel) - image_a)^2.  The voxels are points of
+        the REFERENCE configuration (the cached grid sampler of sample_image; sample_image('displacement', step) produces
+        such an image).  Voxels outside the mesh and voxels with a NaN in an observed component are not observed; `mask`
+        (array like one channel of the image, >= 0) weighs the voxels -- mask out where the registration is unreliable;
+        `components` are the per-component weights kappa (default 1; (1, 0, 0) observes a midline shift alone); `scale`
+        converts the simulated displacement to the image's sign convention and unit.  With volume_weighted the weight is
+        multiplied by the voxel volume.  Pass the term to adjoint_gradient / adjoint_hessian / ReducedFunctional with the
+        other terms: it is quadratic in u, so second order is exact, also in E and nu (elastic_hessian=True).  The same
+        arguments give the same term object, whose arrays the backend uploads once.  Needs a run with mechanics (ValueError);
+        partitioned runs raise NotImplementedError.
+        """
+        who = "displacement_image_term"
+        if self._backend is None:
+            raise RuntimeError("%s needs a run() first (the grid is located in the run's device mesh)" % who)
+        dim = self._backend.dim
+        if not getattr(image, 'is_vector', False):
+            raise ValueError("%s takes a vector image with %d channels (image_term takes the scalar ones)" % (who, dim))
+        if image.GetNumberOfComponentsPerPixel() != dim or image.dim != dim:
+            raise ValueError("%s: the image has %d channels on %d axes, the mesh %d dimensions"
+                             % (who, image.GetNumberOfComponentsPerPixel(), image.dim, dim))
+        self._displacement_term_checks(who)
+        cw = self._component_weights(components, dim, who)
+        key = ('grid', int(step), id(image), float(weight), id(mask), bool(volume_weighted), float(scale), cw)
+        cache = getattr(self, '_displacement_terms', None)
+        if cache is None or cache[0] is not self._backend:
+            cache = self._displacement_terms = (self._backend, {})
+        if key not in cache[1]:
+            sampler = self._grid_sampler(image.GetOrigin(), image.GetSpacing(), image.GetSize())[1]
+            target = np.ascontiguousarray(image.array, dtype=np.float64).reshape(-1, dim)   # [z, y, x][a]: the sampler's order
+            q = None
+            if mask is not None:
+                q = np.ascontiguousarray(mask, dtype=np.float64).reshape(-1)
+                if q.shape[0] != target.shape[0]:
+                    raise ValueError("%s: the mask has %d voxels, the image %d" % (who, q.size, target.shape[0]))
+            w = float(weight) * (float(np.prod(image.GetSpacing())) if volume_weighted else 1.0)
+            term = dict(step=int(step), kind='img_u_l2', sampler=sampler, target=target, pweight=q, weight=w,
+                        scale=float(scale), cweight=cw)
+            cache[1][key] = (term, image, mask)   # (image and mask stay alive: their identity is the key)
+        return cache[1][key][0]
+
+    def landmark_term(self, step, points, displacements, weight=1.0, pweight=None, scale=1.0, components=None):
+        """
+        displacement_image_term for a POINT SET: `points` [n, dim] are landmarks of the reference configuration,
+        `displacements` [n, dim] what was measured there (NaN = not observed), `pweight` [n] optional weights >= 0.
+        1/2 w sum_p q_p sum_a kappa_a (scale u_a(X_p) - displacements_pa)^2.  The point sampler is located once per point
+        array and simulation; the same arguments give the same term object.
+        """
+        who = "landmark_term"
+        self._displacement_term_checks(who)
+        h = self._backend
+        dim = h.dim
+        cw = self._component_weights(components, dim, who)
+        key = ('points', int(step), id(points), id(displacements), float(weight), id(pweight), float(scale), cw)
+        cache = getattr(self, '_displacement_terms', None)
+        if cache is None or cache[0] is not h:
+            cache = self._displacement_terms = (h, {})
+        if key not in cache[1]:
+            xyz = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, dim)
+            target = np.ascontiguousarray(displacements, dtype=np.float64).reshape(-1, dim)
+            if target.shape != xyz.shape:
+                raise ValueError("%s: %d points, %d displacements" % (who, xyz.shape[0], target.shape[0]))
+            q = None
+            if pweight is not None:
+                q = np.ascontiguousarray(pweight, dtype=np.float64).reshape(-1)
+                if q.shape[0] != xyz.shape[0]:
+                    raise ValueError("%s: %d points, %d weights" % (who, xyz.shape[0], q.size))
+            pcache = getattr(self, '_landmark_samplers', None)
+            if pcache is None or pcache[0] is not h:
+                pcache = self._landmark_samplers = (h, {})
+            if id(points) not in pcache[1]:
+                pcache[1][id(points)] = (h.sampler_points(xyz), points)
+            term = dict(step=int(step), kind='img_u_l2', sampler=pcache[1][id(points)][0], target=target, pweight=q,
+                        weight=float(weight), scale=float(scale), cweight=cw)
+            cache[1][key] = (term, points, displacements, pweight)
+        return cache[1][key][0]
+
     def volume_term(self, step, target, threshold=0.12, kind='smooth', smooth=0.01, tissues=None, weight=1.0, deformed=False,
                     scale=1.0):
         """

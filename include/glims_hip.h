@@ -1124,6 +1124,48 @@ int glims_adjoint_observable_terms3(glims_ctx* h, int n, const glims_observable_
  * com[0 .. dim-1] = the last X = M / V: NaN before the first evaluation, when empty, for a volume term and in com[dim ..] */
 int glims_adjoint_observable_info3(glims_ctx* h, int k, int64_t out[4], double* V, double* min_ratio, double com[3]);
 
+/* ---- displacement-image misfit terms: a registration warp field or landmark displacements as data ----------------------------
+ * The reference's third misfit term compares the displacement with the warp-field image of an ANTs registration, after
+ * interpolating that image onto the mesh (optimization_workflow/image_based_optimization.py:660-708, :943-978).  Here the data
+ * stay where they were measured: with P the operator of a FIXED (reference-configuration) sampler, p its points and
+ * u_k = K_el^-1 (G c_k + f) the displacement of recorded step k (the adjoint's own solve, to 1e-12 ||rhs||),
+ *   J_uimg        = 1/2 w sum_p q_p sum_a kappa_a (s (P u_k)_p,a - d_p,a)^2,
+ *   dJ/du_k       = P^T R,    R_p,a  = w q_p kappa_a s (s (P u_k)_p,a - d_p,a)       [n_points][dim],
+ *   d(dJ/du_k).du = P^T R2,   R2_p,a = w q_p kappa_a s^2 (P du)_p,a.
+ * d is the target [n_points][dim], q_p >= 0 an optional point weight, kappa_a >= 0 the component weights (cweight; (1,0,0)
+ * observes a midline shift alone), s a finite scale (warp fields come in both signs and in voxel or mm units).  A point is
+ * OBSERVED iff the sampler found it, q_p != 0 and d_p,a is not NaN for every component with kappa_a != 0; a NaN in a
+ * component with kappa_a = 0 is allowed and enters no arithmetic; the other points add nothing.  The term has no direct
+ * c-derivative: dJ/du_k is added to the right-hand side of the elastic adjoint, the vector a GLIMS_MISFIT_U_L2 term of the
+ * same step writes to, so u_k is solved ONCE per observed step and mu_k = K_el^-1 dJ/du_k once, whatever mix of terms needs
+ * them; G^T mu_k and the gamma, E and nu sums follow as for a displacement term.
+ *
+ * The terms are a THIRD stored list with the semantics of glims_adjoint_image_terms: the call replaces its own list only
+ * (n = 0 clears it), target and pweight are copied to the device once, the list survives glims_setup, glims_set_materials,
+ * glims_set_state and a new recording, glims_sampler_destroy of a sampler it uses is refused, and with an empty list every
+ * call issues exactly the work it issued before.  Per step glims_adjoint_gradient / _gradient_full evaluate the nodal terms,
+ * the fixed image terms, the displacement image terms in list order, then the deformed image terms and the observable terms.
+ * The term is quadratic in u and u is linear in c: glims_adjoint_hessian / _hessian_full add P^T R2 of each direction's own
+ * tangent du (which holds the dK part of an E / nu direction) to the right-hand side of the second elastic adjoint -- the
+ * products are exact, E and nu included.  No float atomics, sums in a fixed order: the same call gives the same bits.
+ *
+ * GLIMS_E_USAGE with a reason, the old list left in place: a partitioned handle (world > 1), a handle set up without
+ * mechanics, an unknown or DEFORMED sampler, a non-finite weight or scale, a negative or non-finite q_p or kappa_a, all
+ * kappa_a = 0, a null target, a negative step.  A step beyond the trajectory is refused by the gradient / Hessian call.
+ * Not built: partitioned handles, a warp field defined on the deformed grid (u at the material point sitting at x_p),
+ * interpolation other than the sampler's P1. */
+typedef struct glims_displacement_image_misfit {
+  int64_t step;            /* recorded step observed */
+  int64_t sampler;         /* id of a fixed sampler (glims_sampler_create_grid / _points) on this handle */
+  double  weight, scale;
+  double  cweight[3];      /* kappa_a, the first dim are read */
+  const double* target;    /* [n_points][dim], point order of the sampler */
+  const double* pweight;   /* [n_points] q_p, or NULL = 1 */
+} glims_displacement_image_misfit;
+int glims_adjoint_displacement_image_terms(glims_ctx* h, int n, const glims_displacement_image_misfit* terms);
+/* out = (sampler id, number of points, number of observed points) of stored term k */
+int glims_adjoint_displacement_image_info(glims_ctx* h, int k, int64_t out[3]);
+
 /* ---- single-node multi-GPU (one process per GPU, RCCL over xGMI) ------------------------------------- */
 
 #define GLIMS_UNIQUE_ID_BYTES 256   /* two RCCL unique ids: halo communicator + reduction communicator */
