@@ -182,6 +182,8 @@ SIGNATURES = {
     "glims_destroy": (C.c_int, [_h]),
     "glims_last_error": (C.c_char_p, [_h]),
     "glims_set_materials": (C.c_int, [_h, C.c_int, _dp, _dp, _dp, _dp, _dp]),
+    "glims_set_diffusion_tensor": (C.c_int, [_h, _dp]),
+    "glims_diffusion_tensor_info": (C.c_int, [_h, _i64p, _dp]),
     "glims_options_default": (C.c_int, [C.POINTER(Options)]),
     "glims_set_options": (C.c_int, [_h, C.POINTER(Options)]),
     "glims_set_dirichlet_u": (C.c_int, [_h, C.c_int64, _i64p, _dp]),
@@ -292,6 +294,28 @@ def _ptr(a, typ):
     return a.ctypes.data_as(typ) if a is not None else None
 
 
+def pack_diffusion_tensor(T, n_cells, dim):
+    """The packed field [n_cells, d (d + 1) / 2] (upper triangle row by row, the ITK order) of a tensor field given as
+    [n_cells, d, d], as the packed array itself, or as ONE [d, d] matrix for every cell.  ValueError for any other shape and
+    for a full matrix that is not symmetric (to 1e-12 of its largest entry); positive definiteness is the library's check."""
+    T = np.asarray(T, dtype=np.float64)
+    nt = dim * (dim + 1) // 2
+    iu = np.triu_indices(dim)
+    if T.shape == (dim, dim):
+        T = np.broadcast_to(T, (n_cells, dim, dim))
+    if T.shape == (n_cells, dim, dim):
+        asym = np.abs(T - np.swapaxes(T, 1, 2)).max(axis=(1, 2)) if n_cells else np.zeros(0)
+        scale = np.abs(T).max(axis=(1, 2)) if n_cells else np.zeros(0)
+        bad = np.nonzero(asym > 1e-12 * scale)[0]   # (a NaN compares False here and goes on to the library's check)
+        if len(bad):
+            raise ValueError("diffusion tensor of cell %d is not symmetric (%d such cells)" % (bad[0], len(bad)))
+        return np.ascontiguousarray(T[:, iu[0], iu[1]])
+    if T.shape == (n_cells, nt):
+        return np.ascontiguousarray(T)
+    raise ValueError("diffusion tensor of shape %s: need [%d, %d, %d], the packed [%d, %d] or one [%d, %d] matrix"
+                     % (T.shape, n_cells, dim, dim, n_cells, nt, dim, dim))
+
+
 class Handle:
     """Thin OO view of one ``glims_ctx`` (one mesh on one GPU)."""
 
@@ -346,6 +370,26 @@ class Handle:
         assert all(a.shape == (n,) for a in arrs)
         self._check(self.lib.glims_set_materials(self._h, n, *[_ptr(a, _dp) for a in arrs]))
         self.n_labels = n
+
+    def set_diffusion_tensor(self, T):
+        """glims_set_diffusion_tensor: the per-cell tensor field of the anisotropic model, flux D_t * T_cell grad c.  T is
+        [n_cells, d, d] (symmetric) or the packed [n_cells, d (d + 1) / 2] upper triangles row by row -- (xx, xy, yy) /
+        (xx, xy, xz, yy, yz, zz) -- in the caller's cell order; None clears the field.  Takes effect with the next setup()
+        (the contract of set_materials).  A non-finite or not positive-definite tensor raises BackendError(GLIMS_E_USAGE)
+        naming the first bad cell, and the previous field stays."""
+        if T is None:
+            self._check(self.lib.glims_set_diffusion_tensor(self._h, None))
+            return
+        T = pack_diffusion_tensor(T, self.n_cells, self.dim)
+        self._check(self.lib.glims_set_diffusion_tensor(self._h, _ptr(T, _dp)))
+
+    def diffusion_tensor_info(self):
+        """dict(present, n_cells, max_ratio): whether a tensor field is set and the largest lambda_max / lambda_min over its
+        cells (1.0 without a field)."""
+        out = np.zeros(2, dtype=np.int64)
+        r = C.c_double(0.0)
+        self._check(self.lib.glims_diffusion_tensor_info(self._h, _ptr(out, _i64p), C.byref(r)))
+        return dict(present=bool(out[0]), n_cells=int(out[1]), max_ratio=r.value)
 
     def set_options(self, **kw):
         for k, v in kw.items():

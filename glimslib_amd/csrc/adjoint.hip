@@ -13,6 +13,7 @@
 //   C_t = dJ/dgamma_t / (2 mu_t + d lam_t) give dJ/dp_t = gamma_t (2 mu' + d lam') C_t - (2 mu' A_t + lam' B_t).
 // (carrying capacity 1, as in the forward kernels: the reaction weights of k_corner_weights are rho |T| d!/(d+3)!.)
 #include "glims_internal.h"
+#include "diffusion_tensor.h"
 #include "hessian_plan.h"
 #include "lame_derivs.h"
 
@@ -127,12 +128,16 @@ __global__ void k_cell_counted(int64_t n_cells, int64_t n_own, int rank, const i
 // bitwise reproducible.  Bytes per cell: the geometry record (1 + NV D) x 8 (56 B in 2-D, 104 B in 3-D), NV x 4 B of vertex ids,
 // 1 B of label (+ 8 B of qcell in MODE 1); the gathered vectors (2 x 8 B per node, mu: 8 d B; MODE 2: u and mu, 2 x 8 d B)
 // mostly hit the caches.
-template <int D, int MODE>
+// ANISO (MODE 0 alone): q0 = int_T grad lambda^T TT_T grad c with the cell's tensor dten[e] (diffusion_tensor.h), + 8 d (d + 1) / 2
+// B per cell; ANISO = 0 is the kernel as it was: DT is empty there (the signature and kernel-argument layout of before), one
+// `const double*` with ANISO.
+template <int D, int MODE, int ANISO = 0, class... DT>
 __global__ __launch_bounds__(256) void k_sens(int64_t n_cells, int l0, const int32_t* __restrict__ cell_nodes,
                                               const double* __restrict__ egeo, const uint8_t* __restrict__ label,
                                               const double* __restrict__ mat, const double* __restrict__ c,
                                               const double* __restrict__ v, const uint8_t* __restrict__ counted,
-                                              double* __restrict__ qcell, double* __restrict__ partials) {
+                                              double* __restrict__ qcell, double* __restrict__ partials, DT... dten) {
+  static_assert(sizeof...(DT) == (ANISO ? 1 : 0), "the tensor field is passed with ANISO alone");
   constexpr int NV = D + 1, GE = 1 + NV * D;
   constexpr double f3 = D == 2 ? 1.0 / 60.0 : 1.0 / 120.0;   // d! / (d+3)!
   constexpr double f2 = D == 2 ? 1.0 / 12.0 : 1.0 / 20.0;    // d! / (d+2)!
@@ -197,8 +202,12 @@ __global__ __launch_bounds__(256) void k_sens(int64_t n_cells, int l0, const int
           lcc += lv[m] * cv[m] * cv[m];
         }
         double gg = 0.0;
+        if constexpr (ANISO != 0) {
+          gg = glims_dt_form<D>(glims_dt_field(dten...) + e * glims_dt_size<D>(), gl, gc);
+        } else {
 #pragma unroll
-        for (int a = 0; a < D; ++a) gg += gl[a] * gc[a];
+          for (int a = 0; a < D; ++a) gg += gl[a] * gc[a];
+        }
         a0 = vol * gg;
         // sum_{abc} l_a c_b c_c prod(alpha!) = Sl Sc^2 + 2 Sc (l.c) + Sl (c.c) + 2 sum l_a c_a^2;
         // sum_{ab} l_a c_b (1 + delta_ab)
@@ -458,9 +467,14 @@ void sens_pass(glims_ctx* h, int mode, const double* mat, const double* c, const
                double* qcell, double* part, double* sums, int ls, int k_off) {
   const int nb = sens_blocks(h);
   const auto kern = mode == 0 ? k_sens<D, 0> : mode == 1 ? k_sens<D, 1> : k_sens<D, 2>;
+  const bool aniso = mode == 0 && h->dten.p;   // a tensor field (glims_set_diffusion_tensor): the ANISO instance of mode 0
   for (int l0 = 0; l0 < h->n_labels; l0 += GL_ADJ_LT) {
-    hipLaunchKernelGGL(kern, dim3(nb), dim3(256), 0, h->st, h->n_cells, l0, h->adj.cell_nodes.p, h->egeo.p, h->label.p, mat, c,
-                       v, counted, qcell, part);
+    if (aniso)
+      hipLaunchKernelGGL((k_sens<D, 0, 1, const double*>), dim3(nb), dim3(256), 0, h->st, h->n_cells, l0, h->adj.cell_nodes.p,
+                         h->egeo.p, h->label.p, mat, c, v, counted, qcell, part, (const double*)h->dten.p);
+    else
+      hipLaunchKernelGGL(kern, dim3(nb), dim3(256), 0, h->st, h->n_cells, l0, h->adj.cell_nodes.p, h->egeo.p, h->label.p, mat, c,
+                         v, counted, qcell, part);
     GL_CHECK_LAUNCH();
     if (!sums) break;
     hipLaunchKernelGGL(k_sens_final, dim3(1), dim3(1024), 0, h->st, nb, l0, h->n_labels, ls, k_off, part, sums);
@@ -880,14 +894,18 @@ int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_o
 //                           + drho_p[t] int_T (2c - 1) lam phi_i)
 // Bytes per row and incidence: the slot word, cell id, geometry record and label as in the assembly; the gathered c / lam /
 // dc_p values mostly hit the caches.
-template <int D, int MODE>
+// ANISO: grad phi_i is replaced by TT_T grad phi_i once per incidence (the cell's tensor dten[e] is dead after that: no more
+// live registers in the direction loop), so gg[m] = grad phi_m^T TT_T grad phi_i.  ANISO = 0 is the kernel as it was (DT empty,
+// as in k_sens).
+template <int D, int MODE, int ANISO = 0, class... DT>
 __global__ __launch_bounds__(256) void k_hess_rows(int64_t n_own, int P, int64_t ld, const int64_t* __restrict__ cslice_ptr,
                                                    const uint32_t* __restrict__ cslots, const int32_t* __restrict__ celem,
                                                    const uint8_t* __restrict__ diag_k, const int32_t* __restrict__ cell_nodes,
                                                    const double* __restrict__ egeo, const uint8_t* __restrict__ label,
                                                    const double* __restrict__ mat, const double* __restrict__ dir, double dt,
                                                    const double* __restrict__ c, const double* __restrict__ lam,
-                                                   const double* __restrict__ dc, double* __restrict__ y) {
+                                                   const double* __restrict__ dc, double* __restrict__ y, DT... dten) {
+  static_assert(sizeof...(DT) == (ANISO ? 1 : 0), "the tensor field is passed with ANISO alone");
   constexpr int NV = D + 1, GE = 1 + NV * D;
   constexpr double f3 = D == 2 ? 1.0 / 60.0 : 1.0 / 120.0;   // d! / (d+3)!
   constexpr double f2 = D == 2 ? 1.0 / 12.0 : 1.0 / 20.0;    // d! / (d+2)!
@@ -916,6 +934,12 @@ __global__ __launch_bounds__(256) void k_hess_rows(int64_t n_own, int P, int64_t
       if (((sl >> (8 * m)) & 255u) == dk)
 #pragma unroll
         for (int a = 0; a < D; ++a) gi[a] = g[1 + m * D + a];
+    if constexpr (ANISO != 0) {   // gi <- TT_T gi
+      double t[D];
+      glims_dt_apply<D>(glims_dt_field(dten...) + (int64_t)e * glims_dt_size<D>(), gi, t);
+#pragma unroll
+      for (int a = 0; a < D; ++a) gi[a] = t[a];
+    }
     int nd[NV];
     double cv[NV], gg[NV];   // gg[m] = grad phi_m . grad phi_i
     double Sc = 0.0, cc = 0.0;
@@ -983,12 +1007,15 @@ __global__ __launch_bounds__(256) void k_hess_rows(int64_t n_own, int P, int64_t
 // Per-label Hessian sums of one direction, the layout, grid and fixed-order reduction of k_sens (then k_sens_final):
 //   q0 = int_T grad nu . grad c + grad lam . grad dc,   q1 = int_T nu (c^2 - c) + lam (2c - 1) dc   (exact for P1)
 // counted: as in k_sens (partitioned handles, else nullptr)
-template <int D>
+// ANISO: both gradient forms take the cell's tensor dten[e] in the middle; ANISO = 0 is the kernel as it was (DT empty, as in
+// k_sens).
+template <int D, int ANISO = 0, class... DT>
 __global__ __launch_bounds__(256) void k_hsens(int64_t n_cells, int l0, const int32_t* __restrict__ cell_nodes,
                                                const double* __restrict__ egeo, const uint8_t* __restrict__ label,
                                                const double* __restrict__ c, const double* __restrict__ lam,
                                                const double* __restrict__ dc, const double* __restrict__ nu,
-                                               const uint8_t* __restrict__ counted, double* __restrict__ partials) {
+                                               const uint8_t* __restrict__ counted, double* __restrict__ partials, DT... dten) {
+  static_assert(sizeof...(DT) == (ANISO ? 1 : 0), "the tensor field is passed with ANISO alone");
   constexpr int NV = D + 1, GE = 1 + NV * D;
   constexpr double f3 = D == 2 ? 1.0 / 60.0 : 1.0 / 120.0;
   constexpr double f2 = D == 2 ? 1.0 / 12.0 : 1.0 / 20.0;
@@ -1028,8 +1055,13 @@ __global__ __launch_bounds__(256) void k_hsens(int64_t n_cells, int l0, const in
       lcd += lm * cm * dm;
     }
     double gg = 0.0;
+    if constexpr (ANISO != 0) {
+      const double* T = glims_dt_field(dten...) + e * glims_dt_size<D>();
+      gg = glims_dt_form<D>(T, gv, gc) + glims_dt_form<D>(T, gl, gd);
+    } else {
 #pragma unroll
-    for (int a = 0; a < D; ++a) gg += gv[a] * gc[a] + gl[a] * gd[a];
+      for (int a = 0; a < D; ++a) gg += gv[a] * gc[a] + gl[a] * gd[a];
+    }
     const double a0 = vol * gg;
     // sum_{abc} x_a y_b z_c prod(alpha!) = Sx Sy Sz + Sx (y.z) + Sy (x.z) + Sz (x.y) + 2 sum x y z
     const double a1 = vol * (f3 * (Sv * Sc * Sc + 2.0 * Sc * vc + Sv * cc + 2.0 * vcc) - f2 * (Sv * Sc + vc) +
@@ -1727,9 +1759,14 @@ struct HessianSweep {
   }
   template <int MODE>
   void hess_rows(const double* c, const double* lam, const double* dc) {
-    hipLaunchKernelGGL((k_hess_rows<D, MODE>), dim3(grid_of(n)), dim3(256), 0, h->st, n, P, nn, pt.cslice_ptr.p, pt.cslots.p,
-                       pt.celem.p, pt.diag_k.p, h->adj.cell_nodes.p, h->egeo.p, h->label.p, h->mat.p, m.d_dir.p, dt, c, lam, dc,
-                       m.hrhs.p);
+    if (h->dten.p)   // a tensor field (glims_set_diffusion_tensor)
+      hipLaunchKernelGGL((k_hess_rows<D, MODE, 1, const double*>), dim3(grid_of(n)), dim3(256), 0, h->st, n, P, nn,
+                         pt.cslice_ptr.p, pt.cslots.p, pt.celem.p, pt.diag_k.p, h->adj.cell_nodes.p, h->egeo.p, h->label.p,
+                         h->mat.p, m.d_dir.p, dt, c, lam, dc, m.hrhs.p, (const double*)h->dten.p);
+    else
+      hipLaunchKernelGGL((k_hess_rows<D, MODE>), dim3(grid_of(n)), dim3(256), 0, h->st, n, P, nn, pt.cslice_ptr.p, pt.cslots.p,
+                         pt.celem.p, pt.diag_k.p, h->adj.cell_nodes.p, h->egeo.p, h->label.p, h->mat.p, m.d_dir.p, dt, c, lam, dc,
+                         m.hrhs.p);
     GL_CHECK_LAUNCH();
   }
   // mode 1 of the sensitivity pass into the directions' own qcell and partials: qcell of every cell, into `sums` (if any) the
@@ -1888,8 +1925,13 @@ struct HessianSweep {
     if (sw.status == GLIMS_OK) exchange_cols(m.nu.p);   // k_hsens and M nu_{n+1} read the ghosts
     for (int p = 0; p < P && sw.status == GLIMS_OK; ++p)
       for (int l0 = 0; l0 < L; l0 += GL_ADJ_LT) {
-        hipLaunchKernelGGL(k_hsens<D>, dim3(sens_blocks(h)), dim3(256), 0, h->st, h->n_cells, l0, h->adj.cell_nodes.p, h->egeo.p,
-                           h->label.p, c, wk.lam.p, m.dc_of(step, p), m.col(m.nu, p), counted, m.hpart.p);
+        if (h->dten.p)
+          hipLaunchKernelGGL((k_hsens<D, 1, const double*>), dim3(sens_blocks(h)), dim3(256), 0, h->st, h->n_cells, l0,
+                             h->adj.cell_nodes.p, h->egeo.p, h->label.p, c, wk.lam.p, m.dc_of(step, p), m.col(m.nu, p), counted,
+                             m.hpart.p, (const double*)h->dten.p);
+        else
+          hipLaunchKernelGGL(k_hsens<D>, dim3(sens_blocks(h)), dim3(256), 0, h->st, h->n_cells, l0, h->adj.cell_nodes.p, h->egeo.p,
+                             h->label.p, c, wk.lam.p, m.dc_of(step, p), m.col(m.nu, p), counted, m.hpart.p);
         GL_CHECK_LAUNCH();
         hipLaunchKernelGGL(k_sens_final, dim3(1), dim3(1024), 0, h->st, sens_blocks(h), l0, L, 3, 0, m.hpart.p, m.hsums_of(p));
         GL_CHECK_LAUNCH();

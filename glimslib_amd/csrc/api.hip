@@ -1,5 +1,6 @@
 // extern "C" surface of libglimship.so (see include/glims_hip.h for the contract of every entry point).
 #include "glims_internal.h"
+#include "diffusion_tensor.h"
 
 #include <cerrno>
 #include <cmath>
@@ -73,6 +74,41 @@ uint64_t fnv_of(glims_ctx* h, const T* dev, size_t n) {
   const unsigned char* b = reinterpret_cast<const unsigned char*>(host.data());
   for (size_t i = 0; i < n * sizeof(T); ++i) x = (x ^ b[i]) * 1099511628211ull;
   return x;
+}
+
+// glims_set_diffusion_tensor: the caller's field into the internal cell order, checked on the way.  bad[0] counts the cells
+// whose tensor is not finite or not positive definite, bad[1] is the smallest caller's index among them (as k_egeo reports
+// degenerate cells); ratio[block] = the block's largest lambda_max / lambda_min over its valid cells (a maximum: any order
+// gives the same bits).
+template <int D>
+__global__ __launch_bounds__(256) void k_dten_store(int64_t n_cells, const double* __restrict__ src,
+                                                    const int32_t* __restrict__ cell_new2old, double* __restrict__ dst,
+                                                    unsigned long long* __restrict__ bad, double* __restrict__ ratio) {
+  constexpr int NT = glims_dt_size<D>();
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  double r = 1.0;
+  if (e < n_cells) {
+    const int64_t old = cell_new2old ? (int64_t)cell_new2old[e] : e;
+    double T[NT];
+#pragma unroll
+    for (int k = 0; k < NT; ++k) T[k] = src[old * NT + k];
+#pragma unroll
+    for (int k = 0; k < NT; ++k) dst[e * NT + k] = T[k];
+    if (glims_dt_spd<D>(T)) {
+      r = glims_dt_ratio<D>(T);
+    } else {
+      atomicAdd(bad, 1ull);
+      atomicMin(bad + 1, (unsigned long long)old);
+    }
+  }
+  __shared__ double sm[256];
+  sm[threadIdx.x] = r;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) sm[threadIdx.x] = fmax(sm[threadIdx.x], sm[threadIdx.x + w]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) ratio[blockIdx.x] = sm[0];
 }
 
 template <class F>
@@ -367,6 +403,69 @@ int glims_set_materials(glims_ctx* h, int n_labels, const double* D, const doubl
     h->prepared.drop();
     return GLIMS_OK;
   });
+}
+
+int glims_set_diffusion_tensor(glims_ctx* h, const double* T) {
+  return guarded(h, [&]() {
+    // what the operators of the next glims_setup are built from changes: the dependent state goes as in glims_set_materials
+    // (only once the field is accepted: after a refusal the handle is as it was and still steps)
+    auto forget = [&]() {
+      h->mech.forget_operator();
+      h->mg.ready = h->mg_rd.ready = false;
+      h->rd_precond_active = 0;
+      h->derive.forget_u();
+      h->adj.invalidate("glims_set_diffusion_tensor after recording started");
+      h->is_setup = false;
+      h->prepared.drop();
+    };
+    if (!T) {
+      if (!h->dten.p) return GLIMS_OK;   // none before, none now
+      h->dten.release();
+      h->dten_ratio = 1.0;
+      forget();
+      return GLIMS_OK;
+    }
+    const int NT = h->dim * (h->dim + 1) / 2;
+    const int64_t nc = h->n_cells;
+    dvec<double> src, dst, ratio;
+    dvec<unsigned long long> bad;
+    const unsigned long long init[2] = {0ull, ~0ull};
+    bad.upload(init, 2, h->st);
+    src.upload(T, (size_t)nc * NT, h->st);
+    dst.alloc((size_t)nc * NT);
+    const unsigned grid = grid_of(nc);
+    ratio.alloc(grid);
+    if (h->dim == 2)
+      hipLaunchKernelGGL(k_dten_store<2>, dim3(grid), dim3(256), 0, h->st, nc, src.p, h->cell_new2old.p, dst.p, bad.p, ratio.p);
+    else
+      hipLaunchKernelGGL(k_dten_store<3>, dim3(grid), dim3(256), 0, h->st, nc, src.p, h->cell_new2old.p, dst.p, bad.p, ratio.p);
+    GL_HIP(hipGetLastError());
+    unsigned long long res[2];
+    std::vector<double> rmax(grid);
+    GL_HIP(hipMemcpyAsync(res, bad.p, sizeof(res), hipMemcpyDeviceToHost, h->st));
+    GL_HIP(hipMemcpyAsync(rmax.data(), ratio.p, rmax.size() * sizeof(double), hipMemcpyDeviceToHost, h->st));
+    GL_HIP(hipStreamSynchronize(h->st));
+    if (res[0] != 0)
+      throw glims_error(GLIMS_E_USAGE, std::to_string(res[0]) + " diffusion tensor(s) not finite or not positive definite, "
+                                           "the first one is cell " + std::to_string(res[1]) +
+                                           " (the previous field, or none, stays in place)");
+    std::swap(h->dten.p, dst.p);   // (dst now holds the previous field and frees it)
+    std::swap(h->dten.n, dst.n);
+    h->dten_ratio = 1.0;
+    for (double r : rmax) h->dten_ratio = std::max(h->dten_ratio, r);
+    forget();
+    return GLIMS_OK;
+  });
+}
+
+int glims_diffusion_tensor_info(const glims_ctx* h, int64_t out[2], double* max_ratio) {
+  if (!h) return GLIMS_E_USAGE;
+  if (out) {
+    out[0] = h->dten.p ? 1 : 0;
+    out[1] = h->n_cells;
+  }
+  if (max_ratio) *max_ratio = h->dten.p ? h->dten_ratio : 1.0;
+  return GLIMS_OK;
 }
 
 int glims_set_options(glims_ctx* h, const glims_options* opt) {

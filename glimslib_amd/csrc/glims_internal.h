@@ -649,6 +649,9 @@ struct glims_ctx {
   dvec<int32_t> cell_new2old;              // internal cell index -> caller's (device-side symbolic phase: cells sorted by first owner; empty = identity)
   dvec<double> egeo;                       // per cell: |T|, grad(lambda_a) [nv][dim]
   dvec<double> evol;                       // per cell: |T| once more, compact (the per-incidence weights read 8 B, not a 104-B record)
+  dvec<double> dten;                       // per cell, INTERNAL cell order: the packed diffusion tensor (diffusion_tensor.h), dim (dim + 1) / 2
+                                           // doubles; empty = none (the isotropic kernels).  glims_set_diffusion_tensor
+  double dten_ratio = 1.0;                 // largest lambda_max / lambda_min over the cells of dten
   dvec<double> mat;                        // [5][GL_MAX_LABELS]: D, rho, gamma, mu, lambda
   std::vector<double> mat_host;            // host copy of mat, then E [GL_MAX_LABELS] and nu [GL_MAX_LABELS] (adjoint E / nu)
   bool have_materials = false, is_setup = false, have_mech = false, have_state = false;

@@ -7,6 +7,7 @@
 // private LDS column acc[slot*64 + lane] (bank = lane -> conflict-free for any slot), so the segmented scatter-add
 // of FEM assembly needs neither atomics nor colouring and is bitwise reproducible.
 #include "glims_internal.h"
+#include "diffusion_tensor.h"
 #include "record_words.h"
 #include "value_codes.h"
 #include "sweep_instances.h"
@@ -232,12 +233,17 @@ struct PlaneOut {
   double* out[3];
   int stride[3], off[3];
 };
-template <int D, int NP>
+// ANISO (MODE_M alone): the S plane's stiffness term is dt D_t |T| grad phi_i^T TT_T grad phi_m with the cell's tensor
+// dten[e] (diffusion_tensor.h, internal cell order), read once per incidence; M, K_el and G do not see it.  ANISO = 0 is the
+// kernel as it was: DT is empty there (the signature and the kernel-argument layout of before), one `const double*` with ANISO.
+template <int D, int NP, int ANISO = 0, class... DT>
 __global__ __launch_bounds__(GL_WAVE) void k_assemble_static(
     int mode, int ca, int64_t n_own, const int64_t* __restrict__ slice_ptr,
     const int64_t* __restrict__ cslice_ptr, const uint32_t* __restrict__ cslots,
     const int32_t* __restrict__ celem, const uint8_t* __restrict__ diag_k, const double* __restrict__ egeo,
-    const uint8_t* __restrict__ label, const double* __restrict__ mat, double dt, const PlaneOut po, int max_len) {
+    const uint8_t* __restrict__ label, const double* __restrict__ mat, double dt, const PlaneOut po, int max_len,
+    DT... dten) {
+  static_assert(sizeof...(DT) == (ANISO ? 1 : 0), "the tensor field is passed with ANISO alone");
   constexpr int NV = D + 1, GE = 1 + NV * D;
   constexpr double mfac = 1.0 / ((D + 1) * (D + 2));
   extern __shared__ double acc[];   // [NP][max_len][64]
@@ -267,6 +273,8 @@ __global__ __launch_bounds__(GL_WAVE) void k_assemble_static(
     double gi[D];
 #pragma unroll
     for (int a = 0; a < D; ++a) gi[a] = g[1 + li * D + a];
+    double tgi[D];   // TT_T grad phi_i (ANISO)
+    if constexpr (ANISO != 0) glims_dt_apply<D>(glims_dt_field(dten...) + (int64_t)e * glims_dt_size<D>(), gi, tgi);
     const double Dc = mat[0 * GL_MAX_LABELS + lab], rho = mat[1 * GL_MAX_LABELS + lab],
                  gam = mat[2 * GL_MAX_LABELS + lab], mu = mat[3 * GL_MAX_LABELS + lab],
                  lam = mat[4 * GL_MAX_LABELS + lab];
@@ -278,6 +286,11 @@ __global__ __launch_bounds__(GL_WAVE) void k_assemble_static(
       for (int a = 0; a < D; ++a) {
         gm[a] = g[1 + m * D + a];
         gg += gi[a] * gm[a];
+      }
+      if constexpr (ANISO != 0) {
+        gg = 0.0;
+#pragma unroll
+        for (int a = 0; a < D; ++a) gg += gm[a] * tgi[a];
       }
 #pragma unroll
       for (int pl = 0; pl < NP; ++pl) {
@@ -1803,14 +1816,21 @@ __global__ void k_to_float(int64_t n, const double* __restrict__ a, float* __res
   if (i < n) b[i] = (float)a[i];
 }
 
-template <int D, int NP>
+template <int D, int NP, int ANISO = 0>
 static void assemble_planes(glims_ctx* h, int mode, int ca, const PlaneOut& po) {
   const DevPattern& p = h->pat;
   const size_t lds = (size_t)NP * p.max_len * GL_WAVE * sizeof(double);
-  set_lds(k_assemble_static<D, NP>, lds);
-  hipLaunchKernelGGL((k_assemble_static<D, NP>), dim3(p.n_slices), dim3(GL_WAVE), lds, h->st, mode, ca, h->n_own,
-                     p.slice_ptr.p, p.cslice_ptr.p, p.cslots.p, p.celem.p, p.diag_k.p, h->egeo.p, h->label.p,
-                     h->mat.p, h->opt.dt, po, p.max_len);
+  if constexpr (ANISO != 0) {
+    set_lds(k_assemble_static<D, NP, 1, const double*>, lds);
+    hipLaunchKernelGGL((k_assemble_static<D, NP, 1, const double*>), dim3(p.n_slices), dim3(GL_WAVE), lds, h->st, mode, ca,
+                       h->n_own, p.slice_ptr.p, p.cslice_ptr.p, p.cslots.p, p.celem.p, p.diag_k.p, h->egeo.p, h->label.p,
+                       h->mat.p, h->opt.dt, po, p.max_len, (const double*)h->dten.p);
+  } else {
+    set_lds(k_assemble_static<D, NP>, lds);
+    hipLaunchKernelGGL((k_assemble_static<D, NP>), dim3(p.n_slices), dim3(GL_WAVE), lds, h->st, mode, ca, h->n_own,
+                       p.slice_ptr.p, p.cslice_ptr.p, p.cslots.p, p.celem.p, p.diag_k.p, h->egeo.p, h->label.p,
+                       h->mat.p, h->opt.dt, po, p.max_len);
+  }
   GL_HIP(hipGetLastError());
 }
 
@@ -1821,7 +1841,9 @@ static void assemble_static_t(glims_ctx* h, int with_mechanics) {
   h->vM.alloc(ne);
   h->vS.alloc(ne);
   h->vA.alloc(ne);
-  assemble_planes<D, 2>(h, MODE_M, 0, PlaneOut{{h->vM.p, h->vS.p, nullptr}, {1, 1, 0}, {0, 0, 0}});
+  // (with a diffusion-tensor field the S plane takes the cells' tensors; without one, the instance of before)
+  if (h->dten.p) assemble_planes<D, 2, 1>(h, MODE_M, 0, PlaneOut{{h->vM.p, h->vS.p, nullptr}, {1, 1, 0}, {0, 0, 0}});
+  else assemble_planes<D, 2>(h, MODE_M, 0, PlaneOut{{h->vM.p, h->vS.p, nullptr}, {1, 1, 0}, {0, 0, 0}});
   GL_HIP(hipMemcpyAsync(h->vA.p, h->vS.p, ne * sizeof(double), hipMemcpyDeviceToDevice, h->st));
   if (h->jac32) {
     h->vA32.alloc(ne);

@@ -288,6 +288,7 @@ class DistributedHandle:
         self.dist, self.rank, self.world = dist, rank, world
         self.n_global = len(points)
         self.dim = np.asarray(points).shape[1]
+        self.n_cells_global = len(cells)
         self.part = partition_mesh(points, cells, world, rank)
         p = self.part
         self.h = _backend.Handle(p.points, p.cells, np.asarray(cell_label)[p.cell_ids], n_own=p.n_own, device=device)
@@ -309,6 +310,18 @@ class DistributedHandle:
     # -- pass-through -----------------------------------------------------------------------------------------
     def set_materials(self, *a):
         self.h.set_materials(*a)
+
+    def set_diffusion_tensor(self, T):
+        """``Handle.set_diffusion_tensor`` with the field in the GLOBAL cell order (or one [d, d] matrix, or None): every rank
+        keeps the tensors of its own cells.  Rank-local, no communication."""
+        if T is None:
+            self.h.set_diffusion_tensor(None)
+            return
+        T = _backend.pack_diffusion_tensor(T, self.n_cells_global, self.dim)
+        self.h.set_diffusion_tensor(T[self.part.cell_ids])
+
+    def diffusion_tensor_info(self):
+        return self.h.diffusion_tensor_info()
 
     def set_options(self, **kw):
         self.h.set_options(**kw)

@@ -166,6 +166,38 @@ class TumorGrowth(FenicsSimulation):
         self.required_params = ['diffusion', 'coupling', 'proliferation', 'E', 'poisson']
         self.optional_params = []
 
+    # -- anisotropic diffusion ----------------------------------------------------------------------------------
+    def setup_model_parameters(self, iv_expression, diffusion_tensor=None, **kwargs):
+        """As the base class; ``diffusion_tensor`` (extension): see ``set_diffusion_tensor``."""
+        super().setup_model_parameters(iv_expression, **kwargs)
+        self.set_diffusion_tensor(diffusion_tensor)
+
+    def set_diffusion_tensor(self, T):
+        """A per-cell diffusion tensor (extension; the reference's flux is D grad c): the flux of a cell of tissue t becomes
+        D_t * T_cell grad c with the tissue's scalar `diffusion` D_t -- still the control of every gradient and Hessian -- and a
+        dimensionless symmetric positive-definite tensor per cell, fixed during a fit.  Takes effect with the next run.
+
+        T: an array [n_cells, d, d]; the packed [n_cells, d (d + 1) / 2] upper triangles row by row (the ITK order); ONE
+        [d, d] matrix for every cell; a callable of the cell centroids [n_cells, d] returning one of these; a tensor ``Image``
+        with d (d + 1) / 2 components, sampled nearest-voxel at the centroids (cells outside the image or on a NaN voxel get
+        the identity, their number is warned about once); None = isotropic.  ``data_io.tensor_from_fibres`` builds the tensors
+        of a fibre field.  A non-symmetric or wrongly shaped T raises ValueError here; a tensor that is not positive definite
+        is refused by the library when the run sets the problem up."""
+        from ..utils import data_io
+        d = self.geometric_dimension
+        nc = len(self.mesh.cells)
+        if T is None:
+            self._diffusion_tensor = None
+            return
+        if isinstance(T, data_io.Image):
+            T, n_out = data_io.tensor_image_at_points(T, self.mesh.cell_midpoints())
+            if n_out:
+                self.logger.warning("diffusion tensor image: %d of %d cells lie outside the image or on a NaN voxel and get "
+                                    "the identity" % (n_out, nc))
+        elif callable(T):
+            T = T(self.mesh.cell_midpoints())
+        self._diffusion_tensor = _backend.pack_diffusion_tensor(T, nc, d)
+
     # -- coefficient tables -----------------------------------------------------------------------------------
     def _labels(self):
         return np.asarray(self.subdomains.subdomains.array(), dtype=np.int32)
@@ -274,6 +306,7 @@ class TumorGrowth(FenicsSimulation):
         h = self._backend
         t = self._material_tables(n_labels)
         h.set_materials(t['D'], t['rho'], t['gamma'], t['E'], t['nu'])
+        h.set_diffusion_tensor(getattr(self, '_diffusion_tensor', None))
         opts = {k: v for k, v in self.solver_options.items() if k != 'mechanics'}
         h.set_options(dt=float(self.params.sim_time_step), **opts)
         self._upload_loads_and_bcs(h)

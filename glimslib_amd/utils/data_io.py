@@ -256,6 +256,43 @@ def sample_image_at_points(image, points, order='nearest'):
     return a[tuple(ijk[:, k] for k in reversed(range(d)))]
 
 
+def tensor_from_fibres(directions, ratio, normalise=True):
+    """Diffusion tensors T = I + (ratio - 1) e e^T from fibre directions e ([n, d], normalised here; a zero direction gives
+    the identity): diffusion along the fibre is `ratio` (a number or [n]) times the diffusion across it.  normalise: scaled to
+    trace d, so that the mean diffusivity is the tissue's scalar D.  Returns [n, d, d], what
+    ``sim.set_diffusion_tensor`` / ``Handle.set_diffusion_tensor`` take."""
+    e = np.atleast_2d(np.asarray(directions, dtype=np.float64))
+    n, d = e.shape
+    r = np.broadcast_to(np.asarray(ratio, dtype=np.float64), (n,))
+    if not np.all(r > 0.0):
+        raise ValueError("tensor_from_fibres: the ratio must be positive")
+    norm = np.linalg.norm(e, axis=1)
+    e = np.where(norm[:, None] > 0.0, e / np.where(norm > 0.0, norm, 1.0)[:, None], 0.0)
+    T = np.eye(d)[None] + (r - 1.0)[:, None, None] * e[:, :, None] * e[:, None, :]
+    if normalise:
+        T = T * (d / np.trace(T, axis1=1, axis2=2))[:, None, None]
+    return T
+
+
+def tensor_image_at_points(image, points):
+    """A tensor ``Image`` (d (d + 1) / 2 components per voxel, the upper triangle row by row: the ITK order) sampled
+    nearest-voxel at physical points.  Returns (packed [n, d (d + 1) / 2], number of points replaced by the identity): points
+    outside the image and voxels with a NaN component become the identity."""
+    pts = np.asarray(points, dtype=np.float64)
+    d = pts.shape[1]
+    nt = d * (d + 1) // 2
+    if not image.is_vector or image.dim != d or image.GetNumberOfComponentsPerPixel() != nt:
+        raise ValueError("a %d-D tensor image with %d components per voxel is needed" % (d, nt))
+    img = dict(array=image.array, origin=image.origin, spacing=image.spacing)
+    T = np.array(sample_image_at_points(img, pts), dtype=np.float64)
+    ijk = np.rint((pts - np.asarray(image.origin)) / np.asarray(image.spacing)).astype(np.int64)
+    size = np.asarray(image.GetSize())
+    out = np.any((ijk < 0) | (ijk >= size[None]), axis=1) | np.isnan(T).any(axis=1)
+    iu = np.triu_indices(d)
+    T[out] = np.eye(d)[iu[0], iu[1]]
+    return T, int(out.sum())
+
+
 # ---- functions <-> images (data_io.py:101-227, 363-411) ------------------------------------------------------------------
 class Image:
     """What the reference passes around as a SimpleITK image, reduced to the parts its converters touch: a voxel array

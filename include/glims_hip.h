@@ -1166,6 +1166,36 @@ int glims_adjoint_displacement_image_terms(glims_ctx* h, int n, const glims_disp
 /* out = (sampler id, number of points, number of observed points) of stored term k */
 int glims_adjoint_displacement_image_info(glims_ctx* h, int k, int64_t out[3]);
 
+/* ---- anisotropic diffusion: a per-cell tensor ("Anisotropic diffusion") ---------------------- */
+
+/* The flux of cell T with label t becomes D_t * TT_T grad c: D_t is still the per-tissue scalar of glims_set_materials
+ * (and still the control of every gradient and Hessian), TT_T a dimensionless symmetric positive-definite dim x dim tensor
+ * per cell, fixed during a fit.  T[n_cells][dim (dim + 1) / 2] in the CALLER's cell order, each tensor packed as its upper
+ * triangle row by row (the ITK order): (xx, xy, yy) in 2-D, (xx, xy, xz, yy, yz, zz) in 3-D.  NULL clears the field: TT = I,
+ * the isotropic kernels, the bits of a handle that never had one.
+ *
+ * The contract of glims_set_materials: the field is copied to the device (8 dim (dim + 1) / 2 bytes per cell, stored in the
+ * internal cell order) and takes effect with the next glims_setup; the call forgets the mechanics operator and the derive
+ * displacement, marks both multigrid hierarchies not ready, invalidates an adjoint recording and requires a new glims_setup.
+ * What changes is the static operator S = M - dt M_rho + dt K with K_ij = sum_T D_t |T| grad phi_i^T TT_T grad phi_j, and
+ * the gradient forms of the sensitivity passes (dJ/dD_t = -dt sum_{T in t} |T| grad lambda^T TT_T grad c, and the three forms
+ * of the second order).  The time stepper, its solvers and fast paths read S alone and run the code they run without a field;
+ * rho, gamma, E, nu, mechanics, every misfit term, the samplers, derive and observe do not see the tensor.
+ *
+ * A device pass validates the field: every entry finite and the leading principal minors > 0.  Otherwise GLIMS_E_USAGE, the
+ * message naming the number of bad cells and the smallest caller's index among them, and the previous field (or none) stays
+ * in place with the handle as it was.  On a partitioned handle the call is rank-local (the cells are the rank's cells) and
+ * communicates nothing.
+ *
+ * Not built: tensor entries or an anisotropy ratio as controls, tensors that vary in time, anisotropic mechanics.  P1
+ * elements with a strongly anisotropic tensor lose the discrete maximum principle (small negative concentrations are
+ * possible); a Neumann load on the concentration (glims_set_rd_load) is passed as it is -- the natural condition
+ * is on the tensor flux D_t TT grad c . n. */
+int glims_set_diffusion_tensor(glims_ctx* h, const double* T);
+/* out[0] = 1 if a field is set, else 0; out[1] = n_cells; *max_ratio = the largest lambda_max / lambda_min over the cells
+ * (1 without a field).  Either pointer may be NULL. */
+int glims_diffusion_tensor_info(const glims_ctx* h, int64_t out[2], double* max_ratio);
+
 /* ---- single-node multi-GPU (one process per GPU, RCCL over xGMI) ------------------------------------- */
 
 #define GLIMS_UNIQUE_ID_BYTES 256   /* two RCCL unique ids: halo communicator + reduction communicator */
