@@ -184,6 +184,8 @@ SIGNATURES = {
     "glims_set_materials": (C.c_int, [_h, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "glims_set_diffusion_tensor": (C.c_int, [_h, _dp]),
     "glims_diffusion_tensor_info": (C.c_int, [_h, _i64p, _dp]),
+    "glims_set_diffusion_tensor_tangents": (C.c_int, [_h, C.c_int, _dp]),
+    "glims_adjoint_tensor_gradient": (C.c_int, [_h, C.c_int, C.c_int, _dp]),
     "glims_options_default": (C.c_int, [C.POINTER(Options)]),
     "glims_set_options": (C.c_int, [_h, C.POINTER(Options)]),
     "glims_set_dirichlet_u": (C.c_int, [_h, C.c_int64, _i64p, _dp]),
@@ -316,6 +318,22 @@ def pack_diffusion_tensor(T, n_cells, dim):
                      % (T.shape, n_cells, dim, dim, n_cells, nt, dim, dim))
 
 
+DT_MAX_TANGENTS = 4   # GLIMS_DT_MAX_TANGENTS
+
+
+def pack_diffusion_tensor_tangents(dT, n_cells, dim):
+    """The packed tangent fields [K, n_cells, d (d + 1) / 2] of dT given as [K, n_cells, d, d], as the packed array itself, or
+    as a list of K fields in any form ``pack_diffusion_tensor`` takes (its ValueErrors: shape, a full matrix that is not
+    symmetric).  More than DT_MAX_TANGENTS fields go on to the library's refusal."""
+    if isinstance(dT, np.ndarray) and dT.ndim in (3, 4):
+        dT = list(dT)
+    elif isinstance(dT, np.ndarray):
+        raise ValueError("diffusion tensor tangents of shape %s: need [K, %d, %d, %d], the packed [K, %d, %d] or a list of fields"
+                         % (dT.shape, n_cells, dim, dim, n_cells, dim * (dim + 1) // 2))
+    fields = [pack_diffusion_tensor(f, n_cells, dim) for f in dT]
+    return np.ascontiguousarray(np.stack(fields)) if fields else np.zeros((0, n_cells, dim * (dim + 1) // 2))
+
+
 class Handle:
     """Thin OO view of one ``glims_ctx`` (one mesh on one GPU)."""
 
@@ -339,6 +357,7 @@ class Handle:
         self.options = Options()
         lib.glims_options_default(C.byref(self.options))
         self.n_labels = None   # label count of the last successful set_materials
+        self.n_tangents = 0    # tangent fields of the last successful set_diffusion_tensor_tangents
         self._image_terms = []   # what the library's stored image terms were made from (see _sync_image_terms)
         self._deformed_terms = []   # ... and the stored deformed image terms (see _split_terms)
         self._displacement_terms = []   # ... and the stored displacement image terms
@@ -382,6 +401,30 @@ class Handle:
             return
         T = pack_diffusion_tensor(T, self.n_cells, self.dim)
         self._check(self.lib.glims_set_diffusion_tensor(self._h, _ptr(T, _dp)))
+
+    def set_diffusion_tensor_tangents(self, dT):
+        """glims_set_diffusion_tensor_tangents: K <= 4 tangent fields dT/dtheta_k of the tensor field -- [K, n_cells, d, d],
+        the packed [K, n_cells, d (d + 1) / 2], or a list of fields in any form set_diffusion_tensor takes -- in the caller's
+        cell order; None (or no field) clears them.  Symmetric, not necessarily definite.  Every backward sweep that follows
+        (adjoint_gradient, adjoint_hessian*) adds up dJ/dtheta_k per label: adjoint_tensor_gradient().  Nothing of the set-up
+        or a recording is invalidated.  A non-finite entry raises BackendError(GLIMS_E_USAGE) naming the tangent and the
+        first bad cell, more than 4 fields likewise, and the stored tangents stay."""
+        if dT is None:
+            self._check(self.lib.glims_set_diffusion_tensor_tangents(self._h, 0, None))
+            self.n_tangents = 0
+            return
+        dT = pack_diffusion_tensor_tangents(dT, self.n_cells, self.dim)
+        self._check(self.lib.glims_set_diffusion_tensor_tangents(self._h, len(dT), _ptr(dT, _dp) if len(dT) else None))
+        self.n_tangents = len(dT)
+
+    def adjoint_tensor_gradient(self):
+        """glims_adjoint_tensor_gradient: [K, n_labels], dJ/dtheta_k per label from the last completed backward sweep
+        (-dt D_t sum_steps sum_cells |T| grad lambda^T dT_k grad c).  BackendError(GLIMS_E_USAGE) when no sweep has completed
+        since the tangents were set."""
+        K, L = int(getattr(self, "n_tangents", 0)), int(self.n_labels or 0)
+        out = np.zeros((K, L))
+        self._check(self.lib.glims_adjoint_tensor_gradient(self._h, K, L, _ptr(out, _dp)))
+        return out
 
     def diffusion_tensor_info(self):
         """dict(present, n_cells, max_ratio): whether a tensor field is set and the largest lambda_max / lambda_min over its

@@ -266,6 +266,68 @@ __global__ __launch_bounds__(1024) void k_sens_final(int n_blocks, int l0, int n
   if (lane == 0 && l0 + q < n_labels && k_off + k < ls) sums[(l0 + q) * ls + k_off + k] += s;
 }
 
+// Tangent-field sensitivities (glims_set_diffusion_tensor_tangents; DESIGN.md section 17, "Tangent fields"), next to
+// k_sens<D, 0> with its grid, label windows and counting rule: per cell of label l0 + q and tangent k
+//   q_k = |T| grad lambda^T (dTT_T / dtheta_k) grad c,     acc[q][k] += q_k
+// The geometry record and the vertex ids are read once, grad lambda and grad c formed once, the K forms taken through
+// glims_dt_form (a tangent need not be definite: the form does not care).  dtan: [K][n_cells][NT] planes, internal cell order.
+// Per-block partials [block][LT][K] in the fixed order of block_partials; no atomics.  Bytes per cell: the geometry record
+// (56 / 104 B), NV x 4 B of vertex ids, 1 B of label, 8 K d (d + 1) / 2 B of tangents (3-D: 104 + 16 + 1 + 48 K).
+template <int D, int K>
+__global__ __launch_bounds__(256) void k_sens_tangent(int64_t n_cells, int l0, const int32_t* __restrict__ cell_nodes,
+                                                      const double* __restrict__ egeo, const uint8_t* __restrict__ label,
+                                                      const double* __restrict__ c, const double* __restrict__ v,
+                                                      const uint8_t* __restrict__ counted, const double* __restrict__ dtan,
+                                                      double* __restrict__ partials) {
+  constexpr int NV = D + 1, GE = 1 + NV * D, NT = glims_dt_size<D>();
+  double acc[GL_ADJ_LT * K];   // flat: [q][k] at q * K + k
+#pragma unroll
+  for (int j = 0; j < GL_ADJ_LT * K; ++j) acc[j] = 0.0;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n_cells; e += stride) {
+    const int j = (int)label[e] - l0;
+    if (j < 0 || j >= GL_ADJ_LT || (counted && !counted[e])) continue;
+    const double* g = egeo + e * GE;
+    const double vol = g[0];
+    double gc[D] = {0.0}, gl[D] = {0.0};
+#pragma unroll
+    for (int m = 0; m < NV; ++m) {
+      const int nd = cell_nodes[e * NV + m];
+      const double cm = c[nd], lm = v[nd];
+#pragma unroll
+      for (int a = 0; a < D; ++a) {
+        gc[a] += cm * g[1 + m * D + a];
+        gl[a] += lm * g[1 + m * D + a];
+      }
+    }
+    double a[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) a[k] = vol * glims_dt_form<D>(dtan + ((int64_t)k * n_cells + e) * NT, gl, gc);
+#pragma unroll
+    for (int q = 0; q < GL_ADJ_LT; ++q)
+      if (q == j) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) acc[q * K + k] += a[k];
+      }
+  }
+  block_partials(acc, partials);
+}
+
+// second stage of k_sens_tangent, the order of k_sens_final: one wave per sum (16 waves take the LT x K <= 32 sums in turn),
+// lane l adds blocks l, l + 64, ... in order, then the wave's butterfly.  sums[k][GL_MAX_LABELS] += the partials of label l0 + q.
+template <int K>
+__global__ __launch_bounds__(1024) void k_sens_tangent_final(int n_blocks, int l0, int n_labels,
+                                                             const double* __restrict__ partials, double* __restrict__ sums) {
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (int t = w; t < GL_ADJ_LT * K; t += 16) {
+    double s = 0.0;
+    for (int b = lane; b < n_blocks; b += 64) s += partials[(size_t)b * GL_ADJ_LT * K + t];
+    s = wsum(s);
+    const int q = t / K, k = t % K;
+    if (lane == 0 && l0 + q < n_labels) sums[k * GL_MAX_LABELS + l0 + q] += s;
+  }
+}
+
 // g[row] += sum over the row's incidences of qcell[cell]  (G^T mu, atomics-free through the row-owned lists)
 __global__ void k_gt_rows(int64_t n_own, const int64_t* __restrict__ cslice_ptr, const int32_t* __restrict__ celem,
                           const double* __restrict__ qcell, double* __restrict__ g) {
@@ -482,6 +544,68 @@ void sens_pass(glims_ctx* h, int mode, const double* mat, const double* c, const
   }
 }
 
+// k_sens_tangent<D, K> over the labels with the stored tangent fields, each launch followed by its second stage into the
+// handle's sums; the grid and the label windows of sens_pass.  Nothing stored: no launch.
+template <int D, int K>
+void tangent_pass_k(glims_ctx* h, const double* c, const double* v, const uint8_t* counted) {
+  const int nb = sens_blocks(h);
+  GlTensorTangents& t = h->dtan;
+  for (int l0 = 0; l0 < h->n_labels; l0 += GL_ADJ_LT) {
+    hipLaunchKernelGGL((k_sens_tangent<D, K>), dim3(nb), dim3(256), 0, h->st, h->n_cells, l0, h->adj.cell_nodes.p, h->egeo.p,
+                       h->label.p, c, v, counted, (const double*)t.planes.p, t.part.p);
+    GL_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_sens_tangent_final<K>, dim3(1), dim3(1024), 0, h->st, nb, l0, h->n_labels, t.part.p, t.sums.p);
+    GL_CHECK_LAUNCH();
+  }
+}
+template <int D>
+void tangent_pass(glims_ctx* h, const double* c, const double* v, const uint8_t* counted) {
+  switch (h->dtan.K) {
+    case 0: return;
+    case 1: return tangent_pass_k<D, 1>(h, c, v, counted);
+    case 2: return tangent_pass_k<D, 2>(h, c, v, counted);
+    case 3: return tangent_pass_k<D, 3>(h, c, v, counted);
+    case 4: return tangent_pass_k<D, 4>(h, c, v, counted);
+    default: throw std::logic_error("adjoint: more tangent fields than k_sens_tangent has instances for");
+  }
+}
+static_assert(GLIMS_DT_MAX_TANGENTS == 4, "tangent_pass lists the instances of k_sens_tangent");
+
+// The tangent sums of a sweep into the handle's host copy: the rows of the ranks gathered as gather_label_sums does (zeros
+// outside the own row, one all-reduce, added in rank order: the same bits on every rank), from the handle's own buffers;
+// out[k][t] = -dt D_t sums[k][t].  Reached by every rank, also after a failed solve (`status` then keeps the getter closed).
+void finish_tangent_sums(glims_ctx* h, int status) {
+  GlTensorTangents& t = h->dtan;
+  if (t.K == 0) return;
+  const int K = t.K, L = h->n_labels;
+  const size_t W = (size_t)K * L;
+  std::vector<double> sum(W);
+  if (h->world <= 1) {
+    for (int k = 0; k < K; ++k)
+      GL_HIP(hipMemcpyAsync(sum.data() + (size_t)k * L, t.sums.p + (size_t)k * GL_MAX_LABELS, L * sizeof(double),
+                            hipMemcpyDeviceToHost, h->st));
+    GL_HIP(hipStreamSynchronize(h->st));
+  } else {
+    t.gather.alloc((size_t)h->world * K * GL_MAX_LABELS);   // (the set call's size: allocates only if the transport came later)
+    GL_HIP(hipMemsetAsync(t.gather.p, 0, W * h->world * sizeof(double), h->st));
+    for (int k = 0; k < K; ++k)
+      GL_HIP(hipMemcpyAsync(t.gather.p + W * h->rank + (size_t)k * L, t.sums.p + (size_t)k * GL_MAX_LABELS, L * sizeof(double),
+                            hipMemcpyDeviceToDevice, h->st));
+    gl_allreduce_bulk(h, t.gather.p, W * h->world);
+    std::vector<double> rows(W * h->world);
+    GL_HIP(hipMemcpyAsync(rows.data(), t.gather.p, rows.size() * sizeof(double), hipMemcpyDeviceToHost, h->st));
+    GL_HIP(hipStreamSynchronize(h->st));
+    add_rows_in_rank_order(h->world, W, rows.data(), sum.data());
+  }
+  const double dt = h->opt.dt;
+  t.grad.assign(W, 0.0);
+  for (int k = 0; k < K; ++k)
+    for (int l = 0; l < L; ++l) t.grad[(size_t)k * L + l] = -dt * h->mat_host[l] * sum[(size_t)k * L + l];
+  t.grad_labels = L;
+  t.have = status == GLIMS_OK;
+  if (!t.have) t.why = "the last backward sweep stopped with status " + std::to_string(status);
+}
+
 // A host vector [n_nodes][bs] in the caller's numbering into dst in the internal numbering, and a scalar device vector back
 // out, both through the staging buffer and synchronised (the buffer is free again on return)
 void upload_permuted(glims_ctx* h, AdjWork& wk, const double* host, int bs, double* dst) {
@@ -641,6 +765,11 @@ struct BackwardSweep {
     rd_mg = h->rd_precond_active == GLIMS_RD_PRECOND_MULTIGRID;
     if (rd_mg && !h->mg_rd.ready) gl_mg_setup_rd(h);
     rd_deg = h->opt.rd_mg_smooth > 0 ? h->opt.rd_mg_smooth : (h->mg_rd.lattice ? 1 : 3);
+    if (h->dtan.K > 0) {   // stored tangent fields: their sums start at 0 and are this sweep's once it completes
+      h->dtan.have = false;
+      h->dtan.why = "the last backward sweep did not complete";
+      GL_HIP(hipMemsetAsync(h->dtan.sums.p, 0, h->dtan.sums.n * sizeof(double), h->st));
+    }
   }
   int last_step() const { return (int)h->adj.traj.size() - 1; }
 
@@ -648,6 +777,7 @@ struct BackwardSweep {
   void sens(int mode, const double* c, const double* v) {
     sens_pass<D>(h, mode, h->mat.p, c, v, h->world > 1 ? h->adj.counted.p : nullptr, wk.qcell.p, wk.part.p,
                  mode < 2 ? wk.sums.p : wk.esums.p, mode < 2 ? 3 : 2, mode == 1 ? 2 : 0);
+    if (mode == 0) tangent_pass<D>(h, c, v, h->world > 1 ? h->adj.counted.p : nullptr);   // (no launch without tangents)
   }
 
   // c_n with current ghosts, g = 0
@@ -875,6 +1005,7 @@ int gradient_t(glims_ctx* h, int n_terms, const glims_misfit* terms, double* J_o
                     hess_buffer(table, "gather").count);
   sw.write_labels(sums.data(), dD, drho, dgamma);
   if (elastic) write_elastic_labels(h->mat_host.data(), h->n_labels, D, sums.data(), esums.data(), dE, dnu);
+  finish_tangent_sums(h, status);
   *J_out = sw.J;
   a.gradients++;
   a.ms_backward += 1e3 * (omp_get_wtime() - t0);
@@ -1952,6 +2083,7 @@ struct HessianSweep {
     if (call.el) write_elastic_labels(h->mat_host.data(), L, D, sums.data(), esums.data(), el.dE, el.dnu);
     hessian_label_rows(dirs, call.el != nullptr, dt, h->mat_host.data(), sums.data(), hs.data(), esums.data(), hes.data(),
                        call.hv_D, call.hv_rho, call.hv_gamma, el.hv_E, el.hv_nu);
+    finish_tangent_sums(h, sw.status);
   }
 };
 
@@ -2113,13 +2245,14 @@ int gl_adjoint_gradient(glims_ctx* h, int n_terms, const glims_misfit* terms, do
     }
     // (second row: whether the rank asks for dJ/dE or dJ/dnu -- the size of the final all-reduce follows it; third and fourth:
     // the stored image terms, their count and a checksum of their steps -- the all-reduces of the sweep follow them)
-    std::vector<double> flag((size_t)h->world * 4, 0.0);
+    std::vector<double> flag((size_t)h->world * 5, 0.0);
     flag[(size_t)h->rank] = why.empty() ? 0.0 : 1.0;
     flag[(size_t)(h->world + h->rank)] = (dE || dnu) ? 1.0 : 0.0;
     uint64_t sum_steps = 0;
     for (const GlImageTerm* t : h->img_terms) sum_steps = (sum_steps * 1000003ull + (uint64_t)t->step + 1) & ((1ull << 52) - 1);
     flag[(size_t)(2 * h->world + h->rank)] = (double)h->img_terms.size();
     flag[(size_t)(3 * h->world + h->rank)] = (double)sum_steps;
+    flag[(size_t)(4 * h->world + h->rank)] = (double)h->dtan.K;   // fifth: the stored tangent fields -- their gather follows the sweep
     dvec<double> d_flag;
     d_flag.upload(flag, h->st);
     gl_allreduce_bulk(h, d_flag.p, flag.size());
@@ -2139,6 +2272,10 @@ int gl_adjoint_gradient(glims_ctx* h, int n_terms, const glims_misfit* terms, do
           flag[(size_t)(3 * h->world + r)] != flag[(size_t)(3 * h->world)])
         throw glims_error(GLIMS_E_USAGE, "glims_adjoint_gradient: the ranks disagree on the stored image terms (their count "
                                          "or the steps they observe)");
+    for (int r = 1; r < h->world; ++r)
+      if (flag[(size_t)(4 * h->world + r)] != flag[(size_t)(4 * h->world)])
+        throw glims_error(GLIMS_E_USAGE, "glims_adjoint_gradient: the ranks disagree on the number of stored tangent fields "
+                                         "(glims_set_diffusion_tensor_tangents)");
   }
   return h->dim == 2 ? gradient_t<2>(h, n_terms, terms, J, dD, drho, dgamma, dc0, dE, dnu)
                      : gradient_t<3>(h, n_terms, terms, J, dD, drho, dgamma, dc0, dE, dnu);
@@ -2198,7 +2335,7 @@ int gl_adjoint_hessian_spmd(glims_ctx* h, int n_terms, const glims_misfit* terms
                               hv_rho, hv_gamma, hv_c0, stats);
   // Collective, as the partitioned gl_adjoint_gradient: every rank's verdict on its arguments and trajectory, its n_dir, the
   // NULL pattern of its direction arrays, its stored image terms and its memory verdict go through ONE all-reduce
-  // ([6][world], zeros outside the own column) before any other collective; every rank returns the same status.
+  // ([7][world], the last row the number of stored tangent fields; zeros outside the own column) before any other collective; every rank returns the same status.
   const std::string who = "glims_adjoint_hessian_spmd";
   std::string why, why_mem;
   try {
@@ -2212,7 +2349,7 @@ int gl_adjoint_hessian_spmd(glims_ctx* h, int n_terms, const glims_misfit* terms
                          hv_gamma, hv_c0, stats, true};
   const bool fits = !why.empty() || hessian_fits(hessian_shape(h, call), &why_mem);
   const size_t w = (size_t)h->world, r0 = (size_t)h->rank;
-  std::vector<double> flag(w * 6, 0.0);
+  std::vector<double> flag(w * 7, 0.0);
   uint64_t sum_steps = 0;
   for (const GlImageTerm* t : h->img_terms) sum_steps = (sum_steps * 1000003ull + (uint64_t)t->step + 1) & ((1ull << 52) - 1);
   flag[r0] = why.empty() ? 0.0 : 1.0;
@@ -2221,6 +2358,7 @@ int gl_adjoint_hessian_spmd(glims_ctx* h, int n_terms, const glims_misfit* terms
   flag[3 * w + r0] = (double)h->img_terms.size();
   flag[4 * w + r0] = (double)sum_steps;
   flag[5 * w + r0] = fits ? 0.0 : 1.0;
+  flag[6 * w + r0] = (double)h->dtan.K;
   dvec<double> d_flag;
   d_flag.upload(flag, h->st);
   gl_allreduce_bulk(h, d_flag.p, flag.size());
@@ -2246,6 +2384,9 @@ int gl_adjoint_hessian_spmd(glims_ctx* h, int n_terms, const glims_misfit* terms
   if (differs(3) || differs(4))
     throw glims_error(GLIMS_E_USAGE, who + ": the ranks disagree on the stored image terms (their count or the steps they "
                                          "observe)");
+  if (differs(6))
+    throw glims_error(GLIMS_E_USAGE, who + ": the ranks disagree on the number of stored tangent fields "
+                                           "(glims_set_diffusion_tensor_tangents)");
   const std::string short_mem = ranks_with(5);
   if (!fits) throw glims_error(GLIMS_E_HIP, why_mem + " (ranks short of memory: " + short_mem + ")");
   if (!short_mem.empty()) throw glims_error(GLIMS_E_HIP, who + ": rank(s) " + short_mem + " are short of device memory");

@@ -1,6 +1,7 @@
 // extern "C" surface of libglimship.so (see include/glims_hip.h for the contract of every entry point).
 #include "glims_internal.h"
 #include "diffusion_tensor.h"
+#include "hessian_plan.h"
 
 #include <cerrno>
 #include <cmath>
@@ -109,6 +110,30 @@ __global__ __launch_bounds__(256) void k_dten_store(int64_t n_cells, const doubl
     __syncthreads();
   }
   if (threadIdx.x == 0) ratio[blockIdx.x] = sm[0];
+}
+
+// glims_set_diffusion_tensor_tangents: K tangent fields of the caller into the internal cell order, plane after plane
+// ([K][n_cells][NT]), checked on the way.  bad[2 k] counts the cells of tangent k with an entry that is not finite, bad[2 k + 1]
+// is the smallest caller's index among them.  A sibling of k_dten_store: no definiteness test, no ratio.
+template <int D>
+__global__ __launch_bounds__(256) void k_dtan_store(int64_t n_cells, int K, const double* __restrict__ src,
+                                                    const int32_t* __restrict__ cell_new2old, double* __restrict__ dst,
+                                                    unsigned long long* __restrict__ bad) {
+  constexpr int NT = glims_dt_size<D>();
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n_cells) return;
+  const int64_t old = cell_new2old ? (int64_t)cell_new2old[e] : e;
+  for (int k = 0; k < K; ++k) {
+    double T[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) T[j] = src[((int64_t)k * n_cells + old) * NT + j];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) dst[((int64_t)k * n_cells + e) * NT + j] = T[j];
+    if (!glims_dt_finite<D>(T)) {
+      atomicAdd(bad + 2 * k, 1ull);
+      atomicMin(bad + 2 * k + 1, (unsigned long long)old);
+    }
+  }
 }
 
 template <class F>
@@ -466,6 +491,79 @@ int glims_diffusion_tensor_info(const glims_ctx* h, int64_t out[2], double* max_
   }
   if (max_ratio) *max_ratio = h->dten.p ? h->dten_ratio : 1.0;
   return GLIMS_OK;
+}
+
+int glims_set_diffusion_tensor_tangents(glims_ctx* h, int K, const double* dT) {
+  return guarded(h, [&]() {
+    GlTensorTangents& t = h->dtan;
+    GL_REQUIRE(K >= 0 && K <= GLIMS_DT_MAX_TANGENTS,
+               "glims_set_diffusion_tensor_tangents: K = " + std::to_string(K) + ", at most " +
+                   std::to_string(GLIMS_DT_MAX_TANGENTS) + " tangent fields (the stored tangents stay)");
+    // (nothing of the set-up, the prepared step or a recording depends on the tangents: only the sums of the NEXT sweep do)
+    if (K == 0 || !dT) {
+      t.K = 0;
+      t.planes.release();
+      t.part.release();
+      t.gather.release();
+      t.have = false;
+      t.why = "no tangent fields are stored";
+      return GLIMS_OK;
+    }
+    const int NT = h->dim * (h->dim + 1) / 2;
+    const int64_t nc = h->n_cells;
+    dvec<double> src, dst;
+    dvec<unsigned long long> bad;
+    std::vector<unsigned long long> res((size_t)2 * K);
+    for (int k = 0; k < K; ++k) res[2 * k] = 0ull, res[2 * k + 1] = ~0ull;
+    bad.upload(res, h->st);
+    src.upload(dT, (size_t)K * nc * NT, h->st);
+    dst.alloc((size_t)K * nc * NT);
+    if (h->dim == 2)
+      hipLaunchKernelGGL(k_dtan_store<2>, dim3(grid_of(nc)), dim3(256), 0, h->st, nc, K, src.p, h->cell_new2old.p, dst.p, bad.p);
+    else
+      hipLaunchKernelGGL(k_dtan_store<3>, dim3(grid_of(nc)), dim3(256), 0, h->st, nc, K, src.p, h->cell_new2old.p, dst.p, bad.p);
+    GL_HIP(hipGetLastError());
+    GL_HIP(hipMemcpyAsync(res.data(), bad.p, res.size() * sizeof(res[0]), hipMemcpyDeviceToHost, h->st));
+    GL_HIP(hipStreamSynchronize(h->st));
+    std::string why;
+    for (int k = 0; k < K; ++k)
+      if (res[2 * k] != 0)
+        why += (why.empty() ? "" : "; ") + std::string("tangent ") + std::to_string(k) + ": " + std::to_string(res[2 * k]) +
+               " cell(s) with an entry that is not finite, the first one is cell " + std::to_string(res[2 * k + 1]);
+    if (!why.empty())
+      throw glims_error(GLIMS_E_USAGE, "glims_set_diffusion_tensor_tangents: " + why +
+                                           " (the previously stored tangents, or none, stay in place)");
+    // the sweep's own memory, before anything of the handle changes (an allocation that fails leaves the old tangents)
+    dvec<double> part, gather;
+    part.alloc((size_t)GL_ADJ_BLOCKS * GL_ADJ_LT * K);
+    if (h->world > 1) gather.alloc((size_t)h->world * K * GL_MAX_LABELS);
+    t.sums.alloc((size_t)GLIMS_DT_MAX_TANGENTS * GL_MAX_LABELS);
+    std::swap(t.planes.p, dst.p);   // (dst now holds the previous fields and frees them)
+    std::swap(t.planes.n, dst.n);
+    std::swap(t.part.p, part.p);
+    std::swap(t.part.n, part.n);
+    std::swap(t.gather.p, gather.p);
+    std::swap(t.gather.n, gather.n);
+    t.K = K;
+    t.have = false;
+    t.why = "no backward sweep has completed since the tangent fields were set";
+    return GLIMS_OK;
+  });
+}
+
+int glims_adjoint_tensor_gradient(glims_ctx* h, int K, int n_labels, double* out) {
+  return guarded(h, [&]() {
+    const GlTensorTangents& t = h->dtan;
+    const std::string who = "glims_adjoint_tensor_gradient: ";
+    GL_REQUIRE(out, who + "null out");
+    GL_REQUIRE(t.K > 0, who + "no tangent fields are stored (glims_set_diffusion_tensor_tangents)");
+    GL_REQUIRE(K == t.K, who + "K = " + std::to_string(K) + ", " + std::to_string(t.K) + " tangent fields are stored");
+    GL_REQUIRE(t.have, who + t.why);
+    GL_REQUIRE(n_labels == t.grad_labels, who + "n_labels = " + std::to_string(n_labels) + ", the sweep had " +
+                                              std::to_string(t.grad_labels) + " labels");
+    std::memcpy(out, t.grad.data(), (size_t)K * n_labels * sizeof(double));
+    return GLIMS_OK;
+  });
 }
 
 int glims_set_options(glims_ctx* h, const glims_options* opt) {

@@ -65,6 +65,16 @@ GL_DT_HD double glims_dt_form(const double* T, const double* a, const double* b)
   return s;
 }
 
+// every entry finite: the whole test of a TANGENT field dTT/dtheta (glims_set_diffusion_tensor_tangents), which is symmetric by
+// its layout and need not be definite.  glims_dt_form takes a tangent as it takes a tensor.
+template <int D>
+GL_DT_HD bool glims_dt_finite(const double* T) {
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < glims_dt_size<D>(); ++k) ok = ok && std::isfinite(T[k]);
+  return ok;
+}
+
 // symmetric positive definite: every entry finite and the leading principal minors > 0 (Sylvester's criterion)
 template <int D>
 GL_DT_HD bool glims_dt_spd(const double* T) {

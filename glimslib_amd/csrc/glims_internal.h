@@ -483,6 +483,21 @@ struct AdjointState {
   }
 };
 
+// Tangent fields of the diffusion tensor (glims_set_diffusion_tensor_tangents; DESIGN.md section 17, "Tangent fields") and the
+// per-label sums that every backward sweep adds up for them (k_sens_tangent in adjoint.hip).  All of it is the handle's own
+// memory, allocated by the set call: no entry of an adjoint call's buffer table.
+struct GlTensorTangents {
+  int K = 0;                               // stored fields, 0 = none (no launch, no gather)
+  dvec<double> planes;                     // [K][n_cells][dim (dim + 1) / 2], INTERNAL cell order, packed as diffusion_tensor.h
+  dvec<double> part;                       // [GL_ADJ_BLOCKS][GL_ADJ_LT * K]: block partials of one launch
+  dvec<double> sums;                       // [K][GL_MAX_LABELS]: zeroed when a sweep starts, accumulated over its steps
+  dvec<double> gather;                     // partitioned handles: [world][K * n_labels], the rows of the ranks
+  std::vector<double> grad;                // [K][n_labels]: -dt D_t sums of the last completed sweep (every rank: the same bits)
+  int grad_labels = 0;
+  bool have = false;                       // grad is of a sweep that completed after the fields were set
+  std::string why = "no tangent fields are stored";   // why not (message of GLIMS_E_USAGE)
+};
+
 struct GlSampler;   // sample.hip
 
 // One stored image-space misfit term (glims_adjoint_image_terms; kernels in sample.hip).  target holds NaN at every point that
@@ -652,6 +667,7 @@ struct glims_ctx {
   dvec<double> dten;                       // per cell, INTERNAL cell order: the packed diffusion tensor (diffusion_tensor.h), dim (dim + 1) / 2
                                            // doubles; empty = none (the isotropic kernels).  glims_set_diffusion_tensor
   double dten_ratio = 1.0;                 // largest lambda_max / lambda_min over the cells of dten
+  GlTensorTangents dtan;                   // tangent fields dTT/dtheta_k and the sums of the last backward sweep
   dvec<double> mat;                        // [5][GL_MAX_LABELS]: D, rho, gamma, mu, lambda
   std::vector<double> mat_host;            // host copy of mat, then E [GL_MAX_LABELS] and nu [GL_MAX_LABELS] (adjoint E / nu)
   bool have_materials = false, is_setup = false, have_mech = false, have_state = false;

@@ -67,13 +67,28 @@ class ReducedFunctional:
     rate).  A seed is only identifiable with a centre-of-mass term (``sim.com_term``) or an image as data.  A list with a
     centre-of-mass term is first order only as well.
 
+    ``tensor_controls=('ratio',)`` appends TENSOR controls: parameters of the simulation's tensor family
+    (``sim.set_diffusion_tensor_family``; ValueError for a name the family does not have).  The control vector is the model
+    parameters, then ``iv_controls``, then the tensor controls -- vectors without them are prefixes.  dJ/dtheta_k is the sum
+    over the labels of ``sim.adjoint_gradient(...)['tensor'][name]``, from the same backward sweep as the rest.  Tensor
+    controls are first order only (``hessian`` / ``hessian_matrix`` raise NotImplementedError before any device work; use
+    L-BFGS-B) and need bounds of their own in ``minimize`` (``bounds=(lo_list, hi_list)``: a ratio is not a rate).
+
     ``terms_builder(sim, n_steps)`` returns the misfit terms (see ``Handle.adjoint_gradient``) once the forward run of m has
     taken ``n_steps`` steps.  The last m is cached: scipy's ``fun`` / ``jac`` pair for one m costs one forward and one
     backward run.
     """
 
-    def __init__(self, sim, n_params, terms_builder, run_kwargs=None, names=None, elastic_hessian=False, iv_controls=()):
+    def __init__(self, sim, n_params, terms_builder, run_kwargs=None, names=None, elastic_hessian=False, iv_controls=(),
+                 tensor_controls=()):
         self.sim = sim
+        self.tensor_controls = tuple(tensor_controls)
+        if self.tensor_controls:
+            have = tuple(getattr(sim, "tensor_params", None) or ())
+            bad = [n for n in self.tensor_controls if n not in have]
+            if bad or len(set(self.tensor_controls)) != len(self.tensor_controls):
+                raise ValueError("tensor_controls: distinct parameter names of the simulation's tensor family %s expected "
+                                 "(sim.set_diffusion_tensor_family), got %s" % (have, self.tensor_controls))
         self.iv_controls = tuple(iv_controls)
         if len(set(self.iv_controls)) != len(self.iv_controls):
             raise ValueError("iv_controls: distinct parameter names expected, got %s" % (self.iv_controls,))
@@ -133,7 +148,10 @@ class ReducedFunctional:
         return (up - dn) / (2.0 * h)
 
     def _set_params(self, m):
-        m, seed = m[:self.n_params], m[self.n_params:]
+        n_iv = self.n_params + len(self.iv_controls)
+        for name, v in zip(self.tensor_controls, m[n_iv:]):
+            self.sim.tensor_params[name] = float(v)
+        m, seed = m[:self.n_params], m[self.n_params:n_iv]
         if self.iv_controls:
             iv = self._iv_expression()
             for name, v in zip(self.iv_controls, seed):
@@ -148,8 +166,9 @@ class ReducedFunctional:
 
     def _evaluate(self, m):
         m = np.array(m, dtype=np.float64).reshape(-1)
-        if m.shape != (self.n_params + len(self.iv_controls),):
-            raise ValueError("expected %d controls, got %s" % (self.n_params + len(self.iv_controls), m.shape))
+        n_controls = self.n_params + len(self.iv_controls) + len(self.tensor_controls)
+        if m.shape != (n_controls,):
+            raise ValueError("expected %d controls, got %s" % (n_controls, m.shape))
         if self._m is not None and np.array_equal(m, self._m):
             return
         self._set_params(m)
@@ -161,6 +180,8 @@ class ReducedFunctional:
         if self.iv_controls:
             dc0 = np.asarray(g["c0"], dtype=np.float64).reshape(-1)
             self._dJ = np.concatenate([self._dJ, [float(dc0 @ self.iv_derivative(name)) for name in self.iv_controls]])
+        if self.tensor_controls:
+            self._dJ = np.concatenate([self._dJ, [float(np.sum(g["tensor"][name])) for name in self.tensor_controls]])
         self._H, self._n_steps = None, n_steps
         self.evaluations += 1
         self.history.append((m.copy(), self._J, float(np.linalg.norm(self._dJ))))
@@ -186,6 +207,9 @@ class ReducedFunctional:
     def hessian_matrix(self, m):
         """P^T H P at m: all n_params directions in one Hessian call (after the forward run of m, shared with ``__call__``
         and ``derivative``); cached with m."""
+        if self.tensor_controls:
+            raise NotImplementedError("ReducedFunctional.hessian: tensor controls %s are first order only; use a "
+                                      "first-order method (L-BFGS-B)" % (self.tensor_controls,))
         if self.iv_controls:
             raise NotImplementedError("ReducedFunctional.hessian: initial-value controls %s are first order only; use a "
                                       "first-order method (L-BFGS-B)" % (self.iv_controls,))
@@ -224,9 +248,13 @@ def minimize(rf, m0, bounds=(0.005, 0.5), method="L-BFGS-B", tol=1e-6, options=N
     every control, L-BFGS-B, tol 1e-6, gtol 1e-6; image_based_optimization.py:710-722).  method='trust-constr' also gets
     ``hessp=rf.hessian``, the second-order adjoint.  ``bounds`` is one (lo, hi) pair for every control or per-control
     ``(lo_list, hi_list)``; with ``iv_controls`` give the latter: the seed controls need bounds of their own (the box the
-    seed may lie in) -- the default rate bounds would pin a position to 0.005 .. 0.5."""
+    seed may lie in) -- the default rate bounds would pin a position to 0.005 .. 0.5.  The same holds with
+    ``tensor_controls`` (ValueError otherwise): a ratio is not a rate."""
     from scipy.optimize import minimize as _minimize
     m0 = np.asarray(m0, dtype=np.float64)
+    if getattr(rf, "tensor_controls", ()) and np.ndim(bounds[0]) == 0:
+        raise ValueError("minimize: tensor controls %s need bounds of their own, bounds=(lo_list, hi_list)"
+                         % (rf.tensor_controls,))
     opts = {"disp": False, "gtol": 1e-6}
     opts.update(options or {})
     bnds = [tuple(bounds)] * len(m0) if np.ndim(bounds[0]) == 0 else list(zip(*bounds))

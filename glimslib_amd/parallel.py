@@ -323,6 +323,23 @@ class DistributedHandle:
     def diffusion_tensor_info(self):
         return self.h.diffusion_tensor_info()
 
+    def set_diffusion_tensor_tangents(self, dT):
+        """``Handle.set_diffusion_tensor_tangents`` with the fields in the GLOBAL cell order (or None): every rank keeps the
+        tangents of its own cells.  Rank-local, no communication; every rank stores the same number of fields."""
+        if dT is None:
+            self.h.set_diffusion_tensor_tangents(None)
+            return
+        dT = _backend.pack_diffusion_tensor_tangents(dT, self.n_cells_global, self.dim)
+        self.h.set_diffusion_tensor_tangents(dT[:, self.part.cell_ids])
+
+    @property
+    def n_tangents(self):
+        return self.h.n_tangents
+
+    def adjoint_tensor_gradient(self):
+        """``Handle.adjoint_tensor_gradient``: gathered over the ranks in the last sweep, the same bits on every rank."""
+        return self.h.adjoint_tensor_gradient()
+
     def set_options(self, **kw):
         self.h.set_options(**kw)
 

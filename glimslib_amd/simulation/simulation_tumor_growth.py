@@ -182,10 +182,11 @@ class TumorGrowth(FenicsSimulation):
         with d (d + 1) / 2 components, sampled nearest-voxel at the centroids (cells outside the image or on a NaN voxel get
         the identity, their number is warned about once); None = isotropic.  ``data_io.tensor_from_fibres`` builds the tensors
         of a fibre field.  A non-symmetric or wrongly shaped T raises ValueError here; a tensor that is not positive definite
-        is refused by the library when the run sets the problem up."""
+        is refused by the library when the run sets the problem up.  Clears a family of ``set_diffusion_tensor_family``."""
         from ..utils import data_io
         d = self.geometric_dimension
         nc = len(self.mesh.cells)
+        self._tensor_family, self._tensor_names, self.tensor_params, self._diffusion_tangents = None, (), {}, None
         if T is None:
             self._diffusion_tensor = None
             return
@@ -197,6 +198,58 @@ class TumorGrowth(FenicsSimulation):
         elif callable(T):
             T = T(self.mesh.cell_midpoints())
         self._diffusion_tensor = _backend.pack_diffusion_tensor(T, nc, d)
+
+    def set_diffusion_tensor_family(self, family, theta, names):
+        """A tensor field that depends on up to 4 scalar parameters theta -- an anisotropy ratio, say -- which the adjoint
+        differentiates by: ``family(theta_dict, centroids) -> (T, [dT_k])`` returns the field and one tangent field
+        dT/dtheta_k per name in ``names``, in that order, each in any form ``set_diffusion_tensor`` takes for an array
+        (``data_io.tensor_from_fibres(..., derivative=True)`` builds both for a fibre field).  ``theta``: the start values,
+        a dict name -> value or a sequence in the order of ``names``; ``sim.tensor_params`` holds the current values and
+        may be changed between runs.  Every ``run()`` builds T and the tangents from them and hands both to the handle;
+        ``adjoint_gradient`` then returns dJ/dtheta_k per label under the key 'tensor', and
+        ``ReducedFunctional(tensor_controls=...)`` makes them controls.  First order only."""
+        names = tuple(names)
+        if not 1 <= len(names) <= _backend.DT_MAX_TANGENTS or len(set(names)) != len(names):
+            raise ValueError("set_diffusion_tensor_family: 1 .. %d distinct parameter names expected, got %s"
+                             % (_backend.DT_MAX_TANGENTS, names))
+        if isinstance(theta, dict):
+            if set(theta) != set(names):
+                raise ValueError("set_diffusion_tensor_family: theta has %s, names are %s" % (tuple(theta), names))
+            values = [theta[n] for n in names]
+        else:
+            values = list(np.atleast_1d(theta))
+            if len(values) != len(names):
+                raise ValueError("set_diffusion_tensor_family: %d values for %d names" % (len(values), len(names)))
+        if not callable(family):
+            raise ValueError("set_diffusion_tensor_family: family(theta_dict, centroids) -> (T, [dT_k]) expected")
+        before = (getattr(self, '_tensor_family', None), getattr(self, '_tensor_names', ()), getattr(self, 'tensor_params', {}))
+        self._tensor_family, self._tensor_names = family, names
+        self.tensor_params = {n: float(v) for n, v in zip(names, values)}
+        try:
+            self._build_tensor_family()
+        except Exception:   # a family that does not fit leaves the simulation as it was
+            self._tensor_family, self._tensor_names, self.tensor_params = before
+            raise
+
+    def _build_tensor_family(self):
+        """T and the tangents of the family at sim.tensor_params, packed (the ValueErrors of set_diffusion_tensor)."""
+        d, nc = self.geometric_dimension, len(self.mesh.cells)
+        names = self._tensor_names
+        if set(self.tensor_params) != set(names):
+            raise ValueError("sim.tensor_params has %s, the family's names are %s" % (tuple(self.tensor_params), names))
+        T, dTs = self._tensor_family({n: float(self.tensor_params[n]) for n in names}, self.mesh.cell_midpoints())
+        dTs = list(dTs)
+        if len(dTs) != len(names):
+            raise ValueError("the tensor family returned %d tangent fields for %d names" % (len(dTs), len(names)))
+        self._diffusion_tensor = _backend.pack_diffusion_tensor(T, nc, d)
+        self._diffusion_tangents = _backend.pack_diffusion_tensor_tangents(dTs, nc, d)
+
+    def _tensor_gradient(self):
+        """{name: dJ/dtheta per label} of the last backward sweep, or None without a family."""
+        if getattr(self, '_tensor_family', None) is None:
+            return None
+        g = self._backend.adjoint_tensor_gradient()
+        return {n: g[k] for k, n in enumerate(self._tensor_names)}
 
     # -- coefficient tables -----------------------------------------------------------------------------------
     def _labels(self):
@@ -306,7 +359,11 @@ class TumorGrowth(FenicsSimulation):
         h = self._backend
         t = self._material_tables(n_labels)
         h.set_materials(t['D'], t['rho'], t['gamma'], t['E'], t['nu'])
+        if getattr(self, '_tensor_family', None) is not None:
+            self._build_tensor_family()   # T and its tangents at the present sim.tensor_params
         h.set_diffusion_tensor(getattr(self, '_diffusion_tensor', None))
+        if getattr(self, '_diffusion_tangents', None) is not None or getattr(h, 'n_tangents', 0):
+            h.set_diffusion_tensor_tangents(getattr(self, '_diffusion_tangents', None))
         opts = {k: v for k, v in self.solver_options.items() if k != 'mechanics'}
         h.set_options(dt=float(self.params.sim_time_step), **opts)
         self._upload_loads_and_bcs(h)
@@ -750,10 +807,15 @@ class TumorGrowth(FenicsSimulation):
         J and dJ/dm of the recorded run for the misfit ``terms`` (see ``Handle.adjoint_gradient``; the counterpart of
         fenics.ReducedFunctional(J, controls).derivative, image_based_optimization.py:700-708).  Returns
         {'J', 'diffusion', 'proliferation', 'coupling', 'E', 'poisson' (per-label arrays: the tables of DiscontinuousScalar),
-        'c0'}.  'E' and 'poisson' are 0 unless a term observes the displacement.
+        'c0'}.  'E' and 'poisson' are 0 unless a term observes the displacement.  With a tensor family
+        (``set_diffusion_tensor_family``) the dict gains 'tensor': {name: dJ/dtheta per label}.
         """
         J, dD, drho, dgamma, dc0, dE, dnu = self._adjoint_raw(terms, elastic=True)
-        return {'J': J, 'diffusion': dD, 'proliferation': drho, 'coupling': dgamma, 'E': dE, 'poisson': dnu, 'c0': dc0}
+        g = {'J': J, 'diffusion': dD, 'proliferation': drho, 'coupling': dgamma, 'E': dE, 'poisson': dnu, 'c0': dc0}
+        tensor = self._tensor_gradient()
+        if tensor is not None:
+            g['tensor'] = tensor
+        return g
 
     def _adjoint_hessian_raw(self, terms, directions, elastic=False):
         """Handle.adjoint_hessian of the recorded run; directions keyed 'D' / 'rho' / 'gamma' / 'c0' (elastic=True: also

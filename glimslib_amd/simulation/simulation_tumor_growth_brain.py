@@ -87,6 +87,9 @@ class TumorGrowthBrain(TumorGrowth):
             t = self._tissue_id(tissue)
             g['E_' + suffix] = pick(dE, t)
             g['nu_' + suffix] = pick(dnu, t)
+        tensor = self._tensor_gradient()   # (a family of set_diffusion_tensor_family: per-label arrays by name)
+        if tensor is not None:
+            g['tensor'] = tensor
         return g
 
     _ELASTIC_TISSUES = (('GM', 'GM'), ('WM', 'WM'), ('CSF', 'CSF'), ('VENT', 'Ventricles'))

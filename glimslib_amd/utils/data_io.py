@@ -256,11 +256,16 @@ def sample_image_at_points(image, points, order='nearest'):
     return a[tuple(ijk[:, k] for k in reversed(range(d)))]
 
 
-def tensor_from_fibres(directions, ratio, normalise=True):
+def tensor_from_fibres(directions, ratio, normalise=True, derivative=False):
     """Diffusion tensors T = I + (ratio - 1) e e^T from fibre directions e ([n, d], normalised here; a zero direction gives
     the identity): diffusion along the fibre is `ratio` (a number or [n]) times the diffusion across it.  normalise: scaled to
     trace d, so that the mean diffusivity is the tissue's scalar D.  Returns [n, d, d], what
-    ``sim.set_diffusion_tensor`` / ``Handle.set_diffusion_tensor`` take."""
+    ``sim.set_diffusion_tensor`` / ``Handle.set_diffusion_tensor`` take.
+
+    derivative=True: returns (T, dT/dratio), the tangent field that ``set_diffusion_tensor_tangents`` and a family of
+    ``sim.set_diffusion_tensor_family`` take.  Not normalised dT/dr = e e^T; normalised, with s = d / (d + r - 1):
+    T = s (I + (r - 1) e e^T) and dT/dr = s' (I + (r - 1) e e^T) + s e e^T, s' = -d / (d + r - 1)^2 (trace 0).  A zero
+    direction gives (I, 0)."""
     e = np.atleast_2d(np.asarray(directions, dtype=np.float64))
     n, d = e.shape
     r = np.broadcast_to(np.asarray(ratio, dtype=np.float64), (n,))
@@ -269,9 +274,15 @@ def tensor_from_fibres(directions, ratio, normalise=True):
     norm = np.linalg.norm(e, axis=1)
     e = np.where(norm[:, None] > 0.0, e / np.where(norm > 0.0, norm, 1.0)[:, None], 0.0)
     T = np.eye(d)[None] + (r - 1.0)[:, None, None] * e[:, :, None] * e[:, None, :]
+    if derivative:
+        ee = e[:, :, None] * e[:, None, :]
+        dT = ee
+        if normalise:   # T = U d / tr U with U = I + (r - 1) e e^T, tr U = d + (r - 1) |e|^2
+            tr, dtr = np.trace(T, axis1=1, axis2=2), np.trace(ee, axis1=1, axis2=2)
+            dT = ee * (d / tr)[:, None, None] - T * (d * dtr / (tr * tr))[:, None, None]
     if normalise:
         T = T * (d / np.trace(T, axis1=1, axis2=2))[:, None, None]
-    return T
+    return (T, dT) if derivative else T
 
 
 def tensor_image_at_points(image, points):

@@ -1187,7 +1187,8 @@ int glims_adjoint_displacement_image_info(glims_ctx* h, int k, int64_t out[3]);
  * in place with the handle as it was.  On a partitioned handle the call is rank-local (the cells are the rank's cells) and
  * communicates nothing.
  *
- * Not built: tensor entries or an anisotropy ratio as controls, tensors that vary in time, anisotropic mechanics.  P1
+ * Not built: single tensor entries per cell as controls (parameters of a tensor family are: the tangent fields below), tensors
+ * that vary in time, anisotropic mechanics.  P1
  * elements with a strongly anisotropic tensor lose the discrete maximum principle (small negative concentrations are
  * possible); a Neumann load on the concentration (glims_set_rd_load) is passed as it is -- the natural condition
  * is on the tensor flux D_t TT grad c . n. */
@@ -1195,6 +1196,34 @@ int glims_set_diffusion_tensor(glims_ctx* h, const double* T);
 /* out[0] = 1 if a field is set, else 0; out[1] = n_cells; *max_ratio = the largest lambda_max / lambda_min over the cells
  * (1 without a field).  Either pointer may be NULL. */
 int glims_diffusion_tensor_info(const glims_ctx* h, int64_t out[2], double* max_ratio);
+
+/* ---- tensor-field controls: tangent fields of the diffusion tensor ("Tangent fields") ---- */
+
+#define GLIMS_DT_MAX_TANGENTS 4
+
+/* For a tensor field TT(theta) the caller stores, next to TT itself, K <= GLIMS_DT_MAX_TANGENTS tangent fields
+ * dTT/dtheta_k: dT[K][n_cells][dim (dim + 1) / 2] in the CALLER's cell order and the packed layout of
+ * glims_set_diffusion_tensor, symmetric, not necessarily definite (a zero or indefinite tangent is fine).  K = 0 or
+ * dT = NULL clears them.  Every backward sweep that follows -- glims_adjoint_gradient* and the glims_adjoint_hessian* entry
+ * points run the same one -- then also adds up, per label t and tangent k,
+ *     dJ/dtheta_k |_t = -dt D_t sum_steps sum_{T in t} |T| grad lambda_h^T (dTT_T/dtheta_k) grad c_h
+ * (dJ/dD_t with the tangent in place of the tensor, times D_t), in a fixed order without atomics: the same call gives the
+ * same bits.  First order only.
+ *
+ * Tangents are data of the sensitivity pass alone: the call does NOT invalidate the set-up, the multigrids, the prepared
+ * step or an adjoint recording -- set them after a recorded run and ask for a gradient without a new run.  They work with
+ * and without a base field (none: tangents about TT = I), are kept by glims_set_diffusion_tensor (they belong to the mesh's
+ * cells), and cost 8 K dim (dim + 1) / 2 bytes per cell plus the handle-owned sums and partials.  A device pass checks every
+ * entry for finiteness; otherwise GLIMS_E_USAGE, the message naming the first bad tangent, the number of bad entries' cells
+ * and the smallest caller's index of a bad cell of that tangent, and the previously stored tangents stay.  K outside
+ * 0..GLIMS_DT_MAX_TANGENTS is GLIMS_E_USAGE.  On a partitioned handle the call is rank-local (the rank's cells); every rank
+ * must store the same K (the adjoint calls check it collectively). */
+int glims_set_diffusion_tensor_tangents(glims_ctx* h, int K, const double* dT);
+/* out[K][n_labels] = the sums above of the last completed backward sweep (on a partitioned handle gathered over the ranks
+ * and added in rank order: every rank gets the same bits).  K and n_labels must be those of the stored tangents and of
+ * glims_set_materials.  GLIMS_E_USAGE when no sweep has completed since the tangents were last set, or when the last sweep
+ * stopped with a status. */
+int glims_adjoint_tensor_gradient(glims_ctx* h, int K, int n_labels, double* out);
 
 /* ---- single-node multi-GPU (one process per GPU, RCCL over xGMI) ------------------------------------- */
 
